@@ -2,7 +2,11 @@
 """Headline benchmark: training images/sec of one full JPD-SE `Pix2PixHDTrainer.step`
 (G fwd/bwd + batched 2-scale PatchGAN + 2x VGG19 + both Adam updates) at 1024x512.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run sets up, runs W warm-up and K timed steps, and prints the headline figure (`value` images/sec, `ms_per_step`).
+--full adds everything else the benchmark measures: the in-library kernel timers inside the timed region (`roofline*`),
+the data-parallel timeline and the fp32-wire repeat for N > 1 (`multi_gpu`), and the CPU baseline (`cpu_baseline`); the
+keys are there in a plain run too, as null.  --dump-outputs DIR writes what the last timed step computed (see dump_outputs).
 N > 1 works both ways: under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...`
 (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment), or invoked directly, in which case this process
 -- BEFORE it makes any GPU call -- starts that very launcher as a child, relays rank 0's JSON line and exits with the
@@ -15,7 +19,7 @@ accumulation, fp32 master weights/Adam; synthetic Cityscapes-shaped inputs resid
 One JSON line on rank 0.  `roofline`: the ResnetBlock 3x3 implicit-GEMM kernel (N=1024,
 K=9216), algorithmic FLOPs / hipEvent-measured kernel time inside the timed region, against the
 2.5 PFLOP/s dense bf16 MFMA peak.  `cpu_baseline`: the torch-CPU oracle stepping the same
-network on the host cores (bounded sample; a reported baseline, not the target).
+network on the host cores (bounded sample; a reported baseline, not the target).  `roofline*` and `cpu_baseline` need --full.
 """
 import argparse
 import ctypes
@@ -71,8 +75,8 @@ def parse():
                   help='rehearsal: ranks take device LOCAL_RANK %% device_count (several ranks per GPU; needs --backend gloo)')
   ap.add_argument('--grad-reduce', default='auto', choices=['auto', 'bf16', 'fp32'],
                   help='N > 1: wire dtype of the gradient all-reduce.  auto (default) = bf16 -- half the xGMI bytes, one rounding '
-                       'of each rank\'s contribution and of the sum -- and the SAME run then repeats the timed steps on an fp32 '
-                       'wire and prints that figure next to it as "fp32_wire" (SURVEY.md 8d config 4 asks for both)')
+                       'of each rank\'s contribution and of the sum -- and with --full the SAME run then repeats the timed steps on '
+                       'an fp32 wire and prints that figure next to it as "fp32_wire" (SURVEY.md 8d config 4 asks for both)')
   ap.add_argument('--bf16-reduce', action='store_true', help='same as --grad-reduce bf16 (kept for round-2/3 command lines)')
   ap.add_argument('--ddp-overlap', default='d_backward', choices=['d_backward', 'layers'],
                   help='N > 1: the generator gradient all-reduce overlaps the discriminator backward (default) or is fired '
@@ -80,7 +84,15 @@ def parse():
   ap.add_argument('--master-port', type=int, default=0, help='self-launch only: rendezvous port (0 = pick a free one)')
   ap.add_argument('--debug-mode', type=int, default=None,
                   help='developer A/B runs: use libjpdse_hip_dev.so with this kernel-selection mode (include/jpdse_dev.h)')
-  return ap.parse_args()
+  ap.add_argument('--full', action='store_true',
+                  help='also measure what the headline figure does not need: kernel timers and roofline entries, the data-parallel '
+                       'timeline and the fp32-wire repeat (N > 1), the CPU baseline (N = 1)')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='after the timed steps, write what the last one computed as DIR/<name>.npy (see dump_outputs)')
+  args = ap.parse_args()
+  if args.steps < 1 or args.warmup < 0:
+    ap.error('--steps must be >= 1 and --warmup >= 0')
+  return args
 
 
 def make_opt(args, device_index):
@@ -146,6 +158,39 @@ def cpu_baseline(args, budget_s=75.0):
             'batch %d)' % (size, ' / '.join('%.2f' % t for t in ts), best, sweep_txt, ncpu, args.batch))
   torch.set_num_threads(saved)
   return dict(value=round(value, 5), unit='images/sec', cores=best, cores_available=ncpu, kind='port', sample=sample)
+
+
+DUMP_BUDGET_BYTES = 64 << 20          # --dump-outputs: all files together
+DUMP_SAMPLE_SEED = 1234
+
+
+def dump_outputs(out_dir, losses, loss_names, nets):
+  """--dump-outputs: what the last timed step handed its caller, as .npy files under out_dir, so that two builds can be compared
+  output for output on identical inputs (same arguments = same seeded weights and batch).
+    losses.npy          float64 [6]: the losses Pix2PixHDTrainer.step returned, in `loss_names` order
+    <net>_weights.npy   float32: every floating tensor of <net>.state_dict() after the step's Adam update, flattened in logical
+                        (NCHW) order and concatenated in state_dict order
+  A tensor larger than its share of the 64 MB budget (at most 64 Ki elements) contributes a fixed sample of its elements
+  instead: sorted indices drawn without replacement by a numpy generator seeded with DUMP_SAMPLE_SEED, in the same order, so
+  the sample is the same in every run of the same configuration."""
+  import numpy as np
+  os.makedirs(out_dir, exist_ok=True)
+  np.save(os.path.join(out_dir, 'losses.npy'), np.array([losses[k] for k in loss_names], dtype=np.float64))
+  tensors = [(tag, [t for t in net.state_dict().values() if t.is_floating_point()]) for tag, net in nets]
+  sizes = [t.numel() for _, ts in tensors for t in ts]
+  cap = 1 << 16
+  while 4 * sum(min(n, cap) for n in sizes) > DUMP_BUDGET_BYTES - (1 << 20):
+    cap //= 2
+  rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+  for tag, ts in tensors:
+    parts = []
+    for t in ts:
+      flat = t.detach().reshape(-1)
+      if flat.numel() > cap:
+        idx = np.sort(rng.choice(flat.numel(), size=cap, replace=False))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+      parts.append(flat.float().cpu())
+    np.save(os.path.join(out_dir, tag + '_weights.npy'), torch.cat(parts).numpy())
 
 
 def visible_gpu_count():
@@ -303,15 +348,17 @@ def main():
   # step of the timed region only -- one step holds 36 ResnetBlock GEMM launches, 18 weight gradients, 72 norm calls.
   # Round 4: the ResnetBlock GEMM regions -- the headline `roofline` fractions -- are sampled on the first
   # THREE timed steps (3 x 72 regions = 432 events = 1.6 ms spread over the timed region: 0.08 ms per step at the driver's 20
-  # steps), the HBM regions on the first step (148 events = 0.55 ms); `kernel_timers` in the output says so.
-  timed_steps = 0 if args.no_kernel_timers else (min(3, args.steps) if args.steps >= 12 else min(1, args.steps))   # short runs: one step (0.5 ms of events)
-  hbm_steps = 0 if args.no_kernel_timers else min(1, args.steps)
+  # steps), the HBM regions on the first step (148 events = 0.55 ms); `kernel_timers` in the output says so.  --full only: a plain
+  # run times the steps alone.
+  timers = args.full and not args.no_kernel_timers
+  timed_steps = (min(3, args.steps) if args.steps >= 12 else min(1, args.steps)) if timers else 0   # short runs: one step (0.5 ms of events)
+  hbm_steps = min(1, args.steps) if timers else 0
   tsteps = max(timed_steps, 1)
   hsteps = max(hbm_steps, 1)
   if timed_steps:
     check(L.jpdse_prof_select(1, 1024, 9216, 72 * timed_steps), 'prof_select')        # 36 halo + 18 ring + 18 wgrad regions per step
     check(L.jpdse_prof_hbm_select(1, 74 * hbm_steps), 'prof_hbm_select')             # 72 norm calls + 2 Adams per step
-  if world > 1:
+  if world > 1 and args.full:
     trainer.model.ddp_timeline = []          # per-step timing events of the data-parallel schedule (7 events per step)
   barrier()
   note('timed region: %d steps' % args.steps)
@@ -321,8 +368,12 @@ def main():
   barrier()
   elapsed = time.perf_counter() - t0
   note('timed region done: %.1f ms per step' % (1e3 * elapsed / args.steps))
+  if args.dump_outputs and rank == 0:           # before anything below steps the trainer again
+    from ctu.models.pix2pixHD_model import LOSS_NAMES
+    dump_outputs(args.dump_outputs, trainer.last_losses, LOSS_NAMES,
+                 [('netG', trainer.model.netG), ('netD', trainer.model.netD)])
   ddp_info = None
-  if world > 1:
+  if world > 1 and args.full:
     tl, trainer.model.ddp_timeline = trainer.model.ddp_timeline, None
     mean = lambda a, b: sum(t[a].elapsed_time(t[b]) for t in tl) / max(len(tl), 1)
     bg = trainer.model.grad_buckets.get('G')
@@ -335,7 +386,7 @@ def main():
                          'it overlaps (DESIGN.md 6 budget: <= 1.5 ms per step at 8 GPUs on the bf16 wire)')
   # N > 1, --grad-reduce auto: the same K steps again on an fp32 wire (twice the xGMI bytes), reported next to the bf16 figure
   fp32_wire = None
-  if world > 1 and args.grad_reduce == 'auto' and not args.bf16_reduce:
+  if world > 1 and args.full and args.grad_reduce == 'auto' and not args.bf16_reduce:
     try:
       trainer.enable_data_parallel(reduce_dtype=None)
       for _ in range(max(1, min(2, args.warmup))):
@@ -354,19 +405,20 @@ def main():
     except Exception as e:             # the headline (bf16-wire) figure above must survive a failure of the side measurement
       fp32_wire = dict(error=repr(e)[:300])
   ms, fl, n = ctypes.c_double(), ctypes.c_double(), ctypes.c_int64()
-  extra = {}
-  for cls, name in ((1, 'ring'), (2, 'wgrad')):      # the other two regions of the same layer, before the log is reset
-    m2, f2, n2 = ctypes.c_double(), ctypes.c_double(), ctypes.c_int64()
-    check(L.jpdse_prof_collect_class(cls, ctypes.byref(m2), ctypes.byref(f2), ctypes.byref(n2)), 'prof_collect_class')
-    extra[name] = (m2.value, f2.value, n2.value)
-  check(L.jpdse_prof_collect(ctypes.byref(ms), ctypes.byref(fl), ctypes.byref(n)), 'prof_collect')
-  check(L.jpdse_prof_select(0, 0, 0, 0), 'prof_select off')
-  hbm = {}
-  for cls, name in ((0, 'inorm_fwd'), (1, 'inorm_bwd'), (2, 'adam')):
-    m2, b2, n2 = ctypes.c_double(), ctypes.c_double(), ctypes.c_int64()
-    check(L.jpdse_prof_hbm_collect(cls, ctypes.byref(m2), ctypes.byref(b2), ctypes.byref(n2)), 'prof_hbm_collect')
-    hbm[name] = (m2.value, b2.value, n2.value)
-  check(L.jpdse_prof_hbm_select(0, 0), 'prof_hbm_select off')
+  extra = {name: (0.0, 0.0, 0) for name in ('ring', 'wgrad')}
+  hbm = {name: (0.0, 0.0, 0) for name in ('inorm_fwd', 'inorm_bwd', 'adam')}
+  if args.full:                                      # a plain run selected no timer: nothing to collect, no roofline entry
+    for cls, name in ((1, 'ring'), (2, 'wgrad')):      # the other two regions of the same layer, before the log is reset
+      m2, f2, n2 = ctypes.c_double(), ctypes.c_double(), ctypes.c_int64()
+      check(L.jpdse_prof_collect_class(cls, ctypes.byref(m2), ctypes.byref(f2), ctypes.byref(n2)), 'prof_collect_class')
+      extra[name] = (m2.value, f2.value, n2.value)
+    check(L.jpdse_prof_collect(ctypes.byref(ms), ctypes.byref(fl), ctypes.byref(n)), 'prof_collect')
+    check(L.jpdse_prof_select(0, 0, 0, 0), 'prof_select off')
+    for cls, name in ((0, 'inorm_fwd'), (1, 'inorm_bwd'), (2, 'adam')):
+      m2, b2, n2 = ctypes.c_double(), ctypes.c_double(), ctypes.c_int64()
+      check(L.jpdse_prof_hbm_collect(cls, ctypes.byref(m2), ctypes.byref(b2), ctypes.byref(n2)), 'prof_hbm_collect')
+      hbm[name] = (m2.value, b2.value, n2.value)
+    check(L.jpdse_prof_hbm_select(0, 0), 'prof_hbm_select off')
   if world > 1:
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -455,14 +507,14 @@ def main():
         'roofline': roof,
         'roofline_resblock_all_passes': roof_all,
         'roofline_hbm': roof_hbm,
-        'kernel_timers': {'steps_covered': timed_steps, 'hbm_steps_covered': hbm_steps, 'of_timed_steps': args.steps,
+        'kernel_timers': None if not args.full else {'steps_covered': timed_steps, 'hbm_steps_covered': hbm_steps, 'of_timed_steps': args.steps,
                           'note': 'hipEvent pairs inside the timed region: ResnetBlock GEMM regions on the first 3 steps (1 when fewer '
                                   'than 12 steps are timed), norm / Adam regions on the first (each event costs the stream ~3.7 us: '
                                   '~2.1 ms in all at 3 steps)'},
         'multi_gpu': ({'ddp': ddp_info, 'fp32_wire': fp32_wire} if world > 1 else
                       'N = 1: no collective ran; the 1/2/4/8-GPU curve needs the driver\'s 8-GPU node (python bench.py --gpus N)'),
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
       out['cpu_baseline'] = cpu_baseline(args)
     else:
       out['cpu_baseline'] = None

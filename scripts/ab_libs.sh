@@ -4,7 +4,7 @@ cd ${GRAFT_REPO_ROOT:-/root/repo}
 for i in 1 2; do
 for lib in "" "$@"; do
 full=""; [ -n "$lib" ] && full="$PWD/jpd-se_amd/jpdse_hip/$lib"
-JPDSE_HIP_LIB=$full timeout -k 10 150 python bench.py --steps 20 --warmup 8 --no-cpu-baseline 2>/dev/null | python3 -c "
+JPDSE_HIP_LIB=$full timeout -k 10 150 python bench.py --steps 20 --warmup 8 --full --no-cpu-baseline 2>/dev/null | python3 -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

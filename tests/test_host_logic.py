@@ -157,3 +157,36 @@ def test_bench_gpus_n_without_launcher_fails_cleanly_when_gpus_are_missing():
   r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2'], stdout=subprocess.PIPE,
                      stderr=subprocess.PIPE, text=True, env=env, timeout=300)
   assert r.returncode == 2 and 'WORLD_SIZE=4 but --gpus 2' in r.stderr
+  r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '0'], stdout=subprocess.PIPE,
+                     stderr=subprocess.PIPE, text=True, env=env, timeout=300)
+  assert r.returncode == 2 and '--steps must be >= 1' in r.stderr
+
+
+def test_bench_dump_outputs_fixed_sample_within_budget(tmp_path, monkeypatch):
+  """bench.py --dump-outputs writes float32 / float64 .npy files within its byte budget; the same state gives the same files
+  (a fixed sample of each large tensor, small tensors whole, losses in the order asked for)."""
+  import importlib.util
+  spec = importlib.util.spec_from_file_location('jpdse_bench', os.path.join(ROOT, 'bench.py'))
+  bench = importlib.util.module_from_spec(spec)
+  spec.loader.exec_module(bench)
+  monkeypatch.setattr(bench, 'DUMP_BUDGET_BYTES', 3 << 19)     # 1.5 MB: the 64 Ki-element cap has to halve once
+  torch.manual_seed(0)
+  g = torch.nn.Sequential(torch.nn.Conv2d(64, 256, 7), torch.nn.Conv2d(256, 512, 3)).to(memory_format=torch.channels_last)
+  d = torch.nn.Conv2d(8, 4, 3)
+  for sub in ('a', 'b'):
+    bench.dump_outputs(str(tmp_path / sub), {'x': 0.5, 'y': 1.25}, ('y', 'x'), [('netG', g), ('netD', d)])
+  files = sorted(os.listdir(str(tmp_path / 'a')))
+  assert files == ['losses.npy', 'netD_weights.npy', 'netG_weights.npy']
+  total = 0
+  for name in files:
+    a, b = np.load(str(tmp_path / 'a' / name)), np.load(str(tmp_path / 'b' / name))
+    assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), name
+    total += a.nbytes
+  assert total <= 3 << 19
+  assert np.load(str(tmp_path / 'a' / 'losses.npy')).tolist() == [1.25, 0.5]
+  dw = np.load(str(tmp_path / 'a' / 'netD_weights.npy'))
+  assert np.array_equal(dw, torch.cat([d.weight.detach().reshape(-1), d.bias.detach().reshape(-1)]).numpy())
+  gw = np.load(str(tmp_path / 'a' / 'netG_weights.npy'))
+  assert gw.shape == (2 * 32768 + 256 + 512,)
+  w0 = g[0].weight.detach().reshape(-1).numpy()            # logical (NCHW) order, whatever the memory format
+  assert np.isin(gw[:32768], w0).all() and np.array_equal(gw[32768:32768 + 256], g[0].bias.detach().numpy())
