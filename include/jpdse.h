@@ -33,7 +33,9 @@ extern "C" {
 #endif
 
 #define JPDSE_ABI_VERSION 2   /* 2 (round 4): + jpdse_conv_dgrad_nsum_slots / _fused_nsums, jpdse_inorm_bwd_from_sums; round 3 had already added
-                                * jpdse_loss_finalize, jpdse_conv_fwd_pool, jpdse_conv_dgrad_fused_lrelu, jpdse_input_builder, jpdse_copy, jpdse_prof_hbm_* under version 1 */
+                                * jpdse_loss_finalize, jpdse_conv_fwd_pool, jpdse_conv_dgrad_fused_lrelu, jpdse_input_builder, jpdse_copy, jpdse_prof_hbm_* under version 1;
+                                * the learned codec (jpdse_binarize_fwd, jpdse_code_stats[_workspace_size], jpdse_code_export) was added to
+                                * version 2 later: purely additive, nothing existing changed */
 
 enum { JPDSE_F32 = 0, JPDSE_BF16 = 1 };
 enum { JPDSE_PAD_ZERO = 0, JPDSE_PAD_REFLECT = 1 };
@@ -355,6 +357,28 @@ size_t jpdse_quant_loss_workspace_size(void);
 int jpdse_quant_loss(int32_t dtype_a, int32_t dtype_b, int64_t npix, int32_t C, const void* a, const void* b,
                      const double* mean, const double* std, int32_t mse, float* out, void* ws, size_t ws_bytes,
                      void* stream);
+
+/* ---- learned codec: the encoder's stochastic binarizer and its bitstream --------------------------------------------
+ * t, b: NHWC [N][H][W][CPAD(C)] in `dtype`.  Element e = (c*H + y)*W + x is the logical NCHW index inside an image. */
+/* Binarizer (ctu/quantizers/binarize.py:13-65; t is the stored tanh output of the 1x1 conv).  train != 0:
+ * b = ((1.0f - t) / 2.0f <= u) ? +1 : -1 (SoftSignFunction.forward, binarize.py:17-24) with t widened to fp32 and
+ * u = (w >> 8) * 2^-24, w = word (e & 3) of Philox4x32-10(counter = (e >> 2, n_global0 + n, draw lo, draw hi),
+ * key = (seed lo, seed hi)) -- the reference draws u with torch's uniform_; here it is a pure function of (seed, image index in
+ * the global batch, draw, e), so codes do not depend on how a batch is split.  u != NULL (fp32 NCHW [N][C][H][W]) replaces
+ * the generator.  train == 0: b = sign(t), sign(0) = 0 (DifferentiableSign eval, binarize.py:41-44).  Padding lanes of b
+ * are written as 0.  The backward is the straight-through estimator (binarize.py:26-28): db passes unchanged. */
+int jpdse_binarize_fwd(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, const void* t, void* b, int32_t train,
+                       uint64_t seed, uint64_t draw, int64_t n_global0, const float* u, void* stream);
+/* Per-image counts (model.py:468-491, get_eval_rate: torch.mean((b + 1) / 2) = (n_pos + n_zero / 2) / (C*H*W)):
+ * counts[n][0] = #(b == +1), counts[n][1] = #(b == 0), int32, over the logical elements.  Deterministic (integer sums,
+ * fixed order); ws: jpdse_code_stats_workspace_size() bytes. */
+size_t jpdse_code_stats_workspace_size(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C);
+int jpdse_code_stats(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, const void* b, int32_t* counts, void* ws,
+                     size_t ws_bytes, void* stream);
+/* Code export (model.py:557-563 get_code: (code.view(N, -1) + 1) / 2).  packed == 0: out = fp32 [N][C*H*W] in NCHW flatten
+ * order; packed != 0: out = uint8 [N][ceil(C*H*W / 8)], bit (b > 0) of element 8k+j in bit 7-j of byte k (np.packbits order). */
+int jpdse_code_export(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, const void* b, int32_t packed, void* out,
+                      void* stream);
 
 /* ---- optimizer ---------------------------------------------------------------------- */
 /* torch.optim.Adam (model.py:275,279) over a table of tensors, one launch.  `table` is a

@@ -19,6 +19,7 @@ raise NotImplementedError.
 import os
 
 import torch
+import torch.distributed as dist
 
 from jpdse_hip import F32, BF16, JpdseError, require_gpu
 from jpdse_hip import ops
@@ -126,10 +127,22 @@ class Pix2PixHDModel(BaseModel):
     super(Pix2PixHDModel, self).__init__(opt)
     g = lambda name, default=False: getattr(opt, name, default)
     unsupported = []
-    if not g('no_label_encoding') or not g('no_feat_encoding'):
-      unsupported.append('learned label/feature encoders (run with --no_label_encoding --no_feat_encoding)')
+    # learned codec (feature encoder netE): accepted for the global generator
+    feat_enc = not g('no_feat_encoding')
+    if not g('no_label_encoding'):
+      unsupported.append('the learned label encoder netE4label (run with --no_label_encoding)')
     if not g('no_generator_binarization'):
       unsupported.append('generator binarization (run with --no_generator_binarization)')
+    if feat_enc:
+      if g('netG', 'global') != 'global':
+        unsupported.append('learned feature encoding with --netG %s (only the global generator back-propagates into its '
+                           'input; run with --netG global or --no_feat_encoding)' % g('netG'))
+      if g('netE_groups', 1) != 1:
+        unsupported.append('--netE_groups %s' % g('netE_groups'))
+      if g('n_downsample_E', 4) < 1:
+        unsupported.append('--n_downsample_E %s (an encoder without downsampling)' % g('n_downsample_E'))
+      if g('pool_size', 0) > 0:
+        unsupported.append('--pool_size %s' % g('pool_size'))
     for flag in ('sem_masking', 'no_label', 'no_feat', 'match_raw_feat', 'no_lsgan', 'use_netE_output',
                  'zero_sem', 'zero_ins', 'zero_vis', 'binary_mask', 'inst_wise_pool'):
       if g(flag):
@@ -149,7 +162,10 @@ class Pix2PixHDModel(BaseModel):
     # channel bookkeeping (pix2pixHD_model.py:117-158)
     self.n_onehot = opt.num_labels + 1 if g('contain_dontcare_label') else opt.num_labels
     self.label_nc = self.n_onehot + (0 if g('no_instance') else 1)
-    netG_input_nc = self.label_nc + opt.input_nc
+    self.use_feat_encoding = feat_enc
+    # generator input: semantics + encoded image (feat_num channels) or + the image itself (model.py:135-139)
+    self.feat_nc = g('feat_num', 3) if feat_enc else opt.input_nc
+    netG_input_nc = self.label_nc + self.feat_nc
     netD_input_nc = self.label_nc + opt.num_out_channels
 
     self.netG = networks.define_G(netG_input_nc, opt.num_out_channels, opt.ngf, opt.netG,
@@ -163,11 +179,25 @@ class Pix2PixHDModel(BaseModel):
     if self.is_train:
       self.netD = networks.define_D(netD_input_nc, opt.ndf, opt.n_layers_D, opt.norm, False, opt.num_D, True,
                                     gpu_ids=self.gpu_ids, compute_dtype=cd)
+    # feature encoder of the learned codec, built after G and D as in the reference (model.py:167-175)
+    self.netE = None
+    if feat_enc:
+      self.netE = networks.define_G(opt.input_nc, g('feat_num', 3), g('nef', 64), 'encoder', g('n_downsample_E', 4),
+                                    norm=opt.norm, gpu_ids=self.gpu_ids,
+                                    binarize_encoder=not g('no_encoder_binarization'),
+                                    encoder_binarizer_out_channels=g('encoder_binarizer_out_channels', 128),
+                                    encoder_groups=g('netE_groups', 1), compute_dtype=cd)
+    # binarizer noise: Philox key = the run's seed, counter = (element, image index in the global batch,
+    # number of training forwards so far)
+    self.codec_seed = int(g('seed', None) or 0)
+    self.codec_draw = 0
     print('---------- networks initialized -------------')
     if not self.is_train or g('load_model'):
       self.load_network(self.netG, 'G', opt)
       if self.is_train:
         self.load_network(self.netD, 'D', opt)
+      if self.netE is not None:
+        self.load_network(self.netE, 'E', opt)
     if self.is_train:
       if opt.pool_size > 0 and len(self.gpu_ids) > 1:
         raise NotImplementedError('Fake Pool Not Implemented for MultiGPU')
@@ -208,8 +238,10 @@ class Pix2PixHDModel(BaseModel):
       return self.get_train_loss(x_dict)
     if mode == 'get_eval_loss':
       return self.get_eval_loss(x_dict)
-    if mode in ('get_code', 'get_eval_rate'):
-      raise NotImplementedError('binary codes exist only for the learned-codec ablations (SURVEY.md §2 row 3)')
+    if mode == 'get_code':
+      return self.get_code(x_dict)
+    if mode == 'get_eval_rate':
+      return self.get_eval_rate(x_dict)
     raise ValueError('Invalid forward mode: {}'.format(mode))
 
   def create_optimizers(self, opt):
@@ -228,7 +260,11 @@ class Pix2PixHDModel(BaseModel):
             % opt.niter_fix_global)
     else:
       params = list(self.netG.parameters())
-    for m in list(self.netG.modules()) + list(self.netD.modules()):
+    e_modules = []
+    if self.netE is not None:      # one Adam over G then E, the reference's order (model.py:269-270)
+      params += list(self.netE.parameters())
+      e_modules = list(self.netE.modules())
+    for m in list(self.netG.modules()) + list(self.netD.modules()) + e_modules:
       if hasattr(m, 'ensure_grads'):
         m.ensure_grads()
     optimizer_G = FusedAdam(params, lr=opt.lr, betas=(opt.beta1, opt.beta2))
@@ -269,7 +305,7 @@ class Pix2PixHDModel(BaseModel):
     image = x_dict['image'].to(dev, dtype=torch.float32, non_blocking=True).contiguous()
     if getattr(opt, 'no_instance', False):
       inst = torch.zeros_like(inst)      # a constant map has no edges; its channel is not part of label_nc
-    total_c = self.label_nc + opt.input_nc
+    total_c = self.label_nc + self.feat_nc
     base = ops.onehot_edge(label, inst, self.n_onehot, total_c, self.cdtype) if build_base else None
     real = ops.nchw_to_nhwc(image, self.cdtype)
     src = real
@@ -282,11 +318,71 @@ class Pix2PixHDModel(BaseModel):
     dst = out if out is not None else base.empty_like()
     return ops.concat_channels(base, img, self.label_nc, dst)
 
+  # ---- learned codec ---------------------------------------------------------------------------
+  def _encoder_eval(self, fn):
+    """Run fn() with netE in eval mode (deterministic sign binarizer), restoring its mode afterwards."""
+    was = self.netE.training
+    self.netE.train(False)
+    try:
+      return fn()
+    finally:
+      self.netE.train(was)
+
+  def _g_input_eval(self, pre):
+    """The generator input of the inference paths: [semantics | image], or [semantics | netE(image)] (model.py:568-595)."""
+    if self.netE is None:
+      return self._with_image(pre['base'], pre['src'])
+    feat, _ = self._encoder_eval(lambda: self.netE.fwd(pre['src']))
+    return self._with_image(pre['base'], feat)
+
+  def _set_codec_rng(self, local_batch):
+    """Point the binarizer at this call's images: n_global = rank * local_batch + i."""
+    b = self.netE._binarizer
+    if b is None:
+      return
+    # the rank within the group the gradients are reduced over (set by the trainer's enable_data_parallel)
+    group = getattr(self, 'codec_process_group', None)
+    rank = dist.get_rank(group) if dist.is_available() and dist.is_initialized() else 0
+    b.seed, b.draw, b.n_global0 = self.codec_seed, self.codec_draw, rank * local_batch
+
+  def _code_act(self, x_dict):
+    """The encoder's eval-mode bitstream of x_dict (the decoded frame with --use_compressed) as an NHWC Act."""
+    if self.netE is None or not self.netE.binarize:
+      raise ValueError('binary codes need the learned codec with encoder binarization '
+                       '(--no_feat_encoding and --no_encoder_binarization must both be off)')
+    pre = self.preprocess(x_dict, build_base=False)
+    return self._encoder_eval(lambda: self.netE.code(pre['src']))
+
+  def get_code(self, x_dict, packed=False):
+    """[image_code] (model.py:494-505, 557-563): (b + 1) / 2 as fp32 [N, bits] in NCHW flatten order -- or, packed=True
+    (extension), the bitstream itself, uint8 [N, ceil(bits / 8)] MSB first."""
+    with torch.no_grad():
+      return [ops.code_export(self._code_act(x_dict), packed)]
+
+  def get_eval_rate(self, x_dict):
+    """(Shannon bpp, raw bpp) averaged over the batch, with the reference's formula and types (model.py:468-491): per image
+    p = mean((b + 1) / 2), entropy -p ln p - (1 - p) ln(1 - p) -- in NATS, as the reference computes it (torch.log) --
+    times bits / pixels; nan when p is 0 or 1.  First value a 0-dim float tensor, second a Python float.  p comes from the
+    integer per-image counts of jpdse_code_stats (exact: torch.mean's fp32 sum of halves is exact below 2^24 bits)."""
+    with torch.no_grad():
+      b = self._code_act(x_dict)
+      counts = ops.code_stats(b).to(torch.float64)
+      bits = b.C * b.H * b.W
+      pixels = int(x_dict['image'].shape[-2]) * int(x_dict['image'].shape[-1])
+      p_all = ((2.0 * counts[:, 0] + counts[:, 1]) / (2.0 * bits)).to(torch.float32)
+      shannon, actual = 0., 0.
+      for j in range(b.N):
+        p = p_all[j]
+        ent = - p * torch.log(p) - (1 - p) * torch.log(1 - p)
+        shannon += ent * bits / pixels
+        actual += bits / pixels
+      return shannon / b.N, actual / b.N
+
   # ---- inference ------------------------------------------------------------------------------
   def get_img(self, x_dict):
     with torch.no_grad():
       pre = self.preprocess(x_dict)
-      fake, _ = self.netG.fwd(self._with_image(pre['base'], pre['src']))
+      fake, _ = self.netG.fwd(self._g_input_eval(pre))
       return ops.nhwc_to_nchw(fake)
 
   def get_eval_loss(self, x_dict):
@@ -295,7 +391,7 @@ class Pix2PixHDModel(BaseModel):
     (jpdse_quant_loss: the same float64 arithmetic, bit-identical quantisation, no device->host image copies)."""
     with torch.no_grad():
       pre = self.preprocess(x_dict)
-      fake, _ = self.netG.fwd(self._with_image(pre['base'], pre['src']))
+      fake, _ = self.netG.fwd(self._g_input_eval(pre))
       real32 = ops.nchw_to_nhwc(pre['image_nchw'], F32)       # the original image un-rounded, as the reference uses it
       slot = torch.zeros(1, dtype=torch.float32, device=self._device())
       ops.quant_loss(fake, real32, self.opt.normalize_mean, self.opt.normalize_std,
@@ -320,13 +416,28 @@ class Pix2PixHDModel(BaseModel):
     pre = self.preprocess(x_dict, build_base=False)
     real, src, label, inst = pre['real'], pre['src'], pre['label'], pre['inst']
     B, H, W = real.N, real.H, real.W
-    g_in = Act.empty(B, H, W, pre['total_c'], self.cdtype, dev)
-    d_in = Act.empty(2 * B, H, W, pre['total_c'], self.cdtype, dev) if run_d else None
-    if run_d:
-      ops.input_builder(label, inst, self.n_onehot, [g_in, d_in.batch_slice(B, 2 * B), d_in.batch_slice(0, B)],
-                        [src, real, None], self.label_nc)
+    e_ctx = None
+    if self.netE is not None:
+      # learned codec: G sees [semantics | netE(image)] (model.py:568-595), netE in the trainer's mode (stochastic binarizer
+      # when training); D sees [semantics | real / fake] as always
+      self._set_codec_rng(B)
+      feat, e_ctx = self.netE.fwd(src)
+      if self.netE.training:
+        self.codec_draw += 1
+      g_in = Act.empty(B, H, W, self.label_nc + feat.C, self.cdtype, dev)
+      ops.input_builder(label, inst, self.n_onehot, [g_in], [feat], self.label_nc)
+      d_in = Act.empty(2 * B, H, W, self.label_nc + real.C, self.cdtype, dev) if run_d else None
+      if run_d:
+        ops.input_builder(label, inst, self.n_onehot, [d_in.batch_slice(B, 2 * B), d_in.batch_slice(0, B)], [real, None],
+                          self.label_nc)
     else:
-      ops.input_builder(label, inst, self.n_onehot, [g_in], [src], self.label_nc)
+      g_in = Act.empty(B, H, W, pre['total_c'], self.cdtype, dev)
+      d_in = Act.empty(2 * B, H, W, pre['total_c'], self.cdtype, dev) if run_d else None
+      if run_d:
+        ops.input_builder(label, inst, self.n_onehot, [g_in, d_in.batch_slice(B, 2 * B), d_in.batch_slice(0, B)],
+                          [src, real, None], self.label_nc)
+      else:
+        ops.input_builder(label, inst, self.n_onehot, [g_in], [src], self.label_nc)
     fake, g_ctx = self.netG.fwd(g_in)
 
     pred, d_ctx = None, None
@@ -391,7 +502,7 @@ class Pix2PixHDModel(BaseModel):
         d_dist = ops.l1_fwd_bwd(fake, real, s(layout['dist']), gw['dist'])
       else:
         (ops.l1_fwd if opt.distortion_loss_fn == 'l1' else ops.mse_fwd)(fake, real, s(layout['dist']))
-    state = dict(B=B, fake=fake, real=real, g_ctx=g_ctx, pred=pred, d_ctx=d_ctx, vf=vf, vr=vr, v_ctx=v_ctx,
+    state = dict(B=B, fake=fake, real=real, g_ctx=g_ctx, e_ctx=e_ctx, pred=pred, d_ctx=d_ctx, vf=vf, vr=vr, v_ctx=v_ctx,
                  d_feat=d_feat, d_vgg=d_vgg, d_dist=d_dist)
     return state, slots, layout
 
@@ -455,8 +566,22 @@ class Pix2PixHDModel(BaseModel):
       d_fake = dd if d_fake is None else ops.add_(d_fake, dd)
     if d_fake is None:
       return False
-    self.netG.bwd(state['g_ctx'], d_fake, need_dx=False, need_dw=True)
+    if self.netE is None:
+      self.netG.bwd(state['g_ctx'], d_fake, need_dx=False, need_dw=True)
+      return True
+    # learned codec: the gradient w.r.t. the feature channels of G's input goes on into the encoder
+    d_feat_map = self.netG.bwd(state['g_ctx'], d_fake, need_dx=True, need_dw=True,
+                               dx_channels=(self.label_nc, self.label_nc + self.feat_nc))
+    self.netE.bwd(state['e_ctx'], d_feat_map)
     return True
+
+  def g_nets(self):
+    """What optimizer G trains: netG, or netG and netE (one module for PackBatcher / gradient buckets; not registered)."""
+    if self.netE is None:
+      return self.netG
+    if getattr(self, '_g_nets', None) is None:
+      self.__dict__['_g_nets'] = torch.nn.ModuleList([self.netG, self.netE])
+    return self._g_nets
 
   def _repack(self, which):
     """One-launch re-pack of the stepped network's data-gradient panels (jpdse_hip.layers.PackBatcher)."""
@@ -464,7 +589,7 @@ class Pix2PixHDModel(BaseModel):
       self._pack_batchers = {}
     b = self._pack_batchers.get(which)
     if b is None:
-      b = self._pack_batchers[which] = PackBatcher(self.netG if which == 'G' else self.netD)
+      b = self._pack_batchers[which] = PackBatcher(self.g_nets() if which == 'G' else self.netD)
     b.run()
 
   def backward_D(self, state, w_d):
@@ -567,6 +692,8 @@ class Pix2PixHDModel(BaseModel):
   def save(self):
     self.save_network(self.netG, 'G', self.opt)
     self.save_network(self.netD, 'D', self.opt)
+    if self.netE is not None:
+      self.save_network(self.netE, 'E', self.opt)
 
   def update_fixed_params(self, optimizer_G):
     """After niter_fix_global epochs also fine-tune the coarse generator (model.py:795-804): a fresh Adam over ALL
@@ -577,5 +704,8 @@ class Pix2PixHDModel(BaseModel):
     for m in self.netG.modules():
       if hasattr(m, 'ensure_grads'):
         m.ensure_grads()
-    return FusedAdam(list(self.netG.parameters()), lr=self.opt.lr, betas=(self.opt.beta1, 0.999),
+    params = list(self.netG.parameters())
+    if self.netE is not None:            # the encoder keeps training (model.py:797-799)
+      params += list(self.netE.parameters())
+    return FusedAdam(params, lr=self.opt.lr, betas=(self.opt.beta1, 0.999),
                      grad_scale=getattr(optimizer_G, 'grad_scale', 1.0))

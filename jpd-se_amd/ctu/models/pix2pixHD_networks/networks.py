@@ -17,8 +17,8 @@ from jpdse_hip import (ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, PAD_ZERO, PAD_RE
                        require_gpu)
 from jpdse_hip import ops
 from jpdse_hip.ops import Act
-from jpdse_hip.layers import (HipConv2d, HipResnetBlock, InstNormAct, ConvNormAct, Ctx, _Slot, run_chain_fwd,
-                              run_chain_bwd)
+from jpdse_hip.layers import (HipConv2d, HipResnetBlock, HipBinarizer, InstNormAct, ConvNormAct, Ctx, _Slot,
+                              run_chain_fwd, run_chain_bwd)
 
 ResnetBlock = HipResnetBlock
 
@@ -120,8 +120,18 @@ class GlobalGenerator(nn.Module):
   def fwd(self, x):
     return run_chain_fwd(self._stages, x)
 
-  def bwd(self, ctxs, dy, need_dx=False, need_dw=True):
-    return run_chain_bwd(self._stages, ctxs, dy, need_dx, need_dw)
+  def bwd(self, ctxs, dy, need_dx=False, need_dw=True, dx_channels=None):
+    """dx_channels=(c0, c1): also return the gradient w.r.t. input channels [c0, c1) only -- the encoded features of the
+    learned codec (pix2pixHD_model.py:595: torch.cat((input_label, feat_map))); the first conv's data gradient is then
+    restricted to those channels (HipConv2d.bwd_input_slice), the label channels need none."""
+    if dx_channels is None:
+      return run_chain_bwd(self._stages, ctxs, dy, need_dx, need_dw)
+    d = run_chain_bwd(self._stages[1:], ctxs[1:], dy, True, need_dw)
+    first = self._stages[0]
+    c_conv, c_norm = ctxs[0].items
+    dh = first.norm.bwd(c_norm, d)
+    first.conv.bwd(c_conv, dh, False, need_dw)
+    return first.conv.bwd_input_slice(c_conv, dh, dx_channels[0], dx_channels[1])
 
   def forward(self, input, mode='get_continuous_img'):
     if mode == 'get_binary_code':
@@ -198,6 +208,87 @@ class LocalEnhancer(nn.Module):
     return ops.nhwc_to_nchw(y)
 
 
+class Encoder(nn.Module):
+  """Feature encoder of the learned codec (networks.py:307-369): [ReflPad3, Conv7, IN, ReLU], n x [Conv3 s2, IN, ReLU],
+  the Binarizer (optional: the bitstream), n x [ConvT3 s2, IN, ReLU], [ReflPad3, Conv7, Tanh].  Same Sequential indices as
+  the reference, so `state_dict()` keys / shapes equal a reference net_E.pth (every conv carries its bias; the ones in
+  front of an affine-less InstanceNorm are not applied -- the norm cancels them)."""
+
+  def __init__(self, input_nc, output_nc, ngf=32, n_downsampling=4, norm_layer=None, binarize=False,
+               binarizer_out_channels=128, groups=1, compute_dtype='fp32', device=None):
+    super(Encoder, self).__init__()
+    if groups != 1:
+      raise NotImplementedError('grouped encoder convolutions (--netE_groups != 1) are not implemented on the HIP path')
+    if n_downsampling < 1:
+      raise NotImplementedError('an encoder without downsampling (--n_downsample_E 0) is not implemented on the HIP path')
+    self.output_nc, self.binarize, self.n_downsampling = output_nc, binarize, n_downsampling
+    self.cdtype = dtype_code(compute_dtype)
+    kw = dict(dtype=self.cdtype, device=device)
+    n, B = n_downsampling, binarizer_out_channels
+    o = 4 + 3 * n + (1 if binarize else 0)            # first up-sampling conv
+    last = o + 3 * n + 1
+    slots = [_Slot() for _ in range(last + 2)]
+    slots[1] = HipConv2d(input_nc, ngf, 7, 1, 3, PAD_REFLECT, apply_bias=False, **kw)
+    self._pre = [ConvNormAct(slots[1], InstNormAct(ACT_RELU))]
+    for i in range(n):
+      c = ngf * 2 ** i
+      slots[4 + 3 * i] = HipConv2d(c, 2 * c, 3, 2, 1, PAD_ZERO, apply_bias=False, **kw)
+      self._pre.append(ConvNormAct(slots[4 + 3 * i], InstNormAct(ACT_RELU)))
+    if binarize:
+      slots[4 + 3 * n] = HipBinarizer(ngf * 2 ** n, B, **kw)
+    self._post = []
+    for i in range(n):
+      c = ngf * 2 ** (n - i)
+      cin = B if (i == 0 and binarize) else c
+      slots[o + 3 * i] = HipConv2d(cin, c // 2, 3, 2, 1, transposed=True, apply_bias=False, **kw)
+      self._post.append(ConvNormAct(slots[o + 3 * i], InstNormAct(ACT_RELU)))
+    slots[last] = HipConv2d(ngf, output_nc, 7, 1, 3, PAD_REFLECT, act=ACT_TANH, apply_bias=True, **kw)
+    self._post.append(slots[last])
+    self.model = nn.Sequential(*slots)
+
+  @property
+  def _binarizer(self):
+    """model[4 + 3n] (a property, so the module is registered once, under its reference key)."""
+    return self.model[4 + 3 * self.n_downsampling] if self.binarize else None
+
+  def fwd(self, x):
+    """(features, ctx); the binarizer's mode follows its `training` flag."""
+    h, c_pre = run_chain_fwd(self._pre, x)
+    c_bin = None
+    if self._binarizer is not None:
+      h, c_bin = self._binarizer.fwd(h)
+    y, c_post = run_chain_fwd(self._post, h)
+    return y, (c_pre, c_bin, c_post)
+
+  def bwd(self, ctxs, dy, need_dw=True):
+    """Weight gradients of every layer from dy = d loss / d features.  No gradient w.r.t. the encoder input (the image)."""
+    c_pre, c_bin, c_post = ctxs
+    d = run_chain_bwd(self._post, c_post, dy, True, need_dw)
+    if self._binarizer is not None:
+      d = self._binarizer.bwd(c_bin, d, True, need_dw)
+    run_chain_bwd(self._pre, c_pre, d, False, need_dw)
+
+  def code(self, x):
+    """The binarizer's output (+-1; 0 where eval-mode tanh is exactly 0) as an NHWC Act: model[:4 + 3n + 1](x)."""
+    if self._binarizer is None:
+      raise AttributeError('Encoder: no binarizer found')
+    h, _ = run_chain_fwd(self._pre, x)
+    b, _ = self._binarizer.fwd(h)
+    return b
+
+  def forward(self, input, inst=None, mode='get_continuous_img', inst_wise_pool=False):
+    if mode == 'get_binary_code':
+      if self._binarizer is None:
+        raise AttributeError('Encoder: no binarizer found')
+      return ops.nhwc_to_nchw(self.code(_to_act(input, self.cdtype)))
+    if mode != 'get_continuous_img':
+      raise ValueError('Invalid encoding mode: {}'.format(mode))
+    if inst_wise_pool:
+      raise NotImplementedError('instance-wise pooling of the encoder output (--inst_wise_pool) is not implemented')
+    y, _ = self.fwd(_to_act(input, self.cdtype))
+    return ops.nhwc_to_nchw(y)
+
+
 def define_G(input_nc, output_nc, ngf, netG, n_downsample_global=3, n_blocks_global=9, n_local_enhancers=1,
              n_blocks_local=3, norm='instance', gpu_ids=[], binarize_encoder=False,
              encoder_binarizer_out_channels=128, encoder_groups=1, binarize_generator=False,
@@ -213,7 +304,9 @@ def define_G(input_nc, output_nc, ngf, netG, n_downsample_global=3, n_blocks_glo
     net = LocalEnhancer(input_nc, output_nc, ngf, n_downsample_global, n_blocks_global, n_local_enhancers,
                         n_blocks_local, compute_dtype=compute_dtype, device=device)
   elif netG == 'encoder':
-    raise NotImplementedError('the learned-codec Encoder is outside the JPD-SE hot path (SURVEY.md §2 row 3)')
+    net = Encoder(input_nc, output_nc, ngf, n_downsample_global, binarize=binarize_encoder,
+                  binarizer_out_channels=encoder_binarizer_out_channels, groups=encoder_groups,
+                  compute_dtype=compute_dtype, device=device)
   else:
     raise ValueError('generator not implemented!')
   return net

@@ -42,7 +42,8 @@ class Pix2PixHDTrainer(BaseTrainer):
     calls are then no-ops in value, which is how the path is exercised on a one-GPU box).  reduce_dtype
     torch.bfloat16 halves the bytes on the wire (SURVEY.md 8d config 4 reports both)."""
     world = dist.get_world_size(process_group)
-    for net in (self.model.netG, self.model.netD):
+    nets = [self.model.netG, self.model.netD] + ([self.model.netE] if self.model.netE is not None else [])
+    for net in nets:
       for p in net.parameters():
         # 4-D masters are channels_last: hand the collective the dense KRSC view of the same memory
         dense = p.data.permute(0, 2, 3, 1) if p.dim() == 4 else p.data
@@ -59,10 +60,18 @@ class Pix2PixHDTrainer(BaseTrainer):
       # done; 'd_backward': everything starts at once, so fewer and larger collectives (256 MB: the generator's 730 MB in 3 + the
       # small layers) -- a ring all-reduce's fixed cost (2 (N-1) hops of latency + a kernel launch) is paid per bucket
       bucket_bytes = (64 << 20) if overlap == 'layers' else (256 << 20)
+    self.model.codec_process_group = process_group     # images are indexed within this group (learned-codec noise)
     self._dp = dict(bucket_bytes=bucket_bytes, process_group=process_group, reduce_dtype=reduce_dtype, world=world,
                     overlap=overlap)
-    self._rebuild_buckets('G', self.model.netG, self.optimizer_G)
+    self._rebuild_buckets('G', self._g_bucket_nets(), self.optimizer_G)
     self._rebuild_buckets('D', self.model.netD, self.optimizer_D)
+
+  def _g_bucket_nets(self):
+    """The networks optimizer G trains, in forward order of the backward's reverse: netE (its gradients are written last)
+    then netG -- the buckets follow reverse-backward order."""
+    if self.model.netE is None:
+      return self.model.netG
+    return torch.nn.ModuleList([self.model.netE, self.model.netG])
 
   def _rebuild_buckets(self, tag, net, optim):
     """(Re)create the gradient buckets of one network over the parameters its optimizer trains, fold 1/world into the
@@ -85,7 +94,7 @@ class Pix2PixHDTrainer(BaseTrainer):
     that, under data parallelism, the new parameters get gradient buckets, hooks and the 1/world scale as well."""
     self.optimizer_G = self.model.update_fixed_params(self.optimizer_G)
     if getattr(self, '_dp', None) is not None:
-      self._rebuild_buckets('G', self.model.netG, self.optimizer_G)
+      self._rebuild_buckets('G', self._g_bucket_nets(), self.optimizer_G)
     if getattr(self.opt, 'schedule_lr', False):
       self.scheduler_G = ReduceLROnPlateau(self.optimizer_G, 'min', factor=self.opt.lr_decay_factor,
                                            patience=self.opt.lr_decay_patience)
@@ -114,10 +123,16 @@ class Pix2PixHDTrainer(BaseTrainer):
     self.eval()
     return self.model(x_dict, self.opt, mode='get_eval_loss').item()
 
-  def get_code(self, x_dict):
-    return self.model(x_dict, self.opt, mode='get_code')
+  def get_code(self, x_dict, packed=False):
+    """The image's binary code as ONE tensor (pix2pixHD_trainer.py:100-103: torch.cat over the model's code list): fp32
+    [N, bits] of 0 / 1 on the GPU, or (packed=True, extension) the uint8 bitstream [N, ceil(bits / 8)]."""
+    self.eval()
+    with torch.no_grad():
+      return torch.cat([c for c in self.model.get_code(x_dict, packed) if c is not None], dim=-1)
 
   def get_eval_rate(self, x_dict):
+    """(Shannon bpp in nats as the reference computes it, raw bpp) of the learned codec (pix2pixHD_trainer.py:106-110)."""
+    self.eval()
     return self.model(x_dict, self.opt, mode='get_eval_rate')
 
   def get_img(self, x_dict):
@@ -148,6 +163,8 @@ class Pix2PixHDTrainer(BaseTrainer):
         if getattr(self.opt, flag, False):
           src = getattr(self, key[:-len('_state_dict')], None) if key.endswith('_state_dict') else getattr(self, key)
           record[key] = src.state_dict() if key.endswith('_state_dict') else src
+      if self.model.netE is not None:
+        record['codec_draw'] = self.model.codec_draw      # the binarizer's noise counter (extension)
       torch.save(record, os.path.join(self.opt.save_dir, 'stats_and_optim.pt'))
       self.model.save()
     if dist.is_available() and dist.is_initialized():
@@ -172,6 +189,8 @@ class Pix2PixHDTrainer(BaseTrainer):
         setattr(self, key, record[key])
     self.best_val_loss = record['best_val_loss']
     self.steps_taken = record['steps_taken']
+    if self.model.netE is not None:
+      self.model.codec_draw = int(record.get('codec_draw', self.steps_taken))
     self.start_epoch = record['epoch'] + 1
     print('\nresumed %s: best val loss %.4f, continuing with epoch %d\n'
           % (path, self.best_val_loss, self.start_epoch + 1))

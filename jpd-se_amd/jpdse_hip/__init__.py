@@ -127,6 +127,10 @@ SIGNATURES = {
     'jpdse_mse_const_fwd': (_I32, [_I32, _I64, _I32, _F, _P, _P, _P, _SZ, _P]),
     'jpdse_mse_const_bwd': (_I32, [_I32, _I64, _I32, _F, _P, _P, _F, _P, _P]),
     'jpdse_adam_step': (_I32, [_P, _I32, _I64, _F, _F, _F, _F, _I32, _F, _P]),
+    'jpdse_binarize_fwd': (_I32, [_I32, _I32, _I32, _I32, _I32, _P, _P, _I32, ctypes.c_uint64, ctypes.c_uint64, _I64, _P, _P]),
+    'jpdse_code_stats_workspace_size': (_SZ, [_I32, _I32, _I32, _I32, _I32]),
+    'jpdse_code_stats': (_I32, [_I32, _I32, _I32, _I32, _I32, _P, _P, _P, _SZ, _P]),
+    'jpdse_code_export': (_I32, [_I32, _I32, _I32, _I32, _I32, _P, _I32, _P, _P]),
 }
 
 # the developer build (same sources, -DJPDSE_DEV): the shipped ABI plus include/jpdse_dev.h

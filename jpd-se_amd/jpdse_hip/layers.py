@@ -64,12 +64,13 @@ class HipConv2d(nn.Module):
   """nn.Conv2d / nn.ConvTranspose2d with the padding layer and the activation folded in."""
 
   def __init__(self, cin, cout, k, stride=1, pad=0, pad_mode=PAD_ZERO, act=ACT_NONE, slope=0.2,
-               apply_bias=True, transposed=False, dtype=F32, device=None):
+               apply_bias=True, transposed=False, dtype=F32, device=None, bias=True):
     super(HipConv2d, self).__init__()
     self.cin, self.cout, self.k = cin, cout, k
     self.stride, self.pad, self.pad_mode = stride, pad, pad_mode
     self.act, self.slope = act, slope
     self.apply_bias = apply_bias      # False: conv feeds an affine-less InstanceNorm (bias is dead)
+    assert bias or not apply_bias     # bias=False: no bias parameter at all (nn.Conv2d(..., bias=False))
     self.transposed = transposed
     self.cdtype = dtype
     if transposed:
@@ -83,7 +84,10 @@ class HipConv2d(nn.Module):
     bound = 1.0 / math.sqrt(fan_in)
     b = torch.empty(cout, device=device).uniform_(-bound, bound)
     self.weight = nn.Parameter(w)
-    self.bias = nn.Parameter(b)
+    if bias:
+      self.bias = nn.Parameter(b)
+    else:
+      self.register_parameter('bias', None)
     self._packs = None
     self._pack_key = None
     self._bias_grad_store = None
@@ -177,6 +181,8 @@ class HipConv2d(nn.Module):
     return w.grad
 
   def _bgrad_buffer(self):
+    if self.bias is None:
+      return None
     if self._bias_grad_store is None or self._bias_grad_store.device != self.bias.device:
       self._bias_grad_store = torch.zeros(ops.cpad(self.cout), dtype=torch.float32, device=self.bias.device)
       self.bias.grad = self._bias_grad_store[:self.cout]
@@ -301,6 +307,33 @@ class HipConv2d(nn.Module):
   def _fire(self):
     if self.grad_ready_hook is not None:
       self.grad_ready_hook(self)
+
+
+class HipBinarizer(nn.Module):
+  """Binarizer (ctu/quantizers/binarize.py:47-65): 1x1 conv without bias -> tanh (the conv's epilogue) -> sign, stochastic
+  in training (SoftSignFunction) and deterministic in eval, following the module's `training` flag.  The conv is
+  registered as `conv`: state-dict key `<prefix>.conv.weight` [cout, cin, 1, 1] as in the reference.
+
+  Noise (train mode): the Philox stream of jpdse_binarize_fwd, addressed by `seed`, `draw` (the caller's count of training
+  forwards) and `n_global0` (index of the call's first image in the global batch), all set by the owner before fwd.
+  `noise_override`: fp32 [N, C, H, W] cuda tensor used by the NEXT fwd only, instead of the stream (test hook)."""
+
+  def __init__(self, cin, cout, dtype=F32, device=None):
+    super(HipBinarizer, self).__init__()
+    self.conv = HipConv2d(cin, cout, 1, act=ACT_TANH, apply_bias=False, bias=False, dtype=dtype, device=device)
+    self.seed, self.draw, self.n_global0 = 0, 0, 0
+    self.noise_override = None
+
+  def fwd(self, x):
+    t, ctx = self.conv.fwd(x)                     # ctx = (x, t): the tanh backward reads the stored t
+    u, self.noise_override = self.noise_override, None
+    b = ops.binarize_fwd(t, self.training, self.seed, self.draw, self.n_global0, u)
+    return b, ctx
+
+  def bwd(self, ctx, db, need_dx=True, need_dw=True):
+    """Straight-through estimator (binarize.py:26-28): db is the gradient w.r.t. tanh's output; conv.bwd applies
+    tanh' = 1 - t^2 and runs the 1x1 conv's data / weight gradients."""
+    return self.conv.bwd(ctx, db, need_dx, need_dw)
 
 
 class PackBatcher(object):

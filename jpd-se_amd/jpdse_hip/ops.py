@@ -506,3 +506,39 @@ def mse_const_bwd(x, target, gout, scale, out=None):
   check(lib().jpdse_mse_const_bwd(x.dtype, npix, x.Cs, target, _p(x.t), _p(gout), scale, _p(dx.t), _stream()),
         'mse_const_bwd')
   return dx
+
+
+# ---- learned codec (binarize.hip) ---------------------------------------------------------------
+def binarize_fwd(t, train, seed=0, draw=0, n_global0=0, u=None, out=None):
+  """b = stochastic sign of the tanh output `t` (train) or sign(t) (eval), same dtype / layout as t (jpdse_binarize_fwd).
+  u: optional fp32 [N, C, H, W] noise replacing the Philox stream (test hook)."""
+  b = out if out is not None else t.empty_like()
+  if u is not None:
+    assert u.dtype == torch.float32 and u.is_cuda and u.is_contiguous() and tuple(u.shape) == (t.N, t.C, t.H, t.W)
+  m64 = (1 << 64) - 1
+  check(lib().jpdse_binarize_fwd(t.dtype, t.N, t.H, t.W, t.C, _p(t.t), _p(b.t), 1 if train else 0, int(seed) & m64,
+                                 int(draw) & m64, int(n_global0), _p(u), _stream()), 'binarize_fwd')
+  return b
+
+
+def code_stats(b):
+  """int32 [N, 2] device tensor: per image the number of +1 and of 0 entries of the code `b` (jpdse_code_stats)."""
+  L = lib()
+  counts = torch.empty((b.N, 2), dtype=torch.int32, device=b.t.device)
+  n = L.jpdse_code_stats_workspace_size(b.dtype, b.N, b.H, b.W, b.C)
+  ws = workspace(n, b.t.device)
+  check(L.jpdse_code_stats(b.dtype, b.N, b.H, b.W, b.C, _p(b.t), _p(counts), _p(ws), ws.numel(), _stream()), 'code_stats')
+  return counts
+
+
+def code_export(b, packed=False):
+  """(b + 1) / 2 as fp32 [N, C*H*W] in NCHW flatten order, or (packed) the bits b > 0 as uint8 [N, ceil(C*H*W / 8)],
+  MSB first (jpdse_code_export)."""
+  bits = b.C * b.H * b.W
+  if packed:
+    out = torch.empty((b.N, (bits + 7) // 8), dtype=torch.uint8, device=b.t.device)
+  else:
+    out = torch.empty((b.N, bits), dtype=torch.float32, device=b.t.device)
+  check(lib().jpdse_code_export(b.dtype, b.N, b.H, b.W, b.C, _p(b.t), 1 if packed else 0, _p(out), _stream()),
+        'code_export')
+  return out
