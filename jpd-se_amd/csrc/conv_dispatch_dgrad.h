@@ -192,92 +192,29 @@ static int conv_dgrad_t(const jpdse_conv_desc* d, const ConvPlan& p, const void*
   const int st = d->stride;
   // LeakyReLU-backward epilogue (mask_slope != 0): only the generic tile kernels and the unfused pass apply it
   const bool lrelu = mask != nullptr && mask_slope != 0.f;
+  // phase 0 as the single-launch kernels see it; `whole`: it is the whole data gradient, written straight into dx (zero padding, stride 1)
+  ConvView v = {};
   if constexpr (sizeof(T) == 2) {
-    if (!lrelu && !refl && p.nph == 1 && st == 1 && p.ph[0].cnth == d->H && p.ph[0].cntw == d->W &&
-        rows_ok(p.ph[0].Uh, p.ph[0].Uw, 1, 0, JPDSE_ACT_NONE, d->H, d->W, p.Ks, p.Cs) && p.ph[0].Lk == 3 * p.Ks) {
-      const Phase& f = p.ph[0];
-      RowsArgs r = {};
-      r.X = reinterpret_cast<const bf16_t*>(dy);
-      r.B = reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(pack) + f.pack_off);
-      r.Y = reinterpret_cast<bf16_t*>(dx);
-      r.N = d->N;
-      r.OH = d->H;
-      r.OW = d->W;
-      r.IH = p.OH;
-      r.IW = p.OW;
-      r.py = (f.Uh - 1) - f.i0h;
-      r.px = (f.Uw - 1) - f.i0w;
-      r.Kout = d->C;
-      r.Ks = p.Cs;
-      r.b_rows = p.Cs;
-      r.out_sn = (long long)d->H * d->W * p.Cs;
-      r.out_sh = (long long)d->W * p.Cs;
-      r.out_sw = p.Cs;
-      r.out_base = 0;
-      r.act = JPDSE_ACT_NONE;
-      r.mask = reinterpret_cast<const bf16_t*>(mask);
-      r.addend = reinterpret_cast<const bf16_t*>(addend);
-      return launch_rows(r, 1, s);
-    }
+    v = view_dgrad_phase(d, p, 0, dy, pack, dx);
+    v.mask = reinterpret_cast<const bf16_t*>(mask);
+    v.addend = reinterpret_cast<const bf16_t*>(addend);
   }
+  const bool whole = !lrelu && !refl && p.nph == 1 && v.OH == d->H && v.OW == d->W;
   if constexpr (sizeof(T) == 2) {
-    if (!lrelu && !refl && p.nph == 1 && p.ph[0].cnth == d->H && p.ph[0].cntw == d->W &&
-        halo_ok(p.ph[0].Uh, p.ph[0].Uw, st, d->H, d->W, p.Ks, p.Cs)) {
-      const Phase& f = p.ph[0];
-      HaloArgs h = {};
-      h.X = reinterpret_cast<const bf16_t*>(dy);
-      h.B = reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(pack) + f.pack_off);
-      h.bias = nullptr;
-      h.Y = reinterpret_cast<bf16_t*>(dx);
-      h.N = d->N;
-      h.OH = d->H;
-      h.OW = d->W;
-      h.IH = p.OH;
-      h.IW = p.OW;
-      h.Cs = p.Ks;
-      h.py = (f.Uh - 1) - f.i0h;
-      h.px = (f.Uw - 1) - f.i0w;
-      h.reflect = 0;
-      h.Kout = d->C;
-      h.Ks = p.Cs;
-      h.b_rows = p.Cs;
-      h.out_sn = (long long)d->H * d->W * p.Cs;
-      h.out_sh = (long long)d->W * p.Cs;
-      h.out_sw = p.Cs;
-      h.out_base = 0;
-      h.act = JPDSE_ACT_NONE;
-      h.mask = reinterpret_cast<const bf16_t*>(mask);
-      h.addend = reinterpret_cast<const bf16_t*>(addend);
-      return p.Cs > 64 ? launch_halo_cfg<2>(h, s) : launch_halo_cfg<1>(h, s);
-    }
+    if (whole && st == 1 && rows_ok(v) && p.ph[0].Lk == 3 * p.Ks) return launch_rows(to_rows(v), 1, s);
+    if (whole && halo_ok(v)) return p.Cs > 64 ? launch_halo_cfg<2>(to_halo(v), s) : launch_halo_cfg<1>(to_halo(v), s);
     // the same for grids of 8 x 32 patches (W = 32): tap-program kernel, nine taps, split-K over the dy channel slabs
-    if (!lrelu && !refl && p.nph == 1 && st == 1 && p.ph[0].cnth == d->H && p.ph[0].cntw == d->W && p.ph[0].Lk == p.ph[0].Uw * p.Ks &&
-        taps9_shape_ok(p.ph[0].Uh, p.ph[0].Uw, 1, d->H, d->W, p.Ks, p.Cs, (long long)d->N * p.OH * p.OW * p.Ks, (long long)p.Cs * 9 * p.Ks)) {
-      const Phase& f = p.ph[0];
-      Taps4View v = {};
-      v.X = reinterpret_cast<const bf16_t*>(dy);
-      v.B = reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(pack) + f.pack_off);
-      v.Y = reinterpret_cast<bf16_t*>(dx);
-      v.N = d->N;
-      v.IH = p.OH;
-      v.IW = p.OW;
-      v.Cin_s = p.Ks;
-      v.OH = d->H;
-      v.OW = d->W;
-      v.py = (f.Uh - 1) - f.i0h;
-      v.px = (f.Uw - 1) - f.i0w;
-      v.Kout = d->C;
-      v.Ks_out = p.Cs;
-      v.ktot = (long long)f.Uh * f.Lk;
-      v.tap_r = f.Lk;
-      v.tap_s = p.Ks;
-      v.act = JPDSE_ACT_NONE;
-      v.addend = reinterpret_cast<const bf16_t*>(addend);
-      v.mask = reinterpret_cast<const bf16_t*>(mask);
-      return launch_taps9(v, reinterpret_cast<float*>(wsb + p.splitk_off), s);
-    }
+    if (whole && st == 1 && taps9_shape_ok(v)) return launch_taps9(v, reinterpret_cast<float*>(wsb + p.splitk_off), s);
   }
   if constexpr (sizeof(T) == 2) {
+    // reflect-padded 3x3: the zero-padded data gradient on the image's own grid (pad 1, straight into dx) + the ring.  The mask
+    // rides in the one-launch forms only; the others apply it after the fold.
+    ConvView r = v;
+    r.OH = d->H;
+    r.OW = d->W;
+    r.py = r.px = 1;
+    r.out_base = 0;
+    r.mask = nullptr;
     const bool ring_halo = halo_ok(3, 3, 1, d->H, d->W, p.Ks, p.Cs);
     const bool ring_taps = !ring_halo && taps9_shape_ok(3, 3, 1, d->H, d->W, p.Ks, p.Cs, (long long)d->N * d->H * d->W * p.Ks,
                                                         (long long)p.Cs * 9 * p.Ks);
@@ -285,67 +222,31 @@ static int conv_dgrad_t(const jpdse_conv_desc* d, const ConvPlan& p, const void*
         (ring_halo || ring_taps) && p.ph[0].Lk == 3 * p.Ks) {
       // (1) zero-padded data gradient straight into dx: halo kernel, or the nine-tap program on 8 x 32 patches (W = 32)
       if (ring_taps) {
-        Taps4View v = {};
-        v.X = reinterpret_cast<const bf16_t*>(dy);
-        v.B = reinterpret_cast<const bf16_t*>(pack);
-        v.Y = reinterpret_cast<bf16_t*>(dx);
-        v.N = d->N;
-        v.IH = d->H;
-        v.IW = d->W;
-        v.Cin_s = p.Ks;
-        v.OH = d->H;
-        v.OW = d->W;
-        v.py = v.px = 1;
-        v.Kout = d->C;
-        v.Ks_out = p.Cs;
-        v.ktot = 3LL * p.ph[0].Lk;
-        v.tap_r = p.ph[0].Lk;
-        v.tap_s = p.Ks;
-        v.act = JPDSE_ACT_NONE;
-        v.addend = reinterpret_cast<const bf16_t*>(addend);
         if (g_ring_virt && d->H >= 16) {
           // one launch (+ the split-K finish): the ring rides in the frame of dy (gemm_taps.h VIRT)
           bf16_t* frame = reinterpret_cast<bf16_t*>(wsb);       // in front of the split-K slabs (splitk_off lies behind the padded-dy region)
           const long long fv = (long long)d->N * (2 * (d->W + 2) + 2 * d->H) * (p.Ks / 8);
           if ((size_t)fv * 16 > p.splitk_off) return set_error(JPDSE_EWORKSPACE, "reflect data gradient: no room for the frame in front of the slabs");
-          hipLaunchKernelGGL(ring_frame_kernel, dim3(ew_blocks(fv)), dim3(256), 0, s, v.X, frame, d->N, d->H, d->W, p.Ks, fv);
+          hipLaunchKernelGGL(ring_frame_kernel, dim3(ew_blocks(fv)), dim3(256), 0, s, r.X, frame, d->N, d->H, d->W, p.Ks, fv);
           if (int rc = check_launch("ring_frame_kernel")) return rc;
-          v.frame = frame;
-          v.mask = reinterpret_cast<const bf16_t*>(mask);
-          return launch_taps9(v, reinterpret_cast<float*>(wsb + p.splitk_off), s);
+          r.frame = frame;
+          r.mask = v.mask;
+          return launch_taps9(r, reinterpret_cast<float*>(wsb + p.splitk_off), s);
         }
-        if (int rc = launch_taps9(v, reinterpret_cast<float*>(wsb + p.splitk_off), s)) return rc;
+        if (int rc = launch_taps9(r, reinterpret_cast<float*>(wsb + p.splitk_off), s)) return rc;
       }
-      HaloArgs h = {};
-      h.X = reinterpret_cast<const bf16_t*>(dy);
-      h.B = reinterpret_cast<const bf16_t*>(pack);
-      h.Y = reinterpret_cast<bf16_t*>(dx);
-      h.N = d->N;
-      h.OH = d->H;
-      h.OW = d->W;
-      h.IH = d->H;
-      h.IW = d->W;
-      h.Cs = p.Ks;
-      h.py = h.px = 1;
-      h.Kout = d->C;
-      h.Ks = p.Cs;
-      h.b_rows = p.Cs;
-      h.out_sn = (long long)d->H * d->W * p.Cs;
-      h.out_sh = (long long)d->W * p.Cs;
-      h.out_sw = p.Cs;
-      h.act = JPDSE_ACT_NONE;
-      h.addend = reinterpret_cast<const bf16_t*>(addend);
+      HaloArgs h = to_halo(r);
       if (ring_halo && g_ring_virt && (p.Ks >= 128 || (p.Ks == 64 && g_halo_single))) {
         // one launch: the ring rides in the frame of dy (gemm_halo.h, VIRT); the mask, if any, in the same epilogue
         bf16_t* frame = reinterpret_cast<bf16_t*>(wsb);
         const long long fv = (long long)d->N * (2 * (d->W + 2) + 2 * d->H) * (p.Ks / 8);
-        const int pslot = (p.Cs == g_prof.Ks && 9LL * p.Ks == g_prof.kdim) ? prof_begin(s) : -1;
+        const int pslot = prof_begin(s, p.Cs, 9LL * p.Ks);
         hipLaunchKernelGGL(ring_frame_kernel, dim3(ew_blocks(fv)), dim3(256), 0, s, h.X, frame, d->N, d->H, d->W, p.Ks, fv);
         int rc = check_launch("ring_frame_kernel");
         prof_end(pslot, 1, 0.0, s);
         if (rc) return rc;
         h.V = frame;
-        h.mask = reinterpret_cast<const bf16_t*>(mask);
+        h.mask = v.mask;
         if (sink != nullptr) {
           h.nx = reinterpret_cast<const bf16_t*>(sink->x);
           h.nstats = sink->stats;
@@ -408,7 +309,7 @@ static int conv_dgrad_t(const jpdse_conv_desc* d, const ConvPlan& p, const void*
         g.partial = slab + (q == 0 ? 0 : (q == 1 ? tb_elems : (q == 2 ? 2 * tb_elems : 2 * tb_elems + lr_elems)));
         rb.p[rb.n++] = g;
       }
-      const int pslot = (p.Cs == g_prof.Ks && 9LL * p.Ks == g_prof.kdim) ? prof_begin(s) : -1;
+      const int pslot = prof_begin(s, p.Cs, 9LL * p.Ks);
       if (int rc = launch_fast_batch(rb, s)) return rc;
       // (3) fold the ring into rows 1 / H-2 and columns 1 / W-2 of dx
       RingFoldArgs rf = {};
@@ -512,33 +413,8 @@ static int conv_dgrad_t(const jpdse_conv_desc* d, const ConvPlan& p, const void*
     }
   }
   if constexpr (sizeof(T) == 2) {
-    if (taps_dgrad2_ok(d, p, mask, addend, mom)) return launch_taps_dgrad2(d, p, dy, pack, dx, s, mask, addend, mask_slope);
-    if (!lrelu && !refl && p.nph == 1 && st == 1 && mom == nullptr && p.ph[0].cnth == d->H &&
-        p.ph[0].cntw == d->W && p.ph[0].Lk == p.ph[0].Uw * p.Ks &&
-        taps4_shape_ok(p.ph[0].Uh, p.ph[0].Uw, 1, d->H, d->W, p.Ks, p.Cs, (long long)d->N * p.OH * p.OW * p.Ks, (long long)p.Cs * 16 * p.Ks)) {
-      const Phase& f = p.ph[0];
-      Taps4View v = {};
-      v.X = reinterpret_cast<const bf16_t*>(dy);
-      v.B = reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(pack) + f.pack_off);
-      v.Y = reinterpret_cast<bf16_t*>(dx);
-      v.N = d->N;
-      v.IH = p.OH;
-      v.IW = p.OW;
-      v.Cin_s = p.Ks;
-      v.OH = d->H;
-      v.OW = d->W;
-      v.py = (f.Uh - 1) - f.i0h;
-      v.px = (f.Uw - 1) - f.i0w;
-      v.Kout = d->C;
-      v.Ks_out = p.Cs;
-      v.ktot = (long long)f.Uh * f.Lk;
-      v.tap_r = f.Lk;
-      v.tap_s = p.Ks;
-      v.act = JPDSE_ACT_NONE;
-      v.addend = reinterpret_cast<const bf16_t*>(addend);
-      v.mask = reinterpret_cast<const bf16_t*>(mask);
-      return launch_taps4(v, ws, s);
-    }
+    if (taps_dgrad2_ok(d, p, mom)) return launch_taps_dgrad2(d, p, dy, pack, dx, s, mask, addend, mask_slope);
+    if (whole && st == 1 && mom == nullptr && taps4_shape_ok(v)) return launch_taps4(v, ws, s);
   }
   if constexpr (sizeof(T) == 2) {
     // one output channel (PatchGAN 512 -> 1): dx is written once by an FMA kernel (thin_out1.h)
@@ -596,43 +472,18 @@ static int conv_dgrad_t(const jpdse_conv_desc* d, const ConvPlan& p, const void*
     if (f.cnth <= 0 || f.cntw <= 0) continue;
     if constexpr (sizeof(T) == 2) {
       if (fast) {
-        FastArgs g = {};
-        g.X = reinterpret_cast<const bf16_t*>(dy);
-        g.B = reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(pack) + f.pack_off);
-        g.bias = nullptr;
-        g.M = d->N * f.cnth * f.cntw;
-        g.OH = f.cnth;
-        g.OW = f.cntw;
-        g.IH = p.OH;
-        g.IW = p.OW;
-        g.Cs = p.Ks;
-        g.R = f.Uh;
-        g.S = f.Uw;
-        g.sy = g.sx = 1;
-        g.py = (f.Uh - 1) - f.i0h;
-        g.px = (f.Uw - 1) - f.i0w;
-        g.reflect = 0;
-        g.Kout = d->C;
-        g.Ks = p.Cs;
-        g.b_rows = p.Cs;
-        if (refl) {
+        FastArgs g = to_fast(view_dgrad_phase(d, p, i, dy, pack, dx));
+        if (refl) {               // onto the padded domain; reflect_fold_kernel and the unfused pass below finish it
           g.Y = reinterpret_cast<bf16_t*>(dxp);
           g.out_sn = (long long)p.Hp * p.Wp * p.Cs;
           g.out_sh = (long long)st * p.Wp * p.Cs;
           g.out_sw = (long long)st * p.Cs;
           g.out_base = ((long long)(st * f.i0h + f.qh) * p.Wp + (st * f.i0w + f.qw)) * p.Cs;
         } else {
-          g.Y = reinterpret_cast<bf16_t*>(dx);
-          g.out_sn = (long long)d->H * d->W * p.Cs;
-          g.out_sh = (long long)st * d->W * p.Cs;
-          g.out_sw = (long long)st * p.Cs;
-          g.out_base = ((long long)(st * f.i0h + f.qh - d->pad) * d->W + (st * f.i0w + f.qw - d->pad)) * p.Cs;
+          g.mask = v.mask;
+          g.addend = v.addend;
         }
-        g.act = JPDSE_ACT_NONE;
-        g.slope = 0.f;
-        g.mask = refl ? nullptr : reinterpret_cast<const bf16_t*>(mask);
         g.mask_slope = mask_slope;
-        g.addend = refl ? nullptr : reinterpret_cast<const bf16_t*>(addend);
         g.splits = nlive_phases == 1 ? splitk_for(g.M, p.Cs, f.Uh * f.Uw * p.Ks / 64) : 1;
         g.partial = reinterpret_cast<float*>(wsb + p.splitk_off);
         batch.p[batch.n++] = g;

@@ -121,104 +121,13 @@ static int conv_fwd_t(const jpdse_conv_desc* d, const ConvPlan& p, const void* x
                          d->pad_mode == JPDSE_PAD_REFLECT ? 1 : 0, zs, d->act, d->slope, total);
       return check_launch("tapsum_kernel");
     }
-    if (rows_ok(d->R, d->S, d->stride, d->pad_mode == JPDSE_PAD_REFLECT, d->act, p.OH, p.OW, p.Cs, p.Ks)) {
-      RowsArgs r = {};
-      r.X = reinterpret_cast<const bf16_t*>(x);
-      r.B = reinterpret_cast<const bf16_t*>(pack);
-      r.bias = bias;
-      r.Y = reinterpret_cast<bf16_t*>(y);
-      r.N = d->N;
-      r.OH = p.OH;
-      r.OW = p.OW;
-      r.IH = d->H;
-      r.IW = d->W;
-      r.py = r.px = d->pad;
-      r.Kout = d->K;
-      r.Ks = p.Ks;
-      r.b_rows = p.Ks;
-      r.out_sn = (long long)p.OH * p.OW * p.Ks;
-      r.out_sh = (long long)p.OW * p.Ks;
-      r.out_sw = p.Ks;
-      r.out_base = 0;
-      r.act = d->act;
-      r.slope = d->slope;
-      r.mom = mom;
-      return launch_rows(r, d->stride, s);
-    }
-    if (d->pad_mode != JPDSE_PAD_REFLECT && p.Lk_fwd == d->S * p.Cs && mom == nullptr &&
-        taps4_shape_ok(d->R, d->S, d->stride, p.OH, p.OW, p.Cs, p.Ks, (long long)d->N * d->H * d->W * p.Cs, (long long)p.Ks * 16 * p.Cs)) {
-      Taps4View v = {};
-      v.X = reinterpret_cast<const bf16_t*>(x);
-      v.B = reinterpret_cast<const bf16_t*>(pack);
-      v.bias = bias;
-      v.Y = reinterpret_cast<bf16_t*>(y);
-      v.N = d->N;
-      v.IH = d->H;
-      v.IW = d->W;
-      v.Cin_s = p.Cs;
-      v.OH = p.OH;
-      v.OW = p.OW;
-      v.py = v.px = d->pad;
-      v.Kout = d->K;
-      v.Ks_out = p.Ks;
-      v.ktot = (long long)d->R * p.Lk_fwd;
-      v.tap_r = p.Lk_fwd;
-      v.tap_s = p.Cs;
-      v.act = d->act;
-      v.slope = d->slope;
-      return launch_taps4(v, ws, s);
-    }
-    if (p.Lk_fwd == d->S * p.Cs && mom == nullptr &&
-        taps9_shape_ok(d->R, d->S, d->stride, p.OH, p.OW, p.Cs, p.Ks, (long long)d->N * d->H * d->W * p.Cs, (long long)p.Ks * 9 * p.Cs)) {
-      Taps4View v = {};
-      v.X = reinterpret_cast<const bf16_t*>(x);
-      v.B = reinterpret_cast<const bf16_t*>(pack);
-      v.bias = bias;
-      v.Y = reinterpret_cast<bf16_t*>(y);
-      v.N = d->N;
-      v.IH = d->H;
-      v.IW = d->W;
-      v.Cin_s = p.Cs;
-      v.OH = p.OH;
-      v.OW = p.OW;
-      v.py = v.px = d->pad;
-      v.reflect = d->pad_mode == JPDSE_PAD_REFLECT;
-      v.Kout = d->K;
-      v.Ks_out = p.Ks;
-      v.ktot = (long long)d->R * p.Lk_fwd;
-      v.tap_r = p.Lk_fwd;
-      v.tap_s = p.Cs;
-      v.act = d->act;
-      v.slope = d->slope;
-      return launch_taps9(v, reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + p.splitk_off), s);
-    }
-    if (halo_ok(d->R, d->S, d->stride, p.OH, p.OW, p.Cs, p.Ks)) {
-      HaloArgs h = {};
-      h.X = reinterpret_cast<const bf16_t*>(x);
-      h.B = reinterpret_cast<const bf16_t*>(pack);
-      h.bias = bias;
-      h.Y = reinterpret_cast<bf16_t*>(y);
-      h.N = d->N;
-      h.OH = p.OH;
-      h.OW = p.OW;
-      h.IH = d->H;
-      h.IW = d->W;
-      h.Cs = p.Cs;
-      h.py = h.px = d->pad;
-      h.reflect = d->pad_mode == JPDSE_PAD_REFLECT;
-      h.Kout = d->K;
-      h.Ks = p.Ks;
-      h.b_rows = p.Ks;
-      h.out_sn = (long long)p.OH * p.OW * p.Ks;
-      h.out_sh = (long long)p.OW * p.Ks;
-      h.out_sw = p.Ks;
-      h.out_base = 0;
-      h.act = d->act;
-      h.slope = d->slope;
-      if (mom != nullptr) {
-        h.mom = mom;
-        h.mom_slots = (p.OH / 4) * (p.OW / 64);
-      }
+    ConvView v = view_fwd(d, p, x, pack, bias, y);
+    v.mom = mom;
+    if (rows_ok(v)) return launch_rows(to_rows(v), d->stride, s);
+    if (!v.reflect && mom == nullptr && taps4_shape_ok(v)) return launch_taps4(v, ws, s);
+    if (mom == nullptr && taps9_shape_ok(v)) return launch_taps9(v, reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + p.splitk_off), s);
+    if (halo_ok(v)) {
+      HaloArgs h = to_halo(v);
       if (pool != nullptr && mom == nullptr && pooled != nullptr && !g_halo_abl) {
         h.pool = reinterpret_cast<bf16_t*>(pool);
         *pooled = true;
@@ -242,31 +151,7 @@ static int conv_fwd_t(const jpdse_conv_desc* d, const ConvPlan& p, const void* x
       return p.Ks > 64 ? launch_halo_cfg<2>(h, s) : launch_halo_cfg<1>(h, s);
     }
     if (p.Cs % 64 == 0 && fast_pays(d->N * p.OH * p.OW, p.Ks, d->R * d->S * p.Cs / 64)) {
-      FastArgs f = {};
-      f.X = reinterpret_cast<const bf16_t*>(x);
-      f.B = reinterpret_cast<const bf16_t*>(pack);
-      f.bias = bias;
-      f.Y = reinterpret_cast<bf16_t*>(y);
-      f.M = d->N * p.OH * p.OW;
-      f.OH = p.OH;
-      f.OW = p.OW;
-      f.IH = d->H;
-      f.IW = d->W;
-      f.Cs = p.Cs;
-      f.R = d->R;
-      f.S = d->S;
-      f.sy = f.sx = d->stride;
-      f.py = f.px = d->pad;
-      f.reflect = d->pad_mode == JPDSE_PAD_REFLECT;
-      f.Kout = d->K;
-      f.Ks = p.Ks;
-      f.b_rows = p.Ks;
-      f.out_sn = (long long)p.OH * p.OW * p.Ks;
-      f.out_sh = (long long)p.OW * p.Ks;
-      f.out_sw = p.Ks;
-      f.out_base = 0;
-      f.act = d->act;
-      f.slope = d->slope;
+      FastArgs f = to_fast(v);
       f.splits = splitk_for(f.M, p.Ks, d->R * d->S * p.Cs / 64);
       f.partial = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + p.splitk_off);
       return launch_fast(f, s);

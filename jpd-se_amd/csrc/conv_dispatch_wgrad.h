@@ -38,13 +38,7 @@ static int launch_wgrad_fast_cfg(FastWgArgs a, float* slabs, size_t* slab_bytes_
     *slab_bytes_out = a.splits > 1 ? (size_t)a.splits * a.slab_stride * sizeof(float) : 0;
     return JPDSE_OK;
   }
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_fast_kernel<WM, WN, TM, TN, ABL>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return set_error(JPDSE_ELAUNCH, "wgrad_fast: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    configured = true;
-  }
+  if (int rc = opt_in_lds<&wgrad_fast_kernel<WM, WN, TM, TN, ABL>>("wgrad_fast", lds)) return rc;
   const int tiles = ((a.Ks + BM - 1) / BM) * (a.run_mode ? a.R : a.R * a.S) *
                     (((a.run_mode ? a.run_len : a.Cs) + BN - 1) / BN);
   a.partial = slabs;
@@ -231,13 +225,7 @@ static size_t wgrad_taps_ws_bytes(const jpdse_conv_desc* d, const ConvPlan& p) {
 template <int TMW, int WM, int WN, int S, int NROW, int ST, int BKP, int NSTG>
 static int launch_wgrad_taps_cfg(const TapsWgArgs& a, int lds, hipStream_t s) {
   constexpr int BM = WM * TMW * 32, BN = WN * 32;
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_taps_kernel<TMW, WM, WN, S, NROW, ST, BKP, NSTG>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return set_error(JPDSE_ELAUNCH, "wgrad_taps: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    configured = true;
-  }
+  if (int rc = opt_in_lds<&wgrad_taps_kernel<TMW, WM, WN, S, NROW, ST, BKP, NSTG>>("wgrad_taps", lds)) return rc;
   const int blocks = a.k_tiles * a.r_groups * a.c_tiles * a.blocks_per_tile;
   hipLaunchKernelGGL((wgrad_taps_kernel<TMW, WM, WN, S, NROW, ST, BKP, NSTG>), dim3(blocks), dim3(64 * WM * WN), lds, s, a);
   if (int rc = check_launch("wgrad_taps_kernel")) return rc;
@@ -325,17 +313,11 @@ static size_t wgrad_nine_ws_bytes(const jpdse_conv_desc* d, const ConvPlan& p) {
 
 template <bool REFLECT, int SCHED, bool W32 = false>
 static int launch_wgrad_nine_cfg(const NineWgArgs& a, hipStream_t s) {
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_nine_kernel<REFLECT, SCHED, 0, W32>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kNineLds);
-    if (e != hipSuccess) return set_error(JPDSE_ELAUNCH, "wgrad_nine: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    configured = true;
-  }
+  if (int rc = opt_in_lds<&wgrad_nine_kernel<REFLECT, SCHED, 0, W32>>("wgrad_nine", kNineLds)) return rc;
   const int blocks = a.k_tiles * a.c_tiles * a.splits;
-  const int pslot = (a.Ks == g_prof.Ks && 9LL * a.Cs == g_prof.kdim) ? prof_begin(s) : -1;
   if (W32 && (a.W != 32 || (a.H & 1) || a.chunks_total != a.N * (a.H / 2)))
     return set_error(JPDSE_EINVAL, "wgrad_nine: the row-pair form needs 32-pixel-wide images with an even number of rows");
+  const int pslot = prof_begin(s, a.Ks, 9LL * a.Cs);
   hipLaunchKernelGGL((wgrad_nine_kernel<REFLECT, SCHED, 0, W32>), dim3(blocks), dim3(512), kNineLds, s, a);
   if (int rc = check_launch("wgrad_nine_kernel")) return rc;
   if (a.splits > 1) {

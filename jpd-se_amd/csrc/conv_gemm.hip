@@ -121,6 +121,23 @@ __device__ __forceinline__ float apply_act(float v, int act, float slope) {
 
 using namespace jpdse;
 
+// What every launching entry point `who` does first, in this order: the descriptor, the caller's pointers, the plan, the entry
+// point's own requirement on the layer (`layer_ok(plan)`: JPDSE_OK, or the code of an error it has set), the workspace.
+template <typename LayerOk>
+static int conv_enter(const char* who, const jpdse_conv_desc* d, bool pointers_ok, const void* ws, size_t ws_bytes, ConvPlan* p,
+                      LayerOk layer_ok) {
+  if (int rc = validate(d)) return rc;
+  JPDSE_REQUIRE(pointers_ok, "%s: null pointer", who);
+  make_plan(d, p);
+  if (int rc = layer_ok(*p)) return rc;
+  const size_t need = jpdse_conv_workspace_size(d);
+  if (ws == nullptr || ws_bytes < need) return set_error(JPDSE_EWORKSPACE, "%s: workspace %zu < %zu", who, ws_bytes, need);
+  return JPDSE_OK;
+}
+static int conv_enter(const char* who, const jpdse_conv_desc* d, bool pointers_ok, const void* ws, size_t ws_bytes, ConvPlan* p) {
+  return conv_enter(who, d, pointers_ok, ws, ws_bytes, p, [](const ConvPlan&) { return JPDSE_OK; });
+}
+
 extern "C" {
 
 int jpdse_conv_out_shape(const jpdse_conv_desc* d, int32_t* OH, int32_t* OW) {
@@ -154,61 +171,59 @@ int jpdse_debug_occupy_cus(int32_t blocks, const int32_t* release_flag, int32_t 
   JPDSE_REQUIRE(blocks > 0 && blocks <= 128 && release_flag != nullptr && max_ms > 0 && max_ms <= 20000,
                 "debug_occupy_cus: blocks in 1..128, a flag, max_ms in 1..20000");
   constexpr int lds = 160 * 1024;
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&occupy_cus_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return set_error(JPDSE_ELAUNCH, "occupy_cus: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    configured = true;
-  }
+  if (int rc = opt_in_lds<&occupy_cus_kernel>("occupy_cus", lds)) return rc;
   hipLaunchKernelGGL(occupy_cus_kernel, dim3(blocks), dim3(256), lds, as_stream(stream), release_flag,
                      (unsigned long long)max_ms * 100000ULL);
   return check_launch("occupy_cus_kernel");
 }
 
 int jpdse_debug_set_fast_path(int32_t enable) {
-  // 0: generic kernels only; 1: fast kernels (default schedule 0); 2: fast kernels, alternative schedule 1
-  g_fast_enabled = enable != 0;
-  g_halo_enabled = enable != 3;      // 3: fast kernels but no halo kernel (A/B)
-  g_moments_fused = enable != 32 && enable != 6;   // 32: InstanceNorm moments always in their own pass (A/B); 6 keeps the generic kernels' rounding points
-  g_ring_virt = enable != 40 && enable != 6;   // 40: reflect ring as four split-K strip GEMMs + ring_fold_kernel instead of the folded frame (A/B); 6 keeps every product in fp32 until the fold
-  g_thin1_enabled = enable != 41 && enable != 6;   // 41: the one-output-channel layers (PatchGAN 512 -> 1) backward on the GEMM paths (A/B)
-  g_taps_dgrad4_enabled = enable != 42 && enable != 6;   // 42: 4x4 stride-2 data gradients (PatchGAN layers 1-2) on the merged-phase fast kernel (A/B)
-  g_taps_dgrad4_min_tiles = enable == 43 ? 1 : (1 << 30);     // 43: 4x4 stride-2 data gradients on the tap program + fringe (developer build only: slower in the step)
-  g_taps9_enabled = enable != 38 && enable != 6;   // 38: 3x3 layers with 32-pixel-wide grids on the split-K fast kernel (A/B)
-  g_taps4_enabled = enable != 36 && enable != 6;   // 36: 4x4 stride-1 layers on the fast kernel alone (A/B)
-  g_taps_enabled = enable != 35 && enable != 6;   // 35: stride-2 data gradients on the merged-phase fast kernel instead of the tap-program halo kernel (A/B); 6 keeps the generic kernels' summation order (tap outer, slab inner)
-  g_rows_enabled = enable != 29 && enable != 3;   // 29: 64-channel 3x3 layers on the halo / fast kernels instead of conv_rows (A/B)
-  g_halo_abl = (enable >= 100 && enable < 200) ? enable - 100 : 0;
-  g_wgrad_nine_enabled = enable != 4;    // 4: wide 3x3 layers on the per-tap fast weight gradient instead of the all-nine-taps one (A/B)
-  g_wgrad_taps_enabled = enable != 12;   // 12: fast kernels without the all-taps weight gradient (A/B)
-  g_ring_enabled = enable != 7 && enable != 3;   // 7: reflect data gradient on the padded domain + fold (A/B)
-  g_merge_min_kt = enable == 9 ? 16 : 4;
-  g_norm_fused = enable == 27 ? 0 : (enable == 28 ? 2 : 1);   // 27: InstanceNorm always as three kernels; 28: one-kernel form with the in-launch exchange (A/B)
-  g_merge_min_tiles = enable == 26 ? 384 : 64;    // 9: merged stride-phase data gradient only for long K loops (A/B)
-  g_fast_small = enable == 10 ? 0 : 20;     // 10: no 128-row / 2-stage configs for short K loops (A/B)   // 9: merged stride-phase data gradient also for short K loops (A/B)
-  g_halo_xcd = enable == 15 ? 1 : (enable == 16 ? 2 : (enable == 17 ? 3 : 0));   // 17: 4 N-tiles x 8 patches per XCD (one-round grids)   // 15 / 16: XCD-aware tile orders of the halo kernel (A/B)
-  g_halo_mf16 = enable == 19;         // 19: halo kernel on 16x16x32 MFMAs (A/B)
-  g_halo_single = enable != 8;        // 8: halo kernel always with two patch buffers (A/B)
-  g_head_fwd_enabled = enable != 14 && enable != 6;   // 14: heads on the Toeplitz GEMM (A/B); 6 keeps the generic order
-  g_thin_fwd_enabled = enable != 18;  // 18: thin-input forward on the generic kernel (A/B)
-  g_tapsum_enabled = enable != 13;    // 13: narrow-output layers without the tap-sum forward (A/B)
-  g_thin_out_fast = enable != 13;     // 13: narrow-output long-K layers on the generic kernel (A/B)
-  g_toep_enabled = enable != 5;       // 5: fast kernels, plain head forward
-  g_pers_enabled = enable == 51 || enable == 52 || enable == 61;   // 61: the persistent form on its whole-round grids (the default of round 4 until the epilogue fix made gemm_fast_kernel faster); 50 = 1 now
-  g_pers_max_kt = (enable == 51 || enable == 52) ? (1 << 20) : 24;
-  g_pers_min_tiles = enable == 52 ? 1 : 256;      // 52: the persistent form from one tile on and for any K (tests)  // 51: every fast-kernel layer without split-K on the persistent form (A/B)
-  g_halo4 = enable == 53 ? 1 : (enable == 56 ? 16 : 0);   // 56: ... on the sixteen-wave / 64 x 32 wave-tile form (A/B, gemm_halo16.h)
-  //             // 53: plain halo forward on the four-wave / 128 x 64 wave-tile form (A/B, gemm_halo4.h)
-  g_wgrad_nine32_enabled = enable != 55;     // 55: the 1024-channel trunk at 16 x 32 on the per-tap weight-gradient kernel (A/B)
-  g_head_rows32 = enable != 57;       // 57: the 32 -> 3 head forward on head_fwd_kernel (A/B)
-  g_wgrad_taps_abl = (enable >= 200 && enable < 204) ? enable - 200 : 0;   // 201 / 202 / 203: all-taps weight gradient without DMA / without MFMAs / neither (timing only)
-  g_fast_abl = (enable >= 210 && enable < 220) ? (enable == 210 ? 16 : enable - 210) : (enable == 220 ? 32 : (enable == 221 ? 64 : (enable == 222 ? 96 : (enable == 223 ? 39 : (enable == 224 ? 192 : (enable == 225 ? 128 : 0))))));   // 224: no K loop, epilogue without its global stores; 225: whole kernel without the global stores of the epilogue   // 220 no epilogue, 221 no K loop, 222 neither (launch + set-up only), 223 MFMA-only loop without epilogue;   // 210-219: timing-only ablations of the 256 x 128 fast configuration (wrong results): 210 = activation tile staged for one tap in four; 210 + bits: 1 no DMA, 2 no barrier, 4 fragments of k-step 0 only, 8 no MFMAs
-  g_halo_xcd_auto = enable != 60;     // 60: halo kernel, block b -> tile b on every grid (no XCD-aware order on the one-round grids, A/B)
-  g_fast_fill = enable != 59;         // 59: few-tile medium-K layers on the 256-row tiles as before round 4 (A/B)
-  g_wgrad_taps_xcd = enable == 58;    // 58: all-taps weight gradient with the tiles of a pixel range co-located on one XCD (A/B: slower)
-  g_dgrad2_noconf = enable == 54;     // 54: dgrad2_rows_kernel with conflict-free LDS addresses (timing only, wrong results)
-  g_generic_splitk = enable != 48;    // 48: fp32 generic kernel without split-K (A/B; BASELINE config 2)
-  g_splitk_enabled = enable != 6;     // 6: fast kernels, no split-K  // 4: fast kernels but the per-tap weight-gradient kernel (A/B)
+  // 1 (any mode not named below): the shipped dispatch.  6 = fast kernels with the generic kernels' rounding points and summation
+  // order (it switches several paths off at once); 100-199, 200-203, 210-225 and 54: timing-only ablations, wrong results.
+  g_fast_enabled = enable != 0;                          // 0: generic kernels only
+  g_halo_enabled = enable != 3;                          // 3: fast kernels but no halo kernel (with the rows and ring paths off as well)
+  g_moments_fused = enable != 32 && enable != 6;         // 32: InstanceNorm moments always in their own pass; 6
+  g_ring_virt = enable != 40 && enable != 6;             // 40: reflect ring as four split-K strip GEMMs + ring_fold_kernel instead of the folded frame; 6: every product in fp32 until the fold
+  g_thin1_enabled = enable != 41 && enable != 6;         // 41: the one-output-channel layers (PatchGAN 512 -> 1) backward on the GEMM paths; 6
+  g_taps_dgrad4_enabled = enable != 42 && enable != 6;   // 42: 4x4 stride-2 data gradients (PatchGAN layers 1-2) on the merged-phase fast kernel; 6
+  g_taps_dgrad4_min_tiles = enable == 43 ? 1 : (1 << 30);   // 43: 4x4 stride-2 data gradients on the tap program + fringe at any size (slower in the step)
+  g_taps9_enabled = enable != 38 && enable != 6;         // 38: 3x3 layers with 32-pixel-wide grids on the split-K fast kernel; 6
+  g_taps4_enabled = enable != 36 && enable != 6;         // 36: 4x4 stride-1 layers on the fast kernel alone; 6
+  g_taps_enabled = enable != 35 && enable != 6;          // 35: stride-2 data gradients on the merged-phase fast kernel instead of the tap-program kernel; 6: tap outer, slab inner
+  g_rows_enabled = enable != 29 && enable != 3;          // 29: 64-channel 3x3 layers on the halo / fast kernels instead of conv_rows; 3
+  g_halo_abl = (enable >= 100 && enable < 200) ? enable - 100 : 0;   // 100 + bits: timing-only ablations of the halo kernel (gemm_halo.h ABL)
+  g_wgrad_nine_enabled = enable != 4;                    // 4: wide 3x3 layers on the per-tap fast weight gradient instead of the all-nine-taps one
+  g_wgrad_taps_enabled = enable != 12;                   // 12: fast kernels without the all-taps weight gradient
+  g_ring_enabled = enable != 7 && enable != 3;           // 7: reflect data gradient on the padded domain + fold; 3
+  g_merge_min_kt = enable == 9 ? 16 : 4;                 // 9: merged stride-phase data gradient only for long K loops
+  g_norm_fused = enable == 27 ? 0 : (enable == 28 ? 2 : 1);   // 27: InstanceNorm always as three kernels; 28: one-kernel form with the in-launch exchange
+  g_merge_min_tiles = enable == 26 ? 384 : 64;           // 26: merged stride-phase data gradient from 384 tiles on, as in round 1
+  g_fast_small = enable == 10 ? 0 : 20;                  // 10: no 128-row / 2-stage configs for short K loops
+  g_halo_xcd = enable == 15 ? 1 : (enable == 16 ? 2 : (enable == 17 ? 3 : 0));   // 15 / 16: XCD-aware tile orders of the halo kernel; 17: 4 N-tiles x 8 patches per XCD (one-round grids)
+  g_halo_mf16 = enable == 19;                            // 19: halo kernel on 16x16x32 MFMAs
+  g_halo_single = enable != 8;                           // 8: halo kernel always with two patch buffers
+  g_head_fwd_enabled = enable != 14 && enable != 6;      // 14: heads on the Toeplitz GEMM; 6
+  g_thin_fwd_enabled = enable != 18;                     // 18: thin-input forward on the generic kernel
+  g_tapsum_enabled = enable != 13;                       // 13: narrow-output layers without the tap-sum forward ...
+  g_thin_out_fast = enable != 13;                        // 13: ... and the narrow-output long-K layers on the generic kernel
+  g_toep_enabled = enable != 5;                          // 5: fast kernels, plain head forward
+  g_pers_enabled = enable == 51 || enable == 52 || enable == 61;   // 51 / 52 / 61: the persistent form (off by default) ...
+  g_pers_max_kt = (enable == 51 || enable == 52) ? (1 << 20) : 24;   // ... 51, 52: for any K; 61: up to 24 K-tiles, the round-4 rule
+  g_pers_min_tiles = enable == 52 ? 1 : 256;             // ... 52: from one tile on (tests); 51, 61: on whole-round grids of >= 256 tiles
+  g_halo4 = enable == 53 ? 1 : (enable == 56 ? 16 : 0);  // 53: plain halo forward on the four-wave form (gemm_halo4.h); 56: on the sixteen-wave form (gemm_halo16.h)
+  g_wgrad_nine32_enabled = enable != 55;                 // 55: the 1024-channel trunk at 16 x 32 on the per-tap weight-gradient kernel
+  g_head_rows32 = enable != 57;                          // 57: the 32 -> 3 head forward on head_fwd_kernel
+  g_wgrad_taps_abl = (enable >= 200 && enable < 204) ? enable - 200 : 0;   // 201 / 202 / 203: all-taps weight gradient without DMA / without MFMAs / neither
+  // 210-219: the 256 x 128 fast configuration, 210 = activation tile staged for one tap in four, 210 + bits: 1 no DMA, 2 no barrier,
+  // 4 fragments of k-step 0 only, 8 no MFMAs; 220 no epilogue, 221 no K loop, 222 neither (launch + set-up only), 223 MFMA-only loop
+  // without epilogue; 224: no K loop, epilogue without its global stores; 225: whole kernel without the global stores of the epilogue
+  g_fast_abl = (enable >= 210 && enable < 220) ? (enable == 210 ? 16 : enable - 210) : (enable == 220 ? 32 : (enable == 221 ? 64 : (enable == 222 ? 96 : (enable == 223 ? 39 : (enable == 224 ? 192 : (enable == 225 ? 128 : 0))))));
+  g_halo_xcd_auto = enable != 60;                        // 60: halo kernel, block b -> tile b on every grid (no XCD-aware order on the one-round grids)
+  g_fast_fill = enable != 59;                            // 59: few-tile medium-K layers on the 256-row tiles as before round 4
+  g_wgrad_taps_xcd = enable == 58;                       // 58: all-taps weight gradient with the tiles of a pixel range co-located on one XCD (slower)
+  g_dgrad2_noconf = enable == 54;                        // 54: dgrad2_rows_kernel with conflict-free LDS addresses
+  g_generic_splitk = enable != 48;                       // 48: fp32 generic kernel without split-K
+  g_splitk_enabled = enable != 6;                        // 6: no split-K on the fast kernels
   return JPDSE_OK;
 }
 #endif
@@ -455,27 +470,19 @@ int jpdse_conv_pack_weights(const jpdse_conv_desc* d, const float* w, void* fwd_
 
 int jpdse_conv_fwd(const jpdse_conv_desc* d, const void* x, const void* fwd_pack, const float* bias, void* y,
                    void* ws, size_t ws_bytes, void* stream) {
-  if (int rc = validate(d)) return rc;
-  JPDSE_REQUIRE(x && fwd_pack && y, "conv_fwd: null pointer");
   ConvPlan p;
-  make_plan(d, &p);
-  const size_t need = jpdse_conv_workspace_size(d);
-  if (ws == nullptr || ws_bytes < need)
-    return set_error(JPDSE_EWORKSPACE, "conv_fwd: workspace %zu < %zu", ws_bytes, need);
+  if (int rc = conv_enter("conv_fwd", d, x && fwd_pack && y, ws, ws_bytes, &p)) return rc;
   return d->dtype == JPDSE_BF16 ? conv_fwd_t<bf16_t>(d, p, x, fwd_pack, bias, y, ws, as_stream(stream))
                                 : conv_fwd_t<float>(d, p, x, fwd_pack, bias, y, ws, as_stream(stream));
 }
 
 int jpdse_conv_fwd_pool(const jpdse_conv_desc* d, const void* x, const void* fwd_pack, const float* bias, void* y,
                         void* y_pool, void* ws, size_t ws_bytes, void* stream) {
-  if (int rc = validate(d)) return rc;
-  JPDSE_REQUIRE(x && fwd_pack && y && y_pool, "conv_fwd_pool: null pointer");
   ConvPlan p;
-  make_plan(d, &p);
-  JPDSE_REQUIRE(p.OH >= 2 && p.OW >= 2, "conv_fwd_pool: output of %d x %d pixels", p.OH, p.OW);
-  const size_t need = jpdse_conv_workspace_size(d);
-  if (ws == nullptr || ws_bytes < need)
-    return set_error(JPDSE_EWORKSPACE, "conv_fwd_pool: workspace %zu < %zu", ws_bytes, need);
+  if (int rc = conv_enter("conv_fwd_pool", d, x && fwd_pack && y && y_pool, ws, ws_bytes, &p, [](const ConvPlan& q) {
+        JPDSE_REQUIRE(q.OH >= 2 && q.OW >= 2, "conv_fwd_pool: output of %d x %d pixels", q.OH, q.OW);
+        return (int)JPDSE_OK;
+      })) return rc;
   bool pooled = false;
   const int rc = d->dtype == JPDSE_BF16
                      ? conv_fwd_t<bf16_t>(d, p, x, fwd_pack, bias, y, ws, as_stream(stream), nullptr, y_pool, &pooled)
@@ -500,38 +507,28 @@ int32_t jpdse_convT_moment_slots(const jpdse_conv_desc* d) {
 
 int jpdse_conv_fwd_moments(const jpdse_conv_desc* d, const void* x, const void* fwd_pack, void* y, float* moments, void* ws,
                            size_t ws_bytes, void* stream) {
-  if (int rc = validate(d)) return rc;
-  JPDSE_REQUIRE(x && fwd_pack && y && moments, "conv_fwd_moments: null pointer");
   ConvPlan p;
-  make_plan(d, &p);
-  JPDSE_REQUIRE(conv_fwd_moment_slots(d, p) > 0, "conv_fwd_moments: this layer has no moment epilogue (jpdse_conv_moment_slots == 0)");
-  const size_t need = jpdse_conv_workspace_size(d);
-  if (ws == nullptr || ws_bytes < need)
-    return set_error(JPDSE_EWORKSPACE, "conv_fwd_moments: workspace %zu < %zu", ws_bytes, need);
+  if (int rc = conv_enter("conv_fwd_moments", d, x && fwd_pack && y && moments, ws, ws_bytes, &p, [d](const ConvPlan& q) {
+        JPDSE_REQUIRE(conv_fwd_moment_slots(d, q) > 0, "conv_fwd_moments: this layer has no moment epilogue (jpdse_conv_moment_slots == 0)");
+        return (int)JPDSE_OK;
+      })) return rc;
   return conv_fwd_t<bf16_t>(d, p, x, fwd_pack, nullptr, y, ws, as_stream(stream), moments);
 }
 
 int jpdse_convT_fwd_moments(const jpdse_conv_desc* d, const void* x, const void* dgrad_pack, void* y, float* moments, void* ws,
                             size_t ws_bytes, void* stream) {
-  if (int rc = validate(d)) return rc;
-  JPDSE_REQUIRE(x && dgrad_pack && y && moments, "convT_fwd_moments: null pointer");
   ConvPlan p;
-  make_plan(d, &p);
-  JPDSE_REQUIRE(convT_fwd_moment_slots(d, p) > 0, "convT_fwd_moments: this layer has no moment epilogue (jpdse_convT_moment_slots == 0)");
-  const size_t need = jpdse_conv_workspace_size(d);
-  if (ws == nullptr || ws_bytes < need)
-    return set_error(JPDSE_EWORKSPACE, "convT_fwd_moments: workspace %zu < %zu", ws_bytes, need);
+  if (int rc = conv_enter("convT_fwd_moments", d, x && dgrad_pack && y && moments, ws, ws_bytes, &p, [d](const ConvPlan& q) {
+        JPDSE_REQUIRE(convT_fwd_moment_slots(d, q) > 0, "convT_fwd_moments: this layer has no moment epilogue (jpdse_convT_moment_slots == 0)");
+        return (int)JPDSE_OK;
+      })) return rc;
   return conv_dgrad_t<bf16_t>(d, p, x, dgrad_pack, y, ws, as_stream(stream), nullptr, nullptr, moments);
 }
 
 int jpdse_conv_dgrad(const jpdse_conv_desc* d, const void* dy, const void* dgrad_pack, void* dx, void* ws,
                      size_t ws_bytes, void* stream) {
-  if (int rc = validate(d)) return rc;
-  JPDSE_REQUIRE(dy && dgrad_pack && dx, "conv_dgrad: null pointer");
   ConvPlan p;
-  make_plan(d, &p);
-  const size_t need = jpdse_conv_workspace_size(d);
-  if (ws == nullptr || ws_bytes < need) return set_error(JPDSE_EWORKSPACE, "conv_dgrad: workspace %zu < %zu", ws_bytes, need);
+  if (int rc = conv_enter("conv_dgrad", d, dy && dgrad_pack && dx, ws, ws_bytes, &p)) return rc;
   return d->dtype == JPDSE_BF16 ? conv_dgrad_t<bf16_t>(d, p, dy, dgrad_pack, dx, ws, as_stream(stream))
                                 : conv_dgrad_t<float>(d, p, dy, dgrad_pack, dx, ws, as_stream(stream));
 }
@@ -544,27 +541,19 @@ int jpdse_conv_dgrad_relu(const jpdse_conv_desc* d, const void* dy, const void* 
 
 int jpdse_conv_dgrad_fused(const jpdse_conv_desc* d, const void* dy, const void* dgrad_pack, const void* x,
                            const void* addend, void* dx, void* ws, size_t ws_bytes, void* stream) {
-  if (int rc = validate(d)) return rc;
-  JPDSE_REQUIRE(dy && dgrad_pack && dx, "conv_dgrad_fused: null pointer");
   ConvPlan p;
-  make_plan(d, &p);
-  const size_t need = jpdse_conv_workspace_size(d);
-  if (ws == nullptr || ws_bytes < need)
-    return set_error(JPDSE_EWORKSPACE, "conv_dgrad_fused: workspace %zu < %zu", ws_bytes, need);
+  if (int rc = conv_enter("conv_dgrad_fused", d, dy && dgrad_pack && dx, ws, ws_bytes, &p)) return rc;
   return d->dtype == JPDSE_BF16 ? conv_dgrad_t<bf16_t>(d, p, dy, dgrad_pack, dx, ws, as_stream(stream), x, addend)
                                 : conv_dgrad_t<float>(d, p, dy, dgrad_pack, dx, ws, as_stream(stream), x, addend);
 }
 
 int jpdse_conv_dgrad_fused_lrelu(const jpdse_conv_desc* d, const void* dy, const void* dgrad_pack, const void* x,
                                  float slope, const void* addend, void* dx, void* ws, size_t ws_bytes, void* stream) {
-  if (int rc = validate(d)) return rc;
-  JPDSE_REQUIRE(dy && dgrad_pack && dx && x, "conv_dgrad_fused_lrelu: null pointer");
-  JPDSE_REQUIRE(slope >= 0.f && slope < 1.f, "conv_dgrad_fused_lrelu: slope %g outside [0, 1)", (double)slope);
   ConvPlan p;
-  make_plan(d, &p);
-  const size_t need = jpdse_conv_workspace_size(d);
-  if (ws == nullptr || ws_bytes < need)
-    return set_error(JPDSE_EWORKSPACE, "conv_dgrad_fused_lrelu: workspace %zu < %zu", ws_bytes, need);
+  if (int rc = conv_enter("conv_dgrad_fused_lrelu", d, dy && dgrad_pack && dx && x, ws, ws_bytes, &p, [slope](const ConvPlan&) {
+        JPDSE_REQUIRE(slope >= 0.f && slope < 1.f, "conv_dgrad_fused_lrelu: slope %g outside [0, 1)", (double)slope);
+        return (int)JPDSE_OK;
+      })) return rc;
   return d->dtype == JPDSE_BF16
              ? conv_dgrad_t<bf16_t>(d, p, dy, dgrad_pack, dx, ws, as_stream(stream), x, addend, nullptr, slope)
              : conv_dgrad_t<float>(d, p, dy, dgrad_pack, dx, ws, as_stream(stream), x, addend, nullptr, slope);
@@ -580,29 +569,23 @@ int32_t jpdse_conv_dgrad_nsum_slots(const jpdse_conv_desc* d) {
 int jpdse_conv_dgrad_fused_nsums(const jpdse_conv_desc* d, const void* dy, const void* dgrad_pack, const void* x,
                                  const void* addend, void* dx, const void* norm_x, const float* norm_stats, int32_t norm_act,
                                  float norm_slope, float* sums, void* ws, size_t ws_bytes, void* stream) {
-  if (int rc = validate(d)) return rc;
-  JPDSE_REQUIRE(dy && dgrad_pack && dx && norm_x && norm_stats && sums, "conv_dgrad_fused_nsums: null pointer");
-  JPDSE_REQUIRE(norm_act == JPDSE_ACT_NONE || norm_act == JPDSE_ACT_RELU || norm_act == JPDSE_ACT_LRELU,
-                "conv_dgrad_fused_nsums: activation %d", norm_act);
   ConvPlan p;
-  make_plan(d, &p);
-  JPDSE_REQUIRE(d->dtype == JPDSE_BF16 && dgrad_nsum_slots(d, p) > 0,
-                "conv_dgrad_fused_nsums: this layer has no norm-backward-sum epilogue (jpdse_conv_dgrad_nsum_slots == 0)");
-  const size_t need = jpdse_conv_workspace_size(d);
-  if (ws == nullptr || ws_bytes < need)
-    return set_error(JPDSE_EWORKSPACE, "conv_dgrad_fused_nsums: workspace %zu < %zu", ws_bytes, need);
+  if (int rc = conv_enter("conv_dgrad_fused_nsums", d, dy && dgrad_pack && dx && norm_x && norm_stats && sums, ws, ws_bytes, &p,
+                          [d, norm_act](const ConvPlan& q) {
+        JPDSE_REQUIRE(norm_act == JPDSE_ACT_NONE || norm_act == JPDSE_ACT_RELU || norm_act == JPDSE_ACT_LRELU,
+                      "conv_dgrad_fused_nsums: activation %d", norm_act);
+        JPDSE_REQUIRE(d->dtype == JPDSE_BF16 && dgrad_nsum_slots(d, q) > 0,
+                      "conv_dgrad_fused_nsums: this layer has no norm-backward-sum epilogue (jpdse_conv_dgrad_nsum_slots == 0)");
+        return (int)JPDSE_OK;
+      })) return rc;
   const NormSink sink = {norm_x, norm_stats, sums, norm_act, norm_slope};
   return conv_dgrad_t<bf16_t>(d, p, dy, dgrad_pack, dx, ws, as_stream(stream), x, addend, nullptr, 0.f, &sink);
 }
 
 int jpdse_conv_wgrad(const jpdse_conv_desc* d, const void* x, const void* dy, float* dw, void* ws, size_t ws_bytes,
                      void* stream) {
-  if (int rc = validate(d)) return rc;
-  JPDSE_REQUIRE(x && dy && dw, "conv_wgrad: null pointer");
   ConvPlan p;
-  make_plan(d, &p);
-  if (ws == nullptr || ws_bytes < jpdse_conv_workspace_size(d))
-    return set_error(JPDSE_EWORKSPACE, "conv_wgrad: workspace %zu < %zu", ws_bytes, p.xpad_bytes);
+  if (int rc = conv_enter("conv_wgrad", d, x && dy && dw, ws, ws_bytes, &p)) return rc;
   return d->dtype == JPDSE_BF16 ? conv_wgrad_t<bf16_t>(d, p, x, dy, dw, ws, as_stream(stream))
                                 : conv_wgrad_t<float>(d, p, x, dy, dw, ws, as_stream(stream));
 }

@@ -29,9 +29,21 @@ static int check_tile_grid(const char* who, int N, int OH, int OW, int th, int t
   return JPDSE_OK;
 }
 
-// regions other than the plain GEMM launches (which record in place): returns the slot or -1
-static int prof_begin(hipStream_t s) {
-  if (!g_prof.on || (size_t)(2 * g_prof.used + 2) > g_prof.ev.size()) return -1;
+// Opts `Kernel` into `bytes` of dynamic LDS (more than the 64 KiB a launch gets by default), once per kernel instantiation.
+template <auto Kernel>
+static int opt_in_lds(const char* who, int bytes) {
+  static bool configured = false;
+  if (configured) return JPDSE_OK;
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e != hipSuccess) return set_error(JPDSE_ELAUNCH, "%s: hipFuncSetAttribute(%d B LDS): %s", who, bytes, hipGetErrorString(e));
+  configured = true;
+  return JPDSE_OK;
+}
+
+// A timed region on stream s (every launcher that times itself brackets its launches with these two): the slot, or -1 when
+// the timer is off, full, or (Ks, kdim) is not the GEMM signature that was selected.  prof_end files the region under its class.
+static int prof_begin(hipStream_t s, int Ks, long long kdim) {
+  if (!g_prof.on || Ks != g_prof.Ks || kdim != g_prof.kdim || (size_t)(2 * g_prof.used + 2) > g_prof.ev.size()) return -1;
   (void)hipEventRecord(g_prof.ev[2 * g_prof.used], s);
   return g_prof.used;
 }
@@ -43,6 +55,99 @@ static void prof_end(int slot, int cls, double flops, hipStream_t s) {
   g_prof.used = slot + 1;
 }
 
+// ---- the layer as the bf16 single-launch kernels see it: a conv over X with panel B into Y -- the forward of a layer, or one
+// stride phase of its data gradient (a stride-1 conv over dy).  Every bf16 path of conv_fwd_t / conv_dgrad_t starts from one of the
+// two constructors and hands the view to its kernel family through a converter (to_rows / to_halo / to_fast; the tap-program
+// launchers take the view itself): a new fused operand is added here and in the converters, not once per dispatch branch.
+struct ConvView {
+  const bf16_t* X; const bf16_t* B; const float* bias; bf16_t* Y;
+  int N, IH, IW, Cin_s, OH, OW, py, px;
+  int R, S, stride, reflect;      // reflect: mirrored instead of zero padding
+  int Kout, Ks_out;
+  long long ktot;                 // panel row stride (elements)
+  int tap_r, tap_s;               // panel offsets per filter-row / filter-column step
+  long long out_sn, out_sh, out_sw, out_base;
+  int act; float slope;
+  // optional fused operands, set by the dispatch after construction
+  const bf16_t* mask; float mask_slope; const bf16_t* addend;   // data gradient, Y's addressing: Y = (result + addend) * (mask > 0 ? 1 : mask_slope)
+  float* mom;                     // InstanceNorm moments of Y from the epilogue (rows / halo kernels)
+  const bf16_t* frame;            // folded frame of X: reflect data gradient in one launch (halo kernel, nine-tap program)
+};
+
+static ConvView view_fwd(const jpdse_conv_desc* d, const ConvPlan& p, const void* x, const void* pack, const float* bias, void* y) {
+  ConvView v = {};
+  v.X = reinterpret_cast<const bf16_t*>(x);
+  v.B = reinterpret_cast<const bf16_t*>(pack);
+  v.bias = bias;
+  v.Y = reinterpret_cast<bf16_t*>(y);
+  v.N = d->N; v.IH = d->H; v.IW = d->W; v.Cin_s = p.Cs; v.OH = p.OH; v.OW = p.OW;
+  v.py = v.px = d->pad;
+  v.R = d->R; v.S = d->S; v.stride = d->stride;
+  v.reflect = d->pad_mode == JPDSE_PAD_REFLECT;
+  v.Kout = d->K; v.Ks_out = p.Ks;
+  v.ktot = (long long)d->R * p.Lk_fwd; v.tap_r = p.Lk_fwd; v.tap_s = p.Cs;
+  v.out_sn = (long long)p.OH * p.OW * p.Ks; v.out_sh = (long long)p.OW * p.Ks; v.out_sw = p.Ks;
+  v.act = d->act; v.slope = d->slope;
+  return v;
+}
+
+// stride phase `i` of the data gradient: Uh x Uw taps over dy, written to every stride-th pixel of dx from the phase's first one
+static ConvView view_dgrad_phase(const jpdse_conv_desc* d, const ConvPlan& p, int i, const void* dy, const void* pack, void* dx) {
+  const Phase& f = p.ph[i];
+  const int st = d->stride;
+  ConvView v = {};
+  v.X = reinterpret_cast<const bf16_t*>(dy);
+  v.B = reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(pack) + f.pack_off);
+  v.Y = reinterpret_cast<bf16_t*>(dx);
+  v.N = d->N; v.IH = p.OH; v.IW = p.OW; v.Cin_s = p.Ks; v.OH = f.cnth; v.OW = f.cntw;
+  v.py = (f.Uh - 1) - f.i0h; v.px = (f.Uw - 1) - f.i0w;
+  v.R = f.Uh; v.S = f.Uw; v.stride = 1;
+  v.Kout = d->C; v.Ks_out = p.Cs;
+  v.ktot = (long long)f.Uh * f.Lk; v.tap_r = f.Lk; v.tap_s = p.Ks;
+  v.out_sn = (long long)d->H * d->W * p.Cs; v.out_sh = (long long)st * d->W * p.Cs; v.out_sw = (long long)st * p.Cs;
+  v.out_base = ((long long)(st * f.i0h + f.qh - d->pad) * d->W + (st * f.i0w + f.qw - d->pad)) * p.Cs;
+  v.act = JPDSE_ACT_NONE;
+  return v;
+}
+
+// the fields every argument struct of the tiled kernels shares, under the same names
+template <typename Args>
+static Args view_to(const ConvView& v) {
+  Args a = {};
+  a.X = v.X; a.B = v.B; a.bias = v.bias; a.Y = v.Y;
+  a.OH = v.OH; a.OW = v.OW; a.IH = v.IH; a.IW = v.IW; a.py = v.py; a.px = v.px;
+  a.Kout = v.Kout; a.Ks = v.Ks_out; a.b_rows = v.Ks_out;
+  a.out_sn = v.out_sn; a.out_sh = v.out_sh; a.out_sw = v.out_sw; a.out_base = v.out_base;
+  a.act = v.act; a.slope = v.slope;
+  a.mask = v.mask; a.addend = v.addend;
+  return a;
+}
+static RowsArgs to_rows(const ConvView& v) {        // 64-channel input, 3x3: the stride goes to launch_rows
+  RowsArgs r = view_to<RowsArgs>(v);
+  r.N = v.N;
+  r.mom = v.mom;                                    // (launch_rows_cfg sets the slot count with the band height)
+  return r;
+}
+static HaloArgs to_halo(const ConvView& v) {
+  HaloArgs h = view_to<HaloArgs>(v);
+  h.N = v.N; h.Cs = v.Cin_s; h.reflect = v.reflect;
+  h.V = v.frame;
+  h.mom = v.mom;
+  h.mom_slots = v.mom != nullptr ? (v.OH / 4) * (v.OW / 64) : 0;
+  return h;
+}
+static FastArgs to_fast(const ConvView& v) {        // dense panel (b_stride / b_tap_* = 0); splits and slabs are the caller's
+  FastArgs f = view_to<FastArgs>(v);
+  f.M = v.N * v.OH * v.OW; f.Cs = v.Cin_s;
+  f.R = v.R; f.S = v.S; f.sy = f.sx = v.stride; f.reflect = v.reflect;
+  f.mask_slope = v.mask_slope;
+  return f;
+}
+static bool rows_ok(int R, int S, int stride, int reflect, int act, int OH, int OW, int Cs_in, int Ks_out);
+static bool halo_ok(int R, int S, int stride, int OH, int OW, int Cs_in, int Ks_out);
+static bool rows_ok(const ConvView& v) { return rows_ok(v.R, v.S, v.stride, v.reflect, v.act, v.OH, v.OW, v.Cin_s, v.Ks_out); }
+static bool halo_ok(const ConvView& v) { return halo_ok(v.R, v.S, v.stride, v.OH, v.OW, v.Cin_s, v.Ks_out); }
+
 template <typename T, int BM, int BN, int WM, int WN>
 static int launch_fwd_cfg(const GemmFwdArgs& a_in, hipStream_t s) {
   GemmFwdArgs a = a_in;
@@ -52,9 +157,7 @@ static int launch_fwd_cfg(const GemmFwdArgs& a_in, hipStream_t s) {
   a.splits = (a.col_mod == 0 && a.partial != nullptr) ? generic_splitk_for((int)sizeof(T), a.M, a.Ks, a.R * a.cpr, a.M / (a.OH * a.OW)) : 1;
   if (a.splits > 1 && (size_t)a.splits * a.M * a.Ks * sizeof(float) > a.partial_cap) a.splits = 1;
   const long long kdim = (long long)a.R * a.cpr * (64 / (int)sizeof(T));
-  const bool timed = g_prof.on && a.Ks == g_prof.Ks && kdim == g_prof.kdim &&
-                     (size_t)(2 * g_prof.used + 2) <= g_prof.ev.size();
-  if (timed) (void)hipEventRecord(g_prof.ev[2 * g_prof.used], s);
+  const int pslot = prof_begin(s, a.Ks, kdim);
   hipLaunchKernelGGL((gemm_fwd_kernel<T, BM, BN, WM, WN>), dim3(tiles_m * tiles_n, a.splits > 1 ? a.splits : 1), dim3(64 * WM * WN), lds, s, a);
   int rc = check_launch("gemm_fwd_kernel");
   if (rc == JPDSE_OK && a.splits > 1) {
@@ -62,12 +165,7 @@ static int launch_fwd_cfg(const GemmFwdArgs& a_in, hipStream_t s) {
     hipLaunchKernelGGL((gemm_splitk_finish_kernel<T>), dim3((unsigned)((total_vec + 255) / 256)), dim3(256), 0, s, a, total_vec);
     rc = check_launch("gemm_splitk_finish_kernel");
   }
-  if (timed) {
-    (void)hipEventRecord(g_prof.ev[2 * g_prof.used + 1], s);
-    g_prof.flops[g_prof.used] = 2.0 * (double)a.M * (double)a.Ks * (double)kdim;
-    g_prof.cls[g_prof.used] = 0;
-    ++g_prof.used;
-  }
+  prof_end(pslot, 0, 2.0 * (double)a.M * (double)a.Ks * (double)kdim, s);
   return rc;
 }
 
@@ -134,16 +232,8 @@ template <int WM, int WN, int TM, int TN, int VAR, int STAGES = 3>
 static int launch_fast_cfg(FastBatch& b, hipStream_t s) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   constexpr int lds = STAGES * (BM + BN) * 128;
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_fast_kernel<WM, WN, TM, TN, VAR, STAGES>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return set_error(JPDSE_ELAUNCH, "gemm_fast: hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
-    configured = true;
-  }
+  if (int rc = opt_in_lds<&gemm_fast_kernel<WM, WN, TM, TN, VAR, STAGES>>("gemm_fast", lds)) return rc;
   int total = 0;
-  double flops = 0.0;
-  bool timed = g_prof.on && (size_t)(2 * g_prof.used + 2) <= g_prof.ev.size();
   for (int i = 0; i < b.n; ++i) {
     const FastArgs& a = b.p[i];
     if ((a.Y == nullptr && !a.no_finish) || ((a.splits > 1 || a.no_finish) && a.partial == nullptr))
@@ -164,23 +254,16 @@ static int launch_fast_cfg(FastBatch& b, hipStream_t s) {
     b.p[i].abl = g_fast_abl;
     b.p[i].xcd_map = 0;       // (the XCD-aware tile order, round-3 developer mode 30, measured neutral and was retired: DESIGN.md 4.1 (xi))
     total += ((a.M + BM - 1) / BM) * ((a.Ks + BN - 1) / BN) * (a.splits > 1 ? a.splits : 1);
-    const long long kdim = (long long)a.R * a.S * a.Cs;
-    flops += 2.0 * (double)a.M * (double)a.Ks * (double)kdim;
-    timed = timed && b.n == 1 && a.Ks == g_prof.Ks && kdim == g_prof.kdim;
   }
   for (int i = b.n; i < 5; ++i) b.first_tile[i] = total;
-  if (timed) (void)hipEventRecord(g_prof.ev[2 * g_prof.used], s);
+  const long long kdim = (long long)b.p[0].R * b.p[0].S * b.p[0].Cs;
+  const int pslot = b.n == 1 ? prof_begin(s, b.p[0].Ks, kdim) : -1;      // a multi-problem launch is not one GEMM: not timed
   hipLaunchKernelGGL((gemm_fast_kernel<WM, WN, TM, TN, VAR, STAGES>), dim3(total), dim3(64 * WM * WN), lds, s, b);
   if (b.n == 1 && b.p[0].splits > 1 && !b.p[0].no_finish) {
     const long long total_vec = (long long)b.p[0].M * (b.p[0].Ks / 8);
     hipLaunchKernelGGL(splitk_finish_kernel, dim3(ew_blocks(total_vec)), dim3(256), 0, s, b.p[0], total_vec);
   }
-  if (timed) {
-    (void)hipEventRecord(g_prof.ev[2 * g_prof.used + 1], s);
-    g_prof.flops[g_prof.used] = flops;
-    g_prof.cls[g_prof.used] = 0;
-    ++g_prof.used;
-  }
+  prof_end(pslot, 0, 2.0 * (double)b.p[0].M * (double)b.p[0].Ks * (double)kdim, s);
   return check_launch("gemm_fast_kernel");
 }
 
@@ -228,15 +311,11 @@ template <int TN>
 static int launch_pers_cfg(FastBatch& b, hipStream_t s) {
   constexpr int BN = 2 * TN * 32;
   constexpr int lds = 3 * (256 + BN) * 128;
-  static bool configured = false;
-  static int cus = 256;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pers_kernel<TN>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return set_error(JPDSE_ELAUNCH, "gemm_pers: hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
+  if (int rc = opt_in_lds<&gemm_pers_kernel<TN>>("gemm_pers", lds)) return rc;
+  static const int cus = [] {
     int dev = 0, n = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) cus = n;
-    configured = true;
-  }
+    return (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
+  }();
   int total = 0;
   for (int i = 0; i < b.n; ++i) {
     const FastArgs& a = b.p[i];
@@ -339,7 +418,6 @@ JPDSE_SWITCH(bool, g_fast_enabled, true);   // jpdse_debug_set_fast_path(0) forc
 // the 256 CUs many times over or be an exact multiple of them; in between (e.g. the 288 tiles of the
 // ResnetBlock data gradient) the generic 128x128 kernel with 3 co-resident blocks per CU wins
 // (measured: scripts/bench_conv.py, profiles/r01_conv_layers_*.log).
-static bool prefer_320(int M, int Ks);
 static bool fast_pays(int M, int Ks, int k_tiles) {
   if (!g_fast_enabled) return false;
   if (g_pers_min_tiles <= 1 && g_pers_enabled && k_tiles >= 4 && Ks >= 64) return true;   // developer mode 52 (tests): small problems reach the persistent form
@@ -373,13 +451,7 @@ static int launch_halo_cfg_impl(const HaloArgs& a, hipStream_t s) {
   constexpr int BN = 2 * TN * 32;
   constexpr int UH = ((4 + 2) * (64 + 2) + 7) / 8;
   constexpr int lds = (SINGLE ? 1 : 2) * UH * 1024 + 3 * BN * 128;
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_halo_kernel<4, TN, ABL, SINGLE, MF16, MOM, VIRT, NSUM>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return set_error(JPDSE_ELAUNCH, "gemm_halo: hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
-    configured = true;
-  }
+  if (int rc = opt_in_lds<&gemm_halo_kernel<4, TN, ABL, SINGLE, MF16, MOM, VIRT, NSUM>>("gemm_halo", lds)) return rc;
   if (int rc = check_tile_grid("gemm_halo", a.N, a.OH, a.OW, 4, 64, a.Cs, (long long)a.N * a.IH * a.IW * a.Cs, (long long)a.N * a.OH * a.OW * a.Ks)) return rc;
   if (VIRT && (a.V == nullptr || a.py != 1 || a.px != 1 || a.IH != a.OH || a.IW != a.OW || a.OH < 8 || a.reflect || (a.Cs < 128) != SINGLE))
     return set_error(JPDSE_EINVAL, "gemm_halo: folded-frame form needs a frame, pad 1, equal grids, >= 8 rows");
@@ -391,16 +463,9 @@ static int launch_halo_cfg_impl(const HaloArgs& a, hipStream_t s) {
   const int tiles = a.N * (a.OH / 4) * (a.OW / 64) * ((a.Ks + BN - 1) / BN);
   const long long kdim = 9LL * a.Cs;
   const int M = a.N * a.OH * a.OW;
-  const bool timed = g_prof.on && a.Ks == g_prof.Ks && kdim == g_prof.kdim &&
-                     (size_t)(2 * g_prof.used + 2) <= g_prof.ev.size();
-  if (timed) (void)hipEventRecord(g_prof.ev[2 * g_prof.used], s);
+  const int pslot = prof_begin(s, a.Ks, kdim);
   hipLaunchKernelGGL((gemm_halo_kernel<4, TN, ABL, SINGLE, MF16, MOM, VIRT, NSUM>), dim3(tiles), dim3(512), lds, s, a);
-  if (timed) {
-    (void)hipEventRecord(g_prof.ev[2 * g_prof.used + 1], s);
-    g_prof.flops[g_prof.used] = 2.0 * (double)M * (double)a.Ks * (double)kdim;
-    g_prof.cls[g_prof.used] = 0;
-    ++g_prof.used;
-  }
+  prof_end(pslot, 0, 2.0 * (double)M * (double)a.Ks * (double)kdim, s);
   return check_launch("gemm_halo_kernel");
 }
 
@@ -410,25 +475,14 @@ static int g_halo4 = 0;
 static int launch_halo4(const HaloArgs& a, hipStream_t s) {
   constexpr int UH = ((4 + 2) * (64 + 2) + 7) / 8;
   constexpr int lds = 2 * UH * 1024 + 3 * 128 * 128;
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_halo4_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return set_error(JPDSE_ELAUNCH, "gemm_halo4: hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
-    configured = true;
-  }
+  if (int rc = opt_in_lds<&gemm_halo4_kernel>("gemm_halo4", lds)) return rc;
   if (int rc = check_tile_grid("gemm_halo4", a.N, a.OH, a.OW, 4, 64, a.Cs, (long long)a.N * a.IH * a.IW * a.Cs, (long long)a.N * a.OH * a.OW * a.Ks)) return rc;
   if (a.Cs < 128 || a.Ks % 128 != 0) return set_error(JPDSE_EINVAL, "gemm_halo4: needs >= 128 input channels and 128-channel output tiles");
   const int tiles = a.N * (a.OH / 4) * (a.OW / 64) * (a.Ks / 128);
   const long long kdim = 9LL * a.Cs;
-  const bool timed = g_prof.on && a.Ks == g_prof.Ks && kdim == g_prof.kdim && (size_t)(2 * g_prof.used + 2) <= g_prof.ev.size();
-  if (timed) (void)hipEventRecord(g_prof.ev[2 * g_prof.used], s);
+  const int pslot = prof_begin(s, a.Ks, kdim);
   hipLaunchKernelGGL(gemm_halo4_kernel, dim3(tiles), dim3(256), lds, s, a);
-  if (timed) {
-    (void)hipEventRecord(g_prof.ev[2 * g_prof.used + 1], s);
-    g_prof.flops[g_prof.used] = 2.0 * (double)a.N * a.OH * a.OW * (double)a.Ks * (double)kdim;
-    g_prof.cls[g_prof.used] = 0;
-    ++g_prof.used;
-  }
+  prof_end(pslot, 0, 2.0 * (double)a.N * a.OH * a.OW * (double)a.Ks * (double)kdim, s);
   return check_launch("gemm_halo4_kernel");
 }
 #endif
@@ -438,12 +492,7 @@ static int launch_halo4(const HaloArgs& a, hipStream_t s) {
 static int launch_halo16(const HaloArgs& a, hipStream_t s) {
   constexpr int UH = ((4 + 2) * (64 + 2) + 7) / 8;
   constexpr int lds = 2 * UH * 1024 + 3 * 128 * 128;
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_halo16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return set_error(JPDSE_ELAUNCH, "gemm_halo16: hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
-    configured = true;
-  }
+  if (int rc = opt_in_lds<&gemm_halo16_kernel>("gemm_halo16", lds)) return rc;
   if (int rc = check_tile_grid("gemm_halo16", a.N, a.OH, a.OW, 4, 64, a.Cs, (long long)a.N * a.IH * a.IW * a.Cs, (long long)a.N * a.OH * a.OW * a.Ks)) return rc;
   if (a.Cs < 128 || a.Ks % 128 != 0) return set_error(JPDSE_EINVAL, "gemm_halo16: needs >= 128 input channels and 128-channel output tiles");
   const int tiles = a.N * (a.OH / 4) * (a.OW / 64) * (a.Ks / 128);
@@ -510,6 +559,18 @@ static int rows_band_height(int N, int OH, int strips, int n_tiles, long long wa
     if (OH % cand == 0) return cand;
   return min_th;
 }
+// the same choice for the thin-input passes, whose last band may be ragged: fewest (rounds of 512 blocks: two per CU) x (rows per
+// block + the ~4 rows a block pays for its filter load and prologue)
+static int rows_band_height_by_cost(int N, int OH, int tiles_w) {
+  int th = 8;
+  long long best = -1;
+  for (int cand = 64; cand >= 8; cand >>= 1) {
+    const long long blocks = (long long)N * ((OH + cand - 1) / cand) * tiles_w;
+    const long long cost = ((blocks + 511) / 512) * (cand + 4);
+    if (best < 0 || cost < best) { best = cost; th = cand; }
+  }
+  return th;
+}
 
 // 3x3 convs over 64-channel inputs (stride 1 | 2, zero padding): filter in registers, input rows streamed once (conv_rows.h)
 JPDSE_SWITCH(int, g_rows_enabled, 1);       // 29: these layers on the halo / fast kernels (A/B)
@@ -523,13 +584,7 @@ static bool rows_ok(int R, int S, int stride, int reflect, int act, int OH, int 
 template <int STRIDE, int WC, bool FUSED>
 static int launch_rows_cfg(RowsArgs a, hipStream_t s) {
   typedef RowsGeom<STRIDE, WC> G;
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_rows_kernel<STRIDE, WC, FUSED>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-    if (e != hipSuccess) return set_error(JPDSE_ELAUNCH, "conv_rows: hipFuncSetAttribute(%d B LDS): %s", G::LDS, hipGetErrorString(e));
-    configured = true;
-  }
+  if (int rc = opt_in_lds<&conv_rows_kernel<STRIDE, WC, FUSED>>("conv_rows", G::LDS)) return rc;
   if (int rc = check_tile_grid("conv_rows", a.N, a.OH, a.OW, 4, 64, 64, (long long)a.N * a.IH * a.IW * 64, (long long)a.N * a.OH * a.OW * a.Ks)) return rc;
   if (a.Ks % (32 * WC) != 0) return set_error(JPDSE_EINVAL, "conv_rows: %d output channels do not split into %d-wide wave tiles", a.Ks, 32 * WC);
   a.n_tiles = a.Ks / (32 * WC);
@@ -560,16 +615,10 @@ static int launch_rows(const RowsArgs& a, int stride, hipStream_t s) {
 JPDSE_SWITCH(int, g_dgrad2_noconf, 0);    // 54: TIMING-ONLY ablation, conflict-free LDS addresses (developer build)
 static int launch_dgrad2_rows(Dgrad2Args a, hipStream_t s) {
   typedef Dgrad2Geom G;
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dgrad2_rows_kernel<false>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
+  if (int rc = opt_in_lds<&dgrad2_rows_kernel<false>>("dgrad2_rows", G::LDS)) return rc;
 #ifdef JPDSE_DEV
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dgrad2_rows_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
+  if (int rc = opt_in_lds<&dgrad2_rows_kernel<true>>("dgrad2_rows", G::LDS)) return rc;
 #endif
-    if (e != hipSuccess) return set_error(JPDSE_ELAUNCH, "dgrad2_rows: hipFuncSetAttribute(%d B LDS): %s", G::LDS, hipGetErrorString(e));
-    configured = true;
-  }
   if (int rc = check_tile_grid("dgrad2_rows", a.N, a.OH, a.OW, 4, 64, 128, (long long)a.N * a.OH * a.OW * 128, 4LL * a.N * a.OH * a.OW * 64)) return rc;
   a.strips = a.OW / 64;
   const int th = rows_band_height(a.N, a.OH, a.strips, 1, 256);
@@ -596,24 +645,11 @@ static bool head_rows_ok(const HeadFwdArgs& a, int cin) {
 template <int R, int CIN = 64>
 static int launch_head_rows(const HeadFwdArgs& a, hipStream_t s) {
   typedef HeadRowsGeom<R, CIN> G;
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&head_rows_kernel<R, CIN>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-    if (e != hipSuccess) return set_error(JPDSE_ELAUNCH, "head_rows: hipFuncSetAttribute(%d B LDS): %s", G::LDS, hipGetErrorString(e));
-    configured = true;
-  }
+  if (int rc = opt_in_lds<&head_rows_kernel<R, CIN>>("head_rows", G::LDS)) return rc;
   const int strips = a.OW / 128;
-  int th = 0;
-  for (int cand = 64; cand >= 8; cand >>= 1) {
-    if (a.OH % cand != 0) continue;
-    if ((long long)a.N * strips * (a.OH / cand) >= 512) { th = cand; break; }
-  }
-  if (th == 0)
-    for (int cand = 16; cand >= 8; cand >>= 1)
-      if (a.OH % cand == 0) { th = cand; break; }
-  if (th == 0 || strips == 0 || a.OW % 128 != 0)
+  if (a.OH % 8 != 0 || strips == 0 || a.OW % 128 != 0)       // (rows_band_height would answer its minimum for a height no band divides)
     return set_error(JPDSE_EINVAL, "head_rows: output grid %d x %d does not tile into bands of >= 8 rows x 128-pixel strips", a.OH, a.OW);
+  const int th = rows_band_height(a.N, a.OH, strips, 1, 512, 8);
   const int bands = a.OH / th;
   hipLaunchKernelGGL((head_rows_kernel<R, CIN>), dim3((unsigned)(a.N * bands * strips)), dim3(256), G::LDS, s, a, th, bands, strips);
   return check_launch("head_rows_kernel");
@@ -623,24 +659,12 @@ static int launch_head_rows(const HeadFwdArgs& a, hipStream_t s) {
 // data gradient of PatchGAN layer 0 with respect to the image channels (thin_dgrad2_rows.h)
 static int launch_thin_dgrad2_rows(ThinDgrad2Args a, hipStream_t s) {
   typedef ThinDgrad2Geom G;
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&thin_dgrad2_rows_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-    if (e != hipSuccess) return set_error(JPDSE_ELAUNCH, "thin_dgrad2_rows: hipFuncSetAttribute(%d B LDS): %s", G::LDS, hipGetErrorString(e));
-    configured = true;
-  }
+  if (int rc = opt_in_lds<&thin_dgrad2_rows_kernel>("thin_dgrad2_rows", G::LDS)) return rc;
+  if (a.H % 8 != 0 || a.W <= 0 || a.W % 256 != 0)
+    return set_error(JPDSE_EINVAL, "thin_dgrad2_rows: image of %d x %d does not tile into bands of >= 8 rows x 256-pixel strips", a.H, a.W);
   a.strips = a.W / 256;
-  int th = 0;
-  for (int cand = 64; cand >= 8; cand >>= 1) {
-    if (a.H % cand != 0) continue;
-    if ((long long)a.N * a.strips * (a.H / cand) >= 512) { th = cand; break; }
-  }
-  if (th == 0)
-    for (int cand = 16; cand >= 8; cand >>= 1)
-      if (a.H % cand == 0) { th = cand; break; }
-  a.TH = th;
-  a.bands = a.H / th;
+  a.TH = rows_band_height(a.N, a.H, a.strips, 1, 512, 8);
+  a.bands = a.H / a.TH;
   hipLaunchKernelGGL(thin_dgrad2_rows_kernel, dim3((unsigned)(a.N * a.bands * a.strips)), dim3(256), G::LDS, s, a);
   return check_launch("thin_dgrad2_rows_kernel");
 }
@@ -649,22 +673,9 @@ static int launch_thin_dgrad2_rows(ThinDgrad2Args a, hipStream_t s) {
 // PatchGAN layer 0 forward (40-channel input, 4x4 stride 2, 64 outputs) as a row-streaming pass (thin_rows.h)
 static int launch_thin_rows(ThinFwdArgs a, hipStream_t s) {
   typedef ThinRowsGeom G;
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&thin_rows_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-    if (e != hipSuccess) return set_error(JPDSE_ELAUNCH, "thin_rows: hipFuncSetAttribute(%d B LDS): %s", G::LDS, hipGetErrorString(e));
-    configured = true;
-  }
+  if (int rc = opt_in_lds<&thin_rows_kernel>("thin_rows", G::LDS)) return rc;
   a.tiles_w = (a.OW + 63) / 64;
-  // band height: fewest (rounds of 512 blocks: two per CU) x (rows per block + the ~4 rows a block pays for its filter load and prologue)
-  int th = 8;
-  long long best = -1;
-  for (int cand = 64; cand >= 8; cand >>= 1) {
-    const long long blocks = (long long)a.N * ((a.OH + cand - 1) / cand) * a.tiles_w;
-    const long long cost = ((blocks + 511) / 512) * (cand + 4);
-    if (best < 0 || cost < best) { best = cost; th = cand; }
-  }
+  const int th = rows_band_height_by_cost(a.N, a.OH, a.tiles_w);
   const int bands = (a.OH + th - 1) / th;
   hipLaunchKernelGGL(thin_rows_kernel, dim3((unsigned)(a.N * bands * a.tiles_w)), dim3(256), G::LDS, s, a, th, bands);
   return check_launch("thin_rows_kernel");
@@ -676,23 +687,10 @@ static int launch_thin_rows(ThinFwdArgs a, hipStream_t s) {
 template <int R, bool DUAL>
 static int launch_thin_in_rows(ThinInArgs a, hipStream_t s) {
   typedef ThinInGeom<R> G;
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&thin_in_rows_kernel<R, DUAL>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-    if (e != hipSuccess) return set_error(JPDSE_ELAUNCH, "thin_in_rows: hipFuncSetAttribute(%d B LDS): %s", G::LDS, hipGetErrorString(e));
-    configured = true;
-  }
+  if (int rc = opt_in_lds<&thin_in_rows_kernel<R, DUAL>>("thin_in_rows", G::LDS)) return rc;
   a.strips = (a.OW + 63) / 64;
-  int th = 8;
-  long long best = -1;
-  for (int cand = 64; cand >= 8; cand >>= 1) {
-    const long long blocks = (long long)a.N * ((a.OH + cand - 1) / cand) * a.strips;
-    const long long cost = ((blocks + 511) / 512) * (cand + 4);
-    if (best < 0 || cost < best) { best = cost; th = cand; }
-  }
-  a.TH = th;
-  a.bands = (a.OH + th - 1) / th;
+  a.TH = rows_band_height_by_cost(a.N, a.OH, a.strips);
+  a.bands = (a.OH + a.TH - 1) / a.TH;
   hipLaunchKernelGGL((thin_in_rows_kernel<R, DUAL>), dim3((unsigned)(a.N * a.bands * a.strips)), dim3(256), G::LDS, s, a);
   if (int rc = check_launch("thin_in_rows_kernel")) return rc;
   if (DUAL) {
@@ -717,8 +715,7 @@ JPDSE_SWITCH(int, g_taps_enabled, 1);       // 35: these layers on the merged-ph
 JPDSE_SWITCH(int, g_taps_dgrad4_enabled, 1);     // 42: the 4x4 stride-2 data gradients on the merged-phase fast kernel (A/B)
 JPDSE_SWITCH(int, g_taps_dgrad4_min_tiles, 1 << 30);   // 43: take the path at any size (developer build: tests, A/B) -- the shipped build never does, see below
 struct TapsDgrad2Geom { int core_h, core_w, fringe, taps4; };
-static bool taps_dgrad2_geom(const jpdse_conv_desc* d, const ConvPlan& p, const void* mask, const void* addend, const float* mom,
-                             TapsDgrad2Geom* g) {
+static bool taps_dgrad2_geom(const jpdse_conv_desc* d, const ConvPlan& p, const float* mom, TapsDgrad2Geom* g) {
   if (!(g_fast_enabled && g_taps_enabled) || d->dtype != JPDSE_BF16 || d->pad_mode == JPDSE_PAD_REFLECT) return false;
   const bool k3 = d->R == 3 && d->S == 3 && d->pad == 1, k4 = d->R == 4 && d->S == 4 && d->pad == 2 && g_taps_dgrad4_enabled;
   if (d->stride != 2 || !(k3 || k4) || p.nph != 4) return false;
@@ -752,24 +749,17 @@ static bool taps_dgrad2_geom(const jpdse_conv_desc* d, const ConvPlan& p, const 
   // prologue / epilogue bound on either kernel; the path stays in the developer build only.
   if (k4 && (long long)d->N * (core_h / 4) * (core_w / 64) * ((p.Cs + 127) / 128) < g_taps_dgrad4_min_tiles) return false;
   if (g != nullptr) *g = {core_h, core_w, fringe, k4 ? 1 : 0};
-  (void)mask; (void)addend;
   return true;
 }
-static bool taps_dgrad2_ok(const jpdse_conv_desc* d, const ConvPlan& p, const void* mask, const void* addend, const float* mom) {
-  return taps_dgrad2_geom(d, p, mask, addend, mom, nullptr);
+static bool taps_dgrad2_ok(const jpdse_conv_desc* d, const ConvPlan& p, const float* mom) {
+  return taps_dgrad2_geom(d, p, mom, nullptr);
 }
 
 template <int TN, int T1A, int T0B, int T1B>
 static int launch_taps_dgrad2_cfg(const TapsArgs& a, int total, hipStream_t s) {
   constexpr int PH = 5, PW = 65;
   constexpr int lds = 2 * ((PH * PW + 7) / 8) * 1024 + 3 * (2 * TN * 32) * 128;
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_taps_kernel<TN, 4, T1A, T0B, T1B, 1, PH, PW>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return set_error(JPDSE_ELAUNCH, "gemm_taps: hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
-    configured = true;
-  }
+  if (int rc = opt_in_lds<&gemm_taps_kernel<TN, 4, T1A, T0B, T1B, 1, PH, PW>>("gemm_taps", lds)) return rc;
   if (int rc = check_tile_grid("gemm_taps(stride-2 data gradient)", a.N, a.OH, a.OW, 4, 64, a.Cs, (long long)a.N * a.IH * a.IW * a.Cs,
                                4LL * a.N * a.OH * a.OW * a.Ks)) return rc;
   if (total != 2 * a.nblk0 || a.nblk0 != a.N * (a.OH / 4) * (a.OW / 64) * ((a.Ks + 2 * TN * 32 - 1) / (2 * TN * 32)))
@@ -781,7 +771,7 @@ static int launch_taps_dgrad2_cfg(const TapsArgs& a, int total, hipStream_t s) {
 static int launch_taps_dgrad2(const jpdse_conv_desc* d, const ConvPlan& p, const void* dy, const void* pack, void* dx, hipStream_t s,
                               const void* mask, const void* addend, float mask_slope = 0.f) {
   TapsDgrad2Geom geo = {};
-  if (!taps_dgrad2_geom(d, p, mask, addend, nullptr, &geo)) return set_error(JPDSE_EINVAL, "gemm_taps: not a stride-2 data gradient it covers");
+  if (!taps_dgrad2_geom(d, p, nullptr, &geo)) return set_error(JPDSE_EINVAL, "gemm_taps: not a stride-2 data gradient it covers");
   TapsArgs a = {};
   a.mask = reinterpret_cast<const bf16_t*>(mask);
   a.mask_slope = mask_slope;
@@ -842,29 +832,13 @@ static int launch_taps_dgrad2(const jpdse_conv_desc* d, const ConvPlan& p, const
     for (int q = 0; q < 2; ++q) {
       const int j0 = rect[q][0], c0 = rect[q][1], rows = rect[q][2], cols = rect[q][3];
       if (rows <= 0 || cols <= 0) continue;
-      FastArgs g = {};
-      g.X = a.X;
-      g.B = reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(pack) + f.pack_off);
-      g.Y = a.Y;
+      FastArgs g = to_fast(view_dgrad_phase(d, p, i, dy, pack, dx));      // the phase, cut down to the rectangle
       g.M = d->N * rows * cols;
       g.OH = rows;
       g.OW = cols;
-      g.IH = p.OH;
-      g.IW = p.OW;
-      g.Cs = p.Ks;
-      g.R = f.Uh;
-      g.S = f.Uw;
-      g.sy = g.sx = 1;
-      g.py = (f.Uh - 1) - f.i0h - j0;
-      g.px = (f.Uw - 1) - f.i0w - c0;
-      g.Kout = d->C;
-      g.Ks = p.Cs;
-      g.b_rows = p.Cs;
-      g.out_sn = a.out_sn;
-      g.out_sh = a.out_sh;
-      g.out_sw = a.out_sw;
-      g.out_base = ((long long)(2 * (f.i0h + j0) + f.qh - d->pad) * d->W + (2 * (f.i0w + c0) + f.qw - d->pad)) * p.Cs;
-      g.act = JPDSE_ACT_NONE;
+      g.py -= j0;
+      g.px -= c0;
+      g.out_base += j0 * g.out_sh + c0 * g.out_sw;
       g.mask = a.mask;
       g.mask_slope = mask_slope;
       g.addend = a.addend;
@@ -884,20 +858,14 @@ static int launch_taps_dgrad2(const jpdse_conv_desc* d, const ConvPlan& p, const
 // (fp32 slabs, fixed summation order) + its finish kernels.
 JPDSE_SWITCH(int, g_taps4_enabled, 1);      // 36: these layers on the fast kernel alone (A/B)
 
-struct Taps4View {            // a stride-1 4x4 conv as the kernels see it: forward, or the data gradient over dy
-  const bf16_t* X; const bf16_t* B; const float* bias; bf16_t* Y;
-  int N, IH, IW, Cin_s, OH, OW, py, px, Kout, Ks_out;
-  long long ktot;             // panel row stride (elements)
-  int tap_r, tap_s;           // panel offsets per filter-row / filter-column step
-  int act; float slope;
-  const bf16_t* addend; const bf16_t* mask;   // optional fused operands of a data gradient (Y's addressing)
-  const bf16_t* frame;                        // nine-tap program only: folded frame of X (reflect data gradient in one launch)
-  int reflect;                                // 3x3 view only: mirrored instead of zero padding
-};
-
 static bool taps4_shape_ok(int R, int S, int stride, int OH, int OW, int Cin_s, int Ks_out, long long x_elems, long long b_elems) {
   return g_fast_enabled && g_taps4_enabled && R == 4 && S == 4 && stride == 1 && OH >= 8 && OW >= 32 && Cin_s % 64 == 0 &&
          Cin_s >= 128 && Ks_out % 64 == 0 && Ks_out >= 64 && x_elems < (1LL << 31) && b_elems < (1LL << 31);
+}
+
+static bool taps4_shape_ok(const ConvView& v) {
+  return v.tap_r == v.S * v.Cin_s && taps4_shape_ok(v.R, v.S, v.stride, v.OH, v.OW, v.Cin_s, v.Ks_out, (long long)v.N * v.IH * v.IW * v.Cin_s,
+                                                    (long long)v.Ks_out * 16 * v.Cin_s);      // (a panel without K padding inside its rows)
 }
 
 static int taps4_fringe_splits(int N, int OH, int OW, int Ks_out, int k_tiles) {
@@ -922,13 +890,7 @@ template <int TN>
 static int launch_taps4_cfg(const TapsArgs& a, int total, hipStream_t s) {
   constexpr int PH = 11, PW = 35;
   constexpr int lds = 2 * ((PH * PW + 7) / 8) * 1024 + 3 * (2 * TN * 32) * 128;
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_taps_kernel<TN, 16, 0, 0, 0, 2, PH, PW>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return set_error(JPDSE_ELAUNCH, "gemm_taps(4x4): hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
-    configured = true;
-  }
+  if (int rc = opt_in_lds<&gemm_taps_kernel<TN, 16, 0, 0, 0, 2, PH, PW>>("gemm_taps(4x4)", lds)) return rc;
   if (int rc = check_tile_grid("gemm_taps(4x4)", a.N, a.OH, a.OW, 8, 32, a.Cs, (long long)a.N * a.IH * a.IW * a.Cs,
                                (long long)a.N * a.OH * a.OW * a.Ks)) return rc;
   if (total != a.N * (a.OH / 8) * (a.OW / 32) * ((a.Ks + 2 * TN * 32 - 1) / (2 * TN * 32)))
@@ -937,38 +899,36 @@ static int launch_taps4_cfg(const TapsArgs& a, int total, hipStream_t s) {
   return check_launch("gemm_taps_kernel(4x4)");
 }
 
-static int launch_taps4(const Taps4View& v, void* ws, hipStream_t s) {
-  const int OHc = v.OH / 8 * 8, OWc = v.OW / 32 * 32;
+// one-program TapsArgs of a stride-1 view: every filter tap of the R x S window over a staged patch of `patch_w` pixels per row
+static TapsArgs to_taps(const ConvView& v, int patch_w) {
   TapsArgs a = {};
   a.X = v.X;
   a.Y = v.Y;
   a.bias = v.bias;
-  a.N = v.N;
-  a.OH = OHc;
-  a.OW = OWc;
-  a.IH = v.IH;
-  a.IW = v.IW;
-  a.Cs = v.Cin_s;
-  a.py = v.py;
-  a.px = v.px;
-  a.Kout = v.Kout;
-  a.Ks = v.Ks_out;
-  a.b_rows = v.Ks_out;
-  a.out_sn = (long long)v.OH * v.OW * v.Ks_out;
-  a.out_sh = (long long)v.OW * v.Ks_out;
-  a.out_sw = v.Ks_out;
+  a.N = v.N; a.OH = v.OH; a.OW = v.OW; a.IH = v.IH; a.IW = v.IW; a.Cs = v.Cin_s;
+  a.py = v.py; a.px = v.px;
+  a.Kout = v.Kout; a.Ks = v.Ks_out; a.b_rows = v.Ks_out;
+  a.out_sn = v.out_sn; a.out_sh = v.out_sh; a.out_sw = v.out_sw;
   a.act = v.act;
   a.slope = v.slope;
   a.addend = v.addend;
   a.mask = v.mask;
   a.prog[0].B[0] = v.B;
   a.prog[0].ktot[0] = v.ktot;
-  a.prog[0].out_base[0] = 0;
-  for (int r = 0; r < 4; ++r)
-    for (int c = 0; c < 4; ++c) {
-      a.prog[0].tap_off[r * 4 + c] = r * 35 + c;
-      a.prog[0].tap_koff[r * 4 + c] = r * v.tap_r + c * v.tap_s;
+  a.prog[0].out_base[0] = v.out_base;
+  for (int r = 0; r < v.R; ++r)
+    for (int c = 0; c < v.S; ++c) {
+      a.prog[0].tap_off[r * v.S + c] = r * patch_w + c;
+      a.prog[0].tap_koff[r * v.S + c] = r * v.tap_r + c * v.tap_s;
     }
+  return a;
+}
+
+static int launch_taps4(const ConvView& v, void* ws, hipStream_t s) {
+  const int OHc = v.OH / 8 * 8, OWc = v.OW / 32 * 32;
+  TapsArgs a = to_taps(v, 35);
+  a.OH = OHc;                    // the kernel covers the core, the fast kernel the fringe
+  a.OW = OWc;
   const int bn = v.Ks_out % 128 == 0 ? 128 : 64;
   a.nblk0 = v.N * (OHc / 8) * (OWc / 32) * ((v.Ks_out + bn - 1) / bn);
   if (int rc = bn == 128 ? launch_taps4_cfg<2>(a, a.nblk0, s) : launch_taps4_cfg<1>(a, a.nblk0, s)) return rc;
@@ -982,39 +942,19 @@ static int launch_taps4(const Taps4View& v, void* ws, hipStream_t s) {
   for (int q = 0; q < 2; ++q) {
     const int oh0 = rect[q][0], ow0 = rect[q][1], rows = rect[q][2], cols = rect[q][3];
     if (rows <= 0 || cols <= 0) continue;
-    FastArgs g = {};
-    g.X = v.X;
-    g.B = v.B;
-    g.bias = v.bias;
-    g.Y = v.Y;
+    FastArgs g = to_fast(v);      // (addend / mask are applied by splitk_finish_kernel)
     g.M = v.N * rows * cols;
     g.OH = rows;
     g.OW = cols;
-    g.IH = v.IH;
-    g.IW = v.IW;
-    g.Cs = v.Cin_s;
-    g.R = g.S = 4;
-    g.sy = g.sx = 1;
     g.py = v.py - oh0;
     g.px = v.px - ow0;
-    g.reflect = 0;
-    g.Kout = v.Kout;
-    g.Ks = v.Ks_out;
-    g.b_rows = v.Ks_out;
-    g.out_sn = a.out_sn;
-    g.out_sh = a.out_sh;
-    g.out_sw = a.out_sw;
-    g.out_base = ((long long)oh0 * v.OW + ow0) * v.Ks_out;
-    g.act = v.act;
-    g.slope = v.slope;
+    g.out_base = v.out_base + oh0 * v.out_sh + ow0 * v.out_sw;
     g.splits = sp;
     g.no_finish = 1;
     g.partial = slab;
     g.b_stride = v.ktot;
     g.b_tap_r = v.tap_r;
     g.b_tap_s = v.tap_s;
-    g.addend = v.addend;        // applied by splitk_finish_kernel
-    g.mask = v.mask;
     slab += (size_t)sp * g.M * v.Ks_out;
     fb.p[fb.n++] = g;
   }
@@ -1036,6 +976,11 @@ static bool taps9_shape_ok(int R, int S, int stride, int OH, int OW, int Cin_s, 
          Cin_s % 64 == 0 && Cin_s >= 128 && Ks_out % 64 == 0 && x_elems < (1LL << 31) && b_elems < (1LL << 31);
 }
 
+static bool taps9_shape_ok(const ConvView& v) {
+  return v.tap_r == v.S * v.Cin_s && taps9_shape_ok(v.R, v.S, v.stride, v.OH, v.OW, v.Cin_s, v.Ks_out, (long long)v.N * v.IH * v.IW * v.Cin_s,
+                                                    (long long)v.Ks_out * 9 * v.Cin_s);
+}
+
 static int taps9_splits(int N, int OH, int OW, int Cin_s, int Ks_out) {
   const int sp = splitk_for(N * OH * OW, Ks_out, 9 * Cin_s / 64);      // the split-K fast path's choice: its workspace region is reused
   const int cc = Cin_s / 64;
@@ -1046,13 +991,7 @@ template <int TN, bool VIRT = false>
 static int launch_taps9_cfg(const TapsArgs& a, int total, hipStream_t s) {
   constexpr int PH = 10, PW = 34;
   constexpr int lds = 2 * ((PH * PW + 7) / 8) * 1024 + 3 * (2 * TN * 32) * 128;
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_taps_kernel<TN, 9, 0, 0, 0, 2, PH, PW, VIRT>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return set_error(JPDSE_ELAUNCH, "gemm_taps(3x3): hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
-    configured = true;
-  }
+  if (int rc = opt_in_lds<&gemm_taps_kernel<TN, 9, 0, 0, 0, 2, PH, PW, VIRT>>("gemm_taps(3x3)", lds)) return rc;
   if (int rc = check_tile_grid("gemm_taps(3x3)", a.N, a.OH, a.OW, 8, 32, a.Cs, (long long)a.N * a.IH * a.IW * a.Cs,
                                (long long)a.N * a.OH * a.OW * a.Ks)) return rc;
   const int sp = a.splits > 1 ? a.splits : 1;
@@ -1065,39 +1004,10 @@ static int launch_taps9_cfg(const TapsArgs& a, int total, hipStream_t s) {
 }
 
 // `slabs`: fp32 workspace of >= splits * N OH OW * Ks_out floats (the plan's split-K region)
-static int launch_taps9(const Taps4View& v, float* slabs, hipStream_t s) {
-  TapsArgs a = {};
-  a.X = v.X;
-  a.Y = v.Y;
-  a.bias = v.bias;
-  a.N = v.N;
-  a.OH = v.OH;
-  a.OW = v.OW;
-  a.IH = v.IH;
-  a.IW = v.IW;
-  a.Cs = v.Cin_s;
-  a.py = v.py;
-  a.px = v.px;
+static int launch_taps9(const ConvView& v, float* slabs, hipStream_t s) {
+  TapsArgs a = to_taps(v, 34);
   a.reflect = v.reflect;
-  a.Kout = v.Kout;
-  a.Ks = v.Ks_out;
-  a.b_rows = v.Ks_out;
-  a.out_sn = (long long)v.OH * v.OW * v.Ks_out;
-  a.out_sh = (long long)v.OW * v.Ks_out;
-  a.out_sw = v.Ks_out;
-  a.act = v.act;
-  a.slope = v.slope;
-  a.addend = v.addend;
-  a.mask = v.mask;
   a.V = v.frame;
-  a.prog[0].B[0] = v.B;
-  a.prog[0].ktot[0] = v.ktot;
-  a.prog[0].out_base[0] = 0;
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) {
-      a.prog[0].tap_off[r * 3 + c] = r * 34 + c;
-      a.prog[0].tap_koff[r * 3 + c] = r * v.tap_r + c * v.tap_s;
-    }
   const int bn = v.Ks_out % 128 == 0 ? 128 : 64;
   const int tiles = v.N * (v.OH / 8) * (v.OW / 32) * ((v.Ks_out + bn - 1) / bn);
   a.splits = taps9_splits(v.N, v.OH, v.OW, v.Cin_s, v.Ks_out);
@@ -1116,10 +1026,10 @@ static int launch_taps9(const Taps4View& v, float* slabs, hipStream_t s) {
   f.OW = v.OW;
   f.Kout = v.Kout;
   f.Ks = v.Ks_out;
-  f.out_sn = a.out_sn;
-  f.out_sh = a.out_sh;
-  f.out_sw = a.out_sw;
-  f.out_base = 0;
+  f.out_sn = v.out_sn;
+  f.out_sh = v.out_sh;
+  f.out_sw = v.out_sw;
+  f.out_base = v.out_base;
   f.act = v.act;
   f.slope = v.slope;
   f.splits = a.splits;
@@ -1198,13 +1108,7 @@ static bool thin_fwd_geom(const jpdse_conv_desc* d, const ConvPlan& p, ThinFwdGe
 
 template <int TN, int TH, int ST, int TW>
 static int launch_thin_fwd(const ThinFwdArgs& a, int lds, hipStream_t s) {
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&thin_fwd_kernel<TN, TH, ST, TW>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return set_error(JPDSE_ELAUNCH, "thin_fwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    configured = true;
-  }
+  if (int rc = opt_in_lds<&thin_fwd_kernel<TN, TH, ST, TW>>("thin_fwd", 160 * 1024)) return rc;
   hipLaunchKernelGGL((thin_fwd_kernel<TN, TH, ST, TW>), dim3(a.N * a.tiles_h * a.tiles_w), dim3(512), lds, s, a);
   return check_launch("thin_fwd_kernel");
 }
@@ -1219,13 +1123,7 @@ static bool head_fwd_ok(const jpdse_conv_desc* d, const ConvPlan& p) {
 template <int CIN, int NT = 5, int FR = 7, int FS = 7>
 static int launch_head_fwd(const HeadFwdArgs& a, hipStream_t s) {
   constexpr int lds = NT * 32 * CIN * 2 + 3 * kHeadMR * CIN * 2 + NT * 32 * kHeadZP * 4 + kHeadTH * 64 * 4 * 4;
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&head_fwd_kernel<CIN, NT, FR, FS>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return set_error(JPDSE_ELAUNCH, "head_fwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    configured = true;
-  }
+  if (int rc = opt_in_lds<&head_fwd_kernel<CIN, NT, FR, FS>>("head_fwd", lds)) return rc;
   hipLaunchKernelGGL((head_fwd_kernel<CIN, NT, FR, FS>), dim3(a.N * a.tiles_h * a.tiles_w), dim3(64 * NT), lds, s, a);
   return check_launch("head_fwd_kernel");
 }
