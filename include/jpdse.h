@@ -35,7 +35,8 @@ extern "C" {
 #define JPDSE_ABI_VERSION 2   /* 2 (round 4): + jpdse_conv_dgrad_nsum_slots / _fused_nsums, jpdse_inorm_bwd_from_sums; round 3 had already added
                                 * jpdse_loss_finalize, jpdse_conv_fwd_pool, jpdse_conv_dgrad_fused_lrelu, jpdse_input_builder, jpdse_copy, jpdse_prof_hbm_* under version 1;
                                 * the learned codec (jpdse_binarize_fwd, jpdse_code_stats[_workspace_size], jpdse_code_export) was added to
-                                * version 2 later: purely additive, nothing existing changed */
+                                * version 2 later, and so were the evaluation metrics (jpdse_eval_metrics[_workspace_size]): purely additive,
+                                * nothing existing changed */
 
 enum { JPDSE_F32 = 0, JPDSE_BF16 = 1 };
 enum { JPDSE_PAD_ZERO = 0, JPDSE_PAD_REFLECT = 1 };
@@ -379,6 +380,24 @@ int jpdse_code_stats(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, 
  * order; packed != 0: out = uint8 [N][ceil(C*H*W / 8)], bit (b > 0) of element 8k+j in bit 7-j of byte k (np.packbits order). */
 int jpdse_code_export(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, const void* b, int32_t packed, void* out,
                       void* stream);
+
+/* ---- evaluation metrics: L1, MSE and MS-SSIM of a reconstruction in one pass (test.py:114-125) --------------------------
+ * fake (fp32 or bf16) and real (fp32): NHWC [N][H][W][CPAD(3)] normalised images; both are quantised with q() of
+ * jpdse_quant_loss (the same device function) and compared on the 0..255 scale.  out: DEVICE array of doubles
+ * [N][4 + 2*5]; per image
+ *   out[0] = sum |q(fake) - q(real)|, out[1] = sum (q(fake) - q(real))^2 over the 3*H*W elements (integers, exact),
+ *   out[2] = 3*H*W, out[3] = 0 (reserved),
+ *   out[4..8] = cs_1..cs_5, out[9..13] = ssim_1..ssim_5: the per-scale means of the MS-SSIM maps (Wang, Simoncelli, Bovik
+ *   2003; DESIGN.md 4.5: 11x11 Gaussian window of sigma 1.5 applied "valid" per channel, C1 = (0.01*255)^2,
+ *   C2 = (0.03*255)^2, scales linked by a 2x2 mean).
+ * The caller forms ms_ssim = prod_{j<5} cs_j^w_j * ssim_5^w_5 and PSNR in float64 from one read-back.  C must be 3 and
+ * min(H, W) >= 176 (the fifth scale still holds one window), else JPDSE_EINVAL before any launch.  No floating-point
+ * atomics: partials are combined in a fixed order, two calls give bit-identical `out`.  ws:
+ * jpdse_eval_metrics_workspace_size() bytes (0 for an unsupported shape). */
+size_t jpdse_eval_metrics_workspace_size(int32_t N, int32_t H, int32_t W, int32_t C);
+int jpdse_eval_metrics(int32_t dtype_fake, int32_t dtype_real, int32_t N, int32_t H, int32_t W, int32_t C, const void* fake,
+                       const void* real, const double* mean, const double* std, double* out, void* ws, size_t ws_bytes,
+                       void* stream);
 
 /* ---- optimizer ---------------------------------------------------------------------- */
 /* torch.optim.Adam (model.py:275,279) over a table of tensors, one launch.  `table` is a

@@ -169,6 +169,15 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// uint8 quantiser of the evaluation paths (elementwise.hip jpdse_quant_loss, metrics.hip jpdse_eval_metrics):
+// q(x) = uint8(clip((double(x) * std[c] + mean[c]) * 255.0, 0, 255)), the IEEE double operations numpy performs, unfused
+struct QuantParams { double mean[8]; double std[8]; };
+__device__ __forceinline__ int quant_u8(float x, double sd, double mu) {
+  double v = __dmul_rn(__dadd_rn(__dmul_rn((double)x, sd), mu), 255.0);
+  v = v < 0.0 ? 0.0 : (v > 255.0 ? 255.0 : v);
+  return (int)v;           // truncation, as ndarray.astype(np.uint8) on a value in [0, 255]
+}
+
 // grid-stride launch geometry for HBM-bound kernels: <= 256 CUs x 8 blocks
 static inline int ew_blocks(int64_t work_items, int threads = 256) {
   int64_t b = (work_items + threads - 1) / threads;

@@ -664,13 +664,7 @@ __global__ void cast_bf16_f32_kernel(const bf16_t* __restrict__ src, float* __re
 // q(x) = uint8( clip( (double(x) * std[c] + mean[c]) * 255.0, 0, 255 ) )  -- numpy evaluates this in float64 (the
 // std / mean lists become float64 arrays) and astype(uint8) truncates; the same IEEE double operations, unfused, are
 // done here, so the quantised images are bit-identical.  The |qa - qb| / (qa - qb)^2 sums are integers, kept exactly
-// in double.
-struct QuantParams { double mean[8]; double std[8]; };
-__device__ __forceinline__ int quant_u8(float x, double sd, double mu) {
-  double v = __dmul_rn(__dadd_rn(__dmul_rn((double)x, sd), mu), 255.0);
-  v = v < 0.0 ? 0.0 : (v > 255.0 ? 255.0 : v);
-  return (int)v;           // truncation, as ndarray.astype(np.uint8) on a value in [0, 255]
-}
+// in double.  QuantParams / quant_u8 live in common.h: metrics.hip quantises with the same function.
 template <typename TA, typename TB, int MODE>
 __global__ __launch_bounds__(256) void quant_loss_partial_kernel(const TA* __restrict__ a, const TB* __restrict__ b,
                                                                 int C, int cs, long long npix, QuantParams qp,

@@ -1,0 +1,377 @@
+// Test-time distortion metrics of a reconstruction against its original, in one device pass (reference test.py:114-125:
+// L1, MSE and MS-SSIM of the de-normalised, clipped, uint8-truncated images).  Entry points: include/jpdse.h,
+// "evaluation metrics".  MS-SSIM is the definition of Wang, Simoncelli and Bovik 2003 as written out in DESIGN.md 4.5:
+// 11x11 Gaussian window (sigma 1.5, "valid"), five scales linked by a 2x2 mean, per channel.
+//
+// Kernels, in launch order:
+//   metrics_quant_kernel   both images -> quantised planar fp32 planes [N][3][H][W] (scale 1) + exact integer |d|, d^2 sums
+//   msssim_scale_kernel    one per scale: LDS tile + halo of both planes, separable 11-tap filter of x, y, x^2, y^2, xy,
+//                          cs / ssim per position, one (cs, ssim) partial pair per block
+//   msssim_down_kernel     2x2 mean -> next scale's planes (exact in fp32: scale j values carry 8 + 2(j-1) bits)
+//   metrics_final_kernel   per image: partials -> out[n][14], fixed order, no atomics: two runs are bit-identical
+//
+// Cancellation: every tile is filtered about its own pivot (the value of its first pixel, per image of the pair): the local
+// statistics are shift invariant, E[(x-p)^2] - (mu-p)^2 is formed from values of the size of the tile's contrast instead
+// of 0..255, and a constant tile gives variance exactly 0.  The filter runs in fp32; the per-position cs / ssim and every
+// sum over positions are fp64.
+#include "common.h"
+
+namespace jpdse {
+
+constexpr int kMsScales = 5;
+constexpr int kWin = 11;                 // window taps
+constexpr int kHalo = kWin - 1;
+constexpr int kTW = 64, kTH = 16;        // outputs per block: one wave per 64-wide row, four rows per wave
+constexpr int kSW = kTW + kHalo;         // staged columns (74)
+constexpr int kSH = kTH + kHalo;         // staged rows (26)
+constexpr int kQuantBlocksMax = 1024;    // per image
+constexpr int kOutPerImage = 4 + 2 * kMsScales;
+
+struct GaussWin { float w[kWin]; };
+
+// fake: NHWC [N][H][W][cs] fp32 or bf16, real: NHWC fp32.  One thread per pixel; planes x (fake) / y (real): [N][3][H*W].
+template <typename TF>
+__global__ __launch_bounds__(256) void metrics_quant_kernel(const TF* __restrict__ fake, const float* __restrict__ real,
+                                                           int cs, long long HW, QuantParams qp, float* __restrict__ px,
+                                                           float* __restrict__ py,
+                                                           unsigned long long* __restrict__ partial) {
+  __shared__ unsigned long long red[2][4];
+  const int n = blockIdx.y;
+  const TF* f = fake + (long long)n * HW * cs;
+  const float* r = real + (long long)n * HW * cs;
+  float* ox = px + (long long)n * 3 * HW;
+  float* oy = py + (long long)n * 3 * HW;
+  unsigned long long l1 = 0, se = 0;
+  for (long long p = blockIdx.x * 256LL + threadIdx.x; p < HW; p += (long long)gridDim.x * 256) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const int qa = quant_u8(ElemOps<TF>::ld(f + p * cs + c), qp.std[c], qp.mean[c]);
+      const int qb = quant_u8(r[p * cs + c], qp.std[c], qp.mean[c]);
+      const int d = qa - qb;
+      l1 += (unsigned)(d < 0 ? -d : d);
+      se += (unsigned)(d * d);
+      ox[c * HW + p] = (float)qa;
+      oy[c * HW + p] = (float)qb;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    l1 += __shfl_xor(l1, off, 64);
+    se += __shfl_xor(se, off, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    red[0][threadIdx.x >> 6] = l1;
+    red[1][threadIdx.x >> 6] = se;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long* o = partial + ((long long)n * gridDim.x + blockIdx.x) * 2;
+    o[0] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+    o[1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+  }
+}
+
+// x, y: planes [NC][Hs][Ws]; grid (tiles_x, tiles_y, NC); partial: [NC][tiles_y][tiles_x][2] doubles (sum cs, sum ssim over
+// the block's valid positions).  LDS: 2 staged tiles + 5 horizontally filtered planes = 48.7 KB, three blocks per CU.  Every
+// LDS access of a wave is 64 consecutive dwords of one row (plus a tap offset): conflict free on the 64 banks.
+__global__ __launch_bounds__(256) void msssim_scale_kernel(const float* __restrict__ x, const float* __restrict__ y, int Hs,
+                                                          int Ws, GaussWin g, double c1, double c2,
+                                                          double* __restrict__ partial) {
+  __shared__ float sx[kSH][kSW];
+  __shared__ float sy[kSH][kSW];
+  __shared__ float hq[5][kSH][kTW];
+  __shared__ double red[2][4];
+  const int Ho = Hs - kHalo, Wo = Ws - kHalo;
+  const int x0 = blockIdx.x * kTW, y0 = blockIdx.y * kTH;
+  const long long plane = (long long)blockIdx.z * Hs * Ws;
+  const float* xp = x + plane;
+  const float* yp = y + plane;
+  // pivots: the tile's first pixel (always inside the plane: x0 < Wo, y0 < Ho)
+  const float pvx = xp[(long long)y0 * Ws + x0];
+  const float pvy = yp[(long long)y0 * Ws + x0];
+  for (int i = threadIdx.x; i < kSH * kSW; i += 256) {
+    const int r = i / kSW, c = i - r * kSW;
+    const int gy = y0 + r, gx = x0 + c;
+    float vx = 0.f, vy = 0.f;            // outside the plane: only feeds positions that are masked out below
+    if (gy < Hs && gx < Ws) {
+      vx = xp[(long long)gy * Ws + gx] - pvx;
+      vy = yp[(long long)gy * Ws + gx] - pvy;
+    }
+    sx[r][c] = vx;
+    sy[r][c] = vy;
+  }
+  __syncthreads();
+  // horizontal pass: 26 rows x 64 columns, one row per wave and iteration
+  for (int i = threadIdx.x; i < kSH * kTW; i += 256) {
+    const int r = i >> 6, c = i & 63;
+    float ax = 0.f, ay = 0.f, axx = 0.f, ayy = 0.f, axy = 0.f;
+#pragma unroll
+    for (int k = 0; k < kWin; ++k) {
+      const float a = sx[r][c + k], b = sy[r][c + k], w = g.w[k];
+      const float wa = w * a, wb = w * b;
+      ax += wa;
+      ay += wb;
+      axx = fmaf(wa, a, axx);
+      ayy = fmaf(wb, b, ayy);
+      axy = fmaf(wa, b, axy);
+    }
+    hq[0][r][c] = ax;
+    hq[1][r][c] = ay;
+    hq[2][r][c] = axx;
+    hq[3][r][c] = ayy;
+    hq[4][r][c] = axy;
+  }
+  __syncthreads();
+  // vertical pass: thread = (column, group of 4 output rows); 14 filtered rows feed its 4 outputs per quantity
+  const int c = threadIdx.x & 63, r0 = (threadIdx.x >> 6) * 4;
+  float acc[5][4];
+#pragma unroll
+  for (int q = 0; q < 5; ++q) {
+    float v[4 + kHalo];
+#pragma unroll
+    for (int j = 0; j < 4 + kHalo; ++j) v[j] = hq[q][r0 + j][c];
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+      float a = 0.f;
+#pragma unroll
+      for (int k = 0; k < kWin; ++k) a = fmaf(g.w[k], v[o + k], a);
+      acc[q][o] = a;
+    }
+  }
+  double scs = 0.0, sss = 0.0;
+#pragma unroll
+  for (int o = 0; o < 4; ++o) {
+    if (x0 + c < Wo && y0 + r0 + o < Ho) {
+      const double mx = acc[0][o], my = acc[1][o];
+      const double vxx = (double)acc[2][o] - mx * mx, vyy = (double)acc[3][o] - my * my;
+      const double vxy = (double)acc[4][o] - mx * my;
+      const double mux = (double)pvx + mx, muy = (double)pvy + my;
+      const double cs = (2.0 * vxy + c2) / (vxx + vyy + c2);
+      // unfused, so that identical images give num == den bit for bit (2 mu^2 is formed the same way on both sides)
+      const double pxy = __dmul_rn(mux, muy);
+      const double lum = __dadd_rn(__dadd_rn(pxy, pxy), c1) /
+                         __dadd_rn(__dadd_rn(__dmul_rn(mux, mux), __dmul_rn(muy, muy)), c1);
+      scs += cs;
+      sss += cs * lum;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    scs += __shfl_xor(scs, off, 64);
+    sss += __shfl_xor(sss, off, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    red[0][threadIdx.x >> 6] = scs;
+    red[1][threadIdx.x >> 6] = sss;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double* o = partial + (((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 2;
+    o[0] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+    o[1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+  }
+}
+
+// 2x2 mean, stride 2, odd last row / column dropped; one thread per output, both planes
+__global__ __launch_bounds__(256) void msssim_down_kernel(const float* __restrict__ x, const float* __restrict__ y, int Hs,
+                                                         int Ws, float* __restrict__ ox, float* __restrict__ oy,
+                                                         long long total) {
+  const int Hd = Hs >> 1, Wd = Ws >> 1;
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int cx = (int)(i % Wd);
+    const long long t = i / Wd;
+    const int cy = (int)(t % Hd);
+    const long long nc = t / Hd;
+    const long long s = (nc * Hs + 2 * cy) * Ws + 2 * cx;
+    ox[i] = ((x[s] + x[s + 1]) + (x[s + Ws] + x[s + Ws + 1])) * 0.25f;
+    oy[i] = ((y[s] + y[s + 1]) + (y[s + Ws] + y[s + Ws + 1])) * 0.25f;
+  }
+}
+
+struct FinalArgs {
+  long long scale_off[kMsScales];   // first partial pair of the scale (in pairs), image 0
+  int scale_cnt[kMsScales];         // pairs per image (3 channels x tiles)
+  double pos[kMsScales];            // 3 * Ho * Wo: positions behind a per-scale mean
+  double count;                     // 3 * H * W: the elements behind the two integer sums
+  int qblocks;
+};
+
+// one block per image: every sum is thread-strided, then wave-reduced, then the four waves in order
+__global__ __launch_bounds__(256) void metrics_final_kernel(const unsigned long long* __restrict__ qpartial,
+                                                           const double* __restrict__ spartial, FinalArgs fa,
+                                                           double* __restrict__ out) {
+  __shared__ double red[2][4];
+  const int n = blockIdx.x;
+  for (int item = 0; item <= kMsScales; ++item) {
+    double a = 0.0, b = 0.0;
+    if (item == 0) {
+      unsigned long long l1 = 0, se = 0;
+      for (int i = threadIdx.x; i < fa.qblocks; i += 256) {
+        l1 += qpartial[((long long)n * fa.qblocks + i) * 2];
+        se += qpartial[((long long)n * fa.qblocks + i) * 2 + 1];
+      }
+      a = (double)l1;          // integers below 2^53: every double sum that follows is exact
+      b = (double)se;
+    } else {
+      const int j = item - 1;
+      const double* p = spartial + (fa.scale_off[j] + (long long)n * fa.scale_cnt[j]) * 2;
+      for (int i = threadIdx.x; i < fa.scale_cnt[j]; i += 256) {
+        a += p[2 * i];
+        b += p[2 * i + 1];
+      }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      a += __shfl_xor(a, off, 64);
+      b += __shfl_xor(b, off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+      red[0][threadIdx.x >> 6] = a;
+      red[1][threadIdx.x >> 6] = b;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const double sa = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+      const double sb = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+      double* o = out + (long long)n * kOutPerImage;
+      if (item == 0) {
+        o[0] = sa;
+        o[1] = sb;
+        o[2] = fa.count;
+        o[3] = 0.0;
+      } else {
+        o[4 + item - 1] = sa / fa.pos[item - 1];
+        o[4 + kMsScales + item - 1] = sb / fa.pos[item - 1];
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// ---- host side: geometry and workspace layout -------------------------------------------------------------------------------
+struct MetricsPlan {
+  int Hs[kMsScales], Ws[kMsScales], tx[kMsScales], ty[kMsScales];
+  size_t plane_off[kMsScales];     // floats, from the start of the x planes (the y planes have the same layout)
+  size_t plane_floats;             // all scales, one image of the pair
+  int qblocks;
+  size_t off_y, off_qpartial, off_spartial, bytes;
+  FinalArgs fa;
+};
+
+static int metrics_quant_blocks(long long HW) {
+  long long b = (HW + 1023) / 1024;      // >= 4 pixels per thread
+  if (b < 1) b = 1;
+  if (b > kQuantBlocksMax) b = kQuantBlocksMax;
+  return (int)b;
+}
+
+static void metrics_plan(int N, int H, int W, MetricsPlan& p) {
+  size_t off = 0;
+  long long pairs = 0;
+  for (int j = 0; j < kMsScales; ++j) {
+    p.Hs[j] = H >> j;
+    p.Ws[j] = W >> j;
+    p.tx[j] = (p.Ws[j] - kHalo + kTW - 1) / kTW;
+    p.ty[j] = (p.Hs[j] - kHalo + kTH - 1) / kTH;
+    p.plane_off[j] = off;
+    off += align_up((size_t)N * 3 * p.Hs[j] * p.Ws[j], 64);
+    p.fa.scale_off[j] = pairs;
+    p.fa.scale_cnt[j] = 3 * p.tx[j] * p.ty[j];
+    p.fa.pos[j] = 3.0 * (double)(p.Hs[j] - kHalo) * (double)(p.Ws[j] - kHalo);
+    pairs += (long long)N * p.fa.scale_cnt[j];
+  }
+  p.plane_floats = off;
+  p.qblocks = metrics_quant_blocks((long long)H * W);
+  p.fa.qblocks = p.qblocks;
+  p.fa.count = 3.0 * (double)H * (double)W;
+  p.off_y = align_up(p.plane_floats * sizeof(float), 256);
+  p.off_qpartial = 2 * p.off_y;
+  p.off_spartial = p.off_qpartial + align_up((size_t)N * p.qblocks * 2 * sizeof(unsigned long long), 256);
+  p.bytes = p.off_spartial + align_up((size_t)pairs * 2 * sizeof(double), 256);
+}
+
+static const char* metrics_shape_error(int N, int H, int W, int C) {
+  if (N <= 0 || H <= 0 || W <= 0) return "eval_metrics: bad shape";
+  if (C != 3) return "eval_metrics: 3 channels only";
+  if (H < 176 || W < 176) return "eval_metrics: the shorter side must be at least 176 (five MS-SSIM scales of an 11x11 window)";
+  if ((long long)N * 3 > 65535) return "eval_metrics: more than 21845 images per call";
+  if ((long long)H * W > (1LL << 28)) return "eval_metrics: image beyond 2^28 pixels";
+  // grid y / x of msssim_scale_kernel at scale 1: ceil((H - 10) / 16), ceil((W - 10) / 64) tiles
+  if ((H - kHalo + kTH - 1) / kTH > 65535 || (W - kHalo + kTW - 1) / kTW > 65535) return "eval_metrics: image side beyond the tile grid";
+  return nullptr;
+}
+
+}  // namespace jpdse
+
+using namespace jpdse;
+
+extern "C" {
+
+size_t jpdse_eval_metrics_workspace_size(int32_t N, int32_t H, int32_t W, int32_t C) {
+  if (metrics_shape_error(N, H, W, C)) return 0;
+  MetricsPlan p;
+  metrics_plan(N, H, W, p);
+  return p.bytes;
+}
+
+int jpdse_eval_metrics(int32_t dtype_fake, int32_t dtype_real, int32_t N, int32_t H, int32_t W, int32_t C, const void* fake,
+                       const void* real, const double* mean, const double* std, double* out, void* ws, size_t ws_bytes,
+                       void* stream) {
+  JPDSE_REQUIRE(dtype_fake == JPDSE_F32 || dtype_fake == JPDSE_BF16, "eval_metrics: fake must be fp32 or bf16");
+  JPDSE_REQUIRE(dtype_real == JPDSE_F32, "eval_metrics: real must be fp32");
+  JPDSE_REQUIRE(fake && real && mean && std && out, "eval_metrics: null argument");
+  if (const char* msg = metrics_shape_error(N, H, W, C)) return set_error(JPDSE_EINVAL, "%s (N %d, H %d, W %d, C %d)", msg, N, H, W, C);
+  MetricsPlan p;
+  metrics_plan(N, H, W, p);
+  if (ws == nullptr || ws_bytes < p.bytes) return set_error(JPDSE_EWORKSPACE, "eval_metrics: workspace too small");
+  JPDSE_REQUIRE(((uintptr_t)ws & 15) == 0, "eval_metrics: workspace not 16-byte aligned");
+  hipStream_t s = as_stream(stream);
+  char* base = reinterpret_cast<char*>(ws);
+  float* px = reinterpret_cast<float*>(base);
+  float* py = reinterpret_cast<float*>(base + p.off_y);
+  unsigned long long* qpartial = reinterpret_cast<unsigned long long*>(base + p.off_qpartial);
+  double* spartial = reinterpret_cast<double*>(base + p.off_spartial);
+
+  QuantParams qp = {};
+  for (int c = 0; c < 3; ++c) { qp.mean[c] = mean[c]; qp.std[c] = std[c]; }
+  GaussWin g;
+  {
+    double w[kWin], sum = 0.0;
+    for (int k = 0; k < kWin; ++k) {
+      const double d = k - (kWin - 1) / 2;
+      w[k] = exp(-d * d / (2.0 * 1.5 * 1.5));
+      sum += w[k];
+    }
+    for (int k = 0; k < kWin; ++k) g.w[k] = (float)(w[k] / sum);
+  }
+  const double c1 = (0.01 * 255.0) * (0.01 * 255.0), c2 = (0.03 * 255.0) * (0.03 * 255.0);
+  const long long HW = (long long)H * W;
+  const int cs = cpad(C);
+
+  if (dtype_fake == JPDSE_BF16)
+    hipLaunchKernelGGL((metrics_quant_kernel<bf16_t>), dim3(p.qblocks, N), dim3(256), 0, s,
+                       reinterpret_cast<const bf16_t*>(fake), reinterpret_cast<const float*>(real), cs, HW, qp, px, py,
+                       qpartial);
+  else
+    hipLaunchKernelGGL((metrics_quant_kernel<float>), dim3(p.qblocks, N), dim3(256), 0, s,
+                       reinterpret_cast<const float*>(fake), reinterpret_cast<const float*>(real), cs, HW, qp, px, py,
+                       qpartial);
+  if (int rc = check_launch("eval_metrics(quantise)")) return rc;
+  for (int j = 0; j < kMsScales; ++j) {
+    const float* xj = px + p.plane_off[j];
+    const float* yj = py + p.plane_off[j];
+    hipLaunchKernelGGL(msssim_scale_kernel, dim3(p.tx[j], p.ty[j], N * 3), dim3(256), 0, s, xj, yj, p.Hs[j], p.Ws[j], g, c1,
+                       c2, spartial + p.fa.scale_off[j] * 2);
+    if (int rc = check_launch("eval_metrics(scale)")) return rc;
+    if (j + 1 < kMsScales) {
+      const long long total = (long long)N * 3 * p.Hs[j + 1] * p.Ws[j + 1];
+      hipLaunchKernelGGL(msssim_down_kernel, dim3(ew_blocks(total)), dim3(256), 0, s, xj, yj, p.Hs[j], p.Ws[j],
+                         px + p.plane_off[j + 1], py + p.plane_off[j + 1], total);
+      if (int rc = check_launch("eval_metrics(downsample)")) return rc;
+    }
+  }
+  hipLaunchKernelGGL(metrics_final_kernel, dim3(N), dim3(256), 0, s, qpartial, spartial, p.fa, out);
+  return check_launch("eval_metrics(final)");
+}
+
+}  // extern "C"

@@ -242,6 +242,8 @@ class Pix2PixHDModel(BaseModel):
       return self.get_code(x_dict)
     if mode == 'get_eval_rate':
       return self.get_eval_rate(x_dict)
+    if mode == 'get_eval_metrics':
+      return self.get_eval_metrics(x_dict)
     raise ValueError('Invalid forward mode: {}'.format(mode))
 
   def create_optimizers(self, opt):
@@ -397,6 +399,16 @@ class Pix2PixHDModel(BaseModel):
       ops.quant_loss(fake, real32, self.opt.normalize_mean, self.opt.normalize_std,
                      self.opt.distortion_loss_fn == 'mse', slot)
       return slot[0]
+
+  def get_eval_metrics(self, x_dict):
+    """Every distortion figure of the reference's test loop (test.py:114-125) from ONE generator forward: dict(l1, mse,
+    psnr, ms_ssim, per_image) on the 0..255 scale of the quantised images (ops.eval_metrics; MS-SSIM: DESIGN.md 4.5).
+    l1 / mse are the numbers get_eval_loss returns for --distortion_loss_fn l1 / mse."""
+    with torch.no_grad():
+      pre = self.preprocess(x_dict)
+      fake, _ = self.netG.fwd(self._g_input_eval(pre))
+      real32 = ops.nchw_to_nhwc(pre['image_nchw'], F32)
+      return ops.eval_metrics(fake, real32, self.opt.normalize_mean, self.opt.normalize_std)
 
   # ---- training -------------------------------------------------------------------------------
   def _forward_losses(self, x_dict, grad_w=None):

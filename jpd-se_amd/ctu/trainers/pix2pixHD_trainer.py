@@ -135,6 +135,12 @@ class Pix2PixHDTrainer(BaseTrainer):
     self.eval()
     return self.model(x_dict, self.opt, mode='get_eval_rate')
 
+  def get_eval_metrics(self, x_dict):
+    """L1, MSE, PSNR and MS-SSIM of the reconstruction (test.py:114-125) from one generator forward: dict of Python floats
+    (batch means) plus `per_image`, four float64 CPU tensors [B]."""
+    self.eval()
+    return self.model(x_dict, self.opt, mode='get_eval_metrics')
+
   def get_img(self, x_dict):
     self.eval()
     return self.model(x_dict, self.opt, mode='get_img')

@@ -542,3 +542,50 @@ def code_export(b, packed=False):
   check(lib().jpdse_code_export(b.dtype, b.N, b.H, b.W, b.C, _p(b.t), 1 if packed else 0, _p(out), _stream()),
         'code_export')
   return out
+
+
+# ---- evaluation metrics (metrics.hip) ------------------------------------------------------------
+MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+
+
+def eval_metrics_finish(raw):
+  """The host half of eval_metrics: `raw` is the float64 CPU tensor [N, 14] jpdse_eval_metrics wrote (per image: |d| sum,
+  d^2 sum, element count, 0, cs_1..5, ssim_1..5).  A few float64 operations per image:
+    l1_i, mse_i = sums / count;  psnr_i = 10 log10(255^2 / mse_i) (inf when mse_i is 0);
+    ms_ssim_i = prod_{j<5} cs_j^w_j * ssim_5^w_5, 0 when one of those five means is <= 0 (never nan).
+  Returns dict(l1, mse, psnr, ms_ssim: Python floats, batch means of the per-image values; per_image: the four float64
+  tensors [N]; raw: the input, part of the contract -- the per-scale means are only there).  l1 and mse are rounded exactly as jpdse_quant_loss rounds them (float32(total * (1 / count))), so
+  they are bit-equal to get_eval_loss of the same batch."""
+  import math
+  raw = raw.to(torch.float64)
+  n = raw.shape[0]
+  count = raw[:, 2]
+  l1_i, mse_i = raw[:, 0] / count, raw[:, 1] / count
+  psnr_i = torch.tensor([10.0 * math.log10(255.0 ** 2 / m) if m > 0 else math.inf for m in mse_i.tolist()],
+                        dtype=torch.float64)
+  ms = []
+  for row in raw.tolist():
+    terms = row[4:8] + [row[13]]
+    ms.append(0.0 if min(terms) <= 0.0 else math.prod(t ** w for t, w in zip(terms, MS_SSIM_WEIGHTS)))
+  ms_i = torch.tensor(ms, dtype=torch.float64)
+  inv = 1.0 / float(count.sum().item())
+  as_f32 = lambda v: float(torch.tensor(v, dtype=torch.float64).to(torch.float32).item())
+  return dict(l1=as_f32(float(raw[:, 0].sum().item()) * inv), mse=as_f32(float(raw[:, 1].sum().item()) * inv),
+              psnr=float(psnr_i.mean().item()), ms_ssim=float(ms_i.mean().item()),
+              per_image=dict(l1=l1_i, mse=mse_i, psnr=psnr_i, ms_ssim=ms_i), raw=raw)
+
+
+def eval_metrics(fake, real32, mean, std):
+  """L1, MSE, PSNR and MS-SSIM (0..255 scale) of the uint8-quantised de-normalised images `fake` (Act, fp32 or bf16: the
+  generator's output) against `real32` (Act, fp32), both 3-channel NHWC: one device pass (jpdse_eval_metrics), one
+  read-back of 14 doubles per image, then eval_metrics_finish."""
+  assert fake.t.shape == real32.t.shape and fake.C == real32.C and len(mean) == fake.C and len(std) == fake.C
+  L = lib()
+  n = L.jpdse_eval_metrics_workspace_size(fake.N, fake.H, fake.W, fake.C)
+  ws = workspace(max(n, 1), fake.t.device)
+  out = torch.empty((fake.N, 14), dtype=torch.float64, device=fake.t.device)
+  arr = ctypes.c_double * fake.C
+  check(L.jpdse_eval_metrics(fake.dtype, real32.dtype, fake.N, fake.H, fake.W, fake.C, _p(fake.t), _p(real32.t),
+                             arr(*[float(v) for v in mean]), arr(*[float(v) for v in std]), _p(out), _p(ws), ws.numel(),
+                             _stream()), 'eval_metrics')
+  return eval_metrics_finish(out.cpu())

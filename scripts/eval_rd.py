@@ -1,0 +1,106 @@
+"""Rate-distortion evaluation loop on the device path: the numbers of the reference's test.py (its per-batch and test-set lines:
+L1 / MSE / MS-SSIM, bpp before / after entropy coding when the learned codec is on) plus PSNR, without the visualiser and the
+HTML page.  Per batch: trainer.get_eval_metrics (one generator forward) and, with the codec, trainer.get_eval_rate.
+
+Batches: seeded synthetic ones (ctu.utils.synthetic), or --data DIR holding pre-decoded batches as *.pt files, each a dict with
+the x_dict keys (label, instance, image, optionally compressed_img, path).  The test-set line averages the per-batch values
+over the batches, as the reference does (so, like there, a ragged last batch weighs as much as a full one); a second line
+gives the per-image averages, which are the ones to quote.  PSNR is the mean of the per-image PSNRs.
+
+  python scripts/eval_rd.py [--batches 4] [--batch 2] [--width 1024] [--height 512] [--dtype bf16] [--codec]
+                            [--checkpoints_dir DIR] [--data DIR]
+"""
+import argparse
+import contextlib
+import glob
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, 'jpd-se_amd')):
+  if p not in sys.path:
+    sys.path.insert(0, p)
+
+import torch  # noqa: E402
+
+
+def batches(args):
+  if args.data:
+    files = sorted(glob.glob(os.path.join(args.data, '*.pt')))
+    if not files:
+      raise SystemExit('no *.pt batch under %s' % args.data)
+    for f in files:
+      yield torch.load(f)
+  else:
+    from ctu.utils.synthetic import synthetic_batch
+    for i in range(args.batches):
+      yield synthetic_batch(args.batch, args.height, args.width, seed=1234 + i)
+
+
+def main():
+  ap = argparse.ArgumentParser()
+  ap.add_argument('--batches', type=int, default=4)
+  ap.add_argument('--batch', type=int, default=2)
+  ap.add_argument('--width', type=int, default=1024)
+  ap.add_argument('--height', type=int, default=512)
+  ap.add_argument('--dtype', default='bf16', choices=['bf16', 'fp32'])
+  ap.add_argument('--ngf', type=int, default=64)
+  ap.add_argument('--codec', action='store_true', help='learned codec (netE + binarizer): also report bpp')
+  ap.add_argument('--checkpoints_dir', default=None, help='load net_G.pth (and net_E.pth) from here')
+  ap.add_argument('--data', default=None, help='directory of pre-decoded *.pt batches instead of synthetic ones')
+  args = ap.parse_args()
+  import jpdse_hip
+  from ctu.trainers import get_trainer
+  from ctu.utils.synthetic import default_opt
+  jpdse_hip.require_gpu(0)
+  kw = dict(gpu_ids=[0], print_losses=False, compute_dtype=args.dtype, ngf=args.ngf, batch_size=args.batch)
+  if args.codec:
+    kw.update(no_feat_encoding=False, no_encoder_binarization=False, feat_num=3, nef=args.ngf, n_downsample_E=4,
+              encoder_binarizer_out_channels=128)
+  if args.checkpoints_dir:
+    kw.update(is_train=False, load_model=True, checkpoints_dir=args.checkpoints_dir)
+  opt = default_opt(**kw)
+  torch.manual_seed(1234)
+  with contextlib.redirect_stdout(sys.stderr):
+    trainer = get_trainer(opt)(opt, 'test' if args.checkpoints_dir else 'train')
+  keys = ('l1', 'mse', 'ms_ssim', 'psnr')
+  by_batch = dict.fromkeys(keys + ('shannon', 'actual'), 0.0)
+  by_image = dict.fromkeys(keys + ('shannon', 'actual'), 0.0)
+  images, n_batches = 0, 0
+  start = time.time()
+  for i, x_dict in enumerate(batches(args)):
+    m = trainer.get_eval_metrics(x_dict)
+    b = int(m['per_image']['l1'].numel())
+    line = 'batch {}, recon loss (L1/MSE/MS-SSIM) {:.4f}/{:.4f}/{:.4f}, PSNR {:.3f} dB'.format(i + 1, m['l1'], m['mse'], m['ms_ssim'],
+                                                                                         m['psnr'])
+    if args.codec:
+      shannon, actual = trainer.get_eval_rate(x_dict)
+      shannon = float(shannon)
+      by_batch['shannon'] += shannon
+      by_batch['actual'] += actual
+      by_image['shannon'] += shannon * b
+      by_image['actual'] += actual * b
+      line += ', pre-/(estimated) post-entropy coding bpp {:.4f}/{:.4f}'.format(actual, shannon)
+    end = time.time()
+    print(line + ', batch processing time (s) {:.4f}'.format(end - start))
+    start = end
+    for k in keys:
+      by_batch[k] += m[k]
+      by_image[k] += float(m['per_image'][k].sum())
+    images += b
+    n_batches += 1
+  print('\ntest done!\n')
+
+  def summary(head, t, n):
+    line = '{} (L1/MSE/MS-SSIM) {:.4f}/{:.4f}/{:.4f}, avg PSNR {:.3f} dB'.format(head, t['l1'] / n, t['mse'] / n,
+                                                                            t['ms_ssim'] / n, t['psnr'] / n)
+    if args.codec:
+      line += ', avg pre-/(estimated) post-entropy coding bpp {:.4f}/{:.4f}'.format(t['actual'] / n, t['shannon'] / n)
+    return line
+  print('\n' + summary('test set avg recon loss', by_batch, n_batches))
+  print(summary('per-image avg recon loss', by_image, images) + '\n')
+
+
+if __name__ == '__main__':
+  main()
