@@ -161,18 +161,13 @@ __global__ void code_pack_kernel(const T* __restrict__ b, uint8_t* __restrict__ 
   }
 }
 
-static int bad_dtype(int dtype) { return !(dtype == JPDSE_F32 || dtype == JPDSE_BF16); }
-
 static int stats_blocks(int dtype, int H, int W, int C) {
-  const long long vpi = (long long)H * W * (cpad(C) / (16 / (int)esize(dtype)));
+  const long long vpi = (long long)H * W * (cpad(C) / vec_elems(dtype));
   long long blocks = (vpi + 1023) / 1024;           // >= 4 vectors per thread
   if (blocks < 1) blocks = 1;
   if (blocks > 256) blocks = 256;
   return (int)blocks;
 }
-
-template <typename T> static const T* cptr(const void* p) { return reinterpret_cast<const T*>(p); }
-template <typename T> static T* mptr(void* p) { return reinterpret_cast<T*>(p); }
 
 }  // namespace jpdse
 
@@ -186,18 +181,13 @@ int jpdse_binarize_fwd(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C
                 "binarize_fwd: bad argument");
   JPDSE_REQUIRE(n_global0 + N <= 0xffffffffLL, "binarize_fwd: image index beyond 32 bits");
   const int Cs = cpad(C);
-  const int VE = 16 / (int)esize(dtype);
-  const long long tv = (long long)N * H * W * (Cs / VE);
+  const long long tv = (long long)N * H * W * (Cs / vec_elems(dtype));
   const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), d0 = (uint32_t)draw, d1 = (uint32_t)(draw >> 32);
-  if (dtype == JPDSE_BF16)
-    hipLaunchKernelGGL((binarize_fwd_kernel<bf16_t>), dim3(ew_blocks(tv)), dim3(256), 0, as_stream(stream),
-                       cptr<bf16_t>(t), mptr<bf16_t>(b), H, W, C, Cs, train ? 1 : 0, k0, k1, d0, d1,
-                       (long long)n_global0, u, tv);
-  else
-    hipLaunchKernelGGL((binarize_fwd_kernel<float>), dim3(ew_blocks(tv)), dim3(256), 0, as_stream(stream),
-                       cptr<float>(t), mptr<float>(b), H, W, C, Cs, train ? 1 : 0, k0, k1, d0, d1, (long long)n_global0,
-                       u, tv);
-  return check_launch("binarize_fwd");
+  return by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return ew_launch("binarize_fwd", binarize_fwd_kernel<T>, tv, stream, cptr<T>(t), mptr<T>(b), H, W, C, Cs, train ? 1 : 0, k0,
+                     k1, d0, d1, n_global0, u, tv);
+  });
 }
 
 size_t jpdse_code_stats_workspace_size(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C) {
@@ -212,17 +202,14 @@ int jpdse_code_stats(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, 
   if (ws == nullptr || ws_bytes < jpdse_code_stats_workspace_size(dtype, N, H, W, C))
     return set_error(JPDSE_EWORKSPACE, "code_stats: workspace too small");
   const int Cs = cpad(C);
-  const int VE = 16 / (int)esize(dtype);
-  const long long vpi = (long long)H * W * (Cs / VE);
+  const long long vpi = (long long)H * W * (Cs / vec_elems(dtype));
   const int blocks = stats_blocks(dtype, H, W, C);
-  int32_t* partial = reinterpret_cast<int32_t*>(ws);
-  if (dtype == JPDSE_BF16)
-    hipLaunchKernelGGL((code_stats_kernel<bf16_t>), dim3(blocks, N), dim3(256), 0, as_stream(stream), cptr<bf16_t>(b),
-                       partial, C, Cs, vpi);
-  else
-    hipLaunchKernelGGL((code_stats_kernel<float>), dim3(blocks, N), dim3(256), 0, as_stream(stream), cptr<float>(b),
-                       partial, C, Cs, vpi);
-  if (int rc = check_launch("code_stats")) return rc;
+  int32_t* partial = mptr<int32_t>(ws);
+  if (int rc = by_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        return launch256("code_stats", code_stats_kernel<T>, dim3(blocks, N), stream, cptr<T>(b), partial, C, Cs, vpi);
+      }))
+    return rc;
   hipLaunchKernelGGL(code_stats_final_kernel, dim3((N + 63) / 64), dim3(64), 0, as_stream(stream), partial, counts, N,
                      blocks);
   return check_launch("code_stats_final");
@@ -233,24 +220,14 @@ int jpdse_code_export(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C,
   JPDSE_REQUIRE(!bad_dtype(dtype) && b && out && N > 0 && H > 0 && W > 0 && C > 0, "code_export: bad argument");
   const int Cs = cpad(C);
   const long long HW = (long long)H * W, bits = (long long)C * HW;
-  if (packed) {
-    const long long nbytes = (bits + 7) / 8, total = (long long)N * nbytes;
-    if (dtype == JPDSE_BF16)
-      hipLaunchKernelGGL((code_pack_kernel<bf16_t>), dim3(ew_blocks(total)), dim3(256), 0, as_stream(stream),
-                         cptr<bf16_t>(b), mptr<uint8_t>(out), C, Cs, HW, nbytes, total);
-    else
-      hipLaunchKernelGGL((code_pack_kernel<float>), dim3(ew_blocks(total)), dim3(256), 0, as_stream(stream),
-                         cptr<float>(b), mptr<uint8_t>(out), C, Cs, HW, nbytes, total);
-    return check_launch("code_export(packed)");
-  }
-  const long long total = (long long)N * bits;
-  if (dtype == JPDSE_BF16)
-    hipLaunchKernelGGL((code_export_kernel<bf16_t>), dim3(ew_blocks(total)), dim3(256), 0, as_stream(stream),
-                       cptr<bf16_t>(b), mptr<float>(out), C, Cs, HW, total);
-  else
-    hipLaunchKernelGGL((code_export_kernel<float>), dim3(ew_blocks(total)), dim3(256), 0, as_stream(stream),
-                       cptr<float>(b), mptr<float>(out), C, Cs, HW, total);
-  return check_launch("code_export");
+  const long long nbytes = (bits + 7) / 8, total = (long long)N * (packed ? nbytes : bits);
+  return by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    if (packed)
+      return ew_launch("code_export(packed)", code_pack_kernel<T>, total, stream, cptr<T>(b), mptr<uint8_t>(out), C, Cs, HW,
+                       nbytes, total);
+    return ew_launch("code_export", code_export_kernel<T>, total, stream, cptr<T>(b), mptr<float>(out), C, Cs, HW, total);
+  });
 }
 
 }  // extern "C"

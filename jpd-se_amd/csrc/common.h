@@ -26,6 +26,10 @@ void hbm_prof_end(int slot, int cls, double algorithmic_bytes, hipStream_t s);  
 static inline int cpad(int c) { return (c + 7) & ~7; }
 static inline size_t esize(int dtype) { return dtype == JPDSE_BF16 ? 2 : 4; }
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+static inline int bad_dtype(int dtype) { return !(dtype == JPDSE_F32 || dtype == JPDSE_BF16); }
+static inline int vec_elems(int dtype) { return 16 / (int)esize(dtype); }   // elements per 16-byte vector
+template <typename T> static const T* cptr(const void* p) { return reinterpret_cast<const T*>(p); }
+template <typename T> static T* mptr(void* p) { return reinterpret_cast<T*>(p); }
 
 // Kernel-selection switches: compile-time constants in the shipped library, run-time variables in the developer build
 // (libjpdse_hip_dev.so, -DJPDSE_DEV; set through include/jpdse_dev.h).
@@ -184,6 +188,23 @@ static inline int ew_blocks(int64_t work_items, int threads = 256) {
   if (b < 1) b = 1;
   if (b > 2048) b = 2048;
   return (int)b;
+}
+
+// ---- host-side launch helpers of the HBM-bound sources (norm, elementwise, binarize, metrics) -------------------------------
+// The one bf16 / fp32 dispatch: f is a generic lambda that receives a value of the element type,
+//   by_dtype(dtype, [&](auto tag) { using T = decltype(tag); return launch256("x", x_kernel<T>, grid, stream, ...); })
+template <typename F> static inline auto by_dtype(int dtype, F&& f) { return dtype == JPDSE_BF16 ? f(bf16_t{}) : f(float{}); }
+
+// kernel<<<grid, 256, 0, stream>>>(args...) + check_launch(what); args convert to the kernel's parameter types
+template <typename... P, typename... A>
+static inline int launch256(const char* what, void (*kernel)(P...), dim3 grid, void* stream, A... args) {
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, as_stream(stream), static_cast<P>(args)...);
+  return check_launch(what);
+}
+// the same over ew_blocks(work_items) blocks: the grid-stride kernels
+template <typename... P, typename... A>
+static inline int ew_launch(const char* what, void (*kernel)(P...), long long work_items, void* stream, A... args) {
+  return launch256(what, kernel, dim3(ew_blocks(work_items)), stream, args...);
 }
 
 }  // namespace jpdse

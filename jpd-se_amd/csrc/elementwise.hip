@@ -697,18 +697,21 @@ __global__ __launch_bounds__(256) void quant_loss_final_kernel(const double* __r
   if (threadIdx.x == 0) out[0] = (float)((red[0] + red[1] + red[2] + red[3]) * inv_count);
 }
 
-static int bad_dtype(int dtype) { return !(dtype == JPDSE_F32 || dtype == JPDSE_BF16); }
+// ---- host side ------------------------------------------------------------------------------------------------------------
+// Every entry point below reads: argument check, geometry, one launch line (by_dtype / ew_launch / launch256: common.h).
 
-#define DISPATCH(dtype, KERNEL, grid, s, ...)                                                    \
-  do {                                                                                           \
-    if ((dtype) == JPDSE_BF16)                                                                   \
-      hipLaunchKernelGGL((KERNEL<bf16_t>), dim3(grid), dim3(256), 0, s, __VA_ARGS__);            \
-    else                                                                                         \
-      hipLaunchKernelGGL((KERNEL<float>), dim3(grid), dim3(256), 0, s, __VA_ARGS__);             \
-  } while (0)
+// 16-byte vectors of an NHWC tensor of `pixels` pixels with `cs` storage channels
+static long long nhwc_vecs(int dtype, long long pixels, int cs) { return pixels * (cs / vec_elems(dtype)); }
 
-template <typename T> static const T* cptr(const void* p) { return reinterpret_cast<const T*>(p); }
-template <typename T> static T* mptr(void* p) { return reinterpret_cast<T*>(p); }
+// n elements as whole 16-byte vectors (`positive`: n > 0 is part of the same refusal)
+static int vec_count(const char* name, int dtype, int64_t n, long long* tv, bool positive = true) {
+  JPDSE_REQUIRE(!bad_dtype(dtype), "%s: bad dtype", name);
+  const int VE = vec_elems(dtype);
+  JPDSE_REQUIRE((n > 0 || !positive) && n % VE == 0, "%s: n=%lld not a %smultiple of %d", name, (long long)n,
+                positive ? "positive " : "", VE);
+  *tv = n / VE;
+  return JPDSE_OK;
+}
 
 }  // namespace jpdse
 
@@ -720,95 +723,67 @@ int jpdse_avgpool3s2_fwd(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t
                          void* stream) {
   JPDSE_REQUIRE(!bad_dtype(dtype) && x && y && N > 0 && H > 0 && W > 0 && C > 0, "avgpool3s2_fwd: bad argument");
   const int Cs = cpad(C), OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
-  const long long tv = (long long)N * OH * OW * (Cs / (16 / (int)esize(dtype)));
-  if (dtype == JPDSE_BF16)
-    hipLaunchKernelGGL((avgpool3s2_fwd_kernel<bf16_t>), dim3(ew_blocks(tv)), dim3(256), 0, as_stream(stream),
-                       cptr<bf16_t>(x), mptr<bf16_t>(y), H, W, OH, OW, Cs, tv);
-  else
-    hipLaunchKernelGGL((avgpool3s2_fwd_kernel<float>), dim3(ew_blocks(tv)), dim3(256), 0, as_stream(stream),
-                       cptr<float>(x), mptr<float>(y), H, W, OH, OW, Cs, tv);
-  return check_launch("avgpool3s2_fwd");
+  const long long tv = nhwc_vecs(dtype, (long long)N * OH * OW, Cs);
+  return by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return ew_launch("avgpool3s2_fwd", avgpool3s2_fwd_kernel<T>, tv, stream, cptr<T>(x), mptr<T>(y), H, W, OH, OW, Cs, tv);
+  });
 }
 
 int jpdse_avgpool3s2_bwd(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, const void* dy, void* dx,
                          void* stream) {
   JPDSE_REQUIRE(!bad_dtype(dtype) && dy && dx && N > 0 && H > 0 && W > 0 && C > 0, "avgpool3s2_bwd: bad argument");
   const int Cs = cpad(C), OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
-  const long long tv = (long long)N * H * W * (Cs / (16 / (int)esize(dtype)));
-  if (dtype == JPDSE_BF16)
-    hipLaunchKernelGGL((avgpool3s2_bwd_kernel<bf16_t>), dim3(ew_blocks(tv)), dim3(256), 0, as_stream(stream),
-                       cptr<bf16_t>(dy), mptr<bf16_t>(dx), H, W, OH, OW, Cs, tv);
-  else
-    hipLaunchKernelGGL((avgpool3s2_bwd_kernel<float>), dim3(ew_blocks(tv)), dim3(256), 0, as_stream(stream),
-                       cptr<float>(dy), mptr<float>(dx), H, W, OH, OW, Cs, tv);
-  return check_launch("avgpool3s2_bwd");
+  const long long tv = nhwc_vecs(dtype, (long long)N * H * W, Cs);
+  return by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return ew_launch("avgpool3s2_bwd", avgpool3s2_bwd_kernel<T>, tv, stream, cptr<T>(dy), mptr<T>(dx), H, W, OH, OW, Cs, tv);
+  });
 }
 
 int jpdse_maxpool2_fwd(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, const void* x, void* y,
                        void* stream) {
   JPDSE_REQUIRE(!bad_dtype(dtype) && x && y && N > 0 && H > 1 && W > 1 && C > 0, "maxpool2_fwd: bad argument");
   const int Cs = cpad(C), OH = H / 2, OW = W / 2;
-  const long long tv = (long long)N * OH * OW * (Cs / (16 / (int)esize(dtype)));
-  if (dtype == JPDSE_BF16)
-    hipLaunchKernelGGL((maxpool2_fwd_kernel<bf16_t>), dim3(ew_blocks(tv)), dim3(256), 0, as_stream(stream),
-                       cptr<bf16_t>(x), mptr<bf16_t>(y), H, W, OH, OW, Cs, tv);
-  else
-    hipLaunchKernelGGL((maxpool2_fwd_kernel<float>), dim3(ew_blocks(tv)), dim3(256), 0, as_stream(stream),
-                       cptr<float>(x), mptr<float>(y), H, W, OH, OW, Cs, tv);
-  return check_launch("maxpool2_fwd");
+  const long long tv = nhwc_vecs(dtype, (long long)N * OH * OW, Cs);
+  return by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return ew_launch("maxpool2_fwd", maxpool2_fwd_kernel<T>, tv, stream, cptr<T>(x), mptr<T>(y), H, W, OH, OW, Cs, tv);
+  });
 }
 
 int jpdse_maxpool2_bwd(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, const void* x, const void* dy,
                        void* dx, void* stream) {
   JPDSE_REQUIRE(!bad_dtype(dtype) && x && dy && dx && N > 0 && H > 1 && W > 1 && C > 0, "maxpool2_bwd: bad argument");
   const int Cs = cpad(C), OH = H / 2, OW = W / 2;
-  const long long tv = (long long)N * H * W * (Cs / (16 / (int)esize(dtype)));
-  if (H % 2 == 0 && W % 2 == 0) {
-    const long long wv = tv / 4;
-    if (dtype == JPDSE_BF16)
-      hipLaunchKernelGGL((maxpool2_bwd_win_kernel<bf16_t>), dim3(ew_blocks(wv)), dim3(256), 0, as_stream(stream),
-                         cptr<bf16_t>(x), cptr<bf16_t>(dy), mptr<bf16_t>(dx), H, W, OH, OW, Cs, wv);
-    else
-      hipLaunchKernelGGL((maxpool2_bwd_win_kernel<float>), dim3(ew_blocks(wv)), dim3(256), 0, as_stream(stream),
-                         cptr<float>(x), cptr<float>(dy), mptr<float>(dx), H, W, OH, OW, Cs, wv);
-    return check_launch("maxpool2_bwd");
-  }
-  if (dtype == JPDSE_BF16)
-    hipLaunchKernelGGL((maxpool2_bwd_kernel<bf16_t>), dim3(ew_blocks(tv)), dim3(256), 0, as_stream(stream),
-                       cptr<bf16_t>(x), cptr<bf16_t>(dy), mptr<bf16_t>(dx), H, W, OH, OW, Cs, tv);
-  else
-    hipLaunchKernelGGL((maxpool2_bwd_kernel<float>), dim3(ew_blocks(tv)), dim3(256), 0, as_stream(stream),
-                       cptr<float>(x), cptr<float>(dy), mptr<float>(dx), H, W, OH, OW, Cs, tv);
-  return check_launch("maxpool2_bwd");
+  const bool windows = H % 2 == 0 && W % 2 == 0;        // one thread per window instead of one per pixel
+  const long long tv = nhwc_vecs(dtype, (long long)N * H * W, Cs) / (windows ? 4 : 1);
+  return by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return ew_launch("maxpool2_bwd", windows ? maxpool2_bwd_win_kernel<T> : maxpool2_bwd_kernel<T>, tv, stream, cptr<T>(x),
+                     cptr<T>(dy), mptr<T>(dx), H, W, OH, OW, Cs, tv);
+  });
 }
 
 int jpdse_act_bwd(int32_t dtype, int64_t n, int32_t act, float slope, const void* y, const void* dy, void* dz,
                   void* stream) {
   JPDSE_REQUIRE(!bad_dtype(dtype) && y && dy && dz && n > 0, "act_bwd: bad argument");
-  const int VE = 16 / (int)esize(dtype);
-  JPDSE_REQUIRE(n % VE == 0, "act_bwd: n=%lld not a multiple of %d", (long long)n, VE);
-  const long long tv = n / VE;
-  if (dtype == JPDSE_BF16)
-    hipLaunchKernelGGL((act_bwd_kernel<bf16_t>), dim3(ew_blocks(tv)), dim3(256), 0, as_stream(stream),
-                       cptr<bf16_t>(y), cptr<bf16_t>(dy), mptr<bf16_t>(dz), act, slope, tv);
-  else
-    hipLaunchKernelGGL((act_bwd_kernel<float>), dim3(ew_blocks(tv)), dim3(256), 0, as_stream(stream), cptr<float>(y),
-                       cptr<float>(dy), mptr<float>(dz), act, slope, tv);
-  return check_launch("act_bwd");
+  long long tv;
+  if (int rc = vec_count("act_bwd", dtype, n, &tv, false)) return rc;
+  return by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return ew_launch("act_bwd", act_bwd_kernel<T>, tv, stream, cptr<T>(y), cptr<T>(dy), mptr<T>(dz), act, slope, tv);
+  });
 }
 
 int jpdse_add(int32_t dtype, int64_t n, const void* a, const void* b, void* out, void* stream) {
   JPDSE_REQUIRE(!bad_dtype(dtype) && a && b && out && n > 0, "add: bad argument");
-  const int VE = 16 / (int)esize(dtype);
-  JPDSE_REQUIRE(n % VE == 0, "add: n=%lld not a multiple of %d", (long long)n, VE);
-  const long long tv = n / VE;
-  if (dtype == JPDSE_BF16)
-    hipLaunchKernelGGL((add_kernel<bf16_t>), dim3(ew_blocks(tv)), dim3(256), 0, as_stream(stream), cptr<bf16_t>(a),
-                       cptr<bf16_t>(b), mptr<bf16_t>(out), tv);
-  else
-    hipLaunchKernelGGL((add_kernel<float>), dim3(ew_blocks(tv)), dim3(256), 0, as_stream(stream), cptr<float>(a),
-                       cptr<float>(b), mptr<float>(out), tv);
-  return check_launch("add");
+  long long tv;
+  if (int rc = vec_count("add", dtype, n, &tv, false)) return rc;
+  return by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return ew_launch("add", add_kernel<T>, tv, stream, cptr<T>(a), cptr<T>(b), mptr<T>(out), tv);
+  });
 }
 
 int jpdse_zero(int32_t dtype, int64_t n, void* p, void* stream) {
@@ -820,8 +795,7 @@ int jpdse_zero(int32_t dtype, int64_t n, void* p, void* stream) {
 }
 
 static void csum_geom(int dtype, int64_t npix, int Cs, int& TX, int& TY, long long& ppb, int& nblk) {
-  const int VE = 16 / (int)esize(dtype);
-  const int cv = Cs / VE;
+  const int cv = Cs / vec_elems(dtype);
   TX = 1;
   while (TX < cv && TX < 256) TX <<= 1;
   TY = 256 / TX;
@@ -845,19 +819,15 @@ int jpdse_channel_sum(int32_t dtype, int64_t npix, int32_t C, const void* dy, fl
   int TX, TY, nblk;
   long long ppb;
   csum_geom(dtype, npix, Cs, TX, TY, ppb, nblk);
-  const int VE = 16 / (int)esize(dtype);
-  const int col_blocks = (Cs / VE + TX - 1) / TX;
-  float* partial = reinterpret_cast<float*>(ws);
-  if (dtype == JPDSE_BF16)
-    hipLaunchKernelGGL((channel_sum_kernel<bf16_t>), dim3(nblk * col_blocks), dim3(256), 0, as_stream(stream),
-                       cptr<bf16_t>(dy), partial, (long long)npix, Cs, TX, TY, ppb);
-  else
-    hipLaunchKernelGGL((channel_sum_kernel<float>), dim3(nblk * col_blocks), dim3(256), 0, as_stream(stream),
-                       cptr<float>(dy), partial, (long long)npix, Cs, TX, TY, ppb);
-  if (int rc = check_launch("channel_sum")) return rc;
-  hipLaunchKernelGGL(channel_sum_final_kernel, dim3((Cs + 63) / 64), dim3(256), 0, as_stream(stream), partial, out,
-                     Cs, nblk);
-  return check_launch("channel_sum_final");
+  const int col_blocks = (Cs / vec_elems(dtype) + TX - 1) / TX;
+  float* partial = mptr<float>(ws);
+  if (int rc = by_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        return launch256("channel_sum", channel_sum_kernel<T>, dim3(nblk * col_blocks), stream, cptr<T>(dy), partial, npix, Cs,
+                         TX, TY, ppb);
+      }))
+    return rc;
+  return launch256("channel_sum_final", channel_sum_final_kernel, dim3((Cs + 63) / 64), stream, partial, out, Cs, nblk);
 }
 
 int jpdse_channel_copy(int32_t dtype, int64_t npix, const void* src, int32_t src_cs, int32_t src_c0, void* dst,
@@ -866,27 +836,23 @@ int jpdse_channel_copy(int32_t dtype, int64_t npix, const void* src, int32_t src
   JPDSE_REQUIRE(src_c0 >= 0 && dst_c0 >= 0 && src_c0 + nch <= src_cs && dst_c0 + nch <= dst_cs,
                 "channel_copy: channel range out of bounds");
   const long long total = (long long)npix * nch;
-  if (dtype == JPDSE_BF16)
-    hipLaunchKernelGGL((channel_copy_kernel<bf16_t>), dim3(ew_blocks(total)), dim3(256), 0, as_stream(stream),
-                       cptr<bf16_t>(src), src_cs, src_c0, mptr<bf16_t>(dst), dst_cs, dst_c0, nch, total);
-  else
-    hipLaunchKernelGGL((channel_copy_kernel<float>), dim3(ew_blocks(total)), dim3(256), 0, as_stream(stream),
-                       cptr<float>(src), src_cs, src_c0, mptr<float>(dst), dst_cs, dst_c0, nch, total);
-  return check_launch("channel_copy");
+  return by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return ew_launch("channel_copy", channel_copy_kernel<T>, total, stream, cptr<T>(src), src_cs, src_c0, mptr<T>(dst), dst_cs,
+                     dst_c0, nch, total);
+  });
 }
 
 int jpdse_concat_channels(int32_t dtype, int64_t npix, const void* base, int32_t cs, const void* img, int32_t img_cs,
                           int32_t c0, int32_t nch, void* out, void* stream) {
   JPDSE_REQUIRE(!bad_dtype(dtype) && base && img && out && npix > 0 && nch > 0, "concat_channels: bad argument");
   JPDSE_REQUIRE(cs % 8 == 0 && c0 >= 0 && c0 + nch <= cs && nch <= img_cs, "concat_channels: channel range out of bounds");
-  const long long tv = (long long)npix * (cs / (16 / (int)esize(dtype)));
-  if (dtype == JPDSE_BF16)
-    hipLaunchKernelGGL((concat_channels_kernel<bf16_t>), dim3(ew_blocks(tv)), dim3(256), 0, as_stream(stream),
-                       cptr<bf16_t>(base), cptr<bf16_t>(img), mptr<bf16_t>(out), cs, img_cs, c0, nch, tv);
-  else
-    hipLaunchKernelGGL((concat_channels_kernel<float>), dim3(ew_blocks(tv)), dim3(256), 0, as_stream(stream),
-                       cptr<float>(base), cptr<float>(img), mptr<float>(out), cs, img_cs, c0, nch, tv);
-  return check_launch("concat_channels");
+  const long long tv = nhwc_vecs(dtype, npix, cs);
+  return by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return ew_launch("concat_channels", concat_channels_kernel<T>, tv, stream, cptr<T>(base), cptr<T>(img), mptr<T>(out), cs,
+                     img_cs, c0, nch, tv);
+  });
 }
 
 int jpdse_nchw_to_nhwc(int32_t dtype, int32_t N, int32_t C, int32_t H, int32_t W, const float* src, void* dst,
@@ -894,13 +860,10 @@ int jpdse_nchw_to_nhwc(int32_t dtype, int32_t N, int32_t C, int32_t H, int32_t W
   JPDSE_REQUIRE(!bad_dtype(dtype) && src && dst && N > 0 && C > 0 && H > 0 && W > 0, "nchw_to_nhwc: bad argument");
   const int Cs = cpad(C);
   const long long HW = (long long)H * W, total = (long long)N * Cs * HW;
-  if (dtype == JPDSE_BF16)
-    hipLaunchKernelGGL((nchw_to_nhwc_kernel<bf16_t>), dim3(ew_blocks(total)), dim3(256), 0, as_stream(stream), src,
-                       mptr<bf16_t>(dst), C, Cs, HW, total);
-  else
-    hipLaunchKernelGGL((nchw_to_nhwc_kernel<float>), dim3(ew_blocks(total)), dim3(256), 0, as_stream(stream), src,
-                       mptr<float>(dst), C, Cs, HW, total);
-  return check_launch("nchw_to_nhwc");
+  return by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return ew_launch("nchw_to_nhwc", nchw_to_nhwc_kernel<T>, total, stream, src, mptr<T>(dst), C, Cs, HW, total);
+  });
 }
 
 int jpdse_nhwc_to_nchw(int32_t dtype, int32_t N, int32_t C, int32_t H, int32_t W, const void* src, float* dst,
@@ -908,28 +871,22 @@ int jpdse_nhwc_to_nchw(int32_t dtype, int32_t N, int32_t C, int32_t H, int32_t W
   JPDSE_REQUIRE(!bad_dtype(dtype) && src && dst && N > 0 && C > 0 && H > 0 && W > 0, "nhwc_to_nchw: bad argument");
   const int Cs = cpad(C);
   const long long HW = (long long)H * W, total = (long long)N * C * HW;
-  if (dtype == JPDSE_BF16)
-    hipLaunchKernelGGL((nhwc_to_nchw_kernel<bf16_t>), dim3(ew_blocks(total)), dim3(256), 0, as_stream(stream),
-                       cptr<bf16_t>(src), dst, C, Cs, HW, total);
-  else
-    hipLaunchKernelGGL((nhwc_to_nchw_kernel<float>), dim3(ew_blocks(total)), dim3(256), 0, as_stream(stream),
-                       cptr<float>(src), dst, C, Cs, HW, total);
-  return check_launch("nhwc_to_nchw");
+  return by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return ew_launch("nhwc_to_nchw", nhwc_to_nchw_kernel<T>, total, stream, cptr<T>(src), dst, C, Cs, HW, total);
+  });
 }
 
 int jpdse_onehot_edge(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t num_labels, const float* label,
                       const int64_t* instance, void* dst, int32_t cs, void* stream) {
   JPDSE_REQUIRE(!bad_dtype(dtype) && label && instance && dst && N > 0 && H > 0 && W > 0, "onehot_edge: bad argument");
   JPDSE_REQUIRE(num_labels > 0 && num_labels < cs && cs % 8 == 0, "onehot_edge: need num_labels < cs, cs %% 8 == 0");
-  const int VE = 16 / (int)esize(dtype);
-  const long long tv = (long long)N * H * W * (cs / VE);
-  if (dtype == JPDSE_BF16)
-    hipLaunchKernelGGL((onehot_edge_kernel<bf16_t>), dim3(ew_blocks(tv)), dim3(256), 0, as_stream(stream), label,
-                       reinterpret_cast<const long long*>(instance), mptr<bf16_t>(dst), H, W, num_labels, cs, tv);
-  else
-    hipLaunchKernelGGL((onehot_edge_kernel<float>), dim3(ew_blocks(tv)), dim3(256), 0, as_stream(stream), label,
-                       reinterpret_cast<const long long*>(instance), mptr<float>(dst), H, W, num_labels, cs, tv);
-  return check_launch("onehot_edge");
+  const long long tv = nhwc_vecs(dtype, (long long)N * H * W, cs);
+  return by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return ew_launch("onehot_edge", onehot_edge_kernel<T>, tv, stream, label, reinterpret_cast<const long long*>(instance),
+                     mptr<T>(dst), H, W, num_labels, cs, tv);
+  });
 }
 
 int jpdse_input_builder(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t num_labels, const float* label,
@@ -955,40 +912,27 @@ int jpdse_input_builder(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t 
   a.img_cs = img_cs;
   a.c0 = c0;
   a.nch = nch;
-  const long long npix = (long long)N * H * W;
-  const int cv = cs / (16 / (int)esize(dtype));
-  JPDSE_REQUIRE(npix * cv < (1LL << 32), "input_builder: more than 2^32 vectors");
-  const unsigned grid = (unsigned)((npix * cv + 255) / 256);
+  const long long tv = nhwc_vecs(dtype, (long long)N * H * W, cs);
+  JPDSE_REQUIRE(tv < (1LL << 32), "input_builder: more than 2^32 vectors");
   // the vector count per pixel is a template parameter (cheap index arithmetic): 40 storage channels are the hot path
   // (5 bf16 / 10 fp32 vectors), other widths up to 64 channels have their own instantiation
-#define JPDSE_BUILDER(T, CVN) hipLaunchKernelGGL((input_builder_kernel<T, CVN>), dim3(grid), dim3(256), 0, as_stream(stream), a, (unsigned)(npix * cv))
-  if (dtype == JPDSE_BF16) {
-    switch (cv) {
-      case 1: JPDSE_BUILDER(bf16_t, 1); break;
-      case 2: JPDSE_BUILDER(bf16_t, 2); break;
-      case 3: JPDSE_BUILDER(bf16_t, 3); break;
-      case 4: JPDSE_BUILDER(bf16_t, 4); break;
-      case 5: JPDSE_BUILDER(bf16_t, 5); break;
-      case 6: JPDSE_BUILDER(bf16_t, 6); break;
-      case 7: JPDSE_BUILDER(bf16_t, 7); break;
-      case 8: JPDSE_BUILDER(bf16_t, 8); break;
+  return by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    constexpr int M = 8 / Vec16<T>::N;          // vectors per 8 storage channels
+    void (*kernel)(const BuilderArgs, unsigned) = nullptr;
+    switch (cs / 8) {
+      case 1: kernel = input_builder_kernel<T, 1 * M>; break;
+      case 2: kernel = input_builder_kernel<T, 2 * M>; break;
+      case 3: kernel = input_builder_kernel<T, 3 * M>; break;
+      case 4: kernel = input_builder_kernel<T, 4 * M>; break;
+      case 5: kernel = input_builder_kernel<T, 5 * M>; break;
+      case 6: kernel = input_builder_kernel<T, 6 * M>; break;
+      case 7: kernel = input_builder_kernel<T, 7 * M>; break;
+      case 8: kernel = input_builder_kernel<T, 8 * M>; break;
       default: return set_error(JPDSE_EINVAL, "input_builder: %d storage channels unsupported (<= 64)", cs);
     }
-  } else {
-    switch (cv) {
-      case 2: JPDSE_BUILDER(float, 2); break;
-      case 4: JPDSE_BUILDER(float, 4); break;
-      case 6: JPDSE_BUILDER(float, 6); break;
-      case 8: JPDSE_BUILDER(float, 8); break;
-      case 10: JPDSE_BUILDER(float, 10); break;
-      case 12: JPDSE_BUILDER(float, 12); break;
-      case 14: JPDSE_BUILDER(float, 14); break;
-      case 16: JPDSE_BUILDER(float, 16); break;
-      default: return set_error(JPDSE_EINVAL, "input_builder: %d storage channels unsupported (<= 64)", cs);
-    }
-  }
-#undef JPDSE_BUILDER
-  return check_launch("input_builder");
+    return launch256("input_builder", kernel, dim3((unsigned)((tv + 255) / 256)), stream, a, (unsigned)tv);
+  });
 }
 
 int jpdse_insert_channels(int32_t dtype, int64_t npix, void* dst, int32_t cs, const void* img, int32_t img_cs, int32_t c0,
@@ -996,82 +940,72 @@ int jpdse_insert_channels(int32_t dtype, int64_t npix, void* dst, int32_t cs, co
   JPDSE_REQUIRE(!bad_dtype(dtype) && dst && img && npix > 0, "insert_channels: bad argument");
   JPDSE_REQUIRE(cs % 8 == 0 && img_cs % 8 == 0 && nch > 0 && nch <= img_cs && c0 >= 0 && c0 + nch <= cs,
                 "insert_channels: channels [%d, %d) outside 0..%d", c0, c0 + nch, cs);
-  const int VE = 16 / (int)esize(dtype);
+  const int VE = vec_elems(dtype);
   const int v0 = c0 / VE, v1 = (c0 + nch - 1) / VE, nv = v1 - v0 + 1;
   const long long total = (long long)npix * nv;
-  if (dtype == JPDSE_BF16)
-    hipLaunchKernelGGL((insert_channels_kernel<bf16_t>), dim3(ew_blocks(total)), dim3(256), 0, as_stream(stream),
-                       mptr<bf16_t>(dst), cptr<bf16_t>(img), cs, img_cs, c0, nch, v0, nv, total);
-  else
-    hipLaunchKernelGGL((insert_channels_kernel<float>), dim3(ew_blocks(total)), dim3(256), 0, as_stream(stream),
-                       mptr<float>(dst), cptr<float>(img), cs, img_cs, c0, nch, v0, nv, total);
-  return check_launch("insert_channels");
+  return by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return ew_launch("insert_channels", insert_channels_kernel<T>, total, stream, mptr<T>(dst), cptr<T>(img), cs, img_cs, c0,
+                     nch, v0, nv, total);
+  });
 }
 
 int jpdse_copy(int64_t nbytes, const void* src, void* dst, void* stream) {
   JPDSE_REQUIRE(src && dst && nbytes > 0 && nbytes % 16 == 0, "copy: %lld bytes (a positive multiple of 16 is required)", (long long)nbytes);
   JPDSE_REQUIRE((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) % 16 == 0, "copy: pointers must be 16-byte aligned");
   const long long nvec = nbytes / 16;
-  hipLaunchKernelGGL(copy16_kernel, dim3(ew_blocks(nvec)), dim3(256), 0, as_stream(stream), reinterpret_cast<const u32x4*>(src),
-                     reinterpret_cast<u32x4*>(dst), nvec);
-  return check_launch("copy");
+  return ew_launch("copy", copy16_kernel, nvec, stream, cptr<u32x4>(src), mptr<u32x4>(dst), nvec);
 }
 
 size_t jpdse_loss_workspace_size(int64_t n) { return kRedBlocks * sizeof(float); }
-
-}  // extern "C"
-
-template <int MODE>
-static int loss_fwd(const char* name, int dtype, long long total, long long count, const void* a, const void* b,
-                    float target, int cs, float* out, void* ws, size_t ws_bytes, void* stream) {
-  JPDSE_REQUIRE(!bad_dtype(dtype) && a && total > 0 && count > 0, "%s: bad argument", name);
-  if (ws == nullptr || ws_bytes < kRedBlocks * sizeof(float))
-    return set_error(JPDSE_EWORKSPACE, "%s: workspace too small", name);
-  int grid = ew_blocks(total);
-  if (grid > kRedBlocks) grid = kRedBlocks;
-  float* partial = reinterpret_cast<float*>(ws);
-  if (dtype == JPDSE_BF16)
-    hipLaunchKernelGGL((loss_partial_kernel<bf16_t, MODE>), dim3(grid), dim3(256), 0, as_stream(stream),
-                       cptr<bf16_t>(a), cptr<bf16_t>(b), target, cs, partial, total);
-  else
-    hipLaunchKernelGGL((loss_partial_kernel<float, MODE>), dim3(grid), dim3(256), 0, as_stream(stream), cptr<float>(a),
-                       cptr<float>(b), target, cs, partial, total);
-  if (int rc = check_launch(name)) return rc;
-  if (out == nullptr) return JPDSE_OK;                  // deferred: jpdse_loss_finalize reduces the partials
-  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, as_stream(stream), partial, grid,
-                     1.f / (float)count, out);
-  return check_launch(name);
-}
-
-template <int MODE>
-static int loss_bwd(const char* name, int dtype, long long total, long long count, const void* a, const void* b,
-                    float target, int cs, const float* gout, float scale, void* da, void* stream, int relu_a = 0) {
-  JPDSE_REQUIRE(!bad_dtype(dtype) && a && gout && da && total > 0 && count > 0, "%s: bad argument", name);
-  const float sc = scale / (float)count;
-  if (dtype == JPDSE_BF16)
-    hipLaunchKernelGGL((loss_bwd_kernel<bf16_t, MODE>), dim3(ew_blocks(total)), dim3(256), 0, as_stream(stream),
-                       cptr<bf16_t>(a), cptr<bf16_t>(b), target, cs, gout, sc, mptr<bf16_t>(da), total, relu_a);
-  else
-    hipLaunchKernelGGL((loss_bwd_kernel<float, MODE>), dim3(ew_blocks(total)), dim3(256), 0, as_stream(stream),
-                       cptr<float>(a), cptr<float>(b), target, cs, gout, sc, mptr<float>(da), total, relu_a);
-  return check_launch(name);
-}
-
-static int vec_count(const char* name, int dtype, int64_t n, long long* tv) {
-  JPDSE_REQUIRE(!bad_dtype(dtype), "%s: bad dtype", name);
-  const int VE = 16 / (int)esize(dtype);
-  JPDSE_REQUIRE(n > 0 && n % VE == 0, "%s: n=%lld not a positive multiple of %d", name, (long long)n, VE);
-  *tv = n / VE;
-  return JPDSE_OK;
-}
-
-extern "C" {
 
 int32_t jpdse_loss_partial_count(int64_t work_items) {
   if (work_items <= 0) return 0;
   const int grid = ew_blocks(work_items);
   return grid > kRedBlocks ? kRedBlocks : grid;
 }
+
+}  // extern "C"
+
+// First stage of a loss into the partials of `ws` and, unless deferred (out == nullptr: jpdse_loss_finalize reduces them), the
+// second stage.  da (L1 only, optional): the gradient written in the same pass.
+template <int MODE>
+static int loss_reduce(const char* name, int dtype, long long total, long long count, const void* a, const void* b, float target,
+                       int cs, float* out, void* ws, size_t ws_bytes, void* stream, void* da = nullptr, float gscale = 0.f,
+                       int relu_a = 0) {
+  if (ws == nullptr || ws_bytes < kRedBlocks * sizeof(float))
+    return set_error(JPDSE_EWORKSPACE, "%s: workspace too small", name);
+  const int grid = jpdse_loss_partial_count(total);
+  float* partial = mptr<float>(ws);
+  if (int rc = by_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        return launch256(name, loss_partial_kernel<T, MODE>, dim3(grid), stream, cptr<T>(a), cptr<T>(b), target, cs, partial,
+                         total, mptr<T>(da), gscale, relu_a);
+      }))
+    return rc;
+  if (out == nullptr) return JPDSE_OK;
+  return launch256(name, loss_final_kernel, dim3(1), stream, partial, grid, 1.f / (float)count, out);
+}
+
+template <int MODE>
+static int loss_fwd(const char* name, int dtype, long long total, long long count, const void* a, const void* b,
+                    float target, int cs, float* out, void* ws, size_t ws_bytes, void* stream) {
+  JPDSE_REQUIRE(!bad_dtype(dtype) && a && total > 0 && count > 0, "%s: bad argument", name);
+  return loss_reduce<MODE>(name, dtype, total, count, a, b, target, cs, out, ws, ws_bytes, stream);
+}
+
+template <int MODE>
+static int loss_bwd(const char* name, int dtype, long long total, long long count, const void* a, const void* b,
+                    float target, int cs, const float* gout, float scale, void* da, void* stream, int relu_a = 0) {
+  JPDSE_REQUIRE(!bad_dtype(dtype) && a && gout && da && total > 0 && count > 0, "%s: bad argument", name);
+  return by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return ew_launch(name, loss_bwd_kernel<T, MODE>, total, stream, cptr<T>(a), cptr<T>(b), target, cs, gout,
+                     scale / (float)count, mptr<T>(da), total, relu_a);
+  });
+}
+
+extern "C" {
 
 int jpdse_loss_finalize(const jpdse_loss_term* terms, int32_t n_terms, void* stream) {
   JPDSE_REQUIRE(terms != nullptr && n_terms > 0, "loss_finalize: bad argument");
@@ -1083,8 +1017,7 @@ int jpdse_loss_finalize(const jpdse_loss_term* terms, int32_t n_terms, void* str
       JPDSE_REQUIRE(e.partial != nullptr && e.out != nullptr && e.n > 0 && e.n <= kRedBlocks, "loss_finalize: term %d is malformed", t0 + i);
       tab.t[i] = e;
     }
-    hipLaunchKernelGGL(loss_final_many_kernel, dim3(n), dim3(256), 0, as_stream(stream), tab);
-    if (int rc = check_launch("loss_finalize")) return rc;
+    if (int rc = launch256("loss_finalize", loss_final_many_kernel, dim3(n), stream, tab)) return rc;
   }
   return JPDSE_OK;
 }
@@ -1108,22 +1041,8 @@ int jpdse_l1_fwd_bwd(int32_t dtype, int64_t n, int64_t count, const void* a, con
   long long tv;
   if (int rc = vec_count("l1_fwd_bwd", dtype, n, &tv)) return rc;
   JPDSE_REQUIRE(a && b && da && count > 0, "l1_fwd_bwd: bad argument");
-  if (ws == nullptr || ws_bytes < kRedBlocks * sizeof(float))
-    return set_error(JPDSE_EWORKSPACE, "l1_fwd_bwd: workspace too small");
-  int grid = ew_blocks(tv);
-  if (grid > kRedBlocks) grid = kRedBlocks;
-  float* partial = reinterpret_cast<float*>(ws);
-  const float gs = scale / (float)count;
-  if (dtype == JPDSE_BF16)
-    hipLaunchKernelGGL((loss_partial_kernel<bf16_t, RED_L1>), dim3(grid), dim3(256), 0, as_stream(stream),
-                       cptr<bf16_t>(a), cptr<bf16_t>(b), 0.f, 0, partial, tv, mptr<bf16_t>(da), gs, relu_a);
-  else
-    hipLaunchKernelGGL((loss_partial_kernel<float, RED_L1>), dim3(grid), dim3(256), 0, as_stream(stream),
-                       cptr<float>(a), cptr<float>(b), 0.f, 0, partial, tv, mptr<float>(da), gs, relu_a);
-  if (int rc = check_launch("l1_fwd_bwd")) return rc;
-  if (out == nullptr) return JPDSE_OK;                  // deferred: jpdse_loss_finalize reduces the partials
-  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, as_stream(stream), partial, grid, 1.f / (float)count, out);
-  return check_launch("l1_fwd_bwd");
+  return loss_reduce<RED_L1>("l1_fwd_bwd", dtype, tv, count, a, b, 0.f, 0, out, ws, ws_bytes, stream, da, scale / (float)count,
+                             relu_a);
 }
 int jpdse_l1_bwd_relu(int32_t dtype, int64_t n, int64_t count, const void* a, const void* b, const float* gout,
                       float scale, void* da, void* stream) {
@@ -1177,31 +1096,11 @@ int jpdse_cast(int32_t src_dtype, int32_t dst_dtype, int64_t n, const void* src,
   JPDSE_REQUIRE(src && dst && n > 0 && n % 8 == 0, "cast: n=%lld must be a positive multiple of 8", (long long)n);
   const long long t8 = n / 8;
   if (src_dtype == JPDSE_F32)
-    hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3(ew_blocks(t8)), dim3(256), 0, as_stream(stream), cptr<float>(src),
-                       mptr<bf16_t>(dst), t8);
-  else
-    hipLaunchKernelGGL(cast_bf16_f32_kernel, dim3(ew_blocks(t8)), dim3(256), 0, as_stream(stream), cptr<bf16_t>(src),
-                       mptr<float>(dst), t8);
-  return check_launch("cast");
+    return ew_launch("cast", cast_f32_bf16_kernel, t8, stream, cptr<float>(src), mptr<bf16_t>(dst), t8);
+  return ew_launch("cast", cast_bf16_f32_kernel, t8, stream, cptr<bf16_t>(src), mptr<float>(dst), t8);
 }
 
 size_t jpdse_quant_loss_workspace_size(void) { return kRedBlocks * sizeof(double); }
-
-}  // extern "C"
-
-template <typename TA, typename TB>
-static int quant_loss_launch(int mse, const void* a, const void* b, int C, int cs, long long npix, const QuantParams& qp,
-                             double* partial, int grid, hipStream_t s) {
-  if (mse)
-    hipLaunchKernelGGL((quant_loss_partial_kernel<TA, TB, RED_MSE>), dim3(grid), dim3(256), 0, s, cptr<TA>(a), cptr<TB>(b),
-                       C, cs, npix, qp, partial);
-  else
-    hipLaunchKernelGGL((quant_loss_partial_kernel<TA, TB, RED_L1>), dim3(grid), dim3(256), 0, s, cptr<TA>(a), cptr<TB>(b),
-                       C, cs, npix, qp, partial);
-  return check_launch("quant_loss");
-}
-
-extern "C" {
 
 int jpdse_quant_loss(int32_t dtype_a, int32_t dtype_b, int64_t npix, int32_t C, const void* a, const void* b,
                      const double* mean, const double* std, int32_t mse, float* out, void* ws, size_t ws_bytes,
@@ -1213,19 +1112,18 @@ int jpdse_quant_loss(int32_t dtype_a, int32_t dtype_b, int64_t npix, int32_t C, 
     return set_error(JPDSE_EWORKSPACE, "quant_loss: workspace too small");
   QuantParams qp = {};
   for (int c = 0; c < C; ++c) { qp.mean[c] = mean[c]; qp.std[c] = std[c]; }
-  int grid = ew_blocks(npix);
-  if (grid > kRedBlocks) grid = kRedBlocks;
-  double* partial = reinterpret_cast<double*>(ws);
-  hipStream_t s = as_stream(stream);
-  const int cs = cpad(C);
-  int rc;
-  if (dtype_a == JPDSE_BF16 && dtype_b == JPDSE_BF16) rc = quant_loss_launch<bf16_t, bf16_t>(mse, a, b, C, cs, npix, qp, partial, grid, s);
-  else if (dtype_a == JPDSE_BF16) rc = quant_loss_launch<bf16_t, float>(mse, a, b, C, cs, npix, qp, partial, grid, s);
-  else if (dtype_b == JPDSE_BF16) rc = quant_loss_launch<float, bf16_t>(mse, a, b, C, cs, npix, qp, partial, grid, s);
-  else rc = quant_loss_launch<float, float>(mse, a, b, C, cs, npix, qp, partial, grid, s);
-  if (rc) return rc;
-  hipLaunchKernelGGL(quant_loss_final_kernel, dim3(1), dim3(256), 0, s, partial, grid, 1.0 / ((double)npix * C), out);
-  return check_launch("quant_loss");
+  const int grid = jpdse_loss_partial_count(npix), cs = cpad(C);
+  double* partial = mptr<double>(ws);
+  if (int rc = by_dtype(dtype_a, [&](auto tag_a) {
+        return by_dtype(dtype_b, [&](auto tag_b) {
+          using TA = decltype(tag_a);
+          using TB = decltype(tag_b);
+          return launch256("quant_loss", mse ? quant_loss_partial_kernel<TA, TB, RED_MSE> : quant_loss_partial_kernel<TA, TB, RED_L1>,
+                           dim3(grid), stream, cptr<TA>(a), cptr<TB>(b), C, cs, npix, qp, partial);
+        });
+      }))
+    return rc;
+  return launch256("quant_loss", quant_loss_final_kernel, dim3(1), stream, partial, grid, 1.0 / ((double)npix * C), out);
 }
 
 }  // extern "C"

@@ -348,15 +348,12 @@ int jpdse_eval_metrics(int32_t dtype_fake, int32_t dtype_real, int32_t N, int32_
   const long long HW = (long long)H * W;
   const int cs = cpad(C);
 
-  if (dtype_fake == JPDSE_BF16)
-    hipLaunchKernelGGL((metrics_quant_kernel<bf16_t>), dim3(p.qblocks, N), dim3(256), 0, s,
-                       reinterpret_cast<const bf16_t*>(fake), reinterpret_cast<const float*>(real), cs, HW, qp, px, py,
-                       qpartial);
-  else
-    hipLaunchKernelGGL((metrics_quant_kernel<float>), dim3(p.qblocks, N), dim3(256), 0, s,
-                       reinterpret_cast<const float*>(fake), reinterpret_cast<const float*>(real), cs, HW, qp, px, py,
-                       qpartial);
-  if (int rc = check_launch("eval_metrics(quantise)")) return rc;
+  if (int rc = by_dtype(dtype_fake, [&](auto tag) {
+        using T = decltype(tag);
+        return launch256("eval_metrics(quantise)", metrics_quant_kernel<T>, dim3(p.qblocks, N), stream, cptr<T>(fake),
+                         cptr<float>(real), cs, HW, qp, px, py, qpartial);
+      }))
+    return rc;
   for (int j = 0; j < kMsScales; ++j) {
     const float* xj = px + p.plane_off[j];
     const float* yj = py + p.plane_off[j];

@@ -1,13 +1,16 @@
 // InstanceNorm2d(affine=False) fused with ReLU / LeakyReLU / residual add, forward and
-// backward, NHWC (reference: networks.py:31 and the activation sites listed in jpdse.h).
+// backward, NHWC (reference: networks.py:31 and the activation sites listed in jpdse.h).  HBM-bound.
 //
-// HBM-bound.  Per-(n,c) reductions run as: (1) a moment kernel in which each thread owns one
-// 16-byte channel vector column and walks pixels (coalesced: a pixel's channels are
-// contiguous), partial sums per pixel-split written to the workspace; (2) a tiny finalize
-// kernel (deterministic order, no atomics); (3) a fully parallel apply kernel.
-//
-// Tensors with few pixel splits per image (everything up to 67 MB in the bench step) take the register-held two-kernel
-// form further down: no finalize launch, its work folded into the apply kernel's prologue.
+// Forms, chosen per call by the host layer at the end of this file:
+//   * two register-held kernels (the shipped default; any tensor with <= 64 pixel splits per image, everything up to 67 MB in
+//     the bench step): a block keeps its pixels in registers, PHASE 1 writes a row of partial sums per block, PHASE 2 sums its
+//     group's rows in its prologue and applies;
+//   * three kernels (larger tensors; developer mode 27 everywhere): (1) a moment kernel in which each thread owns one 16-byte
+//     channel vector column and walks pixels (coalesced: a pixel's channels are contiguous), partial sums per pixel split
+//     written to the workspace; (2) a tiny finalize kernel (deterministic order, no atomics); (3) a fully parallel apply kernel;
+//   * one register-held kernel with an in-launch exchange (PHASE 0; developer mode 28 only);
+//   * statistics from the slots a conv epilogue wrote (jpdse_inorm_fwd_from_moments / _bwd_from_sums): one register-held
+//     kernel that merges the slots itself (PHASE 3), or a slot finalize kernel + the apply kernel of the three-kernel form.
 #include "common.h"
 #include <map>
 #include <mutex>
@@ -66,7 +69,7 @@ template <typename T> struct FwdMoments {
       s2[e] += d * d;
     }
   }
-  __device__ __forceinline__ void at(long long off, int, const float (&aux)[8], float (&s1)[8], float (&s2)[8]) const {
+  __device__ __forceinline__ void at(long long off, const float (&aux)[8], float (&s1)[8], float (&s2)[8]) const {
     float v[Vec16<T>::N];
     Vec16<T>::load(x + off, v);
     acc(v, aux, s1, s2);
@@ -91,20 +94,6 @@ template <typename T> struct BwdMoments {
 #pragma unroll
     for (int e = 0; e < Vec16<T>::N; ++e) {
       const float yh = (v[e] - mean[e]) * rstd[e];
-      const float dz = g[e] * act_grad(yh, act, slope);
-      s1[e] += dz;
-      s2[e] += dz * yh;
-    }
-  }
-  // aux packs mean[e] in [0..VE) -- rstd kept separately
-  __device__ __forceinline__ void at2(long long off, int n, int Cs, int c0, float (&s1)[8], float (&s2)[8]) const {
-    float v[Vec16<T>::N], g[Vec16<T>::N];
-    Vec16<T>::load(x + off, v);
-    Vec16<T>::load(dy + off, g);
-    const float* st = stats + ((long long)n * Cs + c0) * 2;
-#pragma unroll
-    for (int e = 0; e < Vec16<T>::N; ++e) {
-      const float yh = (v[e] - st[2 * e]) * st[2 * e + 1];
       const float dz = g[e] * act_grad(yh, act, slope);
       s1[e] += dz;
       s2[e] += dz * yh;
@@ -147,7 +136,7 @@ __global__ __launch_bounds__(256) void moment_kernel(const T* __restrict__ x, co
 #pragma unroll
         for (int u = 0; u < JPDSE_NORM_ILP; ++u) f.acc(v[u], aux, s1, s2);
       }
-      for (; p < p1; p += g.TY) f.at(base + (long long)p * g.Cs, 0, aux, s1, s2);
+      for (; p < p1; p += g.TY) f.at(base + (long long)p * g.Cs, aux, s1, s2);
     } else {
       BwdMoments<T> f{x, dy, stats, act, slope};
       float mean[VE], rstd[VE];
@@ -265,6 +254,14 @@ __global__ void finalize_bwd_kernel(const float* __restrict__ partial, float* __
   sums[2 * idx + 1] = b * inv;
 }
 
+// y = act((x - mean) * rstd): the forward's per-element expression (the residual is added by the caller)
+__device__ __forceinline__ float norm_act(float x, float mean, float rstd, int act, float slope) {
+  float t = (x - mean) * rstd;
+  if (act == JPDSE_ACT_RELU) t = t > 0.f ? t : 0.f;
+  else if (act == JPDSE_ACT_LRELU) t = t > 0.f ? t : t * slope;
+  return t;
+}
+
 // Apply kernels: same block decomposition as the moment kernel (one 16-byte channel-vector column per
 // lane, pixels walked with stride TY), so the per-channel constants are loaded once per thread and the
 // inner loop has no integer division; coalescing is along the contiguous channel axis.
@@ -307,9 +304,7 @@ __global__ __launch_bounds__(256) void inorm_apply_fwd_kernel(const T* __restric
       if (pu >= p1) break;
 #pragma unroll
       for (int e = 0; e < VE; ++e) {
-        float t = (v[u][e] - mean[e]) * rstd[e];
-        if (act == JPDSE_ACT_RELU) t = t > 0.f ? t : 0.f;
-        else if (act == JPDSE_ACT_LRELU) t = t > 0.f ? t : t * slope;
+        float t = norm_act(v[u][e], mean[e], rstd[e], act, slope);
         if (res != nullptr) t += r[u][e];
         v[u][e] = t;
       }
@@ -456,6 +451,15 @@ __device__ __forceinline__ float sum_rows(const float* rows, int splits, int nv)
   return total;
 }
 
+// PHASE 2: on return red[j] holds the group total of value j, summed from the rows PHASE 1 wrote
+__device__ __forceinline__ void group_totals(float* red, const float* partial, int grp, const FusedGeom& g) {
+  const int tid = threadIdx.x;
+  const float* rows = partial + (long long)grp * g.splits * g.nv;
+  const float total = tid < g.nv ? sum_rows<false>(rows + tid, g.splits, g.nv) : 0.f;
+  if (tid < g.nv) red[tid] = total;
+  __syncthreads();
+}
+
 // PHASE 0: on return red[j] holds the group total of value j.  `count`: one zeroed word per group, used once.
 template <int VE>
 __device__ __forceinline__ void exchange_totals(float* red, int* s_ctl, float tsum, float* partial, unsigned* count, int grp,
@@ -543,10 +547,7 @@ __global__ __launch_bounds__(256, 4) void inorm_reg_fwd_kernel(const T* __restri
     }
     __syncthreads();
   } else if constexpr (PHASE == 2) {
-    const float* rows = partial + (long long)grp * g.splits * g.nv;
-    const float total = tid < g.nv ? sum_rows<false>(rows + tid, g.splits, g.nv) : 0.f;
-    if (tid < g.nv) red[tid] = total;
-    __syncthreads();
+    group_totals(red, partial, grp, g);
   } else {
 #pragma unroll
     for (int i = 0; i < P; ++i) {
@@ -600,9 +601,7 @@ __global__ __launch_bounds__(256, 4) void inorm_reg_fwd_kernel(const T* __restri
       if (res != nullptr) Vec16<T>::load(res + off, r);
 #pragma unroll
       for (int e = 0; e < VE; ++e) {
-        float t = (v[e] - mean[e]) * rstd[e];
-        if (act == JPDSE_ACT_RELU) t = t > 0.f ? t : 0.f;
-        else if (act == JPDSE_ACT_LRELU) t = t > 0.f ? t : t * slope;
+        float t = norm_act(v[e], mean[e], rstd[e], act, slope);
         if (res != nullptr) t += r[e];
         v[e] = t;
       }
@@ -667,10 +666,7 @@ __global__ __launch_bounds__(256, (P == 8 ? 3 : 2)) void inorm_reg_bwd_kernel(co
     }
     __syncthreads();
   } else if constexpr (PHASE == 2) {
-    const float* rows = partial + (long long)grp * g.splits * g.nv;
-    const float total = tid < g.nv ? sum_rows<false>(rows + tid, g.splits, g.nv) : 0.f;
-    if (tid < g.nv) red[tid] = total;
-    __syncthreads();
+    group_totals(red, partial, grp, g);
   } else {
 #pragma unroll
     for (int i = 0; i < P; ++i) {
@@ -788,165 +784,13 @@ template <typename T, bool BWD> static int reg_pick(const jpdse_inorm_desc* d, b
 }
 
 static size_t reg_ws_bytes(const jpdse_inorm_desc* d) {
-  // sized for either P (P = 8 has the larger split count); 0 when the register-held forms do not apply
-  const int VE = d->dtype == JPDSE_BF16 ? 8 : 4;
-  const FusedGeom g = fused_geom(d->N, d->H * d->W, cpad(d->C), VE, 8);
+  // Rows of the register-held forms, counted with P = 8 (the larger split count); 0 when they do not apply.  The bound is 128
+  // splits although reg_pick admits 64: the one-kernel form may hold 16 pixels per thread, and its 64 splits are 128 at P = 8.
+  // jpdse_inorm_workspace_size reports this number, so it stays as it is.
+  const FusedGeom g = fused_geom(d->N, d->H * d->W, cpad(d->C), vec_elems(d->dtype), 8);
   if (g.splits > 128) return 0;
   return align_up((size_t)d->N * g.col_blocks * g.splits * g.nv * sizeof(float), 256);
 }
-
-template <typename T, int P>
-static int launch_reg_fwd(int form, const FusedGeom& fg, const jpdse_inorm_desc* d, const void* x, const void* res, void* y,
-                          float* stats, float* part, unsigned* count, hipStream_t s) {
-  const dim3 grid((unsigned)((size_t)d->N * fg.col_blocks * fg.splits));
-  const T* xp = reinterpret_cast<const T*>(x);
-  const T* rp = reinterpret_cast<const T*>(res);
-  T* yp = reinterpret_cast<T*>(y);
-#ifdef JPDSE_DEV
-  if (form == 2) {
-    hipLaunchKernelGGL((inorm_reg_fwd_kernel<T, P, 0>), grid, dim3(256), 0, s, xp, rp, yp, stats, part, count, d->act, d->slope,
-                       d->eps, fg);
-    return check_launch("inorm one-kernel fwd");
-  }
-#endif
-  hipLaunchKernelGGL((inorm_reg_fwd_kernel<T, P, 1>), grid, dim3(256), 0, s, xp, rp, yp, stats, part, count, d->act, d->slope,
-                     d->eps, fg);
-  if (int rc = check_launch("inorm rows fwd")) return rc;
-  hipLaunchKernelGGL((inorm_reg_fwd_kernel<T, P, 2>), grid, dim3(256), 0, s, xp, rp, yp, stats, part, count, d->act, d->slope,
-                     d->eps, fg);
-  return check_launch("inorm apply-from-rows fwd");
-}
-
-template <typename T, int P>
-static int launch_reg_bwd(int form, const FusedGeom& fg, const jpdse_inorm_desc* d, const void* x, const float* stats,
-                          const void* dy, void* dx, float* part, unsigned* count, hipStream_t s) {
-  const dim3 grid((unsigned)((size_t)d->N * fg.col_blocks * fg.splits));
-  const T* xp = reinterpret_cast<const T*>(x);
-  const T* gp = reinterpret_cast<const T*>(dy);
-  T* dp = reinterpret_cast<T*>(dx);
-#ifdef JPDSE_DEV
-  if (form == 2) {
-    hipLaunchKernelGGL((inorm_reg_bwd_kernel<T, P, 0>), grid, dim3(256), 0, s, xp, gp, dp, stats, part, count, d->act, d->slope,
-                       fg);
-    return check_launch("inorm one-kernel bwd");
-  }
-#endif
-  hipLaunchKernelGGL((inorm_reg_bwd_kernel<T, P, 1>), grid, dim3(256), 0, s, xp, gp, dp, stats, part, count, d->act, d->slope, fg);
-  if (int rc = check_launch("inorm rows bwd")) return rc;
-  hipLaunchKernelGGL((inorm_reg_bwd_kernel<T, P, 2>), grid, dim3(256), 0, s, xp, gp, dp, stats, part, count, d->act, d->slope, fg);
-  return check_launch("inorm apply-from-rows bwd");
-}
-
-// 1 = handled by a register-held form, 0 = not applicable, < 0 = error
-template <typename T>
-static int try_reg_fwd(const jpdse_inorm_desc* d, const void* x, const void* res, void* y, float* stats, void* ws,
-                       hipStream_t s) {
-  int form = norm_form();
-  if (form == 0) return 0;
-  FusedGeom fg;
-  int P = reg_pick<T, false>(d, form == 2, &fg);
-  if (P == 0 && form == 2) { form = 1; P = reg_pick<T, false>(d, false, &fg); }
-  if (P == 0) return 0;
-  unsigned* count = nullptr;
-  if (form == 2 && fg.splits > 1) {
-    count = count_slots(s, d->N * fg.col_blocks);
-    if (count == nullptr) form = 1;
-  }
-  float* part = reinterpret_cast<float*>(ws);
-  const int rc = P == 8 ? launch_reg_fwd<T, 8>(form, fg, d, x, res, y, stats, part, count, s)
-                        : launch_reg_fwd<T, 16>(form, fg, d, x, res, y, stats, part, count, s);
-  return rc == JPDSE_OK ? 1 : -1;
-}
-
-template <typename T>
-static int try_reg_bwd(const jpdse_inorm_desc* d, const void* x, const float* stats, const void* dy, void* dx, void* ws,
-                       hipStream_t s) {
-  int form = norm_form();
-  if (form == 0) return 0;
-  FusedGeom fg;
-  int P = reg_pick<T, true>(d, form == 2, &fg);
-  if (P == 0 && form == 2) { form = 1; P = reg_pick<T, true>(d, false, &fg); }
-  if (P == 0) return 0;
-  unsigned* count = nullptr;
-  if (form == 2 && fg.splits > 1) {
-    count = count_slots(s, d->N * fg.col_blocks);
-    if (count == nullptr) form = 1;
-  }
-  float* part = reinterpret_cast<float*>(ws);
-  const int rc = P == 8 ? launch_reg_bwd<T, 8>(form, fg, d, x, stats, dy, dx, part, count, s)
-                        : launch_reg_bwd<T, 16>(form, fg, d, x, stats, dy, dx, part, count, s);
-  return rc == JPDSE_OK ? 1 : -1;
-}
-
-static int validate(const jpdse_inorm_desc* d) {
-  JPDSE_REQUIRE(d != nullptr, "inorm: null descriptor");
-  JPDSE_REQUIRE(d->dtype == JPDSE_F32 || d->dtype == JPDSE_BF16, "inorm: bad dtype");
-  JPDSE_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->C > 0, "inorm: non-positive shape");
-  JPDSE_REQUIRE(d->act == JPDSE_ACT_NONE || d->act == JPDSE_ACT_RELU || d->act == JPDSE_ACT_LRELU,
-                "inorm: unsupported activation %d", d->act);
-  return JPDSE_OK;
-}
-
-static size_t ws_bytes_for(const jpdse_inorm_desc* d) {
-  const int VE = d->dtype == JPDSE_BF16 ? 8 : 4;
-  MomentGeom g = moment_geom(d->N, d->H * d->W, cpad(d->C), VE);
-  const size_t partial = (size_t)d->N * g.splits * g.Cs * 2 * sizeof(float);
-  const size_t sums = (size_t)d->N * g.Cs * 2 * sizeof(float);
-  const size_t three = align_up(partial, 256) + align_up(sums, 256), one = reg_ws_bytes(d);
-  return three > one ? three : one;
-}
-
-template <typename T>
-static int inorm_fwd_t(const jpdse_inorm_desc* d, const void* x, const void* res, void* y, float* stats, void* ws,
-                       hipStream_t s) {
-  constexpr int VE = Vec16<T>::N;
-  const int HW = d->H * d->W, Cs = cpad(d->C);
-  {
-    const int r = try_reg_fwd<T>(d, x, res, y, stats, ws, s);
-    if (r != 0) return r > 0 ? JPDSE_OK : JPDSE_ELAUNCH;
-  }
-  MomentGeom g = moment_geom(d->N, HW, Cs, VE);
-  float* partial = reinterpret_cast<float*>(ws);
-  const int col_blocks = (g.cv + g.TX - 1) / g.TX;
-  hipLaunchKernelGGL((moment_kernel<T, false>), dim3(d->N * g.splits * col_blocks), dim3(256), 0, s,
-                     reinterpret_cast<const T*>(x), (const T*)nullptr, (const float*)nullptr, 0, 0.f, partial, g);
-  if (int rc = check_launch("inorm moment fwd")) return rc;
-  hipLaunchKernelGGL((finalize_fwd_kernel<T>), dim3((d->N * Cs * 8 + 255) / 256), dim3(256), 0, s,
-                     reinterpret_cast<const T*>(x), partial, stats, d->N, HW, Cs, g.splits, d->eps);
-  if (int rc = check_launch("inorm finalize fwd")) return rc;
-  hipLaunchKernelGGL((inorm_apply_fwd_kernel<T>), dim3(d->N * g.splits * col_blocks), dim3(256), 0, s,
-                     reinterpret_cast<const T*>(x), reinterpret_cast<const T*>(res), reinterpret_cast<T*>(y), stats,
-                     d->act, d->slope, g);
-  return check_launch("inorm apply fwd");
-}
-
-template <typename T>
-static int inorm_bwd_t(const jpdse_inorm_desc* d, const void* x, const float* stats, const void* dy, void* dx,
-                       void* ws, hipStream_t s) {
-  constexpr int VE = Vec16<T>::N;
-  const int HW = d->H * d->W, Cs = cpad(d->C);
-  {
-    const int r = try_reg_bwd<T>(d, x, stats, dy, dx, ws, s);
-    if (r != 0) return r > 0 ? JPDSE_OK : JPDSE_ELAUNCH;
-  }
-  MomentGeom g = moment_geom(d->N, HW, Cs, VE);
-  float* partial = reinterpret_cast<float*>(ws);
-  float* sums = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) +
-                                         align_up((size_t)d->N * g.splits * g.Cs * 2 * sizeof(float), 256));
-  const int col_blocks = (g.cv + g.TX - 1) / g.TX;
-  hipLaunchKernelGGL((moment_kernel<T, true>), dim3(d->N * g.splits * col_blocks), dim3(256), 0, s,
-                     reinterpret_cast<const T*>(x), reinterpret_cast<const T*>(dy), stats, d->act, d->slope,
-                     partial, g);
-  if (int rc = check_launch("inorm moment bwd")) return rc;
-  hipLaunchKernelGGL(finalize_bwd_kernel, dim3((d->N * Cs * 8 + 255) / 256), dim3(256), 0, s, partial, sums, d->N, HW,
-                     Cs, g.splits);
-  if (int rc = check_launch("inorm finalize bwd")) return rc;
-  hipLaunchKernelGGL((inorm_apply_bwd_kernel<T>), dim3(d->N * g.splits * col_blocks), dim3(256), 0, s,
-                     reinterpret_cast<const T*>(x), reinterpret_cast<const T*>(dy), reinterpret_cast<T*>(dx), stats,
-                     sums, d->act, d->slope, g);
-  return check_launch("inorm apply bwd");
-}
-
 
 // Forward statistics from per-block moments written by a conv epilogue: moments[n][c][slot] = (mean, M2) of the block's
 // (bf16-rounded) values, every slot over the same number of pixels HW / slots (common.h).  One wave per (n, c) merges them with
@@ -1012,71 +856,188 @@ __global__ __launch_bounds__(256) void finalize_bwd_slots_kernel(const float* __
   sums[2 * idx + 1] = b * inv;
 }
 
-template <typename T>
-static int inorm_bwd_from_sums_t(const jpdse_inorm_desc* d, const void* x, const float* stats, const void* dy, const float* slot_sums,
-                                 int slots, void* dx, void* ws, hipStream_t s) {
-  constexpr int VE = Vec16<T>::N;
-  const int HW = d->H * d->W, Cs = cpad(d->C);
-  if (norm_form() != 0 && slots <= 64) {
-    FusedGeom fg;
-    const int P = reg_pick<T, true>(d, false, &fg);
-    if (P == 8) {
-      const dim3 grid((unsigned)((size_t)d->N * fg.col_blocks * fg.splits));
-      hipLaunchKernelGGL((inorm_reg_bwd_kernel<T, 8, 3>), grid, dim3(256), 0, s, reinterpret_cast<const T*>(x),
-                         reinterpret_cast<const T*>(dy), reinterpret_cast<T*>(dx), stats, const_cast<float*>(slot_sums), nullptr,
-                         d->act, d->slope, fg, slots);
-      return check_launch("inorm apply-from-slots bwd");
-    }
-  }
-  float* const sums = reinterpret_cast<float*>(ws);
-  const int NC = d->N * Cs;
-  hipLaunchKernelGGL(finalize_bwd_slots_kernel, dim3((NC * 8 + 255) / 256), dim3(256), 0, s, slot_sums, sums, NC, slots, HW);
-  if (int rc = check_launch("inorm finalize bwd from slots")) return rc;
-  MomentGeom g = moment_geom(d->N, HW, Cs, VE);
-  const int col_blocks = (g.cv + g.TX - 1) / g.TX;
-  hipLaunchKernelGGL((inorm_apply_bwd_kernel<T>), dim3(d->N * g.splits * col_blocks), dim3(256), 0, s,
-                     reinterpret_cast<const T*>(x), reinterpret_cast<const T*>(dy), reinterpret_cast<T*>(dx), stats,
-                     sums, d->act, d->slope, g);
-  return check_launch("inorm apply bwd");
+// ---- host layer -----------------------------------------------------------------------------------------------------------
+// One norm call: forward in2 = the residual (or null) and out = y; backward in2 = dy and out = dx.
+struct NormCall {
+  const jpdse_inorm_desc* d;
+  const void* x;
+  const void* in2;
+  void* out;
+  float* stats;          // written by the forward, read by the backward
+  void* stream;
+};
+
+static MomentGeom moment_geom(const jpdse_inorm_desc* d) {
+  return moment_geom(d->N, d->H * d->W, cpad(d->C), vec_elems(d->dtype));
+}
+// grid of the MomentGeom kernels (moment_kernel, inorm_apply_*): a block per (image, pixel split, TX channel columns)
+static dim3 moment_grid(const MomentGeom& g) { return dim3(g.N * g.splits * ((g.cv + g.TX - 1) / g.TX)); }
+// grid of the kernels that give 8 lanes to each (image, channel): the finalize kernels
+static dim3 lanes8_grid(const jpdse_inorm_desc* d) { return dim3((d->N * cpad(d->C) * 8 + 255) / 256); }
+static dim3 fused_grid(const FusedGeom& g) { return dim3((unsigned)((size_t)g.N * g.col_blocks * g.splits)); }
+
+// Workspace of moment -> finalize -> apply: the partials [N][splits][Cs][2], then the backward's sums [N][Cs][2], each region
+// rounded up to 256 bytes.  jpdse_inorm_bwd_from_sums needs the sums region alone, at offset 0.
+static size_t ws_sums_bytes(const jpdse_inorm_desc* d) { return align_up((size_t)d->N * cpad(d->C) * 2 * sizeof(float), 256); }
+static size_t ws_sums_offset(const jpdse_inorm_desc* d, const MomentGeom& g) {
+  return align_up((size_t)d->N * g.splits * g.Cs * 2 * sizeof(float), 256);
+}
+static size_t ws_bytes_for(const jpdse_inorm_desc* d) {
+  const size_t three = ws_sums_offset(d, moment_geom(d)) + ws_sums_bytes(d), reg = reg_ws_bytes(d);
+  return three > reg ? three : reg;
 }
 
-template <typename T>
-static int inorm_from_moments_t(const jpdse_inorm_desc* d, const void* x, const float* mom, int slots, const void* res, void* y,
-                                float* stats, hipStream_t s) {
-  constexpr int VE = Vec16<T>::N;
-  const int HW = d->H * d->W, Cs = cpad(d->C);
-  const int NC = d->N * Cs;
-  // tensors the register-held form covers (<= 64 pixel splits, e.g. the ResnetBlock norms) and few slots: ONE kernel, every
-  // block merges its channels' slots itself
-  if (norm_form() != 0 && slots <= 64) {
-    FusedGeom fg;
-    const int P = reg_pick<T, false>(d, false, &fg);
-    if (P == 8) {
-      const dim3 grid((unsigned)((size_t)d->N * fg.col_blocks * fg.splits));
-      hipLaunchKernelGGL((inorm_reg_fwd_kernel<T, 8, 3>), grid, dim3(256), 0, s, reinterpret_cast<const T*>(x),
-                         reinterpret_cast<const T*>(res), reinterpret_cast<T*>(y), stats, const_cast<float*>(mom), nullptr,
-                         d->act, d->slope, d->eps, fg, slots);
-      return check_launch("inorm apply-from-slots fwd");
-    }
+// inorm_reg_{fwd,bwd}_kernel<T, P, PHASE>.  `part`: the partial rows (PHASE 0-2) or the producer's `mslots` slots (PHASE 3).
+template <typename T, int P, int PHASE, bool BWD>
+static int launch_reg(const NormCall& c, const FusedGeom& fg, float* part, unsigned* count, int mslots = 0) {
+  static const char* const what[2][4] = {
+      {"inorm one-kernel fwd", "inorm rows fwd", "inorm apply-from-rows fwd", "inorm apply-from-slots fwd"},
+      {"inorm one-kernel bwd", "inorm rows bwd", "inorm apply-from-rows bwd", "inorm apply-from-slots bwd"}};
+  const jpdse_inorm_desc* d = c.d;
+  if constexpr (BWD)
+    return launch256(what[1][PHASE], inorm_reg_bwd_kernel<T, P, PHASE>, fused_grid(fg), c.stream, cptr<T>(c.x), cptr<T>(c.in2),
+                     mptr<T>(c.out), c.stats, part, count, d->act, d->slope, fg, mslots);
+  else
+    return launch256(what[0][PHASE], inorm_reg_fwd_kernel<T, P, PHASE>, fused_grid(fg), c.stream, cptr<T>(c.x), cptr<T>(c.in2),
+                     mptr<T>(c.out), c.stats, part, count, d->act, d->slope, d->eps, fg, mslots);
+}
+
+// form 2: the one kernel (developer build only); form 1: rows, then apply-from-rows
+template <typename T, int P, bool BWD>
+static int launch_reg_form(int form, const NormCall& c, const FusedGeom& fg, float* part, unsigned* count) {
+#ifdef JPDSE_DEV
+  if (form == 2) return launch_reg<T, P, 0, BWD>(c, fg, part, count);
+#endif
+  if (int rc = launch_reg<T, P, 1, BWD>(c, fg, part, count)) return rc;
+  return launch_reg<T, P, 2, BWD>(c, fg, part, count);
+}
+
+constexpr int kNoRegForm = 1;      // returned by the two routines below when the register-held forms do not cover the call
+
+// The register-held forms, in the order one kernel (form 2, when the grid is resident and count words are to be had) ->
+// two kernels (form 1) -> kNoRegForm: the caller runs moment -> finalize -> apply.  Otherwise the launch's return code.
+template <typename T, bool BWD> static int try_reg(const NormCall& c, void* ws) {
+  int form = norm_form();
+  if (form == 0) return kNoRegForm;
+  FusedGeom fg;
+  int P = reg_pick<T, BWD>(c.d, form == 2, &fg);
+  if (P == 0 && form == 2) { form = 1; P = reg_pick<T, BWD>(c.d, false, &fg); }
+  if (P == 0) return kNoRegForm;
+  unsigned* count = nullptr;
+  if (form == 2 && fg.splits > 1) {
+    count = count_slots(as_stream(c.stream), c.d->N * fg.col_blocks);
+    if (count == nullptr) form = 1;
   }
-  hipLaunchKernelGGL(finalize_slots_kernel, dim3((NC + 3) / 4), dim3(256), 0, s, mom, stats, NC, slots, HW, d->eps);
-  if (int rc = check_launch("inorm finalize from moments")) return rc;
-  MomentGeom g = moment_geom(d->N, HW, Cs, VE);
-  const int col_blocks = (g.cv + g.TX - 1) / g.TX;
-  hipLaunchKernelGGL((inorm_apply_fwd_kernel<T>), dim3(d->N * g.splits * col_blocks), dim3(256), 0, s,
-                     reinterpret_cast<const T*>(x), reinterpret_cast<const T*>(res), reinterpret_cast<T*>(y), stats,
-                     d->act, d->slope, g);
-  return check_launch("inorm apply fwd");
+  float* part = mptr<float>(ws);
+  return P == 8 ? launch_reg_form<T, 8, BWD>(form, c, fg, part, count) : launch_reg_form<T, 16, BWD>(form, c, fg, part, count);
+}
+
+// PHASE 3, ONE kernel per norm: every block merges the producer's slots of its channels itself and applies.  For tensors the
+// two-kernel form covers with 8 pixels per thread (e.g. the ResnetBlock norms) and at most 64 slots per (image, channel).
+template <typename T, bool BWD> static int try_reg_from_slots(const NormCall& c, const float* slots_in, int slots) {
+  FusedGeom fg;
+  if (norm_form() == 0 || slots > 64 || reg_pick<T, BWD>(c.d, false, &fg) != 8) return kNoRegForm;
+  return launch_reg<T, 8, 3, BWD>(c, fg, const_cast<float*>(slots_in), nullptr, slots);
+}
+
+// third kernel of moment -> finalize -> apply; `sums`: backward only
+template <typename T, bool BWD> static int launch_apply(const NormCall& c, const MomentGeom& g, const float* sums = nullptr) {
+  if constexpr (BWD)
+    return launch256("inorm apply bwd", inorm_apply_bwd_kernel<T>, moment_grid(g), c.stream, cptr<T>(c.x), cptr<T>(c.in2),
+                     mptr<T>(c.out), c.stats, sums, c.d->act, c.d->slope, g);
+  else
+    return launch256("inorm apply fwd", inorm_apply_fwd_kernel<T>, moment_grid(g), c.stream, cptr<T>(c.x), cptr<T>(c.in2),
+                     mptr<T>(c.out), c.stats, c.d->act, c.d->slope, g);
+}
+
+template <typename T> static int inorm_fwd_t(const NormCall& c, void* ws) {
+  if (const int r = try_reg<T, false>(c, ws); r != kNoRegForm) return r;
+  const jpdse_inorm_desc* d = c.d;
+  const MomentGeom g = moment_geom(d);
+  float* partial = mptr<float>(ws);
+  if (int rc = launch256("inorm moment fwd", moment_kernel<T, false>, moment_grid(g), c.stream, cptr<T>(c.x), nullptr, nullptr, 0,
+                         0.f, partial, g))
+    return rc;
+  if (int rc = launch256("inorm finalize fwd", finalize_fwd_kernel<T>, lanes8_grid(d), c.stream, cptr<T>(c.x), partial, c.stats,
+                         d->N, g.HW, g.Cs, g.splits, d->eps))
+    return rc;
+  return launch_apply<T, false>(c, g);
+}
+
+template <typename T> static int inorm_bwd_t(const NormCall& c, void* ws) {
+  if (const int r = try_reg<T, true>(c, ws); r != kNoRegForm) return r;
+  const jpdse_inorm_desc* d = c.d;
+  const MomentGeom g = moment_geom(d);
+  float* partial = mptr<float>(ws);
+  float* sums = reinterpret_cast<float*>(mptr<char>(ws) + ws_sums_offset(d, g));
+  if (int rc = launch256("inorm moment bwd", moment_kernel<T, true>, moment_grid(g), c.stream, cptr<T>(c.x), cptr<T>(c.in2),
+                         c.stats, d->act, d->slope, partial, g))
+    return rc;
+  if (int rc = launch256("inorm finalize bwd", finalize_bwd_kernel, lanes8_grid(d), c.stream, partial, sums, d->N, g.HW, g.Cs,
+                         g.splits))
+    return rc;
+  return launch_apply<T, true>(c, g, sums);
+}
+
+template <typename T> static int inorm_bwd_from_sums_t(const NormCall& c, const float* slot_sums, int slots, void* ws) {
+  if (const int r = try_reg_from_slots<T, true>(c, slot_sums, slots); r != kNoRegForm) return r;
+  const jpdse_inorm_desc* d = c.d;
+  float* const sums = mptr<float>(ws);
+  if (int rc = launch256("inorm finalize bwd from slots", finalize_bwd_slots_kernel, lanes8_grid(d), c.stream, slot_sums, sums,
+                         d->N * cpad(d->C), slots, d->H * d->W))
+    return rc;
+  return launch_apply<T, true>(c, moment_geom(d), sums);
+}
+
+template <typename T> static int inorm_from_moments_t(const NormCall& c, const float* mom, int slots) {
+  if (const int r = try_reg_from_slots<T, false>(c, mom, slots); r != kNoRegForm) return r;
+  const jpdse_inorm_desc* d = c.d;
+  const int NC = d->N * cpad(d->C);
+  if (int rc = launch256("inorm finalize from moments", finalize_slots_kernel, dim3((NC + 3) / 4), c.stream, mom, c.stats, NC,
+                         slots, d->H * d->W, d->eps))
+    return rc;
+  return launch_apply<T, false>(c, moment_geom(d));
+}
+
+static int validate(const jpdse_inorm_desc* d) {
+  JPDSE_REQUIRE(d != nullptr, "inorm: null descriptor");
+  JPDSE_REQUIRE(d->dtype == JPDSE_F32 || d->dtype == JPDSE_BF16, "inorm: bad dtype");
+  JPDSE_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->C > 0, "inorm: non-positive shape");
+  JPDSE_REQUIRE(d->act == JPDSE_ACT_NONE || d->act == JPDSE_ACT_RELU || d->act == JPDSE_ACT_LRELU,
+                "inorm: unsupported activation %d", d->act);
+  return JPDSE_OK;
+}
+
+// Prologue of the four launching entry points: descriptor, the call's own pointer check (`args_ok`, refused as `args_what`),
+// the residual (forward calls pass theirs: it comes back null unless the descriptor has one) and the workspace.
+enum NormWs { WS_NONE, WS_FULL, WS_SUMS };
+static int inorm_enter(const char* name, const jpdse_inorm_desc* d, bool args_ok, const char* args_what, const void** residual,
+                       NormWs kind, const void* ws, size_t ws_bytes) {
+  if (int rc = validate(d)) return rc;
+  JPDSE_REQUIRE(args_ok, "%s: %s", name, args_what);
+  if (residual != nullptr) {
+    JPDSE_REQUIRE(!d->has_residual || *residual, "%s: has_residual set but residual is null", name);
+    if (!d->has_residual) *residual = nullptr;
+  }
+  if (kind != WS_NONE) {
+    const size_t need = kind == WS_FULL ? ws_bytes_for(d) : ws_sums_bytes(d);
+    if (ws == nullptr || ws_bytes < need) return set_error(JPDSE_EWORKSPACE, "%s: workspace %zu < %zu", name, ws_bytes, need);
+  }
+  return JPDSE_OK;
+}
+
+// run(T{}) for the descriptor's dtype between hbm_prof_begin / _end (jpdse_prof_hbm_*): class `cls`, algorithmic bytes =
+// `tensors` x one [N][H][W][CPAD(C)] tensor of that dtype
+template <typename F> static int timed_by_dtype(const jpdse_inorm_desc* d, void* stream, int cls, double tensors, F&& run) {
+  const int pslot = hbm_prof_begin(as_stream(stream));
+  const int rc = by_dtype(d->dtype, run);
+  hbm_prof_end(pslot, cls, (double)d->N * d->H * d->W * cpad(d->C) * (double)esize(d->dtype) * tensors, as_stream(stream));
+  return rc;
 }
 
 }  // namespace jpdse
 
 using namespace jpdse;
-
-// bytes of one [N][H][W][CPAD(C)] tensor of the descriptor's dtype (the unit of the algorithmic byte counts of jpdse_prof_hbm_*)
-static double tensor_bytes(const jpdse_inorm_desc* d) {
-  return (double)d->N * d->H * d->W * cpad(d->C) * (double)esize(d->dtype);
-}
 
 extern "C" {
 
@@ -1087,56 +1048,37 @@ size_t jpdse_inorm_workspace_size(const jpdse_inorm_desc* d) {
 
 int jpdse_inorm_fwd(const jpdse_inorm_desc* d, const void* x, const void* residual, void* y, float* stats, void* ws,
                     size_t ws_bytes, void* stream) {
-  if (int rc = jpdse::validate(d)) return rc;
-  JPDSE_REQUIRE(x && y && stats, "inorm_fwd: null pointer");
-  JPDSE_REQUIRE(!d->has_residual || residual, "inorm_fwd: has_residual set but residual is null");
-  if (ws == nullptr || ws_bytes < ws_bytes_for(d))
-    return set_error(JPDSE_EWORKSPACE, "inorm_fwd: workspace %zu < %zu", ws_bytes, ws_bytes_for(d));
-  const void* res = d->has_residual ? residual : nullptr;
-  const int pslot = hbm_prof_begin(as_stream(stream));
-  const int rc = d->dtype == JPDSE_BF16 ? inorm_fwd_t<bf16_t>(d, x, res, y, stats, ws, as_stream(stream))
-                                        : inorm_fwd_t<float>(d, x, res, y, stats, ws, as_stream(stream));
-  hbm_prof_end(pslot, JPDSE_HBM_INORM_FWD, tensor_bytes(d) * (d->has_residual ? 4.0 : 3.0), as_stream(stream));
-  return rc;
+  if (int rc = inorm_enter("inorm_fwd", d, x && y && stats, "null pointer", &residual, WS_FULL, ws, ws_bytes)) return rc;
+  const NormCall c = {d, x, residual, y, stats, stream};
+  return timed_by_dtype(d, stream, JPDSE_HBM_INORM_FWD, d->has_residual ? 4.0 : 3.0,
+                        [&](auto tag) { return inorm_fwd_t<decltype(tag)>(c, ws); });
 }
 
 int jpdse_inorm_bwd(const jpdse_inorm_desc* d, const void* x, const float* stats, const void* dy, void* dx, void* ws,
                     size_t ws_bytes, void* stream) {
-  if (int rc = jpdse::validate(d)) return rc;
-  JPDSE_REQUIRE(x && stats && dy && dx, "inorm_bwd: null pointer");
-  if (ws == nullptr || ws_bytes < ws_bytes_for(d))
-    return set_error(JPDSE_EWORKSPACE, "inorm_bwd: workspace %zu < %zu", ws_bytes, ws_bytes_for(d));
-  const int pslot = hbm_prof_begin(as_stream(stream));
-  const int rc = d->dtype == JPDSE_BF16 ? inorm_bwd_t<bf16_t>(d, x, stats, dy, dx, ws, as_stream(stream))
-                                        : inorm_bwd_t<float>(d, x, stats, dy, dx, ws, as_stream(stream));
-  hbm_prof_end(pslot, JPDSE_HBM_INORM_BWD, tensor_bytes(d) * 5.0, as_stream(stream));
-  return rc;
+  if (int rc = inorm_enter("inorm_bwd", d, x && stats && dy && dx, "null pointer", nullptr, WS_FULL, ws, ws_bytes)) return rc;
+  const NormCall c = {d, x, dy, dx, const_cast<float*>(stats), stream};
+  return timed_by_dtype(d, stream, JPDSE_HBM_INORM_BWD, 5.0, [&](auto tag) { return inorm_bwd_t<decltype(tag)>(c, ws); });
 }
 
 int jpdse_inorm_bwd_from_sums(const jpdse_inorm_desc* d, const void* x, const float* stats, const void* dy, const float* sums,
                               int32_t slots, void* dx, void* ws, size_t ws_bytes, void* stream) {
-  if (int rc = jpdse::validate(d)) return rc;
-  JPDSE_REQUIRE(x && stats && dy && dx && sums && slots > 0, "inorm_bwd_from_sums: null pointer / no slots");
-  const size_t need = align_up((size_t)d->N * cpad(d->C) * 2 * sizeof(float), 256);
-  if (ws == nullptr || ws_bytes < need) return set_error(JPDSE_EWORKSPACE, "inorm_bwd_from_sums: workspace %zu < %zu", ws_bytes, need);
-  const int pslot = hbm_prof_begin(as_stream(stream));
-  const int rc = d->dtype == JPDSE_BF16 ? inorm_bwd_from_sums_t<bf16_t>(d, x, stats, dy, sums, slots, dx, ws, as_stream(stream))
-                                        : inorm_bwd_from_sums_t<float>(d, x, stats, dy, sums, slots, dx, ws, as_stream(stream));
-  hbm_prof_end(pslot, JPDSE_HBM_INORM_BWD, tensor_bytes(d) * 3.0, as_stream(stream));      // x, dy read once, dx written
-  return rc;
+  if (int rc = inorm_enter("inorm_bwd_from_sums", d, x && stats && dy && dx && sums && slots > 0, "null pointer / no slots",
+                           nullptr, WS_SUMS, ws, ws_bytes))
+    return rc;
+  const NormCall c = {d, x, dy, dx, const_cast<float*>(stats), stream};
+  return timed_by_dtype(d, stream, JPDSE_HBM_INORM_BWD, 3.0,        // x, dy read once, dx written
+                        [&](auto tag) { return inorm_bwd_from_sums_t<decltype(tag)>(c, sums, slots, ws); });
 }
 
 int jpdse_inorm_fwd_from_moments(const jpdse_inorm_desc* d, const void* x, const float* moments, int32_t slots,
                                  const void* residual, void* y, float* stats, void* stream) {
-  if (int rc = jpdse::validate(d)) return rc;
-  JPDSE_REQUIRE(x && y && stats && moments && slots > 0, "inorm_fwd_from_moments: null pointer / no slots");
-  JPDSE_REQUIRE(!d->has_residual || residual, "inorm_fwd_from_moments: has_residual set but residual is null");
-  const void* res = d->has_residual ? residual : nullptr;
-  const int pslot = hbm_prof_begin(as_stream(stream));
-  const int rc = d->dtype == JPDSE_BF16 ? inorm_from_moments_t<bf16_t>(d, x, moments, slots, res, y, stats, as_stream(stream))
-                                        : inorm_from_moments_t<float>(d, x, moments, slots, res, y, stats, as_stream(stream));
-  hbm_prof_end(pslot, JPDSE_HBM_INORM_FWD, tensor_bytes(d) * (d->has_residual ? 3.0 : 2.0), as_stream(stream));
-  return rc;
+  if (int rc = inorm_enter("inorm_fwd_from_moments", d, x && y && stats && moments && slots > 0, "null pointer / no slots",
+                           &residual, WS_NONE, nullptr, 0))
+    return rc;
+  const NormCall c = {d, x, residual, y, stats, stream};
+  return timed_by_dtype(d, stream, JPDSE_HBM_INORM_FWD, d->has_residual ? 3.0 : 2.0,
+                        [&](auto tag) { return inorm_from_moments_t<decltype(tag)>(c, moments, slots); });
 }
 
 }  // extern "C"
