@@ -35,8 +35,8 @@ extern "C" {
 #define JPDSE_ABI_VERSION 2   /* 2 (round 4): + jpdse_conv_dgrad_nsum_slots / _fused_nsums, jpdse_inorm_bwd_from_sums; round 3 had already added
                                 * jpdse_loss_finalize, jpdse_conv_fwd_pool, jpdse_conv_dgrad_fused_lrelu, jpdse_input_builder, jpdse_copy, jpdse_prof_hbm_* under version 1;
                                 * the learned codec (jpdse_binarize_fwd, jpdse_code_stats[_workspace_size], jpdse_code_export) was added to
-                                * version 2 later, and so were the evaluation metrics (jpdse_eval_metrics[_workspace_size]): purely additive,
-                                * nothing existing changed */
+                                * version 2 later, and so were the evaluation metrics (jpdse_eval_metrics[_workspace_size]) and their
+                                * per-class form (jpdse_eval_metrics_sem[_workspace_size]): purely additive, nothing existing changed */
 
 enum { JPDSE_F32 = 0, JPDSE_BF16 = 1 };
 enum { JPDSE_PAD_ZERO = 0, JPDSE_PAD_REFLECT = 1 };
@@ -398,6 +398,33 @@ size_t jpdse_eval_metrics_workspace_size(int32_t N, int32_t H, int32_t W, int32_
 int jpdse_eval_metrics(int32_t dtype_fake, int32_t dtype_real, int32_t N, int32_t H, int32_t W, int32_t C, const void* fake,
                        const void* real, const double* mean, const double* std, double* out, void* ws, size_t ws_bytes,
                        void* stream);
+/* The same pass with the two integer sums also split by semantic class (the intent of get_sem_wise_distortion,
+ * pix2pixHD_model.py:646-706, which cannot run as written).  label: DEVICE fp32 [N][1][H][W], integer-valued, the map
+ * jpdse_input_builder reads; n_classes in [1, 256].  cls: DEVICE int64 [N][n_classes + 1][3]; row k of image n =
+ * (sum |q(fake) - q(real)|, sum (q(fake) - q(real))^2, pixels) over the 3 channels of the pixels labelled k.  Row n_classes
+ * collects every pixel whose label is outside [0, n_classes) or not an integer (NaN included), so per image the rows add up
+ * to out[0], out[1] and H*W exactly.  `out` is what jpdse_eval_metrics writes for the same images, bit for bit; the images
+ * are read once and the label map once.  Integer sums throughout: two calls give bit-identical cls.  A bad n_classes or a
+ * NULL pointer is JPDSE_EINVAL before any launch; ws: jpdse_eval_metrics_sem_workspace_size() bytes (0 for an unsupported
+ * shape or n_classes). */
+size_t jpdse_eval_metrics_sem_workspace_size(int32_t N, int32_t H, int32_t W, int32_t C, int32_t n_classes);
+/* The seventeen arguments travel in one struct, like the descriptors of the conv and norm families: the first fields are the
+ * arguments of jpdse_eval_metrics with the same names and meanings. */
+typedef struct jpdse_eval_metrics_sem_args {
+  int32_t dtype_fake, dtype_real, N, H, W, C;
+  const void* fake;    /* NHWC [N][H][W][CPAD(3)], fp32 or bf16 */
+  const void* real;    /* NHWC fp32 */
+  const float* label;  /* device fp32 [N][1][H][W] */
+  int32_t n_classes;   /* 1..256 */
+  const double* mean;  /* host, 3 doubles */
+  const double* std;   /* host, 3 doubles */
+  double* out;         /* device [N][14] */
+  int64_t* cls;        /* device [N][n_classes + 1][3] */
+  void* ws;
+  size_t ws_bytes;
+  void* stream;
+} jpdse_eval_metrics_sem_args;
+int jpdse_eval_metrics_sem(const jpdse_eval_metrics_sem_args* args);
 
 /* ---- optimizer ---------------------------------------------------------------------- */
 /* torch.optim.Adam (model.py:275,279) over a table of tensors, one launch.  `table` is a

@@ -9,6 +9,8 @@
 //                          cs / ssim per position, one (cs, ssim) partial pair per block
 //   msssim_down_kernel     2x2 mean -> next scale's planes (exact in fp32: scale j values carry 8 + 2(j-1) bits)
 //   metrics_final_kernel   per image: partials -> out[n][14], fixed order, no atomics: two runs are bit-identical
+// With a label map (jpdse_eval_metrics_sem) the quantise pass also splits its two integer sums by semantic class -- one table
+// per wave in LDS, one partial row per block -- and metrics_cls_final_kernel adds the rows into cls[n][n_classes + 1][3].
 //
 // Cancellation: every tile is filtered about its own pivot (the value of its first pixel, per image of the pair): the local
 // statistics are shift invariant, E[(x-p)^2] - (mu-p)^2 is formed from values of the size of the tile's contrast instead
@@ -26,32 +28,82 @@ constexpr int kSW = kTW + kHalo;         // staged columns (74)
 constexpr int kSH = kTH + kHalo;         // staged rows (26)
 constexpr int kQuantBlocksMax = 1024;    // per image
 constexpr int kOutPerImage = 4 + 2 * kMsScales;
+constexpr int kClassesMax = 256;         // jpdse_eval_metrics_sem
 
 struct GaussWin { float w[kWin]; };
 
 // fake: NHWC [N][H][W][cs] fp32 or bf16, real: NHWC fp32.  One thread per pixel; planes x (fake) / y (real): [N][3][H*W].
-template <typename TF>
+// kCls: label [N][H*W] fp32 is read as well and the two sums are split by class into cpartial[n][block][n_classes + 1][3]
+// (|d| sum, d^2 sum, pixels; row n_classes = labels outside [0, n_classes) or not integers).  A wave first reduces over the
+// lanes of one class (ballot on equality with the first open lane's class, then a shuffle sum: neighbouring pixels mostly
+// share a class, so the loop runs once or twice), then lane 0 adds into the wave's OWN table in LDS: no atomics, no lanes
+// meeting on one address.  Entries are 64-bit: a block of 2^18 pixels sums d^2 up to 5.1e10.  Dynamic LDS: 4 waves x
+// (n_classes + 1) x 3 x 8 bytes (24.1 KB at 256 classes).
+template <typename TF, bool kCls>
 __global__ __launch_bounds__(256) void metrics_quant_kernel(const TF* __restrict__ fake, const float* __restrict__ real,
                                                            int cs, long long HW, QuantParams qp, float* __restrict__ px,
                                                            float* __restrict__ py,
-                                                           unsigned long long* __restrict__ partial) {
+                                                           unsigned long long* __restrict__ partial,
+                                                           const float* __restrict__ label, int n_classes,
+                                                           unsigned long long* __restrict__ cpartial) {
   __shared__ unsigned long long red[2][4];
+  extern __shared__ unsigned long long ctab[];      // kCls: [4 waves][(n_classes + 1) * 3]
   const int n = blockIdx.y;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int centries = (n_classes + 1) * 3;
   const TF* f = fake + (long long)n * HW * cs;
   const float* r = real + (long long)n * HW * cs;
   float* ox = px + (long long)n * 3 * HW;
   float* oy = py + (long long)n * 3 * HW;
+  if constexpr (kCls) {
+    for (int i = threadIdx.x; i < 4 * centries; i += 256) ctab[i] = 0;
+    __syncthreads();
+  }
   unsigned long long l1 = 0, se = 0;
-  for (long long p = blockIdx.x * 256LL + threadIdx.x; p < HW; p += (long long)gridDim.x * 256) {
+  // the trip count is the same for the whole block (the class reduction below runs wave-wide); lanes past the end idle
+  for (long long base = blockIdx.x * 256LL; base < HW; base += (long long)gridDim.x * 256) {
+    const long long p = base + threadIdx.x;
+    const bool valid = p < HW;
+    unsigned pl1 = 0, pse = 0;
+    if (valid) {
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const int qa = quant_u8(ElemOps<TF>::ld(f + p * cs + c), qp.std[c], qp.mean[c]);
-      const int qb = quant_u8(r[p * cs + c], qp.std[c], qp.mean[c]);
-      const int d = qa - qb;
-      l1 += (unsigned)(d < 0 ? -d : d);
-      se += (unsigned)(d * d);
-      ox[c * HW + p] = (float)qa;
-      oy[c * HW + p] = (float)qb;
+      for (int c = 0; c < 3; ++c) {
+        const int qa = quant_u8(ElemOps<TF>::ld(f + p * cs + c), qp.std[c], qp.mean[c]);
+        const int qb = quant_u8(r[p * cs + c], qp.std[c], qp.mean[c]);
+        const int d = qa - qb;
+        pl1 += (unsigned)(d < 0 ? -d : d);
+        pse += (unsigned)(d * d);
+        ox[c * HW + p] = (float)qa;
+        oy[c * HW + p] = (float)qb;
+      }
+    }
+    l1 += pl1;
+    se += pse;
+    if constexpr (kCls) {
+      int k = -1;                                   // idle lane: matches no class
+      if (valid) {
+        const float lab = label[(long long)n * HW + p];
+        k = (lab >= 0.f && lab < (float)n_classes && lab == floorf(lab)) ? (int)lab : n_classes;   // NaN: the extra row
+      }
+      unsigned long long open = __ballot(valid);
+      unsigned long long* tab = ctab + wave * centries;
+      while (open) {                                // wave-uniform
+        const int kc = __shfl(k, __ffsll((long long)open) - 1, 64);
+        const bool mine = k == kc;
+        const unsigned long long m = __ballot(mine);
+        unsigned a = mine ? pl1 : 0u, b = mine ? pse : 0u;     // <= 64 * 765 and 64 * 195075: 32 bits hold the wave's sums
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+          a += __shfl_xor(a, off, 64);
+          b += __shfl_xor(b, off, 64);
+        }
+        if (lane == 0) {
+          tab[kc * 3 + 0] += a;
+          tab[kc * 3 + 1] += b;
+          tab[kc * 3 + 2] += (unsigned)__popcll(m);
+        }
+        open &= ~m;
+      }
     }
   }
 #pragma unroll
@@ -59,9 +111,9 @@ __global__ __launch_bounds__(256) void metrics_quant_kernel(const TF* __restrict
     l1 += __shfl_xor(l1, off, 64);
     se += __shfl_xor(se, off, 64);
   }
-  if ((threadIdx.x & 63) == 0) {
-    red[0][threadIdx.x >> 6] = l1;
-    red[1][threadIdx.x >> 6] = se;
+  if (lane == 0) {
+    red[0][wave] = l1;
+    red[1][wave] = se;
   }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -69,6 +121,30 @@ __global__ __launch_bounds__(256) void metrics_quant_kernel(const TF* __restrict
     o[0] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
     o[1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
   }
+  if constexpr (kCls) {
+    unsigned long long* o = cpartial + ((long long)n * gridDim.x + blockIdx.x) * centries;
+    for (int i = threadIdx.x; i < centries; i += 256)
+      o[i] = ctab[i] + ctab[centries + i] + ctab[2 * centries + i] + ctab[3 * centries + i];
+  }
+}
+
+// cpartial[n][qblocks][entries] -> cls[n][entries], entries = (n_classes + 1) * 3.  grid (ceil(entries / 64), N): lane =
+// entry, the four waves take the blocks 4i + wave in order and are then added in order (integers: exact in any order).
+__global__ __launch_bounds__(256) void metrics_cls_final_kernel(const unsigned long long* __restrict__ cpartial, int qblocks,
+                                                               int entries, long long* __restrict__ cls) {
+  __shared__ unsigned long long red[4][64];
+  const int n = blockIdx.y;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int e = blockIdx.x * 64 + lane;
+  unsigned long long a = 0;
+  if (e < entries) {
+    const unsigned long long* p = cpartial + (long long)n * qblocks * entries + e;
+    for (int b = wave; b < qblocks; b += 4) a += p[(long long)b * entries];
+  }
+  red[wave][lane] = a;
+  __syncthreads();
+  if (wave == 0 && e < entries)
+    cls[(long long)n * entries + e] = (long long)(red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane]);
 }
 
 // x, y: planes [NC][Hs][Ws]; grid (tiles_x, tiles_y, NC); partial: [NC][tiles_y][tiles_x][2] doubles (sum cs, sum ssim over
@@ -301,29 +377,23 @@ static const char* metrics_shape_error(int N, int H, int W, int C) {
   return nullptr;
 }
 
-}  // namespace jpdse
 
-using namespace jpdse;
-
-extern "C" {
-
-size_t jpdse_eval_metrics_workspace_size(int32_t N, int32_t H, int32_t W, int32_t C) {
-  if (metrics_shape_error(N, H, W, C)) return 0;
-  MetricsPlan p;
-  metrics_plan(N, H, W, p);
-  return p.bytes;
+static size_t cls_partial_bytes(int N, int qblocks, int n_classes) {
+  return align_up((size_t)N * qblocks * (n_classes + 1) * 3 * sizeof(unsigned long long), 256);
 }
 
-int jpdse_eval_metrics(int32_t dtype_fake, int32_t dtype_real, int32_t N, int32_t H, int32_t W, int32_t C, const void* fake,
-                       const void* real, const double* mean, const double* std, double* out, void* ws, size_t ws_bytes,
-                       void* stream) {
+// both entry points: label == nullptr is jpdse_eval_metrics; with a label the class partials sit behind the plain workspace
+static int metrics_run(int32_t dtype_fake, int32_t dtype_real, int32_t N, int32_t H, int32_t W, int32_t C, const void* fake,
+                       const void* real, const float* label, int32_t n_classes, const double* mean, const double* std,
+                       double* out, int64_t* cls, void* ws, size_t ws_bytes, void* stream) {
   JPDSE_REQUIRE(dtype_fake == JPDSE_F32 || dtype_fake == JPDSE_BF16, "eval_metrics: fake must be fp32 or bf16");
   JPDSE_REQUIRE(dtype_real == JPDSE_F32, "eval_metrics: real must be fp32");
   JPDSE_REQUIRE(fake && real && mean && std && out, "eval_metrics: null argument");
   if (const char* msg = metrics_shape_error(N, H, W, C)) return set_error(JPDSE_EINVAL, "%s (N %d, H %d, W %d, C %d)", msg, N, H, W, C);
   MetricsPlan p;
   metrics_plan(N, H, W, p);
-  if (ws == nullptr || ws_bytes < p.bytes) return set_error(JPDSE_EWORKSPACE, "eval_metrics: workspace too small");
+  const size_t need = p.bytes + (label ? cls_partial_bytes(N, p.qblocks, n_classes) : 0);
+  if (ws == nullptr || ws_bytes < need) return set_error(JPDSE_EWORKSPACE, "eval_metrics: workspace too small");
   JPDSE_REQUIRE(((uintptr_t)ws & 15) == 0, "eval_metrics: workspace not 16-byte aligned");
   hipStream_t s = as_stream(stream);
   char* base = reinterpret_cast<char*>(ws);
@@ -331,6 +401,7 @@ int jpdse_eval_metrics(int32_t dtype_fake, int32_t dtype_real, int32_t N, int32_
   float* py = reinterpret_cast<float*>(base + p.off_y);
   unsigned long long* qpartial = reinterpret_cast<unsigned long long*>(base + p.off_qpartial);
   double* spartial = reinterpret_cast<double*>(base + p.off_spartial);
+  unsigned long long* cpartial = reinterpret_cast<unsigned long long*>(base + p.bytes);
 
   QuantParams qp = {};
   for (int c = 0; c < 3; ++c) { qp.mean[c] = mean[c]; qp.std[c] = std[c]; }
@@ -350,8 +421,13 @@ int jpdse_eval_metrics(int32_t dtype_fake, int32_t dtype_real, int32_t N, int32_
 
   if (int rc = by_dtype(dtype_fake, [&](auto tag) {
         using T = decltype(tag);
-        return launch256("eval_metrics(quantise)", metrics_quant_kernel<T>, dim3(p.qblocks, N), stream, cptr<T>(fake),
-                         cptr<float>(real), cs, HW, qp, px, py, qpartial);
+        if (!label)
+          return launch256("eval_metrics(quantise)", metrics_quant_kernel<T, false>, dim3(p.qblocks, N), stream,
+                           cptr<T>(fake), cptr<float>(real), cs, HW, qp, px, py, qpartial, nullptr, 0, nullptr);
+        const size_t lds = (size_t)4 * (n_classes + 1) * 3 * sizeof(unsigned long long);
+        hipLaunchKernelGGL((metrics_quant_kernel<T, true>), dim3(p.qblocks, N), dim3(256), lds, s, cptr<T>(fake),
+                           cptr<float>(real), cs, HW, qp, px, py, qpartial, label, n_classes, cpartial);
+        return check_launch("eval_metrics_sem(quantise)");
       }))
     return rc;
   for (int j = 0; j < kMsScales; ++j) {
@@ -368,7 +444,49 @@ int jpdse_eval_metrics(int32_t dtype_fake, int32_t dtype_real, int32_t N, int32_
     }
   }
   hipLaunchKernelGGL(metrics_final_kernel, dim3(N), dim3(256), 0, s, qpartial, spartial, p.fa, out);
-  return check_launch("eval_metrics(final)");
+  if (int rc = check_launch("eval_metrics(final)")) return rc;
+  if (label) {
+    const int entries = (n_classes + 1) * 3;
+    hipLaunchKernelGGL(metrics_cls_final_kernel, dim3((entries + 63) / 64, N), dim3(256), 0, s, cpartial, p.qblocks, entries,
+                       reinterpret_cast<long long*>(cls));
+    return check_launch("eval_metrics_sem(final)");
+  }
+  return JPDSE_OK;
+}
+
+}  // namespace jpdse
+
+using namespace jpdse;
+
+extern "C" {
+
+size_t jpdse_eval_metrics_workspace_size(int32_t N, int32_t H, int32_t W, int32_t C) {
+  if (metrics_shape_error(N, H, W, C)) return 0;
+  MetricsPlan p;
+  metrics_plan(N, H, W, p);
+  return p.bytes;
+}
+
+size_t jpdse_eval_metrics_sem_workspace_size(int32_t N, int32_t H, int32_t W, int32_t C, int32_t n_classes) {
+  if (metrics_shape_error(N, H, W, C) || n_classes < 1 || n_classes > kClassesMax) return 0;
+  MetricsPlan p;
+  metrics_plan(N, H, W, p);
+  return p.bytes + cls_partial_bytes(N, p.qblocks, n_classes);
+}
+
+int jpdse_eval_metrics(int32_t dtype_fake, int32_t dtype_real, int32_t N, int32_t H, int32_t W, int32_t C, const void* fake,
+                       const void* real, const double* mean, const double* std, double* out, void* ws, size_t ws_bytes,
+                       void* stream) {
+  return metrics_run(dtype_fake, dtype_real, N, H, W, C, fake, real, nullptr, 0, mean, std, out, nullptr, ws, ws_bytes, stream);
+}
+
+int jpdse_eval_metrics_sem(const jpdse_eval_metrics_sem_args* a) {
+  JPDSE_REQUIRE(a != nullptr, "eval_metrics_sem: null argument struct");
+  JPDSE_REQUIRE(a->label && a->cls, "eval_metrics_sem: null argument");
+  JPDSE_REQUIRE(a->n_classes >= 1 && a->n_classes <= kClassesMax, "eval_metrics_sem: n_classes %d outside [1, %d]",
+                a->n_classes, kClassesMax);
+  return metrics_run(a->dtype_fake, a->dtype_real, a->N, a->H, a->W, a->C, a->fake, a->real, a->label, a->n_classes, a->mean,
+                     a->std, a->out, a->cls, a->ws, a->ws_bytes, a->stream);
 }
 
 }  // extern "C"

@@ -144,7 +144,7 @@ class Pix2PixHDModel(BaseModel):
       if g('pool_size', 0) > 0:
         unsupported.append('--pool_size %s' % g('pool_size'))
     for flag in ('sem_masking', 'no_label', 'no_feat', 'match_raw_feat', 'no_lsgan', 'use_netE_output',
-                 'zero_sem', 'zero_ins', 'zero_vis', 'binary_mask', 'inst_wise_pool'):
+                 'binary_mask', 'inst_wise_pool'):
       if g(flag):
         unsupported.append('--' + flag)
     if g('norm', 'instance') != 'instance':
@@ -163,6 +163,10 @@ class Pix2PixHDModel(BaseModel):
     self.n_onehot = opt.num_labels + 1 if g('contain_dontcare_label') else opt.num_labels
     self.label_nc = self.n_onehot + (0 if g('no_instance') else 1)
     self.use_feat_encoding = feat_enc
+    # ablation inputs (model.py:583-606): blank the visual lanes, every semantic lane, or the instance-edge lane of G's input
+    self.zero_vis, self.zero_sem = bool(g('zero_vis')), bool(g('zero_sem'))
+    # the edge lane is only consulted when the semantics stay and an edge lane exists (model.py:588)
+    self.zero_ins = bool(g('zero_ins')) and not self.zero_sem and not g('no_instance')
     # generator input: semantics + encoded image (feat_num channels) or + the image itself (model.py:135-139)
     self.feat_nc = g('feat_num', 3) if feat_enc else opt.input_nc
     netG_input_nc = self.label_nc + self.feat_nc
@@ -244,6 +248,8 @@ class Pix2PixHDModel(BaseModel):
       return self.get_eval_rate(x_dict)
     if mode == 'get_eval_metrics':
       return self.get_eval_metrics(x_dict)
+    if mode == 'get_eval_metrics_per_class':
+      return self.get_eval_metrics(x_dict, per_class=True)
     raise ValueError('Invalid forward mode: {}'.format(mode))
 
   def create_optimizers(self, opt):
@@ -307,6 +313,10 @@ class Pix2PixHDModel(BaseModel):
     image = x_dict['image'].to(dev, dtype=torch.float32, non_blocking=True).contiguous()
     if getattr(opt, 'no_instance', False):
       inst = torch.zeros_like(inst)      # a constant map has no edges; its channel is not part of label_nc
+    elif self.zero_ins:
+      # --zero_ins: the reference zeroes the edge channel of input_label IN PLACE (model.py:591) and hands that tensor on to
+      # the discriminator (:610, :717-733), so G and D both see a zero edge lane: a constant instance map everywhere
+      inst = torch.zeros_like(inst)
     total_c = self.label_nc + self.feat_nc
     base = ops.onehot_edge(label, inst, self.n_onehot, total_c, self.cdtype) if build_base else None
     real = ops.nchw_to_nhwc(image, self.cdtype)
@@ -330,12 +340,24 @@ class Pix2PixHDModel(BaseModel):
     finally:
       self.netE.train(was)
 
+  def _g_input_zero_sem(self, vis, like):
+    """--zero_sem (model.py:585-587): G's input with all label_nc semantic lanes zero and `vis` (Act or None) in the visual
+    lanes.  Only G's input: the discriminator keeps the real semantics (_get_img returns input_label untouched)."""
+    g_in = Act.empty(like.N, like.H, like.W, self.label_nc + self.feat_nc, self.cdtype, like.t.device)
+    ops.zero_(g_in.t)
+    return g_in if vis is None else ops.insert_channels(g_in, vis, self.label_nc)
+
   def _g_input_eval(self, pre):
-    """The generator input of the inference paths: [semantics | image], or [semantics | netE(image)] (model.py:568-595)."""
-    if self.netE is None:
-      return self._with_image(pre['base'], pre['src'])
-    feat, _ = self._encoder_eval(lambda: self.netE.fwd(pre['src']))
-    return self._with_image(pre['base'], feat)
+    """The generator input of the inference paths: [semantics | image], or [semantics | netE(image)] (model.py:568-595), with
+    the --zero_vis / --zero_sem lanes blanked (:583-587; --zero_ins is already in the edge lane, see preprocess)."""
+    vis = None if self.zero_vis else pre['src']      # --zero_vis: nothing visual reaches the generator
+    if vis is not None and self.netE is not None:
+      vis, _ = self._encoder_eval(lambda: self.netE.fwd(vis))
+    if self.zero_sem:
+      return self._g_input_zero_sem(vis, pre['real'])
+    if vis is None:
+      return pre['base']                 # onehot_edge leaves every lane behind the semantics zero
+    return self._with_image(pre['base'], vis)
 
   def _set_codec_rng(self, local_batch):
     """Point the binarizer at this call's images: n_global = rank * local_batch + i."""
@@ -383,7 +405,7 @@ class Pix2PixHDModel(BaseModel):
   # ---- inference ------------------------------------------------------------------------------
   def get_img(self, x_dict):
     with torch.no_grad():
-      pre = self.preprocess(x_dict)
+      pre = self.preprocess(x_dict, build_base=not self.zero_sem)
       fake, _ = self.netG.fwd(self._g_input_eval(pre))
       return ops.nhwc_to_nchw(fake)
 
@@ -392,7 +414,7 @@ class Pix2PixHDModel(BaseModel):
     the host through tensor2im (pix2pixHD_model.py:636-641, utils/misc.py:64-95) -- here one device pass
     (jpdse_quant_loss: the same float64 arithmetic, bit-identical quantisation, no device->host image copies)."""
     with torch.no_grad():
-      pre = self.preprocess(x_dict)
+      pre = self.preprocess(x_dict, build_base=not self.zero_sem)
       fake, _ = self.netG.fwd(self._g_input_eval(pre))
       real32 = ops.nchw_to_nhwc(pre['image_nchw'], F32)       # the original image un-rounded, as the reference uses it
       slot = torch.zeros(1, dtype=torch.float32, device=self._device())
@@ -400,14 +422,18 @@ class Pix2PixHDModel(BaseModel):
                      self.opt.distortion_loss_fn == 'mse', slot)
       return slot[0]
 
-  def get_eval_metrics(self, x_dict):
+  def get_eval_metrics(self, x_dict, per_class=False):
     """Every distortion figure of the reference's test loop (test.py:114-125) from ONE generator forward: dict(l1, mse,
     psnr, ms_ssim, per_image) on the 0..255 scale of the quantised images (ops.eval_metrics; MS-SSIM: DESIGN.md 4.5).
-    l1 / mse are the numbers get_eval_loss returns for --distortion_loss_fn l1 / mse."""
+    l1 / mse are the numbers get_eval_loss returns for --distortion_loss_fn l1 / mse.  per_class=True adds `per_class`:
+    L1, MSE and PSNR of each of the n_onehot semantic classes from the same device pass (the intent of the reference's
+    get_sem_wise_distortion, model.py:646-706; ops.eval_metrics_per_class)."""
     with torch.no_grad():
-      pre = self.preprocess(x_dict)
+      pre = self.preprocess(x_dict, build_base=not self.zero_sem)
       fake, _ = self.netG.fwd(self._g_input_eval(pre))
       real32 = ops.nchw_to_nhwc(pre['image_nchw'], F32)
+      if per_class:
+        return ops.eval_metrics(fake, real32, self.opt.normalize_mean, self.opt.normalize_std, pre['label'], self.n_onehot)
       return ops.eval_metrics(fake, real32, self.opt.normalize_mean, self.opt.normalize_std)
 
   # ---- training -------------------------------------------------------------------------------
@@ -429,15 +455,25 @@ class Pix2PixHDModel(BaseModel):
     real, src, label, inst = pre['real'], pre['src'], pre['label'], pre['inst']
     B, H, W = real.N, real.H, real.W
     e_ctx = None
-    if self.netE is not None:
+    if self.zero_vis:
+      src = None
+    # --zero_vis: without a source the visual lanes of G's input stay zero (input_builder zeroes them for a missing image) and the
+    # encoder, whose output the reference replaces by zeros (model.py:583-584: no gradient reaches it), is not run.
+    # --zero_sem: G's input is built apart with blank semantic lanes; D's halves keep the real semantics (model.py:585-587).
+    if self.netE is not None or self.zero_sem:
       # learned codec: G sees [semantics | netE(image)] (model.py:568-595), netE in the trainer's mode (stochastic binarizer
       # when training); D sees [semantics | real / fake] as always
-      self._set_codec_rng(B)
-      feat, e_ctx = self.netE.fwd(src)
-      if self.netE.training:
-        self.codec_draw += 1
-      g_in = Act.empty(B, H, W, self.label_nc + feat.C, self.cdtype, dev)
-      ops.input_builder(label, inst, self.n_onehot, [g_in], [feat], self.label_nc)
+      vis = src
+      if self.netE is not None and src is not None:
+        self._set_codec_rng(B)
+        vis, e_ctx = self.netE.fwd(src)
+        if self.netE.training:
+          self.codec_draw += 1
+      if self.zero_sem:
+        g_in = self._g_input_zero_sem(vis, real)
+      else:
+        g_in = Act.empty(B, H, W, self.label_nc + self.feat_nc, self.cdtype, dev)
+        ops.input_builder(label, inst, self.n_onehot, [g_in], [vis], self.label_nc)
       d_in = Act.empty(2 * B, H, W, self.label_nc + real.C, self.cdtype, dev) if run_d else None
       if run_d:
         ops.input_builder(label, inst, self.n_onehot, [d_in.batch_slice(B, 2 * B), d_in.batch_slice(0, B)], [real, None],
@@ -578,7 +614,7 @@ class Pix2PixHDModel(BaseModel):
       d_fake = dd if d_fake is None else ops.add_(d_fake, dd)
     if d_fake is None:
       return False
-    if self.netE is None:
+    if state['e_ctx'] is None:           # no encoder, or --zero_vis cut it off G's input
       self.netG.bwd(state['g_ctx'], d_fake, need_dx=False, need_dw=True)
       return True
     # learned codec: the gradient w.r.t. the feature channels of G's input goes on into the encoder

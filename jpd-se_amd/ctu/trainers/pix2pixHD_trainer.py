@@ -135,11 +135,13 @@ class Pix2PixHDTrainer(BaseTrainer):
     self.eval()
     return self.model(x_dict, self.opt, mode='get_eval_rate')
 
-  def get_eval_metrics(self, x_dict):
+  def get_eval_metrics(self, x_dict, per_class=False):
     """L1, MSE, PSNR and MS-SSIM of the reconstruction (test.py:114-125) from one generator forward: dict of Python floats
-    (batch means) plus `per_image`, four float64 CPU tensors [B]."""
+    (batch means) plus `per_image`, four float64 CPU tensors [B].  per_class=True adds `per_class`: pixels, l1, mse and psnr
+    of every semantic class ([n_classes], pixel-weighted over the batch, 0 for an absent class), `unlabelled` and the same
+    four keys `per_image` ([B, n_classes]), from the same device pass."""
     self.eval()
-    return self.model(x_dict, self.opt, mode='get_eval_metrics')
+    return self.model(x_dict, self.opt, mode='get_eval_metrics_per_class' if per_class else 'get_eval_metrics')
 
   def get_img(self, x_dict):
     self.eval()

@@ -50,6 +50,13 @@ class AdamEntry(ctypes.Structure):
               ('cast_bf16', ctypes.c_void_p)]
 
 
+class EvalMetricsSemArgs(ctypes.Structure):
+  _fields_ = [(n, ctypes.c_int32) for n in ('dtype_fake', 'dtype_real', 'N', 'H', 'W', 'C')] + \
+             [('fake', ctypes.c_void_p), ('real', ctypes.c_void_p), ('label', ctypes.c_void_p), ('n_classes', ctypes.c_int32),
+              ('mean', ctypes.POINTER(ctypes.c_double)), ('std', ctypes.POINTER(ctypes.c_double)), ('out', ctypes.c_void_p),
+              ('cls', ctypes.c_void_p), ('ws', ctypes.c_void_p), ('ws_bytes', ctypes.c_size_t), ('stream', ctypes.c_void_p)]
+
+
 _P, _I32, _I64, _F, _SZ = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float,
                            ctypes.c_size_t)
 _CD, _ND = ctypes.POINTER(ConvDesc), ctypes.POINTER(InormDesc)
@@ -134,6 +141,8 @@ SIGNATURES = {
     'jpdse_eval_metrics_workspace_size': (_SZ, [_I32, _I32, _I32, _I32]),
     'jpdse_eval_metrics': (_I32, [_I32, _I32, _I32, _I32, _I32, _I32, _P, _P, ctypes.POINTER(ctypes.c_double),
                                   ctypes.POINTER(ctypes.c_double), _P, _P, _SZ, _P]),
+    'jpdse_eval_metrics_sem_workspace_size': (_SZ, [_I32, _I32, _I32, _I32, _I32]),
+    'jpdse_eval_metrics_sem': (_I32, [ctypes.POINTER(EvalMetricsSemArgs)]),
 }
 
 # the developer build (same sources, -DJPDSE_DEV): the shipped ABI plus include/jpdse_dev.h

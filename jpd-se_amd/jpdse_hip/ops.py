@@ -8,7 +8,7 @@ import ctypes
 
 import torch
 
-from . import (lib, check, F32, BF16, ConvDesc, InormDesc, ACT_NONE, PAD_ZERO, PAD_REFLECT)
+from . import (lib, check, F32, BF16, ConvDesc, InormDesc, EvalMetricsSemArgs, ACT_NONE, PAD_ZERO, PAD_REFLECT)
 
 
 def cpad(c):
@@ -575,17 +575,71 @@ def eval_metrics_finish(raw):
               per_image=dict(l1=l1_i, mse=mse_i, psnr=psnr_i, ms_ssim=ms_i), raw=raw)
 
 
-def eval_metrics(fake, real32, mean, std):
+def eval_metrics_per_class(cls):
+  """The host half of the per-class breakdown: `cls` is the int64 CPU tensor [N, n_classes + 1, 3] jpdse_eval_metrics_sem
+  wrote (per image and class: |d| sum, d^2 sum, pixels over the 3 channels; the last row = pixels without a class).  Returns
+  dict(pixels int64 [n_classes], l1 / mse / psnr float64 [n_classes], unlabelled int, per_image: the same four keys
+  [N, n_classes], raw: the input).  l1, mse = sum / (3 * pixels), 0 for a class that does not occur (the reference's rule,
+  pix2pixHD_model.py:674-677); psnr = 10 log10(255^2 / mse): inf for an exact class, nan for an absent one.  The batch
+  figures are pixel-weighted -- sums over the batch before the division, as the reference sums over dims [0, 2, 3] -- not
+  means of the per-image figures."""
+  cls = cls.to(torch.int64)
+
+  def figures(t):                       # t: [..., n_classes, 3]
+    pix = t[..., 2]
+    den = (3 * pix).to(torch.float64)
+    seen = pix > 0
+    safe = torch.where(seen, den, torch.ones_like(den))
+    zero = torch.zeros_like(den)
+    l1 = torch.where(seen, t[..., 0].to(torch.float64) / safe, zero)
+    mse = torch.where(seen, t[..., 1].to(torch.float64) / safe, zero)
+    psnr = torch.where(mse > 0, 10.0 * torch.log10(255.0 ** 2 / torch.where(mse > 0, mse, torch.ones_like(mse))),
+                       torch.full_like(mse, float('inf')))
+    psnr = torch.where(seen, psnr, torch.full_like(mse, float('nan')))
+    return dict(pixels=pix.clone(), l1=l1, mse=mse, psnr=psnr)
+
+  r = figures(cls[:, :-1].sum(dim=0))
+  r['unlabelled'] = int(cls[:, -1, 2].sum().item())
+  r['per_image'] = figures(cls[:, :-1])
+  r['raw'] = cls
+  return r
+
+
+def eval_metrics(fake, real32, mean, std, label=None, n_classes=None):
   """L1, MSE, PSNR and MS-SSIM (0..255 scale) of the uint8-quantised de-normalised images `fake` (Act, fp32 or bf16: the
   generator's output) against `real32` (Act, fp32), both 3-channel NHWC: one device pass (jpdse_eval_metrics), one
-  read-back of 14 doubles per image, then eval_metrics_finish."""
+  read-back of 14 doubles per image, then eval_metrics_finish.  With `label` (device fp32 [N,1,H,W], the map
+  input_builder reads) and `n_classes` the same pass also splits L1 and MSE by semantic class (jpdse_eval_metrics_sem): the
+  class table rides in the same read-back and the result gains `per_class` (eval_metrics_per_class)."""
   assert fake.t.shape == real32.t.shape and fake.C == real32.C and len(mean) == fake.C and len(std) == fake.C
   L = lib()
-  n = L.jpdse_eval_metrics_workspace_size(fake.N, fake.H, fake.W, fake.C)
-  ws = workspace(max(n, 1), fake.t.device)
-  out = torch.empty((fake.N, 14), dtype=torch.float64, device=fake.t.device)
   arr = ctypes.c_double * fake.C
-  check(L.jpdse_eval_metrics(fake.dtype, real32.dtype, fake.N, fake.H, fake.W, fake.C, _p(fake.t), _p(real32.t),
-                             arr(*[float(v) for v in mean]), arr(*[float(v) for v in std]), _p(out), _p(ws), ws.numel(),
-                             _stream()), 'eval_metrics')
-  return eval_metrics_finish(out.cpu())
+  mean_c, std_c = arr(*[float(v) for v in mean]), arr(*[float(v) for v in std])
+  dev = fake.t.device
+  if label is None:
+    if n_classes is not None:
+      raise ValueError('eval_metrics: n_classes without a label map')
+    n = L.jpdse_eval_metrics_workspace_size(fake.N, fake.H, fake.W, fake.C)
+    ws = workspace(max(n, 1), dev)
+    out = torch.empty((fake.N, 14), dtype=torch.float64, device=dev)
+    check(L.jpdse_eval_metrics(fake.dtype, real32.dtype, fake.N, fake.H, fake.W, fake.C, _p(fake.t), _p(real32.t),
+                               mean_c, std_c, _p(out), _p(ws), ws.numel(), _stream()), 'eval_metrics')
+    return eval_metrics_finish(out.cpu())
+  if n_classes is None:
+    raise ValueError('eval_metrics: a label map needs n_classes')
+  n_classes = int(n_classes)
+  assert label.dtype == torch.float32 and label.is_contiguous() and label.device == dev
+  assert tuple(label.shape) == (fake.N, 1, fake.H, fake.W)
+  n = L.jpdse_eval_metrics_sem_workspace_size(fake.N, fake.H, fake.W, fake.C, n_classes)
+  ws = workspace(max(n, 1), dev)
+  rows = max(n_classes, 0) + 1
+  both = torch.empty(fake.N * (14 + rows * 3), dtype=torch.int64, device=dev)      # out | cls: 8-byte words, ONE read-back
+  out, cls = both[:fake.N * 14], both[fake.N * 14:]
+  args = EvalMetricsSemArgs(fake.dtype, real32.dtype, fake.N, fake.H, fake.W, fake.C, fake.t.data_ptr(), real32.t.data_ptr(),
+                            label.data_ptr(), n_classes, mean_c, std_c, out.data_ptr(), cls.data_ptr(), ws.data_ptr(),
+                            ws.numel(), torch.cuda.current_stream().cuda_stream)
+  check(L.jpdse_eval_metrics_sem(ctypes.byref(args)), 'eval_metrics_sem')
+  host = both.cpu()
+  r = eval_metrics_finish(host[:fake.N * 14].view(torch.float64).view(fake.N, 14))
+  r['per_class'] = eval_metrics_per_class(host[fake.N * 14:].view(fake.N, rows, 3))
+  return r

@@ -5,10 +5,12 @@ HTML page.  Per batch: trainer.get_eval_metrics (one generator forward) and, wit
 Batches: seeded synthetic ones (ctu.utils.synthetic), or --data DIR holding pre-decoded batches as *.pt files, each a dict with
 the x_dict keys (label, instance, image, optionally compressed_img, path).  The test-set line averages the per-batch values
 over the batches, as the reference does (so, like there, a ragged last batch weighs as much as a full one); a second line
-gives the per-image averages, which are the ones to quote.  PSNR is the mean of the per-image PSNRs.
+gives the per-image averages, which are the ones to quote.  PSNR is the mean of the per-image PSNRs.  --per-class adds the
+table of the distortion per semantic class over the whole test set (pixel-weighted: the raw integer sums of every batch are
+added before the division), from the same device pass; --zero_sem / --zero_ins / --zero_vis run the reference's ablations.
 
   python scripts/eval_rd.py [--batches 4] [--batch 2] [--width 1024] [--height 512] [--dtype bf16] [--codec]
-                            [--checkpoints_dir DIR] [--data DIR]
+                            [--checkpoints_dir DIR] [--data DIR] [--per-class] [--zero_sem] [--zero_ins] [--zero_vis]
 """
 import argparse
 import contextlib
@@ -49,12 +51,17 @@ def main():
   ap.add_argument('--codec', action='store_true', help='learned codec (netE + binarizer): also report bpp')
   ap.add_argument('--checkpoints_dir', default=None, help='load net_G.pth (and net_E.pth) from here')
   ap.add_argument('--data', default=None, help='directory of pre-decoded *.pt batches instead of synthetic ones')
+  ap.add_argument('--per-class', action='store_true', help='also print L1 / MSE / PSNR per semantic class')
+  for flag in ('zero_sem', 'zero_ins', 'zero_vis'):
+    ap.add_argument('--' + flag, action='store_true', help='ablation input of the reference (same flag)')
   args = ap.parse_args()
   import jpdse_hip
+  from jpdse_hip import ops
   from ctu.trainers import get_trainer
   from ctu.utils.synthetic import default_opt
   jpdse_hip.require_gpu(0)
-  kw = dict(gpu_ids=[0], print_losses=False, compute_dtype=args.dtype, ngf=args.ngf, batch_size=args.batch)
+  kw = dict(gpu_ids=[0], print_losses=False, compute_dtype=args.dtype, ngf=args.ngf, batch_size=args.batch,
+            zero_sem=args.zero_sem, zero_ins=args.zero_ins, zero_vis=args.zero_vis)
   if args.codec:
     kw.update(no_feat_encoding=False, no_encoder_binarization=False, feat_num=3, nef=args.ngf, n_downsample_E=4,
               encoder_binarizer_out_channels=128)
@@ -68,9 +75,13 @@ def main():
   by_batch = dict.fromkeys(keys + ('shannon', 'actual'), 0.0)
   by_image = dict.fromkeys(keys + ('shannon', 'actual'), 0.0)
   images, n_batches = 0, 0
+  class_sums = None                  # int64 [1, n_classes + 1, 3]: the raw class tables of every image so far, added up
   start = time.time()
   for i, x_dict in enumerate(batches(args)):
-    m = trainer.get_eval_metrics(x_dict)
+    m = trainer.get_eval_metrics(x_dict, per_class=args.per_class)
+    if args.per_class:
+      tab = m['per_class']['raw'].sum(dim=0, keepdim=True)
+      class_sums = tab if class_sums is None else class_sums + tab
     b = int(m['per_image']['l1'].numel())
     line = 'batch {}, recon loss (L1/MSE/MS-SSIM) {:.4f}/{:.4f}/{:.4f}, PSNR {:.3f} dB'.format(i + 1, m['l1'], m['mse'], m['ms_ssim'],
                                                                                          m['psnr'])
@@ -100,6 +111,17 @@ def main():
     return line
   print('\n' + summary('test set avg recon loss', by_batch, n_batches))
   print(summary('per-image avg recon loss', by_image, images) + '\n')
+  if args.per_class:
+    r = ops.eval_metrics_per_class(class_sums)
+    total = int(r['pixels'].sum()) + r['unlabelled']
+    print('per-class distortion over the test set (classes that occur; %d pixels, %d without a class)' % (total, r['unlabelled']))
+    print('{:>5} {:>12} {:>8} {:>9} {:>11} {:>9}'.format('class', 'pixels', 'share', 'L1', 'MSE', 'PSNR dB'))
+    for k in range(r['pixels'].numel()):
+      n = int(r['pixels'][k])
+      if n:
+        print('{:>5} {:>12} {:>7.2f}% {:>9.4f} {:>11.4f} {:>9.3f}'.format(k, n, 100.0 * n / total, float(r['l1'][k]),
+                                                                      float(r['mse'][k]), float(r['psnr'][k])))
+    print('')
 
 
 if __name__ == '__main__':
