@@ -1,8 +1,7 @@
 /*
  * jpdse_dev.h -- the extra entry points of the developer build libjpdse_hip_dev.so (compiled with -DJPDSE_DEV from
  * the same sources as libjpdse_hip.so).  Not part of the drop-in boundary: the shipped library neither exports this
- * symbols nor contains the run-time switches behind them (they are compile-time constants there) nor the timing-only
- * ablation kernels.  Used by scripts/ (same-process A/B measurements) and by the tests that compare two kernels of one
+ * symbols nor contains the run-time switches behind them (they are compile-time constants there).  Used by scripts/ (same-process A/B measurements) and by the tests that compare two kernels of one
  * layer with each other; no reference counterpart.
  */
 #ifndef JPDSE_DEV_H_
@@ -14,7 +13,7 @@
 extern "C" {
 #endif
 
-/* Developer A/B switch (kernel SELECTION only, results stay correct except for the timing-only ablation codes >= 100):
+/* Developer A/B switch (kernel SELECTION only: results stay correct under every code):
  * 0 = every convolution on the generic register-staged kernels; 1 (default) = all specialised bf16 kernels; 3 = no halo kernel;
  * 4 = no all-nine-taps weight gradient; 5 = heads without the Toeplitz GEMM; 6 = no split-K, no head kernel, no tap programs, no
  * persistent kernel (same summation order as the generic kernels: bit-comparable); 7 = reflect data gradient on the padded domain;
@@ -30,21 +29,24 @@ extern "C" {
  * the merged-phase fast kernel only; 43 = the same layers on the tap program + fringe (measured slower in the step);
  * 48 = fp32 generic kernel without split-K; 50 = the short-K layers on gemm_fast_kernel instead of the persistent form
  * (gemm_pers.h); 51 = every fast-kernel layer without split-K on the persistent form; 52 = the persistent form from one tile on
- * and for any K (tests); 53 / 56 = ResnetBlock / VGG forward on the four-wave / sixteen-wave halo kernels (gemm_halo4.h, gemm_halo16.h:
- * the wave-tile A/B of profiles/r04_halo_wavetile_ab.txt; results identical); 54 = dgrad2_rows with the timing-only conflict-free
- * addressing of round 4's first experiment (WRONG results); 55 = 32-pixel-wide 1024-channel weight gradients on the per-tap kernel
+ * and for any K (tests); 55 = 32-pixel-wide 1024-channel weight gradients on the per-tap kernel
  * instead of the row-pair nine-tap form; 57 = the 32 -> 3 head forward on head_fwd_kernel instead of head_rows_kernel<7, 32>;
  * 58 = all-taps weight gradient (wgrad_taps.h) with the tiles of a pixel range co-located on one XCD (measured slower);
  * 61 = the short-K whole-round layers on the persistent form (gemm_pers.h), as shipped during round 4 before the epilogue fix (50 is the default again);
  * 60 = halo kernel without the XCD-aware tile order on its one-round grids (15 / 16 / 17 force an order on every grid);
  * 59 = the few-tile medium-K layers of the fast kernel on 256-row tiles as before round 4;
- * 201 / 202 / 203 = timing-only ablations of that kernel's loop (no DMA after the prologue / no fragment reads and MFMAs / neither);
- * 210 = timing-only ablation of gemm_fast_kernel: activation tiles staged for one tap in four (WRONG results; persistent form off).
- * 100 + bits = timing-only ablations of the halo loop.
+ * Any other code that is not retired selects the shipped dispatch, like 1.
  * Retired in round 4 with their negative results on record (profiles/r0*_ab.txt; the code paths are gone):
  * 21 / 22 / 24 (unpipelined loop forms of the nine-tap weight gradient), 23 (halo kernel, staggered DMA issue), 25 (halo kernel,
  * hand-pipelined fragment reads), 30 (fast kernel, XCD-aware tile order), 31 (ring strips on 128-row tiles), 44 / 45 (3- / 4-stage
  * rings for the 128-row short-K configurations), 46 (no 64-row tiles for the short loops).
+ * Retired later, once their measurements were settled (the code paths are gone; these codes return JPDSE_EINVAL so that a sweep
+ * cannot measure the shipped dispatch under their label): 53 / 56 (halo forward on four / sixteen waves, gemm_halo4.h / gemm_halo16.h:
+ * profiles/r04_halo_wavetile_ab.txt), 54 (dgrad2_rows with conflict-free LDS addresses, timing only:
+ * profiles/r04_dgrad2_rows_conflicts_ab.txt), 100-199 (100 + bits: timing-only ablations of the halo loop:
+ * profiles/r01_ablation_resblock.txt, profiles/r04_virt_conflicts_ab.txt), 201-203 (timing-only ablations of the all-taps
+ * weight-gradient loop: profiles/r04_wgrad_taps_ab.txt), 210-225 (timing-only ablations of gemm_fast_kernel's loader, loop and
+ * epilogue: profiles/r04_fast_astage_ablation.txt, profiles/r04_epilogue_act_ab.txt).
  * Each call resets the others to their defaults. */
 int jpdse_debug_set_fast_path(int32_t enable);
 

@@ -128,26 +128,10 @@ static int conv_fwd_t(const jpdse_conv_desc* d, const ConvPlan& p, const void* x
     if (mom == nullptr && taps9_shape_ok(v)) return launch_taps9(v, reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + p.splitk_off), s);
     if (halo_ok(v)) {
       HaloArgs h = to_halo(v);
-      if (pool != nullptr && mom == nullptr && pooled != nullptr && !g_halo_abl) {
+      if (pool != nullptr && mom == nullptr && pooled != nullptr) {
         h.pool = reinterpret_cast<bf16_t*>(pool);
         *pooled = true;
       }
-#ifdef JPDSE_DEV
-      if (g_halo_abl && p.Ks > 64) {      // timing-only ablations (scripts/bench_conv.py --fast 11..)
-        switch (g_halo_abl) {
-          case 1: return launch_halo_cfg<2, 1>(h, s);
-          case 2: return launch_halo_cfg<2, 2>(h, s);
-          case 4: return launch_halo_cfg<2, 4>(h, s);
-          case 9: return launch_halo_cfg<2, 9>(h, s);
-          case 11: return launch_halo_cfg<2, 11>(h, s);
-          case 15: return launch_halo_cfg<2, 15>(h, s);
-          case 16: return launch_halo_cfg<2, 16>(h, s);
-          case 32: return launch_halo_cfg<2, 32>(h, s);
-          case 48: return launch_halo_cfg<2, 48>(h, s);
-          default: break;
-        }
-      }
-#endif
       return p.Ks > 64 ? launch_halo_cfg<2>(h, s) : launch_halo_cfg<1>(h, s);
     }
     if (p.Cs % 64 == 0 && fast_pays(d->N * p.OH * p.OW, p.Ks, d->R * d->S * p.Cs / 64)) {

@@ -29,7 +29,7 @@ static void fast_wgrad_partition(FastWgArgs* a, int lds) {
   a->slab_stride = ((long long)a->K * a->R * a->S * a->C + 3) / 4 * 4;
 }
 
-template <int WM, int WN, int TM, int TN, int ABL = 0>
+template <int WM, int WN, int TM, int TN>
 static int launch_wgrad_fast_cfg(FastWgArgs a, float* slabs, size_t* slab_bytes_out, hipStream_t s) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   constexpr int lds = 2 * 64 * 2 * (BM + BN);
@@ -38,11 +38,11 @@ static int launch_wgrad_fast_cfg(FastWgArgs a, float* slabs, size_t* slab_bytes_
     *slab_bytes_out = a.splits > 1 ? (size_t)a.splits * a.slab_stride * sizeof(float) : 0;
     return JPDSE_OK;
   }
-  if (int rc = opt_in_lds<&wgrad_fast_kernel<WM, WN, TM, TN, ABL>>("wgrad_fast", lds)) return rc;
+  if (int rc = opt_in_lds<&wgrad_fast_kernel<WM, WN, TM, TN>>("wgrad_fast", lds)) return rc;
   const int tiles = ((a.Ks + BM - 1) / BM) * (a.run_mode ? a.R : a.R * a.S) *
                     (((a.run_mode ? a.run_len : a.Cs) + BN - 1) / BN);
   a.partial = slabs;
-  hipLaunchKernelGGL((wgrad_fast_kernel<WM, WN, TM, TN, ABL>), dim3(tiles * a.splits), dim3(64 * WM * WN), lds, s, a);
+  hipLaunchKernelGGL((wgrad_fast_kernel<WM, WN, TM, TN>), dim3(tiles * a.splits), dim3(64 * WM * WN), lds, s, a);
   if (int rc = check_launch("wgrad_fast_kernel")) return rc;
   return a.splits > 1 ? launch_slab_reduce(slabs, a.DW, (long long)a.K * a.R * a.S * a.C, a.slab_stride, a.splits, s) : JPDSE_OK;
 }
@@ -137,7 +137,6 @@ static int launch_wgrad_thin(const ThinWgArgs& a, hipStream_t s) {
 // ---- all-taps weight gradient of the narrow high-resolution layers (wgrad_taps.h) -----------------
 // config id: 0 none; 1: 3x3 s2 K%128 C%64; 2: 3x3 s1 K%64 C%64; 3: 4x4 s2 K%128 C%64; 4: 3x3 s2 K%256 C%128
 JPDSE_SWITCH(int, g_wgrad_taps_enabled, 1);
-JPDSE_SWITCH(int, g_wgrad_taps_abl, 0);           // 200 + bits: timing-only ablations of the all-taps loop (developer build)
 JPDSE_SWITCH(int, g_wgrad_taps_xcd, 0);           // 58: XCD co-location of the tiles of a pixel range (A/B; measured 0-13 % slower)
 static int wgrad_taps_cfg(const jpdse_conv_desc* d, const ConvPlan& p) {
   if (!g_fast_enabled || !g_wgrad_taps_enabled || p.ES != 2 || d->R != d->S) return 0;
@@ -260,7 +259,6 @@ static int launch_wgrad_taps(const jpdse_conv_desc* d, const ConvPlan& p, int cf
   a.pad = d->pad;
   a.reflect = d->pad_mode == JPDSE_PAD_REFLECT;
   taps_partition(d, p, cfg, &a);
-  a.abl = g_wgrad_taps_abl;
   const int lds = taps_geom(cfg).lds;
   switch (cfg) {
     case 1: return launch_wgrad_taps_cfg<1, 4, 2, 3, 3, 2, 64, 2>(a, lds, s);
@@ -311,14 +309,14 @@ static size_t wgrad_nine_ws_bytes(const jpdse_conv_desc* d, const ConvPlan& p) {
   return a.splits > 1 ? (size_t)a.splits * d->K * 9 * d->C * sizeof(float) : 0;
 }
 
-template <bool REFLECT, int SCHED, bool W32 = false>
+template <bool REFLECT, bool W32 = false>
 static int launch_wgrad_nine_cfg(const NineWgArgs& a, hipStream_t s) {
-  if (int rc = opt_in_lds<&wgrad_nine_kernel<REFLECT, SCHED, 0, W32>>("wgrad_nine", kNineLds)) return rc;
+  if (int rc = opt_in_lds<&wgrad_nine_kernel<REFLECT, W32>>("wgrad_nine", kNineLds)) return rc;
   const int blocks = a.k_tiles * a.c_tiles * a.splits;
   if (W32 && (a.W != 32 || (a.H & 1) || a.chunks_total != a.N * (a.H / 2)))
     return set_error(JPDSE_EINVAL, "wgrad_nine: the row-pair form needs 32-pixel-wide images with an even number of rows");
   const int pslot = prof_begin(s, a.Ks, 9LL * a.Cs);
-  hipLaunchKernelGGL((wgrad_nine_kernel<REFLECT, SCHED, 0, W32>), dim3(blocks), dim3(512), kNineLds, s, a);
+  hipLaunchKernelGGL((wgrad_nine_kernel<REFLECT, W32>), dim3(blocks), dim3(512), kNineLds, s, a);
   if (int rc = check_launch("wgrad_nine_kernel")) return rc;
   if (a.splits > 1) {
     const long long n4 = (long long)a.K * 9 * a.C / 4;
@@ -346,9 +344,9 @@ static int launch_wgrad_nine(const jpdse_conv_desc* d, const ConvPlan& p, const 
   nine_partition(d, p, &a);
   if (a.splits > 1 && ((long long)d->K * 9 * d->C) % 4 != 0)
     return set_error(JPDSE_EINVAL, "wgrad_nine: K*9*C = %lld is not a multiple of 4", (long long)d->K * 9 * d->C);
-  if (p.OW % 64 != 0) return launch_wgrad_nine_cfg<true, 3, true>(a, s);          // wgrad_nine32_shape: reflect, W = 32
-  if (d->pad_mode != JPDSE_PAD_REFLECT) return launch_wgrad_nine_cfg<false, 3>(a, s);
-  return launch_wgrad_nine_cfg<true, 3>(a, s);
+  if (p.OW % 64 != 0) return launch_wgrad_nine_cfg<true, true>(a, s);          // wgrad_nine32_shape: reflect, W = 32
+  if (d->pad_mode != JPDSE_PAD_REFLECT) return launch_wgrad_nine_cfg<false>(a, s);
+  return launch_wgrad_nine_cfg<true>(a, s);
 }
 
 // heads with <= 8 output channels on a 32- / 64-channel input, stride 1 (64->3, 32->3 7x7)

@@ -19,9 +19,9 @@
 
 #include <vector>
 
-// Kernel-selection switches (which of two correct kernels runs) and timing-only ablations are DEVELOPER tools: in the
-// shipped library (libjpdse_hip.so) they are compile-time constants -- no mutable global state behind the ABI besides the
-// init-once launch attributes and the opt-in kernel timer -- and the ablation kernels are not even instantiated.  The
+// Kernel-selection switches (which of two correct kernels runs) are DEVELOPER tools: in the shipped library
+// (libjpdse_hip.so) they are compile-time constants -- no mutable global state behind the ABI besides the init-once
+// launch attributes and the opt-in kernel timer.  The
 // developer build (libjpdse_hip_dev.so, -DJPDSE_DEV, include/jpdse_dev.h) makes them run-time variables behind
 // jpdse_debug_set_fast_path for same-process A/B measurements and for the tests that compare two kernels of one layer.
 // (JPDSE_SWITCH itself lives in common.h.)
@@ -92,10 +92,6 @@ __device__ __forceinline__ float apply_act(float v, int act, float slope) {
 }  // namespace jpdse
 #include "gemm_fast.h"
 #include "gemm_halo.h"
-#ifdef JPDSE_DEV
-#include "gemm_halo4.h"
-#include "gemm_halo16.h"
-#endif
 #include "gemm_taps.h"
 #include "wgrad_fast.h"
 #include "wgrad_thin.h"
@@ -179,7 +175,11 @@ int jpdse_debug_occupy_cus(int32_t blocks, const int32_t* release_flag, int32_t 
 
 int jpdse_debug_set_fast_path(int32_t enable) {
   // 1 (any mode not named below): the shipped dispatch.  6 = fast kernels with the generic kernels' rounding points and summation
-  // order (it switches several paths off at once); 100-199, 200-203, 210-225 and 54: timing-only ablations, wrong results.
+  // order (it switches several paths off at once).  Retired codes (include/jpdse_dev.h: their code paths are gone) are refused, so
+  // that a sweep which still passes one does not measure the shipped dispatch under another label.
+  if (enable == 53 || enable == 54 || enable == 56 || (enable >= 100 && enable <= 199) || (enable >= 201 && enable <= 203) ||
+      (enable >= 210 && enable <= 225))
+    return set_error(JPDSE_EINVAL, "debug_set_fast_path: mode %d is retired (its code path was removed; see include/jpdse_dev.h)", (int)enable);
   g_fast_enabled = enable != 0;                          // 0: generic kernels only
   g_halo_enabled = enable != 3;                          // 3: fast kernels but no halo kernel (with the rows and ring paths off as well)
   g_moments_fused = enable != 32 && enable != 6;         // 32: InstanceNorm moments always in their own pass; 6
@@ -191,7 +191,6 @@ int jpdse_debug_set_fast_path(int32_t enable) {
   g_taps4_enabled = enable != 36 && enable != 6;         // 36: 4x4 stride-1 layers on the fast kernel alone; 6
   g_taps_enabled = enable != 35 && enable != 6;          // 35: stride-2 data gradients on the merged-phase fast kernel instead of the tap-program kernel; 6: tap outer, slab inner
   g_rows_enabled = enable != 29 && enable != 3;          // 29: 64-channel 3x3 layers on the halo / fast kernels instead of conv_rows; 3
-  g_halo_abl = (enable >= 100 && enable < 200) ? enable - 100 : 0;   // 100 + bits: timing-only ablations of the halo kernel (gemm_halo.h ABL)
   g_wgrad_nine_enabled = enable != 4;                    // 4: wide 3x3 layers on the per-tap fast weight gradient instead of the all-nine-taps one
   g_wgrad_taps_enabled = enable != 12;                   // 12: fast kernels without the all-taps weight gradient
   g_ring_enabled = enable != 7 && enable != 3;           // 7: reflect data gradient on the padded domain + fold; 3
@@ -210,18 +209,11 @@ int jpdse_debug_set_fast_path(int32_t enable) {
   g_pers_enabled = enable == 51 || enable == 52 || enable == 61;   // 51 / 52 / 61: the persistent form (off by default) ...
   g_pers_max_kt = (enable == 51 || enable == 52) ? (1 << 20) : 24;   // ... 51, 52: for any K; 61: up to 24 K-tiles, the round-4 rule
   g_pers_min_tiles = enable == 52 ? 1 : 256;             // ... 52: from one tile on (tests); 51, 61: on whole-round grids of >= 256 tiles
-  g_halo4 = enable == 53 ? 1 : (enable == 56 ? 16 : 0);  // 53: plain halo forward on the four-wave form (gemm_halo4.h); 56: on the sixteen-wave form (gemm_halo16.h)
   g_wgrad_nine32_enabled = enable != 55;                 // 55: the 1024-channel trunk at 16 x 32 on the per-tap weight-gradient kernel
   g_head_rows32 = enable != 57;                          // 57: the 32 -> 3 head forward on head_fwd_kernel
-  g_wgrad_taps_abl = (enable >= 200 && enable < 204) ? enable - 200 : 0;   // 201 / 202 / 203: all-taps weight gradient without DMA / without MFMAs / neither
-  // 210-219: the 256 x 128 fast configuration, 210 = activation tile staged for one tap in four, 210 + bits: 1 no DMA, 2 no barrier,
-  // 4 fragments of k-step 0 only, 8 no MFMAs; 220 no epilogue, 221 no K loop, 222 neither (launch + set-up only), 223 MFMA-only loop
-  // without epilogue; 224: no K loop, epilogue without its global stores; 225: whole kernel without the global stores of the epilogue
-  g_fast_abl = (enable >= 210 && enable < 220) ? (enable == 210 ? 16 : enable - 210) : (enable == 220 ? 32 : (enable == 221 ? 64 : (enable == 222 ? 96 : (enable == 223 ? 39 : (enable == 224 ? 192 : (enable == 225 ? 128 : 0))))));
   g_halo_xcd_auto = enable != 60;                        // 60: halo kernel, block b -> tile b on every grid (no XCD-aware order on the one-round grids)
   g_fast_fill = enable != 59;                            // 59: few-tile medium-K layers on the 256-row tiles as before round 4
   g_wgrad_taps_xcd = enable == 58;                       // 58: all-taps weight gradient with the tiles of a pixel range co-located on one XCD (slower)
-  g_dgrad2_noconf = enable == 54;                        // 54: dgrad2_rows_kernel with conflict-free LDS addresses
   g_generic_splitk = enable != 48;                       // 48: fp32 generic kernel without split-K
   g_splitk_enabled = enable != 6;                        // 6: no split-K on the fast kernels
   return JPDSE_OK;

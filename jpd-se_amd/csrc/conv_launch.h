@@ -227,12 +227,11 @@ static int launch_wgrad(const GemmWgradArgs& a, float* slabs, hipStream_t s) {
   return launch_wgrad_cfg<T, 32, 256, 1, 4>(a, slabs, s);
 }
 
-JPDSE_SWITCH(int, g_fast_abl, 0);                 // 210: timing-only ablation of the fast kernel (activation tiles staged for one tap in four)
-template <int WM, int WN, int TM, int TN, int VAR, int STAGES = 3>
+template <int WM, int WN, int TM, int TN, int STAGES = 3>
 static int launch_fast_cfg(FastBatch& b, hipStream_t s) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   constexpr int lds = STAGES * (BM + BN) * 128;
-  if (int rc = opt_in_lds<&gemm_fast_kernel<WM, WN, TM, TN, VAR, STAGES>>("gemm_fast", lds)) return rc;
+  if (int rc = opt_in_lds<&gemm_fast_kernel<WM, WN, TM, TN, STAGES>>("gemm_fast", lds)) return rc;
   int total = 0;
   for (int i = 0; i < b.n; ++i) {
     const FastArgs& a = b.p[i];
@@ -251,14 +250,13 @@ static int launch_fast_cfg(FastBatch& b, hipStream_t s) {
         return set_error(JPDSE_EINVAL, "gemm_fast: problem %d addresses element %lld of a %lld-element input", i, last, a.x_extent);
     }
     b.first_tile[i] = total;
-    b.p[i].abl = g_fast_abl;
     b.p[i].xcd_map = 0;       // (the XCD-aware tile order, round-3 developer mode 30, measured neutral and was retired: DESIGN.md 4.1 (xi))
     total += ((a.M + BM - 1) / BM) * ((a.Ks + BN - 1) / BN) * (a.splits > 1 ? a.splits : 1);
   }
   for (int i = b.n; i < 5; ++i) b.first_tile[i] = total;
   const long long kdim = (long long)b.p[0].R * b.p[0].S * b.p[0].Cs;
   const int pslot = b.n == 1 ? prof_begin(s, b.p[0].Ks, kdim) : -1;      // a multi-problem launch is not one GEMM: not timed
-  hipLaunchKernelGGL((gemm_fast_kernel<WM, WN, TM, TN, VAR, STAGES>), dim3(total), dim3(64 * WM * WN), lds, s, b);
+  hipLaunchKernelGGL((gemm_fast_kernel<WM, WN, TM, TN, STAGES>), dim3(total), dim3(64 * WM * WN), lds, s, b);
   if (b.n == 1 && b.p[0].splits > 1 && !b.p[0].no_finish) {
     const long long total_vec = (long long)b.p[0].M * (b.p[0].Ks / 8);
     hipLaunchKernelGGL(splitk_finish_kernel, dim3(ew_blocks(total_vec)), dim3(256), 0, s, b.p[0], total_vec);
@@ -341,67 +339,47 @@ static int launch_fast_batch(FastBatch& b, hipStream_t s) {
   if (b.n <= 0) return JPDSE_OK;
   const int Ks = b.p[0].Ks;
   if (b.n == 1 && b.p[0].splits > 1) {   // split-K
-    if (Ks > 64) return launch_fast_cfg<4, 2, 2, 2, 0>(b, s);
-    if (Ks > 32) return launch_fast_cfg<4, 2, 2, 1, 0>(b, s);
-    return launch_fast_cfg<8, 1, 1, 1, 0>(b, s);
+    if (Ks > 64) return launch_fast_cfg<4, 2, 2, 2>(b, s);
+    if (Ks > 32) return launch_fast_cfg<4, 2, 2, 1>(b, s);
+    return launch_fast_cfg<8, 1, 1, 1>(b, s);
   }
   for (int i = 0; i < b.n; ++i)
     if (b.n > 1 && !b.p[i].no_finish) b.p[i].splits = 1;
   if (pers_ok(b)) return launch_pers(b, s);
   if (b.small_m) {
-    if (Ks > 64) return launch_fast_cfg<2, 2, 2, 2, 0, 2>(b, s);
-    if (Ks > 32) return launch_fast_cfg<2, 2, 2, 1, 0, 2>(b, s);
+    if (Ks > 64) return launch_fast_cfg<2, 2, 2, 2, 2>(b, s);
+    if (Ks > 32) return launch_fast_cfg<2, 2, 2, 1, 2>(b, s);
   }
   int kt = 0;
   for (int i = 0; i < b.n; ++i) {
     const int k = b.p[i].R * b.p[i].S * (b.p[i].Cs / 64);
     kt = k > kt ? k : kt;
   }
-  if (g_fast_small && kt <= g_fast_small && b.p[0].splits <= 1 && !g_fast_abl) {
+  if (g_fast_small && kt <= g_fast_small && b.p[0].splits <= 1) {
     // short reductions are prologue / epilogue bound: 128-row tiles, 4 waves, 2 stages = 64 (48) KiB of LDS, so two
     // (three) blocks share a CU and overlap each other's fill and store phases
     // (deeper rings for the same tiles -- round-3 developer modes 44 / 45 -- measured 25-50 % slower: profiles/r03_fast_stages_ab.txt)
     // up to 16 K-tiles and wide outputs: 64 x 128 tiles (48 KiB of LDS, three blocks per CU).  Measured per layer in one process
     // (profiles/r03_fast_tile64_ab.txt): PatchGAN layer 1 forward +7 % / +32 % (first / second scale), layer 2 data gradient
     // +10 % / +24 %; longer loops (18-32 tiles) and the 64-wide outputs (64 x 64 tiles) lose 3-6 % and keep the 128-row tiles.
-    if (Ks > 64 && kt <= 16) return launch_fast_cfg<2, 2, 1, 2, 0, 2>(b, s);   // 64 x 128
-    if (Ks > 64) return launch_fast_cfg<2, 2, 2, 2, 0, 2>(b, s);   // 128 x 128
-    if (Ks > 32) return launch_fast_cfg<2, 2, 2, 1, 0, 2>(b, s);   // 128 x 64
+    if (Ks > 64 && kt <= 16) return launch_fast_cfg<2, 2, 1, 2, 2>(b, s);   // 64 x 128
+    if (Ks > 64) return launch_fast_cfg<2, 2, 2, 2, 2>(b, s);   // 128 x 128
+    if (Ks > 32) return launch_fast_cfg<2, 2, 2, 1, 2>(b, s);   // 128 x 64
   }
-  if (g_fast_fill && Ks > 64 && kt <= 64 && b.p[0].splits <= 1 && !g_fast_abl) {
+  if (g_fast_fill && Ks > 64 && kt <= 64 && b.p[0].splits <= 1) {
     // Few tiles, medium K (round 4): 256-row tiles of a small layer leave most of the chip idle (PatchGAN layer 2 of the second scale:
     // 17,160 pixels x 256 channels = 136 tiles for 256 CUs, 279 TFLOP/s).  Smaller tiles of the same loop (same summation order) fill it.
     long long t256 = 0;
     for (int i = 0; i < b.n; ++i) t256 += (long long)((b.p[i].M + 255) / 256) * ((Ks + 127) / 128);
     if (t256 < 224) {
-      if (t256 < 160) return launch_fast_cfg<2, 2, 1, 2, 0, 2>(b, s);   // 64 x 128
-      return launch_fast_cfg<2, 2, 2, 2, 0, 2>(b, s);                    // 128 x 128
+      if (t256 < 160) return launch_fast_cfg<2, 2, 1, 2, 2>(b, s);   // 64 x 128
+      return launch_fast_cfg<2, 2, 2, 2, 2>(b, s);                    // 128 x 128
     }
   }
-  if (b.n == 1 && prefer_320(b.p[0].M, Ks)) return launch_fast_cfg<2, 4, 5, 1, 0, 2>(b, s);   // 320 x 128, 2 stages
-#ifdef JPDSE_DEV
-  if (Ks > 64 && g_fast_abl) {
-    switch (g_fast_abl) {
-      case 1: return launch_fast_cfg<4, 2, 2, 2, 1>(b, s);
-      case 2: return launch_fast_cfg<4, 2, 2, 2, 2>(b, s);
-      case 4: return launch_fast_cfg<4, 2, 2, 2, 4>(b, s);
-      case 5: return launch_fast_cfg<4, 2, 2, 2, 5>(b, s);
-      case 8: return launch_fast_cfg<4, 2, 2, 2, 8>(b, s);
-      case 9: return launch_fast_cfg<4, 2, 2, 2, 9>(b, s);
-      case 7: return launch_fast_cfg<4, 2, 2, 2, 7>(b, s);
-      case 32: return launch_fast_cfg<4, 2, 2, 2, 32>(b, s);
-      case 64: return launch_fast_cfg<4, 2, 2, 2, 64>(b, s);
-      case 96: return launch_fast_cfg<4, 2, 2, 2, 96>(b, s);
-      case 39: return launch_fast_cfg<4, 2, 2, 2, 39>(b, s);
-      case 192: return launch_fast_cfg<4, 2, 2, 2, 192>(b, s);
-      case 128: return launch_fast_cfg<4, 2, 2, 2, 128>(b, s);
-      default: return launch_fast_cfg<4, 2, 2, 2, 16>(b, s);
-    }
-  }
-#endif
-  if (Ks > 64) return launch_fast_cfg<4, 2, 2, 2, 0>(b, s);   // 256 x 128
-  if (Ks > 32) return launch_fast_cfg<4, 2, 2, 1, 0>(b, s);   // 256 x 64
-  return launch_fast_cfg<8, 1, 1, 1, 0>(b, s);                // 256 x 32
+  if (b.n == 1 && prefer_320(b.p[0].M, Ks)) return launch_fast_cfg<2, 4, 5, 1, 2>(b, s);   // 320 x 128, 2 stages
+  if (Ks > 64) return launch_fast_cfg<4, 2, 2, 2>(b, s);   // 256 x 128
+  if (Ks > 32) return launch_fast_cfg<4, 2, 2, 1>(b, s);   // 256 x 64
+  return launch_fast_cfg<8, 1, 1, 1>(b, s);                // 256 x 32
 }
 
 static int launch_fast(const FastArgs& a, hipStream_t s) {
@@ -444,14 +422,13 @@ JPDSE_SWITCH(int, g_merge_min_kt, 4);
 JPDSE_SWITCH(int, g_merge_min_tiles, 64);    // merged stride-phase data gradient on the fast kernel from this many 256-row tiles on (26: 384 as in round 1, A/B)
 JPDSE_SWITCH(int, g_halo_single, 1);
 JPDSE_SWITCH(int, g_halo_enabled, 1);
-JPDSE_SWITCH(int, g_halo_abl, 0);
 
-template <int TN, int ABL = 0, bool SINGLE = false, bool MF16 = false, bool MOM = false, bool VIRT = false, bool NSUM = false>
+template <int TN, bool SINGLE = false, bool MF16 = false, bool MOM = false, bool VIRT = false, bool NSUM = false>
 static int launch_halo_cfg_impl(const HaloArgs& a, hipStream_t s) {
   constexpr int BN = 2 * TN * 32;
   constexpr int UH = ((4 + 2) * (64 + 2) + 7) / 8;
   constexpr int lds = (SINGLE ? 1 : 2) * UH * 1024 + 3 * BN * 128;
-  if (int rc = opt_in_lds<&gemm_halo_kernel<4, TN, ABL, SINGLE, MF16, MOM, VIRT, NSUM>>("gemm_halo", lds)) return rc;
+  if (int rc = opt_in_lds<&gemm_halo_kernel<4, TN, SINGLE, MF16, MOM, VIRT, NSUM>>("gemm_halo", lds)) return rc;
   if (int rc = check_tile_grid("gemm_halo", a.N, a.OH, a.OW, 4, 64, a.Cs, (long long)a.N * a.IH * a.IW * a.Cs, (long long)a.N * a.OH * a.OW * a.Ks)) return rc;
   if (VIRT && (a.V == nullptr || a.py != 1 || a.px != 1 || a.IH != a.OH || a.IW != a.OW || a.OH < 8 || a.reflect || (a.Cs < 128) != SINGLE))
     return set_error(JPDSE_EINVAL, "gemm_halo: folded-frame form needs a frame, pad 1, equal grids, >= 8 rows");
@@ -464,42 +441,10 @@ static int launch_halo_cfg_impl(const HaloArgs& a, hipStream_t s) {
   const long long kdim = 9LL * a.Cs;
   const int M = a.N * a.OH * a.OW;
   const int pslot = prof_begin(s, a.Ks, kdim);
-  hipLaunchKernelGGL((gemm_halo_kernel<4, TN, ABL, SINGLE, MF16, MOM, VIRT, NSUM>), dim3(tiles), dim3(512), lds, s, a);
+  hipLaunchKernelGGL((gemm_halo_kernel<4, TN, SINGLE, MF16, MOM, VIRT, NSUM>), dim3(tiles), dim3(512), lds, s, a);
   prof_end(pslot, 0, 2.0 * (double)M * (double)a.Ks * (double)kdim, s);
   return check_launch("gemm_halo_kernel");
 }
-
-#ifdef JPDSE_DEV
-// developer A/B (mode 53): the plain forward launch of the 128-channel-tile halo kernel on the four-wave form (gemm_halo4.h)
-static int g_halo4 = 0;
-static int launch_halo4(const HaloArgs& a, hipStream_t s) {
-  constexpr int UH = ((4 + 2) * (64 + 2) + 7) / 8;
-  constexpr int lds = 2 * UH * 1024 + 3 * 128 * 128;
-  if (int rc = opt_in_lds<&gemm_halo4_kernel>("gemm_halo4", lds)) return rc;
-  if (int rc = check_tile_grid("gemm_halo4", a.N, a.OH, a.OW, 4, 64, a.Cs, (long long)a.N * a.IH * a.IW * a.Cs, (long long)a.N * a.OH * a.OW * a.Ks)) return rc;
-  if (a.Cs < 128 || a.Ks % 128 != 0) return set_error(JPDSE_EINVAL, "gemm_halo4: needs >= 128 input channels and 128-channel output tiles");
-  const int tiles = a.N * (a.OH / 4) * (a.OW / 64) * (a.Ks / 128);
-  const long long kdim = 9LL * a.Cs;
-  const int pslot = prof_begin(s, a.Ks, kdim);
-  hipLaunchKernelGGL(gemm_halo4_kernel, dim3(tiles), dim3(256), lds, s, a);
-  prof_end(pslot, 0, 2.0 * (double)a.N * a.OH * a.OW * (double)a.Ks * (double)kdim, s);
-  return check_launch("gemm_halo4_kernel");
-}
-#endif
-
-#ifdef JPDSE_DEV
-// developer A/B (mode 56): the same launch on the sixteen-wave form (gemm_halo16.h)
-static int launch_halo16(const HaloArgs& a, hipStream_t s) {
-  constexpr int UH = ((4 + 2) * (64 + 2) + 7) / 8;
-  constexpr int lds = 2 * UH * 1024 + 3 * 128 * 128;
-  if (int rc = opt_in_lds<&gemm_halo16_kernel>("gemm_halo16", lds)) return rc;
-  if (int rc = check_tile_grid("gemm_halo16", a.N, a.OH, a.OW, 4, 64, a.Cs, (long long)a.N * a.IH * a.IW * a.Cs, (long long)a.N * a.OH * a.OW * a.Ks)) return rc;
-  if (a.Cs < 128 || a.Ks % 128 != 0) return set_error(JPDSE_EINVAL, "gemm_halo16: needs >= 128 input channels and 128-channel output tiles");
-  const int tiles = a.N * (a.OH / 4) * (a.OW / 64) * (a.Ks / 128);
-  hipLaunchKernelGGL(gemm_halo16_kernel, dim3(tiles), dim3(1024), lds, s, a);
-  return check_launch("gemm_halo16_kernel");
-}
-#endif
 
 JPDSE_SWITCH(int, g_halo_xcd, 0);
 // One-round grids of the multi-slab form (the ResnetBlock convs: 32 patches x 8 channel tiles on 256 CUs): XCD-aware tile order 2 -- an XCD
@@ -508,7 +453,7 @@ JPDSE_SWITCH(int, g_halo_xcd, 0);
 // on multi-round and single-slab grids the same order costs 1-4 %, so it is not used there.  60: off (A/B).
 JPDSE_SWITCH(int, g_halo_xcd_auto, 1);
 JPDSE_SWITCH(int, g_halo_mf16, 0);     // measured: 1020 vs 1032 TFLOP/s on the ResnetBlock conv -- the kernel is not MFMA-clock bound
-template <int TN, int ABL = 0>
+template <int TN>
 static int launch_halo_cfg(const HaloArgs& a0, hipStream_t s) {
   HaloArgs a = a0;
   a.xcd_mode = g_halo_xcd;
@@ -517,33 +462,26 @@ static int launch_halo_cfg(const HaloArgs& a0, hipStream_t s) {
     if (g_halo_xcd == 0 && g_halo_xcd_auto && a.Cs > 64 && blocks <= 256 && blocks % 8 == 0) a.xcd_mode = 2;
   }
   if (a.V != nullptr) {                   // reflect data gradient with the folded frame
-    if constexpr (ABL == 0 && TN == 2) {
+    if constexpr (TN == 2) {
       if (a.nsums != nullptr) {           // ... and the sums of the InstanceNorm backward that consumes its output
         if (a.Cs == 64) return set_error(JPDSE_EINVAL, "gemm_halo: norm-backward sums are built for the double-buffered form (>= 128 input channels)");
-        return launch_halo_cfg_impl<TN, 0, false, false, false, true, true>(a, s);
+        return launch_halo_cfg_impl<TN, false, false, false, true, true>(a, s);
       }
     }
     if (a.nsums != nullptr) return set_error(JPDSE_EINVAL, "gemm_halo: norm-backward sums need the 128-channel tile");
-    if constexpr (ABL == 0) {
-      if (a.Cs == 64) return launch_halo_cfg_impl<TN, 0, true, false, false, true>(a, s);     // one slab: single patch buffer
-      return launch_halo_cfg_impl<TN, 0, false, false, false, true>(a, s);
-    }
+    if (a.Cs == 64) return launch_halo_cfg_impl<TN, true, false, false, true>(a, s);     // one slab: single patch buffer
+    return launch_halo_cfg_impl<TN, false, false, false, true>(a, s);
   }
-  if (a.mom != nullptr) {                 // conv -> InstanceNorm with the moments in this kernel's epilogue (double-buffered form)
-    if constexpr (ABL == 0) return launch_halo_cfg_impl<TN, 0, false, false, true>(a, s);
-  }
+  // conv -> InstanceNorm with the moments in this kernel's epilogue (double-buffered form)
+  if (a.mom != nullptr) return launch_halo_cfg_impl<TN, false, false, true>(a, s);
 #ifdef JPDSE_DEV
-  if (ABL == 0 && TN == 2 && g_halo4 == 16 && a.Cs >= 128 && a.Ks % 128 == 0 && a.pool == nullptr && a.mask == nullptr && a.addend == nullptr)
-    return launch_halo16(a, s);
-  if (ABL == 0 && TN == 2 && g_halo4 == 1 && a.Cs >= 128 && a.Ks % 128 == 0 && a.pool == nullptr && a.mask == nullptr && a.addend == nullptr)
-    return launch_halo4(a, s);
-  if (ABL == 0 && g_halo_mf16) {
-    if (a.Cs == 64 && g_halo_single) return launch_halo_cfg_impl<TN, 0, true, true>(a, s);
-    return launch_halo_cfg_impl<TN, 0, false, true>(a, s);
+  if (g_halo_mf16) {
+    if (a.Cs == 64 && g_halo_single) return launch_halo_cfg_impl<TN, true, true>(a, s);
+    return launch_halo_cfg_impl<TN, false, true>(a, s);
   }
 #endif
-  if (a.Cs == 64 && ABL == 0 && g_halo_single) return launch_halo_cfg_impl<TN, 0, true>(a, s);   // one slab: single patch buffer
-  return launch_halo_cfg_impl<TN, ABL, false>(a, s);
+  if (a.Cs == 64 && g_halo_single) return launch_halo_cfg_impl<TN, true>(a, s);   // one slab: single patch buffer
+  return launch_halo_cfg_impl<TN, false>(a, s);
 }
 
 
@@ -612,26 +550,16 @@ static int launch_rows(const RowsArgs& a, int stride, hipStream_t s) {
 
 
 // data gradient of the 64 -> 128 3x3 stride-2 conv / forward of the 128 -> 64 ConvTranspose2d at full resolution (dgrad2_rows.h)
-JPDSE_SWITCH(int, g_dgrad2_noconf, 0);    // 54: TIMING-ONLY ablation, conflict-free LDS addresses (developer build)
 static int launch_dgrad2_rows(Dgrad2Args a, hipStream_t s) {
   typedef Dgrad2Geom G;
-  if (int rc = opt_in_lds<&dgrad2_rows_kernel<false>>("dgrad2_rows", G::LDS)) return rc;
-#ifdef JPDSE_DEV
-  if (int rc = opt_in_lds<&dgrad2_rows_kernel<true>>("dgrad2_rows", G::LDS)) return rc;
-#endif
+  if (int rc = opt_in_lds<&dgrad2_rows_kernel>("dgrad2_rows", G::LDS)) return rc;
   if (int rc = check_tile_grid("dgrad2_rows", a.N, a.OH, a.OW, 4, 64, 128, (long long)a.N * a.OH * a.OW * 128, 4LL * a.N * a.OH * a.OW * 64)) return rc;
   a.strips = a.OW / 64;
   const int th = rows_band_height(a.N, a.OH, a.strips, 1, 256);
   a.TH = th;
   a.bands = a.OH / th;
   a.mom_slots = a.bands * a.strips;
-#ifdef JPDSE_DEV
-  if (g_dgrad2_noconf) {      // timing-only ablation (developer mode 54): conflict-free LDS addresses, wrong results
-    hipLaunchKernelGGL(dgrad2_rows_kernel<true>, dim3((unsigned)(a.N * a.bands * a.strips)), dim3(256), G::LDS, s, a);
-    return check_launch("dgrad2_rows_kernel<noconf>");
-  }
-#endif
-  hipLaunchKernelGGL(dgrad2_rows_kernel<false>, dim3((unsigned)(a.N * a.bands * a.strips)), dim3(256), G::LDS, s, a);
+  hipLaunchKernelGGL(dgrad2_rows_kernel, dim3((unsigned)(a.N * a.bands * a.strips)), dim3(256), G::LDS, s, a);
   return check_launch("dgrad2_rows_kernel");
 }
 
@@ -1167,7 +1095,7 @@ static int conv_fwd_moment_slots(const jpdse_conv_desc* d, const ConvPlan& p) {
       taps9_shape_ok(d->R, d->S, d->stride, p.OH, p.OW, p.Cs, p.Ks, (long long)d->N * d->H * d->W * p.Cs, (long long)p.Ks * 9 * p.Cs))
     return 0;
   // halo kernel (double-buffered form: inputs of 128+ channels): one slot per 4 x 64 output patch
-  if (halo_ok(d->R, d->S, d->stride, p.OH, p.OW, p.Cs, p.Ks) && p.Cs > 64 && g_halo_abl == 0) return (p.OH / 4) * (p.OW / 64);
+  if (halo_ok(d->R, d->S, d->stride, p.OH, p.OW, p.Cs, p.Ks) && p.Cs > 64) return (p.OH / 4) * (p.OW / 64);
   return 0;
 }
 static bool dgrad2_rows_takes(const jpdse_conv_desc* d, const ConvPlan& p) {

@@ -51,7 +51,6 @@ struct FastArgs {
   int no_finish;       // split-K: leave the slabs to the caller (no splitk_finish_kernel)
   long long x_extent;  // elements readable from X (0 = not given): the launcher refuses a problem whose last pixel lies beyond
   int xcd_map;         // N-tiles of an M-tile on consecutive slots of one XCD (set by the launcher)
-  int abl;             // unused by the kernel (the ablations are compile-time VAR bits); kept so that the struct layout does not depend on the build
 };
 
 // Up to 4 independent problems in one launch (the stride-2 sub-pixel phases of a data gradient /
@@ -86,7 +85,7 @@ __device__ __forceinline__ int swz128(int row, int slot) { return (row << 7) + (
 // The activation is a COMPILE-TIME parameter of the body and the run-time `act` is dispatched once around it (round 4): with
 // apply_act(v, act, slope) called per value, hipcc kept the four-way choice -- incl. the tanh expansion -- as scalar branches
 // around every one of the 64 values of a wave: ~7,900 instructions and 557 branches behind the last MFMA of the halo kernel,
-// 6-8 us per 256 x 128 tile (timing-only ablations, profiles/r04_fast_astage_ablation.txt).  The lane-pair exchange is a DPP
+// 6-8 us per 256 x 128 tile (timing-only ablations since removed: DESIGN.md 4.1 (xxvii)).  The lane-pair exchange is a DPP
 // quad permute (no LDS round trip), as in the row-streaming kernels.
 __device__ __forceinline__ float pair_swap(float v) {      // value of lane ^ 1
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));
@@ -218,13 +217,11 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// VAR: 0 in every shipped instantiation; the developer build instantiates timing-only ablations of two configurations
-// (bits documented at the loader; modes 210-219 of jpdse_debug_set_fast_path).  (A software-pipelined fragment schedule was
-// measured 2-3 % SLOWER than the plain one in the same process and removed.)
+// (A software-pipelined fragment schedule was measured 2-3 % SLOWER than the plain one in the same process and removed.)
 // STAGES = 3: ring with one tile in flight across the barrier (counted vmcnt).  STAGES = 2 (used by
 // the 320-row tile, whose 3-stage ring would not fit 160 KiB): next tile issued right after the barrier,
 // vmcnt(0) at the following one.
-template <int WM, int WN, int TM, int TN, int VAR, int STAGES>
+template <int WM, int WN, int TM, int TN, int STAGES>
 __global__ __launch_bounds__(64 * WM * WN) void gemm_fast_kernel(const FastBatch batch) {
   int q = 0;
 #pragma unroll
@@ -366,23 +363,18 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_fast_kernel(const FastBatch
       a_step[i] = ok ? 64 : 0;
     }
   };
-  bool primed = false;                   // VAR & 1: set after the prologue issues
   auto issue = [&]() {
     char* const st = smem + istage * STAGE_BYTES;
     if (ic == 0) retap();
-    // VAR (developer build, timing only, wrong results): 1 = no DMA after the prologue tiles, 2 = no barrier, 4 = fragments read for k-step 0 only,
-    // 8 = no MFMAs (fragment reads kept alive), 16 = activation tile staged for one tap in four (the waits then pass early: optimistic),
-    // 32 = no epilogue, 64 = no K loop
-    const bool skip_a = (VAR & 16) != 0 && ((ir * a.S + is) & 3) != 0;
 #pragma unroll
     for (int i = 0; i < AU; ++i) {
-      if (!skip_a && !((VAR & 1) && primed)) glds16(a_src[i], st + a_lds[i]);
+      glds16(a_src[i], st + a_lds[i]);
       a_src[i] += a_step[i];
     }
     const long long koff = (long long)ir * b_tap_r + is * b_tap_s + ic * 64;
 #pragma unroll
     for (int j = 0; j < BU; ++j)
-      if (b_on[j] && !((VAR & 1) && primed)) glds16(b_ptr[j] + koff, st + b_lds[j]);
+      if (b_on[j]) glds16(b_ptr[j] + koff, st + b_lds[j]);
     if (++ic == CC) {
       ic = 0;
       if (++is == a.S) { is = 0; ++ir; }
@@ -402,8 +394,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_fast_kernel(const FastBatch
   if (AHEAD > 1 && T_total > 1) issue();
   if (AHEAD > 2 && T_total > 2) issue();
   int cstage = 0;
-  primed = true;
-  for (int t = 0; t < ((VAR & 64) ? 0 : T_total); ++t) {      // VAR & 64 (timing only): no loop at all -- prologue (+ epilogue) alone
+  for (int t = 0; t < T_total; ++t) {
     if (AHEAD > 2 && t + 2 < T_total) {
       wait_vmcnt<2 * (AU + BU)>();            // tiles t+1 and t+2 stay in flight
     } else if (AHEAD > 1 && t + 1 < T_total) {
@@ -412,47 +403,28 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_fast_kernel(const FastBatch
     } else {
       wait_vmcnt<0>();
     }
-    if (!(VAR & 2)) __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_s_barrier();
     const char* const st = smem + cstage * STAGE_BYTES;
     if (t + AHEAD < T_total) issue();
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       s16x8 af[TM], bf[TN];
-      const int ks_r = (VAR & 4) ? 0 : ks;
 #pragma unroll
-      for (int i = 0; i < TM; ++i) af[i] = *reinterpret_cast<const s16x8*>(st + a_rd[i][ks_r]);
+      for (int i = 0; i < TM; ++i) af[i] = *reinterpret_cast<const s16x8*>(st + a_rd[i][ks]);
 #pragma unroll
-      for (int j = 0; j < TN; ++j) bf[j] = *reinterpret_cast<const s16x8*>(st + b_rd[j][ks_r]);
-      if constexpr ((VAR & 8) != 0) {
+      for (int j = 0; j < TN; ++j) bf[j] = *reinterpret_cast<const s16x8*>(st + b_rd[j][ks]);
 #pragma unroll
-        for (int i = 0; i < TM; ++i) asm volatile("" :: "v"(af[i]));
+      for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) asm volatile("" :: "v"(bf[j]));
-      } else {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bf[j], acc[i][j], 0, 0, 0);
-      }
+        for (int j = 0; j < TN; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bf[j], acc[i][j], 0, 0, 0);
     }
     __builtin_amdgcn_s_setprio(0);
     cstage = cstage == STAGES - 1 ? 0 : cstage + 1;
   }
 
   // ---- epilogue --------------------------------------------------------------------------
-  if constexpr ((VAR & 32) != 0) {        // timing only: no epilogue (one store per thread keeps the accumulators alive)
-    float keep = 0.f;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) keep += acc[i][j][e];
-    if (keep == 12345.678f) a.Y[0] = 0;
-    return;
-  }
   if (a.splits > 1 || a.no_finish) {
     float* const slab = a.partial + (long long)split * a.M * a.Ks;
 #pragma unroll
@@ -521,11 +493,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_fast_kernel(const FastBatch
     const int row = idx / VPR, v = idx - row * VPR;
     const long long off = row_off[row];
     if (off < 0 || n0 + v * 8 >= a.Ks) continue;
-    if constexpr ((VAR & 128) != 0) {      // timing only: the staging without the global stores (one conditional store keeps the reads alive)
-      const u32x4 val = *reinterpret_cast<const u32x4*>(tile + row * PITCH + v * 16);
-      if (val[0] == 0x12345678u && val[3] == 0x9abcdef0u) *reinterpret_cast<u32x4*>(a.Y + off + n0 + v * 8) = val;
-      continue;
-    }
     *reinterpret_cast<u32x4*>(a.Y + off + n0 + v * 8) = *reinterpret_cast<const u32x4*>(tile + row * PITCH + v * 16);
   }
 }

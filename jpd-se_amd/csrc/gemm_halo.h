@@ -55,9 +55,6 @@ struct HaloArgs {
   float nslope;
 };
 
-// ABL: timing-only ablation bits (results are wrong when non-zero): 1 = no DMA after the prologue,
-// 2 = no barrier, 4 = fragments read once per tap-group only (no per-k-step LDS reads), 8 = no vmcnt waits,
-// 16 = every block reads the same weight rows, 32 = every block reads the same input patch (both: L2 hits only)
 // SINGLE: one patch buffer instead of two -- for 64-channel inputs (one slab per tile, nothing to prefetch).
 // With the 64-wide N tile the block then needs 74 KiB of LDS and TWO blocks share a CU, overlapping one
 // block's patch load / epilogue with the other's MFMAs (these K = 576 layers are prologue-bound).
@@ -72,7 +69,7 @@ struct HaloArgs {
 // that hold the zero padding otherwise; the reads that must still see that padding (output row 0 at u = 0, ...) go to a zero
 // pixel in the slack of the patch buffer.  Costs an add and a min per fragment address and tap; replaces the four ring-strip
 // GEMMs + ring_fold_kernel.  Needs py = px = 1, IH = OH, IW = OW, OH >= 8.
-template <int TH, int TN, int ABL = 0, bool SINGLE = false, bool MF16 = false, bool MOM = false, bool VIRT = false, bool NSUM = false>
+template <int TH, int TN, bool SINGLE = false, bool MF16 = false, bool MOM = false, bool VIRT = false, bool NSUM = false>
 __global__ __launch_bounds__(512) void gemm_halo_kernel(const HaloArgs a) {
   constexpr int R = 3, S = 3, TAPS = 9;
   constexpr int NW = 8, WN = 2;                       // waves: TH (=4) x 2
@@ -138,7 +135,7 @@ __global__ __launch_bounds__(512) void gemm_halo_kernel(const HaloArgs a) {
     b_on[j] = u < B_UNITS;
     const int uu = b_on[j] ? u : 0;
     const int row = uu * 8 + lrow;
-    int br = ((ABL & 16) ? 0 : n0) + row;       // ABL 16: every block streams the SAME weight rows (L2-resident)
+    int br = n0 + row;
     br = br < a.b_rows ? br : a.b_rows - 1;
     b_ptr[j] = a.B + (long long)br * ktot + (MF16 ? (lslot ^ (row & 6)) : ((lslot ^ (row >> 1)) & 7)) * 8;
     b_lds[j] = uu * 1024;
@@ -165,7 +162,7 @@ __global__ __launch_bounds__(512) void gemm_halo_kernel(const HaloArgs a) {
     const bool slack = p >= NP;
     p = p < NP ? p : NP - 1;
     const int hr = p / PW, wc = p - hr * PW;
-    int ih = ((ABL & 32) ? 0 : oh0) - a.py + hr, iw = ((ABL & 32) ? 0 : ow0) - a.px + wc;   // ABL 32: same patch
+    int ih = oh0 - a.py + hr, iw = ow0 - a.px + wc;
     bool ok = true;
     if (a.reflect) {
       ih = ih < 0 ? -ih : (ih >= a.IH ? 2 * (a.IH - 1) - ih : ih);
@@ -174,7 +171,7 @@ __global__ __launch_bounds__(512) void gemm_halo_kernel(const HaloArgs a) {
       ok = ((unsigned)ih < (unsigned)a.IH) & ((unsigned)iw < (unsigned)a.IW);
     }
     const int chunk = MF16 ? (lslot ^ (swz_p & 6)) : ((lslot ^ (swz_p >> 1)) & 7);
-    h_off[i] = ok ? (((long long)((ABL & 32) ? 0 : n) * a.IH + ih) * a.IW + iw) * a.Cs + chunk * 8 : -1;
+    h_off[i] = ok ? (((long long)n * a.IH + ih) * a.IW + iw) * a.Cs + chunk * 8 : -1;
     if constexpr (VIRT) {
       // padding pixels come from the frame: rows [2][IW + 2] (column index iw + 1), then columns [2][IH]; slack pixels are zeros
       if (!ok && !slack) {
@@ -279,28 +276,24 @@ __global__ __launch_bounds__(512) void gemm_halo_kernel(const HaloArgs a) {
   static_assert(B_UNITS % NW == 0, "every wave issues exactly BU weight pieces per tile");
   auto tap_body = [&](const int tap_r, const int tap_s, const int slab, const bool more, const char* const hb) {
     const int tap = tap_r * S + tap_s;               // tap_s is a compile-time constant in both callers
-    if (!(ABL & 8)) {
-      if (tap < TAPS - 1 || more) wait_vmcnt<BU>(); else wait_vmcnt<0>();
-    }
-    if (!(ABL & 2)) __builtin_amdgcn_s_barrier();
+    if (tap < TAPS - 1 || more) wait_vmcnt<BU>(); else wait_vmcnt<0>();
+    __builtin_amdgcn_s_barrier();
     // issue group t+2: one patch unit of the NEXT slab (from the slab's first tap on: its buffer was being
     // read until the previous slab ended), then weight tile t+2
     auto issue_group = [&]() {
-      if (!(ABL & 1)) {
-        if constexpr (!SINGLE) {
-          if (tap < HU && tap < n_hu && more) {
+      if constexpr (!SINGLE) {
+        if (tap < HU && tap < n_hu && more) {
 #pragma unroll
-            for (int i = 0; i < HU; ++i)
-              if (i == tap) issue_patch_unit(i, slab + 1);          // tap is a constant here (unrolled caller)
-          }
+          for (int i = 0; i < HU; ++i)
+            if (i == tap) issue_patch_unit(i, slab + 1);            // tap is a constant here (unrolled caller)
         }
-        const int tap2 = tap + 2 < TAPS ? tap + 2 : tap + 2 - TAPS;
-        if (tap + 2 < TAPS || more) {
-          char* const st2 = bring + ((tap_s + 2) % 3) * B_STAGE;    // (t + 2) % 3 with t = 9 * slab + 3 * tap_r + tap_s
-          const long long koff = (long long)tap2 * a.Cs + (slab + (tap + 2 < TAPS ? 0 : 1)) * 64;
+      }
+      const int tap2 = tap + 2 < TAPS ? tap + 2 : tap + 2 - TAPS;
+      if (tap + 2 < TAPS || more) {
+        char* const st2 = bring + ((tap_s + 2) % 3) * B_STAGE;      // (t + 2) % 3 with t = 9 * slab + 3 * tap_r + tap_s
+        const long long koff = (long long)tap2 * a.Cs + (slab + (tap + 2 < TAPS ? 0 : 1)) * 64;
 #pragma unroll
-          for (int jj = 0; jj < BU; ++jj) glds16(b_ptr[jj] + koff, st2 + b_lds[jj]);
-        }
+        for (int jj = 0; jj < BU; ++jj) glds16(b_ptr[jj] + koff, st2 + b_lds[jj]);
       }
     };
     // (Tried and removed in round 4, negative results on record in DESIGN.md 4.1: waves 4..7 issuing their DMA group AFTER the MFMA
@@ -338,12 +331,11 @@ __global__ __launch_bounds__(512) void gemm_halo_kernel(const HaloArgs a) {
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       s16x8 af[FM], bf[FN];
-      const int ks_r = (ABL & 4) ? 0 : ks;
 #pragma unroll
       for (int i = 0; i < FM; ++i)
-        af[i] = *reinterpret_cast<const s16x8*>(hb + a_base[i] + ((((MF16 ? 4 : 2) * ks_r + hsel) << 4) ^ a_sw[i]));
+        af[i] = *reinterpret_cast<const s16x8*>(hb + a_base[i] + ((((MF16 ? 4 : 2) * ks + hsel) << 4) ^ a_sw[i]));
 #pragma unroll
-      for (int j = 0; j < FN; ++j) bf[j] = *reinterpret_cast<const s16x8*>(st + b_rd[j][ks_r]);
+      for (int j = 0; j < FN; ++j) bf[j] = *reinterpret_cast<const s16x8*>(st + b_rd[j][ks]);
 #pragma unroll
       for (int i = 0; i < FM; ++i)
 #pragma unroll

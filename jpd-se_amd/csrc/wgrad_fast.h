@@ -106,9 +106,7 @@ __device__ __forceinline__ void wg_mma_step(uint32_t sbase, const int (&a_tr)[TM
 //   <2,2,TM,TN>  64..128 square-ish tiles, 4 waves, 2 blocks per CU (small layers)
 //   <2,4,4,2>    256 x 256, 8 waves, 1 block per CU: 2x the FLOPs per staged byte -- the kernel is bound
 //                by the L2->LDS fill (ablation: no DMA => 2.2x).
-// ABL: timing-only ablation bits (wrong results when non-zero): 1 = no DMA after the first chunk,
-// 2 = no barrier, 4 = fragments read once per chunk, 8 = no vmcnt waits
-template <int WM, int WN, int TM, int TN, int ABL = 0>
+template <int WM, int WN, int TM, int TN>
 __global__ __launch_bounds__(64 * WM * WN) void wgrad_fast_kernel(const FastWgArgs a) {
   constexpr int NW = WM * WN;
   constexpr int BKP = 64;                         // pixels per chunk
@@ -288,16 +286,16 @@ __global__ __launch_bounds__(64 * WM * WN) void wgrad_fast_kernel(const FastWgAr
   wait_vmcnt<0>();
   __builtin_amdgcn_s_barrier();
   for (int c = ch_begin; c < ch_end; ++c) {
-    if (c + 1 < ch_end && !(ABL & 1)) issue(stage ^ 1);
+    if (c + 1 < ch_end) issue(stage ^ 1);
     const uint32_t sbase = lds0 + stage * STAGE;
     __builtin_amdgcn_s_setprio(1);
     wg_mma_step<TM, TN, A_ROWB, B_ROWB, 0>(sbase, a_tr, b_tr, acc);
-    wg_mma_step<TM, TN, A_ROWB, B_ROWB, (ABL & 4) ? 0 : 1>(sbase, a_tr, b_tr, acc);
-    wg_mma_step<TM, TN, A_ROWB, B_ROWB, (ABL & 4) ? 0 : 2>(sbase, a_tr, b_tr, acc);
-    wg_mma_step<TM, TN, A_ROWB, B_ROWB, (ABL & 4) ? 0 : 3>(sbase, a_tr, b_tr, acc);
+    wg_mma_step<TM, TN, A_ROWB, B_ROWB, 1>(sbase, a_tr, b_tr, acc);
+    wg_mma_step<TM, TN, A_ROWB, B_ROWB, 2>(sbase, a_tr, b_tr, acc);
+    wg_mma_step<TM, TN, A_ROWB, B_ROWB, 3>(sbase, a_tr, b_tr, acc);
     __builtin_amdgcn_s_setprio(0);
-    if (!(ABL & 8)) wait_vmcnt<0>();
-    if (!(ABL & 2)) __builtin_amdgcn_s_barrier();
+    wait_vmcnt<0>();
+    __builtin_amdgcn_s_barrier();
     stage ^= 1;
   }
 

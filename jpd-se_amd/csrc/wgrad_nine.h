@@ -58,8 +58,7 @@ static constexpr int kNine32Slot = 40 * 128;          // W32: input row slot, 40
 static constexpr int kNine32Slots = 8;
 static_assert(3 * kNineStage + kNine32Slots * kNine32Slot <= kNineLds, "the W32 loop fits the same allocation");
 
-// SCHED: where the DMA issue of chunk t+2 sits in iteration t (see the loop).  ABL (timing-only): 1 = no epilogue
-template <bool REFLECT, int SCHED = 3, int ABL = 0, bool W32 = false>
+template <bool REFLECT, bool W32 = false>
 __global__ __launch_bounds__(512) void wgrad_nine_kernel(const NineWgArgs a) {
   static_assert(!W32 || REFLECT, "the 32-pixel-wide form is built for reflect padding");
   constexpr int NW = 8, BKP = 64, ROWB = 128;
@@ -277,7 +276,7 @@ __global__ __launch_bounds__(512) void wgrad_nine_kernel(const NineWgArgs a) {
       acc[t9] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bf[t9], acc[t9], 0, 0, 0);
   };
 
-  // SCHED 3: the six (k-step, filter-row) groups of a chunk as a software pipeline -- the transposed reads of group g+1
+  // The six (k-step, filter-row) groups of a chunk as a software pipeline -- the transposed reads of group g+1
   // are in flight while the three MFMAs of group g issue, with COUNTED lgkmcnt waits (LDS operations return in order; the
   // loop holds no scalar-memory loads, which would share the counter -- checked in the .s).  The plain form waits for
   // lgkmcnt(0) after each k-step's 20 reads: two exposed LDS round trips per chunk and wave.
@@ -354,7 +353,6 @@ __global__ __launch_bounds__(512) void wgrad_nine_kernel(const NineWgArgs a) {
     // sits inside it for the second pixel half and behind it for the first.  (The unpipelined loop forms -- DMA issue right
     // behind the barrier, between the two k-steps, alternating between the two waves of a SIMD: round-2 developer modes
     // 21 / 22 / 24 -- measured 7-9 % slower and were removed in round 4; A/B record: DESIGN.md 4.1 (vii).)
-    static_assert(SCHED == 3, "only the software-pipelined loop form is built");
     __builtin_amdgcn_s_setprio(1);
     if constexpr (W32) chunk_pipelined(a_addr, boff, [&]() { if (ph == 1 && more) { issue_dy32(); issue_pair(); } });
     else chunk_pipelined(a_addr, boff, [&]() { if (ph == 1 && more) { issue_dy(); issue_row(); } });
@@ -379,7 +377,7 @@ __global__ __launch_bounds__(512) void wgrad_nine_kernel(const NineWgArgs a) {
       }
   }
   __syncthreads();
-  if (ph == 0 && !(ABL & 1)) {
+  if (ph == 0) {
     float* const out = a.splits > 1 ? a.partial + (long long)sp * a.K * 9 * a.C : a.DW;
     const int cc = c0 + wc * 32 + (lane & 31);
 #pragma unroll

@@ -31,7 +31,6 @@ struct TapsWgArgs {
   int blocks_per_tile, chunks_per_block;
   int tiles;                           // k_tiles * r_groups * c_tiles
   int xg_gs, xg_gpx;                   // XCD co-location (conv_dispatch_wgrad.h::taps_partition): group size, groups per XCD; 0 = linear order
-  int abl;                             // developer build, timing only (modes 200 + bits): 1 = no DMA after the prologue, 2 = no fragment reads / MFMAs (the finer ablations of round 4 -- no B reads, reads without MFMAs, no padding arithmetic -- sat inside the loop, cost it 10 % themselves and were removed)
 };
 
 // LDS row of patch pixel (filter row rr, patch column col).  Stride 2: the columns of a patch row are stored DE-INTERLEAVED,
@@ -231,22 +230,14 @@ __global__ __launch_bounds__(64 * WM * WN) void wgrad_taps_kernel(const TapsWgAr
     else if (NSTG >= 3 && rem >= 1) wait_vmcnt<G>();
     else wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
-#ifdef JPDSE_DEV
-    if (!(a.abl & 1))
-#endif
     if (wid < NI && c + NSTG - 1 < ch_end) issue(c + NSTG - 1, stage == 0 ? NSTG - 1 : stage - 1);
     const uint32_t sbase = lds0 + stage * STAGE;
-#ifdef JPDSE_DEV
-    if (!(a.abl & 2))
-#endif
-    {
-      __builtin_amdgcn_s_setprio(1);
-      mma_step.template operator()<0>(sbase);
-      if constexpr (BKP > 16) mma_step.template operator()<1>(sbase);
-      if constexpr (BKP > 32) mma_step.template operator()<2>(sbase);
-      if constexpr (BKP > 48) mma_step.template operator()<3>(sbase);
-      __builtin_amdgcn_s_setprio(0);
-    }
+    __builtin_amdgcn_s_setprio(1);
+    mma_step.template operator()<0>(sbase);
+    if constexpr (BKP > 16) mma_step.template operator()<1>(sbase);
+    if constexpr (BKP > 32) mma_step.template operator()<2>(sbase);
+    if constexpr (BKP > 48) mma_step.template operator()<3>(sbase);
+    __builtin_amdgcn_s_setprio(0);
     stage = stage == NSTG - 1 ? 0 : stage + 1;
   }
 

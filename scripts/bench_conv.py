@@ -14,7 +14,7 @@ ap.add_argument('--batch', type=int, default=4)
 ap.add_argument('--fast', type=str, default='1', help='comma list of fast-path modes to A/B in one process')
 ap.add_argument('--filter', default='')
 ap.add_argument('--iters', type=int, default=10)
-ap.add_argument('--fwd-only', action='store_true', help='time the forward launch only (long steady runs for scripts/clock_probe.sh)')
+ap.add_argument('--fwd-only', action='store_true', help='time the forward launch only (long steady runs, e.g. while clock and power are sampled)')
 args = ap.parse_args()
 dev = torch.device('cuda', 0)
 modes = [int(x) for x in args.fast.split(',')]

@@ -28,7 +28,7 @@ with open(out, 'w') as fh:
   fh.write('%-62s %9s %6s %12s %12s %12s\n' % ('kernel', 'grid', 'calls', 'fetch MB', 'write MB', 'total MB'))
   for name, grid, n, f, w, _ in rows[:70]:
     fh.write('%-62s %9d %6d %12.1f %12.1f %12.1f\n' % (name[:62], grid, n, f, w, f + w))
-head = [r for r in rows if r[0].startswith('gemm_halo_kernel<4, 2, 0, false') and r[1] == 131072]
+head = [r for r in rows if r[0].startswith('gemm_halo_kernel<4, 2, false') and r[1] == 131072]
 if head:
   name, grid, n, f, w, _ = head[0]
   js = dict(kernel='gemm_halo_kernel<4,2> grid 131072 (ResnetBlock 3x3, N=1024 K=9216)', fetch_bytes_per_launch=f * 1e6,
