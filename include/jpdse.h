@@ -36,7 +36,8 @@ extern "C" {
                                 * jpdse_loss_finalize, jpdse_conv_fwd_pool, jpdse_conv_dgrad_fused_lrelu, jpdse_input_builder, jpdse_copy, jpdse_prof_hbm_* under version 1;
                                 * the learned codec (jpdse_binarize_fwd, jpdse_code_stats[_workspace_size], jpdse_code_export) was added to
                                 * version 2 later, and so were the evaluation metrics (jpdse_eval_metrics[_workspace_size]) and their
-                                * per-class form (jpdse_eval_metrics_sem[_workspace_size]): purely additive, nothing existing changed */
+                                * per-class form (jpdse_eval_metrics_sem[_workspace_size]), and the receiver side of the codec
+                                * (jpdse_code_import): purely additive, nothing existing changed */
 
 enum { JPDSE_F32 = 0, JPDSE_BF16 = 1 };
 enum { JPDSE_PAD_ZERO = 0, JPDSE_PAD_REFLECT = 1 };
@@ -380,6 +381,15 @@ int jpdse_code_stats(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, 
  * order; packed != 0: out = uint8 [N][ceil(C*H*W / 8)], bit (b > 0) of element 8k+j in bit 7-j of byte k (np.packbits order). */
 int jpdse_code_export(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, const void* b, int32_t packed, void* out,
                       void* stream);
+/* Code import, the inverse of jpdse_code_export (no reference counterpart: the reference never decodes a stored code).
+ * b = NHWC [N][H][W][CPAD(C)] in `dtype`: element e of image n becomes +1 or -1, never 0; every padding lane c >= C is
+ * written as 0.  packed != 0: in = uint8 [N][ceil(C*H*W / 8)], element 8k+j = bit 7-j of byte k, every image starting on a
+ * byte as jpdse_code_export writes it; the unused low bits of an image's last byte are ignored.  packed == 0: in = fp32
+ * [N][C*H*W], in > 0.5f gives +1 and anything else (NaN included) -1.  So import(export(b)) == b except where b == 0 (the
+ * eval binarizer's sign(0)): that element was exported as bit 0 (or 0.5) and comes back as -1 -- what a receiver sees.
+ * A NULL pointer, a non-positive extent or a bad dtype is JPDSE_EINVAL before any launch. */
+int jpdse_code_import(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, const void* in, int32_t packed, void* b,
+                      void* /* hipStream_t */ stream);
 
 /* ---- evaluation metrics: L1, MSE and MS-SSIM of a reconstruction in one pass (test.py:114-125) --------------------------
  * fake (fp32 or bf16) and real (fp32): NHWC [N][H][W][CPAD(3)] normalised images; both are quantised with q() of

@@ -23,6 +23,14 @@ int check_launch(const char* what) {
   return JPDSE_OK;
 }
 
+// jpdse_code_import (binarize.hip): everything that can be refused without a device
+int code_import_check(int dtype, int N, int H, int W, int C, const void* in, const void* b) {
+  JPDSE_REQUIRE(!bad_dtype(dtype), "code_import: bad dtype %d", dtype);
+  JPDSE_REQUIRE(in != nullptr && b != nullptr, "code_import: null pointer");
+  JPDSE_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0, "code_import: non-positive extent (N %d, H %d, W %d, C %d)", N, H, W, C);
+  return JPDSE_OK;
+}
+
 // ---- in-library timer for the HBM-bound calls (bench.py "roofline_hbm"): hipEvent pairs around whole InstanceNorm /
 // Adam calls, recorded on the stream the kernels run on; each region carries the call's ALGORITHMIC bytes.
 struct HbmProf {

@@ -1,5 +1,5 @@
-// Stochastic binarizer of the learned-codec encoder (reference ctu/quantizers/binarize.py:13-65) and the statistics /
-// export of the bitstream it produces (reference pix2pixHD_model.py:468-505).  Entry points: include/jpdse.h, "learned codec".
+// Stochastic binarizer of the learned-codec encoder (reference ctu/quantizers/binarize.py:13-65), the statistics /
+// export of the bitstream it produces (reference pix2pixHD_model.py:468-505) and the import of a stored bitstream (receiver side).  Entry points: include/jpdse.h, "learned codec".
 //
 // RNG contract: the noise of element e = (c*H + y)*W + x (logical NCHW index inside its image) of image
 // n_global at training forward `draw` is word (e & 3) of Philox4x32-10(counter = (e >> 2, n_global, draw lo, draw hi),
@@ -161,6 +161,41 @@ __global__ void code_pack_kernel(const T* __restrict__ b, uint8_t* __restrict__ 
   }
 }
 
+// The inverse of the two export kernels: b = +1 / -1 from the stored code, never 0; padding lanes 0.  One thread per 16-byte
+// vector of b (the mapping of binarize_fwd_kernel: a wave's stores are contiguous); its VE channels sit H*W elements apart in
+// the code, so channel c of pixel p is element e = c*HW + p: bit 7 - (e & 7) of byte e >> 3 (a channel does not start on a byte
+// when HW % 8 != 0), or in[e] > 0.5f of the fp32 form (NaN: -1).  Neighbouring pixels read neighbouring bits of the same
+// bytes.  row = bytes (packed) or elements (fp32) per image; e < C*HW, so no read leaves the image's row.
+template <typename T, bool PACKED>
+__global__ void code_import_kernel(const void* __restrict__ in, T* __restrict__ b, int C, int Cs, long long HW, long long row,
+                                   long long total_vec) {
+  constexpr int VE = Vec16<T>::N;
+  const int cv = Cs / VE;
+  GRID_STRIDE(idx, total_vec) {
+    const int c0 = (int)(idx % cv) * VE;
+    const long long pix = idx / cv;              // n * HW + y * W + x
+    const long long n = pix / HW;
+    const long long p = pix - n * HW;
+    float v[VE];
+#pragma unroll
+    for (int j = 0; j < VE; ++j) {
+      const int c = c0 + j;
+      float o = 0.f;
+      if (c < C) {
+        const long long e = (long long)c * HW + p;
+        bool one;
+        if constexpr (PACKED)
+          one = (static_cast<const uint8_t*>(in)[n * row + (e >> 3)] >> (7 - (int)(e & 7))) & 1;
+        else
+          one = static_cast<const float*>(in)[n * row + e] > 0.5f;
+        o = one ? 1.f : -1.f;
+      }
+      v[j] = o;
+    }
+    Vec16<T>::store(b + idx * VE, v);
+  }
+}
+
 static int stats_blocks(int dtype, int H, int W, int C) {
   const long long vpi = (long long)H * W * (cpad(C) / vec_elems(dtype));
   long long blocks = (vpi + 1023) / 1024;           // >= 4 vectors per thread
@@ -227,6 +262,21 @@ int jpdse_code_export(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C,
       return ew_launch("code_export(packed)", code_pack_kernel<T>, total, stream, cptr<T>(b), mptr<uint8_t>(out), C, Cs, HW,
                        nbytes, total);
     return ew_launch("code_export", code_export_kernel<T>, total, stream, cptr<T>(b), mptr<float>(out), C, Cs, HW, total);
+  });
+}
+
+int jpdse_code_import(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, const void* in, int32_t packed, void* b,
+                      void* stream) {
+  if (int rc = code_import_check(dtype, N, H, W, C, in, b)) return rc;
+  const int Cs = cpad(C);
+  const long long HW = (long long)H * W, bits = (long long)C * HW;
+  const long long row = packed ? (bits + 7) / 8 : bits;
+  const long long tv = (long long)N * HW * (Cs / vec_elems(dtype));
+  return by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    if (packed)
+      return ew_launch("code_import(packed)", code_import_kernel<T, true>, tv, stream, in, mptr<T>(b), C, Cs, HW, row, tv);
+    return ew_launch("code_import", code_import_kernel<T, false>, tv, stream, in, mptr<T>(b), C, Cs, HW, row, tv);
   });
 }
 

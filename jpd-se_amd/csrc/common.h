@@ -18,6 +18,9 @@ int check_launch(const char* what);
     if (!(cond)) return ::jpdse::set_error(JPDSE_EINVAL, __VA_ARGS__); \
   } while (0)
 
+// argument checks of jpdse_code_import (api.cpp): JPDSE_EINVAL + message before any launch, JPDSE_OK otherwise
+int code_import_check(int dtype, int N, int H, int W, int C, const void* in, const void* b);
+
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 // opt-in timer of the HBM-bound calls (api.cpp; jpdse_prof_hbm_select / _collect): begin returns a slot or -1 (off / full)

@@ -308,15 +308,8 @@ class Pix2PixHDModel(BaseModel):
       comp = x_dict.get('compressed_img')
       if comp is None:
         comp = self.compress(x_dict, os.path.join(opt.save_dir, 'tmp_imgs'))   # a private sub-directory per process
-    label = x_dict['label'].to(dev, dtype=torch.float32, non_blocking=True).contiguous()
-    inst = x_dict['instance'].to(dev, dtype=torch.int64, non_blocking=True).contiguous()
+    label, inst = self._semantics(x_dict)
     image = x_dict['image'].to(dev, dtype=torch.float32, non_blocking=True).contiguous()
-    if getattr(opt, 'no_instance', False):
-      inst = torch.zeros_like(inst)      # a constant map has no edges; its channel is not part of label_nc
-    elif self.zero_ins:
-      # --zero_ins: the reference zeroes the edge channel of input_label IN PLACE (model.py:591) and hands that tensor on to
-      # the discriminator (:610, :717-733), so G and D both see a zero edge lane: a constant instance map everywhere
-      inst = torch.zeros_like(inst)
     total_c = self.label_nc + self.feat_nc
     base = ops.onehot_edge(label, inst, self.n_onehot, total_c, self.cdtype) if build_base else None
     real = ops.nchw_to_nhwc(image, self.cdtype)
@@ -324,6 +317,19 @@ class Pix2PixHDModel(BaseModel):
     if comp is not None:
       src = ops.nchw_to_nhwc(comp.to(dev, dtype=torch.float32, non_blocking=True).contiguous(), self.cdtype)
     return dict(base=base, real=real, src=src, image_nchw=image, label=label, inst=inst, total_c=total_c)
+
+  def _semantics(self, x_dict):
+    """The device label and instance maps of x_dict, as the input builders read them."""
+    dev = self._device()
+    label = x_dict['label'].to(dev, dtype=torch.float32, non_blocking=True).contiguous()
+    inst = x_dict['instance'].to(dev, dtype=torch.int64, non_blocking=True).contiguous()
+    if getattr(self.opt, 'no_instance', False):
+      inst = torch.zeros_like(inst)      # a constant map has no edges; its channel is not part of label_nc
+    elif self.zero_ins:
+      # --zero_ins: the reference zeroes the edge channel of input_label IN PLACE (model.py:591) and hands that tensor on to
+      # the discriminator (:610, :717-733), so G and D both see a zero edge lane: a constant instance map everywhere
+      inst = torch.zeros_like(inst)
+    return label, inst
 
   def _with_image(self, base, img, out=None):
     """torch.cat((input_label, img), dim=1) in NHWC: copy of `base` with the image channels filled."""
@@ -340,10 +346,10 @@ class Pix2PixHDModel(BaseModel):
     finally:
       self.netE.train(was)
 
-  def _g_input_zero_sem(self, vis, like):
-    """--zero_sem (model.py:585-587): G's input with all label_nc semantic lanes zero and `vis` (Act or None) in the visual
-    lanes.  Only G's input: the discriminator keeps the real semantics (_get_img returns input_label untouched)."""
-    g_in = Act.empty(like.N, like.H, like.W, self.label_nc + self.feat_nc, self.cdtype, like.t.device)
+  def _g_input_zero_sem(self, vis, N, H, W):
+    """--zero_sem (model.py:585-587): G's input [N, H, W] with all label_nc semantic lanes zero and `vis` (Act or None) in the
+    visual lanes.  Only G's input: the discriminator keeps the real semantics (_get_img returns input_label untouched)."""
+    g_in = Act.empty(N, H, W, self.label_nc + self.feat_nc, self.cdtype, self._device())
     ops.zero_(g_in.t)
     return g_in if vis is None else ops.insert_channels(g_in, vis, self.label_nc)
 
@@ -353,11 +359,16 @@ class Pix2PixHDModel(BaseModel):
     vis = None if self.zero_vis else pre['src']      # --zero_vis: nothing visual reaches the generator
     if vis is not None and self.netE is not None:
       vis, _ = self._encoder_eval(lambda: self.netE.fwd(vis))
+    return self._g_input_from_vis(vis, pre['base'], pre['real'].N, pre['real'].H, pre['real'].W)
+
+  def _g_input_from_vis(self, vis, base, N, H, W):
+    """[semantics | vis] with the --zero_sem lanes blanked; vis None: the visual lanes stay zero.  `base` is preprocess's
+    one-hot + edge tensor (unused, and may be None, under --zero_sem)."""
     if self.zero_sem:
-      return self._g_input_zero_sem(vis, pre['real'])
+      return self._g_input_zero_sem(vis, N, H, W)
     if vis is None:
-      return pre['base']                 # onehot_edge leaves every lane behind the semantics zero
-    return self._with_image(pre['base'], vis)
+      return base                        # onehot_edge leaves every lane behind the semantics zero
+    return self._with_image(base, vis)
 
   def _set_codec_rng(self, local_batch):
     """Point the binarizer at this call's images: n_global = rank * local_batch + i."""
@@ -369,11 +380,14 @@ class Pix2PixHDModel(BaseModel):
     rank = dist.get_rank(group) if dist.is_available() and dist.is_initialized() else 0
     b.seed, b.draw, b.n_global0 = self.codec_seed, self.codec_draw, rank * local_batch
 
-  def _code_act(self, x_dict):
-    """The encoder's eval-mode bitstream of x_dict (the decoded frame with --use_compressed) as an NHWC Act."""
+  def _require_binarizer(self):
     if self.netE is None or not self.netE.binarize:
       raise ValueError('binary codes need the learned codec with encoder binarization '
                        '(--no_feat_encoding and --no_encoder_binarization must both be off)')
+
+  def _code_act(self, x_dict):
+    """The encoder's eval-mode bitstream of x_dict (the decoded frame with --use_compressed) as an NHWC Act."""
+    self._require_binarizer()
     pre = self.preprocess(x_dict, build_base=False)
     return self._encoder_eval(lambda: self.netE.code(pre['src']))
 
@@ -422,6 +436,64 @@ class Pix2PixHDModel(BaseModel):
                      self.opt.distortion_loss_fn == 'mse', slot)
       return slot[0]
 
+  def _decode_act(self, code, x_dict):
+    """decode() up to the generator's NHWC output; also returns the device label map."""
+    self._require_binarizer()
+    if not torch.is_tensor(code) or code.dim() != 2 or code.dtype not in (torch.uint8, torch.float32):
+      raise ValueError('decode: the code must be what get_code returns: a uint8 [N, ceil(bits / 8)] or float32 [N, bits] tensor')
+    N, H, W = int(x_dict['label'].shape[0]), int(x_dict['label'].shape[-2]), int(x_dict['label'].shape[-1])
+    step = 1 << self.netE.n_downsampling
+    if H % step or W % step:
+      raise ValueError('decode: a %d x %d label map is no multiple of the encoder\'s down-sampling factor %d' % (H, W, step))
+    C, h, w = self.netE.code_shape(H, W)
+    bits = C * h * w
+    want = (N, (bits + 7) // 8) if code.dtype == torch.uint8 else (N, bits)
+    if tuple(code.shape) != want:
+      raise ValueError('decode: code of shape %s, but %d label maps of %d x %d carry a %s code of shape %s (%d x %d x %d bits '
+                       'per image)' % (tuple(code.shape), N, H, W, 'packed' if code.dtype == torch.uint8 else 'float32',
+                                       want, C, h, w))
+    label, inst = self._semantics(x_dict)
+    vis = None                           # --zero_vis: nothing visual reaches the generator, the code is not read
+    if not self.zero_vis:
+      b = ops.code_import(code.to(self._device(), non_blocking=True), N, h, w, C, self.cdtype)
+      vis = self.netE.decode_code(b)
+    base = None if self.zero_sem else ops.onehot_edge(label, inst, self.n_onehot, self.label_nc + self.feat_nc, self.cdtype)
+    fake, _ = self.netG.fwd(self._g_input_from_vis(vis, base, N, H, W))
+    return fake, label
+
+  def decode(self, code, x_dict):
+    """The receiver (extension; the reference never decodes a stored code): the reconstructed image, NCHW as get_img returns
+    it, from `code` -- what get_code returned, float32 [N, bits] or (packed) uint8 [N, ceil(bits / 8)], on the CPU or the
+    device -- and the semantics x_dict['label'], x_dict['instance'].  Neither 'image' nor 'compressed_img' is read.  The
+    code goes through ops.code_import and the encoder's second half (Encoder.decode_code); the generator input is then
+    built as get_img builds it from the features, --zero_sem / --zero_ins / --zero_vis included (--zero_vis ignores the code
+    as get_img ignores the image).
+    Zero rule: decode(get_code(x)) equals get_img(x) bit for bit when the eval code has no exact zero (ops.code_stats column
+    1).  Where the encoder's tanh is exactly 0, get_img feeds sign(0) = 0 forward but the stored bit is 0, so the decoder
+    sees -1 there: the stored code, not the tensor get_img used, is what a receiver reconstructs from.
+    ValueError without an encoder or a binarizer, and for a code whose size does not fit the label map (before any device
+    work)."""
+    with torch.no_grad():
+      fake, _ = self._decode_act(code, x_dict)
+      return ops.nhwc_to_nchw(fake)
+
+  def _eval_metrics_of(self, fake, image, label, per_class):
+    """The tail get_eval_metrics and get_eval_metrics_decoded share: `fake` (the generator's NHWC output) against the original
+    image (NCHW, any device), un-rounded as the reference uses it."""
+    image = image.to(self._device(), dtype=torch.float32, non_blocking=True).contiguous()
+    real32 = ops.nchw_to_nhwc(image, F32)
+    if per_class:
+      return ops.eval_metrics(fake, real32, self.opt.normalize_mean, self.opt.normalize_std, label, self.n_onehot)
+    return ops.eval_metrics(fake, real32, self.opt.normalize_mean, self.opt.normalize_std)
+
+  def get_eval_metrics_decoded(self, code, x_dict, per_class=False):
+    """get_eval_metrics of the image a receiver reconstructs: the same dict, computed on decode(code, x_dict) against
+    x_dict['image'].  Equal to get_eval_metrics(x_dict) for code = get_code(x_dict) under decode's zero rule: where the eval
+    code holds an exact zero the decoder sees -1 and get_eval_metrics, like get_img, sees 0."""
+    with torch.no_grad():
+      fake, label = self._decode_act(code, x_dict)
+      return self._eval_metrics_of(fake, x_dict['image'], label, per_class)
+
   def get_eval_metrics(self, x_dict, per_class=False):
     """Every distortion figure of the reference's test loop (test.py:114-125) from ONE generator forward: dict(l1, mse,
     psnr, ms_ssim, per_image) on the 0..255 scale of the quantised images (ops.eval_metrics; MS-SSIM: DESIGN.md 4.5).
@@ -431,10 +503,7 @@ class Pix2PixHDModel(BaseModel):
     with torch.no_grad():
       pre = self.preprocess(x_dict, build_base=not self.zero_sem)
       fake, _ = self.netG.fwd(self._g_input_eval(pre))
-      real32 = ops.nchw_to_nhwc(pre['image_nchw'], F32)
-      if per_class:
-        return ops.eval_metrics(fake, real32, self.opt.normalize_mean, self.opt.normalize_std, pre['label'], self.n_onehot)
-      return ops.eval_metrics(fake, real32, self.opt.normalize_mean, self.opt.normalize_std)
+      return self._eval_metrics_of(fake, pre['image_nchw'], pre['label'], per_class)
 
   # ---- training -------------------------------------------------------------------------------
   def _forward_losses(self, x_dict, grad_w=None):
@@ -470,7 +539,7 @@ class Pix2PixHDModel(BaseModel):
         if self.netE.training:
           self.codec_draw += 1
       if self.zero_sem:
-        g_in = self._g_input_zero_sem(vis, real)
+        g_in = self._g_input_zero_sem(vis, B, H, W)
       else:
         g_in = Act.empty(B, H, W, self.label_nc + self.feat_nc, self.cdtype, dev)
         ops.input_builder(label, inst, self.n_onehot, [g_in], [vis], self.label_nc)

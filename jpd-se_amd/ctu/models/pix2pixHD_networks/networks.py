@@ -276,6 +276,20 @@ class Encoder(nn.Module):
     b, _ = self._binarizer.fwd(h)
     return b
 
+  def code_shape(self, H, W):
+    """(C, h, w) of the code of an H x W image: the binarizer's channels at 1 / 2^n of the resolution."""
+    if self._binarizer is None:
+      raise AttributeError('Encoder: no binarizer found')
+    n = self.n_downsampling
+    return (self._binarizer.conv.cout, H >> n, W >> n)
+
+  def decode_code(self, b):
+    """The receiver's half: features from a code Act (+-1, e.g. ops.code_import of a stored bitstream): model[4 + 3n + 1:](b)."""
+    if self._binarizer is None:
+      raise AttributeError('Encoder: no binarizer found')
+    y, _ = run_chain_fwd(self._post, b)
+    return y
+
   def forward(self, input, inst=None, mode='get_continuous_img', inst_wise_pool=False):
     if mode == 'get_binary_code':
       if self._binarizer is None:

@@ -147,6 +147,18 @@ class Pix2PixHDTrainer(BaseTrainer):
     self.eval()
     return self.model(x_dict, self.opt, mode='get_img')
 
+  def decode(self, code, x_dict):
+    """The receiver of the learned codec: the image reconstructed from `code` (what get_code returned, either form, CPU or
+    device) and x_dict['label'] / x_dict['instance'] alone.  Equal to get_img(x_dict) bit for bit unless the eval code
+    holds an exact zero, which is stored as a 0 bit and decoded as -1 (Pix2PixHDModel.decode)."""
+    self.eval()
+    return self.model.decode(code, x_dict)
+
+  def get_eval_metrics_decoded(self, code, x_dict, per_class=False):
+    """get_eval_metrics of decode(code, x_dict) against x_dict['image']: what a receiver of the stored code reconstructs."""
+    self.eval()
+    return self.model.get_eval_metrics_decoded(code, x_dict, per_class)
+
   # ---- checkpoints ------------------------------------------------------------------------------
   # File contract of the reference (pix2pixHD_trainer.py:119-176, base_model.py:54-59): <save_dir>/net_G.pth,
   # net_D.pth (state dicts) and stats_and_optim.pt with the keys below.  Optional entries are written / read only when

@@ -138,6 +138,7 @@ SIGNATURES = {
     'jpdse_code_stats_workspace_size': (_SZ, [_I32, _I32, _I32, _I32, _I32]),
     'jpdse_code_stats': (_I32, [_I32, _I32, _I32, _I32, _I32, _P, _P, _P, _SZ, _P]),
     'jpdse_code_export': (_I32, [_I32, _I32, _I32, _I32, _I32, _P, _I32, _P, _P]),
+    'jpdse_code_import': (_I32, [_I32, _I32, _I32, _I32, _I32, _P, _I32, _P, _P]),
     'jpdse_eval_metrics_workspace_size': (_SZ, [_I32, _I32, _I32, _I32]),
     'jpdse_eval_metrics': (_I32, [_I32, _I32, _I32, _I32, _I32, _I32, _P, _P, ctypes.POINTER(ctypes.c_double),
                                   ctypes.POINTER(ctypes.c_double), _P, _P, _SZ, _P]),

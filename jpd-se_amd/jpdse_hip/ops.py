@@ -544,6 +544,27 @@ def code_export(b, packed=False):
   return out
 
 
+def code_import(code, N, H, W, C, dtype_code, out=None):
+  """The inverse of code_export (jpdse_code_import): `code` -- the uint8 bitstream [N, ceil(C*H*W / 8)], MSB first, or fp32
+  [N, C*H*W] of 0 / 1 -- as the NHWC Act [N, H, W, C] of +1 / -1 the encoder's second half takes.  Never 0: an element that
+  was an exact zero before export (bit 0, or 0.5 in the fp32 form) comes back as -1.  A wrong shape is a ValueError before
+  any library call.  out: an Act [N, H, W, C] of that dtype to write into (every lane is written)."""
+  bits = C * H * W
+  packed = code.dtype == torch.uint8
+  want = (N, (bits + 7) // 8) if packed else (N, bits)
+  if tuple(code.shape) != want:
+    raise ValueError('code_import: %s code of shape %s, expected %s for N %d, C %d, H %d, W %d'
+                     % ('packed' if packed else 'fp32', tuple(code.shape), want, N, C, H, W))
+  if not packed and code.dtype != torch.float32:
+    raise ValueError('code_import: the code must be uint8 (packed) or float32, got %s' % (code.dtype,))
+  assert code.is_cuda, 'code_import: the code must be on the device'
+  code = code.contiguous()
+  b = out if out is not None else Act.empty(N, H, W, C, dtype_code, code.device)
+  assert (b.N, b.H, b.W, b.C, b.dtype) == (N, H, W, C, dtype_code) and b.t.device == code.device
+  check(lib().jpdse_code_import(dtype_code, N, H, W, C, _p(code), 1 if packed else 0, _p(b.t), _stream()), 'code_import')
+  return b
+
+
 # ---- evaluation metrics (metrics.hip) ------------------------------------------------------------
 MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
 

@@ -4,9 +4,11 @@ Both trainers are built side by side (1024x512, batch 4, bf16, ngf 64, use_compr
 n_downsample_E 4, B 128, feat_num 3) and timed in alternating blocks of `--steps` steps after `--warmup` warm-up steps each;
 the reported ms/step is the median block.  Prints ONE JSON line on stdout.  --layers also writes a per-layer profile of the
 encoder's launches (forward, backward and the generator's feature-channel data gradient, hipEvent pairs around each layer
-call outside a step) to stderr.
+call outside a step) to stderr.  --decode times the receiver instead: trainer.decode (code import, the encoder's second
+half, the generator) against trainer.get_img (the whole encoder, the generator) on the codec trainer alone, same workload,
+same alternating blocks, the code and the batch resident on the device; one JSON line with both medians.
 
-  python scripts/bench_learned_codec.py [--steps 10] [--warmup 3] [--blocks 3] [--layers]
+  python scripts/bench_learned_codec.py [--steps 10] [--warmup 3] [--blocks 3] [--layers | --decode]
 """
 import argparse
 import contextlib
@@ -46,6 +48,40 @@ def time_block(tr, xd, steps):
     tr.step(xd)
   torch.cuda.synchronize()
   return 1e3 * (time.perf_counter() - t0) / steps
+
+
+def time_calls(fn, calls):
+  torch.cuda.synchronize()
+  t0 = time.perf_counter()
+  for _ in range(calls):
+    fn()
+  torch.cuda.synchronize()
+  return 1e3 * (time.perf_counter() - t0) / calls
+
+
+def decode_bench(args, xd):
+  """ms per call of trainer.decode and trainer.get_img, alternating blocks in one process."""
+  tr = build(True, args)
+  code = tr.get_code(xd, packed=True)
+  receiver = dict(label=xd['label'], instance=xd['instance'])
+  fns = {'decode': lambda: tr.decode(code, receiver), 'get_img': lambda: tr.get_img(xd)}
+  same = bool(torch.equal(fns['decode'](), fns['get_img']()))
+  gc.collect()
+  gc.freeze()
+  for fn in fns.values():
+    for _ in range(args.warmup):
+      fn()
+  times = {k: [] for k in fns}
+  for _ in range(args.blocks):
+    for k, fn in fns.items():
+      times[k].append(time_calls(fn, args.steps))
+  ms = {k: statistics.median(v) for k, v in times.items()}
+  return dict(metric='ms_per_call', workload='%dx%d batch %d %s ngf 64 use_compressed' % (args.width, args.height, args.batch,
+                                                                                          args.dtype),
+              codec='nef 64, n_downsample_E 4, B 128, feat_num 3', calls_per_block=args.steps, blocks=args.blocks,
+              decode_ms=round(ms['decode'], 3), get_img_ms=round(ms['get_img'], 3),
+              ratio=round(ms['decode'] / ms['get_img'], 4), decode_equals_get_img=same,
+              blocks_ms={k: [round(x, 3) for x in v] for k, v in times.items()}, device=torch.cuda.get_device_name(0))
 
 
 def layer_profile(tr, xd, reps=5):
@@ -123,6 +159,7 @@ def main():
   ap.add_argument('--height', type=int, default=512)
   ap.add_argument('--dtype', default='bf16', choices=['bf16', 'fp32'])
   ap.add_argument('--layers', action='store_true')
+  ap.add_argument('--decode', action='store_true', help='time trainer.decode against trainer.get_img instead of the steps')
   args = ap.parse_args()
   import jpdse_hip
   from ctu.utils.synthetic import synthetic_batch
@@ -130,6 +167,9 @@ def main():
   torch.cuda.set_device(0)
   xd = synthetic_batch(args.batch, args.height, args.width, seed=1234)
   xd = {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in xd.items()}
+  if args.decode:
+    print(json.dumps(decode_bench(args, xd)))
+    return
   trainers = {'bpg': build(False, args), 'learned_codec': build(True, args)}
   gc.collect()
   gc.freeze()

@@ -9,8 +9,16 @@ gives the per-image averages, which are the ones to quote.  PSNR is the mean of 
 table of the distortion per semantic class over the whole test set (pixel-weighted: the raw integer sums of every batch are
 added before the division), from the same device pass; --zero_sem / --zero_ins / --zero_vis run the reference's ablations.
 
+--roundtrip DIR (needs --codec) evaluates what a receiver reconstructs: every image's packed code is written to
+DIR/b<batch>_i<image>.jpdc (ctu.utils.bitstream), read back, and the batch is decoded from the files and the label /
+instance maps alone (trainer.get_eval_metrics_decoded).  The reported distortion is then that of the decoded images, the
+line gains the bpp of the files (header included) beside get_eval_rate's actual_bpp, and the largest absolute difference
+between the decoded image and get_img's: 0 unless the eval code holds an exact zero, which is stored as a 0 bit and decoded
+as -1 while get_img feeds the 0 forward.
+
   python scripts/eval_rd.py [--batches 4] [--batch 2] [--width 1024] [--height 512] [--dtype bf16] [--codec]
                             [--checkpoints_dir DIR] [--data DIR] [--per-class] [--zero_sem] [--zero_ins] [--zero_vis]
+                            [--roundtrip DIR]
 """
 import argparse
 import contextlib
@@ -40,6 +48,24 @@ def batches(args):
       yield synthetic_batch(args.batch, args.height, args.width, seed=1234 + i)
 
 
+def roundtrip(trainer, x_dict, folder, batch_index):
+  """Encode x_dict, store one file per image, read the files back: (code [N, bytes] uint8 CPU tensor, file bpp per image)."""
+  from ctu.utils import bitstream
+  code = trainer.get_code(x_dict, packed=True).cpu()
+  H, W = int(x_dict['label'].shape[-2]), int(x_dict['label'].shape[-1])
+  shape = trainer.model.netE.code_shape(H, W)
+  rows, bpp = [], []
+  for j in range(code.shape[0]):
+    path = os.path.join(folder, 'b%04d_i%02d.jpdc' % (batch_index, j))
+    bitstream.write_code(path, code[j], shape)
+    row, got = bitstream.read_code(path)
+    if tuple(got) != tuple(shape):
+      raise SystemExit('%s: code shape %s, expected %s' % (path, got, shape))
+    rows.append(row)
+    bpp.append(8.0 * os.path.getsize(path) / (H * W))
+  return torch.stack(rows), bpp
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--batches', type=int, default=4)
@@ -54,7 +80,13 @@ def main():
   ap.add_argument('--per-class', action='store_true', help='also print L1 / MSE / PSNR per semantic class')
   for flag in ('zero_sem', 'zero_ins', 'zero_vis'):
     ap.add_argument('--' + flag, action='store_true', help='ablation input of the reference (same flag)')
+  ap.add_argument('--roundtrip', default=None, metavar='DIR',
+                  help='with --codec: store every code under DIR, decode from the files, report the decoded images')
   args = ap.parse_args()
+  if args.roundtrip and not args.codec:
+    ap.error('--roundtrip needs --codec')
+  if args.roundtrip:
+    os.makedirs(args.roundtrip, exist_ok=True)
   import jpdse_hip
   from jpdse_hip import ops
   from ctu.trainers import get_trainer
@@ -72,13 +104,21 @@ def main():
   with contextlib.redirect_stdout(sys.stderr):
     trainer = get_trainer(opt)(opt, 'test' if args.checkpoints_dir else 'train')
   keys = ('l1', 'mse', 'ms_ssim', 'psnr')
-  by_batch = dict.fromkeys(keys + ('shannon', 'actual'), 0.0)
-  by_image = dict.fromkeys(keys + ('shannon', 'actual'), 0.0)
-  images, n_batches = 0, 0
+  by_batch = dict.fromkeys(keys + ('shannon', 'actual', 'file'), 0.0)
+  by_image = dict.fromkeys(keys + ('shannon', 'actual', 'file'), 0.0)
+  images, n_batches, worst_diff = 0, 0, 0.0
   class_sums = None                  # int64 [1, n_classes + 1, 3]: the raw class tables of every image so far, added up
   start = time.time()
   for i, x_dict in enumerate(batches(args)):
-    m = trainer.get_eval_metrics(x_dict, per_class=args.per_class)
+    if args.roundtrip:
+      code, file_bpp = roundtrip(trainer, x_dict, args.roundtrip, i)
+      receiver = dict(label=x_dict['label'], instance=x_dict['instance'])      # all the receiver has besides the files
+      decoded = trainer.decode(code, receiver)
+      diff = float((decoded - trainer.get_img(x_dict)).abs().max())
+      worst_diff = max(worst_diff, diff)
+      m = trainer.get_eval_metrics_decoded(code, x_dict, per_class=args.per_class)
+    else:
+      m = trainer.get_eval_metrics(x_dict, per_class=args.per_class)
     if args.per_class:
       tab = m['per_class']['raw'].sum(dim=0, keepdim=True)
       class_sums = tab if class_sums is None else class_sums + tab
@@ -93,6 +133,10 @@ def main():
       by_image['shannon'] += shannon * b
       by_image['actual'] += actual * b
       line += ', pre-/(estimated) post-entropy coding bpp {:.4f}/{:.4f}'.format(actual, shannon)
+    if args.roundtrip:
+      by_batch['file'] += sum(file_bpp) / len(file_bpp)
+      by_image['file'] += sum(file_bpp)
+      line += ', decoded from files: file bpp {:.4f}, max |decoded - get_img| {:.3e}'.format(sum(file_bpp) / len(file_bpp), diff)
     end = time.time()
     print(line + ', batch processing time (s) {:.4f}'.format(end - start))
     start = end
@@ -108,9 +152,14 @@ def main():
                                                                             t['ms_ssim'] / n, t['psnr'] / n)
     if args.codec:
       line += ', avg pre-/(estimated) post-entropy coding bpp {:.4f}/{:.4f}'.format(t['actual'] / n, t['shannon'] / n)
+    if args.roundtrip:
+      line += ', avg file bpp {:.4f}'.format(t['file'] / n)
     return line
   print('\n' + summary('test set avg recon loss', by_batch, n_batches))
   print(summary('per-image avg recon loss', by_image, images) + '\n')
+  if args.roundtrip:
+    print('distortion above: images decoded from the files under %s; largest |decoded - get_img| over the test set %.3e\n'
+          % (args.roundtrip, worst_diff))
   if args.per_class:
     r = ops.eval_metrics_per_class(class_sums)
     total = int(r['pixels'].sum()) + r['unlabelled']
