@@ -37,7 +37,8 @@ extern "C" {
                                 * the learned codec (jpdse_binarize_fwd, jpdse_code_stats[_workspace_size], jpdse_code_export) was added to
                                 * version 2 later, and so were the evaluation metrics (jpdse_eval_metrics[_workspace_size]) and their
                                 * per-class form (jpdse_eval_metrics_sem[_workspace_size]), and the receiver side of the codec
-                                * (jpdse_code_import): purely additive, nothing existing changed */
+                                * (jpdse_code_import), and the MS-SSIM training loss (jpdse_msssim_loss[_workspace_size]): purely additive,
+                                * nothing existing changed */
 
 enum { JPDSE_F32 = 0, JPDSE_BF16 = 1 };
 enum { JPDSE_PAD_ZERO = 0, JPDSE_PAD_REFLECT = 1 };
@@ -435,6 +436,34 @@ typedef struct jpdse_eval_metrics_sem_args {
   void* stream;
 } jpdse_eval_metrics_sem_args;
 int jpdse_eval_metrics_sem(const jpdse_eval_metrics_sem_args* args);
+
+/* ---- MS-SSIM training loss: --distortion_loss_fn ms_ssim (no reference counterpart) --------------------------
+ * out[0] = mean_n (1 - ms_ssim_n) of fake against real, both NHWC [N][H][W][CPAD(3)] normalised images of the SAME `dtype`
+ * (fp32 or bf16), de-normalised per channel (u = v * std[c] + mean[c]) and neither clipped nor quantised: L = 1, C1 = 1e-4,
+ * C2 = 9e-4, otherwise the MS-SSIM of jpdse_eval_metrics (11x11 Gaussian window of sigma 1.5 applied "valid" per channel,
+ * five scales linked by a 2x2 mean, ms_ssim_n = prod_{j<5} cs_j^w_j * ssim_5^w_5).  An image with one of those five means
+ * <= 0 has ms_ssim_n = 0 and a gradient of exact zeros.  `out` is a DEVICE fp32 slot written by the call's own final kernel
+ * (no jpdse_loss_finalize term).  stats (optional, DEVICE doubles [N][11]): cs_1..5, ssim_1..5, ms_ssim_n.
+ * dfake != NULL: the same call also writes dfake = scale * d out[0] / d fake in fake's dtype and layout (padding lanes 0).
+ * No atomics: two calls on the same buffers give bit-identical out, stats and dfake.  C must be 3 and min(H, W) >= 176, else
+ * JPDSE_EINVAL before any launch; ws: jpdse_msssim_loss_workspace_size() bytes (0 for an unsupported shape; with_grad != 0
+ * includes the coefficient maps and gradient planes a call with dfake needs). */
+size_t jpdse_msssim_loss_workspace_size(int32_t N, int32_t H, int32_t W, int32_t C, int32_t with_grad);
+typedef struct jpdse_msssim_loss_args {
+  int32_t dtype, N, H, W, C;
+  const void* fake;    /* NHWC [N][H][W][CPAD(3)] in `dtype` */
+  const void* real;    /* the same shape and dtype */
+  const double* mean;  /* host, 3 doubles */
+  const double* std;   /* host, 3 doubles */
+  float* out;          /* device fp32 slot */
+  double* stats;       /* device [N][11], or NULL */
+  void* dfake;         /* device, fake's shape and dtype, or NULL: forward only */
+  float scale;         /* read when dfake != NULL */
+  void* ws;
+  size_t ws_bytes;
+  void* stream;
+} jpdse_msssim_loss_args;
+int jpdse_msssim_loss(const jpdse_msssim_loss_args* args);
 
 /* ---- optimizer ---------------------------------------------------------------------- */
 /* torch.optim.Adam (model.py:275,279) over a table of tensors, one launch.  `table` is a

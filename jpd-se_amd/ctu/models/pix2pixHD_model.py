@@ -151,6 +151,8 @@ class Pix2PixHDModel(BaseModel):
       unsupported.append('--norm ' + str(opt.norm))
     if unsupported:
       raise NotImplementedError('outside the accelerated JPD-SE path (SURVEY.md §2): ' + '; '.join(unsupported))
+    if opt.distortion_loss_fn not in ('l1', 'mse', 'ms_ssim'):      # before any network (hence any device allocation) exists
+      raise ValueError('distortion_loss_fn must be l1, mse or ms_ssim')
     self.opt = opt
     self.is_train = opt.is_train
     self.use_features = True
@@ -221,8 +223,6 @@ class Pix2PixHDModel(BaseModel):
       self.loss_names = LOSS_NAMES
     else:
       self.loss_names = ('G_Distortion')
-    if opt.distortion_loss_fn not in ('l1', 'mse'):
-      raise ValueError('distortion_loss_fn must be l1 or mse')
     self.grad_buckets = {}           # 'G' / 'D' -> jpdse_hip.ddp.GradBuckets (set by the trainer for DDP)
     self._one = None
 
@@ -423,10 +423,25 @@ class Pix2PixHDModel(BaseModel):
       fake, _ = self.netG.fwd(self._g_input_eval(pre))
       return ops.nhwc_to_nchw(fake)
 
+  def _require_ms_ssim_size(self, x_dict):
+    """--distortion_loss_fn ms_ssim: five scales of an 11x11 window need a shorter side of 176; refused before any device work."""
+    if self.opt.distortion_loss_fn != 'ms_ssim':
+      return
+    h, w = int(x_dict['label'].shape[-2]), int(x_dict['label'].shape[-1])
+    if min(h, w) < ops.MSSSIM_MIN_SIDE:
+      raise ValueError('distortion_loss_fn ms_ssim: the shorter image side must be at least %d (five MS-SSIM scales of an '
+                       '11x11 window), got %d x %d' % (ops.MSSSIM_MIN_SIDE, h, w))
+
   def get_eval_loss(self, x_dict):
     """Distortion on de-normalised, clipped, uint8-truncated images (0..255 scale), as the reference computes it on
     the host through tensor2im (pix2pixHD_model.py:636-641, utils/misc.py:64-95) -- here one device pass
-    (jpdse_quant_loss: the same float64 arithmetic, bit-identical quantisation, no device->host image copies)."""
+    (jpdse_quant_loss: the same float64 arithmetic, bit-identical quantisation, no device->host image copies).
+    Under --distortion_loss_fn ms_ssim (extension): 1 - ms_ssim of the same quantised images, from the jpdse_eval_metrics
+    pass (get_eval_metrics' figure)."""
+    self._require_ms_ssim_size(x_dict)
+    if self.opt.distortion_loss_fn == 'ms_ssim':
+      m = self.get_eval_metrics(x_dict)
+      return torch.tensor(1.0 - m['ms_ssim'], dtype=torch.float32, device=self._device())
     with torch.no_grad():
       pre = self.preprocess(x_dict, build_base=not self.zero_sem)
       fake, _ = self.netG.fwd(self._g_input_eval(pre))
@@ -512,6 +527,7 @@ class Pix2PixHDModel(BaseModel):
     gradient is just that constant weight -- are produced in the same pass as the loss values
     (jpdse_l1_fwd_bwd) and handed to backward_G through `state`."""
     opt = self.opt
+    self._require_ms_ssim_size(x_dict)
     dev = self._device()
     skip = bool(getattr(opt, 'skip_unused_losses', False))
     run_d = not (skip and opt.no_g_gan_loss and opt.no_gan_feat_loss and opt.no_d_gan_loss)
@@ -615,7 +631,13 @@ class Pix2PixHDModel(BaseModel):
           d_vgg[k] = ops.l1_fwd_bwd(vf[k], vr[k], s(layout['vgg'][k]), gw['vgg'] * wk[k], relu_a=True)
         else:
           ops.l1_fwd(vf[k], vr[k], s(layout['vgg'][k]))
-      if opt.distortion_loss_fn == 'l1' and gw.get('dist'):
+      if opt.distortion_loss_fn == 'ms_ssim':
+        # its own final kernel writes the slot (no jpdse_loss_finalize term): valid where the other slots are
+        if gw.get('dist'):
+          d_dist = ops.msssim_loss_fwd_bwd(fake, real, opt.normalize_mean, opt.normalize_std, s(layout['dist']), gw['dist'])
+        else:
+          ops.msssim_loss_fwd(fake, real, opt.normalize_mean, opt.normalize_std, s(layout['dist']))
+      elif opt.distortion_loss_fn == 'l1' and gw.get('dist'):
         d_dist = ops.l1_fwd_bwd(fake, real, s(layout['dist']), gw['dist'])
       else:
         (ops.l1_fwd if opt.distortion_loss_fn == 'l1' else ops.mse_fwd)(fake, real, s(layout['dist']))
@@ -678,8 +700,15 @@ class Pix2PixHDModel(BaseModel):
       dv = self.criterionVGG.vgg.bwd(state['v_ctx'], dmaps)
       d_fake = dv if d_fake is None else ops.add_(d_fake, dv)
     if w_dist != 0.0:
-      fn = ops.l1_bwd if opt.distortion_loss_fn == 'l1' else ops.mse_bwd
-      dd = state['d_dist'] if state.get('d_dist') is not None else fn(fake, real, one, w_dist)
+      if state.get('d_dist') is not None:
+        dd = state['d_dist']
+      elif opt.distortion_loss_fn == 'ms_ssim':
+        # the gradient needs the per-image means of all five scales: the op runs its forward again (the value goes to a scratch slot)
+        dd = ops.msssim_loss_fwd_bwd(fake, real, opt.normalize_mean, opt.normalize_std,
+                                     torch.empty(1, dtype=torch.float32, device=fake.t.device), w_dist)
+      else:
+        fn = ops.l1_bwd if opt.distortion_loss_fn == 'l1' else ops.mse_bwd
+        dd = fn(fake, real, one, w_dist)
       d_fake = dd if d_fake is None else ops.add_(d_fake, dd)
     if d_fake is None:
       return False

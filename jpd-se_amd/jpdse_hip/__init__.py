@@ -57,6 +57,14 @@ class EvalMetricsSemArgs(ctypes.Structure):
               ('cls', ctypes.c_void_p), ('ws', ctypes.c_void_p), ('ws_bytes', ctypes.c_size_t), ('stream', ctypes.c_void_p)]
 
 
+class MsssimLossArgs(ctypes.Structure):
+  _fields_ = [(n, ctypes.c_int32) for n in ('dtype', 'N', 'H', 'W', 'C')] + \
+             [('fake', ctypes.c_void_p), ('real', ctypes.c_void_p), ('mean', ctypes.POINTER(ctypes.c_double)),
+              ('std', ctypes.POINTER(ctypes.c_double)), ('out', ctypes.c_void_p), ('stats', ctypes.c_void_p),
+              ('dfake', ctypes.c_void_p), ('scale', ctypes.c_float), ('ws', ctypes.c_void_p), ('ws_bytes', ctypes.c_size_t),
+              ('stream', ctypes.c_void_p)]
+
+
 _P, _I32, _I64, _F, _SZ = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float,
                            ctypes.c_size_t)
 _CD, _ND = ctypes.POINTER(ConvDesc), ctypes.POINTER(InormDesc)
@@ -144,6 +152,8 @@ SIGNATURES = {
                                   ctypes.POINTER(ctypes.c_double), _P, _P, _SZ, _P]),
     'jpdse_eval_metrics_sem_workspace_size': (_SZ, [_I32, _I32, _I32, _I32, _I32]),
     'jpdse_eval_metrics_sem': (_I32, [ctypes.POINTER(EvalMetricsSemArgs)]),
+    'jpdse_msssim_loss_workspace_size': (_SZ, [_I32, _I32, _I32, _I32, _I32]),
+    'jpdse_msssim_loss': (_I32, [ctypes.POINTER(MsssimLossArgs)]),
 }
 
 # the developer build (same sources, -DJPDSE_DEV): the shipped ABI plus include/jpdse_dev.h

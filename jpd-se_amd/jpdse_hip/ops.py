@@ -8,7 +8,7 @@ import ctypes
 
 import torch
 
-from . import (lib, check, F32, BF16, ConvDesc, InormDesc, EvalMetricsSemArgs, ACT_NONE, PAD_ZERO, PAD_REFLECT)
+from . import (lib, check, F32, BF16, ConvDesc, InormDesc, EvalMetricsSemArgs, MsssimLossArgs, ACT_NONE, PAD_ZERO, PAD_REFLECT)
 
 
 def cpad(c):
@@ -664,3 +664,41 @@ def eval_metrics(fake, real32, mean, std, label=None, n_classes=None):
   r = eval_metrics_finish(host[:fake.N * 14].view(torch.float64).view(fake.N, 14))
   r['per_class'] = eval_metrics_per_class(host[fake.N * 14:].view(fake.N, rows, 3))
   return r
+
+
+# ---- MS-SSIM training loss (msssim_loss.hip) -----------------------------------------------------
+MSSSIM_MIN_SIDE = 176
+
+
+def _msssim_loss(fake, real, mean, std, out, scale, stats):
+  assert fake.t.shape == real.t.shape and fake.C == real.C and fake.dtype == real.dtype
+  assert len(mean) == fake.C and len(std) == fake.C
+  assert out.dtype == torch.float32 and out.numel() >= 1
+  L = lib()
+  dev = fake.t.device
+  if stats is not None:
+    assert stats.dtype == torch.float64 and stats.is_contiguous() and tuple(stats.shape) == (fake.N, 11) and stats.device == dev
+  arr = ctypes.c_double * fake.C
+  with_grad = scale is not None
+  n = L.jpdse_msssim_loss_workspace_size(fake.N, fake.H, fake.W, fake.C, int(with_grad))
+  ws = workspace(max(n, 1), dev)
+  dfake = fake.empty_like() if with_grad else None
+  args = MsssimLossArgs(fake.dtype, fake.N, fake.H, fake.W, fake.C, fake.t.data_ptr(), real.t.data_ptr(),
+                        arr(*[float(v) for v in mean]), arr(*[float(v) for v in std]), out.data_ptr(),
+                        stats.data_ptr() if stats is not None else None, dfake.t.data_ptr() if with_grad else None,
+                        float(scale) if with_grad else 0.0, ws.data_ptr(), ws.numel(),
+                        torch.cuda.current_stream().cuda_stream)
+  check(L.jpdse_msssim_loss(ctypes.byref(args)), 'msssim_loss')    # an unsupported shape is refused here, before any launch
+  return dfake
+
+
+def msssim_loss_fwd(fake, real, mean, std, out, stats=None):
+  """out (fp32 device slot) = mean_n (1 - ms_ssim_n) of the de-normalised, un-quantised images `fake` against `real` (Acts of
+  one dtype, 3 channels).  The slot is written by the call itself, also inside deferred_loss_finals.
+  stats: optional float64 device tensor [N, 11] that receives cs_1..5, ssim_1..5 and ms_ssim_n per image."""
+  _msssim_loss(fake, real, mean, std, out, None, stats)
+
+
+def msssim_loss_fwd_bwd(fake, real, mean, std, out, scale, stats=None):
+  """msssim_loss_fwd and, from the same call, the Act scale * d out / d fake (fake's dtype and layout)."""
+  return _msssim_loss(fake, real, mean, std, out, scale, stats)
