@@ -37,8 +37,9 @@ extern "C" {
                                 * the learned codec (jpdse_binarize_fwd, jpdse_code_stats[_workspace_size], jpdse_code_export) was added to
                                 * version 2 later, and so were the evaluation metrics (jpdse_eval_metrics[_workspace_size]) and their
                                 * per-class form (jpdse_eval_metrics_sem[_workspace_size]), and the receiver side of the codec
-                                * (jpdse_code_import), and the MS-SSIM training loss (jpdse_msssim_loss[_workspace_size]): purely additive,
-                                * nothing existing changed */
+                                * (jpdse_code_import), and the MS-SSIM training loss (jpdse_msssim_loss[_workspace_size]), and the input
+                                * builder for more than 64 storage channels (jpdse_input_builder_wide): purely additive, nothing existing
+                                * changed */
 
 enum { JPDSE_F32 = 0, JPDSE_BF16 = 1 };
 enum { JPDSE_PAD_ZERO = 0, JPDSE_PAD_REFLECT = 1 };
@@ -300,6 +301,15 @@ int jpdse_onehot_edge(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t nu
 int jpdse_input_builder(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t num_labels, const float* label,
                         const int64_t* instance, int32_t n_dst, void* const* dst, const void* const* img, int32_t cs,
                         int32_t img_cs, int32_t c0, int32_t nch, void* stream);
+/* The same pass for wide label sets (ADE20K: 151 one-hot lanes + edge + 3 image lanes = 160 storage channels).
+ * jpdse_input_builder has one kernel per storage width up to 64 channels and refuses anything wider; this entry point takes
+ * the same arguments with the same meaning for ANY cs % 8 == 0 with num_labels < cs: the vector count per pixel is a
+ * run-time value of the one kernel behind it.  A label id >= num_labels lights no lane; lanes of [c0, c0 + nch) come from
+ * img[i] (zero where img[i] is NULL); every other lane is zero.  Refusals are those of jpdse_input_builder, without the
+ * width limit. */
+int jpdse_input_builder_wide(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t num_labels, const float* label,
+                             const int64_t* instance, int32_t n_dst, void* const* dst, const void* const* img, int32_t cs,
+                             int32_t img_cs, int32_t c0, int32_t nch, void* /* hipStream_t */ stream);
 /* dst[..., c0 : c0 + nch] = img[..., 0 : nch] in place (the generated image into the discriminator input, model.py:456):
  * touches only the 16-byte vectors of dst that hold those channels. */
 int jpdse_insert_channels(int32_t dtype, int64_t npix, void* dst, int32_t cs, const void* img, int32_t img_cs, int32_t c0,

@@ -401,6 +401,8 @@ struct BuilderArgs {
 // One thread per 16-byte vector, consecutive lanes = consecutive vectors (every store instruction of a wave writes 1 KiB of
 // contiguous bytes; a thread-per-pixel form, whose lanes store 80 bytes apart, ran at 2.1 TB/s), 32-bit index arithmetic with
 // the vector count per pixel a compile-time constant (the first version did four 64-bit divisions per vector: 1.9 TB/s).
+// CV == 0 is the wide form (jpdse_input_builder_wide, more than 64 storage channels): the vector count per pixel comes from
+// the arguments and costs the one 32-bit division below; everything else is the same code.
 template <typename T, int CV>
 __global__ __launch_bounds__(256) void input_builder_kernel(const BuilderArgs a, unsigned total_vec) {
   constexpr int VE = Vec16<T>::N;
@@ -408,8 +410,9 @@ __global__ __launch_bounds__(256) void input_builder_kernel(const BuilderArgs a,
   // compiler knows) the next iteration's label load could not start, and the loop ran at memory latency per iteration
   const unsigned idx = blockIdx.x * 256u + threadIdx.x;
   if (idx < total_vec) {
-    const unsigned pix = idx / (unsigned)CV;
-    const int cb = (int)(idx - pix * (unsigned)CV) * VE;
+    const unsigned cv = CV > 0 ? (unsigned)CV : (unsigned)a.cs / (unsigned)VE;
+    const unsigned pix = idx / cv;
+    const int cb = (int)(idx - pix * cv) * VE;
     const int lab = (int)(long long)a.label[pix];
     float v[VE];
 #pragma unroll
@@ -889,9 +892,11 @@ int jpdse_onehot_edge(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t nu
   });
 }
 
-int jpdse_input_builder(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t num_labels, const float* label,
+// Argument checks and the kernel arguments shared by jpdse_input_builder and jpdse_input_builder_wide; *tv = 16-byte vectors
+// per destination.
+static int builder_args(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t num_labels, const float* label,
                         const int64_t* instance, int32_t n_dst, void* const* dst, const void* const* img, int32_t cs,
-                        int32_t img_cs, int32_t c0, int32_t nch, void* stream) {
+                        int32_t img_cs, int32_t c0, int32_t nch, BuilderArgs* out, long long* tv) {
   JPDSE_REQUIRE(!bad_dtype(dtype) && label && instance && dst && img && N > 0 && H > 0 && W > 0, "input_builder: bad argument");
   JPDSE_REQUIRE(n_dst >= 1 && n_dst <= 3, "input_builder: 1..3 destinations");
   JPDSE_REQUIRE(num_labels >= 0 && num_labels < cs && cs % 8 == 0 && img_cs % 8 == 0, "input_builder: bad channel counts");
@@ -912,8 +917,18 @@ int jpdse_input_builder(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t 
   a.img_cs = img_cs;
   a.c0 = c0;
   a.nch = nch;
-  const long long tv = nhwc_vecs(dtype, (long long)N * H * W, cs);
-  JPDSE_REQUIRE(tv < (1LL << 32), "input_builder: more than 2^32 vectors");
+  *tv = nhwc_vecs(dtype, (long long)N * H * W, cs);
+  JPDSE_REQUIRE(*tv < (1LL << 32), "input_builder: more than 2^32 vectors");
+  *out = a;
+  return JPDSE_OK;
+}
+
+int jpdse_input_builder(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t num_labels, const float* label,
+                        const int64_t* instance, int32_t n_dst, void* const* dst, const void* const* img, int32_t cs,
+                        int32_t img_cs, int32_t c0, int32_t nch, void* stream) {
+  BuilderArgs a;
+  long long tv;
+  if (int rc = builder_args(dtype, N, H, W, num_labels, label, instance, n_dst, dst, img, cs, img_cs, c0, nch, &a, &tv)) return rc;
   // the vector count per pixel is a template parameter (cheap index arithmetic): 40 storage channels are the hot path
   // (5 bf16 / 10 fp32 vectors), other widths up to 64 channels have their own instantiation
   return by_dtype(dtype, [&](auto tag) {
@@ -932,6 +947,19 @@ int jpdse_input_builder(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t 
       default: return set_error(JPDSE_EINVAL, "input_builder: %d storage channels unsupported (<= 64)", cs);
     }
     return launch256("input_builder", kernel, dim3((unsigned)((tv + 255) / 256)), stream, a, (unsigned)tv);
+  });
+}
+
+int jpdse_input_builder_wide(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t num_labels, const float* label,
+                             const int64_t* instance, int32_t n_dst, void* const* dst, const void* const* img, int32_t cs,
+                             int32_t img_cs, int32_t c0, int32_t nch, void* stream) {
+  BuilderArgs a;
+  long long tv;
+  if (int rc = builder_args(dtype, N, H, W, num_labels, label, instance, n_dst, dst, img, cs, img_cs, c0, nch, &a, &tv)) return rc;
+  return by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return launch256("input_builder_wide", input_builder_kernel<T, 0>, dim3((unsigned)((tv + 255) / 256)), stream, a,
+                     (unsigned)tv);
   });
 }
 

@@ -129,6 +129,8 @@ SIGNATURES = {
     'jpdse_onehot_edge': (_I32, [_I32, _I32, _I32, _I32, _I32, _P, _P, _P, _I32, _P]),
     'jpdse_input_builder': (_I32, [_I32, _I32, _I32, _I32, _I32, _P, _P, _I32, ctypes.POINTER(_P), ctypes.POINTER(_P), _I32, _I32,
                                    _I32, _I32, _P]),
+    'jpdse_input_builder_wide': (_I32, [_I32, _I32, _I32, _I32, _I32, _P, _P, _I32, ctypes.POINTER(_P), ctypes.POINTER(_P), _I32,
+                                        _I32, _I32, _I32, _P]),
     'jpdse_insert_channels': (_I32, [_I32, _I64, _P, _I32, _P, _I32, _I32, _I32, _P]),
     'jpdse_loss_workspace_size': (_SZ, [_I64]),
     'jpdse_loss_partial_count': (_I32, [_I64]),

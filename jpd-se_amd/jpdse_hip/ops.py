@@ -370,7 +370,8 @@ def onehot_edge(label, instance, num_labels, total_c, dtype_code):
 
 def input_builder(label, instance, num_labels, dsts, imgs, c0):
   """One pass: every Act of `dsts` (same N,H,W,C) gets one-hot(label) | edge(instance) | its image of `imgs` (Act or None)
-  at channels [c0, c0 + 3).  Replaces onehot_edge + one concat_channels per destination."""
+  at channels [c0, c0 + 3).  Replaces onehot_edge + one concat_channels per destination.  Up to 64 storage channels take
+  jpdse_input_builder (one kernel per width), wider destinations (more than 60 labels) jpdse_input_builder_wide."""
   assert label.dtype == torch.float32 and instance.dtype == torch.int64 and label.is_contiguous() and instance.is_contiguous()
   assert 1 <= len(dsts) <= 3 and len(imgs) == len(dsts)
   N, _, H, W = label.shape
@@ -381,9 +382,10 @@ def input_builder(label, instance, num_labels, dsts, imgs, c0):
     assert tuple(d.t.shape) == tuple(d0.t.shape) and d.t.shape[:3] == (N, H, W) and d.dtype == d0.dtype
     assert im is None or (im.Cs == img_cs and im.C == nch and im.dtype == d0.dtype and im.t.shape[:3] == (N, H, W))
   arr = ctypes.c_void_p * len(dsts)
-  check(lib().jpdse_input_builder(d0.dtype, N, H, W, num_labels, _p(label), _p(instance), len(dsts),
-                                  arr(*[d.t.data_ptr() for d in dsts]), arr(*[(im.t.data_ptr() if im is not None else None) for im in imgs]),
-                                  d0.Cs, img_cs, c0, nch, _stream()), 'input_builder')
+  entry = lib().jpdse_input_builder if d0.Cs <= 64 else lib().jpdse_input_builder_wide
+  check(entry(d0.dtype, N, H, W, num_labels, _p(label), _p(instance), len(dsts),
+              arr(*[d.t.data_ptr() for d in dsts]), arr(*[(im.t.data_ptr() if im is not None else None) for im in imgs]),
+              d0.Cs, img_cs, c0, nch, _stream()), 'input_builder')
   return dsts
 
 
