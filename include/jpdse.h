@@ -38,8 +38,8 @@ extern "C" {
                                 * version 2 later, and so were the evaluation metrics (jpdse_eval_metrics[_workspace_size]) and their
                                 * per-class form (jpdse_eval_metrics_sem[_workspace_size]), and the receiver side of the codec
                                 * (jpdse_code_import), and the MS-SSIM training loss (jpdse_msssim_loss[_workspace_size]), and the input
-                                * builder for more than 64 storage channels (jpdse_input_builder_wide): purely additive, nothing existing
-                                * changed */
+                                * builder for more than 64 storage channels (jpdse_input_builder_wide), and the entropy-coded bitstream
+                                * (jpdse_code_entropy_*): purely additive, nothing existing changed */
 
 enum { JPDSE_F32 = 0, JPDSE_BF16 = 1 };
 enum { JPDSE_PAD_ZERO = 0, JPDSE_PAD_REFLECT = 1 };
@@ -401,6 +401,35 @@ int jpdse_code_export(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C,
  * A NULL pointer, a non-positive extent or a bad dtype is JPDSE_EINVAL before any launch. */
 int jpdse_code_import(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, const void* in, int32_t packed, void* b,
                       void* /* hipStream_t */ stream);
+
+/* ---- learned codec: entropy-coded bitstream (no reference counterpart; format: DESIGN.md 4.8) ---------------------------
+ * A lossless, context-adaptive binary range coder over the bits (b > 0) of the code b = NHWC [N][H][W][CPAD(C)]: every
+ * (image, channel) pair is one stream of H*W symbols in raster order with 16 adaptive probabilities (context = the coded
+ * neighbours left | up << 1 | upleft << 2 | upright << 3), coded by the carry-propagating range coder of LZMA.  The payload
+ * of one image is C little-endian uint32 stream lengths followed by the C streams in channel order.  Bit-exact and
+ * deterministic: the same code gives the same bytes on every call.
+ * Limits: N <= 65535, W <= 4096 and a payload capacity below 2^31 bytes; anything else is JPDSE_EINVAL before any launch, as
+ * are a NULL pointer, a bad dtype, a non-positive extent and a buffer or row stride that is too small. */
+/* Bytes one image's payload can never exceed: C * (4 + H*W + 8) (a symbol costs less than 6.05 bits); 0 for
+ * a shape outside the limits.  Host only. */
+size_t jpdse_code_entropy_capacity(int32_t H, int32_t W, int32_t C);
+/* Host only; 0 for a shape outside the limits. */
+size_t jpdse_code_entropy_workspace_size(int32_t N, int32_t H, int32_t W, int32_t C);
+/* out: DEVICE uint8 [N][out_stride], out_stride >= jpdse_code_entropy_capacity(); image n's payload is the first sizes[n]
+ * bytes of row n, the rest of the row is not written.  sizes, status: DEVICE int32 [N]; status[n] != 0: a stream of image n
+ * outgrew its H*W + 8 bytes and was cut (the derived bound says it cannot; nothing is ever written past a capacity).
+ * An exact 0 of the eval binarizer is coded as bit 0, as jpdse_code_export stores it.  ws:
+ * jpdse_code_entropy_workspace_size() bytes. */
+int jpdse_code_entropy_encode(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, const void* b, uint8_t* out,
+                              int64_t out_stride, int32_t* sizes, int32_t* status, void* ws, size_t ws_bytes,
+                              void* /* hipStream_t */ stream);
+/* in: DEVICE uint8 [N][in_stride], payload n in the first sizes[n] bytes of row n; sizes: HOST int32 [N], checked against
+ * [4 C, in_stride] before any launch.  b: every logical lane becomes +1 or -1 and every padding lane 0 -- what
+ * jpdse_code_import writes for the raw code.  The length tables inside the payloads are device data and are not trusted: a
+ * stream is clipped to its row, bytes past a stream's end read as 0 and the symbol count is fixed at H*W, so no payload can
+ * make the call read outside `in` or write outside `b`. */
+int jpdse_code_entropy_decode(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, const uint8_t* in, int64_t in_stride,
+                              const int32_t* sizes, void* b, void* /* hipStream_t */ stream);
 
 /* ---- evaluation metrics: L1, MSE and MS-SSIM of a reconstruction in one pass (test.py:114-125) --------------------------
  * fake (fp32 or bf16) and real (fp32): NHWC [N][H][W][CPAD(3)] normalised images; both are quantised with q() of

@@ -26,6 +26,7 @@ from jpdse_hip import ops
 from jpdse_hip.ops import Act
 from jpdse_hip.optim import FusedAdam
 from jpdse_hip.layers import PackBatcher
+from ctu.utils import bitstream, entropy
 from ctu.utils.image_pool import ImagePool
 from ctu.models.pix2pixHD_networks.base_model import BaseModel
 from ctu.models.pix2pixHD_networks import networks
@@ -467,11 +468,15 @@ class Pix2PixHDModel(BaseModel):
       raise ValueError('decode: code of shape %s, but %d label maps of %d x %d carry a %s code of shape %s (%d x %d x %d bits '
                        'per image)' % (tuple(code.shape), N, H, W, 'packed' if code.dtype == torch.uint8 else 'float32',
                                        want, C, h, w))
+    return self._generate_from_code(
+        lambda: ops.code_import(code.to(self._device(), non_blocking=True), N, h, w, C, self.cdtype), x_dict, N, H, W)
+
+  def _generate_from_code(self, import_b, x_dict, N, H, W):
+    """The receiver's device work, shared by decode and decode_coded: import_b() gives the code Act."""
     label, inst = self._semantics(x_dict)
     vis = None                           # --zero_vis: nothing visual reaches the generator, the code is not read
     if not self.zero_vis:
-      b = ops.code_import(code.to(self._device(), non_blocking=True), N, h, w, C, self.cdtype)
-      vis = self.netE.decode_code(b)
+      vis = self.netE.decode_code(import_b())
     base = None if self.zero_sem else ops.onehot_edge(label, inst, self.n_onehot, self.label_nc + self.feat_nc, self.cdtype)
     fake, _ = self.netG.fwd(self._g_input_from_vis(vis, base, N, H, W))
     return fake, label
@@ -491,6 +496,46 @@ class Pix2PixHDModel(BaseModel):
     with torch.no_grad():
       fake, _ = self._decode_act(code, x_dict)
       return ops.nhwc_to_nchw(fake)
+
+  # ---- entropy-coded bitstream (extension) ------------------------------------------------------------------
+  def get_coded(self, x_dict):
+    """The entropy-coded form of get_code(x_dict, packed=True): a list of N `bytes`, per image the C stream lengths and the C
+    range-coded streams (ops.code_entropy_encode).  Lossless: decode_coded(get_coded(x), x) equals
+    decode(get_code(x, packed=True), x) bit for bit."""
+    with torch.no_grad():
+      return ops.code_entropy_encode(self._code_act(x_dict))
+
+  def decode_coded(self, payloads, x_dict):
+    """decode() from what get_coded returned: a list of one `bytes` payload per label map.  ValueError, before any device
+    work, without an encoder or a binarizer, for a label map that is no multiple of the encoder's down-sampling factor, a
+    wrong payload count, an item that is not bytes, and a payload whose length table does not add up."""
+    self._require_binarizer()
+    N, H, W = int(x_dict['label'].shape[0]), int(x_dict['label'].shape[-2]), int(x_dict['label'].shape[-1])
+    step = 1 << self.netE.n_downsampling
+    if H % step or W % step:
+      raise ValueError('decode_coded: a %d x %d label map is no multiple of the encoder\'s down-sampling factor %d' % (H, W, step))
+    C, h, w = self.netE.code_shape(H, W)
+    if not isinstance(payloads, (list, tuple)) or len(payloads) != N:
+      raise ValueError('decode_coded: the payloads must be what get_coded returns: a list of %d bytes objects, one per label map'
+                       % N)
+    for j, p in enumerate(payloads):
+      entropy.check_payload(p, C, 'decode_coded: payload %d' % j)
+    with torch.no_grad():
+      fake, _ = self._generate_from_code(
+          lambda: ops.code_entropy_decode(list(payloads), N, h, w, C, self.cdtype, self._device()), x_dict, N, H, W)
+      return ops.nhwc_to_nchw(fake)
+
+  def get_coded_rate(self, x_dict):
+    """(coded bpp, raw bpp) averaged over the batch, two Python floats: 8 * file bytes / pixels of the .jpda file
+    (ctu.utils.entropy: 24-byte header, and the raw payload where coding does not pay) and of the .jpdc file
+    (ctu.utils.bitstream: 20-byte header) of each image.  Sizes of real files, not estimates; get_eval_rate is the
+    reference's Shannon figure."""
+    payloads = self.get_coded(x_dict)
+    H, W = int(x_dict['image'].shape[-2]), int(x_dict['image'].shape[-1])
+    shape = self.netE.code_shape(H, W)
+    coded = sum(8.0 * entropy.file_bytes(len(p), shape) / (H * W) for p in payloads) / len(payloads)
+    raw = 8.0 * (bitstream.HEADER_BYTES + bitstream.payload_bytes(shape)) / (H * W)
+    return coded, raw
 
   def _eval_metrics_of(self, fake, image, label, per_class):
     """The tail get_eval_metrics and get_eval_metrics_decoded share: `fake` (the generator's NHWC output) against the original

@@ -159,6 +159,24 @@ class Pix2PixHDTrainer(BaseTrainer):
     self.eval()
     return self.model.get_eval_metrics_decoded(code, x_dict, per_class)
 
+  def get_coded(self, x_dict):
+    """The entropy-coded bitstream (extension): a list with one `bytes` payload per image, the lossless
+    range-coded form of get_code(x_dict, packed=True).  ctu.utils.entropy.write_coded stores one as a .jpda file."""
+    self.eval()
+    return self.model.get_coded(x_dict)
+
+  def decode_coded(self, payloads, x_dict):
+    """decode() from the payloads get_coded returned: equal to decode(get_code(x_dict, packed=True), x_dict) bit for bit.
+    A wrong payload count, an item that is not bytes or an inconsistent length table is a ValueError before device work."""
+    self.eval()
+    return self.model.decode_coded(payloads, x_dict)
+
+  def get_coded_rate(self, x_dict):
+    """(coded bpp, raw bpp), Python floats, batch means: the sizes of the .jpda and of the .jpdc file of each image, headers
+    included, in bits per pixel.  What a coder produced -- next to get_eval_rate's Shannon estimate, which stays as it is."""
+    self.eval()
+    return self.model.get_coded_rate(x_dict)
+
   # ---- checkpoints ------------------------------------------------------------------------------
   # File contract of the reference (pix2pixHD_trainer.py:119-176, base_model.py:54-59): <save_dir>/net_G.pth,
   # net_D.pth (state dicts) and stats_and_optim.pt with the keys below.  Optional entries are written / read only when

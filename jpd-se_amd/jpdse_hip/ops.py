@@ -5,10 +5,11 @@ arithmetic happens inside libjpdse_hip.so.  Activations travel as `Act`: an NHWC
 [N,H,W,CPAD(C)] (fp32 or bf16) plus its logical channel count.
 """
 import ctypes
+import struct
 
 import torch
 
-from . import (lib, check, F32, BF16, ConvDesc, InormDesc, EvalMetricsSemArgs, MsssimLossArgs, ACT_NONE, PAD_ZERO, PAD_REFLECT)
+from . import (lib, check, JpdseError, F32, BF16, ConvDesc, InormDesc, EvalMetricsSemArgs, MsssimLossArgs, ACT_NONE, PAD_ZERO, PAD_REFLECT)
 
 
 def cpad(c):
@@ -564,6 +565,62 @@ def code_import(code, N, H, W, C, dtype_code, out=None):
   b = out if out is not None else Act.empty(N, H, W, C, dtype_code, code.device)
   assert (b.N, b.H, b.W, b.C, b.dtype) == (N, H, W, C, dtype_code) and b.t.device == code.device
   check(lib().jpdse_code_import(dtype_code, N, H, W, C, _p(code), 1 if packed else 0, _p(b.t), _stream()), 'code_import')
+  return b
+
+
+# ---- learned codec: entropy-coded bitstream (entropy.hip; format: DESIGN.md 4.8) -------------------------------------------
+def code_entropy_encode(b):
+  """The entropy-coded payload of every image of the code `b` (jpdse_code_entropy_encode): a list of N `bytes`, each the
+  image's C little-endian uint32 stream lengths followed by its C streams.  One device buffer -- the N sizes, the N status
+  words, then the payload rows -- is copied to the host once.  JpdseError if a stream outgrew its derived capacity."""
+  L = lib()
+  N, dev = b.N, b.t.device
+  cap = L.jpdse_code_entropy_capacity(b.H, b.W, b.C)
+  n_ws = L.jpdse_code_entropy_workspace_size(N, b.H, b.W, b.C)
+  if cap == 0 or n_ws == 0:
+    raise ValueError('code_entropy_encode: a %d x %d x %d x %d code is beyond the coder\'s limits' % (N, b.C, b.H, b.W))
+  head = (8 * N + 15) // 16 * 16
+  buf = torch.empty(head + N * cap, dtype=torch.uint8, device=dev)
+  meta = buf[:8 * N].view(torch.int32)
+  ws = workspace(n_ws, dev)
+  check(L.jpdse_code_entropy_encode(b.dtype, N, b.H, b.W, b.C, _p(b.t), _p(buf[head:]), cap, _p(meta[:N]), _p(meta[N:]),
+                                    _p(ws), ws.numel(), _stream()), 'code_entropy_encode')
+  host = buf.cpu().numpy()
+  sizes, status = host[:4 * N].view('<i4'), host[4 * N:8 * N].view('<i4')
+  if status.any():
+    raise JpdseError('code_entropy_encode: a stream outgrew its H*W + 8 bytes (status %s)' % (status.tolist(),))
+  return [host[head + n * cap:head + n * cap + int(sizes[n])].tobytes() for n in range(N)]
+
+
+def code_entropy_decode(payloads, N, H, W, C, dtype_code, device=None):
+  """The inverse (jpdse_code_entropy_decode): N payloads as code_entropy_encode returns them -> the NHWC Act [N, H, W, C] of
+  +1 / -1 that code_import gives for the raw code.  ValueError before any library call for a wrong payload count, an item
+  that is not `bytes`, or a payload whose length table does not add up to the bytes that follow it.  device: where the Act
+  is made (default: the current device)."""
+  if not isinstance(payloads, (list, tuple)) or len(payloads) != N:
+    raise ValueError('code_entropy_decode: expected a list of %d payloads, got %s'
+                     % (N, 'a list of %d' % len(payloads) if isinstance(payloads, (list, tuple)) else type(payloads).__name__))
+  for n, p in enumerate(payloads):
+    if not isinstance(p, (bytes, bytearray)):
+      raise ValueError('code_entropy_decode: payload %d is %s, not bytes' % (n, type(p).__name__))
+    if len(p) < 4 * C:
+      raise ValueError('code_entropy_decode: payload %d of %d bytes is shorter than its table of %d stream lengths' % (n, len(p), C))
+    total = sum(struct.unpack_from('<%dI' % C, p))
+    if total != len(p) - 4 * C:
+      raise ValueError('code_entropy_decode: the length table of payload %d sums to %d, but %d bytes follow it'
+                       % (n, total, len(p) - 4 * C))
+  stride = max(len(p) for p in payloads)
+  if stride >= 1 << 31:
+    raise ValueError('code_entropy_decode: a payload of %d bytes' % stride)
+  rows = torch.zeros((N, stride), dtype=torch.uint8)
+  for n, p in enumerate(payloads):
+    rows[n, :len(p)] = torch.frombuffer(bytearray(p), dtype=torch.uint8)
+  sizes = (ctypes.c_int32 * N)(*[len(p) for p in payloads])
+  dev = device if device is not None else torch.device('cuda', torch.cuda.current_device())
+  rows = rows.to(dev)
+  b = Act.empty(N, H, W, C, dtype_code, dev)
+  check(lib().jpdse_code_entropy_decode(dtype_code, N, H, W, C, _p(rows), stride, sizes, _p(b.t), _stream()),
+        'code_entropy_decode')
   return b
 
 

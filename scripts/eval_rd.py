@@ -16,9 +16,13 @@ line gains the bpp of the files (header included) beside get_eval_rate's actual_
 between the decoded image and get_img's: 0 unless the eval code holds an exact zero, which is stored as a 0 bit and decoded
 as -1 while get_img feeds the 0 forward.
 
+--entropy (needs --codec) adds the bpp a coder actually produced: trainer.get_coded_rate, the size of each image's .jpda file
+(ctu.utils.entropy: the range-coded payload of DESIGN.md 4.8, or the raw one where coding does not pay), header included,
+beside get_eval_rate's Shannon estimate.  With --roundtrip the files written and decoded from are those .jpda files.
+
   python scripts/eval_rd.py [--batches 4] [--batch 2] [--width 1024] [--height 512] [--dtype bf16] [--codec]
                             [--checkpoints_dir DIR] [--data DIR] [--per-class] [--zero_sem] [--zero_ins] [--zero_vis]
-                            [--roundtrip DIR]
+                            [--roundtrip DIR] [--entropy]
 """
 import argparse
 import contextlib
@@ -48,17 +52,29 @@ def batches(args):
       yield synthetic_batch(args.batch, args.height, args.width, seed=1234 + i)
 
 
-def roundtrip(trainer, x_dict, folder, batch_index):
-  """Encode x_dict, store one file per image, read the files back: (code [N, bytes] uint8 CPU tensor, file bpp per image)."""
-  from ctu.utils import bitstream
+def roundtrip(trainer, x_dict, folder, batch_index, coded=False):
+  """Encode x_dict, store one file per image, read the files back: (code [N, bytes] uint8 tensor, file bpp per image).
+  coded: .jpda files (ctu.utils.entropy) instead of .jpdc ones; the rows of their range-coded payloads are decoded on the
+  device (ops.code_entropy_decode) and re-packed, so the receiver below is the same for both kinds of file."""
+  from ctu.utils import bitstream, entropy
+  from jpdse_hip import ops
   code = trainer.get_code(x_dict, packed=True).cpu()
+  payloads = trainer.get_coded(x_dict) if coded else None
   H, W = int(x_dict['label'].shape[-2]), int(x_dict['label'].shape[-1])
   shape = trainer.model.netE.code_shape(H, W)
   rows, bpp = [], []
   for j in range(code.shape[0]):
-    path = os.path.join(folder, 'b%04d_i%02d.jpdc' % (batch_index, j))
-    bitstream.write_code(path, code[j], shape)
-    row, got = bitstream.read_code(path)
+    path = os.path.join(folder, 'b%04d_i%02d%s' % (batch_index, j, entropy.SUFFIX if coded else '.jpdc'))
+    if coded:
+      entropy.write_coded(path, payloads[j], code[j], shape)
+      row, mode, got = entropy.read_coded(path)
+      if mode == entropy.MODE_CODED:
+        C, h, w = got
+        b = ops.code_entropy_decode([row], 1, h, w, C, trainer.model.cdtype, trainer.model._device())
+        row = ops.code_export(b, packed=True)[0].cpu()
+    else:
+      bitstream.write_code(path, code[j], shape)
+      row, got = bitstream.read_code(path)
     if tuple(got) != tuple(shape):
       raise SystemExit('%s: code shape %s, expected %s' % (path, got, shape))
     rows.append(row)
@@ -82,9 +98,13 @@ def main():
     ap.add_argument('--' + flag, action='store_true', help='ablation input of the reference (same flag)')
   ap.add_argument('--roundtrip', default=None, metavar='DIR',
                   help='with --codec: store every code under DIR, decode from the files, report the decoded images')
+  ap.add_argument('--entropy', action='store_true',
+                  help='with --codec: also report the bpp of the entropy-coded files; --roundtrip then stores and decodes those')
   args = ap.parse_args()
   if args.roundtrip and not args.codec:
     ap.error('--roundtrip needs --codec')
+  if args.entropy and not args.codec:
+    ap.error('--entropy needs --codec')
   if args.roundtrip:
     os.makedirs(args.roundtrip, exist_ok=True)
   import jpdse_hip
@@ -104,14 +124,14 @@ def main():
   with contextlib.redirect_stdout(sys.stderr):
     trainer = get_trainer(opt)(opt, 'test' if args.checkpoints_dir else 'train')
   keys = ('l1', 'mse', 'ms_ssim', 'psnr')
-  by_batch = dict.fromkeys(keys + ('shannon', 'actual', 'file'), 0.0)
-  by_image = dict.fromkeys(keys + ('shannon', 'actual', 'file'), 0.0)
+  by_batch = dict.fromkeys(keys + ('shannon', 'actual', 'file', 'coded'), 0.0)
+  by_image = dict.fromkeys(keys + ('shannon', 'actual', 'file', 'coded'), 0.0)
   images, n_batches, worst_diff = 0, 0, 0.0
   class_sums = None                  # int64 [1, n_classes + 1, 3]: the raw class tables of every image so far, added up
   start = time.time()
   for i, x_dict in enumerate(batches(args)):
     if args.roundtrip:
-      code, file_bpp = roundtrip(trainer, x_dict, args.roundtrip, i)
+      code, file_bpp = roundtrip(trainer, x_dict, args.roundtrip, i, coded=args.entropy)
       receiver = dict(label=x_dict['label'], instance=x_dict['instance'])      # all the receiver has besides the files
       decoded = trainer.decode(code, receiver)
       diff = float((decoded - trainer.get_img(x_dict)).abs().max())
@@ -133,6 +153,11 @@ def main():
       by_image['shannon'] += shannon * b
       by_image['actual'] += actual * b
       line += ', pre-/(estimated) post-entropy coding bpp {:.4f}/{:.4f}'.format(actual, shannon)
+    if args.entropy:
+      coded_bpp, raw_file_bpp = trainer.get_coded_rate(x_dict)
+      by_batch['coded'] += coded_bpp
+      by_image['coded'] += coded_bpp * b
+      line += ', coded file bpp {:.4f} (raw file {:.4f})'.format(coded_bpp, raw_file_bpp)
     if args.roundtrip:
       by_batch['file'] += sum(file_bpp) / len(file_bpp)
       by_image['file'] += sum(file_bpp)
@@ -152,6 +177,8 @@ def main():
                                                                             t['ms_ssim'] / n, t['psnr'] / n)
     if args.codec:
       line += ', avg pre-/(estimated) post-entropy coding bpp {:.4f}/{:.4f}'.format(t['actual'] / n, t['shannon'] / n)
+    if args.entropy:
+      line += ', avg coded file bpp {:.4f}'.format(t['coded'] / n)
     if args.roundtrip:
       line += ', avg file bpp {:.4f}'.format(t['file'] / n)
     return line
