@@ -39,7 +39,8 @@ extern "C" {
                                 * per-class form (jpdse_eval_metrics_sem[_workspace_size]), and the receiver side of the codec
                                 * (jpdse_code_import), and the MS-SSIM training loss (jpdse_msssim_loss[_workspace_size]), and the input
                                 * builder for more than 64 storage channels (jpdse_input_builder_wide), and the entropy-coded bitstream
-                                * (jpdse_code_entropy_*): purely additive, nothing existing changed */
+                                * (jpdse_code_entropy_*), and the coded label and instance maps (jpdse_semantics_*): purely
+                                * additive, nothing existing changed */
 
 enum { JPDSE_F32 = 0, JPDSE_BF16 = 1 };
 enum { JPDSE_PAD_ZERO = 0, JPDSE_PAD_REFLECT = 1 };
@@ -430,6 +431,44 @@ int jpdse_code_entropy_encode(int32_t dtype, int32_t N, int32_t H, int32_t W, in
  * make the call read outside `in` or write outside `b`. */
 int jpdse_code_entropy_decode(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, const uint8_t* in, int64_t in_stride,
                               const int32_t* sizes, void* b, void* /* hipStream_t */ stream);
+
+/* ---- learned codec: coded label and instance maps (no reference counterpart; format: DESIGN.md 4.9) ---------------------
+ * A lossless, context-adaptive coder for the two integer maps the receiver of the learned codec needs.  Plane 0 (bit 0 of
+ * plane_mask) is the label map, float32 [N][1][H][W] with integer values 0..255; plane 1 (bit 1) the instance map, int64
+ * [N][1][H][W] with values 0..2^31-1 -- the tensors jpdse_input_builder reads.  Every plane of every image is cut into
+ * strips of strip_rows rows (the last may be shorter); a strip is one independent stream: per pixel "equal to the left
+ * one" / "equal to the upper one" in 11 adaptive contexts, else an 8- or 32-bit literal, through the range coder of the
+ * entropy-coded bitstream above.  The payload of one plane of one image is S = ceil(H / strip_rows) little-endian uint32
+ * stream lengths followed by the S streams in strip order.  Bit-exact and deterministic.
+ * A stream's slot is its strip's raw size (1 or 4 bytes per pixel) + 8 bytes; a stream that needs more is cut and flagged,
+ * and the caller stores that plane raw.
+ * Limits: N <= 65535 (a grid dimension), S <= 65535 (compaction reads S lengths per stream: at most 2^32 reads per image),
+ * and a capacity below 2^31 bytes (offsets inside a row are int32); anything else is JPDSE_EINVAL before any launch, as are
+ * a NULL pointer, a non-positive extent or strip_rows, a plane mask outside 1..3, a missing buffer of a plane the mask
+ * names and a row stride that is too small. */
+/* Bytes of one image's row: per present plane 4 S + (H*W*raw + 8 S), label plane first; 0 for a shape outside the limits.
+ * Plane 1's payload starts at jpdse_semantics_capacity(H, W, strip_rows, 1) when both planes are present.  Host only. */
+size_t jpdse_semantics_capacity(int32_t H, int32_t W, int32_t strip_rows, int32_t plane_mask);
+/* Host only; 0 for a shape outside the limits. */
+size_t jpdse_semantics_workspace_size(int32_t N, int32_t H, int32_t W, int32_t strip_rows, int32_t plane_mask);
+/* out: DEVICE uint8 [N][out_stride], out_stride >= jpdse_semantics_capacity(); sizes, status: DEVICE int32 [N][2], indexed
+ * by plane; the entries of an absent plane are not written.  The payload of plane p of image n is the first sizes[n][p]
+ * bytes at its plane offset of row n.  status[n][p] bit 0: a stream was cut (store the plane raw); bit 1: a value was out
+ * of range (a label that is not an integer in [0, 255], an instance value outside [0, 2^31)): the payload is not usable.
+ * label / inst may be NULL when the mask does not name their plane.  ws: jpdse_semantics_workspace_size() bytes. */
+int jpdse_semantics_encode(int32_t N, int32_t H, int32_t W, int32_t strip_rows, int32_t plane_mask, const float* label,
+                           const int64_t* inst, uint8_t* out, int64_t out_stride, int32_t* sizes, int32_t* status, void* ws,
+                           size_t ws_bytes, void* /* hipStream_t */ stream);
+/* in: DEVICE uint8 [N][in_stride]; the label payload of image n starts at byte 0 of row n and, with both planes, the
+ * instance payload at inst_offset (ignored with one plane: that plane starts at 0).  sizes: DEVICE int32 [N][2] by plane;
+ * sizes[n][p] <= 0: plane p of image n is not coded here and its output is left alone (the caller fills it from a raw
+ * plane).  Nothing on the device is trusted: a size is clipped to the plane's part of the row, a table entry outside it
+ * reads as 0, streams are clipped, bytes past a stream's end read as 0 and every strip decodes exactly its pixel count, so
+ * no payload can make the call read outside `in` or write outside label / inst.  bad: DEVICE int32 [N], written by the
+ * call: bit 0 a decoded label >= num_labels (1..256), bit 1 a decoded instance value >= 2^31. */
+int jpdse_semantics_decode(int32_t N, int32_t H, int32_t W, int32_t strip_rows, int32_t plane_mask, int32_t num_labels,
+                           const uint8_t* in, int64_t in_stride, int64_t inst_offset, const int32_t* sizes, float* label,
+                           int64_t* inst, int32_t* bad, void* /* hipStream_t */ stream);
 
 /* ---- evaluation metrics: L1, MSE and MS-SSIM of a reconstruction in one pass (test.py:114-125) --------------------------
  * fake (fp32 or bf16) and real (fp32): NHWC [N][H][W][CPAD(3)] normalised images; both are quantised with q() of

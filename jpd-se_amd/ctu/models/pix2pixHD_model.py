@@ -27,6 +27,7 @@ from jpdse_hip.ops import Act
 from jpdse_hip.optim import FusedAdam
 from jpdse_hip.layers import PackBatcher
 from ctu.utils import bitstream, entropy
+from ctu.utils import semantics as semantics_file
 from ctu.utils.image_pool import ImagePool
 from ctu.models.pix2pixHD_networks.base_model import BaseModel
 from ctu.models.pix2pixHD_networks import networks
@@ -536,6 +537,64 @@ class Pix2PixHDModel(BaseModel):
     coded = sum(8.0 * entropy.file_bytes(len(p), shape) / (H * W) for p in payloads) / len(payloads)
     raw = 8.0 * (bitstream.HEADER_BYTES + bitstream.payload_bytes(shape)) / (H * W)
     return coded, raw
+
+  # ---- coded label and instance maps (extension) --------------------------------------------------------------
+  def _label_set(self):
+    """The label values a decoded map may hold: what the one-hot lanes of the input builder cover, 256 at the most."""
+    return min(self.n_onehot, 256)
+
+  def get_coded_semantics(self, x_dict, strip_rows=8):
+    """The label and instance maps of x_dict as the receiver needs them, coded losslessly on the device
+    (ops.semantics_encode): a list of N `bytes`, each the body of a .jpds file (ctu.utils.semantics).  The maps are coded as
+    the dataset gives them -- --zero_ins / --zero_sem act where decode builds the generator input, not here; with
+    --no_instance there is no instance plane.  ValueError for a label that is not an integer in [0, 255] or an instance id
+    outside [0, 2^31)."""
+    dev = self._device()
+    label = x_dict['label'].to(dev, dtype=torch.float32, non_blocking=True).contiguous()
+    inst = None
+    if not getattr(self.opt, 'no_instance', False):
+      inst = x_dict['instance'].to(dev, dtype=torch.int64, non_blocking=True).contiguous()
+    if label.dim() != 4 or label.shape[1] != 1:
+      raise ValueError('get_coded_semantics: the label map is [N, 1, H, W], got %s' % (tuple(label.shape),))
+    H, W = int(label.shape[-2]), int(label.shape[-1])
+    with torch.no_grad():
+      items = ops.semantics_encode(label, inst, strip_rows)
+    return [semantics_file.pack(H, W, strip_rows, item) for item in items]
+
+  def decode_semantics(self, blobs):
+    """{'label': float32 [N, 1, H, W], 'instance': int64 [N, 1, H, W]} on the device from what get_coded_semantics returned
+    (or ctu.utils.semantics.read read): an x_dict for decode / decode_coded.  Without an instance plane the instance map is
+    zeros.  ValueError, before any device work, for anything ctu.utils.semantics.unpack refuses and for blobs of different
+    shapes; ValueError for a map that holds a label outside the label set, before the input builder sees it."""
+    if not isinstance(blobs, (list, tuple)) or len(blobs) == 0:
+      raise ValueError('decode_semantics: expected a list of .jpds bodies, one per image')
+    parsed = [semantics_file.unpack(b, 'decode_semantics: blob %d' % j) for j, b in enumerate(blobs)]
+    H, W, strip_rows, mask, _ = parsed[0]
+    for j, q in enumerate(parsed):
+      if q[:4] != (H, W, strip_rows, mask):
+        raise ValueError('decode_semantics: blob %d is %d x %d, strips of %d rows, plane mask %d; blob 0 is %d x %d, %d, %d'
+                         % ((j,) + q[:4] + (H, W, strip_rows, mask)))
+    want = 1 if getattr(self.opt, 'no_instance', False) else 3
+    if mask != want:
+      raise ValueError('decode_semantics: the blobs have plane mask %d, this model reads %d (%s)'
+                       % (mask, want, 'label only: --no_instance' if want == 1 else 'label and instance'))
+    with torch.no_grad():
+      label, inst = ops.semantics_decode([q[4] for q in parsed], H, W, strip_rows, self._label_set(), self._device())
+    return {'label': label, 'instance': inst}
+
+  def decode_from_files(self, coded_payloads, semantics_blobs):
+    """The receiver from bytes alone: decode_coded(coded_payloads, decode_semantics(semantics_blobs))."""
+    return self.decode_coded(coded_payloads, self.decode_semantics(semantics_blobs))
+
+  def get_total_rate(self, x_dict, strip_rows=8):
+    """(code bpp, semantics bpp, total bpp), Python floats, batch means: 8 * file bytes / pixels of the .jpda file of the
+    code (get_coded_rate's first figure) and of the .jpds file of the maps, headers and raw fallbacks included -- the rate
+    of everything decode_from_files needs."""
+    code_bpp, _ = self.get_coded_rate(x_dict)
+    blobs = self.get_coded_semantics(x_dict, strip_rows)
+    H, W = int(x_dict['label'].shape[-2]), int(x_dict['label'].shape[-1])
+    sem_bpp = sum(8.0 * len(b) / (H * W) for b in blobs) / len(blobs)
+    return code_bpp, sem_bpp, code_bpp + sem_bpp
 
   def _eval_metrics_of(self, fake, image, label, per_class):
     """The tail get_eval_metrics and get_eval_metrics_decoded share: `fake` (the generator's NHWC output) against the original

@@ -177,6 +177,29 @@ class Pix2PixHDTrainer(BaseTrainer):
     self.eval()
     return self.model.get_coded_rate(x_dict)
 
+  def get_coded_semantics(self, x_dict, strip_rows=8):
+    """The label and instance maps, coded losslessly on the device (extension): a list with the body of one
+    .jpds file (ctu.utils.semantics) per image."""
+    self.eval()
+    return self.model.get_coded_semantics(x_dict, strip_rows)
+
+  def decode_semantics(self, blobs):
+    """{'label', 'instance'} on the device from the blobs get_coded_semantics returned: an x_dict for decode / decode_coded.
+    A malformed blob or a label outside the label set is a ValueError."""
+    self.eval()
+    return self.model.decode_semantics(blobs)
+
+  def decode_from_files(self, coded_payloads, semantics_blobs):
+    """The image from bytes alone: decode_coded(coded_payloads, decode_semantics(semantics_blobs))."""
+    self.eval()
+    return self.model.decode_from_files(coded_payloads, semantics_blobs)
+
+  def get_total_rate(self, x_dict, strip_rows=8):
+    """(code bpp, semantics bpp, total bpp): the sizes of the .jpda and .jpds files of each image, headers included, in bits
+    per pixel, batch means -- the rate of a complete stream."""
+    self.eval()
+    return self.model.get_total_rate(x_dict, strip_rows)
+
   # ---- checkpoints ------------------------------------------------------------------------------
   # File contract of the reference (pix2pixHD_trainer.py:119-176, base_model.py:54-59): <save_dir>/net_G.pth,
   # net_D.pth (state dicts) and stats_and_optim.pt with the keys below.  Optional entries are written / read only when

@@ -153,6 +153,10 @@ SIGNATURES = {
     'jpdse_code_entropy_workspace_size': (_SZ, [_I32, _I32, _I32, _I32]),
     'jpdse_code_entropy_encode': (_I32, [_I32, _I32, _I32, _I32, _I32, _P, _P, _I64, _P, _P, _P, _SZ, _P]),
     'jpdse_code_entropy_decode': (_I32, [_I32, _I32, _I32, _I32, _I32, _P, _I64, ctypes.POINTER(_I32), _P, _P]),
+    'jpdse_semantics_capacity': (_SZ, [_I32, _I32, _I32, _I32]),
+    'jpdse_semantics_workspace_size': (_SZ, [_I32, _I32, _I32, _I32, _I32]),
+    'jpdse_semantics_encode': (_I32, [_I32, _I32, _I32, _I32, _I32, _P, _P, _P, _I64, _P, _P, _P, _SZ, _P]),
+    'jpdse_semantics_decode': (_I32, [_I32, _I32, _I32, _I32, _I32, _I32, _P, _I64, _I64, _P, _P, _P, _P, _P]),
     'jpdse_eval_metrics_workspace_size': (_SZ, [_I32, _I32, _I32, _I32]),
     'jpdse_eval_metrics': (_I32, [_I32, _I32, _I32, _I32, _I32, _I32, _P, _P, ctypes.POINTER(ctypes.c_double),
                                   ctypes.POINTER(ctypes.c_double), _P, _P, _SZ, _P]),

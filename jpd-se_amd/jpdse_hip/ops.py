@@ -624,6 +624,169 @@ def code_entropy_decode(payloads, N, H, W, C, dtype_code, device=None):
   return b
 
 
+# ---- learned codec: coded label and instance maps (semantics.hip; format: DESIGN.md 4.9) -----------------------------------
+SEM_RAW, SEM_CODED = 0, 1
+SEM_RAW_BYTES = (1, 4)                      # label plane: uint8, instance plane: little-endian int32
+_SEM_RAW_DTYPE = (torch.uint8, torch.int32)
+_SEM_NAMES = ('label', 'instance')
+
+
+def semantics_strips(H, strip_rows):
+  return (H + strip_rows - 1) // strip_rows
+
+
+def _sem_maps(label, inst, who):
+  if not torch.is_tensor(label) or label.dtype != torch.float32 or label.dim() != 4 or label.shape[1] != 1:
+    raise ValueError('%s: the label map is a float32 [N, 1, H, W] tensor' % who)
+  if inst is not None and (not torch.is_tensor(inst) or inst.dtype != torch.int64 or tuple(inst.shape) != tuple(label.shape)):
+    raise ValueError('%s: the instance map is an int64 tensor of the label map\'s shape %s' % (who, tuple(label.shape)))
+  if not label.is_contiguous() or (inst is not None and not inst.is_contiguous()):
+    raise ValueError('%s: the maps must be contiguous' % who)
+  return int(label.shape[0]), int(label.shape[2]), int(label.shape[3])
+
+
+def semantics_encode(label, inst, strip_rows=8):
+  """The coded planes of every image (jpdse_semantics_encode).  label: device float32 [N, 1, H, W] with integer values in
+  [0, 255]; inst: device int64 [N, 1, H, W] with values in [0, 2^31), or None for no instance plane -- the tensors the input
+  builder reads.  Returns a list of N items [label entry, instance entry]; an entry is (mode, payload) and None for the
+  absent instance plane.  mode 1: payload = the plane's S uint32 stream lengths and its S streams; mode 0: the raw plane
+  (uint8, or little-endian int32), taken where a stream outgrew its slot (status bit 0) or coding did not make the plane
+  smaller.  ValueError, naming the image, for a value out of range (status bit 1).  The sizes and status words are copied
+  to the host first, then each payload by itself: the rows of the device buffer are capacity-sized, the payloads are not."""
+  N, H, W = _sem_maps(label, inst, 'semantics_encode')
+  strip_rows = int(strip_rows)
+  if strip_rows < 1:
+    raise ValueError('semantics_encode: strip_rows %d is below 1' % strip_rows)
+  L = lib()
+  mask = 1 | (2 if inst is not None else 0)
+  cap = L.jpdse_semantics_capacity(H, W, strip_rows, mask)
+  n_ws = L.jpdse_semantics_workspace_size(N, H, W, strip_rows, mask)
+  if cap == 0 or n_ws == 0:
+    raise ValueError('semantics_encode: %d maps of %d x %d in strips of %d rows are beyond the coder\'s limits' % (N, H, W, strip_rows))
+  dev = label.device
+  offs = (0, L.jpdse_semantics_capacity(H, W, strip_rows, 1))
+  head = (16 * N + 15) // 16 * 16
+  buf = torch.empty(head + N * cap, dtype=torch.uint8, device=dev)
+  meta = buf[:16 * N].view(torch.int32)
+  meta.zero_()
+  ws = workspace(n_ws, dev)
+  check(L.jpdse_semantics_encode(N, H, W, strip_rows, mask, _p(label), _p(inst), _p(buf[head:]), cap, _p(meta[:2 * N]),
+                                 _p(meta[2 * N:]), _p(ws), ws.numel(), _stream()), 'semantics_encode')
+  # the rows are capacity-sized (raw + 12 S bytes per plane): the sizes and status words go to the host first, then only
+  # the payloads themselves
+  host = meta.cpu().numpy()
+  sizes, status = host[:2 * N].reshape(N, 2), host[2 * N:].reshape(N, 2)
+  planes = [(0, label)] + ([(1, inst)] if inst is not None else [])
+  for n in range(N):
+    for p, _ in planes:
+      if status[n, p] & 2:
+        raise ValueError('semantics_encode: the %s map of image %d holds a value outside the plane\'s range (%s)'
+                         % (_SEM_NAMES[p], n, 'integers in [0, 255]' if p == 0 else '[0, 2^31)'))
+  out = []
+  for n in range(N):
+    item = [None, None]
+    for p, t in planes:
+      raw = H * W * SEM_RAW_BYTES[p]
+      size = int(sizes[n, p])
+      if (status[n, p] & 1) or size >= raw:
+        item[p] = (SEM_RAW, t[n, 0].to(_SEM_RAW_DTYPE[p]).cpu().numpy().astype('u1' if p == 0 else '<i4').tobytes())
+      else:
+        at = head + n * cap + offs[p]
+        item[p] = (SEM_CODED, buf[at:at + size].cpu().numpy().tobytes())
+    out.append(item)
+  return out
+
+
+def semantics_check_entry(entry, plane, H, W, strip_rows, who):
+  """ValueError unless `entry` is (mode, bytes) holding a raw plane of the right size or a coded payload whose table of
+  S = ceil(H / strip_rows) lengths adds up to the bytes after it.  Host only."""
+  if not isinstance(entry, (tuple, list)) or len(entry) != 2 or not isinstance(entry[1], (bytes, bytearray)):
+    raise ValueError('%s: an entry is (mode, bytes)' % who)
+  mode, payload = entry
+  if mode not in (SEM_RAW, SEM_CODED):
+    raise ValueError('%s: unknown mode %r (0 = raw, 1 = coded)' % (who, mode))
+  S = semantics_strips(H, strip_rows)
+  if mode == SEM_RAW:
+    if len(payload) != H * W * SEM_RAW_BYTES[plane]:
+      raise ValueError('%s: a raw plane (%s) of %d x %d is %d bytes, got %d'
+                       % (who, _SEM_NAMES[plane], H, W, H * W * SEM_RAW_BYTES[plane], len(payload)))
+    return
+  if len(payload) < 4 * S:
+    raise ValueError('%s: truncated, %d bytes are shorter than the table of %d stream lengths' % (who, len(payload), S))
+  total = sum(struct.unpack_from('<%dI' % S, payload))
+  if total != len(payload) - 4 * S:
+    raise ValueError('%s: the length table sums to %d, but %d bytes follow it' % (who, total, len(payload) - 4 * S))
+
+
+def semantics_decode(items, H, W, strip_rows, num_labels, device=None):
+  """The inverse (jpdse_semantics_decode): N items as semantics_encode returns them -> (label float32 [N, 1, H, W],
+  instance int64 [N, 1, H, W]) on the device, the form the input builder reads; without an instance plane the instance map
+  is zeros.  ValueError before any library call for anything that is not such a list (all items with the same planes), a raw
+  plane of the wrong size and a length table that does not add up; ValueError after the decode for a label >= num_labels
+  or an instance value >= 2^31, naming the image."""
+  who = 'semantics_decode'
+  if not isinstance(items, (list, tuple)) or len(items) == 0:
+    raise ValueError('%s: expected a list of per-image [label entry, instance entry] items' % who)
+  N = len(items)
+  H, W, strip_rows, num_labels = int(H), int(W), int(strip_rows), int(num_labels)
+  if min(H, W, strip_rows) < 1 or not 1 <= num_labels <= 256:
+    raise ValueError('%s: bad shape %d x %d, strip_rows %d or num_labels %d' % (who, H, W, strip_rows, num_labels))
+  mask = None
+  for n, item in enumerate(items):
+    if not isinstance(item, (list, tuple)) or len(item) != 2 or item[0] is None:
+      raise ValueError('%s: item %d is not [label entry, instance entry or None]' % (who, n))
+    m = 1 | (2 if item[1] is not None else 0)
+    if mask is not None and m != mask:
+      raise ValueError('%s: item %d has other planes than item 0' % (who, n))
+    mask = m
+    for p in range(2):
+      if item[p] is not None:
+        semantics_check_entry(item[p], p, H, W, strip_rows, '%s: %s plane of image %d' % (who, _SEM_NAMES[p], n))
+  # raw planes are checked on the host, before any device work
+  raws = {}
+  for n, item in enumerate(items):
+    for p in range(2):
+      if item[p] is not None and item[p][0] == SEM_RAW:
+        a = torch.frombuffer(bytearray(item[p][1]), dtype=_SEM_RAW_DTYPE[p]).view(H, W)
+        if p == 0 and int(a.max()) >= num_labels:
+          raise ValueError('%s: the label map of image %d holds label %d, the label set has %d' % (who, n, int(a.max()), num_labels))
+        if p == 1 and int(a.min()) < 0:
+          raise ValueError('%s: the instance map of image %d holds a negative value' % (who, n))
+        raws[(n, p)] = a
+  dev = device if device is not None else torch.device('cuda', torch.cuda.current_device())
+  S = semantics_strips(H, strip_rows)
+  longest = [max([len(it[p][1]) for it in items if it[p] is not None and it[p][0] == SEM_CODED] + [4 * S]) for p in range(2)]
+  inst_off = longest[0] if mask == 3 else 0
+  stride = inst_off + (longest[1] if mask & 2 else 0) if mask == 3 else longest[0]
+  label = torch.empty((N, 1, H, W), dtype=torch.float32, device=dev)
+  inst = torch.empty((N, 1, H, W), dtype=torch.int64, device=dev) if mask & 2 else torch.zeros((N, 1, H, W), dtype=torch.int64, device=dev)
+  if len(raws) < N * (2 if mask == 3 else 1):
+    if stride >= 1 << 31:
+      raise ValueError('%s: payloads of %d bytes' % (who, stride))
+    head = (8 * N + 15) // 16 * 16
+    host = torch.zeros(head + N * stride, dtype=torch.uint8)
+    sizes = host[:8 * N].view(torch.int32).view(N, 2)
+    for n, item in enumerate(items):
+      for p in range(2):
+        if item[p] is not None and item[p][0] == SEM_CODED:
+          at = head + n * stride + (inst_off if p else 0)
+          host[at:at + len(item[p][1])] = torch.frombuffer(bytearray(item[p][1]), dtype=torch.uint8)
+          sizes[n, p] = len(item[p][1])
+    buf = host.to(dev)
+    bad = torch.empty(N, dtype=torch.int32, device=dev)
+    check(lib().jpdse_semantics_decode(N, H, W, strip_rows, mask, num_labels, _p(buf[head:]), stride, inst_off, _p(buf),
+                                       _p(label), _p(inst) if mask & 2 else ctypes.c_void_p(0), _p(bad), _stream()), who)
+    flags = bad.cpu().tolist()
+    for n, f in enumerate(flags):
+      if f & 1:
+        raise ValueError('%s: the label map of image %d decodes to a label outside the set of %d' % (who, n, num_labels))
+      if f & 2:
+        raise ValueError('%s: the instance map of image %d decodes to a value of 2^31 or more' % (who, n))
+  for (n, p), a in raws.items():
+    (inst if p else label)[n, 0].copy_(a.to(dev))
+  return label, inst
+
+
 # ---- evaluation metrics (metrics.hip) ------------------------------------------------------------
 MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
 

@@ -22,7 +22,13 @@ beside get_eval_rate's Shannon estimate.  With --roundtrip the files written and
 
   python scripts/eval_rd.py [--batches 4] [--batch 2] [--width 1024] [--height 512] [--dtype bf16] [--codec]
                             [--checkpoints_dir DIR] [--data DIR] [--per-class] [--zero_sem] [--zero_ins] [--zero_vis]
-                            [--roundtrip DIR] [--entropy]
+                            [--roundtrip DIR] [--entropy] [--semantics]
+
+--semantics (needs --codec --entropy --roundtrip DIR) completes the stream: every image's label and instance maps are coded
+(trainer.get_coded_semantics) and written as a .jpds file beside the .jpda one, the receiver's maps come from
+those files alone (trainer.decode_semantics), the decoded image is checked against get_img under the zero rule above, and
+the line gains the three rates trainer.get_total_rate reports (code, semantics and total bpp, headers included), taken from
+the sizes of the files just written.
 """
 import argparse
 import contextlib
@@ -82,6 +88,20 @@ def roundtrip(trainer, x_dict, folder, batch_index, coded=False):
   return torch.stack(rows), bpp
 
 
+def semantics_roundtrip(trainer, x_dict, folder, batch_index):
+  """Code the maps of x_dict, store one .jpds file per image, read the files back: (the receiver's {'label', 'instance'},
+  file bpp per image)."""
+  from ctu.utils import semantics
+  blobs = trainer.get_coded_semantics(x_dict)
+  pixels = int(x_dict['label'].shape[-2]) * int(x_dict['label'].shape[-1])
+  back, bpp = [], []
+  for j, blob in enumerate(blobs):
+    path = os.path.join(folder, 'b%04d_i%02d%s' % (batch_index, j, semantics.SUFFIX))
+    bpp.append(8.0 * semantics.write(path, blob) / pixels)
+    back.append(semantics.read(path))
+  return trainer.decode_semantics(back), bpp
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--batches', type=int, default=4)
@@ -100,11 +120,15 @@ def main():
                   help='with --codec: store every code under DIR, decode from the files, report the decoded images')
   ap.add_argument('--entropy', action='store_true',
                   help='with --codec: also report the bpp of the entropy-coded files; --roundtrip then stores and decodes those')
+  ap.add_argument('--semantics', action='store_true',
+                  help='with --codec --entropy --roundtrip: also store the label / instance maps as .jpds files and decode from files only')
   args = ap.parse_args()
   if args.roundtrip and not args.codec:
     ap.error('--roundtrip needs --codec')
   if args.entropy and not args.codec:
     ap.error('--entropy needs --codec')
+  if args.semantics and not (args.codec and args.entropy and args.roundtrip):
+    ap.error('--semantics needs --codec --entropy --roundtrip DIR')
   if args.roundtrip:
     os.makedirs(args.roundtrip, exist_ok=True)
   import jpdse_hip
@@ -124,8 +148,8 @@ def main():
   with contextlib.redirect_stdout(sys.stderr):
     trainer = get_trainer(opt)(opt, 'test' if args.checkpoints_dir else 'train')
   keys = ('l1', 'mse', 'ms_ssim', 'psnr')
-  by_batch = dict.fromkeys(keys + ('shannon', 'actual', 'file', 'coded'), 0.0)
-  by_image = dict.fromkeys(keys + ('shannon', 'actual', 'file', 'coded'), 0.0)
+  by_batch = dict.fromkeys(keys + ('shannon', 'actual', 'file', 'coded', 'semantics', 'total'), 0.0)
+  by_image = dict.fromkeys(keys + ('shannon', 'actual', 'file', 'coded', 'semantics', 'total'), 0.0)
   images, n_batches, worst_diff = 0, 0, 0.0
   class_sums = None                  # int64 [1, n_classes + 1, 3]: the raw class tables of every image so far, added up
   start = time.time()
@@ -133,6 +157,8 @@ def main():
     if args.roundtrip:
       code, file_bpp = roundtrip(trainer, x_dict, args.roundtrip, i, coded=args.entropy)
       receiver = dict(label=x_dict['label'], instance=x_dict['instance'])      # all the receiver has besides the files
+      if args.semantics:
+        receiver, sem_file_bpp = semantics_roundtrip(trainer, x_dict, args.roundtrip, i)     # ... unless the maps come from files too
       decoded = trainer.decode(code, receiver)
       diff = float((decoded - trainer.get_img(x_dict)).abs().max())
       worst_diff = max(worst_diff, diff)
@@ -158,6 +184,15 @@ def main():
       by_batch['coded'] += coded_bpp
       by_image['coded'] += coded_bpp * b
       line += ', coded file bpp {:.4f} (raw file {:.4f})'.format(coded_bpp, raw_file_bpp)
+    if args.semantics:
+      # trainer.get_total_rate's three figures, from the .jpda rate and the .jpds files already in hand
+      code_bpp, sem_bpp = coded_bpp, sum(sem_file_bpp) / len(sem_file_bpp)
+      total_bpp = code_bpp + sem_bpp
+      by_batch['semantics'] += sem_bpp
+      by_image['semantics'] += sem_bpp * b
+      by_batch['total'] += total_bpp
+      by_image['total'] += total_bpp * b
+      line += ', code/semantics/total file bpp {:.4f}/{:.4f}/{:.4f}'.format(code_bpp, sem_bpp, total_bpp)
     if args.roundtrip:
       by_batch['file'] += sum(file_bpp) / len(file_bpp)
       by_image['file'] += sum(file_bpp)
@@ -179,6 +214,8 @@ def main():
       line += ', avg pre-/(estimated) post-entropy coding bpp {:.4f}/{:.4f}'.format(t['actual'] / n, t['shannon'] / n)
     if args.entropy:
       line += ', avg coded file bpp {:.4f}'.format(t['coded'] / n)
+    if args.semantics:
+      line += ', avg semantics/total file bpp {:.4f}/{:.4f}'.format(t['semantics'] / n, t['total'] / n)
     if args.roundtrip:
       line += ', avg file bpp {:.4f}'.format(t['file'] / n)
     return line
