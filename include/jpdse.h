@@ -39,8 +39,9 @@ extern "C" {
                                 * per-class form (jpdse_eval_metrics_sem[_workspace_size]), and the receiver side of the codec
                                 * (jpdse_code_import), and the MS-SSIM training loss (jpdse_msssim_loss[_workspace_size]), and the input
                                 * builder for more than 64 storage channels (jpdse_input_builder_wide), and the entropy-coded bitstream
-                                * (jpdse_code_entropy_*), and the coded label and instance maps (jpdse_semantics_*): purely
-                                * additive, nothing existing changed */
+                                * (jpdse_code_entropy_*), and the coded label and instance maps (jpdse_semantics_*), and the
+                                * context-model rate term (jpdse_code_rate_loss[_workspace_size]): purely additive, nothing
+                                * existing changed */
 
 enum { JPDSE_F32 = 0, JPDSE_BF16 = 1 };
 enum { JPDSE_PAD_ZERO = 0, JPDSE_PAD_REFLECT = 1 };
@@ -542,6 +543,41 @@ typedef struct jpdse_msssim_loss_args {
   void* stream;
 } jpdse_msssim_loss_args;
 int jpdse_msssim_loss(const jpdse_msssim_loss_args* args);
+
+/* ---- learned codec: context-model rate term, --lambda_rate (no reference counterpart) ---------------------
+ * The expected length of the code under a static form of the entropy-coded bitstream's context model, and its gradient
+ * w.r.t. the binarizer's tanh output.  b, t, grad: NHWC [N][H][W][CPAD(C)] in `dtype`.  One stream per (image n, channel c);
+ * bit = b > 0 (an exact 0 of the eval binarizer is bit 0); ctx = left | up << 1 | upleft << 2 | upright << 3 over the bits
+ * of the same stream, a neighbour outside the frame counting as 0 -- the rule of jpdse_code_entropy_encode.
+ *   n0 / n1 [n][c][k] = positions of the stream with ctx == k and bit 0 / 1                            (int32)
+ *   p1 = (n1 + 1) / (n0 + n1 + 2),  cost1 = -log2(p1),  cost0 = -log2(1 - p1)                          (per stream and ctx)
+ *   e = (1 + t) / 2 * cost1[ctx] + (1 - t) / 2 * cost0[ctx]                                            (per element)
+ *   per_image[n] = sum_{c,y,x} e / pixels,   out[0] = sum_n per_image[n] / N                           (bits per image pixel)
+ *   grad = scale * (cost1[ctx] - cost0[ctx]) / (2 * N * pixels)       (ctx and the costs are constants: stop-gradient)
+ * t == NULL ("hard mode"): t := +1 where b > 0 and -1 elsewhere, so out[0] is the static conditional-entropy estimate of the
+ * code.  The arithmetic is fp32 (the sums over partials fp64); grad is rounded once on its store, its padding lanes are
+ * written as 0.  The counts are integer atomics and every floating-point sum has a fixed order: two calls on the same
+ * buffers give bit-identical out, per_image, grad and counts.
+ * Limits: N <= 65535, C <= 64 * 65535 and H * W <= 2^30 (a count fits an int32).  A NULL args, b or out, a bad dtype, a
+ * non-positive extent or `pixels`, a NaN scale with grad, a shape beyond the limits and a workspace that is missing or too
+ * small are all JPDSE_EINVAL before any launch.  ws: jpdse_code_rate_workspace_size() bytes (0 for a shape outside the
+ * limits; host only). */
+size_t jpdse_code_rate_workspace_size(int32_t N, int32_t H, int32_t W, int32_t C);
+typedef struct jpdse_code_rate_args {
+  int32_t dtype, N, H, W, C;
+  int64_t pixels;      /* the image's H*W behind "per pixel" (not the code's) */
+  const void* b;       /* the code as the binarizer wrote it */
+  const void* t;       /* the tanh output, or NULL: hard mode */
+  void* grad;          /* scale * d out[0] / d t in `dtype`, or NULL: value only */
+  float scale;         /* read when grad != NULL */
+  float* out;          /* device fp32 slot: R, unscaled */
+  float* per_image;    /* device fp32 [N], or NULL */
+  int32_t* counts;     /* device int32 [N][C][16][2], (n0, n1) per context, or NULL */
+  void* ws;
+  size_t ws_bytes;
+  void* stream;
+} jpdse_code_rate_args;
+int jpdse_code_rate_loss(const jpdse_code_rate_args* args);
 
 /* ---- optimizer ---------------------------------------------------------------------- */
 /* torch.optim.Adam (model.py:275,279) over a table of tensors, one launch.  `table` is a

@@ -43,7 +43,7 @@ class Pix2PixHDModel(BaseModel):
     (pinned by tests/golden/option_setter_flags.json, dumped from the reference), so that a reference command line or
     opt.pkl parses unchanged; flags of branches outside the accelerated path are accepted here and refused in
     __init__ when they would change the computation.  Extensions: --compute_dtype, --skip_unused_losses,
-    --vgg19_state_dict, --vgg_random_init."""
+    --vgg19_state_dict, --vgg_random_init, --lambda_rate."""
     a = parser.add_argument
     a('--num_D', type=int, default=2)
     a('--n_layers_D', type=int, default=3)
@@ -119,6 +119,10 @@ class Pix2PixHDModel(BaseModel):
       help='extension (data parallelism): where the generator gradient all-reduce runs -- behind the discriminator backward '
            '(default; keeps RCCL off the chip while the one-workgroup-per-CU ResnetBlock GEMMs run) or layer by layer from '
            'the backward hooks')
+    a('--lambda_rate', type=float, default=0.0,
+      help='extension (DESIGN.md 4.10): weight of the rate term in the generator / encoder loss -- the expected length of the '
+           'code under a static form of the entropy coder\'s context model, in bits per pixel; needs the learned codec with '
+           'encoder binarization; 0 (default): no rate term, the step is what it was')
     a('--vgg_random_init', action='store_true',
       help='extension: explicitly accept a seeded random-weight VGG19 for the VGG loss (tests, benchmarks); without '
            'this flag training with the VGG loss and no --vgg19_state_dict is refused')
@@ -155,6 +159,12 @@ class Pix2PixHDModel(BaseModel):
       raise NotImplementedError('outside the accelerated JPD-SE path (SURVEY.md §2): ' + '; '.join(unsupported))
     if opt.distortion_loss_fn not in ('l1', 'mse', 'ms_ssim'):      # before any network (hence any device allocation) exists
       raise ValueError('distortion_loss_fn must be l1, mse or ms_ssim')
+    self.lambda_rate = float(g('lambda_rate', 0.0) or 0.0)
+    if not self.lambda_rate >= 0.0:
+      raise ValueError('lambda_rate must be a non-negative number, got %r' % (g('lambda_rate'),))
+    if self.lambda_rate > 0.0 and (not feat_enc or g('no_encoder_binarization') or g('zero_vis')):
+      raise ValueError('lambda_rate > 0 needs the learned codec with encoder binarization (--no_feat_encoding and '
+                       '--no_encoder_binarization must both be off) and an encoder that runs (no --zero_vis)')
     self.opt = opt
     self.is_train = opt.is_train
     self.use_features = True
@@ -398,6 +408,16 @@ class Pix2PixHDModel(BaseModel):
     (extension), the bitstream itself, uint8 [N, ceil(bits / 8)] MSB first."""
     with torch.no_grad():
       return [ops.code_export(self._code_act(x_dict), packed)]
+
+  def get_context_rate(self, x_dict):
+    """The hard-mode rate term of the eval-mode code, batch mean in bits per pixel, a Python float: the code's
+    conditional entropy under the static, Laplace-smoothed form of the 4.8 coder's context model, counted on the code itself.
+    An estimate that stays below the coded size (no flush, no adaptation cost) -- not a size; get_coded_rate measures files."""
+    with torch.no_grad():
+      b = self._code_act(x_dict)
+      pixels = int(x_dict['image'].shape[-2]) * int(x_dict['image'].shape[-1])
+      value, _, _, _ = ops.code_rate_loss(b, None, pixels, want_grad=False)
+      return float(value.item())
 
   def get_eval_rate(self, x_dict):
     """(Shannon bpp, raw bpp) averaged over the batch, with the reference's formula and types (model.py:468-491): per image
@@ -655,7 +675,17 @@ class Pix2PixHDModel(BaseModel):
       vis = src
       if self.netE is not None and src is not None:
         self._set_codec_rng(B)
-        vis, e_ctx = self.netE.fwd(src)
+        # --lambda_rate: a training step's forward also asks the binarizer for the rate term and its gradient
+        # w.r.t. tanh's output, scaled like the distortion gradient: the weight, the kernel's mean over the local batch, and
+        # the ranks' average in Adam's grad_scale
+        rate_bin = self.netE._binarizer if (self.lambda_rate > 0.0 and grad_w is not None) else None
+        if rate_bin is not None:
+          rate_bin.rate_scale, rate_bin.rate_pixels = self.lambda_rate, H * W
+        try:
+          vis, e_ctx = self.netE.fwd(src)
+        finally:
+          if rate_bin is not None:
+            rate_bin.rate_scale = None
         if self.netE.training:
           self.codec_draw += 1
       if self.zero_sem:
@@ -710,7 +740,14 @@ class Pix2PixHDModel(BaseModel):
     layout['vgg'] = list(range(o, o + n_vgg))
     o += n_vgg
     layout['dist'] = o
-    slots = torch.zeros(o + 1, dtype=torch.float32, device=dev)
+    rate_value = None
+    if self.lambda_rate > 0.0 and grad_w is not None and e_ctx is not None:
+      rate_value = self.netE._binarizer.rate_value
+    if rate_value is not None:
+      layout['rate'] = o + 1
+    slots = torch.zeros(o + (1 if rate_value is None else 2), dtype=torch.float32, device=dev)
+    if rate_value is not None:
+      slots[o + 1:o + 2].copy_(rate_value)          # G_Rate, unscaled: read back with the six losses
     s = lambda i: slots[i:i + 1]
     gw = grad_w or {}
     d_feat, d_vgg, d_dist = None, None, None
@@ -753,13 +790,16 @@ class Pix2PixHDModel(BaseModel):
     """Host arithmetic on the slot values -> the reference's six loss scalars."""
     nD = self.opt.num_D
     w = networks.VGGLoss.weights
-    return dict(
+    L = dict(
         G_GAN=sum(vals[i] for i in layout['G_GAN']),
         G_GAN_Feat=sum((1.0 / nD) * vals[i] for row in layout['feat'] for i in row),
         G_VGG=sum(w[k] * vals[i] for k, i in enumerate(layout['vgg'])),
         G_Distortion=vals[layout['dist']],
         D_real=sum(vals[i] for i in layout['D_real']),
         D_fake=sum(vals[i] for i in layout['D_fake']))
+    if 'rate' in layout:             # --lambda_rate: the unscaled rate term in bits per pixel, after the six losses
+      L['G_Rate'] = vals[layout['rate']]
+    return L
 
   def get_train_loss(self, x_dict):
     """The six losses as 0-dim device tensors in `loss_names` order (values only: the HIP path

@@ -111,7 +111,8 @@ class Pix2PixHDTrainer(BaseTrainer):
     if self.print_losses:
       print('g_gan: {:.4f}, g_gan_feat_match: {:.4f}, g_vgg: {:.4f}, g_distortion ({}): {:.4f}, d_real: {:.4f}, '
             'd_fake: {:.4f}'.format(L['G_GAN'], L['G_GAN_Feat'], L['G_VGG'], self.opt.distortion_loss_fn,
-                                    L['G_Distortion'], L['D_real'], L['D_fake']))
+                                    L['G_Distortion'], L['D_real'], L['D_fake'])
+            + (', g_rate: {:.4f}'.format(L['G_Rate']) if 'G_Rate' in L else ''))
     self.steps_taken += 1
     if self.opt.anneal_lambda and not (self.steps_taken % self.opt.anneal_interval):
       self.lambda_distortion_weight *= self.opt.anneal_factor
@@ -176,6 +177,12 @@ class Pix2PixHDTrainer(BaseTrainer):
     included, in bits per pixel.  What a coder produced -- next to get_eval_rate's Shannon estimate, which stays as it is."""
     self.eval()
     return self.model.get_coded_rate(x_dict)
+
+  def get_context_rate(self, x_dict):
+    """The context-model estimate of the code's length in bits per pixel (extension), a Python float, batch
+    mean: the hard-mode rate term of --lambda_rate on the eval-mode code.  Stays below get_coded_rate's coded figure."""
+    self.eval()
+    return self.model.get_context_rate(x_dict)
 
   def get_coded_semantics(self, x_dict, strip_rows=8):
     """The label and instance maps, coded losslessly on the device (extension): a list with the body of one

@@ -65,6 +65,13 @@ class MsssimLossArgs(ctypes.Structure):
               ('stream', ctypes.c_void_p)]
 
 
+class CodeRateArgs(ctypes.Structure):
+  _fields_ = [(n, ctypes.c_int32) for n in ('dtype', 'N', 'H', 'W', 'C')] + \
+             [('pixels', ctypes.c_int64), ('b', ctypes.c_void_p), ('t', ctypes.c_void_p), ('grad', ctypes.c_void_p),
+              ('scale', ctypes.c_float), ('out', ctypes.c_void_p), ('per_image', ctypes.c_void_p), ('counts', ctypes.c_void_p),
+              ('ws', ctypes.c_void_p), ('ws_bytes', ctypes.c_size_t), ('stream', ctypes.c_void_p)]
+
+
 _P, _I32, _I64, _F, _SZ = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float,
                            ctypes.c_size_t)
 _CD, _ND = ctypes.POINTER(ConvDesc), ctypes.POINTER(InormDesc)
@@ -164,6 +171,8 @@ SIGNATURES = {
     'jpdse_eval_metrics_sem': (_I32, [ctypes.POINTER(EvalMetricsSemArgs)]),
     'jpdse_msssim_loss_workspace_size': (_SZ, [_I32, _I32, _I32, _I32, _I32]),
     'jpdse_msssim_loss': (_I32, [ctypes.POINTER(MsssimLossArgs)]),
+    'jpdse_code_rate_workspace_size': (_SZ, [_I32, _I32, _I32, _I32]),
+    'jpdse_code_rate_loss': (_I32, [ctypes.POINTER(CodeRateArgs)]),
 }
 
 # the developer build (same sources, -DJPDSE_DEV): the shipped ABI plus include/jpdse_dev.h

@@ -323,16 +323,26 @@ class HipBinarizer(nn.Module):
     self.conv = HipConv2d(cin, cout, 1, act=ACT_TANH, apply_bias=False, bias=False, dtype=dtype, device=device)
     self.seed, self.draw, self.n_global0 = 0, 0, 0
     self.noise_override = None
+    self.rate_scale, self.rate_pixels, self.rate_value = None, 0, None
 
   def fwd(self, x):
     t, ctx = self.conv.fwd(x)                     # ctx = (x, t): the tanh backward reads the stored t
     u, self.noise_override = self.noise_override, None
     b = ops.binarize_fwd(t, self.training, self.seed, self.draw, self.n_global0, u)
+    if self.rate_scale is not None:
+      # --lambda_rate: the owner set rate_scale / rate_pixels for this call; the value slot stays in
+      # rate_value and the gradient w.r.t. t travels with the context
+      self.rate_value, _, d_rate, _ = ops.code_rate_loss(b, t, self.rate_pixels, self.rate_scale)
+      ctx = Ctx(ctx, d_rate)
     return b, ctx
 
   def bwd(self, ctx, db, need_dx=True, need_dw=True):
     """Straight-through estimator (binarize.py:26-28): db is the gradient w.r.t. tanh's output; conv.bwd applies
-    tanh' = 1 - t^2 and runs the 1x1 conv's data / weight gradients."""
+    tanh' = 1 - t^2 and runs the 1x1 conv's data / weight gradients.  A context of a forward with a rate scale also holds
+    the rate term's gradient w.r.t. t, which is added to db first."""
+    if len(ctx.items) == 2 and isinstance(ctx.items[0], Ctx):
+      ctx, d_rate = ctx.items
+      db = ops.add(db, d_rate)
     return self.conv.bwd(ctx, db, need_dx, need_dw)
 
 

@@ -9,7 +9,7 @@ import struct
 
 import torch
 
-from . import (lib, check, JpdseError, F32, BF16, ConvDesc, InormDesc, EvalMetricsSemArgs, MsssimLossArgs, ACT_NONE, PAD_ZERO, PAD_REFLECT)
+from . import (lib, check, JpdseError, F32, BF16, ConvDesc, InormDesc, EvalMetricsSemArgs, MsssimLossArgs, CodeRateArgs, ACT_NONE, PAD_ZERO, PAD_REFLECT)
 
 
 def cpad(c):
@@ -924,3 +924,31 @@ def msssim_loss_fwd(fake, real, mean, std, out, stats=None):
 def msssim_loss_fwd_bwd(fake, real, mean, std, out, scale, stats=None):
   """msssim_loss_fwd and, from the same call, the Act scale * d out / d fake (fake's dtype and layout)."""
   return _msssim_loss(fake, real, mean, std, out, scale, stats)
+
+
+# ---- learned codec: context-model rate term (code_rate.hip; definition: DESIGN.md 4.10) ----------------------------------
+def code_rate_loss(b, t, pixels, scale=1.0, want_grad=True, want_counts=False, out=None):
+  """The expected length R of the code `b` under the static context model of DESIGN.md 4.10, in bits per image pixel
+  (`pixels` = the image's H*W), from one call (jpdse_code_rate_loss).  t: the Act of the tanh output behind b, or None for
+  the hard mode (t := +1 where b > 0, -1 elsewhere: the conditional-entropy estimate of the code).  Returns
+  (value, per_image, grad, counts): the fp32 device slot [1] holding R (unscaled; `out` when given), the fp32 per-image
+  values [N], the Act scale * dR/dt in b's dtype (None unless want_grad; padding lanes 0) and the int32 counts
+  [N, C, 16, 2] = (n0, n1) per stream and context (None unless want_counts)."""
+  L = lib()
+  dev = b.t.device
+  if t is not None:
+    assert t.t.shape == b.t.shape and t.C == b.C and t.dtype == b.dtype and t.t.device == dev
+  if out is None:
+    out = torch.empty(1, dtype=torch.float32, device=dev)
+  assert out.dtype == torch.float32 and out.numel() >= 1 and out.device == dev
+  per_image = torch.empty(b.N, dtype=torch.float32, device=dev)
+  grad = b.empty_like() if want_grad else None
+  counts = torch.empty((b.N, b.C, 16, 2), dtype=torch.int32, device=dev) if want_counts else None
+  n = L.jpdse_code_rate_workspace_size(b.N, b.H, b.W, b.C)
+  ws = workspace(max(n, 1), dev)
+  args = CodeRateArgs(b.dtype, b.N, b.H, b.W, b.C, int(pixels), b.t.data_ptr(), t.t.data_ptr() if t is not None else None,
+                      grad.t.data_ptr() if want_grad else None, float(scale), out.data_ptr(), per_image.data_ptr(),
+                      counts.data_ptr() if want_counts else None, ws.data_ptr(), ws.numel(),
+                      torch.cuda.current_stream().cuda_stream)
+  check(L.jpdse_code_rate_loss(ctypes.byref(args)), 'code_rate_loss')    # a shape beyond the limits is refused here
+  return out, per_image, grad, counts

@@ -1,6 +1,7 @@
 """Rate-distortion evaluation loop on the device path: the numbers of the reference's test.py (its per-batch and test-set lines:
 L1 / MSE / MS-SSIM, bpp before / after entropy coding when the learned codec is on) plus PSNR, without the visualiser and the
-HTML page.  Per batch: trainer.get_eval_metrics (one generator forward) and, with the codec, trainer.get_eval_rate.
+HTML page.  Per batch: trainer.get_eval_metrics (one generator forward) and, with the codec, trainer.get_eval_rate and
+trainer.get_context_rate (the context model's estimate of the code's length in bits per pixel).
 
 Batches: seeded synthetic ones (ctu.utils.synthetic), or --data DIR holding pre-decoded batches as *.pt files, each a dict with
 the x_dict keys (label, instance, image, optionally compressed_img, path).  The test-set line averages the per-batch values
@@ -148,8 +149,8 @@ def main():
   with contextlib.redirect_stdout(sys.stderr):
     trainer = get_trainer(opt)(opt, 'test' if args.checkpoints_dir else 'train')
   keys = ('l1', 'mse', 'ms_ssim', 'psnr')
-  by_batch = dict.fromkeys(keys + ('shannon', 'actual', 'file', 'coded', 'semantics', 'total'), 0.0)
-  by_image = dict.fromkeys(keys + ('shannon', 'actual', 'file', 'coded', 'semantics', 'total'), 0.0)
+  by_batch = dict.fromkeys(keys + ('shannon', 'actual', 'context', 'file', 'coded', 'semantics', 'total'), 0.0)
+  by_image = dict.fromkeys(keys + ('shannon', 'actual', 'context', 'file', 'coded', 'semantics', 'total'), 0.0)
   images, n_batches, worst_diff = 0, 0, 0.0
   class_sums = None                  # int64 [1, n_classes + 1, 3]: the raw class tables of every image so far, added up
   start = time.time()
@@ -179,6 +180,10 @@ def main():
       by_image['shannon'] += shannon * b
       by_image['actual'] += actual * b
       line += ', pre-/(estimated) post-entropy coding bpp {:.4f}/{:.4f}'.format(actual, shannon)
+      context = trainer.get_context_rate(x_dict)       # the context model's estimate, in bits (a lower bound
+      by_batch['context'] += context                   # of the coded size, not a size)
+      by_image['context'] += context * b
+      line += ', context-model bpp {:.4f}'.format(context)
     if args.entropy:
       coded_bpp, raw_file_bpp = trainer.get_coded_rate(x_dict)
       by_batch['coded'] += coded_bpp
@@ -212,6 +217,7 @@ def main():
                                                                             t['ms_ssim'] / n, t['psnr'] / n)
     if args.codec:
       line += ', avg pre-/(estimated) post-entropy coding bpp {:.4f}/{:.4f}'.format(t['actual'] / n, t['shannon'] / n)
+      line += ', avg context-model bpp {:.4f}'.format(t['context'] / n)
     if args.entropy:
       line += ', avg coded file bpp {:.4f}'.format(t['coded'] / n)
     if args.semantics:
