@@ -3,8 +3,8 @@
 // gradient w.r.t. the binarizer's tanh output.  Definition: DESIGN.md 4.10.  Entry point: include/jpdse.h, "context-model
 // rate term".
 //
-// The context of a symbol depends on the code alone (entropy.hip's rule: left | up << 1 | upleft << 2 | upright << 3 over the
-// bits b > 0 of the same (image, channel) stream), so unlike the coder nothing here is serial.  Kernels, in launch order:
+// The context of a symbol depends on the code alone (the coder's own rule, context_of of range_coder.h, over the bits b > 0
+// of the same (image, channel) stream), so unlike the coder nothing here is serial.  Kernels, in launch order:
 //   rate_count_kernel   lane = channel, as in entropy.hip: the 64 lanes of a wave read 64 neighbouring channels of a pixel.
 //                       grid (row chunks, 64-channel groups, images), four waves, wave w takes the chunk's rows w, w + 4, ...
 //                       Every lane counts (ctx, bit) pairs in an LDS column of its own; the four waves' columns are summed
@@ -15,7 +15,7 @@
 //   rate_final_kernel   ONE block: the partials of an image in a fixed order (fp64), per_image and the value slot.
 // Lanes c >= C of the last group hold no stream: they load nothing, count nothing, and write zeros into the padding lanes
 // C <= c < CPAD(C) of the gradient.  Every loop is bounded by the shape.
-#include "common.h"
+#include "range_coder.h"
 
 namespace jpdse {
 
@@ -39,13 +39,7 @@ __device__ __forceinline__ void rate_walk_row(const T* __restrict__ img, int y, 
   const int nw = (W + 31) >> 5;
   auto word = [&](int yy, int j) -> uint32_t {
     uint32_t w = 0;
-    if (active && yy >= 0 && j < nw) {
-      const int kmax = min(32, W - 32 * j);
-      const T* px = img + ((long long)yy * W + 32 * j) * Cs;
-#pragma unroll
-      for (int k = 0; k < 32; ++k)
-        if (k < kmax) w |= (uint32_t)(ElemOps<T>::ld(px + (long long)k * Cs) > 0.f) << k;
-    }
+    if (active && yy >= 0 && j < nw) w = load_bit_word(img + ((long long)yy * W + 32 * j) * Cs, Cs, min(32, W - 32 * j));
     return w;
   };
   uint32_t upw = word(y - 1, 0), left = 0, ul = 0;
@@ -55,10 +49,8 @@ __device__ __forceinline__ void rate_walk_row(const T* __restrict__ img, int y, 
     const uint32_t inw = word(y, j);
     const int kmax = min(32, W - 32 * j);
     for (int k = 0; k < kmax; ++k) {
-      const uint32_t bit = (inw >> k) & 1u;
-      const uint32_t up = (upw >> k) & 1u;
-      const uint32_t ctx = left | up << 1 | ul << 2 | ((urw >> k) & 1u) << 3;
-      f(32 * j + k, ctx, bit);
+      const uint32_t bit = (inw >> k) & 1u, up = (upw >> k) & 1u;
+      f(32 * j + k, context_of(left, up, ul, (urw >> k) & 1u), bit);
       ul = up;
       left = bit;
     }

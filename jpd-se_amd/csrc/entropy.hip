@@ -3,20 +3,17 @@
 // include/jpdse.h, "learned codec: entropy-coded bitstream".
 //
 // Every (image, channel) pair is one independent stream of H*W symbols (bit = b > 0, raster order) with its own 16 adaptive
-// probabilities, selected by the four already-coded neighbours left | up << 1 | upleft << 2 | upright << 3.  The coder is the
-// carry-propagating range coder of LZMA (I. Pavlov, LZMA SDK, public domain; 11-bit probabilities, shift 5): the work of one
-// stream is serial, so one LANE codes one stream and lane = channel -- the 64 lanes of a wave read (or write) 64 neighbouring
-// channels of one pixel of the NHWC tensor.  All streams of a call have the same H and W: the loops over y and x are
-// wave-uniform, only the byte output (encoder) / input (decoder) diverges.  A lane's probability table and the bits of its
-// previous row (32 per word) live in LDS columns that no other lane touches, so no barrier is needed.
-#include "common.h"
+// probabilities, selected by the four already-coded neighbours.  The coder core, the payload layout and the context rule are
+// range_coder.h's; this file is the walk over the code tensor.  The work of one stream is serial, so one LANE codes one
+// stream and lane = channel -- the 64 lanes of a wave read (or write) 64 neighbouring channels of one pixel of the NHWC
+// tensor.  All streams of a call have the same H and W: the loops over y and x are wave-uniform, only the byte output
+// (encoder) / input (decoder) diverges.  A lane's probability table and the bits of its previous row (32 per word) live in
+// LDS columns that no other lane touches, so no barrier is needed.
+#include "range_coder.h"
 
 namespace jpdse {
 
 constexpr int kEntropyMaxW = 4096;             // 128 words of row bits per lane: (16 + 128) * 64 * 4 = 36 KiB of LDS
-constexpr uint32_t kTop = 1u << 24;
-constexpr uint32_t kProbInit = 1024, kProbOne = 2048;
-constexpr int kMoveBits = 5;
 
 static inline long long stream_cap(int H, int W) { return (long long)H * W + 8; }
 // bytes of one image's payload at most: the table of C lengths and C full slots; 0: a shape the kernels do not take
@@ -28,13 +25,9 @@ static long long image_cap(int H, int W, int C) {
 }
 static inline size_t entropy_lds_bytes(int W) { return (size_t)(16 + (W + 31) / 32) * 64 * sizeof(uint32_t); }
 
-// ctx of the symbol at bit k of the current word: upw = the row above (bit k = up), urw = the same shifted down by one
-__device__ __forceinline__ uint32_t context_of(uint32_t left, uint32_t ul, uint32_t upw, uint32_t urw, int k) {
-  return left | ((upw >> k) & 1u) << 1 | ul << 2 | ((urw >> k) & 1u) << 3;
-}
-
-// Phase 1 of the encoder: stream (n, c) into its slot of `scap` bytes; lens[n*C + c] = the bytes the stream needs (more than
-// scap: it did not fit, the slot holds the first scap of them).  grid (ceil(C / 64), N), one wave per block.
+// Phase 1 of the encoder: stream (n, c) into its slot of `scap` bytes; lens[n*C + c] = the bytes the stream needs (scap + 1:
+// it did not fit, the slot holds the first scap of them -- unreachable).  grid (ceil(C / 64), N), one wave
+// per block.
 template <typename T>
 __global__ void __launch_bounds__(64) entropy_encode_kernel(const T* __restrict__ b, uint8_t* __restrict__ slots,
                                                             int32_t* __restrict__ lens, int H, int W, int C, int Cs,
@@ -48,26 +41,8 @@ __global__ void __launch_bounds__(64) entropy_encode_kernel(const T* __restrict_
   for (int k = 0; k < 16; ++k) prob[k * 64] = kProbInit;
   for (int j = 0; j < nw; ++j) row[j * 64] = 0;
   const T* src = b + (long long)n * H * W * Cs + c;
-  uint8_t* slot = slots + ((long long)n * C + c) * scap;
-
-  uint64_t low = 0;
-  uint32_t range = 0xFFFFFFFFu, cache = 0, cache_size = 1;
-  int emitted = 0;                              // bytes emitted so far, the unstored first one included
-  auto emit = [&](uint32_t byte) {
-    if (emitted >= 1 && emitted <= scap) slot[emitted - 1] = (uint8_t)byte;      // clipped to the slot
-    ++emitted;
-  };
-  auto shift_low = [&]() {
-    if ((uint32_t)low < 0xFF000000u || (low >> 32) != 0) {
-      const uint32_t carry = (uint32_t)(low >> 32);
-      emit(cache + carry);
-      for (uint32_t k = 1; k < cache_size; ++k) emit(0xFFu + carry);              // bounded by the bytes pending
-      cache_size = 0;
-      cache = (uint32_t)(low >> 24) & 0xFFu;
-    }
-    ++cache_size;
-    low = (low & 0x00FFFFFFull) << 8;
-  };
+  RcEncoder rc;
+  rc.init(slots + ((long long)n * C + c) * scap, scap);
 
   for (int y = 0; y < H; ++y) {
     uint32_t upw = row[0], left = 0, ul = 0;
@@ -75,77 +50,42 @@ __global__ void __launch_bounds__(64) entropy_encode_kernel(const T* __restrict_
       const uint32_t nextw = j + 1 < nw ? row[(j + 1) * 64] : 0u;
       const uint32_t urw = (upw >> 1) | (nextw << 31);
       const int kmax = min(32, W - 32 * j);
-      // the word's 32 input symbols first: independent loads, one memory latency per word instead of one per symbol
-      const T* px = src + ((long long)y * W + 32 * j) * Cs;
-      uint32_t inw = 0;
-#pragma unroll
-      for (int k = 0; k < 32; ++k)
-        if (k < kmax) inw |= (uint32_t)(ElemOps<T>::ld(px + (long long)k * Cs) > 0.f) << k;
+      // the word's 32 input symbols before any of them is coded
+      const uint32_t inw = load_bit_word(src + ((long long)y * W + 32 * j) * Cs, Cs, kmax);
       for (int k = 0; k < kmax; ++k) {
-        const uint32_t bit = (inw >> k) & 1u;
-        const uint32_t ctx = context_of(left, ul, upw, urw, k);
-        uint32_t p = prob[ctx * 64];
-        const uint32_t bound = (range >> 11) * p;
-        if (bit == 0) {
-          range = bound;
-          p += (kProbOne - p) >> kMoveBits;
-        } else {
-          low += bound;
-          range -= bound;
-          p -= p >> kMoveBits;
-        }
-        prob[ctx * 64] = p;
-        // range >= 1 here (0 < bound < range), so three shifts always reach 2^24
-        for (int it = 0; it < 3 && range < kTop; ++it) {
-          range <<= 8;
-          shift_low();
-        }
-        ul = (upw >> k) & 1u;
+        const uint32_t bit = (inw >> k) & 1u, up = (upw >> k) & 1u;
+        rc.encode(prob[context_of(left, up, ul, (urw >> k) & 1u) * 64], bit);
+        ul = up;
         left = bit;
       }
-      row[j * 64] = inw;                        // bits beyond W stay 0: nothing is loaded for k >= kmax
+      row[j * 64] = inw;                        // bits beyond W stay 0
       upw = nextw;
     }
   }
-  for (int k = 0; k < 5; ++k) shift_low();
-  lens[(long long)n * C + c] = emitted - 1;
+  lens[(long long)n * C + c] = rc.finish();
 }
 
 // Phase 2: the payload of image n = C little-endian uint32 stream lengths, then the streams in channel order.  One wave per
-// stream: it adds up the lengths in front of its own (C reads), writes its table entry and copies its slot.  The wave of the
-// last channel also writes sizes[n] and status[n].  grid (ceil(C / 4), N), 256 threads.
+// stream (compact_stream); the wave of the last channel also writes sizes[n] and status[n].  grid (ceil(C / 4), N), 256
+// threads.
 __global__ void entropy_compact_kernel(const uint8_t* __restrict__ slots, const int32_t* __restrict__ lens,
                                        uint8_t* __restrict__ out, long long out_stride, int32_t* __restrict__ sizes,
                                        int32_t* __restrict__ status, int C, int scap) {
   const int lane = threadIdx.x & 63, c = blockIdx.x * 4 + (threadIdx.x >> 6), n = blockIdx.y;
   if (c >= C) return;                           // wave-uniform
-  const int32_t* ln = lens + (long long)n * C;
-  int before = 0, overflow = 0;
-  for (int j = lane; j < c; j += 64) {
-    before += min(ln[j], scap);
-    overflow |= ln[j] > scap;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    before += __shfl_xor(before, off, 64);
-    overflow |= __shfl_xor(overflow, off, 64);
-  }
-  const int need = ln[c], len = min(need, scap);
-  uint8_t* image = out + (long long)n * out_stride;
-  if (lane < 4) image[4 * c + lane] = (uint8_t)((uint32_t)len >> (8 * lane));
-  // 4 C + before + len <= (4 + scap) C, the capacity the host checked out_stride against
-  uint8_t* dst = image + 4LL * C + before;
-  const uint8_t* src = slots + ((long long)n * C + c) * scap;
-  for (int i = lane; i < len; i += 64) dst[i] = src[i];
+  // the host checked out_stride against (4 + scap) C
+  const Compacted r = compact_stream(out + (long long)n * out_stride, slots + ((long long)n * C + c) * scap,
+                                     lens + (long long)n * C, nullptr, C, c, lane, [=](int) { return scap; });
   if (c == C - 1 && lane == 0) {
-    sizes[n] = 4 * C + before + len;
-    status[n] = (overflow | (need > scap)) ? 1 : 0;
+    sizes[n] = r.end;
+    status[n] = r.status;
   }
 }
 
 // Decoder: lane c < C decodes stream (n, c) and writes +1 / -1 into its lane of b; the padding lanes C <= c < Cs write 0.
-// The length table comes from the payload and is not trusted: every stream is clipped to its image's row of `stride` bytes,
-// a byte past the end of a stream reads as 0, and the symbol count is H*W whatever the bytes are.
+// The length table comes from the payload and is not trusted: every stream is clipped to its image's row of `stride` bytes
+// (stream_span; 4 C <= stride: checked by the host), a byte past the end of a stream reads as 0, and the symbol count is
+// H*W whatever the bytes are.
 // grid (ceil(Cs / 64), N), one wave per block.
 template <typename T>
 __global__ void __launch_bounds__(64) entropy_decode_kernel(const uint8_t* __restrict__ in, long long stride,
@@ -153,59 +93,20 @@ __global__ void __launch_bounds__(64) entropy_decode_kernel(const uint8_t* __res
   extern __shared__ uint32_t lds[];
   const int lane = threadIdx.x, c0 = blockIdx.x * 64, c = c0 + lane, n = blockIdx.y;
   const uint8_t* image = in + (long long)n * stride;
-  auto table = [&](int j) -> unsigned long long {            // 4 C <= stride: checked by the host
-    if (j >= C) return 0;
-    const uint8_t* t = image + 4LL * j;
-    return (uint32_t)t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
-  };
-  // where the stream starts: the lengths of all channels in front of it (whole wave, before any lane leaves)
-  unsigned long long base = 0;
-  for (int j0 = 0; j0 < c0; j0 += 64) {
-    unsigned long long v = table(j0 + lane);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    base += v;
-  }
-  const unsigned long long mine = table(c);
-  unsigned long long incl = mine;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned long long t = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += t;
-  }
+  const StreamSpan span = stream_span(image, C, c0, lane, stride);
   if (c >= Cs) return;
   T* dst = b + (long long)n * H * W * Cs + c;
   if (c >= C) {
     for (long long p = 0; p < (long long)H * W; ++p) ElemOps<T>::st(dst + p * Cs, 0.f);
     return;
   }
-  // sums of up to C values below 2^32 cannot wrap 64 bits
-  const unsigned long long ustride = (unsigned long long)stride;
-  const unsigned long long start = min(4ull * C + base + (incl - mine), ustride);
-  const unsigned long long end = min(start + mine, ustride);
-  const uint8_t* sp = image + start;
-  const long long slen = (long long)(end - start);
-  long long rp = 0;
-  uint32_t buf = 0;
-  int nbuf = 0;
-  auto next_byte = [&]() -> uint32_t {          // four bytes per refill: independent loads, zeros past the stream's end
-    if (nbuf == 0) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) buf = buf << 8 | (rp + i < slen ? (uint32_t)sp[rp + i] : 0u);
-      rp += 4;
-      nbuf = 4;
-    }
-    --nbuf;
-    return (buf >> (8 * nbuf)) & 0xFFu;
-  };
-
   uint32_t* prob = lds + lane;
   uint32_t* row = lds + 16 * 64 + lane;
   const int nw = (W + 31) >> 5;
   for (int k = 0; k < 16; ++k) prob[k * 64] = kProbInit;
   for (int j = 0; j < nw; ++j) row[j * 64] = 0;
-  uint32_t range = 0xFFFFFFFFu, code = 0;
-  for (int k = 0; k < 4; ++k) code = code << 8 | next_byte();
+  RcDecoder rc;
+  rc.init(image + span.start, (long long)(span.end - span.start));
 
   for (int y = 0; y < H; ++y) {
     uint32_t upw = row[0], left = 0, ul = 0;
@@ -216,28 +117,11 @@ __global__ void __launch_bounds__(64) entropy_decode_kernel(const uint8_t* __res
       T* px = dst + ((long long)y * W + 32 * j) * Cs;
       uint32_t outw = 0;
       for (int k = 0; k < kmax; ++k) {
-        const uint32_t ctx = context_of(left, ul, upw, urw, k);
-        uint32_t p = prob[ctx * 64];
-        const uint32_t bound = (range >> 11) * p;
-        uint32_t bit;
-        if (code < bound) {
-          range = bound;
-          p += (kProbOne - p) >> kMoveBits;
-          bit = 0;
-        } else {
-          range -= bound;
-          code -= bound;
-          p -= p >> kMoveBits;
-          bit = 1;
-        }
-        prob[ctx * 64] = p;
-        for (int it = 0; it < 3 && range < kTop; ++it) {      // 0 < bound < range whatever `code` is: range >= 1
-          range <<= 8;
-          code = code << 8 | next_byte();
-        }
+        const uint32_t up = (upw >> k) & 1u;
+        const uint32_t bit = rc.decode(prob[context_of(left, up, ul, (urw >> k) & 1u) * 64]);
         ElemOps<T>::st(px + (long long)k * Cs, bit ? 1.f : -1.f);
         outw |= bit << k;
-        ul = (upw >> k) & 1u;
+        ul = up;
         left = bit;
       }
       row[j * 64] = outw;

@@ -11,13 +11,16 @@
 // lane reads its row in chunks of 16 pixels with independent (and, where the row pitch allows, 16-byte) loads and stages them
 // in an LDS column of its own next to its probabilities: no other lane touches a column, so no barrier is needed.  The row
 // above comes from the input (encoder) or from what the same lane has already written to the output (decoder).
-#include "common.h"
+//
+// The coder's constants and the second phase of the encoder (compact_stream) are range_coder.h's.  The strip encoder and
+// decoder keep the coder's arithmetic and the reader of the length table as local code, a second copy of what RcEncoder,
+// RcDecoder and stream_span hold: each is one serial, latency-bound loop, and through the shared structs its time moved by
+// -6 % to +9 % with the input and with where the compiler put the same instructions (profiles/rc_refactor_ab.txt).  They
+// stay on the form whose machine code is the measured one; the tests hold both copies to the same bytes.
+#include "range_coder.h"
 
 namespace jpdse {
 
-constexpr uint32_t kSemTop = 1u << 24;
-constexpr uint32_t kSemProbInit = 1024, kSemProbOne = 2048;
-constexpr int kSemMoveBits = 5;
 constexpr int kSemProbs = 11;                  // 8 contexts of "== left", 3 of "== up"
 constexpr int kSemChunk = 16;                  // pixels per staged chunk
 constexpr int kSemLdsWords = (kSemProbs + 2 * kSemChunk) * 64;      // probabilities, the chunk, the chunk above it
@@ -123,7 +126,7 @@ __device__ __forceinline__ uint32_t sem_encode_strip(const typename P::Elem* __r
   uint32_t* prob = lds + lane;                                   // [11][64]
   uint32_t* cur = lds + kSemProbs * 64 + lane;                   // [16][64]: the chunk being coded
   uint32_t* upc = lds + (kSemProbs + kSemChunk) * 64 + lane;     // [16][64]: the same columns of the row above
-  for (int k = 0; k < kSemProbs; ++k) prob[k * 64] = kSemProbInit;
+  for (int k = 0; k < kSemProbs; ++k) prob[k * 64] = kProbInit;
 
   uint64_t low = 0;
   uint32_t range = 0xFFFFFFFFu, cache = 0, cache_size = 1, bad = 0;
@@ -151,7 +154,7 @@ __device__ __forceinline__ uint32_t sem_encode_strip(const typename P::Elem* __r
       range -= bound;
     }
     // 2^17 < bound < range - 2^17 for every probability in [31, 2017]: one shift reaches 2^24
-    for (int it = 0; it < 3 && range < kSemTop; ++it) {
+    for (int it = 0; it < 3 && range < kTop; ++it) {
       range <<= 8;
       shift_low();
     }
@@ -159,7 +162,7 @@ __device__ __forceinline__ uint32_t sem_encode_strip(const typename P::Elem* __r
   auto code = [&](int ctx, uint32_t bit) {
     uint32_t p = prob[ctx * 64];
     const uint32_t bound = (range >> 11) * p;
-    p = bit ? p - (p >> kSemMoveBits) : p + ((kSemProbOne - p) >> kSemMoveBits);
+    p = bit ? p - (p >> kMoveBits) : p + ((kProbOne - p) >> kMoveBits);
     prob[ctx * 64] = p;
     split(bound, bit);
   };
@@ -233,9 +236,8 @@ __global__ void __launch_bounds__(64) semantics_encode_kernel(SemEncArgs a, int3
 }
 
 // Phase 2: the payload of plane p of image n = S little-endian uint32 stream lengths, then the streams in strip order, at
-// out_off of the image's row.  One wave per stream: it adds up the lengths in front of its own (S reads), writes its table
-// entry and copies its slot.  The wave of the last strip also writes sizes[n][plane] and status[n][plane].
-// grid (ceil(S / 4), N, planes), 256 threads.
+// out_off of the image's row.  One wave per stream (compact_stream); the wave of the last strip also writes sizes[n][plane]
+// and status[n][plane].  grid (ceil(S / 4), N, planes), 256 threads.
 __global__ void semantics_compact_kernel(SemEncArgs a, const int32_t* __restrict__ oor, uint8_t* __restrict__ out,
                                          long long out_stride, int32_t* __restrict__ sizes, int32_t* __restrict__ status) {
   const SemGeom& g = a.g;
@@ -243,29 +245,13 @@ __global__ void semantics_compact_kernel(SemEncArgs a, const int32_t* __restrict
   if (s >= S) return;                           // wave-uniform
   const SemEncPlane& pl = a.p[blockIdx.z];
   const int raw = pl.id == 0 ? 1 : 4;
-  const int32_t* ln = pl.lens + (long long)n * S;
-  const int32_t* flags = oor + ((long long)n * 2 + pl.id) * S;
-  int before = 0, st = 0;
-  for (int j = lane; j < S; j += 64) {          // the status needs every strip, the offset those in front
-    const int cap = g.scap(j, raw), need = ln[j];
-    if (j < s) before += min(need, cap);
-    st |= (need > cap ? 1 : 0) | flags[j];
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    before += __shfl_xor(before, off, 64);
-    st |= __shfl_xor(st, off, 64);
-  }
-  const int len = min(ln[s], g.scap(s, raw));
-  uint8_t* image = out + (long long)n * out_stride + pl.out_off;
-  if (lane < 4) image[4 * s + lane] = (uint8_t)((uint32_t)len >> (8 * lane));
-  // 4 S + before + len <= 4 S + the sum of all slots = the plane's capacity, which the host checked out_stride against
-  uint8_t* dst = image + 4LL * S + before;
-  const uint8_t* src = pl.slots + ((long long)n * S + s) * pl.slot_stride;
-  for (int i = lane; i < len; i += 64) dst[i] = src[i];
+  // the host checked out_stride against the plane's capacity: 4 S + the sum of all slots
+  const Compacted r = compact_stream(out + (long long)n * out_stride + pl.out_off, pl.slots + ((long long)n * S + s) * pl.slot_stride,
+                                     pl.lens + (long long)n * S, oor + ((long long)n * 2 + pl.id) * S, S, s, lane,
+                                     [&](int j) { return g.scap(j, raw); });
   if (s == S - 1 && lane == 0) {
-    sizes[2 * n + pl.id] = 4 * S + before + len;
-    status[2 * n + pl.id] = st;
+    sizes[2 * n + pl.id] = r.end;
+    status[2 * n + pl.id] = r.status;
   }
 }
 
@@ -280,7 +266,7 @@ __device__ __forceinline__ uint32_t sem_decode_strip(typename P::Elem* img, cons
   const int lane = threadIdx.x, W = g.W, rows = g.rows(s);
   uint32_t* prob = lds + lane;
   uint32_t* upc = lds + (kSemProbs + kSemChunk) * 64 + lane;
-  for (int k = 0; k < kSemProbs; ++k) prob[k * 64] = kSemProbInit;
+  for (int k = 0; k < kSemProbs; ++k) prob[k * 64] = kProbInit;
   long long rp = 0;
   uint32_t buf = 0;
   int nbuf = 0;
@@ -305,7 +291,7 @@ __device__ __forceinline__ uint32_t sem_decode_strip(typename P::Elem* img, cons
       code -= bound;
       bit = 1;
     }
-    for (int it = 0; it < 3 && range < kSemTop; ++it) {         // 0 < bound < range whatever `code` is: range >= 1
+    for (int it = 0; it < 3 && range < kTop; ++it) {         // 0 < bound < range whatever `code` is: range >= 1
       range <<= 8;
       code = code << 8 | next_byte();
     }
@@ -314,7 +300,7 @@ __device__ __forceinline__ uint32_t sem_decode_strip(typename P::Elem* img, cons
   auto decode = [&](int ctx) -> uint32_t {
     uint32_t p = prob[ctx * 64];
     const uint32_t bit = split((range >> 11) * p);
-    p = bit ? p - (p >> kSemMoveBits) : p + ((kSemProbOne - p) >> kSemMoveBits);
+    p = bit ? p - (p >> kMoveBits) : p + ((kProbOne - p) >> kMoveBits);
     prob[ctx * 64] = p;
     return bit;
   };

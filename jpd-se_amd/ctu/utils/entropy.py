@@ -20,6 +20,7 @@ import struct
 
 import torch
 
+from jpdse_hip.ops import check_length_table
 from . import bitstream
 
 MAGIC = b'JPDA'
@@ -41,11 +42,7 @@ def check_payload(payload, C, who='payload'):
   """ValueError unless `payload` is bytes holding a table of C uint32 lengths that add up to the bytes after it."""
   if not isinstance(payload, (bytes, bytearray)):
     raise ValueError('%s: a coded payload is bytes, got %s' % (who, type(payload).__name__))
-  if len(payload) < 4 * C:
-    raise ValueError('%s: truncated, %d bytes are shorter than the table of %d stream lengths' % (who, len(payload), C))
-  total = sum(struct.unpack_from('<%dI' % C, payload))
-  if total != len(payload) - 4 * C:
-    raise ValueError('%s: the length table sums to %d, but %d bytes follow it' % (who, total, len(payload) - 4 * C))
+  check_length_table(payload, C, who)
 
 
 def mode_of(payload_len, code_shape):

@@ -22,7 +22,7 @@ are those of jpdse_hip.ops, which produces and consumes the entries: semantics_c
 import struct
 
 from jpdse_hip.ops import (SEM_RAW as MODE_RAW, SEM_CODED as MODE_CODED, SEM_RAW_BYTES as RAW_BYTES, semantics_strips as strips,
-                           semantics_check_entry)
+                           semantics_check_entry, length_table_size)
 
 MAGIC = b'JPDS'
 VERSION = 1
@@ -100,12 +100,8 @@ def unpack(blob, who='semantics blob'):
     if not mask >> p & 1:
       continue
     name = '%s: %s plane' % (who, PLANES[p])
-    if modes[p] == MODE_RAW:
-      size = raw_plane_bytes(p, H, W)
-    else:
-      if len(blob) - at < 4 * S:
-        raise ValueError('%s: truncated, %d bytes are shorter than the table of %d stream lengths' % (name, len(blob) - at, S))
-      size = 4 * S + sum(struct.unpack_from('<%dI' % S, blob, at))
+    # a coded plane is self-delimiting; whether the blob holds all of it shows below, as for a raw one
+    size = raw_plane_bytes(p, H, W) if modes[p] == MODE_RAW else length_table_size(blob, S, name, at)
     if len(blob) - at < size:
       raise ValueError('%s: truncated, %d bytes of the %d the plane needs (%s)'
                        % (name, len(blob) - at, size, 'raw' if modes[p] == MODE_RAW else 'its length table sums to %d' % (size - 4 * S)))

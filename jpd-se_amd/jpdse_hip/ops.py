@@ -592,6 +592,22 @@ def code_entropy_encode(b):
   return [host[head + n * cap:head + n * cap + int(sizes[n])].tobytes() for n in range(N)]
 
 
+def length_table_size(buf, count, who, at=0):
+  """The payload layout of DESIGN.md 4.8 on the host: buf[at:] starts with a table of `count` little-endian uint32 stream
+  lengths, then the streams.  Returns the size the table gives the payload, 4 * count + its sum; ValueError when buf ends
+  inside the table.  Nothing is copied."""
+  if len(buf) - at < 4 * count:
+    raise ValueError('%s: truncated, %d bytes are shorter than the table of %d stream lengths' % (who, len(buf) - at, count))
+  return 4 * count + sum(struct.unpack_from('<%dI' % count, buf, at))
+
+
+def check_length_table(payload, count, who):
+  """ValueError unless the table of `count` lengths at the start of `payload` adds up to exactly the bytes that follow it."""
+  size = length_table_size(payload, count, who)
+  if size != len(payload):
+    raise ValueError('%s: the length table sums to %d, but %d bytes follow it' % (who, size - 4 * count, len(payload) - 4 * count))
+
+
 def code_entropy_decode(payloads, N, H, W, C, dtype_code, device=None):
   """The inverse (jpdse_code_entropy_decode): N payloads as code_entropy_encode returns them -> the NHWC Act [N, H, W, C] of
   +1 / -1 that code_import gives for the raw code.  ValueError before any library call for a wrong payload count, an item
@@ -603,12 +619,7 @@ def code_entropy_decode(payloads, N, H, W, C, dtype_code, device=None):
   for n, p in enumerate(payloads):
     if not isinstance(p, (bytes, bytearray)):
       raise ValueError('code_entropy_decode: payload %d is %s, not bytes' % (n, type(p).__name__))
-    if len(p) < 4 * C:
-      raise ValueError('code_entropy_decode: payload %d of %d bytes is shorter than its table of %d stream lengths' % (n, len(p), C))
-    total = sum(struct.unpack_from('<%dI' % C, p))
-    if total != len(p) - 4 * C:
-      raise ValueError('code_entropy_decode: the length table of payload %d sums to %d, but %d bytes follow it'
-                       % (n, total, len(p) - 4 * C))
+    check_length_table(p, C, 'code_entropy_decode: payload %d' % n)
   stride = max(len(p) for p in payloads)
   if stride >= 1 << 31:
     raise ValueError('code_entropy_decode: a payload of %d bytes' % stride)
@@ -705,17 +716,11 @@ def semantics_check_entry(entry, plane, H, W, strip_rows, who):
   mode, payload = entry
   if mode not in (SEM_RAW, SEM_CODED):
     raise ValueError('%s: unknown mode %r (0 = raw, 1 = coded)' % (who, mode))
-  S = semantics_strips(H, strip_rows)
-  if mode == SEM_RAW:
-    if len(payload) != H * W * SEM_RAW_BYTES[plane]:
-      raise ValueError('%s: a raw plane (%s) of %d x %d is %d bytes, got %d'
-                       % (who, _SEM_NAMES[plane], H, W, H * W * SEM_RAW_BYTES[plane], len(payload)))
-    return
-  if len(payload) < 4 * S:
-    raise ValueError('%s: truncated, %d bytes are shorter than the table of %d stream lengths' % (who, len(payload), S))
-  total = sum(struct.unpack_from('<%dI' % S, payload))
-  if total != len(payload) - 4 * S:
-    raise ValueError('%s: the length table sums to %d, but %d bytes follow it' % (who, total, len(payload) - 4 * S))
+  if mode == SEM_CODED:
+    check_length_table(payload, semantics_strips(H, strip_rows), who)
+  elif len(payload) != H * W * SEM_RAW_BYTES[plane]:
+    raise ValueError('%s: a raw plane (%s) of %d x %d is %d bytes, got %d'
+                     % (who, _SEM_NAMES[plane], H, W, H * W * SEM_RAW_BYTES[plane], len(payload)))
 
 
 def semantics_decode(items, H, W, strip_rows, num_labels, device=None):

@@ -5,9 +5,9 @@ them alone; it is what stands in for "kernel speed unchanged").
   python scripts/diff_code_objects.py [--match-by-content] CSRC_DIR_A CSRC_DIR_B
 
 CSRC_DIR_x: a csrc directory after `make` (it holds conv_gemm.o, conv_gemm.dev.o, norm.o, norm.dev.o, elementwise.o,
-binarize.o, metrics.o).  Per object file the gfx950 code object is taken out of the .hip_fatbin section (llvm-objcopy +
-clang-offload-bundler), then compared PER SYMBOL -- host code that instantiates kernels in another order may reorder them
-inside the object:
+binarize.o, metrics.o, msssim_loss.o, entropy.o, semantics.o, code_rate.o).  Per object file the gfx950 code object is
+taken out of the .hip_fatbin section (llvm-objcopy + clang-offload-bundler), then compared PER SYMBOL -- host code that
+instantiates kernels in another order may reorder them inside the object:
   * the set of kernels (the .kd symbols),
   * the resources of each (vgpr / sgpr / agpr count, LDS and scratch size, kernarg size: the metadata note),
   * the instruction stream of each function (llvm-objdump -d, addresses and encodings stripped).
@@ -23,7 +23,8 @@ import sys
 import tempfile
 
 LLVM = os.environ.get('ROCM_LLVM_BIN', '/opt/rocm/llvm/bin')
-OBJECTS = ['conv_gemm.o', 'conv_gemm.dev.o', 'norm.o', 'norm.dev.o', 'elementwise.o', 'binarize.o', 'metrics.o']
+OBJECTS = ['conv_gemm.o', 'conv_gemm.dev.o', 'norm.o', 'norm.dev.o', 'elementwise.o', 'binarize.o', 'metrics.o', 'msssim_loss.o',
+           'entropy.o', 'semantics.o', 'code_rate.o']
 TARGET = 'hipv4-amdgcn-amd-amdhsa--gfx950'
 RESOURCES = ('.vgpr_count', '.sgpr_count', '.agpr_count', '.group_segment_fixed_size', '.private_segment_fixed_size',
              '.kernarg_segment_size')

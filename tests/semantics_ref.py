@@ -1,6 +1,6 @@
 """Pure-Python restatement of the coded label / instance maps (TEST INFRASTRUCTURE), written from the format text of
-DESIGN.md 4.9 and from nothing else.  The binary coder is the one of 4.8 (tests/entropy_ref.py has its constants and the
-carry counters); only the modelling is new:
+DESIGN.md 4.9 and from nothing else.  The binary coder and the payload layout are those of 4.8 (tests/rc_ref.py has both, and
+the carry counters); only the modelling is new:
 
   planes    0: label map, values 0..255, 8-bit literal, 1 raw byte;  1: instance map, values 0..2^31-1, 32-bit literal,
             4 raw bytes (little-endian int32)
@@ -12,11 +12,9 @@ carry counters); only the modelling is new:
             3. otherwise the value, most significant bit first, each bit at the fixed probability 1024 (no update)
   payload   of one plane of one image: S little-endian uint32 stream lengths, then the S streams in strip order
 """
-import struct
-
 import numpy as np
 
-from entropy_ref import Counters, PROB_INIT, PROB_ONE, MOVE_BITS, TOP
+from rc_ref import Counters, Encoder, Decoder, PROB_INIT, join_payload, split_payload  # noqa: F401  (Counters, split_payload: re-exported)
 
 LITERAL_BITS = (8, 32)
 RAW_BYTES = (1, 4)
@@ -47,46 +45,7 @@ def encode_stream(values, rows, W, plane, counters=None):
   """values: rows*W ints in raster order -> the stream's bytes (uncut, whatever their number)."""
   assert len(values) == rows * W
   nlit = LITERAL_BITS[plane]
-  probs = [PROB_INIT] * N_PROBS
-  low, rng, cache, cache_size = 0, 0xFFFFFFFF, 0, 1
-  out = bytearray()
-  stats = counters if counters is not None else Counters()
-
-  def shift_low():
-    nonlocal low, cache, cache_size
-    if (low & 0xFFFFFFFF) < 0xFF000000 or (low >> 32) != 0:
-      carry = low >> 32
-      run = cache_size - 1
-      stats.longest_run = max(stats.longest_run, run)
-      stats.carries += carry
-      if carry and run >= 2:
-        stats.carries_into_run2 += 1
-      out.append((cache + carry) & 0xFF)
-      for _ in range(run):
-        out.append((0xFF + carry) & 0xFF)
-      cache_size = 0
-      cache = (low >> 24) & 0xFF
-    cache_size += 1
-    low = (low & 0x00FFFFFF) << 8
-
-  def code(ctx, bit):
-    """One binary decision; ctx None: the fixed probability 1024, no update."""
-    nonlocal low, rng
-    p = PROB_INIT if ctx is None else probs[ctx]
-    bound = (rng >> 11) * p
-    if bit == 0:
-      rng = bound
-      if ctx is not None:
-        probs[ctx] = p + ((PROB_ONE - p) >> MOVE_BITS)
-    else:
-      low += bound
-      rng -= bound
-      if ctx is not None:
-        probs[ctx] = p - (p >> MOVE_BITS)
-    while rng < TOP:
-      rng = (rng << 8) & 0xFFFFFFFF
-      shift_low()
-
+  probs, rc = [PROB_INIT] * N_PROBS, Encoder(counters)
   for y in range(rows):
     for x in range(W):
       v = values[y * W + x]
@@ -97,50 +56,22 @@ def encode_stream(values, rows, W, plane, counters=None):
       done = False
       if has_l:
         ctx = int(has_u and L == U) | int(UL is not None and UL == L) << 1 | int(UL is not None and UL == U) << 2
-        code(ctx, int(v == L))
+        rc.encode(probs, ctx, int(v == L))
         done = v == L
       if not done and has_u and not (has_l and U == L):
-        code(8 + int(UL is not None and UL == L) if has_l else 10, int(v == U))
+        rc.encode(probs, 8 + int(UL is not None and UL == L) if has_l else 10, int(v == U))
         done = v == U
       if not done:
         for k in range(nlit - 1, -1, -1):
-          code(None, (v >> k) & 1)
-  for _ in range(5):
-    shift_low()
-  assert out[0] == 0
-  return bytes(out[1:])
+          rc.encode(probs, None, (v >> k) & 1)      # None: the fixed probability 1024, no update
+  return rc.finish()
 
 
 def decode_stream(data, rows, W, plane):
   """The rows*W values of a stream; bytes past the end of `data` read as 0, the pixel count is fixed."""
   nlit = LITERAL_BITS[plane]
-  probs = [PROB_INIT] * N_PROBS
-  n = len(data)
-  code = int.from_bytes((bytes(data[:4]) + b'\0\0\0\0')[:4], 'big')
-  pos, rng = 4, 0xFFFFFFFF
+  probs, rc = [PROB_INIT] * N_PROBS, Decoder(data)
   values = [0] * (rows * W)
-
-  def bit_of(ctx):
-    nonlocal code, rng, pos
-    p = PROB_INIT if ctx is None else probs[ctx]
-    bound = (rng >> 11) * p
-    if code < bound:
-      rng = bound
-      if ctx is not None:
-        probs[ctx] = p + ((PROB_ONE - p) >> MOVE_BITS)
-      bit = 0
-    else:
-      rng -= bound
-      code -= bound
-      if ctx is not None:
-        probs[ctx] = p - (p >> MOVE_BITS)
-      bit = 1
-    while rng < TOP:
-      rng = (rng << 8) & 0xFFFFFFFF
-      code = ((code << 8) & 0xFFFFFFFF) | (data[pos] if pos < n else 0)
-      pos += 1
-    return bit
-
   for y in range(rows):
     for x in range(W):
       has_l, has_u = x > 0, y > 0
@@ -150,15 +81,15 @@ def decode_stream(data, rows, W, plane):
       v = None
       if has_l:
         ctx = int(has_u and L == U) | int(UL is not None and UL == L) << 1 | int(UL is not None and UL == U) << 2
-        if bit_of(ctx):
+        if rc.decode(probs, ctx):
           v = L
       if v is None and has_u and not (has_l and U == L):
-        if bit_of(8 + int(UL is not None and UL == L) if has_l else 10):
+        if rc.decode(probs, 8 + int(UL is not None and UL == L) if has_l else 10):
           v = U
       if v is None:
         v = 0
         for _ in range(nlit):
-          v = v << 1 | bit_of(None)
+          v = v << 1 | rc.decode(probs, None)
       values[y * W + x] = v
   return values
 
@@ -176,20 +107,7 @@ def encode_plane(a, plane, strip_rows, counters=None):
     if len(s) > cap:
       s, cut = s[:cap], True
     streams.append(s)
-  return b''.join([struct.pack('<I', len(s)) for s in streams] + streams), cut
-
-
-def split_payload(payload, S):
-  if len(payload) < 4 * S:
-    raise ValueError('payload of %d bytes is shorter than its table of %d lengths' % (len(payload), S))
-  lens = struct.unpack('<%dI' % S, payload[:4 * S])
-  if sum(lens) != len(payload) - 4 * S:
-    raise ValueError('length table sums to %d, %d bytes follow it' % (sum(lens), len(payload) - 4 * S))
-  out, at = [], 4 * S
-  for n in lens:
-    out.append(payload[at:at + n])
-    at += n
-  return out
+  return join_payload(streams), cut
 
 
 def decode_plane(payload, plane, H, W, strip_rows):
