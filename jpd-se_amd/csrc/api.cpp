@@ -31,28 +31,6 @@ int code_import_check(int dtype, int N, int H, int W, int C, const void* in, con
   return JPDSE_OK;
 }
 
-// jpdse_msssim_loss (msssim_loss.hip): the shapes the five-scale pass and its launch grids can take
-const char* msssim_loss_shape_error(int N, int H, int W, int C) {
-  if (N <= 0 || H <= 0 || W <= 0) return "msssim_loss: bad shape";
-  if (C != 3) return "msssim_loss: 3 channels only";
-  if (H < 176 || W < 176) return "msssim_loss: the shorter side must be at least 176 (five MS-SSIM scales of an 11x11 window)";
-  if ((long long)N * 3 > 65535) return "msssim_loss: more than 21845 images per call";
-  if ((long long)H * W > (1LL << 28)) return "msssim_loss: image beyond 2^28 pixels";
-  // grid y / x of the gradient's tiles at scale 1: ceil(H / 16), ceil(W / 64)
-  if ((H + 15) / 16 > 65535 || (W + 63) / 64 > 65535) return "msssim_loss: image side beyond the tile grid";
-  return nullptr;
-}
-
-int msssim_loss_check(const jpdse_msssim_loss_args* a) {
-  JPDSE_REQUIRE(a != nullptr, "msssim_loss: null argument struct");
-  JPDSE_REQUIRE(!bad_dtype(a->dtype), "msssim_loss: bad dtype %d (fake and real are both fp32 or both bf16)", a->dtype);
-  JPDSE_REQUIRE(a->fake && a->real && a->mean && a->std && a->out, "msssim_loss: null argument");
-  if (const char* msg = msssim_loss_shape_error(a->N, a->H, a->W, a->C))
-    return set_error(JPDSE_EINVAL, "%s (N %d, H %d, W %d, C %d)", msg, a->N, a->H, a->W, a->C);
-  JPDSE_REQUIRE(a->dfake == nullptr || a->scale == a->scale, "msssim_loss: scale is NaN");
-  return JPDSE_OK;
-}
-
 // ---- in-library timer for the HBM-bound calls (bench.py "roofline_hbm"): hipEvent pairs around whole InstanceNorm /
 // Adam calls, recorded on the stream the kernels run on; each region carries the call's ALGORITHMIC bytes.
 struct HbmProf {

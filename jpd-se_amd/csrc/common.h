@@ -20,9 +20,6 @@ int check_launch(const char* what);
 
 // argument checks of jpdse_code_import (api.cpp): JPDSE_EINVAL + message before any launch, JPDSE_OK otherwise
 int code_import_check(int dtype, int N, int H, int W, int C, const void* in, const void* b);
-// shape and argument checks of jpdse_msssim_loss (api.cpp): a message / JPDSE_EINVAL before any launch, nullptr / JPDSE_OK otherwise
-const char* msssim_loss_shape_error(int N, int H, int W, int C);
-int msssim_loss_check(const jpdse_msssim_loss_args* a);
 
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 

@@ -15,22 +15,15 @@
 // Cancellation: every tile is filtered about its own pivot (the value of its first pixel, per image of the pair): the local
 // statistics are shift invariant, E[(x-p)^2] - (mu-p)^2 is formed from values of the size of the tile's contrast instead
 // of 0..255, and a constant tile gives variance exactly 0.  The filter runs in fp32; the per-position cs / ssim and every
-// sum over positions are fp64.
-#include "common.h"
+// sum over positions are fp64.  The window, the staging, the filter passes, the downsample, the block sum and the geometry
+// are in msssim_core.h, shared with msssim_loss.hip.
+#include "msssim_core.h"
 
 namespace jpdse {
 
-constexpr int kMsScales = 5;
-constexpr int kWin = 11;                 // window taps
-constexpr int kHalo = kWin - 1;
-constexpr int kTW = 64, kTH = 16;        // outputs per block: one wave per 64-wide row, four rows per wave
-constexpr int kSW = kTW + kHalo;         // staged columns (74)
-constexpr int kSH = kTH + kHalo;         // staged rows (26)
 constexpr int kQuantBlocksMax = 1024;    // per image
 constexpr int kOutPerImage = 4 + 2 * kMsScales;
 constexpr int kClassesMax = 256;         // jpdse_eval_metrics_sem
-
-struct GaussWin { float w[kWin]; };
 
 // fake: NHWC [N][H][W][cs] fp32 or bf16, real: NHWC fp32.  One thread per pixel; planes x (fake) / y (real): [N][3][H*W].
 // kCls: label [N][H*W] fp32 is read as well and the two sums are split by class into cpartial[n][block][n_classes + 1][3]
@@ -160,60 +153,12 @@ __global__ __launch_bounds__(256) void msssim_scale_kernel(const float* __restri
   const int Ho = Hs - kHalo, Wo = Ws - kHalo;
   const int x0 = blockIdx.x * kTW, y0 = blockIdx.y * kTH;
   const long long plane = (long long)blockIdx.z * Hs * Ws;
-  const float* xp = x + plane;
-  const float* yp = y + plane;
-  // pivots: the tile's first pixel (always inside the plane: x0 < Wo, y0 < Ho)
-  const float pvx = xp[(long long)y0 * Ws + x0];
-  const float pvy = yp[(long long)y0 * Ws + x0];
-  for (int i = threadIdx.x; i < kSH * kSW; i += 256) {
-    const int r = i / kSW, c = i - r * kSW;
-    const int gy = y0 + r, gx = x0 + c;
-    float vx = 0.f, vy = 0.f;            // outside the plane: only feeds positions that are masked out below
-    if (gy < Hs && gx < Ws) {
-      vx = xp[(long long)gy * Ws + gx] - pvx;
-      vy = yp[(long long)gy * Ws + gx] - pvy;
-    }
-    sx[r][c] = vx;
-    sy[r][c] = vy;
-  }
-  __syncthreads();
-  // horizontal pass: 26 rows x 64 columns, one row per wave and iteration
-  for (int i = threadIdx.x; i < kSH * kTW; i += 256) {
-    const int r = i >> 6, c = i & 63;
-    float ax = 0.f, ay = 0.f, axx = 0.f, ayy = 0.f, axy = 0.f;
-#pragma unroll
-    for (int k = 0; k < kWin; ++k) {
-      const float a = sx[r][c + k], b = sy[r][c + k], w = g.w[k];
-      const float wa = w * a, wb = w * b;
-      ax += wa;
-      ay += wb;
-      axx = fmaf(wa, a, axx);
-      ayy = fmaf(wb, b, ayy);
-      axy = fmaf(wa, b, axy);
-    }
-    hq[0][r][c] = ax;
-    hq[1][r][c] = ay;
-    hq[2][r][c] = axx;
-    hq[3][r][c] = ayy;
-    hq[4][r][c] = axy;
-  }
-  __syncthreads();
-  // vertical pass: thread = (column, group of 4 output rows); 14 filtered rows feed its 4 outputs per quantity
-  const int c = threadIdx.x & 63, r0 = (threadIdx.x >> 6) * 4;
-  float acc[5][4];
-#pragma unroll
-  for (int q = 0; q < 5; ++q) {
-    float v[4 + kHalo];
-#pragma unroll
-    for (int j = 0; j < 4 + kHalo; ++j) v[j] = hq[q][r0 + j][c];
-#pragma unroll
-    for (int o = 0; o < 4; ++o) {
-      float a = 0.f;
-#pragma unroll
-      for (int k = 0; k < kWin; ++k) a = fmaf(g.w[k], v[o + k], a);
-      acc[q][o] = a;
-    }
-  }
+  float pvx, pvy, acc[5][4];          // pivots; filtered x, y, x^2, y^2, xy of the thread's 4 positions
+  stage_centred(x + plane, y + plane, Hs, Ws, x0, y0, sx, sy, pvx, pvy);
+  horizontal_pass5(sx, sy, g, hq);
+  vertical_pass<5>(hq, g, acc);
+  const int c = threadIdx.x & 63, r0 = (threadIdx.x >> 6) * 4;   // acc[q][o] is position (r0 + o, c): must match vertical_pass
+  // own epilogue, not msssim_loss.hip's: cs is written with plain operators here and these bits are jpdse_eval_metrics' contract
   double scs = 0.0, sss = 0.0;
 #pragma unroll
   for (int o = 0; o < 4; ++o) {
@@ -231,43 +176,14 @@ __global__ __launch_bounds__(256) void msssim_scale_kernel(const float* __restri
       sss += cs * lum;
     }
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    scs += __shfl_xor(scs, off, 64);
-    sss += __shfl_xor(sss, off, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    red[0][threadIdx.x >> 6] = scs;
-    red[1][threadIdx.x >> 6] = sss;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
+  if (block_sum_pair(scs, sss, red)) {
     double* o = partial + (((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 2;
-    o[0] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-    o[1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+    o[0] = scs;
+    o[1] = sss;
   }
 }
 
-// 2x2 mean, stride 2, odd last row / column dropped; one thread per output, both planes
-__global__ __launch_bounds__(256) void msssim_down_kernel(const float* __restrict__ x, const float* __restrict__ y, int Hs,
-                                                         int Ws, float* __restrict__ ox, float* __restrict__ oy,
-                                                         long long total) {
-  const int Hd = Hs >> 1, Wd = Ws >> 1;
-  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-    const int cx = (int)(i % Wd);
-    const long long t = i / Wd;
-    const int cy = (int)(t % Hd);
-    const long long nc = t / Hd;
-    const long long s = (nc * Hs + 2 * cy) * Ws + 2 * cx;
-    ox[i] = ((x[s] + x[s + 1]) + (x[s + Ws] + x[s + Ws + 1])) * 0.25f;
-    oy[i] = ((y[s] + y[s + 1]) + (y[s + Ws] + y[s + Ws + 1])) * 0.25f;
-  }
-}
-
-struct FinalArgs {
-  long long scale_off[kMsScales];   // first partial pair of the scale (in pairs), image 0
-  int scale_cnt[kMsScales];         // pairs per image (3 channels x tiles)
-  double pos[kMsScales];            // 3 * Ho * Wo: positions behind a per-scale mean
+struct FinalArgs : MsPartials {
   double count;                     // 3 * H * W: the elements behind the two integer sums
   int qblocks;
 };
@@ -296,28 +212,16 @@ __global__ __launch_bounds__(256) void metrics_final_kernel(const unsigned long 
         b += p[2 * i + 1];
       }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      a += __shfl_xor(a, off, 64);
-      b += __shfl_xor(b, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-      red[0][threadIdx.x >> 6] = a;
-      red[1][threadIdx.x >> 6] = b;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const double sa = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-      const double sb = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+    if (block_sum_pair(a, b, red)) {
       double* o = out + (long long)n * kOutPerImage;
       if (item == 0) {
-        o[0] = sa;
-        o[1] = sb;
+        o[0] = a;
+        o[1] = b;
         o[2] = fa.count;
         o[3] = 0.0;
       } else {
-        o[4 + item - 1] = sa / fa.pos[item - 1];
-        o[4 + kMsScales + item - 1] = sb / fa.pos[item - 1];
+        o[4 + item - 1] = a / fa.pos[item - 1];
+        o[4 + kMsScales + item - 1] = b / fa.pos[item - 1];
       }
     }
     __syncthreads();
@@ -325,10 +229,7 @@ __global__ __launch_bounds__(256) void metrics_final_kernel(const unsigned long 
 }
 
 // ---- host side: geometry and workspace layout -------------------------------------------------------------------------------
-struct MetricsPlan {
-  int Hs[kMsScales], Ws[kMsScales], tx[kMsScales], ty[kMsScales];
-  size_t plane_off[kMsScales];     // floats, from the start of the x planes (the y planes have the same layout)
-  size_t plane_floats;             // all scales, one image of the pair
+struct MetricsPlan : MsGeometry {
   int qblocks;
   size_t off_y, off_qpartial, off_spartial, bytes;
   FinalArgs fa;
@@ -342,21 +243,7 @@ static int metrics_quant_blocks(long long HW) {
 }
 
 static void metrics_plan(int N, int H, int W, MetricsPlan& p) {
-  size_t off = 0;
-  long long pairs = 0;
-  for (int j = 0; j < kMsScales; ++j) {
-    p.Hs[j] = H >> j;
-    p.Ws[j] = W >> j;
-    p.tx[j] = (p.Ws[j] - kHalo + kTW - 1) / kTW;
-    p.ty[j] = (p.Hs[j] - kHalo + kTH - 1) / kTH;
-    p.plane_off[j] = off;
-    off += align_up((size_t)N * 3 * p.Hs[j] * p.Ws[j], 64);
-    p.fa.scale_off[j] = pairs;
-    p.fa.scale_cnt[j] = 3 * p.tx[j] * p.ty[j];
-    p.fa.pos[j] = 3.0 * (double)(p.Hs[j] - kHalo) * (double)(p.Ws[j] - kHalo);
-    pairs += (long long)N * p.fa.scale_cnt[j];
-  }
-  p.plane_floats = off;
+  const long long pairs = ms_geometry(N, H, W, p, p.fa);
   p.qblocks = metrics_quant_blocks((long long)H * W);
   p.fa.qblocks = p.qblocks;
   p.fa.count = 3.0 * (double)H * (double)W;
@@ -366,17 +253,8 @@ static void metrics_plan(int N, int H, int W, MetricsPlan& p) {
   p.bytes = p.off_spartial + align_up((size_t)pairs * 2 * sizeof(double), 256);
 }
 
-static const char* metrics_shape_error(int N, int H, int W, int C) {
-  if (N <= 0 || H <= 0 || W <= 0) return "eval_metrics: bad shape";
-  if (C != 3) return "eval_metrics: 3 channels only";
-  if (H < 176 || W < 176) return "eval_metrics: the shorter side must be at least 176 (five MS-SSIM scales of an 11x11 window)";
-  if ((long long)N * 3 > 65535) return "eval_metrics: more than 21845 images per call";
-  if ((long long)H * W > (1LL << 28)) return "eval_metrics: image beyond 2^28 pixels";
-  // grid y / x of msssim_scale_kernel at scale 1: ceil((H - 10) / 16), ceil((W - 10) / 64) tiles
-  if ((H - kHalo + kTH - 1) / kTH > 65535 || (W - kHalo + kTW - 1) / kTW > 65535) return "eval_metrics: image side beyond the tile grid";
-  return nullptr;
-}
-
+// the tile grid: msssim_scale_kernel at scale 1, ceil((H - 10) / 16) x ceil((W - 10) / 64) tiles
+static const char* metrics_shape_error(int N, int H, int W, int C) { return ms_shape_error(N, H, W, C, kHalo); }
 
 static size_t cls_partial_bytes(int N, int qblocks, int n_classes) {
   return align_up((size_t)N * qblocks * (n_classes + 1) * 3 * sizeof(unsigned long long), 256);
@@ -389,7 +267,8 @@ static int metrics_run(int32_t dtype_fake, int32_t dtype_real, int32_t N, int32_
   JPDSE_REQUIRE(dtype_fake == JPDSE_F32 || dtype_fake == JPDSE_BF16, "eval_metrics: fake must be fp32 or bf16");
   JPDSE_REQUIRE(dtype_real == JPDSE_F32, "eval_metrics: real must be fp32");
   JPDSE_REQUIRE(fake && real && mean && std && out, "eval_metrics: null argument");
-  if (const char* msg = metrics_shape_error(N, H, W, C)) return set_error(JPDSE_EINVAL, "%s (N %d, H %d, W %d, C %d)", msg, N, H, W, C);
+  if (const char* msg = metrics_shape_error(N, H, W, C))
+    return set_error(JPDSE_EINVAL, "eval_metrics: %s (N %d, H %d, W %d, C %d)", msg, N, H, W, C);
   MetricsPlan p;
   metrics_plan(N, H, W, p);
   const size_t need = p.bytes + (label ? cls_partial_bytes(N, p.qblocks, n_classes) : 0);
@@ -405,16 +284,7 @@ static int metrics_run(int32_t dtype_fake, int32_t dtype_real, int32_t N, int32_
 
   QuantParams qp = {};
   for (int c = 0; c < 3; ++c) { qp.mean[c] = mean[c]; qp.std[c] = std[c]; }
-  GaussWin g;
-  {
-    double w[kWin], sum = 0.0;
-    for (int k = 0; k < kWin; ++k) {
-      const double d = k - (kWin - 1) / 2;
-      w[k] = exp(-d * d / (2.0 * 1.5 * 1.5));
-      sum += w[k];
-    }
-    for (int k = 0; k < kWin; ++k) g.w[k] = (float)(w[k] / sum);
-  }
+  const GaussWin g = gauss_window();
   const double c1 = (0.01 * 255.0) * (0.01 * 255.0), c2 = (0.03 * 255.0) * (0.03 * 255.0);
   const long long HW = (long long)H * W;
   const int cs = cpad(C);

@@ -2,14 +2,15 @@
 // (u = v * std_c + mean_c, L = 1, C1 = 1e-4, C2 = 9e-4) and its gradient w.r.t. the generator's output.  Entry point:
 // include/jpdse.h, "MS-SSIM training loss"; definition and derivation: DESIGN.md 4.6.  The structure is that of the
 // evaluation pass (metrics.hip): 11x11 Gaussian window (sigma 1.5, "valid"), five scales linked by a 2x2
-// mean, per channel.  This file shares no device code with metrics.hip, whose code object stays as it was.
+// mean, per channel.  The window, the tile geometry, the centred staging, the separable filter up to the filtered moments,
+// the downsample, the block sum and the host geometry are those of metrics.hip, from msssim_core.h; the per-position
+// arithmetic is this file's own (unfused throughout; jpdse_eval_metrics' differs in its bits, which are a contract).
 //
 // Kernels, in launch order (forward: 11 launches, with the gradient: 22):
 //   msl_planes_kernel      fake, real (NHWC) -> planar fp32 planes of u, [N][3][H][W] (scale 1)
 //   msl_scale_kernel<0>    one per scale: LDS tile + halo, separable 11-tap filter of x, y, x^2, y^2, xy, cs / ssim per
-//                          position, one (cs, ssim) partial pair per block (the tile shape and row access of
-//                          msssim_scale_kernel)
-//   msl_down_kernel        2x2 mean -> next scale's planes
+//                          position, one (cs, ssim) partial pair per block
+//   msssim_down_kernel     2x2 mean -> next scale's planes (msssim_core.h)
 //   msl_final_kernel       partials -> per-scale means, ms_ssim_n and the factors a_j / positions_j per image, in a fixed
 //                          order; writes the loss slot
 //   msl_scale_kernel<1|2>  (gradient) the same filter again, now writing three coefficient maps per position on the valid
@@ -26,19 +27,12 @@
 // bit for bit and a constant tile variance exactly 0.  The coefficient maps themselves are absolute quantities (partials
 // w.r.t. the un-shifted moments), so the back-correlation is not centred; its cancellation is eps_fp32 * mu / contrast.
 // The filters run in fp32; the per-position cs / ssim, the coefficients and every sum over positions are fp64.
-#include "common.h"
+#include "msssim_core.h"
 
 namespace jpdse {
 
-constexpr int kScales = 5;
-constexpr int kWin = 11;                 // window taps
-constexpr int kHalo = kWin - 1;
-constexpr int kTW = 64, kTH = 16;        // outputs per block: one wave per 64-wide row, four rows per wave
-constexpr int kSW = kTW + kHalo;         // staged columns (74)
-constexpr int kSH = kTH + kHalo;         // staged rows (26)
 constexpr int kStats = 11;               // per image: cs_1..5, ssim_1..5, ms_ssim
 
-struct MslWin { float w[kWin]; };
 struct MslNorm { float mean[3]; float std[3]; };
 
 // fake, real: NHWC [N][H][W][8] of T; one thread per pixel; planes x (fake) / y (real): [N][3][HW] of u = v * std + mean
@@ -66,7 +60,7 @@ __global__ __launch_bounds__(256) void msl_planes_kernel(const T* __restrict__ f
 // d/d E[xy]) of fac * cs (1) or fac * ssim (2).
 template <int kMode>
 __global__ __launch_bounds__(256) void msl_scale_kernel(const float* __restrict__ x, const float* __restrict__ y, int Hs, int Ws,
-                                                       MslWin g, double c1, double c2, double* __restrict__ partial,
+                                                       GaussWin g, double c1, double c2, double* __restrict__ partial,
                                                        const double* __restrict__ fac, int scale, float* __restrict__ coef,
                                                        long long map_stride) {
   __shared__ float sx[kSH][kSW];
@@ -76,67 +70,18 @@ __global__ __launch_bounds__(256) void msl_scale_kernel(const float* __restrict_
   const int Ho = Hs - kHalo, Wo = Ws - kHalo;
   const int x0 = blockIdx.x * kTW, y0 = blockIdx.y * kTH;
   const long long plane = (long long)blockIdx.z * Hs * Ws;
-  const float* xp = x + plane;
-  const float* yp = y + plane;
-  // pivots: the tile's first pixel (always inside the plane: x0 < Wo, y0 < Ho)
-  const float pvx = xp[(long long)y0 * Ws + x0];
-  const float pvy = yp[(long long)y0 * Ws + x0];
-  for (int i = threadIdx.x; i < kSH * kSW; i += 256) {
-    const int r = i / kSW, c = i - r * kSW;
-    const int gy = y0 + r, gx = x0 + c;
-    float vx = 0.f, vy = 0.f;            // outside the plane: only feeds positions that are masked out below
-    if (gy < Hs && gx < Ws) {
-      vx = xp[(long long)gy * Ws + gx] - pvx;
-      vy = yp[(long long)gy * Ws + gx] - pvy;
-    }
-    sx[r][c] = vx;
-    sy[r][c] = vy;
-  }
-  __syncthreads();
-  // horizontal pass: 26 rows x 64 columns, one row per wave and iteration
-  for (int i = threadIdx.x; i < kSH * kTW; i += 256) {
-    const int r = i >> 6, c = i & 63;
-    float ax = 0.f, ay = 0.f, axx = 0.f, ayy = 0.f, axy = 0.f;
-#pragma unroll
-    for (int k = 0; k < kWin; ++k) {
-      const float a = sx[r][c + k], b = sy[r][c + k], w = g.w[k];
-      const float wa = w * a, wb = w * b;
-      ax += wa;
-      ay += wb;
-      axx = fmaf(wa, a, axx);
-      ayy = fmaf(wb, b, ayy);
-      axy = fmaf(wa, b, axy);
-    }
-    hq[0][r][c] = ax;
-    hq[1][r][c] = ay;
-    hq[2][r][c] = axx;
-    hq[3][r][c] = ayy;
-    hq[4][r][c] = axy;
-  }
-  __syncthreads();
-  // vertical pass: thread = (column, group of 4 output rows); 14 filtered rows feed its 4 outputs per quantity
-  const int c = threadIdx.x & 63, r0 = (threadIdx.x >> 6) * 4;
-  float acc[5][4];
-#pragma unroll
-  for (int q = 0; q < 5; ++q) {
-    float v[4 + kHalo];
-#pragma unroll
-    for (int j = 0; j < 4 + kHalo; ++j) v[j] = hq[q][r0 + j][c];
-#pragma unroll
-    for (int o = 0; o < 4; ++o) {
-      float a = 0.f;
-#pragma unroll
-      for (int k = 0; k < kWin; ++k) a = fmaf(g.w[k], v[o + k], a);
-      acc[q][o] = a;
-    }
-  }
+  float pvx, pvy, acc[5][4];          // pivots; filtered x, y, x^2, y^2, xy of the thread's 4 positions
+  stage_centred(x + plane, y + plane, Hs, Ws, x0, y0, sx, sy, pvx, pvy);
+  horizontal_pass5(sx, sy, g, hq);
+  vertical_pass<5>(hq, g, acc);
+  const int c = threadIdx.x & 63, r0 = (threadIdx.x >> 6) * 4;   // acc[q][o] is position (r0 + o, c): must match vertical_pass
   double f = 0.0;
-  if constexpr (kMode != 0) f = fac[(blockIdx.z / 3) * kScales + scale];
+  if constexpr (kMode != 0) f = fac[(blockIdx.z / 3) * kMsScales + scale];
   double scs = 0.0, sss = 0.0;
 #pragma unroll
   for (int o = 0; o < 4; ++o) {
     if (x0 + c < Wo && y0 + r0 + o < Ho) {
-      // unfused throughout, so that identical images give numerator == denominator bit for bit
+      // own epilogue, not metrics.hip's: unfused throughout, so that identical images give numerator == denominator bit for bit
       const double mx = acc[0][o], my = acc[1][o];
       const double vxx = __dsub_rn((double)acc[2][o], __dmul_rn(mx, mx));
       const double vyy = __dsub_rn((double)acc[3][o], __dmul_rn(my, my));
@@ -174,44 +119,16 @@ __global__ __launch_bounds__(256) void msl_scale_kernel(const float* __restrict_
     }
   }
   if constexpr (kMode == 0) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      scs += __shfl_xor(scs, off, 64);
-      sss += __shfl_xor(sss, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-      red[0][threadIdx.x >> 6] = scs;
-      red[1][threadIdx.x >> 6] = sss;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
+    if (block_sum_pair(scs, sss, red)) {
       double* o = partial + (((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 2;
-      o[0] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-      o[1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+      o[0] = scs;
+      o[1] = sss;
     }
   }
 }
 
-// 2x2 mean, stride 2, odd last row / column dropped; one thread per output, both planes
-__global__ __launch_bounds__(256) void msl_down_kernel(const float* __restrict__ x, const float* __restrict__ y, int Hs, int Ws,
-                                                      float* __restrict__ ox, float* __restrict__ oy, long long total) {
-  const int Hd = Hs >> 1, Wd = Ws >> 1;
-  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-    const int cx = (int)(i % Wd);
-    const long long t = i / Wd;
-    const int cy = (int)(t % Hd);
-    const long long nc = t / Hd;
-    const long long s = (nc * Hs + 2 * cy) * Ws + 2 * cx;
-    ox[i] = ((x[s] + x[s + 1]) + (x[s + Ws] + x[s + Ws + 1])) * 0.25f;
-    oy[i] = ((y[s] + y[s + 1]) + (y[s + Ws] + y[s + Ws + 1])) * 0.25f;
-  }
-}
-
-struct MslFinalArgs {
-  long long scale_off[kScales];   // first partial pair of the scale (in pairs), image 0
-  int scale_cnt[kScales];         // pairs per image (3 channels x tiles)
-  double pos[kScales];            // 3 * Ho * Wo: positions behind a per-scale mean
-  double weight[kScales];
+struct MslFinalArgs : MsPartials {
+  double weight[kMsScales];
   int N;
 };
 
@@ -223,48 +140,38 @@ __global__ __launch_bounds__(256) void msl_final_kernel(const double* __restrict
   __shared__ double red[2][4];
   double loss = 0.0;                     // thread 0 only
   for (int n = 0; n < fa.N; ++n) {
-    double mean[kScales], ssim5 = 0.0;   // thread 0 only: cs_1..5
-    for (int j = 0; j < kScales; ++j) {
+    double mean[kMsScales], ssim5 = 0.0; // thread 0 only: cs_1..5
+    for (int j = 0; j < kMsScales; ++j) {
       double a = 0.0, b = 0.0;
       const double* p = spartial + (fa.scale_off[j] + (long long)n * fa.scale_cnt[j]) * 2;
       for (int i = threadIdx.x; i < fa.scale_cnt[j]; i += 256) {
         a += p[2 * i];
         b += p[2 * i + 1];
       }
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-        a += __shfl_xor(a, off, 64);
-        b += __shfl_xor(b, off, 64);
-      }
-      if ((threadIdx.x & 63) == 0) {
-        red[0][threadIdx.x >> 6] = a;
-        red[1][threadIdx.x >> 6] = b;
-      }
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        const double cs = ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) / fa.pos[j];
-        const double ss = ((red[1][0] + red[1][1]) + (red[1][2] + red[1][3])) / fa.pos[j];
+      if (block_sum_pair(a, b, red)) {
+        const double cs = a / fa.pos[j];
+        const double ss = b / fa.pos[j];
         mean[j] = cs;
-        if (j == kScales - 1) ssim5 = ss;
+        if (j == kMsScales - 1) ssim5 = ss;
         if (stats) {
           stats[(long long)n * kStats + j] = cs;
-          stats[(long long)n * kStats + kScales + j] = ss;
+          stats[(long long)n * kStats + kMsScales + j] = ss;
         }
       }
       __syncthreads();
     }
     if (threadIdx.x == 0) {
-      mean[kScales - 1] = ssim5;         // the five means of the product: cs_1..4, ssim_5
+      mean[kMsScales - 1] = ssim5;       // the five means of the product: cs_1..4, ssim_5
       bool positive = true;
-      for (int j = 0; j < kScales; ++j) positive = positive && mean[j] > 0.0;
+      for (int j = 0; j < kMsScales; ++j) positive = positive && mean[j] > 0.0;
       double ms = 0.0;
       if (positive) {
         ms = 1.0;
-        for (int j = 0; j < kScales; ++j) ms *= pow(mean[j], fa.weight[j]);
+        for (int j = 0; j < kMsScales; ++j) ms *= pow(mean[j], fa.weight[j]);
       }
-      for (int j = 0; j < kScales; ++j)
-        fac[(long long)n * kScales + j] = positive ? fa.weight[j] * ms / mean[j] / fa.pos[j] : 0.0;
-      if (stats) stats[(long long)n * kStats + 2 * kScales] = ms;
+      for (int j = 0; j < kMsScales; ++j)
+        fac[(long long)n * kMsScales + j] = positive ? fa.weight[j] * ms / mean[j] / fa.pos[j] : 0.0;
+      if (stats) stats[(long long)n * kStats + 2 * kMsScales] = ms;
       loss += 1.0 - ms;
     }
   }
@@ -278,7 +185,7 @@ __global__ __launch_bounds__(256) void msl_final_kernel(const double* __restrict
 // LDS: 3 staged maps (23.1 KB) + 3 horizontally filtered ones (20.0 KB); row accesses as in msl_scale_kernel.
 __global__ __launch_bounds__(256) void msl_back_kernel(const float* __restrict__ coef, long long map_stride,
                                                       const float* __restrict__ x, const float* __restrict__ y, int Hs, int Ws,
-                                                      MslWin g, const float* __restrict__ up, int Hu, int Wu,
+                                                      GaussWin g, const float* __restrict__ up, int Hu, int Wu,
                                                       float* __restrict__ dst) {
   __shared__ float sg[3][kSH][kSW];
   __shared__ float hg[3][kSH][kTW];
@@ -316,21 +223,9 @@ __global__ __launch_bounds__(256) void msl_back_kernel(const float* __restrict__
     hg[2][r][c] = d;
   }
   __syncthreads();
-  const int c = threadIdx.x & 63, r0 = (threadIdx.x >> 6) * 4;
   float acc[3][4];
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    float v[4 + kHalo];
-#pragma unroll
-    for (int j = 0; j < 4 + kHalo; ++j) v[j] = hg[q][r0 + j][c];
-#pragma unroll
-    for (int o = 0; o < 4; ++o) {
-      float a = 0.f;
-#pragma unroll
-      for (int k = 0; k < kWin; ++k) a = fmaf(g.w[k], v[o + k], a);
-      acc[q][o] = a;
-    }
-  }
+  vertical_pass<3>(hg, g, acc);
+  const int c = threadIdx.x & 63, r0 = (threadIdx.x >> 6) * 4;   // acc[q][o] is position (r0 + o, c): must match vertical_pass
   const int gx = x0 + c;
   if (gx >= Ws) return;
 #pragma unroll
@@ -366,45 +261,41 @@ __global__ __launch_bounds__(256) void msl_pack_kernel(const float* __restrict__
 }
 
 // ---- host side: geometry and workspace layout -------------------------------------------------------------------------------
-struct MslPlan {
-  int Hs[kScales], Ws[kScales], tx[kScales], ty[kScales];
-  size_t plane_off[kScales];       // floats, from the start of the x planes (the y and gradient planes have the same layout)
-  size_t plane_floats;             // all scales, one image of the pair
+struct MslPlan : MsGeometry {
   size_t map_floats;               // one coefficient map of scale 1 (the largest)
   size_t off_y, off_spartial, off_fac, off_coef, off_grad, bytes;
   MslFinalArgs fa;
 };
 
 static void msl_plan(int N, int H, int W, bool with_grad, MslPlan& p) {
-  static const double kWeights[kScales] = {0.0448, 0.2856, 0.3001, 0.2363, 0.1333};
-  size_t off = 0;
-  long long pairs = 0;
-  for (int j = 0; j < kScales; ++j) {
-    p.Hs[j] = H >> j;
-    p.Ws[j] = W >> j;
-    p.tx[j] = (p.Ws[j] - kHalo + kTW - 1) / kTW;
-    p.ty[j] = (p.Hs[j] - kHalo + kTH - 1) / kTH;
-    p.plane_off[j] = off;
-    off += align_up((size_t)N * 3 * p.Hs[j] * p.Ws[j], 64);
-    p.fa.scale_off[j] = pairs;
-    p.fa.scale_cnt[j] = 3 * p.tx[j] * p.ty[j];
-    p.fa.pos[j] = 3.0 * (double)(p.Hs[j] - kHalo) * (double)(p.Ws[j] - kHalo);
-    p.fa.weight[j] = kWeights[j];
-    pairs += (long long)N * p.fa.scale_cnt[j];
-  }
+  const long long pairs = ms_geometry(N, H, W, p, p.fa);
+  for (int j = 0; j < kMsScales; ++j) p.fa.weight[j] = kMsWeights[j];
   p.fa.N = N;
-  p.plane_floats = off;
   p.map_floats = align_up((size_t)N * 3 * (H - kHalo) * (W - kHalo), 64);
   p.off_y = align_up(p.plane_floats * sizeof(float), 256);
   p.off_spartial = 2 * p.off_y;
   p.off_fac = p.off_spartial + align_up((size_t)pairs * 2 * sizeof(double), 256);
-  p.off_coef = p.off_fac + align_up((size_t)N * kScales * sizeof(double), 256);
+  p.off_coef = p.off_fac + align_up((size_t)N * kMsScales * sizeof(double), 256);
   p.off_grad = p.off_coef;
   p.bytes = p.off_coef;
   if (with_grad) {
     p.off_grad = p.off_coef + align_up(3 * p.map_floats * sizeof(float), 256);
     p.bytes = p.off_grad + p.off_y;
   }
+}
+
+// the tile grid: msl_back_kernel at scale 1 covers the full plane, ceil(H / 16) x ceil(W / 64) tiles
+static const char* msl_shape_error(int N, int H, int W, int C) { return ms_shape_error(N, H, W, C, 0); }
+
+// everything that can be refused before any launch
+static int msl_check(const jpdse_msssim_loss_args* a) {
+  JPDSE_REQUIRE(a != nullptr, "msssim_loss: null argument struct");
+  JPDSE_REQUIRE(!bad_dtype(a->dtype), "msssim_loss: bad dtype %d (fake and real are both fp32 or both bf16)", a->dtype);
+  JPDSE_REQUIRE(a->fake && a->real && a->mean && a->std && a->out, "msssim_loss: null argument");
+  if (const char* msg = msl_shape_error(a->N, a->H, a->W, a->C))
+    return set_error(JPDSE_EINVAL, "msssim_loss: %s (N %d, H %d, W %d, C %d)", msg, a->N, a->H, a->W, a->C);
+  JPDSE_REQUIRE(a->dfake == nullptr || a->scale == a->scale, "msssim_loss: scale is NaN");
+  return JPDSE_OK;
 }
 
 }  // namespace jpdse
@@ -414,14 +305,14 @@ using namespace jpdse;
 extern "C" {
 
 size_t jpdse_msssim_loss_workspace_size(int32_t N, int32_t H, int32_t W, int32_t C, int32_t with_grad) {
-  if (msssim_loss_shape_error(N, H, W, C)) return 0;
+  if (msl_shape_error(N, H, W, C)) return 0;
   MslPlan p;
   msl_plan(N, H, W, with_grad != 0, p);
   return p.bytes;
 }
 
 int jpdse_msssim_loss(const jpdse_msssim_loss_args* a) {
-  if (int rc = msssim_loss_check(a)) return rc;
+  if (int rc = msl_check(a)) return rc;
   const int N = a->N, H = a->H, W = a->W;
   const bool with_grad = a->dfake != nullptr;
   MslPlan p;
@@ -440,16 +331,7 @@ int jpdse_msssim_loss(const jpdse_msssim_loss_args* a) {
 
   MslNorm nm;
   for (int c = 0; c < 3; ++c) { nm.mean[c] = (float)a->mean[c]; nm.std[c] = (float)a->std[c]; }
-  MslWin g;
-  {
-    double w[kWin], sum = 0.0;
-    for (int k = 0; k < kWin; ++k) {
-      const double d = k - (kWin - 1) / 2;
-      w[k] = exp(-d * d / (2.0 * 1.5 * 1.5));
-      sum += w[k];
-    }
-    for (int k = 0; k < kWin; ++k) g.w[k] = (float)(w[k] / sum);
-  }
+  const GaussWin g = gauss_window();
   const double c1 = 0.01 * 0.01, c2 = 0.03 * 0.03;
   const long long HW = (long long)H * W, total = (long long)N * HW;
 
@@ -459,15 +341,15 @@ int jpdse_msssim_loss(const jpdse_msssim_loss_args* a) {
                          total, nm, px, py);
       }))
     return rc;
-  for (int j = 0; j < kScales; ++j) {
+  for (int j = 0; j < kMsScales; ++j) {
     const float* xj = px + p.plane_off[j];
     const float* yj = py + p.plane_off[j];
     if (int rc = launch256("msssim_loss(scale)", msl_scale_kernel<0>, dim3(p.tx[j], p.ty[j], N * 3), a->stream, xj, yj, p.Hs[j],
                            p.Ws[j], g, c1, c2, spartial + p.fa.scale_off[j] * 2, nullptr, j, nullptr, 0))
       return rc;
-    if (j + 1 < kScales) {
+    if (j + 1 < kMsScales) {
       const long long n_down = (long long)N * 3 * p.Hs[j + 1] * p.Ws[j + 1];
-      if (int rc = ew_launch("msssim_loss(downsample)", msl_down_kernel, n_down, a->stream, xj, yj, p.Hs[j], p.Ws[j],
+      if (int rc = ew_launch("msssim_loss(downsample)", msssim_down_kernel, n_down, a->stream, xj, yj, p.Hs[j], p.Ws[j],
                              px + p.plane_off[j + 1], py + p.plane_off[j + 1], n_down))
         return rc;
     }
@@ -476,15 +358,15 @@ int jpdse_msssim_loss(const jpdse_msssim_loss_args* a) {
     return rc;
   if (!with_grad) return JPDSE_OK;
 
-  for (int j = kScales - 1; j >= 0; --j) {
+  for (int j = kMsScales - 1; j >= 0; --j) {
     const float* xj = px + p.plane_off[j];
     const float* yj = py + p.plane_off[j];
     const long long stride = (long long)N * 3 * (p.Hs[j] - kHalo) * (p.Ws[j] - kHalo);
-    auto* coef_kernel = j == kScales - 1 ? msl_scale_kernel<2> : msl_scale_kernel<1>;
+    auto* coef_kernel = j == kMsScales - 1 ? msl_scale_kernel<2> : msl_scale_kernel<1>;
     if (int rc = launch256("msssim_loss(coefficients)", coef_kernel, dim3(p.tx[j], p.ty[j], N * 3), a->stream, xj, yj, p.Hs[j],
                            p.Ws[j], g, c1, c2, nullptr, fac, j, coef, stride))
       return rc;
-    const bool top = j == kScales - 1;
+    const bool top = j == kMsScales - 1;
     const float* up = top ? nullptr : grad + p.plane_off[j + 1];
     if (int rc = launch256("msssim_loss(back)", msl_back_kernel, dim3((p.Ws[j] + kTW - 1) / kTW, (p.Hs[j] + kTH - 1) / kTH, N * 3),
                            a->stream, coef, stride, xj, yj, p.Hs[j], p.Ws[j], g, up, top ? 0 : p.Hs[j + 1], top ? 0 : p.Ws[j + 1],
