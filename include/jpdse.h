@@ -40,8 +40,8 @@ extern "C" {
                                 * (jpdse_code_import), and the MS-SSIM training loss (jpdse_msssim_loss[_workspace_size]), and the input
                                 * builder for more than 64 storage channels (jpdse_input_builder_wide), and the entropy-coded bitstream
                                 * (jpdse_code_entropy_*), and the coded label and instance maps (jpdse_semantics_*), and the
-                                * context-model rate term (jpdse_code_rate_loss[_workspace_size]): purely additive, nothing
-                                * existing changed */
+                                * context-model rate term (jpdse_code_rate_loss[_workspace_size]), and the semantics-weighted
+                                * distortion (jpdse_sem_weighted_loss): purely additive, nothing existing changed */
 
 enum { JPDSE_F32 = 0, JPDSE_BF16 = 1 };
 enum { JPDSE_PAD_ZERO = 0, JPDSE_PAD_REFLECT = 1 };
@@ -578,6 +578,47 @@ typedef struct jpdse_code_rate_args {
   void* stream;
 } jpdse_code_rate_args;
 int jpdse_code_rate_loss(const jpdse_code_rate_args* args);
+
+/* ---- semantics-weighted distortion: --class_distortion_weights / --edge_distortion_weight (no reference counterpart;
+ * DESIGN.md 4.11) ----------------------------------------------------------------------------------------------------------
+ * The l1 / mse training distortion with a weight per pixel taken from the label and instance maps, and its gradient, in one
+ * pass.  fake, real, dfake: NHWC [N][H][W][CPAD(C)] in `dtype` (padding lanes zero).
+ *   w(p)   = table[label(p)] * (edge_w if edge(p) else 1)
+ *            label(p) is truncated toward zero; a value outside [0, n_table) -- negative, >= n_table, NaN -- has weight 1
+ *   edge(p): the id of p differs from the id of its left, right, upper or lower neighbour inside the same image (no wrap
+ *            from a row's end to the next row, no neighbour across the image border or across images; the rule of the
+ *            reference's get_edges, pix2pixHD_model.py:774-783).  Ids are compared as 64-bit integers.
+ *   out[0] = sum_p sum_c w(p) f(d) / (N H W C),  d = fake - real,  f(d) = |d| (JPDSE_SEM_L1) or d^2 (JPDSE_SEM_MSE)
+ *   dfake  = scale * w(p) * sign(d) / (N H W C)  (l1; sign(0) = 0 as jpdse_l1_fwd_bwd)   or   scale * w(p) * 2 d / (N H W C)
+ * The normaliser is the element count, not sum w: a table of ones with edge_w = 1 IS jpdse_l1_fwd / jpdse_mse_fwd, and dfake
+ * is then bit-identical to jpdse_l1_fwd_bwd's / jpdse_mse_bwd's (*gout = 1).  inst == NULL or edge_w == 1: no edge term, the ids
+ * are not read.  `table` is a HOST array of n_table floats, copied into the launch.  `out` is a DEVICE fp32 slot written by
+ * the call's own final kernel (no jpdse_loss_finalize term).  The arithmetic is fp32, the sum over block partials fp64; the
+ * grid and every order of summation are fixed and there are no atomics: two calls on the same buffers give bit-identical
+ * out and dfake.  ws: jpdse_loss_workspace_size() bytes.
+ * JPDSE_EINVAL before any launch: a NULL args, fake, real, label, table or out; a bad dtype or kind; a non-positive extent or
+ * N * H * W >= 2^31; n_table outside 1 .. JPDSE_SEM_TABLE; a table entry or edge_w that is negative or not finite; a NaN
+ * scale with dfake; a workspace that is missing or too small. */
+#define JPDSE_SEM_TABLE 256
+enum { JPDSE_SEM_L1 = 0, JPDSE_SEM_MSE = 1 };
+typedef struct jpdse_sem_loss_args {
+  int32_t dtype, N, H, W, C;
+  int32_t kind;        /* JPDSE_SEM_L1 or JPDSE_SEM_MSE */
+  const void* fake;
+  const void* real;
+  const float* label;  /* device float32 [N][H][W] */
+  const int64_t* inst; /* device int64 [N][H][W], or NULL: no edge term */
+  const float* table;  /* host, n_table floats: the class weights of labels 0 .. n_table - 1 */
+  int32_t n_table;
+  float edge_w;
+  float scale;         /* read when dfake != NULL */
+  float* out;          /* device fp32 slot */
+  void* dfake;         /* device, fake's shape and dtype, or NULL: value only */
+  void* ws;
+  size_t ws_bytes;
+  void* stream;
+} jpdse_sem_loss_args;
+int jpdse_sem_weighted_loss(const jpdse_sem_loss_args* args);
 
 /* ---- optimizer ---------------------------------------------------------------------- */
 /* torch.optim.Adam (model.py:275,279) over a table of tensors, one launch.  `table` is a

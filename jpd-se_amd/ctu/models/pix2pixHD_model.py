@@ -35,6 +35,38 @@ from ctu.models.pix2pixHD_networks import networks
 LOSS_NAMES = ('G_GAN', 'G_GAN_Feat', 'G_VGG', 'G_Distortion', 'D_real', 'D_fake')
 
 
+def parse_class_distortion_weights(text, n_labels):
+  """--class_distortion_weights: 'label:weight,label:weight,...' -> the table [cw[0], ..., cw[n_labels - 1]],
+  1.0 for a label that is not named.  ValueError for malformed text, a label that is not an integer in [0, n_labels), a
+  duplicate label, or a weight that is negative or not finite."""
+  table = [1.0] * n_labels
+  text = (text or '').strip()
+  if not text:
+    return table
+  seen = set()
+  for pair in text.split(','):
+    parts = pair.split(':')
+    if len(parts) != 2:
+      raise ValueError('class_distortion_weights: %r is not a label:weight pair (expected e.g. "24:4,26:2")' % (pair,))
+    try:
+      label = int(parts[0].strip())
+    except ValueError:
+      raise ValueError('class_distortion_weights: the label %r is not an integer' % (parts[0],))
+    try:
+      weight = float(parts[1].strip())
+    except ValueError:
+      raise ValueError('class_distortion_weights: the weight %r of label %d is not a number' % (parts[1], label))
+    if not 0 <= label < n_labels:
+      raise ValueError('class_distortion_weights: label %d is outside [0, %d)' % (label, n_labels))
+    if label in seen:
+      raise ValueError('class_distortion_weights: label %d is named twice' % label)
+    if not (weight >= 0.0 and weight != float('inf')):
+      raise ValueError('class_distortion_weights: the weight of label %d must be a finite number >= 0, got %r' % (label, parts[1]))
+    seen.add(label)
+    table[label] = weight
+  return table
+
+
 class Pix2PixHDModel(BaseModel):
 
   @staticmethod
@@ -43,7 +75,7 @@ class Pix2PixHDModel(BaseModel):
     (pinned by tests/golden/option_setter_flags.json, dumped from the reference), so that a reference command line or
     opt.pkl parses unchanged; flags of branches outside the accelerated path are accepted here and refused in
     __init__ when they would change the computation.  Extensions: --compute_dtype, --skip_unused_losses,
-    --vgg19_state_dict, --vgg_random_init, --lambda_rate."""
+    --vgg19_state_dict, --vgg_random_init, --lambda_rate, --class_distortion_weights, --edge_distortion_weight."""
     a = parser.add_argument
     a('--num_D', type=int, default=2)
     a('--n_layers_D', type=int, default=3)
@@ -123,6 +155,15 @@ class Pix2PixHDModel(BaseModel):
       help='extension (DESIGN.md 4.10): weight of the rate term in the generator / encoder loss -- the expected length of the '
            'code under a static form of the entropy coder\'s context model, in bits per pixel; needs the learned codec with '
            'encoder binarization; 0 (default): no rate term, the step is what it was')
+    a('--class_distortion_weights', type=str, default='',
+      help='extension (DESIGN.md 4.11): comma-separated label:weight pairs, e.g. "24:4,26:2": the l1 / mse training distortion '
+           'of a pixel is multiplied by the weight of its class; a class that is not named has weight 1.  The loss is still '
+           'divided by the element count, not by the sum of the weights, so all-ones weights are the reference loss: rescale '
+           'with --lambda_distortion.  Default: no weights, the step is what it was')
+    a('--edge_distortion_weight', type=float, default=1.0,
+      help='extension (DESIGN.md 4.11): the distortion of a pixel on an instance edge (its instance id differs from a '
+           '4-neighbour\'s; the dataset\'s own map, also under --zero_ins) is multiplied by this on top of its class weight; '
+           'same normaliser as --class_distortion_weights (rescale with --lambda_distortion).  1 (default): no edge term')
     a('--vgg_random_init', action='store_true',
       help='extension: explicitly accept a seeded random-weight VGG19 for the VGG loss (tests, benchmarks); without '
            'this flag training with the VGG loss and no --vgg19_state_dict is refused')
@@ -165,6 +206,22 @@ class Pix2PixHDModel(BaseModel):
     if self.lambda_rate > 0.0 and (not feat_enc or g('no_encoder_binarization') or g('zero_vis')):
       raise ValueError('lambda_rate > 0 needs the learned codec with encoder binarization (--no_feat_encoding and '
                        '--no_encoder_binarization must both be off) and an encoder that runs (no --zero_vis)')
+    # semantics-weighted distortion: (class table, edge weight), or None when every weight is 1 -- the
+    # step then takes the plain l1 / mse path
+    n_onehot = opt.num_labels + 1 if g('contain_dontcare_label') else opt.num_labels
+    table = parse_class_distortion_weights(g('class_distortion_weights', ''), min(n_onehot, ops.SEM_TABLE))
+    edge_w = g('edge_distortion_weight', 1.0)
+    edge_w = 1.0 if edge_w is None else float(edge_w)
+    if not (edge_w >= 0.0 and edge_w != float('inf')):
+      raise ValueError('edge_distortion_weight must be a finite number >= 0, got %r' % (g('edge_distortion_weight'),))
+    if edge_w != 1.0 and g('no_instance'):
+      raise ValueError('edge_distortion_weight != 1 needs the instance map: it cannot be combined with --no_instance')
+    self.sem_weights = None
+    if edge_w != 1.0 or any(w != 1.0 for w in table):
+      if opt.distortion_loss_fn == 'ms_ssim':
+        raise ValueError('class_distortion_weights / edge_distortion_weight weight the l1 and mse distortions only: they '
+                         'cannot be combined with --distortion_loss_fn ms_ssim')
+      self.sem_weights = (table, edge_w)
     self.opt = opt
     self.is_train = opt.is_train
     self.use_features = True
@@ -321,6 +378,10 @@ class Pix2PixHDModel(BaseModel):
       if comp is None:
         comp = self.compress(x_dict, os.path.join(opt.save_dir, 'tmp_imgs'))   # a private sub-directory per process
     label, inst = self._semantics(x_dict)
+    inst_raw = None
+    if self.sem_weights is not None and self.sem_weights[1] != 1.0:
+      # the loss weights read the dataset's own instance map: --zero_ins blanks the networks' edge lane, not the weights
+      inst_raw = inst if not self.zero_ins else x_dict['instance'].to(dev, dtype=torch.int64, non_blocking=True).contiguous()
     image = x_dict['image'].to(dev, dtype=torch.float32, non_blocking=True).contiguous()
     total_c = self.label_nc + self.feat_nc
     base = ops.onehot_edge(label, inst, self.n_onehot, total_c, self.cdtype) if build_base else None
@@ -328,7 +389,7 @@ class Pix2PixHDModel(BaseModel):
     src = real
     if comp is not None:
       src = ops.nchw_to_nhwc(comp.to(dev, dtype=torch.float32, non_blocking=True).contiguous(), self.cdtype)
-    return dict(base=base, real=real, src=src, image_nchw=image, label=label, inst=inst, total_c=total_c)
+    return dict(base=base, real=real, src=src, image_nchw=image, label=label, inst=inst, inst_raw=inst_raw, total_c=total_c)
 
   def _semantics(self, x_dict):
     """The device label and instance maps of x_dict, as the input builders read them."""
@@ -453,6 +514,28 @@ class Pix2PixHDModel(BaseModel):
     if min(h, w) < ops.MSSSIM_MIN_SIDE:
       raise ValueError('distortion_loss_fn ms_ssim: the shorter image side must be at least %d (five MS-SSIM scales of an '
                        '11x11 window), got %d x %d' % (ops.MSSSIM_MIN_SIDE, h, w))
+
+  def _sem_weighted(self, fake, real, label, inst_raw, out, scale=None):
+    """The weighted l1 / mse distortion of DESIGN.md 4.11 under the model's weights into `out`; the gradient Act when `scale`
+    is given."""
+    table, edge_w = self.sem_weights
+    return ops.sem_weighted_loss(fake, real, label, inst_raw, table, edge_w, self.opt.distortion_loss_fn, out, scale)
+
+  def get_weighted_distortion(self, x_dict):
+    """The training distortion of the eval-mode reconstruction as a Python float: un-quantised (the normalised images, as
+    G_Distortion), under the model's class and edge weights (the kernel of the train step, value only).  With
+    trivial weights the plain l1 / mse mean.  get_eval_loss / get_eval_metrics stay the unweighted, quantised figures."""
+    if self.opt.distortion_loss_fn == 'ms_ssim':
+      raise ValueError('get_weighted_distortion covers the l1 and mse distortions, not --distortion_loss_fn ms_ssim')
+    with torch.no_grad():
+      pre = self.preprocess(x_dict, build_base=not self.zero_sem)
+      fake, _ = self.netG.fwd(self._g_input_eval(pre))
+      slot = torch.zeros(1, dtype=torch.float32, device=self._device())
+      if self.sem_weights is not None:
+        self._sem_weighted(fake, pre['real'], pre['label'], pre['inst_raw'], slot)
+      else:
+        (ops.l1_fwd if self.opt.distortion_loss_fn == 'l1' else ops.mse_fwd)(fake, pre['real'], slot)
+      return float(slot.item())
 
   def get_eval_loss(self, x_dict):
     """Distortion on de-normalised, clipped, uint8-truncated images (0..255 scale), as the reference computes it on
@@ -778,12 +861,15 @@ class Pix2PixHDModel(BaseModel):
           d_dist = ops.msssim_loss_fwd_bwd(fake, real, opt.normalize_mean, opt.normalize_std, s(layout['dist']), gw['dist'])
         else:
           ops.msssim_loss_fwd(fake, real, opt.normalize_mean, opt.normalize_std, s(layout['dist']))
+      elif self.sem_weights is not None:
+        # value and, in a training step, gradient from one pass; its own final kernel writes the slot
+        d_dist = self._sem_weighted(fake, real, label, pre['inst_raw'], s(layout['dist']), gw.get('dist') or None)
       elif opt.distortion_loss_fn == 'l1' and gw.get('dist'):
         d_dist = ops.l1_fwd_bwd(fake, real, s(layout['dist']), gw['dist'])
       else:
         (ops.l1_fwd if opt.distortion_loss_fn == 'l1' else ops.mse_fwd)(fake, real, s(layout['dist']))
     state = dict(B=B, fake=fake, real=real, g_ctx=g_ctx, e_ctx=e_ctx, pred=pred, d_ctx=d_ctx, vf=vf, vr=vr, v_ctx=v_ctx,
-                 d_feat=d_feat, d_vgg=d_vgg, d_dist=d_dist)
+                 d_feat=d_feat, d_vgg=d_vgg, d_dist=d_dist, label=label, inst_raw=pre['inst_raw'])
     return state, slots, layout
 
   def _reduce_losses(self, vals, layout):
@@ -850,6 +936,10 @@ class Pix2PixHDModel(BaseModel):
         # the gradient needs the per-image means of all five scales: the op runs its forward again (the value goes to a scratch slot)
         dd = ops.msssim_loss_fwd_bwd(fake, real, opt.normalize_mean, opt.normalize_std,
                                      torch.empty(1, dtype=torch.float32, device=fake.t.device), w_dist)
+      elif self.sem_weights is not None:
+        # the forward was a value-only call: the op runs again for the gradient (the value goes to a scratch slot)
+        dd = self._sem_weighted(fake, real, state['label'], state['inst_raw'],
+                                torch.empty(1, dtype=torch.float32, device=fake.t.device), w_dist)
       else:
         fn = ops.l1_bwd if opt.distortion_loss_fn == 'l1' else ops.mse_bwd
         dd = fn(fake, real, one, w_dist)

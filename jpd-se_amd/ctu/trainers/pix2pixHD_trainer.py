@@ -144,6 +144,13 @@ class Pix2PixHDTrainer(BaseTrainer):
     self.eval()
     return self.model(x_dict, self.opt, mode='get_eval_metrics_per_class' if per_class else 'get_eval_metrics')
 
+  def get_weighted_distortion(self, x_dict):
+    """The training distortion (l1 / mse, un-quantised, normalised scale) of the eval-mode reconstruction under the model's
+    --class_distortion_weights / --edge_distortion_weight (extension), a Python float.  With trivial weights
+    the plain mean.  get_eval_loss and get_eval_metrics stay the reference's unweighted, quantised figures."""
+    self.eval()
+    return self.model.get_weighted_distortion(x_dict)
+
   def get_img(self, x_dict):
     self.eval()
     return self.model(x_dict, self.opt, mode='get_img')

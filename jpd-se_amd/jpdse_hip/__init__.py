@@ -72,6 +72,14 @@ class CodeRateArgs(ctypes.Structure):
               ('ws', ctypes.c_void_p), ('ws_bytes', ctypes.c_size_t), ('stream', ctypes.c_void_p)]
 
 
+class SemLossArgs(ctypes.Structure):
+  _fields_ = [(n, ctypes.c_int32) for n in ('dtype', 'N', 'H', 'W', 'C', 'kind')] + \
+             [('fake', ctypes.c_void_p), ('real', ctypes.c_void_p), ('label', ctypes.c_void_p), ('inst', ctypes.c_void_p),
+              ('table', ctypes.POINTER(ctypes.c_float)), ('n_table', ctypes.c_int32), ('edge_w', ctypes.c_float),
+              ('scale', ctypes.c_float), ('out', ctypes.c_void_p), ('dfake', ctypes.c_void_p), ('ws', ctypes.c_void_p),
+              ('ws_bytes', ctypes.c_size_t), ('stream', ctypes.c_void_p)]
+
+
 _P, _I32, _I64, _F, _SZ = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float,
                            ctypes.c_size_t)
 _CD, _ND = ctypes.POINTER(ConvDesc), ctypes.POINTER(InormDesc)
@@ -173,6 +181,7 @@ SIGNATURES = {
     'jpdse_msssim_loss': (_I32, [ctypes.POINTER(MsssimLossArgs)]),
     'jpdse_code_rate_workspace_size': (_SZ, [_I32, _I32, _I32, _I32]),
     'jpdse_code_rate_loss': (_I32, [ctypes.POINTER(CodeRateArgs)]),
+    'jpdse_sem_weighted_loss': (_I32, [ctypes.POINTER(SemLossArgs)]),
 }
 
 # the developer build (same sources, -DJPDSE_DEV): the shipped ABI plus include/jpdse_dev.h

@@ -9,7 +9,7 @@ import struct
 
 import torch
 
-from . import (lib, check, JpdseError, F32, BF16, ConvDesc, InormDesc, EvalMetricsSemArgs, MsssimLossArgs, CodeRateArgs, ACT_NONE, PAD_ZERO, PAD_REFLECT)
+from . import (lib, check, JpdseError, F32, BF16, ConvDesc, InormDesc, EvalMetricsSemArgs, MsssimLossArgs, CodeRateArgs, SemLossArgs, ACT_NONE, PAD_ZERO, PAD_REFLECT)
 
 
 def cpad(c):
@@ -929,6 +929,41 @@ def msssim_loss_fwd(fake, real, mean, std, out, stats=None):
 def msssim_loss_fwd_bwd(fake, real, mean, std, out, scale, stats=None):
   """msssim_loss_fwd and, from the same call, the Act scale * d out / d fake (fake's dtype and layout)."""
   return _msssim_loss(fake, real, mean, std, out, scale, stats)
+
+
+# ---- semantics-weighted distortion (sem_loss.hip; definition: DESIGN.md 4.11) --------------------------------------------------
+SEM_TABLE = 256
+SEM_KINDS = {'l1': 0, 'mse': 1}
+
+
+def sem_weighted_loss(fake, real, label, inst, table, edge_w, kind, out, scale=None):
+  """out (fp32 device slot) = sum_p sum_c w(p) f(fake - real) / (N H W C), f = |.| (kind 'l1') or (.)^2 ('mse'), with
+  w(p) = table[label(p)] * (edge_w on an instance edge, else 1) (jpdse_sem_weighted_loss).  label: float32
+  [N,H,W] device map; inst: int64 [N,H,W] device map or None (no edge term); table: up to 256 host floats, the class weights
+  of labels 0 .. len(table) - 1 (any other label has weight 1).  scale given: returns the Act scale * d out / d fake from the
+  same pass; scale None: a value-only call, returns None.  The slot is written by the call itself, also inside
+  deferred_loss_finals."""
+  assert fake.t.shape == real.t.shape and fake.C == real.C and fake.dtype == real.dtype
+  assert out.dtype == torch.float32 and out.numel() >= 1
+  if kind not in SEM_KINDS:
+    raise ValueError("sem_weighted_loss: kind must be 'l1' or 'mse', got %r" % (kind,))
+  dev = fake.t.device
+  shape = (fake.N, fake.H, fake.W)
+  assert label.dtype == torch.float32 and label.is_contiguous() and label.numel() == fake.N * fake.H * fake.W and label.device == dev, \
+      (label.dtype, tuple(label.shape), shape)
+  if inst is not None:
+    assert inst.dtype == torch.int64 and inst.is_contiguous() and inst.numel() == label.numel() and inst.device == dev, \
+        (inst.dtype, tuple(inst.shape), shape)
+  table = [float(v) for v in table]
+  tab = (ctypes.c_float * max(len(table), 1))(*table)
+  ws = _loss_ws(dev)
+  dfake = fake.empty_like() if scale is not None else None
+  args = SemLossArgs(fake.dtype, fake.N, fake.H, fake.W, fake.C, SEM_KINDS[kind], fake.t.data_ptr(), real.t.data_ptr(),
+                     label.data_ptr(), inst.data_ptr() if inst is not None else None, tab, len(table), float(edge_w),
+                     float(scale) if scale is not None else 0.0, out.data_ptr(), dfake.t.data_ptr() if dfake is not None else None,
+                     ws.data_ptr(), ws.numel() * ws.element_size(), torch.cuda.current_stream().cuda_stream)
+  check(lib().jpdse_sem_weighted_loss(ctypes.byref(args)), 'sem_weighted_loss')
+  return dfake
 
 
 # ---- learned codec: context-model rate term (code_rate.hip; definition: DESIGN.md 4.10) ----------------------------------

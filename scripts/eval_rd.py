@@ -123,6 +123,9 @@ def main():
                   help='with --codec: also report the bpp of the entropy-coded files; --roundtrip then stores and decodes those')
   ap.add_argument('--semantics', action='store_true',
                   help='with --codec --entropy --roundtrip: also store the label / instance maps as .jpds files and decode from files only')
+  ap.add_argument('--class_distortion_weights', default='',
+                  help='label:weight pairs of the training flag (DESIGN.md 4.11): also print the weighted, un-quantised distortion')
+  ap.add_argument('--edge_distortion_weight', type=float, default=1.0, help='the training flag of the same name (DESIGN.md 4.11)')
   args = ap.parse_args()
   if args.roundtrip and not args.codec:
     ap.error('--roundtrip needs --codec')
@@ -138,7 +141,8 @@ def main():
   from ctu.utils.synthetic import default_opt
   jpdse_hip.require_gpu(0)
   kw = dict(gpu_ids=[0], print_losses=False, compute_dtype=args.dtype, ngf=args.ngf, batch_size=args.batch,
-            zero_sem=args.zero_sem, zero_ins=args.zero_ins, zero_vis=args.zero_vis)
+            zero_sem=args.zero_sem, zero_ins=args.zero_ins, zero_vis=args.zero_vis,
+            class_distortion_weights=args.class_distortion_weights, edge_distortion_weight=args.edge_distortion_weight)
   if args.codec:
     kw.update(no_feat_encoding=False, no_encoder_binarization=False, feat_num=3, nef=args.ngf, n_downsample_E=4,
               encoder_binarizer_out_channels=128)
@@ -149,8 +153,9 @@ def main():
   with contextlib.redirect_stdout(sys.stderr):
     trainer = get_trainer(opt)(opt, 'test' if args.checkpoints_dir else 'train')
   keys = ('l1', 'mse', 'ms_ssim', 'psnr')
-  by_batch = dict.fromkeys(keys + ('shannon', 'actual', 'context', 'file', 'coded', 'semantics', 'total'), 0.0)
-  by_image = dict.fromkeys(keys + ('shannon', 'actual', 'context', 'file', 'coded', 'semantics', 'total'), 0.0)
+  by_batch = dict.fromkeys(keys + ('shannon', 'actual', 'context', 'file', 'coded', 'semantics', 'total', 'weighted'), 0.0)
+  by_image = dict.fromkeys(keys + ('shannon', 'actual', 'context', 'file', 'coded', 'semantics', 'total', 'weighted'), 0.0)
+  weighted = trainer.model.sem_weights is not None      # class / edge weights are set
   images, n_batches, worst_diff = 0, 0, 0.0
   class_sums = None                  # int64 [1, n_classes + 1, 3]: the raw class tables of every image so far, added up
   start = time.time()
@@ -172,6 +177,11 @@ def main():
     b = int(m['per_image']['l1'].numel())
     line = 'batch {}, recon loss (L1/MSE/MS-SSIM) {:.4f}/{:.4f}/{:.4f}, PSNR {:.3f} dB'.format(i + 1, m['l1'], m['mse'], m['ms_ssim'],
                                                                                          m['psnr'])
+    if weighted:
+      wd = trainer.get_weighted_distortion(x_dict)      # the training distortion under the weights: un-quantised, normalised scale
+      by_batch['weighted'] += wd
+      by_image['weighted'] += wd * b
+      line += ', weighted {} (un-quantised) {:.6f}'.format(opt.distortion_loss_fn, wd)
     if args.codec:
       shannon, actual = trainer.get_eval_rate(x_dict)
       shannon = float(shannon)
@@ -215,6 +225,8 @@ def main():
   def summary(head, t, n):
     line = '{} (L1/MSE/MS-SSIM) {:.4f}/{:.4f}/{:.4f}, avg PSNR {:.3f} dB'.format(head, t['l1'] / n, t['mse'] / n,
                                                                             t['ms_ssim'] / n, t['psnr'] / n)
+    if weighted:
+      line += ', avg weighted {} (un-quantised) {:.6f}'.format(opt.distortion_loss_fn, t['weighted'] / n)
     if args.codec:
       line += ', avg pre-/(estimated) post-entropy coding bpp {:.4f}/{:.4f}'.format(t['actual'] / n, t['shannon'] / n)
       line += ', avg context-model bpp {:.4f}'.format(t['context'] / n)
