@@ -41,7 +41,8 @@ extern "C" {
                                 * builder for more than 64 storage channels (jpdse_input_builder_wide), and the entropy-coded bitstream
                                 * (jpdse_code_entropy_*), and the coded label and instance maps (jpdse_semantics_*), and the
                                 * context-model rate term (jpdse_code_rate_loss[_workspace_size]), and the semantics-weighted
-                                * distortion (jpdse_sem_weighted_loss): purely additive, nothing existing changed */
+                                * distortion (jpdse_sem_weighted_loss), and the code-length map (jpdse_code_cost[_table,
+                                * _workspace_size]): purely additive, nothing existing changed */
 
 enum { JPDSE_F32 = 0, JPDSE_BF16 = 1 };
 enum { JPDSE_PAD_ZERO = 0, JPDSE_PAD_REFLECT = 1 };
@@ -578,6 +579,52 @@ typedef struct jpdse_code_rate_args {
   void* stream;
 } jpdse_code_rate_args;
 int jpdse_code_rate_loss(const jpdse_code_rate_args* args);
+
+/* ---- learned codec: code-length map and per-class rate (no reference counterpart) -------------------------
+ * The exact cost, symbol by symbol, that the adaptive model of the entropy-coded bitstream above assigns to a code.
+ * b: NHWC [N][h][w][CPAD(C)] in `dtype`.  Every (image, channel) pair is one stream of h*w symbols in raster order, bit = b > 0
+ * (an exact 0 is bit 0), with 16 adaptive 11-bit probabilities q of bit 0 starting at 1024, selected by
+ * ctx = left | up << 1 | upleft << 2 | upright << 3 and updated q -= q >> 5 (bit 1) / q += (2048 - q) >> 5 (bit 0): the model
+ * of jpdse_code_entropy_encode, statement for statement.  A symbol coded with q (before its update) costs T[q] for bit 0 and
+ * T[2048 - q] for bit 1, T[v] = round(-log2(v / 2048) * 65536) for v in 1 .. 2047 and T[0] = T[2048] = 0: integers in units
+ * of 2^-16 bit, at most T[31] = 396218 (6.05 bits).  All sums below are 64-bit integer sums of those units: order-free, two
+ * calls give identical bits.
+ *   symbol[n][y][x][c]   uint32, the cost of the symbol (LOGICAL channels, no padding lanes); optional
+ *   cell[n][y][x]        = sum_c symbol: the rate map
+ *   channel[n][c]        = sum_{y,x} symbol
+ *   class_units[n][k]    = sum over the pixels p of image n with class k of cell[n][y(p) / s][x(p) / s], s = H / h = W / w: a
+ *                          cell's units go undivided to each of its s*s pixels, the caller divides by s*s
+ *   class_pixels[n][k]   = pixels of image n with class k
+ * label: DEVICE fp32 [N][1][H][W]; the class of a pixel is jpdse_eval_metrics_sem's: its label when that is an integer in
+ * [0, n_classes), else the extra last row k = n_classes (NaN included); both class tables are [N][n_classes + 1].  So
+ * sum_k class_units[n][k] == s*s * sum cell[n] and sum_c channel[n][c] == sum cell[n], exactly.  label == NULL: no class
+ * tables; H, W, n_classes and the two class pointers are not read.
+ * The cost is the model's ideal code length, not a size: per stream |8 * stream bytes - units / 65536| <= 48 + h*w / 64 bits
+ * (DESIGN.md 4.12).
+ * JPDSE_EINVAL before any launch: a NULL args, b, cell or channel (with a label: class_units, class_pixels); a bad dtype; a
+ * non-positive extent; w > 4096 (the walk keeps a row's bits in LDS, as the encoder does); N > 65535, C > 64 * 65535 or
+ * N*h*w*C > 2^40; with a label: H, W that are not the same power-of-two multiple s >= 1 of h, w, n_classes outside [1, 256],
+ * H*W*C > 2^40.  A workspace that is missing or too small is JPDSE_EWORKSPACE.  ws: jpdse_code_cost_workspace_size() bytes
+ * (host only; 0 for a shape the call refuses or n_classes outside [0, 256], 0 standing for "no label map"). */
+/* Host only: out[v] = T[v], v = 0 .. 2048, built in fp64. */
+int jpdse_code_cost_table(uint32_t* out /* [2049] */);
+size_t jpdse_code_cost_workspace_size(int32_t N, int32_t h, int32_t w, int32_t C, int32_t n_classes);
+typedef struct jpdse_code_cost_args {
+  int32_t dtype, N, h, w, C;
+  const void* b;           /* the code */
+  int32_t H, W;            /* the image's extents behind the label map */
+  const float* label;      /* device fp32 [N][1][H][W], or NULL: no class tables */
+  int32_t n_classes;       /* 1..256 with a label */
+  uint32_t* symbol;        /* device uint32 [N][h][w][C], or NULL: aggregates only */
+  uint64_t* cell;          /* device [N][h][w] */
+  uint64_t* channel;       /* device [N][C] */
+  uint64_t* class_units;   /* device [N][n_classes + 1], or NULL without a label */
+  uint64_t* class_pixels;  /* device [N][n_classes + 1], or NULL without a label */
+  void* ws;
+  size_t ws_bytes;
+  void* stream;
+} jpdse_code_cost_args;
+int jpdse_code_cost(const jpdse_code_cost_args* args);
 
 /* ---- semantics-weighted distortion: --class_distortion_weights / --edge_distortion_weight (no reference counterpart;
  * DESIGN.md 4.11) ----------------------------------------------------------------------------------------------------------

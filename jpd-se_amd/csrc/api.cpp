@@ -1,6 +1,7 @@
 // Library-level entry points: version, error string, architecture check.
 #include "common.h"
 
+#include <math.h>
 #include <string.h>
 
 #include <vector>
@@ -29,6 +30,20 @@ int code_import_check(int dtype, int N, int H, int W, int C, const void* in, con
   JPDSE_REQUIRE(in != nullptr && b != nullptr, "code_import: null pointer");
   JPDSE_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0, "code_import: non-positive extent (N %d, H %d, W %d, C %d)", N, H, W, C);
   return JPDSE_OK;
+}
+
+// jpdse_code_cost (code_cost.hip): T[v] = round(-log2(v / 2048) * 2^16) for v in 1 .. 2047, T[0] = T[2048] = 0 (a probability
+// never leaves [31, 2017]: neither end is ever looked up).  fp64 on the host; v / 2048 is exact.
+const uint32_t* code_cost_table_host() {
+  struct Table {
+    uint32_t t[2049];
+    Table() {
+      t[0] = t[2048] = 0;
+      for (int v = 1; v < 2048; ++v) t[v] = (uint32_t)llround(-log2((double)v / 2048.0) * 65536.0);
+    }
+  };
+  static const Table table;
+  return table.t;
 }
 
 // ---- in-library timer for the HBM-bound calls (bench.py "roofline_hbm"): hipEvent pairs around whole InstanceNorm /
@@ -98,6 +113,12 @@ int jpdse_prof_hbm_collect(int32_t cls, double* total_ms, double* total_bytes, i
   *total_ms = ms;
   *total_bytes = by;
   *regions = n;
+  return JPDSE_OK;
+}
+
+int jpdse_code_cost_table(uint32_t* out) {
+  JPDSE_REQUIRE(out != nullptr, "code_cost_table: null pointer");
+  memcpy(out, jpdse::code_cost_table_host(), 2049 * sizeof(uint32_t));
   return JPDSE_OK;
 }
 

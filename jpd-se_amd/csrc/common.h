@@ -21,6 +21,9 @@ int check_launch(const char* what);
 // argument checks of jpdse_code_import (api.cpp): JPDSE_EINVAL + message before any launch, JPDSE_OK otherwise
 int code_import_check(int dtype, int N, int H, int W, int C, const void* in, const void* b);
 
+// the cost table of jpdse_code_cost_table (api.cpp): 2049 entries, built once on the host in fp64
+const uint32_t* code_cost_table_host();
+
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 // opt-in timer of the HBM-bound calls (api.cpp; jpdse_prof_hbm_select / _collect): begin returns a slot or -1 (off / full)

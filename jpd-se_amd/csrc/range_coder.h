@@ -1,5 +1,5 @@
-// The coder core of entropy.hip, shared in parts with semantics.hip and code_rate.hip: the binary range
-// coder of LZMA (the "rc" scheme; I. Pavlov, LZMA SDK, public domain; 11-bit probabilities of bit 0, shift 5), the payload
+// The coder core of entropy.hip, shared in parts with semantics.hip, code_rate.hip and code_cost.hip: the
+// binary range coder of LZMA (the "rc" scheme; I. Pavlov, LZMA SDK, public domain; 11-bit probabilities of bit 0, shift 5), the payload
 // layout -- a table of little-endian uint32 stream lengths, then the streams -- as the encoders write it and as the decoders
 // read it from data they do not trust, and the context rule of the code tensor's streams.  The modelling (which decision in
 // which context) stays with each source.  Device code only; plain C++ loads and stores.
@@ -11,6 +11,12 @@ namespace jpdse {
 constexpr uint32_t kTop = 1u << 24;
 constexpr uint32_t kProbInit = 1024, kProbOne = 2048;
 constexpr int kMoveBits = 5;
+
+// The adaptive probability of bit 0 after `bit` was coded with q -- the ONE statement of the update the coder, the decoder
+// and the cost walk of code_cost.hip share.
+__device__ __forceinline__ uint32_t adapted(uint32_t q, uint32_t bit) {
+  return bit ? q - (q >> kMoveBits) : q + ((kProbOne - q) >> kMoveBits);
+}
 
 // One lane codes one stream into its slot of `scap` bytes.  A probability is passed by reference: it may live in an LDS
 // column (prob[ctx * 64]).
@@ -60,7 +66,7 @@ struct RcEncoder {
   // an adaptive decision
   __device__ __forceinline__ void encode(uint32_t& p, uint32_t bit) {
     const uint32_t q = p;
-    p = bit ? q - (q >> kMoveBits) : q + ((kProbOne - q) >> kMoveBits);
+    p = adapted(q, bit);
     split((range >> 11) * q, bit);
   }
   // the flush; returns the bytes the stream needs, or scap + 1 when they are more than scap
@@ -109,7 +115,7 @@ struct RcDecoder {
   }
   __device__ __forceinline__ uint32_t decode(uint32_t& p) {
     const uint32_t q = p, bit = split((range >> 11) * q);
-    p = bit ? q - (q >> kMoveBits) : q + ((kProbOne - q) >> kMoveBits);
+    p = adapted(q, bit);
     return bit;
   }
 };

@@ -319,6 +319,10 @@ class Pix2PixHDModel(BaseModel):
       return self.get_eval_metrics(x_dict)
     if mode == 'get_eval_metrics_per_class':
       return self.get_eval_metrics(x_dict, per_class=True)
+    if mode == 'get_rate_map':
+      return self.get_rate_map(x_dict)
+    if mode == 'get_class_rates':
+      return self.get_class_rates(x_dict)
     raise ValueError('Invalid forward mode: {}'.format(mode))
 
   def create_optimizers(self, opt):
@@ -640,6 +644,47 @@ class Pix2PixHDModel(BaseModel):
     coded = sum(8.0 * entropy.file_bytes(len(p), shape) / (H * W) for p in payloads) / len(payloads)
     raw = 8.0 * (bitstream.HEADER_BYTES + bitstream.payload_bytes(shape)) / (H * W)
     return coded, raw
+
+  # ---- where the bits go (extension) ------------------------------------------------------------------------
+  def get_rate_map(self, x_dict):
+    """The code length of the eval-mode code (the one get_code / get_coded produce) under the 4.8 coder's own adaptive model,
+    symbol by symbol (ops.code_cost): dict of float64 CPU tensors, `map` [N, h, w] bits per code cell, `per_channel` [N, C]
+    bits, `bits` [N] and `bpp` [N] = bits / (H * W).  map and per_channel each sum to bits.  The model's ideal length, not a
+    file size: get_coded_rate measures files, and stays within the bound of DESIGN.md 4.12 of this figure."""
+    with torch.no_grad():
+      r = ops.code_cost(self._code_act(x_dict))
+      cell, channel = r['cell'].cpu(), r['channel'].cpu()
+    pixels = int(x_dict['image'].shape[-2]) * int(x_dict['image'].shape[-1])
+    unit = float(ops.CODE_COST_UNIT)
+    bits = cell.sum(dim=(1, 2)).to(torch.float64) / unit            # integer sums first: exact
+    return dict(map=cell.to(torch.float64) / unit, per_channel=channel.to(torch.float64) / unit, bits=bits, bpp=bits / pixels)
+
+  def get_class_rates(self, x_dict):
+    """The same code length attributed to the semantic classes of the pixels each code cell covers -- a cell's bits are
+    shared evenly among its s*s pixels, s the encoder's down-sampling factor.  Rows: the n_onehot classes of
+    get_eval_metrics(per_class=True) in its order, then one row for the pixels without a class.  dict(pixels int64, bits, bpp,
+    share float64, each [n_classes + 1], over the batch: bits summed, bpp = bits of the class / pixels of the class (nan for
+    an absent class), share = the class's fraction of all bits; per_image: the same four keys [N, n_classes + 1], share being
+    the fraction of that image's bits)."""
+    with torch.no_grad():
+      b = self._code_act(x_dict)
+      label, _ = self._semantics(x_dict)
+      r = ops.code_cost(b, label, self.n_onehot)
+      units, pix = r['class_units'].cpu(), r['class_pixels'].cpu()
+    s = int(label.shape[-1]) // b.W
+    den = float(ops.CODE_COST_UNIT) * s * s
+
+    def figures(u, p):                  # integer tensors [..., rows]
+      bits = u.to(torch.float64) / den
+      seen = p > 0
+      nan = torch.full_like(bits, float('nan'))
+      bpp = torch.where(seen, bits / torch.where(seen, p, torch.ones_like(p)).to(torch.float64), nan)
+      total = u.sum(dim=-1, keepdim=True).to(torch.float64) / den
+      return dict(pixels=p.clone(), bits=bits, bpp=bpp, share=bits / total)
+
+    out = figures(units.sum(dim=0), pix.sum(dim=0))
+    out['per_image'] = figures(units, pix)
+    return out
 
   # ---- coded label and instance maps (extension; DESIGN.md 4.9) --------------------------------------------------------------
   def _label_set(self):

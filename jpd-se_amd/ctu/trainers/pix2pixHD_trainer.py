@@ -191,6 +191,21 @@ class Pix2PixHDTrainer(BaseTrainer):
     self.eval()
     return self.model.get_context_rate(x_dict)
 
+  def get_rate_map(self, x_dict):
+    """Where the bits go (extension): the code length of the eval-mode code under the 4.8 coder's own adaptive
+    model, exact per symbol.  dict of float64 CPU tensors: `map` [N, h, w] bits per code cell, `per_channel` [N, C] bits,
+    `bits` [N], `bpp` [N] = bits / (H * W).  An ideal code length; get_coded_rate stays the size of the files."""
+    self.eval()
+    return self.model(x_dict, self.opt, mode='get_rate_map')
+
+  def get_class_rates(self, x_dict):
+    """The same bits attributed to the semantic classes of the pixels each code cell covers: dict(pixels, bits, bpp, share)
+    with one row per class of get_eval_metrics(per_class=True) plus a last row for the pixels without a class, over the
+    batch, and `per_image` with the same keys [N, rows].  bpp = bits of the class / pixels of the class, nan for an absent
+    class; share = the class's fraction of the bits."""
+    self.eval()
+    return self.model(x_dict, self.opt, mode='get_class_rates')
+
   def get_coded_semantics(self, x_dict, strip_rows=8):
     """The label and instance maps, coded losslessly on the device (extension): a list with the body of one
     .jpds file (ctu.utils.semantics) per image."""

@@ -80,6 +80,14 @@ class SemLossArgs(ctypes.Structure):
               ('ws_bytes', ctypes.c_size_t), ('stream', ctypes.c_void_p)]
 
 
+class CodeCostArgs(ctypes.Structure):
+  _fields_ = [(n, ctypes.c_int32) for n in ('dtype', 'N', 'h', 'w', 'C')] + \
+             [('b', ctypes.c_void_p), ('H', ctypes.c_int32), ('W', ctypes.c_int32), ('label', ctypes.c_void_p),
+              ('n_classes', ctypes.c_int32), ('symbol', ctypes.c_void_p), ('cell', ctypes.c_void_p), ('channel', ctypes.c_void_p),
+              ('class_units', ctypes.c_void_p), ('class_pixels', ctypes.c_void_p), ('ws', ctypes.c_void_p),
+              ('ws_bytes', ctypes.c_size_t), ('stream', ctypes.c_void_p)]
+
+
 _P, _I32, _I64, _F, _SZ = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float,
                            ctypes.c_size_t)
 _CD, _ND = ctypes.POINTER(ConvDesc), ctypes.POINTER(InormDesc)
@@ -182,6 +190,9 @@ SIGNATURES = {
     'jpdse_code_rate_workspace_size': (_SZ, [_I32, _I32, _I32, _I32]),
     'jpdse_code_rate_loss': (_I32, [ctypes.POINTER(CodeRateArgs)]),
     'jpdse_sem_weighted_loss': (_I32, [ctypes.POINTER(SemLossArgs)]),
+    'jpdse_code_cost_table': (_I32, [ctypes.POINTER(ctypes.c_uint32)]),
+    'jpdse_code_cost_workspace_size': (_SZ, [_I32, _I32, _I32, _I32, _I32]),
+    'jpdse_code_cost': (_I32, [ctypes.POINTER(CodeCostArgs)]),
 }
 
 # the developer build (same sources, -DJPDSE_DEV): the shipped ABI plus include/jpdse_dev.h

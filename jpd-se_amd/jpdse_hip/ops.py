@@ -9,7 +9,7 @@ import struct
 
 import torch
 
-from . import (lib, check, JpdseError, F32, BF16, ConvDesc, InormDesc, EvalMetricsSemArgs, MsssimLossArgs, CodeRateArgs, SemLossArgs, ACT_NONE, PAD_ZERO, PAD_REFLECT)
+from . import (lib, check, JpdseError, F32, BF16, ConvDesc, InormDesc, EvalMetricsSemArgs, MsssimLossArgs, CodeRateArgs, SemLossArgs, CodeCostArgs, ACT_NONE, PAD_ZERO, PAD_REFLECT)
 
 
 def cpad(c):
@@ -992,3 +992,44 @@ def code_rate_loss(b, t, pixels, scale=1.0, want_grad=True, want_counts=False, o
                       torch.cuda.current_stream().cuda_stream)
   check(L.jpdse_code_rate_loss(ctypes.byref(args)), 'code_rate_loss')    # a shape beyond the limits is refused here
   return out, per_image, grad, counts
+
+
+# ---- learned codec: code-length map and per-class rate (code_cost.hip; definition: DESIGN.md 4.12) ------------------------
+CODE_COST_UNIT = 65536        # units per bit
+
+
+def code_cost(b, label=None, n_classes=0, want_symbols=False):
+  """Where the bits of the code `b` go (jpdse_code_cost): the exact cost the adaptive model of the 4.8 coder assigns to every
+  symbol, in units of 2^-16 bit, summed three ways.  Returns a dict of int64 device tensors: `cell` [N, h, w] (the rate map),
+  `channel` [N, C], `symbol` [N, h, w, C] (int32; None unless want_symbols) and, with `label` (device fp32 [N, 1, H, W], H / h
+  = W / w = s a power of two) and `n_classes`, `class_units` and `class_pixels` [N, n_classes + 1]: a cell's units go
+  undivided to each of the s*s pixels it covers (divide by s*s for bits), the last row collects the pixels without a class
+  (the rule of eval_metrics' per-class table).  Both are None without a label.  Integer sums throughout: two calls give
+  identical tensors.  A shape or label map the library does not take is refused there, before any launch."""
+  L = lib()
+  dev = b.t.device
+  N, h, w, C = b.N, b.H, b.W, b.C
+  H = W = 0
+  units = pixels = None
+  if label is not None:
+    n_classes = int(n_classes)
+    assert label.dtype == torch.float32 and label.is_contiguous() and label.device == dev
+    assert label.dim() == 4 and label.shape[0] == N and label.shape[1] == 1, (tuple(label.shape), N)
+    H, W = int(label.shape[2]), int(label.shape[3])
+    rows = max(n_classes, 0) + 1
+    units = torch.empty((N, rows), dtype=torch.int64, device=dev)
+    pixels = torch.empty((N, rows), dtype=torch.int64, device=dev)
+  elif n_classes:
+    raise ValueError('code_cost: n_classes without a label map')
+  symbol = torch.empty((N, h, w, C), dtype=torch.int32, device=dev) if want_symbols else None
+  cell = torch.empty((N, h, w), dtype=torch.int64, device=dev)
+  channel = torch.empty((N, C), dtype=torch.int64, device=dev)
+  n = L.jpdse_code_cost_workspace_size(N, h, w, C, 0)
+  ws = workspace(max(n, 1), dev)
+  args = CodeCostArgs(b.dtype, N, h, w, C, b.t.data_ptr(), H, W, label.data_ptr() if label is not None else None,
+                      n_classes if label is not None else 0, symbol.data_ptr() if want_symbols else None, cell.data_ptr(),
+                      channel.data_ptr(), units.data_ptr() if units is not None else None,
+                      pixels.data_ptr() if pixels is not None else None, ws.data_ptr(), ws.numel(),
+                      torch.cuda.current_stream().cuda_stream)
+  check(L.jpdse_code_cost(ctypes.byref(args)), 'code_cost')
+  return dict(symbol=symbol, cell=cell, channel=channel, class_units=units, class_pixels=pixels)

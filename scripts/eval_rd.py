@@ -23,13 +23,19 @@ beside get_eval_rate's Shannon estimate.  With --roundtrip the files written and
 
   python scripts/eval_rd.py [--batches 4] [--batch 2] [--width 1024] [--height 512] [--dtype bf16] [--codec]
                             [--checkpoints_dir DIR] [--data DIR] [--per-class] [--zero_sem] [--zero_ins] [--zero_vis]
-                            [--roundtrip DIR] [--entropy] [--semantics]
+                            [--roundtrip DIR] [--entropy] [--semantics] [--rate-map DIR]
 
 --semantics (needs --codec --entropy --roundtrip DIR) completes the stream: every image's label and instance maps are coded
 (trainer.get_coded_semantics) and written as a .jpds file beside the .jpda one, the receiver's maps come from
 those files alone (trainer.decode_semantics), the decoded image is checked against get_img under the zero rule above, and
 the line gains the three rates trainer.get_total_rate reports (code, semantics and total bpp, headers included), taken from
 the sizes of the files just written.
+
+With --codec, --per-class also says where the bits go: next to each class's L1 / MSE / PSNR the table gains
+the bits of the code attributed to the class (trainer.get_class_rates: the code length under the 4.8 coder's own adaptive
+model, a cell's bits shared evenly among the pixels it covers), its bpp (bits / pixels of the class) and its share of all
+bits.  --rate-map DIR (needs --codec) writes the map behind it, trainer.get_rate_map's float64 [h, w] bits per code cell, as
+DIR/b<batch>_i<image>.npy, and the line gains the model's bpp.
 """
 import argparse
 import contextlib
@@ -123,6 +129,8 @@ def main():
                   help='with --codec: also report the bpp of the entropy-coded files; --roundtrip then stores and decodes those')
   ap.add_argument('--semantics', action='store_true',
                   help='with --codec --entropy --roundtrip: also store the label / instance maps as .jpds files and decode from files only')
+  ap.add_argument('--rate-map', default=None, metavar='DIR',
+                  help='with --codec: write every image\'s code-length map (bits per code cell, float64 [h, w]) as DIR/*.npy')
   ap.add_argument('--class_distortion_weights', default='',
                   help='label:weight pairs of the training flag (DESIGN.md 4.11): also print the weighted, un-quantised distortion')
   ap.add_argument('--edge_distortion_weight', type=float, default=1.0, help='the training flag of the same name (DESIGN.md 4.11)')
@@ -133,8 +141,12 @@ def main():
     ap.error('--entropy needs --codec')
   if args.semantics and not (args.codec and args.entropy and args.roundtrip):
     ap.error('--semantics needs --codec --entropy --roundtrip DIR')
+  if args.rate_map and not args.codec:
+    ap.error('--rate-map needs --codec')
   if args.roundtrip:
     os.makedirs(args.roundtrip, exist_ok=True)
+  if args.rate_map:
+    os.makedirs(args.rate_map, exist_ok=True)
   import jpdse_hip
   from jpdse_hip import ops
   from ctu.trainers import get_trainer
@@ -153,11 +165,12 @@ def main():
   with contextlib.redirect_stdout(sys.stderr):
     trainer = get_trainer(opt)(opt, 'test' if args.checkpoints_dir else 'train')
   keys = ('l1', 'mse', 'ms_ssim', 'psnr')
-  by_batch = dict.fromkeys(keys + ('shannon', 'actual', 'context', 'file', 'coded', 'semantics', 'total', 'weighted'), 0.0)
-  by_image = dict.fromkeys(keys + ('shannon', 'actual', 'context', 'file', 'coded', 'semantics', 'total', 'weighted'), 0.0)
+  by_batch = dict.fromkeys(keys + ('shannon', 'actual', 'context', 'file', 'coded', 'semantics', 'total', 'weighted', 'model'), 0.0)
+  by_image = dict.fromkeys(keys + ('shannon', 'actual', 'context', 'file', 'coded', 'semantics', 'total', 'weighted', 'model'), 0.0)
   weighted = trainer.model.sem_weights is not None      # class / edge weights are set
   images, n_batches, worst_diff = 0, 0, 0.0
   class_sums = None                  # int64 [1, n_classes + 1, 3]: the raw class tables of every image so far, added up
+  class_bits = None                  # float64 [n_classes + 1]: the bits of the code attributed to each class so far (with --codec)
   start = time.time()
   for i, x_dict in enumerate(batches(args)):
     if args.roundtrip:
@@ -194,6 +207,18 @@ def main():
       by_batch['context'] += context                   # of the coded size, not a size)
       by_image['context'] += context * b
       line += ', context-model bpp {:.4f}'.format(context)
+    if args.codec and args.per_class:
+      cr = trainer.get_class_rates(x_dict)             # bits are sums of k / 2^16: adding batches stays exact
+      class_bits = cr['bits'] if class_bits is None else class_bits + cr['bits']
+    if args.rate_map:
+      import numpy as np
+      rm = trainer.get_rate_map(x_dict)
+      for j in range(b):
+        np.save(os.path.join(args.rate_map, 'b%04d_i%02d.npy' % (i, j)), rm['map'][j].numpy())
+      model_bpp = float(rm['bpp'].mean())
+      by_batch['model'] += model_bpp
+      by_image['model'] += float(rm['bpp'].sum())
+      line += ', model code length bpp {:.4f}'.format(model_bpp)
     if args.entropy:
       coded_bpp, raw_file_bpp = trainer.get_coded_rate(x_dict)
       by_batch['coded'] += coded_bpp
@@ -230,6 +255,8 @@ def main():
     if args.codec:
       line += ', avg pre-/(estimated) post-entropy coding bpp {:.4f}/{:.4f}'.format(t['actual'] / n, t['shannon'] / n)
       line += ', avg context-model bpp {:.4f}'.format(t['context'] / n)
+    if args.rate_map:
+      line += ', avg model code length bpp {:.4f}'.format(t['model'] / n)
     if args.entropy:
       line += ', avg coded file bpp {:.4f}'.format(t['coded'] / n)
     if args.semantics:
@@ -246,12 +273,24 @@ def main():
     r = ops.eval_metrics_per_class(class_sums)
     total = int(r['pixels'].sum()) + r['unlabelled']
     print('per-class distortion over the test set (classes that occur; %d pixels, %d without a class)' % (total, r['unlabelled']))
-    print('{:>5} {:>12} {:>8} {:>9} {:>11} {:>9}'.format('class', 'pixels', 'share', 'L1', 'MSE', 'PSNR dB'))
+    rate_head = ' {:>12} {:>8} {:>9}'.format('bits', 'bpp', 'bit share') if class_bits is not None else ''
+    print('{:>5} {:>12} {:>8} {:>9} {:>11} {:>9}'.format('class', 'pixels', 'share', 'L1', 'MSE', 'PSNR dB') + rate_head)
+    all_bits = float(class_bits.sum()) if class_bits is not None else 0.0
+
+    def rate_columns(k, n):
+      if class_bits is None:
+        return ''
+      return ' {:>12.1f} {:>8.4f} {:>8.2f}%'.format(float(class_bits[k]), float(class_bits[k]) / n, 100.0 * float(class_bits[k]) / all_bits)
     for k in range(r['pixels'].numel()):
       n = int(r['pixels'][k])
       if n:
         print('{:>5} {:>12} {:>7.2f}% {:>9.4f} {:>11.4f} {:>9.3f}'.format(k, n, 100.0 * n / total, float(r['l1'][k]),
-                                                                      float(r['mse'][k]), float(r['psnr'][k])))
+                                                                      float(r['mse'][k]), float(r['psnr'][k])) + rate_columns(k, n))
+    if class_bits is not None and r['unlabelled']:
+      print('{:>5} {:>12} {:>7.2f}% {:>9} {:>11} {:>9}'.format('none', r['unlabelled'], 100.0 * r['unlabelled'] / total, '', '', '')
+            + rate_columns(-1, r['unlabelled']))
+    if class_bits is not None:
+      print('bits: the code length under the coder\'s own adaptive model (DESIGN.md 4.12), %.1f in all, %.4f bpp' % (all_bits, all_bits / total))
     print('')
 
 
