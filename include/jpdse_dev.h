@@ -47,8 +47,17 @@ extern "C" {
  * profiles/r01_ablation_resblock.txt, profiles/r04_virt_conflicts_ab.txt), 201-203 (timing-only ablations of the all-taps
  * weight-gradient loop: profiles/r04_wgrad_taps_ab.txt), 210-225 (timing-only ablations of gemm_fast_kernel's loader, loop and
  * epilogue: profiles/r04_fast_astage_ablation.txt, profiles/r04_epilogue_act_ab.txt).
- * Each call resets the others to their defaults. */
+ * Each call resets the others to their defaults.
+ * The kernel names above are prose; which kernel family a layer runs on under a mode is a ROUTE, and the routes' names come from
+ * route_name() in jpd-se_amd/csrc/conv_route.h (jpdse_debug_conv_route / jpdse_debug_route_name below). */
 int jpdse_debug_set_fast_path(int32_t enable);
+
+/* The routes (conv_route.h: FwdRoute, DgradRoute, WgradRoute) the forward, data gradient and weight gradient of a layer take under
+ * the current switch setting: out[0..2].  Launches nothing.  flags = what the caller would ask for: 1 forward moments, 2 pooled
+ * output; data gradient: 4 mask, 8 addend, 16 the mask has a non-zero (LeakyReLU) slope, 32 moments, 64 norm-backward sums.
+ * jpdse_debug_route_name(direction 0 | 1 | 2, route) is the route's printable name, NULL when there is no such route. */
+int jpdse_debug_conv_route(const jpdse_conv_desc* d, int32_t flags, int32_t out[3]);
+const char* jpdse_debug_route_name(int32_t direction, int32_t route);
 
 /* CU occupier for the one-GPU rehearsal of "compute kernels share the chip with a collective" (scripts/cu_contention.py,
  * profiles/r03_cu_contention.txt): launches `blocks` (1..128) workgroups on `stream`, each holding a whole CU's 160 KiB of LDS,

@@ -1,5 +1,6 @@
-// Data-gradient dispatch of the convolution family (also the forward of ConvTranspose2d): reflect ring path, stride-phase
-// programs, single-phase layers.  Part of conv_gemm.hip (one translation unit).
+// Data-gradient dispatch of the convolution family (also the forward of ConvTranspose2d): conv_dgrad_t launches the route
+// select_dgrad (conv_route.h) chose, one function per route; the ConvTranspose moment-slot and norm-sum slot queries read the same
+// choice.  Part of conv_gemm.hip (one translation unit).
 #pragma once
 
 namespace jpdse {
@@ -170,384 +171,341 @@ struct NormSink {
   float slope;
 };
 
-// blocks per image whose norm-backward sums the data gradient of this layer writes (0: its kernel has no such epilogue):
-// the reflect-padded 3x3 convs on the folded-frame halo kernel with 128-channel output tiles -- the ResnetBlock convs
+struct DgradCall {      // what a data-gradient route is handed
+  const jpdse_conv_desc* d; const ConvPlan& p;
+  const void* dy; const void* pack; void* dx; void* ws; hipStream_t s;
+  const void* mask; const void* addend; float* mom; float mask_slope; const NormSink* sink;
+};
+static void* dgrad_dxp(const DgradCall& c) { return reinterpret_cast<char*>(c.ws) + c.p.dypad_bytes; }      // dx on the reflect-padded domain
+
+// phase 0 as the single-launch kernels see it
+static ConvView dgrad_view(const DgradCall& c) {
+  ConvView v = view_dgrad_phase(c.d, c.p, 0, c.dy, c.pack, c.dx);
+  v.mask = reinterpret_cast<const bf16_t*>(c.mask);
+  v.addend = reinterpret_cast<const bf16_t*>(c.addend);
+  return v;
+}
+// reflect-padded 3x3: the zero-padded data gradient on the image's own grid (pad 1, straight into dx).  The mask rides in the
+// one-launch (frame) forms only; the strip forms apply it after the fold.
+static ConvView ring_view(const DgradCall& c) {
+  ConvView r = dgrad_view(c);
+  r.OH = c.d->H;
+  r.OW = c.d->W;
+  r.py = r.px = 1;
+  r.out_base = 0;
+  r.mask = nullptr;
+  return r;
+}
+
+// one launch (+ the split-K finish of the nine-tap program): the ring rides in the frame of dy (gemm_halo.h / gemm_taps.h VIRT);
+// the mask, if any, in the same epilogue
+static int dgrad_ring_frame(const DgradCall& c, DgradRoute route) {      // ring_taps9_frame | ring_halo_frame
+  const jpdse_conv_desc* d = c.d;
+  const ConvPlan& p = c.p;
+  const bool taps = route == DgradRoute::ring_taps9_frame;
+  ConvView r = ring_view(c);
+  bf16_t* frame = reinterpret_cast<bf16_t*>(c.ws);       // in front of the split-K slabs (splitk_off lies behind the padded-dy region)
+  const long long fv = (long long)d->N * (2 * (d->W + 2) + 2 * d->H) * (p.Ks / 8);
+  if (taps && (size_t)fv * 16 > p.splitk_off) return set_error(JPDSE_EWORKSPACE, "reflect data gradient: no room for the frame in front of the slabs");
+  const int pslot = taps ? -1 : prof_begin(c.s, p.Cs, 9LL * p.Ks);
+  hipLaunchKernelGGL(ring_frame_kernel, dim3(ew_blocks(fv)), dim3(256), 0, c.s, r.X, frame, d->N, d->H, d->W, p.Ks, fv);
+  const int rc = check_launch("ring_frame_kernel");
+  prof_end(pslot, 1, 0.0, c.s);
+  if (rc) return rc;
+  r.frame = frame;
+  r.mask = reinterpret_cast<const bf16_t*>(c.mask);
+  if (taps) return launch_taps9(r, splitk_slabs(p, c.ws), c.s);
+  HaloArgs h = to_halo(r);
+  if (c.sink != nullptr) {
+    h.nx = reinterpret_cast<const bf16_t*>(c.sink->x);
+    h.nstats = c.sink->stats;
+    h.nsums = c.sink->sums;
+    h.nact = c.sink->act;
+    h.nslope = c.sink->slope;
+    h.mom_slots = halo_slots(d->H, d->W);
+  }
+  return p.Cs > 64 ? launch_halo_cfg<2>(h, c.s) : launch_halo_cfg<1>(h, c.s);
+}
+
+// (1) the zero-padded data gradient, (2) the four ring strips of the reflect-padded domain as split-K GEMMs into fp32 slabs,
+// (3) ring_fold_kernel, (4) the mask
+static int dgrad_ring_strips(const DgradCall& c, DgradRoute route) {      // ring_taps9_strips | ring_halo_strips
+  const jpdse_conv_desc* d = c.d;
+  const ConvPlan& p = c.p;
+  hipStream_t s = c.s;
+  const ConvView r = ring_view(c);
+  if (route == DgradRoute::ring_taps9_strips) {
+    if (int rc = launch_taps9(r, splitk_slabs(p, c.ws), s)) return rc;
+  } else if (int rc = p.Cs > 64 ? launch_halo_cfg<2>(to_halo(r), s) : launch_halo_cfg<1>(to_halo(r), s)) return rc;
+  const int H = d->H, W = d->W, Ks = p.Ks, Lk = p.ph[0].Lk;
+  const bf16_t* dyb = reinterpret_cast<const bf16_t*>(c.dy);
+  const bf16_t* pk = reinterpret_cast<const bf16_t*>(c.pack);
+  const int Mtb = d->N * (W + 2), Mlr = d->N * H;
+  const int nt = (p.Cs + 127) / 128;
+  // the strips have few rows (N (W + 2) and N H); 128-row tiles (two blocks per CU) measured slower (round-2 mode 31, retired)
+  const int bm = 256;
+  const int tiles = 2 * ((Mtb + bm - 1) / bm) * nt + 2 * ((Mlr + bm - 1) / bm) * nt;
+  const int kt = 3 * Ks / 64;
+  int sp = 256 / tiles;
+  if (sp > kt / 8) sp = kt / 8;
+  if (sp > 8) sp = 8;
+  if (sp < 1) sp = 1;
+  float* slab = reinterpret_cast<float*>(c.ws);
+  const size_t tb_elems = (size_t)sp * Mtb * p.Cs, lr_elems = (size_t)sp * Mlr * p.Cs;
+  FastBatch rb = {};
+  rb.small_m = 0;
+  for (int q = 0; q < 4; ++q) {
+    FastArgs g = {};
+    const bool row_strip = q < 2;         // 0 top, 1 bottom, 2 left, 3 right
+    g.X = dyb + (q == 1 ? (long long)(H - 1) * W * Ks : (q == 3 ? (long long)(W - 1) * Ks : 0));
+    g.x_sn = (long long)H * W * Ks;
+    g.x_sh = (long long)W * Ks;
+    g.x_extent = (long long)d->N * H * W * Ks - (g.X - dyb);
+    g.IH = row_strip ? 1 : H;
+    g.IW = row_strip ? W : 1;
+    g.Cs = Ks;
+    g.R = row_strip ? 1 : 3;
+    g.S = row_strip ? 3 : 1;
+    g.sy = g.sx = 1;
+    g.py = row_strip ? 0 : 1;
+    g.px = row_strip ? 2 : 0;
+    g.OH = row_strip ? 1 : H;
+    g.OW = row_strip ? W + 2 : 1;
+    g.M = row_strip ? Mtb : Mlr;
+    // panel [c][u'][w'][k] with u' = 2 - r, w' = 2 - s: top r=0 -> u'=2, bottom u'=0, left s=0 -> w'=2, right w'=0
+    g.B = pk + (q == 0 ? 2LL * Lk : (q == 2 ? 2LL * Ks : 0));
+    g.b_stride = 3LL * Lk;
+    g.b_tap_r = Lk;
+    g.b_tap_s = Ks;
+    g.Kout = d->C;
+    g.Ks = p.Cs;
+    g.b_rows = p.Cs;
+    g.act = JPDSE_ACT_NONE;
+    g.splits = sp;
+    g.no_finish = 1;
+    g.partial = slab + (q == 0 ? 0 : (q == 1 ? tb_elems : (q == 2 ? 2 * tb_elems : 2 * tb_elems + lr_elems)));
+    rb.p[rb.n++] = g;
+  }
+  const int pslot = prof_begin(s, p.Cs, 9LL * p.Ks);
+  if (int rc = launch_fast_batch(rb, s)) return rc;
+  // fold the ring into rows 1 / H-2 and columns 1 / W-2 of dx
+  RingFoldArgs rf = {};
+  rf.dx = reinterpret_cast<bf16_t*>(c.dx);
+  rf.top = rb.p[0].partial;
+  rf.bot = rb.p[1].partial;
+  rf.left = rb.p[2].partial;
+  rf.right = rb.p[3].partial;
+  rf.splits_tb = rf.splits_lr = sp;
+  rf.N = d->N;
+  rf.H = H;
+  rf.W = W;
+  rf.Cs = p.Cs;
+  const long long tv = (long long)d->N * (2 * W + 2 * (H - 2)) * (p.Cs / 8);
+  hipLaunchKernelGGL(ring_fold_kernel, dim3(ew_blocks(tv)), dim3(256), 0, s, rf, tv);
+  int rc = check_launch("ring_fold_kernel");
+  if (rc == JPDSE_OK && c.mask != nullptr) {
+    const long long total_vec = (long long)d->N * H * W * (p.Cs / 8);
+    hipLaunchKernelGGL((relu_mask_kernel<bf16_t>), dim3(ew_blocks(total_vec)), dim3(256), 0, s, reinterpret_cast<bf16_t*>(c.dx),
+                       reinterpret_cast<const bf16_t*>(c.mask), total_vec);
+    rc = check_launch("relu_mask_kernel");
+  }
+  prof_end(pslot, 1, 0.0, s);
+  return rc;
+}
+
+static int dgrad_head(const DgradCall& c) {
+  const jpdse_conv_desc* d = c.d;
+  const ConvPlan& p = c.p;
+  HeadFwdArgs h = {};
+  h.X = reinterpret_cast<const bf16_t*>(c.dy);
+  h.Wp = reinterpret_cast<const bf16_t*>(c.pack);
+  h.Y = reinterpret_cast<bf16_t*>(c.dx);
+  h.N = d->N; h.H = p.OH; h.W = p.OW; h.OH = d->H; h.OW = d->W;
+  h.K = d->C; h.Ks_out = p.Cs;
+  h.R = h.S = 3;
+  h.pad = 1;
+  h.act = JPDSE_ACT_NONE;
+  h.tiles_w = (d->W + 63) / 64;
+  h.tiles_h = (d->H + kHeadTH - 1) / kHeadTH;
+  if (head_rows_ok(64, h.R, h.K, h.Ks_out, h.H, h.W, h.OH, h.OW)) return launch_head_rows<3>(h, c.s);
+  return launch_head_fwd<64, 3, 3, 3>(h, c.s);
+}
+
+// the two all-phases row-streaming kernels: DY, the four phase panels, DX and the sizes both argument structs name alike
+template <typename Args>
+static Args phases_rows_args(const DgradCall& c) {
+  Args g = {};
+  g.DY = reinterpret_cast<const bf16_t*>(c.dy);
+  for (int i = 0; i < 4; ++i) g.P[i] = reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(c.pack) + c.p.ph[i].pack_off);
+  g.DX = reinterpret_cast<bf16_t*>(c.dx);
+  g.N = c.d->N; g.OH = c.p.OH; g.OW = c.p.OW;
+  return g;
+}
+static int dgrad_dgrad2_rows(const DgradCall& c) {
+  Dgrad2Args g = phases_rows_args<Dgrad2Args>(c);
+  g.mom = c.mom;
+  return launch_dgrad2_rows(g, c.s);
+}
+static int dgrad_thin_dgrad2_rows(const DgradCall& c) {
+  ThinDgrad2Args g = phases_rows_args<ThinDgrad2Args>(c);
+  g.H = c.d->H; g.W = c.d->W; g.K = c.d->C;
+  return launch_thin_dgrad2_rows(g, c.s);
+}
+
+static int dgrad_thin_in_rows(const DgradCall& c) {
+  ThinInArgs g = {};
+  g.DY = reinterpret_cast<const bf16_t*>(c.dy);
+  g.P = reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(c.pack) + c.p.ph[0].pack_off);
+  g.DX = reinterpret_cast<bf16_t*>(c.dx);
+  g.DXP = reinterpret_cast<bf16_t*>(dgrad_dxp(c));
+  g.N = c.d->N; g.H = c.d->H; g.W = c.d->W; g.OH = c.d->H + 6; g.OW = c.d->W + 6;
+  g.py = g.px = 6;
+  g.act = JPDSE_ACT_NONE;
+  return launch_thin_in_rows<7, true>(g, c.s);
+}
+
+static int dgrad_thin1(const DgradCall& c) {      // dx is written once by an FMA kernel (thin_out1.h)
+  const Phase& f = c.p.ph[0];
+  Thin1DgradArgs t = {};
+  t.DY = reinterpret_cast<const bf16_t*>(c.dy);
+  t.B = reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(c.pack) + f.pack_off);
+  t.taps = reinterpret_cast<float*>(c.ws);        // 16 x Cs floats: inside the padded-dy region of every plan
+  t.DX = reinterpret_cast<bf16_t*>(c.dx);
+  t.addend = reinterpret_cast<const bf16_t*>(c.addend);
+  t.N = c.d->N; t.H = c.d->H; t.W = c.d->W; t.Cs = c.p.Cs; t.OH = c.p.OH; t.OW = c.p.OW;
+  t.py = (f.Uh - 1) - f.i0h;
+  t.px = (f.Uw - 1) - f.i0w;
+  t.Lk = f.Lk;
+  t.b_stride = (long long)f.Uh * f.Lk;
+  return launch_thin1_dgrad(t, c.s);
+}
+
+// where stride phase f of the phase loops writes: every stride-th pixel of dx, or (reflect) of dx on the padded domain
+template <typename Args>
+static void phase_out(Args* a, const DgradCall& c, const Phase& f) {
+  const jpdse_conv_desc* d = c.d;
+  const ConvPlan& p = c.p;
+  const bool refl = d->pad_mode == JPDSE_PAD_REFLECT;
+  const int st = d->stride, H = refl ? p.Hp : d->H, W = refl ? p.Wp : d->W, off = refl ? 0 : d->pad;
+  a->Y = reinterpret_cast<decltype(a->Y)>(refl ? dgrad_dxp(c) : c.dx);
+  a->out_sn = (long long)H * W * p.Cs;
+  a->out_sh = (long long)st * W * p.Cs;
+  a->out_sw = (long long)st * p.Cs;
+  a->out_base = ((long long)(st * f.i0h + f.qh - off) * W + (st * f.i0w + f.qw - off)) * p.Cs;
+}
+// behind the phase loops: the fold of the padded domain (reflect), then the fused operands no epilogue has applied
+template <typename T>
+static int dgrad_finish(const DgradCall& c, bool in_epilogue) {
+  const jpdse_conv_desc* d = c.d;
+  const long long total_vec = (long long)d->N * d->H * d->W * (c.p.Cs / (16 / (int)sizeof(T)));
+  int rc = JPDSE_OK;
+  if (d->pad_mode == JPDSE_PAD_REFLECT) {
+    hipLaunchKernelGGL((reflect_fold_kernel<T>), dim3(ew_blocks(total_vec)), dim3(256), 0, c.s, reinterpret_cast<const T*>(dgrad_dxp(c)),
+                       reinterpret_cast<T*>(c.dx), d->N, d->H, d->W, c.p.Cs, d->pad, total_vec);
+    rc = check_launch("reflect_fold_kernel");
+  }
+  if (rc == JPDSE_OK && (c.mask != nullptr || c.addend != nullptr) && !in_epilogue) {
+    hipLaunchKernelGGL((relu_mask_kernel<T>), dim3(ew_blocks(total_vec)), dim3(256), 0, c.s, reinterpret_cast<T*>(c.dx),
+                       reinterpret_cast<const T*>(c.mask), total_vec, reinterpret_cast<const T*>(c.addend), c.mask_slope);
+    rc = check_launch("relu_mask_kernel");
+  }
+  return rc;
+}
+
+// all stride phases in ONE launch of the fast kernel; the fused operands ride in its epilogue unless the padded domain is folded first
+static int dgrad_fast(const DgradCall& c) {
+  const jpdse_conv_desc* d = c.d;
+  const ConvPlan& p = c.p;
+  const bool refl = d->pad_mode == JPDSE_PAD_REFLECT;
+  const int nlive = live_phases(p);
+  FastBatch batch = {};
+  for (int i = 0; i < p.nph; ++i) {
+    const Phase& f = p.ph[i];
+    if (f.cnth <= 0 || f.cntw <= 0) continue;
+    FastArgs g = to_fast(view_dgrad_phase(d, p, i, c.dy, c.pack, c.dx));
+    phase_out(&g, c, f);
+    if (!refl) {
+      g.mask = reinterpret_cast<const bf16_t*>(c.mask);
+      g.addend = reinterpret_cast<const bf16_t*>(c.addend);
+    }
+    g.mask_slope = c.mask_slope;
+    g.splits = nlive == 1 ? splitk_for(g.M, p.Cs, f.Uh * f.Uw * p.Ks / 64) : 1;
+    g.partial = splitk_slabs(p, c.ws);
+    batch.p[batch.n++] = g;
+  }
+  if (int rc = launch_fast_batch(batch, c.s)) return rc;
+  return dgrad_finish<bf16_t>(c, !refl);
+}
+
+// one launch of the generic GEMM per stride phase over the zero-padded copy of dy
+template <typename T>
+static int dgrad_generic(const DgradCall& c) {
+  const jpdse_conv_desc* d = c.d;
+  const ConvPlan& p = c.p;
+  if (int rc = launch_pad<T>(c.dy, c.ws, d->N, p.OH, p.OW, p.Ks, p.PT, p.PB, p.PL, p.PR, JPDSE_PAD_ZERO, c.s)) return rc;
+  for (int i = 0; i < p.nph; ++i) {
+    const Phase& f = p.ph[i];
+    if (f.cnth <= 0 || f.cntw <= 0) continue;
+    GemmFwdArgs a = {};
+    a.A = c.ws;
+    a.B = reinterpret_cast<const char*>(c.pack) + f.pack_off;
+    a.M = d->N * f.cnth * f.cntw; a.OH = f.cnth; a.OW = f.cntw;
+    a.Kout = d->C; a.Ks = a.b_rows = p.Cs;
+    a.R = f.Uh; a.cpr = f.Lk / p.BKE; a.b_row_stride = (long long)f.Uh * f.Lk;
+    a.in_sn = (long long)p.DH * p.DW * p.Ks; a.in_sh = a.in_sr = (long long)p.DW * p.Ks; a.in_sw = p.Ks;
+    a.in_base = ((long long)(f.i0h + p.PT - (f.Uh - 1)) * p.DW + (f.i0w + p.PL - (f.Uw - 1))) * p.Ks;
+    phase_out(&a, c, f);
+    a.act = JPDSE_ACT_NONE;
+    a.partial = splitk_slabs(p, c.ws);     // split-K slabs, reused by the phases (stream order)
+    a.partial_cap = p.splitk_bytes;
+    if (int rc = launch_fwd<T>(a, c.s)) return rc;
+  }
+  return dgrad_finish<T>(c, false);
+}
+
+// moment slots per image of the ConvTranspose2d forward (jpdse_convT_fwd_moments): dgrad2_rows is the route with that epilogue
+static int convT_fwd_moment_slots(const jpdse_conv_desc* d, const ConvPlan& p) {
+  if (!g_moments_fused || select_dgrad(d, p, {false, false, false, true, false}) != DgradRoute::dgrad2_rows) return 0;
+  return dgrad2_rows_slots(dgrad2_rows_band(d->N, p.OH, p.OW), p.OH, p.OW);
+}
+// blocks per image whose norm-backward sums the data gradient of this layer writes (0: its kernel has no such epilogue): the
+// folded-frame halo route with 128-channel output tiles (gemm_halo.h NSUM: the double-buffered form, a dense dx) -- the ResnetBlock convs
 static int dgrad_nsum_slots(const jpdse_conv_desc* d, const ConvPlan& p) {
-  if (d->dtype != JPDSE_BF16 || d->pad_mode != JPDSE_PAD_REFLECT || d->R != 3 || d->S != 3 || d->stride != 1 || d->pad != 1) return 0;
-  if (!g_ring_enabled || !g_ring_virt || d->H < 8 || p.ph[0].Lk != 3 * p.Ks || p.Ks < 128 || p.Cs <= 64 || p.Cs % 128 != 0 || d->C != p.Cs) return 0;
-  if (!halo_ok(3, 3, 1, d->H, d->W, p.Ks, p.Cs)) return 0;
-  return (d->H / 4) * (d->W / 64);
+  if (select_dgrad(d, p, {false, false, false, false, true}) != DgradRoute::ring_halo_frame) return 0;
+  return p.Ks >= 128 && p.Cs % 128 == 0 && d->C == p.Cs ? halo_slots(d->H, d->W) : 0;
 }
 
 template <typename T>
 static int conv_dgrad_t(const jpdse_conv_desc* d, const ConvPlan& p, const void* dy, const void* pack, void* dx,
                         void* ws, hipStream_t s, const void* mask = nullptr, const void* addend = nullptr, float* mom = nullptr,
                         float mask_slope = 0.f, const NormSink* sink = nullptr) {
-  if (sink != nullptr && (sizeof(T) != 2 || dgrad_nsum_slots(d, p) == 0 || (mask != nullptr && mask_slope != 0.f)))
-    return set_error(JPDSE_EINVAL, "conv_dgrad: this layer's data-gradient kernel writes no norm-backward sums (jpdse_conv_dgrad_nsum_slots == 0)");
-  char* wsb = reinterpret_cast<char*>(ws);
-  void* dyp = wsb;
-  void* dxp = wsb + p.dypad_bytes;
-  const bool refl = d->pad_mode == JPDSE_PAD_REFLECT;
-  const int st = d->stride;
-  // LeakyReLU-backward epilogue (mask_slope != 0): only the generic tile kernels and the unfused pass apply it
+  // LeakyReLU-backward epilogue (mask_slope != 0): only the fast / generic tile kernels and the unfused pass apply it
   const bool lrelu = mask != nullptr && mask_slope != 0.f;
-  // phase 0 as the single-launch kernels see it; `whole`: it is the whole data gradient, written straight into dx (zero padding, stride 1)
-  ConvView v = {};
-  if constexpr (sizeof(T) == 2) {
-    v = view_dgrad_phase(d, p, 0, dy, pack, dx);
-    v.mask = reinterpret_cast<const bf16_t*>(mask);
-    v.addend = reinterpret_cast<const bf16_t*>(addend);
-  }
-  const bool whole = !lrelu && !refl && p.nph == 1 && v.OH == d->H && v.OW == d->W;
-  if constexpr (sizeof(T) == 2) {
-    if (whole && st == 1 && rows_ok(v) && p.ph[0].Lk == 3 * p.Ks) return launch_rows(to_rows(v), 1, s);
-    if (whole && halo_ok(v)) return p.Cs > 64 ? launch_halo_cfg<2>(to_halo(v), s) : launch_halo_cfg<1>(to_halo(v), s);
-    // the same for grids of 8 x 32 patches (W = 32): tap-program kernel, nine taps, split-K over the dy channel slabs
-    if (whole && st == 1 && taps9_shape_ok(v)) return launch_taps9(v, reinterpret_cast<float*>(wsb + p.splitk_off), s);
-  }
-  if constexpr (sizeof(T) == 2) {
-    // reflect-padded 3x3: the zero-padded data gradient on the image's own grid (pad 1, straight into dx) + the ring.  The mask
-    // rides in the one-launch forms only; the others apply it after the fold.
-    ConvView r = v;
-    r.OH = d->H;
-    r.OW = d->W;
-    r.py = r.px = 1;
-    r.out_base = 0;
-    r.mask = nullptr;
-    const bool ring_halo = halo_ok(3, 3, 1, d->H, d->W, p.Ks, p.Cs);
-    const bool ring_taps = !ring_halo && taps9_shape_ok(3, 3, 1, d->H, d->W, p.Ks, p.Cs, (long long)d->N * d->H * d->W * p.Ks,
-                                                        (long long)p.Cs * 9 * p.Ks);
-    if (!lrelu && refl && g_ring_enabled && d->R == 3 && d->S == 3 && st == 1 && d->pad == 1 && d->H >= 8 &&
-        (ring_halo || ring_taps) && p.ph[0].Lk == 3 * p.Ks) {
-      // (1) zero-padded data gradient straight into dx: halo kernel, or the nine-tap program on 8 x 32 patches (W = 32)
-      if (ring_taps) {
-        if (g_ring_virt && d->H >= 16) {
-          // one launch (+ the split-K finish): the ring rides in the frame of dy (gemm_taps.h VIRT)
-          bf16_t* frame = reinterpret_cast<bf16_t*>(wsb);       // in front of the split-K slabs (splitk_off lies behind the padded-dy region)
-          const long long fv = (long long)d->N * (2 * (d->W + 2) + 2 * d->H) * (p.Ks / 8);
-          if ((size_t)fv * 16 > p.splitk_off) return set_error(JPDSE_EWORKSPACE, "reflect data gradient: no room for the frame in front of the slabs");
-          hipLaunchKernelGGL(ring_frame_kernel, dim3(ew_blocks(fv)), dim3(256), 0, s, r.X, frame, d->N, d->H, d->W, p.Ks, fv);
-          if (int rc = check_launch("ring_frame_kernel")) return rc;
-          r.frame = frame;
-          r.mask = v.mask;
-          return launch_taps9(r, reinterpret_cast<float*>(wsb + p.splitk_off), s);
-        }
-        if (int rc = launch_taps9(r, reinterpret_cast<float*>(wsb + p.splitk_off), s)) return rc;
-      }
-      HaloArgs h = to_halo(r);
-      if (ring_halo && g_ring_virt && (p.Ks >= 128 || (p.Ks == 64 && g_halo_single))) {
-        // one launch: the ring rides in the frame of dy (gemm_halo.h, VIRT); the mask, if any, in the same epilogue
-        bf16_t* frame = reinterpret_cast<bf16_t*>(wsb);
-        const long long fv = (long long)d->N * (2 * (d->W + 2) + 2 * d->H) * (p.Ks / 8);
-        const int pslot = prof_begin(s, p.Cs, 9LL * p.Ks);
-        hipLaunchKernelGGL(ring_frame_kernel, dim3(ew_blocks(fv)), dim3(256), 0, s, h.X, frame, d->N, d->H, d->W, p.Ks, fv);
-        int rc = check_launch("ring_frame_kernel");
-        prof_end(pslot, 1, 0.0, s);
-        if (rc) return rc;
-        h.V = frame;
-        h.mask = v.mask;
-        if (sink != nullptr) {
-          h.nx = reinterpret_cast<const bf16_t*>(sink->x);
-          h.nstats = sink->stats;
-          h.nsums = sink->sums;
-          h.nact = sink->act;
-          h.nslope = sink->slope;
-          h.mom_slots = (d->H / 4) * (d->W / 64);
-        }
-        return p.Cs > 64 ? launch_halo_cfg<2>(h, s) : launch_halo_cfg<1>(h, s);
-      }
-      if (ring_halo)
-        if (int rc = p.Cs > 64 ? launch_halo_cfg<2>(h, s) : launch_halo_cfg<1>(h, s)) return rc;
-      // (2) the four ring strips of the reflect-padded domain as split-K GEMMs into fp32 slabs
-      const int H = d->H, W = d->W, Ks = p.Ks, Lk = p.ph[0].Lk;
-      const bf16_t* dyb = reinterpret_cast<const bf16_t*>(dy);
-      const bf16_t* pk = reinterpret_cast<const bf16_t*>(pack);
-      const int Mtb = d->N * (W + 2), Mlr = d->N * H;
-      const int nt = (p.Cs + 127) / 128;
-      // the strips have few rows (N (W + 2) and N H); 128-row tiles (two blocks per CU) measured slower (round-2 mode 31, retired)
-      const int bm = 256;
-      const int tiles = 2 * ((Mtb + bm - 1) / bm) * nt + 2 * ((Mlr + bm - 1) / bm) * nt;
-      const int kt = 3 * Ks / 64;
-      int sp = 256 / tiles;
-      if (sp > kt / 8) sp = kt / 8;
-      if (sp > 8) sp = 8;
-      if (sp < 1) sp = 1;
-      float* slab = reinterpret_cast<float*>(wsb);
-      const size_t tb_elems = (size_t)sp * Mtb * p.Cs, lr_elems = (size_t)sp * Mlr * p.Cs;
-      FastBatch rb = {};
-      rb.small_m = 0;
-      for (int q = 0; q < 4; ++q) {
-        FastArgs g = {};
-        const bool row_strip = q < 2;         // 0 top, 1 bottom, 2 left, 3 right
-        g.X = dyb + (q == 1 ? (long long)(H - 1) * W * Ks : (q == 3 ? (long long)(W - 1) * Ks : 0));
-        g.x_sn = (long long)H * W * Ks;
-        g.x_sh = (long long)W * Ks;
-        g.x_extent = (long long)d->N * H * W * Ks - (g.X - dyb);
-        g.IH = row_strip ? 1 : H;
-        g.IW = row_strip ? W : 1;
-        g.Cs = Ks;
-        g.R = row_strip ? 1 : 3;
-        g.S = row_strip ? 3 : 1;
-        g.sy = g.sx = 1;
-        g.py = row_strip ? 0 : 1;
-        g.px = row_strip ? 2 : 0;
-        g.OH = row_strip ? 1 : H;
-        g.OW = row_strip ? W + 2 : 1;
-        g.M = row_strip ? Mtb : Mlr;
-        // panel [c][u'][w'][k] with u' = 2 - r, w' = 2 - s: top r=0 -> u'=2, bottom u'=0, left s=0 -> w'=2, right w'=0
-        g.B = pk + (q == 0 ? 2LL * Lk : (q == 2 ? 2LL * Ks : 0));
-        g.b_stride = 3LL * Lk;
-        g.b_tap_r = Lk;
-        g.b_tap_s = Ks;
-        g.Kout = d->C;
-        g.Ks = p.Cs;
-        g.b_rows = p.Cs;
-        g.act = JPDSE_ACT_NONE;
-        g.splits = sp;
-        g.no_finish = 1;
-        g.partial = slab + (q == 0 ? 0 : (q == 1 ? tb_elems : (q == 2 ? 2 * tb_elems : 2 * tb_elems + lr_elems)));
-        rb.p[rb.n++] = g;
-      }
-      const int pslot = prof_begin(s, p.Cs, 9LL * p.Ks);
-      if (int rc = launch_fast_batch(rb, s)) return rc;
-      // (3) fold the ring into rows 1 / H-2 and columns 1 / W-2 of dx
-      RingFoldArgs rf = {};
-      rf.dx = reinterpret_cast<bf16_t*>(dx);
-      rf.top = rb.p[0].partial;
-      rf.bot = rb.p[1].partial;
-      rf.left = rb.p[2].partial;
-      rf.right = rb.p[3].partial;
-      rf.splits_tb = rf.splits_lr = sp;
-      rf.N = d->N;
-      rf.H = H;
-      rf.W = W;
-      rf.Cs = p.Cs;
-      const long long tv = (long long)d->N * (2 * W + 2 * (H - 2)) * (p.Cs / 8);
-      hipLaunchKernelGGL(ring_fold_kernel, dim3(ew_blocks(tv)), dim3(256), 0, s, rf, tv);
-      int rc = check_launch("ring_fold_kernel");
-      if (rc == JPDSE_OK && mask != nullptr) {
-        const long long total_vec = (long long)d->N * H * W * (p.Cs / 8);
-        hipLaunchKernelGGL((relu_mask_kernel<T>), dim3(ew_blocks(total_vec)), dim3(256), 0, s, reinterpret_cast<T*>(dx),
-                           reinterpret_cast<const T*>(mask), total_vec);
-        rc = check_launch("relu_mask_kernel");
-      }
-      prof_end(pslot, 1, 0.0, s);
-      return rc;
+  if (sink != nullptr && (dgrad_nsum_slots(d, p) == 0 || lrelu))
+    return set_error(JPDSE_EINVAL, "conv_dgrad: this layer's data-gradient kernel writes no norm-backward sums (jpdse_conv_dgrad_nsum_slots == 0)");
+  const DgradCall c = {d, p, dy, pack, dx, ws, s, mask, addend, mom, mask_slope, sink};
+  const DgradRoute route = select_dgrad(d, p, {mask != nullptr, addend != nullptr, lrelu, mom != nullptr, sink != nullptr});
+  if constexpr (sizeof(T) == 2) {      // (the bf16 kernels are not instantiated for fp32 layers, which select_dgrad sends to the generic GEMM)
+    switch (route) {
+      case DgradRoute::rows: return launch_rows(to_rows(dgrad_view(c)), 1, s);
+      case DgradRoute::halo: return p.Cs > 64 ? launch_halo_cfg<2>(to_halo(dgrad_view(c)), s) : launch_halo_cfg<1>(to_halo(dgrad_view(c)), s);
+      case DgradRoute::taps9: return launch_taps9(dgrad_view(c), splitk_slabs(p, ws), s);
+      case DgradRoute::ring_taps9_frame:
+      case DgradRoute::ring_halo_frame: return dgrad_ring_frame(c, route);
+      case DgradRoute::ring_taps9_strips:
+      case DgradRoute::ring_halo_strips: return dgrad_ring_strips(c, route);
+      case DgradRoute::head: return dgrad_head(c);
+      case DgradRoute::dgrad2_rows: return dgrad_dgrad2_rows(c);
+      case DgradRoute::thin_dgrad2_rows: return dgrad_thin_dgrad2_rows(c);
+      case DgradRoute::thin_in_rows: return dgrad_thin_in_rows(c);
+      case DgradRoute::taps_dgrad2: return launch_taps_dgrad2(d, p, dy, pack, dx, s, mask, addend, mask_slope);
+      case DgradRoute::taps4: return launch_taps4(dgrad_view(c), ws, s);
+      case DgradRoute::thin1: return dgrad_thin1(c);
+      case DgradRoute::fast: return dgrad_fast(c);
+      default: break;
     }
   }
-  if constexpr (sizeof(T) == 2) {
-    // few INPUT channels (VGG conv1_1: 3 <- 64): the data gradient is itself a conv with <= 3 output channels; the
-    // single-phase dgrad panel [c][u'][w'][k] is exactly the "plain forward panel" head_fwd_kernel expects
-    if (g_fast_enabled && g_head_fwd_enabled && !refl && st == 1 && d->R == 3 && d->S == 3 && d->pad == 1 && d->C <= 3 &&
-        p.Cs == 8 && p.Ks == 64 && p.nph == 1 && p.ph[0].Lk == 3 * p.Ks && mask == nullptr && addend == nullptr) {
-      HeadFwdArgs h = {};
-      h.X = reinterpret_cast<const bf16_t*>(dy);
-      h.Wp = reinterpret_cast<const bf16_t*>(pack);
-      h.Y = reinterpret_cast<bf16_t*>(dx);
-      h.N = d->N;
-      h.H = p.OH;
-      h.W = p.OW;
-      h.OH = d->H;
-      h.OW = d->W;
-      h.K = d->C;
-      h.Ks_out = p.Cs;
-      h.R = 3;
-      h.S = 3;
-      h.pad = 1;
-      h.act = JPDSE_ACT_NONE;
-      h.tiles_w = (d->W + 63) / 64;
-      h.tiles_h = (d->H + kHeadTH - 1) / kHeadTH;
-      if (head_rows_ok(h, 64)) return launch_head_rows<3>(h, s);
-      return launch_head_fwd<64, 3, 3, 3>(h, s);
-    }
-  }
-  if constexpr (sizeof(T) == 2) {
-    if (g_fast_enabled && g_rows_enabled && !refl && st == 2 && d->R == 3 && d->S == 3 && d->pad == 1 && p.Ks == 128 && p.Cs == 64 &&
-        d->C == 64 && d->H == 2 * p.OH && d->W == 2 * p.OW && p.OW % 64 == 0 && p.OH % 4 == 0 && p.nph == 4 &&
-        mask == nullptr && addend == nullptr) {
-      Dgrad2Args g = {};
-      g.DY = reinterpret_cast<const bf16_t*>(dy);
-      for (int i = 0; i < 4; ++i) g.P[i] = reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(pack) + p.ph[i].pack_off);
-      g.DX = reinterpret_cast<bf16_t*>(dx);
-      g.N = d->N;
-      g.OH = p.OH;
-      g.OW = p.OW;
-      g.mom = mom;
-      return launch_dgrad2_rows(g, s);
-    }
-  }
-  if constexpr (sizeof(T) == 2) {
-    if (g_fast_enabled && g_rows_enabled && !refl && st == 2 && d->R == 4 && d->S == 4 && d->pad == 2 && p.Cs == 8 && d->C <= 3 &&
-        p.Ks == 64 && d->H % 8 == 0 && d->W % 256 == 0 && p.OH == d->H / 2 + 1 && p.OW == d->W / 2 + 1 && p.nph == 4 &&
-        p.ph[0].Lk == 128 && mask == nullptr && addend == nullptr) {
-      ThinDgrad2Args g = {};
-      g.DY = reinterpret_cast<const bf16_t*>(dy);
-      for (int i = 0; i < 4; ++i) g.P[i] = reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(pack) + p.ph[i].pack_off);
-      g.DX = reinterpret_cast<bf16_t*>(dx);
-      g.N = d->N;
-      g.OH = p.OH;
-      g.OW = p.OW;
-      g.H = d->H;
-      g.W = d->W;
-      g.K = d->C;
-      return launch_thin_dgrad2_rows(g, s);
-    }
-  }
-  if constexpr (sizeof(T) == 2) {
-    if (g_fast_enabled && g_rows_enabled && refl && st == 1 && d->R == 7 && d->S == 7 && d->pad == 3 && p.Ks == 8 && p.Cs == 64 &&
-        d->C == 64 && d->H >= 8 && d->W >= 8 && p.nph == 1 && p.ph[0].Lk == 64 && mask == nullptr && addend == nullptr) {
-      ThinInArgs g = {};
-      g.DY = reinterpret_cast<const bf16_t*>(dy);
-      g.P = reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(pack) + p.ph[0].pack_off);
-      g.DX = reinterpret_cast<bf16_t*>(dx);
-      g.DXP = reinterpret_cast<bf16_t*>(dxp);
-      g.N = d->N;
-      g.H = d->H;
-      g.W = d->W;
-      g.OH = d->H + 6;
-      g.OW = d->W + 6;
-      g.py = g.px = 6;
-      g.act = JPDSE_ACT_NONE;
-      return launch_thin_in_rows<7, true>(g, s);
-    }
-  }
-  if constexpr (sizeof(T) == 2) {
-    if (taps_dgrad2_ok(d, p, mom)) return launch_taps_dgrad2(d, p, dy, pack, dx, s, mask, addend, mask_slope);
-    if (whole && st == 1 && mom == nullptr && taps4_shape_ok(v)) return launch_taps4(v, ws, s);
-  }
-  if constexpr (sizeof(T) == 2) {
-    // one output channel (PatchGAN 512 -> 1): dx is written once by an FMA kernel (thin_out1.h)
-    if (thin1_shape_ok(d, p.Cs, p.Ks) && p.nph == 1 && mask == nullptr && mom == nullptr && p.ph[0].Uh == 4 && p.ph[0].Uw == 4 &&
-        p.ph[0].cnth == d->H && p.ph[0].cntw == d->W) {
-      const Phase& f = p.ph[0];
-      Thin1DgradArgs t = {};
-      t.DY = reinterpret_cast<const bf16_t*>(dy);
-      t.B = reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(pack) + f.pack_off);
-      t.taps = reinterpret_cast<float*>(wsb);        // 16 x Cs floats: inside the padded-dy region of every plan
-      t.DX = reinterpret_cast<bf16_t*>(dx);
-      t.addend = reinterpret_cast<const bf16_t*>(addend);
-      t.N = d->N;
-      t.H = d->H;
-      t.W = d->W;
-      t.Cs = p.Cs;
-      t.OH = p.OH;
-      t.OW = p.OW;
-      t.py = (f.Uh - 1) - f.i0h;
-      t.px = (f.Uw - 1) - f.i0w;
-      t.Lk = f.Lk;
-      t.b_stride = (long long)f.Uh * f.Lk;
-      return launch_thin1_dgrad(t, s);
-    }
-  }
-  bool fast = false;
-  int nlive_phases = 0;
-  if constexpr (sizeof(T) == 2) {
-    // all stride phases go into ONE launch of the fast kernel: judge the merged grid
-    fast = p.Ks % 64 == 0;
-    long long tiles = 0;
-    int kt_max = 0, nlive = 0, m_single = 0;
-    const int bn = p.Cs > 64 ? 128 : (p.Cs > 32 ? 64 : 32);
-    for (int i = 0; i < p.nph; ++i) {
-      if (p.ph[i].cnth <= 0 || p.ph[i].cntw <= 0) continue;
-      const int Mi = d->N * p.ph[i].cnth * p.ph[i].cntw;
-      tiles += (long long)((Mi + 255) / 256) * ((p.Cs + bn - 1) / bn);
-      const int kt = p.ph[i].Uh * p.ph[i].Uw * p.Ks / 64;
-      kt_max = kt > kt_max ? kt : kt_max;
-      m_single = Mi;
-      ++nlive;
-    }
-    nlive_phases = nlive;
-    if (nlive == 1) fast = fast && fast_pays(m_single, p.Cs, kt_max);
-    else fast = fast && g_fast_enabled && p.Cs > 32 && kt_max >= g_merge_min_kt && tiles >= g_merge_min_tiles;   // few tiles / short K loops: generic wins
-  }
-  FastBatch batch = {};
-  int rc = JPDSE_OK;
-  if (!fast) {
-    rc = launch_pad<T>(dy, dyp, d->N, p.OH, p.OW, p.Ks, p.PT, p.PB, p.PL, p.PR, JPDSE_PAD_ZERO, s);
-    if (rc) return rc;
-  }
-  for (int i = 0; i < p.nph; ++i) {
-    const Phase& f = p.ph[i];
-    if (f.cnth <= 0 || f.cntw <= 0) continue;
-    if constexpr (sizeof(T) == 2) {
-      if (fast) {
-        FastArgs g = to_fast(view_dgrad_phase(d, p, i, dy, pack, dx));
-        if (refl) {               // onto the padded domain; reflect_fold_kernel and the unfused pass below finish it
-          g.Y = reinterpret_cast<bf16_t*>(dxp);
-          g.out_sn = (long long)p.Hp * p.Wp * p.Cs;
-          g.out_sh = (long long)st * p.Wp * p.Cs;
-          g.out_sw = (long long)st * p.Cs;
-          g.out_base = ((long long)(st * f.i0h + f.qh) * p.Wp + (st * f.i0w + f.qw)) * p.Cs;
-        } else {
-          g.mask = v.mask;
-          g.addend = v.addend;
-        }
-        g.mask_slope = mask_slope;
-        g.splits = nlive_phases == 1 ? splitk_for(g.M, p.Cs, f.Uh * f.Uw * p.Ks / 64) : 1;
-        g.partial = reinterpret_cast<float*>(wsb + p.splitk_off);
-        batch.p[batch.n++] = g;
-        continue;
-      }
-    }
-    GemmFwdArgs a = {};
-    a.A = dyp;
-    a.B = reinterpret_cast<const char*>(pack) + f.pack_off;
-    a.bias = nullptr;
-    a.M = d->N * f.cnth * f.cntw;
-    a.OH = f.cnth;
-    a.OW = f.cntw;
-    a.Kout = d->C;
-    a.Ks = p.Cs;
-    a.R = f.Uh;
-    a.cpr = f.Lk / p.BKE;
-    a.b_rows = p.Cs;
-    a.b_row_stride = (long long)f.Uh * f.Lk;
-    a.in_sn = (long long)p.DH * p.DW * p.Ks;
-    a.in_sh = (long long)p.DW * p.Ks;
-    a.in_sw = p.Ks;
-    a.in_sr = (long long)p.DW * p.Ks;
-    a.in_base = ((long long)(f.i0h + p.PT - (f.Uh - 1)) * p.DW + (f.i0w + p.PL - (f.Uw - 1))) * p.Ks;
-    if (refl) {
-      a.Y = dxp;
-      a.out_sn = (long long)p.Hp * p.Wp * p.Cs;
-      a.out_sh = (long long)st * p.Wp * p.Cs;
-      a.out_sw = (long long)st * p.Cs;
-      a.out_base = ((long long)(st * f.i0h + f.qh) * p.Wp + (st * f.i0w + f.qw)) * p.Cs;
-    } else {
-      a.Y = dx;
-      a.out_sn = (long long)d->H * d->W * p.Cs;
-      a.out_sh = (long long)st * d->W * p.Cs;
-      a.out_sw = (long long)st * p.Cs;
-      a.out_base = ((long long)(st * f.i0h + f.qh - d->pad) * d->W + (st * f.i0w + f.qw - d->pad)) * p.Cs;
-    }
-    a.act = JPDSE_ACT_NONE;
-    a.slope = 0.f;
-    a.partial = reinterpret_cast<float*>(wsb + p.splitk_off);     // split-K slabs, reused by the phases (stream order)
-    a.partial_cap = p.splitk_bytes;
-    rc = launch_fwd<T>(a, s);
-    if (rc) return rc;
-  }
-  if (batch.n > 0) {
-    rc = launch_fast_batch(batch, s);
-    if (rc) return rc;
-  }
-  if (refl) {
-    const int VE = 16 / (int)sizeof(T);
-    const long long total_vec = (long long)d->N * d->H * d->W * (p.Cs / VE);
-    hipLaunchKernelGGL((reflect_fold_kernel<T>), dim3(ew_blocks(total_vec)), dim3(256), 0, s,
-                       reinterpret_cast<const T*>(dxp), reinterpret_cast<T*>(dx), d->N, d->H, d->W, p.Cs, d->pad,
-                       total_vec);
-    rc = check_launch("reflect_fold_kernel");
-  }
-  if (rc == JPDSE_OK && (mask != nullptr || addend != nullptr) && !(fast && !refl)) {
-    const int VE = 16 / (int)sizeof(T);
-    const long long total_vec = (long long)d->N * d->H * d->W * (p.Cs / VE);
-    hipLaunchKernelGGL((relu_mask_kernel<T>), dim3(ew_blocks(total_vec)), dim3(256), 0, s, reinterpret_cast<T*>(dx),
-                       reinterpret_cast<const T*>(mask), total_vec, reinterpret_cast<const T*>(addend), mask_slope);
-    rc = check_launch("relu_mask_kernel");
-  }
-  return rc;
+  return dgrad_generic<T>(c);
 }
 
 }  // namespace jpdse

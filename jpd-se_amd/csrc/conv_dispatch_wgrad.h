@@ -1,5 +1,6 @@
 // Weight-gradient launchers and dispatch of the convolution family (all split reductions go through fp32 slabs summed in a
-// fixed order: no atomics).  Part of conv_gemm.hip (one translation unit).
+// fixed order: no atomics).  conv_wgrad_t launches the route select_wgrad (conv_route.h) chose; wgrad_slab_bytes asks the same
+// route for its slab size.  Part of conv_gemm.hip (one translation unit).
 #pragma once
 
 namespace jpdse {
@@ -29,15 +30,28 @@ static void fast_wgrad_partition(FastWgArgs* a, int lds) {
   a->slab_stride = ((long long)a->K * a->R * a->S * a->C + 3) / 4 * 4;
 }
 
-template <int WM, int WN, int TM, int TN>
-static int launch_wgrad_fast_cfg(FastWgArgs a, float* slabs, size_t* slab_bytes_out, hipStream_t s) {
-  constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-  constexpr int lds = 2 * 64 * 2 * (BM + BN);
+template <int WM_, int WN_, int TM_, int TN_>
+struct WgFastCfg {
+  static constexpr int WM = WM_, WN = WN_, TM = TM_, TN = TN_, BM = WM * TM * 32, BN = WN * TN * 32, lds = 2 * 64 * 2 * (BM + BN);
+};
+// f(the tile configuration of the fast weight-gradient kernel for problem a): the launch and the slab query choose alike
+template <typename F>
+static auto with_wgrad_fast_cfg(const FastWgArgs& a, F&& f) {
+  const int cols = a.run_mode ? a.run_len : a.Cs;
+  const bool m2 = a.Ks >= 128, n2 = cols >= 128;
+  // 256 x 256 tiles, 8 waves, one block per CU.  (Round 3 tried 128 x 128 tiles, two blocks per CU, for the short reductions
+  // of the LocalEnhancer trunk -- 144 large tiles cover 56 % of the chip -- and measured it 0.45 ms per step SLOWER.)
+  if (a.Ks >= 256 && cols >= 256 && a.Ks % 256 == 0 && cols % 256 == 0 && !a.run_mode) return f(WgFastCfg<2, 4, 4, 2>{});
+  if (m2 && n2) return f(WgFastCfg<2, 2, 2, 2>{});
+  if (m2) return f(WgFastCfg<2, 2, 2, 1>{});
+  if (n2) return f(WgFastCfg<2, 2, 1, 2>{});
+  return f(WgFastCfg<2, 2, 1, 1>{});
+}
+
+template <typename Cfg>
+static int launch_wgrad_fast_cfg(FastWgArgs a, float* slabs, hipStream_t s) {
+  constexpr int WM = Cfg::WM, WN = Cfg::WN, TM = Cfg::TM, TN = Cfg::TN, BM = Cfg::BM, BN = Cfg::BN, lds = Cfg::lds;
   fast_wgrad_partition<BM, BN>(&a, lds);
-  if (slab_bytes_out != nullptr) {        // workspace query only
-    *slab_bytes_out = a.splits > 1 ? (size_t)a.splits * a.slab_stride * sizeof(float) : 0;
-    return JPDSE_OK;
-  }
   if (int rc = opt_in_lds<&wgrad_fast_kernel<WM, WN, TM, TN>>("wgrad_fast", lds)) return rc;
   const int tiles = ((a.Ks + BM - 1) / BM) * (a.run_mode ? a.R : a.R * a.S) *
                     (((a.run_mode ? a.run_len : a.Cs) + BN - 1) / BN);
@@ -46,19 +60,14 @@ static int launch_wgrad_fast_cfg(FastWgArgs a, float* slabs, size_t* slab_bytes_
   if (int rc = check_launch("wgrad_fast_kernel")) return rc;
   return a.splits > 1 ? launch_slab_reduce(slabs, a.DW, (long long)a.K * a.R * a.S * a.C, a.slab_stride, a.splits, s) : JPDSE_OK;
 }
-
-// slab_bytes_out != nullptr: report the slab bytes the launch would need instead of launching (workspace query)
-static int launch_wgrad_fast(const FastWgArgs& a, float* slabs, hipStream_t s, size_t* slab_bytes_out = nullptr) {
-  const int cols = a.run_mode ? a.run_len : a.Cs;
-  const bool m2 = a.Ks >= 128, n2 = cols >= 128;
-  // 256 x 256 tiles, 8 waves, one block per CU.  (Round 3 tried 128 x 128 tiles, two blocks per CU, for the short reductions
-  // of the LocalEnhancer trunk -- 144 large tiles cover 56 % of the chip -- and measured it 0.45 ms per step SLOWER.)
-  if (a.Ks >= 256 && cols >= 256 && a.Ks % 256 == 0 && cols % 256 == 0 && !a.run_mode)
-    return launch_wgrad_fast_cfg<2, 4, 4, 2>(a, slabs, slab_bytes_out, s);
-  if (m2 && n2) return launch_wgrad_fast_cfg<2, 2, 2, 2>(a, slabs, slab_bytes_out, s);
-  if (m2) return launch_wgrad_fast_cfg<2, 2, 2, 1>(a, slabs, slab_bytes_out, s);
-  if (n2) return launch_wgrad_fast_cfg<2, 2, 1, 2>(a, slabs, slab_bytes_out, s);
-  return launch_wgrad_fast_cfg<2, 2, 1, 1>(a, slabs, slab_bytes_out, s);
+static int launch_wgrad_fast(const FastWgArgs& a, float* slabs, hipStream_t s) {
+  return with_wgrad_fast_cfg(a, [&](auto cfg) { return launch_wgrad_fast_cfg<decltype(cfg)>(a, slabs, s); });
+}
+static size_t wgrad_fast_slab_bytes(FastWgArgs a) {
+  return with_wgrad_fast_cfg(a, [&](auto cfg) {
+    fast_wgrad_partition<decltype(cfg)::BM, decltype(cfg)::BN>(&a, decltype(cfg)::lds);
+    return a.splits > 1 ? (size_t)a.splits * a.slab_stride * sizeof(float) : (size_t)0;
+  });
 }
 
 template <int TM, int NW, int NT, int RR, int WM, int PITCH>
@@ -116,12 +125,6 @@ static int launch_wgrad_thin_pitch(ThinWgArgs a, hipStream_t s) {
   return launch_slab_reduce(a.partial, a.DW, (long long)a.K * a.R * a.S * a.C, a.slab_stride, a.ranges, s);
 }
 
-static bool wgrad_thin_ok(const jpdse_conv_desc* d, const ConvPlan& p) {
-  const int n_tiles = (d->S * p.Cs + 31) / 32;
-  return g_fast_enabled && p.Cs % 64 != 0 && (p.Ks == 32 || p.Ks == 64) && n_tiles <= 12 &&
-         (126 * d->stride * p.Cs + 64 * 12) <= 20 * 1024;
-}
-
 static int launch_wgrad_thin(const ThinWgArgs& a, hipStream_t s) {
   const int n_tiles = (a.S * a.Cs + 31) / 32;
   if (a.Ks == 64) {
@@ -134,25 +137,8 @@ static int launch_wgrad_thin(const ThinWgArgs& a, hipStream_t s) {
   return launch_wgrad_thin_cfg<1, 4, 3>(a, s);
 }
 
-// ---- all-taps weight gradient of the narrow high-resolution layers (wgrad_taps.h) -----------------
-// config id: 0 none; 1: 3x3 s2 K%128 C%64; 2: 3x3 s1 K%64 C%64; 3: 4x4 s2 K%128 C%64; 4: 3x3 s2 K%256 C%128
-JPDSE_SWITCH(int, g_wgrad_taps_enabled, 1);
+// ---- all-taps weight gradient of the narrow high-resolution layers (wgrad_taps.h; wgrad_taps_cfg, conv_route.h, says which config)
 JPDSE_SWITCH(int, g_wgrad_taps_xcd, 0);           // 58: XCD co-location of the tiles of a pixel range (A/B; measured 0-13 % slower)
-static int wgrad_taps_cfg(const jpdse_conv_desc* d, const ConvPlan& p) {
-  if (!g_fast_enabled || !g_wgrad_taps_enabled || p.ES != 2 || d->R != d->S) return 0;
-  if ((long long)d->N * p.OH * ((p.OW + 63) / 64) < 32) return 0;
-  if ((long long)d->N * p.OH * p.OW * p.Ks >= (1LL << 31) || (long long)d->N * d->H * d->W * p.Cs >= (1LL << 31)) return 0;
-  // 3x3 stride 2 with wide outputs, any width: the down-sampling convs 128 -> 256 ... 512 -> 1024 and, with the roles of
-  // x and dy swapped by the caller, the ConvTranspose2d layers 1024 -> 512 ... 128 -> 64 (round 1 sent the wide ones to
-  // the per-tap kernel, whose stream-K partial tiles met in fp32 atomics)
-  if (d->R == 3 && d->stride == 2 && p.Ks % 256 == 0 && p.Cs % 64 == 0) return 4;      // (round 3: the all-nine-taps config 1 on these wide layers measured -3 ... -11 %, +5 % only at 512 -> 1024)
-  if (p.Ks > 256 || p.Cs > 128) return 0;
-  if (d->R == 3 && d->stride == 2 && p.Ks % 128 == 0 && p.Cs % 64 == 0) return 1;
-  if (d->R == 3 && d->stride == 1 && p.Ks % 64 == 0 && p.Ks <= 128 && p.Cs % 64 == 0) return 2;
-  if (d->R == 4 && d->stride == 2 && p.Ks % 128 == 0 && p.Cs % 64 == 0) return 3;
-  return 0;
-}
-
 struct TapsGeom { int BM, BN, T, NROW, lds, blocks_per_cu, bkp; };
 // LDS of one launch: stages x (dy tile + patch units + one scratch unit), wgrad_taps.h
 static constexpr int taps_lds(int BM, int S, int NROW, int ST, int bkp, int stages) {
@@ -269,19 +255,6 @@ static int launch_wgrad_taps(const jpdse_conv_desc* d, const ConvPlan& p, int cf
 }
 
 // ---- all-nine-taps weight gradient of the wide 3x3 stride-1 layers (wgrad_nine.h): no atomics, no partial tiles ----
-JPDSE_SWITCH(int, g_wgrad_nine_enabled, 1);
-JPDSE_SWITCH(int, g_wgrad_nine32_enabled, 1);     // 55: 32-pixel-wide images on the per-tap kernel, as before round 4 (A/B)
-// images 32 pixels wide (the LocalEnhancer's 1024-channel trunk at 16 x 32): the row-pair form of the kernel (wgrad_nine.h, W32)
-static bool wgrad_nine32_shape(const jpdse_conv_desc* d, const ConvPlan& p) {
-  return g_wgrad_nine32_enabled && d->W == 32 && p.OW == 32 && d->H % 2 == 0 && d->H >= 4 && d->pad_mode == JPDSE_PAD_REFLECT &&
-         p.Ks >= 256 && p.Cs >= 256;         // wide layers only: 64 k x 64 c tiles must fill the chip
-}
-static bool wgrad_nine_ok(const jpdse_conv_desc* d, const ConvPlan& p) {
-  return g_fast_enabled && g_wgrad_nine_enabled && p.ES == 2 && d->R == 3 && d->S == 3 && d->stride == 1 && d->pad == 1 &&
-         (p.OW % 64 == 0 || wgrad_nine32_shape(d, p)) && p.Ks % 64 == 0 && p.Cs % 64 == 0 && d->H >= 2 && d->W >= 8 &&
-         (long long)d->N * d->H * d->W * (p.Ks > p.Cs ? p.Ks : p.Cs) < (1LL << 31);
-}
-
 static void nine_partition(const jpdse_conv_desc* d, const ConvPlan& p, NineWgArgs* a) {
   const bool w32 = p.OW % 64 != 0;           // wgrad_nine_ok: then the row-pair form (chunk = two image rows)
   a->strips = w32 ? 1 : d->W / 64;
@@ -315,16 +288,16 @@ static int launch_wgrad_nine_cfg(const NineWgArgs& a, hipStream_t s) {
   const int blocks = a.k_tiles * a.c_tiles * a.splits;
   if (W32 && (a.W != 32 || (a.H & 1) || a.chunks_total != a.N * (a.H / 2)))
     return set_error(JPDSE_EINVAL, "wgrad_nine: the row-pair form needs 32-pixel-wide images with an even number of rows");
-  const int pslot = prof_begin(s, a.Ks, 9LL * a.Cs);
+  const int pslot = prof_begin(s, a.Ks, 9LL * a.Cs);      // (behind the argument checks; nothing below returns before prof_end)
   hipLaunchKernelGGL((wgrad_nine_kernel<REFLECT, W32>), dim3(blocks), dim3(512), kNineLds, s, a);
-  if (int rc = check_launch("wgrad_nine_kernel")) return rc;
-  if (a.splits > 1) {
+  int rc = check_launch("wgrad_nine_kernel");
+  if (rc == JPDSE_OK && a.splits > 1) {
     const long long n4 = (long long)a.K * 9 * a.C / 4;
     hipLaunchKernelGGL(wgrad_nine_reduce_kernel, dim3(ew_blocks(n4)), dim3(256), 0, s, a.partial, a.DW, n4, a.splits);
-    if (int rc = check_launch("wgrad_nine_reduce_kernel")) return rc;
+    rc = check_launch("wgrad_nine_reduce_kernel");
   }
   prof_end(pslot, 2, 2.0 * (double)a.N * a.H * a.W * (double)a.Ks * 9.0 * (double)a.Cs, s);
-  return JPDSE_OK;
+  return rc;
 }
 
 static int launch_wgrad_nine(const jpdse_conv_desc* d, const ConvPlan& p, const void* x, const void* dy, float* dw,
@@ -349,12 +322,6 @@ static int launch_wgrad_nine(const jpdse_conv_desc* d, const ConvPlan& p, const 
   return launch_wgrad_nine_cfg<true>(a, s);
 }
 
-// heads with <= 8 output channels on a 32- / 64-channel input, stride 1 (64->3, 32->3 7x7)
-static bool wgrad_head_ok(const jpdse_conv_desc* d, const ConvPlan& p) {
-  return g_fast_enabled && p.Ks == 8 && d->stride == 1 && (p.Cs == 32 || p.Cs == 64) && d->S * 8 <= 64 && d->R <= 7 &&
-         d->R == d->S;
-}
-
 static int launch_wgrad_head(const ThinWgArgs& a, hipStream_t s) {
   // 2 waves x 1 run tile (S*8 <= 64 columns), all R <= 7 filter rows per block
   return a.Ks == 64 ? launch_wgrad_thin_cfg<1, 2, 1, 7, 2>(a, s) : launch_wgrad_thin_cfg<1, 2, 1, 7>(a, s);
@@ -373,218 +340,182 @@ static size_t wgrad_front_bytes(const jpdse_conv_desc* d, const ConvPlan& p) {
   return align_up(p.xpad_bytes + dz, 256);
 }
 
-template <typename T>
-static int conv_wgrad_t(const jpdse_conv_desc* d, const ConvPlan& p, const void* x, const void* dy, float* dw,
-                        void* ws, hipStream_t s, size_t* slab_bytes_out = nullptr) {
-  // slab_bytes_out != nullptr: dry run for jpdse_conv_workspace_size -- follows the dispatch below and reports the slab
-  // bytes of the path that would run, launching nothing
-  float* const slabs = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + wgrad_front_bytes(d, p));
-  const bool dry = slab_bytes_out != nullptr;
-  if (dry) *slab_bytes_out = 0;
-  if constexpr (sizeof(T) == 2) {
-    if (thin1_shape_ok(d, p.Cs, p.Ks)) {
-      // one output channel (PatchGAN 512 -> 1): x read once by an FMA kernel, no copies (thin_out1.h)
-      if (dry) {
-        *slab_bytes_out = thin1_wgrad_slab_bytes(d->N, d->H, d->W, p.Cs);
-        return JPDSE_OK;
-      }
-      Thin1WgradArgs t = {};
-      t.X = reinterpret_cast<const bf16_t*>(x);
-      t.DY = reinterpret_cast<const bf16_t*>(dy);
-      t.partial = slabs;
-      t.N = d->N;
-      t.H = d->H;
-      t.W = d->W;
-      t.Cs = p.Cs;
-      t.OH = p.OH;
-      t.OW = p.OW;
-      t.pad = d->pad;
-      return launch_thin1_wgrad(t, dw, s);
-    }
-    const int kexp = d->K * d->R * d->S, kexp_s = round_up(kexp, 64);
-    if (g_fast_enabled && !wgrad_head_ok(d, p) && p.Ks == 8 && d->stride == 1 && p.Cs % 64 == 0 && kexp_s <= 256) {
-      // few output channels: dense 1x1 weight gradient over the tap-expanded dy (see expand_dy_taps_kernel)
-      bf16_t* dz = reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(ws) + p.xpad_bytes);
-      FastWgArgs f = {};
-      f.X = reinterpret_cast<const bf16_t*>(ws);
-      f.DY = dz;
-      f.DW = dw;
-      f.M = d->N * p.Hp * p.Wp;
-      f.OH = p.Hp;
-      f.OW = p.Wp;
-      f.IH = p.Hp;
-      f.IW = p.Wp;
-      f.Cs = p.Cs;
-      f.C = d->C;
-      f.Ks = kexp_s;
-      f.K = kexp;
-      f.R = f.S = 1;
-      f.sy = f.sx = 1;
-      f.py = f.px = 0;
-      f.reflect = 0;
-      if (dry) return launch_wgrad_fast(f, nullptr, s, slab_bytes_out);
-      if (int rc = launch_pad<T>(x, ws, d->N, d->H, d->W, p.Cs, d->pad, d->pad, d->pad, d->pad, d->pad_mode, s))
-        return rc;
-      const long long tv = (long long)d->N * p.Hp * p.Wp * (kexp_s / 8);
-      hipLaunchKernelGGL(expand_dy_taps_kernel, dim3(ew_blocks(tv)), dim3(256), 0, s,
-                         reinterpret_cast<const bf16_t*>(dy), dz, p.OH, p.OW, p.Ks, d->K, d->R, d->S, p.Hp, p.Wp,
-                         kexp_s, tv);
-      if (int rc = check_launch("expand_dy_taps_kernel")) return rc;
-      return launch_wgrad_fast(f, slabs, s);
-    }
-    if (const int tcfg = wgrad_taps_cfg(d, p)) return dry ? JPDSE_OK : launch_wgrad_taps(d, p, tcfg, x, dy, dw, ws, s);
-    if (wgrad_nine_ok(d, p) && ((long long)d->K * 9 * d->C) % 4 == 0)
-      return dry ? JPDSE_OK : launch_wgrad_nine(d, p, x, dy, dw, ws, s);
-    if (wgrad_head_ok(d, p)) {
-      // roles swapped (see wgrad_thin.h): A = padded input, run operand = dy zero-padded by (R-1, S-1); both
-      // paddings are resolved by the loader
-      ThinWgArgs t = {};
-      t.XP = reinterpret_cast<const bf16_t*>(dy);
-      t.DY = reinterpret_cast<const bf16_t*>(x);
-      t.DW = dw;
-      t.N = d->N;
-      t.OH = p.Hp;
-      t.OW = p.Wp;
-      t.Hp = p.OH + 2 * (d->R - 1);
-      t.Wp = p.OW + 2 * (d->S - 1);
-      t.Cs = 8;
-      t.C = d->K;
-      t.Ks = p.Cs;
-      t.K = d->C;
-      t.R = d->R;
-      t.S = d->S;
-      t.st = 1;
-      t.unpadded = 1;
-      t.RH = p.OH;
-      t.RW = p.OW;
-      t.r_pad = d->R - 1;            // square filters on this path (R == S checked by wgrad_head_ok)
-      t.r_reflect = 0;
-      t.AH = d->H;
-      t.AW = d->W;
-      t.a_pad = d->pad;
-      t.a_reflect = d->pad_mode == JPDSE_PAD_REFLECT;
-      t.transposed = 1;
-      t.partial = slabs;
-      if (dry) {
-        *slab_bytes_out = thin_wgrad_slab_bytes(t, 7);
-        return JPDSE_OK;
-      }
-      return launch_wgrad_head(t, s);
-    }
-    if (wgrad_thin_ok(d, p)) {
-      // thin inputs (40-channel network inputs): input strips staged once (wgrad_thin.h)
-      ThinWgArgs t = {};
-      t.XP = reinterpret_cast<const bf16_t*>(x);
-      t.DY = reinterpret_cast<const bf16_t*>(dy);
-      t.DW = dw;
-      t.N = d->N;
-      t.OH = p.OH;
-      t.OW = p.OW;
-      t.Hp = p.Hp;
-      t.Wp = p.Wp;
-      t.Cs = p.Cs;
-      t.C = d->C;
-      t.Ks = p.Ks;
-      t.K = d->K;
-      t.R = d->R;
-      t.S = d->S;
-      t.st = d->stride;
-      t.partial = slabs;
-      if (dry) {
-        *slab_bytes_out = thin_wgrad_slab_bytes(t, 1);
-        return JPDSE_OK;
-      }
-      if (d->stride == 2) {
-        // padding resolved by the loader (no padded copy): pays for the stride-2 layers (PatchGAN layer 0)
-        t.unpadded = 1;
-        t.RH = d->H;
-        t.RW = d->W;
-        t.r_pad = d->pad;
-        t.r_reflect = d->pad_mode == JPDSE_PAD_REFLECT;
-        t.AH = p.OH;
-        t.AW = p.OW;
-      } else {
-        // 7x7 stride-1 first convs: 7 filter rows re-read every strip, the per-lane padding arithmetic costs more
-        // than one pass of pad_kernel (measured 0.65 vs 0.84 ms)
-        if (int rc = launch_pad<T>(x, ws, d->N, d->H, d->W, p.Cs, d->pad, d->pad, d->pad, d->pad, d->pad_mode, s))
-          return rc;
-        t.XP = reinterpret_cast<const bf16_t*>(ws);
-        t.x_limit = (long long)d->N * p.Hp * p.Wp * p.Cs + (long long)(kSlackBytes / 2);
-      }
-      return launch_wgrad_thin(t, s);
-    }
-    // the fast kernel's loader uses 32-bit element offsets
-    const bool fits32 = (long long)d->N * p.OH * p.OW * p.Ks < (1LL << 31) &&
-                        (long long)d->N * p.Hp * p.Wp * p.Cs < (1LL << 31);
-    if (g_fast_enabled && p.Ks % 64 == 0 && fits32) {
-      FastWgArgs f = {};
-      f.DY = reinterpret_cast<const bf16_t*>(dy);
-      f.DW = dw;
-      f.M = d->N * p.OH * p.OW;
-      f.OH = p.OH;
-      f.OW = p.OW;
-      f.Cs = p.Cs;
-      f.C = d->C;
-      f.Ks = p.Ks;
-      f.K = d->K;
-      f.R = d->R;
-      f.S = d->S;
-      f.sy = f.sx = d->stride;
-      if (p.Cs % 64 == 0) {
-        f.X = reinterpret_cast<const bf16_t*>(x);
-        f.IH = d->H;
-        f.IW = d->W;
-        f.py = f.px = d->pad;
-        f.reflect = d->pad_mode == JPDSE_PAD_REFLECT;
-      } else {
-        // run mode over the materially padded input (40-channel network inputs, 8-channel images)
-        if (!dry)
-          if (int rc = launch_pad<T>(x, ws, d->N, d->H, d->W, p.Cs, d->pad, d->pad, d->pad, d->pad, d->pad_mode, s))
-            return rc;
-        f.X = reinterpret_cast<const bf16_t*>(ws);
-        f.IH = p.Hp;
-        f.IW = p.Wp;
-        f.py = f.px = 0;
-        f.reflect = 0;
-        f.run_mode = 1;
-        f.run_len = d->S * p.Cs;
-      }
-      return launch_wgrad_fast(f, slabs, s, slab_bytes_out);
-    }
+struct WgradCall {      // what a weight-gradient route is handed; the slab query hands it null tensors
+  const jpdse_conv_desc* d; const ConvPlan& p;
+  const void* x; const void* dy; float* dw; void* ws; hipStream_t s;
+};
+static float* wgrad_slabs(const WgradCall& c) { return reinterpret_cast<float*>(reinterpret_cast<char*>(c.ws) + wgrad_front_bytes(c.d, c.p)); }
+static int wgrad_pad_x(const WgradCall& c) {      // the materially padded input at the front of the workspace
+  const jpdse_conv_desc* d = c.d;
+  return d->dtype == JPDSE_BF16 ? launch_pad<bf16_t>(c.x, c.ws, d->N, d->H, d->W, c.p.Cs, d->pad, d->pad, d->pad, d->pad, d->pad_mode, c.s)
+                                : launch_pad<float>(c.x, c.ws, d->N, d->H, d->W, c.p.Cs, d->pad, d->pad, d->pad, d->pad, d->pad_mode, c.s);
+}
+
+static int wgrad_thin1(const WgradCall& c) {      // x read once by an FMA kernel, no copies (thin_out1.h)
+  Thin1WgradArgs t = {};
+  t.X = reinterpret_cast<const bf16_t*>(c.x);
+  t.DY = reinterpret_cast<const bf16_t*>(c.dy);
+  t.partial = wgrad_slabs(c);
+  t.N = c.d->N; t.H = c.d->H; t.W = c.d->W; t.Cs = c.p.Cs; t.OH = c.p.OH; t.OW = c.p.OW;
+  t.pad = c.d->pad;
+  return launch_thin1_wgrad(t, c.dw, c.s);
+}
+
+// few output channels: dense 1x1 weight gradient over the padded input and the tap-expanded dy behind it (see expand_dy_taps_kernel)
+static FastWgArgs wgrad_tap_expanded_args(const WgradCall& c) {
+  const ConvPlan& p = c.p;
+  FastWgArgs f = {};
+  f.X = reinterpret_cast<const bf16_t*>(c.ws);
+  f.DY = reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(c.ws) + p.xpad_bytes);
+  f.DW = c.dw;
+  f.M = c.d->N * p.Hp * p.Wp; f.OH = f.IH = p.Hp; f.OW = f.IW = p.Wp;
+  f.Cs = p.Cs; f.C = c.d->C;
+  f.K = c.d->K * c.d->R * c.d->S; f.Ks = round_up(f.K, 64);      // dy's channels, tap-expanded
+  f.R = f.S = 1; f.sy = f.sx = 1;
+  return f;
+}
+static int wgrad_tap_expanded(const WgradCall& c) {
+  const jpdse_conv_desc* d = c.d;
+  const ConvPlan& p = c.p;
+  const FastWgArgs f = wgrad_tap_expanded_args(c);
+  if (int rc = wgrad_pad_x(c)) return rc;
+  const long long tv = (long long)d->N * p.Hp * p.Wp * (f.Ks / 8);
+  hipLaunchKernelGGL(expand_dy_taps_kernel, dim3(ew_blocks(tv)), dim3(256), 0, c.s, reinterpret_cast<const bf16_t*>(c.dy),
+                     const_cast<bf16_t*>(f.DY), p.OH, p.OW, p.Ks, d->K, d->R, d->S, p.Hp, p.Wp, f.Ks, tv);
+  if (int rc = check_launch("expand_dy_taps_kernel")) return rc;
+  return launch_wgrad_fast(f, wgrad_slabs(c), c.s);
+}
+
+// wgrad_thin.h on its two routes.  head: roles swapped -- A = padded input, run operand = dy zero-padded by (R-1, S-1), both paddings
+// resolved by the loader.  thin (40-channel network inputs): input strips staged once.
+static ThinWgArgs wgrad_thin_args(const WgradCall& c, WgradRoute route) {
+  const jpdse_conv_desc* d = c.d;
+  const ConvPlan& p = c.p;
+  const int refl = d->pad_mode == JPDSE_PAD_REFLECT;
+  ThinWgArgs t = {};
+  t.DW = c.dw;
+  t.N = d->N; t.R = d->R; t.S = d->S;
+  t.partial = wgrad_slabs(c);
+  if (route == WgradRoute::head) {
+    t.XP = reinterpret_cast<const bf16_t*>(c.dy);
+    t.DY = reinterpret_cast<const bf16_t*>(c.x);
+    t.OH = p.Hp; t.OW = p.Wp; t.Hp = p.OH + 2 * (d->R - 1); t.Wp = p.OW + 2 * (d->S - 1);
+    t.Cs = 8; t.C = d->K; t.Ks = p.Cs; t.K = d->C;
+    t.st = 1;
+    t.unpadded = 1;
+    t.RH = p.OH; t.RW = p.OW;
+    t.r_pad = d->R - 1;            // square filters on this route (R == S checked by wgrad_head_ok)
+    t.AH = d->H; t.AW = d->W; t.a_pad = d->pad; t.a_reflect = refl;
+    t.transposed = 1;
+    return t;
   }
-  // always staged through the workspace: the GEMM loaders rely on the zeroed slack behind it
-  if (!dry)
-    if (int rc = launch_pad<T>(x, ws, d->N, d->H, d->W, p.Cs, d->pad, d->pad, d->pad, d->pad, d->pad_mode, s))
-      return rc;
-  const void* xin = ws;
+  t.XP = reinterpret_cast<const bf16_t*>(c.x);
+  t.DY = reinterpret_cast<const bf16_t*>(c.dy);
+  t.OH = p.OH; t.OW = p.OW; t.Hp = p.Hp; t.Wp = p.Wp;
+  t.Cs = p.Cs; t.C = d->C; t.Ks = p.Ks; t.K = d->K;
+  t.st = d->stride;
+  if (d->stride == 2) {
+    // padding resolved by the loader (no padded copy): pays for the stride-2 layers (PatchGAN layer 0)
+    t.unpadded = 1;
+    t.RH = d->H; t.RW = d->W; t.r_pad = d->pad; t.r_reflect = refl;
+    t.AH = p.OH; t.AW = p.OW;
+  } else {
+    // 7x7 stride-1 first convs: 7 filter rows re-read every strip, the per-lane padding arithmetic costs more
+    // than one pass of pad_kernel (measured 0.65 vs 0.84 ms): wgrad_thin pads x into the workspace first
+    t.XP = reinterpret_cast<const bf16_t*>(c.ws);
+    t.x_limit = (long long)d->N * p.Hp * p.Wp * p.Cs + (long long)(kSlackBytes / 2);
+  }
+  return t;
+}
+static int wgrad_thin(const WgradCall& c) {
+  if (c.d->stride != 2)
+    if (int rc = wgrad_pad_x(c)) return rc;
+  return launch_wgrad_thin(wgrad_thin_args(c, WgradRoute::thin), c.s);
+}
+
+// the per-tap fast kernel; inputs that are no multiple of 64 channels wide (40-channel network inputs, 8-channel images) in run
+// mode over the materially padded input
+static FastWgArgs wgrad_fast_args(const WgradCall& c) {
+  const jpdse_conv_desc* d = c.d;
+  const ConvPlan& p = c.p;
+  FastWgArgs f = {};
+  f.DY = reinterpret_cast<const bf16_t*>(c.dy);
+  f.DW = c.dw;
+  f.M = d->N * p.OH * p.OW;
+  f.OH = p.OH; f.OW = p.OW;
+  f.Cs = p.Cs; f.C = d->C; f.Ks = p.Ks; f.K = d->K;
+  f.R = d->R; f.S = d->S;
+  f.sy = f.sx = d->stride;
+  if (p.Cs % 64 == 0) {
+    f.X = reinterpret_cast<const bf16_t*>(c.x);
+    f.IH = d->H; f.IW = d->W;
+    f.py = f.px = d->pad;
+    f.reflect = d->pad_mode == JPDSE_PAD_REFLECT;
+  } else {
+    f.X = reinterpret_cast<const bf16_t*>(c.ws);
+    f.IH = p.Hp; f.IW = p.Wp;
+    f.run_mode = 1;
+    f.run_len = d->S * p.Cs;
+  }
+  return f;
+}
+static int wgrad_fast(const WgradCall& c) {
+  if (c.p.Cs % 64 != 0)
+    if (int rc = wgrad_pad_x(c)) return rc;
+  return launch_wgrad_fast(wgrad_fast_args(c), wgrad_slabs(c), c.s);
+}
+
+// generic kernel: always staged through the workspace, the GEMM loaders rely on the zeroed slack behind it
+static GemmWgradArgs wgrad_generic_args(const WgradCall& c) {
+  const jpdse_conv_desc* d = c.d;
+  const ConvPlan& p = c.p;
   GemmWgradArgs a = {};
-  a.X = xin;
-  a.DY = dy;
-  a.DW = dw;
-  a.M = d->N * p.OH * p.OW;
-  a.OH = p.OH;
-  a.OW = p.OW;
-  a.K = d->K;
-  a.Ks = p.Ks;
-  a.C = d->C;
-  a.Cs = p.Cs;
-  a.R = d->R;
-  a.S = d->S;
-  a.run = d->S * p.Cs;
-  a.in_sn = (long long)p.Hp * p.Wp * p.Cs;
-  a.in_sh = (long long)d->stride * p.Wp * p.Cs;
-  a.in_sw = (long long)d->stride * p.Cs;
-  a.in_sr = (long long)p.Wp * p.Cs;
-  a.in_base = 0;
-  a.dy_sn = (long long)p.OH * p.OW * p.Ks;
-  a.dy_sh = (long long)p.OW * p.Ks;
-  a.dy_sw = p.Ks;
-  a.dy_base = 0;
-  if (dry) {
-    *slab_bytes_out = generic_wgrad_slab_bytes<T>(a);
-    return JPDSE_OK;
+  a.X = c.ws;
+  a.DY = c.dy;
+  a.DW = c.dw;
+  a.M = d->N * p.OH * p.OW; a.OH = p.OH; a.OW = p.OW;
+  a.K = d->K; a.Ks = p.Ks; a.C = d->C; a.Cs = p.Cs;
+  a.R = d->R; a.S = d->S; a.run = d->S * p.Cs;
+  a.in_sn = (long long)p.Hp * p.Wp * p.Cs; a.in_sr = (long long)p.Wp * p.Cs;
+  a.in_sh = (long long)d->stride * p.Wp * p.Cs; a.in_sw = (long long)d->stride * p.Cs;
+  a.dy_sn = (long long)p.OH * p.OW * p.Ks; a.dy_sh = (long long)p.OW * p.Ks; a.dy_sw = p.Ks;
+  return a;
+}
+
+template <typename T>
+static int conv_wgrad_t(const jpdse_conv_desc* d, const ConvPlan& p, const void* x, const void* dy, float* dw, void* ws, hipStream_t s) {
+  const WgradCall c = {d, p, x, dy, dw, ws, s};
+  const WgradRoute route = select_wgrad(d, p);
+  if constexpr (sizeof(T) == 2) {      // (the bf16 kernels are not instantiated for fp32 layers, which select_wgrad sends to the generic kernel)
+    switch (route) {
+      case WgradRoute::thin1: return wgrad_thin1(c);
+      case WgradRoute::tap_expanded: return wgrad_tap_expanded(c);
+      case WgradRoute::taps: return launch_wgrad_taps(d, p, wgrad_taps_cfg(d, p), x, dy, dw, ws, s);
+      case WgradRoute::nine: return launch_wgrad_nine(d, p, x, dy, dw, ws, s);
+      case WgradRoute::head: return launch_wgrad_head(wgrad_thin_args(c, route), s);
+      case WgradRoute::thin: return wgrad_thin(c);
+      case WgradRoute::fast: return wgrad_fast(c);
+      default: break;
+    }
   }
-  return launch_wgrad<T>(a, slabs, s);
+  if (int rc = wgrad_pad_x(c)) return rc;
+  return launch_wgrad<T>(wgrad_generic_args(c), wgrad_slabs(c), s);
+}
+
+// fp32 slab bytes behind wgrad_front_bytes that the layer's route needs (jpdse_conv_workspace_size): the route's arguments with
+// null tensors, handed to the route's own slab function
+static size_t wgrad_slab_bytes(const jpdse_conv_desc* d, const ConvPlan& p) {
+  const WgradCall c = {d, p, nullptr, nullptr, nullptr, nullptr, nullptr};
+  switch (const WgradRoute route = select_wgrad(d, p)) {
+    case WgradRoute::thin1: return thin1_wgrad_slab_bytes(d->N, d->H, d->W, p.Cs);
+    case WgradRoute::tap_expanded: return wgrad_fast_slab_bytes(wgrad_tap_expanded_args(c));
+    case WgradRoute::taps:
+    case WgradRoute::nine: return 0;      // no copies, slabs at offset 0: wgrad_taps_ws_bytes / wgrad_nine_ws_bytes
+    case WgradRoute::head:
+    case WgradRoute::thin: return thin_wgrad_slab_bytes(wgrad_thin_args(c, route), route == WgradRoute::head ? 7 : 1);
+    case WgradRoute::fast: return wgrad_fast_slab_bytes(wgrad_fast_args(c));
+    default: return d->dtype == JPDSE_BF16 ? generic_wgrad_slab_bytes<bf16_t>(wgrad_generic_args(c)) : generic_wgrad_slab_bytes<float>(wgrad_generic_args(c));
+  }
 }
 
 }  // namespace jpdse

@@ -108,6 +108,7 @@ __device__ __forceinline__ float apply_act(float v, int act, float slope) {
 #include "thin_in_rows.h"
 #include "conv_generic.h"
 #include "conv_plan.h"
+#include "conv_route.h"
 #include "conv_launch.h"
 #include "thin_out1.h"
 #include "conv_dispatch_fwd.h"
@@ -218,6 +219,25 @@ int jpdse_debug_set_fast_path(int32_t enable) {
   g_splitk_enabled = enable != 6;                        // 6: no split-K on the fast kernels
   return JPDSE_OK;
 }
+
+int jpdse_debug_conv_route(const jpdse_conv_desc* d, int32_t flags, int32_t out[3]) {
+  if (int rc = validate(d)) return rc;
+  JPDSE_REQUIRE(out != nullptr && (flags & ~0x7f) == 0, "debug_conv_route: null output or unknown flag bits");
+  ConvPlan p;
+  make_plan(d, &p);
+  out[0] = (int32_t)select_fwd(d, p, {(flags & 1) != 0, (flags & 2) != 0});
+  out[1] = (int32_t)select_dgrad(d, p, {(flags & 4) != 0, (flags & 8) != 0, (flags & 4) != 0 && (flags & 16) != 0, (flags & 32) != 0, (flags & 64) != 0});
+  out[2] = (int32_t)select_wgrad(d, p);
+  return JPDSE_OK;
+}
+
+const char* jpdse_debug_route_name(int32_t direction, int32_t route) {
+  if (route < 0) return nullptr;
+  if (direction == 0 && route <= (int)FwdRoute::generic) return route_name((FwdRoute)route);
+  if (direction == 1 && route <= (int)DgradRoute::generic) return route_name((DgradRoute)route);
+  if (direction == 2 && route <= (int)WgradRoute::generic) return route_name((WgradRoute)route);
+  return nullptr;
+}
 #endif
 
 int jpdse_prof_select(int32_t enable, int32_t Ks, int64_t kdim, int32_t max_launches) {
@@ -309,10 +329,7 @@ size_t jpdse_conv_workspace_size(const jpdse_conv_desc* d) {
   ConvPlan p;
   make_plan(d, &p);
   // wgrad: padded x (+ tap-expanded dy for few-output-channel layers) + the slabs of the split reduction
-  size_t slab_bytes = 0;
-  if (d->dtype == JPDSE_BF16) (void)conv_wgrad_t<bf16_t>(d, p, nullptr, nullptr, nullptr, nullptr, nullptr, &slab_bytes);
-  else (void)conv_wgrad_t<float>(d, p, nullptr, nullptr, nullptr, nullptr, nullptr, &slab_bytes);
-  const size_t fwd = wgrad_front_bytes(d, p) + slab_bytes;
+  const size_t fwd = wgrad_front_bytes(d, p) + wgrad_slab_bytes(d, p);
   size_t dgrad = p.dypad_bytes + p.dxp_bytes;
   if (thin1_shape_ok(d, p.Cs, p.Ks) && dgrad < (size_t)16 * p.Cs * sizeof(float)) dgrad = (size_t)16 * p.Cs * sizeof(float);   // tap table of thin1_dgrad_kernel
   size_t sk = p.splitk_off + p.splitk_bytes;

@@ -1,5 +1,5 @@
-// Launchers of the forward / data-gradient kernel families (generic, fast, halo, tap-program, row-streaming, thin, head),
-// the predicates that say which layer takes which kernel, and the in-library GEMM timer.  Every launcher re-checks the
+// Launchers of the forward / data-gradient kernel families (generic, fast, halo, tap-program, row-streaming, thin, head)
+// and the in-library GEMM timer; which layer takes which kernel is conv_route.h's business.  Every launcher re-checks the
 // divisibility / extent assumptions of its kernel's grid before it enqueues anything (a wrong launch argument must be an error
 // code, not a GPU memory fault: DESIGN.md 9).  Part of conv_gemm.hip (one translation unit).
 #pragma once
@@ -55,19 +55,17 @@ static void prof_end(int slot, int cls, double flops, hipStream_t s) {
   g_prof.used = slot + 1;
 }
 
-// ---- the layer as the bf16 single-launch kernels see it: a conv over X with panel B into Y -- the forward of a layer, or one
-// stride phase of its data gradient (a stride-1 conv over dy).  Every bf16 path of conv_fwd_t / conv_dgrad_t starts from one of the
+// ---- the layer as the bf16 single-launch kernels see it: a conv over X with panel B into Y (its ConvShape, conv_route.h, plus the
+// pointers and the addressing).  Every bf16 path of conv_fwd_t / conv_dgrad_t starts from one of the
 // two constructors and hands the view to its kernel family through a converter (to_rows / to_halo / to_fast; the tap-program
 // launchers take the view itself): a new fused operand is added here and in the converters, not once per dispatch branch.
-struct ConvView {
+struct ConvView : ConvShape {
   const bf16_t* X; const bf16_t* B; const float* bias; bf16_t* Y;
-  int N, IH, IW, Cin_s, OH, OW, py, px;
-  int R, S, stride, reflect;      // reflect: mirrored instead of zero padding
-  int Kout, Ks_out;
+  int py, px, Kout;
   long long ktot;                 // panel row stride (elements)
-  int tap_r, tap_s;               // panel offsets per filter-row / filter-column step
+  int tap_s;                      // panel offset per filter-column step
   long long out_sn, out_sh, out_sw, out_base;
-  int act; float slope;
+  float slope;
   // optional fused operands, set by the dispatch after construction
   const bf16_t* mask; float mask_slope; const bf16_t* addend;   // data gradient, Y's addressing: Y = (result + addend) * (mask > 0 ? 1 : mask_slope)
   float* mom;                     // InstanceNorm moments of Y from the epilogue (rows / halo kernels)
@@ -76,18 +74,16 @@ struct ConvView {
 
 static ConvView view_fwd(const jpdse_conv_desc* d, const ConvPlan& p, const void* x, const void* pack, const float* bias, void* y) {
   ConvView v = {};
+  static_cast<ConvShape&>(v) = shape_fwd(d, p);
   v.X = reinterpret_cast<const bf16_t*>(x);
   v.B = reinterpret_cast<const bf16_t*>(pack);
   v.bias = bias;
   v.Y = reinterpret_cast<bf16_t*>(y);
-  v.N = d->N; v.IH = d->H; v.IW = d->W; v.Cin_s = p.Cs; v.OH = p.OH; v.OW = p.OW;
   v.py = v.px = d->pad;
-  v.R = d->R; v.S = d->S; v.stride = d->stride;
-  v.reflect = d->pad_mode == JPDSE_PAD_REFLECT;
-  v.Kout = d->K; v.Ks_out = p.Ks;
-  v.ktot = (long long)d->R * p.Lk_fwd; v.tap_r = p.Lk_fwd; v.tap_s = p.Cs;
+  v.Kout = d->K;
+  v.ktot = (long long)d->R * p.Lk_fwd; v.tap_s = p.Cs;
   v.out_sn = (long long)p.OH * p.OW * p.Ks; v.out_sh = (long long)p.OW * p.Ks; v.out_sw = p.Ks;
-  v.act = d->act; v.slope = d->slope;
+  v.slope = d->slope;
   return v;
 }
 
@@ -96,17 +92,15 @@ static ConvView view_dgrad_phase(const jpdse_conv_desc* d, const ConvPlan& p, in
   const Phase& f = p.ph[i];
   const int st = d->stride;
   ConvView v = {};
+  static_cast<ConvShape&>(v) = shape_dgrad_phase(d, p, i);
   v.X = reinterpret_cast<const bf16_t*>(dy);
   v.B = reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(pack) + f.pack_off);
   v.Y = reinterpret_cast<bf16_t*>(dx);
-  v.N = d->N; v.IH = p.OH; v.IW = p.OW; v.Cin_s = p.Ks; v.OH = f.cnth; v.OW = f.cntw;
   v.py = (f.Uh - 1) - f.i0h; v.px = (f.Uw - 1) - f.i0w;
-  v.R = f.Uh; v.S = f.Uw; v.stride = 1;
-  v.Kout = d->C; v.Ks_out = p.Cs;
-  v.ktot = (long long)f.Uh * f.Lk; v.tap_r = f.Lk; v.tap_s = p.Ks;
+  v.Kout = d->C;
+  v.ktot = (long long)f.Uh * f.Lk; v.tap_s = p.Ks;
   v.out_sn = (long long)d->H * d->W * p.Cs; v.out_sh = (long long)st * d->W * p.Cs; v.out_sw = (long long)st * p.Cs;
   v.out_base = ((long long)(st * f.i0h + f.qh - d->pad) * d->W + (st * f.i0w + f.qw - d->pad)) * p.Cs;
-  v.act = JPDSE_ACT_NONE;
   return v;
 }
 
@@ -128,12 +122,13 @@ static RowsArgs to_rows(const ConvView& v) {        // 64-channel input, 3x3: th
   r.mom = v.mom;                                    // (launch_rows_cfg sets the slot count with the band height)
   return r;
 }
+static int halo_slots(int OH, int OW) { return (OH / 4) * (OW / 64); }      // moment / norm-sum slots per image: one per 4 x 64 output patch
 static HaloArgs to_halo(const ConvView& v) {
   HaloArgs h = view_to<HaloArgs>(v);
   h.N = v.N; h.Cs = v.Cin_s; h.reflect = v.reflect;
   h.V = v.frame;
   h.mom = v.mom;
-  h.mom_slots = v.mom != nullptr ? (v.OH / 4) * (v.OW / 64) : 0;
+  h.mom_slots = v.mom != nullptr ? halo_slots(v.OH, v.OW) : 0;
   return h;
 }
 static FastArgs to_fast(const ConvView& v) {        // dense panel (b_stride / b_tap_* = 0); splits and slabs are the caller's
@@ -143,10 +138,6 @@ static FastArgs to_fast(const ConvView& v) {        // dense panel (b_stride / b
   f.mask_slope = v.mask_slope;
   return f;
 }
-static bool rows_ok(int R, int S, int stride, int reflect, int act, int OH, int OW, int Cs_in, int Ks_out);
-static bool halo_ok(int R, int S, int stride, int OH, int OW, int Cs_in, int Ks_out);
-static bool rows_ok(const ConvView& v) { return rows_ok(v.R, v.S, v.stride, v.reflect, v.act, v.OH, v.OW, v.Cin_s, v.Ks_out); }
-static bool halo_ok(const ConvView& v) { return halo_ok(v.R, v.S, v.stride, v.OH, v.OW, v.Cin_s, v.Ks_out); }
 
 template <typename T, int BM, int BN, int WM, int WN>
 static int launch_fwd_cfg(const GemmFwdArgs& a_in, hipStream_t s) {
@@ -265,23 +256,9 @@ static int launch_fast_cfg(FastBatch& b, hipStream_t s) {
   return check_launch("gemm_fast_kernel");
 }
 
-static bool prefer_320(int M, int Ks) {
-  // one round of 320-row tiles beats two rounds of 256-row tiles (e.g. the ResnetBlock data gradient
-  // on the reflect-padded domain: M = 8976 -> 232 tiles instead of 288 on 256 CUs)
-  if (Ks <= 64) return false;
-  const long long nt = (Ks + 127) / 128;
-  const long long t256 = (long long)((M + 255) / 256) * nt, t320 = (long long)((M + 319) / 320) * nt;
-  const long long c256 = ((t256 + 255) / 256) * 256, c320 = ((t320 + 255) / 256) * 320;
-  return c320 < c256;
-}
-
 // ---- persistent, cross-tile-pipelined form for the short-K layers (gemm_pers.h) -------------------------------------------
-// Off since the end of round 4: with the epilogue staging fixed (gemm_fast.h, acc_tile_to_lds) the fast kernel runs the two launches the persistent form
-// was shipped for 5-7 % FASTER than it (697 vs 650, 685 vs 640 TFLOP/s; step 24.93 vs 24.95 ms) -- its +8 % had been the lean epilogue it happened to have.
-// Developer modes 51 / 52 (tests) / 61 (the round-4 rule: whole-round grids, <= 24 K-tiles) still reach it.
-JPDSE_SWITCH(int, g_pers_enabled, 0);
+// Off by default (g_pers_enabled, conv_route.h).
 JPDSE_SWITCH(int, g_pers_max_kt, 24);     // K-tile count up to which the persistent form is taken (51: every fast-kernel layer without split-K, A/B)
-JPDSE_SWITCH(int, g_pers_min_tiles, 256); // 52: from one tile on (tests: ragged tails and multi-problem launches at small sizes)
 static bool pers_ok(const FastBatch& b) {
   if (!g_pers_enabled || b.n <= 0 || b.small_m) return false;
   const int Ks = b.p[0].Ks;
@@ -390,39 +367,6 @@ static int launch_fast(const FastArgs& a, hipStream_t s) {
   return launch_fast_batch(b, s);
 }
 
-JPDSE_SWITCH(bool, g_fast_enabled, true);   // jpdse_debug_set_fast_path(0) forces the generic kernels (A/B tests)
-
-// The fast kernel runs ONE 256-row tile per CU (144 KiB of LDS), so its grid should either cover
-// the 256 CUs many times over or be an exact multiple of them; in between (e.g. the 288 tiles of the
-// ResnetBlock data gradient) the generic 128x128 kernel with 3 co-resident blocks per CU wins
-// (measured: scripts/bench_conv.py, profiles/r01_conv_layers_*.log).
-static bool fast_pays(int M, int Ks, int k_tiles) {
-  if (!g_fast_enabled) return false;
-  if (g_pers_min_tiles <= 1 && g_pers_enabled && k_tiles >= 4 && Ks >= 64) return true;   // developer mode 52 (tests): small problems reach the persistent form
-  if (k_tiles < 8) return false;   // short reductions (stride-2 sub-pixel phases of 2x2 taps x 64 ch) do not fill the 3-stage ring
-  if (Ks <= 32) {
-    // measured: the generic 256x32 kernel beats the 8-wave 256x32 fast config on short reductions; with a long
-    // one (512 -> 1 PatchGAN map, K = 8192) the fast kernel needs no padded copy and streams the input by DMA
-    if (!(g_thin_out_fast && k_tiles >= 64)) return false;
-    return splitk_for(M, Ks, k_tiles) > 1 || (M + 255) / 256 >= 128;
-  }
-  if (splitk_for(M, Ks, k_tiles) > 1) return true;
-  const int bn = Ks > 64 ? 128 : (Ks > 32 ? 64 : 32);
-  const long long tiles = (long long)((M + 255) / 256) * ((Ks + bn - 1) / bn);
-  if (prefer_320(M, Ks)) {
-    const long long t320 = (long long)((M + 319) / 320) * ((Ks + 127) / 128);
-    if (t320 % 256 == 0 || t320 % 256 >= 192 || t320 >= 448) return true;   // well-filled rounds
-  }
-  return tiles >= 448 || (tiles >= 256 && tiles % 256 == 0);
-}
-
-JPDSE_SWITCH(int, g_ring_enabled, 1);
-JPDSE_SWITCH(int, g_ring_virt, 1);        // 40: ring strips as four split-K GEMMs + ring_fold_kernel (the round-1..3 form) instead of the folded frame
-JPDSE_SWITCH(int, g_merge_min_kt, 4);
-JPDSE_SWITCH(int, g_merge_min_tiles, 64);    // merged stride-phase data gradient on the fast kernel from this many 256-row tiles on (26: 384 as in round 1, A/B)
-JPDSE_SWITCH(int, g_halo_single, 1);
-JPDSE_SWITCH(int, g_halo_enabled, 1);
-
 template <int TN, bool SINGLE = false, bool MF16 = false, bool MOM = false, bool VIRT = false, bool NSUM = false>
 static int launch_halo_cfg_impl(const HaloArgs& a, hipStream_t s) {
   constexpr int BN = 2 * TN * 32;
@@ -510,14 +454,13 @@ static int rows_band_height_by_cost(int N, int OH, int tiles_w) {
   return th;
 }
 
-// 3x3 convs over 64-channel inputs (stride 1 | 2, zero padding): filter in registers, input rows streamed once (conv_rows.h)
-JPDSE_SWITCH(int, g_rows_enabled, 1);       // 29: these layers on the halo / fast kernels (A/B)
-
-static bool rows_ok(int R, int S, int stride, int reflect, int act, int OH, int OW, int Cs_in, int Ks_out) {
-  return g_fast_enabled && g_rows_enabled && R == 3 && S == 3 && (stride == 1 || stride == 2) && !reflect && Cs_in == 64 &&
-         Ks_out % 64 == 0 && OW % 64 == 0 && OH % 4 == 0 &&
-         (act == JPDSE_ACT_NONE || act == JPDSE_ACT_RELU || act == JPDSE_ACT_LRELU);
+// 3x3 convs over 64-channel inputs (conv_rows.h): wave-tile width, band height and moment slots per image of a layer -- the
+// launcher's geometry, which the slot query (conv_fwd_moment_slots) reads too
+static int rows_wc(int Ks) { return Ks % 128 == 0 ? 4 : 2; }
+static int rows_band(int N, int OH, int OW, int Ks, int stride) {
+  return rows_band_height(N, OH, OW / 64, Ks / (32 * rows_wc(Ks)), 256LL * ((stride == 1 && rows_wc(Ks) == 2) ? 2 : 1));
 }
+static int rows_slots(int th, int OH, int OW, int Ks) { return (OH / th) * (OW / 64) * (4 / rows_wc(Ks)); }      // th: rows_band(...)
 
 template <int STRIDE, int WC, bool FUSED>
 static int launch_rows_cfg(RowsArgs a, hipStream_t s) {
@@ -527,10 +470,10 @@ static int launch_rows_cfg(RowsArgs a, hipStream_t s) {
   if (a.Ks % (32 * WC) != 0) return set_error(JPDSE_EINVAL, "conv_rows: %d output channels do not split into %d-wide wave tiles", a.Ks, 32 * WC);
   a.n_tiles = a.Ks / (32 * WC);
   a.strips = a.OW / 64;
-  a.TH = rows_band_height(a.N, a.OH, a.strips, a.n_tiles, 256LL * ((STRIDE == 1 && WC == 2) ? 2 : 1));
-  const int th = a.TH;
-  a.bands = a.OH / th;
-  a.mom_slots = a.bands * a.strips * (4 / WC);
+  if (WC != rows_wc(a.Ks)) return set_error(JPDSE_EINVAL, "conv_rows: %d-wide wave tiles for %d output channels", 32 * WC, a.Ks);
+  a.TH = rows_band(a.N, a.OH, a.OW, a.Ks, STRIDE);
+  a.bands = a.OH / a.TH;
+  a.mom_slots = rows_slots(a.TH, a.OH, a.OW, a.Ks);
   const long long blocks = (long long)a.N * a.bands * a.strips * a.n_tiles;
   if (blocks > 0x7fffffffLL) return set_error(JPDSE_EINVAL, "conv_rows: grid too large");
   hipLaunchKernelGGL((conv_rows_kernel<STRIDE, WC, FUSED>), dim3((unsigned)blocks), dim3(256), G::LDS, s, a);
@@ -539,7 +482,7 @@ static int launch_rows_cfg(RowsArgs a, hipStream_t s) {
 
 static int launch_rows(const RowsArgs& a, int stride, hipStream_t s) {
   const bool fused = a.mask != nullptr || a.addend != nullptr;
-  const bool wide = a.Ks % 128 == 0;
+  const bool wide = rows_wc(a.Ks) == 4;
   if (stride == 1) {
     if (wide) return fused ? launch_rows_cfg<1, 4, true>(a, s) : launch_rows_cfg<1, 4, false>(a, s);
     return fused ? launch_rows_cfg<1, 2, true>(a, s) : launch_rows_cfg<1, 2, false>(a, s);
@@ -550,26 +493,23 @@ static int launch_rows(const RowsArgs& a, int stride, hipStream_t s) {
 
 
 // data gradient of the 64 -> 128 3x3 stride-2 conv / forward of the 128 -> 64 ConvTranspose2d at full resolution (dgrad2_rows.h)
+static int dgrad2_rows_band(int N, int OH, int OW) { return rows_band_height(N, OH, OW / 64, 1, 256); }
+static int dgrad2_rows_slots(int th, int OH, int OW) { return (OH / th) * (OW / 64); }      // moment slots per image; th: dgrad2_rows_band(...)
 static int launch_dgrad2_rows(Dgrad2Args a, hipStream_t s) {
   typedef Dgrad2Geom G;
   if (int rc = opt_in_lds<&dgrad2_rows_kernel>("dgrad2_rows", G::LDS)) return rc;
   if (int rc = check_tile_grid("dgrad2_rows", a.N, a.OH, a.OW, 4, 64, 128, (long long)a.N * a.OH * a.OW * 128, 4LL * a.N * a.OH * a.OW * 64)) return rc;
   a.strips = a.OW / 64;
-  const int th = rows_band_height(a.N, a.OH, a.strips, 1, 256);
+  const int th = dgrad2_rows_band(a.N, a.OH, a.OW);
   a.TH = th;
   a.bands = a.OH / th;
-  a.mom_slots = a.bands * a.strips;
+  a.mom_slots = dgrad2_rows_slots(th, a.OH, a.OW);
   hipLaunchKernelGGL(dgrad2_rows_kernel, dim3((unsigned)(a.N * a.bands * a.strips)), dim3(256), G::LDS, s, a);
   return check_launch("dgrad2_rows_kernel");
 }
 
 
 // 64 -> <= 3 channel heads (7x7 reflect + Tanh; 3x3 zero-pad data gradient of VGG conv1_1) as a row-streaming pass (head_rows.h)
-JPDSE_SWITCH(int, g_head_rows32, 1);      // 57: the 32-channel head on head_fwd_kernel, as before round 4 (A/B)
-static bool head_rows_ok(const HeadFwdArgs& a, int cin) {
-  return g_rows_enabled && (cin == 64 || (cin == 32 && g_head_rows32 && a.R == 7)) && a.K <= 3 && a.Ks_out == 8 && a.OW % 128 == 0 &&
-         a.OH % 8 == 0 && a.OH == a.H && a.OW == a.W;
-}
 template <int R, int CIN = 64>
 static int launch_head_rows(const HeadFwdArgs& a, hipStream_t s) {
   typedef HeadRowsGeom<R, CIN> G;
@@ -632,57 +572,7 @@ static int launch_thin_in_rows(ThinInArgs a, hipStream_t s) {
   return JPDSE_OK;
 }
 
-// ---- tap-program halo kernel (gemm_taps.h): all four sub-pixel phases of a stride-2 data gradient / ConvTranspose forward
-JPDSE_SWITCH(int, g_taps_enabled, 1);       // 35: these layers on the merged-phase fast kernel (A/B)
-
-// Stride-2 data gradients on the tap-program kernel.  3x3 (pad 1, even input): phases (0,0) 2x2 taps, (0,1) 2x1, (1,0) 1x2,
-// (1,1) 1x1 over the same dy pixels.  4x4 (pad 2: the PatchGAN layers 1-2, networks.py:430-436): 2x2 taps in every phase; their
-// inputs have 2^k + 1 rows / columns, so the phases differ by one row / column: the kernel covers the CORE every phase has
-// (a multiple of 4 x 64 sub-pixels), the one-row / one-column FRINGE of the longer phases runs as sub-rectangle problems of the
-// fast kernel behind it (fused operands in its epilogue).
-JPDSE_SWITCH(int, g_taps_dgrad4_enabled, 1);     // 42: the 4x4 stride-2 data gradients on the merged-phase fast kernel (A/B)
-JPDSE_SWITCH(int, g_taps_dgrad4_min_tiles, 1 << 30);   // 43: take the path at any size (developer build: tests, A/B) -- the shipped build never does, see below
-struct TapsDgrad2Geom { int core_h, core_w, fringe, taps4; };
-static bool taps_dgrad2_geom(const jpdse_conv_desc* d, const ConvPlan& p, const float* mom, TapsDgrad2Geom* g) {
-  if (!(g_fast_enabled && g_taps_enabled) || d->dtype != JPDSE_BF16 || d->pad_mode == JPDSE_PAD_REFLECT) return false;
-  const bool k3 = d->R == 3 && d->S == 3 && d->pad == 1, k4 = d->R == 4 && d->S == 4 && d->pad == 2 && g_taps_dgrad4_enabled;
-  if (d->stride != 2 || !(k3 || k4) || p.nph != 4) return false;
-  if (mom != nullptr) return false;
-  if (p.Ks % 64 != 0 || p.Ks < 128 || p.Cs % 64 != 0) return false;
-  // the kernel's loaders carry 32-bit element offsets into dy and into each phase's panel
-  if ((long long)d->N * p.OH * p.OW * p.Ks >= (1LL << 31) || (long long)p.Cs * 4 * p.Ks >= (1LL << 31)) return false;
-  int min_h = 1 << 30, min_w = 1 << 30, fringe = 0;
-  for (int i = 0; i < 4; ++i) {
-    const Phase& f = p.ph[i];
-    if (f.Lk != f.Uw * p.Ks) return false;
-    if (k3 && (f.Uh != (f.qh == 0 ? 2 : 1) || f.Uw != (f.qw == 0 ? 2 : 1))) return false;
-    if (k4 && (f.Uh != 2 || f.Uw != 2)) return false;
-    if ((f.Uh - 1) - f.i0h != 0 || (f.Uw - 1) - f.i0w != 0) return false;      // every phase starts at dy pixel (oh, ow)
-    min_h = f.cnth < min_h ? f.cnth : min_h;
-    min_w = f.cntw < min_w ? f.cntw : min_w;
-  }
-  const int core_h = min_h / 4 * 4, core_w = min_w / 64 * 64;
-  if (core_h < 4 || core_w < 64) return false;
-  for (int i = 0; i < 4; ++i) {
-    const Phase& f = p.ph[i];
-    if (f.cnth > core_h) ++fringe;
-    if (f.cntw > core_w) ++fringe;
-  }
-  if (k3 && fringe != 0) return false;              // the 3x3 layers of the generator have even inputs: no fringe path needed
-  // 4x4: measured against the merged-phase fast kernel (profiles/r03_taps_dgrad4_ab.txt).  Bare data gradient, one process:
-  // +14 % with 1024 core tiles per program (layer 1 at 257 x 513), +5 % with 256 (layer 2), -9 ... -31 % on the second scale.
-  // In the step, where the LeakyReLU mask and the feature-matching addend ride in the epilogue, layer 1 was SLOWER
-  // (0.195 + 0.130 ms vs 0.186 + 0.116 ms for the two launches): with one block per CU the operand loads of the two epilogues
-  // are exposed, the fast kernel overlaps them across its three co-resident blocks.  These K = 512 ... 1024 loops are
-  // prologue / epilogue bound on either kernel; the path stays in the developer build only.
-  if (k4 && (long long)d->N * (core_h / 4) * (core_w / 64) * ((p.Cs + 127) / 128) < g_taps_dgrad4_min_tiles) return false;
-  if (g != nullptr) *g = {core_h, core_w, fringe, k4 ? 1 : 0};
-  return true;
-}
-static bool taps_dgrad2_ok(const jpdse_conv_desc* d, const ConvPlan& p, const float* mom) {
-  return taps_dgrad2_geom(d, p, mom, nullptr);
-}
-
+// ---- tap-program halo kernel (gemm_taps.h) on the stride-2 data gradients: taps_dgrad2_geom (conv_route.h) says which, and how they split
 template <int TN, int T1A, int T0B, int T1B>
 static int launch_taps_dgrad2_cfg(const TapsArgs& a, int total, hipStream_t s) {
   constexpr int PH = 5, PW = 65;
@@ -699,7 +589,7 @@ static int launch_taps_dgrad2_cfg(const TapsArgs& a, int total, hipStream_t s) {
 static int launch_taps_dgrad2(const jpdse_conv_desc* d, const ConvPlan& p, const void* dy, const void* pack, void* dx, hipStream_t s,
                               const void* mask, const void* addend, float mask_slope = 0.f) {
   TapsDgrad2Geom geo = {};
-  if (!taps_dgrad2_geom(d, p, nullptr, &geo)) return set_error(JPDSE_EINVAL, "gemm_taps: not a stride-2 data gradient it covers");
+  if (!taps_dgrad2_geom(d, p, false, &geo)) return set_error(JPDSE_EINVAL, "gemm_taps: not a stride-2 data gradient it covers");
   TapsArgs a = {};
   a.mask = reinterpret_cast<const bf16_t*>(mask);
   a.mask_slope = mask_slope;
@@ -784,18 +674,6 @@ static int launch_taps_dgrad2(const jpdse_conv_desc* d, const ConvPlan& p, const
 // (64 x 128: 95 % of the pixels) with the 11 x 35 input patch staged once per 64-channel slab for all 16 taps; the fringe (the
 // last OH % 8 rows, the last OW % 32 columns) runs as two sub-rectangle problems of ONE split-K launch of gemm_fast_kernel
 // (fp32 slabs, fixed summation order) + its finish kernels.
-JPDSE_SWITCH(int, g_taps4_enabled, 1);      // 36: these layers on the fast kernel alone (A/B)
-
-static bool taps4_shape_ok(int R, int S, int stride, int OH, int OW, int Cin_s, int Ks_out, long long x_elems, long long b_elems) {
-  return g_fast_enabled && g_taps4_enabled && R == 4 && S == 4 && stride == 1 && OH >= 8 && OW >= 32 && Cin_s % 64 == 0 &&
-         Cin_s >= 128 && Ks_out % 64 == 0 && Ks_out >= 64 && x_elems < (1LL << 31) && b_elems < (1LL << 31);
-}
-
-static bool taps4_shape_ok(const ConvView& v) {
-  return v.tap_r == v.S * v.Cin_s && taps4_shape_ok(v.R, v.S, v.stride, v.OH, v.OW, v.Cin_s, v.Ks_out, (long long)v.N * v.IH * v.IW * v.Cin_s,
-                                                    (long long)v.Ks_out * 16 * v.Cin_s);      // (a panel without K padding inside its rows)
-}
-
 static int taps4_fringe_splits(int N, int OH, int OW, int Ks_out, int k_tiles) {
   const int OHc = OH / 8 * 8, OWc = OW / 32 * 32;
   const long long m_bot = (long long)N * (OH - OHc) * OW, m_right = (long long)N * OHc * (OW - OWc);
@@ -897,18 +775,6 @@ static int launch_taps4(const ConvView& v, void* ws, hipStream_t s) {
 // ---- 3x3 stride-1 convs whose grid does not tile into the halo kernel's 4 x 64 patches but into 8 x 32 ones (W = 32: the
 // 1024-channel ResnetBlocks of the LocalEnhancer trunk at 16 x 32 pixels, BASELINE config 3): the tap-program kernel with nine
 // taps, zero or mirrored padding in the patch loader, and -- few tiles, K = 9216 -- split-K over the channel slabs.
-JPDSE_SWITCH(int, g_taps9_enabled, 1);      // 38: these layers on the split-K fast kernel (A/B)
-
-static bool taps9_shape_ok(int R, int S, int stride, int OH, int OW, int Cin_s, int Ks_out, long long x_elems, long long b_elems) {
-  return g_fast_enabled && g_taps9_enabled && R == 3 && S == 3 && stride == 1 && OH % 8 == 0 && OW % 32 == 0 && OW % 64 != 0 &&
-         Cin_s % 64 == 0 && Cin_s >= 128 && Ks_out % 64 == 0 && x_elems < (1LL << 31) && b_elems < (1LL << 31);
-}
-
-static bool taps9_shape_ok(const ConvView& v) {
-  return v.tap_r == v.S * v.Cin_s && taps9_shape_ok(v.R, v.S, v.stride, v.OH, v.OW, v.Cin_s, v.Ks_out, (long long)v.N * v.IH * v.IW * v.Cin_s,
-                                                    (long long)v.Ks_out * 9 * v.Cin_s);
-}
-
 static int taps9_splits(int N, int OH, int OW, int Cin_s, int Ks_out) {
   const int sp = splitk_for(N * OH * OW, Ks_out, 9 * Cin_s / 64);      // the split-K fast path's choice: its workspace region is reused
   const int cc = Cin_s / 64;
@@ -969,13 +835,6 @@ static int launch_taps9(const ConvView& v, float* slabs, hipStream_t s) {
   return check_launch("taps9 split-K finish");
 }
 
-// 3x3 stride-1 convs whose output grid tiles into 4 x 64 patches (ResnetBlocks, VGG19, and the data
-// gradient of the zero-padded ones): LDS-resident input halo, see gemm_halo.h
-static bool halo_ok(int R, int S, int stride, int OH, int OW, int Cs_in, int Ks_out) {
-  return g_fast_enabled && g_halo_enabled && R == 3 && S == 3 && stride == 1 && OH % 4 == 0 && OW % 64 == 0 &&
-         Cs_in % 64 == 0 && Ks_out > 32;
-}
-
 // Convs with K*R*S <= 32 outputs-times-taps (the 512 -> 1 PatchGAN map): y[p][k] = sum_taps Z[p + tap][k, tap] with
 // Z[q][(k, tap)] = sum_c x[q][c] * w[k][tap][c] -- a 1x1 GEMM over the INPUT pixels (K*R*S <= 32 columns: one MFMA
 // tile, every input pixel read once, no padded copy) followed by this gather-sum over the taps.  The direct
@@ -1010,42 +869,11 @@ __global__ __launch_bounds__(256) void tapsum_kernel(const float* __restrict__ Z
   y[idx] = f2bf(v);
 }
 
-JPDSE_SWITCH(int, g_thin_fwd_enabled, 1);
-// geometry of the thin forward kernel for a layer: TH output rows per block (8, or 4 for stride 2 / when LDS is short)
-struct ThinFwdGeom { int TH, TW, strip_units, w_units, lds; };
-static bool thin_fwd_geom(const jpdse_conv_desc* d, const ConvPlan& p, ThinFwdGeom* g) {
-  if (!(g_fast_enabled && g_thin_fwd_enabled && p.thinf)) return false;
-  const int st = d->stride;
-  g->w_units = (p.Ks * p.KP_thin * 2 + 1023) / 1024;
-  static const int cand[3][2] = {{8, 64}, {4, 64}, {4, 32}};
-  // 8-channel inputs (VGG conv1_1) are output-write bound: the smaller block keeps the epilogue tile at 48 KiB so that
-  // three blocks share a CU
-  for (int c = (p.Cs <= 8 && p.Ks == 64) ? 1 : 0; c < 3; ++c) {
-    const int TH = cand[c][0], TW = cand[c][1];
-    if (TH == 4 && p.Ks != 64) break;                 // 4 rows x 2 column groups needs K = 64 (32 per group)
-    g->strip_units = (((TW - 1) * st + d->S) * p.Cs * 2 + 16 + 1023) / 1024;
-    const int lds = (((TH - 1) * st + d->R) * g->strip_units + 2 * g->w_units) * 1024;
-    const int epi = TH * TW * (p.Ks * 2 + 64);
-    g->TH = TH;
-    g->TW = TW;
-    g->lds = lds > epi ? lds : epi;
-    if (g->lds <= 160 * 1024) return true;
-  }
-  return false;
-}
-
 template <int TN, int TH, int ST, int TW>
 static int launch_thin_fwd(const ThinFwdArgs& a, int lds, hipStream_t s) {
   if (int rc = opt_in_lds<&thin_fwd_kernel<TN, TH, ST, TW>>("thin_fwd", 160 * 1024)) return rc;
   hipLaunchKernelGGL((thin_fwd_kernel<TN, TH, ST, TW>), dim3(a.N * a.tiles_h * a.tiles_w), dim3(512), lds, s, a);
   return check_launch("thin_fwd_kernel");
-}
-
-JPDSE_SWITCH(int, g_head_fwd_enabled, 1);
-static bool head_fwd_ok(const jpdse_conv_desc* d, const ConvPlan& p) {
-  const int ncols = d->K * d->R * d->S;
-  return g_fast_enabled && g_head_fwd_enabled && p.ES == 2 && d->stride == 1 && d->K <= 3 && p.Ks == 8 &&
-         (p.Cs == 64 || p.Cs == 32) && d->R == 7 && d->S == 7 && ncols <= 160 && p.Lk_fwd == d->S * p.Cs;
 }
 
 template <int CIN, int NT = 5, int FR = 7, int FS = 7>
@@ -1054,59 +882,6 @@ static int launch_head_fwd(const HeadFwdArgs& a, hipStream_t s) {
   if (int rc = opt_in_lds<&head_fwd_kernel<CIN, NT, FR, FS>>("head_fwd", lds)) return rc;
   hipLaunchKernelGGL((head_fwd_kernel<CIN, NT, FR, FS>), dim3(a.N * a.tiles_h * a.tiles_w), dim3(64 * NT), lds, s, a);
   return check_launch("head_fwd_kernel");
-}
-
-JPDSE_SWITCH(int, g_tapsum_enabled, 1);
-static bool tapsum_ok(const jpdse_conv_desc* d, const ConvPlan& p) {
-  return g_fast_enabled && g_tapsum_enabled && p.ES == 2 && d->stride == 1 && d->K * d->R * d->S <= 32 &&
-         p.Cs % 64 == 0 && p.Cs >= 256 && p.Lk_fwd == d->S * p.Cs;
-}
-
-
-// ---- forward moments for the InstanceNorm that follows a conv (jpdse_conv_fwd_moments): which layers write them, and how many
-// slots per image.  These mirror the dispatch order of conv_fwd_t / conv_dgrad_t.
-static bool thin_rows_takes(const jpdse_conv_desc* d, const ConvPlan& p) {
-  return g_rows_enabled && d->stride == 2 && d->R == 4 && d->S == 4 && p.Cs == 40 && p.Ks == 64 && d->K == 64 &&
-         d->pad_mode != JPDSE_PAD_REFLECT && p.KP_thin == 168;
-}
-static bool thin_in_rows_takes(const jpdse_conv_desc* d, const ConvPlan& p) {
-  return g_fast_enabled && g_rows_enabled && p.Cs == 8 && d->R == 3 && d->S == 3 && d->stride == 1 && d->pad == 1 &&
-         d->pad_mode == JPDSE_PAD_ZERO && p.Ks == 64 && d->K == 64 && p.Lk_fwd == 32;
-}
-JPDSE_SWITCH(int, g_moments_fused, 1);     // 32 (and 6: the rounding-point-preserving comparison mode): no moment epilogues
-static int conv_fwd_moment_slots(const jpdse_conv_desc* d, const ConvPlan& p) {
-  if (!g_moments_fused || d->dtype != JPDSE_BF16 || d->act != JPDSE_ACT_NONE) return 0;
-  if (thin_in_rows_takes(d, p)) return 0;
-  ThinFwdGeom tg;
-  if (thin_fwd_geom(d, p, &tg)) {
-    if (thin_rows_takes(d, p)) return 0;
-    return (p.OH % tg.TH == 0 && p.OW % tg.TW == 0) ? (p.OH / tg.TH) * (p.OW / tg.TW) : 0;
-  }
-  if (head_fwd_ok(d, p) || tapsum_ok(d, p)) return 0;
-  if (rows_ok(d->R, d->S, d->stride, d->pad_mode == JPDSE_PAD_REFLECT, d->act, p.OH, p.OW, p.Cs, p.Ks)) {
-    const int WC = p.Ks % 128 == 0 ? 4 : 2, strips = p.OW / 64, n_tiles = p.Ks / (32 * WC);
-    const int th = rows_band_height(d->N, p.OH, strips, n_tiles, 256LL * ((d->stride == 1 && WC == 2) ? 2 : 1));
-    return (p.OH / th) * strips * (4 / WC);
-  }
-  if (d->pad_mode != JPDSE_PAD_REFLECT && p.Lk_fwd == d->S * p.Cs &&
-      taps4_shape_ok(d->R, d->S, d->stride, p.OH, p.OW, p.Cs, p.Ks, (long long)d->N * d->H * d->W * p.Cs, (long long)p.Ks * 16 * p.Cs))
-    return 0;
-  if (p.Lk_fwd == d->S * p.Cs &&
-      taps9_shape_ok(d->R, d->S, d->stride, p.OH, p.OW, p.Cs, p.Ks, (long long)d->N * d->H * d->W * p.Cs, (long long)p.Ks * 9 * p.Cs))
-    return 0;
-  // halo kernel (double-buffered form: inputs of 128+ channels): one slot per 4 x 64 output patch
-  if (halo_ok(d->R, d->S, d->stride, p.OH, p.OW, p.Cs, p.Ks) && p.Cs > 64) return (p.OH / 4) * (p.OW / 64);
-  return 0;
-}
-static bool dgrad2_rows_takes(const jpdse_conv_desc* d, const ConvPlan& p) {
-  return d->dtype == JPDSE_BF16 && g_fast_enabled && g_rows_enabled && d->pad_mode != JPDSE_PAD_REFLECT && d->stride == 2 && d->R == 3 &&
-         d->S == 3 && d->pad == 1 && p.Ks == 128 && p.Cs == 64 && d->C == 64 && d->H == 2 * p.OH && d->W == 2 * p.OW &&
-         p.OW % 64 == 0 && p.OH % 4 == 0 && p.nph == 4;
-}
-static int convT_fwd_moment_slots(const jpdse_conv_desc* d, const ConvPlan& p) {
-  if (!g_moments_fused || !dgrad2_rows_takes(d, p)) return 0;
-  const int strips = p.OW / 64;
-  return (p.OH / rows_band_height(d->N, p.OH, strips, 1, 256)) * strips;
 }
 
 }  // namespace jpdse

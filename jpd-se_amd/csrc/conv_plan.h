@@ -66,8 +66,7 @@ static void phase_axis(int st, int q, int Rf, int lo, int hi, int& U, int& i0, i
 
 // Split-K factor of the fast 256x128 kernel for a GEMM of M rows, Ks output channels and k_tiles
 // 64-wide K-tiles: only when the tiles alone would leave most of the 256 CUs idle.
-JPDSE_SWITCH(int, g_splitk_enabled, 1);   // A/B switches (jpdse_debug_set_fast_path 6 / 5)
-JPDSE_SWITCH(int, g_toep_enabled, 1);
+JPDSE_SWITCH(int, g_splitk_enabled, 1);   // A/B switches (jpdse_debug_set_fast_path 6 / 13)
 JPDSE_SWITCH(int, g_thin_out_fast, 1);
 static int splitk_for(int M, int Ks, int k_tiles) {
   if (!g_splitk_enabled) return 1;

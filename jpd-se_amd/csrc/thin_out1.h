@@ -271,15 +271,6 @@ __global__ __launch_bounds__(256) void thin1_reduce_kernel(const float* __restri
   }
 }
 
-JPDSE_SWITCH(int, g_thin1_enabled, 1);      // 41: the one-output-channel layers on the GEMM paths (A/B)
-
-static bool thin1_shape_ok(const jpdse_conv_desc* d, int Cs, int Ks) {
-  const int cv = Cs >> 3;
-  return g_fast_enabled && g_thin1_enabled && d->dtype == JPDSE_BF16 && d->K == 1 && Ks == 8 && d->stride == 1 &&
-         d->pad_mode != JPDSE_PAD_REFLECT && d->R == 4 && d->S == 4 && d->pad <= 3 && Cs % 128 == 0 && d->C == Cs &&
-         cv <= 256 && (cv & (cv - 1)) == 0;
-}
-
 static int launch_thin1_dgrad(Thin1DgradArgs a, hipStream_t s) {
   const int cv = a.Cs >> 3;
   if (cv < 8 || cv > 256 || (cv & (cv - 1)) != 0 || a.N <= 0 || a.H <= 0 || a.W <= 0 || (long long)a.N * a.H * a.W >= (1LL << 28))

@@ -198,7 +198,9 @@ SIGNATURES = {
 # the developer build (same sources, -DJPDSE_DEV): the shipped ABI plus include/jpdse_dev.h
 DEV_LIB_PATH = os.path.join(_HERE, 'libjpdse_hip_dev.so')
 DEV_SIGNATURES = {'jpdse_debug_set_fast_path': (_I32, [_I32]),
-                  'jpdse_debug_occupy_cus': (_I32, [_I32, _P, _I32, _P])}
+                  'jpdse_debug_occupy_cus': (_I32, [_I32, _P, _I32, _P]),
+                  'jpdse_debug_conv_route': (_I32, [_CD, _I32, ctypes.POINTER(_I32)]),
+                  'jpdse_debug_route_name': (ctypes.c_char_p, [_I32, _I32])}
 
 _lib = None
 _dev = None
