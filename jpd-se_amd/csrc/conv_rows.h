@@ -9,7 +9,7 @@
 //   * wave (wc, wp) owns 32 output channels (wc) of 64 / WP pixels (wp) and keeps its 32 x 576 filter slice as 36
 //     MFMA B-fragments (144 VGPRs), loaded once per block straight from the packed panel;
 //   * input rows arrive by LDS-DMA into a ring of NR rows, issued LA iterations ahead (counted vmcnt, one raw barrier per
-//     output row); padding is resolved by the loader (zero page); for stride 2 the loader de-interleaves a row into
+//     output row: the skeleton and its invariants are in rows_stream.h); padding is resolved by the loader (zero page); for stride 2 the loader de-interleaves a row into
 //     [even pixels | odd pixels] so that a tap's 32 pixels are 32 CONSECUTIVE 128-byte LDS rows and the halo kernel's
 //     conflict-free swizzle (16-byte chunk ^ (row >> 1)) applies unchanged;
 //   * per output row and wave: 9 taps x 4 k-steps x MT MFMAs, A fragments read at tap-shifted addresses; the result goes
@@ -17,15 +17,12 @@
 // LDS fill per output row: STRIDE new input rows (8.4 / 33 KB) instead of 9 x 32 KB per 128 pixels.
 #pragma once
 #include "common.h"
-#include "gemm_fast.h"
-#include "gemm_halo.h"
-#include "head_fwd.h"
+#include "gemm_fast.h"   // g_zero_page, add_bf16x8, relu_mask8
+#include "lds_ops.h"
+#include "rows_stream.h"
 
 namespace jpdse {
 
-__device__ __forceinline__ void lds_store32u(uint32_t addr, uint32_t v) {
-  asm volatile("ds_write_b32 %0, %1" ::"v"(addr), "v"(v) : "memory");
-}
 
 // acc_tile_to_lds (gemm_fast.h) with the LDS stores as inline asm: an ordinary LDS store issued while an LDS-DMA is in
 // flight gets `s_waitcnt vmcnt(0)` from hipcc (it cannot prove that the two do not overlap), which would drain the row
@@ -48,9 +45,7 @@ __device__ __forceinline__ void acc_rows_to_lds(uint32_t tile, int pitch, int la
       v1 = (v1 > 0.f ? v1 : v1 * nslope) * keep;
       // neighbour exchange as a DPP quad permutation [1,0,3,2]: __shfl_xor is a ds_bpermute round trip, 16 of them per
       // output row with nothing to hide them behind (one wave per SIMD)
-      const float recv = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, odd ? v0 : v1), 0xB1, 0xF, 0xF, false));
-      const float lo = odd ? recv : v0, hi = odd ? v1 : recv;
-      const uint32_t word = (uint32_t)f2bf(lo) | ((uint32_t)f2bf(hi) << 16);
+      const uint32_t word = pack_bf16_pair(v0, v1, odd);
       const int row = i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5) + odd;
       lds_store32u(tile + row * pitch + (lcol - odd) * 2, word);
     }
@@ -95,29 +90,12 @@ template <int STRIDE, int WC> struct RowsGeom {
   static constexpr int LDS = NR * ROWB + 4 * WTILE;
 };
 
-// s_waitcnt vmcnt(BASE + k * STEP), k = 0 .. MAXK chosen at run time (the immediate must be a constant)
-template <int BASE, int STEP, int MAXK = 8> __device__ __forceinline__ void wait_vmcnt_sel(int k) {
-  static_assert(MAXK <= 8 && BASE + MAXK * STEP <= 63, "vmcnt is a 6-bit counter");
-  constexpr auto at = [](int j) constexpr { return BASE + (j < MAXK ? j : MAXK) * STEP; };
-  switch (k) {
-    case 0: wait_vmcnt<at(0)>(); break;
-    case 1: wait_vmcnt<at(1)>(); break;
-    case 2: wait_vmcnt<at(2)>(); break;
-    case 3: wait_vmcnt<at(3)>(); break;
-    case 4: wait_vmcnt<at(4)>(); break;
-    case 5: wait_vmcnt<at(5)>(); break;
-    case 6: wait_vmcnt<at(6)>(); break;
-    case 7: wait_vmcnt<at(7)>(); break;
-    default: wait_vmcnt<at(8)>(); break;
-  }
-}
-
 template <int STRIDE, int WC, bool FUSED>
 __global__ __launch_bounds__(256, ((STRIDE == 1 && WC == 2) ? 2 : 1)) void conv_rows_kernel(const RowsArgs a) {
   typedef RowsGeom<STRIDE, WC> G;
   constexpr int WP = 4 / WC, MW = 64 / WP, MT = G::MT;        // pixel groups, pixels per wave, 32-row m-tiles per wave
   static_assert(MT == MW / 32 && G::LA <= 8, "geometry");
-  constexpr int U0 = G::UNITS / 4, U1 = U0 + 1, EXTRA = G::UNITS % 4;
+  typedef RowUnits<G::UNITS> RU;                              // this wave's DMA units of a row
   constexpr int NST = MT * 2;                                 // 16-byte stores per lane and output row
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -135,9 +113,9 @@ __global__ __launch_bounds__(256, ((STRIDE == 1 && WC == 2) ? 2 : 1)) void conv_
   const uint32_t smem0 = lds_addr32(smem);
 
   // ---- loader state: this wave's DMA units of a row (u = wid, wid + 4, ...); per lane the source column offset
-  int col_off[U1];
+  int col_off[RU::U1];
 #pragma unroll
-  for (int k = 0; k < U1; ++k) {
+  for (int k = 0; k < RU::U1; ++k) {
     const int u = wid + 4 * k;
     const int lp = u * 8 + (lane >> 3);
     int pp;                                                   // padded column of LDS pixel lp
@@ -157,8 +135,8 @@ __global__ __launch_bounds__(256, ((STRIDE == 1 && WC == 2) ? 2 : 1)) void conv_
     const bf16_t* const xrow = ximg + (row_ok ? ih : 0) * (long long)row_elems;
     char* const dst = smem + slot * G::ROWB;
 #pragma unroll
-    for (int k = 0; k < U1; ++k) {
-      if (k < U0 || wid < EXTRA) {
+    for (int k = 0; k < RU::U1; ++k) {
+      if (k < RU::U0 || wid < RU::EXTRA) {
         const bf16_t* src = (row_ok && col_off[k] >= 0) ? xrow + col_off[k] : zero;
         glds16(src, dst + (wid + 4 * k) * 1024);
       }
@@ -204,15 +182,12 @@ __global__ __launch_bounds__(256, ((STRIDE == 1 && WC == 2) ? 2 : 1)) void conv_
   for (int i = 0; i < a.TH; ++i) {
     // rows of iteration i landed; in flight behind them: the rows of iterations i+1 .. i+LA-1 and the stores of up to LA
     // earlier iterations (fewer at the start) -- see the issue order below
-    {
-      constexpr int B1 = (G::LA - 1) * STRIDE * U1, B0 = (G::LA - 1) * STRIDE * U0;
-      if constexpr (FUSED) {
-        // i > 0: the epilogue of iteration i-1 waited for its own addend / mask loads, which are younger than these rows
-        if (i == 0) { if (wid < EXTRA) wait_vmcnt<B1>(); else wait_vmcnt<B0>(); }
-      } else {
-        const int k = i < G::LA ? i : G::LA;                  // iterations whose NST stores may still be in flight
-        if (wid < EXTRA) wait_vmcnt_sel<B1, NST, G::LA>(k); else wait_vmcnt_sel<B0, NST, G::LA>(k);
-      }
+    if constexpr (FUSED) {
+      // i > 0: the epilogue of iteration i-1 waited for its own addend / mask loads, which are younger than these rows
+      if (i == 0) wait_rows<G::UNITS, (G::LA - 1) * STRIDE>(wid);
+    } else {
+      const int k = i < G::LA ? i : G::LA;                    // iterations whose NST stores may still be in flight
+      wait_rows<G::UNITS, (G::LA - 1) * STRIDE, NST, G::LA>(wid, k);
     }
     __builtin_amdgcn_s_barrier();     // every wave's pieces of these rows landed; the slots issued below were last read in i-1
     asm volatile("" ::: "memory");
@@ -232,24 +207,17 @@ __global__ __launch_bounds__(256, ((STRIDE == 1 && WC == 2) ? 2 : 1)) void conv_
     for (int k = 0; k < STRIDE; ++k) {                        // rows of iteration i + LA
       issue_row(njr, nslot);
       ++njr;
-      nslot = nslot + 1 == G::NR ? 0 : nslot + 1;
+      nslot = ring_next<G::NR>(nslot);
     }
     f32x16 acc[MT][1];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[mt][0][e] = 0.f;
-    // One wave per SIMD: nothing else hides the LDS round trip, and hipcc's own schedule (read, wait lgkmcnt(0), MFMA)
-    // exposed it at every one of the 36 k-steps (0.16 ms per launch at 512x1024, mostly waiting).  The fragment reads are
-    // inline asm, issued DEPTH k-steps ahead and waited for with a counted lgkmcnt (LDS operations return in order; the
-    // loop has no scalar-memory loads sharing the counter).
+    // fragment reads DEPTH k-steps ahead (rows_stream.h (4)): hipcc's own schedule cost 0.16 ms per launch at 512x1024
     uint32_t rbase[3];
 #pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      int slot = base + r;
-      slot = slot >= G::NR ? slot - G::NR : slot;
-      rbase[r] = smem0 + slot * G::ROWB;
-    }
+    for (int r = 0; r < 3; ++r) rbase[r] = smem0 + ring_slot<G::NR>(base, r) * G::ROWB;
     constexpr int DEPTH = 3;                                  // k-steps of fragments in flight
     s16x8 fr[DEPTH + 1][MT];
     auto rd = [&](int t, s16x8 (&f)[MT]) {                    // t = tap * 4 + ks, compile-time after unrolling
@@ -265,6 +233,8 @@ __global__ __launch_bounds__(256, ((STRIDE == 1 && WC == 2) ? 2 : 1)) void conv_
     for (int t = 0; t < 36; ++t) {
       if (t + DEPTH < 36) rd(t + DEPTH, fr[(t + DEPTH) % (DEPTH + 1)]);
       s16x8 (&f)[MT] = fr[t % (DEPTH + 1)];
+      // rows_stream.h's wait_unit, written out: behind the shared helper hipcc unrolls the row loop of the <2, 2, fused>
+      // instantiation differently (1855 instead of 2726 instructions), and this pass keeps every kernel's code as it was
       const int behind = (36 - 1 - t) < DEPTH ? (36 - 1 - t) : DEPTH;      // k-steps issued after step t
       if constexpr (MT == 2) {
         if (behind == 3) asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(f[0]), "+v"(f[1]));
@@ -282,8 +252,7 @@ __global__ __launch_bounds__(256, ((STRIDE == 1 && WC == 2) ? 2 : 1)) void conv_
         acc[mt][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f[mt], breg[t], acc[mt][0], 0, 0, 0);
     }
     __builtin_amdgcn_s_setprio(0);
-    base += STRIDE;
-    base = base >= G::NR ? base - G::NR : base;
+    base = ring_slot<G::NR>(base, STRIDE);
     if (a.mom != nullptr) {
       if (i == 0) mpilot = bf16_round(acc[0][0][0]);          // this lane's own pilot (no cross-lane traffic in this loop)
 #pragma unroll
@@ -299,7 +268,7 @@ __global__ __launch_bounds__(256, ((STRIDE == 1 && WC == 2) ? 2 : 1)) void conv_
     acc_rows_to_lds<MT>(lds_addr32(wtile), G::WPITCH, lane, acc, bv, nslope, keep);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if constexpr (FUSED) {                                    // addend / mask loads are older than this iteration's row DMA
-      if (wid < EXTRA) wait_vmcnt<STRIDE * U1>(); else wait_vmcnt<STRIDE * U0>();
+      wait_rows<G::UNITS, STRIDE>(wid);
     }
     // (the launcher guarantees OH % TH == 0: every iteration issues its NST stores, which the counted waits rely on)
 #pragma unroll

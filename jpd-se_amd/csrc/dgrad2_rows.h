@@ -3,7 +3,7 @@
 // 256x512, dx 64 channels at 512x1024.  As four stride-phase GEMMs on the tiled kernel it runs at 310 TFLOP/s: K-dims
 // of 128..512 (2..8 K-tiles) never fill a pipeline, dy is re-staged once per phase and tap, the filter once per tile.
 //
-// conv_rows.h's scheme, transposed: the FILTER LIVES IN REGISTERS, dy streams through LDS once, and one pass over a dy
+// conv_rows.h's scheme (rows_stream.h), transposed: the FILTER LIVES IN REGISTERS, dy streams through LDS once, and one pass over a dy
 // row produces BOTH output rows it feeds, all four phases at once:
 //   dx[2a  ][2b  ] = dy[a][b] W11                                   (phase qh=1,qw=1: one tap)
 //   dx[2a  ][2b+1] = dy[a][b] W10' + dy[a][b+1] W10''               (two taps)
@@ -16,10 +16,9 @@
 // The 2 x 128 output pixels of a dy row go through one LDS tile and leave as full 128-byte pixels (8 lanes x 16 B).
 #pragma once
 #include "common.h"
-#include "gemm_fast.h"
-#include "gemm_halo.h"
-#include "head_fwd.h"
-#include "conv_rows.h"
+#include "gemm_fast.h"   // g_zero_page
+#include "lds_ops.h"
+#include "rows_stream.h"
 
 namespace jpdse {
 
@@ -53,7 +52,7 @@ __device__ __forceinline__ int d2_tile_off(int row, int part) {       // byte of
 
 __global__ __launch_bounds__(256) void dgrad2_rows_kernel(const Dgrad2Args a) {
   typedef Dgrad2Geom G;
-  constexpr int U0 = G::UNITS / 4, U1 = U0 + 1, EXTRA = G::UNITS % 4;
+  typedef RowUnits<G::UNITS> RU;                        // this wave's DMA units of a row
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -67,9 +66,9 @@ __global__ __launch_bounds__(256) void dgrad2_rows_kernel(const Dgrad2Args a) {
   const uint32_t tile0 = smem0 + G::NR * G::ROWB;
 
   // ---- loader: this wave's units of a dy row (u = wid, wid + 4, ...): 4 pixels x 16 chunks of 16 B per unit
-  int col_off[U1];
+  int col_off[RU::U1];
 #pragma unroll
-  for (int k = 0; k < U1; ++k) {
+  for (int k = 0; k < RU::U1; ++k) {
     const int u = wid + 4 * k;
     const int lp = u * 4 + (lane >> 4);                // LDS pixel = dy column b0 + lp
     const int bw = b0 + lp;
@@ -89,8 +88,8 @@ __global__ __launch_bounds__(256) void dgrad2_rows_kernel(const Dgrad2Args a) {
     const bf16_t* const xrow = img + (row_ok ? ih : 0) * (long long)row_elems;
     char* const dst = smem + slot * G::ROWB;
 #pragma unroll
-    for (int k = 0; k < U1; ++k) {
-      if (k < U0 || wid < EXTRA) {
+    for (int k = 0; k < RU::U1; ++k) {
+      if (k < RU::U0 || wid < RU::EXTRA) {
         const bf16_t* src = (row_ok && col_off[k] >= 0) ? xrow + col_off[k] : zero;
         glds16(src, dst + (wid + 4 * k) * 1024);
       }
@@ -144,7 +143,7 @@ __global__ __launch_bounds__(256) void dgrad2_rows_kernel(const Dgrad2Args a) {
     {
       int k = i - 1;
       k = k < 0 ? 0 : (k > G::LA - 1 ? G::LA - 1 : k);
-      if (wid < EXTRA) wait_vmcnt_sel<(G::LA - 1) * U1, 8, G::LA - 1>(k); else wait_vmcnt_sel<(G::LA - 1) * U0, 8, G::LA - 1>(k);
+      wait_rows<G::UNITS, G::LA - 1, 8, G::LA - 1>(wid, k);
     }
     __builtin_amdgcn_s_barrier();       // A: rows i, i+1 complete for every wave; the tile of iteration i-1 is written
     asm volatile("" ::: "memory");
@@ -161,7 +160,7 @@ __global__ __launch_bounds__(256) void dgrad2_rows_kernel(const Dgrad2Args a) {
     }
     issue_row(njr, nslot);
     ++njr;
-    nslot = nslot + 1 == G::NR ? 0 : nslot + 1;
+    nslot = ring_next<G::NR>(nslot);
 
     f32x4 acc[4][4];                                    // [m-tile][ee, eo, oe, oo]
 #pragma unroll
@@ -169,7 +168,7 @@ __global__ __launch_bounds__(256) void dgrad2_rows_kernel(const Dgrad2Args a) {
 #pragma unroll
       for (int ph = 0; ph < 4; ++ph) acc[mt][ph] = f32x4{0.f, 0.f, 0.f, 0.f};
     const uint32_t r0 = smem0 + base * G::ROWB;
-    const uint32_t r1 = smem0 + (base + 1 == G::NR ? 0 : base + 1) * G::ROWB;
+    const uint32_t r1 = smem0 + ring_next<G::NR>(base) * G::ROWB;
     s16x8 fr[3][4];                                     // [unit in flight][dy[a][b], dy[a][b+1], dy[a+1][b], dy[a+1][b+1]]
     auto rd = [&](int u, s16x8 (&f)[4]) {               // unit u = mt * 4 + ks
       const int mt = u >> 2, ks = u & 3;
@@ -187,9 +186,7 @@ __global__ __launch_bounds__(256) void dgrad2_rows_kernel(const Dgrad2Args a) {
     for (int u = 0; u < 16; ++u) {
       if (u + 2 < 16) rd(u + 2, fr[(u + 2) % 3]);
       s16x8 (&f)[4] = fr[u % 3];
-      if (u + 2 < 16) asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]));
-      else if (u + 1 < 16) asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]));
-      else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]));
+      wait_unit<16, 2>(u, f[0], f[1], f[2], f[3]);
       const int mt = u >> 2, ks = u & 3;
       acc[mt][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[0], breg[0 * 4 + ks], acc[mt][0], 0, 0, 0);
       acc[mt][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[0], breg[1 * 4 + ks], acc[mt][1], 0, 0, 0);
@@ -201,7 +198,7 @@ __global__ __launch_bounds__(256) void dgrad2_rows_kernel(const Dgrad2Args a) {
       acc[mt][3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[2], breg[7 * 4 + ks], acc[mt][3], 0, 0, 0);
       acc[mt][3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[3], breg[8 * 4 + ks], acc[mt][3], 0, 0, 0);
     }
-    base = base + 1 == G::NR ? 0 : base + 1;
+    base = ring_next<G::NR>(base);
     if (a.mom != nullptr) {
       if (i == 0) mpilot = bf16_round(acc[0][0][0]);      // this lane's own pilot (no cross-lane traffic in this loop)
 #pragma unroll
@@ -226,9 +223,7 @@ __global__ __launch_bounds__(256) void dgrad2_rows_kernel(const Dgrad2Args a) {
 #pragma unroll
         for (int ep = 0; ep < 2; ++ep) {
           const float v0 = acc[mt][ph][2 * ep], v1 = acc[mt][ph][2 * ep + 1];
-          const float recv = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, odd ? v0 : v1), 0xB1, 0xF, 0xF, false));
-          const float lo = odd ? recv : v0, hi = odd ? v1 : recv;
-          const uint32_t word = (uint32_t)f2bf(lo) | ((uint32_t)f2bf(hi) << 16);
+          const uint32_t word = pack_bf16_pair(v0, v1, odd);
           const int bl = mt * 16 + 4 * (lane >> 4) + 2 * ep + odd;       // dy column inside the strip
           const int ch = wid * 16 + (lane & 15) - odd;
           lds_store32u(tile0 + d2_tile_off(pr * 128 + 2 * bl + pc, ch >> 3) + (ch & 7) * 2, word);

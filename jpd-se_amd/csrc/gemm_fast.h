@@ -14,6 +14,7 @@
 //   * 8 waves (2 per SIMD), BK = 64, s_setprio around the MFMA cluster.
 #pragma once
 #include "common.h"
+#include "lds_ops.h"
 
 namespace jpdse {
 
@@ -61,15 +62,6 @@ struct FastBatch {
   int n;
   int small_m;         // host only: every problem has few rows (the ring strips): 128-row tiles, two blocks per CU
 };
-
-__device__ __forceinline__ uint32_t lds_addr_of(const void* p) {      // 32-bit LDS address of a generic pointer into LDS
-  return (uint32_t)(uintptr_t)((__attribute__((address_space(3))) const char*)p);
-}
-
-__device__ __forceinline__ void glds16(const void* g, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 
 // LDS tile [rows][128 B] (one row = 64 bf16 of K): the eight 16-byte slots of a row are XOR-swizzled
 // with (row >> 1) & 7, which makes ds_read_b128 conflict free (rows of equal parity in a 16-lane read
@@ -211,10 +203,6 @@ __device__ __forceinline__ u32x4 lrelu_mask8(u32x4 v, u32x4 m, float slope) {
     v[i] = rlo | (rhi << 16);
   }
   return v;
-}
-
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
 // (A software-pipelined fragment schedule was measured 2-3 % SLOWER than the plain one in the same process and removed.)

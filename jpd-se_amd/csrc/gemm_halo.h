@@ -19,12 +19,6 @@
 
 namespace jpdse {
 
-// ds_read_b128 as inline asm (invisible to hipcc's wait insertion: the caller counts lgkmcnt by hand)
-__device__ __forceinline__ s16x8 lds_read128_asm(uint32_t addr) {
-  s16x8 v;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr));
-  return v;
-}
 struct HaloArgs {
   const bf16_t* X;   // [N][IH][IW][Cs]
   const bf16_t* B;   // panel [b_rows][9*Cs]

@@ -30,8 +30,7 @@
 #pragma once
 #include "gemm_fast.h"
 #include "gemm_halo.h"
-#include "head_fwd.h"
-#include "conv_rows.h"
+#include "lds_ops.h"
 
 namespace jpdse {
 

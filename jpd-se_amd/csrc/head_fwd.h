@@ -15,19 +15,8 @@
 
 namespace jpdse {
 
-// LDS stores as inline asm: hipcc puts `s_waitcnt vmcnt(0)` in front of every ordinary LDS STORE issued while
-// an LDS-DMA is in flight (it cannot prove that the two do not overlap), which drained the input-row prefetch
-// at the first Z store of every row.  The asm form is ordered by hand (lgkmcnt(0) + barrier before any reader).
-__device__ __forceinline__ void lds_store128(uint32_t addr, f32x4 v) {
-  asm volatile("ds_write_b128 %0, %1" ::"v"(addr), "v"(v) : "memory");
-}
-__device__ __forceinline__ void lds_store32(uint32_t addr, float v) {
-  asm volatile("ds_write_b32 %0, %1" ::"v"(addr), "v"(v) : "memory");
-}
-__device__ __forceinline__ uint32_t lds_addr32(const void* p) {
-  return (uint32_t)(uintptr_t)((__attribute__((address_space(3))) const char*)p);
-}
-
+// The Z and output-tile stores are inline asm (lds_ops.h): as ordinary LDS stores they drained the input-row prefetch at the
+// first Z store of every row.  They are ordered by hand (lgkmcnt(0) + barrier before any reader).
 struct HeadFwdArgs {
   const bf16_t* X;     // [N][H][W][CIN] unpadded
   const bf16_t* Wp;    // plain forward panel [Ks][R][S*CIN] (row k: (r, s, c) contiguous)

@@ -4,7 +4,7 @@
 // output: per input row an MFMA phase, a 64 KB Z tile through LDS and an owner phase, serialised behind two barriers
 // with one block per CU -- 0.37 ms where reading the input once takes 0.06.
 //
-// Row-streaming form (conv_rows.h's skeleton): the column taps go INTO the GEMM, the row taps into its columns:
+// Row-streaming form (rows_stream.h): the column taps go INTO the GEMM, the row taps into its columns:
 //     Z'[q][(r, k)] = sum_{s, c} x[j][q + s][c] * w[k][r][s][c]        (N = R x 4 <= 28 columns, K-dim = S x 64)
 //     y[j - r][q][k] += Z'[q][(r, k)]
 // One MFMA pass per input row j with the A fragments read at s-shifted addresses (no im2col) and the 28-column filter in
@@ -15,10 +15,10 @@
 // A block = 128 output pixels x TH rows, wave w = pixels [32w, 32w + 32).
 #pragma once
 #include "common.h"
-#include "gemm_fast.h"
-#include "gemm_halo.h"
-#include "head_fwd.h"
-#include "conv_rows.h"
+#include "gemm_fast.h"   // g_zero_page
+#include "head_fwd.h"    // HeadFwdArgs
+#include "lds_ops.h"
+#include "rows_stream.h"
 
 namespace jpdse {
 
@@ -38,9 +38,6 @@ template <int R, int CIN = 64> struct HeadRowsGeom {
   static constexpr int LDS = NR * ROWB + 4 * OTILE;
 };
 
-__device__ __forceinline__ void lds_add_f32(uint32_t addr, float v) {
-  asm volatile("ds_add_f32 %0, %1" ::"v"(addr), "v"(v) : "memory");
-}
 
 template <int R, int CIN = 64>
 __global__ __launch_bounds__(256, 2) void head_rows_kernel(const HeadFwdArgs a, int TH, int bands, int strips) {
@@ -48,7 +45,7 @@ __global__ __launch_bounds__(256, 2) void head_rows_kernel(const HeadFwdArgs a, 
   typedef HeadRowsGeom<R, CIN> G;
   constexpr int KPT = CIN / 16;                               // k16-steps per column tap
   constexpr int S = R, T = S * KPT;                           // k16-steps per input row
-  constexpr int U0 = G::UNITS / 4, U1 = U0 + 1, EXTRA = G::UNITS % 4;
+  typedef RowUnits<G::UNITS> RU;                              // this wave's DMA units of a row
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -62,15 +59,15 @@ __global__ __launch_bounds__(256, 2) void head_rows_kernel(const HeadFwdArgs a, 
   char* const otile = smem + G::NR * G::ROWB + wid * G::OTILE;
   const uint32_t otile0 = lds_addr32(otile);
 
-  // zero the output rows under construction BEFORE any DMA is in flight (plain LDS stores: see head_fwd.h)
+  // zero the output rows under construction BEFORE any DMA is in flight (plain LDS stores: see lds_ops.h)
   for (int i = lane; i < G::OTILE / 16; i += 64) *reinterpret_cast<f32x4*>(otile + i * 16) = f32x4{0.f, 0.f, 0.f, 0.f};
   float fz = reinterpret_cast<const float*>(g_zero_page)[0];  // a zero the compiler cannot fold (MFMA -> asm LDS data: head_fwd.h)
   asm volatile("" : "+v"(fz));
 
   // ---- loader
-  int col_off[U1];
+  int col_off[RU::U1];
 #pragma unroll
-  for (int k = 0; k < U1; ++k) {
+  for (int k = 0; k < RU::U1; ++k) {
     const int u = wid + 4 * k;
     const int lp = CIN == 64 ? u * 8 + (lane >> 3) : u * 16 + (lane >> 2);
     int iw = ow0 - a.pad + lp;
@@ -89,8 +86,8 @@ __global__ __launch_bounds__(256, 2) void head_rows_kernel(const HeadFwdArgs a, 
     const bf16_t* const xrow = ximg + (row_ok ? ih : 0) * (long long)row_elems;
     char* const dst = smem + slot * G::ROWB;
 #pragma unroll
-    for (int k = 0; k < U1; ++k) {
-      if (k < U0 || wid < EXTRA) {
+    for (int k = 0; k < RU::U1; ++k) {
+      if (k < RU::U0 || wid < RU::EXTRA) {
         const bf16_t* src = (row_ok && col_off[k] >= 0) ? xrow + col_off[k] : zero;
         glds16(src, dst + (wid + 4 * k) * 1024);
       }
@@ -133,13 +130,13 @@ __global__ __launch_bounds__(256, 2) void head_rows_kernel(const HeadFwdArgs a, 
     {
       int k = j - (R - 1);
       k = k < 0 ? 0 : (k > G::LA ? G::LA : k);
-      if (wid < EXTRA) wait_vmcnt_sel<G::LA * U1, 1, G::LA>(k); else wait_vmcnt_sel<G::LA * U0, 1, G::LA>(k);
+      wait_rows<G::UNITS, G::LA, 1, G::LA>(wid, k);       // behind row j: LA rows and the pixel stores of up to LA iterations
     }
     __builtin_amdgcn_s_barrier();       // row j complete for every wave; the slot issued below held row j-1
     asm volatile("" ::: "memory");
     issue_row(njr, nslot);
     ++njr;
-    nslot = nslot + 1 == G::NR ? 0 : nslot + 1;
+    nslot = ring_next<G::NR>(nslot);
 
     f32x16 acc;
 #pragma unroll
@@ -157,14 +154,10 @@ __global__ __launch_bounds__(256, 2) void head_rows_kernel(const HeadFwdArgs a, 
     for (int t = 0; t < T; ++t) {
       if (t + DEPTH < T) fr[(t + DEPTH) % (DEPTH + 1)] = rd(t + DEPTH);
       s16x8& f = fr[t % (DEPTH + 1)];
-      const int behind = (T - 1 - t) < DEPTH ? (T - 1 - t) : DEPTH;
-      if (behind == 3) asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(f));
-      else if (behind == 2) asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(f));
-      else if (behind == 1) asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(f));
-      else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f));
+      wait_unit<T, DEPTH>(t, f);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f, breg[t], acc, 0, 0, 0);
     }
-    base = base + 1 == G::NR ? 0 : base + 1;
+    base = ring_next<G::NR>(base);
 
     // ---- column (r, k) -> output row j - r of the wave's tile: read, add, write back (ds_add_f32 is correct here too, but
     // LDS float atomics run lane by lane: 16 of them cost ~4 us per input row).  Each address belongs to one lane per

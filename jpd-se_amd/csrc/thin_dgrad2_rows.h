@@ -12,10 +12,9 @@
 // read-add-write in a fixed order (deterministic), as in head_rows.h.  Block = 256 output pixels x TH rows, wave = 64 pixels.
 #pragma once
 #include "common.h"
-#include "gemm_fast.h"
-#include "gemm_halo.h"
-#include "head_fwd.h"
-#include "conv_rows.h"
+#include "gemm_fast.h"   // g_zero_page
+#include "lds_ops.h"
+#include "rows_stream.h"
 
 namespace jpdse {
 
@@ -40,7 +39,7 @@ struct ThinDgrad2Geom {
 __global__ __launch_bounds__(256, 2) void thin_dgrad2_rows_kernel(const ThinDgrad2Args a) {
   typedef ThinDgrad2Geom G;
   constexpr int T = 8;                                 // k16-steps per dy row: 2 column taps x 64 channels
-  constexpr int U0 = G::UNITS / 4, U1 = U0 + 1, EXTRA = G::UNITS % 4;
+  typedef RowUnits<G::UNITS> RU;                        // this wave's DMA units of a row
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -58,9 +57,9 @@ __global__ __launch_bounds__(256, 2) void thin_dgrad2_rows_kernel(const ThinDgra
   float fz = reinterpret_cast<const float*>(g_zero_page)[0];
   asm volatile("" : "+v"(fz));
 
-  int col_off[U1];
+  int col_off[RU::U1];
 #pragma unroll
-  for (int k = 0; k < U1; ++k) {
+  for (int k = 0; k < RU::U1; ++k) {
     const int u = wid + 4 * k;
     const int lp = u * 8 + (lane >> 3);                // LDS pixel = dy column m0 + lp
     const int ow = m0 + lp;
@@ -76,8 +75,8 @@ __global__ __launch_bounds__(256, 2) void thin_dgrad2_rows_kernel(const ThinDgra
     const bf16_t* const xrow = img + (row_ok ? oh : 0) * (long long)row_elems;
     char* const dst = smem + slot * G::ROWB;
 #pragma unroll
-    for (int k = 0; k < U1; ++k) {
-      if (k < U0 || wid < EXTRA) {
+    for (int k = 0; k < RU::U1; ++k) {
+      if (k < RU::U0 || wid < RU::EXTRA) {
         const bf16_t* src = (row_ok && col_off[k] >= 0) ? xrow + col_off[k] : zero;
         glds16(src, dst + (wid + 4 * k) * 1024);
       }
@@ -119,13 +118,13 @@ __global__ __launch_bounds__(256, 2) void thin_dgrad2_rows_kernel(const ThinDgra
     {
       int k = jj - 1;
       k = k < 0 ? 0 : (k > G::LA ? G::LA : k);
-      if (wid < EXTRA) wait_vmcnt_sel<G::LA * U1, 2, G::LA>(k); else wait_vmcnt_sel<G::LA * U0, 2, G::LA>(k);
+      wait_rows<G::UNITS, G::LA, 2, G::LA>(wid, k);       // behind row jj: LA rows and the two pixel stores of up to LA iterations
     }
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     issue_row(njr, nslot);
     ++njr;
-    nslot = nslot + 1 == G::NR ? 0 : nslot + 1;
+    nslot = ring_next<G::NR>(nslot);
 
     f32x16 acc;
 #pragma unroll
@@ -136,17 +135,10 @@ __global__ __launch_bounds__(256, 2) void thin_dgrad2_rows_kernel(const ThinDgra
     for (int t2 = 0; t2 < T; ++t2) fr[t2] = lds_read128_asm(rb + a_base[t2 >> 2] + (((2 * (t2 & 3) + hsel) << 4) ^ a_sw[t2 >> 2]));
 #pragma unroll
     for (int t2 = 0; t2 < T; ++t2) {
-      if (t2 == 0) asm volatile("s_waitcnt lgkmcnt(7)" : "+v"(fr[0]));
-      else if (t2 == 1) asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(fr[1]));
-      else if (t2 == 2) asm volatile("s_waitcnt lgkmcnt(5)" : "+v"(fr[2]));
-      else if (t2 == 3) asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(fr[3]));
-      else if (t2 == 4) asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(fr[4]));
-      else if (t2 == 5) asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(fr[5]));
-      else if (t2 == 6) asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(fr[6]));
-      else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fr[7]));
+      wait_unit<T, T - 1>(t2, fr[t2]);                  // all eight k-steps are in flight: lgkmcnt(7 - t2)
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[t2], breg[t2], acc, 0, 0, 0);
     }
-    base = base + 1 == G::NR ? 0 : base + 1;
+    base = ring_next<G::NR>(base);
 
     // ---- column (r, b, k) -> dx row 2 jj - 2 + r of the band, pixel 2 m' + b
     {

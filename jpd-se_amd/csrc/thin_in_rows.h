@@ -13,10 +13,9 @@
 // scratch tensor; reflect_ring_fold_kernel then adds the ring into the <= 2 % of dx pixels that have aliases.
 #pragma once
 #include "common.h"
-#include "gemm_fast.h"
-#include "gemm_halo.h"
-#include "head_fwd.h"
-#include "conv_rows.h"
+#include "gemm_fast.h"   // g_zero_page
+#include "lds_ops.h"
+#include "rows_stream.h"
 
 namespace jpdse {
 
@@ -146,7 +145,7 @@ __global__ __launch_bounds__(256, 2) void thin_in_rows_kernel(const ThinInArgs a
     if (i > 0) store_tile(oh0 + i - 1);
     issue_row(njr, nslot);
     ++njr;
-    nslot = nslot + 1 == G::NR ? 0 : nslot + 1;
+    nslot = ring_next<G::NR>(nslot);
 
     f32x4 acc[2][2];
 #pragma unroll
@@ -157,9 +156,7 @@ __global__ __launch_bounds__(256, 2) void thin_in_rows_kernel(const ThinInArgs a
     s16x8 fr[DEPTH + 1][2];
     auto rd = [&](int t, s16x8 (&f)[2]) {
       const int r = t / KS, ks = t - KS * r;
-      int slot = base + r;
-      slot = slot >= G::NR ? slot - G::NR : slot;
-      const uint32_t rb = smem0 + slot * G::ROWB + ks * 64;
+      const uint32_t rb = smem0 + ring_slot<G::NR>(base, r) * G::ROWB + ks * 64;
 #pragma unroll
       for (int i2 = 0; i2 < 2; ++i2) f[i2] = lds_read128_asm(rb + a_off[i2]);
     };
@@ -169,18 +166,14 @@ __global__ __launch_bounds__(256, 2) void thin_in_rows_kernel(const ThinInArgs a
     for (int t = 0; t < T; ++t) {
       if (t + DEPTH < T) rd(t + DEPTH, fr[(t + DEPTH) % (DEPTH + 1)]);
       s16x8 (&f)[2] = fr[t % (DEPTH + 1)];
-      const int behind = (T - 1 - t) < DEPTH ? (T - 1 - t) : DEPTH;
-      if (behind == 3) asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(f[0]), "+v"(f[1]));
-      else if (behind == 2) asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(f[0]), "+v"(f[1]));
-      else if (behind == 1) asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(f[0]), "+v"(f[1]));
-      else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0]), "+v"(f[1]));
+      wait_unit<T, DEPTH>(t, f[0], f[1]);
 #pragma unroll
       for (int i2 = 0; i2 < 2; ++i2)
 #pragma unroll
         for (int j = 0; j < 2; ++j)
           acc[i2][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[i2], breg[t * 2 + j], acc[i2][j], 0, 0, 0);
     }
-    base = base + 1 == G::NR ? 0 : base + 1;
+    base = ring_next<G::NR>(base);
     __builtin_amdgcn_s_barrier();       // B: the previous tile has been read (THINB)
     asm volatile("" ::: "memory");
 #pragma unroll
@@ -192,9 +185,7 @@ __global__ __launch_bounds__(256, 2) void thin_in_rows_kernel(const ThinInArgs a
           float v0 = acc[i2][j][2 * ep] + bv[j], v1 = acc[i2][j][2 * ep + 1] + bv[j];
           v0 = v0 > 0.f ? v0 : v0 * nslope;
           v1 = v1 > 0.f ? v1 : v1 * nslope;
-          const float recv = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, odd ? v0 : v1), 0xB1, 0xF, 0xF, false));
-          const float lo = odd ? recv : v0, hi = odd ? v1 : recv;
-          const uint32_t word = (uint32_t)f2bf(lo) | ((uint32_t)f2bf(hi) << 16);
+          const uint32_t word = pack_bf16_pair(v0, v1, odd);
           const int px = wp * 32 + i2 * 16 + 4 * (lane >> 4) + 2 * ep + odd;
           const int ch = wc * 32 + j * 16 + (lane & 15) - odd;
           lds_store32u(tile0 + px * G::PITCH + ch * 2, word);

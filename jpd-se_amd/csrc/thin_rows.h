@@ -3,7 +3,7 @@
 // stages the strips of a 4 x 64 output tile once and streams the four filter rows through a barrier-stepped ring: short
 // per-tile pipelines, 0.23 ms (360 TFLOP/s) where the bytes take 0.1.
 //
-// Row-streaming form (conv_rows.h): filter in REGISTERS, input rows streamed once through an LDS-DMA ring, one output row
+// Row-streaming form (rows_stream.h): filter in REGISTERS, input rows streamed once through an LDS-DMA ring, one output row
 // per iteration.  The input stays dense ([pixel][40 channels], 80 B per pixel): the run of output pixel q for filter row r is the
 // 320 contiguous bytes at pixel 2q of input row 2 oh + r - 2, i.e. K-dim 160 = 5 k-steps of v_mfma_f32_16x16x32_bf16 per
 // filter row, and the A fragment of (q, k-step) is a plain 16-byte read at q * 160 + ks * 64 + 16 * (lane >> 4) -- conflict
@@ -12,11 +12,10 @@
 // B = 4 rows x 5 k-steps x 2 tiles x 4 VGPRs = 160 VGPRs, from the thin panel [R][K][KP] the packer already writes.
 #pragma once
 #include "common.h"
-#include "gemm_fast.h"
-#include "gemm_halo.h"
-#include "head_fwd.h"
-#include "conv_rows.h"
-#include "thin_fwd.h"
+#include "gemm_fast.h"   // g_zero_page
+#include "thin_fwd.h"    // ThinFwdArgs
+#include "lds_ops.h"
+#include "rows_stream.h"
 
 namespace jpdse {
 
@@ -33,7 +32,7 @@ struct ThinRowsGeom {
 
 __global__ __launch_bounds__(256, 2) void thin_rows_kernel(const ThinFwdArgs a, int TH, int bands) {
   typedef ThinRowsGeom G;
-  constexpr int U0 = G::UNITS / 4, U1 = U0 + 1, EXTRA = G::UNITS % 4;
+  typedef RowUnits<G::UNITS> RU;                        // this wave's DMA units of a row
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -49,9 +48,9 @@ __global__ __launch_bounds__(256, 2) void thin_rows_kernel(const ThinFwdArgs a, 
   const uint32_t tile0 = smem0 + G::NR * G::ROWB;
 
   // ---- loader: 16-byte chunk g of the dense strip = pixel g / 5, channel part g % 5
-  int col_off[U1];
+  int col_off[RU::U1];
 #pragma unroll
-  for (int k = 0; k < U1; ++k) {
+  for (int k = 0; k < RU::U1; ++k) {
     const int u = wid + 4 * k;
     const int g = u * 64 + lane;
     const int px = g / 5, part = g - px * 5;
@@ -68,8 +67,8 @@ __global__ __launch_bounds__(256, 2) void thin_rows_kernel(const ThinFwdArgs a, 
     const bf16_t* const xrow = ximg + (row_ok ? ih : 0) * (long long)row_elems;
     char* const dst = smem + slot * G::ROWB;
 #pragma unroll
-    for (int k = 0; k < U1; ++k) {
-      if (k < U0 || wid < EXTRA) {
+    for (int k = 0; k < RU::U1; ++k) {
+      if (k < RU::U0 || wid < RU::EXTRA) {
         const bf16_t* src = (row_ok && col_off[k] >= 0) ? xrow + col_off[k] : zero;
         glds16(src, dst + (wid + 4 * k) * 1024);
       }
@@ -113,7 +112,7 @@ __global__ __launch_bounds__(256, 2) void thin_rows_kernel(const ThinFwdArgs a, 
   for (int i = 0; i < rows_here; ++i) {
     // conservative count: only the row DMAs of later iterations may be in flight (the tile stores of the last strip are
     // partly masked, so their number is not a constant)
-    if (wid < EXTRA) wait_vmcnt<(G::LA - 1) * 2 * U1>(); else wait_vmcnt<(G::LA - 1) * 2 * U0>();
+    wait_rows<G::UNITS, (G::LA - 1) * 2>(wid);
     __builtin_amdgcn_s_barrier();       // A: the four rows of this iteration are complete; the tile of row i-1 is written
     asm volatile("" ::: "memory");
     if (i > 0) {
@@ -131,7 +130,7 @@ __global__ __launch_bounds__(256, 2) void thin_rows_kernel(const ThinFwdArgs a, 
     for (int k = 0; k < 2; ++k) {
       issue_row(njr, nslot);
       ++njr;
-      nslot = nslot + 1 == G::NR ? 0 : nslot + 1;
+      nslot = ring_next<G::NR>(nslot);
     }
 
     f32x4 acc[2][2];
@@ -141,11 +140,7 @@ __global__ __launch_bounds__(256, 2) void thin_rows_kernel(const ThinFwdArgs a, 
       for (int j = 0; j < 2; ++j) acc[i2][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     uint32_t rbase[4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      int slot = base + r;
-      slot = slot >= G::NR ? slot - G::NR : slot;
-      rbase[r] = smem0 + slot * G::ROWB;
-    }
+    for (int r = 0; r < 4; ++r) rbase[r] = smem0 + ring_slot<G::NR>(base, r) * G::ROWB;
     constexpr int T = 20, DEPTH = 3;                    // (filter row, k-step) units; units of fragments in flight
     s16x8 fr[DEPTH + 1][2];
     auto rd = [&](int t, s16x8 (&f)[2]) {
@@ -159,19 +154,14 @@ __global__ __launch_bounds__(256, 2) void thin_rows_kernel(const ThinFwdArgs a, 
     for (int t = 0; t < T; ++t) {
       if (t + DEPTH < T) rd(t + DEPTH, fr[(t + DEPTH) % (DEPTH + 1)]);
       s16x8 (&f)[2] = fr[t % (DEPTH + 1)];
-      const int behind = (T - 1 - t) < DEPTH ? (T - 1 - t) : DEPTH;
-      if (behind == 3) asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(f[0]), "+v"(f[1]));
-      else if (behind == 2) asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(f[0]), "+v"(f[1]));
-      else if (behind == 1) asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(f[0]), "+v"(f[1]));
-      else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0]), "+v"(f[1]));
+      wait_unit<T, DEPTH>(t, f[0], f[1]);
 #pragma unroll
       for (int i2 = 0; i2 < 2; ++i2)
 #pragma unroll
         for (int j = 0; j < 2; ++j)
           acc[i2][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[i2], breg[t * 2 + j], acc[i2][j], 0, 0, 0);
     }
-    base += 2;
-    base = base >= G::NR ? base - G::NR : base;
+    base = ring_slot<G::NR>(base, 2);
     __builtin_amdgcn_s_barrier();       // B: the tile of row i-1 has been read by every thread
     asm volatile("" ::: "memory");
     // ---- accumulators (16x16: column lane & 15, rows 4 (lane >> 4) + e) -> bias, activation, bf16 -> tile[pixel][channel]
@@ -184,9 +174,7 @@ __global__ __launch_bounds__(256, 2) void thin_rows_kernel(const ThinFwdArgs a, 
           float v0 = acc[i2][j][2 * ep] + bv[j][0], v1 = acc[i2][j][2 * ep + 1] + bv[j][0];
           v0 = v0 > 0.f ? v0 : v0 * nslope;
           v1 = v1 > 0.f ? v1 : v1 * nslope;
-          const float recv = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, odd ? v0 : v1), 0xB1, 0xF, 0xF, false));
-          const float lo = odd ? recv : v0, hi = odd ? v1 : recv;
-          const uint32_t word = (uint32_t)f2bf(lo) | ((uint32_t)f2bf(hi) << 16);
+          const uint32_t word = pack_bf16_pair(v0, v1, odd);
           const int px = wp * 32 + i2 * 16 + 4 * (lane >> 4) + 2 * ep + odd;
           const int ch = wc * 32 + j * 16 + (lane & 15) - odd;
           lds_store32u(tile0 + px * G::PITCH + ch * 2, word);

@@ -123,7 +123,7 @@ __global__ __launch_bounds__(64 * WM * WN) void wgrad_fast_kernel(const FastWgAr
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wid / WN, wn = wid % WN;
-  const uint32_t lds0 = lds_addr_of(smem);
+  const uint32_t lds0 = lds_addr32(smem);
 
   const int c_tiles = ((a.run_mode ? a.run_len : a.Cs) + BN - 1) / BN;
   const int n_taps = a.run_mode ? a.R : a.R * a.S;

@@ -70,7 +70,7 @@ __global__ __launch_bounds__(512) void wgrad_nine_kernel(const NineWgArgs a) {
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wk = wid & 1, wc = (wid >> 1) & 1, ph = wid >> 2;
   const bf16_t* const zero = reinterpret_cast<const bf16_t*>(g_zero_page);
-  const uint32_t lds0 = lds_addr_of(smem);
+  const uint32_t lds0 = lds_addr32(smem);
 
   // ---- block -> (tile, split) ---------------------------------------------------------------------
   const int tiles = a.k_tiles * a.c_tiles;

@@ -74,7 +74,7 @@ __global__ __launch_bounds__(64 * WM * WN) void wgrad_taps_kernel(const TapsWgAr
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wid / WN, wn = wid % WN;
   const bf16_t* const zero = reinterpret_cast<const bf16_t*>(g_zero_page);
-  const uint32_t lds0 = lds_addr_of(smem);
+  const uint32_t lds0 = lds_addr32(smem);
 
   int tile, sub;
   if (a.xg_gs) {

@@ -63,7 +63,7 @@ __global__ __launch_bounds__(64 * WM * WN) void wgrad_thin_kernel(const ThinWgAr
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wid / WN, wn = wid % WN;
-  const uint32_t lds0 = lds_addr_of(smem);
+  const uint32_t lds0 = lds_addr32(smem);
   // 8 * row_groups consecutive blocks = 8 pixel ranges x all filter-row groups; block b and b + 8 (same XCD) = the
   // same pixel range, next row group
   const int grp = blockIdx.x / (8 * a.row_groups), within = blockIdx.x - grp * (8 * a.row_groups);
