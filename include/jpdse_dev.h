@@ -15,24 +15,20 @@ extern "C" {
 
 /* Developer A/B switch (kernel SELECTION only: results stay correct under every code):
  * 0 = every convolution on the generic register-staged kernels; 1 (default) = all specialised bf16 kernels; 3 = no halo kernel;
- * 4 = no all-nine-taps weight gradient; 5 = heads without the Toeplitz GEMM; 6 = no split-K, no head kernel, no tap programs, no
- * persistent kernel (same summation order as the generic kernels: bit-comparable); 7 = reflect data gradient on the padded domain;
+ * 4 = no all-nine-taps weight gradient; 5 = heads without the Toeplitz GEMM; 6 = no split-K, no head kernel, no tap programs
+ * (same summation order as the generic kernels: bit-comparable); 7 = reflect data gradient on the padded domain;
  * 8 = halo kernel always double buffered; 9 / 10 = long-K-only phase merging / no 128-row tiles; 12 = no all-taps weight gradient;
  * 13 = no tap-sum forward; 14 = no head kernel; 15 / 16 = XCD-aware halo tile orders; 18 = no thin-input forward kernel;
- * 19 = halo kernel on 16x16x32 MFMA fragments; 26 = merged stride-phase data gradient only from 384 tiles on; 27 = InstanceNorm
- * always as three kernels; 28 = InstanceNorm as one kernel with the in-launch exchange; 29 = the 64-channel / thin-input layers on
+ * 26 = merged stride-phase data gradient only from 384 tiles on; 27 = InstanceNorm
+ * always as three kernels; 29 = the 64-channel / thin-input layers on
  * the halo / fast kernels instead of the row-streaming family; 32 = no InstanceNorm moments in conv epilogues; 35 = stride-2 data
  * gradients on the merged-phase fast kernel instead of the tap-program halo kernel (gemm_taps.h); 36 = 4x4 stride-1 layers on the
  * fast kernel alone; 38 = 3x3 layers with 32-pixel-wide grids on the split-K fast kernel instead of the nine-tap program;
  * 40 = reflect data gradient as halo kernel + four ring-strip GEMMs + ring_fold_kernel instead of the folded frame (gemm_halo.h
- * VIRT); 41 = the one-output-channel layers backward on the GEMM paths instead of thin_out1.h; 42 = 4x4 stride-2 data gradients on
- * the merged-phase fast kernel only; 43 = the same layers on the tap program + fringe (measured slower in the step);
- * 48 = fp32 generic kernel without split-K; 50 = the short-K layers on gemm_fast_kernel instead of the persistent form
- * (gemm_pers.h); 51 = every fast-kernel layer without split-K on the persistent form; 52 = the persistent form from one tile on
- * and for any K (tests); 55 = 32-pixel-wide 1024-channel weight gradients on the per-tap kernel
+ * VIRT); 41 = the one-output-channel layers backward on the GEMM paths instead of thin_out1.h;
+ * 48 = fp32 generic kernel without split-K; 55 = 32-pixel-wide 1024-channel weight gradients on the per-tap kernel
  * instead of the row-pair nine-tap form; 57 = the 32 -> 3 head forward on head_fwd_kernel instead of head_rows_kernel<7, 32>;
  * 58 = all-taps weight gradient (wgrad_taps.h) with the tiles of a pixel range co-located on one XCD (measured slower);
- * 61 = the short-K whole-round layers on the persistent form (gemm_pers.h), as shipped during round 4 before the epilogue fix (50 is the default again);
  * 60 = halo kernel without the XCD-aware tile order on its one-round grids (15 / 16 / 17 force an order on every grid);
  * 59 = the few-tile medium-K layers of the fast kernel on 256-row tiles as before round 4;
  * Any other code that is not retired selects the shipped dispatch, like 1.
@@ -47,6 +43,12 @@ extern "C" {
  * profiles/r01_ablation_resblock.txt, profiles/r04_virt_conflicts_ab.txt), 201-203 (timing-only ablations of the all-taps
  * weight-gradient loop: profiles/r04_wgrad_taps_ab.txt), 210-225 (timing-only ablations of gemm_fast_kernel's loader, loop and
  * epilogue: profiles/r04_fast_astage_ablation.txt, profiles/r04_epilogue_act_ab.txt).
+ * Retired in a second pass, each a complete kernel alternative that had lost its A/B (same rule: JPDSE_EINVAL):
+ * 19 (halo kernel on 16x16x32 MFMA fragments, the MF16 form of gemm_halo_kernel: 1020 vs 1032 TFLOP/s),
+ * 28 (InstanceNorm as one kernel with an in-launch exchange between workgroups: profiles/r02_norm_forms.txt),
+ * 42 / 43 (4x4 stride-2 data gradients off / on the tap program + fringe: profiles/r03_taps_dgrad4_ab.txt),
+ * 50 / 51 / 52 / 61 (the persistent form of the fast kernel, gemm_pers.h, and the label of the dispatch without it:
+ * profiles/r04_pers_v1_ab.txt, profiles/r04_pers_v2_ab.txt).
  * Each call resets the others to their defaults.
  * The kernel names above are prose; which kernel family a layer runs on under a mode is a ROUTE, and the routes' names come from
  * route_name() in jpd-se_amd/csrc/conv_route.h (jpdse_debug_conv_route / jpdse_debug_route_name below). */

@@ -41,7 +41,7 @@ template <typename T> static T* mptr(void* p) { return reinterpret_cast<T*>(p); 
 // (libjpdse_hip_dev.so, -DJPDSE_DEV; set through include/jpdse_dev.h).
 #ifdef JPDSE_DEV
 #define JPDSE_SWITCH(type, name, value) static type name = value
-extern int g_norm_fused;     // norm.hip: InstanceNorm form, 1 = two register-held kernels (default), 0 = three kernels (mode 27), 2 = one kernel (mode 28)
+extern int g_norm_fused;     // norm.hip: InstanceNorm form, 1 = two register-held kernels (default), 0 = three kernels (mode 27)
 #else
 #define JPDSE_SWITCH(type, name, value) static constexpr type name = value
 #endif

@@ -100,7 +100,6 @@ __device__ __forceinline__ float apply_act(float v, int act, float slope) {
 #include "head_fwd.h"
 #include "thin_fwd.h"
 #include "conv_rows.h"
-#include "gemm_pers.h"
 #include "dgrad2_rows.h"
 #include "head_rows.h"
 #include "thin_dgrad2_rows.h"
@@ -178,16 +177,14 @@ int jpdse_debug_set_fast_path(int32_t enable) {
   // 1 (any mode not named below): the shipped dispatch.  6 = fast kernels with the generic kernels' rounding points and summation
   // order (it switches several paths off at once).  Retired codes (include/jpdse_dev.h: their code paths are gone) are refused, so
   // that a sweep which still passes one does not measure the shipped dispatch under another label.
-  if (enable == 53 || enable == 54 || enable == 56 || (enable >= 100 && enable <= 199) || (enable >= 201 && enable <= 203) ||
-      (enable >= 210 && enable <= 225))
+  if (enable == 19 || enable == 28 || enable == 42 || enable == 43 || (enable >= 50 && enable <= 54) || enable == 56 || enable == 61 ||
+      (enable >= 100 && enable <= 199) || (enable >= 201 && enable <= 203) || (enable >= 210 && enable <= 225))
     return set_error(JPDSE_EINVAL, "debug_set_fast_path: mode %d is retired (its code path was removed; see include/jpdse_dev.h)", (int)enable);
   g_fast_enabled = enable != 0;                          // 0: generic kernels only
   g_halo_enabled = enable != 3;                          // 3: fast kernels but no halo kernel (with the rows and ring paths off as well)
   g_moments_fused = enable != 32 && enable != 6;         // 32: InstanceNorm moments always in their own pass; 6
   g_ring_virt = enable != 40 && enable != 6;             // 40: reflect ring as four split-K strip GEMMs + ring_fold_kernel instead of the folded frame; 6: every product in fp32 until the fold
   g_thin1_enabled = enable != 41 && enable != 6;         // 41: the one-output-channel layers (PatchGAN 512 -> 1) backward on the GEMM paths; 6
-  g_taps_dgrad4_enabled = enable != 42 && enable != 6;   // 42: 4x4 stride-2 data gradients (PatchGAN layers 1-2) on the merged-phase fast kernel; 6
-  g_taps_dgrad4_min_tiles = enable == 43 ? 1 : (1 << 30);   // 43: 4x4 stride-2 data gradients on the tap program + fringe at any size (slower in the step)
   g_taps9_enabled = enable != 38 && enable != 6;         // 38: 3x3 layers with 32-pixel-wide grids on the split-K fast kernel; 6
   g_taps4_enabled = enable != 36 && enable != 6;         // 36: 4x4 stride-1 layers on the fast kernel alone; 6
   g_taps_enabled = enable != 35 && enable != 6;          // 35: stride-2 data gradients on the merged-phase fast kernel instead of the tap-program kernel; 6: tap outer, slab inner
@@ -196,20 +193,16 @@ int jpdse_debug_set_fast_path(int32_t enable) {
   g_wgrad_taps_enabled = enable != 12;                   // 12: fast kernels without the all-taps weight gradient
   g_ring_enabled = enable != 7 && enable != 3;           // 7: reflect data gradient on the padded domain + fold; 3
   g_merge_min_kt = enable == 9 ? 16 : 4;                 // 9: merged stride-phase data gradient only for long K loops
-  g_norm_fused = enable == 27 ? 0 : (enable == 28 ? 2 : 1);   // 27: InstanceNorm always as three kernels; 28: one-kernel form with the in-launch exchange
+  g_norm_fused = enable != 27;                           // 27: InstanceNorm always as three kernels
   g_merge_min_tiles = enable == 26 ? 384 : 64;           // 26: merged stride-phase data gradient from 384 tiles on, as in round 1
   g_fast_small = enable == 10 ? 0 : 20;                  // 10: no 128-row / 2-stage configs for short K loops
   g_halo_xcd = enable == 15 ? 1 : (enable == 16 ? 2 : (enable == 17 ? 3 : 0));   // 15 / 16: XCD-aware tile orders of the halo kernel; 17: 4 N-tiles x 8 patches per XCD (one-round grids)
-  g_halo_mf16 = enable == 19;                            // 19: halo kernel on 16x16x32 MFMAs
   g_halo_single = enable != 8;                           // 8: halo kernel always with two patch buffers
   g_head_fwd_enabled = enable != 14 && enable != 6;      // 14: heads on the Toeplitz GEMM; 6
   g_thin_fwd_enabled = enable != 18;                     // 18: thin-input forward on the generic kernel
   g_tapsum_enabled = enable != 13;                       // 13: narrow-output layers without the tap-sum forward ...
   g_thin_out_fast = enable != 13;                        // 13: ... and the narrow-output long-K layers on the generic kernel
   g_toep_enabled = enable != 5;                          // 5: fast kernels, plain head forward
-  g_pers_enabled = enable == 51 || enable == 52 || enable == 61;   // 51 / 52 / 61: the persistent form (off by default) ...
-  g_pers_max_kt = (enable == 51 || enable == 52) ? (1 << 20) : 24;   // ... 51, 52: for any K; 61: up to 24 K-tiles, the round-4 rule
-  g_pers_min_tiles = enable == 52 ? 1 : 256;             // ... 52: from one tile on (tests); 51, 61: on whole-round grids of >= 256 tiles
   g_wgrad_nine32_enabled = enable != 55;                 // 55: the 1024-channel trunk at 16 x 32 on the per-tap weight-gradient kernel
   g_head_rows32 = enable != 57;                          // 57: the 32 -> 3 head forward on head_fwd_kernel
   g_halo_xcd_auto = enable != 60;                        // 60: halo kernel, block b -> tile b on every grid (no XCD-aware order on the one-round grids)

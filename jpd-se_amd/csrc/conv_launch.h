@@ -256,60 +256,6 @@ static int launch_fast_cfg(FastBatch& b, hipStream_t s) {
   return check_launch("gemm_fast_kernel");
 }
 
-// ---- persistent, cross-tile-pipelined form for the short-K layers (gemm_pers.h) -------------------------------------------
-// Off by default (g_pers_enabled, conv_route.h).
-JPDSE_SWITCH(int, g_pers_max_kt, 24);     // K-tile count up to which the persistent form is taken (51: every fast-kernel layer without split-K, A/B)
-static bool pers_ok(const FastBatch& b) {
-  if (!g_pers_enabled || b.n <= 0 || b.small_m) return false;
-  const int Ks = b.p[0].Ks;
-  long long tiles = 0;
-  for (int i = 0; i < b.n; ++i) {
-    const FastArgs& a = b.p[i];
-    const int kt = a.R * a.S * (a.Cs / 64);
-    if (a.splits > 1 || a.no_finish || a.mask != nullptr || a.addend != nullptr || a.bias != nullptr || a.act == JPDSE_ACT_TANH) return false;
-    if (a.Ks != Ks || a.Ks < 64 || a.Ks % 8 != 0 || a.Cs % 64 != 0 || kt < 4 || kt > g_pers_max_kt || a.M <= 0) return false;
-    // 32-bit output offsets in the per-wave epilogue
-    const long long n_img = (a.M + (long long)a.OH * a.OW - 1) / ((long long)a.OH * a.OW);
-    const long long last = a.out_base + (n_img - 1) * a.out_sn + (long long)(a.OH - 1) * a.out_sh + (long long)(a.OW - 1) * a.out_sw + a.Ks;
-    if (a.out_base < 0 || last >= (1LL << 31)) return false;
-    tiles += (long long)((a.M + 255) / 256) * ((a.Ks + (Ks > 64 ? 127 : 63)) / (Ks > 64 ? 128 : 64));
-  }
-  if (g_pers_min_tiles <= 1) return tiles >= 1 && tiles < (1LL << 30);       // developer mode 52 (tests)
-  // Measured per layer in one process (profiles/r04_pers_v2_ab.txt): +8-10 % where the 256-row tiles fill whole rounds of the
-  // 256 CUs (128 <-> 256 channels, 3x3 stride 2: 1024 tiles), -4 % on PatchGAN layer 1 (1037 tiles: a fifth round for 13 of
-  // them), -10 % on layer 2 (526 tiles: 2.05 rounds), neutral at 36 K-tiles.  So: whole rounds only (<= 3 % of idle slots), short loops.
-  const long long rounds = (tiles + 255) / 256;
-  return tiles >= g_pers_min_tiles && tiles < (1LL << 30) && (rounds * 256 - tiles) * 32 <= tiles;
-}
-
-template <int TN>
-static int launch_pers_cfg(FastBatch& b, hipStream_t s) {
-  constexpr int BN = 2 * TN * 32;
-  constexpr int lds = 3 * (256 + BN) * 128;
-  if (int rc = opt_in_lds<&gemm_pers_kernel<TN>>("gemm_pers", lds)) return rc;
-  static const int cus = [] {
-    int dev = 0, n = 0;
-    return (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-  }();
-  int total = 0;
-  for (int i = 0; i < b.n; ++i) {
-    const FastArgs& a = b.p[i];
-    if (a.Y == nullptr) return set_error(JPDSE_EINVAL, "gemm_pers: problem %d has no output buffer", i);
-    if ((a.x_sh ? a.x_sh : (long long)a.IW * a.Cs) * a.IH >= (1LL << 31))
-      return set_error(JPDSE_EINVAL, "gemm_pers: one image spans >= 2^31 elements (in-image offsets are 32-bit)");
-    b.first_tile[i] = total;
-    total += ((a.M + 255) / 256) * ((a.Ks + BN - 1) / BN);
-  }
-  for (int i = b.n; i < 5; ++i) b.first_tile[i] = total;
-  const int grid = total < cus ? total : cus;
-  hipLaunchKernelGGL((gemm_pers_kernel<TN>), dim3(grid), dim3(512), lds, s, b, total);
-  return check_launch("gemm_pers_kernel");
-}
-
-static int launch_pers(FastBatch& b, hipStream_t s) {
-  return b.p[0].Ks > 64 ? launch_pers_cfg<2>(b, s) : launch_pers_cfg<1>(b, s);
-}
-
 JPDSE_SWITCH(int, g_fast_small, 20);      // K-tile count up to which the 128-row / 2-stage fast configs are used
 JPDSE_SWITCH(int, g_fast_fill, 1);                // 59: no small tiles for the few-tile medium-K layers (A/B)
 static int launch_fast_batch(FastBatch& b, hipStream_t s) {
@@ -322,7 +268,6 @@ static int launch_fast_batch(FastBatch& b, hipStream_t s) {
   }
   for (int i = 0; i < b.n; ++i)
     if (b.n > 1 && !b.p[i].no_finish) b.p[i].splits = 1;
-  if (pers_ok(b)) return launch_pers(b, s);
   if (b.small_m) {
     if (Ks > 64) return launch_fast_cfg<2, 2, 2, 2, 2>(b, s);
     if (Ks > 32) return launch_fast_cfg<2, 2, 2, 1, 2>(b, s);
@@ -367,12 +312,12 @@ static int launch_fast(const FastArgs& a, hipStream_t s) {
   return launch_fast_batch(b, s);
 }
 
-template <int TN, bool SINGLE = false, bool MF16 = false, bool MOM = false, bool VIRT = false, bool NSUM = false>
+template <int TN, bool SINGLE = false, bool MOM = false, bool VIRT = false, bool NSUM = false>
 static int launch_halo_cfg_impl(const HaloArgs& a, hipStream_t s) {
   constexpr int BN = 2 * TN * 32;
   constexpr int UH = ((4 + 2) * (64 + 2) + 7) / 8;
   constexpr int lds = (SINGLE ? 1 : 2) * UH * 1024 + 3 * BN * 128;
-  if (int rc = opt_in_lds<&gemm_halo_kernel<4, TN, SINGLE, MF16, MOM, VIRT, NSUM>>("gemm_halo", lds)) return rc;
+  if (int rc = opt_in_lds<&gemm_halo_kernel<4, TN, SINGLE, MOM, VIRT, NSUM>>("gemm_halo", lds)) return rc;
   if (int rc = check_tile_grid("gemm_halo", a.N, a.OH, a.OW, 4, 64, a.Cs, (long long)a.N * a.IH * a.IW * a.Cs, (long long)a.N * a.OH * a.OW * a.Ks)) return rc;
   if (VIRT && (a.V == nullptr || a.py != 1 || a.px != 1 || a.IH != a.OH || a.IW != a.OW || a.OH < 8 || a.reflect || (a.Cs < 128) != SINGLE))
     return set_error(JPDSE_EINVAL, "gemm_halo: folded-frame form needs a frame, pad 1, equal grids, >= 8 rows");
@@ -385,7 +330,7 @@ static int launch_halo_cfg_impl(const HaloArgs& a, hipStream_t s) {
   const long long kdim = 9LL * a.Cs;
   const int M = a.N * a.OH * a.OW;
   const int pslot = prof_begin(s, a.Ks, kdim);
-  hipLaunchKernelGGL((gemm_halo_kernel<4, TN, SINGLE, MF16, MOM, VIRT, NSUM>), dim3(tiles), dim3(512), lds, s, a);
+  hipLaunchKernelGGL((gemm_halo_kernel<4, TN, SINGLE, MOM, VIRT, NSUM>), dim3(tiles), dim3(512), lds, s, a);
   prof_end(pslot, 0, 2.0 * (double)M * (double)a.Ks * (double)kdim, s);
   return check_launch("gemm_halo_kernel");
 }
@@ -396,7 +341,6 @@ JPDSE_SWITCH(int, g_halo_xcd, 0);
 // Measured (profiles/r04_halo_xcd_ab.txt): memory-side fetch 172 -> 103 MB per launch, time unchanged (1194-1199 TFLOP/s either way);
 // on multi-round and single-slab grids the same order costs 1-4 %, so it is not used there.  60: off (A/B).
 JPDSE_SWITCH(int, g_halo_xcd_auto, 1);
-JPDSE_SWITCH(int, g_halo_mf16, 0);     // measured: 1020 vs 1032 TFLOP/s on the ResnetBlock conv -- the kernel is not MFMA-clock bound
 template <int TN>
 static int launch_halo_cfg(const HaloArgs& a0, hipStream_t s) {
   HaloArgs a = a0;
@@ -409,21 +353,15 @@ static int launch_halo_cfg(const HaloArgs& a0, hipStream_t s) {
     if constexpr (TN == 2) {
       if (a.nsums != nullptr) {           // ... and the sums of the InstanceNorm backward that consumes its output
         if (a.Cs == 64) return set_error(JPDSE_EINVAL, "gemm_halo: norm-backward sums are built for the double-buffered form (>= 128 input channels)");
-        return launch_halo_cfg_impl<TN, false, false, false, true, true>(a, s);
+        return launch_halo_cfg_impl<TN, false, false, true, true>(a, s);
       }
     }
     if (a.nsums != nullptr) return set_error(JPDSE_EINVAL, "gemm_halo: norm-backward sums need the 128-channel tile");
-    if (a.Cs == 64) return launch_halo_cfg_impl<TN, true, false, false, true>(a, s);     // one slab: single patch buffer
-    return launch_halo_cfg_impl<TN, false, false, false, true>(a, s);
+    if (a.Cs == 64) return launch_halo_cfg_impl<TN, true, false, true>(a, s);     // one slab: single patch buffer
+    return launch_halo_cfg_impl<TN, false, false, true>(a, s);
   }
   // conv -> InstanceNorm with the moments in this kernel's epilogue (double-buffered form)
-  if (a.mom != nullptr) return launch_halo_cfg_impl<TN, false, false, true>(a, s);
-#ifdef JPDSE_DEV
-  if (g_halo_mf16) {
-    if (a.Cs == 64 && g_halo_single) return launch_halo_cfg_impl<TN, true, true>(a, s);
-    return launch_halo_cfg_impl<TN, false, true>(a, s);
-  }
-#endif
+  if (a.mom != nullptr) return launch_halo_cfg_impl<TN, false, true>(a, s);
   if (a.Cs == 64 && g_halo_single) return launch_halo_cfg_impl<TN, true>(a, s);   // one slab: single patch buffer
   return launch_halo_cfg_impl<TN, false>(a, s);
 }
@@ -572,17 +510,17 @@ static int launch_thin_in_rows(ThinInArgs a, hipStream_t s) {
   return JPDSE_OK;
 }
 
-// ---- tap-program halo kernel (gemm_taps.h) on the stride-2 data gradients: taps_dgrad2_geom (conv_route.h) says which, and how they split
-template <int TN, int T1A, int T0B, int T1B>
+// ---- tap-program halo kernel (gemm_taps.h) on the stride-2 data gradients: taps_dgrad2_geom (conv_route.h) says which
+template <int TN>
 static int launch_taps_dgrad2_cfg(const TapsArgs& a, int total, hipStream_t s) {
   constexpr int PH = 5, PW = 65;
   constexpr int lds = 2 * ((PH * PW + 7) / 8) * 1024 + 3 * (2 * TN * 32) * 128;
-  if (int rc = opt_in_lds<&gemm_taps_kernel<TN, 4, T1A, T0B, T1B, 1, PH, PW>>("gemm_taps", lds)) return rc;
+  if (int rc = opt_in_lds<&gemm_taps_kernel<TN, 4, 1, 2, 2, 1, PH, PW>>("gemm_taps", lds)) return rc;
   if (int rc = check_tile_grid("gemm_taps(stride-2 data gradient)", a.N, a.OH, a.OW, 4, 64, a.Cs, (long long)a.N * a.IH * a.IW * a.Cs,
                                4LL * a.N * a.OH * a.OW * a.Ks)) return rc;
   if (total != 2 * a.nblk0 || a.nblk0 != a.N * (a.OH / 4) * (a.OW / 64) * ((a.Ks + 2 * TN * 32 - 1) / (2 * TN * 32)))
     return set_error(JPDSE_EINVAL, "gemm_taps: %d blocks for a grid of 2 x %d", total, a.nblk0);
-  hipLaunchKernelGGL((gemm_taps_kernel<TN, 4, T1A, T0B, T1B, 1, PH, PW>), dim3(total), dim3(512), lds, s, a);
+  hipLaunchKernelGGL((gemm_taps_kernel<TN, 4, 1, 2, 2, 1, PH, PW>), dim3(total), dim3(512), lds, s, a);
   return check_launch("gemm_taps_kernel");
 }
 
@@ -610,7 +548,7 @@ static int launch_taps_dgrad2(const jpdse_conv_desc* d, const ConvPlan& p, const
   a.out_sh = 2LL * d->W * p.Cs;
   a.out_sw = 2LL * p.Cs;
   a.act = JPDSE_ACT_NONE;
-  // program 0 = {phase (0,0), phase (1,1)}, program 1 = {phase (0,1), phase (1,0)}: 4 + 1 and 2 + 2 taps (3x3), 4 + 4 twice (4x4)
+  // program 0 = {phase (0,0), phase (1,1)}, program 1 = {phase (0,1), phase (1,0)}: 4 + 1 and 2 + 2 taps
   const Phase* byq[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
   for (int i = 0; i < 4; ++i) byq[p.ph[i].qh][p.ph[i].qw] = &p.ph[i];
   const Phase* sets[2][2] = {{byq[0][0], byq[1][1]}, {byq[0][1], byq[1][0]}};
@@ -632,41 +570,7 @@ static int launch_taps_dgrad2(const jpdse_conv_desc* d, const ConvPlan& p, const
   }
   const int bn = p.Cs % 128 == 0 ? 128 : 64;
   a.nblk0 = d->N * (a.OH / 4) * (a.OW / 64) * ((p.Cs + bn - 1) / bn);
-  int rc;
-  if (geo.taps4) rc = bn == 128 ? launch_taps_dgrad2_cfg<2, 4, 4, 4>(a, 2 * a.nblk0, s) : launch_taps_dgrad2_cfg<1, 4, 4, 4>(a, 2 * a.nblk0, s);
-  else rc = bn == 128 ? launch_taps_dgrad2_cfg<2, 1, 2, 2>(a, 2 * a.nblk0, s) : launch_taps_dgrad2_cfg<1, 1, 2, 2>(a, 2 * a.nblk0, s);
-  if (rc != JPDSE_OK || geo.fringe == 0) return rc;
-  // fringe: per phase the sub-pixel rows [core_h, cnth) x all its columns, and the columns [core_w, cntw) x rows [0, core_h)
-  FastBatch fb = {};
-  auto flush = [&]() -> int {
-    if (fb.n == 0) return JPDSE_OK;
-    const int r = launch_fast_batch(fb, s);
-    fb = FastBatch{};
-    return r;
-  };
-  for (int i = 0; i < 4; ++i) {
-    const Phase& f = p.ph[i];
-    const int rect[2][4] = {{geo.core_h, 0, f.cnth - geo.core_h, f.cntw}, {0, geo.core_w, geo.core_h, f.cntw - geo.core_w}};   // j0, c0, rows, cols
-    for (int q = 0; q < 2; ++q) {
-      const int j0 = rect[q][0], c0 = rect[q][1], rows = rect[q][2], cols = rect[q][3];
-      if (rows <= 0 || cols <= 0) continue;
-      FastArgs g = to_fast(view_dgrad_phase(d, p, i, dy, pack, dx));      // the phase, cut down to the rectangle
-      g.M = d->N * rows * cols;
-      g.OH = rows;
-      g.OW = cols;
-      g.py -= j0;
-      g.px -= c0;
-      g.out_base += j0 * g.out_sh + c0 * g.out_sw;
-      g.mask = a.mask;
-      g.mask_slope = mask_slope;
-      g.addend = a.addend;
-      g.splits = 1;
-      fb.p[fb.n++] = g;
-      if (fb.n == 4)
-        if (int r = flush()) return r;
-    }
-  }
-  return flush();
+  return bn == 128 ? launch_taps_dgrad2_cfg<2>(a, 2 * a.nblk0, s) : launch_taps_dgrad2_cfg<1>(a, 2 * a.nblk0, s);
 }
 
 // ---- 4x4 stride-1 zero-padded convs and their (single-phase) data gradient on the tap-program kernel: PatchGAN layer 3 of

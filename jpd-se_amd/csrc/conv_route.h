@@ -37,8 +37,6 @@ JPDSE_SWITCH(int, g_thin_fwd_enabled, 1);
 JPDSE_SWITCH(int, g_head_fwd_enabled, 1);
 JPDSE_SWITCH(int, g_tapsum_enabled, 1);
 JPDSE_SWITCH(int, g_taps_enabled, 1);       // 35: stride-2 data gradients on the merged-phase fast kernel (A/B)
-JPDSE_SWITCH(int, g_taps_dgrad4_enabled, 1);     // 42: the 4x4 stride-2 data gradients on the merged-phase fast kernel (A/B)
-JPDSE_SWITCH(int, g_taps_dgrad4_min_tiles, 1 << 30);   // 43: take the path at any size (developer build: tests, A/B) -- the shipped build never does, see taps_dgrad2_geom
 JPDSE_SWITCH(int, g_taps4_enabled, 1);      // 36: the 4x4 stride-1 layers on the fast kernel alone (A/B)
 JPDSE_SWITCH(int, g_taps9_enabled, 1);      // 38: the 3x3 layers on 8 x 32 grids on the split-K fast kernel (A/B)
 JPDSE_SWITCH(int, g_ring_enabled, 1);
@@ -49,12 +47,6 @@ JPDSE_SWITCH(int, g_thin1_enabled, 1);      // 41: the one-output-channel layers
 JPDSE_SWITCH(int, g_wgrad_taps_enabled, 1);
 JPDSE_SWITCH(int, g_wgrad_nine_enabled, 1);
 JPDSE_SWITCH(int, g_wgrad_nine32_enabled, 1);    // 55: 32-pixel-wide images on the per-tap kernel, as before round 4 (A/B)
-// The persistent form of the fast kernel (gemm_pers.h, pers_ok in conv_launch.h).  Off since the end of round 4: with the epilogue staging fixed
-// (gemm_fast.h, acc_tile_to_lds) the fast kernel runs the two launches the persistent form was shipped for 5-7 % FASTER than it (697 vs 650,
-// 685 vs 640 TFLOP/s; step 24.93 vs 24.95 ms) -- its +8 % had been the lean epilogue it happened to have.
-// Developer modes 51 / 52 (tests) / 61 (the round-4 rule: whole-round grids, <= 24 K-tiles) still reach it.
-JPDSE_SWITCH(int, g_pers_enabled, 0);
-JPDSE_SWITCH(int, g_pers_min_tiles, 256);   // 52: from one tile on (tests: ragged tails and multi-problem launches at small sizes)
 
 // ---- the layer as the single-launch bf16 kernels see it: a conv over an N x IH x IW x Cin_s tensor into OH x OW x Ks_out -- the
 // forward of a layer, or one stride phase of its data gradient (a stride-1 conv over dy).  The shape predicates below read it;
@@ -169,7 +161,6 @@ static bool prefer_320(int M, int Ks) {
 // (measured: scripts/bench_conv.py, profiles/r01_conv_layers_*.log).
 static bool fast_pays(int M, int Ks, int k_tiles) {
   if (!g_fast_enabled) return false;
-  if (g_pers_min_tiles <= 1 && g_pers_enabled && k_tiles >= 4 && Ks >= 64) return true;   // developer mode 52 (tests): small problems reach the persistent form
   if (k_tiles < 8) return false;   // short reductions (stride-2 sub-pixel phases of 2x2 taps x 64 ch) do not fill the 3-stage ring
   if (Ks <= 32) {
     // measured: the generic 256x32 kernel beats the 8-wave 256x32 fast config on short reductions; with a long
@@ -207,46 +198,28 @@ static FwdRoute select_fwd(const jpdse_conv_desc* d, const ConvPlan& p, FwdWants
 }
 
 // ---- tap-program halo kernel (gemm_taps.h): all four sub-pixel phases of a stride-2 data gradient / ConvTranspose forward.
-// 3x3 (pad 1, even input): phases (0,0) 2x2 taps, (0,1) 2x1, (1,0) 1x2,
-// (1,1) 1x1 over the same dy pixels.  4x4 (pad 2: the PatchGAN layers 1-2, networks.py:430-436): 2x2 taps in every phase; their
-// inputs have 2^k + 1 rows / columns, so the phases differ by one row / column: the kernel covers the CORE every phase has
-// (a multiple of 4 x 64 sub-pixels), the one-row / one-column FRINGE of the longer phases runs as sub-rectangle problems of the
-// fast kernel behind it (fused operands in its epilogue).
-struct TapsDgrad2Geom { int core_h, core_w, fringe, taps4; };
+// 3x3 (pad 1, even input): phases (0,0) 2x2 taps, (0,1) 2x1, (1,0) 1x2, (1,1) 1x1 over the same dy pixels; every phase covers
+// the same core_h x core_w sub-pixels, a multiple of the kernel's 4 x 64 patch.
+// (The 4x4 pad-2 layers of the PatchGAN on this kernel plus a fringe on the fast kernel, developer modes 42 / 43, lost to the
+// merged-phase fast kernel inside the step and were retired: profiles/r03_taps_dgrad4_ab.txt)
+struct TapsDgrad2Geom { int core_h, core_w; };
 static bool taps_dgrad2_geom(const jpdse_conv_desc* d, const ConvPlan& p, bool mom, TapsDgrad2Geom* g) {
   if (!(g_fast_enabled && g_taps_enabled) || d->dtype != JPDSE_BF16 || d->pad_mode == JPDSE_PAD_REFLECT) return false;
-  const bool k3 = d->R == 3 && d->S == 3 && d->pad == 1, k4 = d->R == 4 && d->S == 4 && d->pad == 2 && g_taps_dgrad4_enabled;
-  if (d->stride != 2 || !(k3 || k4) || p.nph != 4) return false;
+  if (d->stride != 2 || d->R != 3 || d->S != 3 || d->pad != 1 || p.nph != 4) return false;
   if (mom) return false;
   if (p.Ks % 64 != 0 || p.Ks < 128 || p.Cs % 64 != 0) return false;
   // the kernel's loaders carry 32-bit element offsets into dy and into each phase's panel
   if ((long long)d->N * p.OH * p.OW * p.Ks >= (1LL << 31) || (long long)p.Cs * 4 * p.Ks >= (1LL << 31)) return false;
-  int min_h = 1 << 30, min_w = 1 << 30, fringe = 0;
+  const int core_h = p.ph[0].cnth, core_w = p.ph[0].cntw;
+  if (core_h < 4 || core_h % 4 != 0 || core_w < 64 || core_w % 64 != 0) return false;
   for (int i = 0; i < 4; ++i) {
     const Phase& f = p.ph[i];
     if (f.Lk != f.Uw * p.Ks) return false;
-    if (k3 && (f.Uh != (f.qh == 0 ? 2 : 1) || f.Uw != (f.qw == 0 ? 2 : 1))) return false;
-    if (k4 && (f.Uh != 2 || f.Uw != 2)) return false;
+    if (f.Uh != (f.qh == 0 ? 2 : 1) || f.Uw != (f.qw == 0 ? 2 : 1)) return false;
     if ((f.Uh - 1) - f.i0h != 0 || (f.Uw - 1) - f.i0w != 0) return false;      // every phase starts at dy pixel (oh, ow)
-    min_h = f.cnth < min_h ? f.cnth : min_h;
-    min_w = f.cntw < min_w ? f.cntw : min_w;
+    if (f.cnth != core_h || f.cntw != core_w) return false;                    // the generator's layers have even inputs: no fringe
   }
-  const int core_h = min_h / 4 * 4, core_w = min_w / 64 * 64;
-  if (core_h < 4 || core_w < 64) return false;
-  for (int i = 0; i < 4; ++i) {
-    const Phase& f = p.ph[i];
-    if (f.cnth > core_h) ++fringe;
-    if (f.cntw > core_w) ++fringe;
-  }
-  if (k3 && fringe != 0) return false;              // the 3x3 layers of the generator have even inputs: no fringe path needed
-  // 4x4: measured against the merged-phase fast kernel (profiles/r03_taps_dgrad4_ab.txt).  Bare data gradient, one process:
-  // +14 % with 1024 core tiles per program (layer 1 at 257 x 513), +5 % with 256 (layer 2), -9 ... -31 % on the second scale.
-  // In the step, where the LeakyReLU mask and the feature-matching addend ride in the epilogue, layer 1 was SLOWER
-  // (0.195 + 0.130 ms vs 0.186 + 0.116 ms for the two launches): with one block per CU the operand loads of the two epilogues
-  // are exposed, the fast kernel overlaps them across its three co-resident blocks.  These K = 512 ... 1024 loops are
-  // prologue / epilogue bound on either kernel; the path stays in the developer build only.
-  if (k4 && (long long)d->N * (core_h / 4) * (core_w / 64) * ((p.Cs + 127) / 128) < g_taps_dgrad4_min_tiles) return false;
-  if (g != nullptr) *g = {core_h, core_w, fringe, k4 ? 1 : 0};
+  if (g != nullptr) *g = {core_h, core_w};
   return true;
 }
 static bool taps_dgrad2_ok(const jpdse_conv_desc* d, const ConvPlan& p, bool mom) { return taps_dgrad2_geom(d, p, mom, nullptr); }

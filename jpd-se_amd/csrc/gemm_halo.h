@@ -15,7 +15,6 @@
 #pragma once
 #include "common.h"
 #include "gemm_fast.h"
-#include <type_traits>
 
 namespace jpdse {
 
@@ -52,9 +51,6 @@ struct HaloArgs {
 // SINGLE: one patch buffer instead of two -- for 64-channel inputs (one slab per tile, nothing to prefetch).
 // With the 64-wide N tile the block then needs 74 KiB of LDS and TWO blocks share a CU, overlapping one
 // block's patch load / epilogue with the other's MFMAs (these K = 576 layers are prologue-bound).
-// MF16: v_mfma_f32_16x16x32_bf16 instead of 32x32x16 -- same LDS bytes and MFMA cycles per FLOP, but the chip holds
-// a higher clock on it (MI355X_MICROARCH.md, DVFS item 7).  The fragment rows are then 16 pixels x 4 k-chunks, which
-// needs the swizzle chunk ^ (row & 6) instead of chunk ^ ((row >> 1) & 7) to stay conflict-free at any tap shift.
 // VIRT: the data gradient of a REFLECT-padded 3x3 conv in one launch.  The adjoint of the padding adds the padded-domain
 // gradient of row -1 into row 1, of row H into row H-2 (columns alike).  Row -1 of that gradient is the u = 2 taps applied to dy
 // row 0 -- the same taps that output row 1 applies to dy row 2 -- so output row 1 reads, for those taps only, the FRAME row
@@ -63,7 +59,7 @@ struct HaloArgs {
 // that hold the zero padding otherwise; the reads that must still see that padding (output row 0 at u = 0, ...) go to a zero
 // pixel in the slack of the patch buffer.  Costs an add and a min per fragment address and tap; replaces the four ring-strip
 // GEMMs + ring_fold_kernel.  Needs py = px = 1, IH = OH, IW = OW, OH >= 8.
-template <int TH, int TN, bool SINGLE = false, bool MF16 = false, bool MOM = false, bool VIRT = false, bool NSUM = false>
+template <int TH, int TN, bool SINGLE = false, bool MOM = false, bool VIRT = false, bool NSUM = false>
 __global__ __launch_bounds__(512) void gemm_halo_kernel(const HaloArgs a) {
   constexpr int R = 3, S = 3, TAPS = 9;
   constexpr int NW = 8, WN = 2;                       // waves: TH (=4) x 2
@@ -77,7 +73,7 @@ __global__ __launch_bounds__(512) void gemm_halo_kernel(const HaloArgs a) {
   constexpr int HU = (UH + NW - 1) / NW;              // patch units per wave (7 for 50 units / 8 waves)
   static_assert(HU <= TAPS - 2, "patch units of the next slab are spread over taps 0..HU-1");
   constexpr int PZ = UH * 8 - 1;                      // VIRT: the last slack pixel of a patch buffer is kept zero
-  static_assert(!VIRT || (PZ - 1 >= NP && (PZ & 1) == 1 && !MF16 && !MOM), "VIRT needs two slack pixels (even, odd); written for the plain 32x32 form");
+  static_assert(!VIRT || (PZ - 1 >= NP && (PZ & 1) == 1 && !MOM), "VIRT needs two slack pixels (even, odd); written for the plain form");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* const halo0 = smem;
   constexpr int NBUF = SINGLE ? 1 : 2;
@@ -131,7 +127,7 @@ __global__ __launch_bounds__(512) void gemm_halo_kernel(const HaloArgs a) {
     const int row = uu * 8 + lrow;
     int br = n0 + row;
     br = br < a.b_rows ? br : a.b_rows - 1;
-    b_ptr[j] = a.B + (long long)br * ktot + (MF16 ? (lslot ^ (row & 6)) : ((lslot ^ (row >> 1)) & 7)) * 8;
+    b_ptr[j] = a.B + (long long)br * ktot + ((lslot ^ (row >> 1)) & 7) * 8;
     b_lds[j] = uu * 1024;
   }
   // Prologue order (round 4): weight tile 0 goes on the wire FIRST, each patch unit of slab 0 as soon as its address is known, weight
@@ -164,7 +160,7 @@ __global__ __launch_bounds__(512) void gemm_halo_kernel(const HaloArgs a) {
     } else {
       ok = ((unsigned)ih < (unsigned)a.IH) & ((unsigned)iw < (unsigned)a.IW);
     }
-    const int chunk = MF16 ? (lslot ^ (swz_p & 6)) : ((lslot ^ (swz_p >> 1)) & 7);
+    const int chunk = (lslot ^ (swz_p >> 1)) & 7;
     h_off[i] = ok ? (((long long)n * a.IH + ih) * a.IW + iw) * a.Cs + chunk * 8 : -1;
     if constexpr (VIRT) {
       // padding pixels come from the frame: rows [2][IW + 2] (column index iw + 1), then columns [2][IH]; slack pixels are zeros
@@ -202,9 +198,9 @@ __global__ __launch_bounds__(512) void gemm_halo_kernel(const HaloArgs a) {
   for (int j = 0; j < BU; ++j) n_b += b_on[j] ? 1 : 0;
 
   // ---- fragment addressing
-  constexpr int FM = MF16 ? 4 : 2, FN = MF16 ? 2 * TN : TN;   // fragment blocks per wave tile (64 px x TN*32 channels)
-  constexpr int FR = MF16 ? 16 : 32;                            // rows per fragment block
-  constexpr int KS = MF16 ? 2 : 4;                              // k-steps per 64-channel tile
+  constexpr int FM = 2, FN = TN;                      // 32x32 fragment blocks per wave tile (64 px x TN*32 channels)
+  constexpr int FR = 32;                              // rows per fragment block
+  constexpr int KS = 4;                               // k-steps per 64-channel tile
   int pb[FM];                                         // patch pixel of this lane's row for tap (0,0), per row block
 #pragma unroll
   for (int i = 0; i < FM; ++i) pb[i] = wm * PW + i * FR + (lane & (FR - 1));
@@ -222,24 +218,23 @@ __global__ __launch_bounds__(512) void gemm_halo_kernel(const HaloArgs a) {
       vc2[i] = (right && w == 63) ? 1000 : ((left && w == 1) ? (right ? 65 : 0) : w + 2);
     }
   }
-  const int hsel = MF16 ? (lane >> 4) : (lane >> 5);  // k-chunk of this lane inside a k-step
+  const int hsel = lane >> 5;                          // k-chunk of this lane inside a k-step
   int b_rd[FN][KS];
 #pragma unroll
   for (int j = 0; j < FN; ++j) {
     const int row = wn * TN * 32 + j * FR + (lane & (FR - 1));
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks)
-      b_rd[j][ks] = MF16 ? (row << 7) + (((4 * ks + hsel) ^ (row & 6)) << 4) : swz128(row, 2 * ks + hsel);
+      b_rd[j][ks] = swz128(row, 2 * ks + hsel);
   }
 
-  typedef typename std::conditional<MF16, f32x4, f32x16>::type acc_t;
-  acc_t acc[FM][FN];
+  f32x16 acc[FM][FN];
 #pragma unroll
   for (int i = 0; i < FM; ++i)
 #pragma unroll
     for (int j = 0; j < FN; ++j)
 #pragma unroll
-      for (int e = 0; e < (MF16 ? 4 : 16); ++e) acc[i][j][e] = 0.f;
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
   const int CC = a.Cs >> 6;
   const int T_total = CC * TAPS;
@@ -318,7 +313,7 @@ __global__ __launch_bounds__(512) void gemm_halo_kernel(const HaloArgs a) {
         pt = ptv < PZ ? ptv : PZ - 1 + (pt & 1);      // two zero pixels (PZ - 1 even, PZ odd): the parity of the un-redirected pixel
       }
       a_base[i] = pt << 7;
-      a_sw[i] = MF16 ? (psw & 6) << 4 : ((psw >> 1) & 7) << 4;
+      a_sw[i] = ((psw >> 1) & 7) << 4;
     }
     issue_group();
     __builtin_amdgcn_s_setprio(1);
@@ -327,16 +322,13 @@ __global__ __launch_bounds__(512) void gemm_halo_kernel(const HaloArgs a) {
       s16x8 af[FM], bf[FN];
 #pragma unroll
       for (int i = 0; i < FM; ++i)
-        af[i] = *reinterpret_cast<const s16x8*>(hb + a_base[i] + ((((MF16 ? 4 : 2) * ks + hsel) << 4) ^ a_sw[i]));
+        af[i] = *reinterpret_cast<const s16x8*>(hb + a_base[i] + (((2 * ks + hsel) << 4) ^ a_sw[i]));
 #pragma unroll
       for (int j = 0; j < FN; ++j) bf[j] = *reinterpret_cast<const s16x8*>(st + b_rd[j][ks]);
 #pragma unroll
       for (int i = 0; i < FM; ++i)
 #pragma unroll
-        for (int j = 0; j < FN; ++j) {
-          if constexpr (MF16) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bf[j], acc[i][j], 0, 0, 0);
-          else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bf[j], acc[i][j], 0, 0, 0);
-        }
+        for (int j = 0; j < FN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bf[j], acc[i][j], 0, 0, 0);
     }
     __builtin_amdgcn_s_setprio(0);
   };
@@ -360,8 +352,7 @@ __global__ __launch_bounds__(512) void gemm_halo_kernel(const HaloArgs a) {
   // ---- optional moments of the block's 4 x 64 pixels per channel for the InstanceNorm that follows (ResnetBlock convs):
   // (mean, M2) of the bf16-rounded values about a per-lane pilot, lane halves merged, then the four row-waves through LDS
   // with Chan's formula in a fixed order (common.h) -- the norm's own moment kernel (a launch per norm) is not needed
-  if constexpr (MOM && !MF16) {
-    static_assert(FM == 2, "moments are written for the 32x32 accumulator layout");
+  if constexpr (MOM) {
     __syncthreads();                                    // the pipeline LDS is dead
     float* const red = reinterpret_cast<float*>(smem);  // [TH][BN][2]
 #pragma unroll
@@ -408,8 +399,7 @@ __global__ __launch_bounds__(512) void gemm_halo_kernel(const HaloArgs a) {
   __syncthreads();
   constexpr int PITCH = BN * 2 + 64;
   static_assert(TH * 64 * PITCH <= NBUF * HALO + 3 * B_STAGE, "epilogue tile fits the pipeline LDS");
-  if constexpr (MF16) acc16_tile_to_lds<FM, FN>(smem, PITCH, wm * 64, wn * TN * 32, n0, lane, acc, a.bias, a.Kout, a.act, a.slope);
-  else acc_tile_to_lds<2, TN>(smem, PITCH, wm * 64, wn * TN * 32, n0, lane, acc, a.bias, a.Kout, a.act, a.slope);
+  acc_tile_to_lds<2, TN>(smem, PITCH, wm * 64, wn * TN * 32, n0, lane, acc, a.bias, a.Kout, a.act, a.slope);
   __syncthreads();
   const long long blk_base = a.out_base + n * a.out_sn + (long long)oh0 * a.out_sh + (long long)ow0 * a.out_sw;
   constexpr int VPR = BN / 8;
@@ -423,7 +413,7 @@ __global__ __launch_bounds__(512) void gemm_halo_kernel(const HaloArgs a) {
     // thread's vectors all lie in ONE 8-channel column (512 % VPR == 0), so its sums stay in registers over its NV pixels; the
     // four lanes of a wave that share a column are merged by two xor shuffles, the eight waves through LDS in wave order
     // (fixed order: deterministic), one slot per block and channel.
-    static_assert(512 % VPR == 0 && !MF16 && !SINGLE, "one channel column per thread");
+    static_assert(512 % VPR == 0 && !SINGLE, "one channel column per thread");
     constexpr int NRED_OFF = TH * 64 * PITCH;
     static_assert(NRED_OFF + NW * BN * 2 * 4 <= NBUF * HALO + 3 * B_STAGE, "the reduction rows fit behind the epilogue tile");
     const int v = tid % VPR;

@@ -2,12 +2,12 @@
 // set) to the layers that were left on the tap-re-staging gemm_fast_kernel:
 //
 //   * the data gradient of a stride-2 conv / the forward of a ConvTranspose2d (networks.py:215,244): the four sub-pixel
-//     phases of dx are four stride-1 convs over the SAME dy pixels with 4 + 2 + 2 + 1 taps (3x3) or 4 x 4 taps (4x4).
+//     phases of dx are four stride-1 convs over the SAME dy pixels with 4 + 2 + 2 + 1 taps (3x3).
 //     gemm_fast ran them as four independent problems: every phase re-stages dy once per tap (9 activation tiles of 32 KiB
 //     per 64-channel slab and 256 dy pixels) and the short K loops (1 .. 4 taps) are prologue / epilogue bound.  Here a block
 //     stages the (TH+1) x (TW+1) dy patch ONCE per slab and runs a program of taps over it, each tap feeding ONE OF TWO
 //     accumulator sets (= two phases): {phase (0,0): 4 taps, phase (1,1): 1 tap} and {phase (0,1): 2, phase (1,0): 2} are the
-//     two programs of a 3x3 layer, launched together (block-uniform branch); 4x4 stride 2: {4, 4} twice.
+//     two programs of a 3x3 layer, launched together (block-uniform branch).
 //   * 4x4 stride-1 convs (PatchGAN layer 3, networks.py:430-449) and their data gradient: one set, 16 taps, the patch
 //     staged once per slab instead of 16 activation tiles.
 //

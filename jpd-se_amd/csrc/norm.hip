@@ -8,13 +8,9 @@
 //   * three kernels (larger tensors; developer mode 27 everywhere): (1) a moment kernel in which each thread owns one 16-byte
 //     channel vector column and walks pixels (coalesced: a pixel's channels are contiguous), partial sums per pixel split
 //     written to the workspace; (2) a tiny finalize kernel (deterministic order, no atomics); (3) a fully parallel apply kernel;
-//   * one register-held kernel with an in-launch exchange (PHASE 0; developer mode 28 only);
 //   * statistics from the slots a conv epilogue wrote (jpdse_inorm_fwd_from_moments / _bwd_from_sums): one register-held
 //     kernel that merges the slots itself (PHASE 3), or a slot finalize kernel + the apply kernel of the three-kernel form.
 #include "common.h"
-#include <map>
-#include <mutex>
-#include <utility>
 
 namespace jpdse {
 
@@ -368,19 +364,17 @@ __global__ __launch_bounds__(256) void inorm_apply_bwd_kernel(const T* __restric
 
 
 // ---- register-held forms ------------------------------------------------------------------
-// Geometry shared by the two forms below: a block owns `span` = TY * P pixels of TX 16-byte channel columns of one image and
-// holds them in registers; the `splits` blocks of one (image, channel block) = one GROUP are consecutive in the grid.
+// Geometry: a block owns `span` = TY * P pixels of TX 16-byte channel columns of one image and holds them in registers; the
+// `splits` blocks of one (image, channel block) = one GROUP are consecutive in the grid.
 //   TWO kernels (default, any tensor with <= 64 splits): PHASE 1 writes one row of partial sums per block, PHASE 2 loads
 //     its pixels, sums the group's rows itself (split order: deterministic; the rows are L2 hits and load under the
 //     pixel loads), and applies.  Against moment -> finalize -> apply this drops a launch and the finalize round trip.
-//   ONE kernel (PHASE 0; developer A/B mode 28, tensors that fit a resident grid): the blocks of a group exchange their rows
-//     inside the launch -- `sc1` stores and loads for every handed-off byte, one agent-scope add per storing workgroup
-//     behind that workgroup's vmcnt(0) + barrier (MI355X_MICROARCH.md, "inter-workgroup visibility") -- and x / dy are
-//     read once.  Measured on the ResnetBlock tensor (16.8 MB): each cross-XCD hop of the exchange costs ~2 us, which
-//     eats what the saved launch and re-read give (profiles/r02_norm_forms.txt), so it is not the shipped form.
+//   (ONE kernel whose blocks exchanged their rows inside the launch -- PHASE 0, developer mode 28 -- is retired: each
+//     cross-XCD hop of the exchange cost ~2 us, which ate what the saved launch and re-read gave, profiles/r02_norm_forms.txt;
+//     and it was the only place where workgroups waited on other workgroups of their own launch.)
 static inline int norm_form() {
 #ifdef JPDSE_DEV
-  return g_norm_fused;     // 1 = two kernels (shipped default), 0 = moment -> finalize -> apply, 2 = one kernel
+  return g_norm_fused;     // 1 = two kernels (shipped default), 0 = moment -> finalize -> apply
 #else
   return 1;
 #endif
@@ -411,10 +405,6 @@ static FusedGeom fused_geom(int N, int HW, int Cs, int VE, int P) {
   return g;
 }
 
-__device__ __forceinline__ void st_sc1(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ float ld_sc1(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ unsigned ld_sc1(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
 // Sum over the block's TY pixel rows: value j (< nv) of the block's partial row, returned in thread j.
 template <int VE>
 __device__ __forceinline__ float block_row(float* red, const float (&s1)[8], const float (&s2)[8], const FusedGeom& g) {
@@ -433,8 +423,7 @@ __device__ __forceinline__ float block_row(float* red, const float (&s1)[8], con
   return tsum;
 }
 
-// Sum of the group's rows in split order (sixteen loads in flight, added in order); COHERENT: rows written inside this launch.
-template <bool COHERENT>
+// Sum of the group's rows in split order (sixteen loads in flight, added in order).
 __device__ __forceinline__ float sum_rows(const float* rows, int splits, int nv) {
   float total = 0.f;
   for (int s0 = 0; s0 < splits; s0 += 16) {
@@ -443,7 +432,7 @@ __device__ __forceinline__ float sum_rows(const float* rows, int splits, int nv)
     for (int k = 0; k < 16; ++k) {
       const float* q = rows + (long long)(s0 + k) * nv;
       v[k] = 0.f;
-      if (s0 + k < splits) v[k] = COHERENT ? ld_sc1(q) : *q;
+      if (s0 + k < splits) v[k] = *q;
     }
 #pragma unroll
     for (int k = 0; k < 16; ++k) total += v[k];       // + 0.f for the absent rows changes nothing
@@ -455,35 +444,7 @@ __device__ __forceinline__ float sum_rows(const float* rows, int splits, int nv)
 __device__ __forceinline__ void group_totals(float* red, const float* partial, int grp, const FusedGeom& g) {
   const int tid = threadIdx.x;
   const float* rows = partial + (long long)grp * g.splits * g.nv;
-  const float total = tid < g.nv ? sum_rows<false>(rows + tid, g.splits, g.nv) : 0.f;
-  if (tid < g.nv) red[tid] = total;
-  __syncthreads();
-}
-
-// PHASE 0: on return red[j] holds the group total of value j.  `count`: one zeroed word per group, used once.
-template <int VE>
-__device__ __forceinline__ void exchange_totals(float* red, int* s_ctl, float tsum, float* partial, unsigned* count, int grp,
-                                                int split, const FusedGeom& g) {
-  const int tid = threadIdx.x;
-  float total = tsum;
-  if (g.splits > 1) {
-    float* const rows = partial + (long long)grp * g.splits * g.nv;
-    if (tid < g.nv) st_sc1(rows + (long long)split * g.nv + tid, tsum);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-      __hip_atomic_fetch_add(count + grp, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      unsigned it = 0;
-      int gave_up = 0;
-      while (ld_sc1(count + grp) < (unsigned)g.splits) {
-        __builtin_amdgcn_s_sleep(2);
-        if (++it > (1u << 22)) { gave_up = 1; break; }   // every wave reaches an exit; the result is then NaN (loud)
-      }
-      s_ctl[0] = gave_up;
-    }
-    __syncthreads();
-    if (tid < g.nv) total = s_ctl[0] ? __builtin_nanf("") : sum_rows<true>(rows + tid, g.splits, g.nv);
-  }
+  const float total = tid < g.nv ? sum_rows(rows + tid, g.splits, g.nv) : 0.f;
   if (tid < g.nv) red[tid] = total;
   __syncthreads();
 }
@@ -491,13 +452,15 @@ __device__ __forceinline__ void exchange_totals(float* red, int* s_ctl, float ts
 template <typename T, int P, int PHASE>
 __global__ __launch_bounds__(256, 4) void inorm_reg_fwd_kernel(const T* __restrict__ x, const T* __restrict__ res,
                                                              T* __restrict__ y, float* __restrict__ stats, float* partial,
-                                                             unsigned* count, int act, float slope, float eps, FusedGeom g,
+                                                             unsigned* unused, int act, float slope, float eps, FusedGeom g,
                                                              int mslots = 0) {
+  // PHASE 1: rows of partial sums; PHASE 2: apply from the group's rows.  (`unused`: the count words of the retired PHASE 0;
+  // the slot keeps the argument layout, hence the code, of the kernels as they are.)
+  static_assert(PHASE >= 1 && PHASE <= 3, "PHASE 0 (in-launch exchange) is retired");
   // PHASE 3: statistics from the per-block (mean, M2) slots a conv epilogue wrote (`partial` = moments[n][c][mslots][2],
   // common.h): one kernel per norm -- each block merges the slots of its channels itself (Chan's formula, slot order) and applies
   constexpr int VE = Vec16<T>::N;
   __shared__ float red[256 * VE * 2];
-  __shared__ int s_ctl[2];
   const int tid = threadIdx.x;
   const int tx = tid & (g.TX - 1), ty = tid >> g.tx_shift;
   const int split = blockIdx.x % g.splits, grp = blockIdx.x / g.splits;
@@ -564,12 +527,8 @@ __global__ __launch_bounds__(256, 4) void inorm_reg_fwd_kernel(const T* __restri
       }
     }
     const float tsum = block_row<VE>(red, s1, s2, g);
-    if constexpr (PHASE == 1) {
-      if (tid < g.nv) partial[((long long)grp * g.splits + split) * g.nv + tid] = tsum;
-      return;
-    } else {
-      exchange_totals<VE>(red, s_ctl, tsum, partial, count, grp, split, g);
-    }
+    if (tid < g.nv) partial[((long long)grp * g.splits + split) * g.nv + tid] = tsum;
+    return;
   }
   float mean[VE], rstd[VE];
   const float inv = 1.f / (float)g.HW;
@@ -614,14 +573,14 @@ template <typename T, int P, int PHASE>
 __global__ __launch_bounds__(256, (P == 8 ? 3 : 2)) void inorm_reg_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dy,
                                                                              T* __restrict__ dx,
                                                                              const float* __restrict__ stats, float* partial,
-                                                                             unsigned* count, int act, float slope,
+                                                                             unsigned* unused, int act, float slope,
                                                                              FusedGeom g, int mslots = 0) {
+  static_assert(PHASE >= 1 && PHASE <= 3, "PHASE 0 (in-launch exchange) is retired");
   // PHASE 3 (round 4): the two sums come from the per-block slots that the epilogue of the data-gradient kernel producing dy
   // wrote (`partial` = sums[n][c][mslots][2], gemm_halo.h NSUM): ONE kernel per norm backward -- each block adds the slots of
   // its channels itself (slot order: deterministic) and applies
   constexpr int VE = Vec16<T>::N;
   __shared__ float red[256 * VE * 2];
-  __shared__ int s_ctl[2];
   const int tid = threadIdx.x;
   const int tx = tid & (g.TX - 1), ty = tid >> g.tx_shift;
   const int split = blockIdx.x % g.splits, grp = blockIdx.x / g.splits;
@@ -685,12 +644,8 @@ __global__ __launch_bounds__(256, (P == 8 ? 3 : 2)) void inorm_reg_bwd_kernel(co
       }
     }
     const float tsum = block_row<VE>(red, s1, s2, g);
-    if constexpr (PHASE == 1) {
-      if (tid < g.nv) partial[((long long)grp * g.splits + split) * g.nv + tid] = tsum;
-      return;
-    } else {
-      exchange_totals<VE>(red, s_ctl, tsum, partial, count, grp, split, g);
-    }
+    if (tid < g.nv) partial[((long long)grp * g.splits + split) * g.nv + tid] = tsum;
+    return;
   }
   float m1[VE], m2[VE];
   const float inv = 1.f / (float)g.HW;
@@ -717,75 +672,18 @@ __global__ __launch_bounds__(256, (P == 8 ? 3 : 2)) void inorm_reg_bwd_kernel(co
   }
 }
 
-// One-kernel form only: zeroed count words, each used by one group of one launch; a (device, stream) ring that a
-// stream-ordered memset refills when it runs out (every ~2000 launches).
-constexpr int kCountSlots = 1 << 16;
-struct SyncState { unsigned* dev = nullptr; int cursor = 0; };
-static unsigned* count_slots(hipStream_t s, int groups) {
-#ifndef JPDSE_DEV
-  (void)s; (void)groups;
-  return nullptr;            // the shipped library never allocates: the one-kernel form exists in the developer build only
-#else
-  static std::mutex mu;
-  static std::map<std::pair<int, hipStream_t>, SyncState> table;
-  int dev = 0;
-  if (groups > kCountSlots || hipGetDevice(&dev) != hipSuccess) return nullptr;
-  std::lock_guard<std::mutex> lock(mu);
-  SyncState& st = table[std::make_pair(dev, s)];
-  if (st.dev == nullptr) {
-    if (hipMalloc(reinterpret_cast<void**>(&st.dev), kCountSlots * sizeof(unsigned)) != hipSuccess) return nullptr;
-    st.cursor = kCountSlots;     // forces the first fill
-  }
-  if (st.cursor + groups > kCountSlots) {
-    if (hipMemsetAsync(st.dev, 0, kCountSlots * sizeof(unsigned), s) != hipSuccess) return nullptr;
-    st.cursor = 0;
-  }
-  unsigned* p = st.dev + st.cursor;
-  st.cursor += groups;
-  return p;
-#endif
-}
-
-// blocks of `kernel` that are resident at once (the exchange must never wait for a block that cannot start)
-template <typename K> static int resident_blocks(K kernel) {
-  int occ = 0, cus = 0, dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, 256, 0) != hipSuccess) return 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-  return occ * cus;
-}
-
-// Pixels held per thread for the register-held forms (0: moment -> finalize -> apply).  `one`: the one-kernel form is wanted.
-template <typename T, bool BWD> static int reg_pick(const jpdse_inorm_desc* d, bool one, FusedGeom* out) {
-  constexpr int VE = Vec16<T>::N;
-  static int cap8 = -1, cap16 = -1;
-#ifdef JPDSE_DEV
-  if (one && cap8 < 0) {
-    if (BWD) {
-      cap8 = resident_blocks(inorm_reg_bwd_kernel<T, 8, 0>);
-      cap16 = resident_blocks(inorm_reg_bwd_kernel<T, 16, 0>);
-    } else {
-      cap8 = resident_blocks(inorm_reg_fwd_kernel<T, 8, 0>);
-      cap16 = resident_blocks(inorm_reg_fwd_kernel<T, 16, 0>);
-    }
-  }
-#endif
-  // two-kernel form: 8 pixels per thread only -- with 16 (tensors of 17-34 MB) it measured equal or slower than the
-  // three-kernel form (profiles/r02_norm_forms.txt)
-  for (int P = 8; P <= (one ? 16 : 8); P *= 2) {
-    const FusedGeom g = fused_geom(d->N, d->H * d->W, cpad(d->C), VE, P);
-    const long long groups = (long long)d->N * g.col_blocks, blocks = groups * g.splits;
-    if (g.splits > 64 || blocks > (1ll << 30)) continue;
-    if (one && (groups > kCountSlots || blocks > (P == 8 ? cap8 : cap16))) continue;
-    *out = g;
-    return P;
-  }
-  return 0;
+// Geometry of the register-held forms for a call: 8 pixels per thread -- with 16 (tensors of 17-34 MB) the two-kernel form
+// measured equal or slower than the three-kernel form (profiles/r02_norm_forms.txt).  False: moment -> finalize -> apply.
+template <typename T> static bool reg_geom(const jpdse_inorm_desc* d, FusedGeom* out) {
+  const FusedGeom g = fused_geom(d->N, d->H * d->W, cpad(d->C), Vec16<T>::N, 8);
+  if (g.splits > 64 || (long long)d->N * g.col_blocks * g.splits > (1ll << 30)) return false;
+  *out = g;
+  return true;
 }
 
 static size_t reg_ws_bytes(const jpdse_inorm_desc* d) {
-  // Rows of the register-held forms, counted with P = 8 (the larger split count); 0 when they do not apply.  The bound is 128
-  // splits although reg_pick admits 64: the one-kernel form may hold 16 pixels per thread, and its 64 splits are 128 at P = 8.
+  // Rows of the register-held form (8 pixels per thread); 0 when it does not apply.  The bound is 128 splits although
+  // reg_geom admits 64: the retired one-kernel form could hold 16 pixels per thread, whose 64 splits are 128 at 8, and
   // jpdse_inorm_workspace_size reports this number, so it stays as it is.
   const FusedGeom g = fused_geom(d->N, d->H * d->W, cpad(d->C), vec_elems(d->dtype), 8);
   if (g.splits > 128) return 0;
@@ -887,57 +785,37 @@ static size_t ws_bytes_for(const jpdse_inorm_desc* d) {
   return three > reg ? three : reg;
 }
 
-// inorm_reg_{fwd,bwd}_kernel<T, P, PHASE>.  `part`: the partial rows (PHASE 0-2) or the producer's `mslots` slots (PHASE 3).
-template <typename T, int P, int PHASE, bool BWD>
-static int launch_reg(const NormCall& c, const FusedGeom& fg, float* part, unsigned* count, int mslots = 0) {
-  static const char* const what[2][4] = {
-      {"inorm one-kernel fwd", "inorm rows fwd", "inorm apply-from-rows fwd", "inorm apply-from-slots fwd"},
-      {"inorm one-kernel bwd", "inorm rows bwd", "inorm apply-from-rows bwd", "inorm apply-from-slots bwd"}};
+// inorm_reg_{fwd,bwd}_kernel<T, 8, PHASE>.  `part`: the partial rows (PHASE 1-2) or the producer's `mslots` slots (PHASE 3).
+template <typename T, int PHASE, bool BWD>
+static int launch_reg(const NormCall& c, const FusedGeom& fg, float* part, int mslots = 0) {
+  static const char* const what[2][3] = {{"inorm rows fwd", "inorm apply-from-rows fwd", "inorm apply-from-slots fwd"},
+                                         {"inorm rows bwd", "inorm apply-from-rows bwd", "inorm apply-from-slots bwd"}};
   const jpdse_inorm_desc* d = c.d;
   if constexpr (BWD)
-    return launch256(what[1][PHASE], inorm_reg_bwd_kernel<T, P, PHASE>, fused_grid(fg), c.stream, cptr<T>(c.x), cptr<T>(c.in2),
-                     mptr<T>(c.out), c.stats, part, count, d->act, d->slope, fg, mslots);
+    return launch256(what[1][PHASE - 1], inorm_reg_bwd_kernel<T, 8, PHASE>, fused_grid(fg), c.stream, cptr<T>(c.x), cptr<T>(c.in2),
+                     mptr<T>(c.out), c.stats, part, (unsigned*)nullptr, d->act, d->slope, fg, mslots);
   else
-    return launch256(what[0][PHASE], inorm_reg_fwd_kernel<T, P, PHASE>, fused_grid(fg), c.stream, cptr<T>(c.x), cptr<T>(c.in2),
-                     mptr<T>(c.out), c.stats, part, count, d->act, d->slope, d->eps, fg, mslots);
-}
-
-// form 2: the one kernel (developer build only); form 1: rows, then apply-from-rows
-template <typename T, int P, bool BWD>
-static int launch_reg_form(int form, const NormCall& c, const FusedGeom& fg, float* part, unsigned* count) {
-#ifdef JPDSE_DEV
-  if (form == 2) return launch_reg<T, P, 0, BWD>(c, fg, part, count);
-#endif
-  if (int rc = launch_reg<T, P, 1, BWD>(c, fg, part, count)) return rc;
-  return launch_reg<T, P, 2, BWD>(c, fg, part, count);
+    return launch256(what[0][PHASE - 1], inorm_reg_fwd_kernel<T, 8, PHASE>, fused_grid(fg), c.stream, cptr<T>(c.x), cptr<T>(c.in2),
+                     mptr<T>(c.out), c.stats, part, (unsigned*)nullptr, d->act, d->slope, d->eps, fg, mslots);
 }
 
 constexpr int kNoRegForm = 1;      // returned by the two routines below when the register-held forms do not cover the call
 
-// The register-held forms, in the order one kernel (form 2, when the grid is resident and count words are to be had) ->
-// two kernels (form 1) -> kNoRegForm: the caller runs moment -> finalize -> apply.  Otherwise the launch's return code.
+// The two-kernel form (rows, then apply-from-rows), or kNoRegForm: the caller runs moment -> finalize -> apply.
 template <typename T, bool BWD> static int try_reg(const NormCall& c, void* ws) {
-  int form = norm_form();
-  if (form == 0) return kNoRegForm;
   FusedGeom fg;
-  int P = reg_pick<T, BWD>(c.d, form == 2, &fg);
-  if (P == 0 && form == 2) { form = 1; P = reg_pick<T, BWD>(c.d, false, &fg); }
-  if (P == 0) return kNoRegForm;
-  unsigned* count = nullptr;
-  if (form == 2 && fg.splits > 1) {
-    count = count_slots(as_stream(c.stream), c.d->N * fg.col_blocks);
-    if (count == nullptr) form = 1;
-  }
+  if (norm_form() == 0 || !reg_geom<T>(c.d, &fg)) return kNoRegForm;
   float* part = mptr<float>(ws);
-  return P == 8 ? launch_reg_form<T, 8, BWD>(form, c, fg, part, count) : launch_reg_form<T, 16, BWD>(form, c, fg, part, count);
+  if (int rc = launch_reg<T, 1, BWD>(c, fg, part)) return rc;
+  return launch_reg<T, 2, BWD>(c, fg, part);
 }
 
 // PHASE 3, ONE kernel per norm: every block merges the producer's slots of its channels itself and applies.  For tensors the
 // two-kernel form covers with 8 pixels per thread (e.g. the ResnetBlock norms) and at most 64 slots per (image, channel).
 template <typename T, bool BWD> static int try_reg_from_slots(const NormCall& c, const float* slots_in, int slots) {
   FusedGeom fg;
-  if (norm_form() == 0 || slots > 64 || reg_pick<T, BWD>(c.d, false, &fg) != 8) return kNoRegForm;
-  return launch_reg<T, 8, 3, BWD>(c, fg, const_cast<float*>(slots_in), nullptr, slots);
+  if (norm_form() == 0 || slots > 64 || !reg_geom<T>(c.d, &fg)) return kNoRegForm;
+  return launch_reg<T, 3, BWD>(c, fg, const_cast<float*>(slots_in), slots);
 }
 
 // third kernel of moment -> finalize -> apply; `sums`: backward only

@@ -1,5 +1,5 @@
 """A/B of halo-kernel variants (developer build): fwd + dgrad of the ResnetBlock conv and two VGG layers, timing and bit-comparison
-against the first mode.  Usage: python scripts/bench_halo.py 1,19"""
+against the first mode.  Usage: python scripts/bench_halo.py 1,8   (8: always two patch buffers; 60: no XCD-aware tile order)"""
 import sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'jpd-se_amd'))

@@ -1,4 +1,4 @@
-"""A/B of the InstanceNorm forms (developer build): single-kernel (mode 1) against moment -> finalize -> apply (mode 27) on the
+"""A/B of the InstanceNorm forms (developer build): the register-held two-kernel form (mode 1) against moment -> finalize -> apply (mode 27) on the
 tensors of the bench step.  Usage: python scripts/bench_norm.py [1,27]"""
 import sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -239,37 +239,6 @@ def test_conv_fwd_dgrad_wgrad(case, dtype, seed):
   assert_close(layer.bias.grad.cpu(), br.grad, tol, name + ' bias grad')
 
 
-@pytest.mark.parametrize('name', ['halo_vgg_64', 'halo_vgg_256', 'ring_dgrad_192'])
-def test_halo_kernel_mfma_16x16x32_variant(name):
-  # developer mode 19: the halo kernel built on v_mfma_f32_16x16x32_bf16 (other swizzle, fragment and epilogue layout)
-  import jpdse_hip
-  case = [c for c in CONV_CASES if c[0] == name][0]
-  with jpdse_hip.dev_mode(19):          # developer build of the library (include/jpdse_dev.h)
-    test_conv_fwd_dgrad_wgrad(case, BF16, 0)
-
-
-@pytest.mark.parametrize('name', ['taps_4x4s2', 'd_layer2'])
-def test_taps_dgrad4_small_shapes(name):
-  # developer mode 43: the 4x4 stride-2 data gradient on the tap program (core) + fast kernel (fringe: all eight rectangles
-  # for taps_4x4s2) at sizes below the shipped tile-count threshold
-  import jpdse_hip
-  case = [c for c in CONV_CASES if c[0] == name][0]
-  with jpdse_hip.dev_mode(43):
-    test_conv_fwd_dgrad_wgrad(case, BF16, 0)
-
-
-@pytest.mark.parametrize('name', ['d1_like_taps', 'd2_like_taps'])
-def test_taps_dgrad4_fused_epilogues(name):
-  # the same path with the LeakyReLU mask and the fan-in addend in the core's epilogue and in the fringe's
-  import jpdse_hip
-  case = [c for c in LRELU_CASES if c[0] == name][0]
-  with jpdse_hip.dev_mode(43):
-    test_conv_dgrad_fused_lrelu(case, BF16)
-  case = [c for c in FUSED_RELU_CASES if c[0] == 'taps_dgrad4_fused'][0]
-  with jpdse_hip.dev_mode(43):
-    test_conv_dgrad_fused_relu(case, BF16)
-
-
 # conv -> ReLU(inplace) -> conv chains (VGG19): the second conv's data gradient with the ReLU backward fused
 # (jpdse_conv_dgrad_relu), on the halo, fast (merged stride phases), split-K and generic paths
 FUSED_RELU_CASES = [
@@ -605,11 +574,9 @@ def test_conv_norm_fused_moments_offset_channels_full_size(name, make, shape):
   assert_close(y.t.float().cpu(), y2.t.float().cpu(), RTOL[BF16], name + ' norm output, fused vs separate moments')
 
 
-# Persistent, cross-tile-pipelined fast kernel (gemm_pers.h; round 4): forward and merged-phase data gradient of the short-K
-# layers.  It is NOT on the default dispatch any more (once the epilogue staging of gemm_fast_kernel was fixed that kernel became
-# the faster one); it stays built and tested: developer mode 52 sends small problems
-# through it -- ragged M tails, ragged N tails, tiles that cross image boundaries, blocks with several tiles and blocks
-# with one -- against torch-CPU and against the kernels the default dispatch takes for the same layer (mode 50).
+# Short-K layers (forward and merged-phase data gradient) at small sizes under the shipped dispatch: ragged M tails, ragged N
+# tails, tiles that cross image boundaries, grids of more tiles than CUs -- against torch-CPU.  (The cases were written for the
+# persistent form of the fast kernel, retired with developer modes 50 / 51 / 52 / 61: DESIGN.md 4.1 (xxvii).)
 PERS_CASES = [
     # name,          N, H,  W,   C,   K,   k, st, pad, mode
     ('d1_like',      3, 33, 65,  64,  128, 4, 2,  2,   PAD_ZERO),
@@ -623,7 +590,7 @@ PERS_CASES = [
 
 
 @pytest.mark.parametrize('case', PERS_CASES, ids=[c[0] for c in PERS_CASES])
-def test_persistent_fast_kernel(case):
+def test_short_k_layers_small_shapes(case):
   name, N, H, W, C, K, k, st, pad, mode = case
   g = G(zlib.crc32(name.encode()) % 1000 + 3)
   x = quantize_like(torch.randn(N, C, H, W, generator=g), BF16)
@@ -632,20 +599,15 @@ def test_persistent_fast_kernel(case):
   y_ref = _torch_conv(xr, quantize_like(w, BF16), None, st, pad, mode, ACT_NONE)
   gy = quantize_like(torch.randn(y_ref.shape, generator=g), BF16)
   y_ref.backward(gy)
-  out = {}
-  for fm in (52, 50):
-    with jpdse_hip.dev_mode(fm):
-      layer = HipConv2d(C, K, k, st, pad, mode, act=ACT_NONE, apply_bias=False, dtype=BF16, device=DEV)
-      with torch.no_grad():
-        layer.weight.copy_(w)
-      y, ctx = layer.fwd(to_act(x, BF16))
-      dx = layer.bwd(ctx, to_act(gy, BF16), need_dx=True, need_dw=False)
-      torch.cuda.synchronize()
-      out[fm] = (y.t.clone(), dx.t.clone())
-  assert_close(to_nchw(Act(out[52][0], K)), y_ref.detach(), RTOL[BF16], name + ' fwd (persistent kernel)')
-  assert_close(to_nchw(Act(out[52][1], C)), xr.grad, RTOL[BF16], name + ' dgrad (persistent kernel)')
-  assert (out[52][0][..., K:] == 0).all() and (out[52][1][..., C:] == 0).all(), 'padding lanes must stay zero'
-  assert_close(out[52][0].float().cpu(), out[50][0].float().cpu(), RTOL[BF16], name + ' fwd: persistent kernel vs the default dispatch')
+  layer = HipConv2d(C, K, k, st, pad, mode, act=ACT_NONE, apply_bias=False, dtype=BF16, device=DEV)
+  with torch.no_grad():
+    layer.weight.copy_(w)
+  y, ctx = layer.fwd(to_act(x, BF16))
+  dx = layer.bwd(ctx, to_act(gy, BF16), need_dx=True, need_dw=False)
+  torch.cuda.synchronize()
+  assert_close(to_nchw(y), y_ref.detach(), RTOL[BF16], name + ' fwd')
+  assert_close(to_nchw(dx), xr.grad, RTOL[BF16], name + ' dgrad')
+  assert (y.t[..., K:] == 0).all() and (dx.t[..., C:] == 0).all(), 'padding lanes must stay zero'
 
 
 # InstanceNorm backward with its two per-channel sums taken from the epilogue of the data-gradient kernel that produced dy
@@ -768,21 +730,20 @@ def test_instance_norm_act(shape, act, dtype):
 
 
 # register-held InstanceNorm forms (norm.hip, inorm_reg_*): shapes with several pixel splits per (image, channel block), a
-# ragged last split, a ragged channel block, both register depths (8 / 16 pixels per thread), and one tensor with too many
-# splits (three-kernel form).  Checked against torch, against the three-kernel form and the one-kernel form (in-launch
-# exchange) of the developer build, and for run-to-run bit equality (partial rows are summed in split order).
+# ragged last split, a ragged channel block, and tensors with too many splits (three-kernel form).  Checked against torch,
+# against the three-kernel form of the developer build, and for run-to-run bit equality (partial rows are summed in split order).
 FUSED_NORM_SHAPES = [
     ('resblock_real', (4, 1024, 32, 64), True),    # the 36 ResnetBlock norms of the bench step: 512 blocks, 16 splits
     ('ragged_cols',   (2, 72, 40, 50), False),     # 9 channel vectors in a 16-wide block, 16 splits of 128 pixels
-    ('d_scale2_p16',  (8, 128, 65, 129), False),   # 8385 pixels: 33 splits of 256 (16 pixels per thread), ragged tail
-    ('down3_p16',     (2, 512, 64, 128), False),
+    ('d_scale2_p16',  (8, 128, 65, 129), False),   # 8385 pixels: 66 splits of 128, two more than the two-kernel form takes
+    ('down3_p16',     (2, 512, 64, 128), False),   # 8192 pixels: 64 splits, the most it takes
     ('too_large',     (1, 64, 512, 512), False),   # 512 splits: stays on moment -> finalize -> apply
 ]
 
 
 @pytest.mark.parametrize('dtype', DTYPES)
 @pytest.mark.parametrize('name,shape,with_res', FUSED_NORM_SHAPES, ids=[c[0] for c in FUSED_NORM_SHAPES])
-def test_instance_norm_exchange(name, shape, with_res, dtype):
+def test_instance_norm_register_held_forms(name, shape, with_res, dtype):
   N, C, H, W = shape
   g = G(zlib.crc32(name.encode()) & 0xffff)
   x = quantize_like(torch.randn(N, C, H, W, generator=g) * 1.5 + 0.7, dtype)
@@ -806,7 +767,7 @@ def test_instance_norm_exchange(name, shape, with_res, dtype):
   tol = RTOL[dtype]
   assert_close(to_nchw(y), y_ref.detach(), tol, 'inorm fwd')
   assert_close(to_nchw(dx), xr.grad, tol, 'inorm bwd')
-  for rep in range(3):                      # every launch uses a fresh epoch of the exchange flags
+  for rep in range(3):
     y2, stats2, dx2 = run()
     assert torch.equal(y2.t, y.t) and torch.equal(stats2, stats) and torch.equal(dx2.t, dx.t), 'not reproducible'
   with jpdse_hip.dev_mode(27):              # developer build: always the three-kernel form
@@ -816,14 +777,6 @@ def test_instance_norm_exchange(name, shape, with_res, dtype):
   assert_close(stats3.cpu()[:, :C], stats.cpu()[:, :C], st_tol, 'stats vs three-kernel form')
   assert_close(to_nchw(y3), to_nchw(y), tol, 'fwd vs three-kernel form')
   assert_close(to_nchw(dx3), to_nchw(dx), tol, 'bwd vs three-kernel form')
-  with jpdse_hip.dev_mode(28):              # one kernel, rows exchanged inside the launch (8 or 16 pixels per thread: its own
-    y4, stats4, dx4 = run()                 # split count, so another summation order than the shipped form)
-    assert_close(stats4.cpu()[:, :C], stats.cpu()[:, :C], st_tol, 'stats vs one-kernel form')
-    assert_close(to_nchw(y4), to_nchw(y), tol, 'fwd vs one-kernel form')
-    assert_close(to_nchw(dx4), to_nchw(dx), tol, 'bwd vs one-kernel form')
-    for rep in range(3):
-      y5, stats5, dx5 = run()
-      assert torch.equal(y5.t, y4.t) and torch.equal(stats5, stats4) and torch.equal(dx5.t, dx4.t), 'one-kernel form not reproducible'
 
 @pytest.mark.parametrize('dtype', DTYPES)
 def test_resnet_block(dtype):

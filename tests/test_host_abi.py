@@ -38,15 +38,15 @@ def test_library_loads_and_exports_header_symbols():
 
 
 def test_developer_switch_refuses_retired_modes():
-  """Host only (nothing is launched): the kept kernel-selection codes are accepted, the codes of the removed timing-only ablations
-  and wave-tile variants are refused by name instead of silently selecting the shipped dispatch."""
+  """Host only (nothing is launched): the kept kernel-selection codes are accepted, the codes of the removed timing-only ablations,
+  wave-tile variants and settled kernel alternatives are refused by name instead of silently selecting the shipped dispatch."""
   dev = ctypes.CDLL(jpdse_hip.DEV_LIB_PATH)
   dev.jpdse_debug_set_fast_path.restype, dev.jpdse_debug_set_fast_path.argtypes = ctypes.c_int32, [ctypes.c_int32]
   dev.jpdse_last_error.restype = ctypes.c_char_p
-  for mode in (0, 1, 6, 19, 27, 28, 43, 50, 52):
+  for mode in (0, 1, 6, 27, 29, 40):
     assert dev.jpdse_debug_set_fast_path(mode) == 0, mode
     assert dev.jpdse_debug_set_fast_path(1) == 0
-  for mode in (53, 54, 56, 100, 115, 201, 203, 210, 225):
+  for mode in (19, 28, 42, 43, 50, 51, 52, 61, 53, 54, 56, 100, 115, 201, 203, 210, 225):
     assert dev.jpdse_debug_set_fast_path(mode) == -1, mode       # JPDSE_EINVAL
     msg = dev.jpdse_last_error().decode()
     assert 'retired' in msg and str(mode) in msg, msg
