@@ -667,6 +667,109 @@ typedef struct jpdse_sem_loss_args {
 } jpdse_sem_loss_args;
 int jpdse_sem_weighted_loss(const jpdse_sem_loss_args* args);
 
+/* ---- soft-to-hard vector quantizer: ctu.quantizers.S2HVQ (reference ctu/quantizers/s2h_vq.py) ------------
+ * M vectors of D components against a learnable code book of L centres.  x: row-major [M][D] in `dtype` (fp32 or bf16);
+ * code_book: fp32 [L][D]; every [M][L] matrix (p, dp, onehot, s, ds) is fp32, index is int32 [M].  Arithmetic is fp32.
+ *   score        d[m][k]  = sum_j (x[m][j] - c[k][j])^2, j ascending: the direct form (s2h_vq.py:85-87), not the expansion
+ *                           |x|^2 - 2 x.c + |c|^2, which cancels and changes the nearest centre
+ *   soft_fwd     p[m][k]  = exp(-sigma (d[m][k] - dmin[m])) / sum_l exp(-sigma (d[m][l] - dmin[m])), dmin[m] = min_k d[m][k]:
+ *                           finite for every finite x and every sigma > 0 (a row that is numerically one-hot included)
+ *   hard_fwd     index[m] = the k of the smallest d[m][k], the LOWEST k on a tie; onehot[m][k] = (k == index[m]) when the
+ *                           pointer is given.  A NaN score never wins; a row of NaNs gives some index inside [0, L)
+ *   soft_bwd     g[m][k]  = p[m][k] (dp[m][k] - sum_l p[m][l] dp[m][l]),  dd = -sigma g
+ *                dx[m][j] = 2 sum_k dd[m][k] (x[m][j] - c[k][j]), k ascending, stored in x's dtype
+ *                dcode_book[k][j] = -2 sum_m dd[m][k] (x[m][j] - c[k][j]): fp32 partials per block in the workspace (m
+ *                           ascending inside a block's tiles), merged in block order.  dx or dcode_book may be NULL
+ *   decode       y[m]     = c[index[m]] in `dtype` (s2h_vq.py:182-183: the reference always decodes hard)
+ *   decode_bwd   dcode_book[k] = sum over {m : index[m] == k} of dy[m], m ascending inside a block's tiles, the same merge
+ *                An index outside [0, L) reads as centre 0 and sets bit 0 of the device int32 word `status` (a plain store;
+ *                the word is never cleared by the library); it never causes an access outside the code book
+ *   argmax       index[m] = the k of the largest s[m][k], the lowest k on a tie
+ *   pmf          pmf[k]   = (sum_m s[m][k]) / M (s2h_vq.py:312): fp32 sums per block, merged in block order in fp64
+ *   pmf_bwd      ds[m][k] = dpmf[k] / M
+ * No atomics; the grids and every order of summation depend on (M, D, L) alone: two calls on the same buffers give
+ * bit-identical results.  ws: jpdse_vq_workspace_size(M, D, L) bytes (host only; 0 for a shape outside the limits) serve
+ * soft_bwd, decode_bwd and pmf of that shape; soft_bwd reads it only with a dcode_book.
+ * JPDSE_EINVAL before any launch: a NULL args or required pointer; a bad dtype; D outside 1 .. 32, L outside 2 .. 512, M < 1,
+ * M * L >= 2^31; a sigma that is not finite and positive; a workspace that is missing or too small.  No call allocates,
+ * synchronises or throws. */
+size_t jpdse_vq_workspace_size(int32_t M, int32_t D, int32_t L);
+typedef struct jpdse_vq_soft_fwd_args {
+  int32_t dtype, M, D, L;
+  float sigma;
+  const void* x;
+  const float* code_book;
+  float* p;                /* [M][L] */
+  void* stream;
+} jpdse_vq_soft_fwd_args;
+int jpdse_vq_soft_fwd(const jpdse_vq_soft_fwd_args* args);
+typedef struct jpdse_vq_hard_fwd_args {
+  int32_t dtype, M, D, L;
+  const void* x;
+  const float* code_book;
+  int32_t* index;          /* [M] */
+  float* onehot;           /* [M][L], or NULL: indices only */
+  void* stream;
+} jpdse_vq_hard_fwd_args;
+int jpdse_vq_hard_fwd(const jpdse_vq_hard_fwd_args* args);
+typedef struct jpdse_vq_soft_bwd_args {
+  int32_t dtype, M, D, L;
+  float sigma;
+  const float* dp;         /* [M][L] */
+  const float* p;          /* [M][L], as soft_fwd stored it */
+  const void* x;
+  const float* code_book;
+  void* dx;                /* [M][D] in `dtype`, or NULL */
+  float* dcode_book;       /* [L][D], or NULL */
+  void* ws;
+  size_t ws_bytes;
+  void* stream;
+} jpdse_vq_soft_bwd_args;
+int jpdse_vq_soft_bwd(const jpdse_vq_soft_bwd_args* args);
+typedef struct jpdse_vq_decode_args {
+  int32_t dtype, M, D, L;
+  const int32_t* index;
+  const float* code_book;
+  void* y;                 /* [M][D] in `dtype` */
+  int32_t* status;         /* device word */
+  void* stream;
+} jpdse_vq_decode_args;
+int jpdse_vq_decode(const jpdse_vq_decode_args* args);
+typedef struct jpdse_vq_decode_bwd_args {
+  int32_t dtype, M, D, L;
+  const int32_t* index;
+  const void* dy;          /* [M][D] in `dtype` */
+  float* dcode_book;       /* [L][D] */
+  int32_t* status;         /* device word */
+  void* ws;
+  size_t ws_bytes;
+  void* stream;
+} jpdse_vq_decode_bwd_args;
+int jpdse_vq_decode_bwd(const jpdse_vq_decode_bwd_args* args);
+typedef struct jpdse_vq_argmax_args {
+  int32_t M, L;
+  const float* s;          /* [M][L] */
+  int32_t* index;
+  void* stream;
+} jpdse_vq_argmax_args;
+int jpdse_vq_argmax(const jpdse_vq_argmax_args* args);
+typedef struct jpdse_vq_pmf_args {
+  int32_t M, L;
+  const float* s;          /* [M][L] */
+  float* pmf;              /* [L] */
+  void* ws;
+  size_t ws_bytes;
+  void* stream;
+} jpdse_vq_pmf_args;
+int jpdse_vq_pmf(const jpdse_vq_pmf_args* args);
+typedef struct jpdse_vq_pmf_bwd_args {
+  int32_t M, L;
+  const float* dpmf;       /* [L] */
+  float* ds;               /* [M][L] */
+  void* stream;
+} jpdse_vq_pmf_bwd_args;
+int jpdse_vq_pmf_bwd(const jpdse_vq_pmf_bwd_args* args);
+
 /* ---- optimizer ---------------------------------------------------------------------- */
 /* torch.optim.Adam (model.py:275,279) over a table of tensors, one launch.  `table` is a
  * device array of jpdse_adam_entry; bias corrections are computed from `step` (1-based). */

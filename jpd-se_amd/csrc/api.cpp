@@ -32,6 +32,92 @@ int code_import_check(int dtype, int N, int H, int W, int C, const void* in, con
   return JPDSE_OK;
 }
 
+// jpdse_vq_* (vq.hip): everything that can be refused without a device
+int vq_shape_check(const char* who, int M, int D, int L) {
+  JPDSE_REQUIRE(D >= 1 && D <= 32, "%s: center_size D = %d (1 .. 32)", who, D);
+  JPDSE_REQUIRE(L >= 2 && L <= 512, "%s: n_center L = %d (2 .. 512)", who, L);
+  JPDSE_REQUIRE(M >= 1, "%s: M = %d vectors (at least 1)", who, M);
+  JPDSE_REQUIRE((long long)M * L < (1LL << 31), "%s: M * L = %lld (below 2^31)", who, (long long)M * L);
+  return JPDSE_OK;
+}
+
+static int vq_sigma_check(const char* who, float sigma) {
+  JPDSE_REQUIRE(isfinite(sigma) && sigma > 0.f, "%s: sigma is %g (a finite value > 0)", who, (double)sigma);
+  return JPDSE_OK;
+}
+
+static int vq_ws_check(const char* who, const void* ws, size_t ws_bytes, int M, int D, int L) {
+  const size_t need = vq_workspace_bytes(M, D, L);
+  JPDSE_REQUIRE(ws != nullptr && ws_bytes >= need, "%s: workspace too small (%zu bytes, %zu needed)", who,
+                ws ? ws_bytes : (size_t)0, need);
+  return JPDSE_OK;
+}
+
+int vq_soft_fwd_check(const jpdse_vq_soft_fwd_args* a) {
+  JPDSE_REQUIRE(a != nullptr, "vq_soft_fwd: null argument struct");
+  JPDSE_REQUIRE(!bad_dtype(a->dtype), "vq_soft_fwd: bad dtype %d", a->dtype);
+  if (int rc = vq_shape_check("vq_soft_fwd", a->M, a->D, a->L)) return rc;
+  if (int rc = vq_sigma_check("vq_soft_fwd", a->sigma)) return rc;
+  JPDSE_REQUIRE(a->x && a->code_book && a->p, "vq_soft_fwd: null pointer");
+  return JPDSE_OK;
+}
+
+int vq_hard_fwd_check(const jpdse_vq_hard_fwd_args* a) {
+  JPDSE_REQUIRE(a != nullptr, "vq_hard_fwd: null argument struct");
+  JPDSE_REQUIRE(!bad_dtype(a->dtype), "vq_hard_fwd: bad dtype %d", a->dtype);
+  if (int rc = vq_shape_check("vq_hard_fwd", a->M, a->D, a->L)) return rc;
+  JPDSE_REQUIRE(a->x && a->code_book && a->index, "vq_hard_fwd: null pointer");
+  return JPDSE_OK;
+}
+
+int vq_soft_bwd_check(const jpdse_vq_soft_bwd_args* a) {
+  JPDSE_REQUIRE(a != nullptr, "vq_soft_bwd: null argument struct");
+  JPDSE_REQUIRE(!bad_dtype(a->dtype), "vq_soft_bwd: bad dtype %d", a->dtype);
+  if (int rc = vq_shape_check("vq_soft_bwd", a->M, a->D, a->L)) return rc;
+  if (int rc = vq_sigma_check("vq_soft_bwd", a->sigma)) return rc;
+  JPDSE_REQUIRE(a->dp && a->p && a->x && a->code_book, "vq_soft_bwd: null pointer");
+  if (a->dcode_book != nullptr)
+    if (int rc = vq_ws_check("vq_soft_bwd", a->ws, a->ws_bytes, a->M, a->D, a->L)) return rc;
+  return JPDSE_OK;
+}
+
+int vq_decode_check(const jpdse_vq_decode_args* a) {
+  JPDSE_REQUIRE(a != nullptr, "vq_decode: null argument struct");
+  JPDSE_REQUIRE(!bad_dtype(a->dtype), "vq_decode: bad dtype %d", a->dtype);
+  if (int rc = vq_shape_check("vq_decode", a->M, a->D, a->L)) return rc;
+  JPDSE_REQUIRE(a->index && a->code_book && a->y && a->status, "vq_decode: null pointer");
+  return JPDSE_OK;
+}
+
+int vq_decode_bwd_check(const jpdse_vq_decode_bwd_args* a) {
+  JPDSE_REQUIRE(a != nullptr, "vq_decode_bwd: null argument struct");
+  JPDSE_REQUIRE(!bad_dtype(a->dtype), "vq_decode_bwd: bad dtype %d", a->dtype);
+  if (int rc = vq_shape_check("vq_decode_bwd", a->M, a->D, a->L)) return rc;
+  JPDSE_REQUIRE(a->index && a->dy && a->dcode_book && a->status, "vq_decode_bwd: null pointer");
+  return vq_ws_check("vq_decode_bwd", a->ws, a->ws_bytes, a->M, a->D, a->L);
+}
+
+int vq_argmax_check(const jpdse_vq_argmax_args* a) {
+  JPDSE_REQUIRE(a != nullptr, "vq_argmax: null argument struct");
+  if (int rc = vq_shape_check("vq_argmax", a->M, 1, a->L)) return rc;
+  JPDSE_REQUIRE(a->s && a->index, "vq_argmax: null pointer");
+  return JPDSE_OK;
+}
+
+int vq_pmf_check(const jpdse_vq_pmf_args* a) {
+  JPDSE_REQUIRE(a != nullptr, "vq_pmf: null argument struct");
+  if (int rc = vq_shape_check("vq_pmf", a->M, 1, a->L)) return rc;
+  JPDSE_REQUIRE(a->s && a->pmf, "vq_pmf: null pointer");
+  return vq_ws_check("vq_pmf", a->ws, a->ws_bytes, a->M, 1, a->L);
+}
+
+int vq_pmf_bwd_check(const jpdse_vq_pmf_bwd_args* a) {
+  JPDSE_REQUIRE(a != nullptr, "vq_pmf_bwd: null argument struct");
+  if (int rc = vq_shape_check("vq_pmf_bwd", a->M, 1, a->L)) return rc;
+  JPDSE_REQUIRE(a->dpmf && a->ds, "vq_pmf_bwd: null pointer");
+  return JPDSE_OK;
+}
+
 // jpdse_code_cost (code_cost.hip): T[v] = round(-log2(v / 2048) * 2^16) for v in 1 .. 2047, T[0] = T[2048] = 0 (a probability
 // never leaves [31, 2017]: neither end is ever looked up).  fp64 on the host; v / 2048 is exact.
 const uint32_t* code_cost_table_host() {

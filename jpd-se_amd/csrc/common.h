@@ -21,6 +21,20 @@ int check_launch(const char* what);
 // argument checks of jpdse_code_import (api.cpp): JPDSE_EINVAL + message before any launch, JPDSE_OK otherwise
 int code_import_check(int dtype, int N, int H, int W, int C, const void* in, const void* b);
 
+// argument checks of the jpdse_vq_* calls (api.cpp; kernels: vq.hip): JPDSE_EINVAL + message before any launch.  The shape
+// check is the limits 1 <= D <= 32, 2 <= L <= 512, M >= 1, M * L < 2^31; vq_workspace_bytes (vq.hip) is what
+// jpdse_vq_workspace_size returns for a shape inside them.
+int vq_shape_check(const char* who, int M, int D, int L);
+size_t vq_workspace_bytes(int M, int D, int L);
+int vq_soft_fwd_check(const jpdse_vq_soft_fwd_args* a);
+int vq_hard_fwd_check(const jpdse_vq_hard_fwd_args* a);
+int vq_soft_bwd_check(const jpdse_vq_soft_bwd_args* a);
+int vq_decode_check(const jpdse_vq_decode_args* a);
+int vq_decode_bwd_check(const jpdse_vq_decode_bwd_args* a);
+int vq_argmax_check(const jpdse_vq_argmax_args* a);
+int vq_pmf_check(const jpdse_vq_pmf_args* a);
+int vq_pmf_bwd_check(const jpdse_vq_pmf_bwd_args* a);
+
 // the cost table of jpdse_code_cost_table (api.cpp): 2049 entries, built once on the host in fp64
 const uint32_t* code_cost_table_host();
 

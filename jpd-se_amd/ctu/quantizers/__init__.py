@@ -1,0 +1,3 @@
+"""Quantizers of the reference's `ctu.quantizers` that run on the HIP kernels: the soft-to-hard vector quantizer.  (The
+binarizer lives inside the encoder, jpdse_hip.layers.HipBinarizer.)"""
+from .s2h_vq import *  # noqa: F401,F403

@@ -1,0 +1,203 @@
+"""Soft-to-hard vector quantizer (reference ctu/quantizers/s2h_vq.py) on the jpdse_vq_* kernels.
+
+`S2HVQ` keeps the reference's interface -- parameter `_code_book`, properties `center_size` / `code_book` / `sigma`, methods
+`encode` / `decode`, static `get_pmf` / `get_cross_entropy` -- so a reference training loop runs unchanged:
+
+    code_raw = vq.encode(x, code_len)                       # soft assignment, differentiable in x and the code book
+    pmf = S2HVQ.get_pmf(code_raw)
+    loss = S2HVQ.get_cross_entropy(pmf, pmf) + ((vq.decode(code_raw) - x) ** 2).mean()
+    loss.backward()
+
+Every [.., n_center] matrix is float32, as in the reference, where the float32 code book promotes the scores; the hard one-hot
+takes x's dtype.  There is no CPU path: tensors live on the GPU.  Limits (the kernels'): center_size <= 32, 2 <= n_center
+<= 512, n * code_len * n_center < 2^31; anything beyond raises NotImplementedError.
+"""
+import torch
+import torch.nn as nn
+
+import jpdse_hip
+from jpdse_hip import ops
+
+__all__ = ['S2HVQ', 'S2HVQV2']
+
+MAX_CENTER_SIZE = ops.VQ_MAX_D
+MAX_N_CENTER = ops.VQ_MAX_L
+
+
+def _on_gpu(t, what):
+  if not t.is_cuda:
+    raise jpdse_hip.JpdseError('S2HVQ: %s is on %s: the JPD-SE HIP path has no CPU fallback' % (what, t.device))
+
+
+def _rows_limit(rows, n_center):
+  if rows * n_center >= 2 ** 31:
+    raise NotImplementedError('S2HVQ: n * code_len * n_center = %d, the kernels index below 2^31' % (rows * n_center))
+
+
+class _SoftAssign(torch.autograd.Function):
+  """p = softmax_k(-sigma |x_m - c_k|^2) (ops.vq_soft_fwd); backward from the stored p (ops.vq_soft_bwd)."""
+
+  @staticmethod
+  def forward(ctx, x, code_book, sigma):
+    x, code_book = x.contiguous(), code_book.contiguous()
+    p = ops.vq_soft_fwd(x, code_book, sigma)
+    ctx.save_for_backward(x, code_book, p)
+    ctx.sigma = sigma
+    return p
+
+  @staticmethod
+  def backward(ctx, dp):
+    x, code_book, p = ctx.saved_tensors
+    dx, dc = ops.vq_soft_bwd(dp.contiguous(), p, x, code_book, ctx.sigma, want_dx=ctx.needs_input_grad[0],
+                             want_dc=ctx.needs_input_grad[1])
+    return dx, dc, None
+
+
+class _Gather(torch.autograd.Function):
+  """y[m] = code_book[index[m]] (ops.vq_decode); the code book's gradient is the transposed gather (ops.vq_decode_bwd)."""
+
+  @staticmethod
+  def forward(ctx, code_book, index, status):
+    code_book = code_book.contiguous()
+    y, _ = ops.vq_decode(index, code_book, torch.float32, status)
+    ctx.save_for_backward(index)
+    ctx.n_center = code_book.shape[0]
+    return y
+
+  @staticmethod
+  def backward(ctx, dy):
+    index, = ctx.saved_tensors
+    dc, _ = ops.vq_decode_bwd(index, dy.contiguous(), ctx.n_center)
+    return dc, None, None
+
+
+class _Pmf(torch.autograd.Function):
+  """pmf[k] = mean over the rows of scores[.., k] (ops.vq_pmf / ops.vq_pmf_bwd)."""
+
+  @staticmethod
+  def forward(ctx, scores):
+    s = scores.contiguous().view(-1, scores.shape[-1])
+    ctx.shape = tuple(scores.shape)
+    return ops.vq_pmf(s)
+
+  @staticmethod
+  def backward(ctx, dpmf):
+    rows = 1
+    for v in ctx.shape[:-1]:
+      rows *= v
+    return ops.vq_pmf_bwd(dpmf.contiguous(), rows).view(ctx.shape)
+
+
+class S2HVQ(nn.Module):
+  """code_book: tensor [n_center, center_size], learnable (parameter `_code_book`); sigma > 0: the hardness of the soft
+  assignment used in training."""
+
+  def __init__(self, code_book, sigma=10., **kwargs):
+    super(S2HVQ, self).__init__()
+    assert sigma > 0, "sigma must be greater than 0, got {}".format(sigma)
+    if code_book.dim() != 2:
+      raise ValueError('code_book must have shape (n_center, center_size), got {}'.format(tuple(code_book.shape)))
+    n_center, center_size = int(code_book.size(0)), int(code_book.size(1))
+    if not 1 <= center_size <= MAX_CENTER_SIZE:
+      raise NotImplementedError('S2HVQ: center_size %d, the kernels take 1 .. %d' % (center_size, MAX_CENTER_SIZE))
+    if not 2 <= n_center <= MAX_N_CENTER:
+      raise NotImplementedError('S2HVQ: n_center %d, the kernels take 2 .. %d' % (n_center, MAX_N_CENTER))
+    if code_book.dtype != torch.float32:
+      raise NotImplementedError('S2HVQ: a %s code book, the kernels keep it in float32' % (code_book.dtype,))
+    self._center_size = center_size
+    self._code_book = nn.Parameter(code_book)
+    self._sigma = sigma
+
+  @property
+  def center_size(self):
+    return self._center_size
+
+  @property
+  def code_book(self):
+    return self._code_book
+
+  @property
+  def sigma(self):
+    return self._sigma
+
+  @sigma.setter
+  def sigma(self, new_sigma):
+    assert new_sigma > 0, "sigma must be greater than 0, got {}".format(new_sigma)
+    self._sigma = new_sigma
+
+  def _vectors(self, x, code_len):
+    """[n, d] -> the contiguous [n * code_len, center_size] matrix of vectors, after every check that needs no device."""
+    if x.size(1) < code_len:
+      raise ValueError("x.size(1) must be greater than or equal to code_len, got "
+                       "{} and {}, respectively".format(x.size(1), code_len))
+    if x.size(1) % code_len != 0:
+      raise ValueError("code_len must divide x.size(1), got {} and {}, respectively".format(code_len, x.size(1)))
+    if x.size(1) // code_len != self.code_book.size(1):
+      raise ValueError("Illegal code_len. x.size(1) // code_len must equal "
+                       "code_book.size(0), got {}, {}, and {}, respectively.".format(x.size(1), code_len, self.code_book.size(1)))
+    if x.dtype not in (torch.float32, torch.bfloat16):
+      raise NotImplementedError('S2HVQ: x is %s, the kernels take float32 and bfloat16' % (x.dtype,))
+    _rows_limit(x.size(0) * code_len, self.code_book.size(0))
+    _on_gpu(x, 'x')
+    _on_gpu(self.code_book, 'the code book')
+    return x.contiguous().view(x.size(0) * code_len, self._center_size)
+
+  def encode(self, x, code_len, train=True, raw=True):
+    """x [n, d], code_len dividing d with d // code_len == center_size.  raw: the scores over the centres, [n, code_len,
+    n_center] -- the soft assignment (train, float32, differentiable) or the one-hot of the nearest centre (x's dtype);
+    not raw: the index of the highest score, int64 [n, code_len]."""
+    xm = self._vectors(x, code_len)
+    n, L = x.size(0), self.code_book.size(0)
+    if train:
+      p = _SoftAssign.apply(xm, self.code_book, float(self._sigma))
+      if raw:
+        return p.view(n, code_len, L)
+      return ops.vq_argmax(p.detach()).to(torch.int64).view(n, code_len)
+    index, onehot = ops.vq_hard_fwd(xm.detach(), self.code_book.detach().contiguous(), want_onehot=raw)
+    if raw:
+      return onehot.view(n, code_len, L).to(x.dtype)
+    return index.to(torch.int64).view(n, code_len)
+
+  def decode(self, code_raw):
+    """code_raw [n, code_len, n_center] (e.g. encode(..., raw=True)) -> [n, code_len * center_size]: the centre with the highest
+    score of every position (always the hard decoding, as the reference).  Differentiable in the code book."""
+    L = self.code_book.size(0)
+    if code_raw.dim() != 3 or code_raw.size(2) != L:
+      raise ValueError('code_raw must have shape (n, code_len, {}), got {}'.format(L, tuple(code_raw.shape)))
+    _rows_limit(code_raw.size(0) * code_raw.size(1), L)
+    _on_gpu(code_raw, 'code_raw')
+    _on_gpu(self.code_book, 'the code book')
+    s = code_raw.detach().contiguous().view(-1, L)
+    index = ops.vq_argmax(s if s.dtype == torch.float32 else s.float())
+    status = torch.zeros(1, dtype=torch.int32, device=index.device)
+    y = _Gather.apply(self.code_book, index, status)
+    if not self.training and int(status.item()) != 0:      # eval paths synchronise anyway
+      raise ValueError('S2HVQ.decode: an index outside [0, {})'.format(L))
+    return y.view(code_raw.size(0), code_raw.size(1) * self._center_size)
+
+  @staticmethod
+  def get_pmf(scores):
+    """scores [n, code_len, n_center] -> the histogram over the centres, [n_center]: the batch estimate of the code's pmf."""
+    if not 2 <= scores.size(-1) <= MAX_N_CENTER:
+      raise NotImplementedError('S2HVQ.get_pmf: n_center %d, the kernels take 2 .. %d' % (scores.size(-1), MAX_N_CENTER))
+    _rows_limit(scores.numel() // scores.size(-1), scores.size(-1))
+    _on_gpu(scores, 'scores')
+    return _Pmf.apply(scores if scores.dtype == torch.float32 else scores.float())
+
+  @staticmethod
+  def get_cross_entropy(pmf1, pmf2):
+    """H(pmf1, pmf2) = -sum_k pmf1[k] log2 pmf2[k] over the centres with pmf2[k] > 0.  n_center numbers: plain torch."""
+    assert torch.all(pmf1 >= 0), "pmf1 have < 0 or nan element(s)"
+    assert torch.all(pmf2 >= 0), "pmf2 have < 0 or nan element(s)"
+    one = torch.tensor(1., device=pmf1.device)
+    assert torch.allclose(pmf1.sum(), one), "pmf1 is not normalized"
+    assert torch.allclose(pmf2.sum(), one.to(pmf2.device)), "pmf2 is not normalized"
+    keep = pmf2 > 0
+    return (-pmf1[keep] * torch.log2(pmf2[keep])).sum()
+
+
+class S2HVQV2(S2HVQ):
+  """The reference's variant with an MLP score: it needs Linear layers, which this project does not have."""
+
+  def __init__(self, **kwargs):
+    raise NotImplementedError('S2HVQV2 scores with an MLP (three Linear layers): not available on the HIP path')

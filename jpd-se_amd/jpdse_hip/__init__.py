@@ -88,6 +88,53 @@ class CodeCostArgs(ctypes.Structure):
               ('ws_bytes', ctypes.c_size_t), ('stream', ctypes.c_void_p)]
 
 
+# the jpdse_vq_* calls (vq.hip)
+class VqSoftFwdArgs(ctypes.Structure):
+  _fields_ = [(n, ctypes.c_int32) for n in ('dtype', 'M', 'D', 'L')] + \
+             [('sigma', ctypes.c_float), ('x', ctypes.c_void_p), ('code_book', ctypes.c_void_p), ('p', ctypes.c_void_p),
+              ('stream', ctypes.c_void_p)]
+
+
+class VqHardFwdArgs(ctypes.Structure):
+  _fields_ = [(n, ctypes.c_int32) for n in ('dtype', 'M', 'D', 'L')] + \
+             [('x', ctypes.c_void_p), ('code_book', ctypes.c_void_p), ('index', ctypes.c_void_p), ('onehot', ctypes.c_void_p),
+              ('stream', ctypes.c_void_p)]
+
+
+class VqSoftBwdArgs(ctypes.Structure):
+  _fields_ = [(n, ctypes.c_int32) for n in ('dtype', 'M', 'D', 'L')] + \
+             [('sigma', ctypes.c_float), ('dp', ctypes.c_void_p), ('p', ctypes.c_void_p), ('x', ctypes.c_void_p),
+              ('code_book', ctypes.c_void_p), ('dx', ctypes.c_void_p), ('dcode_book', ctypes.c_void_p), ('ws', ctypes.c_void_p),
+              ('ws_bytes', ctypes.c_size_t), ('stream', ctypes.c_void_p)]
+
+
+class VqDecodeArgs(ctypes.Structure):
+  _fields_ = [(n, ctypes.c_int32) for n in ('dtype', 'M', 'D', 'L')] + \
+             [('index', ctypes.c_void_p), ('code_book', ctypes.c_void_p), ('y', ctypes.c_void_p), ('status', ctypes.c_void_p),
+              ('stream', ctypes.c_void_p)]
+
+
+class VqDecodeBwdArgs(ctypes.Structure):
+  _fields_ = [(n, ctypes.c_int32) for n in ('dtype', 'M', 'D', 'L')] + \
+             [('index', ctypes.c_void_p), ('dy', ctypes.c_void_p), ('dcode_book', ctypes.c_void_p), ('status', ctypes.c_void_p),
+              ('ws', ctypes.c_void_p), ('ws_bytes', ctypes.c_size_t), ('stream', ctypes.c_void_p)]
+
+
+class VqArgmaxArgs(ctypes.Structure):
+  _fields_ = [('M', ctypes.c_int32), ('L', ctypes.c_int32), ('s', ctypes.c_void_p), ('index', ctypes.c_void_p),
+              ('stream', ctypes.c_void_p)]
+
+
+class VqPmfArgs(ctypes.Structure):
+  _fields_ = [('M', ctypes.c_int32), ('L', ctypes.c_int32), ('s', ctypes.c_void_p), ('pmf', ctypes.c_void_p),
+              ('ws', ctypes.c_void_p), ('ws_bytes', ctypes.c_size_t), ('stream', ctypes.c_void_p)]
+
+
+class VqPmfBwdArgs(ctypes.Structure):
+  _fields_ = [('M', ctypes.c_int32), ('L', ctypes.c_int32), ('dpmf', ctypes.c_void_p), ('ds', ctypes.c_void_p),
+              ('stream', ctypes.c_void_p)]
+
+
 _P, _I32, _I64, _F, _SZ = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float,
                            ctypes.c_size_t)
 _CD, _ND = ctypes.POINTER(ConvDesc), ctypes.POINTER(InormDesc)
@@ -193,6 +240,15 @@ SIGNATURES = {
     'jpdse_code_cost_table': (_I32, [ctypes.POINTER(ctypes.c_uint32)]),
     'jpdse_code_cost_workspace_size': (_SZ, [_I32, _I32, _I32, _I32, _I32]),
     'jpdse_code_cost': (_I32, [ctypes.POINTER(CodeCostArgs)]),
+    'jpdse_vq_workspace_size': (_SZ, [_I32, _I32, _I32]),
+    'jpdse_vq_soft_fwd': (_I32, [ctypes.POINTER(VqSoftFwdArgs)]),
+    'jpdse_vq_hard_fwd': (_I32, [ctypes.POINTER(VqHardFwdArgs)]),
+    'jpdse_vq_soft_bwd': (_I32, [ctypes.POINTER(VqSoftBwdArgs)]),
+    'jpdse_vq_decode': (_I32, [ctypes.POINTER(VqDecodeArgs)]),
+    'jpdse_vq_decode_bwd': (_I32, [ctypes.POINTER(VqDecodeBwdArgs)]),
+    'jpdse_vq_argmax': (_I32, [ctypes.POINTER(VqArgmaxArgs)]),
+    'jpdse_vq_pmf': (_I32, [ctypes.POINTER(VqPmfArgs)]),
+    'jpdse_vq_pmf_bwd': (_I32, [ctypes.POINTER(VqPmfBwdArgs)]),
 }
 
 # the developer build (same sources, -DJPDSE_DEV): the shipped ABI plus include/jpdse_dev.h

@@ -10,6 +10,7 @@ import struct
 import torch
 
 from . import (lib, check, JpdseError, F32, BF16, ConvDesc, InormDesc, EvalMetricsSemArgs, MsssimLossArgs, CodeRateArgs, SemLossArgs, CodeCostArgs, ACT_NONE, PAD_ZERO, PAD_REFLECT)
+from . import (VqSoftFwdArgs, VqHardFwdArgs, VqSoftBwdArgs, VqDecodeArgs, VqDecodeBwdArgs, VqArgmaxArgs, VqPmfArgs, VqPmfBwdArgs)
 
 
 def cpad(c):
@@ -1033,3 +1034,130 @@ def code_cost(b, label=None, n_classes=0, want_symbols=False):
                       torch.cuda.current_stream().cuda_stream)
   check(L.jpdse_code_cost(ctypes.byref(args)), 'code_cost')
   return dict(symbol=symbol, cell=cell, channel=channel, class_units=units, class_pixels=pixels)
+
+
+# ---- soft-to-hard vector quantizer (vq.hip; definition: DESIGN.md 4.13) -----------------------------------------------------
+# x: [M, D] fp32 or bf16; code_book: fp32 [L, D]; p / dp / onehot / s / ds: fp32 [M, L]; index: int32 [M].  All contiguous, on one
+# device.  The library refuses a shape beyond its limits (1 <= D <= 32, 2 <= L <= 512, M * L < 2^31) before any launch.
+VQ_MAX_D, VQ_MAX_L = 32, 512
+
+
+def _vq_dims(x, code_book):
+  assert x.dim() == 2 and code_book.dim() == 2 and x.is_contiguous() and code_book.is_contiguous(), (tuple(x.shape), tuple(code_book.shape))
+  assert code_book.dtype == torch.float32 and code_book.device == x.device and x.shape[1] == code_book.shape[1]
+  return int(x.shape[0]), int(x.shape[1]), int(code_book.shape[0])
+
+
+def _vq_rows(t, M=None, L=None):
+  assert t.dim() == 2 and t.dtype == torch.float32 and t.is_contiguous(), (t.dtype, tuple(t.shape))
+  assert (M is None or t.shape[0] == M) and (L is None or t.shape[1] == L), (tuple(t.shape), M, L)
+  return int(t.shape[0]), int(t.shape[1])
+
+
+def _vq_index(index, M, dev):
+  assert index.dtype == torch.int32 and index.is_contiguous() and index.numel() == M and index.device == dev, (index.dtype, tuple(index.shape))
+
+
+def _vq_ws(M, D, L, dev):
+  return workspace(max(lib().jpdse_vq_workspace_size(M, D, L), 1), dev)
+
+
+def vq_soft_fwd(x, code_book, sigma):
+  """p[m][k] = softmax_k(-sigma d[m][k]) with d[m][k] = sum_j (x[m][j] - code_book[k][j])^2, the row minimum subtracted first
+  (jpdse_vq_soft_fwd).  Returns fp32 [M, L]."""
+  M, D, L = _vq_dims(x, code_book)
+  p = torch.empty((M, L), dtype=torch.float32, device=x.device)
+  args = VqSoftFwdArgs(code_of(x.dtype), M, D, L, float(sigma), x.data_ptr(), code_book.data_ptr(), p.data_ptr(),
+                       torch.cuda.current_stream().cuda_stream)
+  check(lib().jpdse_vq_soft_fwd(ctypes.byref(args)), 'vq_soft_fwd')
+  return p
+
+
+def vq_hard_fwd(x, code_book, want_onehot=False):
+  """(index, onehot): int32 [M], the nearest centre of every vector (lowest index on a tie), and its fp32 one-hot [M, L]
+  (None unless want_onehot) (jpdse_vq_hard_fwd)."""
+  M, D, L = _vq_dims(x, code_book)
+  index = torch.empty(M, dtype=torch.int32, device=x.device)
+  onehot = torch.empty((M, L), dtype=torch.float32, device=x.device) if want_onehot else None
+  args = VqHardFwdArgs(code_of(x.dtype), M, D, L, x.data_ptr(), code_book.data_ptr(), index.data_ptr(),
+                       onehot.data_ptr() if want_onehot else None, torch.cuda.current_stream().cuda_stream)
+  check(lib().jpdse_vq_hard_fwd(ctypes.byref(args)), 'vq_hard_fwd')
+  return index, onehot
+
+
+def vq_soft_bwd(dp, p, x, code_book, sigma, want_dx=True, want_dc=True):
+  """(dx, dcode_book) of vq_soft_fwd for the upstream gradient dp, from the stored p (jpdse_vq_soft_bwd): dx in x's dtype
+  [M, D], dcode_book fp32 [L, D]; either is None when not wanted."""
+  M, D, L = _vq_dims(x, code_book)
+  _vq_rows(dp, M, L)
+  _vq_rows(p, M, L)
+  dx = torch.empty_like(x) if want_dx else None
+  dc = torch.empty_like(code_book) if want_dc else None
+  ws = _vq_ws(M, D, L, x.device)
+  args = VqSoftBwdArgs(code_of(x.dtype), M, D, L, float(sigma), dp.data_ptr(), p.data_ptr(), x.data_ptr(), code_book.data_ptr(),
+                       dx.data_ptr() if want_dx else None, dc.data_ptr() if want_dc else None, ws.data_ptr(), ws.numel(),
+                       torch.cuda.current_stream().cuda_stream)
+  check(lib().jpdse_vq_soft_bwd(ctypes.byref(args)), 'vq_soft_bwd')
+  return dx, dc
+
+
+def vq_decode(index, code_book, dtype=torch.float32, status=None):
+  """(y, status): y[m] = code_book[index[m]] in `dtype` [M, D] (jpdse_vq_decode).  An index outside [0, L) reads as centre 0 and
+  sets the int32 device word `status` (a zeroed one is made when None); reading it is the caller's choice: it synchronises."""
+  assert code_book.dim() == 2 and code_book.dtype == torch.float32 and code_book.is_contiguous()
+  L, D = int(code_book.shape[0]), int(code_book.shape[1])
+  M = int(index.numel())
+  dev = code_book.device
+  _vq_index(index, M, dev)
+  if status is None:
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+  y = torch.empty((M, D), dtype=dtype, device=dev)
+  args = VqDecodeArgs(code_of(dtype), M, D, L, index.data_ptr(), code_book.data_ptr(), y.data_ptr(), status.data_ptr(),
+                      torch.cuda.current_stream().cuda_stream)
+  check(lib().jpdse_vq_decode(ctypes.byref(args)), 'vq_decode')
+  return y, status
+
+
+def vq_decode_bwd(index, dy, L, status=None):
+  """(dcode_book, status): dcode_book[k] = the sum of the rows dy[m] with index[m] == k, fp32 [L, D] (jpdse_vq_decode_bwd)."""
+  assert dy.dim() == 2 and dy.is_contiguous()
+  M, D = int(dy.shape[0]), int(dy.shape[1])
+  dev = dy.device
+  _vq_index(index, M, dev)
+  if status is None:
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+  dc = torch.empty((int(L), D), dtype=torch.float32, device=dev)
+  ws = _vq_ws(M, D, int(L), dev)
+  args = VqDecodeBwdArgs(code_of(dy.dtype), M, D, int(L), index.data_ptr(), dy.data_ptr(), dc.data_ptr(), status.data_ptr(),
+                         ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+  check(lib().jpdse_vq_decode_bwd(ctypes.byref(args)), 'vq_decode_bwd')
+  return dc, status
+
+
+def vq_argmax(s):
+  """int32 [M]: the column of the largest entry of every row of the fp32 matrix s [M, L], lowest on a tie (jpdse_vq_argmax)."""
+  M, L = _vq_rows(s)
+  index = torch.empty(M, dtype=torch.int32, device=s.device)
+  args = VqArgmaxArgs(M, L, s.data_ptr(), index.data_ptr(), torch.cuda.current_stream().cuda_stream)
+  check(lib().jpdse_vq_argmax(ctypes.byref(args)), 'vq_argmax')
+  return index
+
+
+def vq_pmf(s):
+  """fp32 [L]: the column means of the fp32 matrix s [M, L] (jpdse_vq_pmf)."""
+  M, L = _vq_rows(s)
+  pmf = torch.empty(L, dtype=torch.float32, device=s.device)
+  ws = _vq_ws(M, 1, L, s.device)
+  args = VqPmfArgs(M, L, s.data_ptr(), pmf.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+  check(lib().jpdse_vq_pmf(ctypes.byref(args)), 'vq_pmf')
+  return pmf
+
+
+def vq_pmf_bwd(dpmf, M):
+  """fp32 [M, L]: ds[m][k] = dpmf[k] / M, the gradient of vq_pmf (jpdse_vq_pmf_bwd)."""
+  assert dpmf.dim() == 1 and dpmf.dtype == torch.float32 and dpmf.is_contiguous()
+  L = int(dpmf.numel())
+  ds = torch.empty((int(M), L), dtype=torch.float32, device=dpmf.device)
+  args = VqPmfBwdArgs(int(M), L, dpmf.data_ptr(), ds.data_ptr(), torch.cuda.current_stream().cuda_stream)
+  check(lib().jpdse_vq_pmf_bwd(ctypes.byref(args)), 'vq_pmf_bwd')
+  return ds
