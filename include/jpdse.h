@@ -770,6 +770,52 @@ typedef struct jpdse_vq_pmf_bwd_args {
 } jpdse_vq_pmf_bwd_args;
 int jpdse_vq_pmf_bwd(const jpdse_vq_pmf_bwd_args* args);
 
+/* ---- soft-to-hard vector quantizer: coded index stream (no reference counterpart; format: DESIGN.md 4.14) ------------------
+ * A lossless, order-0 adaptive L-ary range coder for the indices of the quantizer, and its decoder.  index: DEVICE int32 [M],
+ * the row-major [n][code_len] code, every value in [0, L).  The M indices are dealt to S independent streams by interleaving:
+ * stream s holds the symbols s, s + S, s + 2 S, ..., cnt_s = ceil((M - s) / S) of them.  A symbol is nb = max(1, bit_length(L - 1))
+ * binary decisions, most significant bit first, through a bit tree (m = 1; code the bit with prob[m]; m = m << 1 | bit) of 2^nb
+ * adaptive probabilities per stream (entry 0 unused); a decision is the adaptive binary decision of
+ * jpdse_code_entropy_encode: 11-bit probabilities of bit 0 starting at 1024, shift 5, the carry rule, the unstored first byte,
+ * the flush of five bytes.  A stream stores at most nb * cnt_s + 8 bytes (its slot).
+ * Payload: S little-endian uint32 stream lengths, then the S streams in order.
+ *   capacity(M, L, S)  = 4 S + the sum of the slots = nb M + 12 S: the most a payload can take; `out` must hold that many
+ *   encode             writes the payload to out, its size to *size, and *status: bit 0 a stream was cut at its slot (the
+ *                      bound makes that unreachable), bit 1 an index outside [0, L) was met and coded as 0.  Both device
+ *                      words are written by the call's last kernel with plain stores
+ *   decode             reads a payload of in_bytes bytes (device data it does not trust: a length that points outside the
+ *                      payload is clipped to it, a byte past a stream's end reads as 0) and writes exactly M indices, all in
+ *                      [0, L): a decoded value >= L (possible when L is no power of two) is written as L - 1 and sets bit 1
+ *                      of *status with a plain store (the word is never cleared by the library)
+ * Plain loads and stores, no atomics: two calls give identical bytes.  Every loop is bounded by M, nb or the bytes pending.
+ * Limits: 2 <= L <= 512, M >= 1, 1 <= S <= min(M, 65535), nb M < 2^31 and capacity < 2^31.  Both size queries are host-only
+ * and return 0 outside the limits.  JPDSE_EINVAL before any launch: a NULL args or pointer, a value outside the limits,
+ * out_bytes below the capacity, a workspace that is missing or below jpdse_vq_index_workspace_size(), in_bytes below the
+ * 4 S of the table or >= 2^31. */
+size_t jpdse_vq_index_capacity(int32_t M, int32_t L, int32_t S);
+size_t jpdse_vq_index_workspace_size(int32_t M, int32_t L, int32_t S);
+typedef struct jpdse_vq_index_encode_args {
+  int32_t M, L, S;
+  const int32_t* index;    /* device [M] */
+  uint8_t* out;            /* device, out_bytes >= capacity */
+  int64_t out_bytes;
+  int32_t* size;           /* device word: the payload's bytes */
+  int32_t* status;         /* device word */
+  void* ws;
+  size_t ws_bytes;
+  void* stream;
+} jpdse_vq_index_encode_args;
+int jpdse_vq_index_encode(const jpdse_vq_index_encode_args* args);
+typedef struct jpdse_vq_index_decode_args {
+  int32_t M, L, S;
+  const uint8_t* in;       /* device, in_bytes: the payload */
+  int64_t in_bytes;
+  int32_t* index;          /* device [M] */
+  int32_t* status;         /* device word */
+  void* stream;
+} jpdse_vq_index_decode_args;
+int jpdse_vq_index_decode(const jpdse_vq_index_decode_args* args);
+
 /* ---- optimizer ---------------------------------------------------------------------- */
 /* torch.optim.Adam (model.py:275,279) over a table of tensors, one launch.  `table` is a
  * device array of jpdse_adam_entry; bias corrections are computed from `step` (1-based). */

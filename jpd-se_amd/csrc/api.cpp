@@ -118,6 +118,62 @@ int vq_pmf_bwd_check(const jpdse_vq_pmf_bwd_args* a) {
   return JPDSE_OK;
 }
 
+// jpdse_vq_index_* (vq_coder.hip): the limits, the closed forms of the sizes, and everything that can be
+// refused without a device.  nb = max(1, bit_length(L - 1)) decisions per symbol; stream s of the S holds ceil((M - s) / S)
+// symbols and its slot nb of them + 8 bytes, so the slots add up to nb M + 8 S and the capacity is that + the 4 S of the table.
+int vq_index_bits(int L) {
+  int nb = 1;
+  while ((1 << nb) < L) ++nb;
+  return nb;
+}
+
+static bool vq_index_in_limits(int M, int L, int S) {
+  if (L < 2 || L > 512 || M < 1 || S < 1 || S > 65535 || S > M) return false;
+  const long long nb = vq_index_bits(L);
+  return nb * M < (1LL << 31) && nb * M + 12LL * S < (1LL << 31);
+}
+
+long long vq_index_capacity_bytes(int M, int L, int S) {
+  return vq_index_in_limits(M, L, S) ? (long long)vq_index_bits(L) * M + 12LL * S : 0;
+}
+
+size_t vq_index_workspace_bytes(int M, int L, int S) {
+  if (!vq_index_in_limits(M, L, S)) return 0;
+  // the slots, then the lengths and the flags of the streams
+  return align_up((size_t)vq_index_bits(L) * M + 8 * (size_t)S, 16) + 2 * (size_t)S * sizeof(int32_t);
+}
+
+static int vq_index_shape_check(const char* who, int M, int L, int S) {
+  JPDSE_REQUIRE(L >= 2 && L <= 512, "%s: n_center L = %d (2 .. 512)", who, L);
+  JPDSE_REQUIRE(M >= 1, "%s: M = %d indices (at least 1)", who, M);
+  JPDSE_REQUIRE(S >= 1 && S <= 65535 && S <= M, "%s: S = %d streams (1 .. min(M, 65535), M = %d)", who, S, M);
+  JPDSE_REQUIRE(vq_index_in_limits(M, L, S), "%s: M * nb = %lld or the capacity %lld (both below 2^31)", who,
+                (long long)vq_index_bits(L) * M, (long long)vq_index_bits(L) * M + 12LL * S);
+  return JPDSE_OK;
+}
+
+int vq_index_encode_check(const jpdse_vq_index_encode_args* a) {
+  JPDSE_REQUIRE(a != nullptr, "vq_index_encode: null argument struct");
+  if (int rc = vq_index_shape_check("vq_index_encode", a->M, a->L, a->S)) return rc;
+  JPDSE_REQUIRE(a->index && a->out && a->size && a->status, "vq_index_encode: null pointer");
+  const long long cap = vq_index_capacity_bytes(a->M, a->L, a->S);
+  JPDSE_REQUIRE(a->out_bytes >= cap, "vq_index_encode: output of %lld bytes below the payload capacity %lld",
+                (long long)a->out_bytes, cap);
+  const size_t need = vq_index_workspace_bytes(a->M, a->L, a->S);
+  JPDSE_REQUIRE(a->ws != nullptr && a->ws_bytes >= need, "vq_index_encode: workspace too small (%zu bytes, %zu needed)",
+                a->ws ? a->ws_bytes : (size_t)0, need);
+  return JPDSE_OK;
+}
+
+int vq_index_decode_check(const jpdse_vq_index_decode_args* a) {
+  JPDSE_REQUIRE(a != nullptr, "vq_index_decode: null argument struct");
+  if (int rc = vq_index_shape_check("vq_index_decode", a->M, a->L, a->S)) return rc;
+  JPDSE_REQUIRE(a->in && a->index && a->status, "vq_index_decode: null pointer");
+  JPDSE_REQUIRE(a->in_bytes >= 4LL * a->S && a->in_bytes < (1LL << 31),
+                "vq_index_decode: payload of %lld bytes, outside [%d (its length table), 2^31)", (long long)a->in_bytes, 4 * a->S);
+  return JPDSE_OK;
+}
+
 // jpdse_code_cost (code_cost.hip): T[v] = round(-log2(v / 2048) * 2^16) for v in 1 .. 2047, T[0] = T[2048] = 0 (a probability
 // never leaves [31, 2017]: neither end is ever looked up).  fp64 on the host; v / 2048 is exact.
 const uint32_t* code_cost_table_host() {

@@ -35,6 +35,14 @@ int vq_argmax_check(const jpdse_vq_argmax_args* a);
 int vq_pmf_check(const jpdse_vq_pmf_args* a);
 int vq_pmf_bwd_check(const jpdse_vq_pmf_bwd_args* a);
 
+// the same for the jpdse_vq_index_* calls (api.cpp; kernels: vq_coder.hip).  vq_index_bits: the decisions per
+// symbol; the two sizes are 0 outside the limits 2 <= L <= 512, 1 <= S <= min(M, 65535), M * nb and the capacity below 2^31.
+int vq_index_bits(int L);
+long long vq_index_capacity_bytes(int M, int L, int S);
+size_t vq_index_workspace_bytes(int M, int L, int S);
+int vq_index_encode_check(const jpdse_vq_index_encode_args* a);
+int vq_index_decode_check(const jpdse_vq_index_decode_args* a);
+
 // the cost table of jpdse_code_cost_table (api.cpp): 2049 entries, built once on the host in fp64
 const uint32_t* code_cost_table_host();
 

@@ -135,6 +135,19 @@ class VqPmfBwdArgs(ctypes.Structure):
               ('stream', ctypes.c_void_p)]
 
 
+# the jpdse_vq_index_* calls (vq_coder.hip)
+class VqIndexEncodeArgs(ctypes.Structure):
+  _fields_ = [(n, ctypes.c_int32) for n in ('M', 'L', 'S')] + \
+             [('index', ctypes.c_void_p), ('out', ctypes.c_void_p), ('out_bytes', ctypes.c_int64), ('size', ctypes.c_void_p),
+              ('status', ctypes.c_void_p), ('ws', ctypes.c_void_p), ('ws_bytes', ctypes.c_size_t), ('stream', ctypes.c_void_p)]
+
+
+class VqIndexDecodeArgs(ctypes.Structure):
+  _fields_ = [(n, ctypes.c_int32) for n in ('M', 'L', 'S')] + \
+             [('in_', ctypes.c_void_p), ('in_bytes', ctypes.c_int64), ('index', ctypes.c_void_p), ('status', ctypes.c_void_p),
+              ('stream', ctypes.c_void_p)]
+
+
 _P, _I32, _I64, _F, _SZ = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float,
                            ctypes.c_size_t)
 _CD, _ND = ctypes.POINTER(ConvDesc), ctypes.POINTER(InormDesc)
@@ -249,6 +262,10 @@ SIGNATURES = {
     'jpdse_vq_argmax': (_I32, [ctypes.POINTER(VqArgmaxArgs)]),
     'jpdse_vq_pmf': (_I32, [ctypes.POINTER(VqPmfArgs)]),
     'jpdse_vq_pmf_bwd': (_I32, [ctypes.POINTER(VqPmfBwdArgs)]),
+    'jpdse_vq_index_capacity': (_SZ, [_I32, _I32, _I32]),
+    'jpdse_vq_index_workspace_size': (_SZ, [_I32, _I32, _I32]),
+    'jpdse_vq_index_encode': (_I32, [ctypes.POINTER(VqIndexEncodeArgs)]),
+    'jpdse_vq_index_decode': (_I32, [ctypes.POINTER(VqIndexDecodeArgs)]),
 }
 
 # the developer build (same sources, -DJPDSE_DEV): the shipped ABI plus include/jpdse_dev.h

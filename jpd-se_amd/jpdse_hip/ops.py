@@ -10,7 +10,8 @@ import struct
 import torch
 
 from . import (lib, check, JpdseError, F32, BF16, ConvDesc, InormDesc, EvalMetricsSemArgs, MsssimLossArgs, CodeRateArgs, SemLossArgs, CodeCostArgs, ACT_NONE, PAD_ZERO, PAD_REFLECT)
-from . import (VqSoftFwdArgs, VqHardFwdArgs, VqSoftBwdArgs, VqDecodeArgs, VqDecodeBwdArgs, VqArgmaxArgs, VqPmfArgs, VqPmfBwdArgs)
+from . import (VqSoftFwdArgs, VqHardFwdArgs, VqSoftBwdArgs, VqDecodeArgs, VqDecodeBwdArgs, VqArgmaxArgs, VqPmfArgs, VqPmfBwdArgs,
+               VqIndexEncodeArgs, VqIndexDecodeArgs)
 
 
 def cpad(c):
@@ -1161,3 +1162,78 @@ def vq_pmf_bwd(dpmf, M):
   args = VqPmfBwdArgs(int(M), L, dpmf.data_ptr(), ds.data_ptr(), torch.cuda.current_stream().cuda_stream)
   check(lib().jpdse_vq_pmf_bwd(ctypes.byref(args)), 'vq_pmf_bwd')
   return ds
+
+
+# ---- soft-to-hard vector quantizer: coded index stream (vq_coder.hip; format: DESIGN.md 4.14) -------------------------------
+VQ_INDEX_MAX_S = 65535
+
+
+def vq_index_bits(L):
+  """Binary decisions per symbol of an alphabet of L: max(1, bit_length(L - 1))."""
+  return max(1, (int(L) - 1).bit_length())
+
+
+def _vq_index_shape(who, M, L, S):
+  M, L, S = int(M), int(L), int(S)
+  if not 2 <= L <= VQ_MAX_L:
+    raise ValueError('%s: L = %d, the coder takes 2 .. %d' % (who, L, VQ_MAX_L))
+  if M < 1 or not 1 <= S <= min(M, VQ_INDEX_MAX_S):
+    raise ValueError('%s: M = %d indices in S = %d streams (M >= 1, 1 <= S <= min(M, %d))' % (who, M, S, VQ_INDEX_MAX_S))
+  if vq_index_bits(L) * M + 12 * S >= 1 << 31:
+    raise ValueError('%s: M = %d indices of %d bits in %d streams are beyond the coder\'s limits (capacity below 2^31 bytes)'
+                     % (who, M, vq_index_bits(L), S))
+  return M, L, S
+
+
+def vq_index_encode(index, L, S):
+  """The coded payload of the device int32 [M] indices, all in [0, L), in S interleaved streams (jpdse_vq_index_encode):
+  `bytes` holding the S little-endian uint32 stream lengths and the S streams.  One device buffer -- the size, the status
+  word, then the payload at its capacity -- is copied to the host once.  ValueError for an index outside [0, L) (status
+  bit 1), JpdseError if a stream outgrew its derived capacity (bit 0)."""
+  assert index.dim() == 1 and index.is_cuda, (tuple(index.shape), index.device)
+  M, L, S = _vq_index_shape('vq_index_encode', index.numel(), L, S)
+  dev = index.device
+  _vq_index(index, M, dev)
+  lb = lib()
+  cap, n_ws = lb.jpdse_vq_index_capacity(M, L, S), lb.jpdse_vq_index_workspace_size(M, L, S)
+  assert cap == vq_index_bits(L) * M + 12 * S and n_ws > 0, (cap, n_ws)
+  head = 16
+  buf = torch.empty(head + cap, dtype=torch.uint8, device=dev)
+  meta = buf[:8].view(torch.int32)
+  ws = workspace(n_ws, dev)
+  args = VqIndexEncodeArgs(M, L, S, index.data_ptr(), buf[head:].data_ptr(), cap, meta[0:].data_ptr(), meta[1:].data_ptr(),
+                           ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+  check(lb.jpdse_vq_index_encode(ctypes.byref(args)), 'vq_index_encode')
+  host = buf.cpu().numpy()
+  size, status = (int(v) for v in host[:8].view('<i4'))
+  if status & 2:
+    raise ValueError('vq_index_encode: an index outside [0, %d)' % L)
+  if status & 1:
+    raise JpdseError('vq_index_encode: a stream outgrew its slot of nb * count + 8 bytes (status %d)' % status)
+  return host[head:head + size].tobytes()
+
+
+def vq_index_decode(payload, M, L, S, device=None):
+  """The inverse (jpdse_vq_index_decode): a payload as vq_index_encode returns it -> the int32 [M] indices on `device`
+  (default: the current device).  ValueError before any library call for a payload that is not `bytes` or whose table of S
+  lengths does not add up to the bytes that follow it; ValueError after the decode when a decoded value was >= L (status
+  bit 1: the bytes are not a coded stream of this alphabet)."""
+  M, L, S = _vq_index_shape('vq_index_decode', M, L, S)
+  if not isinstance(payload, (bytes, bytearray)):
+    raise ValueError('vq_index_decode: the payload is %s, not bytes' % type(payload).__name__)
+  check_length_table(payload, S, 'vq_index_decode')
+  if len(payload) >= 1 << 31:
+    raise ValueError('vq_index_decode: a payload of %d bytes' % len(payload))
+  dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+  if dev.type != 'cuda':
+    raise JpdseError('vq_index_decode: device %s: the JPD-SE HIP path has no CPU fallback' % (dev,))
+  src = torch.frombuffer(bytearray(payload), dtype=torch.uint8).to(dev)
+  index = torch.empty(M, dtype=torch.int32, device=dev)
+  status = torch.zeros(1, dtype=torch.int32, device=dev)
+  with torch.cuda.device(dev):
+    args = VqIndexDecodeArgs(M, L, S, src.data_ptr(), len(payload), index.data_ptr(), status.data_ptr(),
+                             torch.cuda.current_stream().cuda_stream)
+    check(lib().jpdse_vq_index_decode(ctypes.byref(args)), 'vq_index_decode')
+  if int(status.item()) & 2:
+    raise ValueError('vq_index_decode: a decoded value outside [0, %d): not a coded stream of this alphabet' % L)
+  return index
