@@ -816,6 +816,55 @@ typedef struct jpdse_vq_index_decode_args {
 } jpdse_vq_index_decode_args;
 int jpdse_vq_index_decode(const jpdse_vq_index_decode_args* args);
 
+/* ---- vector-quantizer bottleneck: quantize in one call, [M][L] never in memory (vq_bottleneck.hip) ---------
+ * The quantizer above as a layer: features in, features out.  x, y, dy, dx: row-major [M][D] in `dtype`; code_book: fp32
+ * [L][D]; d[m][k] and p[m][k] as defined above (the direct score, j ascending; the row minimum subtracted, the entry at the
+ * minimum exactly 1 before the division).
+ *   quantize_fwd  index[m] = the k of the smallest d[m][k], the LOWEST k on a tie, a NaN never wins (a row of NaNs: 0)
+ *                 y[m]     = c[index[m]] when hard_forward: a bit-exact gather, rounded to nearest-even for bf16; otherwise
+ *                            y[m][j] = sum_k p[m][k] c[k][j], k ascending (the division by the row sum applied to the sum)
+ *                 pmf[k]   = (sum_m p[m][k]) / M when the pointer is given: fp32 sums per block (m ascending inside a tile's
+ *                            parts, parts and tiles in order), merged in block order in fp64
+ *   quantize_bwd  the gradient of the SOFT form whatever hard_forward was (straight-through); p is recomputed from x
+ *                 dp[m][k] = <dy[m], c[k]> + dpmf[k] / M (dpmf may be NULL: no second term)
+ *                 g = p (dp - <p, dp>), dd = -sigma g
+ *                 dx[m][j] = 2 sum_k dd[m][k] (x[m][j] - c[k][j]), k ascending, in `dtype`
+ *                 dcode_book[k][j] = sum_m (p[m][k] dy[m][j] - 2 dd[m][k] (x[m][j] - c[k][j])): fp32 partials per block, merged
+ *                 in block order.  dx or dcode_book may be NULL
+ * No atomics; grids and orders of summation depend on (M, D, L) alone: two calls give identical bits.  ws:
+ * jpdse_vq_quantize_workspace_size(M, D, L) bytes (host only; 0 outside the limits), read only with a pmf or a dcode_book.
+ * JPDSE_EINVAL before any launch: the limits and refusals of the quantizer above (D 1 .. 32, L 2 .. 512, M >= 1, M * L < 2^31,
+ * sigma finite and positive, NULL args or required pointer, bad dtype, workspace missing or too small). */
+size_t jpdse_vq_quantize_workspace_size(int32_t M, int32_t D, int32_t L);
+typedef struct jpdse_vq_quantize_fwd_args {
+  int32_t dtype, M, D, L;
+  float sigma;
+  int32_t hard_forward;
+  const void* x;
+  const float* code_book;
+  void* y;                 /* [M][D] in `dtype` */
+  int32_t* index;          /* [M] */
+  float* pmf;              /* [L], or NULL */
+  void* ws;
+  size_t ws_bytes;
+  void* stream;
+} jpdse_vq_quantize_fwd_args;
+int jpdse_vq_quantize_fwd(const jpdse_vq_quantize_fwd_args* args);
+typedef struct jpdse_vq_quantize_bwd_args {
+  int32_t dtype, M, D, L;
+  float sigma;
+  const void* dy;          /* [M][D] in `dtype` */
+  const void* x;
+  const float* code_book;
+  const float* dpmf;       /* [L], or NULL */
+  void* dx;                /* [M][D] in `dtype`, or NULL */
+  float* dcode_book;       /* [L][D], or NULL */
+  void* ws;
+  size_t ws_bytes;
+  void* stream;
+} jpdse_vq_quantize_bwd_args;
+int jpdse_vq_quantize_bwd(const jpdse_vq_quantize_bwd_args* args);
+
 /* ---- optimizer ---------------------------------------------------------------------- */
 /* torch.optim.Adam (model.py:275,279) over a table of tensors, one launch.  `table` is a
  * device array of jpdse_adam_entry; bias corrections are computed from `step` (1-based). */

@@ -1,0 +1,457 @@
+// The soft-to-hard vector quantizer as a bottleneck: features in, features out, the [M][L] assignment never in HBM.
+// Entry points: include/jpdse.h, "vector-quantizer bottleneck"; definition, reduction orders and measurements: DESIGN.md 4.15.
+//   d[m][k] and p[m][k] are those of vq.hip: the direct score, j ascending; p with the row minimum subtracted
+//   and the entry at the minimum exactly 1 before the division.
+// Kernels (one THREAD per vector: x[m] lives in DP registers, DP = the power of two >= D in {4, 8, 16, 32}, padded with zeros):
+//   vqb_fwd_kernel   sweep 1 over k: minimum and arg-min (strict <: the lowest k keeps a tie, a NaN never wins);
+//                    sweep 2 (soft forward, or a pmf): e[k] = exp(-sigma (d - dmin)), s = sum e, a[j] = sum e[k] c[k][j], k ascending;
+//                    y = a / s, or the gathered centre.  A pmf takes a third pass in chunks of KC centres: the tile's p = e / s goes
+//                    to LDS, thread (k, part) sums its share of the tile's vectors ascending, the parts are added in order by one
+//                    owner per k into the block's own fp32 partial.
+//   vqb_bwd_kernel   p is recomputed from x: sweep 1 the minimum, sweep 2 s and sum e[k] dp[k] (dp[k] = <dy, c[k]> + dpmf[k] / M), sweep 3
+//                    in chunks of KC centres: dd = -sigma p (dp - <p, dp>), dx += dd (x - c[k]) in registers; with a code-book
+//                    gradient the chunk's p and dd go to LDS and thread ((k, j), part) sums p dy - 2 dd (x - c) over its share of the
+//                    tile's vectors ascending, parts added in order into the block's fp32 partial [L][D].
+//   vqb_merge_kernel / vqb_pmf_final_kernel   the partials in block order: fp32 for dC, fp64 for the pmf.
+// The code book sits in LDS as [L][DP] (zero padded: every lane reads the same word, a broadcast, and the padded components add
+// exact zeros) when that is at most 8 KiB; a larger one is read from global memory at wave-uniform addresses.
+// No atomics; grids, tiles and chunks are functions of (M, D, L) alone; LDS per block below 64 KiB.
+#include <math.h>
+
+#include <initializer_list>
+#include <type_traits>
+
+#include "common.h"
+
+namespace jpdse {
+
+constexpr int kVqbBlocks = 1024;         // cap of the blocks (= fp32 partials) of either kernel
+constexpr int kVqbChunk = 16;            // centres per LDS chunk
+constexpr int kVqbCbLdsBytes = 8192;     // a padded code book up to this size is staged in LDS
+
+// ---- launch geometry: functions of (M, D, L) alone -------------------------------------------------------------------------
+static inline int vqb_dp(int D) { return D <= 4 ? 4 : (D <= 8 ? 8 : (D <= 16 ? 16 : 32)); }
+static inline int vqb_bwd_threads(int D) { return D <= 8 ? 256 : (D <= 16 ? 128 : 64); }   // = vectors per tile
+static inline int vqb_chunk(int L) { return L < kVqbChunk ? L : kVqbChunk; }
+static inline bool vqb_cb_lds(int D, int L) { return (size_t)L * vqb_dp(D) * sizeof(float) <= (size_t)kVqbCbLdsBytes; }
+static inline int vqb_blocks(int M, int V) {
+  const int tiles = (M + V - 1) / V;
+  return tiles < kVqbBlocks ? tiles : kVqbBlocks;
+}
+static inline size_t vqb_workspace_bytes(int M, int D, int L) {
+  const size_t fwd = (size_t)vqb_blocks(M, 256) * L * sizeof(float);
+  const size_t bwd = (size_t)vqb_blocks(M, vqb_bwd_threads(D)) * L * D * sizeof(float);
+  return fwd > bwd ? fwd : bwd;
+}
+static inline size_t vqb_fwd_lds(int D, int L, bool pmf) {
+  size_t n = vqb_cb_lds(D, L) ? (size_t)L * vqb_dp(D) : 0;
+  if (pmf) n += (size_t)vqb_chunk(L) * 257 + 256;
+  return n * sizeof(float);
+}
+static inline size_t vqb_bwd_lds(int D, int L, bool dc) {
+  const int V = vqb_bwd_threads(D), KC = vqb_chunk(L);
+  size_t n = (vqb_cb_lds(D, L) ? (size_t)L * vqb_dp(D) : 0) + L;
+  if (dc) n += 2 * (size_t)KC * (V + 1) + 2 * (size_t)V * D + (size_t)(KC * D > V ? KC * D : V);
+  return n * sizeof(float);
+}
+
+// ---- device helpers ---------------------------------------------------------------------------------------------------------
+// c [L][D] (global) -> cb [L][DP] (LDS), components D .. DP - 1 zero; the caller synchronises
+__device__ __forceinline__ void vqb_stage(const float* __restrict__ c, float* cb, int D, int L, int DP) {
+  for (int i = threadIdx.x; i < L * DP; i += blockDim.x) {
+    const int k = i / DP, j = i - k * DP;
+    cb[i] = j < D ? c[k * D + j] : 0.f;
+  }
+}
+
+// a vector's D components into DP registers (zeros beyond D); vec: 16-byte accesses (D == DP, rows and base 16-byte aligned)
+template <typename T, int DP>
+__device__ __forceinline__ void vqb_load_row(const T* __restrict__ p, int D, bool vec, float (&r)[DP]) {
+  constexpr int N = Vec16<T>::N;
+  if constexpr (DP % N == 0) {
+    if (vec) {
+#pragma unroll
+      for (int i = 0; i < DP; i += N) {
+        float t[N];
+        Vec16<T>::load(p + i, t);
+#pragma unroll
+        for (int u = 0; u < N; ++u) r[i + u] = t[u];
+      }
+      return;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < DP; ++j) r[j] = j < D ? ElemOps<T>::ld(p + j) : 0.f;
+}
+
+template <typename T, int DP>
+__device__ __forceinline__ void vqb_store_row(T* __restrict__ p, int D, bool vec, const float (&r)[DP]) {
+  constexpr int N = Vec16<T>::N;
+  if constexpr (DP % N == 0) {
+    if (vec) {
+#pragma unroll
+      for (int i = 0; i < DP; i += N) {
+        float t[N];
+#pragma unroll
+        for (int u = 0; u < N; ++u) t[u] = r[i + u];
+        Vec16<T>::store(p + i, t);
+      }
+      return;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < DP; ++j)
+    if (j < D) ElemOps<T>::st(p + j, r[j]);
+}
+
+// d = sum_j (x[j] - ck[j])^2, j ascending, one fused multiply-add per component: the same bits in every sweep.  PAD: ck is a
+// zero-padded LDS row of DP words; otherwise a global row of D words
+template <int DP, bool PAD>
+__device__ __forceinline__ float vqb_score(const float (&x)[DP], const float* ck, int D) {
+  float d = 0.f;
+#pragma unroll
+  for (int j = 0; j < DP; ++j)
+    if (PAD || j < D) {
+      const float t = x[j] - ck[j];
+      d = __fmaf_rn(t, t, d);
+    }
+  return d;
+}
+
+template <int DP, bool PAD>
+__device__ __forceinline__ float vqb_dot(const float (&g)[DP], const float* ck, int D) {
+  float q = 0.f;
+#pragma unroll
+  for (int j = 0; j < DP; ++j)
+    if (PAD || j < D) q = __fmaf_rn(g[j], ck[j], q);
+  return q;
+}
+
+// d == dmin: exp(0) = 1 without forming inf - inf when every score overflowed
+__device__ __forceinline__ float vqb_weight(float d, float dmin, float sigma) {
+  return d == dmin ? 1.f : expf(-sigma * (d - dmin));
+}
+
+// ---- forward ----------------------------------------------------------------------------------------------------------------
+// LDS: cb [L][DP] when CBL | pt [KC][257] | red [256] with a pmf.  partial: this block's [L] sums of p, or nullptr.
+template <typename T, int DP, bool CBL>
+__global__ __launch_bounds__(256) void vqb_fwd_kernel(const T* __restrict__ x, const float* __restrict__ c, int M, int D, int L,
+                                                     float sigma, int hard, int vec, T* __restrict__ y, int* __restrict__ index,
+                                                     float* __restrict__ partial) {
+  extern __shared__ float vqb_lds[];
+  constexpr int V = 256;
+  const int KC = L < kVqbChunk ? L : kVqbChunk;
+  float* pt = vqb_lds + (CBL ? L * DP : 0);
+  float* red = pt + KC * (V + 1);
+  if (CBL) {
+    vqb_stage(c, vqb_lds, D, L, DP);
+    __syncthreads();
+  }
+  const float* cc = CBL ? vqb_lds : c;
+  const int ld = CBL ? DP : D;
+  const int t = threadIdx.x;
+  const int ntiles = (M + V - 1) / V;
+  float* mine = partial != nullptr ? partial + (size_t)blockIdx.x * L : nullptr;
+  bool first = true;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int m0 = tile * V;
+    const int nv = M - m0 < V ? M - m0 : V;
+    const bool live = t < nv;
+    const size_t row = (size_t)(m0 + t) * D;
+    float xr[DP];
+#pragma unroll
+    for (int j = 0; j < DP; ++j) xr[j] = 0.f;
+    if (live) vqb_load_row<T, DP>(x + row, D, vec != 0, xr);
+    float dmin = INFINITY;
+    int bk = 0;
+    for (int k = 0; k < L; ++k) {
+      const float d = vqb_score<DP, CBL>(xr, cc + k * ld, D);
+      if (d < dmin) {                          // strict: the lower index keeps a tie; a NaN never wins
+        dmin = d;
+        bk = k;
+      }
+    }
+    float s = 1.f;
+    float a[DP];
+    if (!hard || mine != nullptr) {
+      s = 0.f;
+#pragma unroll
+      for (int j = 0; j < DP; ++j) a[j] = 0.f;
+      for (int k = 0; k < L; ++k) {
+        const float* ck = cc + k * ld;
+        const float e = vqb_weight(vqb_score<DP, CBL>(xr, ck, D), dmin, sigma);
+        s += e;
+#pragma unroll
+        for (int j = 0; j < DP; ++j)
+          if (CBL || j < D) a[j] = __fmaf_rn(e, ck[j], a[j]);
+      }
+    }
+    if (live) {
+      index[m0 + t] = bk;
+      if (hard) {
+        const float* ck = cc + bk * ld;
+#pragma unroll
+        for (int j = 0; j < DP; ++j) a[j] = (CBL || j < D) ? ck[j] : 0.f;
+      } else {
+#pragma unroll
+        for (int j = 0; j < DP; ++j) a[j] = a[j] / s;
+      }
+      vqb_store_row<T, DP>(y + row, D, vec != 0, a);
+    }
+    if (mine != nullptr) {
+      const int parts = V / KC, span = (V + parts - 1) / parts;
+      for (int k0 = 0; k0 < L; k0 += KC) {
+        const int kc = L - k0 < KC ? L - k0 : KC;
+        if (live)
+          for (int kk = 0; kk < kc; ++kk)
+            pt[kk * (V + 1) + t] = vqb_weight(vqb_score<DP, CBL>(xr, cc + (k0 + kk) * ld, D), dmin, sigma) / s;
+        __syncthreads();
+        {
+          const int kk = t % KC, part = t / KC;
+          if (part < parts && kk < kc) {
+            const int v1 = (part + 1) * span < nv ? (part + 1) * span : nv;
+            float acc = 0.f;
+            for (int v = part * span; v < v1; ++v) acc += pt[kk * (V + 1) + v];
+            red[part * KC + kk] = acc;
+          }
+        }
+        __syncthreads();
+        if (t < kc) {
+          float acc = 0.f;
+          for (int part = 0; part < parts; ++part) acc += red[part * KC + t];
+          mine[k0 + t] = first ? acc : mine[k0 + t] + acc;
+        }
+      }
+    }
+    first = false;
+  }
+}
+
+// pmf[k] = (sum_b partial[b][k]) / M, b ascending, in fp64
+__global__ __launch_bounds__(256) void vqb_pmf_final_kernel(const float* __restrict__ partial, int nb, int L, double count,
+                                                           float* __restrict__ pmf) {
+  for (int k = threadIdx.x; k < L; k += 256) {
+    double acc = 0.0;
+    for (int b = 0; b < nb; ++b) acc += (double)partial[(size_t)b * L + k];
+    pmf[k] = (float)(acc / count);
+  }
+}
+
+// out[i] = sum_b partial[b][i], b ascending
+__global__ __launch_bounds__(256) void vqb_merge_kernel(const float* __restrict__ partial, int nb, int n, float* __restrict__ out) {
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    float acc = 0.f;
+    for (int b = 0; b < nb; ++b) acc += partial[(size_t)b * n + i];
+    out[i] = acc;
+  }
+}
+
+// ---- backward ---------------------------------------------------------------------------------------------------------------
+// blockDim.x = V vectors per tile.  LDS: cb [L][DP] when CBL | dq [L] = dpmf / M | with a partial: pt, ddt [KC][V + 1] | xt, dyt
+// [V][D] | red [max(V, KC D)].  partial: this block's [L][D] sums, or nullptr: no code-book gradient.
+template <typename T, int DP, bool CBL>
+__global__ __launch_bounds__(256) void vqb_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x, const float* __restrict__ c,
+                                                     const float* __restrict__ dpmf, int M, int D, int L, float sigma, int vec,
+                                                     T* __restrict__ dx, float* __restrict__ partial) {
+  extern __shared__ float vqb_lds[];
+  const int V = blockDim.x;
+  const int KC = L < kVqbChunk ? L : kVqbChunk;
+  float* dq = vqb_lds + (CBL ? L * DP : 0);
+  float* pt = dq + L;
+  float* ddt = pt + KC * (V + 1);
+  float* xt = ddt + KC * (V + 1);
+  float* dyt = xt + V * D;
+  float* red = dyt + V * D;
+  if (CBL) vqb_stage(c, vqb_lds, D, L, DP);
+  for (int k = threadIdx.x; k < L; k += V) dq[k] = dpmf != nullptr ? dpmf[k] / (float)M : 0.f;
+  __syncthreads();
+  const float* cc = CBL ? vqb_lds : c;
+  const int ld = CBL ? DP : D;
+  const int t = threadIdx.x;
+  const int ntiles = (M + V - 1) / V;
+  float* mine = partial != nullptr ? partial + (size_t)blockIdx.x * L * D : nullptr;
+  const int parts = V / (KC * D) > 1 ? V / (KC * D) : 1, span = (V + parts - 1) / parts;
+  bool first = true;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int m0 = tile * V;
+    const int nv = M - m0 < V ? M - m0 : V;
+    const bool live = t < nv;
+    const size_t row = (size_t)(m0 + t) * D;
+    float xr[DP], gr[DP], dxr[DP];
+#pragma unroll
+    for (int j = 0; j < DP; ++j) xr[j] = gr[j] = dxr[j] = 0.f;
+    if (live) {
+      vqb_load_row<T, DP>(x + row, D, vec != 0, xr);
+      vqb_load_row<T, DP>(dy + row, D, vec != 0, gr);
+    }
+    float dmin = INFINITY;
+    for (int k = 0; k < L; ++k) {
+      const float d = vqb_score<DP, CBL>(xr, cc + k * ld, D);
+      if (d < dmin) dmin = d;
+    }
+    float s = 0.f, pd = 0.f;
+    for (int k = 0; k < L; ++k) {
+      const float* ck = cc + k * ld;
+      const float e = vqb_weight(vqb_score<DP, CBL>(xr, ck, D), dmin, sigma);
+      const float q = vqb_dot<DP, CBL>(gr, ck, D) + dq[k];
+      s += e;
+      pd = __fmaf_rn(e, q, pd);
+    }
+    pd = pd / s;                               // <p, dp>
+    if (mine != nullptr && live) {
+#pragma unroll
+      for (int j = 0; j < DP; ++j)
+        if (j < D) {
+          xt[t * D + j] = xr[j];
+          dyt[t * D + j] = gr[j];
+        }
+    }
+    for (int k0 = 0; k0 < L; k0 += KC) {
+      const int kc = L - k0 < KC ? L - k0 : KC;
+      for (int kk = 0; kk < kc; ++kk) {
+        const float* ck = cc + (k0 + kk) * ld;
+        const float p = vqb_weight(vqb_score<DP, CBL>(xr, ck, D), dmin, sigma) / s;
+        const float q = vqb_dot<DP, CBL>(gr, ck, D) + dq[k0 + kk];
+        const float dd = -sigma * (p * (q - pd));
+#pragma unroll
+        for (int j = 0; j < DP; ++j)
+          if (CBL || j < D) dxr[j] = __fmaf_rn(dd, xr[j] - ck[j], dxr[j]);
+        if (mine != nullptr && live) {
+          pt[kk * (V + 1) + t] = p;
+          ddt[kk * (V + 1) + t] = dd;
+        }
+      }
+      if (mine != nullptr) {
+        const int nown = kc * D;
+        __syncthreads();
+        for (int w = t; w < nown * parts; w += V) {
+          const int part = w / nown, q = w - part * nown;
+          const int kk = q / D, j = q - kk * D;
+          const float ck = cc[(k0 + kk) * ld + j];
+          const int v1 = (part + 1) * span < nv ? (part + 1) * span : nv;
+          const float* pr = pt + kk * (V + 1);
+          const float* dr = ddt + kk * (V + 1);
+          float acc = 0.f;
+          for (int v = part * span; v < v1; ++v) acc += pr[v] * dyt[v * D + j] - 2.f * (dr[v] * (xt[v * D + j] - ck));
+          red[w] = acc;
+        }
+        __syncthreads();
+        for (int q = t; q < nown; q += V) {
+          float acc = 0.f;
+          for (int part = 0; part < parts; ++part) acc += red[part * nown + q];
+          mine[k0 * D + q] = first ? acc : mine[k0 * D + q] + acc;
+        }
+      }
+    }
+    if (live && dx != nullptr) {
+#pragma unroll
+      for (int j = 0; j < DP; ++j) dxr[j] = 2.f * dxr[j];
+      vqb_store_row<T, DP>(dx + row, D, vec != 0, dxr);
+    }
+    first = false;
+    if (mine != nullptr) __syncthreads();      // the tile's xt / dyt / red are free again
+  }
+}
+
+template <typename... P, typename... A>
+static inline int vqb_launch(const char* what, void (*kernel)(P...), int grid, int threads, size_t lds, void* stream, A... args) {
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, as_stream(stream), static_cast<P>(args)...);
+  return check_launch(what);
+}
+
+// f(tag of T, DP as an integral constant, CBL as an integral constant)
+template <typename F>
+static inline int vqb_dispatch(int dtype, int D, int L, F&& f) {
+  return by_dtype(dtype, [&](auto tag) {
+    auto with_dp = [&](auto dp) {
+      return vqb_cb_lds(D, L) ? f(tag, dp, std::true_type{}) : f(tag, dp, std::false_type{});
+    };
+    switch (vqb_dp(D)) {
+      case 4: return with_dp(std::integral_constant<int, 4>{});
+      case 8: return with_dp(std::integral_constant<int, 8>{});
+      case 16: return with_dp(std::integral_constant<int, 16>{});
+      default: return with_dp(std::integral_constant<int, 32>{});
+    }
+  });
+}
+
+// 16-byte accesses of a row: D fills its registers, a row is a whole number of 16-byte words, every base is aligned
+static inline int vqb_vec(int dtype, int D, std::initializer_list<const void*> ptrs) {
+  if (D != vqb_dp(D) || (D * esize(dtype)) % 16 != 0) return 0;
+  for (const void* p : ptrs)
+    if (p != nullptr && reinterpret_cast<uintptr_t>(p) % 16 != 0) return 0;
+  return 1;
+}
+
+static int vqb_common_check(const char* who, int dtype, int M, int D, int L, float sigma) {
+  JPDSE_REQUIRE(!bad_dtype(dtype), "%s: bad dtype %d", who, dtype);
+  if (int rc = vq_shape_check(who, M, D, L)) return rc;
+  JPDSE_REQUIRE(isfinite(sigma) && sigma > 0.f, "%s: sigma is %g (a finite value > 0)", who, (double)sigma);
+  return JPDSE_OK;
+}
+
+}  // namespace jpdse
+
+using namespace jpdse;
+
+extern "C" {
+
+size_t jpdse_vq_quantize_workspace_size(int32_t M, int32_t D, int32_t L) {
+  if (vq_shape_check("vq_quantize_workspace_size", M, D, L) != JPDSE_OK) return 0;
+  return vqb_workspace_bytes(M, D, L);
+}
+
+int jpdse_vq_quantize_fwd(const jpdse_vq_quantize_fwd_args* a) {
+  JPDSE_REQUIRE(a != nullptr, "vq_quantize_fwd: null argument struct");
+  if (int rc = vqb_common_check("vq_quantize_fwd", a->dtype, a->M, a->D, a->L, a->sigma)) return rc;
+  JPDSE_REQUIRE(a->x && a->code_book && a->y && a->index, "vq_quantize_fwd: null pointer");
+  const int M = a->M, D = a->D, L = a->L;
+  const int nb = vqb_blocks(M, 256);
+  float* partial = nullptr;
+  if (a->pmf != nullptr) {
+    const size_t need = vqb_workspace_bytes(M, D, L);
+    JPDSE_REQUIRE(a->ws != nullptr && a->ws_bytes >= need, "vq_quantize_fwd: workspace too small (%zu bytes, %zu needed)",
+                  a->ws ? a->ws_bytes : (size_t)0, need);
+    partial = mptr<float>(a->ws);
+  }
+  const int vec = vqb_vec(a->dtype, D, {a->x, a->y});
+  const size_t lds = vqb_fwd_lds(D, L, partial != nullptr);
+  if (int rc = vqb_dispatch(a->dtype, D, L, [&](auto tag, auto dp, auto cbl) {
+        using T = decltype(tag);
+        return vqb_launch("vq_quantize_fwd", vqb_fwd_kernel<T, decltype(dp)::value, decltype(cbl)::value>, nb, 256, lds, a->stream,
+                          cptr<T>(a->x), a->code_book, M, D, L, a->sigma, a->hard_forward != 0 ? 1 : 0, vec, mptr<T>(a->y),
+                          a->index, partial);
+      }))
+    return rc;
+  if (partial == nullptr) return JPDSE_OK;
+  return vqb_launch("vq_quantize_fwd(pmf)", vqb_pmf_final_kernel, 1, 256, 0, a->stream, partial, nb, L, (double)M, a->pmf);
+}
+
+int jpdse_vq_quantize_bwd(const jpdse_vq_quantize_bwd_args* a) {
+  JPDSE_REQUIRE(a != nullptr, "vq_quantize_bwd: null argument struct");
+  if (int rc = vqb_common_check("vq_quantize_bwd", a->dtype, a->M, a->D, a->L, a->sigma)) return rc;
+  JPDSE_REQUIRE(a->dy && a->x && a->code_book, "vq_quantize_bwd: null pointer");
+  const int M = a->M, D = a->D, L = a->L;
+  float* partial = nullptr;
+  if (a->dcode_book != nullptr) {
+    const size_t need = vqb_workspace_bytes(M, D, L);
+    JPDSE_REQUIRE(a->ws != nullptr && a->ws_bytes >= need, "vq_quantize_bwd: workspace too small (%zu bytes, %zu needed)",
+                  a->ws ? a->ws_bytes : (size_t)0, need);
+    partial = mptr<float>(a->ws);
+  }
+  if (a->dx == nullptr && partial == nullptr) return JPDSE_OK;
+  const int V = vqb_bwd_threads(D), nb = vqb_blocks(M, V);
+  const int vec = vqb_vec(a->dtype, D, {a->x, a->dy, a->dx});
+  const size_t lds = vqb_bwd_lds(D, L, partial != nullptr);
+  if (int rc = vqb_dispatch(a->dtype, D, L, [&](auto tag, auto dp, auto cbl) {
+        using T = decltype(tag);
+        return vqb_launch("vq_quantize_bwd", vqb_bwd_kernel<T, decltype(dp)::value, decltype(cbl)::value>, nb, V, lds, a->stream,
+                          cptr<T>(a->dy), cptr<T>(a->x), a->code_book, a->dpmf, M, D, L, a->sigma, vec, mptr<T>(a->dx), partial);
+      }))
+    return rc;
+  if (partial == nullptr) return JPDSE_OK;
+  return vqb_launch("vq_quantize_bwd(merge)", vqb_merge_kernel, ew_blocks(L * D), 256, 0, a->stream, partial, nb, L * D,
+                    a->dcode_book);
+}
+
+}  // extern "C"

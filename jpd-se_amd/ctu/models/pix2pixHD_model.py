@@ -26,7 +26,7 @@ from jpdse_hip import ops
 from jpdse_hip.ops import Act
 from jpdse_hip.optim import FusedAdam
 from jpdse_hip.layers import PackBatcher
-from ctu.utils import bitstream, entropy
+from ctu.utils import bitstream, entropy, vqstream
 from ctu.utils import semantics as semantics_file
 from ctu.utils.image_pool import ImagePool
 from ctu.models.pix2pixHD_networks.base_model import BaseModel
@@ -75,7 +75,8 @@ class Pix2PixHDModel(BaseModel):
     (pinned by tests/golden/option_setter_flags.json, dumped from the reference), so that a reference command line or
     opt.pkl parses unchanged; flags of branches outside the accelerated path are accepted here and refused in
     __init__ when they would change the computation.  Extensions: --compute_dtype, --skip_unused_losses,
-    --vgg19_state_dict, --vgg_random_init, --lambda_rate, --class_distortion_weights, --edge_distortion_weight."""
+    --vgg19_state_dict, --vgg_random_init, --lambda_rate, --class_distortion_weights, --edge_distortion_weight,
+    --encoder_quantizer, --vq_n_center, --vq_center_size, --vq_sigma, --vq_soft_forward."""
     a = parser.add_argument
     a('--num_D', type=int, default=2)
     a('--n_layers_D', type=int, default=3)
@@ -164,6 +165,17 @@ class Pix2PixHDModel(BaseModel):
       help='extension (DESIGN.md 4.11): the distortion of a pixel on an instance edge (its instance id differs from a '
            '4-neighbour\'s; the dataset\'s own map, also under --zero_ins) is multiplied by this on top of its class weight; '
            'same normaliser as --class_distortion_weights (rescale with --lambda_distortion).  1 (default): no edge term')
+    a('--encoder_quantizer', type=str, default='binarizer', choices=['binarizer', 's2hvq'],
+      help='extension (DESIGN.md 4.15): the bottleneck of the feature encoder -- the reference\'s one-bit binarizer (default: '
+           'every run is what it was) or the soft-to-hard vector quantizer over groups of --vq_center_size of the '
+           '--encoder_binarizer_out_channels channels')
+    a('--vq_n_center', type=int, default=64, help='--encoder_quantizer s2hvq: centres of the code book (2 .. 512)')
+    a('--vq_center_size', type=int, default=8,
+      help='--encoder_quantizer s2hvq: channels per vector (1 .. 32); must divide --encoder_binarizer_out_channels')
+    a('--vq_sigma', type=float, default=10.0, help='--encoder_quantizer s2hvq: hardness of the soft assignment')
+    a('--vq_soft_forward', action='store_true',
+      help='--encoder_quantizer s2hvq: train on the soft assignment\'s mix of the centres instead of the nearest centre (the '
+           'gradient is the soft form\'s either way); eval mode always takes the nearest centre')
     a('--vgg_random_init', action='store_true',
       help='extension: explicitly accept a seeded random-weight VGG19 for the VGG loss (tests, benchmarks); without '
            'this flag training with the VGG loss and no --vgg19_state_dict is refused')
@@ -206,6 +218,21 @@ class Pix2PixHDModel(BaseModel):
     if self.lambda_rate > 0.0 and (not feat_enc or g('no_encoder_binarization') or g('zero_vis')):
       raise ValueError('lambda_rate > 0 needs the learned codec with encoder binarization (--no_feat_encoding and '
                        '--no_encoder_binarization must both be off) and an encoder that runs (no --zero_vis)')
+    # vector-quantizer bottleneck: refused combinations before any network (hence any device allocation) exists
+    self.use_vq = False
+    if g('encoder_quantizer', 'binarizer') not in ('binarizer', 's2hvq'):
+      raise ValueError('encoder_quantizer must be binarizer or s2hvq, got %r' % (g('encoder_quantizer'),))
+    if g('encoder_quantizer', 'binarizer') == 's2hvq':
+      if not feat_enc or g('no_encoder_binarization'):
+        raise ValueError('--encoder_quantizer s2hvq needs the learned codec with its bottleneck (--no_feat_encoding and '
+                         '--no_encoder_binarization must both be off)')
+      if self.lambda_rate > 0.0:
+        raise ValueError('--lambda_rate > 0 is the binarizer\'s context-model rate term: it cannot be combined with '
+                         '--encoder_quantizer s2hvq')
+      from jpdse_hip.layers import vq_bottleneck_check
+      vq_bottleneck_check(int(g('encoder_binarizer_out_channels', 128)), int(g('vq_n_center', 64)),
+                          int(g('vq_center_size', 8)), g('vq_sigma', 10.0), '--encoder_quantizer s2hvq')
+      self.use_vq = True
     # semantics-weighted distortion: (class table, edge weight), or None when every weight is 1 -- the
     # step then takes the plain l1 / mse path
     n_onehot = opt.num_labels + 1 if g('contain_dontcare_label') else opt.num_labels
@@ -261,7 +288,10 @@ class Pix2PixHDModel(BaseModel):
                                     norm=opt.norm, gpu_ids=self.gpu_ids,
                                     binarize_encoder=not g('no_encoder_binarization'),
                                     encoder_binarizer_out_channels=g('encoder_binarizer_out_channels', 128),
-                                    encoder_groups=g('netE_groups', 1), compute_dtype=cd)
+                                    encoder_groups=g('netE_groups', 1), compute_dtype=cd,
+                                    encoder_quantizer=g('encoder_quantizer', 'binarizer'), vq_n_center=g('vq_n_center', 64),
+                                    vq_center_size=g('vq_center_size', 8), vq_sigma=g('vq_sigma', 10.0),
+                                    vq_hard_forward=not g('vq_soft_forward'))
     # binarizer noise: Philox key = the run's seed, counter = (element, image index in the global batch,
     # number of training forwards so far)
     self.codec_seed = int(g('seed', None) or 0)
@@ -457,14 +487,17 @@ class Pix2PixHDModel(BaseModel):
     rank = dist.get_rank(group) if dist.is_available() and dist.is_initialized() else 0
     b.seed, b.draw, b.n_global0 = self.codec_seed, self.codec_draw, rank * local_batch
 
-  def _require_binarizer(self):
+  def _require_binarizer(self, who='binary codes'):
+    if getattr(self, 'use_vq', False):
+      raise ValueError('%s: a call of the one-bit binarizer\'s code, not available with --encoder_quantizer s2hvq (its code: '
+                       'get_vq_code / get_coded / get_coded_rate)' % who)
     if self.netE is None or not self.netE.binarize:
       raise ValueError('binary codes need the learned codec with encoder binarization '
                        '(--no_feat_encoding and --no_encoder_binarization must both be off)')
 
-  def _code_act(self, x_dict):
+  def _code_act(self, x_dict, who='binary codes'):
     """The encoder's eval-mode bitstream of x_dict (the decoded frame with --use_compressed) as an NHWC Act."""
-    self._require_binarizer()
+    self._require_binarizer(who)
     pre = self.preprocess(x_dict, build_base=False)
     return self._encoder_eval(lambda: self.netE.code(pre['src']))
 
@@ -472,14 +505,14 @@ class Pix2PixHDModel(BaseModel):
     """[image_code] (model.py:494-505, 557-563): (b + 1) / 2 as fp32 [N, bits] in NCHW flatten order -- or, packed=True
     (extension), the bitstream itself, uint8 [N, ceil(bits / 8)] MSB first."""
     with torch.no_grad():
-      return [ops.code_export(self._code_act(x_dict), packed)]
+      return [ops.code_export(self._code_act(x_dict, 'get_code'), packed)]
 
   def get_context_rate(self, x_dict):
     """The hard-mode rate term of the eval-mode code, batch mean in bits per pixel, a Python float: the code's
     conditional entropy under the static, Laplace-smoothed form of the 4.8 coder's context model, counted on the code itself.
     An estimate that stays below the coded size (no flush, no adaptation cost) -- not a size; get_coded_rate measures files."""
     with torch.no_grad():
-      b = self._code_act(x_dict)
+      b = self._code_act(x_dict, 'get_context_rate')
       pixels = int(x_dict['image'].shape[-2]) * int(x_dict['image'].shape[-1])
       value, _, _, _ = ops.code_rate_loss(b, None, pixels, want_grad=False)
       return float(value.item())
@@ -490,7 +523,7 @@ class Pix2PixHDModel(BaseModel):
     times bits / pixels; nan when p is 0 or 1.  First value a 0-dim float tensor, second a Python float.  p comes from the
     integer per-image counts of jpdse_code_stats (exact: torch.mean's fp32 sum of halves is exact below 2^24 bits)."""
     with torch.no_grad():
-      b = self._code_act(x_dict)
+      b = self._code_act(x_dict, 'get_eval_rate')
       counts = ops.code_stats(b).to(torch.float64)
       bits = b.C * b.H * b.W
       pixels = int(x_dict['image'].shape[-2]) * int(x_dict['image'].shape[-1])
@@ -560,8 +593,51 @@ class Pix2PixHDModel(BaseModel):
                      self.opt.distortion_loss_fn == 'mse', slot)
       return slot[0]
 
+  # ---- the vector-quantised code (extension) ------------------------------------------------------------------
+  def _require_vq(self, who):
+    if not getattr(self, 'use_vq', False):
+      raise ValueError('%s: the vector-quantised code needs --encoder_quantizer s2hvq' % who)
+
+  def _vq_geometry(self, x_dict, who):
+    """(N, H, W, indices per image, n_center, channel groups) from the label map alone; ValueError for a map that is no
+    multiple of the encoder's down-sampling factor."""
+    N, H, W = int(x_dict['label'].shape[0]), int(x_dict['label'].shape[-2]), int(x_dict['label'].shape[-1])
+    step = 1 << self.netE.n_downsampling
+    if H % step or W % step:
+      raise ValueError('%s: a %d x %d label map is no multiple of the encoder\'s down-sampling factor %d' % (who, H, W, step))
+    vq = self.netE._vq
+    return N, H, W, self.netE.vq_code_len(H, W), vq.n_center, vq.cout // vq.center_size
+
+  def get_vq_code(self, x_dict):
+    """The eval-mode code of the vector-quantizer bottleneck: int64 [N, h * w * C / D] on the device, per image the index of
+    the nearest centre of every group of D channels, pixel by pixel, groups ascending inside a pixel."""
+    self._require_vq('get_vq_code')
+    with torch.no_grad():
+      pre = self.preprocess(x_dict, build_base=False)
+      return self._encoder_eval(lambda: self.netE.vq_code(pre['src'])).to(torch.int64)
+
+  def _decode_vq_act(self, code, x_dict, who='decode'):
+    """decode() of a vector-quantised code up to the generator's NHWC output; also returns the device label map."""
+    N, H, W, code_len, L, _ = self._vq_geometry(x_dict, who)
+    if not torch.is_tensor(code) or code.dim() != 2 or code.dtype not in (torch.int64, torch.int32):
+      raise ValueError('%s: the code must be what get_vq_code returns: an int64 [N, indices] tensor' % who)
+    if tuple(code.shape) != (N, code_len):
+      raise ValueError('%s: code of shape %s, but %d label maps of %d x %d carry a code of shape %s'
+                       % (who, tuple(code.shape), N, H, W, (N, code_len)))
+
+    def features():
+      index = code.to(self._device(), non_blocking=True)
+      if bool(((index < 0) | (index >= L)).any()):      # before the cast to int32 could fold a far value into range
+        raise ValueError('%s: an index outside [0, %d)' % (who, L))
+      y, _ = self.netE.decode_vq_code(index.to(torch.int32).contiguous(), H, W)
+      return y
+
+    return self._generate_from_code(None, x_dict, N, H, W, features=features)
+
   def _decode_act(self, code, x_dict):
     """decode() up to the generator's NHWC output; also returns the device label map."""
+    if getattr(self, 'use_vq', False):
+      return self._decode_vq_act(code, x_dict)
     self._require_binarizer()
     if not torch.is_tensor(code) or code.dim() != 2 or code.dtype not in (torch.uint8, torch.float32):
       raise ValueError('decode: the code must be what get_code returns: a uint8 [N, ceil(bits / 8)] or float32 [N, bits] tensor')
@@ -579,12 +655,13 @@ class Pix2PixHDModel(BaseModel):
     return self._generate_from_code(
         lambda: ops.code_import(code.to(self._device(), non_blocking=True), N, h, w, C, self.cdtype), x_dict, N, H, W)
 
-  def _generate_from_code(self, import_b, x_dict, N, H, W):
-    """The receiver's device work, shared by decode and decode_coded: import_b() gives the code Act."""
+  def _generate_from_code(self, import_b, x_dict, N, H, W, features=None):
+    """The receiver's device work, shared by decode and decode_coded: import_b() gives the code Act -- or features() the
+    encoder's output itself (the vector-quantised code)."""
     label, inst = self._semantics(x_dict)
     vis = None                           # --zero_vis: nothing visual reaches the generator, the code is not read
     if not self.zero_vis:
-      vis = self.netE.decode_code(import_b())
+      vis = features() if features is not None else self.netE.decode_code(import_b())
     base = None if self.zero_sem else ops.onehot_edge(label, inst, self.n_onehot, self.label_nc + self.feat_nc, self.cdtype)
     fake, _ = self.netG.fwd(self._g_input_from_vis(vis, base, N, H, W))
     return fake, label
@@ -600,7 +677,9 @@ class Pix2PixHDModel(BaseModel):
     1).  Where the encoder's tanh is exactly 0, get_img feeds sign(0) = 0 forward but the stored bit is 0, so the decoder
     sees -1 there: the stored code, not the tensor get_img used, is what a receiver reconstructs from.
     ValueError without an encoder or a binarizer, and for a code whose size does not fit the label map (before any device
-    work)."""
+    work).
+    With --encoder_quantizer s2hvq the code is what get_vq_code returned, int64 [N, indices]: decode(get_vq_code(x), x)
+    equals get_img(x) bit for bit, with no zero rule -- both sides see code_book[index]."""
     with torch.no_grad():
       fake, _ = self._decode_act(code, x_dict)
       return ops.nhwc_to_nchw(fake)
@@ -610,13 +689,44 @@ class Pix2PixHDModel(BaseModel):
     """The entropy-coded form of get_code(x_dict, packed=True): a list of N `bytes`, per image the C stream lengths and the C
     range-coded streams (ops.code_entropy_encode).  Lossless: decode_coded(get_coded(x), x) equals
     decode(get_code(x, packed=True), x) bit for bit."""
+    if getattr(self, 'use_vq', False):
+      return self._get_coded_vq(x_dict)
     with torch.no_grad():
       return ops.code_entropy_encode(self._code_act(x_dict))
+
+  def _get_coded_vq(self, x_dict):
+    """--encoder_quantizer s2hvq: a list of N .jpdv blobs (ctu.utils.vqstream), one per image, of that image's
+    get_vq_code row in (C / D) * 8 streams: the stream count is a multiple of the group count, so a stream holds indices of
+    one channel group only (write_indices clamps the count to the number of indices)."""
+    code = self.get_vq_code(x_dict)
+    _, _, _, _, L, groups = self._vq_geometry(x_dict, 'get_coded')
+    return [vqstream.write_indices(None, code[i:i + 1], L, n_streams=groups * 8) for i in range(code.shape[0])]
+
+  def _decode_coded_vq(self, blobs, x_dict):
+    N, H, W, code_len, L, _ = self._vq_geometry(x_dict, 'decode_coded')
+    if not isinstance(blobs, (list, tuple)) or len(blobs) != N:
+      raise ValueError('decode_coded: the blobs must be what get_coded returns: a list of %d .jpdv bytes objects, one per '
+                       'label map' % N)
+    for j, b in enumerate(blobs):                 # every header on the host, before any device work
+      n, cl, Lb, _, _, _ = vqstream.parse_blob(b, 'decode_coded: blob %d' % j)
+      if Lb != L:
+        raise ValueError('decode_coded: blob %d was coded for n_center %d, the code book has %d' % (j, Lb, L))
+      if n * cl != code_len:
+        raise ValueError('decode_coded: blob %d holds %d x %d indices, a %d x %d label map carries %d'
+                         % (j, n, cl, H, W, code_len))
+    with torch.no_grad():
+      code = torch.cat([vqstream.read_indices(bytes(b), self._device()).view(1, code_len) for b in blobs], dim=0)
+      fake, _ = self._decode_vq_act(code, x_dict, 'decode_coded')
+      return ops.nhwc_to_nchw(fake)
 
   def decode_coded(self, payloads, x_dict):
     """decode() from what get_coded returned: a list of one `bytes` payload per label map.  ValueError, before any device
     work, without an encoder or a binarizer, for a label map that is no multiple of the encoder's down-sampling factor, a
-    wrong payload count, an item that is not bytes, and a payload whose length table does not add up."""
+    wrong payload count, an item that is not bytes, and a payload whose length table does not add up.
+    With --encoder_quantizer s2hvq the items are the .jpdv blobs of get_coded; each header's n * code_len and L must fit the
+    label map and the code book (checked on the host first); decode_coded(get_coded(x), x) equals get_img(x) bit for bit."""
+    if getattr(self, 'use_vq', False):
+      return self._decode_coded_vq(payloads, x_dict)
     self._require_binarizer()
     N, H, W = int(x_dict['label'].shape[0]), int(x_dict['label'].shape[-2]), int(x_dict['label'].shape[-1])
     step = 1 << self.netE.n_downsampling
@@ -640,6 +750,11 @@ class Pix2PixHDModel(BaseModel):
     reference's Shannon figure."""
     payloads = self.get_coded(x_dict)
     H, W = int(x_dict['image'].shape[-2]), int(x_dict['image'].shape[-1])
+    if getattr(self, 'use_vq', False):
+      # --encoder_quantizer s2hvq: the .jpdv blobs, and the packed-index file (mode 0) of the same code: nb bits per index + header
+      _, _, _, code_len, L, _ = self._vq_geometry(x_dict, 'get_coded_rate')
+      coded = sum(8.0 * len(p) / (H * W) for p in payloads) / len(payloads)
+      return coded, 8.0 * (vqstream.HEADER_BYTES + vqstream.packed_bytes(code_len, L)) / (H * W)
     shape = self.netE.code_shape(H, W)
     coded = sum(8.0 * entropy.file_bytes(len(p), shape) / (H * W) for p in payloads) / len(payloads)
     raw = 8.0 * (bitstream.HEADER_BYTES + bitstream.payload_bytes(shape)) / (H * W)
@@ -652,7 +767,7 @@ class Pix2PixHDModel(BaseModel):
     bits, `bits` [N] and `bpp` [N] = bits / (H * W).  map and per_channel each sum to bits.  The model's ideal length, not a
     file size: get_coded_rate measures files, and stays within the bound of DESIGN.md 4.12 of this figure."""
     with torch.no_grad():
-      r = ops.code_cost(self._code_act(x_dict))
+      r = ops.code_cost(self._code_act(x_dict, 'get_rate_map'))
       cell, channel = r['cell'].cpu(), r['channel'].cpu()
     pixels = int(x_dict['image'].shape[-2]) * int(x_dict['image'].shape[-1])
     unit = float(ops.CODE_COST_UNIT)
@@ -667,7 +782,7 @@ class Pix2PixHDModel(BaseModel):
     an absent class), share = the class's fraction of all bits; per_image: the same four keys [N, n_classes + 1], share being
     the fraction of that image's bits)."""
     with torch.no_grad():
-      b = self._code_act(x_dict)
+      b = self._code_act(x_dict, 'get_class_rates')
       label, _ = self._semantics(x_dict)
       r = ops.code_cost(b, label, self.n_onehot)
       units, pix = r['class_units'].cpu(), r['class_pixels'].cpu()

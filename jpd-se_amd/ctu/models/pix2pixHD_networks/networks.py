@@ -17,7 +17,8 @@ from jpdse_hip import (ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, PAD_ZERO, PAD_RE
                        require_gpu)
 from jpdse_hip import ops
 from jpdse_hip.ops import Act
-from jpdse_hip.layers import (HipConv2d, HipResnetBlock, HipBinarizer, InstNormAct, ConvNormAct, Ctx, _Slot,
+from jpdse_hip.layers import (HipConv2d, HipResnetBlock, HipBinarizer, HipVQBottleneck, vq_bottleneck_check, InstNormAct,
+                              ConvNormAct, Ctx, _Slot,
                               run_chain_fwd, run_chain_bwd)
 
 ResnetBlock = HipResnetBlock
@@ -212,11 +213,22 @@ class Encoder(nn.Module):
   """Feature encoder of the learned codec (networks.py:307-369): [ReflPad3, Conv7, IN, ReLU], n x [Conv3 s2, IN, ReLU],
   the Binarizer (optional: the bitstream), n x [ConvT3 s2, IN, ReLU], [ReflPad3, Conv7, Tanh].  Same Sequential indices as
   the reference, so `state_dict()` keys / shapes equal a reference net_E.pth (every conv carries its bias; the ones in
-  front of an affine-less InstanceNorm are not applied -- the norm cancels them)."""
+  front of an affine-less InstanceNorm are not applied -- the norm cancels them).
+  quantizer='s2hvq' (extension): the bottleneck slot holds a HipVQBottleneck -- 1x1 conv and soft-to-hard vector
+  quantizer over groups of vq_center_size channels -- instead of the Binarizer; binarizer_out_channels still names the
+  bottleneck's channel count.  Its code is vq_code / decode_vq_code; code / code_shape / decode_code stay the binarizer's."""
+
+  QUANTIZERS = ('binarizer', 's2hvq')
 
   def __init__(self, input_nc, output_nc, ngf=32, n_downsampling=4, norm_layer=None, binarize=False,
-               binarizer_out_channels=128, groups=1, compute_dtype='fp32', device=None):
+               binarizer_out_channels=128, groups=1, compute_dtype='fp32', device=None, quantizer='binarizer',
+               vq_n_center=64, vq_center_size=8, vq_sigma=10.0, vq_hard_forward=True):
     super(Encoder, self).__init__()
+    if quantizer not in self.QUANTIZERS:
+      raise ValueError('Encoder: quantizer must be one of %s, got %r' % (self.QUANTIZERS, quantizer))
+    self.quantizer = quantizer if binarize else None
+    if self.quantizer == 's2hvq':          # before any layer exists
+      vq_bottleneck_check(binarizer_out_channels, int(vq_n_center), int(vq_center_size), vq_sigma, 'Encoder')
     if groups != 1:
       raise NotImplementedError('grouped encoder convolutions (--netE_groups != 1) are not implemented on the HIP path')
     if n_downsampling < 1:
@@ -234,7 +246,9 @@ class Encoder(nn.Module):
       c = ngf * 2 ** i
       slots[4 + 3 * i] = HipConv2d(c, 2 * c, 3, 2, 1, PAD_ZERO, apply_bias=False, **kw)
       self._pre.append(ConvNormAct(slots[4 + 3 * i], InstNormAct(ACT_RELU)))
-    if binarize:
+    if binarize and quantizer == 's2hvq':
+      slots[4 + 3 * n] = HipVQBottleneck(ngf * 2 ** n, B, vq_n_center, vq_center_size, vq_sigma, vq_hard_forward, **kw)
+    elif binarize:
       slots[4 + 3 * n] = HipBinarizer(ngf * 2 ** n, B, **kw)
     self._post = []
     for i in range(n):
@@ -249,14 +263,23 @@ class Encoder(nn.Module):
   @property
   def _binarizer(self):
     """model[4 + 3n] (a property, so the module is registered once, under its reference key)."""
-    return self.model[4 + 3 * self.n_downsampling] if self.binarize else None
+    return self.model[4 + 3 * self.n_downsampling] if self.quantizer == 'binarizer' else None
+
+  @property
+  def _vq(self):
+    """model[4 + 3n] when it is the vector-quantizer bottleneck."""
+    return self.model[4 + 3 * self.n_downsampling] if self.quantizer == 's2hvq' else None
+
+  @property
+  def _bottleneck(self):
+    return self.model[4 + 3 * self.n_downsampling] if self.quantizer is not None else None
 
   def fwd(self, x):
-    """(features, ctx); the binarizer's mode follows its `training` flag."""
+    """(features, ctx); the bottleneck's mode follows its `training` flag."""
     h, c_pre = run_chain_fwd(self._pre, x)
     c_bin = None
-    if self._binarizer is not None:
-      h, c_bin = self._binarizer.fwd(h)
+    if self._bottleneck is not None:
+      h, c_bin = self._bottleneck.fwd(h)
     y, c_post = run_chain_fwd(self._post, h)
     return y, (c_pre, c_bin, c_post)
 
@@ -264,8 +287,8 @@ class Encoder(nn.Module):
     """Weight gradients of every layer from dy = d loss / d features.  No gradient w.r.t. the encoder input (the image)."""
     c_pre, c_bin, c_post = ctxs
     d = run_chain_bwd(self._post, c_post, dy, True, need_dw)
-    if self._binarizer is not None:
-      d = self._binarizer.bwd(c_bin, d, True, need_dw)
+    if self._bottleneck is not None:
+      d = self._bottleneck.bwd(c_bin, d, True, need_dw)
     run_chain_bwd(self._pre, c_pre, d, False, need_dw)
 
   def code(self, x):
@@ -290,6 +313,31 @@ class Encoder(nn.Module):
     y, _ = run_chain_fwd(self._post, b)
     return y
 
+  def _require_vq(self):
+    if self._vq is None:
+      raise AttributeError('Encoder: no vector quantizer found (quantizer=%r)' % (self.quantizer,))
+    return self._vq
+
+  def vq_code_len(self, H, W):
+    """Indices per image of an H x W input: (H / 2^n) (W / 2^n) cout / D."""
+    vq, n = self._require_vq(), self.n_downsampling
+    return (H >> n) * (W >> n) * (vq.cout // vq.center_size)
+
+  def vq_code(self, x):
+    """int32 [N, h * w * cout / D]: the nearest centre of every channel group of every pixel of the bottleneck's features, pixel
+    by pixel, groups ascending inside a pixel: model[:4 + 3n + 1](x) as indices."""
+    vq = self._require_vq()
+    h, _ = run_chain_fwd(self._pre, x)
+    return vq.code(h)
+
+  def decode_vq_code(self, index, H, W):
+    """The receiver's half: (features, status) from the int32 [N, h * w * cout / D] indices of an H x W image (ops.vq_decode,
+    then model[4 + 3n + 1:]); status: the device word of ops.vq_decode, non-zero for an index outside the code book."""
+    vq, n = self._require_vq(), self.n_downsampling
+    b, status = vq.decode(index, int(index.shape[0]), H >> n, W >> n, self.cdtype)
+    y, _ = run_chain_fwd(self._post, b)
+    return y, status
+
   def forward(self, input, inst=None, mode='get_continuous_img', inst_wise_pool=False):
     if mode == 'get_binary_code':
       if self._binarizer is None:
@@ -306,7 +354,8 @@ class Encoder(nn.Module):
 def define_G(input_nc, output_nc, ngf, netG, n_downsample_global=3, n_blocks_global=9, n_local_enhancers=1,
              n_blocks_local=3, norm='instance', gpu_ids=[], binarize_encoder=False,
              encoder_binarizer_out_channels=128, encoder_groups=1, binarize_generator=False,
-             bin_generator_before_res=True, generator_binarizer_out_channels=128, compute_dtype='fp32'):
+             bin_generator_before_res=True, generator_binarizer_out_channels=128, compute_dtype='fp32',
+             encoder_quantizer='binarizer', vq_n_center=64, vq_center_size=8, vq_sigma=10.0, vq_hard_forward=True):
   get_norm_layer(norm)
   device = torch.device('cuda', gpu_ids[0]) if len(gpu_ids) > 0 else None
   if device is not None:
@@ -320,7 +369,8 @@ def define_G(input_nc, output_nc, ngf, netG, n_downsample_global=3, n_blocks_glo
   elif netG == 'encoder':
     net = Encoder(input_nc, output_nc, ngf, n_downsample_global, binarize=binarize_encoder,
                   binarizer_out_channels=encoder_binarizer_out_channels, groups=encoder_groups,
-                  compute_dtype=compute_dtype, device=device)
+                  compute_dtype=compute_dtype, device=device, quantizer=encoder_quantizer, vq_n_center=vq_n_center,
+                  vq_center_size=vq_center_size, vq_sigma=vq_sigma, vq_hard_forward=vq_hard_forward)
   else:
     raise ValueError('generator not implemented!')
   return net

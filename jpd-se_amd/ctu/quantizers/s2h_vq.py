@@ -88,6 +88,31 @@ class _Pmf(torch.autograd.Function):
     return ops.vq_pmf_bwd(dpmf.contiguous(), rows).view(ctx.shape)
 
 
+class _Quantize(torch.autograd.Function):
+  """(y, index, pmf) of ops.vq_quantize_fwd; backward: ops.vq_quantize_bwd, the gradient of the soft form whatever the forward
+  was (straight-through), p recomputed from the saved x.  A gradient arriving on pmf becomes dpmf."""
+
+  @staticmethod
+  def forward(ctx, x, code_book, sigma, hard_forward, want_pmf):
+    x, code_book = x.contiguous(), code_book.contiguous()
+    y, index, pmf = ops.vq_quantize_fwd(x, code_book, sigma, hard_forward, want_pmf)
+    ctx.save_for_backward(x, code_book)
+    ctx.sigma, ctx.want_pmf = sigma, want_pmf
+    ctx.mark_non_differentiable(index)
+    if not want_pmf:
+      pmf = x.new_zeros(0, dtype=torch.float32)           # a placeholder output: autograd wants tensors
+      ctx.mark_non_differentiable(pmf)
+    return y, index, pmf
+
+  @staticmethod
+  def backward(ctx, dy, _dindex, dpmf):
+    x, code_book = ctx.saved_tensors
+    dpmf = dpmf.contiguous() if (ctx.want_pmf and dpmf is not None) else None
+    dx, dc = ops.vq_quantize_bwd(dy.contiguous(), x, code_book, ctx.sigma, dpmf, want_dx=ctx.needs_input_grad[0],
+                                 want_dc=ctx.needs_input_grad[1])
+    return dx, dc, None, None, None
+
+
 class S2HVQ(nn.Module):
   """code_book: tensor [n_center, center_size], learnable (parameter `_code_book`); sigma > 0: the hardness of the soft
   assignment used in training."""
@@ -157,6 +182,22 @@ class S2HVQ(nn.Module):
     if raw:
       return onehot.view(n, code_len, L).to(x.dtype)
     return index.to(torch.int64).view(n, code_len)
+
+  def quantize(self, x, code_len, hard_forward=True, want_pmf=False):
+    """The quantizer as a bottleneck: x [n, d] -> (y [n, d] in x's dtype, code int64 [n, code_len], pmf float32
+    [n_center] or None) in one kernel, the [n * code_len, n_center] assignment never stored.  y is the nearest centre of every
+    vector (hard_forward) or the soft assignment's mix of the centres; pmf the column means of the soft assignment.
+    Training mode: differentiable in x and the code book, and the gradient is the soft form's whatever hard_forward is (the
+    straight-through rule); a gradient on pmf is taken too.  Eval mode: always the hard forward, nothing saved.  Argument checks
+    are encode's."""
+    xm = self._vectors(x, code_len)
+    n = x.size(0)
+    if self.training and torch.is_grad_enabled():
+      y, index, pmf = _Quantize.apply(xm, self.code_book, float(self._sigma), bool(hard_forward), bool(want_pmf))
+    else:
+      y, index, pmf = ops.vq_quantize_fwd(xm.detach(), self.code_book.detach().contiguous(), float(self._sigma),
+                                          bool(hard_forward) or not self.training, bool(want_pmf))
+    return y.view(n, code_len * self._center_size), index.to(torch.int64).view(n, code_len), (pmf if want_pmf else None)
 
   def decode(self, code_raw):
     """code_raw [n, code_len, n_center] (e.g. encode(..., raw=True)) -> [n, code_len * center_size]: the centre with the highest

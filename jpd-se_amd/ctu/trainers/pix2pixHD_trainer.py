@@ -14,7 +14,7 @@ from torch.optim.lr_scheduler import ReduceLROnPlateau
 from ctu.models.pix2pixHD_model import Pix2PixHDModel
 from ctu.trainers.base_trainer import BaseTrainer
 from jpdse_hip.ddp import GradBuckets
-from jpdse_hip.layers import HipConv2d, bump_weights_epoch
+from jpdse_hip.layers import HipConv2d, HipVQBottleneck, bump_weights_epoch
 
 
 class Pix2PixHDTrainer(BaseTrainer):
@@ -87,6 +87,8 @@ class Pix2PixHDTrainer(BaseTrainer):
     for m in net.modules():
       if isinstance(m, HipConv2d):
         m.grad_ready_hook = (lambda mod, b=buckets: (b.mark_ready(mod.weight), b.mark_ready(mod.bias)))
+      elif isinstance(m, HipVQBottleneck):
+        m.grad_ready_hook = (lambda mod, b=buckets: b.mark_ready(mod.vq._code_book))
 
   def update_fixed_params(self):
     """End of the `niter_fix_global` phase (train.py calls model.update_fixed_params and swaps the optimizer,
@@ -130,6 +132,13 @@ class Pix2PixHDTrainer(BaseTrainer):
     self.eval()
     with torch.no_grad():
       return torch.cat([c for c in self.model.get_code(x_dict, packed) if c is not None], dim=-1)
+
+  def get_vq_code(self, x_dict):
+    """The code of the vector-quantizer bottleneck (--encoder_quantizer s2hvq): int64 [N, h * w * C / D] on the
+    device.  decode(get_vq_code(x), x) equals get_img(x) bit for bit; get_coded / decode_coded / get_coded_rate store it as
+    .jpdv blobs."""
+    self.eval()
+    return self.model.get_vq_code(x_dict)
 
   def get_eval_rate(self, x_dict):
     """(Shannon bpp in nats as the reference computes it, raw bpp) of the learned codec (pix2pixHD_trainer.py:106-110)."""

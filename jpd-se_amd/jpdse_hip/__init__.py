@@ -148,6 +148,21 @@ class VqIndexDecodeArgs(ctypes.Structure):
               ('stream', ctypes.c_void_p)]
 
 
+# the jpdse_vq_quantize_* calls (vq_bottleneck.hip)
+class VqQuantizeFwdArgs(ctypes.Structure):
+  _fields_ = [(n, ctypes.c_int32) for n in ('dtype', 'M', 'D', 'L')] + \
+             [('sigma', ctypes.c_float), ('hard_forward', ctypes.c_int32), ('x', ctypes.c_void_p), ('code_book', ctypes.c_void_p),
+              ('y', ctypes.c_void_p), ('index', ctypes.c_void_p), ('pmf', ctypes.c_void_p), ('ws', ctypes.c_void_p),
+              ('ws_bytes', ctypes.c_size_t), ('stream', ctypes.c_void_p)]
+
+
+class VqQuantizeBwdArgs(ctypes.Structure):
+  _fields_ = [(n, ctypes.c_int32) for n in ('dtype', 'M', 'D', 'L')] + \
+             [('sigma', ctypes.c_float), ('dy', ctypes.c_void_p), ('x', ctypes.c_void_p), ('code_book', ctypes.c_void_p),
+              ('dpmf', ctypes.c_void_p), ('dx', ctypes.c_void_p), ('dcode_book', ctypes.c_void_p), ('ws', ctypes.c_void_p),
+              ('ws_bytes', ctypes.c_size_t), ('stream', ctypes.c_void_p)]
+
+
 _P, _I32, _I64, _F, _SZ = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float,
                            ctypes.c_size_t)
 _CD, _ND = ctypes.POINTER(ConvDesc), ctypes.POINTER(InormDesc)
@@ -266,6 +281,9 @@ SIGNATURES = {
     'jpdse_vq_index_workspace_size': (_SZ, [_I32, _I32, _I32]),
     'jpdse_vq_index_encode': (_I32, [ctypes.POINTER(VqIndexEncodeArgs)]),
     'jpdse_vq_index_decode': (_I32, [ctypes.POINTER(VqIndexDecodeArgs)]),
+    'jpdse_vq_quantize_workspace_size': (_SZ, [_I32, _I32, _I32]),
+    'jpdse_vq_quantize_fwd': (_I32, [ctypes.POINTER(VqQuantizeFwdArgs)]),
+    'jpdse_vq_quantize_bwd': (_I32, [ctypes.POINTER(VqQuantizeBwdArgs)]),
 }
 
 # the developer build (same sources, -DJPDSE_DEV): the shipped ABI plus include/jpdse_dev.h

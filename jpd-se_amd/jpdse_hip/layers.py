@@ -346,6 +346,96 @@ class HipBinarizer(nn.Module):
     return self.conv.bwd(ctx, db, need_dx, need_dw)
 
 
+def vq_bottleneck_check(cout, n_center, center_size, sigma, who='HipVQBottleneck'):
+  """ValueError unless a bottleneck of `cout` channels can be quantized in groups of center_size (host only)."""
+  if center_size < 1 or cout % center_size != 0:
+    raise ValueError('%s: center_size %d does not divide the bottleneck\'s %d channels' % (who, center_size, cout))
+  if ops.cpad(cout) != cout:
+    raise ValueError('%s: %d channels are no multiple of 8: the NHWC tensor would carry padding lanes between the vectors'
+                     % (who, cout))
+  if not 1 <= center_size <= ops.VQ_MAX_D or not 2 <= n_center <= ops.VQ_MAX_L:
+    raise ValueError('%s: center_size %d / n_center %d, the kernels take 1 .. %d and 2 .. %d'
+                     % (who, center_size, n_center, ops.VQ_MAX_D, ops.VQ_MAX_L))
+  if not (float(sigma) > 0.0 and float(sigma) != float('inf')):
+    raise ValueError('%s: sigma must be a finite number > 0, got %r' % (who, sigma))
+
+
+class HipVQBottleneck(nn.Module):
+  """The soft-to-hard vector quantizer as the encoder's bottleneck, in the binarizer's Sequential slot: a 1x1
+  conv without bias or activation (`conv`: state-dict key `<prefix>.conv.weight` [cout, cin, 1, 1]) and an S2HVQ (`vq`: key
+  `<prefix>.vq._code_book` [n_center, center_size]).  The conv's NHWC output [N, h, w, cout] IS the quantizer's [M][D] matrix:
+  M = N h w cout / D, vector m = pixel * (cout / D) + group, every vector D consecutive channels of one pixel -- no re-layout
+  pass.  That needs center_size | cout and cpad(cout) == cout (no padding lanes); anything else is a ValueError here.
+
+  Forward: the hard form (y = the nearest centre) in eval mode and, unless `hard_forward` is False, in training; backward: the
+  gradient of the soft form either way (ops.vq_quantize_bwd), the code book's written into its persistent `.grad` buffer.
+  Code book: uniform in [-1, 1], drawn as 2 * torch.rand(n_center, center_size) - 1 in float32 from a CPU torch.Generator
+  seeded with `seed` (default 0) -- the same book on every device and rank; load_state_dict replaces it."""
+
+  def __init__(self, cin, cout, n_center=64, center_size=8, sigma=10.0, hard_forward=True, dtype=F32, device=None, seed=0):
+    super(HipVQBottleneck, self).__init__()
+    n_center, center_size = int(n_center), int(center_size)
+    vq_bottleneck_check(cout, n_center, center_size, sigma)
+    from ctu.quantizers.s2h_vq import S2HVQ      # the module the layer wraps; it refuses n_center / center_size beyond the kernels'
+    book = torch.rand(n_center, center_size, generator=torch.Generator().manual_seed(int(seed))) * 2 - 1
+    self.conv = HipConv2d(cin, cout, 1, act=ACT_NONE, apply_bias=False, bias=False, dtype=dtype, device=device)
+    self.vq = S2HVQ(book.to(device) if device is not None else book, sigma=float(sigma))
+    self.cout, self.center_size, self.n_center = cout, center_size, n_center
+    self.hard_forward = bool(hard_forward)
+    self.grad_ready_hook = None
+
+  def _book(self):
+    c = self.vq._code_book
+    assert c.dtype == torch.float32 and c.is_contiguous(), 'the code book must be contiguous fp32'
+    return c
+
+  def _cgrad_buffer(self):
+    c = self._book()
+    if c.grad is None or not c.grad.is_contiguous():
+      c.grad = torch.zeros_like(c)
+    return c.grad
+
+  def ensure_grads(self):
+    if self.vq._code_book.requires_grad:
+      self._cgrad_buffer()
+
+  def _quantize(self, h, hard):
+    D = self.center_size
+    y, index, _ = ops.vq_quantize_fwd(h.t.view(-1, D), self._book().detach(), self.vq.sigma, hard)
+    return Act(y.view(h.t.shape), h.C), index
+
+  def fwd(self, x):
+    h, c_conv = self.conv.fwd(x)
+    y, _ = self._quantize(h, self.hard_forward or not self.training)
+    return y, Ctx(c_conv, h)
+
+  def code(self, x):
+    """int32 [N, h * w * cout / D]: the index of the nearest centre of every vector of x's features, in the layout above."""
+    h, _ = self.conv.fwd(x)
+    _, index = self._quantize(h, True)
+    return index.view(h.N, -1)
+
+  def decode(self, index, N, h, w, dtype_code):
+    """The features Act [N, h, w, cout] of an index tensor as code() returns it (ops.vq_decode: bit for bit what the hard
+    forward emitted) and the status word of ops.vq_decode."""
+    from .ops import tdtype_of
+    y, status = ops.vq_decode(index.contiguous().view(-1), self._book().detach(), tdtype_of(dtype_code))
+    return Act(y.view(N, h, w, self.cout), self.cout), status
+
+  def bwd(self, ctx, dy, need_dx=True, need_dw=True):
+    """dy: the gradient w.r.t. the quantized features.  Straight-through: the soft form's gradient, then the
+    1x1 conv's data / weight gradients."""
+    c_conv, h = ctx.items
+    D = self.center_size
+    book = self._book()
+    want_dc = need_dw and book.requires_grad
+    dh, _ = ops.vq_quantize_bwd(dy.t.view(-1, D), h.t.view(-1, D), book.detach(), self.vq.sigma, None, want_dx=True,
+                                want_dc=want_dc, dc_out=self._cgrad_buffer() if want_dc else None)
+    if want_dc and self.grad_ready_hook is not None:
+      self.grad_ready_hook(self)
+    return self.conv.bwd(c_conv, Act(dh.view(h.t.shape), h.C), need_dx, need_dw)
+
+
 class PackBatcher(object):
   """Re-packs the data-gradient panels of all conv layers of one network in ONE launch right after its
   optimizer step (jpdse_conv_pack_run); layers it cannot cover keep their lazy per-layer pack."""

@@ -11,7 +11,7 @@ import torch
 
 from . import (lib, check, JpdseError, F32, BF16, ConvDesc, InormDesc, EvalMetricsSemArgs, MsssimLossArgs, CodeRateArgs, SemLossArgs, CodeCostArgs, ACT_NONE, PAD_ZERO, PAD_REFLECT)
 from . import (VqSoftFwdArgs, VqHardFwdArgs, VqSoftBwdArgs, VqDecodeArgs, VqDecodeBwdArgs, VqArgmaxArgs, VqPmfArgs, VqPmfBwdArgs,
-               VqIndexEncodeArgs, VqIndexDecodeArgs)
+               VqIndexEncodeArgs, VqIndexDecodeArgs, VqQuantizeFwdArgs, VqQuantizeBwdArgs)
 
 
 def cpad(c):
@@ -1162,6 +1162,50 @@ def vq_pmf_bwd(dpmf, M):
   args = VqPmfBwdArgs(int(M), L, dpmf.data_ptr(), ds.data_ptr(), torch.cuda.current_stream().cuda_stream)
   check(lib().jpdse_vq_pmf_bwd(ctypes.byref(args)), 'vq_pmf_bwd')
   return ds
+
+
+# ---- vector-quantizer bottleneck (vq_bottleneck.hip): the quantizer in one call, no [M, L] matrix ------------
+def _vq_quantize_ws(M, D, L, dev):
+  return workspace(max(lib().jpdse_vq_quantize_workspace_size(M, D, L), 1), dev)
+
+
+def vq_quantize_fwd(x, code_book, sigma, hard_forward=True, want_pmf=False):
+  """(y, index, pmf) of x [M, D] against code_book fp32 [L, D] (jpdse_vq_quantize_fwd): index int32 [M] the nearest centre
+  (lowest on a tie); y [M, D] in x's dtype, code_book[index] when hard_forward, else sum_k p[m][k] code_book[k] with the soft
+  assignment p of vq_soft_fwd; pmf fp32 [L] = the column means of p (None unless want_pmf)."""
+  M, D, L = _vq_dims(x, code_book)
+  y = torch.empty_like(x)
+  index = torch.empty(M, dtype=torch.int32, device=x.device)
+  pmf = torch.empty(L, dtype=torch.float32, device=x.device) if want_pmf else None
+  ws = _vq_quantize_ws(M, D, L, x.device) if want_pmf else None
+  args = VqQuantizeFwdArgs(code_of(x.dtype), M, D, L, float(sigma), 1 if hard_forward else 0, x.data_ptr(), code_book.data_ptr(),
+                           y.data_ptr(), index.data_ptr(), pmf.data_ptr() if want_pmf else None,
+                           ws.data_ptr() if want_pmf else None, ws.numel() if want_pmf else 0,
+                           torch.cuda.current_stream().cuda_stream)
+  check(lib().jpdse_vq_quantize_fwd(ctypes.byref(args)), 'vq_quantize_fwd')
+  return y, index, pmf
+
+
+def vq_quantize_bwd(dy, x, code_book, sigma, dpmf=None, want_dx=True, want_dc=True, dc_out=None):
+  """(dx, dcode_book) of the SOFT form of vq_quantize_fwd -- the straight-through gradient of the hard one -- for the upstream
+  gradients dy [M, D] (x's dtype) and, optionally, dpmf fp32 [L] (jpdse_vq_quantize_bwd; p is recomputed from x).  dx in x's
+  dtype, dcode_book fp32 [L, D] (written into dc_out when given); either is None when not wanted."""
+  M, D, L = _vq_dims(x, code_book)
+  assert dy.shape == x.shape and dy.dtype == x.dtype and dy.is_contiguous() and dy.device == x.device, (dy.dtype, tuple(dy.shape))
+  if dpmf is not None:
+    assert dpmf.dtype == torch.float32 and dpmf.is_contiguous() and dpmf.numel() == L and dpmf.device == x.device
+  dx = torch.empty_like(x) if want_dx else None
+  dc = None
+  if want_dc:
+    dc = dc_out if dc_out is not None else torch.empty_like(code_book)
+    assert dc.dtype == torch.float32 and dc.is_contiguous() and tuple(dc.shape) == (L, D) and dc.device == x.device
+  ws = _vq_quantize_ws(M, D, L, x.device) if want_dc else None
+  args = VqQuantizeBwdArgs(code_of(x.dtype), M, D, L, float(sigma), dy.data_ptr(), x.data_ptr(), code_book.data_ptr(),
+                           dpmf.data_ptr() if dpmf is not None else None, dx.data_ptr() if want_dx else None,
+                           dc.data_ptr() if want_dc else None, ws.data_ptr() if want_dc else None,
+                           ws.numel() if want_dc else 0, torch.cuda.current_stream().cuda_stream)
+  check(lib().jpdse_vq_quantize_bwd(ctypes.byref(args)), 'vq_quantize_bwd')
+  return dx, dc
 
 
 # ---- soft-to-hard vector quantizer: coded index stream (vq_coder.hip; format: DESIGN.md 4.14) -------------------------------

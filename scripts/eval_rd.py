@@ -118,6 +118,12 @@ def main():
   ap.add_argument('--dtype', default='bf16', choices=['bf16', 'fp32'])
   ap.add_argument('--ngf', type=int, default=64)
   ap.add_argument('--codec', action='store_true', help='learned codec (netE + binarizer): also report bpp')
+  ap.add_argument('--encoder_quantizer', default='binarizer', choices=['binarizer', 's2hvq'],
+                  help='with --codec: the encoder\'s bottleneck, as the training flag (DESIGN.md 4.15).  s2hvq reports the sizes of the '
+                       '.jpdv blobs of the code (trainer.get_coded_rate) in place of the binarizer\'s Shannon / context figures')
+  ap.add_argument('--vq_n_center', type=int, default=64, help='the training flag of the same name')
+  ap.add_argument('--vq_center_size', type=int, default=8, help='the training flag of the same name')
+  ap.add_argument('--vq_sigma', type=float, default=10.0, help='the training flag of the same name')
   ap.add_argument('--checkpoints_dir', default=None, help='load net_G.pth (and net_E.pth) from here')
   ap.add_argument('--data', default=None, help='directory of pre-decoded *.pt batches instead of synthetic ones')
   ap.add_argument('--per-class', action='store_true', help='also print L1 / MSE / PSNR per semantic class')
@@ -143,6 +149,10 @@ def main():
     ap.error('--semantics needs --codec --entropy --roundtrip DIR')
   if args.rate_map and not args.codec:
     ap.error('--rate-map needs --codec')
+  vq = args.codec and args.encoder_quantizer == 's2hvq'
+  if vq and (args.roundtrip or args.rate_map):
+    ap.error('--roundtrip / --rate-map store and walk the binarizer\'s code: not available with --encoder_quantizer s2hvq '
+             '(trainer.get_coded / decode_coded are its files)')
   if args.roundtrip:
     os.makedirs(args.roundtrip, exist_ok=True)
   if args.rate_map:
@@ -157,7 +167,8 @@ def main():
             class_distortion_weights=args.class_distortion_weights, edge_distortion_weight=args.edge_distortion_weight)
   if args.codec:
     kw.update(no_feat_encoding=False, no_encoder_binarization=False, feat_num=3, nef=args.ngf, n_downsample_E=4,
-              encoder_binarizer_out_channels=128)
+              encoder_binarizer_out_channels=128, encoder_quantizer=args.encoder_quantizer, vq_n_center=args.vq_n_center,
+              vq_center_size=args.vq_center_size, vq_sigma=args.vq_sigma)
   if args.checkpoints_dir:
     kw.update(is_train=False, load_model=True, checkpoints_dir=args.checkpoints_dir)
   opt = default_opt(**kw)
@@ -195,7 +206,20 @@ def main():
       by_batch['weighted'] += wd
       by_image['weighted'] += wd * b
       line += ', weighted {} (un-quantised) {:.6f}'.format(opt.distortion_loss_fn, wd)
-    if args.codec:
+    if vq:
+      # the vector-quantised code: sizes of the .jpdv blobs and of the packed-index file, and a check that the
+      # blobs decode to get_img's image
+      coded_bpp, packed_bpp = trainer.get_coded_rate(x_dict)
+      receiver = dict(label=x_dict['label'], instance=x_dict['instance'])
+      diff = float((trainer.decode_coded(trainer.get_coded(x_dict), receiver) - trainer.get_img(x_dict)).abs().max())
+      worst_diff = max(worst_diff, diff)
+      by_batch['coded'] += coded_bpp
+      by_image['coded'] += coded_bpp * b
+      by_batch['actual'] += packed_bpp
+      by_image['actual'] += packed_bpp * b
+      line += ', vq code: coded file bpp {:.4f} (packed indices {:.4f}), max |decoded - get_img| {:.3e}'.format(coded_bpp, packed_bpp,
+                                                                                                        diff)
+    elif args.codec:
       shannon, actual = trainer.get_eval_rate(x_dict)
       shannon = float(shannon)
       by_batch['shannon'] += shannon
@@ -207,7 +231,7 @@ def main():
       by_batch['context'] += context                   # of the coded size, not a size)
       by_image['context'] += context * b
       line += ', context-model bpp {:.4f}'.format(context)
-    if args.codec and args.per_class:
+    if args.codec and args.per_class and not vq:
       cr = trainer.get_class_rates(x_dict)             # bits are sums of k / 2^16: adding batches stays exact
       class_bits = cr['bits'] if class_bits is None else class_bits + cr['bits']
     if args.rate_map:
@@ -219,7 +243,7 @@ def main():
       by_batch['model'] += model_bpp
       by_image['model'] += float(rm['bpp'].sum())
       line += ', model code length bpp {:.4f}'.format(model_bpp)
-    if args.entropy:
+    if args.entropy and not vq:
       coded_bpp, raw_file_bpp = trainer.get_coded_rate(x_dict)
       by_batch['coded'] += coded_bpp
       by_image['coded'] += coded_bpp * b
@@ -252,12 +276,14 @@ def main():
                                                                             t['ms_ssim'] / n, t['psnr'] / n)
     if weighted:
       line += ', avg weighted {} (un-quantised) {:.6f}'.format(opt.distortion_loss_fn, t['weighted'] / n)
-    if args.codec:
+    if vq:
+      line += ', avg vq coded file / packed-index bpp {:.4f}/{:.4f}'.format(t['coded'] / n, t['actual'] / n)
+    elif args.codec:
       line += ', avg pre-/(estimated) post-entropy coding bpp {:.4f}/{:.4f}'.format(t['actual'] / n, t['shannon'] / n)
       line += ', avg context-model bpp {:.4f}'.format(t['context'] / n)
     if args.rate_map:
       line += ', avg model code length bpp {:.4f}'.format(t['model'] / n)
-    if args.entropy:
+    if args.entropy and not vq:
       line += ', avg coded file bpp {:.4f}'.format(t['coded'] / n)
     if args.semantics:
       line += ', avg semantics/total file bpp {:.4f}/{:.4f}'.format(t['semantics'] / n, t['total'] / n)
