@@ -865,6 +865,61 @@ typedef struct jpdse_vq_quantize_bwd_args {
 } jpdse_vq_quantize_bwd_args;
 int jpdse_vq_quantize_bwd(const jpdse_vq_quantize_bwd_args* args);
 
+/* ---- vector-quantizer bottleneck: the rate term on per-group histograms (vq_bottleneck.hip) -----------------
+ * Vectors m = 0 .. M - 1 fall into G >= 1 groups, G | M, g(m) = m % G (4.15's layout m = pixel * (cout / D) + group), n = M / G
+ * vectors per group.  p[m][k] is the soft assignment above (here e[m][k] * (1 / s[m]): one division per vector); with `hard`
+ * the one-hot of quantize_fwd's index[m].
+ *   hist[g][k]  = sum over m with g(m) = g of p[m][k]
+ *   q[g][k]     = hist[g][k] / n
+ *   bits        = - sum_g sum_k hist[g][k] log2 q[g][k], terms with hist <= 0 dropped
+ *   rate        = bits / denom                 (denom = N H W: bits per pixel of the local batch; denom = M: bits per index)
+ *   dhist[g][k] = scale (-(log2 q[g][k] + 1 / ln 2)) / denom where hist > 0, else 0: scale * d rate / d hist
+ *   rate_fwd    one launch sums p (recomputed from x; [M][L] is never stored) into one fp32 partial [G][L] per block, a second
+ *               launch of one block merges the partials in block order in fp64, forms q, bits, rate and dhist in fp64 and
+ *               writes hist, rate and dhist as fp32.  hist or dhist may be NULL.  Order of the fp32 sums: G a power of two
+ *               <= 64 whose per-wave table fits LDS -- the lanes of a wave that share a group (lane % G) are added across
+ *               the wave with xor-shuffles, offsets 32, 16, .. G in that order (hard: counted from a ballot, exact), the G
+ *               owner lanes add the result into the wave's own LDS table tile after tile, and the waves of a block are merged
+ *               in wave order; any other G -- m ascending inside a tile, tiles of a block in order.  bits: every thread of the
+ *               final block adds its entries i = g L + k in ascending i (i = t, t + 1024, ..), the 1024 sums are added in
+ *               ascending t, 32 at a time, then the 32 in order.
+ *   quantize_bwd_grouped   quantize_bwd with dp[m][k] = <dy[m], c[k]> + dhist[g(m)][k] (no division by M: dhist is the gradient
+ *               w.r.t. the un-normalised sums); everything after dp as above.  dhist NULL: exactly quantize_bwd with dpmf NULL.
+ * No atomics; grids, tiles and orders of summation depend on (M, D, L, G) alone: two calls give identical bits.  ws of
+ * rate_fwd: jpdse_vq_rate_workspace_size(M, D, L, G) bytes (host only; 0 outside the limits); of quantize_bwd_grouped:
+ * jpdse_vq_quantize_workspace_size, with a dcode_book.  JPDSE_EINVAL before any launch: the limits and refusals of the calls
+ * above, and G < 1, M % G != 0, G * L > 65536, scale or denom not finite, denom <= 0, NULL rate. */
+size_t jpdse_vq_rate_workspace_size(int32_t M, int32_t D, int32_t L, int32_t G);
+typedef struct jpdse_vq_rate_fwd_args {
+  int32_t dtype, M, D, L, G;
+  float sigma;
+  int32_t hard;
+  const void* x;           /* [M][D] in `dtype` */
+  const float* code_book;  /* [L][D] */
+  float scale, denom;
+  float* hist;             /* [G][L], or NULL */
+  float* rate;             /* [1] */
+  float* dhist;            /* [G][L], or NULL */
+  void* ws;
+  size_t ws_bytes;
+  void* stream;
+} jpdse_vq_rate_fwd_args;
+int jpdse_vq_rate_fwd(const jpdse_vq_rate_fwd_args* args);
+typedef struct jpdse_vq_quantize_bwd_grouped_args {
+  int32_t dtype, M, D, L, G;
+  float sigma;
+  const void* dy;          /* [M][D] in `dtype` */
+  const void* x;
+  const float* code_book;
+  const float* dhist;      /* [G][L], or NULL */
+  void* dx;                /* [M][D] in `dtype`, or NULL */
+  float* dcode_book;       /* [L][D], or NULL */
+  void* ws;
+  size_t ws_bytes;
+  void* stream;
+} jpdse_vq_quantize_bwd_grouped_args;
+int jpdse_vq_quantize_bwd_grouped(const jpdse_vq_quantize_bwd_grouped_args* args);
+
 /* ---- optimizer ---------------------------------------------------------------------- */
 /* torch.optim.Adam (model.py:275,279) over a table of tensors, one launch.  `table` is a
  * device array of jpdse_adam_entry; bias corrections are computed from `step` (1-based). */

@@ -13,6 +13,7 @@
 //                    gradient the chunk's p and dd go to LDS and thread ((k, j), part) sums p dy - 2 dd (x - c) over its share of the
 //                    tile's vectors ascending, parts added in order into the block's fp32 partial [L][D].
 //   vqb_merge_kernel / vqb_pmf_final_kernel   the partials in block order: fp32 for dC, fp64 for the pmf.
+//   vqr_*            the rate term on per-group histograms: described where they stand, below the backward.
 // The code book sits in LDS as [L][DP] (zero padded: every lane reads the same word, a broadcast, and the padded components add
 // exact zeros) when that is at most 8 KiB; a larger one is read from global memory at wave-uniform addresses.
 // No atomics; grids, tiles and chunks are functions of (M, D, L) alone; LDS per block below 64 KiB.
@@ -48,9 +49,10 @@ static inline size_t vqb_fwd_lds(int D, int L, bool pmf) {
   if (pmf) n += (size_t)vqb_chunk(L) * 257 + 256;
   return n * sizeof(float);
 }
-static inline size_t vqb_bwd_lds(int D, int L, bool dc) {
+// nq: the words of the dq region (L: dpmf / M; G (L + 1): a staged dhist; 0: a dhist read from global memory)
+static inline size_t vqb_bwd_lds(int D, int L, bool dc, size_t nq) {
   const int V = vqb_bwd_threads(D), KC = vqb_chunk(L);
-  size_t n = (vqb_cb_lds(D, L) ? (size_t)L * vqb_dp(D) : 0) + L;
+  size_t n = (vqb_cb_lds(D, L) ? (size_t)L * vqb_dp(D) : 0) + nq;
   if (dc) n += 2 * (size_t)KC * (V + 1) + 2 * (size_t)V * D + (size_t)(KC * D > V ? KC * D : V);
   return n * sizeof(float);
 }
@@ -249,21 +251,28 @@ __global__ __launch_bounds__(256) void vqb_merge_kernel(const float* __restrict_
 // ---- backward ---------------------------------------------------------------------------------------------------------------
 // blockDim.x = V vectors per tile.  LDS: cb [L][DP] when CBL | dq [L] = dpmf / M | with a partial: pt, ddt [KC][V + 1] | xt, dyt
 // [V][D] | red [max(V, KC D)].  partial: this block's [L][D] sums, or nullptr: no code-book gradient.
-template <typename T, int DP, bool CBL>
+// GM: the second term of dp[m][k].  0: dq[k] = dpmf[k] / M, G unused (jpdse_vq_quantize_bwd, and the grouped call without a
+// dhist); 1: dpmf IS dhist [G][L], staged in LDS as dq [G][L + 1] (the odd stride: lanes of different groups on different
+// banks) and read at the vector's group (m % G); 2: a dhist too large for LDS, read from global memory.
+template <typename T, int DP, bool CBL, int GM>
 __global__ __launch_bounds__(256) void vqb_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x, const float* __restrict__ c,
-                                                     const float* __restrict__ dpmf, int M, int D, int L, float sigma, int vec,
+                                                     const float* __restrict__ dpmf, int M, int D, int L, int G, float sigma, int vec,
                                                      T* __restrict__ dx, float* __restrict__ partial) {
   extern __shared__ float vqb_lds[];
   const int V = blockDim.x;
   const int KC = L < kVqbChunk ? L : kVqbChunk;
   float* dq = vqb_lds + (CBL ? L * DP : 0);
-  float* pt = dq + L;
+  float* pt = dq + (GM == 1 ? G * (L + 1) : (GM == 2 ? 0 : L));
   float* ddt = pt + KC * (V + 1);
   float* xt = ddt + KC * (V + 1);
   float* dyt = xt + V * D;
   float* red = dyt + V * D;
   if (CBL) vqb_stage(c, vqb_lds, D, L, DP);
-  for (int k = threadIdx.x; k < L; k += V) dq[k] = dpmf != nullptr ? dpmf[k] / (float)M : 0.f;
+  if constexpr (GM == 0) {
+    for (int k = threadIdx.x; k < L; k += V) dq[k] = dpmf != nullptr ? dpmf[k] / (float)M : 0.f;
+  } else if constexpr (GM == 1) {
+    for (int i = threadIdx.x; i < G * L; i += V) dq[(i / L) * (L + 1) + i % L] = dpmf[i];
+  }
   __syncthreads();
   const float* cc = CBL ? vqb_lds : c;
   const int ld = CBL ? DP : D;
@@ -284,6 +293,10 @@ __global__ __launch_bounds__(256) void vqb_bwd_kernel(const T* __restrict__ dy, 
       vqb_load_row<T, DP>(x + row, D, vec != 0, xr);
       vqb_load_row<T, DP>(dy + row, D, vec != 0, gr);
     }
+    // this vector's row of the second term of dp (a vector past M reads group 0's row: inside the table, never used)
+    const float* dqr = dq;
+    if constexpr (GM == 1) dqr = dq + (live ? (m0 + t) % G : 0) * (L + 1);
+    if constexpr (GM == 2) dqr = dpmf + (size_t)(live ? (m0 + t) % G : 0) * L;
     float dmin = INFINITY;
     for (int k = 0; k < L; ++k) {
       const float d = vqb_score<DP, CBL>(xr, cc + k * ld, D);
@@ -293,7 +306,7 @@ __global__ __launch_bounds__(256) void vqb_bwd_kernel(const T* __restrict__ dy, 
     for (int k = 0; k < L; ++k) {
       const float* ck = cc + k * ld;
       const float e = vqb_weight(vqb_score<DP, CBL>(xr, ck, D), dmin, sigma);
-      const float q = vqb_dot<DP, CBL>(gr, ck, D) + dq[k];
+      const float q = vqb_dot<DP, CBL>(gr, ck, D) + dqr[k];
       s += e;
       pd = __fmaf_rn(e, q, pd);
     }
@@ -311,7 +324,7 @@ __global__ __launch_bounds__(256) void vqb_bwd_kernel(const T* __restrict__ dy, 
       for (int kk = 0; kk < kc; ++kk) {
         const float* ck = cc + (k0 + kk) * ld;
         const float p = vqb_weight(vqb_score<DP, CBL>(xr, ck, D), dmin, sigma) / s;
-        const float q = vqb_dot<DP, CBL>(gr, ck, D) + dq[k0 + kk];
+        const float q = vqb_dot<DP, CBL>(gr, ck, D) + dqr[k0 + kk];
         const float dd = -sigma * (p * (q - pd));
 #pragma unroll
         for (int j = 0; j < DP; ++j)
@@ -353,6 +366,205 @@ __global__ __launch_bounds__(256) void vqb_bwd_kernel(const T* __restrict__ dy, 
   }
 }
 
+// ---- rate term: per-group histograms of p (include/jpdse.h, "the rate term on per-group histograms") ---------
+// Group of a vector: m % G.  One thread per vector as above; p = e * (1 / s), or the one-hot of the arg-min with `hard`.
+//   vqr_hist_kernel          G a power of two <= 64 whose [G][L + 1] table per wave fits kVqrSlabBytes with 4, 2 or 1 waves per
+//                            block (= 256, 128 or 64 vectors per tile, all multiples of G: the group of a lane is lane % G).  Per
+//                            centre the lanes of a group are summed across the wave with xor-shuffles, offsets 32, 16, .. G (hard:
+//                            the group's bits of a ballot are counted, exact), lane g < G adds the sum into the wave's own table
+//                            (stride L + 1: the G owners on different banks), tile after tile; the waves are merged in order at the end.
+//   vqr_hist_general_kernel  any other G: chunks of KC centres go to LDS ([KC][257]), thread (slot j < min(G, vectors), kk) sums
+//                            the vectors j, j + G, .. of the tile ascending and adds the sum to the block's partial in the
+//                            workspace (zeroed by the block; a barrier after every chunk orders the tiles).
+//   vqr_final_kernel         one block: the partials in block order in fp64, then q, bits, rate and dhist in fp64.
+// No atomics; grid, tile and path are functions of (M, L, G) alone.
+constexpr int kVqrBlocks = 512;              // cap of the blocks (= fp32 partials [G][L]) of the histogram launch
+constexpr int kVqrPartialWords = 1 << 22;    // cap of blocks * G * L: a workspace of at most 16 MiB
+constexpr int kVqrSlabBytes = 49152;         // the per-wave tables of a block; with the staged code book below 64 KiB
+constexpr int kVqrFinalThreads = 1024;
+
+// waves per block of the shuffle path; 0: the general path
+static inline int vqr_waves(int D, int L, int G) {
+  if (G < 1 || G > 64 || (G & (G - 1)) != 0) return 0;
+  const size_t slab = (size_t)G * (L + 1) * sizeof(float);
+  for (int w = 4; w >= 1; w >>= 1)
+    if (w * slab <= (size_t)kVqrSlabBytes) return w;
+  return 0;
+}
+static inline int vqr_tile(int D, int L, int G) { return vqr_waves(D, L, G) > 0 ? 64 * vqr_waves(D, L, G) : 256; }
+static inline int vqr_blocks(int M, int L, int G) {
+  const int V = vqr_tile(0, L, G);
+  const int tiles = (M + V - 1) / V;
+  int cap = kVqrPartialWords / (G * L);
+  cap = cap < 1 ? 1 : (cap > kVqrBlocks ? kVqrBlocks : cap);
+  return tiles < cap ? tiles : cap;
+}
+static inline size_t vqr_workspace_bytes(int M, int L, int G) { return (size_t)vqr_blocks(M, L, G) * G * L * sizeof(float); }
+static inline size_t vqr_lds(int D, int L, int G) {
+  const int w = vqr_waves(D, L, G);
+  size_t n = vqb_cb_lds(D, L) ? (size_t)L * vqb_dp(D) : 0;
+  n += w > 0 ? (size_t)w * G * (L + 1) : (size_t)vqb_chunk(L) * 257;
+  return n * sizeof(float);
+}
+
+// LDS: cb [L][DP] when CBL | slab [waves][G][L + 1].  partial: this block's [G][L] sums
+template <typename T, int DP, bool CBL>
+__global__ __launch_bounds__(256) void vqr_hist_kernel(const T* __restrict__ x, const float* __restrict__ c, int M, int D, int L, int G,
+                                                      float sigma, int hard, int vec, float* __restrict__ partial) {
+  extern __shared__ float vqb_lds[];
+  const int V = blockDim.x, LS = L + 1, nw = V >> 6;
+  float* slab = vqb_lds + (CBL ? L * DP : 0);
+  if (CBL) vqb_stage(c, vqb_lds, D, L, DP);
+  for (int i = threadIdx.x; i < nw * G * LS; i += V) slab[i] = 0.f;
+  __syncthreads();
+  const float* cc = CBL ? vqb_lds : c;
+  const int ld = CBL ? DP : D;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const bool owner = lane < G;
+  float* mine = slab + wave * G * LS + (owner ? lane : 0) * LS;     // the owner's row of the wave's table
+  unsigned long long gmask = 0;                                     // the lanes of this lane's group
+  for (int b = lane % G; b < 64; b += G) gmask |= 1ull << b;
+  const int ntiles = (M + V - 1) / V;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int m0 = tile * V;                                        // a multiple of G: the group of vector m0 + t is lane % G
+    const int nv = M - m0 < V ? M - m0 : V;
+    const bool live = t < nv;
+    float xr[DP];
+#pragma unroll
+    for (int j = 0; j < DP; ++j) xr[j] = 0.f;
+    if (live) vqb_load_row<T, DP>(x + (size_t)(m0 + t) * D, D, vec != 0, xr);
+    float dmin = INFINITY;
+    int bk = 0;
+    for (int k = 0; k < L; ++k) {
+      const float d = vqb_score<DP, CBL>(xr, cc + k * ld, D);
+      if (d < dmin) {
+        dmin = d;
+        bk = k;
+      }
+    }
+    if (hard) {
+      for (int k = 0; k < L; ++k) {
+        const unsigned long long hit = __ballot(live && bk == k);
+        if (hit != 0 && owner) mine[k] += (float)__popcll(hit & gmask);
+      }
+    } else {
+      float s = 0.f;
+      for (int k = 0; k < L; ++k) s += vqb_weight(vqb_score<DP, CBL>(xr, cc + k * ld, D), dmin, sigma);
+      const float inv = 1.f / s;
+      for (int k = 0; k < L; ++k) {
+        float v = live ? vqb_weight(vqb_score<DP, CBL>(xr, cc + k * ld, D), dmin, sigma) * inv : 0.f;
+        for (int off = 32; off >= G; off >>= 1) v += __shfl_xor(v, off, 64);
+        if (owner) mine[k] += v;
+      }
+    }
+  }
+  __syncthreads();
+  float* out = partial + (size_t)blockIdx.x * G * L;
+  for (int i = t; i < G * L; i += V) {
+    const int g = i / L, k = i - g * L;
+    float acc = 0.f;
+    for (int w = 0; w < nw; ++w) acc += slab[(w * G + g) * LS + k];
+    out[i] = acc;
+  }
+}
+
+// LDS: cb [L][DP] when CBL | pt [KC][257].  partial: this block's [G][L] sums, zeroed here and added to tile after tile
+template <typename T, int DP, bool CBL>
+__global__ __launch_bounds__(256) void vqr_hist_general_kernel(const T* __restrict__ x, const float* __restrict__ c, int M, int D,
+                                                              int L, int G, float sigma, int hard, int vec, float* partial) {
+  extern __shared__ float vqb_lds[];
+  constexpr int V = 256;
+  const int KC = L < kVqbChunk ? L : kVqbChunk;
+  float* pt = vqb_lds + (CBL ? L * DP : 0);
+  if (CBL) vqb_stage(c, vqb_lds, D, L, DP);
+  const int t = threadIdx.x;
+  float* mine = partial + (size_t)blockIdx.x * G * L;
+  for (int i = t; i < G * L; i += V) mine[i] = 0.f;
+  __syncthreads();
+  const float* cc = CBL ? vqb_lds : c;
+  const int ld = CBL ? DP : D;
+  const int ntiles = (M + V - 1) / V;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int m0 = tile * V;
+    const int nv = M - m0 < V ? M - m0 : V;
+    const bool live = t < nv;
+    float xr[DP];
+#pragma unroll
+    for (int j = 0; j < DP; ++j) xr[j] = 0.f;
+    if (live) vqb_load_row<T, DP>(x + (size_t)(m0 + t) * D, D, vec != 0, xr);
+    float dmin = INFINITY;
+    int bk = 0;
+    for (int k = 0; k < L; ++k) {
+      const float d = vqb_score<DP, CBL>(xr, cc + k * ld, D);
+      if (d < dmin) {
+        dmin = d;
+        bk = k;
+      }
+    }
+    float inv = 1.f;
+    if (!hard) {
+      float s = 0.f;
+      for (int k = 0; k < L; ++k) s += vqb_weight(vqb_score<DP, CBL>(xr, cc + k * ld, D), dmin, sigma);
+      inv = 1.f / s;
+    }
+    const int ns = G < nv ? G : nv;            // slot j holds the tile's vectors j, j + G, ..: group (m0 + j) % G
+    for (int k0 = 0; k0 < L; k0 += KC) {
+      const int kc = L - k0 < KC ? L - k0 : KC;
+      if (live)
+        for (int kk = 0; kk < kc; ++kk) {
+          const int k = k0 + kk;
+          pt[kk * (V + 1) + t] = hard ? (bk == k ? 1.f : 0.f) : vqb_weight(vqb_score<DP, CBL>(xr, cc + k * ld, D), dmin, sigma) * inv;
+        }
+      __syncthreads();
+      for (int w = t; w < kc * ns; w += V) {
+        const int j = w / kc, kk = w - j * kc;
+        float acc = 0.f;
+        for (int v = j; v < nv; v += G) acc += pt[kk * (V + 1) + v];
+        const int g = (m0 + j) % G;
+        mine[(size_t)g * L + k0 + kk] += acc;
+      }
+      __syncthreads();                         // pt is free again; the block's adds to `mine` are ordered tile by tile
+    }
+  }
+}
+
+// hist[i] = sum_b partial[b][i] (b ascending, fp64), i = g L + k; n = M / G.  One block of kVqrFinalThreads threads
+__global__ __launch_bounds__(kVqrFinalThreads) void vqr_final_kernel(const float* __restrict__ partial, int nb, int G, int L, double n,
+                                                                    double scale, double denom, float* __restrict__ hist,
+                                                                    float* __restrict__ rate, float* __restrict__ dhist) {
+  __shared__ double red[kVqrFinalThreads];
+  __shared__ double red2[32];
+  const int E = G * L, t = threadIdx.x;
+  double mysum = 0.0;
+  for (int i = t; i < E; i += kVqrFinalThreads) {
+    double acc = 0.0;
+#pragma unroll 8
+    for (int b = 0; b < nb; ++b) acc += (double)partial[(size_t)b * E + i];
+    double term = 0.0, dh = 0.0;
+    if (acc > 0.0) {
+      const double lq = log2(acc / n);
+      term = acc * lq;
+      dh = scale * (-(lq + 1.4426950408889634)) / denom;      // 1 / ln 2
+    }
+    mysum += term;
+    if (hist != nullptr) hist[i] = (float)acc;
+    if (dhist != nullptr) dhist[i] = (float)dh;
+  }
+  red[t] = mysum;
+  __syncthreads();
+  if (t < 32) {
+    double a = 0.0;
+    for (int u = 0; u < 32; ++u) a += red[t * 32 + u];
+    red2[t] = a;
+  }
+  __syncthreads();
+  if (t == 0) {
+    double a = 0.0;
+    for (int u = 0; u < 32; ++u) a += red2[u];
+    rate[0] = (float)((0.0 - a) / denom);
+  }
+}
+
 template <typename... P, typename... A>
 static inline int vqb_launch(const char* what, void (*kernel)(P...), int grid, int threads, size_t lds, void* stream, A... args) {
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, as_stream(stream), static_cast<P>(args)...);
@@ -388,6 +600,49 @@ static int vqb_common_check(const char* who, int dtype, int M, int D, int L, flo
   if (int rc = vq_shape_check(who, M, D, L)) return rc;
   JPDSE_REQUIRE(isfinite(sigma) && sigma > 0.f, "%s: sigma is %g (a finite value > 0)", who, (double)sigma);
   return JPDSE_OK;
+}
+
+static int vqr_group_check(const char* who, int M, int L, int G) {
+  JPDSE_REQUIRE(G >= 1, "%s: G = %d groups (at least 1)", who, G);
+  JPDSE_REQUIRE(M % G == 0, "%s: G = %d does not divide M = %d", who, G, M);
+  JPDSE_REQUIRE((long long)G * L <= 65536, "%s: G * L = %lld (at most 65536)", who, (long long)G * L);
+  return JPDSE_OK;
+}
+
+// both backward entry points after their shape checks.  second: dpmf [L] (grouped false) or dhist [G][L] (grouped true), or NULL
+static int vqb_bwd_run(const char* who, int dtype, int M, int D, int L, int G, float sigma, const void* dy, const void* x,
+                       const float* code_book, const float* second, bool grouped, void* dx, float* dcode_book, void* ws,
+                       size_t ws_bytes, void* stream) {
+  JPDSE_REQUIRE(dy && x && code_book, "%s: null pointer", who);
+  float* partial = nullptr;
+  if (dcode_book != nullptr) {
+    const size_t need = vqb_workspace_bytes(M, D, L);
+    JPDSE_REQUIRE(ws != nullptr && ws_bytes >= need, "%s: workspace too small (%zu bytes, %zu needed)", who,
+                  ws ? ws_bytes : (size_t)0, need);
+    partial = mptr<float>(ws);
+  }
+  if (dx == nullptr && partial == nullptr) return JPDSE_OK;
+  const int V = vqb_bwd_threads(D), nb = vqb_blocks(M, V);
+  const int vec = vqb_vec(dtype, D, {x, dy, dx});
+  // a dhist goes to LDS when the block's LDS stays below 64000 bytes with it, otherwise it is read from global memory
+  int gm = 0;
+  if (grouped) gm = vqb_bwd_lds(D, L, partial != nullptr, (size_t)G * (L + 1)) <= 64000 ? 1 : 2;
+  const size_t lds = vqb_bwd_lds(D, L, partial != nullptr, gm == 1 ? (size_t)G * (L + 1) : (gm == 2 ? 0 : (size_t)L));
+  if (int rc = vqb_dispatch(dtype, D, L, [&](auto tag, auto dp, auto cbl) {
+        using T = decltype(tag);
+        constexpr int DPv = decltype(dp)::value;
+        constexpr bool CBLv = decltype(cbl)::value;
+        auto go = [&](auto kernel) {
+          return vqb_launch(who, kernel, nb, V, lds, stream, cptr<T>(dy), cptr<T>(x), code_book, second, M, D, L, G, sigma, vec,
+                            mptr<T>(dx), partial);
+        };
+        if (gm == 1) return go(vqb_bwd_kernel<T, DPv, CBLv, 1>);
+        if (gm == 2) return go(vqb_bwd_kernel<T, DPv, CBLv, 2>);
+        return go(vqb_bwd_kernel<T, DPv, CBLv, 0>);
+      }))
+    return rc;
+  if (partial == nullptr) return JPDSE_OK;
+  return vqb_launch(who, vqb_merge_kernel, ew_blocks(L * D), 256, 0, stream, partial, nb, L * D, dcode_book);
 }
 
 }  // namespace jpdse
@@ -430,28 +685,53 @@ int jpdse_vq_quantize_fwd(const jpdse_vq_quantize_fwd_args* a) {
 int jpdse_vq_quantize_bwd(const jpdse_vq_quantize_bwd_args* a) {
   JPDSE_REQUIRE(a != nullptr, "vq_quantize_bwd: null argument struct");
   if (int rc = vqb_common_check("vq_quantize_bwd", a->dtype, a->M, a->D, a->L, a->sigma)) return rc;
-  JPDSE_REQUIRE(a->dy && a->x && a->code_book, "vq_quantize_bwd: null pointer");
-  const int M = a->M, D = a->D, L = a->L;
-  float* partial = nullptr;
-  if (a->dcode_book != nullptr) {
-    const size_t need = vqb_workspace_bytes(M, D, L);
-    JPDSE_REQUIRE(a->ws != nullptr && a->ws_bytes >= need, "vq_quantize_bwd: workspace too small (%zu bytes, %zu needed)",
-                  a->ws ? a->ws_bytes : (size_t)0, need);
-    partial = mptr<float>(a->ws);
-  }
-  if (a->dx == nullptr && partial == nullptr) return JPDSE_OK;
-  const int V = vqb_bwd_threads(D), nb = vqb_blocks(M, V);
-  const int vec = vqb_vec(a->dtype, D, {a->x, a->dy, a->dx});
-  const size_t lds = vqb_bwd_lds(D, L, partial != nullptr);
+  return vqb_bwd_run("vq_quantize_bwd", a->dtype, a->M, a->D, a->L, 1, a->sigma, a->dy, a->x, a->code_book, a->dpmf, false, a->dx,
+                     a->dcode_book, a->ws, a->ws_bytes, a->stream);
+}
+
+int jpdse_vq_quantize_bwd_grouped(const jpdse_vq_quantize_bwd_grouped_args* a) {
+  JPDSE_REQUIRE(a != nullptr, "vq_quantize_bwd_grouped: null argument struct");
+  if (int rc = vqb_common_check("vq_quantize_bwd_grouped", a->dtype, a->M, a->D, a->L, a->sigma)) return rc;
+  if (int rc = vqr_group_check("vq_quantize_bwd_grouped", a->M, a->L, a->G)) return rc;
+  return vqb_bwd_run("vq_quantize_bwd_grouped", a->dtype, a->M, a->D, a->L, a->G, a->sigma, a->dy, a->x, a->code_book, a->dhist,
+                     a->dhist != nullptr, a->dx, a->dcode_book, a->ws, a->ws_bytes, a->stream);
+}
+
+size_t jpdse_vq_rate_workspace_size(int32_t M, int32_t D, int32_t L, int32_t G) {
+  if (vq_shape_check("vq_rate_workspace_size", M, D, L) != JPDSE_OK) return 0;
+  if (vqr_group_check("vq_rate_workspace_size", M, L, G) != JPDSE_OK) return 0;
+  return vqr_workspace_bytes(M, L, G);
+}
+
+int jpdse_vq_rate_fwd(const jpdse_vq_rate_fwd_args* a) {
+  JPDSE_REQUIRE(a != nullptr, "vq_rate_fwd: null argument struct");
+  if (int rc = vqb_common_check("vq_rate_fwd", a->dtype, a->M, a->D, a->L, a->sigma)) return rc;
+  if (int rc = vqr_group_check("vq_rate_fwd", a->M, a->L, a->G)) return rc;
+  JPDSE_REQUIRE(isfinite(a->scale), "vq_rate_fwd: scale is %g (a finite value)", (double)a->scale);
+  JPDSE_REQUIRE(isfinite(a->denom) && a->denom > 0.f, "vq_rate_fwd: denom is %g (a finite value > 0)", (double)a->denom);
+  JPDSE_REQUIRE(a->x && a->code_book && a->rate, "vq_rate_fwd: null pointer");
+  const int M = a->M, D = a->D, L = a->L, G = a->G;
+  const size_t need = vqr_workspace_bytes(M, L, G);
+  JPDSE_REQUIRE(a->ws != nullptr && a->ws_bytes >= need, "vq_rate_fwd: workspace too small (%zu bytes, %zu needed)",
+                a->ws ? a->ws_bytes : (size_t)0, need);
+  float* partial = mptr<float>(a->ws);
+  const int waves = vqr_waves(D, L, G), nb = vqr_blocks(M, L, G);
+  const int vec = vqb_vec(a->dtype, D, {a->x});
+  const int hard = a->hard != 0 ? 1 : 0;
+  const size_t lds = vqr_lds(D, L, G);
   if (int rc = vqb_dispatch(a->dtype, D, L, [&](auto tag, auto dp, auto cbl) {
         using T = decltype(tag);
-        return vqb_launch("vq_quantize_bwd", vqb_bwd_kernel<T, decltype(dp)::value, decltype(cbl)::value>, nb, V, lds, a->stream,
-                          cptr<T>(a->dy), cptr<T>(a->x), a->code_book, a->dpmf, M, D, L, a->sigma, vec, mptr<T>(a->dx), partial);
+        constexpr int DPv = decltype(dp)::value;
+        constexpr bool CBLv = decltype(cbl)::value;
+        if (waves > 0)
+          return vqb_launch("vq_rate_fwd", vqr_hist_kernel<T, DPv, CBLv>, nb, 64 * waves, lds, a->stream, cptr<T>(a->x),
+                            a->code_book, M, D, L, G, a->sigma, hard, vec, partial);
+        return vqb_launch("vq_rate_fwd", vqr_hist_general_kernel<T, DPv, CBLv>, nb, 256, lds, a->stream, cptr<T>(a->x),
+                          a->code_book, M, D, L, G, a->sigma, hard, vec, partial);
       }))
     return rc;
-  if (partial == nullptr) return JPDSE_OK;
-  return vqb_launch("vq_quantize_bwd(merge)", vqb_merge_kernel, ew_blocks(L * D), 256, 0, a->stream, partial, nb, L * D,
-                    a->dcode_book);
+  return vqb_launch("vq_rate_fwd(final)", vqr_final_kernel, 1, kVqrFinalThreads, 0, a->stream, partial, nb, G, L, (double)(M / G),
+                    (double)a->scale, (double)a->denom, a->hist, a->rate, a->dhist);
 }
 
 }  // extern "C"

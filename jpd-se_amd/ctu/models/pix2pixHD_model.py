@@ -76,7 +76,7 @@ class Pix2PixHDModel(BaseModel):
     opt.pkl parses unchanged; flags of branches outside the accelerated path are accepted here and refused in
     __init__ when they would change the computation.  Extensions: --compute_dtype, --skip_unused_losses,
     --vgg19_state_dict, --vgg_random_init, --lambda_rate, --class_distortion_weights, --edge_distortion_weight,
-    --encoder_quantizer, --vq_n_center, --vq_center_size, --vq_sigma, --vq_soft_forward."""
+    --encoder_quantizer, --vq_n_center, --vq_center_size, --vq_sigma, --vq_soft_forward, --lambda_vq_rate."""
     a = parser.add_argument
     a('--num_D', type=int, default=2)
     a('--n_layers_D', type=int, default=3)
@@ -176,6 +176,10 @@ class Pix2PixHDModel(BaseModel):
     a('--vq_soft_forward', action='store_true',
       help='--encoder_quantizer s2hvq: train on the soft assignment\'s mix of the centres instead of the nearest centre (the '
            'gradient is the soft form\'s either way); eval mode always takes the nearest centre')
+    a('--lambda_vq_rate', type=float, default=0.0,
+      help='extension (DESIGN.md 4.16): weight of the rate term of --encoder_quantizer s2hvq in the generator / encoder loss '
+           '-- the entropy of the soft assignment\'s histogram per channel group (the model the .jpdv coder adapts to), in '
+           'bits per pixel of the local batch; 0 (default): no rate term, the step is what it was')
     a('--vgg_random_init', action='store_true',
       help='extension: explicitly accept a seeded random-weight VGG19 for the VGG loss (tests, benchmarks); without '
            'this flag training with the VGG loss and no --vgg19_state_dict is refused')
@@ -218,6 +222,14 @@ class Pix2PixHDModel(BaseModel):
     if self.lambda_rate > 0.0 and (not feat_enc or g('no_encoder_binarization') or g('zero_vis')):
       raise ValueError('lambda_rate > 0 needs the learned codec with encoder binarization (--no_feat_encoding and '
                        '--no_encoder_binarization must both be off) and an encoder that runs (no --zero_vis)')
+    # rate term of the vector-quantizer bottleneck
+    lvr = g('lambda_vq_rate', 0.0)
+    self.lambda_vq_rate = float(0.0 if lvr is None or lvr is False else lvr)
+    if not (self.lambda_vq_rate >= 0.0 and self.lambda_vq_rate != float('inf')):
+      raise ValueError('lambda_vq_rate must be a finite non-negative number, got %r' % (lvr,))
+    if self.lambda_vq_rate > 0.0 and (g('encoder_quantizer', 'binarizer') != 's2hvq' or g('zero_vis')):
+      raise ValueError('lambda_vq_rate > 0 is the rate term of the vector-quantizer bottleneck: it needs --encoder_quantizer '
+                       's2hvq and an encoder that runs (no --zero_vis)')
     # vector-quantizer bottleneck: refused combinations before any network (hence any device allocation) exists
     self.use_vq = False
     if g('encoder_quantizer', 'binarizer') not in ('binarizer', 's2hvq'):
@@ -616,6 +628,17 @@ class Pix2PixHDModel(BaseModel):
       pre = self.preprocess(x_dict, build_base=False)
       return self._encoder_eval(lambda: self.netE.vq_code(pre['src'])).to(torch.int64)
 
+  def get_vq_rate(self, x_dict):
+    """The hard-mode rate term of the eval-mode code in bits per pixel of the batch, a Python float: the
+    zero-order entropy of get_vq_code(x_dict) per channel group, histograms taken over the batch.  An estimate, not a size:
+    get_coded_rate measures the .jpdv files, whose adaptive coder may land on either side of it."""
+    self._require_vq('get_vq_rate')
+    with torch.no_grad():
+      pre = self.preprocess(x_dict, build_base=False)
+      src = pre['src']
+      value = self._encoder_eval(lambda: self.netE.vq_rate(src, src.N * src.H * src.W))
+      return float(value.item())
+
   def _decode_vq_act(self, code, x_dict, who='decode'):
     """decode() of a vector-quantised code up to the generator's NHWC output; also returns the device label map."""
     N, H, W, code_len, L, _ = self._vq_geometry(x_dict, who)
@@ -924,11 +947,17 @@ class Pix2PixHDModel(BaseModel):
         rate_bin = self.netE._binarizer if (self.lambda_rate > 0.0 and grad_w is not None) else None
         if rate_bin is not None:
           rate_bin.rate_scale, rate_bin.rate_pixels = self.lambda_rate, H * W
+        # --lambda_vq_rate: the same for the vector-quantizer bottleneck -- bits per pixel of the local batch
+        rate_vq = self.netE._vq if (self.lambda_vq_rate > 0.0 and grad_w is not None) else None
+        if rate_vq is not None:
+          rate_vq.rate_scale, rate_vq.rate_denom = self.lambda_vq_rate, B * H * W
         try:
           vis, e_ctx = self.netE.fwd(src)
         finally:
           if rate_bin is not None:
             rate_bin.rate_scale = None
+          if rate_vq is not None:
+            rate_vq.rate_scale = None
         if self.netE.training:
           self.codec_draw += 1
       if self.zero_sem:
@@ -986,6 +1015,8 @@ class Pix2PixHDModel(BaseModel):
     rate_value = None
     if self.lambda_rate > 0.0 and grad_w is not None and e_ctx is not None:
       rate_value = self.netE._binarizer.rate_value
+    if self.lambda_vq_rate > 0.0 and grad_w is not None and e_ctx is not None:
+      rate_value = self.netE._vq.rate_value
     if rate_value is not None:
       layout['rate'] = o + 1
     slots = torch.zeros(o + (1 if rate_value is None else 2), dtype=torch.float32, device=dev)

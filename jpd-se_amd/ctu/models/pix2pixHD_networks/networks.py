@@ -330,6 +330,12 @@ class Encoder(nn.Module):
     h, _ = run_chain_fwd(self._pre, x)
     return vq.code(h)
 
+  def vq_rate(self, x, denom):
+    """fp32 [1]: the zero-order entropy of vq_code(x) per channel group over the batch, in bits / denom."""
+    vq = self._require_vq()
+    h, _ = run_chain_fwd(self._pre, x)
+    return vq.rate(h, denom)
+
   def decode_vq_code(self, index, H, W):
     """The receiver's half: (features, status) from the int32 [N, h * w * cout / D] indices of an H x W image (ops.vq_decode,
     then model[4 + 3n + 1:]); status: the device word of ops.vq_decode, non-zero for an index outside the code book."""

@@ -113,6 +113,27 @@ class _Quantize(torch.autograd.Function):
     return dx, dc, None, None, None
 
 
+class _Rate(torch.autograd.Function):
+  """rate fp32 [1] of ops.vq_rate_fwd; backward: ops.vq_quantize_bwd(groups, dhist) with dy = 0, dhist scaled
+  by the incoming gradient."""
+
+  @staticmethod
+  def forward(ctx, x, code_book, sigma, groups, denom, hard):
+    x, code_book = x.contiguous(), code_book.contiguous()
+    rate, _, dhist = ops.vq_rate_fwd(x, code_book, sigma, groups, denom, 1.0, hard=hard)
+    ctx.save_for_backward(x, code_book, dhist)
+    ctx.sigma, ctx.groups = sigma, groups
+    return rate
+
+  @staticmethod
+  def backward(ctx, drate):
+    x, code_book, dhist = ctx.saved_tensors
+    dx, dc = ops.vq_quantize_bwd(torch.zeros_like(x), x, code_book, ctx.sigma, want_dx=ctx.needs_input_grad[0],
+                                 want_dc=ctx.needs_input_grad[1], groups=ctx.groups,
+                                 dhist=(dhist * drate.to(torch.float32).reshape(())).contiguous())
+    return dx, dc, None, None, None, None
+
+
 class S2HVQ(nn.Module):
   """code_book: tensor [n_center, center_size], learnable (parameter `_code_book`); sigma > 0: the hardness of the soft
   assignment used in training."""
@@ -198,6 +219,28 @@ class S2HVQ(nn.Module):
       y, index, pmf = ops.vq_quantize_fwd(xm.detach(), self.code_book.detach().contiguous(), float(self._sigma),
                                           bool(hard_forward) or not self.training, bool(want_pmf))
     return y.view(n, code_len * self._center_size), index.to(torch.int64).view(n, code_len), (pmf if want_pmf else None)
+
+  def rate(self, x, code_len, groups=1, denom=None, hard=False):
+    """The rate term on per-group histograms: x [n, d] as in quantize; vector m of the [n * code_len,
+    center_size] matrix belongs to group m % groups (groups must divide n * code_len).  Returns the 0-dim float32
+    -sum_g sum_k hist[g][k] log2(hist[g][k] / (M / groups)) / denom with hist the per-group sums of the soft assignment (hard:
+    of the one-hot of the nearest centre); denom defaults to M = n * code_len: bits per index.  Differentiable in x and the code
+    book when gradients are enabled (the gradient is the soft form's, also with hard); [M, n_center] is never stored.  With
+    groups = 1, rate * denom / M is get_cross_entropy(pmf, pmf) of pmf = get_pmf(encode(x, code_len))."""
+    xm = self._vectors(x, code_len)
+    M, groups = xm.size(0), int(groups)
+    if groups < 1 or M % groups != 0:
+      raise ValueError('groups must divide n * code_len, got {} and {}'.format(groups, M))
+    if groups * self.code_book.size(0) > 65536:
+      raise NotImplementedError('S2HVQ.rate: groups * n_center = %d, the kernels take at most 65536' % (groups * self.code_book.size(0)))
+    denom = float(M if denom is None else denom)
+    if not (denom > 0 and denom != float('inf')):
+      raise ValueError('denom must be a finite number > 0, got {}'.format(denom))
+    if torch.is_grad_enabled() and (xm.requires_grad or self.code_book.requires_grad):
+      return _Rate.apply(xm, self.code_book, float(self._sigma), groups, denom, bool(hard)).reshape(())
+    value, _, _ = ops.vq_rate_fwd(xm.detach(), self.code_book.detach().contiguous(), float(self._sigma), groups, denom,
+                                  hard=bool(hard), want_grad=False)
+    return value.reshape(())
 
   def decode(self, code_raw):
     """code_raw [n, code_len, n_center] (e.g. encode(..., raw=True)) -> [n, code_len * center_size]: the centre with the highest

@@ -140,6 +140,13 @@ class Pix2PixHDTrainer(BaseTrainer):
     self.eval()
     return self.model.get_vq_code(x_dict)
 
+  def get_vq_rate(self, x_dict):
+    """The entropy estimate of the vector-quantised code in bits per pixel (extension), a Python float: the
+    hard-mode rate term of --lambda_vq_rate on the eval-mode code -- the zero-order entropy of get_vq_code(x_dict) per channel
+    group, histograms over the batch.  An estimate, not a size, with no fixed order against get_coded_rate's coded figure."""
+    self.eval()
+    return self.model.get_vq_rate(x_dict)
+
   def get_eval_rate(self, x_dict):
     """(Shannon bpp in nats as the reference computes it, raw bpp) of the learned codec (pix2pixHD_trainer.py:106-110)."""
     self.eval()

@@ -163,6 +163,21 @@ class VqQuantizeBwdArgs(ctypes.Structure):
               ('ws_bytes', ctypes.c_size_t), ('stream', ctypes.c_void_p)]
 
 
+# the rate term of the vector-quantizer bottleneck (vq_bottleneck.hip)
+class VqRateFwdArgs(ctypes.Structure):
+  _fields_ = [(n, ctypes.c_int32) for n in ('dtype', 'M', 'D', 'L', 'G')] + \
+             [('sigma', ctypes.c_float), ('hard', ctypes.c_int32), ('x', ctypes.c_void_p), ('code_book', ctypes.c_void_p),
+              ('scale', ctypes.c_float), ('denom', ctypes.c_float), ('hist', ctypes.c_void_p), ('rate', ctypes.c_void_p),
+              ('dhist', ctypes.c_void_p), ('ws', ctypes.c_void_p), ('ws_bytes', ctypes.c_size_t), ('stream', ctypes.c_void_p)]
+
+
+class VqQuantizeBwdGroupedArgs(ctypes.Structure):
+  _fields_ = [(n, ctypes.c_int32) for n in ('dtype', 'M', 'D', 'L', 'G')] + \
+             [('sigma', ctypes.c_float), ('dy', ctypes.c_void_p), ('x', ctypes.c_void_p), ('code_book', ctypes.c_void_p),
+              ('dhist', ctypes.c_void_p), ('dx', ctypes.c_void_p), ('dcode_book', ctypes.c_void_p), ('ws', ctypes.c_void_p),
+              ('ws_bytes', ctypes.c_size_t), ('stream', ctypes.c_void_p)]
+
+
 _P, _I32, _I64, _F, _SZ = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float,
                            ctypes.c_size_t)
 _CD, _ND = ctypes.POINTER(ConvDesc), ctypes.POINTER(InormDesc)
@@ -284,6 +299,9 @@ SIGNATURES = {
     'jpdse_vq_quantize_workspace_size': (_SZ, [_I32, _I32, _I32]),
     'jpdse_vq_quantize_fwd': (_I32, [ctypes.POINTER(VqQuantizeFwdArgs)]),
     'jpdse_vq_quantize_bwd': (_I32, [ctypes.POINTER(VqQuantizeBwdArgs)]),
+    'jpdse_vq_rate_workspace_size': (_SZ, [_I32, _I32, _I32, _I32]),
+    'jpdse_vq_rate_fwd': (_I32, [ctypes.POINTER(VqRateFwdArgs)]),
+    'jpdse_vq_quantize_bwd_grouped': (_I32, [ctypes.POINTER(VqQuantizeBwdGroupedArgs)]),
 }
 
 # the developer build (same sources, -DJPDSE_DEV): the shipped ABI plus include/jpdse_dev.h

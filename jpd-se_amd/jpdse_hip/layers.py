@@ -383,6 +383,12 @@ class HipVQBottleneck(nn.Module):
     self.cout, self.center_size, self.n_center = cout, center_size, n_center
     self.hard_forward = bool(hard_forward)
     self.grad_ready_hook = None
+    self.rate_scale, self.rate_denom, self.rate_value = None, 0, None
+
+  @property
+  def groups(self):
+    """Channel groups of a pixel: vector m of the [M][D] matrix belongs to group m % groups."""
+    return self.cout // self.center_size
 
   def _book(self):
     c = self.vq._code_book
@@ -407,7 +413,21 @@ class HipVQBottleneck(nn.Module):
   def fwd(self, x):
     h, c_conv = self.conv.fwd(x)
     y, _ = self._quantize(h, self.hard_forward or not self.training)
+    if self.rate_scale is not None:
+      # --lambda_vq_rate: the owner set rate_scale / rate_denom for this call; the value stays in rate_value
+      # and the gradient w.r.t. the per-group sums of the soft assignment travels with the context
+      self.rate_value, _, dhist = ops.vq_rate_fwd(h.t.view(-1, self.center_size), self._book().detach(), self.vq.sigma,
+                                                  self.groups, self.rate_denom, self.rate_scale)
+      return y, Ctx(c_conv, h, dhist)
     return y, Ctx(c_conv, h)
+
+  def rate(self, x, denom):
+    """fp32 [1]: the hard-mode rate of x's features (ops.vq_rate_fwd, hard): the zero-order entropy of code(x) per channel
+    group, in bits / denom."""
+    h, _ = self.conv.fwd(x)
+    value, _, _ = ops.vq_rate_fwd(h.t.view(-1, self.center_size), self._book().detach(), self.vq.sigma, self.groups, denom,
+                                  hard=True, want_grad=False)
+    return value
 
   def code(self, x):
     """int32 [N, h * w * cout / D]: the index of the nearest centre of every vector of x's features, in the layout above."""
@@ -425,12 +445,17 @@ class HipVQBottleneck(nn.Module):
   def bwd(self, ctx, dy, need_dx=True, need_dw=True):
     """dy: the gradient w.r.t. the quantized features.  Straight-through: the soft form's gradient, then the
     1x1 conv's data / weight gradients."""
-    c_conv, h = ctx.items
+    c_conv, h = ctx.items[:2]
     D = self.center_size
     book = self._book()
     want_dc = need_dw and book.requires_grad
-    dh, _ = ops.vq_quantize_bwd(dy.t.view(-1, D), h.t.view(-1, D), book.detach(), self.vq.sigma, None, want_dx=True,
-                                want_dc=want_dc, dc_out=self._cgrad_buffer() if want_dc else None)
+    if len(ctx.items) == 3:      # a forward with a rate scale: its dhist joins dp in the grouped backward
+      dh, _ = ops.vq_quantize_bwd(dy.t.view(-1, D), h.t.view(-1, D), book.detach(), self.vq.sigma, None, want_dx=True,
+                                  want_dc=want_dc, dc_out=self._cgrad_buffer() if want_dc else None, groups=self.groups,
+                                  dhist=ctx.items[2])
+    else:
+      dh, _ = ops.vq_quantize_bwd(dy.t.view(-1, D), h.t.view(-1, D), book.detach(), self.vq.sigma, None, want_dx=True,
+                                  want_dc=want_dc, dc_out=self._cgrad_buffer() if want_dc else None)
     if want_dc and self.grad_ready_hook is not None:
       self.grad_ready_hook(self)
     return self.conv.bwd(c_conv, Act(dh.view(h.t.shape), h.C), need_dx, need_dw)

@@ -11,7 +11,8 @@ import torch
 
 from . import (lib, check, JpdseError, F32, BF16, ConvDesc, InormDesc, EvalMetricsSemArgs, MsssimLossArgs, CodeRateArgs, SemLossArgs, CodeCostArgs, ACT_NONE, PAD_ZERO, PAD_REFLECT)
 from . import (VqSoftFwdArgs, VqHardFwdArgs, VqSoftBwdArgs, VqDecodeArgs, VqDecodeBwdArgs, VqArgmaxArgs, VqPmfArgs, VqPmfBwdArgs,
-               VqIndexEncodeArgs, VqIndexDecodeArgs, VqQuantizeFwdArgs, VqQuantizeBwdArgs)
+               VqIndexEncodeArgs, VqIndexDecodeArgs, VqQuantizeFwdArgs, VqQuantizeBwdArgs, VqRateFwdArgs,
+               VqQuantizeBwdGroupedArgs)
 
 
 def cpad(c):
@@ -1186,26 +1187,56 @@ def vq_quantize_fwd(x, code_book, sigma, hard_forward=True, want_pmf=False):
   return y, index, pmf
 
 
-def vq_quantize_bwd(dy, x, code_book, sigma, dpmf=None, want_dx=True, want_dc=True, dc_out=None):
+def vq_quantize_bwd(dy, x, code_book, sigma, dpmf=None, want_dx=True, want_dc=True, dc_out=None, groups=1, dhist=None):
   """(dx, dcode_book) of the SOFT form of vq_quantize_fwd -- the straight-through gradient of the hard one -- for the upstream
   gradients dy [M, D] (x's dtype) and, optionally, dpmf fp32 [L] (jpdse_vq_quantize_bwd; p is recomputed from x).  dx in x's
-  dtype, dcode_book fp32 [L, D] (written into dc_out when given); either is None when not wanted."""
+  dtype, dcode_book fp32 [L, D] (written into dc_out when given); either is None when not wanted.
+  groups / dhist: with either given the call is jpdse_vq_quantize_bwd_grouped -- vector m belongs to group
+  m % groups and dhist fp32 [groups, L], the gradient w.r.t. vq_rate_fwd's un-normalised sums, is added to dp at the vector's
+  group; it excludes dpmf.  The defaults take exactly the call above."""
   M, D, L = _vq_dims(x, code_book)
   assert dy.shape == x.shape and dy.dtype == x.dtype and dy.is_contiguous() and dy.device == x.device, (dy.dtype, tuple(dy.shape))
+  grouped = dhist is not None or int(groups) != 1
   if dpmf is not None:
+    assert not grouped, 'dpmf and groups / dhist exclude each other'
     assert dpmf.dtype == torch.float32 and dpmf.is_contiguous() and dpmf.numel() == L and dpmf.device == x.device
+  if dhist is not None:
+    assert dhist.dtype == torch.float32 and dhist.is_contiguous() and dhist.numel() == int(groups) * L and dhist.device == x.device
   dx = torch.empty_like(x) if want_dx else None
   dc = None
   if want_dc:
     dc = dc_out if dc_out is not None else torch.empty_like(code_book)
     assert dc.dtype == torch.float32 and dc.is_contiguous() and tuple(dc.shape) == (L, D) and dc.device == x.device
   ws = _vq_quantize_ws(M, D, L, x.device) if want_dc else None
+  tail = (dx.data_ptr() if want_dx else None, dc.data_ptr() if want_dc else None, ws.data_ptr() if want_dc else None,
+          ws.numel() if want_dc else 0, torch.cuda.current_stream().cuda_stream)
+  if grouped:
+    args = VqQuantizeBwdGroupedArgs(code_of(x.dtype), M, D, L, int(groups), float(sigma), dy.data_ptr(), x.data_ptr(),
+                                    code_book.data_ptr(), dhist.data_ptr() if dhist is not None else None, *tail)
+    check(lib().jpdse_vq_quantize_bwd_grouped(ctypes.byref(args)), 'vq_quantize_bwd_grouped')
+    return dx, dc
   args = VqQuantizeBwdArgs(code_of(x.dtype), M, D, L, float(sigma), dy.data_ptr(), x.data_ptr(), code_book.data_ptr(),
-                           dpmf.data_ptr() if dpmf is not None else None, dx.data_ptr() if want_dx else None,
-                           dc.data_ptr() if want_dc else None, ws.data_ptr() if want_dc else None,
-                           ws.numel() if want_dc else 0, torch.cuda.current_stream().cuda_stream)
+                           dpmf.data_ptr() if dpmf is not None else None, *tail)
   check(lib().jpdse_vq_quantize_bwd(ctypes.byref(args)), 'vq_quantize_bwd')
   return dx, dc
+
+
+def vq_rate_fwd(x, code_book, sigma, G, denom, scale=1.0, hard=False, want_hist=False, want_grad=True):
+  """(rate, hist, dhist) of the rate term on per-group histograms (jpdse_vq_rate_fwd): vector m of x [M, D]
+  belongs to group m % G; hist fp32 [G, L] the sums of the soft assignment p per group (hard: of the one-hot of the nearest
+  centre; None unless want_hist), rate fp32 [1] = -sum hist log2(hist / (M / G)) / denom, dhist fp32 [G, L] = scale * d rate /
+  d hist (None unless want_grad): what vq_quantize_bwd(groups=G, dhist=...) takes."""
+  M, D, L = _vq_dims(x, code_book)
+  G = int(G)
+  rate = torch.empty(1, dtype=torch.float32, device=x.device)
+  hist = torch.empty((max(G, 0), L), dtype=torch.float32, device=x.device) if want_hist else None
+  dhist = torch.empty((max(G, 0), L), dtype=torch.float32, device=x.device) if want_grad else None
+  ws = workspace(max(lib().jpdse_vq_rate_workspace_size(M, D, L, G), 1), x.device)
+  args = VqRateFwdArgs(code_of(x.dtype), M, D, L, G, float(sigma), 1 if hard else 0, x.data_ptr(), code_book.data_ptr(),
+                       float(scale), float(denom), hist.data_ptr() if want_hist else None, rate.data_ptr(),
+                       dhist.data_ptr() if want_grad else None, ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+  check(lib().jpdse_vq_rate_fwd(ctypes.byref(args)), 'vq_rate_fwd')
+  return rate, hist, dhist
 
 
 # ---- soft-to-hard vector quantizer: coded index stream (vq_coder.hip; format: DESIGN.md 4.14) -------------------------------

@@ -219,6 +219,9 @@ def main():
       by_image['actual'] += packed_bpp * b
       line += ', vq code: coded file bpp {:.4f} (packed indices {:.4f}), max |decoded - get_img| {:.3e}'.format(coded_bpp, packed_bpp,
                                                                                                         diff)
+      # the per-group zero-order entropy of the same code over the batch: an estimate, not a size, and on
+      # either side of the coded figure (the coder adapts per image and pays headers and flushes)
+      line += ', per-group entropy bpp {:.4f}'.format(trainer.get_vq_rate(x_dict))
     elif args.codec:
       shannon, actual = trainer.get_eval_rate(x_dict)
       shannon = float(shannon)
