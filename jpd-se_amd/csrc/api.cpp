@@ -32,7 +32,7 @@ int code_import_check(int dtype, int N, int H, int W, int C, const void* in, con
   return JPDSE_OK;
 }
 
-// jpdse_vq_* (vq.hip): everything that can be refused without a device
+// jpdse_vq_* (vq.hip, vq_bottleneck.hip): everything that can be refused without a device
 int vq_shape_check(const char* who, int M, int D, int L) {
   JPDSE_REQUIRE(D >= 1 && D <= 32, "%s: center_size D = %d (1 .. 32)", who, D);
   JPDSE_REQUIRE(L >= 2 && L <= 512, "%s: n_center L = %d (2 .. 512)", who, L);
@@ -46,10 +46,22 @@ static int vq_sigma_check(const char* who, float sigma) {
   return JPDSE_OK;
 }
 
-static int vq_ws_check(const char* who, const void* ws, size_t ws_bytes, int M, int D, int L) {
-  const size_t need = vq_workspace_bytes(M, D, L);
+int vq_ws_check(const char* who, const void* ws, size_t ws_bytes, size_t need) {
   JPDSE_REQUIRE(ws != nullptr && ws_bytes >= need, "%s: workspace too small (%zu bytes, %zu needed)", who,
                 ws ? ws_bytes : (size_t)0, need);
+  return JPDSE_OK;
+}
+
+int vqb_common_check(const char* who, int dtype, int M, int D, int L, float sigma) {
+  JPDSE_REQUIRE(!bad_dtype(dtype), "%s: bad dtype %d", who, dtype);
+  if (int rc = vq_shape_check(who, M, D, L)) return rc;
+  return vq_sigma_check(who, sigma);
+}
+
+int vqr_group_check(const char* who, int M, int L, int G) {
+  JPDSE_REQUIRE(G >= 1, "%s: G = %d groups (at least 1)", who, G);
+  JPDSE_REQUIRE(M % G == 0, "%s: G = %d does not divide M = %d", who, G, M);
+  JPDSE_REQUIRE((long long)G * L <= 65536, "%s: G * L = %lld (at most 65536)", who, (long long)G * L);
   return JPDSE_OK;
 }
 
@@ -77,7 +89,7 @@ int vq_soft_bwd_check(const jpdse_vq_soft_bwd_args* a) {
   if (int rc = vq_sigma_check("vq_soft_bwd", a->sigma)) return rc;
   JPDSE_REQUIRE(a->dp && a->p && a->x && a->code_book, "vq_soft_bwd: null pointer");
   if (a->dcode_book != nullptr)
-    if (int rc = vq_ws_check("vq_soft_bwd", a->ws, a->ws_bytes, a->M, a->D, a->L)) return rc;
+    if (int rc = vq_ws_check("vq_soft_bwd", a->ws, a->ws_bytes, vq_workspace_bytes(a->M, a->D, a->L))) return rc;
   return JPDSE_OK;
 }
 
@@ -94,7 +106,7 @@ int vq_decode_bwd_check(const jpdse_vq_decode_bwd_args* a) {
   JPDSE_REQUIRE(!bad_dtype(a->dtype), "vq_decode_bwd: bad dtype %d", a->dtype);
   if (int rc = vq_shape_check("vq_decode_bwd", a->M, a->D, a->L)) return rc;
   JPDSE_REQUIRE(a->index && a->dy && a->dcode_book && a->status, "vq_decode_bwd: null pointer");
-  return vq_ws_check("vq_decode_bwd", a->ws, a->ws_bytes, a->M, a->D, a->L);
+  return vq_ws_check("vq_decode_bwd", a->ws, a->ws_bytes, vq_workspace_bytes(a->M, a->D, a->L));
 }
 
 int vq_argmax_check(const jpdse_vq_argmax_args* a) {
@@ -108,7 +120,7 @@ int vq_pmf_check(const jpdse_vq_pmf_args* a) {
   JPDSE_REQUIRE(a != nullptr, "vq_pmf: null argument struct");
   if (int rc = vq_shape_check("vq_pmf", a->M, 1, a->L)) return rc;
   JPDSE_REQUIRE(a->s && a->pmf, "vq_pmf: null pointer");
-  return vq_ws_check("vq_pmf", a->ws, a->ws_bytes, a->M, 1, a->L);
+  return vq_ws_check("vq_pmf", a->ws, a->ws_bytes, vq_workspace_bytes(a->M, 1, a->L));
 }
 
 int vq_pmf_bwd_check(const jpdse_vq_pmf_bwd_args* a) {
@@ -159,10 +171,7 @@ int vq_index_encode_check(const jpdse_vq_index_encode_args* a) {
   const long long cap = vq_index_capacity_bytes(a->M, a->L, a->S);
   JPDSE_REQUIRE(a->out_bytes >= cap, "vq_index_encode: output of %lld bytes below the payload capacity %lld",
                 (long long)a->out_bytes, cap);
-  const size_t need = vq_index_workspace_bytes(a->M, a->L, a->S);
-  JPDSE_REQUIRE(a->ws != nullptr && a->ws_bytes >= need, "vq_index_encode: workspace too small (%zu bytes, %zu needed)",
-                a->ws ? a->ws_bytes : (size_t)0, need);
-  return JPDSE_OK;
+  return vq_ws_check("vq_index_encode", a->ws, a->ws_bytes, vq_index_workspace_bytes(a->M, a->L, a->S));
 }
 
 int vq_index_decode_check(const jpdse_vq_index_decode_args* a) {

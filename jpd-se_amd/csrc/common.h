@@ -34,6 +34,11 @@ int vq_decode_bwd_check(const jpdse_vq_decode_bwd_args* a);
 int vq_argmax_check(const jpdse_vq_argmax_args* a);
 int vq_pmf_check(const jpdse_vq_pmf_args* a);
 int vq_pmf_bwd_check(const jpdse_vq_pmf_bwd_args* a);
+// shared with the bottleneck and the rate term (kernels: vq_bottleneck.hip): a workspace of at least `need` bytes; dtype, shape
+// and sigma; the groups of the per-group histograms (G >= 1 divides M, G * L <= 65536)
+int vq_ws_check(const char* who, const void* ws, size_t ws_bytes, size_t need);
+int vqb_common_check(const char* who, int dtype, int M, int D, int L, float sigma);
+int vqr_group_check(const char* who, int M, int L, int G);
 
 // the same for the jpdse_vq_index_* calls (api.cpp; kernels: vq_coder.hip).  vq_index_bits: the decisions per
 // symbol; the two sizes are 0 outside the limits 2 <= L <= 512, 1 <= S <= min(M, 65535), M * nb and the capacity below 2^31.

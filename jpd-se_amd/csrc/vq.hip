@@ -13,13 +13,17 @@
 //       LDS, phase 2a (one thread per (vector, component)) sums dx over k ascending, phase 2b (one thread per (centre,
 //       component)) sums the tile's share of dC over the vectors ascending and adds it to the block's own fp32 partial.
 //   vq_decode_kernel / vq_decode_bwd_kernel   gather of centres; its transpose with the same per-block partials
-//   vq_merge_kernel                           out = scale * sum_b partial[b], b ascending (fp32)
-//   vq_pmf_partial_kernel / vq_pmf_final_kernel / vq_pmf_bwd_kernel   column means of [M][L]; second stage in fp64
+//   vq_pmf_partial_kernel / vq_pmf_bwd_kernel column means of [M][L], first stage, and their gradient
+//   vq_core.h (shared with vq_bottleneck.hip) the launcher, vq_weight, vq_partial_put and the two second stages: vq_merge_kernel
+//       (out = scale * sum_b partial[b], b ascending, fp32) and vq_pmf_final_kernel (fp64)
+// VqLanes states the group layout once (soft forward, the scores).  vq_hard_fwd_kernel, vq_argmax_kernel and vq_soft_bwd_kernel
+// spell it out as before: with the struct the first two took one more VGPR and the third ran 5% slower in fp32.
 // No atomics: every output element has one writer and every sum an order fixed by the grid, which depends on (M, D, L) alone,
 // so two calls on the same buffers give identical bits.  LDS per block <= 64 KiB in every kernel.
 #include <math.h>
 
 #include "common.h"
+#include "vq_core.h"
 
 namespace jpdse {
 
@@ -72,24 +76,38 @@ __device__ __forceinline__ void vq_stage_transposed(const float* __restrict__ c,
   }
 }
 
-// the scores of vector m against this lane's centres kk + 64 i; slots beyond L stay 0 and are never read
+// The group layout of a row of [M][L] (the header): this lane is lane kk of group g of its wave and owns the centres
+// centre(i) = kk + 64 i of the slots i with slot_live(i).  Grid-stride over rows: a wave covers the vpw vectors from `base`,
+//   for (long long base = ln.first(); base < M; base += ln.stride()) { const int m = ln.vector(base, M); .. }
+struct VqLanes {
+  int lane, wave, kk, g, vpw, ni, L;
+  __device__ __forceinline__ VqLanes(int G, int L_)
+      : lane(threadIdx.x & 63), wave(threadIdx.x >> 6), kk(lane & (G - 1)), g(lane / G), vpw(64 / G), ni((L_ + 63) >> 6), L(L_) {}
+  __device__ __forceinline__ int centre(int i) const { return kk + 64 * i; }
+  __device__ __forceinline__ bool slot_live(int i) const { return i < ni && kk + 64 * i < L; }
+  __device__ __forceinline__ long long first() const { return (long long)(blockIdx.x * 4 + wave) * vpw; }
+  __device__ __forceinline__ long long stride() const { return (long long)gridDim.x * 4 * vpw; }
+  // this group's vector; an idle group (live false) repeats the last vector and stores nothing
+  __device__ __forceinline__ bool live(long long base, int M) const { return base + g < M; }
+  __device__ __forceinline__ int vector(long long base, int M) const { return live(base, M) ? (int)(base + g) : M - 1; }
+};
+
+// the scores of vector m against this lane's centres; slots beyond L stay 0 and are never read
 template <typename T>
-__device__ __forceinline__ void vq_scores(const T* __restrict__ x, const float* ct, int m, int D, int L, int kk, int ni,
+__device__ __forceinline__ void vq_scores(const T* __restrict__ x, const float* ct, int m, int D, const VqLanes& ln,
                                           float (&d)[kVqSlots]) {
 #pragma unroll
   for (int i = 0; i < kVqSlots; ++i) d[i] = 0.f;
   const T* xr = x + (size_t)m * D;
   for (int j = 0; j < D; ++j) {
     const float xv = ElemOps<T>::ld(xr + j);
-    const float* row = ct + j * L;
+    const float* row = ct + j * ln.L;
 #pragma unroll
-    for (int i = 0; i < kVqSlots; ++i) {
-      const int k = kk + 64 * i;
-      if (i < ni && k < L) {
-        const float t = xv - row[k];
+    for (int i = 0; i < kVqSlots; ++i)
+      if (ln.slot_live(i)) {
+        const float t = xv - row[ln.centre(i)];
         d[i] += t * t;
       }
-    }
   }
 }
 
@@ -121,23 +139,21 @@ __global__ __launch_bounds__(256) void vq_soft_fwd_kernel(const T* __restrict__ 
   extern __shared__ float vq_lds[];
   vq_stage_transposed(c, vq_lds, D, L);
   __syncthreads();
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int kk = lane & (G - 1), g = lane / G, vpw = 64 / G, ni = (L + 63) >> 6;
-  for (long long base = (long long)(blockIdx.x * 4 + wave) * vpw; base < M; base += (long long)gridDim.x * 4 * vpw) {
-    const bool live = base + g < M;
-    const int m = live ? (int)(base + g) : M - 1;      // an idle group repeats the last vector and stores nothing
+  const VqLanes ln(G, L);
+  for (long long base = ln.first(); base < M; base += ln.stride()) {
+    const bool live = ln.live(base, M);
+    const int m = ln.vector(base, M);
     float d[kVqSlots];
-    vq_scores(x, vq_lds, m, D, L, kk, ni, d);
+    vq_scores(x, vq_lds, m, D, ln, d);
     float dmin = INFINITY;
 #pragma unroll
     for (int i = 0; i < kVqSlots; ++i)
-      if (i < ni && kk + 64 * i < L) dmin = fminf(dmin, d[i]);
+      if (ln.slot_live(i)) dmin = fminf(dmin, d[i]);
     for (int off = G >> 1; off > 0; off >>= 1) dmin = fminf(dmin, __shfl_xor(dmin, off, 64));
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < kVqSlots; ++i) {
-      // d == dmin: exp(0) = 1 without forming inf - inf when every score overflowed
-      d[i] = (i < ni && kk + 64 * i < L) ? (d[i] == dmin ? 1.f : expf(-sigma * (d[i] - dmin))) : 0.f;
+      d[i] = ln.slot_live(i) ? vq_weight(d[i], dmin, sigma) : 0.f;
       s += d[i];
     }
     s = vq_group_sum(s, G);
@@ -145,7 +161,7 @@ __global__ __launch_bounds__(256) void vq_soft_fwd_kernel(const T* __restrict__ 
       float* row = p + (size_t)m * L;
 #pragma unroll
       for (int i = 0; i < kVqSlots; ++i)
-        if (i < ni && kk + 64 * i < L) row[kk + 64 * i] = d[i] / s;
+        if (ln.slot_live(i)) row[ln.centre(i)] = d[i] / s;
     }
   }
 }
@@ -162,7 +178,7 @@ __global__ __launch_bounds__(256) void vq_hard_fwd_kernel(const T* __restrict__ 
     const bool live = base + g < M;
     const int m = live ? (int)(base + g) : M - 1;
     float d[kVqSlots];
-    vq_scores(x, vq_lds, m, D, L, kk, ni, d);
+    vq_scores(x, vq_lds, m, D, VqLanes(G, L), d);
     float best = INFINITY;
     int bk = kk < L ? kk : 0x7fffffff;
     if (kk < L) best = d[0];
@@ -291,16 +307,6 @@ __global__ __launch_bounds__(256) void vq_soft_bwd_kernel(const float* __restric
   }
 }
 
-// out[i] = scale * sum_b partial[b][i], b ascending
-__global__ __launch_bounds__(256) void vq_merge_kernel(const float* __restrict__ partial, int nb, int n, float scale,
-                                                      float* __restrict__ out) {
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-    float acc = 0.f;
-    for (int b = 0; b < nb; ++b) acc += partial[(size_t)b * n + i];
-    out[i] = scale * acc;
-  }
-}
-
 // ---- decode -----------------------------------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void vq_decode_kernel(const int* __restrict__ index, const float* __restrict__ c, int M, int D,
@@ -341,7 +347,7 @@ __global__ __launch_bounds__(256) void vq_decode_bwd_kernel(const int* __restric
       float acc = 0.f;
       for (int v = 0; v < nv; ++v)
         if (it[v] == k) acc += ElemOps<T>::ld(dy + (size_t)(m0 + v) * D + j);
-      mine[q] = first ? acc : mine[q] + acc;
+      vq_partial_put(mine, q, first, acc);
     }
     first = false;
     __syncthreads();
@@ -371,26 +377,10 @@ __global__ __launch_bounds__(256) void vq_pmf_partial_kernel(const float* __rest
   }
 }
 
-__global__ __launch_bounds__(256) void vq_pmf_final_kernel(const float* __restrict__ partial, int nb, int L, double count,
-                                                          float* __restrict__ pmf) {
-  for (int k = threadIdx.x; k < L; k += 256) {
-    double acc = 0.0;
-    for (int b = 0; b < nb; ++b) acc += (double)partial[(size_t)b * L + k];
-    pmf[k] = (float)(acc / count);
-  }
-}
-
 __global__ __launch_bounds__(256) void vq_pmf_bwd_kernel(const float* __restrict__ dpmf, long long n, int L, float count,
                                                         float* __restrict__ ds) {
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
     ds[i] = dpmf[(int)(i % L)] / count;
-}
-
-// kernel<<<grid, 256, lds, stream>>>
-template <typename... P, typename... A>
-static inline int vq_launch(const char* what, void (*kernel)(P...), int grid, size_t lds, void* stream, A... args) {
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, as_stream(stream), static_cast<P>(args)...);
-  return check_launch(what);
 }
 
 static inline int vq_row_blocks(int M, int G) { return ew_blocks((long long)M * G); }   // one lane per (row, group lane)
@@ -412,7 +402,7 @@ int jpdse_vq_soft_fwd(const jpdse_vq_soft_fwd_args* a) {
   const size_t lds = (size_t)a->L * a->D * sizeof(float);
   return by_dtype(a->dtype, [&](auto tag) {
     using T = decltype(tag);
-    return vq_launch("vq_soft_fwd", vq_soft_fwd_kernel<T>, vq_row_blocks(a->M, G), lds, a->stream, cptr<T>(a->x), a->code_book,
+    return vq_launch("vq_soft_fwd", vq_soft_fwd_kernel<T>, vq_row_blocks(a->M, G), 256, lds, a->stream, cptr<T>(a->x), a->code_book,
                      a->M, a->D, a->L, G, a->sigma, a->p);
   });
 }
@@ -423,7 +413,7 @@ int jpdse_vq_hard_fwd(const jpdse_vq_hard_fwd_args* a) {
   const size_t lds = (size_t)a->L * a->D * sizeof(float);
   return by_dtype(a->dtype, [&](auto tag) {
     using T = decltype(tag);
-    return vq_launch("vq_hard_fwd", vq_hard_fwd_kernel<T>, vq_row_blocks(a->M, G), lds, a->stream, cptr<T>(a->x), a->code_book,
+    return vq_launch("vq_hard_fwd", vq_hard_fwd_kernel<T>, vq_row_blocks(a->M, G), 256, lds, a->stream, cptr<T>(a->x), a->code_book,
                      a->M, a->D, a->L, G, a->index, a->onehot);
   });
 }
@@ -438,12 +428,12 @@ int jpdse_vq_soft_bwd(const jpdse_vq_soft_bwd_args* a) {
   float* partial = a->dcode_book != nullptr ? mptr<float>(a->ws) : nullptr;
   if (int rc = by_dtype(a->dtype, [&](auto tag) {
         using T = decltype(tag);
-        return vq_launch("vq_soft_bwd", vq_soft_bwd_kernel<T>, nb, lds, a->stream, a->dp, a->p, cptr<T>(a->x), a->code_book, M, D,
+        return vq_launch("vq_soft_bwd", vq_soft_bwd_kernel<T>, nb, 256, lds, a->stream, a->dp, a->p, cptr<T>(a->x), a->code_book, M, D,
                          L, G, V, c_lds, a->sigma, mptr<T>(a->dx), partial);
       }))
     return rc;
   if (partial == nullptr) return JPDSE_OK;
-  return vq_launch("vq_soft_bwd(merge)", vq_merge_kernel, ew_blocks(L * D), 0, a->stream, partial, nb, L * D, -2.f,
+  return vq_launch("vq_soft_bwd(merge)", vq_merge_kernel, ew_blocks(L * D), 256, 0, a->stream, partial, nb, L * D, -2.f,
                    a->dcode_book);
 }
 
@@ -451,7 +441,7 @@ int jpdse_vq_decode(const jpdse_vq_decode_args* a) {
   if (int rc = vq_decode_check(a)) return rc;
   return by_dtype(a->dtype, [&](auto tag) {
     using T = decltype(tag);
-    return vq_launch("vq_decode", vq_decode_kernel<T>, ew_blocks((long long)a->M * a->D), 0, a->stream, a->index, a->code_book,
+    return vq_launch("vq_decode", vq_decode_kernel<T>, ew_blocks((long long)a->M * a->D), 256, 0, a->stream, a->index, a->code_book,
                      a->M, a->D, a->L, mptr<T>(a->y), a->status);
   });
 }
@@ -462,32 +452,32 @@ int jpdse_vq_decode_bwd(const jpdse_vq_decode_bwd_args* a) {
   float* partial = mptr<float>(a->ws);
   if (int rc = by_dtype(a->dtype, [&](auto tag) {
         using T = decltype(tag);
-        return vq_launch("vq_decode_bwd", vq_decode_bwd_kernel<T>, nb, 0, a->stream, a->index, cptr<T>(a->dy), a->M, a->D, a->L,
+        return vq_launch("vq_decode_bwd", vq_decode_bwd_kernel<T>, nb, 256, 0, a->stream, a->index, cptr<T>(a->dy), a->M, a->D, a->L,
                          partial, a->status);
       }))
     return rc;
-  return vq_launch("vq_decode_bwd(merge)", vq_merge_kernel, ew_blocks(n), 0, a->stream, partial, nb, n, 1.f, a->dcode_book);
+  return vq_launch("vq_decode_bwd(merge)", vq_merge_kernel, ew_blocks(n), 256, 0, a->stream, partial, nb, n, 1.f, a->dcode_book);
 }
 
 int jpdse_vq_argmax(const jpdse_vq_argmax_args* a) {
   if (int rc = vq_argmax_check(a)) return rc;
   const int G = vq_group(a->L);
-  return vq_launch("vq_argmax", vq_argmax_kernel, vq_row_blocks(a->M, G), 0, a->stream, a->s, a->M, a->L, G, a->index);
+  return vq_launch("vq_argmax", vq_argmax_kernel, vq_row_blocks(a->M, G), 256, 0, a->stream, a->s, a->M, a->L, G, a->index);
 }
 
 int jpdse_vq_pmf(const jpdse_vq_pmf_args* a) {
   if (int rc = vq_pmf_check(a)) return rc;
   const int nb = vq_pmf_blocks(a->M, a->L);
   float* partial = mptr<float>(a->ws);
-  if (int rc = vq_launch("vq_pmf", vq_pmf_partial_kernel, nb, 0, a->stream, a->s, a->M, a->L, vq_pmf_rows(a->L), partial))
+  if (int rc = vq_launch("vq_pmf", vq_pmf_partial_kernel, nb, 256, 0, a->stream, a->s, a->M, a->L, vq_pmf_rows(a->L), partial))
     return rc;
-  return vq_launch("vq_pmf(final)", vq_pmf_final_kernel, 1, 0, a->stream, partial, nb, a->L, (double)a->M, a->pmf);
+  return vq_launch("vq_pmf(final)", vq_pmf_final_kernel, 1, 256, 0, a->stream, partial, nb, a->L, (double)a->M, a->pmf);
 }
 
 int jpdse_vq_pmf_bwd(const jpdse_vq_pmf_bwd_args* a) {
   if (int rc = vq_pmf_bwd_check(a)) return rc;
   const long long n = (long long)a->M * a->L;
-  return vq_launch("vq_pmf_bwd", vq_pmf_bwd_kernel, ew_blocks(n), 0, a->stream, a->dpmf, n, a->L, (float)a->M, a->ds);
+  return vq_launch("vq_pmf_bwd", vq_pmf_bwd_kernel, ew_blocks(n), 256, 0, a->stream, a->dpmf, n, a->L, (float)a->M, a->ds);
 }
 
 }  // extern "C"

@@ -12,7 +12,12 @@
 //                    in chunks of KC centres: dd = -sigma p (dp - <p, dp>), dx += dd (x - c[k]) in registers; with a code-book
 //                    gradient the chunk's p and dd go to LDS and thread ((k, j), part) sums p dy - 2 dd (x - c) over its share of the
 //                    tile's vectors ascending, parts added in order into the block's fp32 partial [L][D].
-//   vqb_merge_kernel / vqb_pmf_final_kernel   the partials in block order: fp32 for dC, fp64 for the pmf.
+//   vq_merge_kernel / vq_pmf_final_kernel (vq_core.h)   the partials in block order: fp32 for dC, fp64 for the pmf.
+//   Shared by the kernels, below: VqbBook (the code book's view), VqbTile + vqb_load_tile_row, vqb_nearest (sweep 1), vqb_e and
+//   vqb_weight_sum (sweep 2): the forward and the general histogram.  vqb_bwd_kernel and vqr_hist_kernel keep their own
+//   preamble and sweeps: on the helpers some instantiations of the first took more VGPRs, the second ran 2% slower (fp32, G 1).
+//   The three chunk-to-LDS reductions stay apart: a "part" owns a span of vectors of one centre (forward pmf), of one (centre,
+//   component) (backward dC) or a stride-G slot (general histogram); only the chunk bounds are common.
 //   vqr_*            the rate term on per-group histograms: described where they stand, below the backward.
 // The code book sits in LDS as [L][DP] (zero padded: every lane reads the same word, a broadcast, and the padded components add
 // exact zeros) when that is at most 8 KiB; a larger one is read from global memory at wave-uniform addresses.
@@ -23,6 +28,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "vq_core.h"
 
 namespace jpdse {
 
@@ -33,7 +39,7 @@ constexpr int kVqbCbLdsBytes = 8192;     // a padded code book up to this size i
 // ---- launch geometry: functions of (M, D, L) alone -------------------------------------------------------------------------
 static inline int vqb_dp(int D) { return D <= 4 ? 4 : (D <= 8 ? 8 : (D <= 16 ? 16 : 32)); }
 static inline int vqb_bwd_threads(int D) { return D <= 8 ? 256 : (D <= 16 ? 128 : 64); }   // = vectors per tile
-static inline int vqb_chunk(int L) { return L < kVqbChunk ? L : kVqbChunk; }
+__host__ __device__ static inline int vqb_chunk(int L) { return L < kVqbChunk ? L : kVqbChunk; }
 static inline bool vqb_cb_lds(int D, int L) { return (size_t)L * vqb_dp(D) * sizeof(float) <= (size_t)kVqbCbLdsBytes; }
 static inline int vqb_blocks(int M, int V) {
   const int tiles = (M + V - 1) / V;
@@ -129,9 +135,62 @@ __device__ __forceinline__ float vqb_dot(const float (&g)[DP], const float* ck, 
   return q;
 }
 
-// d == dmin: exp(0) = 1 without forming inf - inf when every score overflowed
-__device__ __forceinline__ float vqb_weight(float d, float dmin, float sigma) {
-  return d == dmin ? 1.f : expf(-sigma * (d - dmin));
+// The code book as a kernel reads it: CBL: staged here in LDS as [L][DP] (the caller synchronises before row()); otherwise the
+// global [L][D].  row(k): centre k
+template <int DP, bool CBL>
+struct VqbBook {
+  const float* cc;
+  int ld;
+  __device__ __forceinline__ VqbBook(const float* c, float* lds, int D, int L) : cc(CBL ? lds : c), ld(CBL ? DP : D) {
+    if (CBL) vqb_stage(c, lds, D, L, DP);
+  }
+  __device__ __forceinline__ const float* row(int k) const { return cc + k * ld; }
+};
+
+// tile `tile` of V vectors, one per thread: the first vector, the vectors inside M, whether this thread has one
+struct VqbTile {
+  int m0, nv;
+  bool live;
+  __device__ __forceinline__ VqbTile(int tile, int V, int M) : m0(tile * V), nv(M - m0 < V ? M - m0 : V), live((int)threadIdx.x < nv) {}
+  __device__ __forceinline__ int m() const { return m0 + threadIdx.x; }       // this thread's vector
+};
+
+// this thread's vector of the tile in DP registers; zeros for a thread without one
+template <typename T, int DP>
+__device__ __forceinline__ void vqb_load_tile_row(const T* x, const VqbTile& tl, int D, int vec, float (&xr)[DP]) {
+#pragma unroll
+  for (int j = 0; j < DP; ++j) xr[j] = 0.f;
+  if (tl.live) vqb_load_row<T, DP>(x + (size_t)tl.m() * D, D, vec != 0, xr);
+}
+
+// sweep 1: the minimum score and its centre (strict <: the lower index keeps a tie; a NaN never wins)
+template <int DP, bool CBL>
+__device__ __forceinline__ float vqb_nearest(const float (&xr)[DP], const VqbBook<DP, CBL>& cb, int D, int L, int& bk) {
+  float dmin = INFINITY;
+  bk = 0;
+  for (int k = 0; k < L; ++k) {
+    const float d = vqb_score<DP, CBL>(xr, cb.row(k), D);
+    if (d < dmin) {
+      dmin = d;
+      bk = k;
+    }
+  }
+  return dmin;
+}
+
+// e[k], the numerator of p[m][k]: the callers divide by s (forward, backward) or multiply by 1 / s (rate term)
+template <int DP, bool CBL>
+__device__ __forceinline__ float vqb_e(const float (&xr)[DP], const VqbBook<DP, CBL>& cb, int k, int D, float dmin, float sigma) {
+  return vq_weight(vqb_score<DP, CBL>(xr, cb.row(k), D), dmin, sigma);
+}
+
+// sweep 2 where nothing rides along: s = sum_k e[k], k ascending
+template <int DP, bool CBL>
+__device__ __forceinline__ float vqb_weight_sum(const float (&xr)[DP], const VqbBook<DP, CBL>& cb, int D, int L, float dmin,
+                                                float sigma) {
+  float s = 0.f;
+  for (int k = 0; k < L; ++k) s += vqb_e(xr, cb, k, D, dmin, sigma);
+  return s;
 }
 
 // ---- forward ----------------------------------------------------------------------------------------------------------------
@@ -142,37 +201,24 @@ __global__ __launch_bounds__(256) void vqb_fwd_kernel(const T* __restrict__ x, c
                                                      float* __restrict__ partial) {
   extern __shared__ float vqb_lds[];
   constexpr int V = 256;
-  const int KC = L < kVqbChunk ? L : kVqbChunk;
+  const int KC = vqb_chunk(L);
   float* pt = vqb_lds + (CBL ? L * DP : 0);
   float* red = pt + KC * (V + 1);
-  if (CBL) {
-    vqb_stage(c, vqb_lds, D, L, DP);
-    __syncthreads();
-  }
-  const float* cc = CBL ? vqb_lds : c;
-  const int ld = CBL ? DP : D;
+  const VqbBook<DP, CBL> cb(c, vqb_lds, D, L);
+  if (CBL) __syncthreads();
   const int t = threadIdx.x;
   const int ntiles = (M + V - 1) / V;
   float* mine = partial != nullptr ? partial + (size_t)blockIdx.x * L : nullptr;
   bool first = true;
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int m0 = tile * V;
-    const int nv = M - m0 < V ? M - m0 : V;
-    const bool live = t < nv;
+    const VqbTile tl(tile, V, M);
+    const int m0 = tl.m0, nv = tl.nv;
+    const bool live = tl.live;
     const size_t row = (size_t)(m0 + t) * D;
     float xr[DP];
-#pragma unroll
-    for (int j = 0; j < DP; ++j) xr[j] = 0.f;
-    if (live) vqb_load_row<T, DP>(x + row, D, vec != 0, xr);
-    float dmin = INFINITY;
-    int bk = 0;
-    for (int k = 0; k < L; ++k) {
-      const float d = vqb_score<DP, CBL>(xr, cc + k * ld, D);
-      if (d < dmin) {                          // strict: the lower index keeps a tie; a NaN never wins
-        dmin = d;
-        bk = k;
-      }
-    }
+    vqb_load_tile_row<T, DP>(x, tl, D, vec, xr);
+    int bk;
+    const float dmin = vqb_nearest(xr, cb, D, L, bk);
     float s = 1.f;
     float a[DP];
     if (!hard || mine != nullptr) {
@@ -180,8 +226,8 @@ __global__ __launch_bounds__(256) void vqb_fwd_kernel(const T* __restrict__ x, c
 #pragma unroll
       for (int j = 0; j < DP; ++j) a[j] = 0.f;
       for (int k = 0; k < L; ++k) {
-        const float* ck = cc + k * ld;
-        const float e = vqb_weight(vqb_score<DP, CBL>(xr, ck, D), dmin, sigma);
+        const float* ck = cb.row(k);
+        const float e = vqb_e(xr, cb, k, D, dmin, sigma);
         s += e;
 #pragma unroll
         for (int j = 0; j < DP; ++j)
@@ -191,7 +237,7 @@ __global__ __launch_bounds__(256) void vqb_fwd_kernel(const T* __restrict__ x, c
     if (live) {
       index[m0 + t] = bk;
       if (hard) {
-        const float* ck = cc + bk * ld;
+        const float* ck = cb.row(bk);
 #pragma unroll
         for (int j = 0; j < DP; ++j) a[j] = (CBL || j < D) ? ck[j] : 0.f;
       } else {
@@ -206,7 +252,7 @@ __global__ __launch_bounds__(256) void vqb_fwd_kernel(const T* __restrict__ x, c
         const int kc = L - k0 < KC ? L - k0 : KC;
         if (live)
           for (int kk = 0; kk < kc; ++kk)
-            pt[kk * (V + 1) + t] = vqb_weight(vqb_score<DP, CBL>(xr, cc + (k0 + kk) * ld, D), dmin, sigma) / s;
+            pt[kk * (V + 1) + t] = vqb_e(xr, cb, k0 + kk, D, dmin, sigma) / s;
         __syncthreads();
         {
           const int kk = t % KC, part = t / KC;
@@ -221,30 +267,11 @@ __global__ __launch_bounds__(256) void vqb_fwd_kernel(const T* __restrict__ x, c
         if (t < kc) {
           float acc = 0.f;
           for (int part = 0; part < parts; ++part) acc += red[part * KC + t];
-          mine[k0 + t] = first ? acc : mine[k0 + t] + acc;
+          vq_partial_put(mine, k0 + t, first, acc);
         }
       }
     }
     first = false;
-  }
-}
-
-// pmf[k] = (sum_b partial[b][k]) / M, b ascending, in fp64
-__global__ __launch_bounds__(256) void vqb_pmf_final_kernel(const float* __restrict__ partial, int nb, int L, double count,
-                                                           float* __restrict__ pmf) {
-  for (int k = threadIdx.x; k < L; k += 256) {
-    double acc = 0.0;
-    for (int b = 0; b < nb; ++b) acc += (double)partial[(size_t)b * L + k];
-    pmf[k] = (float)(acc / count);
-  }
-}
-
-// out[i] = sum_b partial[b][i], b ascending
-__global__ __launch_bounds__(256) void vqb_merge_kernel(const float* __restrict__ partial, int nb, int n, float* __restrict__ out) {
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-    float acc = 0.f;
-    for (int b = 0; b < nb; ++b) acc += partial[(size_t)b * n + i];
-    out[i] = acc;
   }
 }
 
@@ -305,7 +332,7 @@ __global__ __launch_bounds__(256) void vqb_bwd_kernel(const T* __restrict__ dy, 
     float s = 0.f, pd = 0.f;
     for (int k = 0; k < L; ++k) {
       const float* ck = cc + k * ld;
-      const float e = vqb_weight(vqb_score<DP, CBL>(xr, ck, D), dmin, sigma);
+      const float e = vq_weight(vqb_score<DP, CBL>(xr, ck, D), dmin, sigma);
       const float q = vqb_dot<DP, CBL>(gr, ck, D) + dqr[k];
       s += e;
       pd = __fmaf_rn(e, q, pd);
@@ -323,7 +350,7 @@ __global__ __launch_bounds__(256) void vqb_bwd_kernel(const T* __restrict__ dy, 
       const int kc = L - k0 < KC ? L - k0 : KC;
       for (int kk = 0; kk < kc; ++kk) {
         const float* ck = cc + (k0 + kk) * ld;
-        const float p = vqb_weight(vqb_score<DP, CBL>(xr, ck, D), dmin, sigma) / s;
+        const float p = vq_weight(vqb_score<DP, CBL>(xr, ck, D), dmin, sigma) / s;
         const float q = vqb_dot<DP, CBL>(gr, ck, D) + dqr[k0 + kk];
         const float dd = -sigma * (p * (q - pd));
 #pragma unroll
@@ -352,7 +379,7 @@ __global__ __launch_bounds__(256) void vqb_bwd_kernel(const T* __restrict__ dy, 
         for (int q = t; q < nown; q += V) {
           float acc = 0.f;
           for (int part = 0; part < parts; ++part) acc += red[part * nown + q];
-          mine[k0 * D + q] = first ? acc : mine[k0 * D + q] + acc;
+          vq_partial_put(mine, k0 * D + q, first, acc);
         }
       }
     }
@@ -449,10 +476,10 @@ __global__ __launch_bounds__(256) void vqr_hist_kernel(const T* __restrict__ x, 
       }
     } else {
       float s = 0.f;
-      for (int k = 0; k < L; ++k) s += vqb_weight(vqb_score<DP, CBL>(xr, cc + k * ld, D), dmin, sigma);
+      for (int k = 0; k < L; ++k) s += vq_weight(vqb_score<DP, CBL>(xr, cc + k * ld, D), dmin, sigma);
       const float inv = 1.f / s;
       for (int k = 0; k < L; ++k) {
-        float v = live ? vqb_weight(vqb_score<DP, CBL>(xr, cc + k * ld, D), dmin, sigma) * inv : 0.f;
+        float v = live ? vq_weight(vqb_score<DP, CBL>(xr, cc + k * ld, D), dmin, sigma) * inv : 0.f;
         for (int off = 32; off >= G; off >>= 1) v += __shfl_xor(v, off, 64);
         if (owner) mine[k] += v;
       }
@@ -474,46 +501,30 @@ __global__ __launch_bounds__(256) void vqr_hist_general_kernel(const T* __restri
                                                               int L, int G, float sigma, int hard, int vec, float* partial) {
   extern __shared__ float vqb_lds[];
   constexpr int V = 256;
-  const int KC = L < kVqbChunk ? L : kVqbChunk;
+  const int KC = vqb_chunk(L);
   float* pt = vqb_lds + (CBL ? L * DP : 0);
-  if (CBL) vqb_stage(c, vqb_lds, D, L, DP);
+  const VqbBook<DP, CBL> cb(c, vqb_lds, D, L);
   const int t = threadIdx.x;
   float* mine = partial + (size_t)blockIdx.x * G * L;
   for (int i = t; i < G * L; i += V) mine[i] = 0.f;
   __syncthreads();
-  const float* cc = CBL ? vqb_lds : c;
-  const int ld = CBL ? DP : D;
   const int ntiles = (M + V - 1) / V;
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int m0 = tile * V;
-    const int nv = M - m0 < V ? M - m0 : V;
-    const bool live = t < nv;
+    const VqbTile tl(tile, V, M);
+    const int m0 = tl.m0, nv = tl.nv;
+    const bool live = tl.live;
     float xr[DP];
-#pragma unroll
-    for (int j = 0; j < DP; ++j) xr[j] = 0.f;
-    if (live) vqb_load_row<T, DP>(x + (size_t)(m0 + t) * D, D, vec != 0, xr);
-    float dmin = INFINITY;
-    int bk = 0;
-    for (int k = 0; k < L; ++k) {
-      const float d = vqb_score<DP, CBL>(xr, cc + k * ld, D);
-      if (d < dmin) {
-        dmin = d;
-        bk = k;
-      }
-    }
-    float inv = 1.f;
-    if (!hard) {
-      float s = 0.f;
-      for (int k = 0; k < L; ++k) s += vqb_weight(vqb_score<DP, CBL>(xr, cc + k * ld, D), dmin, sigma);
-      inv = 1.f / s;
-    }
+    vqb_load_tile_row<T, DP>(x, tl, D, vec, xr);
+    int bk;
+    const float dmin = vqb_nearest(xr, cb, D, L, bk);
+    const float inv = hard ? 1.f : 1.f / vqb_weight_sum(xr, cb, D, L, dmin, sigma);
     const int ns = G < nv ? G : nv;            // slot j holds the tile's vectors j, j + G, ..: group (m0 + j) % G
     for (int k0 = 0; k0 < L; k0 += KC) {
       const int kc = L - k0 < KC ? L - k0 : KC;
       if (live)
         for (int kk = 0; kk < kc; ++kk) {
           const int k = k0 + kk;
-          pt[kk * (V + 1) + t] = hard ? (bk == k ? 1.f : 0.f) : vqb_weight(vqb_score<DP, CBL>(xr, cc + k * ld, D), dmin, sigma) * inv;
+          pt[kk * (V + 1) + t] = hard ? (bk == k ? 1.f : 0.f) : vqb_e(xr, cb, k, D, dmin, sigma) * inv;
         }
       __syncthreads();
       for (int w = t; w < kc * ns; w += V) {
@@ -565,12 +576,6 @@ __global__ __launch_bounds__(kVqrFinalThreads) void vqr_final_kernel(const float
   }
 }
 
-template <typename... P, typename... A>
-static inline int vqb_launch(const char* what, void (*kernel)(P...), int grid, int threads, size_t lds, void* stream, A... args) {
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, as_stream(stream), static_cast<P>(args)...);
-  return check_launch(what);
-}
-
 // f(tag of T, DP as an integral constant, CBL as an integral constant)
 template <typename F>
 static inline int vqb_dispatch(int dtype, int D, int L, F&& f) {
@@ -595,20 +600,6 @@ static inline int vqb_vec(int dtype, int D, std::initializer_list<const void*> p
   return 1;
 }
 
-static int vqb_common_check(const char* who, int dtype, int M, int D, int L, float sigma) {
-  JPDSE_REQUIRE(!bad_dtype(dtype), "%s: bad dtype %d", who, dtype);
-  if (int rc = vq_shape_check(who, M, D, L)) return rc;
-  JPDSE_REQUIRE(isfinite(sigma) && sigma > 0.f, "%s: sigma is %g (a finite value > 0)", who, (double)sigma);
-  return JPDSE_OK;
-}
-
-static int vqr_group_check(const char* who, int M, int L, int G) {
-  JPDSE_REQUIRE(G >= 1, "%s: G = %d groups (at least 1)", who, G);
-  JPDSE_REQUIRE(M % G == 0, "%s: G = %d does not divide M = %d", who, G, M);
-  JPDSE_REQUIRE((long long)G * L <= 65536, "%s: G * L = %lld (at most 65536)", who, (long long)G * L);
-  return JPDSE_OK;
-}
-
 // both backward entry points after their shape checks.  second: dpmf [L] (grouped false) or dhist [G][L] (grouped true), or NULL
 static int vqb_bwd_run(const char* who, int dtype, int M, int D, int L, int G, float sigma, const void* dy, const void* x,
                        const float* code_book, const float* second, bool grouped, void* dx, float* dcode_book, void* ws,
@@ -616,9 +607,7 @@ static int vqb_bwd_run(const char* who, int dtype, int M, int D, int L, int G, f
   JPDSE_REQUIRE(dy && x && code_book, "%s: null pointer", who);
   float* partial = nullptr;
   if (dcode_book != nullptr) {
-    const size_t need = vqb_workspace_bytes(M, D, L);
-    JPDSE_REQUIRE(ws != nullptr && ws_bytes >= need, "%s: workspace too small (%zu bytes, %zu needed)", who,
-                  ws ? ws_bytes : (size_t)0, need);
+    if (int rc = vq_ws_check(who, ws, ws_bytes, vqb_workspace_bytes(M, D, L))) return rc;
     partial = mptr<float>(ws);
   }
   if (dx == nullptr && partial == nullptr) return JPDSE_OK;
@@ -633,7 +622,7 @@ static int vqb_bwd_run(const char* who, int dtype, int M, int D, int L, int G, f
         constexpr int DPv = decltype(dp)::value;
         constexpr bool CBLv = decltype(cbl)::value;
         auto go = [&](auto kernel) {
-          return vqb_launch(who, kernel, nb, V, lds, stream, cptr<T>(dy), cptr<T>(x), code_book, second, M, D, L, G, sigma, vec,
+          return vq_launch(who, kernel, nb, V, lds, stream, cptr<T>(dy), cptr<T>(x), code_book, second, M, D, L, G, sigma, vec,
                             mptr<T>(dx), partial);
         };
         if (gm == 1) return go(vqb_bwd_kernel<T, DPv, CBLv, 1>);
@@ -642,7 +631,7 @@ static int vqb_bwd_run(const char* who, int dtype, int M, int D, int L, int G, f
       }))
     return rc;
   if (partial == nullptr) return JPDSE_OK;
-  return vqb_launch(who, vqb_merge_kernel, ew_blocks(L * D), 256, 0, stream, partial, nb, L * D, dcode_book);
+  return vq_launch(who, vq_merge_kernel, ew_blocks(L * D), 256, 0, stream, partial, nb, L * D, 1.f, dcode_book);
 }
 
 }  // namespace jpdse
@@ -664,22 +653,20 @@ int jpdse_vq_quantize_fwd(const jpdse_vq_quantize_fwd_args* a) {
   const int nb = vqb_blocks(M, 256);
   float* partial = nullptr;
   if (a->pmf != nullptr) {
-    const size_t need = vqb_workspace_bytes(M, D, L);
-    JPDSE_REQUIRE(a->ws != nullptr && a->ws_bytes >= need, "vq_quantize_fwd: workspace too small (%zu bytes, %zu needed)",
-                  a->ws ? a->ws_bytes : (size_t)0, need);
+    if (int rc = vq_ws_check("vq_quantize_fwd", a->ws, a->ws_bytes, vqb_workspace_bytes(M, D, L))) return rc;
     partial = mptr<float>(a->ws);
   }
   const int vec = vqb_vec(a->dtype, D, {a->x, a->y});
   const size_t lds = vqb_fwd_lds(D, L, partial != nullptr);
   if (int rc = vqb_dispatch(a->dtype, D, L, [&](auto tag, auto dp, auto cbl) {
         using T = decltype(tag);
-        return vqb_launch("vq_quantize_fwd", vqb_fwd_kernel<T, decltype(dp)::value, decltype(cbl)::value>, nb, 256, lds, a->stream,
+        return vq_launch("vq_quantize_fwd", vqb_fwd_kernel<T, decltype(dp)::value, decltype(cbl)::value>, nb, 256, lds, a->stream,
                           cptr<T>(a->x), a->code_book, M, D, L, a->sigma, a->hard_forward != 0 ? 1 : 0, vec, mptr<T>(a->y),
                           a->index, partial);
       }))
     return rc;
   if (partial == nullptr) return JPDSE_OK;
-  return vqb_launch("vq_quantize_fwd(pmf)", vqb_pmf_final_kernel, 1, 256, 0, a->stream, partial, nb, L, (double)M, a->pmf);
+  return vq_launch("vq_quantize_fwd(pmf)", vq_pmf_final_kernel, 1, 256, 0, a->stream, partial, nb, L, (double)M, a->pmf);
 }
 
 int jpdse_vq_quantize_bwd(const jpdse_vq_quantize_bwd_args* a) {
@@ -711,9 +698,7 @@ int jpdse_vq_rate_fwd(const jpdse_vq_rate_fwd_args* a) {
   JPDSE_REQUIRE(isfinite(a->denom) && a->denom > 0.f, "vq_rate_fwd: denom is %g (a finite value > 0)", (double)a->denom);
   JPDSE_REQUIRE(a->x && a->code_book && a->rate, "vq_rate_fwd: null pointer");
   const int M = a->M, D = a->D, L = a->L, G = a->G;
-  const size_t need = vqr_workspace_bytes(M, L, G);
-  JPDSE_REQUIRE(a->ws != nullptr && a->ws_bytes >= need, "vq_rate_fwd: workspace too small (%zu bytes, %zu needed)",
-                a->ws ? a->ws_bytes : (size_t)0, need);
+  if (int rc = vq_ws_check("vq_rate_fwd", a->ws, a->ws_bytes, vqr_workspace_bytes(M, L, G))) return rc;
   float* partial = mptr<float>(a->ws);
   const int waves = vqr_waves(D, L, G), nb = vqr_blocks(M, L, G);
   const int vec = vqb_vec(a->dtype, D, {a->x});
@@ -724,13 +709,13 @@ int jpdse_vq_rate_fwd(const jpdse_vq_rate_fwd_args* a) {
         constexpr int DPv = decltype(dp)::value;
         constexpr bool CBLv = decltype(cbl)::value;
         if (waves > 0)
-          return vqb_launch("vq_rate_fwd", vqr_hist_kernel<T, DPv, CBLv>, nb, 64 * waves, lds, a->stream, cptr<T>(a->x),
+          return vq_launch("vq_rate_fwd", vqr_hist_kernel<T, DPv, CBLv>, nb, 64 * waves, lds, a->stream, cptr<T>(a->x),
                             a->code_book, M, D, L, G, a->sigma, hard, vec, partial);
-        return vqb_launch("vq_rate_fwd", vqr_hist_general_kernel<T, DPv, CBLv>, nb, 256, lds, a->stream, cptr<T>(a->x),
+        return vq_launch("vq_rate_fwd", vqr_hist_general_kernel<T, DPv, CBLv>, nb, 256, lds, a->stream, cptr<T>(a->x),
                           a->code_book, M, D, L, G, a->sigma, hard, vec, partial);
       }))
     return rc;
-  return vqb_launch("vq_rate_fwd(final)", vqr_final_kernel, 1, kVqrFinalThreads, 0, a->stream, partial, nb, G, L, (double)(M / G),
+  return vq_launch("vq_rate_fwd(final)", vqr_final_kernel, 1, kVqrFinalThreads, 0, a->stream, partial, nb, G, L, (double)(M / G),
                     (double)a->scale, (double)a->denom, a->hist, a->rate, a->dhist);
 }
 
