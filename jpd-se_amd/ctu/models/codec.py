@@ -1,0 +1,178 @@
+"""The codec of the feature encoder's bottleneck, one class per quantizer: what the model's code, decode, file
+and rate-term calls need from the quantizer in use -- the geometry of a code, the host checks of a code and of payloads (every
+one before any device work), the eval-mode code, the receiver's half, the payloads, the sizes of the files, and the arming of
+the bottleneck layer's rate term.  The model builds one object (CODECS[--encoder_quantizer]) and calls it; its input builders,
+the encoder's mode and the binarizer's counters stay the model's business.
+
+`device` arguments are callables (the model's `_device`): nothing here touches the device before the checks have passed.
+A new quantizer is a new class here and its entry in CODECS."""
+import contextlib
+
+import torch
+
+from jpdse_hip import ops
+from ctu.utils import bitstream, entropy, vqstream
+
+
+class _Codec:
+
+  def __init__(self, netE, cdtype):
+    self.netE, self.cdtype = netE, cdtype
+
+  def _label_geometry(self, x_dict, who):
+    """(N, H, W) of the label map; ValueError for a map that is no multiple of the encoder's down-sampling factor."""
+    N, H, W = int(x_dict['label'].shape[0]), int(x_dict['label'].shape[-2]), int(x_dict['label'].shape[-1])
+    step = 1 << self.netE.n_downsampling
+    if H % step or W % step:
+      raise ValueError('%s: a %d x %d label map is no multiple of the encoder\'s down-sampling factor %d' % (who, H, W, step))
+    return N, H, W
+
+  @contextlib.contextmanager
+  def rate_term(self, weight, B, H, W):
+    """Arm the bottleneck layer's rate term for one training forward of B images of H x W: the layer then leaves the unscaled
+    value in `rate_value` and sends the gradient, times `weight`, along with its context.  The denominator is the form's own."""
+    layer = self.netE._bottleneck
+    layer.rate_scale, layer.rate_denom = weight, self.rate_denom(B, H, W)
+    try:
+      yield
+    finally:
+      layer.rate_scale = None
+
+  @property
+  def rate_value(self):
+    """fp32 [1] on the device: the rate term of the last armed forward, unscaled."""
+    return self.netE._bottleneck.rate_value
+
+
+class BinaryCodec(_Codec):
+  """The one-bit binarizer's code: an NHWC Act of +-1, exported as bits (get_code), coded as .jpda payloads."""
+
+  RATE_OPTION = 'lambda_rate'      # the model's weight of this form's rate term
+
+  def geometry(self, x_dict, who):
+    """(N, H, W, (C, h, w), bits per image)."""
+    N, H, W = self._label_geometry(x_dict, who)
+    C, h, w = self.netE.code_shape(H, W)
+    return N, H, W, (C, h, w), C * h * w
+
+  def check_code(self, code, x_dict, who):
+    if not torch.is_tensor(code) or code.dim() != 2 or code.dtype not in (torch.uint8, torch.float32):
+      raise ValueError('%s: the code must be what get_code returns: a uint8 [N, ceil(bits / 8)] or float32 [N, bits] tensor' % who)
+    geo = N, H, W, (C, h, w), bits = self.geometry(x_dict, who)
+    want = (N, (bits + 7) // 8) if code.dtype == torch.uint8 else (N, bits)
+    if tuple(code.shape) != want:
+      raise ValueError('%s: code of shape %s, but %d label maps of %d x %d carry a %s code of shape %s (%d x %d x %d bits '
+                       'per image)' % (who, tuple(code.shape), N, H, W, 'packed' if code.dtype == torch.uint8 else 'float32',
+                                       want, C, h, w))
+    return geo
+
+  def check_payloads(self, payloads, x_dict, who):
+    geo = self.geometry(x_dict, who)
+    N, C = geo[0], geo[3][0]
+    if not isinstance(payloads, (list, tuple)) or len(payloads) != N:
+      raise ValueError('%s: the payloads must be what get_coded returns: a list of %d bytes objects, one per label map'
+                       % (who, N))
+    for j, p in enumerate(payloads):
+      entropy.check_payload(p, C, '%s: payload %d' % (who, j))
+    return geo
+
+  def code(self, src):
+    """The eval-mode code of the source Act (the caller holds the encoder in eval mode)."""
+    return self.netE.code(src)
+
+  def features_of_code(self, code, geo, device, who):
+    """The receiver's half as a callable: the encoder's output from a checked tensor code."""
+    N, _, _, (C, h, w), _ = geo
+    return lambda: self.netE.decode_code(ops.code_import(code.to(device(), non_blocking=True), N, h, w, C, self.cdtype))
+
+  def features_of_payloads(self, payloads, geo, device, who):
+    N, _, _, (C, h, w), _ = geo
+    return lambda: self.netE.decode_code(ops.code_entropy_decode(list(payloads), N, h, w, C, self.cdtype, device()))
+
+  def payloads(self, code, x_dict):
+    return ops.code_entropy_encode(code)
+
+  def file_rates(self, payloads, H, W):
+    """(coded bpp, raw bpp), batch means: the .jpda file (ctu.utils.entropy: 24-byte header, and the raw payload where coding
+    does not pay) and the .jpdc file (ctu.utils.bitstream: 20-byte header) of each image."""
+    shape = self.netE.code_shape(H, W)
+    coded = sum(8.0 * entropy.file_bytes(len(p), shape) / (H * W) for p in payloads) / len(payloads)
+    return coded, 8.0 * (bitstream.HEADER_BYTES + bitstream.payload_bytes(shape)) / (H * W)
+
+  def rate_denom(self, B, H, W):      # bits per pixel of an image, the kernel takes the batch mean
+    return H * W
+
+
+class VQIndexCodec(_Codec):
+  """The S2HVQ bottleneck's code: int64 [N, indices], coded as .jpdv blobs (ctu.utils.vqstream)."""
+
+  RATE_OPTION = 'lambda_vq_rate'
+
+  def geometry(self, x_dict, who):
+    """(N, H, W, indices per image, n_center, channel groups)."""
+    N, H, W = self._label_geometry(x_dict, who)
+    vq = self.netE._vq
+    return N, H, W, self.netE.vq_code_len(H, W), vq.n_center, vq.cout // vq.center_size
+
+  def check_code(self, code, x_dict, who):
+    geo = N, H, W, code_len, _, _ = self.geometry(x_dict, who)
+    if not torch.is_tensor(code) or code.dim() != 2 or code.dtype not in (torch.int64, torch.int32):
+      raise ValueError('%s: the code must be what get_vq_code returns: an int64 [N, indices] tensor' % who)
+    if tuple(code.shape) != (N, code_len):
+      raise ValueError('%s: code of shape %s, but %d label maps of %d x %d carry a code of shape %s'
+                       % (who, tuple(code.shape), N, H, W, (N, code_len)))
+    return geo
+
+  def check_payloads(self, blobs, x_dict, who):
+    geo = N, H, W, code_len, L, _ = self.geometry(x_dict, who)
+    if not isinstance(blobs, (list, tuple)) or len(blobs) != N:
+      raise ValueError('%s: the blobs must be what get_coded returns: a list of %d .jpdv bytes objects, one per '
+                       'label map' % (who, N))
+    for j, b in enumerate(blobs):                 # every header on the host
+      n, cl, Lb, _, _, _ = vqstream.parse_blob(b, '%s: blob %d' % (who, j))
+      if Lb != L:
+        raise ValueError('%s: blob %d was coded for n_center %d, the code book has %d' % (who, j, Lb, L))
+      if n * cl != code_len:
+        raise ValueError('%s: blob %d holds %d x %d indices, a %d x %d label map carries %d' % (who, j, n, cl, H, W, code_len))
+    return geo
+
+  def code(self, src):
+    """The eval-mode code of the source Act: per image the index of the nearest centre of every group of D channels, pixel by
+    pixel, groups ascending inside a pixel."""
+    return self.netE.vq_code(src).to(torch.int64)
+
+  def features_of_code(self, code, geo, device, who):
+    _, H, W, _, L, _ = geo
+
+    def features():
+      index = code.to(device(), non_blocking=True)
+      if bool(((index < 0) | (index >= L)).any()):      # before the cast to int32 could fold a far value into range
+        raise ValueError('%s: an index outside [0, %d)' % (who, L))
+      y, _ = self.netE.decode_vq_code(index.to(torch.int32).contiguous(), H, W)
+      return y
+
+    return features
+
+  def features_of_payloads(self, blobs, geo, device, who):
+    code_len = geo[3]
+    code = torch.cat([vqstream.read_indices(bytes(b), device()).view(1, code_len) for b in blobs], dim=0)
+    return self.features_of_code(code, geo, device, who)
+
+  def payloads(self, code, x_dict):
+    """One .jpdv blob per image in (C / D) * 8 streams: the stream count is a multiple of the group count, so a stream holds
+    indices of one channel group only (write_indices clamps the count to the number of indices)."""
+    _, _, _, _, L, groups = self.geometry(x_dict, 'get_coded')
+    return [vqstream.write_indices(None, code[i:i + 1], L, n_streams=groups * 8) for i in range(code.shape[0])]
+
+  def file_rates(self, payloads, H, W):
+    """(coded bpp, raw bpp), batch means: the .jpdv blobs, and the packed-index file (mode 0) of the same code: nb bits per
+    index + header."""
+    coded = sum(8.0 * len(p) / (H * W) for p in payloads) / len(payloads)
+    raw = vqstream.HEADER_BYTES + vqstream.packed_bytes(self.netE.vq_code_len(H, W), self.netE._vq.n_center)
+    return coded, 8.0 * raw / (H * W)
+
+  def rate_denom(self, B, H, W):      # bits per pixel of the local batch
+    return B * H * W
+
+
+CODECS = {'binarizer': BinaryCodec, 's2hvq': VQIndexCodec}

@@ -16,6 +16,7 @@ What changed structurally (results identical; DESIGN.md "schedule"):
 Only the flag subset used by scripts/pix2pixHD_bpg_train.sh is accelerated; other branches
 raise NotImplementedError.
 """
+import contextlib
 import os
 
 import torch
@@ -26,9 +27,9 @@ from jpdse_hip import ops
 from jpdse_hip.ops import Act
 from jpdse_hip.optim import FusedAdam
 from jpdse_hip.layers import PackBatcher
-from ctu.utils import bitstream, entropy, vqstream
 from ctu.utils import semantics as semantics_file
 from ctu.utils.image_pool import ImagePool
+from ctu.models.codec import CODECS, VQIndexCodec
 from ctu.models.pix2pixHD_networks.base_model import BaseModel
 from ctu.models.pix2pixHD_networks import networks
 
@@ -231,7 +232,6 @@ class Pix2PixHDModel(BaseModel):
       raise ValueError('lambda_vq_rate > 0 is the rate term of the vector-quantizer bottleneck: it needs --encoder_quantizer '
                        's2hvq and an encoder that runs (no --zero_vis)')
     # vector-quantizer bottleneck: refused combinations before any network (hence any device allocation) exists
-    self.use_vq = False
     if g('encoder_quantizer', 'binarizer') not in ('binarizer', 's2hvq'):
       raise ValueError('encoder_quantizer must be binarizer or s2hvq, got %r' % (g('encoder_quantizer'),))
     if g('encoder_quantizer', 'binarizer') == 's2hvq':
@@ -244,7 +244,6 @@ class Pix2PixHDModel(BaseModel):
       from jpdse_hip.layers import vq_bottleneck_check
       vq_bottleneck_check(int(g('encoder_binarizer_out_channels', 128)), int(g('vq_n_center', 64)),
                           int(g('vq_center_size', 8)), g('vq_sigma', 10.0), '--encoder_quantizer s2hvq')
-      self.use_vq = True
     # semantics-weighted distortion: (class table, edge weight), or None when every weight is 1 -- the
     # step then takes the plain l1 / mse path
     n_onehot = opt.num_labels + 1 if g('contain_dontcare_label') else opt.num_labels
@@ -304,6 +303,12 @@ class Pix2PixHDModel(BaseModel):
                                     encoder_quantizer=g('encoder_quantizer', 'binarizer'), vq_n_center=g('vq_n_center', 64),
                                     vq_center_size=g('vq_center_size', 8), vq_sigma=g('vq_sigma', 10.0),
                                     vq_hard_forward=not g('vq_soft_forward'))
+    # the codec of the encoder's bottleneck and the weight of its rate term, --lambda_rate or --lambda_vq_rate:
+    # the checks above leave a positive weight to the quantizer in use only
+    self.rate_weight = 0.0
+    if self.netE is not None and self.netE.quantizer is not None:
+      self.codec = CODECS[self.netE.quantizer](self.netE, self.cdtype)
+      self.rate_weight = getattr(self, self.codec.RATE_OPTION)
     # binarizer noise: Philox key = the run's seed, counter = (element, image index in the global batch,
     # number of training forwards so far)
     self.codec_seed = int(g('seed', None) or 0)
@@ -499,19 +504,33 @@ class Pix2PixHDModel(BaseModel):
     rank = dist.get_rank(group) if dist.is_available() and dist.is_initialized() else 0
     b.seed, b.draw, b.n_global0 = self.codec_seed, self.codec_draw, rank * local_batch
 
-  def _require_binarizer(self, who='binary codes'):
-    if getattr(self, 'use_vq', False):
+  codec = None      # ctu.models.codec: set by __init__ when the encoder has a bottleneck
+
+  def _binary_codec(self, who='binary codes'):
+    """The binarizer's codec, or the refusal.  The calls that serve either form take `self.codec or self._binary_codec()`:
+    without a bottleneck they refuse as the binary calls do."""
+    if isinstance(self.codec, VQIndexCodec):
       raise ValueError('%s: a call of the one-bit binarizer\'s code, not available with --encoder_quantizer s2hvq (its code: '
                        'get_vq_code / get_coded / get_coded_rate)' % who)
-    if self.netE is None or not self.netE.binarize:
+    if self.codec is None:
       raise ValueError('binary codes need the learned codec with encoder binarization '
                        '(--no_feat_encoding and --no_encoder_binarization must both be off)')
+    return self.codec
+
+  def _vq_codec(self, who):
+    """The vector quantizer's codec, or the refusal."""
+    if not isinstance(self.codec, VQIndexCodec):
+      raise ValueError('%s: the vector-quantised code needs --encoder_quantizer s2hvq' % who)
+    return self.codec
+
+  def _eval_code(self, codec, x_dict):
+    """The encoder's eval-mode code of x_dict (the decoded frame with --use_compressed) in the codec's form."""
+    pre = self.preprocess(x_dict, build_base=False)
+    return self._encoder_eval(lambda: codec.code(pre['src']))
 
   def _code_act(self, x_dict, who='binary codes'):
-    """The encoder's eval-mode bitstream of x_dict (the decoded frame with --use_compressed) as an NHWC Act."""
-    self._require_binarizer(who)
-    pre = self.preprocess(x_dict, build_base=False)
-    return self._encoder_eval(lambda: self.netE.code(pre['src']))
+    """The encoder's eval-mode bitstream of x_dict as an NHWC Act."""
+    return self._eval_code(self._binary_codec(who), x_dict)
 
   def get_code(self, x_dict, packed=False):
     """[image_code] (model.py:494-505, 557-563): (b + 1) / 2 as fp32 [N, bits] in NCHW flatten order -- or, packed=True
@@ -606,85 +625,34 @@ class Pix2PixHDModel(BaseModel):
       return slot[0]
 
   # ---- the vector-quantised code (extension) ------------------------------------------------------------------
-  def _require_vq(self, who):
-    if not getattr(self, 'use_vq', False):
-      raise ValueError('%s: the vector-quantised code needs --encoder_quantizer s2hvq' % who)
-
-  def _vq_geometry(self, x_dict, who):
-    """(N, H, W, indices per image, n_center, channel groups) from the label map alone; ValueError for a map that is no
-    multiple of the encoder's down-sampling factor."""
-    N, H, W = int(x_dict['label'].shape[0]), int(x_dict['label'].shape[-2]), int(x_dict['label'].shape[-1])
-    step = 1 << self.netE.n_downsampling
-    if H % step or W % step:
-      raise ValueError('%s: a %d x %d label map is no multiple of the encoder\'s down-sampling factor %d' % (who, H, W, step))
-    vq = self.netE._vq
-    return N, H, W, self.netE.vq_code_len(H, W), vq.n_center, vq.cout // vq.center_size
-
   def get_vq_code(self, x_dict):
     """The eval-mode code of the vector-quantizer bottleneck: int64 [N, h * w * C / D] on the device, per image the index of
     the nearest centre of every group of D channels, pixel by pixel, groups ascending inside a pixel."""
-    self._require_vq('get_vq_code')
+    codec = self._vq_codec('get_vq_code')
     with torch.no_grad():
-      pre = self.preprocess(x_dict, build_base=False)
-      return self._encoder_eval(lambda: self.netE.vq_code(pre['src'])).to(torch.int64)
+      return self._eval_code(codec, x_dict)
 
   def get_vq_rate(self, x_dict):
     """The hard-mode rate term of the eval-mode code in bits per pixel of the batch, a Python float: the
     zero-order entropy of get_vq_code(x_dict) per channel group, histograms taken over the batch.  An estimate, not a size:
     get_coded_rate measures the .jpdv files, whose adaptive coder may land on either side of it."""
-    self._require_vq('get_vq_rate')
+    self._vq_codec('get_vq_rate')
     with torch.no_grad():
       pre = self.preprocess(x_dict, build_base=False)
       src = pre['src']
       value = self._encoder_eval(lambda: self.netE.vq_rate(src, src.N * src.H * src.W))
       return float(value.item())
 
-  def _decode_vq_act(self, code, x_dict, who='decode'):
-    """decode() of a vector-quantised code up to the generator's NHWC output; also returns the device label map."""
-    N, H, W, code_len, L, _ = self._vq_geometry(x_dict, who)
-    if not torch.is_tensor(code) or code.dim() != 2 or code.dtype not in (torch.int64, torch.int32):
-      raise ValueError('%s: the code must be what get_vq_code returns: an int64 [N, indices] tensor' % who)
-    if tuple(code.shape) != (N, code_len):
-      raise ValueError('%s: code of shape %s, but %d label maps of %d x %d carry a code of shape %s'
-                       % (who, tuple(code.shape), N, H, W, (N, code_len)))
-
-    def features():
-      index = code.to(self._device(), non_blocking=True)
-      if bool(((index < 0) | (index >= L)).any()):      # before the cast to int32 could fold a far value into range
-        raise ValueError('%s: an index outside [0, %d)' % (who, L))
-      y, _ = self.netE.decode_vq_code(index.to(torch.int32).contiguous(), H, W)
-      return y
-
-    return self._generate_from_code(None, x_dict, N, H, W, features=features)
-
   def _decode_act(self, code, x_dict):
     """decode() up to the generator's NHWC output; also returns the device label map."""
-    if getattr(self, 'use_vq', False):
-      return self._decode_vq_act(code, x_dict)
-    self._require_binarizer()
-    if not torch.is_tensor(code) or code.dim() != 2 or code.dtype not in (torch.uint8, torch.float32):
-      raise ValueError('decode: the code must be what get_code returns: a uint8 [N, ceil(bits / 8)] or float32 [N, bits] tensor')
-    N, H, W = int(x_dict['label'].shape[0]), int(x_dict['label'].shape[-2]), int(x_dict['label'].shape[-1])
-    step = 1 << self.netE.n_downsampling
-    if H % step or W % step:
-      raise ValueError('decode: a %d x %d label map is no multiple of the encoder\'s down-sampling factor %d' % (H, W, step))
-    C, h, w = self.netE.code_shape(H, W)
-    bits = C * h * w
-    want = (N, (bits + 7) // 8) if code.dtype == torch.uint8 else (N, bits)
-    if tuple(code.shape) != want:
-      raise ValueError('decode: code of shape %s, but %d label maps of %d x %d carry a %s code of shape %s (%d x %d x %d bits '
-                       'per image)' % (tuple(code.shape), N, H, W, 'packed' if code.dtype == torch.uint8 else 'float32',
-                                       want, C, h, w))
-    return self._generate_from_code(
-        lambda: ops.code_import(code.to(self._device(), non_blocking=True), N, h, w, C, self.cdtype), x_dict, N, H, W)
+    codec = self.codec or self._binary_codec()
+    geo = codec.check_code(code, x_dict, 'decode')
+    return self._generate_from_code(codec.features_of_code(code, geo, self._device, 'decode'), x_dict, *geo[:3])
 
-  def _generate_from_code(self, import_b, x_dict, N, H, W, features=None):
-    """The receiver's device work, shared by decode and decode_coded: import_b() gives the code Act -- or features() the
-    encoder's output itself (the vector-quantised code)."""
+  def _generate_from_code(self, features, x_dict, N, H, W):
+    """The receiver's device work, shared by decode and decode_coded: features() gives the encoder's output from the code."""
     label, inst = self._semantics(x_dict)
-    vis = None                           # --zero_vis: nothing visual reaches the generator, the code is not read
-    if not self.zero_vis:
-      vis = features() if features is not None else self.netE.decode_code(import_b())
+    vis = None if self.zero_vis else features()      # --zero_vis: nothing visual reaches the generator, the code is not read
     base = None if self.zero_sem else ops.onehot_edge(label, inst, self.n_onehot, self.label_nc + self.feat_nc, self.cdtype)
     fake, _ = self.netG.fwd(self._g_input_from_vis(vis, base, N, H, W))
     return fake, label
@@ -711,36 +679,12 @@ class Pix2PixHDModel(BaseModel):
   def get_coded(self, x_dict):
     """The entropy-coded form of get_code(x_dict, packed=True): a list of N `bytes`, per image the C stream lengths and the C
     range-coded streams (ops.code_entropy_encode).  Lossless: decode_coded(get_coded(x), x) equals
-    decode(get_code(x, packed=True), x) bit for bit."""
-    if getattr(self, 'use_vq', False):
-      return self._get_coded_vq(x_dict)
+    decode(get_code(x, packed=True), x) bit for bit.
+    With --encoder_quantizer s2hvq: a list of N .jpdv blobs (ctu.utils.vqstream), one per image, of that image's
+    get_vq_code row."""
+    codec = self.codec or self._binary_codec()
     with torch.no_grad():
-      return ops.code_entropy_encode(self._code_act(x_dict))
-
-  def _get_coded_vq(self, x_dict):
-    """--encoder_quantizer s2hvq: a list of N .jpdv blobs (ctu.utils.vqstream), one per image, of that image's
-    get_vq_code row in (C / D) * 8 streams: the stream count is a multiple of the group count, so a stream holds indices of
-    one channel group only (write_indices clamps the count to the number of indices)."""
-    code = self.get_vq_code(x_dict)
-    _, _, _, _, L, groups = self._vq_geometry(x_dict, 'get_coded')
-    return [vqstream.write_indices(None, code[i:i + 1], L, n_streams=groups * 8) for i in range(code.shape[0])]
-
-  def _decode_coded_vq(self, blobs, x_dict):
-    N, H, W, code_len, L, _ = self._vq_geometry(x_dict, 'decode_coded')
-    if not isinstance(blobs, (list, tuple)) or len(blobs) != N:
-      raise ValueError('decode_coded: the blobs must be what get_coded returns: a list of %d .jpdv bytes objects, one per '
-                       'label map' % N)
-    for j, b in enumerate(blobs):                 # every header on the host, before any device work
-      n, cl, Lb, _, _, _ = vqstream.parse_blob(b, 'decode_coded: blob %d' % j)
-      if Lb != L:
-        raise ValueError('decode_coded: blob %d was coded for n_center %d, the code book has %d' % (j, Lb, L))
-      if n * cl != code_len:
-        raise ValueError('decode_coded: blob %d holds %d x %d indices, a %d x %d label map carries %d'
-                         % (j, n, cl, H, W, code_len))
-    with torch.no_grad():
-      code = torch.cat([vqstream.read_indices(bytes(b), self._device()).view(1, code_len) for b in blobs], dim=0)
-      fake, _ = self._decode_vq_act(code, x_dict, 'decode_coded')
-      return ops.nhwc_to_nchw(fake)
+      return codec.payloads(self._eval_code(codec, x_dict), x_dict)
 
   def decode_coded(self, payloads, x_dict):
     """decode() from what get_coded returned: a list of one `bytes` payload per label map.  ValueError, before any device
@@ -748,40 +692,20 @@ class Pix2PixHDModel(BaseModel):
     wrong payload count, an item that is not bytes, and a payload whose length table does not add up.
     With --encoder_quantizer s2hvq the items are the .jpdv blobs of get_coded; each header's n * code_len and L must fit the
     label map and the code book (checked on the host first); decode_coded(get_coded(x), x) equals get_img(x) bit for bit."""
-    if getattr(self, 'use_vq', False):
-      return self._decode_coded_vq(payloads, x_dict)
-    self._require_binarizer()
-    N, H, W = int(x_dict['label'].shape[0]), int(x_dict['label'].shape[-2]), int(x_dict['label'].shape[-1])
-    step = 1 << self.netE.n_downsampling
-    if H % step or W % step:
-      raise ValueError('decode_coded: a %d x %d label map is no multiple of the encoder\'s down-sampling factor %d' % (H, W, step))
-    C, h, w = self.netE.code_shape(H, W)
-    if not isinstance(payloads, (list, tuple)) or len(payloads) != N:
-      raise ValueError('decode_coded: the payloads must be what get_coded returns: a list of %d bytes objects, one per label map'
-                       % N)
-    for j, p in enumerate(payloads):
-      entropy.check_payload(p, C, 'decode_coded: payload %d' % j)
+    codec = self.codec or self._binary_codec()
+    geo = codec.check_payloads(payloads, x_dict, 'decode_coded')
     with torch.no_grad():
-      fake, _ = self._generate_from_code(
-          lambda: ops.code_entropy_decode(list(payloads), N, h, w, C, self.cdtype, self._device()), x_dict, N, H, W)
+      features = codec.features_of_payloads(payloads, geo, self._device, 'decode_coded')
+      fake, _ = self._generate_from_code(features, x_dict, *geo[:3])
       return ops.nhwc_to_nchw(fake)
 
   def get_coded_rate(self, x_dict):
     """(coded bpp, raw bpp) averaged over the batch, two Python floats: 8 * file bytes / pixels of the .jpda file
     (ctu.utils.entropy: 24-byte header, and the raw payload where coding does not pay) and of the .jpdc file
     (ctu.utils.bitstream: 20-byte header) of each image.  Sizes of real files, not estimates; get_eval_rate is the
-    reference's Shannon figure."""
+    reference's Shannon figure.  With --encoder_quantizer s2hvq: the .jpdv blobs, and the packed-index file of the same code."""
     payloads = self.get_coded(x_dict)
-    H, W = int(x_dict['image'].shape[-2]), int(x_dict['image'].shape[-1])
-    if getattr(self, 'use_vq', False):
-      # --encoder_quantizer s2hvq: the .jpdv blobs, and the packed-index file (mode 0) of the same code: nb bits per index + header
-      _, _, _, code_len, L, _ = self._vq_geometry(x_dict, 'get_coded_rate')
-      coded = sum(8.0 * len(p) / (H * W) for p in payloads) / len(payloads)
-      return coded, 8.0 * (vqstream.HEADER_BYTES + vqstream.packed_bytes(code_len, L)) / (H * W)
-    shape = self.netE.code_shape(H, W)
-    coded = sum(8.0 * entropy.file_bytes(len(p), shape) / (H * W) for p in payloads) / len(payloads)
-    raw = 8.0 * (bitstream.HEADER_BYTES + bitstream.payload_bytes(shape)) / (H * W)
-    return coded, raw
+    return self.codec.file_rates(payloads, int(x_dict['image'].shape[-2]), int(x_dict['image'].shape[-1]))
 
   # ---- where the bits go (extension; DESIGN.md 4.12) ------------------------------------------------------------------------
   def get_rate_map(self, x_dict):
@@ -930,6 +854,7 @@ class Pix2PixHDModel(BaseModel):
     real, src, label, inst = pre['real'], pre['src'], pre['label'], pre['inst']
     B, H, W = real.N, real.H, real.W
     e_ctx = None
+    rate_on = self.rate_weight > 0.0 and grad_w is not None      # a training step with a rate term
     if self.zero_vis:
       src = None
     # --zero_vis: without a source the visual lanes of G's input stay zero (input_builder zeroes them for a missing image) and the
@@ -941,23 +866,11 @@ class Pix2PixHDModel(BaseModel):
       vis = src
       if self.netE is not None and src is not None:
         self._set_codec_rng(B)
-        # --lambda_rate: a training step's forward also asks the binarizer for the rate term and its gradient
-        # w.r.t. tanh's output, scaled like the distortion gradient: the weight, the kernel's mean over the local batch, and
+        # --lambda_rate / --lambda_vq_rate: a training step's forward also asks the bottleneck for its rate
+        # term and the gradient, scaled like the distortion gradient: the weight, the kernel's mean over the local batch, and
         # the ranks' average in Adam's grad_scale
-        rate_bin = self.netE._binarizer if (self.lambda_rate > 0.0 and grad_w is not None) else None
-        if rate_bin is not None:
-          rate_bin.rate_scale, rate_bin.rate_pixels = self.lambda_rate, H * W
-        # --lambda_vq_rate: the same for the vector-quantizer bottleneck -- bits per pixel of the local batch
-        rate_vq = self.netE._vq if (self.lambda_vq_rate > 0.0 and grad_w is not None) else None
-        if rate_vq is not None:
-          rate_vq.rate_scale, rate_vq.rate_denom = self.lambda_vq_rate, B * H * W
-        try:
+        with self.codec.rate_term(self.rate_weight, B, H, W) if rate_on else contextlib.nullcontext():
           vis, e_ctx = self.netE.fwd(src)
-        finally:
-          if rate_bin is not None:
-            rate_bin.rate_scale = None
-          if rate_vq is not None:
-            rate_vq.rate_scale = None
         if self.netE.training:
           self.codec_draw += 1
       if self.zero_sem:
@@ -1012,11 +925,7 @@ class Pix2PixHDModel(BaseModel):
     layout['vgg'] = list(range(o, o + n_vgg))
     o += n_vgg
     layout['dist'] = o
-    rate_value = None
-    if self.lambda_rate > 0.0 and grad_w is not None and e_ctx is not None:
-      rate_value = self.netE._binarizer.rate_value
-    if self.lambda_vq_rate > 0.0 and grad_w is not None and e_ctx is not None:
-      rate_value = self.netE._vq.rate_value
+    rate_value = self.codec.rate_value if rate_on and e_ctx is not None else None
     if rate_value is not None:
       layout['rate'] = o + 1
     slots = torch.zeros(o + (1 if rate_value is None else 2), dtype=torch.float32, device=dev)

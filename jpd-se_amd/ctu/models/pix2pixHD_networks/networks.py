@@ -293,25 +293,26 @@ class Encoder(nn.Module):
 
   def code(self, x):
     """The binarizer's output (+-1; 0 where eval-mode tanh is exactly 0) as an NHWC Act: model[:4 + 3n + 1](x)."""
-    if self._binarizer is None:
-      raise AttributeError('Encoder: no binarizer found')
+    binarizer = self._require_binarizer()
     h, _ = run_chain_fwd(self._pre, x)
-    b, _ = self._binarizer.fwd(h)
+    b, _ = binarizer.fwd(h)
     return b
 
   def code_shape(self, H, W):
     """(C, h, w) of the code of an H x W image: the binarizer's channels at 1 / 2^n of the resolution."""
-    if self._binarizer is None:
-      raise AttributeError('Encoder: no binarizer found')
     n = self.n_downsampling
-    return (self._binarizer.conv.cout, H >> n, W >> n)
+    return (self._require_binarizer().conv.cout, H >> n, W >> n)
 
   def decode_code(self, b):
     """The receiver's half: features from a code Act (+-1, e.g. ops.code_import of a stored bitstream): model[4 + 3n + 1:](b)."""
-    if self._binarizer is None:
-      raise AttributeError('Encoder: no binarizer found')
+    self._require_binarizer()
     y, _ = run_chain_fwd(self._post, b)
     return y
+
+  def _require_binarizer(self):
+    if self._binarizer is None:
+      raise AttributeError('Encoder: no binarizer found')
+    return self._binarizer
 
   def _require_vq(self):
     if self._vq is None:
@@ -346,8 +347,7 @@ class Encoder(nn.Module):
 
   def forward(self, input, inst=None, mode='get_continuous_img', inst_wise_pool=False):
     if mode == 'get_binary_code':
-      if self._binarizer is None:
-        raise AttributeError('Encoder: no binarizer found')
+      self._require_binarizer()
       return ops.nhwc_to_nchw(self.code(_to_act(input, self.cdtype)))
     if mode != 'get_continuous_img':
       raise ValueError('Invalid encoding mode: {}'.format(mode))

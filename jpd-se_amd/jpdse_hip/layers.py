@@ -323,16 +323,16 @@ class HipBinarizer(nn.Module):
     self.conv = HipConv2d(cin, cout, 1, act=ACT_TANH, apply_bias=False, bias=False, dtype=dtype, device=device)
     self.seed, self.draw, self.n_global0 = 0, 0, 0
     self.noise_override = None
-    self.rate_scale, self.rate_pixels, self.rate_value = None, 0, None
+    self.rate_scale, self.rate_denom, self.rate_value = None, 0, None      # rate_denom: pixels per image
 
   def fwd(self, x):
     t, ctx = self.conv.fwd(x)                     # ctx = (x, t): the tanh backward reads the stored t
     u, self.noise_override = self.noise_override, None
     b = ops.binarize_fwd(t, self.training, self.seed, self.draw, self.n_global0, u)
     if self.rate_scale is not None:
-      # --lambda_rate: the owner set rate_scale / rate_pixels for this call; the value slot stays in
+      # --lambda_rate: the owner set rate_scale / rate_denom for this call; the value slot stays in
       # rate_value and the gradient w.r.t. t travels with the context
-      self.rate_value, _, d_rate, _ = ops.code_rate_loss(b, t, self.rate_pixels, self.rate_scale)
+      self.rate_value, _, d_rate, _ = ops.code_rate_loss(b, t, self.rate_denom, self.rate_scale)
       ctx = Ctx(ctx, d_rate)
     return b, ctx
 

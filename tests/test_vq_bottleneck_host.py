@@ -159,9 +159,10 @@ def test_model_constructor_passes_its_checks_with_the_vq_options(monkeypatch):
 def _bare_vq_model():
   """A Pix2PixHDModel that never ran its constructor: only what the refusals read.  Anything that would touch the device raises."""
   from ctu.models.pix2pixHD_model import Pix2PixHDModel
+  from ctu.models.codec import VQIndexCodec
   m = Pix2PixHDModel.__new__(Pix2PixHDModel)
   boom = lambda *a, **k: (_ for _ in ()).throw(AssertionError('device work before the refusal'))
-  m.__dict__.update(use_vq=True, preprocess=boom, _device=boom, _encoder_eval=boom, _semantics=boom)
+  m.__dict__.update(codec=VQIndexCodec.__new__(VQIndexCodec), preprocess=boom, _device=boom, _encoder_eval=boom, _semantics=boom)
   return m
 
 
@@ -178,7 +179,7 @@ def test_binarizer_only_calls_name_the_flag_before_device_work(call):
 def test_vq_calls_need_the_vq_encoder():
   from ctu.models.pix2pixHD_model import Pix2PixHDModel
   m = Pix2PixHDModel.__new__(Pix2PixHDModel)
-  m.__dict__.update(use_vq=False)
+  m.__dict__.update(codec=None)
   with pytest.raises(ValueError, match='encoder_quantizer s2hvq'):
     m.get_vq_code({})
 
@@ -187,7 +188,7 @@ def test_decode_coded_checks_every_header_on_the_host():
   from ctu.utils import vqstream
   m = _bare_vq_model()
   N, H, W, code_len, L, groups = 2, 64, 32, 128, 8, 4
-  m.__dict__['_vq_geometry'] = lambda x_dict, who: (N, H, W, code_len, L, groups)
+  m.codec.geometry = lambda x_dict, who: (N, H, W, code_len, L, groups)
 
   def blob(count, n_center):
     nb = vqstream.index_bits(n_center)

@@ -137,7 +137,7 @@ def test_get_vq_rate_needs_the_vq_encoder():
   from ctu.models.pix2pixHD_model import Pix2PixHDModel
   m = Pix2PixHDModel.__new__(Pix2PixHDModel)
   boom = lambda *a, **k: (_ for _ in ()).throw(AssertionError('device work before the refusal'))
-  m.__dict__.update(use_vq=False, preprocess=boom, _device=boom, _encoder_eval=boom)
+  m.__dict__.update(codec=None, preprocess=boom, _device=boom, _encoder_eval=boom)
   with pytest.raises(ValueError, match='encoder_quantizer') as err:
     m.get_vq_rate({})
   assert 'get_vq_rate' in str(err.value)
