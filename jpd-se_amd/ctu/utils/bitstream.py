@@ -17,6 +17,8 @@ import struct
 
 import torch
 
+from . import container
+
 MAGIC = b'JPDC'
 VERSION = 1
 _HEADER = struct.Struct('<4sIIII')
@@ -34,10 +36,7 @@ def write_code(path, packed_row, code_shape):
   C, H, W = (int(v) for v in code_shape)
   if min(C, H, W) < 1 or max(C, H, W) >= 1 << 32:
     raise ValueError('write_code: bad code shape %r' % (tuple(code_shape),))
-  row = torch.as_tensor(packed_row)
-  if row.dtype != torch.uint8 or row.dim() != 1 or row.numel() != payload_bytes((C, H, W)):
-    raise ValueError('write_code: a %d x %d x %d code is %d uint8 values in one row, got %s %s'
-                     % (C, H, W, payload_bytes((C, H, W)), row.dtype, tuple(row.shape)))
+  row = container.packed_row(packed_row, payload_bytes((C, H, W)), (C, H, W), 'write_code')
   data = _HEADER.pack(MAGIC, VERSION, C, H, W) + row.cpu().contiguous().numpy().tobytes()
   with open(path, 'wb') as fh:
     fh.write(data)
@@ -47,21 +46,11 @@ def write_code(path, packed_row, code_shape):
 def read_code(path):
   """(packed_row, (C, H, W)) of a file write_code wrote: a uint8 CPU tensor [ceil(C*H*W / 8)] and the code shape.
   ValueError on a wrong magic, an unknown version, a truncated or an over-long payload."""
-  with open(path, 'rb') as fh:
-    data = fh.read()
-  if len(data) < HEADER_BYTES:
-    raise ValueError('%s: %d bytes, shorter than the %d-byte header' % (path, len(data), HEADER_BYTES))
-  magic, version, C, H, W = _HEADER.unpack_from(data)
-  if magic != MAGIC:
-    raise ValueError('%s: not a code file (magic %r, expected %r)' % (path, magic, MAGIC))
-  if version != VERSION:
-    raise ValueError('%s: format version %d, this reader knows %d' % (path, version, VERSION))
+  data = container.read_file(path)
+  C, H, W = container.header(data, _HEADER, MAGIC, VERSION, 'code', path)
   if min(C, H, W) < 1:
     raise ValueError('%s: empty code shape (%d, %d, %d)' % (path, C, H, W))
-  want, got = payload_bytes((C, H, W)), len(data) - HEADER_BYTES
-  if got < want:
-    raise ValueError('%s: truncated, %d payload bytes of the %d a %d x %d x %d code needs' % (path, got, want, C, H, W))
-  if got > want:
-    raise ValueError('%s: %d bytes beyond the %d a %d x %d x %d code needs' % (path, got - want, want, C, H, W))
+  container.check_raw_body(len(data) - HEADER_BYTES, payload_bytes((C, H, W)), path, 'payload', 'a %d x %d x %d code needs' % (C, H, W),
+                           trailing='bytes')
   row = torch.frombuffer(bytearray(data[HEADER_BYTES:]), dtype=torch.uint8)
   return row, (C, H, W)

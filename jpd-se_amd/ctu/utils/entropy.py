@@ -20,8 +20,8 @@ import struct
 
 import torch
 
-from jpdse_hip.ops import check_length_table
-from . import bitstream
+from jpdse_hip import streams
+from . import bitstream, container
 
 MAGIC = b'JPDA'
 VERSION = 1
@@ -40,9 +40,7 @@ def _shape(code_shape, who):
 
 def check_payload(payload, C, who='payload'):
   """ValueError unless `payload` is bytes holding a table of C uint32 lengths that add up to the bytes after it."""
-  if not isinstance(payload, (bytes, bytearray)):
-    raise ValueError('%s: a coded payload is bytes, got %s' % (who, type(payload).__name__))
-  check_length_table(payload, C, who)
+  streams.check_payload(payload, C, who, who + ': a coded payload is bytes, got %s')
 
 
 def mode_of(payload_len, code_shape):
@@ -60,11 +58,7 @@ def write_coded(path, payload, packed_row, code_shape):
   (uint8 [ceil(C*H*W / 8)]: the image's row of get_code(packed=True)).  Returns the number of bytes written."""
   C, H, W = _shape(code_shape, 'write_coded')
   check_payload(payload, C, 'write_coded')
-  row = torch.as_tensor(packed_row)
-  raw = bitstream.payload_bytes((C, H, W))
-  if row.dtype != torch.uint8 or row.dim() != 1 or row.numel() != raw:
-    raise ValueError('write_coded: a %d x %d x %d code is %d uint8 values in one row, got %s %s'
-                     % (C, H, W, raw, row.dtype, tuple(row.shape)))
+  row = container.packed_row(packed_row, bitstream.payload_bytes((C, H, W)), (C, H, W), 'write_coded')
   mode = mode_of(len(payload), (C, H, W))
   body = bytes(payload) if mode == MODE_CODED else row.cpu().contiguous().numpy().tobytes()
   data = _HEADER.pack(MAGIC, VERSION, C, H, W, mode) + body
@@ -77,26 +71,15 @@ def read_coded(path):
   """(payload, mode, (C, H, W)) of a file write_coded wrote.  mode 1: payload = the coded bytes; mode 0: payload = the packed
   row, a uint8 CPU tensor [ceil(C*H*W / 8)] as bitstream.read_code returns it.  ValueError on a wrong magic, an unknown
   version or mode, an empty shape, truncated data, trailing bytes, and a mode-1 length table that does not add up."""
-  with open(path, 'rb') as fh:
-    data = fh.read()
-  if len(data) < HEADER_BYTES:
-    raise ValueError('%s: %d bytes, shorter than the %d-byte header' % (path, len(data), HEADER_BYTES))
-  magic, version, C, H, W, mode = _HEADER.unpack_from(data)
-  if magic != MAGIC:
-    raise ValueError('%s: not a coded code file (magic %r, expected %r)' % (path, magic, MAGIC))
-  if version != VERSION:
-    raise ValueError('%s: format version %d, this reader knows %d' % (path, version, VERSION))
+  data = container.read_file(path)
+  C, H, W, mode = container.header(data, _HEADER, MAGIC, VERSION, 'coded code', path)
   if mode not in (MODE_RAW, MODE_CODED):
     raise ValueError('%s: unknown mode %d (0 = raw, 1 = coded)' % (path, mode))
   if min(C, H, W) < 1:
     raise ValueError('%s: empty code shape (%d, %d, %d)' % (path, C, H, W))
   body = data[HEADER_BYTES:]
   if mode == MODE_RAW:
-    want = bitstream.payload_bytes((C, H, W))
-    if len(body) < want:
-      raise ValueError('%s: truncated, %d payload bytes of the %d a %d x %d x %d code needs' % (path, len(body), want, C, H, W))
-    if len(body) > want:
-      raise ValueError('%s: %d trailing bytes beyond the %d a %d x %d x %d code needs' % (path, len(body) - want, want, C, H, W))
+    container.check_raw_body(len(body), bitstream.payload_bytes((C, H, W)), path, 'payload', 'a %d x %d x %d code needs' % (C, H, W))
     return torch.frombuffer(bytearray(body), dtype=torch.uint8), mode, (C, H, W)
   check_payload(bytes(body), C, path)      # mode 1 has no size of its own: truncation and trailing bytes show here
   return bytes(body), mode, (C, H, W)

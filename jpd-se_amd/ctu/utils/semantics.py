@@ -17,12 +17,13 @@ A plane is stored raw whenever a stream of it was cut or coding did not make it 
 decides; `pack` refuses a coded plane that is not smaller than the raw one), so a .jpds file is never larger than the file
 that stores the same planes raw.  The file size is the rate of the semantics: 8 * len(blob) bits.  Everything here runs on
 the host; nothing touches the device library.  The rules of a plane entry (modes, raw sizes, strip count, the length table)
-are those of jpdse_hip.ops, which produces and consumes the entries: semantics_check_entry is the one check of both.
+are those of jpdse_hip.streams, which produces and consumes the entries: semantics_check_entry is the one check of both.
 """
 import struct
 
-from jpdse_hip.ops import (SEM_RAW as MODE_RAW, SEM_CODED as MODE_CODED, SEM_RAW_BYTES as RAW_BYTES, semantics_strips as strips,
-                           semantics_check_entry, length_table_size)
+from jpdse_hip.streams import (SEM_RAW as MODE_RAW, SEM_CODED as MODE_CODED, SEM_RAW_BYTES as RAW_BYTES, semantics_strips as strips,
+                               semantics_check_entry, length_table_size)
+from . import container
 
 MAGIC = b'JPDS'
 VERSION = 1
@@ -78,13 +79,7 @@ def unpack(blob, who='semantics blob'):
   unknown version, mode or mask, an empty shape, truncated data, trailing bytes and a length table that does not add up."""
   if not isinstance(blob, (bytes, bytearray)):
     raise ValueError('%s: the body of a %s file is bytes, got %s' % (who, SUFFIX, type(blob).__name__))
-  if len(blob) < HEADER_BYTES:
-    raise ValueError('%s: %d bytes, shorter than the %d-byte header' % (who, len(blob), HEADER_BYTES))
-  magic, version, H, W, strip_rows, mask, mode0, mode1 = _HEADER.unpack_from(blob)
-  if magic != MAGIC:
-    raise ValueError('%s: not a coded semantics file (magic %r, expected %r)' % (who, magic, MAGIC))
-  if version != VERSION:
-    raise ValueError('%s: format version %d, this reader knows %d' % (who, version, VERSION))
+  H, W, strip_rows, mask, mode0, mode1 = container.header(blob, _HEADER, MAGIC, VERSION, 'coded semantics', who)
   if mask not in (1, 3):
     raise ValueError('%s: unknown plane mask %d (1 = label, 3 = label and instance)' % (who, mask))
   modes = (mode0, mode1)
@@ -122,7 +117,6 @@ def write(path, blob):
 
 def read(path):
   """The blob of a file `write` wrote, checked: ValueError as `unpack` raises it, on the host, before any device call."""
-  with open(path, 'rb') as fh:
-    blob = fh.read()
+  blob = container.read_file(path)
   unpack(blob, path)
   return blob

@@ -23,7 +23,8 @@ import struct
 import numpy as np
 import torch
 
-from jpdse_hip import ops
+from jpdse_hip import ops, streams
+from . import container
 
 MAGIC = b'JPDV'
 VERSION = 1
@@ -32,9 +33,9 @@ MODE_PACKED, MODE_CODED = 0, 1
 _HEADER = struct.Struct('<4sIIIIII')
 HEADER_BYTES = _HEADER.size
 MAX_N_CENTER = ops.VQ_MAX_L
-MAX_STREAMS = ops.VQ_INDEX_MAX_S
+MAX_STREAMS = streams.VQ_INDEX_MAX_S
 
-index_bits = ops.vq_index_bits
+index_bits = streams.vq_index_bits
 
 
 def packed_bytes(M, n_center):
@@ -83,9 +84,7 @@ def build_blob(shape, n_center, n_streams, payload, indices):
   M = n * code_len
   if not 1 <= S <= min(M, MAX_STREAMS):
     raise ValueError('build_blob: S = %d streams, outside 1 .. min(M = %d, %d)' % (S, M, MAX_STREAMS))
-  if not isinstance(payload, (bytes, bytearray)):
-    raise ValueError('build_blob: a coded payload is bytes, got %s' % type(payload).__name__)
-  ops.check_length_table(payload, S, 'build_blob')
+  streams.check_payload(payload, S, 'build_blob', 'build_blob: a coded payload is bytes, got %s')
   flat = np.asarray(indices).reshape(-1)
   if flat.size != M:
     raise ValueError('build_blob: %d indices for a code of %d x %d' % (flat.size, n, code_len))
@@ -102,13 +101,8 @@ def parse_blob(blob, who='blob'):
   truncated data, trailing bytes, a mode-1 length table that does not add up and a mode-0 value >= L.  Host only."""
   if not isinstance(blob, (bytes, bytearray)):
     raise ValueError('%s: a .jpdv blob is bytes, got %s' % (who, type(blob).__name__))
-  if len(blob) < HEADER_BYTES:
-    raise ValueError('%s: truncated, %d bytes are shorter than the %d-byte header' % (who, len(blob), HEADER_BYTES))
-  magic, version, n, code_len, L, S, mode = _HEADER.unpack_from(blob)
-  if magic != MAGIC:
-    raise ValueError('%s: not a coded index file (magic %r, expected %r)' % (who, magic, MAGIC))
-  if version != VERSION:
-    raise ValueError('%s: format version %d, this reader knows %d' % (who, version, VERSION))
+  n, code_len, L, S, mode = container.header(blob, _HEADER, MAGIC, VERSION, 'coded index', who,
+                                             short='%s: truncated, %d bytes are shorter than the %d-byte header')
   if mode not in (MODE_PACKED, MODE_CODED):
     raise ValueError('%s: unknown mode %d (0 = packed, 1 = coded)' % (who, mode))
   _limits(n, code_len, L, who)
@@ -117,26 +111,15 @@ def parse_blob(blob, who='blob'):
   if mode == MODE_PACKED:
     if S != 0:
       raise ValueError('%s: S = %d streams in mode 0, which stores 0' % (who, S))
-    want = packed_bytes(M, L)
-    if len(body) < want:
-      raise ValueError('%s: truncated, %d body bytes of the %d that %d indices of %d bits take' % (who, len(body), want, M, index_bits(L)))
-    if len(body) > want:
-      raise ValueError('%s: %d trailing bytes beyond the %d that %d indices of %d bits take' % (who, len(body) - want, want, M, index_bits(L)))
+    container.check_raw_body(len(body), packed_bytes(M, L), who, 'body', 'that %d indices of %d bits take' % (M, index_bits(L)))
     values = unpack_indices(body, M, index_bits(L))
     if values.size and values.max() >= L:
       raise ValueError('%s: a packed value %d outside [0, %d)' % (who, int(values.max()), L))
     return n, code_len, L, S, mode, values
   if not 1 <= S <= min(M, MAX_STREAMS):
     raise ValueError('%s: S = %d streams, outside 1 .. min(M = %d, %d)' % (who, S, M, MAX_STREAMS))
-  ops.check_length_table(body, S, who)         # mode 1 has no size of its own: truncation and trailing bytes show here
+  streams.check_length_table(body, S, who)     # mode 1 has no size of its own: truncation and trailing bytes show here
   return n, code_len, L, S, mode, body
-
-
-def _blob_of(blob_or_path):
-  if isinstance(blob_or_path, (bytes, bytearray)):
-    return bytes(blob_or_path), 'blob'
-  with open(blob_or_path, 'rb') as fh:
-    return fh.read(), str(blob_or_path)
 
 
 def write_indices(path, code, n_center, n_streams=64):
@@ -162,9 +145,9 @@ def write_indices(path, code, n_center, n_streams=64):
 
 def _read(blob_or_path, device):
   """(code, L) of a blob or file."""
-  blob, who = _blob_of(blob_or_path)
+  blob, who = container.load(blob_or_path)
   n, code_len, L, S, mode, body = parse_blob(blob, who)
-  dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+  dev = torch.device(streams.default_device(device))
   if mode == MODE_PACKED:
     return torch.from_numpy(body.astype(np.int64)).view(n, code_len).to(dev), L
   return ops.vq_index_decode(body, n * code_len, L, S, dev).to(torch.int64).view(n, code_len), L

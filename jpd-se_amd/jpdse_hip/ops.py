@@ -2,17 +2,16 @@
 
 torch is used for device memory (caching allocator) and the current HIP stream only; all
 arithmetic happens inside libjpdse_hip.so.  Activations travel as `Act`: an NHWC tensor
-[N,H,W,CPAD(C)] (fp32 or bf16) plus its logical channel count.
+[N,H,W,CPAD(C)] (fp32 or bf16) plus its logical channel count.  What is more than a wrapper -- the host half of the three
+device coders: buffer layout, payload rules, row staging, refusals -- lives in streams.py and is re-exported at the end.
 """
 import ctypes
-import struct
 
 import torch
 
 from . import (lib, check, JpdseError, F32, BF16, ConvDesc, InormDesc, EvalMetricsSemArgs, MsssimLossArgs, CodeRateArgs, SemLossArgs, CodeCostArgs, ACT_NONE, PAD_ZERO, PAD_REFLECT)
 from . import (VqSoftFwdArgs, VqHardFwdArgs, VqSoftBwdArgs, VqDecodeArgs, VqDecodeBwdArgs, VqArgmaxArgs, VqPmfArgs, VqPmfBwdArgs,
-               VqIndexEncodeArgs, VqIndexDecodeArgs, VqQuantizeFwdArgs, VqQuantizeBwdArgs, VqRateFwdArgs,
-               VqQuantizeBwdGroupedArgs)
+               VqQuantizeFwdArgs, VqQuantizeBwdArgs, VqRateFwdArgs, VqQuantizeBwdGroupedArgs)
 
 
 def cpad(c):
@@ -571,230 +570,6 @@ def code_import(code, N, H, W, C, dtype_code, out=None):
   return b
 
 
-# ---- learned codec: entropy-coded bitstream (entropy.hip; format: DESIGN.md 4.8) -------------------------------------------
-def code_entropy_encode(b):
-  """The entropy-coded payload of every image of the code `b` (jpdse_code_entropy_encode): a list of N `bytes`, each the
-  image's C little-endian uint32 stream lengths followed by its C streams.  One device buffer -- the N sizes, the N status
-  words, then the payload rows -- is copied to the host once.  JpdseError if a stream outgrew its derived capacity."""
-  L = lib()
-  N, dev = b.N, b.t.device
-  cap = L.jpdse_code_entropy_capacity(b.H, b.W, b.C)
-  n_ws = L.jpdse_code_entropy_workspace_size(N, b.H, b.W, b.C)
-  if cap == 0 or n_ws == 0:
-    raise ValueError('code_entropy_encode: a %d x %d x %d x %d code is beyond the coder\'s limits' % (N, b.C, b.H, b.W))
-  head = (8 * N + 15) // 16 * 16
-  buf = torch.empty(head + N * cap, dtype=torch.uint8, device=dev)
-  meta = buf[:8 * N].view(torch.int32)
-  ws = workspace(n_ws, dev)
-  check(L.jpdse_code_entropy_encode(b.dtype, N, b.H, b.W, b.C, _p(b.t), _p(buf[head:]), cap, _p(meta[:N]), _p(meta[N:]),
-                                    _p(ws), ws.numel(), _stream()), 'code_entropy_encode')
-  host = buf.cpu().numpy()
-  sizes, status = host[:4 * N].view('<i4'), host[4 * N:8 * N].view('<i4')
-  if status.any():
-    raise JpdseError('code_entropy_encode: a stream outgrew its H*W + 8 bytes (status %s)' % (status.tolist(),))
-  return [host[head + n * cap:head + n * cap + int(sizes[n])].tobytes() for n in range(N)]
-
-
-def length_table_size(buf, count, who, at=0):
-  """The payload layout of DESIGN.md 4.8 on the host: buf[at:] starts with a table of `count` little-endian uint32 stream
-  lengths, then the streams.  Returns the size the table gives the payload, 4 * count + its sum; ValueError when buf ends
-  inside the table.  Nothing is copied."""
-  if len(buf) - at < 4 * count:
-    raise ValueError('%s: truncated, %d bytes are shorter than the table of %d stream lengths' % (who, len(buf) - at, count))
-  return 4 * count + sum(struct.unpack_from('<%dI' % count, buf, at))
-
-
-def check_length_table(payload, count, who):
-  """ValueError unless the table of `count` lengths at the start of `payload` adds up to exactly the bytes that follow it."""
-  size = length_table_size(payload, count, who)
-  if size != len(payload):
-    raise ValueError('%s: the length table sums to %d, but %d bytes follow it' % (who, size - 4 * count, len(payload) - 4 * count))
-
-
-def code_entropy_decode(payloads, N, H, W, C, dtype_code, device=None):
-  """The inverse (jpdse_code_entropy_decode): N payloads as code_entropy_encode returns them -> the NHWC Act [N, H, W, C] of
-  +1 / -1 that code_import gives for the raw code.  ValueError before any library call for a wrong payload count, an item
-  that is not `bytes`, or a payload whose length table does not add up to the bytes that follow it.  device: where the Act
-  is made (default: the current device)."""
-  if not isinstance(payloads, (list, tuple)) or len(payloads) != N:
-    raise ValueError('code_entropy_decode: expected a list of %d payloads, got %s'
-                     % (N, 'a list of %d' % len(payloads) if isinstance(payloads, (list, tuple)) else type(payloads).__name__))
-  for n, p in enumerate(payloads):
-    if not isinstance(p, (bytes, bytearray)):
-      raise ValueError('code_entropy_decode: payload %d is %s, not bytes' % (n, type(p).__name__))
-    check_length_table(p, C, 'code_entropy_decode: payload %d' % n)
-  stride = max(len(p) for p in payloads)
-  if stride >= 1 << 31:
-    raise ValueError('code_entropy_decode: a payload of %d bytes' % stride)
-  rows = torch.zeros((N, stride), dtype=torch.uint8)
-  for n, p in enumerate(payloads):
-    rows[n, :len(p)] = torch.frombuffer(bytearray(p), dtype=torch.uint8)
-  sizes = (ctypes.c_int32 * N)(*[len(p) for p in payloads])
-  dev = device if device is not None else torch.device('cuda', torch.cuda.current_device())
-  rows = rows.to(dev)
-  b = Act.empty(N, H, W, C, dtype_code, dev)
-  check(lib().jpdse_code_entropy_decode(dtype_code, N, H, W, C, _p(rows), stride, sizes, _p(b.t), _stream()),
-        'code_entropy_decode')
-  return b
-
-
-# ---- learned codec: coded label and instance maps (semantics.hip; format: DESIGN.md 4.9) -----------------------------------
-SEM_RAW, SEM_CODED = 0, 1
-SEM_RAW_BYTES = (1, 4)                      # label plane: uint8, instance plane: little-endian int32
-_SEM_RAW_DTYPE = (torch.uint8, torch.int32)
-_SEM_NAMES = ('label', 'instance')
-
-
-def semantics_strips(H, strip_rows):
-  return (H + strip_rows - 1) // strip_rows
-
-
-def _sem_maps(label, inst, who):
-  if not torch.is_tensor(label) or label.dtype != torch.float32 or label.dim() != 4 or label.shape[1] != 1:
-    raise ValueError('%s: the label map is a float32 [N, 1, H, W] tensor' % who)
-  if inst is not None and (not torch.is_tensor(inst) or inst.dtype != torch.int64 or tuple(inst.shape) != tuple(label.shape)):
-    raise ValueError('%s: the instance map is an int64 tensor of the label map\'s shape %s' % (who, tuple(label.shape)))
-  if not label.is_contiguous() or (inst is not None and not inst.is_contiguous()):
-    raise ValueError('%s: the maps must be contiguous' % who)
-  return int(label.shape[0]), int(label.shape[2]), int(label.shape[3])
-
-
-def semantics_encode(label, inst, strip_rows=8):
-  """The coded planes of every image (jpdse_semantics_encode).  label: device float32 [N, 1, H, W] with integer values in
-  [0, 255]; inst: device int64 [N, 1, H, W] with values in [0, 2^31), or None for no instance plane -- the tensors the input
-  builder reads.  Returns a list of N items [label entry, instance entry]; an entry is (mode, payload) and None for the
-  absent instance plane.  mode 1: payload = the plane's S uint32 stream lengths and its S streams; mode 0: the raw plane
-  (uint8, or little-endian int32), taken where a stream outgrew its slot (status bit 0) or coding did not make the plane
-  smaller.  ValueError, naming the image, for a value out of range (status bit 1).  The sizes and status words are copied
-  to the host first, then each payload by itself: the rows of the device buffer are capacity-sized, the payloads are not."""
-  N, H, W = _sem_maps(label, inst, 'semantics_encode')
-  strip_rows = int(strip_rows)
-  if strip_rows < 1:
-    raise ValueError('semantics_encode: strip_rows %d is below 1' % strip_rows)
-  L = lib()
-  mask = 1 | (2 if inst is not None else 0)
-  cap = L.jpdse_semantics_capacity(H, W, strip_rows, mask)
-  n_ws = L.jpdse_semantics_workspace_size(N, H, W, strip_rows, mask)
-  if cap == 0 or n_ws == 0:
-    raise ValueError('semantics_encode: %d maps of %d x %d in strips of %d rows are beyond the coder\'s limits' % (N, H, W, strip_rows))
-  dev = label.device
-  offs = (0, L.jpdse_semantics_capacity(H, W, strip_rows, 1))
-  head = (16 * N + 15) // 16 * 16
-  buf = torch.empty(head + N * cap, dtype=torch.uint8, device=dev)
-  meta = buf[:16 * N].view(torch.int32)
-  meta.zero_()
-  ws = workspace(n_ws, dev)
-  check(L.jpdse_semantics_encode(N, H, W, strip_rows, mask, _p(label), _p(inst), _p(buf[head:]), cap, _p(meta[:2 * N]),
-                                 _p(meta[2 * N:]), _p(ws), ws.numel(), _stream()), 'semantics_encode')
-  # the rows are capacity-sized (raw + 12 S bytes per plane): the sizes and status words go to the host first, then only
-  # the payloads themselves
-  host = meta.cpu().numpy()
-  sizes, status = host[:2 * N].reshape(N, 2), host[2 * N:].reshape(N, 2)
-  planes = [(0, label)] + ([(1, inst)] if inst is not None else [])
-  for n in range(N):
-    for p, _ in planes:
-      if status[n, p] & 2:
-        raise ValueError('semantics_encode: the %s map of image %d holds a value outside the plane\'s range (%s)'
-                         % (_SEM_NAMES[p], n, 'integers in [0, 255]' if p == 0 else '[0, 2^31)'))
-  out = []
-  for n in range(N):
-    item = [None, None]
-    for p, t in planes:
-      raw = H * W * SEM_RAW_BYTES[p]
-      size = int(sizes[n, p])
-      if (status[n, p] & 1) or size >= raw:
-        item[p] = (SEM_RAW, t[n, 0].to(_SEM_RAW_DTYPE[p]).cpu().numpy().astype('u1' if p == 0 else '<i4').tobytes())
-      else:
-        at = head + n * cap + offs[p]
-        item[p] = (SEM_CODED, buf[at:at + size].cpu().numpy().tobytes())
-    out.append(item)
-  return out
-
-
-def semantics_check_entry(entry, plane, H, W, strip_rows, who):
-  """ValueError unless `entry` is (mode, bytes) holding a raw plane of the right size or a coded payload whose table of
-  S = ceil(H / strip_rows) lengths adds up to the bytes after it.  Host only."""
-  if not isinstance(entry, (tuple, list)) or len(entry) != 2 or not isinstance(entry[1], (bytes, bytearray)):
-    raise ValueError('%s: an entry is (mode, bytes)' % who)
-  mode, payload = entry
-  if mode not in (SEM_RAW, SEM_CODED):
-    raise ValueError('%s: unknown mode %r (0 = raw, 1 = coded)' % (who, mode))
-  if mode == SEM_CODED:
-    check_length_table(payload, semantics_strips(H, strip_rows), who)
-  elif len(payload) != H * W * SEM_RAW_BYTES[plane]:
-    raise ValueError('%s: a raw plane (%s) of %d x %d is %d bytes, got %d'
-                     % (who, _SEM_NAMES[plane], H, W, H * W * SEM_RAW_BYTES[plane], len(payload)))
-
-
-def semantics_decode(items, H, W, strip_rows, num_labels, device=None):
-  """The inverse (jpdse_semantics_decode): N items as semantics_encode returns them -> (label float32 [N, 1, H, W],
-  instance int64 [N, 1, H, W]) on the device, the form the input builder reads; without an instance plane the instance map
-  is zeros.  ValueError before any library call for anything that is not such a list (all items with the same planes), a raw
-  plane of the wrong size and a length table that does not add up; ValueError after the decode for a label >= num_labels
-  or an instance value >= 2^31, naming the image."""
-  who = 'semantics_decode'
-  if not isinstance(items, (list, tuple)) or len(items) == 0:
-    raise ValueError('%s: expected a list of per-image [label entry, instance entry] items' % who)
-  N = len(items)
-  H, W, strip_rows, num_labels = int(H), int(W), int(strip_rows), int(num_labels)
-  if min(H, W, strip_rows) < 1 or not 1 <= num_labels <= 256:
-    raise ValueError('%s: bad shape %d x %d, strip_rows %d or num_labels %d' % (who, H, W, strip_rows, num_labels))
-  mask = None
-  for n, item in enumerate(items):
-    if not isinstance(item, (list, tuple)) or len(item) != 2 or item[0] is None:
-      raise ValueError('%s: item %d is not [label entry, instance entry or None]' % (who, n))
-    m = 1 | (2 if item[1] is not None else 0)
-    if mask is not None and m != mask:
-      raise ValueError('%s: item %d has other planes than item 0' % (who, n))
-    mask = m
-    for p in range(2):
-      if item[p] is not None:
-        semantics_check_entry(item[p], p, H, W, strip_rows, '%s: %s plane of image %d' % (who, _SEM_NAMES[p], n))
-  # raw planes are checked on the host, before any device work
-  raws = {}
-  for n, item in enumerate(items):
-    for p in range(2):
-      if item[p] is not None and item[p][0] == SEM_RAW:
-        a = torch.frombuffer(bytearray(item[p][1]), dtype=_SEM_RAW_DTYPE[p]).view(H, W)
-        if p == 0 and int(a.max()) >= num_labels:
-          raise ValueError('%s: the label map of image %d holds label %d, the label set has %d' % (who, n, int(a.max()), num_labels))
-        if p == 1 and int(a.min()) < 0:
-          raise ValueError('%s: the instance map of image %d holds a negative value' % (who, n))
-        raws[(n, p)] = a
-  dev = device if device is not None else torch.device('cuda', torch.cuda.current_device())
-  S = semantics_strips(H, strip_rows)
-  longest = [max([len(it[p][1]) for it in items if it[p] is not None and it[p][0] == SEM_CODED] + [4 * S]) for p in range(2)]
-  inst_off = longest[0] if mask == 3 else 0
-  stride = inst_off + (longest[1] if mask & 2 else 0) if mask == 3 else longest[0]
-  label = torch.empty((N, 1, H, W), dtype=torch.float32, device=dev)
-  inst = torch.empty((N, 1, H, W), dtype=torch.int64, device=dev) if mask & 2 else torch.zeros((N, 1, H, W), dtype=torch.int64, device=dev)
-  if len(raws) < N * (2 if mask == 3 else 1):
-    if stride >= 1 << 31:
-      raise ValueError('%s: payloads of %d bytes' % (who, stride))
-    head = (8 * N + 15) // 16 * 16
-    host = torch.zeros(head + N * stride, dtype=torch.uint8)
-    sizes = host[:8 * N].view(torch.int32).view(N, 2)
-    for n, item in enumerate(items):
-      for p in range(2):
-        if item[p] is not None and item[p][0] == SEM_CODED:
-          at = head + n * stride + (inst_off if p else 0)
-          host[at:at + len(item[p][1])] = torch.frombuffer(bytearray(item[p][1]), dtype=torch.uint8)
-          sizes[n, p] = len(item[p][1])
-    buf = host.to(dev)
-    bad = torch.empty(N, dtype=torch.int32, device=dev)
-    check(lib().jpdse_semantics_decode(N, H, W, strip_rows, mask, num_labels, _p(buf[head:]), stride, inst_off, _p(buf),
-                                       _p(label), _p(inst) if mask & 2 else ctypes.c_void_p(0), _p(bad), _stream()), who)
-    flags = bad.cpu().tolist()
-    for n, f in enumerate(flags):
-      if f & 1:
-        raise ValueError('%s: the label map of image %d decodes to a label outside the set of %d' % (who, n, num_labels))
-      if f & 2:
-        raise ValueError('%s: the instance map of image %d decodes to a value of 2^31 or more' % (who, n))
-  for (n, p), a in raws.items():
-    (inst if p else label)[n, 0].copy_(a.to(dev))
-  return label, inst
-
-
 # ---- evaluation metrics (metrics.hip) ------------------------------------------------------------
 MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
 
@@ -1239,76 +1014,9 @@ def vq_rate_fwd(x, code_book, sigma, G, denom, scale=1.0, hard=False, want_hist=
   return rate, hist, dhist
 
 
-# ---- soft-to-hard vector quantizer: coded index stream (vq_coder.hip; format: DESIGN.md 4.14) -------------------------------
-VQ_INDEX_MAX_S = 65535
-
-
-def vq_index_bits(L):
-  """Binary decisions per symbol of an alphabet of L: max(1, bit_length(L - 1))."""
-  return max(1, (int(L) - 1).bit_length())
-
-
-def _vq_index_shape(who, M, L, S):
-  M, L, S = int(M), int(L), int(S)
-  if not 2 <= L <= VQ_MAX_L:
-    raise ValueError('%s: L = %d, the coder takes 2 .. %d' % (who, L, VQ_MAX_L))
-  if M < 1 or not 1 <= S <= min(M, VQ_INDEX_MAX_S):
-    raise ValueError('%s: M = %d indices in S = %d streams (M >= 1, 1 <= S <= min(M, %d))' % (who, M, S, VQ_INDEX_MAX_S))
-  if vq_index_bits(L) * M + 12 * S >= 1 << 31:
-    raise ValueError('%s: M = %d indices of %d bits in %d streams are beyond the coder\'s limits (capacity below 2^31 bytes)'
-                     % (who, M, vq_index_bits(L), S))
-  return M, L, S
-
-
-def vq_index_encode(index, L, S):
-  """The coded payload of the device int32 [M] indices, all in [0, L), in S interleaved streams (jpdse_vq_index_encode):
-  `bytes` holding the S little-endian uint32 stream lengths and the S streams.  One device buffer -- the size, the status
-  word, then the payload at its capacity -- is copied to the host once.  ValueError for an index outside [0, L) (status
-  bit 1), JpdseError if a stream outgrew its derived capacity (bit 0)."""
-  assert index.dim() == 1 and index.is_cuda, (tuple(index.shape), index.device)
-  M, L, S = _vq_index_shape('vq_index_encode', index.numel(), L, S)
-  dev = index.device
-  _vq_index(index, M, dev)
-  lb = lib()
-  cap, n_ws = lb.jpdse_vq_index_capacity(M, L, S), lb.jpdse_vq_index_workspace_size(M, L, S)
-  assert cap == vq_index_bits(L) * M + 12 * S and n_ws > 0, (cap, n_ws)
-  head = 16
-  buf = torch.empty(head + cap, dtype=torch.uint8, device=dev)
-  meta = buf[:8].view(torch.int32)
-  ws = workspace(n_ws, dev)
-  args = VqIndexEncodeArgs(M, L, S, index.data_ptr(), buf[head:].data_ptr(), cap, meta[0:].data_ptr(), meta[1:].data_ptr(),
-                           ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
-  check(lb.jpdse_vq_index_encode(ctypes.byref(args)), 'vq_index_encode')
-  host = buf.cpu().numpy()
-  size, status = (int(v) for v in host[:8].view('<i4'))
-  if status & 2:
-    raise ValueError('vq_index_encode: an index outside [0, %d)' % L)
-  if status & 1:
-    raise JpdseError('vq_index_encode: a stream outgrew its slot of nb * count + 8 bytes (status %d)' % status)
-  return host[head:head + size].tobytes()
-
-
-def vq_index_decode(payload, M, L, S, device=None):
-  """The inverse (jpdse_vq_index_decode): a payload as vq_index_encode returns it -> the int32 [M] indices on `device`
-  (default: the current device).  ValueError before any library call for a payload that is not `bytes` or whose table of S
-  lengths does not add up to the bytes that follow it; ValueError after the decode when a decoded value was >= L (status
-  bit 1: the bytes are not a coded stream of this alphabet)."""
-  M, L, S = _vq_index_shape('vq_index_decode', M, L, S)
-  if not isinstance(payload, (bytes, bytearray)):
-    raise ValueError('vq_index_decode: the payload is %s, not bytes' % type(payload).__name__)
-  check_length_table(payload, S, 'vq_index_decode')
-  if len(payload) >= 1 << 31:
-    raise ValueError('vq_index_decode: a payload of %d bytes' % len(payload))
-  dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
-  if dev.type != 'cuda':
-    raise JpdseError('vq_index_decode: device %s: the JPD-SE HIP path has no CPU fallback' % (dev,))
-  src = torch.frombuffer(bytearray(payload), dtype=torch.uint8).to(dev)
-  index = torch.empty(M, dtype=torch.int32, device=dev)
-  status = torch.zeros(1, dtype=torch.int32, device=dev)
-  with torch.cuda.device(dev):
-    args = VqIndexDecodeArgs(M, L, S, src.data_ptr(), len(payload), index.data_ptr(), status.data_ptr(),
-                             torch.cuda.current_stream().cuda_stream)
-    check(lib().jpdse_vq_index_decode(ctypes.byref(args)), 'vq_index_decode')
-  if int(status.item()) & 2:
-    raise ValueError('vq_index_decode: a decoded value outside [0, %d): not a coded stream of this alphabet' % L)
-  return index
+# ---- the host half of the three device coders (streams.py) -----------------------------------------------------
+# Re-exported here, where their callers look for them.  At the end, as is the import at the end of streams: whichever of the two
+# modules is imported first finds, half-way through its own import, every name of the other that it asks for.
+from .streams import (code_entropy_encode, code_entropy_decode, length_table_size, check_length_table,  # noqa: E402,F401
+                      SEM_RAW, SEM_CODED, SEM_RAW_BYTES, semantics_strips, semantics_encode, semantics_check_entry, semantics_decode,
+                      VQ_INDEX_MAX_S, vq_index_bits, vq_index_encode, vq_index_decode)

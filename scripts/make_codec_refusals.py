@@ -121,9 +121,10 @@ def run():
   """[[case id, exception type, message]] on the code this file sits beside; 'returned' for a call that raised nothing."""
   import jpdse_hip
   import jpdse_hip.ops, jpdse_hip.layers  # noqa: E401,F401
-  saved = torch.cuda.is_available, jpdse_hip.lib, jpdse_hip.ops.lib
+  streams = getattr(jpdse_hip, 'streams', jpdse_hip.ops)      # binds `lib` too, where the layout has it
+  saved = torch.cuda.is_available, jpdse_hip.lib, jpdse_hip.ops.lib, streams.lib
   touched = lambda: (_ for _ in ()).throw(AssertionError('library touched'))
-  torch.cuda.is_available, jpdse_hip.lib, jpdse_hip.ops.lib = (lambda: False), touched, touched
+  torch.cuda.is_available, jpdse_hip.lib, jpdse_hip.ops.lib, streams.lib = (lambda: False), touched, touched, touched
   rows = []
   try:
     for quantizer in (None, 'binarizer', 's2hvq'):
@@ -135,7 +136,7 @@ def run():
         except Exception as e:      # every outcome is a row
           rows.append(['%s/%s' % (quantizer or 'none', cid), type(e).__name__, str(e)])
   finally:
-    torch.cuda.is_available, jpdse_hip.lib, jpdse_hip.ops.lib = saved
+    torch.cuda.is_available, jpdse_hip.lib, jpdse_hip.ops.lib, streams.lib = saved
   return rows
 
 

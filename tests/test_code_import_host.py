@@ -67,6 +67,7 @@ def test_ops_code_import_refuses_a_wrong_row_length_without_the_library(monkeypa
   touched = lambda: (_ for _ in ()).throw(AssertionError('library touched'))
   monkeypatch.setattr(jpdse_hip, 'lib', touched)
   monkeypatch.setattr(ops, 'lib', touched)                       # ops binds `lib` at import time
+  monkeypatch.setattr(jpdse_hip.streams, 'lib', touched)
   N, H, W, C = 2, 5, 7, 9                                         # 315 bits: 40 bytes
   for bad in (torch.zeros(N, 39, dtype=torch.uint8), torch.zeros(N, 41, dtype=torch.uint8),
               torch.zeros(N + 1, 40, dtype=torch.uint8), torch.zeros(N * 40, dtype=torch.uint8),

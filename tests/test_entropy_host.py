@@ -247,6 +247,7 @@ def test_ops_decode_refuses_bad_payloads_without_the_library(monkeypatch):
   touched = lambda: (_ for _ in ()).throw(AssertionError('library touched'))
   monkeypatch.setattr(jpdse_hip, 'lib', touched)
   monkeypatch.setattr(ops, 'lib', touched)
+  monkeypatch.setattr(jpdse_hip.streams, 'lib', touched)
   shape = (2, 3, 1, 9)
   good = list(cases.reference(shape, 'half')[1])
   bump = bytearray(good[0])

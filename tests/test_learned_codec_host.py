@@ -87,6 +87,7 @@ def test_still_refused_combinations_fail_before_device_work(over, monkeypatch):
   import jpdse_hip.ops, jpdse_hip.layers  # noqa: E401
   monkeypatch.setattr(jpdse_hip, 'lib', touched)
   monkeypatch.setattr(jpdse_hip.ops, 'lib', touched)           # ops binds `lib` at import time
+  monkeypatch.setattr(jpdse_hip.streams, 'lib', touched)
   with pytest.raises(NotImplementedError):
     Pix2PixHDModel(_codec_opts(gpu_ids=[0], **over))
 

@@ -296,6 +296,7 @@ def test_ops_and_model_refuse_bad_input_without_the_library(monkeypatch):
   touched = lambda: (_ for _ in ()).throw(AssertionError('library touched'))
   monkeypatch.setattr(jpdse_hip, 'lib', touched)
   monkeypatch.setattr(ops, 'lib', touched)
+  monkeypatch.setattr(jpdse_hip.streams, 'lib', touched)
   shape = (3, 19, 33, 8)
   _, H, W, sr = shape
   good = [list(_blob(shape, 'rects', n)[1]) for n in range(2)]

@@ -296,6 +296,7 @@ def test_ops_decode_refuses_bad_payloads_without_the_library(monkeypatch):
   touched = lambda: (_ for _ in ()).throw(AssertionError('library touched'))
   monkeypatch.setattr(jpdse_hip, 'lib', touched)
   monkeypatch.setattr(ops, 'lib', touched)
+  monkeypatch.setattr(jpdse_hip.streams, 'lib', touched)
   M, L, S = 3000, 100, 7
   good = cases.reference((M, L, S), 'uniform')[1]
   bump = bytearray(good)
