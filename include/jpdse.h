@@ -816,6 +816,56 @@ typedef struct jpdse_vq_index_decode_args {
 } jpdse_vq_index_decode_args;
 int jpdse_vq_index_decode(const jpdse_vq_index_decode_args* args);
 
+/* ---- soft-to-hard vector quantizer: coded index planes (no reference counterpart; format: DESIGN.md 4.19) ------------------
+ * The code of ONE image as the feature map it is, coded with a spatial context.  index: DEVICE int32 [h * w * G], pixel by
+ * pixel in raster order, groups ascending inside a pixel (cell (y, x, g) at (y * w + x) * G + g), every value in [0, L).  The
+ * plane of a group is cut into K = ceil(h / strip_rows) strips of strip_rows rows (the last may be shorter); stream
+ * s = k * G + g is strip k of group g: cnt_s = rows_k * w symbols in raster order, its own table, no look above the strip.
+ * Per symbol v, with Lf / U / UL the left / upper / upper-left cell of the group inside the strip (a comparison with a cell
+ * that does not exist is false):
+ *   1. if Lf exists: the bit v == Lf with table entry (Lf == U) | (UL == Lf) << 1 | (UL == U) << 2
+ *   2. if no bit 1 yet, U exists and U != Lf (true without Lf): the bit v == U with entry 8 + (UL == Lf), or 10 without Lf
+ *   3. if no bit 1 yet: v through the bit tree of the index stream above, node m at entry 10 + m
+ * A table is 10 + 2^nb adaptive probabilities, nb = max(1, bit_length(L - 1)); a decision is the adaptive binary decision of
+ * jpdse_code_entropy_encode.  A stream stores at most (nb + 2) * cnt_s + 8 bytes (its slot).
+ * Payload: S = K G little-endian uint32 stream lengths, then the S streams in order.
+ *   capacity(...)      = 4 S + the sum of the slots = (nb + 2) h w G + 12 S; `out` must hold that many
+ *   encode             writes the payload to out, its size to *size, and *status: bit 0 a stream was cut at its slot (the
+ *                      bound makes that unreachable), bit 1 an index outside [0, L) was met; it is coded, and seen by later
+ *                      symbols as their neighbour, as 0.  Both device words are written by the call's last kernel
+ *   decode             reads a payload of in_bytes bytes (device data it does not trust: a length that points outside the
+ *                      payload is clipped to it, a byte past a stream's end reads as 0) and writes exactly h w G indices, all
+ *                      in [0, L): a literal is taken as read; a decoded value >= L is written, and seen by later symbols, as
+ *                      L - 1 and sets bit 1 of *status with a plain store (the word is never cleared by the library)
+ * Plain loads and stores, no atomics: two calls give identical bytes.  Every loop is bounded by cnt_s, nb or the bytes pending.
+ * Limits: 2 <= L <= 512, h, w, G, strip_rows >= 1, S <= 65535, h w G < 2^31 and capacity < 2^31.  Both size queries are
+ * host-only and return 0 outside the limits.  JPDSE_EINVAL before any launch: a NULL args or pointer, a value outside the
+ * limits, out_bytes below the capacity, a workspace that is missing or below jpdse_vq_plane_workspace_size(), in_bytes below
+ * the 4 S of the table or >= 2^31. */
+size_t jpdse_vq_plane_capacity(int32_t h, int32_t w, int32_t G, int32_t L, int32_t strip_rows);
+size_t jpdse_vq_plane_workspace_size(int32_t h, int32_t w, int32_t G, int32_t L, int32_t strip_rows);
+typedef struct jpdse_vq_plane_encode_args {
+  int32_t h, w, G, L, strip_rows;
+  const int32_t* index;    /* device [h * w * G] */
+  uint8_t* out;            /* device, out_bytes >= capacity */
+  int64_t out_bytes;
+  int32_t* size;           /* device word: the payload's bytes */
+  int32_t* status;         /* device word */
+  void* ws;
+  size_t ws_bytes;
+  void* stream;
+} jpdse_vq_plane_encode_args;
+int jpdse_vq_plane_encode(const jpdse_vq_plane_encode_args* args);
+typedef struct jpdse_vq_plane_decode_args {
+  int32_t h, w, G, L, strip_rows;
+  const uint8_t* in;       /* device, in_bytes: the payload */
+  int64_t in_bytes;
+  int32_t* index;          /* device [h * w * G] */
+  int32_t* status;         /* device word */
+  void* stream;
+} jpdse_vq_plane_decode_args;
+int jpdse_vq_plane_decode(const jpdse_vq_plane_decode_args* args);
+
 /* ---- vector-quantizer bottleneck: quantize in one call, [M][L] never in memory (vq_bottleneck.hip) ---------
  * The quantizer above as a layer: features in, features out.  x, y, dy, dx: row-major [M][D] in `dtype`; code_book: fp32
  * [L][D]; d[m][k] and p[m][k] as defined above (the direct score, j ascending; the row minimum subtracted, the entry at the

@@ -183,6 +183,62 @@ int vq_index_decode_check(const jpdse_vq_index_decode_args* a) {
   return JPDSE_OK;
 }
 
+// jpdse_vq_plane_* (vq_plane.hip): the same for the index planes.  K = ceil(h / strip_rows) strips, S = K G
+// streams, M = h w G symbols of at most nb + 2 decisions each: the slots add up to (nb + 2) M + 8 S and the capacity is that +
+// the 4 S of the table.
+int vq_plane_streams(int h, int G, int strip_rows) { return (h + strip_rows - 1) / strip_rows * G; }
+
+static bool vq_plane_in_limits(int h, int w, int G, int L, int strip_rows) {
+  if (L < 2 || L > 512 || h < 1 || w < 1 || G < 1 || strip_rows < 1) return false;
+  const long long hw = (long long)h * w;
+  if (hw >= (1LL << 31) || hw * G >= (1LL << 31)) return false;
+  const long long S = ((long long)h + strip_rows - 1) / strip_rows * G;
+  return S <= 65535 && (vq_index_bits(L) + 2) * hw * G + 12 * S < (1LL << 31);
+}
+
+long long vq_plane_capacity_bytes(int h, int w, int G, int L, int strip_rows) {
+  if (!vq_plane_in_limits(h, w, G, L, strip_rows)) return 0;
+  return (long long)(vq_index_bits(L) + 2) * h * w * G + 12LL * vq_plane_streams(h, G, strip_rows);
+}
+
+size_t vq_plane_workspace_bytes(int h, int w, int G, int L, int strip_rows) {
+  if (!vq_plane_in_limits(h, w, G, L, strip_rows)) return 0;
+  // the slots, then the lengths and the flags of the streams
+  const size_t S = (size_t)vq_plane_streams(h, G, strip_rows);
+  return align_up((size_t)(vq_index_bits(L) + 2) * h * w * G + 8 * S, 16) + 2 * S * sizeof(int32_t);
+}
+
+static int vq_plane_shape_check(const char* who, int h, int w, int G, int L, int strip_rows) {
+  JPDSE_REQUIRE(L >= 2 && L <= 512, "%s: n_center L = %d (2 .. 512)", who, L);
+  JPDSE_REQUIRE(h >= 1 && w >= 1 && G >= 1, "%s: a plane of h = %d x w = %d cells in G = %d groups (each at least 1)", who, h, w, G);
+  JPDSE_REQUIRE(strip_rows >= 1, "%s: strip_rows = %d (at least 1)", who, strip_rows);
+  const long long S = ((long long)h + strip_rows - 1) / strip_rows * G;
+  JPDSE_REQUIRE(S <= 65535, "%s: S = %lld streams (ceil(h / strip_rows) * G, at most 65535)", who, S);
+  JPDSE_REQUIRE(vq_plane_in_limits(h, w, G, L, strip_rows), "%s: h * w * G = %lld indices or the capacity (both below 2^31)", who,
+                (long long)h * w * G);
+  return JPDSE_OK;
+}
+
+int vq_plane_encode_check(const jpdse_vq_plane_encode_args* a) {
+  JPDSE_REQUIRE(a != nullptr, "vq_plane_encode: null argument struct");
+  if (int rc = vq_plane_shape_check("vq_plane_encode", a->h, a->w, a->G, a->L, a->strip_rows)) return rc;
+  JPDSE_REQUIRE(a->index && a->out && a->size && a->status, "vq_plane_encode: null pointer");
+  const long long cap = vq_plane_capacity_bytes(a->h, a->w, a->G, a->L, a->strip_rows);
+  JPDSE_REQUIRE(a->out_bytes >= cap, "vq_plane_encode: output of %lld bytes below the payload capacity %lld",
+                (long long)a->out_bytes, cap);
+  return vq_ws_check("vq_plane_encode", a->ws, a->ws_bytes, vq_plane_workspace_bytes(a->h, a->w, a->G, a->L, a->strip_rows));
+}
+
+int vq_plane_decode_check(const jpdse_vq_plane_decode_args* a) {
+  JPDSE_REQUIRE(a != nullptr, "vq_plane_decode: null argument struct");
+  if (int rc = vq_plane_shape_check("vq_plane_decode", a->h, a->w, a->G, a->L, a->strip_rows)) return rc;
+  JPDSE_REQUIRE(a->in && a->index && a->status, "vq_plane_decode: null pointer");
+  const int table = 4 * vq_plane_streams(a->h, a->G, a->strip_rows);
+  JPDSE_REQUIRE(a->in_bytes >= table && a->in_bytes < (1LL << 31),
+                "vq_plane_decode: payload of %lld bytes, outside [%d (its length table), 2^31)", (long long)a->in_bytes, table);
+  return JPDSE_OK;
+}
+
 // jpdse_code_cost (code_cost.hip): T[v] = round(-log2(v / 2048) * 2^16) for v in 1 .. 2047, T[0] = T[2048] = 0 (a probability
 // never leaves [31, 2017]: neither end is ever looked up).  fp64 on the host; v / 2048 is exact.
 const uint32_t* code_cost_table_host() {

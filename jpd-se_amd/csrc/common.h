@@ -48,6 +48,15 @@ size_t vq_index_workspace_bytes(int M, int L, int S);
 int vq_index_encode_check(const jpdse_vq_index_encode_args* a);
 int vq_index_decode_check(const jpdse_vq_index_decode_args* a);
 
+// and for the jpdse_vq_plane_* calls (api.cpp; kernels: vq_plane.hip).  vq_plane_streams: S = ceil(h /
+// strip_rows) * G of a checked shape; the two sizes are 0 outside the limits 2 <= L <= 512, h, w, G, strip_rows >= 1,
+// S <= 65535, h * w * G and the capacity below 2^31.
+int vq_plane_streams(int h, int G, int strip_rows);
+long long vq_plane_capacity_bytes(int h, int w, int G, int L, int strip_rows);
+size_t vq_plane_workspace_bytes(int h, int w, int G, int L, int strip_rows);
+int vq_plane_encode_check(const jpdse_vq_plane_encode_args* a);
+int vq_plane_decode_check(const jpdse_vq_plane_decode_args* a);
+
 // the cost table of jpdse_code_cost_table (api.cpp): 2049 entries, built once on the host in fp64
 const uint32_t* code_cost_table_host();
 

@@ -11,11 +11,9 @@
 // access depends on the lane alone, whatever node each lane's walk has reached, and the 32 lanes of an LDS lane group sit
 // on 32 different banks.  One wave per block, 2^nb * 128 bytes of LDS: 64 KiB at L = 512, within the default limit.
 #include "range_coder.h"
+#include "vq_col.h"
 
 namespace jpdse {
-
-// the halfword of lane l inside a row of 64: lanes l and l + 32 share a dword and belong to different LDS lane groups
-__device__ __forceinline__ int vq_col(int lane) { return ((lane & 31) << 1) | (lane >> 5); }
 
 // the symbols of stream s and its slot (nb * count + 8 bytes) in the workspace: M = q S + r, the first r streams hold q + 1
 __device__ __forceinline__ int vq_stream_count(int s, int q, int r) { return q + (s < r ? 1 : 0); }

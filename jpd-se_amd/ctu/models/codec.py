@@ -11,7 +11,7 @@ import contextlib
 import torch
 
 from jpdse_hip import ops
-from ctu.utils import bitstream, entropy, vqstream
+from ctu.utils import bitstream, entropy, vqplane, vqstream
 
 
 class _Codec:
@@ -103,10 +103,23 @@ class BinaryCodec(_Codec):
     return H * W
 
 
+def _is_plane_blob(blob):
+  """A .jpdw blob by its magic; anything else is the .jpdv reader's to take or to refuse."""
+  return isinstance(blob, (bytes, bytearray)) and bytes(blob[:4]) == vqplane.MAGIC
+
+
 class VQIndexCodec(_Codec):
-  """The S2HVQ bottleneck's code: int64 [N, indices], coded as .jpdv blobs (ctu.utils.vqstream)."""
+  """The S2HVQ bottleneck's code: int64 [N, indices], coded as .jpdv blobs (ctu.utils.vqstream).  With
+  `context_coder` (--vq_context_coder) an image's blob is its .jpdw file (ctu.utils.vqplane) where that is the
+  smaller one; the receiver's half tells the two by their magic, whatever the flag."""
 
   RATE_OPTION = 'lambda_vq_rate'
+  context_coder = False
+
+  def _planes(self, H, W, groups):
+    """(h, w, G) of the index planes of an H x W image."""
+    n = self.netE.n_downsampling
+    return H >> n, W >> n, groups
 
   def geometry(self, x_dict, who):
     """(N, H, W, indices per image, n_center, channel groups)."""
@@ -124,11 +137,20 @@ class VQIndexCodec(_Codec):
     return geo
 
   def check_payloads(self, blobs, x_dict, who):
-    geo = N, H, W, code_len, L, _ = self.geometry(x_dict, who)
+    geo = N, H, W, code_len, L, groups = self.geometry(x_dict, who)
     if not isinstance(blobs, (list, tuple)) or len(blobs) != N:
       raise ValueError('%s: the blobs must be what get_coded returns: a list of %d .jpdv bytes objects, one per '
                        'label map' % (who, N))
     for j, b in enumerate(blobs):                 # every header on the host
+      if _is_plane_blob(b):
+        hb, wb, Gb, Lb, _, _ = vqplane.parse_blob(b, '%s: blob %d' % (who, j))
+        planes = self._planes(H, W, groups)
+        if Lb != L:
+          raise ValueError('%s: blob %d was coded for n_center %d, the code book has %d' % (who, j, Lb, L))
+        if (hb, wb, Gb) != planes:
+          raise ValueError('%s: blob %d holds planes of %d x %d x %d indices, a %d x %d label map carries %d x %d x %d'
+                           % ((who, j, hb, wb, Gb, H, W) + planes))
+        continue
       n, cl, Lb, _, _, _ = vqstream.parse_blob(b, '%s: blob %d' % (who, j))
       if Lb != L:
         raise ValueError('%s: blob %d was coded for n_center %d, the code book has %d' % (who, j, Lb, L))
@@ -155,14 +177,20 @@ class VQIndexCodec(_Codec):
 
   def features_of_payloads(self, blobs, geo, device, who):
     code_len = geo[3]
-    code = torch.cat([vqstream.read_indices(bytes(b), device()).view(1, code_len) for b in blobs], dim=0)
+    read = lambda b: vqplane.read_planes(b, device())[0] if _is_plane_blob(b) else vqstream.read_indices(b, device())
+    code = torch.cat([read(bytes(b)).view(1, code_len) for b in blobs], dim=0)
     return self.features_of_code(code, geo, device, who)
 
   def payloads(self, code, x_dict):
     """One .jpdv blob per image in (C / D) * 8 streams: the stream count is a multiple of the group count, so a stream holds
-    indices of one channel group only (write_indices clamps the count to the number of indices)."""
-    _, _, _, _, L, groups = self.geometry(x_dict, 'get_coded')
-    return [vqstream.write_indices(None, code[i:i + 1], L, n_streams=groups * 8) for i in range(code.shape[0])]
+    indices of one channel group only (write_indices clamps the count to the number of indices).  With the context coder both
+    files of every image are made and the smaller one is returned, the .jpdv one on a tie: never more bytes than without."""
+    _, H, W, _, L, groups = self.geometry(x_dict, 'get_coded')
+    blobs = [vqstream.write_indices(None, code[i:i + 1], L, n_streams=groups * 8) for i in range(code.shape[0])]
+    if self.context_coder:
+      planes = [vqplane.write_planes(None, code[i], self._planes(H, W, groups), L) for i in range(code.shape[0])]
+      blobs = [p if len(p) < len(b) else b for b, p in zip(blobs, planes)]
+    return blobs
 
   def file_rates(self, payloads, H, W):
     """(coded bpp, raw bpp), batch means: the .jpdv blobs, and the packed-index file (mode 0) of the same code: nb bits per

@@ -77,7 +77,8 @@ class Pix2PixHDModel(BaseModel):
     opt.pkl parses unchanged; flags of branches outside the accelerated path are accepted here and refused in
     __init__ when they would change the computation.  Extensions: --compute_dtype, --skip_unused_losses,
     --vgg19_state_dict, --vgg_random_init, --lambda_rate, --class_distortion_weights, --edge_distortion_weight,
-    --encoder_quantizer, --vq_n_center, --vq_center_size, --vq_sigma, --vq_soft_forward, --lambda_vq_rate."""
+    --encoder_quantizer, --vq_n_center, --vq_center_size, --vq_sigma, --vq_soft_forward, --lambda_vq_rate,
+    --vq_context_coder."""
     a = parser.add_argument
     a('--num_D', type=int, default=2)
     a('--n_layers_D', type=int, default=3)
@@ -181,6 +182,10 @@ class Pix2PixHDModel(BaseModel):
       help='extension (DESIGN.md 4.16): weight of the rate term of --encoder_quantizer s2hvq in the generator / encoder loss '
            '-- the entropy of the soft assignment\'s histogram per channel group (the model the .jpdv coder adapts to), in '
            'bits per pixel of the local batch; 0 (default): no rate term, the step is what it was')
+    a('--vq_context_coder', action='store_true',
+      help='extension (DESIGN.md 4.19): with --encoder_quantizer s2hvq, get_coded also codes each image\'s index planes with the '
+           'spatial-context coder (.jpdw) and keeps whichever file is smaller, the .jpdv one on a tie; decode_coded reads '
+           'either file with or without this flag.  Default: .jpdv files only, every run is what it was')
     a('--vgg_random_init', action='store_true',
       help='extension: explicitly accept a seeded random-weight VGG19 for the VGG loss (tests, benchmarks); without '
            'this flag training with the VGG loss and no --vgg19_state_dict is refused')
@@ -231,6 +236,11 @@ class Pix2PixHDModel(BaseModel):
     if self.lambda_vq_rate > 0.0 and (g('encoder_quantizer', 'binarizer') != 's2hvq' or g('zero_vis')):
       raise ValueError('lambda_vq_rate > 0 is the rate term of the vector-quantizer bottleneck: it needs --encoder_quantizer '
                        's2hvq and an encoder that runs (no --zero_vis)')
+    # context coder of the vector-quantizer bottleneck's files
+    self.vq_context_coder = bool(g('vq_context_coder'))
+    if self.vq_context_coder and g('encoder_quantizer', 'binarizer') != 's2hvq':
+      raise ValueError('--vq_context_coder codes the index planes of the vector-quantizer bottleneck: it needs '
+                       '--encoder_quantizer s2hvq')
     # vector-quantizer bottleneck: refused combinations before any network (hence any device allocation) exists
     if g('encoder_quantizer', 'binarizer') not in ('binarizer', 's2hvq'):
       raise ValueError('encoder_quantizer must be binarizer or s2hvq, got %r' % (g('encoder_quantizer'),))
@@ -309,6 +319,8 @@ class Pix2PixHDModel(BaseModel):
     if self.netE is not None and self.netE.quantizer is not None:
       self.codec = CODECS[self.netE.quantizer](self.netE, self.cdtype)
       self.rate_weight = getattr(self, self.codec.RATE_OPTION)
+      if self.vq_context_coder:
+        self.codec.context_coder = True
     # binarizer noise: Philox key = the run's seed, counter = (element, image index in the global batch,
     # number of training forwards so far)
     self.codec_seed = int(g('seed', None) or 0)
@@ -681,7 +693,8 @@ class Pix2PixHDModel(BaseModel):
     range-coded streams (ops.code_entropy_encode).  Lossless: decode_coded(get_coded(x), x) equals
     decode(get_code(x, packed=True), x) bit for bit.
     With --encoder_quantizer s2hvq: a list of N .jpdv blobs (ctu.utils.vqstream), one per image, of that image's
-    get_vq_code row."""
+    get_vq_code row; with --vq_context_coder an item is the image's .jpdw blob (ctu.utils.vqplane) where
+    that is the smaller of the two."""
     codec = self.codec or self._binary_codec()
     with torch.no_grad():
       return codec.payloads(self._eval_code(codec, x_dict), x_dict)
@@ -691,7 +704,9 @@ class Pix2PixHDModel(BaseModel):
     work, without an encoder or a binarizer, for a label map that is no multiple of the encoder's down-sampling factor, a
     wrong payload count, an item that is not bytes, and a payload whose length table does not add up.
     With --encoder_quantizer s2hvq the items are the .jpdv blobs of get_coded; each header's n * code_len and L must fit the
-    label map and the code book (checked on the host first); decode_coded(get_coded(x), x) equals get_img(x) bit for bit."""
+    label map and the code book (checked on the host first); decode_coded(get_coded(x), x) equals get_img(x) bit for bit.
+    A .jpdw blob (--vq_context_coder at the sender; told by its magic, no flag needed here) is taken in any item: its h, w, G
+    and L must fit in the same way."""
     codec = self.codec or self._binary_codec()
     geo = codec.check_payloads(payloads, x_dict, 'decode_coded')
     with torch.no_grad():

@@ -148,6 +148,19 @@ class VqIndexDecodeArgs(ctypes.Structure):
               ('stream', ctypes.c_void_p)]
 
 
+# the jpdse_vq_plane_* calls (vq_plane.hip)
+class VqPlaneEncodeArgs(ctypes.Structure):
+  _fields_ = [(n, ctypes.c_int32) for n in ('h', 'w', 'G', 'L', 'strip_rows')] + \
+             [('index', ctypes.c_void_p), ('out', ctypes.c_void_p), ('out_bytes', ctypes.c_int64), ('size', ctypes.c_void_p),
+              ('status', ctypes.c_void_p), ('ws', ctypes.c_void_p), ('ws_bytes', ctypes.c_size_t), ('stream', ctypes.c_void_p)]
+
+
+class VqPlaneDecodeArgs(ctypes.Structure):
+  _fields_ = [(n, ctypes.c_int32) for n in ('h', 'w', 'G', 'L', 'strip_rows')] + \
+             [('in_', ctypes.c_void_p), ('in_bytes', ctypes.c_int64), ('index', ctypes.c_void_p), ('status', ctypes.c_void_p),
+              ('stream', ctypes.c_void_p)]
+
+
 # the jpdse_vq_quantize_* calls (vq_bottleneck.hip)
 class VqQuantizeFwdArgs(ctypes.Structure):
   _fields_ = [(n, ctypes.c_int32) for n in ('dtype', 'M', 'D', 'L')] + \
@@ -296,6 +309,10 @@ SIGNATURES = {
     'jpdse_vq_index_workspace_size': (_SZ, [_I32, _I32, _I32]),
     'jpdse_vq_index_encode': (_I32, [ctypes.POINTER(VqIndexEncodeArgs)]),
     'jpdse_vq_index_decode': (_I32, [ctypes.POINTER(VqIndexDecodeArgs)]),
+    'jpdse_vq_plane_capacity': (_SZ, [_I32, _I32, _I32, _I32, _I32]),
+    'jpdse_vq_plane_workspace_size': (_SZ, [_I32, _I32, _I32, _I32, _I32]),
+    'jpdse_vq_plane_encode': (_I32, [ctypes.POINTER(VqPlaneEncodeArgs)]),
+    'jpdse_vq_plane_decode': (_I32, [ctypes.POINTER(VqPlaneDecodeArgs)]),
     'jpdse_vq_quantize_workspace_size': (_SZ, [_I32, _I32, _I32]),
     'jpdse_vq_quantize_fwd': (_I32, [ctypes.POINTER(VqQuantizeFwdArgs)]),
     'jpdse_vq_quantize_bwd': (_I32, [ctypes.POINTER(VqQuantizeBwdArgs)]),

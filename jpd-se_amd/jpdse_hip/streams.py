@@ -1,4 +1,4 @@
-"""The host half of the three device coders (entropy.hip, semantics.hip, vq_coder.hip): the layout of their
+"""The host half of the device coders (entropy.hip, semantics.hip, vq_coder.hip: DESIGN.md 4.18; vq_plane.hip: 4.19): the layout of their
 buffers, the payload rules (length tables, plane entries, index limits), the staging of payload rows for one upload, what is
 refused before the library is touched, and the reading of status words.  `jpdse_hip.ops` re-exports every public name.
 
@@ -10,7 +10,7 @@ import struct
 
 import torch
 
-from . import lib, check, JpdseError, VqIndexEncodeArgs, VqIndexDecodeArgs
+from . import lib, check, JpdseError, VqIndexEncodeArgs, VqIndexDecodeArgs, VqPlaneEncodeArgs, VqPlaneDecodeArgs
 
 
 # ---- shared by the three coders ----------------------------------------------------------------------------------------------
@@ -335,6 +335,87 @@ def vq_index_decode(payload, M, L, S, device=None):
     check(lib().jpdse_vq_index_decode(ctypes.byref(args)), 'vq_index_decode')
   if int(status.item()) & 2:
     raise ValueError('vq_index_decode: a decoded value outside [0, %d): not a coded stream of this alphabet' % L)
+  return index
+
+
+# ---- soft-to-hard vector quantizer: coded index planes (vq_plane.hip; format: DESIGN.md 4.19) ---------------------------------
+def vq_plane_streams(h, G, strip_rows):
+  """S = ceil(h / strip_rows) * G: one stream per strip of every group's plane."""
+  return (int(h) + int(strip_rows) - 1) // int(strip_rows) * int(G)
+
+
+def vq_plane_capacity(h, w, G, L, strip_rows):
+  """The most a payload can take: (nb + 2) bytes per symbol and 12 per stream (its table entry and its slot's 8)."""
+  return (vq_index_bits(L) + 2) * h * w * G + 12 * vq_plane_streams(h, G, strip_rows)
+
+
+def vq_plane_shape(who, h, w, G, L, strip_rows):
+  """The checked (h, w, G, L, strip_rows, S) of a call or a header; ValueError outside the coder's limits.  Host only."""
+  h, w, G, L, strip_rows = int(h), int(w), int(G), int(L), int(strip_rows)
+  if not 2 <= L <= VQ_MAX_L:
+    raise ValueError('%s: L = %d, the coder takes 2 .. %d' % (who, L, VQ_MAX_L))
+  if min(h, w, G) < 1:
+    raise ValueError('%s: empty plane shape h = %d, w = %d, G = %d (each at least 1)' % (who, h, w, G))
+  if strip_rows < 1:
+    raise ValueError('%s: strip_rows %d is below 1' % (who, strip_rows))
+  S = vq_plane_streams(h, G, strip_rows)
+  if S > VQ_INDEX_MAX_S:
+    raise ValueError('%s: %d strips of %d groups are S = %d streams, the coder takes at most %d' % (who, S // G, G, S, VQ_INDEX_MAX_S))
+  if vq_plane_capacity(h, w, G, L, strip_rows) >= 1 << 31:
+    raise ValueError('%s: %d x %d x %d indices of %d bits are beyond the coder\'s limits (capacity below 2^31 bytes)'
+                     % (who, h, w, G, vq_index_bits(L)))
+  return h, w, G, L, strip_rows, S
+
+
+def vq_plane_encode(index, h, w, G, L, strip_rows=8):
+  """The context-coded payload of one image's device int32 [h * w * G] indices (pixel by pixel, groups ascending inside a
+  pixel), all in [0, L), in ceil(h / strip_rows) * G streams (jpdse_vq_plane_encode): `bytes` holding the little-endian uint32
+  stream lengths and the streams.  One device buffer -- the size, the status word, then the payload at its capacity -- is
+  copied to the host once.  ValueError for an index outside [0, L) (status bit 1), JpdseError if a stream outgrew its derived
+  capacity (bit 0)."""
+  assert index.dim() == 1 and index.is_cuda, (tuple(index.shape), index.device)
+  h, w, G, L, strip_rows, S = vq_plane_shape('vq_plane_encode', h, w, G, L, strip_rows)
+  M, dev = h * w * G, index.device
+  _vq_index(index, M, dev)
+  lb = lib()
+  cap, n_ws = lb.jpdse_vq_plane_capacity(h, w, G, L, strip_rows), lb.jpdse_vq_plane_workspace_size(h, w, G, L, strip_rows)
+  assert cap == vq_plane_capacity(h, w, G, L, strip_rows) and n_ws > 0, (cap, n_ws)
+  buf, meta, head = _coder_buffer(2, 1, cap, dev)
+  ws = workspace(n_ws, dev)
+  with torch.cuda.device(dev):
+    args = VqPlaneEncodeArgs(h, w, G, L, strip_rows, index.data_ptr(), buf[head:].data_ptr(), cap, meta[0:].data_ptr(),
+                             meta[1:].data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+    check(lb.jpdse_vq_plane_encode(ctypes.byref(args)), 'vq_plane_encode')
+  host = buf.cpu().numpy()
+  size, status = (int(v) for v in host[:8].view('<i4'))
+  if status & 2:
+    raise ValueError('vq_plane_encode: an index outside [0, %d)' % L)
+  if status & 1:
+    raise JpdseError('vq_plane_encode: a stream outgrew its slot of (nb + 2) * count + 8 bytes (status %d)' % status)
+  return host[head:head + size].tobytes()
+
+
+def vq_plane_decode(payload, h, w, G, L, strip_rows=8, device=None):
+  """The inverse (jpdse_vq_plane_decode): a payload as vq_plane_encode returns it -> the int32 [h * w * G] indices on `device`
+  (default: the current device).  ValueError before any library call for a payload that is not `bytes` or whose table of S
+  lengths does not add up to the bytes that follow it; ValueError after the decode when a decoded value was >= L (status
+  bit 1: the bytes are not a coded stream of this alphabet)."""
+  h, w, G, L, strip_rows, S = vq_plane_shape('vq_plane_decode', h, w, G, L, strip_rows)
+  check_payload(payload, S, 'vq_plane_decode', 'vq_plane_decode: the payload is %s, not bytes')
+  if len(payload) >= 1 << 31:
+    raise ValueError('vq_plane_decode: a payload of %d bytes' % len(payload))
+  dev = torch.device(default_device(device))
+  if dev.type != 'cuda':
+    raise JpdseError('vq_plane_decode: device %s: the JPD-SE HIP path has no CPU fallback' % (dev,))
+  src = torch.frombuffer(bytearray(payload), dtype=torch.uint8).to(dev)
+  index = torch.empty(h * w * G, dtype=torch.int32, device=dev)
+  status = torch.zeros(1, dtype=torch.int32, device=dev)
+  with torch.cuda.device(dev):
+    args = VqPlaneDecodeArgs(h, w, G, L, strip_rows, src.data_ptr(), len(payload), index.data_ptr(), status.data_ptr(),
+                             torch.cuda.current_stream().cuda_stream)
+    check(lib().jpdse_vq_plane_decode(ctypes.byref(args)), 'vq_plane_decode')
+  if int(status.item()) & 2:
+    raise ValueError('vq_plane_decode: a decoded value outside [0, %d): not a coded stream of this alphabet' % L)
   return index
 
 

@@ -124,6 +124,9 @@ def main():
   ap.add_argument('--vq_n_center', type=int, default=64, help='the training flag of the same name')
   ap.add_argument('--vq_center_size', type=int, default=8, help='the training flag of the same name')
   ap.add_argument('--vq_sigma', type=float, default=10.0, help='the training flag of the same name')
+  ap.add_argument('--vq_context_coder', action='store_true',
+                  help='with --codec --encoder_quantizer s2hvq: the training flag of the same name (DESIGN.md 4.19).  Also prints '
+                       'the bpp of both forms of every code, .jpdv and .jpdw, and how many images took which container')
   ap.add_argument('--checkpoints_dir', default=None, help='load net_G.pth (and net_E.pth) from here')
   ap.add_argument('--data', default=None, help='directory of pre-decoded *.pt batches instead of synthetic ones')
   ap.add_argument('--per-class', action='store_true', help='also print L1 / MSE / PSNR per semantic class')
@@ -150,6 +153,8 @@ def main():
   if args.rate_map and not args.codec:
     ap.error('--rate-map needs --codec')
   vq = args.codec and args.encoder_quantizer == 's2hvq'
+  if args.vq_context_coder and not vq:
+    ap.error('--vq_context_coder needs --codec --encoder_quantizer s2hvq')
   if vq and (args.roundtrip or args.rate_map):
     ap.error('--roundtrip / --rate-map store and walk the binarizer\'s code: not available with --encoder_quantizer s2hvq '
              '(trainer.get_coded / decode_coded are its files)')
@@ -168,7 +173,7 @@ def main():
   if args.codec:
     kw.update(no_feat_encoding=False, no_encoder_binarization=False, feat_num=3, nef=args.ngf, n_downsample_E=4,
               encoder_binarizer_out_channels=128, encoder_quantizer=args.encoder_quantizer, vq_n_center=args.vq_n_center,
-              vq_center_size=args.vq_center_size, vq_sigma=args.vq_sigma)
+              vq_center_size=args.vq_center_size, vq_sigma=args.vq_sigma, vq_context_coder=args.vq_context_coder)
   if args.checkpoints_dir:
     kw.update(is_train=False, load_model=True, checkpoints_dir=args.checkpoints_dir)
   opt = default_opt(**kw)
@@ -180,6 +185,7 @@ def main():
   by_image = dict.fromkeys(keys + ('shannon', 'actual', 'context', 'file', 'coded', 'semantics', 'total', 'weighted', 'model'), 0.0)
   weighted = trainer.model.sem_weights is not None      # class / edge weights are set
   images, n_batches, worst_diff = 0, 0, 0.0
+  containers = {'jpdw': 0, 'jpdv': 0}                   # with --vq_context_coder: images whose kept blob is of that kind
   class_sums = None                  # int64 [1, n_classes + 1, 3]: the raw class tables of every image so far, added up
   class_bits = None                  # float64 [n_classes + 1]: the bits of the code attributed to each class so far (with --codec)
   start = time.time()
@@ -219,6 +225,25 @@ def main():
       by_image['actual'] += packed_bpp * b
       line += ', vq code: coded file bpp {:.4f} (packed indices {:.4f}), max |decoded - get_img| {:.3e}'.format(coded_bpp, packed_bpp,
                                                                                                         diff)
+      if args.vq_context_coder:
+        # both forms of every code: the .jpdv blobs of a flag-off run, the .jpdw blobs whether or not they
+        # are the smaller ones, and which container get_coded kept
+        from ctu.utils import vqplane
+        codec, pixels = trainer.model.codec, int(x_dict['image'].shape[-2]) * int(x_dict['image'].shape[-1])
+        kept = trainer.get_coded(x_dict)
+        codec.context_coder = False
+        try:
+          jpdv_bpp, _ = trainer.get_coded_rate(x_dict)
+        finally:
+          codec.context_coder = True
+        code = trainer.get_vq_code(x_dict)
+        _, ih, iw, _, n_center, groups = codec.geometry(x_dict, 'eval_rd')
+        planes = [vqplane.write_planes(None, code[j], codec._planes(ih, iw, groups), n_center) for j in range(b)]
+        jpdw_bpp = sum(8.0 * len(p) / pixels for p in planes) / b
+        n_jpdw = sum(1 for blob in kept if blob[:4] == vqplane.MAGIC)
+        containers['jpdw'] += n_jpdw
+        containers['jpdv'] += b - n_jpdw
+        line += ', .jpdv / .jpdw file bpp {:.4f}/{:.4f}, kept {} .jpdw and {} .jpdv'.format(jpdv_bpp, jpdw_bpp, n_jpdw, b - n_jpdw)
       # the per-group zero-order entropy of the same code over the batch: an estimate, not a size, and on
       # either side of the coded figure (the coder adapts per image and pays headers and flushes)
       line += ', per-group entropy bpp {:.4f}'.format(trainer.get_vq_rate(x_dict))
@@ -295,6 +320,9 @@ def main():
     return line
   print('\n' + summary('test set avg recon loss', by_batch, n_batches))
   print(summary('per-image avg recon loss', by_image, images) + '\n')
+  if args.vq_context_coder:
+    print('context coder: {} of {} images kept the .jpdw container, {} the .jpdv one\n'.format(containers['jpdw'], images,
+                                                                                             containers['jpdv']))
   if args.roundtrip:
     print('distortion above: images decoded from the files under %s; largest |decoded - get_img| over the test set %.3e\n'
           % (args.roundtrip, worst_diff))
