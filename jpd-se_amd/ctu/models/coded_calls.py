@@ -1,0 +1,289 @@
+"""The coded-stream and receiver calls of Pix2PixHDModel (extensions: the reference stops at get_code / get_eval_rate): the
+encoder's code in its forms, its rate figures, the entropy-coded files, the coded label and instance maps, and the receiver
+that reconstructs an image from them.  DESIGN.md 4.4, 4.8 - 4.10, 4.12, 4.15 - 4.17 and 4.19."""
+import torch
+
+from jpdse_hip import F32, ops
+from ctu.utils import semantics as semantics_file
+from ctu.models.codec import VQIndexCodec
+
+
+class CodedCalls(object):
+  """Mixin of Pix2PixHDModel.  What it expects from the model -- six hooks:
+    _device()                              the torch device, or the refusal of a run without one
+    _semantics(x_dict)                     the device label and instance maps as the input builders read them
+    _encoder_eval(fn)                      fn() with netE in eval mode
+    preprocess(x_dict, build_base)         the NHWC device activations of a batch
+    _g_input_from_vis(vis, base, N, H, W)  the generator input [semantics | vis] under --zero_sem
+    netG                                   the generator
+  and the attributes of its constructor: codec (ctu.models.codec, None without a bottleneck), netE, opt (normalize_mean /
+  normalize_std), cdtype, n_onehot, label_nc, feat_nc, zero_vis, zero_sem, no_instance.  A bare model (tests,
+  scripts/make_codec_refusals.py) that sets the hooks on the instance short-circuits them here too."""
+
+  @staticmethod
+  def _pixels(x_dict):
+    """H * W of the batch's images: what a rate in bits per pixel is divided by."""
+    return int(x_dict['image'].shape[-2]) * int(x_dict['image'].shape[-1])
+
+  def _binary_codec(self, who='binary codes'):
+    """The binarizer's codec, or the refusal.  The calls that serve either form take `self.codec or self._binary_codec()`:
+    without a bottleneck they refuse as the binary calls do."""
+    if isinstance(self.codec, VQIndexCodec):
+      raise ValueError('%s: a call of the one-bit binarizer\'s code, not available with --encoder_quantizer s2hvq (its code: '
+                       'get_vq_code / get_coded / get_coded_rate)' % who)
+    if self.codec is None:
+      raise ValueError('binary codes need the learned codec with encoder binarization '
+                       '(--no_feat_encoding and --no_encoder_binarization must both be off)')
+    return self.codec
+
+  def _vq_codec(self, who):
+    """The vector quantizer's codec, or the refusal."""
+    if not isinstance(self.codec, VQIndexCodec):
+      raise ValueError('%s: the vector-quantised code needs --encoder_quantizer s2hvq' % who)
+    return self.codec
+
+  def _eval_code(self, codec, x_dict):
+    """The encoder's eval-mode code of x_dict (the decoded frame with --use_compressed) in the codec's form."""
+    pre = self.preprocess(x_dict, build_base=False)
+    return self._encoder_eval(lambda: codec.code(pre['src']))
+
+  def _code_act(self, x_dict, who='binary codes'):
+    """The encoder's eval-mode bitstream of x_dict as an NHWC Act."""
+    return self._eval_code(self._binary_codec(who), x_dict)
+
+  def get_code(self, x_dict, packed=False):
+    """[image_code] (model.py:494-505, 557-563): (b + 1) / 2 as fp32 [N, bits] in NCHW flatten order -- or, packed=True
+    (extension), the bitstream itself, uint8 [N, ceil(bits / 8)] MSB first."""
+    with torch.no_grad():
+      return [ops.code_export(self._code_act(x_dict, 'get_code'), packed)]
+
+  def get_context_rate(self, x_dict):
+    """The hard-mode rate term of the eval-mode code, batch mean in bits per pixel, a Python float: the code's
+    conditional entropy under the static, Laplace-smoothed form of the 4.8 coder's context model, counted on the code itself.
+    An estimate that stays below the coded size (no flush, no adaptation cost) -- not a size; get_coded_rate measures files."""
+    with torch.no_grad():
+      b = self._code_act(x_dict, 'get_context_rate')
+      pixels = self._pixels(x_dict)
+      value, _, _, _ = ops.code_rate_loss(b, None, pixels, want_grad=False)
+      return float(value.item())
+
+  def get_eval_rate(self, x_dict):
+    """(Shannon bpp, raw bpp) averaged over the batch, with the reference's formula and types (model.py:468-491): per image
+    p = mean((b + 1) / 2), entropy -p ln p - (1 - p) ln(1 - p) -- in NATS, as the reference computes it (torch.log) --
+    times bits / pixels; nan when p is 0 or 1.  First value a 0-dim float tensor, second a Python float.  p comes from the
+    integer per-image counts of jpdse_code_stats (exact: torch.mean's fp32 sum of halves is exact below 2^24 bits)."""
+    with torch.no_grad():
+      b = self._code_act(x_dict, 'get_eval_rate')
+      counts = ops.code_stats(b).to(torch.float64)
+      bits = b.C * b.H * b.W
+      pixels = self._pixels(x_dict)
+      p_all = ((2.0 * counts[:, 0] + counts[:, 1]) / (2.0 * bits)).to(torch.float32)
+      shannon, actual = 0., 0.
+      for j in range(b.N):
+        p = p_all[j]
+        ent = - p * torch.log(p) - (1 - p) * torch.log(1 - p)
+        shannon += ent * bits / pixels
+        actual += bits / pixels
+      return shannon / b.N, actual / b.N
+
+  # ---- the vector-quantised code (extension) ------------------------------------------------------------------
+  def get_vq_code(self, x_dict):
+    """The eval-mode code of the vector-quantizer bottleneck: int64 [N, h * w * C / D] on the device, per image the index of
+    the nearest centre of every group of D channels, pixel by pixel, groups ascending inside a pixel."""
+    codec = self._vq_codec('get_vq_code')
+    with torch.no_grad():
+      return self._eval_code(codec, x_dict)
+
+  def get_vq_rate(self, x_dict):
+    """The hard-mode rate term of the eval-mode code in bits per pixel of the batch, a Python float: the
+    zero-order entropy of get_vq_code(x_dict) per channel group, histograms taken over the batch.  An estimate, not a size:
+    get_coded_rate measures the .jpdv files, whose adaptive coder may land on either side of it."""
+    self._vq_codec('get_vq_rate')
+    with torch.no_grad():
+      pre = self.preprocess(x_dict, build_base=False)
+      src = pre['src']
+      value = self._encoder_eval(lambda: self.netE.vq_rate(src, src.N * src.H * src.W))
+      return float(value.item())
+
+  def _decode_act(self, code, x_dict):
+    """decode() up to the generator's NHWC output; also returns the device label map."""
+    codec = self.codec or self._binary_codec()
+    geo = codec.check_code(code, x_dict, 'decode')
+    return self._generate_from_code(codec.features_of_code(code, geo, self._device, 'decode'), x_dict, *geo[:3])
+
+  def _generate_from_code(self, features, x_dict, N, H, W):
+    """The receiver's device work, shared by decode and decode_coded: features() gives the encoder's output from the code."""
+    label, inst = self._semantics(x_dict)
+    vis = None if self.zero_vis else features()      # --zero_vis: nothing visual reaches the generator, the code is not read
+    base = None if self.zero_sem else ops.onehot_edge(label, inst, self.n_onehot, self.label_nc + self.feat_nc, self.cdtype)
+    fake, _ = self.netG.fwd(self._g_input_from_vis(vis, base, N, H, W))
+    return fake, label
+
+  def decode(self, code, x_dict):
+    """The receiver (extension; the reference never decodes a stored code): the reconstructed image, NCHW as get_img returns
+    it, from `code` -- what get_code returned, float32 [N, bits] or (packed) uint8 [N, ceil(bits / 8)], on the CPU or the
+    device -- and the semantics x_dict['label'], x_dict['instance'].  Neither 'image' nor 'compressed_img' is read.  The
+    code goes through ops.code_import and the encoder's second half (Encoder.decode_code); the generator input is then
+    built as get_img builds it from the features, --zero_sem / --zero_ins / --zero_vis included (--zero_vis ignores the code
+    as get_img ignores the image).
+    Zero rule: decode(get_code(x)) equals get_img(x) bit for bit when the eval code has no exact zero (ops.code_stats column
+    1).  Where the encoder's tanh is exactly 0, get_img feeds sign(0) = 0 forward but the stored bit is 0, so the decoder
+    sees -1 there: the stored code, not the tensor get_img used, is what a receiver reconstructs from.
+    ValueError without an encoder or a binarizer, and for a code whose size does not fit the label map (before any device
+    work).
+    With --encoder_quantizer s2hvq the code is what get_vq_code returned, int64 [N, indices]: decode(get_vq_code(x), x)
+    equals get_img(x) bit for bit, with no zero rule -- both sides see code_book[index]."""
+    with torch.no_grad():
+      fake, _ = self._decode_act(code, x_dict)
+      return ops.nhwc_to_nchw(fake)
+
+  # ---- entropy-coded bitstream (extension) ------------------------------------------------------------------
+  def get_coded(self, x_dict):
+    """The entropy-coded form of get_code(x_dict, packed=True): a list of N `bytes`, per image the C stream lengths and the C
+    range-coded streams (ops.code_entropy_encode).  Lossless: decode_coded(get_coded(x), x) equals
+    decode(get_code(x, packed=True), x) bit for bit.
+    With --encoder_quantizer s2hvq: a list of N .jpdv blobs (ctu.utils.vqstream), one per image, of that image's
+    get_vq_code row; with --vq_context_coder an item is the image's .jpdw blob (ctu.utils.vqplane) where
+    that is the smaller of the two."""
+    codec = self.codec or self._binary_codec()
+    with torch.no_grad():
+      return codec.payloads(self._eval_code(codec, x_dict), x_dict)
+
+  def decode_coded(self, payloads, x_dict):
+    """decode() from what get_coded returned: a list of one `bytes` payload per label map.  ValueError, before any device
+    work, without an encoder or a binarizer, for a label map that is no multiple of the encoder's down-sampling factor, a
+    wrong payload count, an item that is not bytes, and a payload whose length table does not add up.
+    With --encoder_quantizer s2hvq the items are the .jpdv blobs of get_coded; each header's n * code_len and L must fit the
+    label map and the code book (checked on the host first); decode_coded(get_coded(x), x) equals get_img(x) bit for bit.
+    A .jpdw blob (--vq_context_coder at the sender; told by its magic, no flag needed here) is taken in any item: its h, w, G
+    and L must fit in the same way."""
+    codec = self.codec or self._binary_codec()
+    geo = codec.check_payloads(payloads, x_dict, 'decode_coded')
+    with torch.no_grad():
+      features = codec.features_of_payloads(payloads, geo, self._device, 'decode_coded')
+      fake, _ = self._generate_from_code(features, x_dict, *geo[:3])
+      return ops.nhwc_to_nchw(fake)
+
+  def get_coded_rate(self, x_dict):
+    """(coded bpp, raw bpp) averaged over the batch, two Python floats: 8 * file bytes / pixels of the .jpda file
+    (ctu.utils.entropy: 24-byte header, and the raw payload where coding does not pay) and of the .jpdc file
+    (ctu.utils.bitstream: 20-byte header) of each image.  Sizes of real files, not estimates; get_eval_rate is the
+    reference's Shannon figure.  With --encoder_quantizer s2hvq: the .jpdv blobs, and the packed-index file of the same code."""
+    payloads = self.get_coded(x_dict)
+    return self.codec.file_rates(payloads, int(x_dict['image'].shape[-2]), int(x_dict['image'].shape[-1]))
+
+  # ---- where the bits go (extension) ------------------------------------------------------------------------
+  def get_rate_map(self, x_dict):
+    """The code length of the eval-mode code (the one get_code / get_coded produce) under the 4.8 coder's own adaptive model,
+    symbol by symbol (ops.code_cost): dict of float64 CPU tensors, `map` [N, h, w] bits per code cell, `per_channel` [N, C]
+    bits, `bits` [N] and `bpp` [N] = bits / (H * W).  map and per_channel each sum to bits.  The model's ideal length, not a
+    file size: get_coded_rate measures files, and stays within the bound of DESIGN.md 4.12 of this figure."""
+    with torch.no_grad():
+      r = ops.code_cost(self._code_act(x_dict, 'get_rate_map'))
+      cell, channel = r['cell'].cpu(), r['channel'].cpu()
+    pixels = self._pixels(x_dict)
+    unit = float(ops.CODE_COST_UNIT)
+    bits = cell.sum(dim=(1, 2)).to(torch.float64) / unit            # integer sums first: exact
+    return dict(map=cell.to(torch.float64) / unit, per_channel=channel.to(torch.float64) / unit, bits=bits, bpp=bits / pixels)
+
+  def get_class_rates(self, x_dict):
+    """The same code length attributed to the semantic classes of the pixels each code cell covers -- a cell's bits are
+    shared evenly among its s*s pixels, s the encoder's down-sampling factor.  Rows: the n_onehot classes of
+    get_eval_metrics(per_class=True) in its order, then one row for the pixels without a class.  dict(pixels int64, bits, bpp,
+    share float64, each [n_classes + 1], over the batch: bits summed, bpp = bits of the class / pixels of the class (nan for
+    an absent class), share = the class's fraction of all bits; per_image: the same four keys [N, n_classes + 1], share being
+    the fraction of that image's bits)."""
+    with torch.no_grad():
+      b = self._code_act(x_dict, 'get_class_rates')
+      label, _ = self._semantics(x_dict)
+      r = ops.code_cost(b, label, self.n_onehot)
+      units, pix = r['class_units'].cpu(), r['class_pixels'].cpu()
+    s = int(label.shape[-1]) // b.W
+    den = float(ops.CODE_COST_UNIT) * s * s
+
+    def figures(u, p):                  # integer tensors [..., rows]
+      bits = u.to(torch.float64) / den
+      seen = p > 0
+      nan = torch.full_like(bits, float('nan'))
+      bpp = torch.where(seen, bits / torch.where(seen, p, torch.ones_like(p)).to(torch.float64), nan)
+      total = u.sum(dim=-1, keepdim=True).to(torch.float64) / den
+      return dict(pixels=p.clone(), bits=bits, bpp=bpp, share=bits / total)
+
+    out = figures(units.sum(dim=0), pix.sum(dim=0))
+    out['per_image'] = figures(units, pix)
+    return out
+
+  # ---- coded label and instance maps (extension) --------------------------------------------------------------
+  def _label_set(self):
+    """The label values a decoded map may hold: what the one-hot lanes of the input builder cover, 256 at the most."""
+    return min(self.n_onehot, 256)
+
+  def get_coded_semantics(self, x_dict, strip_rows=8):
+    """The label and instance maps of x_dict as the receiver needs them, coded losslessly on the device
+    (ops.semantics_encode): a list of N `bytes`, each the body of a .jpds file (ctu.utils.semantics).  The maps are coded as
+    the dataset gives them -- --zero_ins / --zero_sem act where decode builds the generator input, not here; with
+    --no_instance there is no instance plane.  ValueError for a label that is not an integer in [0, 255] or an instance id
+    outside [0, 2^31)."""
+    dev = self._device()
+    label = x_dict['label'].to(dev, dtype=torch.float32, non_blocking=True).contiguous()
+    inst = None
+    if not self.no_instance:
+      inst = x_dict['instance'].to(dev, dtype=torch.int64, non_blocking=True).contiguous()
+    if label.dim() != 4 or label.shape[1] != 1:
+      raise ValueError('get_coded_semantics: the label map is [N, 1, H, W], got %s' % (tuple(label.shape),))
+    H, W = int(label.shape[-2]), int(label.shape[-1])
+    with torch.no_grad():
+      items = ops.semantics_encode(label, inst, strip_rows)
+    return [semantics_file.pack(H, W, strip_rows, item) for item in items]
+
+  def decode_semantics(self, blobs):
+    """{'label': float32 [N, 1, H, W], 'instance': int64 [N, 1, H, W]} on the device from what get_coded_semantics returned
+    (or ctu.utils.semantics.read read): an x_dict for decode / decode_coded.  Without an instance plane the instance map is
+    zeros.  ValueError, before any device work, for anything ctu.utils.semantics.unpack refuses and for blobs of different
+    shapes; ValueError for a map that holds a label outside the label set, before the input builder sees it."""
+    if not isinstance(blobs, (list, tuple)) or len(blobs) == 0:
+      raise ValueError('decode_semantics: expected a list of .jpds bodies, one per image')
+    parsed = [semantics_file.unpack(b, 'decode_semantics: blob %d' % j) for j, b in enumerate(blobs)]
+    H, W, strip_rows, mask, _ = parsed[0]
+    for j, q in enumerate(parsed):
+      if q[:4] != (H, W, strip_rows, mask):
+        raise ValueError('decode_semantics: blob %d is %d x %d, strips of %d rows, plane mask %d; blob 0 is %d x %d, %d, %d'
+                         % ((j,) + q[:4] + (H, W, strip_rows, mask)))
+    want = 1 if self.no_instance else 3
+    if mask != want:
+      raise ValueError('decode_semantics: the blobs have plane mask %d, this model reads %d (%s)'
+                       % (mask, want, 'label only: --no_instance' if want == 1 else 'label and instance'))
+    with torch.no_grad():
+      label, inst = ops.semantics_decode([q[4] for q in parsed], H, W, strip_rows, self._label_set(), self._device())
+    return {'label': label, 'instance': inst}
+
+  def decode_from_files(self, coded_payloads, semantics_blobs):
+    """The receiver from bytes alone: decode_coded(coded_payloads, decode_semantics(semantics_blobs))."""
+    return self.decode_coded(coded_payloads, self.decode_semantics(semantics_blobs))
+
+  def get_total_rate(self, x_dict, strip_rows=8):
+    """(code bpp, semantics bpp, total bpp), Python floats, batch means: 8 * file bytes / pixels of the .jpda file of the
+    code (get_coded_rate's first figure) and of the .jpds file of the maps, headers and raw fallbacks included -- the rate
+    of everything decode_from_files needs."""
+    code_bpp, _ = self.get_coded_rate(x_dict)
+    blobs = self.get_coded_semantics(x_dict, strip_rows)
+    H, W = int(x_dict['label'].shape[-2]), int(x_dict['label'].shape[-1])
+    sem_bpp = sum(8.0 * len(b) / (H * W) for b in blobs) / len(blobs)
+    return code_bpp, sem_bpp, code_bpp + sem_bpp
+
+  def _eval_metrics_of(self, fake, image, label, per_class):
+    """The tail get_eval_metrics and get_eval_metrics_decoded share: `fake` (the generator's NHWC output) against the original
+    image (NCHW, any device), un-rounded as the reference uses it."""
+    image = image.to(self._device(), dtype=torch.float32, non_blocking=True).contiguous()
+    real32 = ops.nchw_to_nhwc(image, F32)
+    if per_class:
+      return ops.eval_metrics(fake, real32, self.opt.normalize_mean, self.opt.normalize_std, label, self.n_onehot)
+    return ops.eval_metrics(fake, real32, self.opt.normalize_mean, self.opt.normalize_std)
+
+  def get_eval_metrics_decoded(self, code, x_dict, per_class=False):
+    """get_eval_metrics of the image a receiver reconstructs: the same dict, computed on decode(code, x_dict) against
+    x_dict['image'].  Equal to get_eval_metrics(x_dict) for code = get_code(x_dict) under decode's zero rule: where the eval
+    code holds an exact zero the decoder sees -1 and get_eval_metrics, like get_img, sees 0."""
+    with torch.no_grad():
+      fake, label = self._decode_act(code, x_dict)
+      return self._eval_metrics_of(fake, x_dict['image'], label, per_class)
