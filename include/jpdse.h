@@ -42,7 +42,9 @@ extern "C" {
                                 * (jpdse_code_entropy_*), and the coded label and instance maps (jpdse_semantics_*), and the
                                 * context-model rate term (jpdse_code_rate_loss[_workspace_size]), and the semantics-weighted
                                 * distortion (jpdse_sem_weighted_loss), and the code-length map (jpdse_code_cost[_table,
-                                * _workspace_size]): purely additive, nothing existing changed */
+                                * _workspace_size]), and the code-length maps of the vector quantizer's two coders
+                                * (jpdse_vq_index_cost[_workspace_size], jpdse_vq_plane_cost[_workspace_size]): purely additive,
+                                * nothing existing changed */
 
 enum { JPDSE_F32 = 0, JPDSE_BF16 = 1 };
 enum { JPDSE_PAD_ZERO = 0, JPDSE_PAD_REFLECT = 1 };
@@ -865,6 +867,81 @@ typedef struct jpdse_vq_plane_decode_args {
   void* stream;
 } jpdse_vq_plane_decode_args;
 int jpdse_vq_plane_decode(const jpdse_vq_plane_decode_args* args);
+
+/* ---- soft-to-hard vector quantizer: code-length maps of the two coders (no reference counterpart) ----------
+ * The exact cost, symbol by symbol, that the adaptive model of the coded index stream (index_cost) or of the coded index
+ * planes (plane_cost) above assigns to the indices of ONE image.  index: DEVICE int32, in the layout of the matching encode
+ * call.  A binary decision coded with the probability q of bit 0 (before its update q -= q >> 5 for bit 1, q += (2048 - q) >> 5
+ * for bit 0) costs T[q] for bit 0 and T[2048 - q] for bit 1, T the table of jpdse_code_cost_table: integers in units of
+ * 2^-16 bit.  The cost of a symbol is the sum over the decisions its coder spends on it, entries and conditions as stated
+ * above, statement for statement:
+ *   index_cost   symbol m lies in stream m % S and costs the nb bit-tree decisions of that stream's table, in stream order;
+ *                it belongs to cell m / G and group m % G (G >= 1 divides M; G need not divide S)
+ *   plane_cost   symbol (y, x, g) lies in stream k * G + g and costs its left-match flag (rule 1, if coded), its upper-match
+ *                flag (rule 2, if coded) and, if neither matched, the nb literal decisions (rule 3); cell y * w + x, group g
+ * An index outside [0, L) is priced as the coder codes it -- as 0, and seen as 0 by its neighbours -- and sets bit 1 of
+ * *status, which the call writes (0 otherwise).  All sums are 64-bit integer sums of units: order-free, two calls give
+ * identical bits.
+ *   symbol[m]            uint32, the cost of the symbol at its own position in the index tensor; optional
+ *   cell[i]              = sum_g symbol[i * G + g], i < M / G: the rate map
+ *   group[g]             = sum_i symbol[i * G + g]
+ *   stream_units[s]      = the sum of the costs of the symbols of stream s
+ *   stream_decisions[s]  = the binary decisions stream s coded: nb * cnt_s for index_cost, data dependent for plane_cost
+ *   class_units[k], class_pixels[k]   the class tables of jpdse_code_cost for N = 1, same rule, same kernel: a cell's units go
+ *                        undivided to each of the s*s pixels it covers, row n_classes collects the pixels without a class
+ * So sum cell == sum group == sum stream_units, and sum_k class_units[k] == s*s * sum cell, exactly.
+ * label: DEVICE fp32 [1][1][H][W], H = s h and W = s w with s a power of two; index_cost reads the cell grid h, w
+ * (h * w * G == M) with a label only.  label == NULL: no class tables; h, w (index_cost), H, W, n_classes and the two class
+ * pointers are not read.
+ * The cost is the model's ideal code length, not a size: per stream
+ *   |8 * stream bytes - stream_units / 65536| <= 48 + stream_decisions / 64 bits.
+ * Plain loads and stores; the only atomics are the integer ones of the class tables.  Every loop is bounded by the shape.
+ * Limits: those of the matching encode call; G >= 1 dividing M; with a label those of jpdse_code_cost's label path
+ * (n_classes in [1, 256], H*W*G <= 2^40).  JPDSE_EINVAL before any launch: a NULL args, index, cell, group, stream_units,
+ * stream_decisions or status (with a label: class_units, class_pixels), a value outside the limits, a workspace that is not
+ * 16-byte aligned.  A workspace that is missing or too small is JPDSE_EWORKSPACE.  ws: the size query's bytes (host only; 0
+ * for a shape the call refuses or n_classes outside [0, 256], 0 standing for "no label map"). */
+size_t jpdse_vq_index_cost_workspace_size(int32_t M, int32_t L, int32_t S, int32_t G, int32_t n_classes);
+typedef struct jpdse_vq_index_cost_args {
+  int32_t M, L, S, G;
+  const int32_t* index;        /* device [M] */
+  int32_t h, w;                /* the cell grid, h * w * G == M; read with a label only */
+  int32_t H, W;                /* the image's extents behind the label map */
+  const float* label;          /* device fp32 [1][1][H][W], or NULL: no class tables */
+  int32_t n_classes;           /* 1..256 with a label */
+  uint32_t* symbol;            /* device uint32 [M], or NULL: aggregates only */
+  uint64_t* cell;              /* device [M / G] */
+  uint64_t* group;             /* device [G] */
+  uint64_t* stream_units;      /* device [S] */
+  uint32_t* stream_decisions;  /* device [S] */
+  int32_t* status;             /* device word */
+  uint64_t* class_units;       /* device [n_classes + 1], or NULL without a label */
+  uint64_t* class_pixels;      /* device [n_classes + 1], or NULL without a label */
+  void* ws;
+  size_t ws_bytes;
+  void* stream;
+} jpdse_vq_index_cost_args;
+int jpdse_vq_index_cost(const jpdse_vq_index_cost_args* args);
+size_t jpdse_vq_plane_cost_workspace_size(int32_t h, int32_t w, int32_t G, int32_t L, int32_t strip_rows, int32_t n_classes);
+typedef struct jpdse_vq_plane_cost_args {
+  int32_t h, w, G, L, strip_rows;
+  const int32_t* index;        /* device [h * w * G] */
+  int32_t H, W;                /* the image's extents behind the label map */
+  const float* label;          /* device fp32 [1][1][H][W], or NULL: no class tables */
+  int32_t n_classes;           /* 1..256 with a label */
+  uint32_t* symbol;            /* device uint32 [h * w * G], or NULL: aggregates only */
+  uint64_t* cell;              /* device [h * w] */
+  uint64_t* group;             /* device [G] */
+  uint64_t* stream_units;      /* device [S], S = ceil(h / strip_rows) * G */
+  uint32_t* stream_decisions;  /* device [S] */
+  int32_t* status;             /* device word */
+  uint64_t* class_units;       /* device [n_classes + 1], or NULL without a label */
+  uint64_t* class_pixels;      /* device [n_classes + 1], or NULL without a label */
+  void* ws;
+  size_t ws_bytes;
+  void* stream;
+} jpdse_vq_plane_cost_args;
+int jpdse_vq_plane_cost(const jpdse_vq_plane_cost_args* args);
 
 /* ---- vector-quantizer bottleneck: quantize in one call, [M][L] never in memory (vq_bottleneck.hip) ---------
  * The quantizer above as a layer: features in, features out.  x, y, dy, dx: row-major [M][D] in `dtype`; code_book: fp32

@@ -253,6 +253,68 @@ const uint32_t* code_cost_table_host() {
   return table.t;
 }
 
+// the label path of the code-length maps (code_cost.hip, vq_cost.hip): log2(s) when H = s h and W = s w with s a power of
+// two, else -1; and everything of a label map that can be refused without a device
+static int cost_scale_shift(int H, int W, int h, int w) {
+  for (int sh = 0; sh < 31; ++sh) {
+    const long long s = 1LL << sh;
+    if (s * h == H && s * w == W) return sh;
+    if (s * h > H) break;
+  }
+  return -1;
+}
+
+int cost_label_check(const char* who, const void* class_units, const void* class_pixels, int H, int W, int h, int w, int C,
+                     int n_classes, int* shift) {
+  JPDSE_REQUIRE(class_units != nullptr && class_pixels != nullptr, "%s: null pointer class_units or class_pixels with a label map",
+                who);
+  JPDSE_REQUIRE(H > 0 && W > 0, "%s: non-positive extent (H %d, W %d)", who, H, W);
+  *shift = cost_scale_shift(H, W, h, w);
+  JPDSE_REQUIRE(*shift >= 0, "%s: H %d x W %d is not the same power-of-two multiple of h %d x w %d", who, H, W, h, w);
+  JPDSE_REQUIRE(n_classes >= 1 && n_classes <= kCostClassesMax, "%s: n_classes %d outside [1, %d]", who, n_classes, kCostClassesMax);
+  JPDSE_REQUIRE((long long)H * W <= kCostMaxUnits / C, "%s: H * W * C above 2^40 (H %d, W %d, C %d)", who, H, W, C);
+  return JPDSE_OK;
+}
+
+// jpdse_vq_*_cost (vq_cost.hip).  The workspace: the cost table (2049 uint32, rounded up to 256 bytes), then the
+// per-symbol costs uint32 [M] (used when the caller does not want them)
+size_t vq_cost_workspace_bytes(long long M) { return align_up(2049 * sizeof(uint32_t), 256) + (size_t)M * sizeof(uint32_t); }
+
+static int vq_cost_ws_check(const char* who, const void* ws, size_t ws_bytes, size_t need) {
+  if (ws == nullptr || ws_bytes < need)
+    return set_error(JPDSE_EWORKSPACE, "%s: workspace too small (%zu bytes, %zu needed)", who, ws ? ws_bytes : (size_t)0, need);
+  JPDSE_REQUIRE(((uintptr_t)ws & 15) == 0, "%s: workspace not 16-byte aligned", who);
+  return JPDSE_OK;
+}
+
+int vq_index_cost_check(const jpdse_vq_index_cost_args* a, int* shift) {
+  JPDSE_REQUIRE(a != nullptr, "vq_index_cost: null argument struct");
+  if (int rc = vq_index_shape_check("vq_index_cost", a->M, a->L, a->S)) return rc;
+  JPDSE_REQUIRE(a->G >= 1 && a->M % a->G == 0, "vq_index_cost: G = %d groups (at least 1, dividing M = %d)", a->G, a->M);
+  JPDSE_REQUIRE(a->index && a->cell && a->group && a->stream_units && a->stream_decisions && a->status,
+                "vq_index_cost: null pointer");
+  *shift = 0;
+  if (a->label != nullptr) {
+    JPDSE_REQUIRE(a->h >= 1 && a->w >= 1 && (long long)a->h * a->w * a->G == a->M,
+                  "vq_index_cost: a cell grid of h = %d x w = %d in G = %d groups does not hold M = %d indices", a->h, a->w, a->G, a->M);
+    if (int rc = cost_label_check("vq_index_cost", a->class_units, a->class_pixels, a->H, a->W, a->h, a->w, a->G, a->n_classes, shift))
+      return rc;
+  }
+  return vq_cost_ws_check("vq_index_cost", a->ws, a->ws_bytes, vq_cost_workspace_bytes(a->M));
+}
+
+int vq_plane_cost_check(const jpdse_vq_plane_cost_args* a, int* shift) {
+  JPDSE_REQUIRE(a != nullptr, "vq_plane_cost: null argument struct");
+  if (int rc = vq_plane_shape_check("vq_plane_cost", a->h, a->w, a->G, a->L, a->strip_rows)) return rc;
+  JPDSE_REQUIRE(a->index && a->cell && a->group && a->stream_units && a->stream_decisions && a->status,
+                "vq_plane_cost: null pointer");
+  *shift = 0;
+  if (a->label != nullptr)
+    if (int rc = cost_label_check("vq_plane_cost", a->class_units, a->class_pixels, a->H, a->W, a->h, a->w, a->G, a->n_classes, shift))
+      return rc;
+  return vq_cost_ws_check("vq_plane_cost", a->ws, a->ws_bytes, vq_cost_workspace_bytes((long long)a->h * a->w * a->G));
+}
+
 // ---- in-library timer for the HBM-bound calls (bench.py "roofline_hbm"): hipEvent pairs around whole InstanceNorm /
 // Adam calls, recorded on the stream the kernels run on; each region carries the call's ALGORITHMIC bytes.
 struct HbmProf {
@@ -327,6 +389,16 @@ int jpdse_code_cost_table(uint32_t* out) {
   JPDSE_REQUIRE(out != nullptr, "code_cost_table: null pointer");
   memcpy(out, jpdse::code_cost_table_host(), 2049 * sizeof(uint32_t));
   return JPDSE_OK;
+}
+
+size_t jpdse_vq_index_cost_workspace_size(int32_t M, int32_t L, int32_t S, int32_t G, int32_t n_classes) {
+  if (jpdse::vq_index_workspace_bytes(M, L, S) == 0 || G < 1 || M % G != 0 || n_classes < 0 || n_classes > jpdse::kCostClassesMax) return 0;
+  return jpdse::vq_cost_workspace_bytes(M);
+}
+
+size_t jpdse_vq_plane_cost_workspace_size(int32_t h, int32_t w, int32_t G, int32_t L, int32_t strip_rows, int32_t n_classes) {
+  if (jpdse::vq_plane_workspace_bytes(h, w, G, L, strip_rows) == 0 || n_classes < 0 || n_classes > jpdse::kCostClassesMax) return 0;
+  return jpdse::vq_cost_workspace_bytes((long long)h * w * G);
 }
 
 int jpdse_version(void) { return JPDSE_ABI_VERSION; }

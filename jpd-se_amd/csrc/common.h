@@ -59,6 +59,18 @@ int vq_plane_decode_check(const jpdse_vq_plane_decode_args* a);
 
 // the cost table of jpdse_code_cost_table (api.cpp): 2049 entries, built once on the host in fp64
 const uint32_t* code_cost_table_host();
+// the label path of the code-length maps (code_cost.hip, vq_cost.hip; kernels: cost_class.h): its limits and its checks.  C: the
+// symbols per cell.  *shift = log2(s) for H = s h, W = s w, s a power of two
+constexpr int kCostClassesMax = 256;             // what jpdse_eval_metrics_sem takes
+constexpr long long kCostMaxUnits = 1LL << 40;   // symbols (and image pixels x C): every 64-bit sum stays below 2^60
+int cost_label_check(const char* who, const void* class_units, const void* class_pixels, int H, int W, int h, int w, int C,
+                     int n_classes, int* shift);
+
+// the jpdse_vq_*_cost calls (api.cpp; kernels: vq_cost.hip): the limits of the matching encode call, G >= 1
+// dividing M, and the label path above.  The size is 0 outside them; *shift as above, 0 without a label
+size_t vq_cost_workspace_bytes(long long M);
+int vq_index_cost_check(const jpdse_vq_index_cost_args* a, int* shift);
+int vq_plane_cost_check(const jpdse_vq_plane_cost_args* a, int* shift);
 
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 

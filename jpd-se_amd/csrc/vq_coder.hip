@@ -12,11 +12,11 @@
 // on 32 different banks.  One wave per block, 2^nb * 128 bytes of LDS: 64 KiB at L = 512, within the default limit.
 #include "range_coder.h"
 #include "vq_col.h"
+#include "vq_model.h"
 
 namespace jpdse {
 
-// the symbols of stream s and its slot (nb * count + 8 bytes) in the workspace: M = q S + r, the first r streams hold q + 1
-__device__ __forceinline__ int vq_stream_count(int s, int q, int r) { return q + (s < r ? 1 : 0); }
+// the slot (nb * count + 8 bytes) of stream s in the workspace; its count: vq_model.h
 __device__ __forceinline__ long long vq_slot_offset(int s, int q, int r, int nb) {
   return (long long)s * (nb * (long long)q + 8) + (long long)nb * min(s, r);
 }

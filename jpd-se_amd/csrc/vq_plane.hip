@@ -13,28 +13,16 @@
 // (10 + 2^nb) * 128 bytes of LDS: 66,816 bytes at nb = 9, which the launch opts in for (vq_plane_lds_optin).
 #include "range_coder.h"
 #include "vq_col.h"
+#include "vq_model.h"
 
 namespace jpdse {
 
-constexpr int kPlaneUp = 8, kPlaneUpOnly = 10, kPlaneTree = 10;   // entries: 0 .. 7 left flag, 8 .. 9 / 10 upper flag, 10 + m
-
-// the geometry of stream s: its group, its strip's first row and its rows; its slot in the workspace.  Only the last strip is
-// short: the streams of the strips in front of stream s have full slots of (nb + 2) * strip_rows * w + 8 bytes, the g streams
-// of its own strip in front of it have slots of its own size -- the slots are packed and add up to (nb + 2) M + 8 S
-struct PlaneStream {
-  int g, y0, rows;
-};
-__device__ __forceinline__ PlaneStream plane_stream(int s, int h, int G, int strip_rows) {
-  const int k = s / G, y0 = k * strip_rows;
-  return PlaneStream{s - k * G, y0, min(strip_rows, h - y0)};
-}
+// The slot of stream s (its geometry: vq_model.h) in the workspace.  Only the last strip is short: the streams of the strips in
+// front of stream s have full slots of (nb + 2) * strip_rows * w + 8 bytes, the g streams of its own strip in front of it have
+// slots of its own size -- the slots are packed and add up to (nb + 2) M + 8 S
 __device__ __forceinline__ int plane_slot_bytes(int rows, int w, int nb) { return (nb + 2) * rows * w + 8; }
 __device__ __forceinline__ long long plane_slot_offset(int s, PlaneStream st, int w, int strip_rows, int nb) {
   return (long long)(s - st.g) * plane_slot_bytes(strip_rows, w, nb) + (long long)st.g * plane_slot_bytes(st.rows, w, nb);
-}
-
-__device__ __forceinline__ void plane_table_init(uint16_t* prob, int nb) {
-  for (int e = 0; e < kPlaneTree + (1 << nb); ++e) prob[e * 64] = (uint16_t)kProbInit;
 }
 
 // one adaptive decision with the lane's table entry e
@@ -48,15 +36,6 @@ __device__ __forceinline__ uint32_t plane_get(RcDecoder& rc, uint16_t* prob, int
   const uint32_t bit = rc.decode(p);
   prob[e * 64] = (uint16_t)p;
   return bit;
-}
-
-// an index as the coder sees it: a value outside [0, L) is 0, for the symbol itself and as a neighbour alike
-__device__ __forceinline__ int plane_clean(int32_t v, int L, int& bad) {
-  if ((uint32_t)v >= (uint32_t)L) {
-    bad = 2;
-    return 0;
-  }
-  return v;
 }
 
 // Phase 1 of the encoder: stream s into its slot; lens[s] = the bytes it needs (slot size + 1: it did not fit, unreachable by
@@ -200,16 +179,6 @@ __global__ void __launch_bounds__(64) vq_plane_decode_kernel(const uint8_t* __re
 }
 
 static inline size_t vq_plane_lds_bytes(int nb) { return (size_t)(kPlaneTree + (1 << nb)) * 64 * sizeof(uint16_t); }
-
-// More than 64 KiB of dynamic LDS (nb = 9: 66,816 bytes) needs the kernel's opt-in; two such blocks still fit a CU's 160 KiB,
-// the occupancy vq_coder.hip has at its 64 KiB.  Host only, idempotent.
-template <typename K>
-static int vq_plane_lds_optin(const char* what, K kernel, size_t lds) {
-  if (lds <= 65536) return JPDSE_OK;
-  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return set_error(JPDSE_ELAUNCH, "%s: %zu bytes of LDS: %s", what, lds, hipGetErrorString(e));
-  return JPDSE_OK;
-}
 
 }  // namespace jpdse
 

@@ -115,6 +115,8 @@ class VQIndexCodec(_Codec):
 
   RATE_OPTION = 'lambda_vq_rate'
   context_coder = False
+  COST_CODERS = (None, 'index', 'plane')      # what cost() prices: the kept file, the .jpdv model, the .jpdw model
+  INDEX_STREAMS_PER_GROUP = 8                 # payloads(): (C / D) * 8 streams per .jpdv blob
 
   def _planes(self, H, W, groups):
     """(h, w, G) of the index planes of an H x W image."""
@@ -186,11 +188,47 @@ class VQIndexCodec(_Codec):
     indices of one channel group only (write_indices clamps the count to the number of indices).  With the context coder both
     files of every image are made and the smaller one is returned, the .jpdv one on a tie: never more bytes than without."""
     _, H, W, _, L, groups = self.geometry(x_dict, 'get_coded')
-    blobs = [vqstream.write_indices(None, code[i:i + 1], L, n_streams=groups * 8) for i in range(code.shape[0])]
+    blobs = [vqstream.write_indices(None, code[i:i + 1], L, n_streams=groups * self.INDEX_STREAMS_PER_GROUP)
+             for i in range(code.shape[0])]
     if self.context_coder:
       planes = [vqplane.write_planes(None, code[i], self._planes(H, W, groups), L) for i in range(code.shape[0])]
       blobs = [p if len(p) < len(b) else b for b, p in zip(blobs, planes)]
     return blobs
+
+  def check_coder(self, coder, who):
+    """ValueError for a `coder` cost() does not know.  Host only."""
+    if coder not in self.COST_CODERS:
+      raise ValueError('%s: coder %r, expected None (the file get_coded keeps), \'index\' (.jpdv) or \'plane\' (.jpdw)' % (who, coder))
+
+  def cost(self, code, x_dict, label=None, n_classes=0, coder=None):
+    """Where the bits of `code` (what code() returned) go, image by image: a list of N (coder, result) pairs,
+    coder 'index' or 'plane' and result the dict of device tensors of ops.vq_index_cost / ops.vq_plane_cost for that image --
+    cell [h * w], group [G], stream_units, stream_decisions and, with `label` (device fp32 [N, 1, H, W]) and `n_classes`, the
+    class tables.
+    coder 'index': the model of the .jpdv file, in the stream count payloads() uses (groups * 8, clamped as write_indices
+    clamps it); 'plane': the model of the .jpdw file, in vqplane's default strip rows; None: the file get_coded keeps for the
+    image -- 'index' without the context coder; with it the blobs are made as payloads() makes them and each image's magic
+    decides.  A .jpdv file that fell back to packed indices (mode 0: coding did not pay) is still priced under the index
+    model: the figure is that model's ideal code length, not the size of the kept file."""
+    self.check_coder(coder, 'cost')
+    N, H, W, code_len, L, groups = self.geometry(x_dict, 'cost')
+    h, w, G = self._planes(H, W, groups)
+    kept = [coder or 'index'] * N
+    if coder is None and self.context_coder:
+      kept = ['plane' if _is_plane_blob(b) else 'index' for b in self.payloads(code, x_dict)]
+    S = vqstream.clamp_streams(groups * self.INDEX_STREAMS_PER_GROUP, code_len)
+    out = []
+    for i in range(N):
+      index = code[i].reshape(-1).to(torch.int32).contiguous()
+      lab = label[i:i + 1] if label is not None else None
+      if kept[i] == 'plane':
+        r = ops.vq_plane_cost(index, (h, w, G), L, vqplane.DEFAULT_STRIP_ROWS, lab, n_classes)
+      else:
+        r = ops.vq_index_cost(index, L, S, G, lab, n_classes, (h, w))
+      out.append((kept[i], r))
+    if any(int(r['status'].item()) & 2 for _, r in out):
+      raise ValueError('cost: an index outside [0, %d)' % L)
+    return out
 
   def file_rates(self, payloads, H, W):
     """(coded bpp, raw bpp), batch means: the .jpdv blobs, and the packed-index file (mode 0) of the same code: nb bits per

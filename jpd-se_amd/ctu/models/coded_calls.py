@@ -1,6 +1,6 @@
 """The coded-stream and receiver calls of Pix2PixHDModel (extensions: the reference stops at get_code / get_eval_rate): the
 encoder's code in its forms, its rate figures, the entropy-coded files, the coded label and instance maps, and the receiver
-that reconstructs an image from them.  DESIGN.md 4.4, 4.8 - 4.10, 4.12, 4.15 - 4.17 and 4.19."""
+that reconstructs an image from them.  DESIGN.md 4.4, 4.8 - 4.10, 4.12, 4.15 - 4.17, 4.19 and 4.20."""
 import torch
 
 from jpdse_hip import F32, ops
@@ -199,7 +199,11 @@ class CodedCalls(object):
       r = ops.code_cost(b, label, self.n_onehot)
       units, pix = r['class_units'].cpu(), r['class_pixels'].cpu()
     s = int(label.shape[-1]) // b.W
-    den = float(ops.CODE_COST_UNIT) * s * s
+    return self._class_figures(units, pix, float(ops.CODE_COST_UNIT) * s * s)
+
+  @staticmethod
+  def _class_figures(units, pix, den):
+    """The dict of get_class_rates from the integer class tables [N, rows] of N images; den: units per bit."""
 
     def figures(u, p):                  # integer tensors [..., rows]
       bits = u.to(torch.float64) / den
@@ -212,6 +216,47 @@ class CodedCalls(object):
     out = figures(units.sum(dim=0), pix.sum(dim=0))
     out['per_image'] = figures(units, pix)
     return out
+
+  # ---- where the bits of the vector-quantised code go (extension) ----------------------------------------------
+  def _vq_cost(self, who, x_dict, coder, with_label):
+    """codec.cost of the eval-mode code; every refusal comes before device work."""
+    codec = self._vq_codec(who)
+    codec.check_coder(coder, who)
+    with torch.no_grad():
+      code = self._eval_code(codec, x_dict)
+      label = self._semantics(x_dict)[0] if with_label else None
+      return codec.cost(code, x_dict, label, self.n_onehot if with_label else 0, coder)
+
+  def get_vq_rate_map(self, x_dict, coder=None):
+    """get_rate_map for --encoder_quantizer s2hvq: the code length of the eval-mode code (the one get_vq_code / get_coded
+    produce) under the adaptive model of its coder, symbol by symbol (ops.vq_index_cost / ops.vq_plane_cost).  coder: 'index'
+    prices the .jpdv model, 'plane' the .jpdw model, None the file get_coded keeps for each image (VQIndexCodec.cost).  dict of
+    float64 CPU tensors: `map` [N, h, w] bits per code cell, `per_group` [N, G] bits per channel group, `bits` [N], `bpp` [N] =
+    bits / (H * W); `stream_bits`: a list of N tensors [S_n], `stream_decisions`: a list of N int64 tensors [S_n] (the binary
+    decisions each stream coded: what the bound of DESIGN.md 4.20 is stated in), `coder`: a list of N strings, the model each
+    image was priced under.  map and per_group each sum to bits.  The model's ideal length, not a file size."""
+    results = self._vq_cost('get_vq_rate_map', x_dict, coder, False)
+    codec = self.codec
+    _, H, W, _, _, groups = codec.geometry(x_dict, 'get_vq_rate_map')
+    h, w, _ = codec._planes(H, W, groups)
+    unit = float(ops.CODE_COST_UNIT)
+    cell = torch.stack([r['cell'] for _, r in results]).cpu().view(len(results), h, w)
+    group = torch.stack([r['group'] for _, r in results]).cpu()
+    bits = cell.sum(dim=(1, 2)).to(torch.float64) / unit            # integer sums first: exact
+    return dict(map=cell.to(torch.float64) / unit, per_group=group.to(torch.float64) / unit, bits=bits,
+                bpp=bits / self._pixels(x_dict),
+                stream_bits=[r['stream_units'].cpu().to(torch.float64) / unit for _, r in results],
+                stream_decisions=[r['stream_decisions'].cpu().to(torch.int64) for _, r in results],
+                coder=[c for c, _ in results])
+
+  def get_vq_class_rates(self, x_dict, coder=None):
+    """get_class_rates for --encoder_quantizer s2hvq: the code length of get_vq_rate_map(x_dict, coder) attributed to the
+    semantic classes of the pixels each code cell covers.  The dict of get_class_rates, same keys, same row order."""
+    results = self._vq_cost('get_vq_class_rates', x_dict, coder, True)
+    units = torch.stack([r['class_units'] for _, r in results]).cpu()
+    pix = torch.stack([r['class_pixels'] for _, r in results]).cpu()
+    s = 1 << self.netE.n_downsampling
+    return self._class_figures(units, pix, float(ops.CODE_COST_UNIT) * s * s)
 
   # ---- coded label and instance maps (extension; DESIGN.md 4.9) --------------------------------------------------------------
   def _label_set(self):

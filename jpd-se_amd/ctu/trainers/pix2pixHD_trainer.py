@@ -222,6 +222,21 @@ class Pix2PixHDTrainer(BaseTrainer):
     self.eval()
     return self.model(x_dict, self.opt, mode='get_class_rates')
 
+  def get_vq_rate_map(self, x_dict, coder=None):
+    """Where the bits of the vector-quantised code go (--encoder_quantizer s2hvq; extension): the code length of
+    the eval-mode code under the adaptive model of its coder, exact per symbol.  coder: 'index' (the .jpdv model), 'plane' (the
+    .jpdw model) or None (per image, the file get_coded keeps).  dict of float64 CPU tensors: `map` [N, h, w] bits per code
+    cell, `per_group` [N, G], `bits` [N], `bpp` [N]; lists with one entry per image: `stream_bits` [S_n], `stream_decisions`
+    (int64 [S_n]) and `coder` ('index' / 'plane').  get_rate_map stays the binarizer's call."""
+    self.eval()
+    return self.model.get_vq_rate_map(x_dict, coder)
+
+  def get_vq_class_rates(self, x_dict, coder=None):
+    """The same bits attributed to the semantic classes of the pixels each code cell covers: the dict of get_class_rates, row
+    for row with get_eval_metrics(per_class=True) plus the last row for the pixels without a class."""
+    self.eval()
+    return self.model.get_vq_class_rates(x_dict, coder)
+
   def get_coded_semantics(self, x_dict, strip_rows=8):
     """The label and instance maps, coded losslessly on the device (extension): a list with the body of one
     .jpds file (ctu.utils.semantics) per image."""

@@ -122,6 +122,11 @@ def parse_blob(blob, who='blob'):
   return n, code_len, L, S, mode, body
 
 
+def clamp_streams(n_streams, M):
+  """The stream count write_indices codes M indices in when asked for n_streams: at least 1, at most M and the coder's limit."""
+  return max(1, min(int(n_streams), int(M), MAX_STREAMS))
+
+
 def write_indices(path, code, n_center, n_streams=64):
   """code: the int64 (n, code_len) device tensor of S2HVQ.encode(..., train=False, raw=False) -> the file's bytes, also
   written to `path` unless that is None.  n_streams is clamped to the number of indices.  ValueError for an index outside
@@ -131,7 +136,7 @@ def write_indices(path, code, n_center, n_streams=64):
   n, code_len, L = int(code.shape[0]), int(code.shape[1]), int(n_center)
   _limits(n, code_len, L, 'write_indices')
   M = n * code_len
-  S = max(1, min(int(n_streams), M, MAX_STREAMS))
+  S = clamp_streams(n_streams, M)
   flat = code.contiguous().view(-1)
   if bool(((flat < 0) | (flat >= L)).any()):      # before the cast to the coder's int32 could fold a far value into range
     raise ValueError('write_indices: an index outside [0, %d)' % L)

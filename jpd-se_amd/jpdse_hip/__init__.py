@@ -161,6 +161,23 @@ class VqPlaneDecodeArgs(ctypes.Structure):
               ('stream', ctypes.c_void_p)]
 
 
+# the jpdse_vq_*_cost calls (vq_cost.hip)
+_VQ_COST_TAIL = [('H', ctypes.c_int32), ('W', ctypes.c_int32), ('label', ctypes.c_void_p), ('n_classes', ctypes.c_int32),
+                 ('symbol', ctypes.c_void_p), ('cell', ctypes.c_void_p), ('group', ctypes.c_void_p),
+                 ('stream_units', ctypes.c_void_p), ('stream_decisions', ctypes.c_void_p), ('status', ctypes.c_void_p),
+                 ('class_units', ctypes.c_void_p), ('class_pixels', ctypes.c_void_p), ('ws', ctypes.c_void_p),
+                 ('ws_bytes', ctypes.c_size_t), ('stream', ctypes.c_void_p)]
+
+
+class VqIndexCostArgs(ctypes.Structure):
+  _fields_ = [(n, ctypes.c_int32) for n in ('M', 'L', 'S', 'G')] + \
+             [('index', ctypes.c_void_p), ('h', ctypes.c_int32), ('w', ctypes.c_int32)] + _VQ_COST_TAIL
+
+
+class VqPlaneCostArgs(ctypes.Structure):
+  _fields_ = [(n, ctypes.c_int32) for n in ('h', 'w', 'G', 'L', 'strip_rows')] + [('index', ctypes.c_void_p)] + _VQ_COST_TAIL
+
+
 # the jpdse_vq_quantize_* calls (vq_bottleneck.hip)
 class VqQuantizeFwdArgs(ctypes.Structure):
   _fields_ = [(n, ctypes.c_int32) for n in ('dtype', 'M', 'D', 'L')] + \
@@ -313,6 +330,10 @@ SIGNATURES = {
     'jpdse_vq_plane_workspace_size': (_SZ, [_I32, _I32, _I32, _I32, _I32]),
     'jpdse_vq_plane_encode': (_I32, [ctypes.POINTER(VqPlaneEncodeArgs)]),
     'jpdse_vq_plane_decode': (_I32, [ctypes.POINTER(VqPlaneDecodeArgs)]),
+    'jpdse_vq_index_cost_workspace_size': (_SZ, [_I32, _I32, _I32, _I32, _I32]),
+    'jpdse_vq_index_cost': (_I32, [ctypes.POINTER(VqIndexCostArgs)]),
+    'jpdse_vq_plane_cost_workspace_size': (_SZ, [_I32, _I32, _I32, _I32, _I32, _I32]),
+    'jpdse_vq_plane_cost': (_I32, [ctypes.POINTER(VqPlaneCostArgs)]),
     'jpdse_vq_quantize_workspace_size': (_SZ, [_I32, _I32, _I32]),
     'jpdse_vq_quantize_fwd': (_I32, [ctypes.POINTER(VqQuantizeFwdArgs)]),
     'jpdse_vq_quantize_bwd': (_I32, [ctypes.POINTER(VqQuantizeBwdArgs)]),

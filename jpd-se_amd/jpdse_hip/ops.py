@@ -1020,4 +1020,5 @@ def vq_rate_fwd(x, code_book, sigma, G, denom, scale=1.0, hard=False, want_hist=
 from .streams import (code_entropy_encode, code_entropy_decode, length_table_size, check_length_table,  # noqa: E402,F401
                       SEM_RAW, SEM_CODED, SEM_RAW_BYTES, semantics_strips, semantics_encode, semantics_check_entry, semantics_decode,
                       VQ_INDEX_MAX_S, vq_index_bits, vq_index_encode, vq_index_decode,
-                      vq_plane_streams, vq_plane_capacity, vq_plane_shape, vq_plane_encode, vq_plane_decode)
+                      vq_plane_streams, vq_plane_capacity, vq_plane_shape, vq_plane_encode, vq_plane_decode,
+                      vq_index_cost, vq_plane_cost)

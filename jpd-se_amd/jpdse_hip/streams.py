@@ -1,4 +1,5 @@
-"""The host half of the device coders (entropy.hip, semantics.hip, vq_coder.hip: DESIGN.md 4.18; vq_plane.hip: 4.19): the layout of their
+"""The host half of the device coders (entropy.hip, semantics.hip, vq_coder.hip: DESIGN.md 4.18; vq_plane.hip: 4.19; the cost walks
+of the two index coders, vq_cost.hip: 4.20): the layout of their
 buffers, the payload rules (length tables, plane entries, index limits), the staging of payload rows for one upload, what is
 refused before the library is touched, and the reading of status words.  `jpdse_hip.ops` re-exports every public name.
 
@@ -10,7 +11,8 @@ import struct
 
 import torch
 
-from . import lib, check, JpdseError, VqIndexEncodeArgs, VqIndexDecodeArgs, VqPlaneEncodeArgs, VqPlaneDecodeArgs
+from . import (lib, check, JpdseError, VqIndexEncodeArgs, VqIndexDecodeArgs, VqPlaneEncodeArgs, VqPlaneDecodeArgs, VqIndexCostArgs,
+               VqPlaneCostArgs)
 
 
 # ---- shared by the three coders ----------------------------------------------------------------------------------------------
@@ -417,6 +419,99 @@ def vq_plane_decode(payload, h, w, G, L, strip_rows=8, device=None):
   if int(status.item()) & 2:
     raise ValueError('vq_plane_decode: a decoded value outside [0, %d): not a coded stream of this alphabet' % L)
   return index
+
+
+# ---- soft-to-hard vector quantizer: code-length maps of the two coders (vq_cost.hip; definition: DESIGN.md 4.20) ---------------
+VQ_COST_MAX_CLASSES = 256
+
+
+def _vq_cost_label(who, label, n_classes, dev):
+  """(H, W, rows of the class tables) of the label map of a cost call, (0, 0, 0) without one.  Host only."""
+  if label is None:
+    if n_classes:
+      raise ValueError('%s: n_classes without a label map' % who)
+    return 0, 0, 0
+  n_classes = int(n_classes)
+  if not torch.is_tensor(label) or label.dtype != torch.float32 or label.dim() != 4 or tuple(label.shape[:2]) != (1, 1):
+    raise ValueError('%s: the label map is a float32 [1, 1, H, W] tensor' % who)
+  if not label.is_contiguous() or label.device != dev:
+    raise ValueError('%s: the label map must be contiguous and on the device of the indices' % who)
+  if not 1 <= n_classes <= VQ_COST_MAX_CLASSES:
+    raise ValueError('%s: n_classes %d outside [1, %d]' % (who, n_classes, VQ_COST_MAX_CLASSES))
+  return int(label.shape[2]), int(label.shape[3]), n_classes + 1
+
+
+def _vq_cost_run(call, n_ws, head, index, M, G, S, label, n_classes, want_symbols):
+  """The outputs of a cost call and the call itself: `head` holds the arguments in front of H of the call's struct, `label`
+  (H, W, rows) as _vq_cost_label gave them and the map."""
+  dev = index.device
+  (H, W, rows), label = label
+  new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+  symbol = new(M, torch.int32) if want_symbols else None
+  cell, group, units = new(M // G, torch.int64), new(G, torch.int64), new(S, torch.int64)
+  decisions, status = new(S, torch.int32), new(1, torch.int32)
+  class_units = new(rows, torch.int64) if rows else None
+  class_pixels = new(rows, torch.int64) if rows else None
+  ptr = lambda t: t.data_ptr() if t is not None else None
+  ws = workspace(n_ws, dev)
+  with torch.cuda.device(dev):
+    args = head + (H, W, ptr(label), int(n_classes) if rows else 0, ptr(symbol), ptr(cell), ptr(group), ptr(units), ptr(decisions),
+                   ptr(status), ptr(class_units), ptr(class_pixels), ws.data_ptr(), ws.numel(),
+                   torch.cuda.current_stream().cuda_stream)
+    call(args)
+  return dict(symbol=symbol, cell=cell, group=group, stream_units=units, stream_decisions=decisions, status=status,
+              class_units=class_units, class_pixels=class_pixels)
+
+
+def vq_index_cost(index, L, n_streams, groups=1, label=None, n_classes=0, hw=None, want_symbols=False):
+  """Where the bits of a coded index stream go (jpdse_vq_index_cost): the exact cost the adaptive model of vq_index_encode(index,
+  L, n_streams) assigns to every index, in units of 2^-16 bit (ops.CODE_COST_UNIT per bit).  index: the device int32 [M] indices
+  of ONE image; symbol m belongs to cell m // groups and group m % groups (groups >= 1 divides M).  Returns a dict of device
+  tensors: `cell` int64 [M / groups] (the rate map), `group` int64 [groups], `stream_units` int64 [S], `stream_decisions` int32
+  [S] (the binary decisions each stream coded), `status` int32 [1] (bit 1: an index outside [0, L) was met and priced, as the
+  coder codes it, as 0), `symbol` int32 [M] (None unless want_symbols) and, with `label` (device fp32 [1, 1, H, W]), `n_classes`
+  and `hw` = (h, w), the cell grid (h * w * groups == M, H / h == W / w a power of two), `class_units` and `class_pixels` int64
+  [n_classes + 1] by the rule of code_cost; both None without a label.  Integer sums throughout: two calls give identical
+  tensors.  ValueError, before the library is touched, for a shape outside the limits of vq_index_encode, a group count that
+  does not divide M, and a label map or class count the call does not take."""
+  who = 'vq_index_cost'
+  assert index.dim() == 1 and index.is_cuda, (tuple(index.shape), index.device)
+  M, L, S = _vq_index_shape(who, index.numel(), L, n_streams)
+  G = int(groups)
+  if G < 1 or M % G:
+    raise ValueError('%s: groups = %d does not divide M = %d indices' % (who, G, M))
+  _vq_index(index, M, index.device)
+  h = w = 0
+  if label is not None:
+    if hw is None or len(hw) != 2 or int(hw[0]) < 1 or int(hw[1]) < 1 or int(hw[0]) * int(hw[1]) * G != M:
+      raise ValueError('%s: a label map needs hw = (h, w) with h * w * groups == M = %d, got %r' % (who, M, hw))
+    h, w = int(hw[0]), int(hw[1])
+  label = _vq_cost_label(who, label, n_classes, index.device), label
+  lb = lib()
+  n_ws = lb.jpdse_vq_index_cost_workspace_size(M, L, S, G, 0)
+  assert n_ws > 0, (M, L, S, G)
+  call = lambda a: check(lb.jpdse_vq_index_cost(ctypes.byref(VqIndexCostArgs(*a))), who)
+  return _vq_cost_run(call, n_ws, (M, L, S, G, index.data_ptr(), h, w), index, M, G, S, label, n_classes, want_symbols)
+
+
+def vq_plane_cost(index, shape, L, strip_rows=8, label=None, n_classes=0, want_symbols=False):
+  """The same for the context-coded index planes (jpdse_vq_plane_cost): the cost under the model of vq_plane_encode(index, h, w,
+  G, L, strip_rows), `shape` = (h, w, G); index: the device int32 [h * w * G] indices of ONE image.  The dict of vq_index_cost:
+  `cell` [h * w], `group` [G], the streams' tensors [ceil(h / strip_rows) * G]; stream_decisions depends on the data (flags
+  that matched save the literal).  label: device fp32 [1, 1, H, W], H / h == W / w a power of two."""
+  who = 'vq_plane_cost'
+  assert index.dim() == 1 and index.is_cuda, (tuple(index.shape), index.device)
+  if not isinstance(shape, (tuple, list)) or len(shape) != 3:
+    raise ValueError('%s: shape is (h, w, G), got %r' % (who, shape))
+  h, w, G, L, strip_rows, S = vq_plane_shape(who, shape[0], shape[1], shape[2], L, strip_rows)
+  M = h * w * G
+  _vq_index(index, M, index.device)
+  label = _vq_cost_label(who, label, n_classes, index.device), label
+  lb = lib()
+  n_ws = lb.jpdse_vq_plane_cost_workspace_size(h, w, G, L, strip_rows, 0)
+  assert n_ws > 0, (h, w, G, L, strip_rows)
+  call = lambda a: check(lb.jpdse_vq_plane_cost(ctypes.byref(VqPlaneCostArgs(*a))), who)
+  return _vq_cost_run(call, n_ws, (h, w, G, L, strip_rows, index.data_ptr()), index, M, G, S, label, n_classes, want_symbols)
 
 
 # At the end, as is the re-export at the end of ops: whichever of the two modules is imported first finds, half-way through its

@@ -35,7 +35,9 @@ With --codec, --per-class also says where the bits go: next to 
 the bits of the code attributed to the class (trainer.get_class_rates: the code length under the 4.8 coder's own adaptive
 model, a cell's bits shared evenly among the pixels it covers), its bpp (bits / pixels of the class) and its share of all
 bits.  --rate-map DIR (needs --codec) writes the map behind it, trainer.get_rate_map's float64 [h, w] bits per code cell, as
-DIR/b<batch>_i<image>.npy, and the line gains the model's bpp.
+DIR/b<batch>_i<image>.npy, and the line gains the model's bpp.  With --encoder_quantizer s2hvq the same columns and the same
+map come from trainer.get_vq_class_rates / get_vq_rate_map: the code length under the model of the coder
+whose file get_coded keeps for each image.
 """
 import argparse
 import contextlib
@@ -155,8 +157,8 @@ def main():
   vq = args.codec and args.encoder_quantizer == 's2hvq'
   if args.vq_context_coder and not vq:
     ap.error('--vq_context_coder needs --codec --encoder_quantizer s2hvq')
-  if vq and (args.roundtrip or args.rate_map):
-    ap.error('--roundtrip / --rate-map store and walk the binarizer\'s code: not available with --encoder_quantizer s2hvq '
+  if vq and args.roundtrip:
+    ap.error('--roundtrip stores the binarizer\'s code: not available with --encoder_quantizer s2hvq '
              '(trainer.get_coded / decode_coded are its files)')
   if args.roundtrip:
     os.makedirs(args.roundtrip, exist_ok=True)
@@ -259,12 +261,13 @@ def main():
       by_batch['context'] += context                   # of the coded size, not a size)
       by_image['context'] += context * b
       line += ', context-model bpp {:.4f}'.format(context)
-    if args.codec and args.per_class and not vq:
-      cr = trainer.get_class_rates(x_dict)             # bits are sums of k / 2^16: adding batches stays exact
+    if args.codec and args.per_class:
+      # bits are sums of k / 2^16: adding batches stays exact
+      cr = trainer.get_vq_class_rates(x_dict) if vq else trainer.get_class_rates(x_dict)
       class_bits = cr['bits'] if class_bits is None else class_bits + cr['bits']
     if args.rate_map:
       import numpy as np
-      rm = trainer.get_rate_map(x_dict)
+      rm = trainer.get_vq_rate_map(x_dict) if vq else trainer.get_rate_map(x_dict)
       for j in range(b):
         np.save(os.path.join(args.rate_map, 'b%04d_i%02d.npy' % (i, j)), rm['map'][j].numpy())
       model_bpp = float(rm['bpp'].mean())
@@ -347,7 +350,8 @@ def main():
       print('{:>5} {:>12} {:>7.2f}% {:>9} {:>11} {:>9}'.format('none', r['unlabelled'], 100.0 * r['unlabelled'] / total, '', '', '')
             + rate_columns(-1, r['unlabelled']))
     if class_bits is not None:
-      print('bits: the code length under the coder\'s own adaptive model (DESIGN.md 4.12), %.1f in all, %.4f bpp' % (all_bits, all_bits / total))
+      print('bits: the code length under the coder\'s own adaptive model (DESIGN.md %s), %.1f in all, %.4f bpp'
+            % ('4.20' if vq else '4.12', all_bits, all_bits / total))
     print('')
 
 
