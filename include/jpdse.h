@@ -772,6 +772,58 @@ typedef struct jpdse_vq_pmf_bwd_args {
 } jpdse_vq_pmf_bwd_args;
 int jpdse_vq_pmf_bwd(const jpdse_vq_pmf_bwd_args* args);
 
+/* ---- soft-to-hard vector quantizer: code-book fit, one Lloyd (k-means) iteration per pass (vq_fit.hip) -------
+ * x, code_book, d[m][k] and the limits are those of the quantizer above; a(m) = the nearest centre of x[m], the lowest k on a tie:
+ * the index jpdse_vq_hard_fwd gives on the same inputs.  The STATE is five device tensors the caller owns:
+ *   counts   int64 [L]     n[k] = the number of vectors with a(m) = k
+ *   sums     fp64  [L][D]  s[k][j] = the sum of x[m][j] over the members of k
+ *   sse      fp64  [L]     e[k] = the sum of the fp32 distances d[m][a(m)] over the members of k
+ *   far_dist fp32  [L]     the largest member distance of k, -1 for a centre without members
+ *   far_vec  fp32  [L][D]  the member that attains it (components converted to fp32; zeros without members); of equal distances
+ *                          the earliest: the lowest m inside a call, and an earlier call before a later one
+ *   lloyd_accum   one pass over x under a fixed code book.  first != 0 initialises the state, first == 0 adds to it (a later call
+ *                 replaces far_dist / far_vec only on a strictly greater distance): any number of batches stream through one
+ *                 iteration.  x is read once (and at most L rows once more, for far_vec); the index is never stored.  Per-block
+ *                 fp32 partials in the workspace, merged in ascending block order in fp64 into the state.
+ *   lloyd_update  the next code book from a state, in place in code_book, one block:
+ *                 n[k] > 0:  c[k][j] = (float)(s[k][j] / (double)n[k])
+ *                 n[k] == 0 and reseed: donors are the centres with n >= 2 and far_dist > 0, ranked by e descending, the lower k
+ *                 first on equal e; the i-th dead centre in ascending k takes far_vec of the i-th donor, bit for bit, while i <
+ *                 the number of donors; further dead centres, and all of them without reseed, keep c[k].  A donor keeps its mean.
+ *                 report: int32 [2] = (dead centres, reseeded centres).
+ * No atomics; every output element has one writer and every sum an order fixed by (M, D, L): two calls on the same buffers give
+ * identical bits.  ws: jpdse_vq_lloyd_workspace_size(M, D, L) bytes (host only; 0 for a shape outside the limits).
+ * JPDSE_EINVAL before any launch: a NULL args or pointer, a bad dtype, a shape outside the limits, a workspace that is missing or
+ * too small.  No call allocates, synchronises or throws. */
+size_t jpdse_vq_lloyd_workspace_size(int32_t M, int32_t D, int32_t L);
+typedef struct jpdse_vq_lloyd_accum_args {
+  int32_t dtype, M, D, L;
+  int32_t first;
+  const void* x;
+  const float* code_book;
+  int64_t* counts;         /* [L] */
+  double* sums;            /* [L][D] */
+  double* sse;             /* [L] */
+  float* far_dist;         /* [L] */
+  float* far_vec;          /* [L][D] */
+  void* ws;
+  size_t ws_bytes;
+  void* stream;
+} jpdse_vq_lloyd_accum_args;
+int jpdse_vq_lloyd_accum(const jpdse_vq_lloyd_accum_args* args);
+typedef struct jpdse_vq_lloyd_update_args {
+  int32_t D, L, reseed;
+  float* code_book;        /* [L][D], updated in place */
+  const int64_t* counts;
+  const double* sums;
+  const double* sse;
+  const float* far_dist;
+  const float* far_vec;
+  int32_t* report;         /* [2] */
+  void* stream;
+} jpdse_vq_lloyd_update_args;
+int jpdse_vq_lloyd_update(const jpdse_vq_lloyd_update_args* args);
+
 /* ---- soft-to-hard vector quantizer: coded index stream (no reference counterpart; format: DESIGN.md 4.14) ------------------
  * A lossless, order-0 adaptive L-ary range coder for the indices of the quantizer, and its decoder.  index: DEVICE int32 [M],
  * the row-major [n][code_len] code, every value in [0, L).  The M indices are dealt to S independent streams by interleaving:

@@ -130,6 +130,23 @@ int vq_pmf_bwd_check(const jpdse_vq_pmf_bwd_args* a) {
   return JPDSE_OK;
 }
 
+// jpdse_vq_lloyd_* (vq_fit.hip)
+int vq_lloyd_accum_check(const jpdse_vq_lloyd_accum_args* a) {
+  JPDSE_REQUIRE(a != nullptr, "vq_lloyd_accum: null argument struct");
+  JPDSE_REQUIRE(!bad_dtype(a->dtype), "vq_lloyd_accum: bad dtype %d", a->dtype);
+  if (int rc = vq_shape_check("vq_lloyd_accum", a->M, a->D, a->L)) return rc;
+  JPDSE_REQUIRE(a->x && a->code_book && a->counts && a->sums && a->sse && a->far_dist && a->far_vec, "vq_lloyd_accum: null pointer");
+  return vq_ws_check("vq_lloyd_accum", a->ws, a->ws_bytes, vq_lloyd_workspace_bytes(a->M, a->D, a->L));
+}
+
+int vq_lloyd_update_check(const jpdse_vq_lloyd_update_args* a) {
+  JPDSE_REQUIRE(a != nullptr, "vq_lloyd_update: null argument struct");
+  if (int rc = vq_shape_check("vq_lloyd_update", 1, a->D, a->L)) return rc;
+  JPDSE_REQUIRE(a->code_book && a->counts && a->sums && a->sse && a->far_dist && a->far_vec && a->report,
+                "vq_lloyd_update: null pointer");
+  return JPDSE_OK;
+}
+
 // jpdse_vq_index_* (vq_coder.hip): the limits, the closed forms of the sizes, and everything that can be
 // refused without a device.  nb = max(1, bit_length(L - 1)) decisions per symbol; stream s of the S holds ceil((M - s) / S)
 // symbols and its slot nb of them + 8 bytes, so the slots add up to nb M + 8 S and the capacity is that + the 4 S of the table.

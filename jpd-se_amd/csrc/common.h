@@ -34,6 +34,11 @@ int vq_decode_bwd_check(const jpdse_vq_decode_bwd_args* a);
 int vq_argmax_check(const jpdse_vq_argmax_args* a);
 int vq_pmf_check(const jpdse_vq_pmf_args* a);
 int vq_pmf_bwd_check(const jpdse_vq_pmf_bwd_args* a);
+// the code-book fit (kernels: vq_fit.hip): vq_lloyd_workspace_bytes (vq_fit.hip) is what
+// jpdse_vq_lloyd_workspace_size returns for a shape inside the limits
+size_t vq_lloyd_workspace_bytes(int M, int D, int L);
+int vq_lloyd_accum_check(const jpdse_vq_lloyd_accum_args* a);
+int vq_lloyd_update_check(const jpdse_vq_lloyd_update_args* a);
 // shared with the bottleneck and the rate term (kernels: vq_bottleneck.hip): a workspace of at least `need` bytes; dtype, shape
 // and sigma; the groups of the per-group histograms (G >= 1 divides M, G * L <= 65536)
 int vq_ws_check(const char* who, const void* ws, size_t ws_bytes, size_t need);

@@ -14,7 +14,8 @@
 //       component)) sums the tile's share of dC over the vectors ascending and adds it to the block's own fp32 partial.
 //   vq_decode_kernel / vq_decode_bwd_kernel   gather of centres; its transpose with the same per-block partials
 //   vq_pmf_partial_kernel / vq_pmf_bwd_kernel column means of [M][L], first stage, and their gradient
-//   vq_core.h (shared with vq_bottleneck.hip) the launcher, vq_weight, vq_partial_put and the two second stages: vq_merge_kernel
+//   vq_core.h (shared with vq_bottleneck.hip and vq_fit.hip) the launcher, vq_weight, vq_partial_put, the group layout and its
+//       score loop (VqLanes, vq_scores, vq_group_arg, vq_stage_transposed) and the two second stages: vq_merge_kernel
 //       (out = scale * sum_b partial[b], b ascending, fp32) and vq_pmf_final_kernel (fp64)
 // VqLanes states the group layout once (soft forward, the scores).  vq_hard_fwd_kernel, vq_argmax_kernel and vq_soft_bwd_kernel
 // spell it out as before: with the struct the first two took one more VGPR and the third ran 5% slower in fp32.
@@ -27,17 +28,11 @@
 
 namespace jpdse {
 
-constexpr int kVqSlots = 8;              // centres per lane: 512 / 64
 constexpr int kVqPartialBlocks = 512;    // cap of the blocks (= fp32 partials) of the two code-book gradients
 constexpr int kVqDecodeTile = 256;       // vectors per tile of vq_decode_bwd_kernel
 constexpr int kVqPmfBlocks = 1024;       // cap of the blocks of vq_pmf_partial_kernel
 
 // ---- launch geometry: functions of (M, D, L) alone, shared by the launchers and jpdse_vq_workspace_size -----------------
-static inline int vq_group(int L) {      // lanes per row
-  int g = 2;
-  while (g < L && g < 64) g <<= 1;
-  return g;
-}
 static inline int vq_bwd_tile(int L) {   // vectors per tile of vq_soft_bwd_kernel: dd tile [V][L + 1] of at most 24 KiB
   const int v = 6144 / (L + 1);
   return v > 64 ? 64 : v;
@@ -68,68 +63,9 @@ size_t vq_workspace_bytes(int M, int D, int L) {
 }
 
 // ---- device helpers ---------------------------------------------------------------------------------------------------------
-// c [L][D] (global) -> ct [D][L] (LDS); the caller synchronises
-__device__ __forceinline__ void vq_stage_transposed(const float* __restrict__ c, float* ct, int D, int L) {
-  for (int i = threadIdx.x; i < L * D; i += 256) {
-    const int k = i / D, j = i - k * D;
-    ct[j * L + k] = c[i];
-  }
-}
-
-// The group layout of a row of [M][L] (the header): this lane is lane kk of group g of its wave and owns the centres
-// centre(i) = kk + 64 i of the slots i with slot_live(i).  Grid-stride over rows: a wave covers the vpw vectors from `base`,
-//   for (long long base = ln.first(); base < M; base += ln.stride()) { const int m = ln.vector(base, M); .. }
-struct VqLanes {
-  int lane, wave, kk, g, vpw, ni, L;
-  __device__ __forceinline__ VqLanes(int G, int L_)
-      : lane(threadIdx.x & 63), wave(threadIdx.x >> 6), kk(lane & (G - 1)), g(lane / G), vpw(64 / G), ni((L_ + 63) >> 6), L(L_) {}
-  __device__ __forceinline__ int centre(int i) const { return kk + 64 * i; }
-  __device__ __forceinline__ bool slot_live(int i) const { return i < ni && kk + 64 * i < L; }
-  __device__ __forceinline__ long long first() const { return (long long)(blockIdx.x * 4 + wave) * vpw; }
-  __device__ __forceinline__ long long stride() const { return (long long)gridDim.x * 4 * vpw; }
-  // this group's vector; an idle group (live false) repeats the last vector and stores nothing
-  __device__ __forceinline__ bool live(long long base, int M) const { return base + g < M; }
-  __device__ __forceinline__ int vector(long long base, int M) const { return live(base, M) ? (int)(base + g) : M - 1; }
-};
-
-// the scores of vector m against this lane's centres; slots beyond L stay 0 and are never read
-template <typename T>
-__device__ __forceinline__ void vq_scores(const T* __restrict__ x, const float* ct, int m, int D, const VqLanes& ln,
-                                          float (&d)[kVqSlots]) {
-#pragma unroll
-  for (int i = 0; i < kVqSlots; ++i) d[i] = 0.f;
-  const T* xr = x + (size_t)m * D;
-  for (int j = 0; j < D; ++j) {
-    const float xv = ElemOps<T>::ld(xr + j);
-    const float* row = ct + j * ln.L;
-#pragma unroll
-    for (int i = 0; i < kVqSlots; ++i)
-      if (ln.slot_live(i)) {
-        const float t = xv - row[ln.centre(i)];
-        d[i] += t * t;
-      }
-  }
-}
-
 __device__ __forceinline__ float vq_group_sum(float v, int G) {
   for (int off = G >> 1; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
-}
-
-// (value, index) butterfly: the smaller value wins (LESS) or the larger (!LESS), the lower index on equal values.  A NaN
-// never wins a comparison, and the sentinel index of a lane without a centre is larger than any real one, so group lane 0
-// ends with an index of a real centre whatever the values are.
-template <bool LESS>
-__device__ __forceinline__ void vq_group_arg(float& v, int& k, int G) {
-  for (int off = G >> 1; off > 0; off >>= 1) {
-    const float ov = __shfl_xor(v, off, 64);
-    const int ok = __shfl_xor(k, off, 64);
-    const bool better = LESS ? ov < v : ov > v;
-    if (better || (ov == v && ok < k)) {
-      v = ov;
-      k = ok;
-    }
-  }
 }
 
 // ---- forward ----------------------------------------------------------------------------------------------------------------

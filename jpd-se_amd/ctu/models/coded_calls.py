@@ -105,6 +105,42 @@ class CodedCalls(object):
       value = self._encoder_eval(lambda: self.netE.vq_rate(src, src.N * src.H * src.W))
       return float(value.item())
 
+  def get_vq_usage(self, x_dict):
+    """int64 [G, L] on the device: how often the eval-mode code get_vq_code(x_dict) uses each of the L centres, per channel group
+    (G = C / D), counted over the batch (ops.vq_rate_fwd, hard, its histogram).  A column of zeros is a dead centre: what
+    fit_vq_code_book repairs.  Every row sums to the indices per group, N h w."""
+    self._vq_codec('get_vq_usage')
+    with torch.no_grad():
+      pre = self.preprocess(x_dict, build_base=False)
+      src = pre['src']
+      hist = self._encoder_eval(lambda: self.netE.vq_usage(src))
+      return hist.to(torch.int64)          # sums of ones in fp32: exact while a count stays below 2^24
+
+  def fit_vq_code_book(self, x_dicts, n_iter=10, init='sample', seed=0, reseed=True):
+    """Fit the vector quantizer's code book to the encoder's own features of a list of batches: the encoder
+    runs once per batch in eval mode under no_grad, the [M, D] feature matrices (fp32 or bf16 following --compute_dtype) stay on
+    the device, and S2HVQ.fit runs n_iter Lloyd iterations over all of them, in place in the code book -- the optimizer and the
+    gradient buckets keep their pointers.  Arguments and the returned report (distortion, dead, reseeded, counts) are
+    S2HVQ.fit's.  Several ranks: the fit is deterministic and adds no collective; every rank that calls it with the same batches
+    gets the same bits, so call it on every rank with the same list (or broadcast the book afterwards).
+    ValueError before any device work: without --encoder_quantizer s2hvq, with --zero_vis (the encoder does not run), for an
+    empty list, and for the arguments S2HVQ.fit refuses."""
+    self._vq_codec('fit_vq_code_book')
+    if self.zero_vis:
+      raise ValueError('fit_vq_code_book: with --zero_vis the encoder does not run, there are no features to fit')
+    if not isinstance(x_dicts, (list, tuple)) or len(x_dicts) == 0:
+      raise ValueError('fit_vq_code_book: expected a non-empty list of batches (x_dict)')
+    if isinstance(n_iter, bool) or not isinstance(n_iter, int) or n_iter < 0:
+      raise ValueError('n_iter must be an int >= 0, got {!r}'.format(n_iter))
+    if init not in ('sample', 'current'):
+      raise ValueError("init must be 'sample' or 'current', got {!r}".format(init))
+    with torch.no_grad():
+      def features(x_dict):
+        src = self.preprocess(x_dict, build_base=False)['src']
+        return self.netE.vq_features(src)
+      mats = self._encoder_eval(lambda: [features(x_dict) for x_dict in x_dicts])
+      return self.netE._vq.fit(mats, n_iter=n_iter, init=init, seed=seed, reseed=reseed)
+
   def _decode_act(self, code, x_dict):
     """decode() up to the generator's NHWC output; also returns the device label map."""
     codec = self.codec or self._binary_codec()

@@ -331,6 +331,19 @@ class Encoder(nn.Module):
     h, _ = run_chain_fwd(self._pre, x)
     return vq.code(h)
 
+  def vq_features(self, x):
+    """The [M, D] matrix the bottleneck's quantizer sees for x (M = N h w cout / D, vector m = pixel * (cout / D) + group): what
+    vq_code assigns and what the code-book fit of DESIGN.md 4.21 runs on."""
+    vq = self._require_vq()
+    h, _ = run_chain_fwd(self._pre, x)
+    return vq.features(h)
+
+  def vq_usage(self, x):
+    """fp32 [cout / D, n_center]: the histogram of vq_code(x) per channel group over the batch."""
+    vq = self._require_vq()
+    h, _ = run_chain_fwd(self._pre, x)
+    return vq.usage(h)
+
   def vq_rate(self, x, denom):
     """fp32 [1]: the zero-order entropy of vq_code(x) per channel group over the batch, in bits / denom."""
     vq = self._require_vq()

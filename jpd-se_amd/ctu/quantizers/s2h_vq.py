@@ -173,6 +173,13 @@ class S2HVQ(nn.Module):
 
   def _vectors(self, x, code_len):
     """[n, d] -> the contiguous [n * code_len, center_size] matrix of vectors, after every check that needs no device."""
+    self._vector_checks(x, code_len)
+    _on_gpu(x, 'x')
+    _on_gpu(self.code_book, 'the code book')
+    return x.contiguous().view(x.size(0) * code_len, self._center_size)
+
+  def _vector_checks(self, x, code_len):
+    """The checks of _vectors that need no device."""
     if x.size(1) < code_len:
       raise ValueError("x.size(1) must be greater than or equal to code_len, got "
                        "{} and {}, respectively".format(x.size(1), code_len))
@@ -184,9 +191,6 @@ class S2HVQ(nn.Module):
     if x.dtype not in (torch.float32, torch.bfloat16):
       raise NotImplementedError('S2HVQ: x is %s, the kernels take float32 and bfloat16' % (x.dtype,))
     _rows_limit(x.size(0) * code_len, self.code_book.size(0))
-    _on_gpu(x, 'x')
-    _on_gpu(self.code_book, 'the code book')
-    return x.contiguous().view(x.size(0) * code_len, self._center_size)
 
   def encode(self, x, code_len, train=True, raw=True):
     """x [n, d], code_len dividing d with d // code_len == center_size.  raw: the scores over the centres, [n, code_len,
@@ -241,6 +245,60 @@ class S2HVQ(nn.Module):
     value, _, _ = ops.vq_rate_fwd(xm.detach(), self.code_book.detach().contiguous(), float(self._sigma), groups, denom,
                                   hard=bool(hard), want_grad=False)
     return value.reshape(())
+
+  def fit(self, x, code_len, n_iter=10, init='sample', seed=0, reseed=True):
+    """Fit the code book to data by Lloyd (k-means) iterations on the device.  x: a tensor [n, d] or a list of
+    such tensors (batches), each checked as encode checks it; every iteration accumulates all of them under the current book
+    (ops.vq_lloyd_accum: one fused pass per tensor) and then moves every centre to the mean of its members
+    (ops.vq_lloyd_update).  reseed: a centre without members takes the farthest member of the centre with the largest summed
+    distance (one donor per dead centre, donors need two members); without it such a centre stays where it is.
+    init: 'current' starts from the book as it is; 'sample' first sets it to n_center distinct vectors of the first tensor, rows
+    torch.randperm(M, generator=<CPU generator seeded with `seed`>)[:n_center] of its [M, center_size] matrix (ValueError when
+    M < n_center).  Deterministic: the same arguments give the same bits, on every device and rank.
+    Runs under no_grad and writes `_code_book` IN PLACE: same storage (the fused Adam and the gradient buckets keep their
+    pointer), requires_grad and .grad untouched.  After the last update one more pass measures the fitted book.  Returns a dict:
+    `distortion`, n_iter + 1 Python floats, the mean squared distance of a vector to its nearest centre -- entry t under the
+    book before update t, the last under the fitted book; `dead` and `reseeded`, n_iter ints each: the centres without members
+    at update t and how many of them were reseeded; `counts`, int64 [n_center] on the device: the members under the fitted
+    book.  The statistics are read back once, at the end."""
+    if isinstance(n_iter, bool) or not isinstance(n_iter, int) or n_iter < 0:
+      raise ValueError('n_iter must be an int >= 0, got {!r}'.format(n_iter))
+    if init not in ('sample', 'current'):
+      raise ValueError("init must be 'sample' or 'current', got {!r}".format(init))
+    xs = list(x) if isinstance(x, (list, tuple)) else [x]
+    if len(xs) == 0:
+      raise ValueError('x must be a tensor [n, d] or a non-empty list of such tensors')
+    for t in xs:
+      if not torch.is_tensor(t) or t.dim() != 2 or t.size(0) < 1:
+        raise ValueError('x must be a tensor [n, d] with n >= 1 or a list of such tensors, got {}'.format(
+            tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+      self._vector_checks(t, code_len)
+    L, D = int(self.code_book.size(0)), self._center_size
+    if init == 'sample' and xs[0].size(0) * code_len < L:
+      raise ValueError("init='sample' draws n_center = {} distinct vectors from the first tensor, which has {}".format(
+          L, xs[0].size(0) * code_len))
+    with torch.no_grad():
+      mats = [self._vectors(t, code_len).detach() for t in xs]
+      book = self._code_book.data
+      if not book.is_contiguous() or any(m.device != book.device for m in mats):
+        raise ValueError('S2HVQ.fit: the code book must be contiguous and on the device of x')
+      if init == 'sample':
+        pick = torch.randperm(mats[0].size(0), generator=torch.Generator().manual_seed(int(seed)))[:L]
+        book.copy_(mats[0].index_select(0, pick.to(book.device)).to(torch.float32))
+      total = float(sum(m.size(0) for m in mats))
+      state = ops.vq_lloyd_state(L, D, book.device)
+      distortion, reports = [], []
+      for it in range(n_iter + 1):
+        for i, m in enumerate(mats):
+          ops.vq_lloyd_accum(m, book, state, first=(i == 0))
+        distortion.append(state['sse'].sum() / total)
+        if it < n_iter:
+          reports.append(ops.vq_lloyd_update(book, state, reseed=bool(reseed)))
+      counts = state['counts'].clone()
+      distortion = torch.stack(distortion).cpu().tolist()
+      reports = torch.stack(reports).cpu().tolist() if reports else []
+    return dict(distortion=[float(v) for v in distortion], dead=[int(r[0]) for r in reports],
+                reseeded=[int(r[1]) for r in reports], counts=counts)
 
   def decode(self, code_raw):
     """code_raw [n, code_len, n_center] (e.g. encode(..., raw=True)) -> [n, code_len * center_size]: the centre with the highest

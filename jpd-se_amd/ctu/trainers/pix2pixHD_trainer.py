@@ -147,6 +147,20 @@ class Pix2PixHDTrainer(BaseTrainer):
     self.eval()
     return self.model.get_vq_rate(x_dict)
 
+  def get_vq_usage(self, x_dict):
+    """int64 [G, L] on the device: how often the eval-mode vector-quantised code of x_dict uses each centre, per channel group
+    (extension).  A zero column is a dead centre."""
+    self.eval()
+    return self.model.get_vq_usage(x_dict)
+
+  def fit_vq_code_book(self, x_dicts, n_iter=10, init='sample', seed=0, reseed=True):
+    """Fit the vector quantizer's code book to the encoder's features of a list of batches by k-means on the device, dead
+    centres reseeded (extension): Pix2PixHDModel.fit_vq_code_book.  In place -- the optimizer keeps working on
+    the same tensor; deterministic and without a collective: call it on every rank with the same batches.  Returns the report
+    dict (distortion, dead, reseeded, counts)."""
+    self.eval()
+    return self.model.fit_vq_code_book(x_dicts, n_iter=n_iter, init=init, seed=seed, reseed=reseed)
+
   def get_eval_rate(self, x_dict):
     """(Shannon bpp in nats as the reference computes it, raw bpp) of the learned codec (pix2pixHD_trainer.py:106-110)."""
     self.eval()

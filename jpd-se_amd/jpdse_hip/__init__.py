@@ -208,6 +208,18 @@ class VqQuantizeBwdGroupedArgs(ctypes.Structure):
               ('ws_bytes', ctypes.c_size_t), ('stream', ctypes.c_void_p)]
 
 
+# the code-book fit (vq_fit.hip)
+class VqLloydAccumArgs(ctypes.Structure):
+  _fields_ = [(n, ctypes.c_int32) for n in ('dtype', 'M', 'D', 'L', 'first')] + \
+             [(n, ctypes.c_void_p) for n in ('x', 'code_book', 'counts', 'sums', 'sse', 'far_dist', 'far_vec', 'ws')] + \
+             [('ws_bytes', ctypes.c_size_t), ('stream', ctypes.c_void_p)]
+
+
+class VqLloydUpdateArgs(ctypes.Structure):
+  _fields_ = [(n, ctypes.c_int32) for n in ('D', 'L', 'reseed')] + \
+             [(n, ctypes.c_void_p) for n in ('code_book', 'counts', 'sums', 'sse', 'far_dist', 'far_vec', 'report', 'stream')]
+
+
 _P, _I32, _I64, _F, _SZ = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float,
                            ctypes.c_size_t)
 _CD, _ND = ctypes.POINTER(ConvDesc), ctypes.POINTER(InormDesc)
@@ -322,6 +334,9 @@ SIGNATURES = {
     'jpdse_vq_argmax': (_I32, [ctypes.POINTER(VqArgmaxArgs)]),
     'jpdse_vq_pmf': (_I32, [ctypes.POINTER(VqPmfArgs)]),
     'jpdse_vq_pmf_bwd': (_I32, [ctypes.POINTER(VqPmfBwdArgs)]),
+    'jpdse_vq_lloyd_workspace_size': (_SZ, [_I32, _I32, _I32]),
+    'jpdse_vq_lloyd_accum': (_I32, [ctypes.POINTER(VqLloydAccumArgs)]),
+    'jpdse_vq_lloyd_update': (_I32, [ctypes.POINTER(VqLloydUpdateArgs)]),
     'jpdse_vq_index_capacity': (_SZ, [_I32, _I32, _I32]),
     'jpdse_vq_index_workspace_size': (_SZ, [_I32, _I32, _I32]),
     'jpdse_vq_index_encode': (_I32, [ctypes.POINTER(VqIndexEncodeArgs)]),

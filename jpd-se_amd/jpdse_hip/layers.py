@@ -429,6 +429,23 @@ class HipVQBottleneck(nn.Module):
                                   hard=True, want_grad=False)
     return value
 
+  def features(self, x):
+    """The 1x1 conv's output as the [M, D] matrix the quantizer sees (the layout above; a view, in the layer's dtype)."""
+    h, _ = self.conv.fwd(x)
+    return h.t.view(-1, self.center_size)
+
+  def usage(self, x):
+    """fp32 [groups, n_center]: how many vectors of x's features have each centre as their nearest, per channel group
+    (ops.vq_rate_fwd, hard: the histogram of code(x))."""
+    _, hist, _ = ops.vq_rate_fwd(self.features(x), self._book().detach(), self.vq.sigma, self.groups, 1.0, hard=True,
+                                 want_hist=True, want_grad=False)
+    return hist
+
+  def fit(self, feature_matrices, n_iter=10, init='sample', seed=0, reseed=True):
+    """Fit the code book to feature matrices as features() returns them (a list of [M, D] tensors): S2HVQ.fit with code_len 1
+    (DESIGN.md 4.21).  In place: the book's storage, requires_grad and .grad stay."""
+    return self.vq.fit(feature_matrices, 1, n_iter=n_iter, init=init, seed=seed, reseed=reseed)
+
   def code(self, x):
     """int32 [N, h * w * cout / D]: the index of the nearest centre of every vector of x's features, in the layout above."""
     h, _ = self.conv.fwd(x)

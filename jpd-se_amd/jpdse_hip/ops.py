@@ -11,7 +11,7 @@ import torch
 
 from . import (lib, check, JpdseError, F32, BF16, ConvDesc, InormDesc, EvalMetricsSemArgs, MsssimLossArgs, CodeRateArgs, SemLossArgs, CodeCostArgs, ACT_NONE, PAD_ZERO, PAD_REFLECT)
 from . import (VqSoftFwdArgs, VqHardFwdArgs, VqSoftBwdArgs, VqDecodeArgs, VqDecodeBwdArgs, VqArgmaxArgs, VqPmfArgs, VqPmfBwdArgs,
-               VqQuantizeFwdArgs, VqQuantizeBwdArgs, VqRateFwdArgs, VqQuantizeBwdGroupedArgs)
+               VqQuantizeFwdArgs, VqQuantizeBwdArgs, VqRateFwdArgs, VqQuantizeBwdGroupedArgs, VqLloydAccumArgs, VqLloydUpdateArgs)
 
 
 def cpad(c):
@@ -938,6 +938,59 @@ def vq_pmf_bwd(dpmf, M):
   args = VqPmfBwdArgs(int(M), L, dpmf.data_ptr(), ds.data_ptr(), torch.cuda.current_stream().cuda_stream)
   check(lib().jpdse_vq_pmf_bwd(ctypes.byref(args)), 'vq_pmf_bwd')
   return ds
+
+
+# ---- code-book fit (vq_fit.hip): one Lloyd iteration per pass over the vectors ----------------------------------
+VQ_LLOYD_STATE = (('counts', torch.int64, False), ('sums', torch.float64, True), ('sse', torch.float64, False),
+                  ('far_dist', torch.float32, False), ('far_vec', torch.float32, True))      # (name, dtype, [L, D] or [L])
+
+
+def vq_lloyd_state(L, D, device):
+  """The running state of one Lloyd iteration, a dict of five device tensors: counts int64 [L], sums float64
+  [L, D], sse float64 [L], far_dist float32 [L], far_vec float32 [L, D].  Uninitialised: vq_lloyd_accum(first=True) fills it."""
+  L, D = int(L), int(D)
+  assert 1 <= D <= VQ_MAX_D and 2 <= L <= VQ_MAX_L, (L, D)
+  return {name: torch.empty((L, D) if wide else (L,), dtype=dt, device=device) for name, dt, wide in VQ_LLOYD_STATE}
+
+
+def _vq_lloyd_state_check(state, L, D, dev):
+  assert isinstance(state, dict) and set(state) == {name for name, _, _ in VQ_LLOYD_STATE}, 'state: what vq_lloyd_state returns'
+  for name, dt, wide in VQ_LLOYD_STATE:
+    t = state[name]
+    assert t.dtype == dt and t.is_contiguous() and tuple(t.shape) == ((L, D) if wide else (L,)) and t.device == dev, \
+        (name, t.dtype, tuple(t.shape), str(t.device))
+
+
+def vq_lloyd_accum(x, code_book, state, first):
+  """One pass of x [M, D] (fp32 or bf16) under the fixed code_book fp32 [L, D] into `state` (jpdse_vq_lloyd_accum): per centre the
+  number of vectors nearest to it (ops.vq_hard_fwd's assignment), their sum, the sum of their distances and the farthest of
+  them.  first: initialise the state; otherwise add to it -- any number of batches stream through one iteration.  Returns state."""
+  M, D, L = _vq_dims(x, code_book)
+  assert x.dtype in (torch.float32, torch.bfloat16), x.dtype
+  _vq_lloyd_state_check(state, L, D, x.device)
+  ws = workspace(max(lib().jpdse_vq_lloyd_workspace_size(M, D, L), 1), x.device)
+  args = VqLloydAccumArgs(code_of(x.dtype), M, D, L, 1 if first else 0, x.data_ptr(), code_book.data_ptr(),
+                          state['counts'].data_ptr(), state['sums'].data_ptr(), state['sse'].data_ptr(),
+                          state['far_dist'].data_ptr(), state['far_vec'].data_ptr(), ws.data_ptr(), ws.numel(),
+                          torch.cuda.current_stream().cuda_stream)
+  check(lib().jpdse_vq_lloyd_accum(ctypes.byref(args)), 'vq_lloyd_accum')
+  return state
+
+
+def vq_lloyd_update(code_book, state, reseed=True):
+  """The next code book from `state`, written IN PLACE into code_book fp32 [L, D] (jpdse_vq_lloyd_update): a centre with members
+  moves to their mean; with reseed the i-th centre without members takes the farthest member of the i-th donor (centres with at
+  least two members and a positive farthest distance, by summed distance descending), the others stay.  Returns the int32 [2]
+  device tensor (dead centres, reseeded centres)."""
+  assert code_book.dim() == 2 and code_book.dtype == torch.float32 and code_book.is_contiguous(), (code_book.dtype, tuple(code_book.shape))
+  L, D = int(code_book.shape[0]), int(code_book.shape[1])
+  _vq_lloyd_state_check(state, L, D, code_book.device)
+  report = torch.empty(2, dtype=torch.int32, device=code_book.device)
+  args = VqLloydUpdateArgs(D, L, 1 if reseed else 0, code_book.data_ptr(), state['counts'].data_ptr(), state['sums'].data_ptr(),
+                           state['sse'].data_ptr(), state['far_dist'].data_ptr(), state['far_vec'].data_ptr(), report.data_ptr(),
+                           torch.cuda.current_stream().cuda_stream)
+  check(lib().jpdse_vq_lloyd_update(ctypes.byref(args)), 'vq_lloyd_update')
+  return report
 
 
 # ---- vector-quantizer bottleneck (vq_bottleneck.hip; DESIGN.md 4.15): the quantizer in one call, no [M, L] matrix ------------

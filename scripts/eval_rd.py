@@ -249,6 +249,9 @@ def main():
       # the per-group zero-order entropy of the same code over the batch: an estimate, not a size, and on
       # either side of the coded figure (the coder adapts per image and pays headers and flushes)
       line += ', per-group entropy bpp {:.4f}'.format(trainer.get_vq_rate(x_dict))
+      # the centres each channel group's code uses at all: a count below n_center means dead centres
+      used = (trainer.get_vq_usage(x_dict) > 0).sum(dim=1).tolist()
+      line += ', centres in use per group {}'.format('/'.join(str(int(u)) for u in used))
     elif args.codec:
       shannon, actual = trainer.get_eval_rate(x_dict)
       shannon = float(shannon)
