@@ -6,11 +6,12 @@
 // The cost of a symbol coded with the probability q of bit 0 is T[q] (bit 0) or T[2048 - q] (bit 1), T[v] =
 // round(-log2(v / 2048) * 2^16): an integer, in units of 2^-16 bit.  T is built once on the host in fp64
 // (jpdse_code_cost_table, api.cpp) and copied into the call's workspace.  Kernels, in launch order:
-//   cost_walk_kernel    the serial walk of entropy_encode_kernel (entropy.hip): lane = channel, one wave per block, grid
-//                       (ceil(C / 64), N), the lane's 16 probabilities and the bits of its previous row in LDS columns of its
-//                       own, wave-uniform loops.  Instead of coding the symbol the lane looks its cost up (T sits in LDS,
-//                       8.2 KB, loaded by the whole wave) and stores it: the 64 lanes write 64 neighbouring channels of one
-//                       cell.  The lane's running sum stays in a register and is written once, to channel[n][c].
+//   cost_walk_kernel    entropy_encode_kernel's walk itself (code_walk, range_coder.h) with the pricing sink (CostPricer,
+//                       cost_class.h) in the encoder's place: lane = channel, one wave per block, grid (ceil(C / 64), N), the
+//                       lane's 16 probabilities and the bits of its previous row in LDS columns of its own, wave-uniform
+//                       loops.  The sink looks a symbol's cost up (T sits in LDS, 8.2 KB, loaded by the whole wave) and
+//                       stores it: the 64 lanes write 64 neighbouring channels of one cell.  The lane's running sum stays
+//                       in a register and is written once, to channel[n][c].  This file holds no model loop of its own.
 //   cost_cell_kernel    (cost_class.h) 16 lanes per cell add its C costs: cell[n][y][x].
 //   cost_class_kernel   (cost_class.h; with a label map) a fixed grid, grid-stride over the pixels of an image: per block an LDS histogram
 //                       of (n_classes + 1) x {units, pixels} filled with 64-bit LDS atomics, flushed with 64-bit global
@@ -37,43 +38,16 @@ __global__ void __launch_bounds__(64) cost_walk_kernel(const T* __restrict__ b, 
                                                        int H, int W, int C, int Cs) {
   extern __shared__ uint32_t lds[];
   const int lane = threadIdx.x, c = blockIdx.x * 64 + lane, n = blockIdx.y;
-  for (int i = lane; i < kCostTable; i += 64) lds[i] = table[i];
-  __syncthreads();                              // the one cross-lane step: the whole wave is still here
+  cost_table_stage(lds, table, lane);
   if (c >= C) return;                           // before the code is read or anything is written
-  const uint32_t* cost = lds;
   uint32_t* prob = lds + kCostTableWords + lane;                // [16][64]
   uint32_t* row = lds + kCostTableWords + 16 * 64 + lane;       // [nw][64]: the bits of the row above, as in entropy.hip
   const int nw = (W + 31) >> 5;
   for (int k = 0; k < 16; ++k) prob[k * 64] = kProbInit;
   for (int j = 0; j < nw; ++j) row[j * 64] = 0;
-  const T* src = b + (long long)n * H * W * Cs + c;
-  uint32_t* dst = symbol + (long long)n * H * W * C + c;
-  unsigned long long total = 0;
-
-  for (int y = 0; y < H; ++y) {
-    uint32_t upw = row[0], left = 0, ul = 0;
-    for (int j = 0; j < nw; ++j) {
-      const uint32_t nextw = j + 1 < nw ? row[(j + 1) * 64] : 0u;
-      const uint32_t urw = (upw >> 1) | (nextw << 31);
-      const int kmax = min(32, W - 32 * j);
-      const long long at = (long long)y * W + 32 * j;
-      const uint32_t inw = load_bit_word(src + at * Cs, Cs, kmax);
-      for (int k = 0; k < kmax; ++k) {
-        const uint32_t bit = (inw >> k) & 1u, up = (upw >> k) & 1u;
-        uint32_t& p = prob[context_of(left, up, ul, (urw >> k) & 1u) * 64];
-        const uint32_t q = p;
-        p = adapted(q, bit);
-        const uint32_t units = cost[bit ? kProbOne - q : q];
-        dst[(at + k) * C] = units;
-        total += units;
-        ul = up;
-        left = bit;
-      }
-      row[j * 64] = inw;                        // bits beyond W stay 0
-      upw = nextw;
-    }
-  }
-  channel[(long long)n * C + c] = total;
+  const CostPricer pr = code_walk(b + (long long)n * H * W * Cs + c, prob, row, H, W, Cs,
+                                  CostPricer{lds, symbol + (long long)n * H * W * C + c, C});
+  channel[(long long)n * C + c] = pr.total;
 }
 
 }  // namespace jpdse

@@ -1,9 +1,9 @@
-// What the code-length maps share (code_cost.hip: DESIGN.md 4.12; vq_cost.hip: 4.20): the LDS footprint of the cost table T,
-// the kernel that adds the per-symbol costs of a cell, and the attribution of the cell map to the semantic classes -- ONE
-// statement of the class rule and of its kernel for the binarizer's code and for the vector quantizer's.  The limits of the
-// label path and its argument checks are api.cpp's (cost_label_check, common.h).
+// What the code-length maps share (code_cost.hip: DESIGN.md 4.12; vq_cost.hip: 4.20): the cost table T in LDS, the sink that
+// prices the decisions of a coder's model walk, the kernel that adds the per-symbol costs of a cell, and the attribution of
+// the cell map to the semantic classes -- ONE statement of the class rule and of its kernel for the binarizer's code and for
+// the vector quantizer's.  The limits of the label path and its argument checks are api.cpp's (cost_label_check, common.h).
 #pragma once
-#include "common.h"
+#include "range_coder.h"
 
 namespace jpdse {
 
@@ -12,6 +12,36 @@ constexpr int kCostTableWords = 33 * 64;         // its LDS footprint: the next 
 constexpr int kCostClassBlocks = 128;            // blocks per image of the class kernel
 
 static inline size_t cost_table_bytes() { return align_up(kCostTable * sizeof(uint32_t), 256); }
+
+// T into LDS: the one cross-lane step of a cost kernel, taken by the whole wave before any lane leaves
+__device__ __forceinline__ void cost_table_stage(uint32_t* cost, const uint32_t* __restrict__ table, int lane) {
+  for (int i = lane; i < kCostTable; i += 64) cost[i] = table[i];
+  __syncthreads();
+}
+
+// The sink that prices (range_coder.h: model walks and their sinks): a decision with the probability q of bit 0 costs T[q]
+// (bit 0) or T[2048 - q] (bit 1) and adapts its word as the coder does; a symbol costs the sum over its decisions, stored at
+// symbol[at * stride].  total, count: the stream's units and decisions, kept in registers.
+struct CostPricer {
+  const uint32_t* cost;                          // T, in LDS
+  uint32_t* symbol;
+  int stride;
+  uint32_t sym = 0, count = 0;
+  unsigned long long total = 0;
+
+  template <typename P>
+  __device__ __forceinline__ void put(P& p, uint32_t bit) {
+    const uint32_t q = p;
+    p = (P)adapted(q, bit);
+    sym += cost[bit ? kProbOne - q : q];
+    ++count;
+  }
+  __device__ __forceinline__ void symbol_done(long long at) {
+    symbol[at * stride] = sym;
+    total += sym;
+    sym = 0;
+  }
+};
 
 // cell[i] = the sum of the C costs of cell i < cells; 16 lanes per cell, every lane of a wave makes the same number of trips
 static __global__ void __launch_bounds__(256) cost_cell_kernel(const uint32_t* __restrict__ symbol, unsigned long long* __restrict__ cell,

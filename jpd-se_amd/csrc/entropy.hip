@@ -3,8 +3,9 @@
 // include/jpdse.h, "learned codec: entropy-coded bitstream".
 //
 // Every (image, channel) pair is one independent stream of H*W symbols (bit = b > 0, raster order) with its own 16 adaptive
-// probabilities, selected by the four already-coded neighbours.  The coder core, the payload layout and the context rule are
-// range_coder.h's; this file is the walk over the code tensor.  The work of one stream is serial, so one LANE codes one
+// probabilities, selected by the four already-coded neighbours.  The coder core, the payload layout, the context rule and the
+// encoder's walk over a stream (code_walk, shared with the cost map of code_cost.hip) are range_coder.h's; this file is the
+// kernels around them and the decoder's loop.  The work of one stream is serial, so one LANE codes one
 // stream and lane = channel -- the 64 lanes of a wave read (or write) 64 neighbouring channels of one pixel of the NHWC
 // tensor.  All streams of a call have the same H and W: the loops over y and x are wave-uniform, only the byte output
 // (encoder) / input (decoder) diverges.  A lane's probability table and the bits of its previous row (32 per word) live in
@@ -43,25 +44,7 @@ __global__ void __launch_bounds__(64) entropy_encode_kernel(const T* __restrict_
   const T* src = b + (long long)n * H * W * Cs + c;
   RcEncoder rc;
   rc.init(slots + ((long long)n * C + c) * scap, scap);
-
-  for (int y = 0; y < H; ++y) {
-    uint32_t upw = row[0], left = 0, ul = 0;
-    for (int j = 0; j < nw; ++j) {
-      const uint32_t nextw = j + 1 < nw ? row[(j + 1) * 64] : 0u;
-      const uint32_t urw = (upw >> 1) | (nextw << 31);
-      const int kmax = min(32, W - 32 * j);
-      // the word's 32 input symbols before any of them is coded
-      const uint32_t inw = load_bit_word(src + ((long long)y * W + 32 * j) * Cs, Cs, kmax);
-      for (int k = 0; k < kmax; ++k) {
-        const uint32_t bit = (inw >> k) & 1u, up = (upw >> k) & 1u;
-        rc.encode(prob[context_of(left, up, ul, (urw >> k) & 1u) * 64], bit);
-        ul = up;
-        left = bit;
-      }
-      row[j * 64] = inw;                        // bits beyond W stay 0
-      upw = nextw;
-    }
-  }
+  rc = code_walk(src, prob, row, H, W, Cs, rc);
   lens[(long long)n * C + c] = rc.finish();
 }
 

@@ -1,8 +1,14 @@
 // The coder core of entropy.hip, shared in parts with semantics.hip, code_rate.hip and code_cost.hip: the
 // binary range coder of LZMA (the "rc" scheme; I. Pavlov, LZMA SDK, public domain; 11-bit probabilities of bit 0, shift 5), the payload
 // layout -- a table of little-endian uint32 stream lengths, then the streams -- as the encoders write it and as the decoders
-// read it from data they do not trust, and the context rule of the code tensor's streams.  The modelling (which decision in
-// which context) stays with each source.  Device code only; plain C++ loads and stores.
+// read it from data they do not trust, and the model of the code tensor's streams: the context rule and the walk over a stream
+// (code_walk) that entropy.hip codes with and code_cost.hip prices with.  The models of the other sources stay with them
+// (the index coders: vq_model.h).  Device code only; plain C++ loads and stores.
+//
+// A model walk is a function template over a SINK: it visits the decisions of a stream in coding order and hands each one to
+// sink.put(p, bit) -- p: the decision's adaptive probability word in the lane's LDS column, which put updates -- and the end
+// of each symbol to sink.symbol_done(at), at: the symbol's position in the walked tensor.  RcEncoder is the sink that codes;
+// CostPricer (cost_class.h) is the one that prices.
 #pragma once
 #include "common.h"
 
@@ -12,8 +18,8 @@ constexpr uint32_t kTop = 1u << 24;
 constexpr uint32_t kProbInit = 1024, kProbOne = 2048;
 constexpr int kMoveBits = 5;
 
-// The adaptive probability of bit 0 after `bit` was coded with q -- the ONE statement of the update the coder, the decoder
-// and the cost walk of code_cost.hip share.
+// The adaptive probability of bit 0 after `bit` was coded with q -- the ONE statement of the update the coders, the decoders
+// and the pricing sink share.
 __device__ __forceinline__ uint32_t adapted(uint32_t q, uint32_t bit) {
   return bit ? q - (q >> kMoveBits) : q + ((kProbOne - q) >> kMoveBits);
 }
@@ -69,6 +75,11 @@ struct RcEncoder {
     p = adapted(q, bit);
     split((range >> 11) * q, bit);
   }
+  // as the sink of a model walk.  A halfword of the index coders' columns is widened around the decision: its store stays
+  // behind the byte emission, where those encoders have always had it
+  __device__ __forceinline__ void put(uint32_t& p, uint32_t bit) { encode(p, bit); }
+  __device__ __forceinline__ void put(uint16_t& p, uint32_t bit) { uint32_t q = p; encode(q, bit); p = (uint16_t)q; }
+  __device__ __forceinline__ void symbol_done(long long) {}
   // the flush; returns the bytes the stream needs, or scap + 1 when they are more than scap
   __device__ __forceinline__ int finish() {
     for (int k = 0; k < 5; ++k) shift_low();
@@ -184,7 +195,8 @@ __device__ __forceinline__ Compacted compact_stream(uint8_t* __restrict__ image,
 }
 
 // The context of a symbol of a code stream from its coded neighbours, left | up << 1 | upleft << 2 | upright << 3 -- the ONE
-// statement of the rule the coder codes with and the rate term prices with.  Every argument is one bit, 0 outside the frame.
+// statement of the rule code_walk and the decoder code with and the rate term prices with.  Every argument is one bit, 0
+// outside the frame.
 __device__ __forceinline__ uint32_t context_of(uint32_t left, uint32_t up, uint32_t upleft, uint32_t upright) {
   return left | up << 1 | upleft << 2 | upright << 3;
 }
@@ -198,6 +210,37 @@ __device__ __forceinline__ uint32_t load_bit_word(const T* px, int Cs, int kmax)
   for (int k = 0; k < 32; ++k)
     if (k < kmax) w |= (uint32_t)(ElemOps<T>::ld(px + (long long)k * Cs) > 0.f) << k;
   return w;
+}
+
+// The walk over one stream of the code tensor -- the ONE statement of its model for the encoder and the cost map: the H x W
+// symbols (bit = b > 0) at src, src + Cs, ... in raster order, 32 per loaded word, each one decision in the entry context_of
+// selects from its coded neighbours.  prob: the lane's 16 entries, row: the bits of its previous row ((W + 31) / 32 words, bit
+// k of word j = the bit at x = 32 j + k), both LDS columns of stride 64 the caller initialised (kProbInit, 0).  A symbol's
+// position is y * W + x.  The sink travels by value and comes back: that form keeps the encoder on its measured code.
+template <typename T, typename Sink>
+__device__ __forceinline__ Sink code_walk(const T* src, uint32_t* prob, uint32_t* row, int H, int W, int Cs, Sink sink) {
+  const int nw = (W + 31) >> 5;
+  for (int y = 0; y < H; ++y) {
+    uint32_t upw = row[0], left = 0, ul = 0;
+    for (int j = 0; j < nw; ++j) {
+      const uint32_t nextw = j + 1 < nw ? row[(j + 1) * 64] : 0u;
+      const uint32_t urw = (upw >> 1) | (nextw << 31);
+      const int kmax = min(32, W - 32 * j);
+      const long long at = (long long)y * W + 32 * j;
+      // the word's 32 input symbols before any of them is visited
+      const uint32_t inw = load_bit_word(src + at * Cs, Cs, kmax);
+      for (int k = 0; k < kmax; ++k) {
+        const uint32_t bit = (inw >> k) & 1u, up = (upw >> k) & 1u;
+        sink.put(prob[context_of(left, up, ul, (urw >> k) & 1u) * 64], bit);
+        sink.symbol_done(at + k);
+        ul = up;
+        left = bit;
+      }
+      row[j * 64] = inw;                        // bits beyond W stay 0
+      upw = nextw;
+    }
+  }
+  return sink;
 }
 
 }  // namespace jpdse

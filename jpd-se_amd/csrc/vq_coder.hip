@@ -6,7 +6,8 @@
 // lanes of a wave read (encoder) or write (decoder) 64 consecutive int32 words per step, and the loop over the steps is
 // wave-uniform.  A symbol is nb = bit_length(L - 1) binary decisions, most significant bit first, through a bit tree of
 // 2^nb adaptive probabilities per stream; every decision is range_coder.h's RcEncoder::encode / RcDecoder::decode, and the
-// payload layout, stream_span and compact_stream are that header's too.  A lane's table is a column of 16-bit entries in
+// payload layout, stream_span and compact_stream are that header's too.  The encoder's loop over a stream is vq_model.h's
+// vq_index_walk, which the cost map of vq_cost.hip runs too.  A lane's table is a column of 16-bit entries in
 // LDS that no other lane touches (no barrier): entry m of lane l is the halfword m * 64 + vq_col(l), so the bank of an
 // access depends on the lane alone, whatever node each lane's walk has reached, and the 32 lanes of an LDS lane group sit
 // on 32 different banks.  One wave per block, 2^nb * 128 bytes of LDS: 64 KiB at L = 512, within the default limit.
@@ -37,24 +38,7 @@ __global__ void __launch_bounds__(64) vq_index_encode_kernel(const int32_t* __re
   RcEncoder rc;
   rc.init(slots + vq_slot_offset(s, q, r, nb), scap);
   int bad = 0;
-  // every stream has at least one symbol (S <= M); the next index is loaded before the current one is coded
-  int32_t next = index[s];
-  for (int i = 0; i < cnt; ++i) {
-    int32_t v = next;
-    if (i + 1 < cnt) next = index[(long long)(i + 1) * S + s];
-    if ((uint32_t)v >= (uint32_t)L) {
-      v = 0;
-      bad = 2;
-    }
-    uint32_t m = 1;
-    for (int k = nb - 1; k >= 0; --k) {
-      const uint32_t bit = ((uint32_t)v >> k) & 1u;
-      uint32_t p = prob[m * 64];
-      rc.encode(p, bit);
-      prob[m * 64] = (uint16_t)p;
-      m = m << 1 | bit;
-    }
-  }
+  rc = vq_index_walk(index, prob, s, M, L, S, nb, rc, bad);
   lens[s] = rc.finish();
   flags[s] = bad;
 }

@@ -6,13 +6,17 @@
 //
 // The cost of a decision coded with the probability q of bit 0 is T[q] (bit 0) or T[2048 - q] (bit 1), code_cost.hip's table,
 // in units of 2^-16 bit; the cost of a symbol is the sum over the decisions its coder spends on it.  Kernels, in launch order:
-//   vq_index_cost_kernel  the serial walk of vq_index_encode_kernel with the byte emission removed: lane = stream, one wave
-//   vq_plane_cost_kernel  per block, grid ceil(S / 64), the lane's table in its private LDS column (vq_col.h), the same loads
-//                         of the indices, the same entries and conditions (vq_model.h), the update range_coder.h's adapted().
-//                         T sits in LDS behind the columns (8,448 bytes, loaded by the whole wave before any lane leaves).
-//                         A lane stores the cost of a symbol at the symbol's own position in the index tensor -- the lanes
-//                         that share an interleave step or a strip write neighbouring words, as the encoders read them -- and
-//                         keeps its stream's total (the plane walk: and its decision count) in registers, written once.
+//   vq_index_cost_kernel  the index encoder's walk itself (vq_index_walk, vq_model.h) with the pricing sink (CostPricer,
+//                         cost_class.h) in the encoder's place: no model loop of its own, only the prologue, the sink and
+//                         the stores.
+//   vq_plane_cost_kernel  the serial walk of vq_plane_encode_kernel with the byte emission removed: the same loads of the
+//                         indices, the same entries and conditions, the update range_coder.h's adapted().  It stays a copy:
+//                         on the shared walk it was 1.3-1.5 % slower than this text (vq_model.h names the figures).
+//                         Both: lane = stream, one wave per block, grid ceil(S / 64), the lane's table in its private LDS
+//                         column (vq_col.h).  T sits in LDS behind the columns (8,448 bytes, loaded by the whole wave before
+//                         any lane leaves).  A lane stores the cost of a symbol at the symbol's own position in the index
+//                         tensor -- the lanes that share an interleave step or a strip write neighbouring words, as the
+//                         encoders read them -- and keeps its stream's total and decision count in registers, written once.
 //   cost_cell_kernel      (cost_class.h) 16 lanes per cell add its G costs.
 //   vq_cost_group_kernel  a block per group adds the group's costs over all cells.
 //   cost_class_kernel     (cost_class.h; with a label map) the class tables, the kernel and the rule of code_cost.hip.
@@ -33,12 +37,6 @@ __device__ __forceinline__ uint32_t cost_put(const uint32_t* cost, uint16_t* pro
   return cost[bit ? kProbOne - q : q];
 }
 
-// T into LDS: the one cross-lane step of a walk, taken by the whole wave before any lane leaves
-__device__ __forceinline__ void cost_table_stage(uint32_t* cost, const uint32_t* __restrict__ table, int lane) {
-  for (int i = lane; i < kCostTable; i += 64) cost[i] = table[i];
-  __syncthreads();
-}
-
 // symbol: uint32 [M], at the positions of index; units / decisions: [S].  A lane that met an index outside [0, L) stores 2 to
 // *status, which the host zeroed: every writer stores the same word.
 // grid ceil(S / 64), one wave per block, (2^nb * 64 halfwords + kCostTableWords words) of dynamic LDS.
@@ -53,29 +51,10 @@ __global__ void __launch_bounds__(64) vq_index_cost_kernel(const int32_t* __rest
   if (s >= S) return;                           // no cross-lane operation below
   uint16_t* prob = reinterpret_cast<uint16_t*>(vq_cost_lds) + vq_col(lane);      // entry 0 is unused
   for (int m = 1; m < (1 << nb); ++m) prob[m * 64] = (uint16_t)kProbInit;
-  const int q = M / S, r = M - q * S, cnt = vq_stream_count(s, q, r);
-  unsigned long long total = 0;
-  bool bad = false;
-  // every stream has at least one symbol (S <= M); the next index is loaded before the current one is priced
-  int32_t next = index[s];
-  for (int i = 0; i < cnt; ++i) {
-    int32_t v = next;
-    if (i + 1 < cnt) next = index[(long long)(i + 1) * S + s];
-    if ((uint32_t)v >= (uint32_t)L) {
-      v = 0;
-      bad = true;
-    }
-    uint32_t m = 1, sym = 0;
-    for (int k = nb - 1; k >= 0; --k) {
-      const uint32_t bit = ((uint32_t)v >> k) & 1u;
-      sym += cost_put(cost, prob, (int)m, bit);
-      m = m << 1 | bit;
-    }
-    symbol[(long long)i * S + s] = sym;
-    total += sym;
-  }
-  units[s] = total;
-  decisions[s] = (uint32_t)(nb * cnt);
+  int bad = 0;
+  const CostPricer pr = vq_index_walk(index, prob, s, M, L, S, nb, CostPricer{cost, symbol, 1}, bad);
+  units[s] = pr.total;
+  decisions[s] = pr.count;
   if (bad) *status = 2;
 }
 

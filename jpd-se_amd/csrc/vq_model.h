@@ -1,7 +1,13 @@
 // The modelling the two index coders of the vector quantizer (vq_coder.hip: DESIGN.md 4.14; vq_plane.hip: 4.19) share with
-// their cost walks (vq_cost.hip: 4.20): which symbols a stream holds, the entries of a plane stream's table, and what an index
-// outside [0, L) counts as -- one statement each, so a walk prices what its coder codes.  The slots of the encoders and the
-// byte side stay with the coders.
+// their cost maps (vq_cost.hip: 4.20).  The order-0 index coder's model is stated ONCE, as a walk over a stream that hands its
+// decisions to a sink (range_coder.h: model walks and their sinks): the encoder runs it with RcEncoder, the cost map runs the
+// same walk with CostPricer, so the map prices what its coder codes by construction.  The tables' LDS columns, the slots of
+// the encoders and the byte side stay with the kernels.
+//
+// The plane coder shares the geometry, the table init and plane_clean only: its encoder, its cost kernel and its decoder keep
+// their own loops.  On the shared walk (both sink forms) and the shared entry functions the cost kernel was 1.3-1.5 % slower
+// than the parent (0.527 -> 0.534 ms, parent's spread 0.001), the decoder 1-3 % (4.113 -> 4.256 ms at strip_rows 16, spread
+// 0.039) and the encoder +1 % at strip_rows 16 though 5 % faster at 8: profiles/coder_walks_ab.txt.
 #pragma once
 #include "range_coder.h"
 
@@ -9,6 +15,33 @@ namespace jpdse {
 
 // index coder: the symbols of stream s, M = q S + r: the first r streams hold q + 1
 __device__ __forceinline__ int vq_stream_count(int s, int q, int r) { return q + (s < r ? 1 : 0); }
+
+// The walk of stream s of the index coder: its symbols index[s], index[s + S], ..., each nb decisions, most significant bit
+// first, through the bit tree of the lane's column prob (node m at entry m).  An index outside [0, L) is walked as 0 and sets
+// bad to 2, the status bit of a bad index.  The sink travels by value: that form keeps the encoders on their measured code.
+template <typename Sink>
+__device__ __forceinline__ Sink vq_index_walk(const int32_t* __restrict__ index, uint16_t* prob, int s, int M, int L, int S,
+                                               int nb, Sink sink, int& bad) {
+  const int q = M / S, r = M - q * S, cnt = vq_stream_count(s, q, r);
+  // every stream has at least one symbol (S <= M); the next index is loaded before the current one is visited
+  int32_t next = index[s];
+  for (int i = 0; i < cnt; ++i) {
+    int32_t v = next;
+    if (i + 1 < cnt) next = index[(long long)(i + 1) * S + s];
+    if ((uint32_t)v >= (uint32_t)L) {
+      v = 0;
+      bad = 2;
+    }
+    uint32_t m = 1;
+    for (int k = nb - 1; k >= 0; --k) {
+      const uint32_t bit = ((uint32_t)v >> k) & 1u;
+      sink.put(prob[m * 64], bit);
+      m = m << 1 | bit;
+    }
+    sink.symbol_done((long long)i * S + s);
+  }
+  return sink;
+}
 
 // plane coder
 constexpr int kPlaneUp = 8, kPlaneUpOnly = 10, kPlaneTree = 10;   // entries: 0 .. 7 left flag, 8 .. 9 / 10 upper flag, 10 + m

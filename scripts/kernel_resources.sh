@@ -1,9 +1,10 @@
 #!/bin/bash
 # VGPR / AGPR / scratch / occupancy of every kernel of the library, from hipcc's kernel-resource-usage remarks (no GPU needed).
-# usage: scripts/kernel_resources.sh > profiles/rNN_kernel_resources.txt
+# usage: scripts/kernel_resources.sh [SOURCE ...] > profiles/rNN_kernel_resources.txt
+# SOURCE: names of csrc/*.hip files without the suffix; default: conv_gemm norm elementwise
 R=$(cd $(dirname $0)/.. && pwd)
 T=$(mktemp -d)
-for f in conv_gemm norm elementwise; do
+for f in ${@:-conv_gemm norm elementwise}; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++20 -fPIC -Wno-unused-function -Wno-unused-variable -I$R/include -I$R/jpd-se_amd/csrc \
     --cuda-device-only -Rpass-analysis=kernel-resource-usage -c $R/jpd-se_amd/csrc/$f.hip -o /dev/null > $T/$f.log 2>&1
 done
