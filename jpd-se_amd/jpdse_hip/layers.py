@@ -8,32 +8,15 @@ layout while their memory is channels_last (= KRSC, the ABI's m
 layout), so `state_dict()` round-trips with reference `net_G.pth` / `net_D.pth` files.
 Weight gradients are written by the kernels straight into persistent `.grad` buffers.
 """
-import ctypes
 import math
 
 import torch
 import torch.nn as nn
 
-from . import ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, PAD_ZERO, PAD_REFLECT, F32, BF16
+from . import ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, PAD_ZERO, PAD_REFLECT, F32, BF16, binding_epoch
 from . import ops
 from .ops import Act
-
-_weights_epoch = [0]
-
-
-def lib_pack_size(d):
-  from . import lib
-  return int(lib().jpdse_conv_dgrad_pack_size(ctypes.byref(d)))
-
-
-def bump_weights_epoch():
-  """Call after any in-place update of master weights done outside torch's version counter
-  (the fused Adam kernel): packed GEMM panels are rebuilt lazily on next use."""
-  _weights_epoch[0] += 1
-
-
-def current_weights_epoch():
-  return _weights_epoch[0]
+from .panels import WeightPanels, ALIAS, CAST, PACKED, bump_weights_epoch   # noqa: F401  (bump_weights_epoch: the trainer's import)
 
 
 class Ctx(object):
@@ -88,8 +71,9 @@ class HipConv2d(nn.Module):
       self.bias = nn.Parameter(b)
     else:
       self.register_parameter('bias', None)
-    self._packs = None
-    self._pack_key = None
+    self._panels = WeightPanels(self._panel_kind(), self._desc(1, 64, 64))
+    self._slice = (None, None)        # bwd_input_slice: (channel range, its WeightPanels)
+    self._route_answers = {}          # _route_answer
     self._bias_grad_store = None
     self.grad_ready_hook = None       # callable(param) fired right after a gradient is written
 
@@ -107,72 +91,24 @@ class HipConv2d(nn.Module):
         'master weights must be fp32 channels_last (KRSC)'
     return w
 
-  def _plain_fwd_panel(self):
-    """True when the forward panel is an element-for-element bf16 cast of the KRSC master (no channel or
-    chunk padding, no Toeplitz extra) -- then the fused Adam kernel can write it."""
+  def _panel_kind(self):
+    """ALIAS: fp32 layers whose forward panel [Ks][R][S*Cs] would be an element-for-element copy of the KRSC master (no channel
+    or chunk padding): the kernels read the master itself -- no copy after each optimizer step (round 4: 32 such copies per
+    step cost BASELINE config 2 0.4 ms of 24).  CAST: bf16 layers whose forward panel is an element-for-element cast of the
+    master (no padding, no Toeplitz extra; thin inputs / heads carry extra panels) -- the fused Adam kernel can write it."""
     C, K = (self.cout, self.cin) if self.transposed else (self.cin, self.cout)
-    return self.cdtype == BF16 and C % 64 == 0 and K % 8 == 0 and K > 8     # thin inputs / heads carry extra panels
-
-  def _fp32_alias_fwd_panel(self):
-    """fp32 layers whose forward panel [Ks][R][S*Cs] would be an element-for-element copy of the KRSC master (no channel or
-    chunk padding): the kernels read the master itself -- no copy after each optimizer step (round 4: 32 such copies per step
-    cost BASELINE config 2 0.4 ms of 24)."""
-    C, K = (self.cout, self.cin) if self.transposed else (self.cin, self.cout)
-    return self.cdtype == F32 and C % 8 == 0 and K % 8 == 0 and (self.k * C) % 16 == 0
+    if self.cdtype == F32:
+      return ALIAS if C % 8 == 0 and K % 8 == 0 and (self.k * C) % 16 == 0 else PACKED
+    return CAST if C % 64 == 0 and K % 8 == 0 and K > 8 else PACKED
 
   def packs(self):
-    w = self._master()
-    wver = getattr(w, '_jpdse_wver', 0)        # bumped by FusedAdam for the tensors it updated
-    key = (w._version, _weights_epoch[0], w.data_ptr(), self.cdtype, wver)
-    if self._pack_key != key and self._fp32_alias_fwd_panel():
-      d = self._desc(1, 64, 64)
-      if self._packs is None or self._pack_key[3] != self.cdtype or self._packs[0].data_ptr() != w.data_ptr():
-        nd = lib_pack_size(d)
-        self._packs = (w.detach(), torch.empty(nd, dtype=torch.uint8, device=w.device))
-      ops.conv_pack_into(d, w, None, self._packs[1])        # the data-gradient panels only
-      self._pack_key = key
-      return self._packs
-    if self._pack_key != key:
-      d = self._desc(1, 64, 64)   # pack layout does not depend on N,H,W
-      if self._packs is None or self._pack_key[3] != self.cdtype:
-        self._packs = ops.conv_pack(d, w, w.device)
-        w._jpdse_cast_out = self._packs[0] if self._plain_fwd_panel() else None
-      elif (getattr(w, '_jpdse_cast_out', None) is self._packs[0] and
-            getattr(w, '_jpdse_cast_wver', None) == wver and self._pack_key[:4] == key[:4]):
-        ops.conv_pack_into(d, w, None, self._packs[1])      # forward panel written by the Adam kernel
-      else:
-        ops.conv_pack_into(d, w, self._packs[0], self._packs[1])
-      self._pack_key = key
-    return self._packs
-
-  def _pack_key_now(self):
-    w = self._master()
-    return (w._version, _weights_epoch[0], w.data_ptr(), self.cdtype, getattr(w, '_jpdse_wver', 0))
+    assert self.cdtype == self._panels.dtype, 'the compute dtype is fixed at construction'
+    return self._panels.get(self._master())
 
   def batched_pack_entries(self):
-    """Table entries for PackBatcher, or None when this layer needs its own pack call right now (first use,
-    fp32, forward panel not written by Adam, weights replaced, padded panel rows)."""
-    w = self._master()
-    if self._packs is None or self._pack_key is None:
-      return None
-    if self.cdtype != BF16 and not (self._fp32_alias_fwd_panel() and self._packs[0].data_ptr() == w.data_ptr()):
-      return None
-    key = self._pack_key_now()
-    if key == self._pack_key:
-      return []                                     # nothing to do
-    if self.cdtype == BF16 and not (getattr(w, '_jpdse_cast_out', None) is self._packs[0] and
-                                    getattr(w, '_jpdse_cast_wver', None) == key[4] and self._pack_key[:4] == key[:4]):
-      return None
-    if self.cdtype != BF16 and self._pack_key[:4] != key[:4]:
-      return None                                   # weights replaced (load_state_dict): the lazy per-layer path
-    if getattr(self, '_pack_entries_cache', None) is None or self._pack_entries_cache[0] != (w.data_ptr(), self._packs[1].data_ptr()):
-      from . import lib, PackEntry
-      buf = (PackEntry * 4)()
-      d = self._desc(1, 64, 64)
-      n = lib().jpdse_conv_pack_entries(ctypes.byref(d), ctypes.c_void_p(w.data_ptr()),
-                                        ctypes.c_void_p(self._packs[1].data_ptr()), buf, 4)
-      self._pack_entries_cache = ((w.data_ptr(), self._packs[1].data_ptr()), [buf[i] for i in range(n)] if n >= 0 else None)
-    return self._pack_entries_cache[1]
+    """Table entries for PackBatcher, [] when there is nothing to do, or None when this layer needs its own pack call right
+    now (panels.decide)."""
+    return self._panels.batch_entries(self._master())
 
   def _wgrad_buffer(self):
     w = self.weight
@@ -220,29 +156,27 @@ class HipConv2d(nn.Module):
     epilogue (or the layer applies a bias / activation)."""
     if self.apply_bias or self.act != ACT_NONE or self.cdtype != BF16:
       return None
-    d = self._desc(x.N, 2 * x.H, 2 * x.W) if self.transposed else self._desc(x.N, x.H, x.W)
-    from . import binding_epoch
-    key = (binding_epoch(), x.N, x.H, x.W)       # the answer depends on which library / kernel-selection mode is bound
-    cache = self.__dict__.setdefault('_moment_slots', {})
-    if key not in cache:
-      cache[key] = ops.conv_moment_slots(d, self.transposed)
-    slots = cache[key]
+    dims = (x.N, 2 * x.H, 2 * x.W) if self.transposed else (x.N, x.H, x.W)
+    slots = self._route_answer(ops.conv_moment_slots, dims, self.transposed)
     if slots <= 0:
       return None
     fwd_pack, dgrad_pack = self.packs()
-    y, mom = ops.conv_fwd_moments(d, x, dgrad_pack if self.transposed else fwd_pack, slots, self.transposed)
+    y, mom = ops.conv_fwd_moments(self._desc(*dims), x, dgrad_pack if self.transposed else fwd_pack, slots, self.transposed)
     return y, (Ctx(x) if self.transposed else Ctx(x, None)), mom, slots
 
   def nsum_slots(self, N, H, W):
     """Slots per image of the norm-backward sums this layer's data-gradient epilogue can write (0: none), cached per shape."""
     if self.transposed or self.cdtype != BF16:
       return 0
-    from . import binding_epoch
-    key = (binding_epoch(), N, H, W)
-    cache = self.__dict__.setdefault('_nsum_slots', {})
-    if key not in cache:
-      cache[key] = ops.conv_dgrad_nsum_slots(self._desc(N, H, W))
-    return cache[key]
+    return self._route_answer(ops.conv_dgrad_nsum_slots, (N, H, W))
+
+  def _route_answer(self, query, dims, *args):
+    """query(self._desc(*dims), *args), asked once per shape and per binding: the answer depends on which library /
+    kernel-selection mode is bound."""
+    key = (query, binding_epoch(), dims)
+    if key not in self._route_answers:
+      self._route_answers[key] = query(self._desc(*dims), *args)
+    return self._route_answers[key]
 
   def bwd(self, ctx, dy, need_dx=True, need_dw=True, dy_is_dz=False, relu_input=False, addend=None, input_slope=0.0, sink=None):
     """dy_is_dz: dy is already the gradient w.r.t. the PRE-activation (the caller fused this layer's
@@ -291,18 +225,14 @@ class HipConv2d(nn.Module):
     x, y = ctx.items
     dz = dy if (self.act == ACT_NONE or dy_is_dz) else ops.act_bwd(y, dy, self.act, self.slope)
     w = self._master()
-    key = (w._version, _weights_epoch[0], w.data_ptr(), self.cdtype, getattr(w, '_jpdse_wver', 0), c0, c1)
     d = ops.conv_desc(self.cdtype, x.N, x.H, x.W, c1 - c0, self.cout, self.k, self.k, self.stride, self.pad,
                       self.pad_mode, ACT_NONE, self.slope)
-    if getattr(self, '_slice_key', None) != key:
-      ws = w.detach()[:, c0:c1].contiguous(memory_format=torch.channels_last)
-      # same dtype and channel range as last time: re-pack into the existing panels (the weight version alone changes every step)
-      if getattr(self, '_slice_packs', None) is None or (self._slice_key[3], self._slice_key[5:]) != (key[3], key[5:]):
-        self._slice_packs = ops.conv_pack(d, ws, w.device)
-      else:
-        ops.conv_pack_into(d, ws, self._slice_packs[0], self._slice_packs[1])
-      self._slice_key = key
-    return ops.conv_dgrad(d, dz, self._slice_packs[1])
+    # panels of their own per channel range: while the range stays, a moved master is re-packed into the existing buffers
+    # (the weight version alone changes every step)
+    if self._slice[0] != (c0, c1):
+      self._slice = ((c0, c1), WeightPanels(PACKED, d))
+    _, dgrad_pack = self._slice[1].get(w, lambda: w.detach()[:, c0:c1].contiguous(memory_format=torch.channels_last))
+    return ops.conv_dgrad(d, dz, dgrad_pack)
 
   def _fire(self):
     if self.grad_ready_hook is not None:
@@ -484,11 +414,9 @@ class PackBatcher(object):
 
   def __init__(self, net):
     self.net = net
-    self._sig = None
-    self._table = None
+    self._table = {}
 
   def run(self):
-    from . import lib, check, PackEntry
     layers, entries = [], []
     for m in self.net.modules():
       if isinstance(m, HipConv2d):
@@ -499,21 +427,9 @@ class PackBatcher(object):
     if not entries:
       return 0
     sig = tuple((e.w, e.out) for e in entries)
-    if sig != self._sig:
-      arr = (PackEntry * len(entries))()
-      block0 = 0
-      for i, e in enumerate(entries):
-        arr[i] = e
-        arr[i].block0 = block0
-        block0 += e.blocks
-      host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
-      self._table = (host.to(layers[0].weight.device), len(entries), block0)
-      self._sig = sig
-    dev, n, total = self._table
-    check(lib().jpdse_conv_pack_run(ctypes.c_void_p(dev.data_ptr()), n, total,
-                                    ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'conv_pack_run')
+    ops.conv_pack_run(*ops.device_table(self._table, 0, sig, lambda: ops.conv_pack_table(entries), layers[0].weight.device))
     for m in layers:
-      m._pack_key = m._pack_key_now()
+      m._panels.mark_fresh(m.weight)
     return len(layers)
 
 
@@ -541,6 +457,19 @@ class InstNormAct(object):
     return (x, stats, self.act, self.slope)
 
 
+def conv_norm_fwd(conv, norm, x, residual=None):
+  """conv -> InstanceNorm (+ activation / residual): (y, conv ctx, norm ctx).  The norm's moment pass runs in the conv's epilogue
+  when its kernel has one (jpdse_conv_fwd_moments: the halo kernel of the full-width blocks), leaving ONE kernel per norm."""
+  fused = conv.fwd_moments(x)
+  if fused is not None:
+    h, c, mom, slots = fused
+    y, n = norm.fwd_from_moments(h, mom, slots, residual=residual)
+    return y, c, n
+  h, c = conv.fwd(x)
+  y, n = norm.fwd(h, residual=residual)
+  return y, c, n
+
+
 class ConvNormAct(object):
   """[pad] conv -> InstanceNorm -> activation: one stage of the generator trunk / PatchGAN.
   A plain object (not an nn.Module) so the conv is registered once, under its reference key."""
@@ -549,13 +478,7 @@ class ConvNormAct(object):
     self.conv, self.norm = conv, norm
 
   def fwd(self, x):
-    fused = self.conv.fwd_moments(x)
-    if fused is not None:                      # the norm's moment pass ran in the conv epilogue
-      h, c1, mom, slots = fused
-      y, c2 = self.norm.fwd_from_moments(h, mom, slots)
-      return y, Ctx(c1, c2)
-    h, c1 = self.conv.fwd(x)
-    y, c2 = self.norm.fwd(h)
+    y, c1, c2 = conv_norm_fwd(self.conv, self.norm, x)
     return y, Ctx(c1, c2)
 
   def bwd(self, ctx, dy, need_dx=True, need_dw=True, addend=None, **conv_kw):
@@ -590,22 +513,9 @@ class HipResnetBlock(nn.Module):
   # kernels being deterministic, bit-identical to the stored-activation path when on (tests/test_hip_configs.py).
   recompute = False
 
-  @staticmethod
-  def _conv_norm(conv, norm, x, residual=None):
-    """conv -> InstanceNorm (+ activation / residual); the norm's moment pass runs in the conv's epilogue when its kernel has
-    one (jpdse_conv_fwd_moments: the halo kernel of the full-width blocks), leaving ONE kernel per norm."""
-    fused = conv.fwd_moments(x)
-    if fused is not None:
-      h, c, mom, slots = fused
-      y, n = norm.fwd_from_moments(h, mom, slots, residual=residual)
-      return y, c, n
-    h, c = conv.fwd(x)
-    y, n = norm.fwd(h, residual=residual)
-    return y, c, n
-
   def _fwd(self, x):
-    h, c1, n1 = self._conv_norm(self.conv_block[1], self.norm1, x)
-    y, c2, n2 = self._conv_norm(self.conv_block[5], self.norm2, h, residual=x)
+    h, c1, n1 = conv_norm_fwd(self.conv_block[1], self.norm1, x)
+    y, c2, n2 = conv_norm_fwd(self.conv_block[5], self.norm2, h, residual=x)
     return y, Ctx(c1, n1, c2, n2)
 
   def fwd(self, x):

@@ -9,7 +9,7 @@ import ctypes
 
 import torch
 
-from . import (lib, check, JpdseError, F32, BF16, ConvDesc, InormDesc, EvalMetricsSemArgs, MsssimLossArgs, CodeRateArgs, SemLossArgs, CodeCostArgs, ACT_NONE, PAD_ZERO, PAD_REFLECT)
+from . import (lib, check, JpdseError, F32, BF16, ConvDesc, PackEntry, InormDesc, EvalMetricsSemArgs, MsssimLossArgs, CodeRateArgs, SemLossArgs, CodeCostArgs, ACT_NONE, PAD_ZERO, PAD_REFLECT)
 from . import (VqSoftFwdArgs, VqHardFwdArgs, VqSoftBwdArgs, VqDecodeArgs, VqDecodeBwdArgs, VqArgmaxArgs, VqPmfArgs, VqPmfBwdArgs,
                VqQuantizeFwdArgs, VqQuantizeBwdArgs, VqRateFwdArgs, VqQuantizeBwdGroupedArgs, VqLloydAccumArgs, VqLloydUpdateArgs)
 
@@ -108,6 +108,41 @@ def conv_pack(d, w_master, device):
 def conv_pack_into(d, w_master, fwd, dgr):
   check(lib().jpdse_conv_pack_weights(ctypes.byref(d), _p(w_master), _p(fwd), _p(dgr), _stream()),
         'conv_pack_weights')
+
+
+def conv_dgrad_pack_size(d):
+  return int(lib().jpdse_conv_dgrad_pack_size(ctypes.byref(d)))
+
+
+def conv_pack_entries(d, w_master, dgr):
+  """The rows of a conv_pack_run table that rebuild data-gradient panel `dgr` from `w_master` (host only; block0 is the
+  table builder's), or None when the library has no such rows for this layer."""
+  buf = (PackEntry * 4)()
+  n = lib().jpdse_conv_pack_entries(ctypes.byref(d), _p(w_master), _p(dgr), buf, 4)
+  return [buf[i] for i in range(n)] if n >= 0 else None
+
+
+def conv_pack_table(entries):
+  """(ctypes array, (n, total blocks)): the rows of many conv_pack_entries calls as one conv_pack_run table."""
+  arr, total = (PackEntry * len(entries))(*entries), 0       # copies of the layers' rows
+  for e in arr:
+    e.block0 = total
+    total += e.blocks
+  return arr, (len(entries), total)
+
+
+def conv_pack_run(table, n, total_blocks):
+  """One launch over a device table of n conv_pack_entries rows."""
+  check(lib().jpdse_conv_pack_run(_p(table), n, total_blocks, _stream()), 'conv_pack_run')
+
+
+def device_table(cache, slot, sig, build, device):
+  """The argument table of a multi-tensor launch: (device tensor, *rest) for build() -> (ctypes array, rest), kept in
+  cache[slot] and built and uploaded again only when `sig` (the pointers its rows hold) changes."""
+  if cache.get(slot, (None,))[0] != sig:
+    arr, rest = build()
+    cache[slot] = (sig, torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)) + rest
+  return cache[slot][1:]
 
 
 def _conv_ws(d, device):

@@ -11,7 +11,8 @@ import ctypes
 import torch
 
 from . import lib, check, AdamEntry
-from .layers import bump_weights_epoch
+from .ops import device_table
+from .panels import cast_target, optimizer_stepped
 
 
 class FusedAdam(torch.optim.Optimizer):
@@ -21,7 +22,7 @@ class FusedAdam(torch.optim.Optimizer):
                     foreach=None, capturable=False, differentiable=False, fused=None)
     super(FusedAdam, self).__init__(params, defaults)
     self.grad_scale = grad_scale     # e.g. 1/world_size after a SUM all-reduce
-    self._table = {}                 # group index -> (ptr signature, device table, n_entries, total_blocks)
+    self._table = {}                 # group index -> ops.device_table's slot
 
   def zero_grad(self, set_to_none=False):
     """Gradients live in persistent buffers that every backward overwrites (beta = 0), so
@@ -70,9 +71,9 @@ class FusedAdam(torch.optim.Optimizer):
       if not (g.stride() == p.stride() and m.stride() == p.stride() and v.stride() == p.stride()):
         raise RuntimeError('FusedAdam: param/grad/state strides differ')
       n = p.numel()
-      # conv layers whose forward GEMM panel is a plain bf16 cast of the master (layers.HipConv2d) let the
+      # conv layers whose forward GEMM panel is a plain bf16 cast of the master (panels.CAST) let the
       # Adam kernel write it: saves the separate cast pass over the weights
-      cast = getattr(p, '_jpdse_cast_out', None)
+      cast = cast_target(p)
       cast_ptr = cast.data_ptr() if cast is not None else None
       entries.append(AdamEntry(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, block0, cast_ptr))
       sig.append((p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), cast_ptr))
@@ -85,31 +86,19 @@ class FusedAdam(torch.optim.Optimizer):
       entries, sig, total_blocks = self._build_table(gi, group)
       if not entries:
         continue
-      cached = self._table.get(gi)
-      if cached is None or cached[0] != sig:
-        arr = (AdamEntry * len(entries))(*entries)
-        host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
-        dev = host.to(group['params'][0].device)
-        cached = (sig, dev, len(entries), total_blocks)
-        self._table[gi] = cached
-      _, dev, n_entries, total_blocks = cached
+      dev, = device_table(self._table, gi, sig, lambda: ((AdamEntry * len(entries))(*entries), ()), group['params'][0].device)
       step_t = None
       for p in group['params']:
         if p.grad is not None:
           st = self.state[p]
           st['step'] += 1
           step_t = st['step']
+          # the kernel updates the masters outside torch's version counter: tell the panel caches (panels.py, optimizer
+          # protocol), only for the tensors that move
+          optimizer_stepped(p)
       b1, b2 = group['betas']
-      check(lib().jpdse_adam_step(ctypes.c_void_p(dev.data_ptr()), n_entries, total_blocks, float(group['lr']),
+      check(lib().jpdse_adam_step(ctypes.c_void_p(dev.data_ptr()), len(entries), total_blocks, float(group['lr']),
                                   float(b1), float(b2), float(group['eps']), int(step_t.item()),
                                   float(self.grad_scale),
                                   ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'adam_step')
-    # the kernel updates the masters outside torch's version counter: bump a per-parameter counter
-    # (layers.HipConv2d.packs keys its packed GEMM panels on it), only for the tensors that moved
-    for group in self.param_groups:
-      for p in group['params']:
-        if p.grad is not None:
-          p._jpdse_wver = getattr(p, '_jpdse_wver', 0) + 1
-          if getattr(p, '_jpdse_cast_out', None) is not None:
-            p._jpdse_cast_wver = p._jpdse_wver      # forward panel already holds the updated weights
     return None
