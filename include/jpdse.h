@@ -188,6 +188,16 @@ int jpdse_conv_dgrad_fused(const jpdse_conv_desc* d, const void* dy, const void*
 int jpdse_conv_dgrad_fused_lrelu(const jpdse_conv_desc* d, const void* dy, const void* dgrad_pack,
                                  const void* x, float slope, const void* addend, void* dx, void* ws,
                                  size_t ws_bytes, void* stream);
+/* jpdse_conv_dgrad_fused / _fused_lrelu (slope 0: the ReLU form) over a batch with more gradient images than saved forward
+ * ones -- the PatchGAN walked backwards once for loss_G and loss_D: d->N counts the images of dy / dx; gradient image n reads
+ * the mask of image n >= alias ? n - alias : n of `x` (which holds d->N - alias images; alias 0: one mask image per gradient
+ * image), and only images n < addend_n take `addend` (which holds addend_n images; 0: every image does).  Each image's
+ * result equals, bit for bit, that of the un-batched call on a batch that contains it with the same kernel.  2 alias <= N; with
+ * both a mask and an addend the batch has one cut: addend_n == alias (or alias 0).  Only the routes of
+ * the PatchGAN's layers take such a call; the others are refused (JPDSE_EINVAL). */
+int jpdse_conv_dgrad_batched(const jpdse_conv_desc* d, const void* dy, const void* dgrad_pack, const void* x, float slope,
+                             const void* addend, int32_t alias, int32_t addend_n, void* dx, void* ws, size_t ws_bytes,
+                             void* stream);
 /* jpdse_conv_dgrad_fused whose output dx is the gradient w.r.t. the OUTPUT of an InstanceNorm2d (+ activation): the chains
  * conv -> InstanceNorm -> ReLU -> [pad] conv and x + conv_block(x) of ResnetBlock (networks.py:283-305).  The norm's backward
  * needs, per (image, channel), sum dz and sum dz * yhat with yhat = (norm_x - mean) rstd and dz = dx act'(yhat); the epilogue
@@ -226,6 +236,11 @@ typedef struct jpdse_inorm_desc {
   float slope;
   float eps;            /* 1e-5 */
   int32_t has_residual; /* y = act(norm(x)) + residual */
+  int32_t alias;        /* jpdse_inorm_bwd only, 0 = off (must be 0 in every other call): the backward runs over more gradient
+                         * images than saved forward ones.  N counts the images of dy / dx; gradient image n reads x and stats of
+                         * image n >= alias ? n - alias : n (x, stats hold N - alias images; 2 alias <= N).  InstanceNorm acts per image: each
+                         * image's dx equals, bit for bit, that of the un-aliased call on a batch that contains it.  The PatchGAN
+                         * walked backwards once for loss_G and loss_D uses it. */
 } jpdse_inorm_desc;
 size_t jpdse_inorm_workspace_size(const jpdse_inorm_desc* d);
 /* stats: fp32 [N][CPAD(C)][2] = (mean, rstd), kept for backward */

@@ -175,6 +175,9 @@ struct DgradCall {      // what a data-gradient route is handed
   const jpdse_conv_desc* d; const ConvPlan& p;
   const void* dy; const void* pack; void* dx; void* ws; hipStream_t s;
   const void* mask; const void* addend; float* mom; float mask_slope; const NormSink* sink;
+  // batched data gradient (jpdse_conv_dgrad_batched; 0 = off): gradient images >= alias read the mask of saved image n - alias,
+  // and only images < addend_n take the addend
+  int alias, addend_n;
 };
 static void* dgrad_dxp(const DgradCall& c) { return reinterpret_cast<char*>(c.ws) + c.p.dypad_bytes; }      // dx on the reflect-padded domain
 
@@ -183,6 +186,8 @@ static ConvView dgrad_view(const DgradCall& c) {
   ConvView v = view_dgrad_phase(c.d, c.p, 0, c.dy, c.pack, c.dx);
   v.mask = reinterpret_cast<const bf16_t*>(c.mask);
   v.addend = reinterpret_cast<const bf16_t*>(c.addend);
+  v.alias = c.mask != nullptr ? c.alias : 0;
+  v.addend_n = c.addend != nullptr ? c.addend_n : 0;
   return v;
 }
 // reflect-padded 3x3: the zero-padded data gradient on the image's own grid (pad 1, straight into dx).  The mask rides in the
@@ -372,6 +377,7 @@ static int dgrad_thin1(const DgradCall& c) {      // dx is written once by an FM
   t.taps = reinterpret_cast<float*>(c.ws);        // 16 x Cs floats: inside the padded-dy region of every plan
   t.DX = reinterpret_cast<bf16_t*>(c.dx);
   t.addend = reinterpret_cast<const bf16_t*>(c.addend);
+  t.addend_n = c.addend_n;
   t.N = c.d->N; t.H = c.d->H; t.W = c.d->W; t.Cs = c.p.Cs; t.OH = c.p.OH; t.OW = c.p.OW;
   t.py = (f.Uh - 1) - f.i0h;
   t.px = (f.Uw - 1) - f.i0w;
@@ -405,9 +411,22 @@ static int dgrad_finish(const DgradCall& c, bool in_epilogue) {
     rc = check_launch("reflect_fold_kernel");
   }
   if (rc == JPDSE_OK && (c.mask != nullptr || c.addend != nullptr) && !in_epilogue) {
-    hipLaunchKernelGGL((relu_mask_kernel<T>), dim3(ew_blocks(total_vec)), dim3(256), 0, c.s, reinterpret_cast<T*>(c.dx),
-                       reinterpret_cast<const T*>(c.mask), total_vec, reinterpret_cast<const T*>(c.addend), c.mask_slope);
-    rc = check_launch("relu_mask_kernel");
+    // one pass per run of images that share their operands: a batched call cuts at addend_n and at alias
+    const int cuts[4] = {0, c.addend != nullptr ? c.addend_n : 0, c.mask != nullptr ? c.alias : 0, d->N};
+    const long long img = (long long)d->H * d->W * c.p.Cs, img_vec = total_vec / d->N;
+    for (int n0 = 0; n0 < d->N && rc == JPDSE_OK;) {
+      int n1 = d->N;
+      for (int q = 1; q < 3; ++q) if (cuts[q] > n0 && cuts[q] < n1) n1 = cuts[q];
+      const T* addend = c.addend != nullptr && (c.addend_n == 0 || n0 < c.addend_n) ? reinterpret_cast<const T*>(c.addend) + n0 * img : nullptr;
+      const T* mask = c.mask != nullptr ? reinterpret_cast<const T*>(c.mask) + (n0 >= c.alias ? n0 - c.alias : n0) * img : nullptr;
+      if (addend != nullptr || mask != nullptr) {
+        const long long nvec = (n1 - n0) * img_vec;
+        hipLaunchKernelGGL((relu_mask_kernel<T>), dim3(ew_blocks(nvec)), dim3(256), 0, c.s, reinterpret_cast<T*>(c.dx) + n0 * img, mask, nvec,
+                           addend, c.mask_slope);
+        rc = check_launch("relu_mask_kernel");
+      }
+      n0 = n1;
+    }
   }
   return rc;
 }
@@ -427,10 +446,33 @@ static int dgrad_fast(const DgradCall& c) {
     if (!refl) {
       g.mask = reinterpret_cast<const bf16_t*>(c.mask);
       g.addend = reinterpret_cast<const bf16_t*>(c.addend);
+      g.alias = c.mask != nullptr ? c.alias : 0;
+      g.addend_n = c.addend != nullptr ? c.addend_n : 0;
     }
     g.mask_slope = c.mask_slope;
     g.splits = nlive == 1 ? splitk_for(g.M, p.Cs, f.Uh * f.Uw * p.Ks / 64) : 1;
     g.partial = splitk_slabs(p, c.ws);
+    if ((g.alias != 0 || g.addend_n != 0) && g.splits <= 1) {
+      // a batched call whose fused operands ride in the kernel's own epilogue: every run of images with the same operands is a
+      // problem of its own (same tiles' arithmetic per row; a tile never spans two runs), addressed by base pointers
+      const int cuts[2] = {g.addend_n, g.alias};
+      const long long x_img = (long long)g.IH * g.IW * g.Cs;
+      for (int n0 = 0; n0 < d->N;) {
+        int n1 = d->N;
+        for (int q = 0; q < 2; ++q) if (cuts[q] > n0 && cuts[q] < n1) n1 = cuts[q];
+        if (batch.n >= kFastBatchMax) return set_error(JPDSE_EINVAL, "conv_dgrad_batched: more than %d problems in one launch", kFastBatchMax);
+        FastArgs r = g;
+        r.alias = r.addend_n = 0;
+        r.X = g.X + n0 * x_img;
+        r.Y = g.Y + n0 * g.out_sn;
+        r.M = (n1 - n0) * g.OH * g.OW;
+        r.addend = g.addend != nullptr && (g.addend_n == 0 || n0 < g.addend_n) ? g.addend + n0 * g.out_sn : nullptr;
+        r.mask = g.mask != nullptr ? g.mask + (long long)(n0 >= g.alias ? n0 - g.alias : n0) * g.out_sn : nullptr;
+        batch.p[batch.n++] = r;
+        n0 = n1;
+      }
+      continue;
+    }
     batch.p[batch.n++] = g;
   }
   if (int rc = launch_fast_batch(batch, c.s)) return rc;
@@ -478,13 +520,18 @@ static int dgrad_nsum_slots(const jpdse_conv_desc* d, const ConvPlan& p) {
 template <typename T>
 static int conv_dgrad_t(const jpdse_conv_desc* d, const ConvPlan& p, const void* dy, const void* pack, void* dx,
                         void* ws, hipStream_t s, const void* mask = nullptr, const void* addend = nullptr, float* mom = nullptr,
-                        float mask_slope = 0.f, const NormSink* sink = nullptr) {
+                        float mask_slope = 0.f, const NormSink* sink = nullptr, int alias = 0, int addend_n = 0) {
   // LeakyReLU-backward epilogue (mask_slope != 0): only the fast / generic tile kernels and the unfused pass apply it
   const bool lrelu = mask != nullptr && mask_slope != 0.f;
   if (sink != nullptr && (dgrad_nsum_slots(d, p) == 0 || lrelu))
     return set_error(JPDSE_EINVAL, "conv_dgrad: this layer's data-gradient kernel writes no norm-backward sums (jpdse_conv_dgrad_nsum_slots == 0)");
-  const DgradCall c = {d, p, dy, pack, dx, ws, s, mask, addend, mom, mask_slope, sink};
+  const DgradCall c = {d, p, dy, pack, dx, ws, s, mask, addend, mom, mask_slope, sink, alias, addend_n};
   const DgradRoute route = select_dgrad(d, p, {mask != nullptr, addend != nullptr, lrelu, mom != nullptr, sink != nullptr});
+  // a batched call: only the routes of the PatchGAN layers resolve the image classes (gemm_fast.h, gemm_taps.h 4x4, thin_out1.h,
+  // and the unfused pass behind the generic GEMM)
+  if ((alias != 0 || addend_n != 0) && route != DgradRoute::fast && route != DgradRoute::taps4 && route != DgradRoute::thin1 &&
+      route != DgradRoute::generic)
+    return set_error(JPDSE_EINVAL, "conv_dgrad_batched: this layer's data-gradient kernel does not take a batched call");
   if constexpr (sizeof(T) == 2) {      // (the bf16 kernels are not instantiated for fp32 layers, which select_dgrad sends to the generic GEMM)
     switch (route) {
       case DgradRoute::rows: return launch_rows(to_rows(dgrad_view(c)), 1, s);

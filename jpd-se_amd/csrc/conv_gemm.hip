@@ -561,6 +561,26 @@ int jpdse_conv_dgrad_fused_lrelu(const jpdse_conv_desc* d, const void* dy, const
              : conv_dgrad_t<float>(d, p, dy, dgrad_pack, dx, ws, as_stream(stream), x, addend, nullptr, slope);
 }
 
+int jpdse_conv_dgrad_batched(const jpdse_conv_desc* d, const void* dy, const void* dgrad_pack, const void* x, float slope,
+                             const void* addend, int32_t alias, int32_t addend_n, void* dx, void* ws, size_t ws_bytes, void* stream) {
+  ConvPlan p;
+  if (int rc = conv_enter("conv_dgrad_batched", d, dy && dgrad_pack && dx, ws, ws_bytes, &p, [=](const ConvPlan&) {
+        JPDSE_REQUIRE(slope >= 0.f && slope < 1.f, "conv_dgrad_batched: slope %g outside [0, 1)", (double)slope);
+        // images n < alias read mask image n, images n >= alias image n - alias, of a tensor that holds N - alias images
+        JPDSE_REQUIRE(alias >= 0 && 2 * (long long)alias <= d->N && addend_n >= 0 && addend_n <= d->N,
+                      "conv_dgrad_batched: alias %d (at most N / 2) / addend_n %d outside the batch of %d", alias, addend_n, d->N);
+        // one cut of the batch: the images that take the addend are the ones in front of the aliased ones
+        JPDSE_REQUIRE(x == nullptr || addend == nullptr || alias == 0 || addend_n == alias,
+                      "conv_dgrad_batched: addend_n %d differs from alias %d", addend_n, alias);
+        return (int)JPDSE_OK;
+      })) return rc;
+  if (x == nullptr) alias = 0;
+  if (addend == nullptr || addend_n == d->N) addend_n = 0;
+  return d->dtype == JPDSE_BF16
+             ? conv_dgrad_t<bf16_t>(d, p, dy, dgrad_pack, dx, ws, as_stream(stream), x, addend, nullptr, slope, nullptr, alias, addend_n)
+             : conv_dgrad_t<float>(d, p, dy, dgrad_pack, dx, ws, as_stream(stream), x, addend, nullptr, slope, nullptr, alias, addend_n);
+}
+
 int32_t jpdse_conv_dgrad_nsum_slots(const jpdse_conv_desc* d) {
   if (validate(d)) return 0;
   ConvPlan p;

@@ -68,6 +68,7 @@ struct ConvView : ConvShape {
   float slope;
   // optional fused operands, set by the dispatch after construction
   const bf16_t* mask; float mask_slope; const bf16_t* addend;   // data gradient, Y's addressing: Y = (result + addend) * (mask > 0 ? 1 : mask_slope)
+  int alias, addend_n;            // batched data gradient (0 = off): images >= alias read the mask of image n - alias; images >= addend_n take no addend
   float* mom;                     // InstanceNorm moments of Y from the epilogue (rows / halo kernels)
   const bf16_t* frame;            // folded frame of X: reflect data gradient in one launch (halo kernel, nine-tap program)
 };
@@ -136,6 +137,7 @@ static FastArgs to_fast(const ConvView& v) {        // dense panel (b_stride / b
   f.M = v.N * v.OH * v.OW; f.Cs = v.Cin_s;
   f.R = v.R; f.S = v.S; f.sy = f.sx = v.stride; f.reflect = v.reflect;
   f.mask_slope = v.mask_slope;
+  f.alias = v.alias; f.addend_n = v.addend_n;
   return f;
 }
 
@@ -244,7 +246,7 @@ static int launch_fast_cfg(FastBatch& b, hipStream_t s) {
     b.p[i].xcd_map = 0;       // (the XCD-aware tile order, round-3 developer mode 30, measured neutral and was retired: DESIGN.md 4.1 (xi))
     total += ((a.M + BM - 1) / BM) * ((a.Ks + BN - 1) / BN) * (a.splits > 1 ? a.splits : 1);
   }
-  for (int i = b.n; i < 5; ++i) b.first_tile[i] = total;
+  for (int i = b.n; i <= kFastBatchMax; ++i) b.first_tile[i] = total;
   const long long kdim = (long long)b.p[0].R * b.p[0].S * b.p[0].Cs;
   const int pslot = b.n == 1 ? prof_begin(s, b.p[0].Ks, kdim) : -1;      // a multi-problem launch is not one GEMM: not timed
   hipLaunchKernelGGL((gemm_fast_kernel<WM, WN, TM, TN, STAGES>), dim3(total), dim3(64 * WM * WN), lds, s, b);
@@ -623,6 +625,7 @@ static TapsArgs to_taps(const ConvView& v, int patch_w) {
   a.slope = v.slope;
   a.addend = v.addend;
   a.mask = v.mask;
+  a.alias = v.alias; a.addend_n = v.addend_n;
   a.prog[0].B[0] = v.B;
   a.prog[0].ktot[0] = v.ktot;
   a.prog[0].out_base[0] = v.out_base;

@@ -52,13 +52,19 @@ struct FastArgs {
   int no_finish;       // split-K: leave the slabs to the caller (no splitk_finish_kernel)
   long long x_extent;  // elements readable from X (0 = not given): the launcher refuses a problem whose last pixel lies beyond
   int xcd_map;         // N-tiles of an M-tile on consecutive slots of one XCD (set by the launcher)
+  // a batch with more gradient images than saved forward ones (0 = off): images >= alias read the mask of image n - alias, and
+  // only images < addend_n take the addend.  Read by splitk_finish_kernel, which resolves n per vector anyway; gemm_fast_kernel's
+  // own epilogue does not: its launcher (dgrad_fast) makes every run of images with the same operands a problem of the batch
+  int alias, addend_n;
 };
 
-// Up to 4 independent problems in one launch (the stride-2 sub-pixel phases of a data gradient /
-// ConvTranspose2d forward): block b belongs to problem q with first_tile[q] <= b < first_tile[q+1].
+// Up to 8 independent problems in one launch (the stride-2 sub-pixel phases of a data gradient /
+// ConvTranspose2d forward, times the two image classes of a batched data gradient): block b belongs to problem q with
+// first_tile[q] <= b < first_tile[q+1].
+constexpr int kFastBatchMax = 8;
 struct FastBatch {
-  FastArgs p[4];
-  int first_tile[5];
+  FastArgs p[kFastBatchMax];
+  int first_tile[kFastBatchMax + 1];
   int n;
   int small_m;         // host only: every problem has few rows (the ring strips): 128-row tiles, two blocks per CU
 };
@@ -176,7 +182,7 @@ template <int WM, int WN, int TM, int TN, int STAGES>
 __global__ __launch_bounds__(64 * WM * WN) void gemm_fast_kernel(const FastBatch batch) {
   int q = 0;
 #pragma unroll
-  for (int i = 1; i < 4; ++i)
+  for (int i = 1; i < kFastBatchMax; ++i)
     if (i < batch.n && (int)blockIdx.x >= batch.first_tile[i]) q = i;
   const FastArgs& a = batch.p[q];
   const int block_id = (int)blockIdx.x - batch.first_tile[q];
@@ -491,7 +497,7 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(const FastArgs a, lo
     const float bv = (a.bias != nullptr && live) ? a.bias[col] : 0.f;
     o[e] = live ? apply_act(acc[e] + bv, a.act, a.slope) : 0.f;
   }
-  if (a.addend != nullptr) {
+  if (a.addend != nullptr && (a.addend_n == 0 || n < a.addend_n)) {
     float ad[8];
     Vec16<bf16_t>::load(a.addend + off + c0, ad);
 #pragma unroll
@@ -499,7 +505,7 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(const FastArgs a, lo
   }
   if (a.mask != nullptr) {
     float mk[8];
-    Vec16<bf16_t>::load(a.mask + off + c0, mk);
+    Vec16<bf16_t>::load(a.mask + (off - (n >= a.alias ? (long long)a.alias * a.out_sn : 0)) + c0, mk);
 #pragma unroll
     for (int e = 0; e < 8; ++e) o[e] = mk[e] > 0.f ? o[e] : (a.mask_slope == 0.f ? 0.f : bf16_round(o[e]) * a.mask_slope);
   }

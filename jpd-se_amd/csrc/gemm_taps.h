@@ -60,6 +60,9 @@ struct TapsArgs {
   float* partial;
   const bf16_t* V;           // VIRT instantiation: the folded frame of X (ring_frame_kernel): reflect data gradient in one launch (gemm_halo.h)
   int nblk0;                 // blocks [0, nblk0) run prog[0], the rest prog[1]
+  // a batch with more gradient images than saved forward ones (0 = off): images >= alias read the mask of image n - alias, and
+  // only images < addend_n take the addend
+  int alias, addend_n;
   TapsProg prog[2];
 };
 
@@ -323,6 +326,9 @@ __device__ __forceinline__ void gemm_taps_body(const TapsArgs& a, const TapsProg
   constexpr int PITCH = BN * 2 + 64;
   static_assert(TH * TW * PITCH <= 2 * HALO + 3 * B_STAGE, "epilogue tile fits the pipeline LDS");
   constexpr int VPR = BN / 8;
+  // the fused operands of this block's image (a tile lies inside one image)
+  const bf16_t* const addend = (a.addend_n == 0 || n < a.addend_n) ? a.addend : nullptr;
+  const bf16_t* const mask = a.mask != nullptr ? a.mask - (n >= a.alias ? (long long)a.alias * a.out_sn : 0) : nullptr;
 #pragma unroll
   for (int q = 0; q < NSETS; ++q) {
     __syncthreads();
@@ -330,7 +336,7 @@ __device__ __forceinline__ void gemm_taps_body(const TapsArgs& a, const TapsProg
     acc_tile_to_lds<2, TN>(smem, PITCH, WROWS == 1 ? wm * 64 : wm * 64, wn * TN * 32, n0, lane, acc[q], a.bias, a.Kout, a.act, a.slope);
     __syncthreads();
     const long long blk_base = pr.out_base[q] + n * a.out_sn + (long long)oh0 * a.out_sh + (long long)ow0 * a.out_sw;
-    if (a.addend != nullptr || a.mask != nullptr) {
+    if (addend != nullptr || mask != nullptr) {
       // fused operands loaded for all of the thread's vectors before the first store (gemm_halo.h: behind a store the compiler
       // cannot hoist them, and the epilogue would pay one memory round trip per vector)
       constexpr int NV = TH * TW * VPR / 512;
@@ -343,8 +349,8 @@ __device__ __forceinline__ void gemm_taps_body(const TapsArgs& a, const TapsProg
         const int r = row / TW, c = row - r * TW;
         const long long off = blk_base + (long long)r * a.out_sh + (long long)c * a.out_sw + n0 + v * 8;
         const bool on = n0 + v * 8 < a.Ks;
-        if (on && a.addend != nullptr) addv[it] = *reinterpret_cast<const u32x4*>(a.addend + off);
-        if (on && a.mask != nullptr) mskv[it] = *reinterpret_cast<const u32x4*>(a.mask + off);
+        if (on && addend != nullptr) addv[it] = *reinterpret_cast<const u32x4*>(addend + off);
+        if (on && mask != nullptr) mskv[it] = *reinterpret_cast<const u32x4*>(mask + off);
       }
 #pragma unroll
       for (int it = 0; it < NV; ++it) {
@@ -354,8 +360,8 @@ __device__ __forceinline__ void gemm_taps_body(const TapsArgs& a, const TapsProg
         const int r = row / TW, c = row - r * TW;
         const long long off = blk_base + (long long)r * a.out_sh + (long long)c * a.out_sw + n0 + v * 8;
         u32x4 val = *reinterpret_cast<const u32x4*>(smem + row * PITCH + v * 16);
-        if (a.addend != nullptr) val = add_bf16x8(val, addv[it]);
-        if (a.mask != nullptr) val = lrelu_mask8(val, mskv[it], a.mask_slope);
+        if (addend != nullptr) val = add_bf16x8(val, addv[it]);
+        if (mask != nullptr) val = lrelu_mask8(val, mskv[it], a.mask_slope);
         *reinterpret_cast<u32x4*>(a.Y + off) = val;
       }
       continue;

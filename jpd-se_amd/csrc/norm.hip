@@ -19,11 +19,12 @@ struct MomentGeom {
   int TX, TY;             // threads across columns / pixels (TX*TY = 256), TX a power of two
   int tx_shift;           // log2(TX)
   int splits, pix_per_split;
+  int alias;              // backward: images >= alias read the saved x / stats of image n - alias (0 = off)
 };
 
 static MomentGeom moment_geom(int N, int HW, int Cs, int VE) {
   MomentGeom g;
-  g.N = N; g.HW = HW; g.Cs = Cs; g.cv = Cs / VE;
+  g.N = N; g.HW = HW; g.Cs = Cs; g.cv = Cs / VE; g.alias = 0;
   int tx = 1;
   while (tx < g.cv && tx < 256) tx <<= 1;
   g.TX = tx; g.TY = 256 / tx;
@@ -136,8 +137,10 @@ __global__ __launch_bounds__(256) void moment_kernel(const T* __restrict__ x, co
     } else {
       BwdMoments<T> f{x, dy, stats, act, slope};
       float mean[VE], rstd[VE];
+      const int nx = n >= g.alias ? n - g.alias : n;      // the saved forward image of gradient image n
+      const long long xbase = (long long)nx * g.HW * g.Cs + c0;
       {
-        const float* st = stats + ((long long)n * g.Cs + c0) * 2;
+        const float* st = stats + ((long long)nx * g.Cs + c0) * 2;
 #pragma unroll
         for (int e = 0; e < VE; ++e) { mean[e] = st[2 * e]; rstd[e] = st[2 * e + 1]; }
       }
@@ -146,16 +149,16 @@ __global__ __launch_bounds__(256) void moment_kernel(const T* __restrict__ x, co
         float v[JPDSE_NORM_ILP][VE], gr[JPDSE_NORM_ILP][VE];
 #pragma unroll
         for (int u = 0; u < JPDSE_NORM_ILP; ++u) {
-          const long long off = base + (long long)(p + u * g.TY) * g.Cs;
-          Vec16<T>::load(x + off, v[u]);
-          Vec16<T>::load(dy + off, gr[u]);
+          const long long po = (long long)(p + u * g.TY) * g.Cs;
+          Vec16<T>::load(x + xbase + po, v[u]);
+          Vec16<T>::load(dy + base + po, gr[u]);
         }
 #pragma unroll
         for (int u = 0; u < JPDSE_NORM_ILP; ++u) f.acc2(v[u], gr[u], mean, rstd, s1, s2);
       }
       for (; p < p1; p += g.TY) {
         float v[VE], gr[VE];
-        Vec16<T>::load(x + base + (long long)p * g.Cs, v);
+        Vec16<T>::load(x + xbase + (long long)p * g.Cs, v);
         Vec16<T>::load(dy + base + (long long)p * g.Cs, gr);
         f.acc2(v, gr, mean, rstd, s1, s2);
       }
@@ -324,27 +327,27 @@ __global__ __launch_bounds__(256) void inorm_apply_bwd_kernel(const T* __restric
   if (col >= g.cv) return;
   const int c0 = col * VE;
   float mean[VE], rstd[VE], s1[VE], s2[VE];
-  const long long sidx = ((long long)n * g.Cs + c0) * 2;
+  const int nx = n >= g.alias ? n - g.alias : n;      // the saved forward image of gradient image n
+  const long long sidx = ((long long)n * g.Cs + c0) * 2, xidx = ((long long)nx * g.Cs + c0) * 2;
 #pragma unroll
   for (int e = 0; e < VE; ++e) {
-    mean[e] = stats[sidx + 2 * e];
-    rstd[e] = stats[sidx + 2 * e + 1];
+    mean[e] = stats[xidx + 2 * e];
+    rstd[e] = stats[xidx + 2 * e + 1];
     s1[e] = sums[sidx + 2 * e];
     s2[e] = sums[sidx + 2 * e + 1];
   }
   const int p0 = split * g.pix_per_split;
   int p1 = p0 + g.pix_per_split;
   p1 = p1 < g.HW ? p1 : g.HW;
-  const long long base = (long long)n * g.HW * g.Cs + c0;
+  const long long base = (long long)n * g.HW * g.Cs + c0, xbase = (long long)nx * g.HW * g.Cs + c0;
   for (int p = p0 + ty; p < p1; p += JPDSE_NORM_ILP * g.TY) {
     float v[JPDSE_NORM_ILP][VE], gr[JPDSE_NORM_ILP][VE];
 #pragma unroll
     for (int u = 0; u < JPDSE_NORM_ILP; ++u) {
       const int pu = p + u * g.TY;
       if (pu < p1) {
-        const long long off = base + (long long)pu * g.Cs;
-        JPDSE_LOAD_LAST(T, x + off, v[u]);
-        JPDSE_LOAD_LAST(T, dy + off, gr[u]);
+        JPDSE_LOAD_LAST(T, x + xbase + (long long)pu * g.Cs, v[u]);
+        JPDSE_LOAD_LAST(T, dy + base + (long long)pu * g.Cs, gr[u]);
       }
     }
 #pragma unroll
@@ -388,11 +391,12 @@ struct FusedGeom {
   int TX, TY, tx_shift;          // threads across 16-byte channel columns / pixels (TX * TY = 256)
   int col_blocks, splits, span;  // blocks per image across channels / pixels; pixels per block (TY * P)
   int nv;                        // floats per partial row: TX * VE * 2
+  int alias;                     // backward: images >= alias read the saved x / stats of image n - alias (0 = off)
 };
 
 static FusedGeom fused_geom(int N, int HW, int Cs, int VE, int P) {
   FusedGeom g;
-  g.N = N; g.HW = HW; g.Cs = Cs; g.cv = Cs / VE;
+  g.N = N; g.HW = HW; g.Cs = Cs; g.cv = Cs / VE; g.alias = 0;
   int tx = 1;
   while (tx < g.cv && tx < 16) tx <<= 1;       // <= 256 contiguous bytes per pixel and block
   g.TX = tx; g.TY = 256 / tx;
@@ -588,14 +592,15 @@ __global__ __launch_bounds__(256, (P == 8 ? 3 : 2)) void inorm_reg_bwd_kernel(co
   const int col = cb * g.TX + tx;
   const bool on = col < g.cv;
   const int c0 = (on ? col : 0) * VE;
-  const long long base = (long long)n * g.HW * g.Cs + c0;
+  const int nx = n >= g.alias ? n - g.alias : n;      // the saved forward image of gradient image n
+  const long long base = (long long)n * g.HW * g.Cs + c0, xbase = (long long)nx * g.HW * g.Cs + c0;
   const int p0 = split * g.span + ty;
   u32x4 xv[P], gv[P];
 #pragma unroll
   for (int i = 0; i < P; ++i) {
     const int p = p0 + i * g.TY;
     if (on && p < g.HW) {
-      xv[i] = *reinterpret_cast<const u32x4*>(x + base + (long long)p * g.Cs);
+      xv[i] = *reinterpret_cast<const u32x4*>(x + xbase + (long long)p * g.Cs);
       gv[i] = *reinterpret_cast<const u32x4*>(dy + base + (long long)p * g.Cs);
     }
   }
@@ -603,7 +608,7 @@ __global__ __launch_bounds__(256, (P == 8 ? 3 : 2)) void inorm_reg_bwd_kernel(co
 #pragma unroll
   for (int e = 0; e < 8; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
   {
-    const float* st = stats + ((long long)n * g.Cs + c0) * 2;
+    const float* st = stats + ((long long)nx * g.Cs + c0) * 2;
 #pragma unroll
     for (int e = 0; e < VE; ++e) { mean[e] = st[2 * e]; rstd[e] = st[2 * e + 1]; }
   }
@@ -763,10 +768,15 @@ struct NormCall {
   void* out;
   float* stats;          // written by the forward, read by the backward
   void* stream;
+  int alias;             // backward over more gradient images than saved ones: images >= alias read x / stats of image n - alias (0 = off)
 };
 
+// an aliased backward (d->alias != 0) splits the pixels as the call over the saved batch does: each image's sums are then added
+// in that call's order
 static MomentGeom moment_geom(const jpdse_inorm_desc* d) {
-  return moment_geom(d->N, d->H * d->W, cpad(d->C), vec_elems(d->dtype));
+  MomentGeom g = moment_geom(d->N - d->alias, d->H * d->W, cpad(d->C), vec_elems(d->dtype));
+  g.N = d->N;
+  return g;
 }
 // grid of the MomentGeom kernels (moment_kernel, inorm_apply_*): a block per (image, pixel split, TX channel columns)
 static dim3 moment_grid(const MomentGeom& g) { return dim3(g.N * g.splits * ((g.cv + g.TX - 1) / g.TX)); }
@@ -787,10 +797,11 @@ static size_t ws_bytes_for(const jpdse_inorm_desc* d) {
 
 // inorm_reg_{fwd,bwd}_kernel<T, 8, PHASE>.  `part`: the partial rows (PHASE 1-2) or the producer's `mslots` slots (PHASE 3).
 template <typename T, int PHASE, bool BWD>
-static int launch_reg(const NormCall& c, const FusedGeom& fg, float* part, int mslots = 0) {
+static int launch_reg(const NormCall& c, FusedGeom fg, float* part, int mslots = 0) {
   static const char* const what[2][3] = {{"inorm rows fwd", "inorm apply-from-rows fwd", "inorm apply-from-slots fwd"},
                                          {"inorm rows bwd", "inorm apply-from-rows bwd", "inorm apply-from-slots bwd"}};
   const jpdse_inorm_desc* d = c.d;
+  fg.alias = BWD ? c.alias : 0;
   if constexpr (BWD)
     return launch256(what[1][PHASE - 1], inorm_reg_bwd_kernel<T, 8, PHASE>, fused_grid(fg), c.stream, cptr<T>(c.x), cptr<T>(c.in2),
                      mptr<T>(c.out), c.stats, part, (unsigned*)nullptr, d->act, d->slope, fg, mslots);
@@ -819,7 +830,8 @@ template <typename T, bool BWD> static int try_reg_from_slots(const NormCall& c,
 }
 
 // third kernel of moment -> finalize -> apply; `sums`: backward only
-template <typename T, bool BWD> static int launch_apply(const NormCall& c, const MomentGeom& g, const float* sums = nullptr) {
+template <typename T, bool BWD> static int launch_apply(const NormCall& c, MomentGeom g, const float* sums = nullptr) {
+  g.alias = BWD ? c.alias : 0;
   if constexpr (BWD)
     return launch256("inorm apply bwd", inorm_apply_bwd_kernel<T>, moment_grid(g), c.stream, cptr<T>(c.x), cptr<T>(c.in2),
                      mptr<T>(c.out), c.stats, sums, c.d->act, c.d->slope, g);
@@ -845,7 +857,8 @@ template <typename T> static int inorm_fwd_t(const NormCall& c, void* ws) {
 template <typename T> static int inorm_bwd_t(const NormCall& c, void* ws) {
   if (const int r = try_reg<T, true>(c, ws); r != kNoRegForm) return r;
   const jpdse_inorm_desc* d = c.d;
-  const MomentGeom g = moment_geom(d);
+  MomentGeom g = moment_geom(d);
+  g.alias = c.alias;
   float* partial = mptr<float>(ws);
   float* sums = reinterpret_cast<float*>(mptr<char>(ws) + ws_sums_offset(d, g));
   if (int rc = launch256("inorm moment bwd", moment_kernel<T, true>, moment_grid(g), c.stream, cptr<T>(c.x), cptr<T>(c.in2),
@@ -883,6 +896,8 @@ static int validate(const jpdse_inorm_desc* d) {
   JPDSE_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->C > 0, "inorm: non-positive shape");
   JPDSE_REQUIRE(d->act == JPDSE_ACT_NONE || d->act == JPDSE_ACT_RELU || d->act == JPDSE_ACT_LRELU,
                 "inorm: unsupported activation %d", d->act);
+  // images n < alias read image n, images n >= alias image n - alias, of tensors that hold N - alias images
+  JPDSE_REQUIRE(d->alias >= 0 && 2 * (long long)d->alias <= d->N, "inorm: alias %d outside [0, N / 2 = %d / 2]", d->alias, d->N);
   return JPDSE_OK;
 }
 
@@ -927,6 +942,7 @@ size_t jpdse_inorm_workspace_size(const jpdse_inorm_desc* d) {
 int jpdse_inorm_fwd(const jpdse_inorm_desc* d, const void* x, const void* residual, void* y, float* stats, void* ws,
                     size_t ws_bytes, void* stream) {
   if (int rc = inorm_enter("inorm_fwd", d, x && y && stats, "null pointer", &residual, WS_FULL, ws, ws_bytes)) return rc;
+  JPDSE_REQUIRE(d->alias == 0, "inorm_fwd: the descriptor's alias is for jpdse_inorm_bwd alone");
   const NormCall c = {d, x, residual, y, stats, stream};
   return timed_by_dtype(d, stream, JPDSE_HBM_INORM_FWD, d->has_residual ? 4.0 : 3.0,
                         [&](auto tag) { return inorm_fwd_t<decltype(tag)>(c, ws); });
@@ -935,7 +951,7 @@ int jpdse_inorm_fwd(const jpdse_inorm_desc* d, const void* x, const void* residu
 int jpdse_inorm_bwd(const jpdse_inorm_desc* d, const void* x, const float* stats, const void* dy, void* dx, void* ws,
                     size_t ws_bytes, void* stream) {
   if (int rc = inorm_enter("inorm_bwd", d, x && stats && dy && dx, "null pointer", nullptr, WS_FULL, ws, ws_bytes)) return rc;
-  const NormCall c = {d, x, dy, dx, const_cast<float*>(stats), stream};
+  const NormCall c = {d, x, dy, dx, const_cast<float*>(stats), stream, d->alias};
   return timed_by_dtype(d, stream, JPDSE_HBM_INORM_BWD, 5.0, [&](auto tag) { return inorm_bwd_t<decltype(tag)>(c, ws); });
 }
 
@@ -944,6 +960,7 @@ int jpdse_inorm_bwd_from_sums(const jpdse_inorm_desc* d, const void* x, const fl
   if (int rc = inorm_enter("inorm_bwd_from_sums", d, x && stats && dy && dx && sums && slots > 0, "null pointer / no slots",
                            nullptr, WS_SUMS, ws, ws_bytes))
     return rc;
+  JPDSE_REQUIRE(d->alias == 0, "inorm_bwd_from_sums: the descriptor's alias is for jpdse_inorm_bwd alone");
   const NormCall c = {d, x, dy, dx, const_cast<float*>(stats), stream};
   return timed_by_dtype(d, stream, JPDSE_HBM_INORM_BWD, 3.0,        // x, dy read once, dx written
                         [&](auto tag) { return inorm_bwd_from_sums_t<decltype(tag)>(c, sums, slots, ws); });
@@ -954,6 +971,7 @@ int jpdse_inorm_fwd_from_moments(const jpdse_inorm_desc* d, const void* x, const
   if (int rc = inorm_enter("inorm_fwd_from_moments", d, x && y && stats && moments && slots > 0, "null pointer / no slots",
                            &residual, WS_NONE, nullptr, 0))
     return rc;
+  JPDSE_REQUIRE(d->alias == 0, "inorm_fwd_from_moments: the descriptor's alias is for jpdse_inorm_bwd alone");
   const NormCall c = {d, x, residual, y, stats, stream};
   return timed_by_dtype(d, stream, JPDSE_HBM_INORM_FWD, d->has_residual ? 3.0 : 2.0,
                         [&](auto tag) { return inorm_from_moments_t<decltype(tag)>(c, moments, slots); });

@@ -26,6 +26,7 @@ struct Thin1DgradArgs {
   long long b_stride;
   int Lk;
   int nseg, segw;        // a row of dx = nseg runs of segw pixels; one run = one work item of a pixel lane
+  int addend_n;          // only images < addend_n take the addend (0 = every image)
 };
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -90,7 +91,7 @@ __global__ __launch_bounds__(256) void thin1_dgrad_kernel(const Thin1DgradArgs a
 #pragma unroll
       for (int u = 0; u < R; ++u) win[v][u] = dyw[pl][u][v - 1];
     bf16_t* __restrict__ out = a.DX + (((long long)n * a.H + ih) * a.W + w0) * a.Cs + cg * 8;
-    const bf16_t* __restrict__ add = a.addend != nullptr ? a.addend + (out - a.DX) : nullptr;
+    const bf16_t* __restrict__ add = (a.addend != nullptr && (a.addend_n == 0 || n < a.addend_n)) ? a.addend + (out - a.DX) : nullptr;
     for (int i0 = 0; i0 < wn; i0 += 4) {
       u32x4 adv[4];
       if (add != nullptr) {

@@ -495,13 +495,45 @@ class Pix2PixHDModel(CodedCalls, BaseModel):
       self._one = torch.ones(1, dtype=torch.float32, device=dev)
     return self._one
 
-  def backward_G(self, state, w_gan, w_feat, w_vgg, w_dist):
-    """d(loss_G)/d(netG params), loss_G = w_gan*G_GAN + w_feat*G_GAN_Feat + w_vgg*G_VGG + w_dist*G_Dist."""
+  # One backward walk of D for loss_G and loss_D.  False: the two walks of before, loss_G's through the fake
+  # half and loss_D's through the whole batch (A/B measurements, tests/test_hip_d_backward_batched.py).  Under data parallelism
+  # (gradient buckets set) the two walks stay whatever this says: G's all-reduce hides behind the WHOLE D backward there, and the one
+  # walk would move D's data gradients and norm backward in front of G's backward, out of that window.
+  d_backward_batched = True
+
+  def backward_G(self, state, w_gan, w_feat, w_vgg, w_dist, w_d=0.0):
+    """d(loss_G)/d(netG params), loss_G = w_gan*G_GAN + w_feat*G_GAN_Feat + w_vgg*G_VGG + w_dist*G_Dist.  With w_d != 0 (train_step)
+    and the batched walk on, D's data gradients of loss_D = w_d * (D_fake + D_real) ride in the same walk of D and the weight
+    gradients of loss_D are left in state['d_wgrads'] for backward_D."""
     opt, B = self.opt, state['B']
     one = self._ones(state['fake'].t.device)
     fake, real = state['fake'], state['real']
     d_fake = None
-    if (w_gan != 0.0 or w_feat != 0.0) and state['pred'] is not None:
+    if (self.d_backward_batched and not self.grad_buckets and w_gan != 0.0 and w_d != 0.0 and state['pred'] is not None
+        and self.netD.can_bwd_batched()
+        and all(p.requires_grad for p in self.netD.parameters())):
+      dfeats, dpred = [], []
+      for i in range(opt.num_D):
+        feats = state['pred'][i]
+        row = []
+        for j, f in enumerate(feats[:-1]):
+          if w_feat == 0.0:
+            row.append(None)
+          elif state.get('d_feat') is not None and state['d_feat'][i][j] is not None:
+            row.append(state['d_feat'][i][j])
+          else:
+            row.append(ops.l1_bwd(f.batch_slice(0, B), f.batch_slice(B, 2 * B), one, w_feat / opt.num_D))
+        dfeats.append(row)
+        # the three loss heads' gradients of this scale in one buffer: [loss_G on fake ; loss_D on fake ; loss_D on real]
+        p = feats[-1]
+        dp = Act.empty(3 * B, p.H, p.W, p.C, p.dtype, p.t.device)
+        ops.mse_const_bwd(p.batch_slice(0, B), 1.0, one, w_gan, out=dp.batch_slice(0, B))
+        ops.mse_const_bwd(p.batch_slice(0, B), 0.0, one, w_d, out=dp.batch_slice(B, 2 * B))
+        ops.mse_const_bwd(p.batch_slice(B, 2 * B), 1.0, one, w_d, out=dp.batch_slice(2 * B, 3 * B))
+        dpred.append(dp)
+      d_fake, state['d_wgrads'] = self.netD.bwd_batched(state['d_ctx'], dfeats, dpred, B,
+                                                        (self.label_nc, self.label_nc + fake.C))
+    elif (w_gan != 0.0 or w_feat != 0.0) and state['pred'] is not None:
       dres = []
       for i in range(opt.num_D):
         row = []
@@ -569,6 +601,12 @@ class Pix2PixHDModel(CodedCalls, BaseModel):
     """d(loss_D)/d(netD params), loss_D = w_d * (D_fake + D_real)  (w_d = 0.5 in the trainer)."""
     if w_d == 0.0 or state['pred'] is None:
       return False
+    if state.get('d_wgrads') is not None:
+      # the batched walk of backward_G has run loss_D's data gradients: its weight gradients are what is left (one GPU only:
+      # under data parallelism the two walks run, DESIGN.md §6)
+      for call in state.pop('d_wgrads'):
+        call()
+      return True
     opt, B = self.opt, state['B']
     one = self._ones(state['fake'].t.device)
     dres = []
@@ -602,7 +640,8 @@ class Pix2PixHDModel(CodedCalls, BaseModel):
     # Order: both backward passes first, then the two Adams.  The reference steps G before it back-propagates loss_D
     # (pix2pixHD_trainer.py:64-78), but loss_D's graph -- D on fake.detach() and on the real image -- does not contain G's
     # weights, so its gradients are the same numbers either way, bit for bit.  Under data parallelism this gives G's
-    # gradient all-reduce (93 % of the bytes) the whole D backward to hide behind (launch_all below), instead of the
+    # gradient all-reduce (93 % of the bytes) the whole D backward to hide behind (launch_all below; which is why the one walk of D
+    # for both losses, backward_G, is left to the single-GPU step: it would move most of that backward in front of launch_all), instead of the
     # ResnetBlock GEMMs whose grids are exactly one workgroup per CU and take a second round when RCCL holds any CU.
     bg, bd = self.grad_buckets.get('G'), self.grad_buckets.get('D')
     # Opt-in timeline of the data-parallel schedule (self.ddp_timeline = []: one dict of timing events per step, recorded on the
@@ -617,14 +656,15 @@ class Pix2PixHDModel(CodedCalls, BaseModel):
         ev.record()
         marks[name] = ev
 
-    did_G = self.backward_G(state, w_gan, w_feat, w_vgg, w_dist)
+    w_d = 0.0 if opt.no_d_gan_loss else 0.5
+    did_G = self.backward_G(state, w_gan, w_feat, w_vgg, w_dist, w_d)
     mark('g_bwd_end')
     if did_G and bg is not None:
       bg.launch_all()                  # no-op for buckets already started from the per-layer hooks (defer=False)
     # (Measured and not adopted, round 4: Adam(G) + the panel re-pack -- 1.2 ms of HBM-bound streaming -- on a second stream
     # beside the discriminator's backward: 26.36-26.40 ms per step against 26.15-26.33 serial, profiles/r04_adam_side_stream_ab.txt.
     # The D backward is itself half HBM-bound passes, and its GEMM launches lose more to the shared CUs than Adam gains.)
-    did_D = self.backward_D(state, 0.0 if opt.no_d_gan_loss else 0.5)
+    did_D = self.backward_D(state, w_d)
     mark('d_bwd_end')
     if did_G:
       if bg is not None:

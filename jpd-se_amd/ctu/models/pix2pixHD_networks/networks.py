@@ -469,6 +469,24 @@ class NLayerDiscriminator(nn.Module):
     return d
 
 
+  def bwd_batched(self, ctxs, dfeats, dpred, B, later, dx_channels):
+    """The backward walks of loss_G and loss_D as one: ctxs is the saved forward of [fake ; real] (2B images),
+    dpred the gradient w.r.t. the last feature for 3B images [loss_G on fake ; loss_D on fake ; loss_D on real], dfeats[j]
+    (j < last; B images or None) loss_G's feature-matching gradients.  Every stage's norm backward and data gradient run
+    once over the 3B images; the weight gradients (loss_D's: images B..3B) are appended to `later` as calls for the owner to
+    make.  Returns the gradient w.r.t. input channels dx_channels of the B fake images (loss_G's).  Needs fuse_lrelu0."""
+    assert self.fuse_lrelu0
+    d = dpred
+    for j in range(len(self._stages) - 1, 0, -1):
+      lrelu0 = dict(relu_input=True, input_slope=self._stages[0].slope) if j == 1 else {}
+      d = self._stages[j].bwd_batched(ctxs[j], d, B, later, addend=dfeats[j - 1], **lrelu0)
+    # stage 0 starts from dz: loss_D needs its weight gradient only, loss_G the gradient to the image channels only
+    st0 = self._stages[0]
+    if st0.weight.requires_grad:
+      later.append(lambda: st0.bwd(ctxs[0], d.batch_slice(B, d.N), need_dx=False, need_dw=True, dy_is_dz=True))
+    return st0.bwd_input_slice(ctxs[0].slice(0, B), d.batch_slice(0, B), dx_channels[0], dx_channels[1], dy_is_dz=True)
+
+
 class MultiscaleDiscriminator(nn.Module):
   """networks.py:371-419 with getIntermFeat hard-wired True (pix2pixHD_model.py:162-163)."""
 
@@ -513,6 +531,21 @@ class MultiscaleDiscriminator(nn.Module):
           d = ops.add_(d, ops.avgpool3s2_bwd(dx, H, W))
         dx = d
     return dx
+
+  def bwd_batched(self, ctxs, dfeats, dpred, B, dx_channels):
+    """NLayerDiscriminator.bwd_batched for every scale.  dfeats[i][j] / dpred[i]: scale i's arguments.  Returns (the gradient
+    w.r.t. input channels dx_channels of the B fake images, the weight-gradient calls still to be made, in walk order)."""
+    dx, later = None, []
+    for i in range(self.num_D - 1, -1, -1):
+      c, H, W = ctxs[i]
+      d = self._scales[self.num_D - 1 - i].bwd_batched(c, dfeats[i], dpred[i], B, later, dx_channels)
+      if dx is not None:          # gradient arriving from the coarser scale through AvgPool
+        d = ops.add_(d, ops.avgpool3s2_bwd(dx, H, W))
+      dx = d
+    return dx, later
+
+  def can_bwd_batched(self):
+    return all(s.fuse_lrelu0 for s in self._scales)
 
   def forward(self, input, keep_input=False):
     if keep_input:

@@ -30,7 +30,8 @@ class ConvDesc(ctypes.Structure):
 class InormDesc(ctypes.Structure):
   _fields_ = [('dtype', ctypes.c_int32), ('N', ctypes.c_int32), ('H', ctypes.c_int32),
               ('W', ctypes.c_int32), ('C', ctypes.c_int32), ('act', ctypes.c_int32),
-              ('slope', ctypes.c_float), ('eps', ctypes.c_float), ('has_residual', ctypes.c_int32)]
+              ('slope', ctypes.c_float), ('eps', ctypes.c_float), ('has_residual', ctypes.c_int32),
+              ('alias', ctypes.c_int32)]
 
 
 class PackEntry(ctypes.Structure):
@@ -248,6 +249,7 @@ SIGNATURES = {
     'jpdse_conv_dgrad_relu': (_I32, [_CD, _P, _P, _P, _P, _P, _SZ, _P]),
     'jpdse_conv_dgrad_fused': (_I32, [_CD, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     'jpdse_conv_dgrad_fused_lrelu': (_I32, [_CD, _P, _P, _P, _F, _P, _P, _P, _SZ, _P]),
+    'jpdse_conv_dgrad_batched': (_I32, [_CD, _P, _P, _P, _F, _P, _I32, _I32, _P, _P, _SZ, _P]),
     'jpdse_conv_dgrad_nsum_slots': (_I32, [_CD]),
     'jpdse_conv_dgrad_fused_nsums': (_I32, [_CD, _P, _P, _P, _P, _P, _P, _P, _I32, _F, _P, _P, _SZ, _P]),
     'jpdse_conv_wgrad': (_I32, [_CD, _P, _P, _P, _P, _SZ, _P]),

@@ -216,6 +216,21 @@ class HipConv2d(nn.Module):
                                     relu_input=x if relu_input else None, addend=addend)
     return ops.conv_dgrad(d, dz, dgrad_pack, relu_input=x if relu_input else None, addend=addend, mask_slope=input_slope)
 
+  def bwd_batched(self, ctx, dy, B, later, relu_input=False, addend=None, input_slope=0.0):
+    """One backward call for two losses (the PatchGAN under loss_G and loss_D): `ctx` is the saved forward of 2B images and
+    dy holds 3B gradient images [loss_G on images 0..B ; loss_D on images 0..2B].  The data gradient runs over all 3B in one
+    launch, gradient image n >= B reading the saved operands of image n - B (jpdse_conv_dgrad_batched); addend (B images)
+    joins the loss_G part only.  The weight gradient is loss_D's: images B..3B of dy against the saved 2B inputs, appended
+    to `later` as a call for the owner to make.  For layers without an activation of their own."""
+    assert not self.transposed and self.act == ACT_NONE
+    _, dgrad_pack = self.packs()
+    x, _ = ctx.items
+    assert dy.N == x.N + B
+    if self.weight.requires_grad:
+      later.append(lambda: self.bwd(ctx, dy.batch_slice(B, dy.N), need_dx=False, need_dw=True))
+    return ops.conv_dgrad_batched(self._desc(dy.N, x.H, x.W), dy, dgrad_pack, B, relu_input=x if relu_input else None,
+                                  addend=addend, mask_slope=input_slope)
+
   def bwd_input_slice(self, ctx, dy, c0, c1, dy_is_dz=False):
     """Data gradient w.r.t. input channels [c0, c1) only (no weight gradient): the conv restricted to those input
     channels has the filter w[:, c0:c1], and its data gradient is that slice of the full one.  Used where only part
@@ -485,6 +500,13 @@ class ConvNormAct(object):
     c1, c2 = ctx.items
     dh = self.norm.bwd(c2, dy)
     return self.conv.bwd(c1, dh, need_dx, need_dw, addend=addend, **conv_kw)
+
+  def bwd_batched(self, ctx, dy, B, later, addend=None, **conv_kw):
+    """HipConv2d.bwd_batched behind the norm's backward over the same 3B gradient images (jpdse_inorm_bwd with the descriptor's alias)."""
+    c1, c2 = ctx.items
+    x, stats = c2.items
+    dh = ops.inorm_bwd_aliased(x, stats, dy, B, self.norm.act, self.norm.slope, self.norm.eps)
+    return self.conv.bwd_batched(c1, dh, B, later, addend=addend, **conv_kw)
 
   def dy_sink(self, ctx):
     """The norm that consumes the gradient handed to bwd(): run_chain_bwd passes it to the stage that produces that gradient."""

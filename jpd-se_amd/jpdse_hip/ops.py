@@ -193,6 +193,20 @@ def conv_dgrad(d, dy, dgrad_pack, relu_input=None, addend=None, mask_slope=0.0):
   return dx
 
 
+def conv_dgrad_batched(d, dy, dgrad_pack, alias, relu_input=None, addend=None, mask_slope=0.0):
+  """conv_dgrad over d.N gradient images of which image n >= alias belongs to the saved forward image n - alias
+  (jpdse_conv_dgrad_batched): relu_input holds d.N - alias images, and addend, when given, covers the first addend.N gradient
+  images only.  Each image's dx is what conv_dgrad gives for it."""
+  dx = Act.empty(d.N, d.H, d.W, d.C, d.dtype, dy.t.device)
+  assert relu_input is None or relu_input.N == d.N - alias, (relu_input.N, d.N, alias)
+  ws, n = _conv_ws(d, dy.t.device)
+  check(lib().jpdse_conv_dgrad_batched(ctypes.byref(d), _p(dy.t), _p(dgrad_pack), _p(relu_input.t if relu_input is not None else None),
+                                       float(mask_slope), _p(addend.t if addend is not None else None), int(alias),
+                                       int(addend.N) if addend is not None else 0, _p(dx.t), _p(ws), ws.numel(), _stream()),
+        'conv_dgrad_batched')
+  return dx
+
+
 def conv_dgrad_nsum_slots(d):
   """Blocks per image whose norm-backward sums the layer's data-gradient kernel can write (0: no such epilogue)."""
   return int(lib().jpdse_conv_dgrad_nsum_slots(ctypes.byref(d)))
@@ -277,6 +291,19 @@ def inorm_bwd(x, stats, dy, act, slope=0.2, eps=1e-5):
     return dx
   check(lib().jpdse_inorm_bwd(ctypes.byref(d), _p(x.t), _p(stats), _p(dy.t), _p(dx.t), _p(ws), ws.numel(), _stream()),
         'inorm_bwd')
+  return dx
+
+
+def inorm_bwd_aliased(x, stats, dy, alias, act, slope=0.2, eps=1e-5):
+  """inorm_bwd over dy.N gradient images of which image n >= alias belongs to the saved image n - alias of x / stats
+  (jpdse_inorm_bwd with the descriptor's `alias`; x holds dy.N - alias images)."""
+  assert x.N == dy.N - alias and tuple(x.t.shape[1:]) == tuple(dy.t.shape[1:]), (tuple(x.t.shape), tuple(dy.t.shape), alias)
+  d = InormDesc(x.dtype, dy.N, x.H, x.W, x.C, act, slope, eps, 0, int(alias))
+  dx = dy.empty_like()
+  n = lib().jpdse_inorm_workspace_size(ctypes.byref(d))
+  ws = workspace(n, x.t.device)
+  check(lib().jpdse_inorm_bwd(ctypes.byref(d), _p(x.t), _p(stats), _p(dy.t), _p(dx.t), _p(ws), ws.numel(), _stream()),
+        'inorm_bwd (aliased)')
   return dx
 
 

@@ -1,7 +1,7 @@
 """Per-conv-call profile of one real train step at the bench workload: wraps ops.conv_fwd /
 conv_dgrad / conv_wgrad with event pairs (includes their pad / fold / expand helper kernels) and
 prints every distinct (op, shape) with its FLOPs, time and TFLOP/s, sorted by time.
-Usage: python scripts/layer_profile.py [--batch 4] [--steps 3] [--fast MODE]"""
+Usage: python scripts/layer_profile.py [--batch 4] [--steps 3] [--fast MODE] [--two-walks]"""
 import sys, os, argparse, collections, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'jpd-se_amd'))
@@ -15,6 +15,7 @@ ap.add_argument('--height', type=int, default=512)
 ap.add_argument('--netG', default='global')
 ap.add_argument('--dtype', default='bf16')
 ap.add_argument('--fast', type=int, default=1)
+ap.add_argument('--two-walks', action='store_true', help='walk D backwards twice (loss_G: N = B, loss_D: N = 2B) instead of once over 3B')
 ap.add_argument('--no-vgg', action='store_true', help='BASELINE config 2: no VGG loss, VGG not run')
 args = ap.parse_args()
 
@@ -31,6 +32,8 @@ opt = default_opt(gpu_ids=[0], print_losses=False, compute_dtype=args.dtype, use
                   **(dict(no_vgg_loss=True, skip_unused_losses=True) if args.no_vgg else {}))
 torch.manual_seed(1234)
 trainer = get_trainer(opt)(opt, 'train')
+if args.two_walks:
+  trainer.model.d_backward_batched = False
 xd = synthetic_batch(args.batch, args.height, args.width, seed=1234)
 xd = {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in xd.items()}
 for _ in range(2):
@@ -85,6 +88,18 @@ def _dgrad_nsums(d, *a, **k):
   records.append((_key('dgrad', d), e0, e1, c1 - c0))
   return r
 ops.conv_dgrad_nsums = _dgrad_nsums
+# the PatchGAN's data gradients over the 3B gradient images of the one walk for loss_G and loss_D
+_db = ops.conv_dgrad_batched
+def _dgrad_batched(d, *a, **k):
+  e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+  e0.record()
+  c0 = time.perf_counter()
+  r = _db(d, *a, **k)
+  c1 = time.perf_counter()
+  e1.record()
+  records.append((_key('dgrad', d), e0, e1, c1 - c0))
+  return r
+ops.conv_dgrad_batched = _dgrad_batched
 t0 = torch.cuda.Event(enable_timing=True); t1 = torch.cuda.Event(enable_timing=True)
 t0.record()
 for _ in range(args.steps):
