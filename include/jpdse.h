@@ -1114,6 +1114,48 @@ typedef struct jpdse_vq_quantize_bwd_grouped_args {
 } jpdse_vq_quantize_bwd_grouped_args;
 int jpdse_vq_quantize_bwd_grouped(const jpdse_vq_quantize_bwd_grouped_args* args);
 
+/* ---- soft-to-hard vector quantizer: entropy-constrained assignment (vq_ec.hip) ---------------------------------
+ * Vectors and groups as in the rate term above (G | M, g(m) = m % G).  d[m][k] is the direct score of jpdse_vq_hard_fwd.
+ *   ec_assign   index[m] = arg-min_k d[m][k] + bias[g(m)][k], the lowest k on equal cost.  bias fp32 [G][L], or NULL for all
+ *               zero; the caller scales it (the kernel knows nothing about code lengths); one fp32 add per centre after the
+ *               score loop, so a zero or NULL bias gives jpdse_vq_hard_fwd's index for index.  +inf is a legal entry: that
+ *               centre is never chosen while another of its row is finite; a row of +inf alone gives index 0.
+ *               hist int32 [G][L], or NULL: hist[g][k] = the vectors of group g with index k (exact).
+ *               sse fp64 [G], or NULL: sse[g] = the sum of the chosen d[m][index[m]] over group g, WITHOUT the bias; each d is
+ *               widened to fp64 before it is added.
+ *   ec_lengths  n[g] = sum_k hist[g][k]; bias[g][k] = lambda (log2 n[g] - log2 hist[g][k]) in fp64, rounded to fp32; +inf
+ *               where hist[g][k] <= 0; exact zeros everywhere when lambda == 0.  bits fp64 [G]: bits[g] = sum_k hist[g][k]
+ *               (log2 n[g] - log2 hist[g][k]), the ideal code length of the group under its own histogram.  bias or bits may be
+ *               NULL, not both.
+ * No atomics: every block sums into a table of its own, the tables are merged in block order; two calls give identical bits.
+ * ws of ec_assign, with a hist or an sse: jpdse_vq_ec_workspace_size(M, D, L, G) bytes, 8-byte aligned (host only; 0 outside the
+ * limits 1 <= D <= 32, 2 <= L <= 512, M >= 1, M * L < 2^31, G >= 1, M % G == 0, G * L <= 65536).  JPDSE_EINVAL before any
+ * launch: those limits, a bad dtype, NULL x, code_book or index, a workspace too small; ec_lengths: L, G * L, a lambda that
+ * is negative or not finite, NULL hist, bias and bits both NULL. */
+size_t jpdse_vq_ec_workspace_size(int32_t M, int32_t D, int32_t L, int32_t G);
+typedef struct jpdse_vq_ec_assign_args {
+  int32_t dtype, M, D, L, G;
+  const void* x;           /* [M][D] in `dtype` */
+  const float* code_book;  /* [L][D] */
+  const float* bias;       /* [G][L], or NULL */
+  int32_t* index;          /* [M] */
+  int32_t* hist;           /* [G][L], or NULL */
+  double* sse;             /* [G], or NULL */
+  void* ws;
+  size_t ws_bytes;
+  void* stream;
+} jpdse_vq_ec_assign_args;
+int jpdse_vq_ec_assign(const jpdse_vq_ec_assign_args* args);
+typedef struct jpdse_vq_ec_lengths_args {
+  int32_t G, L;
+  double lambda;
+  const int32_t* hist;     /* [G][L] */
+  float* bias;             /* [G][L], or NULL */
+  double* bits;            /* [G], or NULL */
+  void* stream;
+} jpdse_vq_ec_lengths_args;
+int jpdse_vq_ec_lengths(const jpdse_vq_ec_lengths_args* args);
+
 /* ---- optimizer ---------------------------------------------------------------------- */
 /* torch.optim.Adam (model.py:275,279) over a table of tensors, one launch.  `table` is a
  * device array of jpdse_adam_entry; bias corrections are computed from `step` (1-based). */

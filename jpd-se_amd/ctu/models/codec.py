@@ -14,6 +14,13 @@ from jpdse_hip import ops
 from ctu.utils import bitstream, entropy, vqplane, vqstream
 
 
+def check_ec_arguments(rate_lambda, n_iter):
+  """float(rate_lambda) after the refusals of S2HVQ.encode_ec, which need no device."""
+  from ctu.quantizers.s2h_vq import _ec_lambda, _ec_iterations
+  _ec_iterations(n_iter)
+  return _ec_lambda(rate_lambda)
+
+
 class _Codec:
 
   def __init__(self, netE, cdtype):
@@ -76,8 +83,13 @@ class BinaryCodec(_Codec):
       entropy.check_payload(p, C, '%s: payload %d' % (who, j))
     return geo
 
-  def code(self, src):
-    """The eval-mode code of the source Act (the caller holds the encoder in eval mode)."""
+  def check_rate_lambda(self, rate_lambda, n_iter, who):
+    """ValueError for a rate_lambda > 0: the entropy-constrained assignment is the vector quantizer's.  Host only."""
+    if check_ec_arguments(rate_lambda, n_iter) > 0:
+      raise ValueError('%s: rate_lambda > 0 (the entropy-constrained code) needs --encoder_quantizer s2hvq' % who)
+
+  def code(self, src, rate_lambda=0.0, n_iter=2):
+    """The eval-mode code of the source Act (the caller holds the encoder in eval mode).  rate_lambda is 0 here."""
     return self.netE.code(src)
 
   def features_of_code(self, code, geo, device, who):
@@ -115,6 +127,7 @@ class VQIndexCodec(_Codec):
 
   RATE_OPTION = 'lambda_vq_rate'
   context_coder = False
+  ec_reports = None                           # the per-image reports of the last code() with rate_lambda > 0
   COST_CODERS = (None, 'index', 'plane')      # what cost() prices: the kept file, the .jpdv model, the .jpdw model
   INDEX_STREAMS_PER_GROUP = 8                 # payloads(): (C / D) * 8 streams per .jpdv blob
 
@@ -160,10 +173,20 @@ class VQIndexCodec(_Codec):
         raise ValueError('%s: blob %d holds %d x %d indices, a %d x %d label map carries %d' % (who, j, n, cl, H, W, code_len))
     return geo
 
-  def code(self, src):
+  def check_rate_lambda(self, rate_lambda, n_iter, who):
+    """ValueError for a rate_lambda that is negative or not finite, or an n_iter that is no int >= 0.  Host only."""
+    check_ec_arguments(rate_lambda, n_iter)
+
+  def code(self, src, rate_lambda=0.0, n_iter=2):
     """The eval-mode code of the source Act: per image the index of the nearest centre of every group of D channels, pixel by
-    pixel, groups ascending inside a pixel."""
-    return self.netE.vq_code(src).to(torch.int64)
+    pixel, groups ascending inside a pixel.  rate_lambda > 0: the entropy-constrained code instead -- the
+    encoder's first half runs once, then S2HVQ.encode_ec per image with groups = C / D on that image's rows of the features;
+    the per-image reports stay in `ec_reports`.  rate_lambda == 0 takes exactly the path above."""
+    if rate_lambda == 0:
+      self.ec_reports = None
+      return self.netE.vq_code(src).to(torch.int64)
+    index, self.ec_reports = self.netE.vq_code_ec(src, float(rate_lambda), n_iter)
+    return index.to(torch.int64)
 
   def features_of_code(self, code, geo, device, who):
     _, H, W, _, L, _ = geo

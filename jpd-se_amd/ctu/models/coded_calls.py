@@ -42,10 +42,12 @@ class CodedCalls(object):
       raise ValueError('%s: the vector-quantised code needs --encoder_quantizer s2hvq' % who)
     return self.codec
 
-  def _eval_code(self, codec, x_dict):
+  def _eval_code(self, codec, x_dict, rate_lambda=0.0, n_iter=2):
     """The encoder's eval-mode code of x_dict (the decoded frame with --use_compressed) in the codec's form."""
     pre = self.preprocess(x_dict, build_base=False)
-    return self._encoder_eval(lambda: codec.code(pre['src']))
+    if rate_lambda == 0:
+      return self._encoder_eval(lambda: codec.code(pre['src']))
+    return self._encoder_eval(lambda: codec.code(pre['src'], rate_lambda, n_iter))
 
   def _code_act(self, x_dict, who='binary codes'):
     """The encoder's eval-mode bitstream of x_dict as an NHWC Act."""
@@ -87,12 +89,28 @@ class CodedCalls(object):
       return shannon / b.N, actual / b.N
 
   # ---- the vector-quantised code (extension) ------------------------------------------------------------------
-  def get_vq_code(self, x_dict):
+  def get_vq_code(self, x_dict, rate_lambda=0.0, n_iter=2):
     """The eval-mode code of the vector-quantizer bottleneck: int64 [N, h * w * C / D] on the device, per image the index of
-    the nearest centre of every group of D channels, pixel by pixel, groups ascending inside a pixel."""
+    the nearest centre of every group of D channels, pixel by pixel, groups ascending inside a pixel.
+    rate_lambda > 0: the entropy-constrained code -- every index minimises |x - c_k|^2 + rate_lambda * the
+    code length of k under the histogram of its image and channel group, n_iter rounds of S2HVQ.encode_ec per image.  An
+    ordinary code: decode, get_coded's files and both cost walks take it unchanged.  ValueError, before any device work, for
+    a rate_lambda that is negative or not finite and an n_iter that is no int >= 0.  The defaults give today's bits."""
     codec = self._vq_codec('get_vq_code')
+    codec.check_rate_lambda(rate_lambda, n_iter, 'get_vq_code')
     with torch.no_grad():
-      return self._eval_code(codec, x_dict)
+      return self._eval_code(codec, x_dict, rate_lambda, n_iter)
+
+  def get_vq_ec_report(self, x_dict, rate_lambda, n_iter=2):
+    """The per-image reports of the entropy-constrained code get_vq_code(x_dict, rate_lambda, n_iter): a list of N dicts
+    (distortion, bits, cost: n_iter + 1 Python floats each; S2HVQ.encode_ec).  rate_lambda == 0 runs the same rounds with a
+    zero bias: every entry repeats the plain code's figures."""
+    codec = self._vq_codec('get_vq_ec_report')
+    codec.check_rate_lambda(rate_lambda, n_iter, 'get_vq_ec_report')
+    with torch.no_grad():
+      pre = self.preprocess(x_dict, build_base=False)
+      _, reports = self._encoder_eval(lambda: self.netE.vq_code_ec(pre['src'], float(rate_lambda), n_iter))
+      return reports
 
   def get_vq_rate(self, x_dict):
     """The hard-mode rate term of the eval-mode code in bits per pixel of the batch, a Python float: the
@@ -185,6 +203,16 @@ class CodedCalls(object):
     with torch.no_grad():
       return codec.payloads(self._eval_code(codec, x_dict), x_dict)
 
+  def get_coded_ec(self, x_dict, rate_lambda=0.0, n_iter=2):
+    """get_coded at another point of the rate-distortion curve: the blobs of get_vq_code(x_dict, rate_lambda,
+    n_iter).  decode_coded takes them unchanged.  The defaults give get_coded's bytes.  (A call of its own: the signature of
+    get_coded is pinned.)  ValueError, before any device work: rate_lambda > 0 without --encoder_quantizer s2hvq, and what
+    get_vq_code refuses."""
+    codec = self.codec or self._binary_codec()
+    codec.check_rate_lambda(rate_lambda, n_iter, 'get_coded_ec')
+    with torch.no_grad():
+      return codec.payloads(self._eval_code(codec, x_dict, rate_lambda, n_iter), x_dict)
+
   def decode_coded(self, payloads, x_dict):
     """decode() from what get_coded returned: a list of one `bytes` payload per label map.  ValueError, before any device
     work, without an encoder or a binarizer, for a label map that is no multiple of the encoder's down-sampling factor, a
@@ -206,6 +234,11 @@ class CodedCalls(object):
     (ctu.utils.bitstream: 20-byte header) of each image.  Sizes of real files, not estimates; get_eval_rate is the
     reference's Shannon figure.  With --encoder_quantizer s2hvq: the .jpdv blobs, and the packed-index file of the same code."""
     payloads = self.get_coded(x_dict)
+    return self.codec.file_rates(payloads, int(x_dict['image'].shape[-2]), int(x_dict['image'].shape[-1]))
+
+  def get_coded_rate_ec(self, x_dict, rate_lambda=0.0, n_iter=2):
+    """get_coded_rate of the files get_coded_ec(x_dict, rate_lambda, n_iter) writes."""
+    payloads = self.get_coded_ec(x_dict, rate_lambda, n_iter)
     return self.codec.file_rates(payloads, int(x_dict['image'].shape[-2]), int(x_dict['image'].shape[-1]))
 
   # ---- where the bits go (extension; DESIGN.md 4.12) ------------------------------------------------------------------------

@@ -331,6 +331,13 @@ class Encoder(nn.Module):
     h, _ = run_chain_fwd(self._pre, x)
     return vq.code(h)
 
+  def vq_code_ec(self, x, lam, n_iter=2):
+    """(index, reports): vq_code under the entropy constraint: the first half runs once, then the bottleneck's
+    code_ec assigns image by image with the rate multiplier lam."""
+    vq = self._require_vq()
+    h, _ = run_chain_fwd(self._pre, x)
+    return vq.code_ec(h, lam, n_iter)
+
   def vq_features(self, x):
     """The [M, D] matrix the bottleneck's quantizer sees for x (M = N h w cout / D, vector m = pixel * (cout / D) + group): what
     vq_code assigns and what the code-book fit of DESIGN.md 4.21 runs on."""

@@ -34,6 +34,23 @@ def _rows_limit(rows, n_center):
     raise NotImplementedError('S2HVQ: n * code_len * n_center = %d, the kernels index below 2^31' % (rows * n_center))
 
 
+def _ec_lambda(lam):
+  """The rate multiplier of the entropy-constrained calls as a float: ValueError unless it is a finite number >= 0."""
+  try:
+    value = float(lam)
+  except (TypeError, ValueError):
+    raise ValueError('lam must be a finite number >= 0, got {!r}'.format(lam))
+  if not (0.0 <= value < float('inf')):
+    raise ValueError('lam must be a finite number >= 0, got {!r}'.format(lam))
+  return value
+
+
+def _ec_iterations(n_iter):
+  if isinstance(n_iter, bool) or not isinstance(n_iter, int) or n_iter < 0:
+    raise ValueError('n_iter must be an int >= 0, got {!r}'.format(n_iter))
+  return n_iter
+
+
 class _SoftAssign(torch.autograd.Function):
   """p = softmax_k(-sigma |x_m - c_k|^2) (ops.vq_soft_fwd); backward from the stored p (ops.vq_soft_bwd)."""
 
@@ -245,6 +262,43 @@ class S2HVQ(nn.Module):
     value, _, _ = ops.vq_rate_fwd(xm.detach(), self.code_book.detach().contiguous(), float(self._sigma), groups, denom,
                                   hard=bool(hard), want_grad=False)
     return value.reshape(())
+
+  def encode_ec(self, x, code_len, lam, groups=1, n_iter=2):
+    """Entropy-constrained encoding (Chou, Lookabaugh, Gray): x [n, d] as in encode; vector m of the [n *
+    code_len, center_size] matrix belongs to group m % groups (groups must divide n * code_len).  Every vector takes the centre
+    that minimises |x - c_k|^2 + lam * len[g][k], len[g][k] = log2(n_g / hist[g][k]) the code length of centre k under the
+    histogram of group g's own code.  Iteration 0 assigns with no bias (the plain code, encode(train=False, raw=False));
+    iteration t = 1 .. n_iter takes the lengths from the histogram of iteration t - 1 (ops.vq_ec_lengths) and assigns again
+    (ops.vq_ec_assign).  The decoder is untouched: the result is an ordinary code.
+    Returns (code int64 [n, code_len], report): report['distortion'][t] the summed squared distance of iteration t,
+    report['bits'][t] the ideal length of its code under its own per-group histograms, report['cost'][t] = distortion[t] +
+    lam * bits[t]; n_iter + 1 Python floats each, read back once, at the end.  cost is non-increasing up to the fp32 rounding
+    of the scores.  lam == 0 or n_iter == 0: the plain code, index for index.
+    A centre that the plain code of a group never uses has length +inf there and stays unused in that group in every later
+    iteration, so the set of centres in use can only shrink.  Runs under no_grad: nothing is differentiable."""
+    lam = _ec_lambda(lam)
+    n_iter = _ec_iterations(n_iter)
+    self._vector_checks(x, code_len)
+    M, groups, L = x.size(0) * code_len, int(groups), self.code_book.size(0)
+    if groups < 1 or M % groups != 0:
+      raise ValueError('groups must divide n * code_len, got {} and {}'.format(groups, M))
+    if groups * L > 65536:
+      raise NotImplementedError('S2HVQ.encode_ec: groups * n_center = %d, the kernels take at most 65536' % (groups * L))
+    with torch.no_grad():
+      xm = self._vectors(x, code_len).detach()
+      book = self.code_book.detach().contiguous()
+      index, hist, sse = ops.vq_ec_assign(xm, book, None, groups)
+      dist, bits = [sse.sum()], []
+      for _ in range(n_iter):
+        bias, b = ops.vq_ec_lengths(hist, lam)
+        bits.append(b.sum())
+        index, hist, sse = ops.vq_ec_assign(xm, book, bias, groups)
+        dist.append(sse.sum())
+      bits.append(ops.vq_ec_lengths(hist, lam)[1].sum())
+      back = torch.stack(dist + bits).cpu().tolist()
+    dist, bits = [float(v) for v in back[:n_iter + 1]], [float(v) for v in back[n_iter + 1:]]
+    report = dict(distortion=dist, bits=bits, cost=[d + lam * b for d, b in zip(dist, bits)])
+    return index.to(torch.int64).view(x.size(0), code_len), report
 
   def fit(self, x, code_len, n_iter=10, init='sample', seed=0, reseed=True):
     """Fit the code book to data by Lloyd (k-means) iterations on the device.  x: a tensor [n, d] or a list of

@@ -133,12 +133,18 @@ class Pix2PixHDTrainer(BaseTrainer):
     with torch.no_grad():
       return torch.cat([c for c in self.model.get_code(x_dict, packed) if c is not None], dim=-1)
 
-  def get_vq_code(self, x_dict):
+  def get_vq_code(self, x_dict, rate_lambda=0.0, n_iter=2):
     """The code of the vector-quantizer bottleneck (--encoder_quantizer s2hvq): int64 [N, h * w * C / D] on the
     device.  decode(get_vq_code(x), x) equals get_img(x) bit for bit; get_coded / decode_coded / get_coded_rate store it as
-    .jpdv blobs."""
+    .jpdv blobs.  rate_lambda > 0: the entropy-constrained code (DESIGN.md 4.22), a lower rate from the same trained model;
+    the receiver is untouched."""
     self.eval()
-    return self.model.get_vq_code(x_dict)
+    return self.model.get_vq_code(x_dict, rate_lambda=rate_lambda, n_iter=n_iter)
+
+  def get_vq_ec_report(self, x_dict, rate_lambda, n_iter=2):
+    """The per-image reports (distortion, bits, cost per round) of the entropy-constrained code."""
+    self.eval()
+    return self.model.get_vq_ec_report(x_dict, rate_lambda, n_iter=n_iter)
 
   def get_vq_rate(self, x_dict):
     """The entropy estimate of the vector-quantised code in bits per pixel (extension), a Python float: the
@@ -203,6 +209,12 @@ class Pix2PixHDTrainer(BaseTrainer):
     self.eval()
     return self.model.get_coded(x_dict)
 
+  def get_coded_ec(self, x_dict, rate_lambda=0.0, n_iter=2):
+    """get_coded of the entropy-constrained code get_vq_code(x_dict, rate_lambda, n_iter); the defaults give
+    get_coded's bytes.  --encoder_quantizer s2hvq only for rate_lambda > 0."""
+    self.eval()
+    return self.model.get_coded_ec(x_dict, rate_lambda=rate_lambda, n_iter=n_iter)
+
   def decode_coded(self, payloads, x_dict):
     """decode() from the payloads get_coded returned: equal to decode(get_code(x_dict, packed=True), x_dict) bit for bit.
     A wrong payload count, an item that is not bytes or an inconsistent length table is a ValueError before device work."""
@@ -214,6 +226,11 @@ class Pix2PixHDTrainer(BaseTrainer):
     included, in bits per pixel.  What a coder produced -- next to get_eval_rate's Shannon estimate, which stays as it is."""
     self.eval()
     return self.model.get_coded_rate(x_dict)
+
+  def get_coded_rate_ec(self, x_dict, rate_lambda=0.0, n_iter=2):
+    """(coded bpp, raw bpp) of the files get_coded_ec(x_dict, rate_lambda, n_iter) writes."""
+    self.eval()
+    return self.model.get_coded_rate_ec(x_dict, rate_lambda=rate_lambda, n_iter=n_iter)
 
   def get_context_rate(self, x_dict):
     """The context-model estimate of the code's length in bits per pixel (extension), a Python float, batch

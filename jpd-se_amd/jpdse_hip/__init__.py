@@ -221,6 +221,18 @@ class VqLloydUpdateArgs(ctypes.Structure):
              [(n, ctypes.c_void_p) for n in ('code_book', 'counts', 'sums', 'sse', 'far_dist', 'far_vec', 'report', 'stream')]
 
 
+# the entropy-constrained assignment (vq_ec.hip)
+class VqEcAssignArgs(ctypes.Structure):
+  _fields_ = [(n, ctypes.c_int32) for n in ('dtype', 'M', 'D', 'L', 'G')] + \
+             [(n, ctypes.c_void_p) for n in ('x', 'code_book', 'bias', 'index', 'hist', 'sse', 'ws')] + \
+             [('ws_bytes', ctypes.c_size_t), ('stream', ctypes.c_void_p)]
+
+
+class VqEcLengthsArgs(ctypes.Structure):
+  _fields_ = [('G', ctypes.c_int32), ('L', ctypes.c_int32), ('lam', ctypes.c_double), ('hist', ctypes.c_void_p),
+              ('bias', ctypes.c_void_p), ('bits', ctypes.c_void_p), ('stream', ctypes.c_void_p)]
+
+
 _P, _I32, _I64, _F, _SZ = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float,
                            ctypes.c_size_t)
 _CD, _ND = ctypes.POINTER(ConvDesc), ctypes.POINTER(InormDesc)
@@ -356,6 +368,9 @@ SIGNATURES = {
     'jpdse_vq_quantize_bwd': (_I32, [ctypes.POINTER(VqQuantizeBwdArgs)]),
     'jpdse_vq_rate_workspace_size': (_SZ, [_I32, _I32, _I32, _I32]),
     'jpdse_vq_rate_fwd': (_I32, [ctypes.POINTER(VqRateFwdArgs)]),
+    'jpdse_vq_ec_workspace_size': (_SZ, [_I32, _I32, _I32, _I32]),
+    'jpdse_vq_ec_assign': (_I32, [ctypes.POINTER(VqEcAssignArgs)]),
+    'jpdse_vq_ec_lengths': (_I32, [ctypes.POINTER(VqEcLengthsArgs)]),
     'jpdse_vq_quantize_bwd_grouped': (_I32, [ctypes.POINTER(VqQuantizeBwdGroupedArgs)]),
 }
 

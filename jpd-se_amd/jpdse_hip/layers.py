@@ -397,6 +397,20 @@ class HipVQBottleneck(nn.Module):
     _, index = self._quantize(h, True)
     return index.view(h.N, -1)
 
+  def code_ec(self, x, lam, n_iter=2):
+    """(index, reports): code() under the entropy constraint -- S2HVQ.encode_ec PER IMAGE on that image's rows
+    of features(x), groups = the channel groups: the coders adapt per image, so the histograms are per image.  index int32
+    [N, h * w * cout / D]; reports: the N report dicts of encode_ec."""
+    f = self.features(x)
+    N = x.N
+    rows = f.shape[0] // N
+    codes, reports = [], []
+    for i in range(N):
+      code, report = self.vq.encode_ec(f[i * rows:(i + 1) * rows], 1, lam, groups=self.groups, n_iter=n_iter)
+      codes.append(code.view(1, rows))
+      reports.append(report)
+    return torch.cat(codes, dim=0).to(torch.int32), reports
+
   def decode(self, index, N, h, w, dtype_code):
     """The features Act [N, h, w, cout] of an index tensor as code() returns it (ops.vq_decode: bit for bit what the hard
     forward emitted) and the status word of ops.vq_decode."""

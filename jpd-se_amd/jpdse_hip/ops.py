@@ -11,7 +11,8 @@ import torch
 
 from . import (lib, check, JpdseError, F32, BF16, ConvDesc, PackEntry, InormDesc, EvalMetricsSemArgs, MsssimLossArgs, CodeRateArgs, SemLossArgs, CodeCostArgs, ACT_NONE, PAD_ZERO, PAD_REFLECT)
 from . import (VqSoftFwdArgs, VqHardFwdArgs, VqSoftBwdArgs, VqDecodeArgs, VqDecodeBwdArgs, VqArgmaxArgs, VqPmfArgs, VqPmfBwdArgs,
-               VqQuantizeFwdArgs, VqQuantizeBwdArgs, VqRateFwdArgs, VqQuantizeBwdGroupedArgs, VqLloydAccumArgs, VqLloydUpdateArgs)
+               VqQuantizeFwdArgs, VqQuantizeBwdArgs, VqRateFwdArgs, VqQuantizeBwdGroupedArgs, VqLloydAccumArgs, VqLloydUpdateArgs,
+               VqEcAssignArgs, VqEcLengthsArgs)
 
 
 def cpad(c):
@@ -1127,6 +1128,42 @@ def vq_rate_fwd(x, code_book, sigma, G, denom, scale=1.0, hard=False, want_hist=
                        dhist.data_ptr() if want_grad else None, ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
   check(lib().jpdse_vq_rate_fwd(ctypes.byref(args)), 'vq_rate_fwd')
   return rate, hist, dhist
+
+
+# ---- entropy-constrained assignment (vq_ec.hip) -----------------------------------------------------------------
+def vq_ec_assign(x, code_book, bias=None, groups=1, want_hist=True, want_sse=True):
+  """(index, hist, sse) of x [M, D] against code_book fp32 [L, D] (jpdse_vq_ec_assign): index int32 [M], the arg-min over k of
+  d[m][k] + bias[m % groups][k] (lowest index on equal cost; d as in vq_hard_fwd); bias fp32 [groups, L], already scaled, +inf
+  for "never", None for all zero: then index is vq_hard_fwd's.  hist int32 [groups, L] the exact counts per group, sse float64
+  [groups] the sum of the chosen d (without the bias) per group; either is None when not wanted."""
+  M, D, L = _vq_dims(x, code_book)
+  G = int(groups)
+  if bias is not None:
+    assert bias.dtype == torch.float32 and bias.is_contiguous() and tuple(bias.shape) == (G, L) and bias.device == x.device, \
+        (bias.dtype, tuple(bias.shape))
+  index = torch.empty(M, dtype=torch.int32, device=x.device)
+  hist = torch.empty((max(G, 0), L), dtype=torch.int32, device=x.device) if want_hist else None
+  sse = torch.empty(max(G, 0), dtype=torch.float64, device=x.device) if want_sse else None
+  stats = want_hist or want_sse
+  ws = workspace(max(lib().jpdse_vq_ec_workspace_size(M, D, L, G), 1), x.device) if stats else None
+  args = VqEcAssignArgs(code_of(x.dtype), M, D, L, G, x.data_ptr(), code_book.data_ptr(), bias.data_ptr() if bias is not None else None,
+                        index.data_ptr(), hist.data_ptr() if want_hist else None, sse.data_ptr() if want_sse else None,
+                        ws.data_ptr() if stats else None, ws.numel() if stats else 0, torch.cuda.current_stream().cuda_stream)
+  check(lib().jpdse_vq_ec_assign(ctypes.byref(args)), 'vq_ec_assign')
+  return index, hist, sse
+
+
+def vq_ec_lengths(hist, lam):
+  """(bias, bits) from the counts hist int32 [G, L] (jpdse_vq_ec_lengths): bias fp32 [G, L] = lam * (log2 n[g] - log2 hist[g][k]),
+  n[g] the row sum, +inf on an empty bin, exact zeros at lam == 0: what vq_ec_assign takes; bits float64 [G] = sum_k hist *
+  (log2 n - log2 hist), the ideal code length of every group under its own histogram."""
+  assert hist.dim() == 2 and hist.dtype == torch.int32 and hist.is_contiguous(), (hist.dtype, tuple(hist.shape))
+  G, L = int(hist.shape[0]), int(hist.shape[1])
+  bias = torch.empty((G, L), dtype=torch.float32, device=hist.device)
+  bits = torch.empty(G, dtype=torch.float64, device=hist.device)
+  args = VqEcLengthsArgs(G, L, float(lam), hist.data_ptr(), bias.data_ptr(), bits.data_ptr(), torch.cuda.current_stream().cuda_stream)
+  check(lib().jpdse_vq_ec_lengths(ctypes.byref(args)), 'vq_ec_lengths')
+  return bias, bits
 
 
 # ---- the host half of the three device coders (streams.py; DESIGN.md 4.18) -----------------------------------------------------

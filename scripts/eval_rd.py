@@ -111,6 +111,20 @@ def semantics_roundtrip(trainer, x_dict, folder, batch_index):
   return trainer.decode_semantics(back), bpp
 
 
+def rate_lambda_rows(trainer, args, lambdas):
+  """One row per multiplier: the files of the entropy-constrained code and the distortion of the images decoded from it."""
+  data = list(batches(args))
+  print('%10s %10s %10s %10s %10s' % ('lambda', 'coded bpp', 'L1', 'PSNR', 'MS-SSIM'))
+  for lam in lambdas:
+    bpp, l1, psnr, ms, n = 0.0, 0.0, 0.0, 0.0, 0
+    for x_dict in data:
+      code = trainer.get_vq_code(x_dict, rate_lambda=lam, n_iter=args.vq_rate_iters)
+      m = trainer.get_eval_metrics_decoded(code, x_dict)
+      bpp += trainer.get_coded_rate_ec(x_dict, rate_lambda=lam, n_iter=args.vq_rate_iters)[0]
+      l1, psnr, ms, n = l1 + m['l1'], psnr + m['psnr'], ms + m['ms_ssim'], n + 1
+    print('%10g %10.5f %10.4f %10.3f %10.5f' % (lam, bpp / n, l1 / n, psnr / n, ms / n))
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--batches', type=int, default=4)
@@ -129,6 +143,11 @@ def main():
   ap.add_argument('--vq_context_coder', action='store_true',
                   help='with --codec --encoder_quantizer s2hvq: the training flag of the same name (DESIGN.md 4.19).  Also prints '
                        'the bpp of both forms of every code, .jpdv and .jpdw, and how many images took which container')
+  ap.add_argument('--vq-rate-lambda', default=None, metavar='L0,L1,..',
+                  help='with --codec --encoder_quantizer s2hvq: the rate-distortion curve of ONE model (DESIGN.md 4.22).  Prints one '
+                       'row per multiplier -- the coded bpp of the files trainer.get_coded_ec writes and L1 / PSNR / MS-SSIM of '
+                       'what a receiver decodes from that code -- and nothing else')
+  ap.add_argument('--vq-rate-iters', type=int, default=2, help='rounds of the entropy-constrained assignment per image')
   ap.add_argument('--checkpoints_dir', default=None, help='load net_G.pth (and net_E.pth) from here')
   ap.add_argument('--data', default=None, help='directory of pre-decoded *.pt batches instead of synthetic ones')
   ap.add_argument('--per-class', action='store_true', help='also print L1 / MSE / PSNR per semantic class')
@@ -157,6 +176,14 @@ def main():
   vq = args.codec and args.encoder_quantizer == 's2hvq'
   if args.vq_context_coder and not vq:
     ap.error('--vq_context_coder needs --codec --encoder_quantizer s2hvq')
+  lambdas = None
+  if args.vq_rate_lambda is not None:
+    if not vq:
+      ap.error('--vq-rate-lambda needs --codec --encoder_quantizer s2hvq')
+    try:
+      lambdas = [float(v) for v in args.vq_rate_lambda.split(',')]
+    except ValueError:
+      ap.error('--vq-rate-lambda takes numbers separated by commas, e.g. 0,0.5,2,8')
   if vq and args.roundtrip:
     ap.error('--roundtrip stores the binarizer\'s code: not available with --encoder_quantizer s2hvq '
              '(trainer.get_coded / decode_coded are its files)')
@@ -182,6 +209,8 @@ def main():
   torch.manual_seed(1234)
   with contextlib.redirect_stdout(sys.stderr):
     trainer = get_trainer(opt)(opt, 'test' if args.checkpoints_dir else 'train')
+  if lambdas is not None:
+    return rate_lambda_rows(trainer, args, lambdas)
   keys = ('l1', 'mse', 'ms_ssim', 'psnr')
   by_batch = dict.fromkeys(keys + ('shannon', 'actual', 'context', 'file', 'coded', 'semantics', 'total', 'weighted', 'model'), 0.0)
   by_image = dict.fromkeys(keys + ('shannon', 'actual', 'context', 'file', 'coded', 'semantics', 'total', 'weighted', 'model'), 0.0)
