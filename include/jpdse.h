@@ -1156,6 +1156,63 @@ typedef struct jpdse_vq_ec_lengths_args {
 } jpdse_vq_ec_lengths_args;
 int jpdse_vq_ec_lengths(const jpdse_vq_ec_lengths_args* args);
 
+/* ---- residual vector quantizer: S stages in one call (vq_residual.hip) ------------------------------------------
+ * x, y, dy, dx: row-major [M][D] in `dtype`; books: fp32 [S][L][D], S <= JPDSE_VQ_RES_MAX_STAGES; n_stages <= S of them in use;
+ * index: int32 [n_stages][M], stage-major.  With r_1 = x widened to fp32:
+ *   index[s][m] = arg-min_k |r_s - C_s[k]|^2, the direct score of jpdse_vq_hard_fwd, the LOWEST k on a tie
+ *   r_{s+1}     = r_s - C_s[index[s][m]]: one fp32 subtraction per component, never rounded between the stages
+ *   y[m]        = C_1[index[0][m]] + .. + C_n[index[n-1][m]]: fp32, stage order, starting from the first centre, rounded once
+ *   res_fwd     one launch; sse fp64 [n_stages] or NULL: sse[s] = sum_m |r_{s+2}|^2 (the error after stage s), every square formed
+ *               and added in fp64, per block, the blocks merged in order; residual fp32 [M][D] or NULL: r_{n_stages+1}.
+ *               n_stages == 0 is legal: y = 0 and residual = x widened.
+ *   res_decode  y from the indices, bit for bit res_fwd's; an index outside [0, L) reads as centre 0 and sets *status to 1.
+ *   res_bwd     the gradient of the SOFT form of every stage (straight-through, as quantize_bwd), stages descending, h_{n+1} = 0:
+ *               a_s = dy - h_{s+1}; (u_s, dbooks[s]) = quantize_bwd at the input r_s (recomputed from x and index by the
+ *               subtractions above) with the upstream gradient a_s and no dpmf; h_s = h_{s+1} + u_s; dx = h_1.  dbooks fp32
+ *               [n_stages][L][D]: fp32 partials per block, merged in block order.  dx or dbooks may be NULL.
+ * No atomics; grids and orders of summation depend on (M, D, L, n_stages) alone: two calls give identical bits.  ws:
+ * jpdse_vq_res_workspace_size(M, D, L, n_stages) bytes, 8-byte aligned (host only; 0 outside the limits), read only with an sse
+ * or a dbooks.  JPDSE_EINVAL before any launch: D 1 .. 32, L 2 .. 512, M >= 1, M * L < 2^31, S 1 .. 8, n_stages 0 .. S (decode,
+ * bwd: 1 .. S), sigma finite and positive, NULL args or required pointer, bad dtype, workspace missing or too small. */
+#define JPDSE_VQ_RES_MAX_STAGES 8
+size_t jpdse_vq_res_workspace_size(int32_t M, int32_t D, int32_t L, int32_t S);
+typedef struct jpdse_vq_res_fwd_args {
+  int32_t dtype, M, D, L, S, n_stages;
+  const void* x;
+  const float* books;
+  void* y;
+  int32_t* index;
+  double* sse;             /* [n_stages], or NULL */
+  float* residual;         /* [M][D], or NULL */
+  void* ws;
+  size_t ws_bytes;
+  void* stream;
+} jpdse_vq_res_fwd_args;
+int jpdse_vq_res_fwd(const jpdse_vq_res_fwd_args* args);
+typedef struct jpdse_vq_res_decode_args {
+  int32_t dtype, M, D, L, S, n_stages;
+  const int32_t* index;
+  const float* books;
+  void* y;
+  int32_t* status;         /* [1] */
+  void* stream;
+} jpdse_vq_res_decode_args;
+int jpdse_vq_res_decode(const jpdse_vq_res_decode_args* args);
+typedef struct jpdse_vq_res_bwd_args {
+  int32_t dtype, M, D, L, S, n_stages;
+  float sigma;
+  const void* dy;
+  const void* x;
+  const float* books;
+  const int32_t* index;
+  void* dx;                /* [M][D] in `dtype`, or NULL */
+  float* dbooks;           /* [n_stages][L][D], or NULL */
+  void* ws;
+  size_t ws_bytes;
+  void* stream;
+} jpdse_vq_res_bwd_args;
+int jpdse_vq_res_bwd(const jpdse_vq_res_bwd_args* args);
+
 /* ---- optimizer ---------------------------------------------------------------------- */
 /* torch.optim.Adam (model.py:275,279) over a table of tensors, one launch.  `table` is a
  * device array of jpdse_adam_entry; bias corrections are computed from `step` (1-based). */

@@ -58,6 +58,15 @@ int vqb_common_check(const char* who, int dtype, int M, int D, int L, float sigm
   return vq_sigma_check(who, sigma);
 }
 
+// jpdse_vq_res_* (vq_residual.hip): S books, of which the first n are in use
+int vq_res_check(const char* who, int dtype, int M, int D, int L, int S, int n) {
+  JPDSE_REQUIRE(!bad_dtype(dtype), "%s: bad dtype %d", who, dtype);
+  if (int rc = vq_shape_check(who, M, D, L)) return rc;
+  JPDSE_REQUIRE(S >= 1 && S <= JPDSE_VQ_RES_MAX_STAGES, "%s: S = %d stages (1 .. %d)", who, S, JPDSE_VQ_RES_MAX_STAGES);
+  JPDSE_REQUIRE(n >= 0 && n <= S, "%s: n_stages = %d (0 .. S = %d)", who, n, S);
+  return JPDSE_OK;
+}
+
 int vqr_group_check(const char* who, int M, int L, int G) {
   JPDSE_REQUIRE(G >= 1, "%s: G = %d groups (at least 1)", who, G);
   JPDSE_REQUIRE(M % G == 0, "%s: G = %d does not divide M = %d", who, G, M);

@@ -44,6 +44,10 @@ int vq_lloyd_update_check(const jpdse_vq_lloyd_update_args* a);
 int vq_ws_check(const char* who, const void* ws, size_t ws_bytes, size_t need);
 int vqb_common_check(const char* who, int dtype, int M, int D, int L, float sigma);
 int vqr_group_check(const char* who, int M, int L, int G);
+// the residual quantizer (kernels: vq_residual.hip): dtype, the shape limits above, 1 <= S <= 8 books and
+// 0 <= n <= S stages in use; vq_res_workspace_bytes (vq_residual.hip) is what jpdse_vq_res_workspace_size returns inside them
+int vq_res_check(const char* who, int dtype, int M, int D, int L, int S, int n);
+size_t vq_res_workspace_bytes(int M, int D, int L, int n);
 
 // the same for the jpdse_vq_index_* calls (api.cpp; kernels: vq_coder.hip).  vq_index_bits: the decisions per
 // symbol; the two sizes are 0 outside the limits 2 <= L <= 512, 1 <= S <= min(M, 65535), M * nb and the capacity below 2^31.

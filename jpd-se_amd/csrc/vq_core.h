@@ -16,6 +16,15 @@ static inline int vq_launch(const char* what, void (*kernel)(P...), int grid, in
   return check_launch(what);
 }
 
+// more than 64 KiB of dynamic LDS needs the kernel's opt-in (host only, idempotent): vq_ec.hip, vq_residual.hip (4.23)
+template <typename K>
+static int vq_lds_optin(const char* who, K kernel, size_t lds) {
+  if (lds <= 65536) return JPDSE_OK;
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return set_error(JPDSE_ELAUNCH, "%s: %zu bytes of LDS: %s", who, lds, hipGetErrorString(e));
+  return JPDSE_OK;
+}
+
 // e = exp(-sigma (d - dmin)).  d == dmin: exp(0) = 1 without forming inf - inf when every score overflowed
 __device__ __forceinline__ float vq_weight(float d, float dmin, float sigma) {
   return d == dmin ? 1.f : expf(-sigma * (d - dmin));

@@ -211,15 +211,6 @@ __global__ __launch_bounds__(256) void vqe_lengths_kernel(const int* __restrict_
   }
 }
 
-// more than 64 KiB of dynamic LDS needs the kernel's opt-in (host only, idempotent)
-template <typename K>
-static int vqe_lds_optin(K kernel, size_t lds) {
-  if (lds <= 65536) return JPDSE_OK;
-  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return set_error(JPDSE_ELAUNCH, "vq_ec_assign: %zu bytes of LDS: %s", lds, hipGetErrorString(e));
-  return JPDSE_OK;
-}
-
 }  // namespace jpdse
 
 using namespace jpdse;
@@ -252,7 +243,7 @@ int jpdse_vq_ec_assign(const jpdse_vq_ec_assign_args* a) {
   if (int rc = by_dtype(a->dtype, [&](auto tag) {
         using T = decltype(tag);
         auto go = [&](auto kernel) {
-          if (int rc = vqe_lds_optin(kernel, lds)) return rc;
+          if (int rc = vq_lds_optin("vq_ec_assign", kernel, lds)) return rc;
           return vq_launch("vq_ec_assign", kernel, nb, 256, lds, a->stream, cptr<T>(a->x), a->code_book, a->bias, M, D, L, G,
                            vq_group(L), vqe_sse_shuffle(G) ? 1 : 0, a->index, phist, psse);
         };

@@ -1,0 +1,367 @@
+// Residual (multi-stage) soft-to-hard vector quantizer (ctu.quantizers.ResidualS2HVQ).
+// Entry points: include/jpdse.h, "residual vector quantizer"; definition, surrogate gradient and measurements: DESIGN.md 4.23.
+//   x [M][D] (fp32 or bf16), S code books fp32 [S][L][D], n <= S stages in use.  r_1 = x widened to fp32 once;
+//   k_s = arg-min_k |r_s - C_s[k]|^2 (the direct score of vq.hip: vq_scores, lowest index on a tie); r_{s+1} = r_s - C_s[k_s], one
+//   fp32 subtraction per component, never rounded in between; y = C_1[k_1] + .. + C_n[k_n], fp32, stage order, rounded once.
+// Kernels:
+//   vqres_fwd_kernel     a block walks tiles of 256 vectors whose residual sits in LDS as fp32 [256][D].  The S books do not fit
+//       in LDS together (4 x 512 x 32 fp32 = 256 KiB), so the STAGE loop is the outer loop of a tile: stage book s transposed
+//       (vq_stage_transposed), assign the tile's vectors in the group layout of vq_hard_fwd_kernel (the residual row takes the place
+//       of x), synchronise, subtract the chosen centres (one thread per (vector, component), the book still in LDS) and sum the
+//       squares of the new residual in fp64, synchronise, next book.  x is read once; y is summed at the end from the tile's
+//       indices (LDS) and the books (L2) by the function the decoder uses; a residual is written only when asked for.
+//   vqres_decode_kernel  one thread per (vector, component): the same sum from the index planes.
+//   vqres_bwd_kernel     one THREAD per vector (vq_rows.h), stages descending.  r_s is recomputed from x and the indices by the
+//       forward's subtractions, a_s = dy - h_{s+1}, then the three sweeps and the code-book-gradient reduction of vqb_bwd_kernel
+//       (vq_bottleneck.hip) at (r_s, a_s): u_s into registers, the stage's [L][D] share into the block's partial [n][L][D];
+//       h_s = h_{s+1} + u_s; dx = h_1.  vq_merge_kernel (vq_core.h) adds the partials in block order.
+//   vqres_sse_kernel     sse[s] = the blocks' fp64 partials in block order.
+// No atomics; grids, tiles and chunks are functions of (M, D, L, n) alone: two calls give identical bits.
+#include <math.h>
+
+#include "common.h"
+#include "vq_core.h"
+#include "vq_rows.h"
+
+namespace jpdse {
+
+constexpr int kVqResMaxStages = JPDSE_VQ_RES_MAX_STAGES;
+constexpr int kVqResTile = 256;              // vectors per tile of the forward
+constexpr int kVqResFwdBlocks = 2048;        // cap of the blocks (= fp64 partials [n]) of the forward
+constexpr int kVqResPartialWords = 1 << 26;  // cap of blocks * n * L * D of the backward: partials of at most 256 MiB
+
+// ---- launch geometry: functions of (M, D, L, n) alone ---------------------------------------------------------------------------
+static inline int vqres_fwd_blocks(int M) {
+  const int tiles = (M + kVqResTile - 1) / kVqResTile;
+  return tiles < kVqResFwdBlocks ? tiles : kVqResFwdBlocks;
+}
+// LDS of the forward: red fp64 [4] | bsse fp64 [8] | ct [D][L] | r [256][D] | it int32 [8][256]: at most 106592 bytes
+static inline size_t vqres_fwd_lds(int D, int L) {
+  return (4 + kVqResMaxStages) * sizeof(double) + ((size_t)D * L + (size_t)kVqResTile * D + (size_t)kVqResMaxStages * kVqResTile) * sizeof(float);
+}
+static inline int vqres_bwd_blocks(int M, int D, int L, int n) {
+  const int nb = vqb_blocks(M, vqb_bwd_threads(D));
+  int cap = kVqResPartialWords / (n * L * D);
+  cap = cap < 1 ? 1 : cap;
+  return nb < cap ? nb : cap;
+}
+// LDS of the backward: cb [L][DP] when staged | with a partial: pt, ddt [KC][V + 1] | xt, dyt [V][D] | red [max(V, KC D)]
+static inline size_t vqres_bwd_lds(int D, int L, bool dc) {
+  const int V = vqb_bwd_threads(D), KC = vqb_chunk(L);
+  size_t w = vqb_cb_lds(D, L) ? (size_t)L * vqb_dp(D) : 0;
+  if (dc) w += 2 * (size_t)KC * (V + 1) + 2 * (size_t)V * D + (size_t)(KC * D > V ? KC * D : V);
+  return w * sizeof(float);
+}
+size_t vq_res_workspace_bytes(int M, int D, int L, int n) {
+  const size_t fwd = (size_t)vqres_fwd_blocks(M) * n * sizeof(double);
+  const size_t bwd = (size_t)vqres_bwd_blocks(M, D, L, n) * n * L * D * sizeof(float);
+  return fwd > bwd ? fwd : bwd;
+}
+
+// ---- device helpers ---------------------------------------------------------------------------------------------------------
+// component j of C_1[k(0)] + .. + C_n[k(n - 1)]: fp32, stage order, starting FROM the first centre (n == 1: a bit-exact gather)
+template <typename K>
+__device__ __forceinline__ float vqres_sum(const float* __restrict__ books, int LD, int D, int n, int j, K k) {
+  if (n == 0) return 0.f;
+  float acc = books[k(0) * D + j];
+  for (int s = 1; s < n; ++s) acc += books[(size_t)s * LD + k(s) * D + j];
+  return acc;
+}
+
+// ---- forward ----------------------------------------------------------------------------------------------------------------
+// psse: this block's fp64 [n] sums of |r_{s+1}|^2, or nullptr.  index: [n][M].  residual: fp32 [M][D] = r_{n+1}, or nullptr
+template <typename T>
+__global__ __launch_bounds__(256) void vqres_fwd_kernel(const T* __restrict__ x, const float* __restrict__ books, int M, int D, int L,
+                                                       int n, int GL, T* __restrict__ y, int* __restrict__ index,
+                                                       double* __restrict__ psse, float* __restrict__ residual) {
+  extern __shared__ double vqres_lds[];
+  constexpr int V = kVqResTile;
+  double* red = vqres_lds;
+  double* bsse = red + 4;
+  float* ct = reinterpret_cast<float*>(bsse + kVqResMaxStages);
+  float* r = ct + D * L;
+  int* it = reinterpret_cast<int*>(r + V * D);
+  const int t = threadIdx.x, LD = L * D;
+  const VqLanes ln(GL, L);
+  const int lane = ln.lane, wave = ln.wave, kk = ln.kk;
+  if (t < kVqResMaxStages) bsse[t] = 0.0;        // thread 0 adds to them after the barriers below
+  const int ntiles = (M + V - 1) / V;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int m0 = tile * V;
+    const int nv = M - m0 < V ? M - m0 : V;
+    const size_t e0 = (size_t)m0 * D;
+    for (int i = t; i < nv * D; i += 256) r[i] = ElemOps<T>::ld(x + e0 + i);
+    for (int s = 0; s < n; ++s) {
+      __syncthreads();                           // r is complete (the load, or the subtraction of stage s - 1); ct is free
+      vq_stage_transposed(books + (size_t)s * LD, ct, D, L);
+      __syncthreads();
+      for (int vb = wave * ln.vpw; vb < nv; vb += 4 * ln.vpw) {
+        const bool live = vb + ln.g < nv;
+        const int v = live ? vb + ln.g : nv - 1;
+        float d[kVqSlots];
+        vq_scores(r, ct, v, D, ln, d);
+        float best = INFINITY;
+        int bk = kk < L ? kk : 0x7fffffff;
+        if (kk < L) best = d[0];
+#pragma unroll
+        for (int i = 1; i < kVqSlots; ++i)
+          if (ln.slot_live(i) && d[i] < best) {  // strict: the lower index keeps a tie
+            best = d[i];
+            bk = ln.centre(i);
+          }
+        vq_group_arg<true>(best, bk, GL);
+        bk = __shfl(bk, lane & ~(GL - 1), 64);   // group lane 0 decides for the row
+        bk = bk < L ? bk : L - 1;
+        if (live && kk == 0) {
+          it[s * V + v] = bk;
+          index[(size_t)s * M + m0 + v] = bk;
+        }
+      }
+      __syncthreads();
+      double acc = 0.0;
+      for (int i = t; i < nv * D; i += 256) {
+        const int v = i / D, j = i - v * D;
+        const float rv = r[i] - ct[j * L + it[s * V + v]];
+        r[i] = rv;
+        acc += (double)rv * (double)rv;
+      }
+      if (psse != nullptr) {
+        for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+        if (lane == 0) red[wave] = acc;
+        __syncthreads();
+        if (t == 0) bsse[s] += ((red[0] + red[1]) + red[2]) + red[3];
+      }
+    }
+    __syncthreads();                             // r and it are final
+    for (int i = t; i < nv * D; i += 256) {
+      const int v = i / D, j = i - v * D;
+      ElemOps<T>::st(y + e0 + i, vqres_sum(books, LD, D, n, j, [&](int s) { return it[s * V + v]; }));
+      if (residual != nullptr) residual[e0 + i] = r[i];
+    }
+    __syncthreads();                             // r and it are free again
+  }
+  if (psse != nullptr && t == 0)
+    for (int s = 0; s < n; ++s) psse[(size_t)blockIdx.x * n + s] = bsse[s];
+}
+
+__global__ __launch_bounds__(64) void vqres_sse_kernel(const double* __restrict__ psse, int nb, int n, double* __restrict__ sse) {
+  const int s = threadIdx.x;
+  if (s >= n) return;
+  double acc = 0.0;
+  for (int b = 0; b < nb; ++b) acc += psse[(size_t)b * n + s];
+  sse[s] = acc;
+}
+
+// ---- decode -----------------------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void vqres_decode_kernel(const int* __restrict__ index, const float* __restrict__ books, int M, int D,
+                                                          int L, int n, T* __restrict__ y, int* __restrict__ status) {
+  const long long total = (long long)M * D;
+  const int LD = L * D;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int m = (int)(i / D), j = (int)(i - (long long)m * D);
+    bool bad = false;
+    const float v = vqres_sum(books, LD, D, n, j, [&](int s) {
+      int k = index[(size_t)s * M + m];
+      if ((unsigned)k >= (unsigned)L) {
+        k = 0;
+        bad = true;
+      }
+      return k;
+    });
+    if (bad && j == 0) *status = 1;              // every writer stores the same word
+    ElemOps<T>::st(y + i, v);
+  }
+}
+
+// ---- backward ---------------------------------------------------------------------------------------------------------------
+// blockDim.x = V vectors per tile.  partial: this block's [n][L][D] sums, or nullptr: no code-book gradient.
+template <typename T, int DP, bool CBL>
+__global__ __launch_bounds__(256) void vqres_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x, const float* __restrict__ books,
+                                                       const int* __restrict__ index, int M, int D, int L, int n, float sigma, int vec,
+                                                       T* __restrict__ dx, float* __restrict__ partial) {
+  extern __shared__ float vqresb_lds[];
+  const int V = blockDim.x;
+  const int KC = vqb_chunk(L);
+  float* pt = vqresb_lds + (CBL ? L * DP : 0);
+  float* ddt = pt + KC * (V + 1);
+  float* xt = ddt + KC * (V + 1);
+  float* dyt = xt + V * D;
+  float* red = dyt + V * D;
+  const int ld = CBL ? DP : D;
+  const int t = threadIdx.x, LD = L * D;
+  const int ntiles = (M + V - 1) / V;
+  float* mine = partial != nullptr ? partial + (size_t)blockIdx.x * n * LD : nullptr;
+  const int parts = V / (KC * D) > 1 ? V / (KC * D) : 1, span = (V + parts - 1) / parts;
+  bool first = true;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int m0 = tile * V;
+    const int nv = M - m0 < V ? M - m0 : V;
+    const bool live = t < nv;
+    const int m = live ? m0 + t : M - 1;
+    const size_t row = (size_t)m * D;
+    float h[DP];                                 // h_{s+1}: the gradient that the later stages sent back to r_{s+1}
+#pragma unroll
+    for (int j = 0; j < DP; ++j) h[j] = 0.f;
+    for (int s = n - 1; s >= 0; --s) {
+      const float* c = books + (size_t)s * LD;
+      __syncthreads();                           // the staged book, xt, dyt and red of the stage before are free
+      if (CBL) vqb_stage(c, vqresb_lds, D, L, DP);
+      float xr[DP], gr[DP], dxr[DP];
+#pragma unroll
+      for (int j = 0; j < DP; ++j) xr[j] = gr[j] = dxr[j] = 0.f;
+      if (live) {
+        vqb_load_row<T, DP>(x + row, D, vec != 0, xr);
+        for (int u = 0; u < s; ++u) {            // r_s by the forward's subtractions, in its order
+          const float* cu = books + (size_t)u * LD + index[(size_t)u * M + m] * D;
+#pragma unroll
+          for (int j = 0; j < DP; ++j)
+            if (j < D) xr[j] = xr[j] - cu[j];
+        }
+        vqb_load_row<T, DP>(dy + row, D, vec != 0, gr);
+#pragma unroll
+        for (int j = 0; j < DP; ++j) gr[j] = gr[j] - h[j];        // a_s
+        if (mine != nullptr) {
+#pragma unroll
+          for (int j = 0; j < DP; ++j)
+            if (j < D) {
+              xt[t * D + j] = xr[j];
+              dyt[t * D + j] = gr[j];
+            }
+        }
+      }
+      __syncthreads();
+      const float* cc = CBL ? vqresb_lds : c;
+      float dmin = INFINITY;
+      for (int k = 0; k < L; ++k) {
+        const float d = vqb_score<DP, CBL>(xr, cc + k * ld, D);
+        if (d < dmin) dmin = d;
+      }
+      float sum = 0.f, pd = 0.f;
+      for (int k = 0; k < L; ++k) {
+        const float* ck = cc + k * ld;
+        const float e = vq_weight(vqb_score<DP, CBL>(xr, ck, D), dmin, sigma);
+        const float q = vqb_dot<DP, CBL>(gr, ck, D);
+        sum += e;
+        pd = __fmaf_rn(e, q, pd);
+      }
+      pd = pd / sum;                             // <p, dp>
+      for (int k0 = 0; k0 < L; k0 += KC) {
+        const int kc = L - k0 < KC ? L - k0 : KC;
+        for (int kq = 0; kq < kc; ++kq) {
+          const float* ck = cc + (k0 + kq) * ld;
+          const float p = vq_weight(vqb_score<DP, CBL>(xr, ck, D), dmin, sigma) / sum;
+          const float q = vqb_dot<DP, CBL>(gr, ck, D);
+          const float dd = -sigma * (p * (q - pd));
+#pragma unroll
+          for (int j = 0; j < DP; ++j)
+            if (CBL || j < D) dxr[j] = __fmaf_rn(dd, xr[j] - ck[j], dxr[j]);
+          if (mine != nullptr && live) {
+            pt[kq * (V + 1) + t] = p;
+            ddt[kq * (V + 1) + t] = dd;
+          }
+        }
+        if (mine != nullptr) {
+          const int nown = kc * D;
+          __syncthreads();
+          for (int w = t; w < nown * parts; w += V) {
+            const int part = w / nown, q = w - part * nown;
+            const int kq = q / D, j = q - kq * D;
+            const float ck = cc[(k0 + kq) * ld + j];
+            const int v1 = (part + 1) * span < nv ? (part + 1) * span : nv;
+            const float* pr = pt + kq * (V + 1);
+            const float* dr = ddt + kq * (V + 1);
+            float acc = 0.f;
+            for (int v = part * span; v < v1; ++v) acc += pr[v] * dyt[v * D + j] - 2.f * (dr[v] * (xt[v * D + j] - ck));
+            red[w] = acc;
+          }
+          __syncthreads();
+          for (int q = t; q < nown; q += V) {
+            float acc = 0.f;
+            for (int part = 0; part < parts; ++part) acc += red[part * nown + q];
+            vq_partial_put(mine + (size_t)s * LD, k0 * D + q, first, acc);
+          }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < DP; ++j) h[j] = h[j] + 2.f * dxr[j];    // h_s = h_{s+1} + u_s
+    }
+    if (live && dx != nullptr) vqb_store_row<T, DP>(dx + row, D, vec != 0, h);
+    first = false;
+  }
+}
+
+}  // namespace jpdse
+
+using namespace jpdse;
+
+extern "C" {
+
+size_t jpdse_vq_res_workspace_size(int32_t M, int32_t D, int32_t L, int32_t S) {
+  if (vq_res_check("vq_res_workspace_size", JPDSE_F32, M, D, L, S, S) != JPDSE_OK || S < 1) return 0;
+  return vq_res_workspace_bytes(M, D, L, S);
+}
+
+int jpdse_vq_res_fwd(const jpdse_vq_res_fwd_args* a) {
+  JPDSE_REQUIRE(a != nullptr, "vq_res_fwd: null argument struct");
+  if (int rc = vq_res_check("vq_res_fwd", a->dtype, a->M, a->D, a->L, a->S, a->n_stages)) return rc;
+  JPDSE_REQUIRE(a->x && a->books && a->y && (a->index || a->n_stages == 0), "vq_res_fwd: null pointer");
+  const int M = a->M, D = a->D, L = a->L, n = a->n_stages;
+  const int nb = vqres_fwd_blocks(M);
+  double* psse = nullptr;
+  if (a->sse != nullptr && n > 0) {
+    if (int rc = vq_ws_check("vq_res_fwd", a->ws, a->ws_bytes, (size_t)nb * n * sizeof(double))) return rc;
+    JPDSE_REQUIRE(reinterpret_cast<uintptr_t>(a->ws) % 8 == 0, "vq_res_fwd: workspace not 8-byte aligned");
+    psse = mptr<double>(a->ws);
+  }
+  const size_t lds = vqres_fwd_lds(D, L);
+  if (int rc = by_dtype(a->dtype, [&](auto tag) {
+        using T = decltype(tag);
+        if (int rc = vq_lds_optin("vq_res_fwd", vqres_fwd_kernel<T>, lds)) return rc;
+        return vq_launch("vq_res_fwd", vqres_fwd_kernel<T>, nb, 256, lds, a->stream, cptr<T>(a->x), a->books, M, D, L, n, vq_group(L),
+                         mptr<T>(a->y), a->index, psse, a->residual);
+      }))
+    return rc;
+  if (psse == nullptr) return JPDSE_OK;
+  return vq_launch("vq_res_fwd(sse)", vqres_sse_kernel, 1, 64, 0, a->stream, psse, nb, n, a->sse);
+}
+
+int jpdse_vq_res_decode(const jpdse_vq_res_decode_args* a) {
+  JPDSE_REQUIRE(a != nullptr, "vq_res_decode: null argument struct");
+  if (int rc = vq_res_check("vq_res_decode", a->dtype, a->M, a->D, a->L, a->S, a->n_stages)) return rc;
+  JPDSE_REQUIRE(a->n_stages >= 1, "vq_res_decode: n_stages = %d (1 .. S = %d)", a->n_stages, a->S);
+  JPDSE_REQUIRE(a->index && a->books && a->y && a->status, "vq_res_decode: null pointer");
+  return by_dtype(a->dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return vq_launch("vq_res_decode", vqres_decode_kernel<T>, ew_blocks((long long)a->M * a->D), 256, 0, a->stream, a->index, a->books,
+                     a->M, a->D, a->L, a->n_stages, mptr<T>(a->y), a->status);
+  });
+}
+
+int jpdse_vq_res_bwd(const jpdse_vq_res_bwd_args* a) {
+  JPDSE_REQUIRE(a != nullptr, "vq_res_bwd: null argument struct");
+  if (int rc = vq_res_check("vq_res_bwd", a->dtype, a->M, a->D, a->L, a->S, a->n_stages)) return rc;
+  JPDSE_REQUIRE(a->n_stages >= 1, "vq_res_bwd: n_stages = %d (1 .. S = %d)", a->n_stages, a->S);
+  JPDSE_REQUIRE(isfinite(a->sigma) && a->sigma > 0.f, "vq_res_bwd: sigma is %g (a finite value > 0)", (double)a->sigma);
+  JPDSE_REQUIRE(a->dy && a->x && a->books && a->index, "vq_res_bwd: null pointer");
+  const int M = a->M, D = a->D, L = a->L, n = a->n_stages;
+  const int V = vqb_bwd_threads(D), nb = vqres_bwd_blocks(M, D, L, n);
+  float* partial = nullptr;
+  if (a->dbooks != nullptr) {
+    if (int rc = vq_ws_check("vq_res_bwd", a->ws, a->ws_bytes, (size_t)nb * n * L * D * sizeof(float))) return rc;
+    partial = mptr<float>(a->ws);
+  }
+  if (a->dx == nullptr && partial == nullptr) return JPDSE_OK;
+  const int vec = vqb_vec(a->dtype, D, {a->x, a->dy, a->dx});
+  const size_t lds = vqres_bwd_lds(D, L, partial != nullptr);
+  if (int rc = vqb_dispatch(a->dtype, D, L, [&](auto tag, auto dp, auto cbl) {
+        using T = decltype(tag);
+        return vq_launch("vq_res_bwd", vqres_bwd_kernel<T, decltype(dp)::value, decltype(cbl)::value>, nb, V, lds, a->stream,
+                         cptr<T>(a->dy), cptr<T>(a->x), a->books, a->index, M, D, L, n, a->sigma, vec, mptr<T>(a->dx), partial);
+      }))
+    return rc;
+  if (partial == nullptr) return JPDSE_OK;
+  return vq_launch("vq_res_bwd(merge)", vq_merge_kernel, ew_blocks(n * L * D), 256, 0, a->stream, partial, nb, n * L * D, 1.f, a->dbooks);
+}
+
+}  // extern "C"

@@ -1,0 +1,206 @@
+"""Residual (multi-stage) soft-to-hard vector quantizer on the jpdse_vq_res_* kernels (an extension: the
+reference has one stage).
+
+S code books C_1 .. C_S of L centres each.  Stage s quantizes what the stages before left over:
+
+    r_1 = x;  k_s = argmin_k |r_s - C_s[k]|^2;  r_{s+1} = r_s - C_s[k_s];  y^(n) = C_1[k_1] + .. + C_n[k_n]
+
+so S stages of L centres address L^S reproduction points for S times the score loop of one, and a stored code (k_1 .. k_S) can be
+cut after any stage: the first n stages reproduce y^(n) (ctu.utils.vqstages).  The gradient is the soft form's at every stage (the
+straight-through rule of S2HVQ.quantize), whatever the forward was.  There is no CPU path.  Limits: 1 <= S <= 8, and S2HVQ's for
+center_size, n_center and n * code_len * n_center.
+"""
+import torch
+import torch.nn as nn
+
+from jpdse_hip import ops
+from .s2h_vq import S2HVQ, MAX_CENTER_SIZE, MAX_N_CENTER, _on_gpu, _rows_limit
+
+__all__ = ['ResidualS2HVQ']
+
+MAX_STAGES = ops.VQ_RES_MAX_STAGES
+
+
+class _ResidualQuantize(torch.autograd.Function):
+  """(y, index) of ops.vq_res_fwd over the first `stages` books; backward: ops.vq_res_bwd from the saved x, books and indices.
+  The books beyond `stages` get a zero gradient."""
+
+  @staticmethod
+  def forward(ctx, x, books, sigma, stages):
+    x, books = x.contiguous(), books.contiguous()
+    y, index, _, _ = ops.vq_res_fwd(x, books, stages)
+    ctx.save_for_backward(x, books, index)
+    ctx.sigma = sigma
+    ctx.mark_non_differentiable(index)
+    return y, index
+
+  @staticmethod
+  def backward(ctx, dy, _dindex):
+    x, books, index = ctx.saved_tensors
+    dx, dc = ops.vq_res_bwd(dy.contiguous(), x, books, index, ctx.sigma, want_dx=ctx.needs_input_grad[0],
+                            want_dc=ctx.needs_input_grad[1])
+    return dx, dc, None, None
+
+
+class ResidualS2HVQ(nn.Module):
+  """code_books: float32 tensor [S, n_center, center_size], learnable (parameter `_code_books`); sigma > 0: the hardness of the
+  soft assignment whose gradient training uses."""
+
+  def __init__(self, code_books, sigma=10., **kwargs):
+    super(ResidualS2HVQ, self).__init__()
+    assert sigma > 0, "sigma must be greater than 0, got {}".format(sigma)
+    if code_books.dim() != 3:
+      raise ValueError('code_books must have shape (stages, n_center, center_size), got {}'.format(tuple(code_books.shape)))
+    stages, n_center, center_size = (int(v) for v in code_books.shape)
+    if not 1 <= stages <= MAX_STAGES:
+      raise NotImplementedError('ResidualS2HVQ: %d stages, the kernels take 1 .. %d' % (stages, MAX_STAGES))
+    if not 1 <= center_size <= MAX_CENTER_SIZE:
+      raise NotImplementedError('ResidualS2HVQ: center_size %d, the kernels take 1 .. %d' % (center_size, MAX_CENTER_SIZE))
+    if not 2 <= n_center <= MAX_N_CENTER:
+      raise NotImplementedError('ResidualS2HVQ: n_center %d, the kernels take 2 .. %d' % (n_center, MAX_N_CENTER))
+    if code_books.dtype != torch.float32:
+      raise NotImplementedError('ResidualS2HVQ: %s code books, the kernels keep them in float32' % (code_books.dtype,))
+    self._center_size = center_size
+    self._code_books = nn.Parameter(code_books)
+    self._sigma = sigma
+
+  @property
+  def center_size(self):
+    return self._center_size
+
+  @property
+  def code_books(self):
+    return self._code_books
+
+  @property
+  def n_stages(self):
+    return int(self._code_books.size(0))
+
+  @property
+  def sigma(self):
+    return self._sigma
+
+  @sigma.setter
+  def sigma(self, new_sigma):
+    assert new_sigma > 0, "sigma must be greater than 0, got {}".format(new_sigma)
+    self._sigma = new_sigma
+
+  @property
+  def code_book(self):
+    """The first stage's book: what S2HVQ's argument checks measure x against (every stage has its shape)."""
+    return self._code_books[0]
+
+  _vector_checks = S2HVQ._vector_checks        # the code_len checks are S2HVQ's, word for word
+
+  def _stages(self, stages):
+    n = self.n_stages if stages is None else stages
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= self.n_stages:
+      raise ValueError('stages must be an int in 1 .. {}, got {!r}'.format(self.n_stages, stages))
+    return n
+
+  def _vectors(self, x, code_len):
+    self._vector_checks(x, code_len)
+    _on_gpu(x, 'x')
+    _on_gpu(self._code_books, 'the code books')
+    return x.contiguous().view(x.size(0) * code_len, self._center_size)
+
+  def quantize(self, x, code_len, stages=None, hard_forward=True):
+    """x [n, d], code_len dividing d with d // code_len == center_size -> (y [n, d] in x's dtype, code int64 [S', n, code_len]) of
+    the first `stages` (default: all) stages, in one kernel.  Training mode: differentiable in x and the books, the gradient
+    the soft form's at every stage; books beyond `stages` get a zero gradient.  Eval mode: nothing saved.  The soft forward
+    exists for one stage only (there it is S2HVQ.quantize's): with more it raises NotImplementedError before any device work."""
+    n_st = self._stages(stages)
+    if not hard_forward and self.n_stages > 1:
+      raise NotImplementedError('ResidualS2HVQ.quantize: the soft forward is built for one stage, this module has %d' % self.n_stages)
+    xm = self._vectors(x, code_len)
+    n = x.size(0)
+    if not hard_forward:
+      y, code, _ = S2HVQ.quantize(self, x, code_len, hard_forward=False)
+      return y, code.unsqueeze(0)
+    if self.training and torch.is_grad_enabled():
+      y, index = _ResidualQuantize.apply(xm, self._code_books, float(self._sigma), n_st)
+    else:
+      y, index, _, _ = ops.vq_res_fwd(xm.detach(), self._code_books.detach().contiguous(), n_st)
+    return y.view(n, code_len * self._center_size), index.to(torch.int64).view(n_st, n, code_len)
+
+  def encode(self, x, code_len, stages=None):
+    """The int64 code [S', n, code_len] of x [n, d].  Nothing is differentiable."""
+    n_st = self._stages(stages)
+    with torch.no_grad():
+      xm = self._vectors(x, code_len).detach()
+      _, index, _, _ = ops.vq_res_fwd(xm, self._code_books.detach().contiguous(), n_st)
+    return index.to(torch.int64).view(n_st, x.size(0), code_len)
+
+  def decode(self, code, stages=None):
+    """code int64 [S', n, code_len] -> float32 [n, code_len * center_size]: the sum of the centres of the first `stages` (default:
+    all S') stages, bit for bit quantize's y.  ValueError for an index outside [0, n_center) (this synchronises)."""
+    if not torch.is_tensor(code) or code.dim() != 3 or code.dtype != torch.int64 or not 1 <= code.size(0) <= self.n_stages:
+      raise ValueError('code must be an int64 tensor (stages <= {}, n, code_len), got {}'.format(
+          self.n_stages, (code.dtype, tuple(code.shape)) if torch.is_tensor(code) else type(code).__name__))
+    n_st = code.size(0) if stages is None else stages
+    if isinstance(n_st, bool) or not isinstance(n_st, int) or not 1 <= n_st <= code.size(0):
+      raise ValueError('stages must be an int in 1 .. {}, got {!r}'.format(code.size(0), stages))
+    L = self._code_books.size(1)
+    _rows_limit(code.size(1) * code.size(2), L)
+    _on_gpu(code, 'code')
+    _on_gpu(self._code_books, 'the code books')
+    if bool(((code[:n_st] < 0) | (code[:n_st] >= L)).any()):     # before the cast to int32 could fold a far value into range
+      raise ValueError('ResidualS2HVQ.decode: an index outside [0, {})'.format(L))
+    index = code[:n_st].reshape(n_st, -1).to(torch.int32).contiguous()
+    y, _ = ops.vq_res_decode(index, self._code_books.detach().contiguous(), n_st)
+    return y.view(code.size(1), code.size(2) * self._center_size)
+
+  def distortion(self, x, code_len):
+    """float64 [S] on the device: the mean squared error per vector, sum |x - y^(s)|^2 / (n * code_len), after every stage s --
+    the measure S2HVQ.fit reports for one."""
+    with torch.no_grad():
+      xm = self._vectors(x, code_len).detach()
+      _, _, sse, _ = ops.vq_res_fwd(xm, self._code_books.detach().contiguous(), want_sse=True)
+    return sse / float(xm.size(0))
+
+  def fit(self, x, code_len, n_iter=10, init='sample', seed=0, reseed=True):
+    """Fit the books stage by stage: stage s is S2HVQ.fit's Lloyd loop (ops.vq_lloyd_accum / vq_lloyd_update, the
+    same sampling rule for init='sample') on the residual r_s that the fitted stages before it leave, taken from ops.vq_res_fwd(...,
+    n_stages=s - 1, want_residual=True).  x: one tensor [n, d].  Runs under no_grad and writes `_code_books` IN PLACE: same
+    storage, requires_grad and .grad untouched.  Deterministic.  Returns a list of S dicts, S2HVQ.fit's report of every stage
+    (its `distortion` measured on r_s), and in each `final`: the mean squared distance after that stage under the fitted books
+    (what distortion(x, code_len) returns); statistics are read back once per stage."""
+    if isinstance(n_iter, bool) or not isinstance(n_iter, int) or n_iter < 0:
+      raise ValueError('n_iter must be an int >= 0, got {!r}'.format(n_iter))
+    if init not in ('sample', 'current'):
+      raise ValueError("init must be 'sample' or 'current', got {!r}".format(init))
+    if not torch.is_tensor(x) or x.dim() != 2 or x.size(0) < 1:
+      raise ValueError('x must be a tensor [n, d] with n >= 1, got {}'.format(tuple(x.shape) if torch.is_tensor(x) else type(x).__name__))
+    self._vector_checks(x, code_len)
+    S, L, D = self.n_stages, int(self._code_books.size(1)), self._center_size
+    if init == 'sample' and x.size(0) * code_len < L:
+      raise ValueError("init='sample' draws n_center = {} distinct vectors from x, which has {}".format(L, x.size(0) * code_len))
+    reports = []
+    with torch.no_grad():
+      xm = self._vectors(x, code_len).detach()
+      books = self._code_books.data
+      if not books.is_contiguous() or xm.device != books.device:
+        raise ValueError('ResidualS2HVQ.fit: the code books must be contiguous and on the device of x')
+      M = xm.size(0)
+      state = ops.vq_lloyd_state(L, D, books.device)
+      for s in range(S):
+        res = ops.vq_res_fwd(xm, books, n_stages=s, want_residual=True)[3]
+        book = books[s]                                        # a view: the updates land in the parameter's storage
+        if init == 'sample':
+          pick = torch.randperm(M, generator=torch.Generator().manual_seed(int(seed) + s))[:L]
+          book.copy_(res.index_select(0, pick.to(book.device)))
+        distortion, updates = [], []
+        for it in range(n_iter + 1):
+          ops.vq_lloyd_accum(res, book, state, first=True)
+          distortion.append(state['sse'].sum() / float(M))
+          if it < n_iter:
+            updates.append(ops.vq_lloyd_update(book, state, reseed=bool(reseed)))
+        counts = state['counts'].clone()
+        distortion = torch.stack(distortion).cpu().tolist()
+        updates = torch.stack(updates).cpu().tolist() if updates else []
+        reports.append(dict(distortion=[float(v) for v in distortion], dead=[int(r[0]) for r in updates],
+                            reseeded=[int(r[1]) for r in updates], counts=counts))
+      final = self.distortion(x, code_len).cpu().tolist()
+    for s, rep in enumerate(reports):
+      rep['final'] = float(final[s])
+    return reports

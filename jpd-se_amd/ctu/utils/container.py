@@ -1,4 +1,4 @@
-"""What the stored forms share (bitstream .jpdc, entropy .jpda, semantics .jpds, vqstream .jpdv: DESIGN.md 4.18; vqplane .jpdw: 4.19): loading a
+"""What the stored forms share (bitstream .jpdc, entropy .jpda, semantics .jpds, vqstream .jpdv: DESIGN.md 4.18; vqplane .jpdw: 4.19; vqstages .jpdr, magic b'JPDR': 4.23): loading a
 file or a blob, the start of every header (size, magic, format version), the size check of a raw body and the one-row check of a
 packed code.  Each format keeps its own fields, modes and shape checks, and every message is the one its module raised before.
 Everything here runs on the host.

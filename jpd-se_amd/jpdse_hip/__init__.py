@@ -233,6 +233,27 @@ class VqEcLengthsArgs(ctypes.Structure):
               ('bias', ctypes.c_void_p), ('bits', ctypes.c_void_p), ('stream', ctypes.c_void_p)]
 
 
+# the residual quantizer (vq_residual.hip)
+VQ_RES_MAX_STAGES = 8
+
+
+class VqResFwdArgs(ctypes.Structure):
+  _fields_ = [(n, ctypes.c_int32) for n in ('dtype', 'M', 'D', 'L', 'S', 'n_stages')] + \
+             [(n, ctypes.c_void_p) for n in ('x', 'books', 'y', 'index', 'sse', 'residual', 'ws')] + \
+             [('ws_bytes', ctypes.c_size_t), ('stream', ctypes.c_void_p)]
+
+
+class VqResDecodeArgs(ctypes.Structure):
+  _fields_ = [(n, ctypes.c_int32) for n in ('dtype', 'M', 'D', 'L', 'S', 'n_stages')] + \
+             [(n, ctypes.c_void_p) for n in ('index', 'books', 'y', 'status', 'stream')]
+
+
+class VqResBwdArgs(ctypes.Structure):
+  _fields_ = [(n, ctypes.c_int32) for n in ('dtype', 'M', 'D', 'L', 'S', 'n_stages')] + [('sigma', ctypes.c_float)] + \
+             [(n, ctypes.c_void_p) for n in ('dy', 'x', 'books', 'index', 'dx', 'dbooks', 'ws')] + \
+             [('ws_bytes', ctypes.c_size_t), ('stream', ctypes.c_void_p)]
+
+
 _P, _I32, _I64, _F, _SZ = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float,
                            ctypes.c_size_t)
 _CD, _ND = ctypes.POINTER(ConvDesc), ctypes.POINTER(InormDesc)
@@ -372,6 +393,10 @@ SIGNATURES = {
     'jpdse_vq_ec_assign': (_I32, [ctypes.POINTER(VqEcAssignArgs)]),
     'jpdse_vq_ec_lengths': (_I32, [ctypes.POINTER(VqEcLengthsArgs)]),
     'jpdse_vq_quantize_bwd_grouped': (_I32, [ctypes.POINTER(VqQuantizeBwdGroupedArgs)]),
+    'jpdse_vq_res_workspace_size': (_SZ, [_I32, _I32, _I32, _I32]),
+    'jpdse_vq_res_fwd': (_I32, [ctypes.POINTER(VqResFwdArgs)]),
+    'jpdse_vq_res_decode': (_I32, [ctypes.POINTER(VqResDecodeArgs)]),
+    'jpdse_vq_res_bwd': (_I32, [ctypes.POINTER(VqResBwdArgs)]),
 }
 
 # the developer build (same sources, -DJPDSE_DEV): the shipped ABI plus include/jpdse_dev.h

@@ -12,7 +12,8 @@ import torch
 from . import (lib, check, JpdseError, F32, BF16, ConvDesc, PackEntry, InormDesc, EvalMetricsSemArgs, MsssimLossArgs, CodeRateArgs, SemLossArgs, CodeCostArgs, ACT_NONE, PAD_ZERO, PAD_REFLECT)
 from . import (VqSoftFwdArgs, VqHardFwdArgs, VqSoftBwdArgs, VqDecodeArgs, VqDecodeBwdArgs, VqArgmaxArgs, VqPmfArgs, VqPmfBwdArgs,
                VqQuantizeFwdArgs, VqQuantizeBwdArgs, VqRateFwdArgs, VqQuantizeBwdGroupedArgs, VqLloydAccumArgs, VqLloydUpdateArgs,
-               VqEcAssignArgs, VqEcLengthsArgs)
+               VqEcAssignArgs, VqEcLengthsArgs, VqResFwdArgs, VqResDecodeArgs, VqResBwdArgs)
+from . import VQ_RES_MAX_STAGES as _VQ_RES_MAX_STAGES
 
 
 def cpad(c):
@@ -1164,6 +1165,98 @@ def vq_ec_lengths(hist, lam):
   args = VqEcLengthsArgs(G, L, float(lam), hist.data_ptr(), bias.data_ptr(), bits.data_ptr(), torch.cuda.current_stream().cuda_stream)
   check(lib().jpdse_vq_ec_lengths(ctypes.byref(args)), 'vq_ec_lengths')
   return bias, bits
+
+
+# ---- residual quantizer (vq_residual.hip): S stages in one call -----------------------------------------------------
+# books: fp32 [S, L, D], 1 <= S <= VQ_RES_MAX_STAGES; index: int32 [n_stages, M], stage-major: a stage prefix is contiguous.
+VQ_RES_MAX_STAGES = _VQ_RES_MAX_STAGES
+
+
+def _vq_res_dims(books, D=None):
+  assert books.dim() == 3 and books.dtype == torch.float32 and books.is_contiguous(), (books.dtype, tuple(books.shape))
+  S, L, Db = (int(v) for v in books.shape)
+  assert D is None or D == Db, (D, Db)
+  return S, L, Db
+
+
+def _vq_res_stages(n_stages, S, lowest):
+  n = S if n_stages is None else int(n_stages)
+  if not lowest <= n <= S:
+    raise ValueError('n_stages must be in %d .. %d, got %r' % (lowest, S, n_stages))
+  return n
+
+
+def _vq_res_ws(M, D, L, n, dev):
+  return workspace(max(lib().jpdse_vq_res_workspace_size(M, D, L, max(n, 1)), 1), dev)
+
+
+def vq_res_fwd(x, books, n_stages=None, want_sse=False, want_residual=False):
+  """(y, index, sse, residual) of x [M, D] (fp32 or bf16) against the first n_stages (default: all) of books fp32 [S, L, D]
+  (jpdse_vq_res_fwd): index int32 [n_stages, M], stage s the nearest centre of book s to the residual r_s (r_1 = x, r_{s+1} = r_s -
+  books[s][index[s]], fp32, lowest index on a tie); y [M, D] in x's dtype the sum of the chosen centres (fp32, stage order, rounded
+  once); sse float64 [n_stages] the summed |r_{s+1}|^2 after every stage; residual fp32 [M, D] = r_{n_stages + 1}.  sse and
+  residual are None unless wanted.  n_stages = 0 is legal: y = 0, residual = x."""
+  assert x.dim() == 2 and x.is_contiguous(), tuple(x.shape)
+  M, D = int(x.shape[0]), int(x.shape[1])
+  S, L, _ = _vq_res_dims(books, D)
+  assert books.device == x.device
+  n = _vq_res_stages(n_stages, S, 0)
+  y = torch.empty_like(x)
+  index = torch.empty((n, M), dtype=torch.int32, device=x.device)
+  sse = torch.empty(n, dtype=torch.float64, device=x.device) if want_sse else None
+  residual = torch.empty((M, D), dtype=torch.float32, device=x.device) if want_residual else None
+  ws = _vq_res_ws(M, D, L, n, x.device) if want_sse and n > 0 else None
+  args = VqResFwdArgs(code_of(x.dtype), M, D, L, S, n, x.data_ptr(), books.data_ptr(), y.data_ptr(), index.data_ptr(),
+                      sse.data_ptr() if want_sse and n > 0 else None, residual.data_ptr() if want_residual else None,
+                      ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0,
+                      torch.cuda.current_stream().cuda_stream)
+  check(lib().jpdse_vq_res_fwd(ctypes.byref(args)), 'vq_res_fwd')
+  return y, index, sse, residual
+
+
+def vq_res_decode(index, books, n_stages=None, dtype=torch.float32, status=None):
+  """(y, status): y[m] = books[0][index[0][m]] + .. over the first n_stages (default: all the rows of index) in `dtype` [M, D],
+  bit for bit the y of vq_res_fwd with the same n_stages (jpdse_vq_res_decode).  index int32 [S', M].  An index outside [0, L)
+  reads as centre 0 and sets the int32 device word `status` (a zeroed one is made when None): the rule of vq_decode."""
+  S, L, D = _vq_res_dims(books)
+  assert index.dim() == 2 and index.dtype == torch.int32 and index.is_contiguous() and index.device == books.device, \
+      (index.dtype, tuple(index.shape))
+  rows, M = int(index.shape[0]), int(index.shape[1])
+  assert rows <= S, (rows, S)
+  n = _vq_res_stages(n_stages, rows, 1)
+  if status is None:
+    status = torch.zeros(1, dtype=torch.int32, device=books.device)
+  y = torch.empty((M, D), dtype=dtype, device=books.device)
+  args = VqResDecodeArgs(code_of(dtype), M, D, L, S, n, index.data_ptr(), books.data_ptr(), y.data_ptr(), status.data_ptr(),
+                         torch.cuda.current_stream().cuda_stream)
+  check(lib().jpdse_vq_res_decode(ctypes.byref(args)), 'vq_res_decode')
+  return y, status
+
+
+def vq_res_bwd(dy, x, books, index, sigma, want_dx=True, want_dc=True, dc_out=None):
+  """(dx, dbooks) of the SOFT form of every stage of vq_res_fwd -- the straight-through gradient -- for the upstream gradient dy
+  [M, D] (x's dtype) (jpdse_vq_res_bwd; the residuals are recomputed from x and index int32 [S', M]).  dx in x's dtype; dbooks
+  fp32 [S, L, D] (written into dc_out when given), zero for the books beyond S'; either is None when not wanted."""
+  assert x.dim() == 2 and x.is_contiguous(), tuple(x.shape)
+  M, D = int(x.shape[0]), int(x.shape[1])
+  S, L, _ = _vq_res_dims(books, D)
+  assert dy.shape == x.shape and dy.dtype == x.dtype and dy.is_contiguous() and dy.device == x.device, (dy.dtype, tuple(dy.shape))
+  assert index.dim() == 2 and index.dtype == torch.int32 and index.is_contiguous() and index.device == x.device and \
+      int(index.shape[1]) == M and 1 <= int(index.shape[0]) <= S, (index.dtype, tuple(index.shape))
+  n = int(index.shape[0])
+  dx = torch.empty_like(x) if want_dx else None
+  dc = None
+  if want_dc:
+    dc = dc_out if dc_out is not None else torch.empty_like(books)
+    assert dc.dtype == torch.float32 and dc.is_contiguous() and tuple(dc.shape) == (S, L, D) and dc.device == x.device
+    if n < S:
+      dc[n:].zero_()
+  ws = _vq_res_ws(M, D, L, n, x.device) if want_dc else None
+  args = VqResBwdArgs(code_of(x.dtype), M, D, L, S, n, float(sigma), dy.data_ptr(), x.data_ptr(), books.data_ptr(), index.data_ptr(),
+                      dx.data_ptr() if want_dx else None, dc.data_ptr() if want_dc else None, ws.data_ptr() if want_dc else None,
+                      ws.numel() if want_dc else 0, torch.cuda.current_stream().cuda_stream)
+  check(lib().jpdse_vq_res_bwd(ctypes.byref(args)), 'vq_res_bwd')
+  return dx, dc
 
 
 # ---- the host half of the three device coders (streams.py; DESIGN.md 4.18) -----------------------------------------------------
