@@ -1189,6 +1189,17 @@ typedef struct jpdse_vq_res_fwd_args {
   void* stream;
 } jpdse_vq_res_fwd_args;
 int jpdse_vq_res_fwd(const jpdse_vq_res_fwd_args* args);
+/* res_rows_fwd: index and y of res_fwd, bit for bit, by one thread per vector with the residual in registers: no
+ * sse, no residual, no workspace.  n_stages 1 .. S; otherwise res_fwd's limits and JPDSE_EINVAL before any launch. */
+typedef struct jpdse_vq_res_rows_fwd_args {
+  int32_t dtype, M, D, L, S, n_stages;
+  const void* x;
+  const float* books;
+  void* y;
+  int32_t* index;          /* [n_stages][M] */
+  void* stream;
+} jpdse_vq_res_rows_fwd_args;
+int jpdse_vq_res_rows_fwd(const jpdse_vq_res_rows_fwd_args* args);
 typedef struct jpdse_vq_res_decode_args {
   int32_t dtype, M, D, L, S, n_stages;
   const int32_t* index;

@@ -10,6 +10,8 @@
 //       of x), synchronise, subtract the chosen centres (one thread per (vector, component), the book still in LDS) and sum the
 //       squares of the new residual in fp64, synchronise, next book.  x is read once; y is summed at the end from the tile's
 //       indices (LDS) and the books (L2) by the function the decoder uses; a residual is written only when asked for.
+//   vqres_rows_fwd_kernel   index and y of the kernel above, bit for bit, by one THREAD per vector (vq_rows.h): the
+//       residual and the running sum in registers, the stage loop inside the thread, the book restaged per stage.  No sse, no residual.
 //   vqres_decode_kernel  one thread per (vector, component): the same sum from the index planes.
 //   vqres_bwd_kernel     one THREAD per vector (vq_rows.h), stages descending.  r_s is recomputed from x and the indices by the
 //       forward's subtractions, a_s = dy - h_{s+1}, then the three sweeps and the code-book-gradient reduction of vqb_bwd_kernel
@@ -142,6 +144,57 @@ __global__ __launch_bounds__(256) void vqres_fwd_kernel(const T* __restrict__ x,
   }
   if (psse != nullptr && t == 0)
     for (int s = 0; s < n; ++s) psse[(size_t)blockIdx.x * n + s] = bsse[s];
+}
+
+// ---- forward, one thread per vector ------------------------------------------------------------------------------
+// The residual r and the running sum a of a vector live in DP registers each; the stage loop runs inside the thread.  LDS: cb
+// [L][DP] when CBL, restaged per stage between two barriers that EVERY thread reaches (a thread without a vector works on zeros
+// and stores nothing); otherwise book s is read from global memory at wave-uniform addresses.  index: [n][M], n >= 1.
+template <typename T, int DP, bool CBL>
+__global__ __launch_bounds__(256) void vqres_rows_fwd_kernel(const T* __restrict__ x, const float* __restrict__ books, int M, int D,
+                                                            int L, int n, int vec, T* __restrict__ y, int* __restrict__ index) {
+  extern __shared__ float vqresr_lds[];
+  constexpr int V = 256;
+  const int ld = CBL ? DP : D;
+  const int t = threadIdx.x, LD = L * D;
+  const int ntiles = (M + V - 1) / V;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int m0 = tile * V;
+    const bool live = t < M - m0;
+    const int m = live ? m0 + t : M - 1;
+    const size_t row = (size_t)m * D;
+    float r[DP], a[DP];
+#pragma unroll
+    for (int j = 0; j < DP; ++j) r[j] = a[j] = 0.f;
+    if (live) vqb_load_row<T, DP>(x + row, D, vec != 0, r);
+    for (int s = 0; s < n; ++s) {
+      const float* c = books + (size_t)s * LD;
+      if (CBL) {
+        __syncthreads();                         // the book of the stage (or tile) before is free
+        vqb_stage(c, vqresr_lds, D, L, DP);
+        __syncthreads();
+      }
+      const float* cc = CBL ? vqresr_lds : c;
+      float dmin = INFINITY;
+      int bk = 0;
+      for (int k = 0; k < L; ++k) {
+        const float d = vqb_score<DP, CBL>(r, cc + k * ld, D);
+        if (d < dmin) {                          // strict: the lower index keeps a tie, a NaN never wins
+          dmin = d;
+          bk = k;
+        }
+      }
+      const float* ck = cc + bk * ld;
+#pragma unroll
+      for (int j = 0; j < DP; ++j) {
+        const float cj = (CBL || j < D) ? ck[j] : 0.f;
+        r[j] = r[j] - cj;
+        a[j] = s == 0 ? cj : a[j] + cj;          // vqres_sum's additions: stage order, starting FROM the first centre
+      }
+      if (live) index[(size_t)s * M + m] = bk;
+    }
+    if (live) vqb_store_row<T, DP>(y + row, D, vec != 0, a);
+  }
 }
 
 __global__ __launch_bounds__(64) void vqres_sse_kernel(const double* __restrict__ psse, int nb, int n, double* __restrict__ sse) {
@@ -324,6 +377,21 @@ int jpdse_vq_res_fwd(const jpdse_vq_res_fwd_args* a) {
     return rc;
   if (psse == nullptr) return JPDSE_OK;
   return vq_launch("vq_res_fwd(sse)", vqres_sse_kernel, 1, 64, 0, a->stream, psse, nb, n, a->sse);
+}
+
+int jpdse_vq_res_rows_fwd(const jpdse_vq_res_rows_fwd_args* a) {
+  JPDSE_REQUIRE(a != nullptr, "vq_res_rows_fwd: null argument struct");
+  if (int rc = vq_res_check("vq_res_rows_fwd", a->dtype, a->M, a->D, a->L, a->S, a->n_stages)) return rc;
+  JPDSE_REQUIRE(a->n_stages >= 1, "vq_res_rows_fwd: n_stages = %d (1 .. S = %d)", a->n_stages, a->S);
+  JPDSE_REQUIRE(a->x && a->books && a->y && a->index, "vq_res_rows_fwd: null pointer");
+  const int M = a->M, D = a->D, L = a->L;
+  const int vec = vqb_vec(a->dtype, D, {a->x, a->y});
+  const size_t lds = vqb_cb_lds(D, L) ? (size_t)L * vqb_dp(D) * sizeof(float) : 0;
+  return vqb_dispatch(a->dtype, D, L, [&](auto tag, auto dp, auto cbl) {
+    using T = decltype(tag);
+    return vq_launch("vq_res_rows_fwd", vqres_rows_fwd_kernel<T, decltype(dp)::value, decltype(cbl)::value>, vqb_blocks(M, 256), 256,
+                     lds, a->stream, cptr<T>(a->x), a->books, M, D, L, a->n_stages, vec, mptr<T>(a->y), a->index);
+  });
 }
 
 int jpdse_vq_res_decode(const jpdse_vq_res_decode_args* a) {

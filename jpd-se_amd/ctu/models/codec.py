@@ -11,7 +11,7 @@ import contextlib
 import torch
 
 from jpdse_hip import ops
-from ctu.utils import bitstream, entropy, vqplane, vqstream
+from ctu.utils import bitstream, entropy, vqplane, vqstages, vqstream
 
 
 def check_ec_arguments(rate_lambda, n_iter):
@@ -262,6 +262,93 @@ class VQIndexCodec(_Codec):
 
   def rate_denom(self, B, H, W):      # bits per pixel of the local batch
     return B * H * W
+
+
+class VQStagesCodec(VQIndexCodec):
+  """The residual bottleneck's code (vq_stages > 1): int64 [N, S', indices per stage], 1 <= S' <= S, coded as one
+  .jpdr blob per image (ctu.utils.vqstages) that can be cut after any stage: a code or a blob of fewer stages
+  than the model's is legal everywhere on the receiver's side.  The rate term, the entropy-constrained assignment, the context
+  coder and the cost walks are built for one stage and refused here.  The model picks this class; CODECS stays by quantizer."""
+
+  def _n_stages(self):
+    return self.netE.vq_stages
+
+  def check_code(self, code, x_dict, who):
+    geo = N, H, W, code_len, _, _ = self.geometry(x_dict, who)
+    S = self._n_stages()
+    if not torch.is_tensor(code) or code.dim() != 3 or code.dtype not in (torch.int64, torch.int32):
+      raise ValueError('%s: the code must be what get_vq_code returns with vq_stages = %d: an int64 [N, stages, indices] tensor'
+                       % (who, S))
+    if not 1 <= int(code.shape[1]) <= S:
+      raise ValueError('%s: a code of %d stages, the model (vq_stages) has 1 .. %d' % (who, int(code.shape[1]), S))
+    if (int(code.shape[0]), int(code.shape[2])) != (N, code_len):
+      raise ValueError('%s: code of shape %s, but %d label maps of %d x %d carry a code of shape %s'
+                       % (who, tuple(code.shape), N, H, W, (N, int(code.shape[1]), code_len)))
+    return geo
+
+  def check_payloads(self, blobs, x_dict, who):
+    geo = N, H, W, code_len, L, groups = self.geometry(x_dict, who)
+    S = self._n_stages()
+    if not isinstance(blobs, (list, tuple)) or len(blobs) != N:
+      raise ValueError('%s: the blobs must be what get_coded returns: a list of %d .jpdr bytes objects, one per '
+                       'label map' % (who, N))
+    counts = []
+    for j, b in enumerate(blobs):                 # every header on the host
+      Sb, n, cl, Lb, _ = vqstages.parse_stages(b, '%s: blob %d' % (who, j))
+      if Lb != L:
+        raise ValueError('%s: blob %d was coded for n_center %d, the code book has %d' % (who, j, Lb, L))
+      if n * cl != code_len:
+        raise ValueError('%s: blob %d holds %d x %d indices per stage, a %d x %d label map carries %d'
+                         % (who, j, n, cl, H, W, code_len))
+      if Sb > S:
+        raise ValueError('%s: blob %d holds %d stages, the model (vq_stages) has %d' % (who, j, Sb, S))
+      counts.append(Sb)
+    if len(set(counts)) > 1:
+      raise ValueError('%s: the blobs of one call must hold the same stage count, got %s' % (who, counts))
+    return geo
+
+  def check_rate_lambda(self, rate_lambda, n_iter, who):
+    if check_ec_arguments(rate_lambda, n_iter) > 0:
+      raise ValueError('%s: rate_lambda > 0 (the entropy-constrained code) is built for one stage, the model has vq_stages = %d'
+                       % (who, self._n_stages()))
+
+  def check_stages(self, stages, who):
+    """ValueError for a stage count outside 1 .. vq_stages.  Host only."""
+    if stages is not None and (isinstance(stages, bool) or not isinstance(stages, int) or not 1 <= stages <= self._n_stages()):
+      raise ValueError('%s: stages must be an int in 1 .. %d (vq_stages), got %r' % (who, self._n_stages(), stages))
+
+  def code(self, src, rate_lambda=0.0, n_iter=2, stages=None):
+    self.ec_reports = None
+    return self.netE.vq_code(src, stages).to(torch.int64)
+
+  def features_of_payloads(self, blobs, geo, device, who):
+    code_len = geo[3]
+
+    def features():
+      code = torch.stack([vqstages.read_stages(bytes(b), device()).view(-1, code_len) for b in blobs], dim=0)
+      return self.features_of_code(code, geo, device, who)()
+
+    return features
+
+  def payloads(self, code, x_dict):
+    """One .jpdr blob per image, every stage a .jpdv blob in (C / D) * 8 streams as VQIndexCodec writes its one."""
+    _, _, _, code_len, L, groups = self.geometry(x_dict, 'get_coded')
+    return [vqstages.write_stages(None, code[i].reshape(code.shape[1], 1, code_len).contiguous(), L,
+                                  n_streams=groups * self.INDEX_STREAMS_PER_GROUP) for i in range(code.shape[0])]
+
+  def check_coder(self, coder, who):
+    raise ValueError('%s: the cost walks are built for one stage, the model has vq_stages = %d' % (who, self._n_stages()))
+
+  def cost(self, code, x_dict, label=None, n_classes=0, coder=None):
+    self.check_coder(coder, 'cost')
+
+  def file_rates(self, payloads, H, W):
+    """(coded bpp, raw bpp), batch means: the .jpdr blobs, and the packed-index files of the same stages (S' times the one-stage
+    packed size)."""
+    coded = sum(8.0 * len(p) / (H * W) for p in payloads) / len(payloads)
+    stages = vqstages.parse_stages(payloads[0], 'file_rates')[0]
+    raw = vqstream.HEADER_BYTES + vqstream.packed_bytes(self.netE.vq_code_len(H, W), self.netE._vq.n_center)
+    return coded, 8.0 * stages * raw / (H * W)
 
 
 CODECS = {'binarizer': BinaryCodec, 's2hvq': VQIndexCodec}

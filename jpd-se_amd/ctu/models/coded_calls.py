@@ -5,7 +5,7 @@ import torch
 
 from jpdse_hip import F32, ops
 from ctu.utils import semantics as semantics_file
-from ctu.models.codec import VQIndexCodec
+from ctu.models.codec import VQIndexCodec, VQStagesCodec
 
 
 class CodedCalls(object):
@@ -42,9 +42,24 @@ class CodedCalls(object):
       raise ValueError('%s: the vector-quantised code needs --encoder_quantizer s2hvq' % who)
     return self.codec
 
-  def _eval_code(self, codec, x_dict, rate_lambda=0.0, n_iter=2):
+  def _one_stage(self, who):
+    """The refusal of a call that is built for one stage of the vector quantizer.  Host only."""
+    if isinstance(self.codec, VQStagesCodec):
+      raise ValueError('%s: built for one stage of the vector quantizer, this model has vq_stages = %d'
+                       % (who, self.codec._n_stages()))
+
+  def _check_stages(self, codec, stages, who):
+    """`stages` of get_vq_code / get_coded_stages against the model's stage count.  Host only."""
+    if isinstance(codec, VQStagesCodec):
+      codec.check_stages(stages, who)
+    elif isinstance(stages, bool) or stages not in (None, 1):
+      raise ValueError('%s: stages = %r, this model has vq_stages = 1: None or 1' % (who, stages))
+
+  def _eval_code(self, codec, x_dict, rate_lambda=0.0, n_iter=2, stages=None):
     """The encoder's eval-mode code of x_dict (the decoded frame with --use_compressed) in the codec's form."""
     pre = self.preprocess(x_dict, build_base=False)
+    if isinstance(codec, VQStagesCodec):
+      return self._encoder_eval(lambda: codec.code(pre['src'], stages=stages))
     if rate_lambda == 0:
       return self._encoder_eval(lambda: codec.code(pre['src']))
     return self._encoder_eval(lambda: codec.code(pre['src'], rate_lambda, n_iter))
@@ -89,23 +104,27 @@ class CodedCalls(object):
       return shannon / b.N, actual / b.N
 
   # ---- the vector-quantised code (extension) ------------------------------------------------------------------
-  def get_vq_code(self, x_dict, rate_lambda=0.0, n_iter=2):
+  def get_vq_code(self, x_dict, rate_lambda=0.0, n_iter=2, stages=None):
     """The eval-mode code of the vector-quantizer bottleneck: int64 [N, h * w * C / D] on the device, per image the index of
     the nearest centre of every group of D channels, pixel by pixel, groups ascending inside a pixel.
     rate_lambda > 0: the entropy-constrained code -- every index minimises |x - c_k|^2 + rate_lambda * the
     code length of k under the histogram of its image and channel group, n_iter rounds of S2HVQ.encode_ec per image.  An
     ordinary code: decode, get_coded's files and both cost walks take it unchanged.  ValueError, before any device work, for
-    a rate_lambda that is negative or not finite and an n_iter that is no int >= 0.  The defaults give today's bits."""
+    a rate_lambda that is negative or not finite and an n_iter that is no int >= 0.  The defaults give today's bits.
+    With vq_stages > 1: int64 [N, stages, h * w * C / D], the first `stages` (default: all) stages; every stage
+    prefix code[:, :n] is a code decode takes; rate_lambda > 0 is refused.  With one stage `stages` must be None or 1."""
     codec = self._vq_codec('get_vq_code')
     codec.check_rate_lambda(rate_lambda, n_iter, 'get_vq_code')
+    self._check_stages(codec, stages, 'get_vq_code')
     with torch.no_grad():
-      return self._eval_code(codec, x_dict, rate_lambda, n_iter)
+      return self._eval_code(codec, x_dict, rate_lambda, n_iter, stages)
 
   def get_vq_ec_report(self, x_dict, rate_lambda, n_iter=2):
     """The per-image reports of the entropy-constrained code get_vq_code(x_dict, rate_lambda, n_iter): a list of N dicts
     (distortion, bits, cost: n_iter + 1 Python floats each; S2HVQ.encode_ec).  rate_lambda == 0 runs the same rounds with a
     zero bias: every entry repeats the plain code's figures."""
     codec = self._vq_codec('get_vq_ec_report')
+    self._one_stage('get_vq_ec_report')
     codec.check_rate_lambda(rate_lambda, n_iter, 'get_vq_ec_report')
     with torch.no_grad():
       pre = self.preprocess(x_dict, build_base=False)
@@ -117,6 +136,7 @@ class CodedCalls(object):
     zero-order entropy of get_vq_code(x_dict) per channel group, histograms taken over the batch.  An estimate, not a size:
     get_coded_rate measures the .jpdv files, whose adaptive coder may land on either side of it."""
     self._vq_codec('get_vq_rate')
+    self._one_stage('get_vq_rate')
     with torch.no_grad():
       pre = self.preprocess(x_dict, build_base=False)
       src = pre['src']
@@ -128,6 +148,7 @@ class CodedCalls(object):
     (G = C / D), counted over the batch (ops.vq_rate_fwd, hard, its histogram).  A column of zeros is a dead centre: what
     fit_vq_code_book repairs.  Every row sums to the indices per group, N h w."""
     self._vq_codec('get_vq_usage')
+    self._one_stage('get_vq_usage')
     with torch.no_grad():
       pre = self.preprocess(x_dict, build_base=False)
       src = pre['src']
@@ -142,7 +163,8 @@ class CodedCalls(object):
     S2HVQ.fit's.  Several ranks: the fit is deterministic and adds no collective; every rank that calls it with the same batches
     gets the same bits, so call it on every rank with the same list (or broadcast the book afterwards).
     ValueError before any device work: without --encoder_quantizer s2hvq, with --zero_vis (the encoder does not run), for an
-    empty list, and for the arguments S2HVQ.fit refuses."""
+    empty list, and for the arguments S2HVQ.fit refuses.
+    With vq_stages > 1 the books are fitted stage by stage (ResidualS2HVQ.fit) and the list of per-stage reports is returned."""
     self._vq_codec('fit_vq_code_book')
     if self.zero_vis:
       raise ValueError('fit_vq_code_book: with --zero_vis the encoder does not run, there are no features to fit')
@@ -198,10 +220,20 @@ class CodedCalls(object):
     decode(get_code(x, packed=True), x) bit for bit.
     With --encoder_quantizer s2hvq: a list of N .jpdv blobs (ctu.utils.vqstream), one per image, of that image's
     get_vq_code row; with --vq_context_coder an item is the image's .jpdw blob (ctu.utils.vqplane) where
-    that is the smaller of the two."""
+    that is the smaller of the two.  With vq_stages > 1: a list of N .jpdr blobs (ctu.utils.vqstages) of all stages, which
+    vqstages.truncate_stages cuts after any stage without the device."""
     codec = self.codec or self._binary_codec()
     with torch.no_grad():
       return codec.payloads(self._eval_code(codec, x_dict), x_dict)
+
+  def get_coded_stages(self, x_dict, stages=None):
+    """get_coded of the first `stages` stages (vq_stages > 1): the .jpdr blobs of get_vq_code(x_dict,
+    stages=stages), byte for byte what vqstages.truncate_stages makes of get_coded's.  (A call of its own: the signature of
+    get_coded is pinned.)  With one stage `stages` must be None or 1 and the blobs are get_coded's."""
+    codec = self._vq_codec('get_coded_stages')
+    self._check_stages(codec, stages, 'get_coded_stages')
+    with torch.no_grad():
+      return codec.payloads(self._eval_code(codec, x_dict, stages=stages), x_dict)
 
   def get_coded_ec(self, x_dict, rate_lambda=0.0, n_iter=2):
     """get_coded at another point of the rate-distortion curve: the blobs of get_vq_code(x_dict, rate_lambda,
@@ -209,6 +241,7 @@ class CodedCalls(object):
     get_coded is pinned.)  ValueError, before any device work: rate_lambda > 0 without --encoder_quantizer s2hvq, and what
     get_vq_code refuses."""
     codec = self.codec or self._binary_codec()
+    self._one_stage('get_coded_ec')
     codec.check_rate_lambda(rate_lambda, n_iter, 'get_coded_ec')
     with torch.no_grad():
       return codec.payloads(self._eval_code(codec, x_dict, rate_lambda, n_iter), x_dict)
@@ -220,7 +253,8 @@ class CodedCalls(object):
     With --encoder_quantizer s2hvq the items are the .jpdv blobs of get_coded; each header's n * code_len and L must fit the
     label map and the code book (checked on the host first); decode_coded(get_coded(x), x) equals get_img(x) bit for bit.
     A .jpdw blob (--vq_context_coder at the sender; told by its magic, no flag needed here) is taken in any item: its h, w, G
-    and L must fit in the same way."""
+    and L must fit in the same way.  With vq_stages > 1 the items are .jpdr blobs of any stage count 1 .. vq_stages, the same
+    in every item: a truncated stream decodes to the image of that stage prefix."""
     codec = self.codec or self._binary_codec()
     geo = codec.check_payloads(payloads, x_dict, 'decode_coded')
     with torch.no_grad():

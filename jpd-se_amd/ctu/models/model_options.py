@@ -165,18 +165,19 @@ def parse_class_distortion_weights(text, n_labels):
 # with its bottleneck whose output reaches the generator (no --zero_vis); sem_weights: (class table, edge weight), or None when
 # every weight is 1; compute_dtype: 'fp32' / 'bf16'; feat_nc (the encoder's output channels), nef, n_downsample_E and the keyword
 # arguments encoder_args: what networks.define_G takes for the encoder; the last five: what the constructor reads behind network
-# construction
+# construction; vq_stages / vq_train_stages: the residual bottleneck's code books and its training schedule
 ModelOptions = collections.namedtuple('ModelOptions', [
     'feat_enc', 'quantizer', 'encoder_runs', 'lambda_rate', 'lambda_vq_rate', 'vq_context_coder', 'sem_weights', 'compute_dtype',
     'n_onehot', 'label_nc', 'feat_nc', 'zero_vis', 'zero_sem', 'zero_ins', 'no_instance', 'codec_seed',
     'nef', 'n_downsample_E', 'encoder_args',
-    'checkpoint_resblocks', 'load_model', 'vgg19_state_dict', 'no_vgg_loss', 'vgg_random_init'])
+    'checkpoint_resblocks', 'load_model', 'vgg19_state_dict', 'no_vgg_loss', 'vgg_random_init', 'vq_stages', 'vq_train_stages'])
 
 
 def resolve_model_options(opt):
   """opt -> ModelOptions, or the refusal.  The order of the checks is part of the contract: first everything outside the
   accelerated path in ONE NotImplementedError, then distortion_loss_fn, lambda_rate, lambda_vq_rate, vq_context_coder,
-  encoder_quantizer (with the bottleneck's own check), then the class weights, the edge weight and their conflict with ms_ssim."""
+  encoder_quantizer (with the bottleneck's own check), vq_stages and vq_train_stages (opt fields without a flag),
+  then the class weights, the edge weight and their conflict with ms_ssim."""
   g = lambda name, default=False: getattr(opt, name, default)
   feat_enc = not g('no_feat_encoding')
   bottleneck = feat_enc and not g('no_encoder_binarization')
@@ -246,6 +247,27 @@ def resolve_model_options(opt):
     from jpdse_hip.layers import vq_bottleneck_check
     vq_bottleneck_check(int(enc['encoder_binarizer_out_channels']), int(enc['vq_n_center']), int(enc['vq_center_size']),
                         enc['vq_sigma'], '--encoder_quantizer s2hvq')
+  # residual bottleneck: fields a caller sets on the parsed namespace; absent or 1 / 'all': nothing changes
+  vq_stages = g('vq_stages', 1)
+  if isinstance(vq_stages, bool) or not isinstance(vq_stages, int) or not 1 <= vq_stages <= ops.VQ_RES_MAX_STAGES:
+    raise ValueError('vq_stages must be an int in 1 .. %d, got %r' % (ops.VQ_RES_MAX_STAGES, vq_stages))
+  if vq_stages > 1:
+    if quantizer != 's2hvq':
+      raise ValueError('vq_stages = %d is the stage count of the vector-quantizer bottleneck: it needs --encoder_quantizer s2hvq'
+                       % vq_stages)
+    if not enc['vq_hard_forward']:
+      raise ValueError('vq_stages = %d cannot be combined with --vq_soft_forward: the soft forward is built for one stage' % vq_stages)
+    if lambda_vq_rate > 0.0:
+      raise ValueError('vq_stages = %d cannot be combined with --lambda_vq_rate > 0: the rate term is built for one stage' % vq_stages)
+    if vq_context_coder:
+      raise ValueError('vq_stages = %d cannot be combined with --vq_context_coder: the context coder is built for one stage'
+                       % vq_stages)
+  vq_train_stages = g('vq_train_stages', 'all')
+  if vq_train_stages not in ('all', 'uniform'):
+    raise ValueError("vq_train_stages must be 'all' or 'uniform', got %r" % (vq_train_stages,))
+  if vq_train_stages == 'uniform' and vq_stages == 1:
+    raise ValueError("vq_train_stages = 'uniform' draws a stage prefix per step: it needs vq_stages > 1")
+  enc['vq_stages'] = vq_stages
   # semantics-weighted distortion: (class table, edge weight), or None when every weight is 1 -- the
   # step then takes the plain l1 / mse path
   n_onehot = opt.num_labels + 1 if g('contain_dontcare_label') else opt.num_labels
@@ -274,4 +296,5 @@ def resolve_model_options(opt):
       zero_vis=zero_vis, zero_sem=zero_sem, zero_ins=bool(g('zero_ins')) and not zero_sem and not no_instance,
       no_instance=no_instance, codec_seed=int(g('seed', None) or 0), nef=g('nef', 64), n_downsample_E=n_downsample_E,
       encoder_args=enc, checkpoint_resblocks=bool(g('checkpoint_resblocks')), load_model=bool(g('load_model')),
-      vgg19_state_dict=g('vgg19_state_dict', None), no_vgg_loss=bool(g('no_vgg_loss')), vgg_random_init=bool(g('vgg_random_init')))
+      vgg19_state_dict=g('vgg19_state_dict', None), no_vgg_loss=bool(g('no_vgg_loss')), vgg_random_init=bool(g('vgg_random_init')),
+      vq_stages=vq_stages, vq_train_stages=vq_train_stages)

@@ -32,7 +32,7 @@ from jpdse_hip.ops import Act
 from jpdse_hip.optim import FusedAdam
 from jpdse_hip.layers import PackBatcher
 from ctu.utils.image_pool import ImagePool
-from ctu.models.codec import CODECS
+from ctu.models.codec import CODECS, VQStagesCodec
 from ctu.models.coded_calls import CodedCalls
 from ctu.models.model_options import add_model_options, parse_class_distortion_weights, resolve_model_options  # noqa: F401
 from ctu.models.pix2pixHD_networks.base_model import BaseModel
@@ -83,13 +83,16 @@ class Pix2PixHDModel(CodedCalls, BaseModel):
     # resolve_model_options leaves a positive weight to the quantizer in use only
     self.rate_weight = 0.0
     if self.netE is not None and self.netE.quantizer is not None:
-      self.codec = CODECS[self.netE.quantizer](self.netE, self.cdtype)
+      # more than one stage of the vector quantizer (opt.vq_stages): the subclass that writes .jpdr files
+      staged = self.netE.quantizer == 's2hvq' and o.vq_stages > 1
+      self.codec = (VQStagesCodec if staged else CODECS[self.netE.quantizer])(self.netE, self.cdtype)
       self.rate_weight = getattr(self, self.codec.RATE_OPTION)
       if self.vq_context_coder:
         self.codec.context_coder = True
     # binarizer noise: Philox key = the run's seed, counter = (element, image index in the global batch,
     # number of training forwards so far)
     self.codec_seed, self.codec_draw = o.codec_seed, 0
+    self.vq_stages, self.vq_train_stages = o.vq_stages, o.vq_train_stages
     print('---------- networks initialized -------------')
     if not self.is_train or o.load_model:
       self.load_network(self.netG, 'G', opt)
@@ -254,8 +257,20 @@ class Pix2PixHDModel(CodedCalls, BaseModel):
       return base                        # onehot_edge leaves every lane behind the semantics zero
     return self._with_image(base, vis)
 
+  def train_stage_count(self, step):
+    """Stages the residual bottleneck uses in training forward `step`: all of them, or with vq_train_stages =
+    'uniform' a draw from 1 .. vq_stages that is a pure host-side function of (seed, step) -- every rank draws the same."""
+    if self.vq_train_stages != 'uniform':
+      return self.vq_stages
+    gen = torch.Generator().manual_seed(self.codec_seed * 1000003 + int(step))
+    return 1 + int(torch.randint(self.vq_stages, (1,), generator=gen))
+
   def _set_codec_rng(self, local_batch):
-    """Point the binarizer at this call's images: n_global = rank * local_batch + i."""
+    """Point the binarizer at this call's images: n_global = rank * local_batch + i.  A residual bottleneck gets this training
+    forward's stage count instead (eval mode ignores it)."""
+    if isinstance(self.codec, VQStagesCodec):
+      self.netE._vq.train_stages = self.train_stage_count(self.codec_draw)
+      return
     b = self.netE._binarizer
     if b is None:
       return

@@ -17,7 +17,7 @@ from jpdse_hip import (ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, PAD_ZERO, PAD_RE
                        require_gpu)
 from jpdse_hip import ops
 from jpdse_hip.ops import Act
-from jpdse_hip.layers import (HipConv2d, HipResnetBlock, HipBinarizer, HipVQBottleneck, vq_bottleneck_check, InstNormAct,
+from jpdse_hip.layers import (HipConv2d, HipResnetBlock, HipBinarizer, HipVQBottleneck, HipResidualVQBottleneck, vq_bottleneck_check, InstNormAct,
                               ConvNormAct, Ctx, _Slot,
                               run_chain_fwd, run_chain_bwd)
 
@@ -216,13 +216,15 @@ class Encoder(nn.Module):
   front of an affine-less InstanceNorm are not applied -- the norm cancels them).
   quantizer='s2hvq' (extension): the bottleneck slot holds a HipVQBottleneck -- 1x1 conv and soft-to-hard vector
   quantizer over groups of vq_center_size channels -- instead of the Binarizer; binarizer_out_channels still names the
-  bottleneck's channel count.  Its code is vq_code / decode_vq_code; code / code_shape / decode_code stay the binarizer's."""
+  bottleneck's channel count.  Its code is vq_code / decode_vq_code; code / code_shape / decode_code stay the binarizer's.
+  vq_stages > 1: the slot holds a HipResidualVQBottleneck of that many code books; vq_code is then int32
+  [N, stages, indices] and every stage prefix of it decodes."""
 
   QUANTIZERS = ('binarizer', 's2hvq')
 
   def __init__(self, input_nc, output_nc, ngf=32, n_downsampling=4, norm_layer=None, binarize=False,
                binarizer_out_channels=128, groups=1, compute_dtype='fp32', device=None, quantizer='binarizer',
-               vq_n_center=64, vq_center_size=8, vq_sigma=10.0, vq_hard_forward=True):
+               vq_n_center=64, vq_center_size=8, vq_sigma=10.0, vq_hard_forward=True, vq_stages=1):
     super(Encoder, self).__init__()
     if quantizer not in self.QUANTIZERS:
       raise ValueError('Encoder: quantizer must be one of %s, got %r' % (self.QUANTIZERS, quantizer))
@@ -246,7 +248,11 @@ class Encoder(nn.Module):
       c = ngf * 2 ** i
       slots[4 + 3 * i] = HipConv2d(c, 2 * c, 3, 2, 1, PAD_ZERO, apply_bias=False, **kw)
       self._pre.append(ConvNormAct(slots[4 + 3 * i], InstNormAct(ACT_RELU)))
-    if binarize and quantizer == 's2hvq':
+    if binarize and quantizer == 's2hvq' and int(vq_stages) > 1:
+      if not vq_hard_forward:
+        raise ValueError('Encoder: vq_stages = %d with the soft forward, which is built for one stage' % int(vq_stages))
+      slots[4 + 3 * n] = HipResidualVQBottleneck(ngf * 2 ** n, B, vq_n_center, vq_center_size, int(vq_stages), vq_sigma, **kw)
+    elif binarize and quantizer == 's2hvq':
       slots[4 + 3 * n] = HipVQBottleneck(ngf * 2 ** n, B, vq_n_center, vq_center_size, vq_sigma, vq_hard_forward, **kw)
     elif binarize:
       slots[4 + 3 * n] = HipBinarizer(ngf * 2 ** n, B, **kw)
@@ -319,17 +325,29 @@ class Encoder(nn.Module):
       raise AttributeError('Encoder: no vector quantizer found (quantizer=%r)' % (self.quantizer,))
     return self._vq
 
+  @property
+  def vq_stages(self):
+    """Code books of the vector-quantizer bottleneck: 1 for HipVQBottleneck."""
+    return getattr(self._require_vq(), 'n_stages', 1)
+
   def vq_code_len(self, H, W):
-    """Indices per image of an H x W input: (H / 2^n) (W / 2^n) cout / D."""
+    """Indices per image AND STAGE of an H x W input: (H / 2^n) (W / 2^n) cout / D."""
     vq, n = self._require_vq(), self.n_downsampling
     return (H >> n) * (W >> n) * (vq.cout // vq.center_size)
 
-  def vq_code(self, x):
+  def vq_code(self, x, stages=None):
     """int32 [N, h * w * cout / D]: the nearest centre of every channel group of every pixel of the bottleneck's features, pixel
-    by pixel, groups ascending inside a pixel: model[:4 + 3n + 1](x) as indices."""
+    by pixel, groups ascending inside a pixel: model[:4 + 3n + 1](x) as indices.  With vq_stages > 1: int32 [N, stages, h * w *
+    cout / D], the first `stages` (default: all) stages; with one stage `stages` must be None or 1."""
     vq = self._require_vq()
+    if self.vq_stages == 1:
+      if stages not in (None, 1) or isinstance(stages, bool):
+        raise ValueError('Encoder.vq_code: stages = %r, the bottleneck has one stage (vq_stages = 1)' % (stages,))
+      h, _ = run_chain_fwd(self._pre, x)
+      return vq.code(h)
+    vq._stages(stages)                     # before any device work
     h, _ = run_chain_fwd(self._pre, x)
-    return vq.code(h)
+    return vq.code(h, stages)
 
   def vq_code_ec(self, x, lam, n_iter=2):
     """(index, reports): vq_code under the entropy constraint: the first half runs once, then the bottleneck's
@@ -359,7 +377,8 @@ class Encoder(nn.Module):
 
   def decode_vq_code(self, index, H, W):
     """The receiver's half: (features, status) from the int32 [N, h * w * cout / D] indices of an H x W image (ops.vq_decode,
-    then model[4 + 3n + 1:]); status: the device word of ops.vq_decode, non-zero for an index outside the code book."""
+    then model[4 + 3n + 1:]); status: the device word of ops.vq_decode, non-zero for an index outside the code book.  With
+    vq_stages > 1 the indices are int32 [N, S', h * w * cout / D], any stage prefix 1 <= S' <= vq_stages (ops.vq_res_decode)."""
     vq, n = self._require_vq(), self.n_downsampling
     b, status = vq.decode(index, int(index.shape[0]), H >> n, W >> n, self.cdtype)
     y, _ = run_chain_fwd(self._post, b)
@@ -381,7 +400,7 @@ def define_G(input_nc, output_nc, ngf, netG, n_downsample_global=3, n_blocks_glo
              n_blocks_local=3, norm='instance', gpu_ids=[], binarize_encoder=False,
              encoder_binarizer_out_channels=128, encoder_groups=1, binarize_generator=False,
              bin_generator_before_res=True, generator_binarizer_out_channels=128, compute_dtype='fp32',
-             encoder_quantizer='binarizer', vq_n_center=64, vq_center_size=8, vq_sigma=10.0, vq_hard_forward=True):
+             encoder_quantizer='binarizer', vq_n_center=64, vq_center_size=8, vq_sigma=10.0, vq_hard_forward=True, vq_stages=1):
   get_norm_layer(norm)
   device = torch.device('cuda', gpu_ids[0]) if len(gpu_ids) > 0 else None
   if device is not None:
@@ -396,7 +415,7 @@ def define_G(input_nc, output_nc, ngf, netG, n_downsample_global=3, n_blocks_glo
     net = Encoder(input_nc, output_nc, ngf, n_downsample_global, binarize=binarize_encoder,
                   binarizer_out_channels=encoder_binarizer_out_channels, groups=encoder_groups,
                   compute_dtype=compute_dtype, device=device, quantizer=encoder_quantizer, vq_n_center=vq_n_center,
-                  vq_center_size=vq_center_size, vq_sigma=vq_sigma, vq_hard_forward=vq_hard_forward)
+                  vq_center_size=vq_center_size, vq_sigma=vq_sigma, vq_hard_forward=vq_hard_forward, vq_stages=vq_stages)
   else:
     raise ValueError('generator not implemented!')
   return net

@@ -22,13 +22,13 @@ MAX_STAGES = ops.VQ_RES_MAX_STAGES
 
 
 class _ResidualQuantize(torch.autograd.Function):
-  """(y, index) of ops.vq_res_fwd over the first `stages` books; backward: ops.vq_res_bwd from the saved x, books and indices.
-  The books beyond `stages` get a zero gradient."""
+  """(y, index) of ops.vq_res_rows_fwd (vq_res_fwd's bits) over the first `stages` books; backward:
+  ops.vq_res_bwd from the saved x, books and indices.  The books beyond `stages` get a zero gradient."""
 
   @staticmethod
   def forward(ctx, x, books, sigma, stages):
     x, books = x.contiguous(), books.contiguous()
-    y, index, _, _ = ops.vq_res_fwd(x, books, stages)
+    y, index = ops.vq_res_rows_fwd(x, books, stages)
     ctx.save_for_backward(x, books, index)
     ctx.sigma = sigma
     ctx.mark_non_differentiable(index)
@@ -120,7 +120,7 @@ class ResidualS2HVQ(nn.Module):
     if self.training and torch.is_grad_enabled():
       y, index = _ResidualQuantize.apply(xm, self._code_books, float(self._sigma), n_st)
     else:
-      y, index, _, _ = ops.vq_res_fwd(xm.detach(), self._code_books.detach().contiguous(), n_st)
+      y, index = ops.vq_res_rows_fwd(xm.detach(), self._code_books.detach().contiguous(), n_st)
     return y.view(n, code_len * self._center_size), index.to(torch.int64).view(n_st, n, code_len)
 
   def encode(self, x, code_len, stages=None):
@@ -128,7 +128,7 @@ class ResidualS2HVQ(nn.Module):
     n_st = self._stages(stages)
     with torch.no_grad():
       xm = self._vectors(x, code_len).detach()
-      _, index, _, _ = ops.vq_res_fwd(xm, self._code_books.detach().contiguous(), n_st)
+      _, index = ops.vq_res_rows_fwd(xm, self._code_books.detach().contiguous(), n_st)
     return index.to(torch.int64).view(n_st, x.size(0), code_len)
 
   def decode(self, code, stages=None):

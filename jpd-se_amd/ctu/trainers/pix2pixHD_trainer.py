@@ -14,7 +14,7 @@ from torch.optim.lr_scheduler import ReduceLROnPlateau
 from ctu.models.pix2pixHD_model import Pix2PixHDModel
 from ctu.trainers.base_trainer import BaseTrainer
 from jpdse_hip.ddp import GradBuckets
-from jpdse_hip.layers import HipConv2d, HipVQBottleneck, bump_weights_epoch
+from jpdse_hip.layers import HipConv2d, HipVQBottleneck, HipResidualVQBottleneck, bump_weights_epoch
 
 
 class Pix2PixHDTrainer(BaseTrainer):
@@ -89,6 +89,8 @@ class Pix2PixHDTrainer(BaseTrainer):
         m.grad_ready_hook = (lambda mod, b=buckets: (b.mark_ready(mod.weight), b.mark_ready(mod.bias)))
       elif isinstance(m, HipVQBottleneck):
         m.grad_ready_hook = (lambda mod, b=buckets: b.mark_ready(mod.vq._code_book))
+      elif isinstance(m, HipResidualVQBottleneck):
+        m.grad_ready_hook = (lambda mod, b=buckets: b.mark_ready(mod.vq._code_books))
 
   def update_fixed_params(self):
     """End of the `niter_fix_global` phase (train.py calls model.update_fixed_params and swaps the optimizer,
@@ -133,13 +135,39 @@ class Pix2PixHDTrainer(BaseTrainer):
     with torch.no_grad():
       return torch.cat([c for c in self.model.get_code(x_dict, packed) if c is not None], dim=-1)
 
-  def get_vq_code(self, x_dict, rate_lambda=0.0, n_iter=2):
+  def get_vq_code(self, x_dict, rate_lambda=0.0, n_iter=2, stages=None):
     """The code of the vector-quantizer bottleneck (--encoder_quantizer s2hvq): int64 [N, h * w * C / D] on the
     device.  decode(get_vq_code(x), x) equals get_img(x) bit for bit; get_coded / decode_coded / get_coded_rate store it as
     .jpdv blobs.  rate_lambda > 0: the entropy-constrained code (DESIGN.md 4.22), a lower rate from the same trained model;
-    the receiver is untouched."""
+    the receiver is untouched.  With opt.vq_stages > 1: int64 [N, stages, h * w * C / D], stored as .jpdr
+    blobs; every stage prefix code[:, :n] decodes."""
     self.eval()
-    return self.model.get_vq_code(x_dict, rate_lambda=rate_lambda, n_iter=n_iter)
+    return self.model.get_vq_code(x_dict, rate_lambda=rate_lambda, n_iter=n_iter, stages=stages)
+
+  def get_coded_stages(self, x_dict, stages=None):
+    """get_coded of the first `stages` stages of a residual bottleneck (opt.vq_stages > 1): byte for byte
+    vqstages.truncate_stages of get_coded's blobs."""
+    self.eval()
+    return self.model.get_coded_stages(x_dict, stages=stages)
+
+  def get_stage_curve(self, x_dict):
+    """The rate-distortion points of one coded stream cut after every stage (opt.vq_stages > 1): a list of
+    vq_stages dicts, one per prefix n = 1 .. vq_stages: `stages`, `bpp` (8 * the bytes of vqstages.truncate_stages(blob, n) per
+    pixel, batch mean) and `l1`, `mse`, `psnr`, `ms_ssim` of get_eval_metrics_decoded of that prefix.  One encoder run, one
+    generator run per prefix."""
+    from ctu.utils import vqstages
+    self.eval()
+    code = self.model.get_vq_code(x_dict)
+    if code.dim() != 3:
+      raise ValueError('get_stage_curve: needs a residual bottleneck (opt.vq_stages > 1)')
+    blobs = self.model.codec.payloads(code, x_dict)
+    pixels = int(x_dict['image'].shape[-2]) * int(x_dict['image'].shape[-1])
+    rows = []
+    for n in range(1, int(code.shape[1]) + 1):
+      m = self.model.get_eval_metrics_decoded(code[:, :n].contiguous(), x_dict)
+      bpp = sum(8.0 * len(vqstages.truncate_stages(b, n)) / pixels for b in blobs) / len(blobs)
+      rows.append(dict(stages=n, bpp=bpp, l1=m['l1'], mse=m['mse'], psnr=m['psnr'], ms_ssim=m['ms_ssim']))
+    return rows
 
   def get_vq_ec_report(self, x_dict, rate_lambda, n_iter=2):
     """The per-image reports (distortion, bits, cost per round) of the entropy-constrained code."""
@@ -163,7 +191,7 @@ class Pix2PixHDTrainer(BaseTrainer):
     """Fit the vector quantizer's code book to the encoder's features of a list of batches by k-means on the device, dead
     centres reseeded (extension): Pix2PixHDModel.fit_vq_code_book.  In place -- the optimizer keeps working on
     the same tensor; deterministic and without a collective: call it on every rank with the same batches.  Returns the report
-    dict (distortion, dead, reseeded, counts)."""
+    dict (distortion, dead, reseeded, counts); with opt.vq_stages > 1 the list of per-stage reports."""
     self.eval()
     return self.model.fit_vq_code_book(x_dicts, n_iter=n_iter, init=init, seed=seed, reseed=reseed)
 

@@ -243,6 +243,11 @@ class VqResFwdArgs(ctypes.Structure):
              [('ws_bytes', ctypes.c_size_t), ('stream', ctypes.c_void_p)]
 
 
+class VqResRowsFwdArgs(ctypes.Structure):
+  _fields_ = [(n, ctypes.c_int32) for n in ('dtype', 'M', 'D', 'L', 'S', 'n_stages')] + \
+             [(n, ctypes.c_void_p) for n in ('x', 'books', 'y', 'index', 'stream')]
+
+
 class VqResDecodeArgs(ctypes.Structure):
   _fields_ = [(n, ctypes.c_int32) for n in ('dtype', 'M', 'D', 'L', 'S', 'n_stages')] + \
              [(n, ctypes.c_void_p) for n in ('index', 'books', 'y', 'status', 'stream')]
@@ -395,6 +400,7 @@ SIGNATURES = {
     'jpdse_vq_quantize_bwd_grouped': (_I32, [ctypes.POINTER(VqQuantizeBwdGroupedArgs)]),
     'jpdse_vq_res_workspace_size': (_SZ, [_I32, _I32, _I32, _I32]),
     'jpdse_vq_res_fwd': (_I32, [ctypes.POINTER(VqResFwdArgs)]),
+    'jpdse_vq_res_rows_fwd': (_I32, [ctypes.POINTER(VqResRowsFwdArgs)]),
     'jpdse_vq_res_decode': (_I32, [ctypes.POINTER(VqResDecodeArgs)]),
     'jpdse_vq_res_bwd': (_I32, [ctypes.POINTER(VqResBwdArgs)]),
 }

@@ -437,6 +437,111 @@ class HipVQBottleneck(nn.Module):
     return self.conv.bwd(c_conv, Act(dh.view(h.t.shape), h.C), need_dx, need_dw)
 
 
+class HipResidualVQBottleneck(nn.Module):
+  """The residual (multi-stage) quantizer as the encoder's bottleneck: HipVQBottleneck's sibling with S code
+  books.  A 1x1 conv (`conv`: `<prefix>.conv.weight`) and a ResidualS2HVQ (`vq`: `<prefix>.vq._code_books` [S, n_center,
+  center_size]) on the same [M][D] view of the conv's NHWC output, under the same geometry check.
+
+  Forward: always the hard form, over the first `stages` books (ops.vq_res_rows_fwd); backward: the soft form's gradient at
+  every stage (ops.vq_res_bwd), books beyond `stages` getting zeros.  The soft forward, the rate term, the entropy-constrained
+  assignment and the usage / cost walks are built for one stage only and are not methods of this layer.
+  Books: stage s is (2 * torch.rand(n_center, center_size) - 1) * 0.5 ** s from a CPU torch.Generator seeded with seed + s --
+  the same books on every device and rank; load_state_dict replaces them."""
+
+  def __init__(self, cin, cout, n_center=64, center_size=8, n_stages=2, sigma=10.0, dtype=F32, device=None, seed=0):
+    super(HipResidualVQBottleneck, self).__init__()
+    n_center, center_size, n_stages = int(n_center), int(center_size), int(n_stages)
+    vq_bottleneck_check(cout, n_center, center_size, sigma, who='HipResidualVQBottleneck')
+    if not 1 <= n_stages <= ops.VQ_RES_MAX_STAGES:
+      raise ValueError('HipResidualVQBottleneck: %d stages, the kernels take 1 .. %d' % (n_stages, ops.VQ_RES_MAX_STAGES))
+    from ctu.quantizers.residual_s2h_vq import ResidualS2HVQ
+    books = torch.stack([(2 * torch.rand(n_center, center_size, generator=torch.Generator().manual_seed(int(seed) + s)) - 1) * 0.5 ** s
+                         for s in range(n_stages)])
+    self.conv = HipConv2d(cin, cout, 1, act=ACT_NONE, apply_bias=False, bias=False, dtype=dtype, device=device)
+    self.vq = ResidualS2HVQ(books.to(device) if device is not None else books, sigma=float(sigma))
+    self.cout, self.center_size, self.n_center, self.n_stages = cout, center_size, n_center, n_stages
+    self.hard_forward = True
+    self.grad_ready_hook = None
+    self.train_stages = None      # the owner's stage count for the next training forward (None: all); eval ignores it
+
+  @property
+  def groups(self):
+    return self.cout // self.center_size
+
+  def _books(self):
+    c = self.vq._code_books
+    assert c.dtype == torch.float32 and c.is_contiguous(), 'the code books must be contiguous fp32'
+    return c
+
+  def _cgrad_buffer(self):
+    c = self._books()
+    if c.grad is None or not c.grad.is_contiguous():
+      c.grad = torch.zeros_like(c)
+    return c.grad
+
+  def ensure_grads(self):
+    if self.vq._code_books.requires_grad:
+      self._cgrad_buffer()
+
+  def _stages(self, stages):
+    n = self.n_stages if stages is None else stages
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= self.n_stages:
+      raise ValueError('stages must be an int in 1 .. %d, got %r' % (self.n_stages, stages))
+    return n
+
+  def _quantize(self, h, n):
+    y, index = ops.vq_res_rows_fwd(h.t.view(-1, self.center_size), self._books().detach(), n)
+    return Act(y.view(h.t.shape), h.C), index
+
+  def fwd(self, x, stages=None):
+    if stages is None and self.training:
+      stages = self.train_stages
+    n = self._stages(stages)
+    h, c_conv = self.conv.fwd(x)
+    y, index = self._quantize(h, n)
+    return y, Ctx(c_conv, h, index)
+
+  def features(self, x):
+    """The 1x1 conv's output as the [M, D] matrix the quantizer sees (a view, in the layer's dtype)."""
+    h, _ = self.conv.fwd(x)
+    return h.t.view(-1, self.center_size)
+
+  def fit(self, feature_matrices, n_iter=10, init='sample', seed=0, reseed=True):
+    """Fit the books stage by stage to feature matrices as features() returns them (a list of [M, D] tensors, concatenated):
+    ResidualS2HVQ.fit with code_len 1, in place.  Returns the list of per-stage reports."""
+    x = feature_matrices if torch.is_tensor(feature_matrices) else torch.cat(list(feature_matrices), dim=0)
+    return self.vq.fit(x, 1, n_iter=n_iter, init=init, seed=seed, reseed=reseed)
+
+  def code(self, x, stages=None):
+    """int32 [N, stages, h * w * cout / D]: per image, the stage-major indices of every vector of x's features."""
+    n = self._stages(stages)
+    h, _ = self.conv.fwd(x)
+    _, index = self._quantize(h, n)
+    return index.view(n, h.N, -1).transpose(0, 1).contiguous()
+
+  def decode(self, index, N, h, w, dtype_code):
+    """The features Act [N, h, w, cout] of an index tensor int32 [N, S', per-image indices], 1 <= S' <= S, as code() returns it
+    or a stage prefix of it (ops.vq_res_decode: bit for bit the forward over S' stages) and the decoder's status word."""
+    from .ops import tdtype_of
+    assert index.dim() == 3 and int(index.shape[0]) == N and 1 <= int(index.shape[1]) <= self.n_stages, tuple(index.shape)
+    planes = index.transpose(0, 1).contiguous().view(int(index.shape[1]), -1)
+    y, status = ops.vq_res_decode(planes, self._books().detach(), dtype=tdtype_of(dtype_code))
+    return Act(y.view(N, h, w, self.cout), self.cout), status
+
+  def bwd(self, ctx, dy, need_dx=True, need_dw=True):
+    """dy: the gradient w.r.t. the quantized features.  Straight-through: the soft form's gradient at every stage of the forward
+    (DESIGN.md 4.23), zeros for the books it did not use, then the 1x1 conv's data / weight gradients."""
+    c_conv, h, index = ctx.items
+    D = self.center_size
+    books = self._books()
+    want_dc = need_dw and books.requires_grad
+    dh, _ = ops.vq_res_bwd(dy.t.view(-1, D), h.t.view(-1, D), books.detach(), index, self.vq.sigma, want_dx=True,
+                           want_dc=want_dc, dc_out=self._cgrad_buffer() if want_dc else None)
+    if want_dc and self.grad_ready_hook is not None:
+      self.grad_ready_hook(self)
+    return self.conv.bwd(c_conv, Act(dh.view(h.t.shape), h.C), need_dx, need_dw)
+
+
 class PackBatcher(object):
   """Re-packs the data-gradient panels of all conv layers of one network in ONE launch right after its
   optimizer step (jpdse_conv_pack_run); layers it cannot cover keep their lazy per-layer pack."""

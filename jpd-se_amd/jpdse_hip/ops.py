@@ -12,7 +12,7 @@ import torch
 from . import (lib, check, JpdseError, F32, BF16, ConvDesc, PackEntry, InormDesc, EvalMetricsSemArgs, MsssimLossArgs, CodeRateArgs, SemLossArgs, CodeCostArgs, ACT_NONE, PAD_ZERO, PAD_REFLECT)
 from . import (VqSoftFwdArgs, VqHardFwdArgs, VqSoftBwdArgs, VqDecodeArgs, VqDecodeBwdArgs, VqArgmaxArgs, VqPmfArgs, VqPmfBwdArgs,
                VqQuantizeFwdArgs, VqQuantizeBwdArgs, VqRateFwdArgs, VqQuantizeBwdGroupedArgs, VqLloydAccumArgs, VqLloydUpdateArgs,
-               VqEcAssignArgs, VqEcLengthsArgs, VqResFwdArgs, VqResDecodeArgs, VqResBwdArgs)
+               VqEcAssignArgs, VqEcLengthsArgs, VqResFwdArgs, VqResRowsFwdArgs, VqResDecodeArgs, VqResBwdArgs)
 from . import VQ_RES_MAX_STAGES as _VQ_RES_MAX_STAGES
 
 
@@ -1212,6 +1212,22 @@ def vq_res_fwd(x, books, n_stages=None, want_sse=False, want_residual=False):
                       torch.cuda.current_stream().cuda_stream)
   check(lib().jpdse_vq_res_fwd(ctypes.byref(args)), 'vq_res_fwd')
   return y, index, sse, residual
+
+
+def vq_res_rows_fwd(x, books, n_stages=None):
+  """(y, index) of vq_res_fwd, bit for bit, from the thread-per-vector kernel with the residual in registers
+  (jpdse_vq_res_rows_fwd): no sse, no residual, no workspace.  n_stages in 1 .. S (default: all)."""
+  assert x.dim() == 2 and x.is_contiguous(), tuple(x.shape)
+  M, D = int(x.shape[0]), int(x.shape[1])
+  S, L, _ = _vq_res_dims(books, D)
+  assert books.device == x.device
+  n = _vq_res_stages(n_stages, S, 1)
+  y = torch.empty_like(x)
+  index = torch.empty((n, M), dtype=torch.int32, device=x.device)
+  args = VqResRowsFwdArgs(code_of(x.dtype), M, D, L, S, n, x.data_ptr(), books.data_ptr(), y.data_ptr(), index.data_ptr(),
+                          torch.cuda.current_stream().cuda_stream)
+  check(lib().jpdse_vq_res_rows_fwd(ctypes.byref(args)), 'vq_res_rows_fwd')
+  return y, index
 
 
 def vq_res_decode(index, books, n_stages=None, dtype=torch.float32, status=None):

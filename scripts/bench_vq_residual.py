@@ -1,7 +1,8 @@
-"""Times the residual quantizer's fused kernels (vq_residual.hip, DESIGN.md 4.23) for S = 2 and S = 4 stages, x in fp32 and bf16,
+"""Times the residual quantizer's fused kernels (vq_residual.hip, DESIGN.md 4.23, 4.24) for S = 2 and S = 4 stages, x in fp32 and bf16,
 on the two shapes of the other VQ benches (M, D, L): 1048576 x 8 against 64 centres and 262144 x 32 against 512.  Arms, interleaved
 round by round in one process on the same random data:
-  fwd            ops.vq_res_fwd: index [S, M] and y in one read of x
+  fwd            ops.vq_res_fwd: index [S, M] and y in one read of x (the group layout, the residual in LDS)
+  fwd_rows       ops.vq_res_rows_fwd: the same bits from one thread per vector, the residual in registers
   fwd_composed   the yardstick: S rounds of ops.vq_quantize_fwd(hard) on a torch-subtracted residual (x widened to fp32 once), the
                  centres summed by torch -- the same indices, S score loops, S - 1 more reads and writes of [M, D] and the launches
   bwd            ops.vq_res_bwd: dx and dbooks
@@ -85,11 +86,14 @@ def main():
 
         yc, kc = fwd_composed()                      # the two ways agree before they are timed
         assert torch.equal(kc, index) and torch.equal(yc, y)
+        yr, kr = ops.vq_res_rows_fwd(x, books)
+        assert torch.equal(kr, index) and torch.equal(yr, y)
         dx, dc = ops.vq_res_bwd(dy, x, books, index, sigma)
         dxc, dcc = bwd_composed()
         assert float((dx.float() - dxc.float()).abs().max()) <= 2e-2 * float(dxc.float().abs().max())
         assert float((dc - dcc).abs().max()) <= 1e-3 * float(dcc.abs().max())
-        arms = {'fwd': lambda: ops.vq_res_fwd(x, books), 'fwd_composed': fwd_composed,
+        arms = {'fwd': lambda: ops.vq_res_fwd(x, books), 'fwd_rows': lambda: ops.vq_res_rows_fwd(x, books),
+                'fwd_composed': fwd_composed,
                 'bwd': lambda: ops.vq_res_bwd(dy, x, books, index, sigma), 'bwd_composed': bwd_composed,
                 'copy': lambda: ops.copy_(src, dst)}
         times = {k: [] for k in arms}

@@ -125,6 +125,18 @@ def rate_lambda_rows(trainer, args, lambdas):
     print('%10g %10.5f %10.4f %10.3f %10.5f' % (lam, bpp / n, l1 / n, psnr / n, ms / n))
 
 
+def stage_curve_rows(trainer, args):
+  """One row per stage prefix of the residual bottleneck's stream: trainer.get_stage_curve, batch means."""
+  rows, n = None, 0
+  for x_dict in batches(args):
+    curve = trainer.get_stage_curve(x_dict)
+    rows = curve if rows is None else [{k: a[k] + b[k] for k in a} for a, b in zip(rows, curve)]
+    n += 1
+  print('%10s %10s %10s %10s %10s' % ('stages', 'coded bpp', 'L1', 'PSNR', 'MS-SSIM'))
+  for r in rows:
+    print('%10d %10.5f %10.4f %10.3f %10.5f' % (r['stages'] // n, r['bpp'] / n, r['l1'] / n, r['psnr'] / n, r['ms_ssim'] / n))
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--batches', type=int, default=4)
@@ -147,6 +159,10 @@ def main():
                   help='with --codec --encoder_quantizer s2hvq: the rate-distortion curve of ONE model (DESIGN.md 4.22).  Prints one '
                        'row per multiplier -- the coded bpp of the files trainer.get_coded_ec writes and L1 / PSNR / MS-SSIM of '
                        'what a receiver decodes from that code -- and nothing else')
+  ap.add_argument('--vq-stages', type=int, default=1,
+                  help='with --codec --encoder_quantizer s2hvq: code books of the residual bottleneck (opt.vq_stages, DESIGN.md 4.24).  '
+                       'More than 1 prints the rate-distortion points of ONE stream cut after every stage (trainer.get_stage_curve)')
+  ap.add_argument('--vq-train-stages', default='all', choices=['all', 'uniform'], help='opt.vq_train_stages (DESIGN.md 4.24)')
   ap.add_argument('--vq-rate-iters', type=int, default=2, help='rounds of the entropy-constrained assignment per image')
   ap.add_argument('--checkpoints_dir', default=None, help='load net_G.pth (and net_E.pth) from here')
   ap.add_argument('--data', default=None, help='directory of pre-decoded *.pt batches instead of synthetic ones')
@@ -184,6 +200,8 @@ def main():
       lambdas = [float(v) for v in args.vq_rate_lambda.split(',')]
     except ValueError:
       ap.error('--vq-rate-lambda takes numbers separated by commas, e.g. 0,0.5,2,8')
+  if args.vq_stages != 1 and not vq:
+    ap.error('--vq-stages needs --codec --encoder_quantizer s2hvq')
   if vq and args.roundtrip:
     ap.error('--roundtrip stores the binarizer\'s code: not available with --encoder_quantizer s2hvq '
              '(trainer.get_coded / decode_coded are its files)')
@@ -206,11 +224,15 @@ def main():
   if args.checkpoints_dir:
     kw.update(is_train=False, load_model=True, checkpoints_dir=args.checkpoints_dir)
   opt = default_opt(**kw)
+  if vq:      # fields without a training flag: set on the namespace
+    opt.vq_stages, opt.vq_train_stages = args.vq_stages, args.vq_train_stages
   torch.manual_seed(1234)
   with contextlib.redirect_stdout(sys.stderr):
     trainer = get_trainer(opt)(opt, 'test' if args.checkpoints_dir else 'train')
   if lambdas is not None:
     return rate_lambda_rows(trainer, args, lambdas)
+  if vq and args.vq_stages > 1:
+    return stage_curve_rows(trainer, args)
   keys = ('l1', 'mse', 'ms_ssim', 'psnr')
   by_batch = dict.fromkeys(keys + ('shannon', 'actual', 'context', 'file', 'coded', 'semantics', 'total', 'weighted', 'model'), 0.0)
   by_image = dict.fromkeys(keys + ('shannon', 'actual', 'context', 'file', 'coded', 'semantics', 'total', 'weighted', 'model'), 0.0)
