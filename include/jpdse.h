@@ -1224,6 +1224,35 @@ typedef struct jpdse_vq_res_bwd_args {
 } jpdse_vq_res_bwd_args;
 int jpdse_vq_res_bwd(const jpdse_vq_res_bwd_args* args);
 
+/* res_ec_assign (vq_res_ec.hip): the entropy-constrained code of the first n_stages stages, one thread per
+ * vector as res_rows_fwd.  G groups, g(m) = m % G, G | M.  bias fp32 [n_stages][G][L], or NULL for all zero; per stage
+ *   index[s][m] = arg-min_k d(r_s, C_s[k]) + bias[s][g(m)][k], d the score of res_rows_fwd, the bias one fp32 add after the score
+ *                 loop; strict <: the lowest k on equal cost, a +inf cost never replaces anything, a row of +inf alone gives 0
+ *   r_{s+1}, y    as above.  y may be NULL (the rounds before the last): then no sum is formed.
+ *   hist          int32 [n_stages][G][L]: hist[s][g][k] = the vectors of group g with index[s] == k (exact)
+ *   sse           fp64 [n_stages][G]: the sum over group g of the chosen d(r_s, C_s[index[s][m]]) WITHOUT the bias, each widened
+ *                 to fp64: the squared error of the stage prefix 1 .. s.  hist and sse are both given or both NULL.
+ * A NULL bias gives res_rows_fwd's index and y bit for bit.  No atomics: every block sums into a table of its own, the tables are
+ * merged in block order; grid and owners depend on (M, D, L, G, n_stages) alone: two calls give identical bits.  ws, with hist and
+ * sse: jpdse_vq_res_ec_workspace_size(M, D, L, G, n_stages) bytes, 8-byte aligned (host only; 0 outside the limits).
+ * JPDSE_EINVAL before any launch: res_rows_fwd's limits (n_stages 1 .. S), G >= 1, M % G == 0, G * L <= 65536, n_stages * G * L <=
+ * 65536, NULL args, x, books or index, one of hist and sse without the other, a workspace missing, too small or misaligned. */
+size_t jpdse_vq_res_ec_workspace_size(int32_t M, int32_t D, int32_t L, int32_t G, int32_t n_stages);
+typedef struct jpdse_vq_res_ec_assign_args {
+  int32_t dtype, M, D, L, S, n_stages, G;
+  const void* x;
+  const float* books;
+  const float* bias;       /* [n_stages][G][L], or NULL */
+  void* y;                 /* [M][D] in `dtype`, or NULL */
+  int32_t* index;          /* [n_stages][M] */
+  int32_t* hist;           /* [n_stages][G][L], or NULL */
+  double* sse;             /* [n_stages][G], or NULL */
+  void* ws;
+  size_t ws_bytes;
+  void* stream;
+} jpdse_vq_res_ec_assign_args;
+int jpdse_vq_res_ec_assign(const jpdse_vq_res_ec_assign_args* args);
+
 /* ---- optimizer ---------------------------------------------------------------------- */
 /* torch.optim.Adam (model.py:275,279) over a table of tensors, one launch.  `table` is a
  * device array of jpdse_adam_entry; bias corrections are computed from `step` (1-based). */

@@ -267,8 +267,9 @@ class VQIndexCodec(_Codec):
 class VQStagesCodec(VQIndexCodec):
   """The residual bottleneck's code (vq_stages > 1): int64 [N, S', indices per stage], 1 <= S' <= S, coded as one
   .jpdr blob per image (ctu.utils.vqstages) that can be cut after any stage: a code or a blob of fewer stages
-  than the model's is legal everywhere on the receiver's side.  The rate term, the entropy-constrained assignment, the context
-  coder and the cost walks are built for one stage and refused here.  The model picks this class; CODECS stays by quantizer."""
+  than the model's is legal everywhere on the receiver's side.  The rate term, the one-stage entropy-constrained assignment, the
+  context coder and the cost walks are built for one stage and refused here; the multi-stage entropy-constrained code (DESIGN.md
+  4.25) is code_ec, under calls of its own.  The model picks this class; CODECS stays by quantizer."""
 
   def _n_stages(self):
     return self.netE.vq_stages
@@ -320,6 +321,13 @@ class VQStagesCodec(VQIndexCodec):
   def code(self, src, rate_lambda=0.0, n_iter=2, stages=None):
     self.ec_reports = None
     return self.netE.vq_code(src, stages).to(torch.int64)
+
+  def code_ec(self, src, rate_lambda, n_iter=2, stages=None):
+    """The entropy-constrained code of the first `stages` stages: the encoder's first half once, then
+    ResidualS2HVQ.encode_ec per image with groups = C / D; int64 [N, stages, indices], the per-image reports in `ec_reports`.
+    rate_lambda == 0 runs the same rounds with a zero bias: code()'s indices."""
+    index, self.ec_reports = self.netE.vq_stage_code_ec(src, float(rate_lambda), n_iter, stages)
+    return index.to(torch.int64)
 
   def features_of_payloads(self, blobs, geo, device, who):
     code_len = geo[3]

@@ -5,7 +5,7 @@ import torch
 
 from jpdse_hip import F32, ops
 from ctu.utils import semantics as semantics_file
-from ctu.models.codec import VQIndexCodec, VQStagesCodec
+from ctu.models.codec import VQIndexCodec, VQStagesCodec, check_ec_arguments
 
 
 class CodedCalls(object):
@@ -234,6 +234,65 @@ class CodedCalls(object):
     self._check_stages(codec, stages, 'get_coded_stages')
     with torch.no_grad():
       return codec.payloads(self._eval_code(codec, x_dict, stages=stages), x_dict)
+
+  # ---- the entropy-constrained code of the residual bottleneck (extension) ------------------------------------
+  def _stages_codec(self, who, instead):
+    """The residual bottleneck's codec, or the refusal that names the one-stage call to use.  Host only."""
+    codec = self._vq_codec(who)
+    if not isinstance(codec, VQStagesCodec):
+      raise ValueError('%s: a call of the residual bottleneck, this model has vq_stages = 1: use %s' % (who, instead))
+    return codec
+
+  def _stage_code_ec(self, who, instead, x_dict, rate_lambda, n_iter, stages):
+    """(codec, code): the checks of the three calls below, every one before device work, then the code."""
+    codec = self._stages_codec(who, instead)
+    lam = check_ec_arguments(rate_lambda, n_iter)
+    codec.check_stages(stages, who)
+    with torch.no_grad():
+      pre = self.preprocess(x_dict, build_base=False)
+      return codec, self._encoder_eval(lambda: codec.code_ec(pre['src'], lam, n_iter, stages))
+
+  def get_stage_code_ec(self, x_dict, rate_lambda, n_iter=2, stages=None):
+    """The entropy-constrained code of a residual bottleneck (vq_stages > 1): int64 [N, stages, h * w * C / D],
+    the first `stages` (default: all) stages.  Stage s of every vector minimises |r_s - C_s[k]|^2 + rate_lambda * the code length
+    of k under the histogram of its image, stage and channel group; n_iter rounds of ResidualS2HVQ.encode_ec per image.  An
+    ordinary code: decode takes it unchanged, and code[:, :n'] is get_stage_code_ec(.., stages=n').  rate_lambda == 0 gives
+    get_vq_code's indices.  ValueError before any device work: a one-stage model (use get_vq_code(rate_lambda=)), a rate_lambda
+    that is negative or not finite, an n_iter that is no int >= 0, stages outside 1 .. vq_stages."""
+    return self._stage_code_ec('get_stage_code_ec', 'get_vq_code(rate_lambda=)', x_dict, rate_lambda, n_iter, stages)[1]
+
+  def get_coded_stages_ec(self, x_dict, rate_lambda, n_iter=2, stages=None):
+    """get_coded_stages at another point of the rate-distortion curve: one .jpdr blob per image of get_stage_code_ec(x_dict,
+    rate_lambda, n_iter, stages).  decode_coded and vqstages.truncate_stages take them unchanged; a blob cut after stage n' is
+    what get_coded_stages_ec(.., stages=n') writes."""
+    codec, code = self._stage_code_ec('get_coded_stages_ec', 'get_coded_ec', x_dict, rate_lambda, n_iter, stages)
+    return codec.payloads(code, x_dict)
+
+  def get_stage_ec_report(self, x_dict, rate_lambda, n_iter=2, stages=None):
+    """The per-image reports of get_stage_code_ec(x_dict, rate_lambda, n_iter, stages): a list of N dicts -- distortion and
+    bits: n_iter + 1 rows of one Python float per stage; cost: n_iter + 1 floats (ResidualS2HVQ.encode_ec)."""
+    codec, _ = self._stage_code_ec('get_stage_ec_report', 'get_vq_ec_report', x_dict, rate_lambda, n_iter, stages)
+    return codec.ec_reports
+
+  def get_stage_usage(self, x_dict):
+    """int64 [S, G, L] on the device: how often stage s of the eval-mode code get_vq_code(x_dict) uses each of the L centres, per
+    channel group (G = C / D), counted over the batch.  A column of zeros is a dead centre of that stage.  Every row sums to
+    the indices per group, N h w."""
+    self._stages_codec('get_stage_usage', 'get_vq_usage')
+    with torch.no_grad():
+      src = self.preprocess(x_dict, build_base=False)['src']
+      return self._encoder_eval(lambda: self.netE.vq_stage_usage(src))
+
+  def get_stage_rates(self, x_dict):
+    """A list of S Python floats: entry s the zero-order entropy of stage s of get_vq_code(x_dict) per channel group, histograms
+    over the batch (get_stage_usage), in bits per pixel of the batch -- what get_vq_rate is for one stage.  An estimate next
+    to get_stage_curve's file sizes, not a size."""
+    self._stages_codec('get_stage_rates', 'get_vq_rate')
+    hist = self.get_stage_usage(x_dict).cpu().to(torch.float64)
+    n = hist.sum(dim=2, keepdim=True)
+    terms = torch.where(hist > 0, hist * (torch.log2(n) - torch.log2(hist.clamp(min=1.0))), torch.zeros_like(hist))
+    pixels = int(x_dict['image'].shape[0]) * self._pixels(x_dict)
+    return [float(v) / pixels for v in terms.sum(dim=(1, 2)).tolist()]
 
   def get_coded_ec(self, x_dict, rate_lambda=0.0, n_iter=2):
     """get_coded at another point of the rate-distortion curve: the blobs of get_vq_code(x_dict, rate_lambda,

@@ -356,6 +356,26 @@ class Encoder(nn.Module):
     h, _ = run_chain_fwd(self._pre, x)
     return vq.code_ec(h, lam, n_iter)
 
+  def _require_stages(self, who):
+    vq = self._require_vq()
+    if self.vq_stages == 1:
+      raise ValueError('Encoder.%s: a call of the residual bottleneck, this one has one stage (vq_stages = 1)' % who)
+    return vq
+
+  def vq_stage_code_ec(self, x, lam, n_iter=2, stages=None):
+    """(index, reports): vq_code of a residual bottleneck under the entropy constraint: int32 [N, stages, h * w
+    * cout / D] and the per-image reports of ResidualS2HVQ.encode_ec.  The first half runs once."""
+    vq = self._require_stages('vq_stage_code_ec')
+    vq._stages(stages)                     # before any device work
+    h, _ = run_chain_fwd(self._pre, x)
+    return vq.code_ec(h, lam, n_iter, stages)
+
+  def vq_stage_usage(self, x):
+    """int64 [vq_stages, cout / D, n_center]: the histogram of every stage of vq_code(x) per channel group over the batch."""
+    vq = self._require_stages('vq_stage_usage')
+    h, _ = run_chain_fwd(self._pre, x)
+    return vq.usage(h)
+
   def vq_features(self, x):
     """The [M, D] matrix the bottleneck's quantizer sees for x (M = N h w cout / D, vector m = pixel * (cout / D) + group): what
     vq_code assigns and what the code-book fit of DESIGN.md 4.21 runs on."""

@@ -14,7 +14,7 @@ import torch
 import torch.nn as nn
 
 from jpdse_hip import ops
-from .s2h_vq import S2HVQ, MAX_CENTER_SIZE, MAX_N_CENTER, _on_gpu, _rows_limit
+from .s2h_vq import S2HVQ, MAX_CENTER_SIZE, MAX_N_CENTER, _on_gpu, _rows_limit, _ec_lambda, _ec_iterations
 
 __all__ = ['ResidualS2HVQ']
 
@@ -130,6 +130,64 @@ class ResidualS2HVQ(nn.Module):
       xm = self._vectors(x, code_len).detach()
       _, index = ops.vq_res_rows_fwd(xm, self._code_books.detach().contiguous(), n_st)
     return index.to(torch.int64).view(n_st, x.size(0), code_len)
+
+  def _ec_groups(self, who, x, code_len, groups, n_st):
+    """groups as an int after S2HVQ.encode_ec's checks, and the table limit n * groups * n_center <= 65536 of DESIGN.md 4.25."""
+    M, groups, L = x.size(0) * code_len, int(groups), int(self._code_books.size(1))
+    if groups < 1 or M % groups != 0:
+      raise ValueError('groups must divide n * code_len, got {} and {}'.format(groups, M))
+    if n_st * groups * L > 65536:
+      raise NotImplementedError('ResidualS2HVQ.%s: stages * groups * n_center = %d, the kernels take at most 65536'
+                                % (who, n_st * groups * L))
+    return groups
+
+  def encode_ec(self, x, code_len, lam, groups=1, n_iter=2, stages=None):
+    """Entropy-constrained encoding of the first `stages` (default: all) stages: S2HVQ.encode_ec's rounds with
+    every stage assigned in one kernel (ops.vq_res_ec_assign).  Stage s of vector m takes the centre that minimises |r_s - C_s[k]|^2
+    + lam * len[s][g][k], g = m % groups, len[s][g][k] = log2(n_g / hist[s][g][k]) the code length of centre k under the histogram
+    of group g's own stage-s code, and hands r_s minus that centre to stage s + 1.  Round 0 assigns with no bias (the plain code,
+    encode(x, code_len, stages)); round t = 1 .. n_iter takes the lengths of every (stage, group) plane from the histograms of
+    round t - 1 (ops.vq_ec_lengths) and assigns all stages again.  The decoder is untouched: the result is an ordinary code, and
+    its first n' stages are encode_ec(.., stages=n')'s.
+    Returns (code int64 [stages, n, code_len], report): report['distortion'][t][s] the summed squared error after stage s of round
+    t, report['bits'][t][s] the ideal length of stage s's code under its own per-group histograms, report['cost'][t] =
+    distortion[t][-1] + lam * sum(bits[t]); n_iter + 1 rows each, read back once, at the end.  Only stage 1 has ECVQ's guarantee
+    (its own cost does not rise over the rounds, up to the fp32 rounding of the scores): a later stage sees another residual every
+    round, and nothing monotone holds for it or for the total.  lam == 0 or n_iter == 0: the plain code, index for index.  Runs
+    under no_grad: nothing is differentiable."""
+    lam = _ec_lambda(lam)
+    n_iter = _ec_iterations(n_iter)
+    n_st = self._stages(stages)
+    self._vector_checks(x, code_len)
+    groups = self._ec_groups('encode_ec', x, code_len, groups, n_st)
+    L = int(self._code_books.size(1))
+    with torch.no_grad():
+      xm = self._vectors(x, code_len).detach()
+      books = self._code_books.detach().contiguous()
+      _, index, hist, sse = ops.vq_res_ec_assign(xm, books, None, groups, n_st, want_y=False)
+      dist, bits = [sse.sum(1)], []
+      for _ in range(n_iter):
+        bias, b = ops.vq_ec_lengths(hist.view(n_st * groups, L), lam)
+        bits.append(b.view(n_st, groups).sum(1))
+        _, index, hist, sse = ops.vq_res_ec_assign(xm, books, bias.view(n_st, groups, L), groups, n_st, want_y=False)
+        dist.append(sse.sum(1))
+      bits.append(ops.vq_ec_lengths(hist.view(n_st * groups, L), lam)[1].view(n_st, groups).sum(1))
+      back = torch.stack(dist + bits).cpu().tolist()
+    dist = [[float(v) for v in row] for row in back[:n_iter + 1]]
+    bits = [[float(v) for v in row] for row in back[n_iter + 1:]]
+    report = dict(distortion=dist, bits=bits, cost=[d[-1] + lam * sum(b) for d, b in zip(dist, bits)])
+    return index.to(torch.int64).view(n_st, x.size(0), code_len), report
+
+  def usage(self, x, code_len, groups=1, stages=None):
+    """int64 [stages, groups, n_center] on the device: how often the plain code of x (encode) uses every centre of every stage, per
+    group m % groups -- one round of ops.vq_res_ec_assign without a bias.  A zero column is a dead centre of that stage."""
+    n_st = self._stages(stages)
+    self._vector_checks(x, code_len)
+    groups = self._ec_groups('usage', x, code_len, groups, n_st)
+    with torch.no_grad():
+      xm = self._vectors(x, code_len).detach()
+      _, _, hist, _ = ops.vq_res_ec_assign(xm, self._code_books.detach().contiguous(), None, groups, n_st, want_y=False)
+    return hist.to(torch.int64)
 
   def decode(self, code, stages=None):
     """code int64 [S', n, code_len] -> float32 [n, code_len * center_size]: the sum of the centres of the first `stages` (default:

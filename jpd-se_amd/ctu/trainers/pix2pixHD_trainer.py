@@ -150,14 +150,19 @@ class Pix2PixHDTrainer(BaseTrainer):
     self.eval()
     return self.model.get_coded_stages(x_dict, stages=stages)
 
-  def get_stage_curve(self, x_dict):
+  def get_stage_curve(self, x_dict, rate_lambda=0.0, n_iter=2):
     """The rate-distortion points of one coded stream cut after every stage (opt.vq_stages > 1): a list of
     vq_stages dicts, one per prefix n = 1 .. vq_stages: `stages`, `bpp` (8 * the bytes of vqstages.truncate_stages(blob, n) per
     pixel, batch mean) and `l1`, `mse`, `psnr`, `ms_ssim` of get_eval_metrics_decoded of that prefix.  One encoder run, one
-    generator run per prefix."""
+    generator run per prefix.  rate_lambda > 0: the curve of the stream get_coded_stages_ec(x_dict, rate_lambda,
+    n_iter) writes; the defaults take the plain code."""
     from ctu.utils import vqstages
+    from ctu.models.codec import check_ec_arguments
     self.eval()
-    code = self.model.get_vq_code(x_dict)
+    if check_ec_arguments(rate_lambda, n_iter) > 0:
+      code = self.model.get_stage_code_ec(x_dict, rate_lambda, n_iter=n_iter)
+    else:
+      code = self.model.get_vq_code(x_dict)
     if code.dim() != 3:
       raise ValueError('get_stage_curve: needs a residual bottleneck (opt.vq_stages > 1)')
     blobs = self.model.codec.payloads(code, x_dict)
@@ -168,6 +173,34 @@ class Pix2PixHDTrainer(BaseTrainer):
       bpp = sum(8.0 * len(vqstages.truncate_stages(b, n)) / pixels for b in blobs) / len(blobs)
       rows.append(dict(stages=n, bpp=bpp, l1=m['l1'], mse=m['mse'], psnr=m['psnr'], ms_ssim=m['ms_ssim']))
     return rows
+
+  def get_stage_code_ec(self, x_dict, rate_lambda, n_iter=2, stages=None):
+    """The entropy-constrained code of a residual bottleneck (opt.vq_stages > 1): int64 [N, stages, h * w * C /
+    D]; decode takes it unchanged and every stage prefix is the shorter encoder's code."""
+    self.eval()
+    return self.model.get_stage_code_ec(x_dict, rate_lambda, n_iter=n_iter, stages=stages)
+
+  def get_coded_stages_ec(self, x_dict, rate_lambda, n_iter=2, stages=None):
+    """The .jpdr blobs of get_stage_code_ec: decode_coded and vqstages.truncate_stages take them unchanged."""
+    self.eval()
+    return self.model.get_coded_stages_ec(x_dict, rate_lambda, n_iter=n_iter, stages=stages)
+
+  def get_stage_ec_report(self, x_dict, rate_lambda, n_iter=2, stages=None):
+    """The per-image reports (distortion and bits per round and stage, cost per round) of get_stage_code_ec."""
+    self.eval()
+    return self.model.get_stage_ec_report(x_dict, rate_lambda, n_iter=n_iter, stages=stages)
+
+  def get_stage_usage(self, x_dict):
+    """int64 [S, G, L] on the device: how often every stage of the eval-mode code uses each centre, per channel group, over the
+    batch.  A zero column is a dead centre of that stage."""
+    self.eval()
+    return self.model.get_stage_usage(x_dict)
+
+  def get_stage_rates(self, x_dict):
+    """A list of S floats: the zero-order entropy of every stage's code per channel group in bits per pixel of the batch
+    (DESIGN.md 4.25).  An estimate next to get_stage_curve's file sizes."""
+    self.eval()
+    return self.model.get_stage_rates(x_dict)
 
   def get_vq_ec_report(self, x_dict, rate_lambda, n_iter=2):
     """The per-image reports (distortion, bits, cost per round) of the entropy-constrained code."""

@@ -248,6 +248,12 @@ class VqResRowsFwdArgs(ctypes.Structure):
              [(n, ctypes.c_void_p) for n in ('x', 'books', 'y', 'index', 'stream')]
 
 
+class VqResEcAssignArgs(ctypes.Structure):
+  _fields_ = [(n, ctypes.c_int32) for n in ('dtype', 'M', 'D', 'L', 'S', 'n_stages', 'G')] + \
+             [(n, ctypes.c_void_p) for n in ('x', 'books', 'bias', 'y', 'index', 'hist', 'sse', 'ws')] + \
+             [('ws_bytes', ctypes.c_size_t), ('stream', ctypes.c_void_p)]
+
+
 class VqResDecodeArgs(ctypes.Structure):
   _fields_ = [(n, ctypes.c_int32) for n in ('dtype', 'M', 'D', 'L', 'S', 'n_stages')] + \
              [(n, ctypes.c_void_p) for n in ('index', 'books', 'y', 'status', 'stream')]
@@ -403,6 +409,8 @@ SIGNATURES = {
     'jpdse_vq_res_rows_fwd': (_I32, [ctypes.POINTER(VqResRowsFwdArgs)]),
     'jpdse_vq_res_decode': (_I32, [ctypes.POINTER(VqResDecodeArgs)]),
     'jpdse_vq_res_bwd': (_I32, [ctypes.POINTER(VqResBwdArgs)]),
+    'jpdse_vq_res_ec_workspace_size': (_SZ, [_I32, _I32, _I32, _I32, _I32]),
+    'jpdse_vq_res_ec_assign': (_I32, [ctypes.POINTER(VqResEcAssignArgs)]),
 }
 
 # the developer build (same sources, -DJPDSE_DEV): the shipped ABI plus include/jpdse_dev.h

@@ -443,8 +443,9 @@ class HipResidualVQBottleneck(nn.Module):
   center_size]) on the same [M][D] view of the conv's NHWC output, under the same geometry check.
 
   Forward: always the hard form, over the first `stages` books (ops.vq_res_rows_fwd); backward: the soft form's gradient at
-  every stage (ops.vq_res_bwd), books beyond `stages` getting zeros.  The soft forward, the rate term, the entropy-constrained
-  assignment and the usage / cost walks are built for one stage only and are not methods of this layer.
+  every stage (ops.vq_res_bwd), books beyond `stages` getting zeros.  The soft forward, the rate term and the cost walks are
+  built for one stage only and are not methods of this layer; the entropy-constrained code and the usage counts are the
+  multi-stage ones of DESIGN.md 4.25 (code_ec, usage).
   Books: stage s is (2 * torch.rand(n_center, center_size) - 1) * 0.5 ** s from a CPU torch.Generator seeded with seed + s --
   the same books on every device and rank; load_state_dict replaces them."""
 
@@ -518,6 +519,26 @@ class HipResidualVQBottleneck(nn.Module):
     h, _ = self.conv.fwd(x)
     _, index = self._quantize(h, n)
     return index.view(n, h.N, -1).transpose(0, 1).contiguous()
+
+  def code_ec(self, x, lam, n_iter=2, stages=None):
+    """(index, reports): code() under the entropy constraint -- ResidualS2HVQ.encode_ec PER IMAGE on that
+    image's rows of features(x), groups = the channel groups, as HipVQBottleneck.code_ec: the coders adapt per image, so the
+    histograms are per image.  index int32 [N, stages, h * w * cout / D]; reports: the N report dicts of encode_ec."""
+    n = self._stages(stages)
+    f = self.features(x)
+    N = x.N
+    rows = f.shape[0] // N
+    codes, reports = [], []
+    for i in range(N):
+      code, report = self.vq.encode_ec(f[i * rows:(i + 1) * rows], 1, lam, groups=self.groups, n_iter=n_iter, stages=n)
+      codes.append(code.view(n, rows))
+      reports.append(report)
+    return torch.stack(codes, dim=0).to(torch.int32), reports
+
+  def usage(self, x):
+    """int64 [S, groups, n_center]: how many vectors of x's features take each centre at each stage of code(x), per channel
+    group, over the batch (ResidualS2HVQ.usage)."""
+    return self.vq.usage(self.features(x), 1, groups=self.groups)
 
   def decode(self, index, N, h, w, dtype_code):
     """The features Act [N, h, w, cout] of an index tensor int32 [N, S', per-image indices], 1 <= S' <= S, as code() returns it

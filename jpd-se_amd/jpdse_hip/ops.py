@@ -12,7 +12,7 @@ import torch
 from . import (lib, check, JpdseError, F32, BF16, ConvDesc, PackEntry, InormDesc, EvalMetricsSemArgs, MsssimLossArgs, CodeRateArgs, SemLossArgs, CodeCostArgs, ACT_NONE, PAD_ZERO, PAD_REFLECT)
 from . import (VqSoftFwdArgs, VqHardFwdArgs, VqSoftBwdArgs, VqDecodeArgs, VqDecodeBwdArgs, VqArgmaxArgs, VqPmfArgs, VqPmfBwdArgs,
                VqQuantizeFwdArgs, VqQuantizeBwdArgs, VqRateFwdArgs, VqQuantizeBwdGroupedArgs, VqLloydAccumArgs, VqLloydUpdateArgs,
-               VqEcAssignArgs, VqEcLengthsArgs, VqResFwdArgs, VqResRowsFwdArgs, VqResDecodeArgs, VqResBwdArgs)
+               VqEcAssignArgs, VqEcLengthsArgs, VqResFwdArgs, VqResRowsFwdArgs, VqResDecodeArgs, VqResBwdArgs, VqResEcAssignArgs)
 from . import VQ_RES_MAX_STAGES as _VQ_RES_MAX_STAGES
 
 
@@ -1273,6 +1273,36 @@ def vq_res_bwd(dy, x, books, index, sigma, want_dx=True, want_dc=True, dc_out=No
                       ws.numel() if want_dc else 0, torch.cuda.current_stream().cuda_stream)
   check(lib().jpdse_vq_res_bwd(ctypes.byref(args)), 'vq_res_bwd')
   return dx, dc
+
+
+def vq_res_ec_assign(x, books, bias=None, groups=1, n_stages=None, want_y=True, want_stats=True):
+  """(y, index, hist, sse): the entropy-constrained code of x [M, D] (fp32 or bf16) under the first n_stages (default: all) of books
+  fp32 [S, L, D] (jpdse_vq_res_ec_assign).  Stage s takes the arg-min over k of d(r_s, books[s][k]) + bias[s][m %
+  groups][k] (lowest index on equal cost, +inf for "never", a row of +inf alone gives 0); bias fp32 [n_stages, groups, L], already
+  scaled, None for all zero: then index and y are vq_res_rows_fwd's bit for bit.  index int32 [n_stages, M]; y [M, D] in x's dtype
+  the sum of the chosen centres, None unless want_y; hist int32 [n_stages, groups, L] the exact counts per stage and group and sse
+  float64 [n_stages, groups] the summed chosen d without the bias (the squared error after that stage), None unless want_stats."""
+  assert x.dim() == 2 and x.is_contiguous(), tuple(x.shape)
+  M, D = int(x.shape[0]), int(x.shape[1])
+  S, L, _ = _vq_res_dims(books, D)
+  assert books.device == x.device
+  n = _vq_res_stages(n_stages, S, 1)
+  G = int(groups)
+  if bias is not None:
+    assert bias.dtype == torch.float32 and bias.is_contiguous() and tuple(bias.shape) == (n, G, L) and bias.device == x.device, \
+        (bias.dtype, tuple(bias.shape))
+  y = torch.empty_like(x) if want_y else None
+  index = torch.empty((n, M), dtype=torch.int32, device=x.device)
+  hist = torch.empty((n, max(G, 0), L), dtype=torch.int32, device=x.device) if want_stats else None
+  sse = torch.empty((n, max(G, 0)), dtype=torch.float64, device=x.device) if want_stats else None
+  ws = workspace(max(lib().jpdse_vq_res_ec_workspace_size(M, D, L, G, n), 1), x.device) if want_stats else None
+  args = VqResEcAssignArgs(code_of(x.dtype), M, D, L, S, n, G, x.data_ptr(), books.data_ptr(),
+                           bias.data_ptr() if bias is not None else None, y.data_ptr() if want_y else None, index.data_ptr(),
+                           hist.data_ptr() if want_stats else None, sse.data_ptr() if want_stats else None,
+                           ws.data_ptr() if want_stats else None, ws.numel() if want_stats else 0,
+                           torch.cuda.current_stream().cuda_stream)
+  check(lib().jpdse_vq_res_ec_assign(ctypes.byref(args)), 'vq_res_ec_assign')
+  return y, index, hist, sse
 
 
 # ---- the host half of the three device coders (streams.py; DESIGN.md 4.18) -----------------------------------------------------

@@ -137,6 +137,30 @@ def stage_curve_rows(trainer, args):
     print('%10d %10.5f %10.4f %10.3f %10.5f' % (r['stages'] // n, r['bpp'] / n, r['l1'] / n, r['psnr'] / n, r['ms_ssim'] / n))
 
 
+def stage_lambda_grid(trainer, args, lambdas):
+  """--vq-stages S with --vq-rate-lambda: the grid of (multiplier, stage prefix) against bpp and distortion --
+  trainer.get_stage_curve(x, rate_lambda), batch means; the rows of lambda 0 are stage_curve_rows'.  Then the centres in use
+  per stage (trainer.get_stage_usage, over all batches) and the entropy estimate of every stage (trainer.get_stage_rates)."""
+  data = list(batches(args))
+  print('%10s %10s %10s %10s %10s %10s' % ('lambda', 'stages', 'coded bpp', 'L1', 'PSNR', 'MS-SSIM'))
+  for lam in lambdas:
+    rows = None
+    for x_dict in data:
+      curve = trainer.get_stage_curve(x_dict, rate_lambda=lam, n_iter=args.vq_rate_iters)
+      rows = curve if rows is None else [{k: a[k] + b[k] for k in a} for a, b in zip(rows, curve)]
+    n = len(data)
+    for r in rows:
+      print('%10g %10d %10.5f %10.4f %10.3f %10.5f' % (lam, r['stages'] // n, r['bpp'] / n, r['l1'] / n, r['psnr'] / n,
+                                                      r['ms_ssim'] / n))
+  usage = sum(trainer.get_stage_usage(x_dict) for x_dict in data)
+  rates = [sum(v) / len(data) for v in zip(*(trainer.get_stage_rates(x_dict) for x_dict in data))]
+  print('%10s %16s %16s %14s' % ('stage', 'centres in use', 'dead in a group', 'entropy bpp'))
+  for s in range(usage.shape[0]):
+    used = int((usage[s].sum(0) > 0).sum())
+    dead = int((usage[s] == 0).sum())
+    print('%10d %10d / %-3d %16d %14.5f' % (s + 1, used, usage.shape[2], dead, rates[s]))
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--batches', type=int, default=4)
@@ -158,7 +182,8 @@ def main():
   ap.add_argument('--vq-rate-lambda', default=None, metavar='L0,L1,..',
                   help='with --codec --encoder_quantizer s2hvq: the rate-distortion curve of ONE model (DESIGN.md 4.22).  Prints one '
                        'row per multiplier -- the coded bpp of the files trainer.get_coded_ec writes and L1 / PSNR / MS-SSIM of '
-                       'what a receiver decodes from that code -- and nothing else')
+                       'what a receiver decodes from that code -- and nothing else.  With --vq-stages S > 1 (DESIGN.md 4.25): the grid '
+                       'of (multiplier, stage prefix), then the centres in use per stage')
   ap.add_argument('--vq-stages', type=int, default=1,
                   help='with --codec --encoder_quantizer s2hvq: code books of the residual bottleneck (opt.vq_stages, DESIGN.md 4.24).  '
                        'More than 1 prints the rate-distortion points of ONE stream cut after every stage (trainer.get_stage_curve)')
@@ -229,6 +254,8 @@ def main():
   torch.manual_seed(1234)
   with contextlib.redirect_stdout(sys.stderr):
     trainer = get_trainer(opt)(opt, 'test' if args.checkpoints_dir else 'train')
+  if lambdas is not None and vq and args.vq_stages > 1:
+    return stage_lambda_grid(trainer, args, lambdas)
   if lambdas is not None:
     return rate_lambda_rows(trainer, args, lambdas)
   if vq and args.vq_stages > 1:
