@@ -1253,6 +1253,56 @@ typedef struct jpdse_vq_res_ec_assign_args {
 } jpdse_vq_res_ec_assign_args;
 int jpdse_vq_res_ec_assign(const jpdse_vq_res_ec_assign_args* args);
 
+/* ---- residual vector quantizer: the rate term (vq_res_rate.hip, vq_residual.hip) ---------------------------------
+ * The rate term on per-group histograms above (4.16), for the first n_stages of S stages.  Vectors m = 0 .. M - 1, G >= 1 groups,
+ * G | M, g(m) = m % G.  The chain is the hard forward's, exactly as in res_rows_fwd: r_1 = x, k_s the arg-min of the score of r_s
+ * against C_s (the lowest index on a tie), r_{s+1} = r_s - C_s[k_s] in fp32.
+ *   p_s[m][k]      = softmax_k(-sigma |r_s[m] - C_s[k]|^2), formed as e * (1 / sum) with the row minimum subtracted, as rate_fwd
+ *   hist[s][g][k]  = sum over m with g(m) = g of p_s[m][k]
+ *   q              = hist / (M / G)
+ *   bits[s]        = - sum_g sum_k hist[s][g][k] log2 q[s][g][k], terms with hist <= 0 dropped
+ *   rates[s]       = bits[s] / denom;  rate = rates[0] + .. + rates[n_stages - 1]: the fp32 sum of the fp32 values, stage order
+ *   dhist[s][g][k] = scale (-(log2 q + 1 / ln 2)) / denom where hist > 0, else exactly 0
+ *   res_rate_fwd   one launch, one thread per vector with the residual in registers and the stage loop inside the thread, sums
+ *                  p_s (recomputed from r_s; [M][L] is never stored, x is read once) into one fp32 partial [n_stages][G][L] per
+ *                  block; a second launch of one block merges the partials in block order in fp64, forms q, bits, rates and dhist
+ *                  in fp64 and writes fp32.  rate [1] and rates [n_stages] are always written; hist and dhist may be NULL.  y and
+ *                  index: both or neither; given, they are res_rows_fwd's results bit for bit.  Order of the fp32 sums: rate_fwd's
+ *                  two paths -- G a power of two <= 64 whose per-wave tables [n_stages][G][L + 1] fit LDS (4, 2 or 1 waves per block
+ *                  within 48 KiB, else one wave within 144 KiB): xor-shuffles over the lanes of a group, offsets 32, 16, .. G, the
+ *                  waves of a block merged in wave order; any other case: m ascending inside a tile of 256, tiles in order.
+ *   res_bwd_grouped   res_bwd with dp_s[m][k] = <a_s[m], C_s[k]> + dhist[s][g(m)][k]; everything after dp as res_bwd.  dhist NULL:
+ *                  exactly res_bwd's launch; dhist all zero: res_bwd's bits.
+ * For S = 1 both calls give rate_fwd's and quantize_bwd_grouped's quantities.  No atomics; grid, tile, path and every order of
+ * summation depend on (M, D, L, G, n_stages) alone: two calls give identical bits.  ws of res_rate_fwd:
+ * jpdse_vq_res_rate_workspace_size(M, D, L, G, n_stages) bytes, at most 16 MiB (host only; 0 outside the limits); of
+ * res_bwd_grouped: res_bwd's.  JPDSE_EINVAL before any launch, outputs untouched: res_bwd's limits (n_stages 1 .. S), G < 1,
+ * M % G != 0, G * L > 65536, n_stages * G * L > 65536, sigma not finite or <= 0, scale or denom not finite, denom <= 0, NULL x,
+ * books, rate or rates, one of y and index without the other, a workspace missing or too small. */
+size_t jpdse_vq_res_rate_workspace_size(int32_t M, int32_t D, int32_t L, int32_t G, int32_t n_stages);
+typedef struct jpdse_vq_res_rate_fwd_args {
+  int32_t dtype, M, D, L, S, n_stages, G;
+  float sigma, scale, denom;
+  const void* x;           /* [M][D] in `dtype` */
+  const float* books;      /* [S][L][D] */
+  float* rate;             /* [1] */
+  float* rates;            /* [n_stages] */
+  float* hist;             /* [n_stages][G][L], or NULL */
+  float* dhist;            /* [n_stages][G][L], or NULL */
+  void* y;                 /* [M][D] in `dtype`, or NULL */
+  int32_t* index;          /* [n_stages][M], or NULL */
+  void* ws;
+  size_t ws_bytes;
+  void* stream;
+} jpdse_vq_res_rate_fwd_args;
+int jpdse_vq_res_rate_fwd(const jpdse_vq_res_rate_fwd_args* args);
+typedef struct jpdse_vq_res_bwd_grouped_args {
+  jpdse_vq_res_bwd_args bwd;
+  int32_t G;
+  const float* dhist;      /* [n_stages][G][L], or NULL */
+} jpdse_vq_res_bwd_grouped_args;
+int jpdse_vq_res_bwd_grouped(const jpdse_vq_res_bwd_grouped_args* args);
+
 /* ---- optimizer ---------------------------------------------------------------------- */
 /* torch.optim.Adam (model.py:275,279) over a table of tensors, one launch.  `table` is a
  * device array of jpdse_adam_entry; bias corrections are computed from `step` (1-based). */

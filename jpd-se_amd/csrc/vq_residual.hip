@@ -47,10 +47,11 @@ static inline int vqres_bwd_blocks(int M, int D, int L, int n) {
   cap = cap < 1 ? 1 : cap;
   return nb < cap ? nb : cap;
 }
-// LDS of the backward: cb [L][DP] when staged | with a partial: pt, ddt [KC][V + 1] | xt, dyt [V][D] | red [max(V, KC D)]
-static inline size_t vqres_bwd_lds(int D, int L, bool dc) {
+// LDS of the backward: cb [L][DP] when staged | dq [G][L + 1] with a staged dhist | with a partial: pt, ddt [KC][V + 1] | xt, dyt [V][D] | red [max(V, KC D)]
+// nq: the words of a staged slice of dhist, G (L + 1), or 0
+static inline size_t vqres_bwd_lds(int D, int L, bool dc, size_t nq = 0) {
   const int V = vqb_bwd_threads(D), KC = vqb_chunk(L);
-  size_t w = vqb_cb_lds(D, L) ? (size_t)L * vqb_dp(D) : 0;
+  size_t w = (vqb_cb_lds(D, L) ? (size_t)L * vqb_dp(D) : 0) + nq;
   if (dc) w += 2 * (size_t)KC * (V + 1) + 2 * (size_t)V * D + (size_t)(KC * D > V ? KC * D : V);
   return w * sizeof(float);
 }
@@ -229,14 +230,20 @@ __global__ __launch_bounds__(256) void vqres_decode_kernel(const int* __restrict
 
 // ---- backward ---------------------------------------------------------------------------------------------------------------
 // blockDim.x = V vectors per tile.  partial: this block's [n][L][D] sums, or nullptr: no code-book gradient.
-template <typename T, int DP, bool CBL>
+// GM: the rate term's share of dp[m][k].  0: none, dhist and G unused (jpdse_vq_res_bwd, and the grouped call without
+// a dhist); 1: dhist [n][G][L], the stage's slice staged in LDS as dq [G][L + 1] where the stage's book is restaged (the odd stride:
+// lanes of different groups on different banks) and read at the vector's group (m % G); 2: a slice too large for LDS, read from
+// global memory.
+template <typename T, int DP, bool CBL, int GM>
 __global__ __launch_bounds__(256) void vqres_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x, const float* __restrict__ books,
-                                                       const int* __restrict__ index, int M, int D, int L, int n, float sigma, int vec,
-                                                       T* __restrict__ dx, float* __restrict__ partial) {
+                                                       const int* __restrict__ index, const float* __restrict__ dhist, int M, int D,
+                                                       int L, int n, int G, float sigma, int vec, T* __restrict__ dx,
+                                                       float* __restrict__ partial) {
   extern __shared__ float vqresb_lds[];
   const int V = blockDim.x;
   const int KC = vqb_chunk(L);
-  float* pt = vqresb_lds + (CBL ? L * DP : 0);
+  float* dq = vqresb_lds + (CBL ? L * DP : 0);
+  float* pt = dq + (GM == 1 ? G * (L + 1) : 0);
   float* ddt = pt + KC * (V + 1);
   float* xt = ddt + KC * (V + 1);
   float* dyt = xt + V * D;
@@ -260,6 +267,14 @@ __global__ __launch_bounds__(256) void vqres_bwd_kernel(const T* __restrict__ dy
       const float* c = books + (size_t)s * LD;
       __syncthreads();                           // the staged book, xt, dyt and red of the stage before are free
       if (CBL) vqb_stage(c, vqresb_lds, D, L, DP);
+      if constexpr (GM == 1) {
+        const float* dh = dhist + (size_t)s * G * L;
+        for (int i = t; i < G * L; i += V) dq[(i / L) * (L + 1) + i % L] = dh[i];
+      }
+      // this vector's row of the stage's slice (a vector past M reads group 0's row: inside the table, never used)
+      const float* dqr = nullptr;
+      if constexpr (GM == 1) dqr = dq + (live ? m % G : 0) * (L + 1);
+      if constexpr (GM == 2) dqr = dhist + ((size_t)s * G + (live ? m % G : 0)) * L;
       float xr[DP], gr[DP], dxr[DP];
 #pragma unroll
       for (int j = 0; j < DP; ++j) xr[j] = gr[j] = dxr[j] = 0.f;
@@ -294,7 +309,8 @@ __global__ __launch_bounds__(256) void vqres_bwd_kernel(const T* __restrict__ dy
       for (int k = 0; k < L; ++k) {
         const float* ck = cc + k * ld;
         const float e = vq_weight(vqb_score<DP, CBL>(xr, ck, D), dmin, sigma);
-        const float q = vqb_dot<DP, CBL>(gr, ck, D);
+        float q = vqb_dot<DP, CBL>(gr, ck, D);
+        if constexpr (GM != 0) q += dqr[k];
         sum += e;
         pd = __fmaf_rn(e, q, pd);
       }
@@ -304,7 +320,8 @@ __global__ __launch_bounds__(256) void vqres_bwd_kernel(const T* __restrict__ dy
         for (int kq = 0; kq < kc; ++kq) {
           const float* ck = cc + (k0 + kq) * ld;
           const float p = vq_weight(vqb_score<DP, CBL>(xr, ck, D), dmin, sigma) / sum;
-          const float q = vqb_dot<DP, CBL>(gr, ck, D);
+          float q = vqb_dot<DP, CBL>(gr, ck, D);
+          if constexpr (GM != 0) q += dqr[k0 + kq];
           const float dd = -sigma * (p * (q - pd));
 #pragma unroll
           for (int j = 0; j < DP; ++j)
@@ -342,6 +359,48 @@ __global__ __launch_bounds__(256) void vqres_bwd_kernel(const T* __restrict__ dy
     if (live && dx != nullptr) vqb_store_row<T, DP>(dx + row, D, vec != 0, h);
     first = false;
   }
+}
+
+// both backward entry points.  grouped: G is checked; dhist [n][G][L] or NULL: NULL is exactly jpdse_vq_res_bwd's launch
+static int vqres_bwd_run(const char* who, const jpdse_vq_res_bwd_args* a, int G, const float* dhist, bool grouped = false) {
+  if (int rc = vq_res_check(who, a->dtype, a->M, a->D, a->L, a->S, a->n_stages)) return rc;
+  JPDSE_REQUIRE(a->n_stages >= 1, "%s: n_stages = %d (1 .. S = %d)", who, a->n_stages, a->S);
+  JPDSE_REQUIRE(isfinite(a->sigma) && a->sigma > 0.f, "%s: sigma is %g (a finite value > 0)", who, (double)a->sigma);
+  if (grouped) {
+    if (int rc = vqr_group_check(who, a->M, a->L, G)) return rc;
+    JPDSE_REQUIRE((long long)a->n_stages * G * a->L <= 65536, "%s: n_stages * G * L = %lld (at most 65536)", who,
+                  (long long)a->n_stages * G * a->L);
+  }
+  JPDSE_REQUIRE(a->dy && a->x && a->books && a->index, "%s: null pointer", who);
+  const int M = a->M, D = a->D, L = a->L, n = a->n_stages;
+  const int V = vqb_bwd_threads(D), nb = vqres_bwd_blocks(M, D, L, n);
+  float* partial = nullptr;
+  if (a->dbooks != nullptr) {
+    if (int rc = vq_ws_check(who, a->ws, a->ws_bytes, (size_t)nb * n * L * D * sizeof(float))) return rc;
+    partial = mptr<float>(a->ws);
+  }
+  if (a->dx == nullptr && partial == nullptr) return JPDSE_OK;
+  const int vec = vqb_vec(a->dtype, D, {a->x, a->dy, a->dx});
+  // a stage's slice of dhist goes to LDS when the block's LDS stays below 64000 bytes with it (the rule of vqb_bwd_run,
+  // vq_bottleneck.hip), otherwise it is read from global memory
+  int gm = 0;
+  if (dhist != nullptr) gm = vqres_bwd_lds(D, L, partial != nullptr, (size_t)G * (L + 1)) <= 64000 ? 1 : 2;
+  const size_t lds = vqres_bwd_lds(D, L, partial != nullptr, gm == 1 ? (size_t)G * (L + 1) : 0);
+  if (int rc = vqb_dispatch(a->dtype, D, L, [&](auto tag, auto dp, auto cbl) {
+        using T = decltype(tag);
+        constexpr int DPv = decltype(dp)::value;
+        constexpr bool CBLv = decltype(cbl)::value;
+        auto go = [&](auto kernel) {
+          return vq_launch(who, kernel, nb, V, lds, a->stream, cptr<T>(a->dy), cptr<T>(a->x), a->books, a->index, dhist, M, D, L, n, G,
+                           a->sigma, vec, mptr<T>(a->dx), partial);
+        };
+        if (gm == 1) return go(vqres_bwd_kernel<T, DPv, CBLv, 1>);
+        if (gm == 2) return go(vqres_bwd_kernel<T, DPv, CBLv, 2>);
+        return go(vqres_bwd_kernel<T, DPv, CBLv, 0>);
+      }))
+    return rc;
+  if (partial == nullptr) return JPDSE_OK;
+  return vq_launch(who, vq_merge_kernel, ew_blocks(n * L * D), 256, 0, a->stream, partial, nb, n * L * D, 1.f, a->dbooks);
 }
 
 }  // namespace jpdse
@@ -408,28 +467,12 @@ int jpdse_vq_res_decode(const jpdse_vq_res_decode_args* a) {
 
 int jpdse_vq_res_bwd(const jpdse_vq_res_bwd_args* a) {
   JPDSE_REQUIRE(a != nullptr, "vq_res_bwd: null argument struct");
-  if (int rc = vq_res_check("vq_res_bwd", a->dtype, a->M, a->D, a->L, a->S, a->n_stages)) return rc;
-  JPDSE_REQUIRE(a->n_stages >= 1, "vq_res_bwd: n_stages = %d (1 .. S = %d)", a->n_stages, a->S);
-  JPDSE_REQUIRE(isfinite(a->sigma) && a->sigma > 0.f, "vq_res_bwd: sigma is %g (a finite value > 0)", (double)a->sigma);
-  JPDSE_REQUIRE(a->dy && a->x && a->books && a->index, "vq_res_bwd: null pointer");
-  const int M = a->M, D = a->D, L = a->L, n = a->n_stages;
-  const int V = vqb_bwd_threads(D), nb = vqres_bwd_blocks(M, D, L, n);
-  float* partial = nullptr;
-  if (a->dbooks != nullptr) {
-    if (int rc = vq_ws_check("vq_res_bwd", a->ws, a->ws_bytes, (size_t)nb * n * L * D * sizeof(float))) return rc;
-    partial = mptr<float>(a->ws);
-  }
-  if (a->dx == nullptr && partial == nullptr) return JPDSE_OK;
-  const int vec = vqb_vec(a->dtype, D, {a->x, a->dy, a->dx});
-  const size_t lds = vqres_bwd_lds(D, L, partial != nullptr);
-  if (int rc = vqb_dispatch(a->dtype, D, L, [&](auto tag, auto dp, auto cbl) {
-        using T = decltype(tag);
-        return vq_launch("vq_res_bwd", vqres_bwd_kernel<T, decltype(dp)::value, decltype(cbl)::value>, nb, V, lds, a->stream,
-                         cptr<T>(a->dy), cptr<T>(a->x), a->books, a->index, M, D, L, n, a->sigma, vec, mptr<T>(a->dx), partial);
-      }))
-    return rc;
-  if (partial == nullptr) return JPDSE_OK;
-  return vq_launch("vq_res_bwd(merge)", vq_merge_kernel, ew_blocks(n * L * D), 256, 0, a->stream, partial, nb, n * L * D, 1.f, a->dbooks);
+  return vqres_bwd_run("vq_res_bwd", a, 1, nullptr);
+}
+
+int jpdse_vq_res_bwd_grouped(const jpdse_vq_res_bwd_grouped_args* a) {
+  JPDSE_REQUIRE(a != nullptr, "vq_res_bwd_grouped: null argument struct");
+  return vqres_bwd_run("vq_res_bwd_grouped", &a->bwd, a->G, a->dhist, true);
 }
 
 }  // extern "C"

@@ -267,9 +267,14 @@ class VQIndexCodec(_Codec):
 class VQStagesCodec(VQIndexCodec):
   """The residual bottleneck's code (vq_stages > 1): int64 [N, S', indices per stage], 1 <= S' <= S, coded as one
   .jpdr blob per image (ctu.utils.vqstages) that can be cut after any stage: a code or a blob of fewer stages
-  than the model's is legal everywhere on the receiver's side.  The rate term, the one-stage entropy-constrained assignment, the
-  context coder and the cost walks are built for one stage and refused here; the multi-stage entropy-constrained code (DESIGN.md
-  4.25) is code_ec, under calls of its own.  The model picks this class; CODECS stays by quantizer."""
+  than the model's is legal everywhere on the receiver's side.  The one-stage entropy-constrained assignment, the context coder
+  and the cost walks are built for one stage and refused here; the multi-stage entropy-constrained code is
+  code_ec, under calls of its own.  The rate term is the multi-stage one under a weight of its own,
+  opt.lambda_vq_stage_rate: rate_term / rate_denom (B H W: bits per pixel of the local batch) / rate_value are VQIndexCodec's, on
+  the residual layer, which sums the stages of the training forward -- under vq_train_stages = 'uniform' the drawn prefix only.
+  The model picks this class; CODECS stays by quantizer."""
+
+  RATE_OPTION = 'lambda_vq_stage_rate'
 
   def _n_stages(self):
     return self.netE.vq_stages

@@ -165,19 +165,21 @@ def parse_class_distortion_weights(text, n_labels):
 # with its bottleneck whose output reaches the generator (no --zero_vis); sem_weights: (class table, edge weight), or None when
 # every weight is 1; compute_dtype: 'fp32' / 'bf16'; feat_nc (the encoder's output channels), nef, n_downsample_E and the keyword
 # arguments encoder_args: what networks.define_G takes for the encoder; the last five: what the constructor reads behind network
-# construction; vq_stages / vq_train_stages: the residual bottleneck's code books and its training schedule
+# construction; lambda_vq_stage_rate: the weight of the residual bottleneck's rate term; vq_stages /
+# vq_train_stages: the residual bottleneck's code books and its training schedule
 ModelOptions = collections.namedtuple('ModelOptions', [
     'feat_enc', 'quantizer', 'encoder_runs', 'lambda_rate', 'lambda_vq_rate', 'vq_context_coder', 'sem_weights', 'compute_dtype',
     'n_onehot', 'label_nc', 'feat_nc', 'zero_vis', 'zero_sem', 'zero_ins', 'no_instance', 'codec_seed',
     'nef', 'n_downsample_E', 'encoder_args',
-    'checkpoint_resblocks', 'load_model', 'vgg19_state_dict', 'no_vgg_loss', 'vgg_random_init', 'vq_stages', 'vq_train_stages'])
+    'checkpoint_resblocks', 'load_model', 'vgg19_state_dict', 'no_vgg_loss', 'vgg_random_init', 'lambda_vq_stage_rate',
+    'vq_stages', 'vq_train_stages'])
 
 
 def resolve_model_options(opt):
   """opt -> ModelOptions, or the refusal.  The order of the checks is part of the contract: first everything outside the
   accelerated path in ONE NotImplementedError, then distortion_loss_fn, lambda_rate, lambda_vq_rate, vq_context_coder,
   encoder_quantizer (with the bottleneck's own check), vq_stages and vq_train_stages (opt fields without a flag),
-  then the class weights, the edge weight and their conflict with ms_ssim."""
+  lambda_vq_stage_rate (an opt field without a flag), then the class weights, the edge weight and their conflict with ms_ssim."""
   g = lambda name, default=False: getattr(opt, name, default)
   feat_enc = not g('no_feat_encoding')
   bottleneck = feat_enc and not g('no_encoder_binarization')
@@ -268,6 +270,17 @@ def resolve_model_options(opt):
   if vq_train_stages == 'uniform' and vq_stages == 1:
     raise ValueError("vq_train_stages = 'uniform' draws a stage prefix per step: it needs vq_stages > 1")
   enc['vq_stages'] = vq_stages
+  # rate term of the residual bottleneck: a field a caller sets on the parsed namespace; absent or 0: nothing changes
+  lvs = g('lambda_vq_stage_rate', 0.0)
+  lvs = 0.0 if lvs is None or lvs is False else lvs
+  if isinstance(lvs, bool) or not isinstance(lvs, (int, float)) or not (float(lvs) >= 0.0 and float(lvs) != float('inf')):
+    raise ValueError('lambda_vq_stage_rate must be a finite number >= 0, got %r' % (lvs,))
+  lambda_vq_stage_rate = float(lvs)
+  if lambda_vq_stage_rate > 0.0 and vq_stages == 1:
+    raise ValueError('lambda_vq_stage_rate > 0 is the rate term of the residual bottleneck: it needs vq_stages > 1 (the one-stage '
+                     'bottleneck takes --lambda_vq_rate)')
+  if lambda_vq_stage_rate > 0.0 and zero_vis:
+    raise ValueError('lambda_vq_stage_rate > 0 needs an encoder that runs: it cannot be combined with --zero_vis')
   # semantics-weighted distortion: (class table, edge weight), or None when every weight is 1 -- the
   # step then takes the plain l1 / mse path
   n_onehot = opt.num_labels + 1 if g('contain_dontcare_label') else opt.num_labels
@@ -297,4 +310,4 @@ def resolve_model_options(opt):
       no_instance=no_instance, codec_seed=int(g('seed', None) or 0), nef=g('nef', 64), n_downsample_E=n_downsample_E,
       encoder_args=enc, checkpoint_resblocks=bool(g('checkpoint_resblocks')), load_model=bool(g('load_model')),
       vgg19_state_dict=g('vgg19_state_dict', None), no_vgg_loss=bool(g('no_vgg_loss')), vgg_random_init=bool(g('vgg_random_init')),
-      vq_stages=vq_stages, vq_train_stages=vq_train_stages)
+      lambda_vq_stage_rate=lambda_vq_stage_rate, vq_stages=vq_stages, vq_train_stages=vq_train_stages)

@@ -58,6 +58,7 @@ class Pix2PixHDModel(CodedCalls, BaseModel):
     o = resolve_model_options(opt)      # every refusal of a flag: before any network (hence any device allocation) exists
     self.use_features = True
     self.lambda_rate, self.lambda_vq_rate, self.vq_context_coder = o.lambda_rate, o.lambda_vq_rate, o.vq_context_coder
+    self.lambda_vq_stage_rate = o.lambda_vq_stage_rate
     self.sem_weights, self.cdtype = o.sem_weights, networks.dtype_code(o.compute_dtype)
     self.n_onehot, self.label_nc, self.feat_nc, self.use_feat_encoding = o.n_onehot, o.label_nc, o.feat_nc, o.feat_enc
     self.zero_vis, self.zero_sem, self.zero_ins, self.no_instance = o.zero_vis, o.zero_sem, o.zero_ins, o.no_instance
@@ -79,7 +80,8 @@ class Pix2PixHDModel(CodedCalls, BaseModel):
     if o.feat_enc:
       self.netE = networks.define_G(opt.input_nc, o.feat_nc, o.nef, 'encoder', o.n_downsample_E, norm=opt.norm,
                                     gpu_ids=self.gpu_ids, compute_dtype=o.compute_dtype, **o.encoder_args)
-    # the codec of the encoder's bottleneck and the weight of its rate term, --lambda_rate or --lambda_vq_rate:
+    # the codec of the encoder's bottleneck and the weight of its rate term, --lambda_rate, --lambda_vq_rate or
+    # opt.lambda_vq_stage_rate:
     # resolve_model_options leaves a positive weight to the quantizer in use only
     self.rate_weight = 0.0
     if self.netE is not None and self.netE.quantizer is not None:

@@ -42,6 +42,32 @@ class _ResidualQuantize(torch.autograd.Function):
     return dx, dc, None, None
 
 
+class _ResidualRate(torch.autograd.Function):
+  """rate fp32 [1] of ops.vq_res_rate_fwd over the first `stages` books; backward: ops.vq_res_bwd(groups, dhist)
+  with dy = 0 on the indices of ops.vq_res_rows_fwd, dhist scaled by the incoming gradient.  The books beyond `stages` get a zero
+  gradient."""
+
+  @staticmethod
+  def forward(ctx, x, books, sigma, groups, denom, stages):
+    x, books = x.contiguous(), books.contiguous()
+    rate, _, _, dhist, _, index = ops.vq_res_rate_fwd(x, books, sigma, groups, denom, 1.0, n_stages=stages, want_code=True)
+    ctx.save_for_backward(x, books, index, dhist)
+    ctx.sigma, ctx.groups = sigma, groups
+    return rate
+
+  @staticmethod
+  def backward(ctx, drate):
+    x, books, index, dhist = ctx.saved_tensors
+    # The softmax backward sees dp only through dp - <p, dp>: a constant added to a row of dhist changes nothing.  With dy = 0 the
+    # rows ARE dp, and on near-uniform histograms they are a large common value plus a small variation that carries the whole
+    # gradient; fp32 would lose it under the common value (DESIGN.md 4.26), so the row means are taken out first.
+    dhist = dhist - dhist.mean(dim=-1, keepdim=True)
+    dx, dc = ops.vq_res_bwd(torch.zeros_like(x), x, books, index, ctx.sigma, want_dx=ctx.needs_input_grad[0],
+                            want_dc=ctx.needs_input_grad[1], groups=ctx.groups,
+                            dhist=(dhist * drate.to(torch.float32).reshape(())).contiguous())
+    return dx, dc, None, None, None, None
+
+
 class ResidualS2HVQ(nn.Module):
   """code_books: float32 tensor [S, n_center, center_size], learnable (parameter `_code_books`); sigma > 0: the hardness of the
   soft assignment whose gradient training uses."""
@@ -122,6 +148,31 @@ class ResidualS2HVQ(nn.Module):
     else:
       y, index = ops.vq_res_rows_fwd(xm.detach(), self._code_books.detach().contiguous(), n_st)
     return y.view(n, code_len * self._center_size), index.to(torch.int64).view(n_st, n, code_len)
+
+  def rate(self, x, code_len, groups=1, denom=None, stages=None):
+    """The rate term of the first `stages` (default: all) stages on per-group histograms: x [n, d] as in
+    quantize; vector m of the [n * code_len, center_size] matrix belongs to group m % groups (groups must divide n * code_len).
+    Returns the 0-dim float32 sum over the stages s of -sum_g sum_k hist[s][g][k] log2(hist[s][g][k] / (M / groups)) / denom, hist[s]
+    the per-group sums of the soft assignment of the residual r_s that the hard forward hands to stage s; denom defaults to M =
+    n * code_len: bits per vector.  Differentiable in x and the books when gradients are enabled: p_s is evaluated at the hard
+    residual and differentiates through the soft chain of quantize's surrogate; books beyond `stages` get a zero gradient.  [M,
+    n_center] is never stored.  With one stage it is S2HVQ.rate's value."""
+    n_st = self._stages(stages)
+    self._vector_checks(x, code_len)
+    M, groups, L = x.size(0) * code_len, int(groups), int(self._code_books.size(1))
+    if groups < 1 or M % groups != 0:
+      raise ValueError('groups must divide n * code_len, got {} and {}'.format(groups, M))
+    if n_st * groups * L > 65536:
+      raise NotImplementedError('ResidualS2HVQ.rate: stages * groups * n_center = %d, the kernels take at most 65536' % (n_st * groups * L))
+    denom = float(M if denom is None else denom)
+    if not (denom > 0 and denom != float('inf')):
+      raise ValueError('denom must be a finite number > 0, got {}'.format(denom))
+    xm = self._vectors(x, code_len)      # every refusal above needs no device
+    if torch.is_grad_enabled() and (xm.requires_grad or self._code_books.requires_grad):
+      return _ResidualRate.apply(xm, self._code_books, float(self._sigma), groups, denom, n_st).reshape(())
+    value = ops.vq_res_rate_fwd(xm.detach(), self._code_books.detach().contiguous(), float(self._sigma), groups, denom,
+                                n_stages=n_st, want_grad=False)[0]
+    return value.reshape(())
 
   def encode(self, x, code_len, stages=None):
     """The int64 code [S', n, code_len] of x [n, d].  Nothing is differentiable."""

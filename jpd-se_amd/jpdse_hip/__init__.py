@@ -265,6 +265,18 @@ class VqResBwdArgs(ctypes.Structure):
              [('ws_bytes', ctypes.c_size_t), ('stream', ctypes.c_void_p)]
 
 
+# the residual quantizer's rate term (vq_res_rate.hip, vq_residual.hip)
+class VqResRateFwdArgs(ctypes.Structure):
+  _fields_ = [(n, ctypes.c_int32) for n in ('dtype', 'M', 'D', 'L', 'S', 'n_stages', 'G')] + \
+             [(n, ctypes.c_float) for n in ('sigma', 'scale', 'denom')] + \
+             [(n, ctypes.c_void_p) for n in ('x', 'books', 'rate', 'rates', 'hist', 'dhist', 'y', 'index', 'ws')] + \
+             [('ws_bytes', ctypes.c_size_t), ('stream', ctypes.c_void_p)]
+
+
+class VqResBwdGroupedArgs(ctypes.Structure):
+  _fields_ = [('bwd', VqResBwdArgs), ('G', ctypes.c_int32), ('dhist', ctypes.c_void_p)]
+
+
 _P, _I32, _I64, _F, _SZ = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float,
                            ctypes.c_size_t)
 _CD, _ND = ctypes.POINTER(ConvDesc), ctypes.POINTER(InormDesc)
@@ -411,6 +423,9 @@ SIGNATURES = {
     'jpdse_vq_res_bwd': (_I32, [ctypes.POINTER(VqResBwdArgs)]),
     'jpdse_vq_res_ec_workspace_size': (_SZ, [_I32, _I32, _I32, _I32, _I32]),
     'jpdse_vq_res_ec_assign': (_I32, [ctypes.POINTER(VqResEcAssignArgs)]),
+    'jpdse_vq_res_rate_workspace_size': (_SZ, [_I32, _I32, _I32, _I32, _I32]),
+    'jpdse_vq_res_rate_fwd': (_I32, [ctypes.POINTER(VqResRateFwdArgs)]),
+    'jpdse_vq_res_bwd_grouped': (_I32, [ctypes.POINTER(VqResBwdGroupedArgs)]),
 }
 
 # the developer build (same sources, -DJPDSE_DEV): the shipped ABI plus include/jpdse_dev.h

@@ -443,9 +443,13 @@ class HipResidualVQBottleneck(nn.Module):
   center_size]) on the same [M][D] view of the conv's NHWC output, under the same geometry check.
 
   Forward: always the hard form, over the first `stages` books (ops.vq_res_rows_fwd); backward: the soft form's gradient at
-  every stage (ops.vq_res_bwd), books beyond `stages` getting zeros.  The soft forward, the rate term and the cost walks are
-  built for one stage only and are not methods of this layer; the entropy-constrained code and the usage counts are the
-  multi-stage ones of DESIGN.md 4.25 (code_ec, usage).
+  every stage (ops.vq_res_bwd), books beyond `stages` getting zeros.  The soft forward and the cost walks are built for one
+  stage only and are not methods of this layer; the entropy-constrained code and the usage counts are the multi-stage ones of
+  DESIGN.md 4.25 (code_ec, usage).
+  Rate term: with `rate_scale` set by the owner (rate_denom with it) a training forward is ONE
+  ops.vq_res_rate_fwd(want_code=True) call on the conv's output -- y and index are ops.vq_res_rows_fwd's bit for bit, the unscaled
+  total stays in `rate_value` (fp32 [1]), the per-stage values in `rate_stage_values` (fp32 [stages]), and dhist, scaled by
+  rate_scale, travels with the context into the grouped backward.  With rate_scale None every call is the one above.
   Books: stage s is (2 * torch.rand(n_center, center_size) - 1) * 0.5 ** s from a CPU torch.Generator seeded with seed + s --
   the same books on every device and rank; load_state_dict replaces them."""
 
@@ -464,6 +468,7 @@ class HipResidualVQBottleneck(nn.Module):
     self.hard_forward = True
     self.grad_ready_hook = None
     self.train_stages = None      # the owner's stage count for the next training forward (None: all); eval ignores it
+    self.rate_scale, self.rate_denom, self.rate_value, self.rate_stage_values = None, 0, None, None
 
   @property
   def groups(self):
@@ -499,6 +504,13 @@ class HipResidualVQBottleneck(nn.Module):
       stages = self.train_stages
     n = self._stages(stages)
     h, c_conv = self.conv.fwd(x)
+    if self.rate_scale is not None:
+      # opt.lambda_vq_stage_rate: the owner set rate_scale / rate_denom for this call; one kernel gives the code
+      # and the histograms of the stages in use, and the gradient w.r.t. those sums travels with the context
+      self.rate_value, self.rate_stage_values, _, dhist, y, index = ops.vq_res_rate_fwd(
+          h.t.view(-1, self.center_size), self._books().detach(), self.vq.sigma, self.groups, self.rate_denom, self.rate_scale,
+          n_stages=n, want_code=True)
+      return Act(y.view(h.t.shape), h.C), Ctx(c_conv, h, index, dhist)
     y, index = self._quantize(h, n)
     return y, Ctx(c_conv, h, index)
 
@@ -552,12 +564,17 @@ class HipResidualVQBottleneck(nn.Module):
   def bwd(self, ctx, dy, need_dx=True, need_dw=True):
     """dy: the gradient w.r.t. the quantized features.  Straight-through: the soft form's gradient at every stage of the forward
     (DESIGN.md 4.23), zeros for the books it did not use, then the 1x1 conv's data / weight gradients."""
-    c_conv, h, index = ctx.items
+    c_conv, h, index = ctx.items[:3]
     D = self.center_size
     books = self._books()
     want_dc = need_dw and books.requires_grad
-    dh, _ = ops.vq_res_bwd(dy.t.view(-1, D), h.t.view(-1, D), books.detach(), index, self.vq.sigma, want_dx=True,
-                           want_dc=want_dc, dc_out=self._cgrad_buffer() if want_dc else None)
+    if len(ctx.items) == 4:      # a forward with a rate scale: its dhist joins dp of every stage in the grouped backward
+      dh, _ = ops.vq_res_bwd(dy.t.view(-1, D), h.t.view(-1, D), books.detach(), index, self.vq.sigma, want_dx=True,
+                             want_dc=want_dc, dc_out=self._cgrad_buffer() if want_dc else None, groups=self.groups,
+                             dhist=ctx.items[3])
+    else:
+      dh, _ = ops.vq_res_bwd(dy.t.view(-1, D), h.t.view(-1, D), books.detach(), index, self.vq.sigma, want_dx=True,
+                             want_dc=want_dc, dc_out=self._cgrad_buffer() if want_dc else None)
     if want_dc and self.grad_ready_hook is not None:
       self.grad_ready_hook(self)
     return self.conv.bwd(c_conv, Act(dh.view(h.t.shape), h.C), need_dx, need_dw)

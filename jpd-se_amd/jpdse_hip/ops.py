@@ -12,7 +12,8 @@ import torch
 from . import (lib, check, JpdseError, F32, BF16, ConvDesc, PackEntry, InormDesc, EvalMetricsSemArgs, MsssimLossArgs, CodeRateArgs, SemLossArgs, CodeCostArgs, ACT_NONE, PAD_ZERO, PAD_REFLECT)
 from . import (VqSoftFwdArgs, VqHardFwdArgs, VqSoftBwdArgs, VqDecodeArgs, VqDecodeBwdArgs, VqArgmaxArgs, VqPmfArgs, VqPmfBwdArgs,
                VqQuantizeFwdArgs, VqQuantizeBwdArgs, VqRateFwdArgs, VqQuantizeBwdGroupedArgs, VqLloydAccumArgs, VqLloydUpdateArgs,
-               VqEcAssignArgs, VqEcLengthsArgs, VqResFwdArgs, VqResRowsFwdArgs, VqResDecodeArgs, VqResBwdArgs, VqResEcAssignArgs)
+               VqEcAssignArgs, VqEcLengthsArgs, VqResFwdArgs, VqResRowsFwdArgs, VqResDecodeArgs, VqResBwdArgs, VqResEcAssignArgs,
+               VqResRateFwdArgs, VqResBwdGroupedArgs)
 from . import VQ_RES_MAX_STAGES as _VQ_RES_MAX_STAGES
 
 
@@ -1249,10 +1250,13 @@ def vq_res_decode(index, books, n_stages=None, dtype=torch.float32, status=None)
   return y, status
 
 
-def vq_res_bwd(dy, x, books, index, sigma, want_dx=True, want_dc=True, dc_out=None):
+def vq_res_bwd(dy, x, books, index, sigma, want_dx=True, want_dc=True, dc_out=None, groups=1, dhist=None):
   """(dx, dbooks) of the SOFT form of every stage of vq_res_fwd -- the straight-through gradient -- for the upstream gradient dy
   [M, D] (x's dtype) (jpdse_vq_res_bwd; the residuals are recomputed from x and index int32 [S', M]).  dx in x's dtype; dbooks
-  fp32 [S, L, D] (written into dc_out when given), zero for the books beyond S'; either is None when not wanted."""
+  fp32 [S, L, D] (written into dc_out when given), zero for the books beyond S'; either is None when not wanted.
+  groups / dhist: with either given the call is jpdse_vq_res_bwd_grouped -- vector m belongs to group m % groups
+  and dhist fp32 [S', groups, L], the gradient w.r.t. vq_res_rate_fwd's un-normalised sums, is added to dp of stage s at the
+  vector's group.  The defaults take exactly the call above."""
   assert x.dim() == 2 and x.is_contiguous(), tuple(x.shape)
   M, D = int(x.shape[0]), int(x.shape[1])
   S, L, _ = _vq_res_dims(books, D)
@@ -1271,8 +1275,45 @@ def vq_res_bwd(dy, x, books, index, sigma, want_dx=True, want_dc=True, dc_out=No
   args = VqResBwdArgs(code_of(x.dtype), M, D, L, S, n, float(sigma), dy.data_ptr(), x.data_ptr(), books.data_ptr(), index.data_ptr(),
                       dx.data_ptr() if want_dx else None, dc.data_ptr() if want_dc else None, ws.data_ptr() if want_dc else None,
                       ws.numel() if want_dc else 0, torch.cuda.current_stream().cuda_stream)
+  if dhist is not None or int(groups) != 1:
+    G = int(groups)
+    if dhist is not None:
+      assert dhist.dtype == torch.float32 and dhist.is_contiguous() and tuple(dhist.shape) == (n, G, L) and dhist.device == x.device, \
+          (dhist.dtype, tuple(dhist.shape))
+    gargs = VqResBwdGroupedArgs(args, G, dhist.data_ptr() if dhist is not None else None)
+    check(lib().jpdse_vq_res_bwd_grouped(ctypes.byref(gargs)), 'vq_res_bwd_grouped')
+    return dx, dc
   check(lib().jpdse_vq_res_bwd(ctypes.byref(args)), 'vq_res_bwd')
   return dx, dc
+
+
+def vq_res_rate_fwd(x, books, sigma, G, denom, scale=1.0, n_stages=None, want_code=False, want_hist=False, want_grad=True):
+  """(rate, rates, hist, dhist, y, index) of the rate term of the residual quantizer (jpdse_vq_res_rate_fwd) over
+  the first n_stages (default: all) of books fp32 [S, L, D]: vector m of x [M, D] belongs to group m % G; hist fp32 [n_stages, G, L]
+  the per-group sums of the soft assignment of every stage's residual r_s (the hard chain of vq_res_rows_fwd; None unless
+  want_hist); rates fp32 [n_stages], rates[s] = -sum hist[s] log2(hist[s] / (M / G)) / denom; rate fp32 [1] their sum in stage
+  order; dhist fp32 [n_stages, G, L] = scale * d rate / d hist (None unless want_grad): what vq_res_bwd(groups=G, dhist=...) takes.
+  want_code: y [M, D] and index int32 [n_stages, M] of vq_res_rows_fwd, bit for bit, from the same kernel (else None)."""
+  assert x.dim() == 2 and x.is_contiguous(), tuple(x.shape)
+  M, D = int(x.shape[0]), int(x.shape[1])
+  S, L, _ = _vq_res_dims(books, D)
+  assert books.device == x.device
+  n = _vq_res_stages(n_stages, S, 1)
+  G = int(G)
+  dev = x.device
+  rate = torch.empty(1, dtype=torch.float32, device=dev)
+  rates = torch.empty(n, dtype=torch.float32, device=dev)
+  hist = torch.empty((n, max(G, 0), L), dtype=torch.float32, device=dev) if want_hist else None
+  dhist = torch.empty((n, max(G, 0), L), dtype=torch.float32, device=dev) if want_grad else None
+  y = torch.empty_like(x) if want_code else None
+  index = torch.empty((n, M), dtype=torch.int32, device=dev) if want_code else None
+  ws = workspace(max(lib().jpdse_vq_res_rate_workspace_size(M, D, L, G, n), 1), dev)
+  args = VqResRateFwdArgs(code_of(x.dtype), M, D, L, S, n, G, float(sigma), float(scale), float(denom), x.data_ptr(), books.data_ptr(),
+                          rate.data_ptr(), rates.data_ptr(), hist.data_ptr() if want_hist else None,
+                          dhist.data_ptr() if want_grad else None, y.data_ptr() if want_code else None,
+                          index.data_ptr() if want_code else None, ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+  check(lib().jpdse_vq_res_rate_fwd(ctypes.byref(args)), 'vq_res_rate_fwd')
+  return rate, rates, hist, dhist, y, index
 
 
 def vq_res_ec_assign(x, books, bias=None, groups=1, n_stages=None, want_y=True, want_stats=True):
