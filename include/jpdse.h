@@ -1303,6 +1303,53 @@ typedef struct jpdse_vq_res_bwd_grouped_args {
 } jpdse_vq_res_bwd_grouped_args;
 int jpdse_vq_res_bwd_grouped(const jpdse_vq_res_bwd_grouped_args* args);
 
+/* ---- residual vector quantizer: a stage depth per cell (vq_residual.hip) ------------------------------------------
+ * x [M][D], books [S][L][D] and n = n_stages <= S stages in use as above; G >= 1 vectors per cell, G | M: the cell of vector m is
+ * m / G (one NHWC pixel of the feature map holds G consecutive vectors).  depth: int32 [M / G], values in 1 .. S; a value outside
+ * is clamped to 1 .. S on the device.  n_m = min(n, depth[m / G]).
+ *   res_rows_fwd_depth   row m is quantized exactly as res_rows_fwd with n_stages = n_m quantizes it: the same score, strict <,
+ *                        r - c, a = c / a += c in stage order, rounded once.  index [n][M]: index[s][m] = -1 for s >= n_m.
+ *   res_decode_depth     y[m] = the sum of the first n_m centres of row m, bit for bit the forward's y; index[s][m] for s >= n_m is
+ *                        never read; an index outside [0, L) inside the depth reads as centre 0 and sets *status to 1.
+ *   res_bwd_depth        res_bwd's recursion per row with h_{n_m + 1} = 0: dx[m] is res_bwd's at n_stages = n_m bit for bit;
+ *                        dbooks[s] sums over the rows with n_m > s only, a row outside a stage adds exactly nothing to it (a stage
+ *                        without a row gets zeros).  The same workspace and block-order merge as res_bwd; no atomics.
+ *   depth_map            depth[i][cy][cx] = the maximum over the step x step pixels of the cell of table[class of the pixel]; the
+ *                        class of a pixel is its label when that is an integer in [0, n_classes) (the rule of code_cost's class
+ *                        attribution), and any other pixel, NaN included, takes default_depth.  label fp32 [N][1][H][W], table
+ *                        int32 [n_classes], depth int32 [N][H / step][W / step].  The values are stored as they are: the three
+ *                        calls above clamp.
+ * Grid, tile and path are functions of (M, D, L, n_stages) alone: two calls give identical bits, and with every depth >= n_stages
+ * y, index, dx and dbooks are those of the calls without a depth, bit for bit.  JPDSE_EINVAL before any launch, outputs untouched:
+ * the limits of the call without a depth, G < 1, M % G != 0, NULL depth, a workspace missing or too small; depth_map: N, H, W < 1,
+ * step < 1 or not dividing H and W, N * H * W >= 2^31, n_classes outside 0 .. 65536, a NULL label, depth, or table with classes. */
+typedef struct jpdse_vq_res_rows_fwd_depth_args {
+  jpdse_vq_res_rows_fwd_args fwd;
+  int32_t G;
+  const int32_t* depth;    /* [M / G] */
+} jpdse_vq_res_rows_fwd_depth_args;
+int jpdse_vq_res_rows_fwd_depth(const jpdse_vq_res_rows_fwd_depth_args* args);
+typedef struct jpdse_vq_res_decode_depth_args {
+  jpdse_vq_res_decode_args dec;
+  int32_t G;
+  const int32_t* depth;    /* [M / G] */
+} jpdse_vq_res_decode_depth_args;
+int jpdse_vq_res_decode_depth(const jpdse_vq_res_decode_depth_args* args);
+typedef struct jpdse_vq_res_bwd_depth_args {
+  jpdse_vq_res_bwd_args bwd;
+  int32_t G;
+  const int32_t* depth;    /* [M / G] */
+} jpdse_vq_res_bwd_depth_args;
+int jpdse_vq_res_bwd_depth(const jpdse_vq_res_bwd_depth_args* args);
+typedef struct jpdse_vq_depth_map_args {
+  int32_t N, H, W, step, n_classes, default_depth;
+  const float* label;      /* [N][1][H][W] */
+  const int32_t* table;    /* [n_classes], or NULL with n_classes == 0 */
+  int32_t* depth;          /* [N][H / step][W / step] */
+  void* stream;
+} jpdse_vq_depth_map_args;
+int jpdse_vq_depth_map(const jpdse_vq_depth_map_args* args);
+
 /* ---- optimizer ---------------------------------------------------------------------- */
 /* torch.optim.Adam (model.py:275,279) over a table of tensors, one launch.  `table` is a
  * device array of jpdse_adam_entry; bias corrections are computed from `step` (1-based). */

@@ -18,7 +18,14 @@
 //       (vq_bottleneck.hip) at (r_s, a_s): u_s into registers, the stage's [L][D] share into the block's partial [n][L][D];
 //       h_s = h_{s+1} + u_s; dx = h_1.  vq_merge_kernel (vq_core.h) adds the partials in block order.
 //   vqres_sse_kernel     sse[s] = the blocks' fp64 partials in block order.
+//   DEP: a per-row stage depth on the three kernels above that work per row.  depth int32 [M / G], the cell of row m
+//       is m / G, n_m = min(n, depth clamped to 1 .. S).  BARRIER RULE: the stage loops hold __syncthreads() (the book restage, the
+//       code-book-gradient reduction), so n_m is a PREDICATE inside the loop and never a thread's loop bound: the bound stays n, every
+//       thread reaches every barrier, a row past its depth computes nothing and stores nothing but its -1 (forward) or the zeros of its
+//       LDS slots (backward); a wave whose rows are all past their depth skips the score loops by ordinary divergence.
+//   vqres_depth_map_kernel  the cell depths from a label map: one thread per cell, the maximum over its step x step pixels.
 // No atomics; grids, tiles and chunks are functions of (M, D, L, n) alone: two calls give identical bits.
+#include <limits.h>
 #include <math.h>
 
 #include "common.h"
@@ -69,6 +76,27 @@ __device__ __forceinline__ float vqres_sum(const float* __restrict__ books, int 
   float acc = books[k(0) * D + j];
   for (int s = 1; s < n; ++s) acc += books[(size_t)s * LD + k(s) * D + j];
   return acc;
+}
+
+// ---- per-row stage depth -------------------------------------------------------------------------------------
+// The last parameter of the per-row kernels.  DEP false: an empty struct, n_m = n for every row, and the kernel's code is what it
+// was without the parameter.
+template <bool DEP>
+struct VqDepth {};
+template <>
+struct VqDepth<true> {
+  const int* depth;                              // [M / G]
+  int G;
+};
+// n_m = min(n, depth[m / G] clamped to 1 .. S) = depth[m / G] clamped to 1 .. n (n <= S): a hostile map cannot reach past the books
+template <bool DEP>
+__device__ __forceinline__ int vqres_row_stages(const VqDepth<DEP>& dep, int m, int n) {
+  if constexpr (DEP) {
+    const int d = dep.depth[m / dep.G];
+    return d < 1 ? 1 : (d < n ? d : n);
+  } else {
+    return n;
+  }
 }
 
 // ---- forward ----------------------------------------------------------------------------------------------------------------
@@ -151,9 +179,12 @@ __global__ __launch_bounds__(256) void vqres_fwd_kernel(const T* __restrict__ x,
 // The residual r and the running sum a of a vector live in DP registers each; the stage loop runs inside the thread.  LDS: cb
 // [L][DP] when CBL, restaged per stage between two barriers that EVERY thread reaches (a thread without a vector works on zeros
 // and stores nothing); otherwise book s is read from global memory at wave-uniform addresses.  index: [n][M], n >= 1.
-template <typename T, int DP, bool CBL>
+// DEP: row m takes its first n_m stages and stores index[s][m] = -1 for the others.  The barrier rule of the file's head: the loop
+// bound is n for every thread, s < n_m is a predicate, and the `continue` of a row past its depth leads to the next stage's barriers.
+template <typename T, int DP, bool CBL, bool DEP>
 __global__ __launch_bounds__(256) void vqres_rows_fwd_kernel(const T* __restrict__ x, const float* __restrict__ books, int M, int D,
-                                                            int L, int n, int vec, T* __restrict__ y, int* __restrict__ index) {
+                                                            int L, int n, int vec, T* __restrict__ y, int* __restrict__ index,
+                                                            VqDepth<DEP> dep) {
   extern __shared__ float vqresr_lds[];
   constexpr int V = 256;
   const int ld = CBL ? DP : D;
@@ -168,12 +199,19 @@ __global__ __launch_bounds__(256) void vqres_rows_fwd_kernel(const T* __restrict
 #pragma unroll
     for (int j = 0; j < DP; ++j) r[j] = a[j] = 0.f;
     if (live) vqb_load_row<T, DP>(x + row, D, vec != 0, r);
+    const int nm = live ? vqres_row_stages(dep, m, n) : 0;     // DEP: a thread without a vector takes no stage
     for (int s = 0; s < n; ++s) {
       const float* c = books + (size_t)s * LD;
       if (CBL) {
         __syncthreads();                         // the book of the stage (or tile) before is free
         vqb_stage(c, vqresr_lds, D, L, DP);
         __syncthreads();
+      }
+      if constexpr (DEP) {
+        if (s >= nm) {                           // past the row's depth: after this stage's barriers, before the next one's
+          if (live) index[(size_t)s * M + m] = -1;
+          continue;
+        }
       }
       const float* cc = CBL ? vqresr_lds : c;
       float dmin = INFINITY;
@@ -207,15 +245,16 @@ __global__ __launch_bounds__(64) void vqres_sse_kernel(const double* __restrict_
 }
 
 // ---- decode -----------------------------------------------------------------------------------------------------------------
-template <typename T>
+// DEP: the first n_m centres of row m; index[s][m] for s >= n_m is never read
+template <typename T, bool DEP>
 __global__ __launch_bounds__(256) void vqres_decode_kernel(const int* __restrict__ index, const float* __restrict__ books, int M, int D,
-                                                          int L, int n, T* __restrict__ y, int* __restrict__ status) {
+                                                          int L, int n, T* __restrict__ y, int* __restrict__ status, VqDepth<DEP> dep) {
   const long long total = (long long)M * D;
   const int LD = L * D;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int m = (int)(i / D), j = (int)(i - (long long)m * D);
     bool bad = false;
-    const float v = vqres_sum(books, LD, D, n, j, [&](int s) {
+    const float v = vqres_sum(books, LD, D, vqres_row_stages(dep, m, n), j, [&](int s) {
       int k = index[(size_t)s * M + m];
       if ((unsigned)k >= (unsigned)L) {
         k = 0;
@@ -234,11 +273,15 @@ __global__ __launch_bounds__(256) void vqres_decode_kernel(const int* __restrict
 // a dhist); 1: dhist [n][G][L], the stage's slice staged in LDS as dq [G][L + 1] where the stage's book is restaged (the odd stride:
 // lanes of different groups on different banks) and read at the vector's group (m % G); 2: a slice too large for LDS, read from
 // global memory.
-template <typename T, int DP, bool CBL, int GM>
+// DEP (with GM 0): row m runs the recursion over its first n_m stages, h_{n_m + 1} = 0.  The barrier rule of the file's head: s runs
+// over all n stages in every thread; at a stage s >= n_m the row reads neither x, dy nor index (index[s][m] is -1 there), skips the
+// sweeps, keeps h = 0 and, with a partial, writes ZEROS into its slots of xt, dyt, pt and ddt, so the reduction adds exactly nothing
+// for it (a stale slot could hold anything, and 0 * stale may be NaN).
+template <typename T, int DP, bool CBL, int GM, bool DEP>
 __global__ __launch_bounds__(256) void vqres_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x, const float* __restrict__ books,
                                                        const int* __restrict__ index, const float* __restrict__ dhist, int M, int D,
                                                        int L, int n, int G, float sigma, int vec, T* __restrict__ dx,
-                                                       float* __restrict__ partial) {
+                                                       float* __restrict__ partial, VqDepth<DEP> dep) {
   extern __shared__ float vqresb_lds[];
   const int V = blockDim.x;
   const int KC = vqb_chunk(L);
@@ -263,7 +306,9 @@ __global__ __launch_bounds__(256) void vqres_bwd_kernel(const T* __restrict__ dy
     float h[DP];                                 // h_{s+1}: the gradient that the later stages sent back to r_{s+1}
 #pragma unroll
     for (int j = 0; j < DP; ++j) h[j] = 0.f;
+    const int nm = live ? vqres_row_stages(dep, m, n) : 0;
     for (int s = n - 1; s >= 0; --s) {
+      const bool act = DEP ? s < nm : live;      // the row takes part in this stage
       const float* c = books + (size_t)s * LD;
       __syncthreads();                           // the staged book, xt, dyt and red of the stage before are free
       if (CBL) vqb_stage(c, vqresb_lds, D, L, DP);
@@ -278,7 +323,7 @@ __global__ __launch_bounds__(256) void vqres_bwd_kernel(const T* __restrict__ dy
       float xr[DP], gr[DP], dxr[DP];
 #pragma unroll
       for (int j = 0; j < DP; ++j) xr[j] = gr[j] = dxr[j] = 0.f;
-      if (live) {
+      if (act) {
         vqb_load_row<T, DP>(x + row, D, vec != 0, xr);
         for (int u = 0; u < s; ++u) {            // r_s by the forward's subtractions, in its order
           const float* cu = books + (size_t)u * LD + index[(size_t)u * M + m] * D;
@@ -297,27 +342,38 @@ __global__ __launch_bounds__(256) void vqres_bwd_kernel(const T* __restrict__ dy
               dyt[t * D + j] = gr[j];
             }
         }
+      } else if constexpr (DEP) {
+        if (live && mine != nullptr)             // a row of the tile past its depth: zeros, never a stale slot
+          for (int j = 0; j < D; ++j) xt[t * D + j] = dyt[t * D + j] = 0.f;
       }
       __syncthreads();
       const float* cc = CBL ? vqresb_lds : c;
       float dmin = INFINITY;
-      for (int k = 0; k < L; ++k) {
-        const float d = vqb_score<DP, CBL>(xr, cc + k * ld, D);
-        if (d < dmin) dmin = d;
-      }
       float sum = 0.f, pd = 0.f;
-      for (int k = 0; k < L; ++k) {
-        const float* ck = cc + k * ld;
-        const float e = vq_weight(vqb_score<DP, CBL>(xr, ck, D), dmin, sigma);
-        float q = vqb_dot<DP, CBL>(gr, ck, D);
-        if constexpr (GM != 0) q += dqr[k];
-        sum += e;
-        pd = __fmaf_rn(e, q, pd);
+      if (!DEP || act) {
+        for (int k = 0; k < L; ++k) {
+          const float d = vqb_score<DP, CBL>(xr, cc + k * ld, D);
+          if (d < dmin) dmin = d;
+        }
+        for (int k = 0; k < L; ++k) {
+          const float* ck = cc + k * ld;
+          const float e = vq_weight(vqb_score<DP, CBL>(xr, ck, D), dmin, sigma);
+          float q = vqb_dot<DP, CBL>(gr, ck, D);
+          if constexpr (GM != 0) q += dqr[k];
+          sum += e;
+          pd = __fmaf_rn(e, q, pd);
+        }
+        pd = pd / sum;                           // <p, dp>
       }
-      pd = pd / sum;                             // <p, dp>
-      for (int k0 = 0; k0 < L; k0 += KC) {
+      for (int k0 = 0; k0 < L; k0 += KC) {       // every thread: the reduction below holds barriers
         const int kc = L - k0 < KC ? L - k0 : KC;
         for (int kq = 0; kq < kc; ++kq) {
+          if constexpr (DEP) {
+            if (!act) {
+              if (mine != nullptr && live) pt[kq * (V + 1) + t] = ddt[kq * (V + 1) + t] = 0.f;
+              continue;
+            }
+          }
           const float* ck = cc + (k0 + kq) * ld;
           const float p = vq_weight(vqb_score<DP, CBL>(xr, ck, D), dmin, sigma) / sum;
           float q = vqb_dot<DP, CBL>(gr, ck, D);
@@ -361,11 +417,23 @@ __global__ __launch_bounds__(256) void vqres_bwd_kernel(const T* __restrict__ dy
   }
 }
 
-// both backward entry points.  grouped: G is checked; dhist [n][G][L] or NULL: NULL is exactly jpdse_vq_res_bwd's launch
-static int vqres_bwd_run(const char* who, const jpdse_vq_res_bwd_args* a, int G, const float* dhist, bool grouped = false) {
+// the depth calls: G vectors per cell, depth [M / G]
+static int vqres_depth_check(const char* who, int M, int G, const int32_t* depth) {
+  JPDSE_REQUIRE(G >= 1, "%s: G = %d vectors per cell (at least 1)", who, G);
+  JPDSE_REQUIRE(M % G == 0, "%s: G = %d does not divide M = %d", who, G, M);
+  JPDSE_REQUIRE(depth != nullptr, "%s: null pointer (depth)", who);
+  return JPDSE_OK;
+}
+
+// the backward entry points.  grouped: G is checked; dhist [n][G][L] or NULL: NULL is exactly jpdse_vq_res_bwd's launch.  deep: G is
+// the cell size of depth [M / G] (no dhist)
+static int vqres_bwd_run(const char* who, const jpdse_vq_res_bwd_args* a, int G, const float* dhist, bool grouped = false,
+                         const int32_t* depth = nullptr, bool deep = false) {
   if (int rc = vq_res_check(who, a->dtype, a->M, a->D, a->L, a->S, a->n_stages)) return rc;
   JPDSE_REQUIRE(a->n_stages >= 1, "%s: n_stages = %d (1 .. S = %d)", who, a->n_stages, a->S);
   JPDSE_REQUIRE(isfinite(a->sigma) && a->sigma > 0.f, "%s: sigma is %g (a finite value > 0)", who, (double)a->sigma);
+  if (deep)
+    if (int rc = vqres_depth_check(who, a->M, G, depth)) return rc;
   if (grouped) {
     if (int rc = vqr_group_check(who, a->M, a->L, G)) return rc;
     JPDSE_REQUIRE((long long)a->n_stages * G * a->L <= 65536, "%s: n_stages * G * L = %lld (at most 65536)", who,
@@ -390,17 +458,77 @@ static int vqres_bwd_run(const char* who, const jpdse_vq_res_bwd_args* a, int G,
         using T = decltype(tag);
         constexpr int DPv = decltype(dp)::value;
         constexpr bool CBLv = decltype(cbl)::value;
-        auto go = [&](auto kernel) {
+        auto go = [&](auto kernel, auto dep) {
           return vq_launch(who, kernel, nb, V, lds, a->stream, cptr<T>(a->dy), cptr<T>(a->x), a->books, a->index, dhist, M, D, L, n, G,
-                           a->sigma, vec, mptr<T>(a->dx), partial);
+                           a->sigma, vec, mptr<T>(a->dx), partial, dep);
         };
-        if (gm == 1) return go(vqres_bwd_kernel<T, DPv, CBLv, 1>);
-        if (gm == 2) return go(vqres_bwd_kernel<T, DPv, CBLv, 2>);
-        return go(vqres_bwd_kernel<T, DPv, CBLv, 0>);
+        if (deep) return go(vqres_bwd_kernel<T, DPv, CBLv, 0, true>, VqDepth<true>{depth, G});
+        if (gm == 1) return go(vqres_bwd_kernel<T, DPv, CBLv, 1, false>, VqDepth<false>{});
+        if (gm == 2) return go(vqres_bwd_kernel<T, DPv, CBLv, 2, false>, VqDepth<false>{});
+        return go(vqres_bwd_kernel<T, DPv, CBLv, 0, false>, VqDepth<false>{});
       }))
     return rc;
   if (partial == nullptr) return JPDSE_OK;
   return vq_launch(who, vq_merge_kernel, ew_blocks(n * L * D), 256, 0, a->stream, partial, nb, n * L * D, 1.f, a->dbooks);
+}
+
+// jpdse_vq_res_rows_fwd and its depth form: the same grid, tile and LDS
+static int vqres_rows_fwd_run(const char* who, const jpdse_vq_res_rows_fwd_args* a, int G, const int32_t* depth, bool deep) {
+  if (int rc = vq_res_check(who, a->dtype, a->M, a->D, a->L, a->S, a->n_stages)) return rc;
+  JPDSE_REQUIRE(a->n_stages >= 1, "%s: n_stages = %d (1 .. S = %d)", who, a->n_stages, a->S);
+  if (deep)
+    if (int rc = vqres_depth_check(who, a->M, G, depth)) return rc;
+  JPDSE_REQUIRE(a->x && a->books && a->y && a->index, "%s: null pointer", who);
+  const int M = a->M, D = a->D, L = a->L;
+  const int vec = vqb_vec(a->dtype, D, {a->x, a->y});
+  const size_t lds = vqb_cb_lds(D, L) ? (size_t)L * vqb_dp(D) * sizeof(float) : 0;
+  return vqb_dispatch(a->dtype, D, L, [&](auto tag, auto dp, auto cbl) {
+    using T = decltype(tag);
+    auto go = [&](auto kernel, auto dep) {
+      return vq_launch(who, kernel, vqb_blocks(M, 256), 256, lds, a->stream, cptr<T>(a->x), a->books, M, D, L, a->n_stages, vec,
+                       mptr<T>(a->y), a->index, dep);
+    };
+    if (deep) return go(vqres_rows_fwd_kernel<T, decltype(dp)::value, decltype(cbl)::value, true>, VqDepth<true>{depth, G});
+    return go(vqres_rows_fwd_kernel<T, decltype(dp)::value, decltype(cbl)::value, false>, VqDepth<false>{});
+  });
+}
+
+static int vqres_decode_run(const char* who, const jpdse_vq_res_decode_args* a, int G, const int32_t* depth, bool deep) {
+  if (int rc = vq_res_check(who, a->dtype, a->M, a->D, a->L, a->S, a->n_stages)) return rc;
+  JPDSE_REQUIRE(a->n_stages >= 1, "%s: n_stages = %d (1 .. S = %d)", who, a->n_stages, a->S);
+  if (deep)
+    if (int rc = vqres_depth_check(who, a->M, G, depth)) return rc;
+  JPDSE_REQUIRE(a->index && a->books && a->y && a->status, "%s: null pointer", who);
+  return by_dtype(a->dtype, [&](auto tag) {
+    using T = decltype(tag);
+    auto go = [&](auto kernel, auto dep) {
+      return vq_launch(who, kernel, ew_blocks((long long)a->M * a->D), 256, 0, a->stream, a->index, a->books, a->M, a->D, a->L,
+                       a->n_stages, mptr<T>(a->y), a->status, dep);
+    };
+    if (deep) return go(vqres_decode_kernel<T, true>, VqDepth<true>{depth, G});
+    return go(vqres_decode_kernel<T, false>, VqDepth<false>{});
+  });
+}
+
+// ---- the depth map -----------------------------------------------------------------------------------------------
+// depth[n][cy][cx] = max over the step x step pixels of the cell of table[class], the class of a pixel by cost_class.h's rule (its
+// label when that is an integer in [0, n_classes), NaN excluded); any other pixel takes def.  One thread per cell.
+__global__ __launch_bounds__(256) void vqres_depth_map_kernel(const float* __restrict__ label, const int* __restrict__ table, int N, int H,
+                                                             int W, int step, int n_classes, int def, int* __restrict__ depth) {
+  const int h = H / step, w = W / step;
+  const long long cells = (long long)N * h * w;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < cells; i += (long long)gridDim.x * 256) {
+    const int cx = (int)(i % w), cy = (int)((i / w) % h), n = (int)(i / ((long long)w * h));
+    const float* lab_n = label + (long long)n * H * W;
+    int best = INT_MIN;
+    for (int dy = 0; dy < step; ++dy)
+      for (int dx = 0; dx < step; ++dx) {
+        const float lab = lab_n[(long long)(cy * step + dy) * W + cx * step + dx];
+        const int v = (lab >= 0.f && lab < (float)n_classes && lab == floorf(lab)) ? table[(int)lab] : def;
+        best = v > best ? v : best;
+      }
+    depth[i] = best;
+  }
 }
 
 }  // namespace jpdse
@@ -440,29 +568,22 @@ int jpdse_vq_res_fwd(const jpdse_vq_res_fwd_args* a) {
 
 int jpdse_vq_res_rows_fwd(const jpdse_vq_res_rows_fwd_args* a) {
   JPDSE_REQUIRE(a != nullptr, "vq_res_rows_fwd: null argument struct");
-  if (int rc = vq_res_check("vq_res_rows_fwd", a->dtype, a->M, a->D, a->L, a->S, a->n_stages)) return rc;
-  JPDSE_REQUIRE(a->n_stages >= 1, "vq_res_rows_fwd: n_stages = %d (1 .. S = %d)", a->n_stages, a->S);
-  JPDSE_REQUIRE(a->x && a->books && a->y && a->index, "vq_res_rows_fwd: null pointer");
-  const int M = a->M, D = a->D, L = a->L;
-  const int vec = vqb_vec(a->dtype, D, {a->x, a->y});
-  const size_t lds = vqb_cb_lds(D, L) ? (size_t)L * vqb_dp(D) * sizeof(float) : 0;
-  return vqb_dispatch(a->dtype, D, L, [&](auto tag, auto dp, auto cbl) {
-    using T = decltype(tag);
-    return vq_launch("vq_res_rows_fwd", vqres_rows_fwd_kernel<T, decltype(dp)::value, decltype(cbl)::value>, vqb_blocks(M, 256), 256,
-                     lds, a->stream, cptr<T>(a->x), a->books, M, D, L, a->n_stages, vec, mptr<T>(a->y), a->index);
-  });
+  return vqres_rows_fwd_run("vq_res_rows_fwd", a, 1, nullptr, false);
+}
+
+int jpdse_vq_res_rows_fwd_depth(const jpdse_vq_res_rows_fwd_depth_args* a) {
+  JPDSE_REQUIRE(a != nullptr, "vq_res_rows_fwd_depth: null argument struct");
+  return vqres_rows_fwd_run("vq_res_rows_fwd_depth", &a->fwd, a->G, a->depth, true);
 }
 
 int jpdse_vq_res_decode(const jpdse_vq_res_decode_args* a) {
   JPDSE_REQUIRE(a != nullptr, "vq_res_decode: null argument struct");
-  if (int rc = vq_res_check("vq_res_decode", a->dtype, a->M, a->D, a->L, a->S, a->n_stages)) return rc;
-  JPDSE_REQUIRE(a->n_stages >= 1, "vq_res_decode: n_stages = %d (1 .. S = %d)", a->n_stages, a->S);
-  JPDSE_REQUIRE(a->index && a->books && a->y && a->status, "vq_res_decode: null pointer");
-  return by_dtype(a->dtype, [&](auto tag) {
-    using T = decltype(tag);
-    return vq_launch("vq_res_decode", vqres_decode_kernel<T>, ew_blocks((long long)a->M * a->D), 256, 0, a->stream, a->index, a->books,
-                     a->M, a->D, a->L, a->n_stages, mptr<T>(a->y), a->status);
-  });
+  return vqres_decode_run("vq_res_decode", a, 1, nullptr, false);
+}
+
+int jpdse_vq_res_decode_depth(const jpdse_vq_res_decode_depth_args* a) {
+  JPDSE_REQUIRE(a != nullptr, "vq_res_decode_depth: null argument struct");
+  return vqres_decode_run("vq_res_decode_depth", &a->dec, a->G, a->depth, true);
 }
 
 int jpdse_vq_res_bwd(const jpdse_vq_res_bwd_args* a) {
@@ -473,6 +594,24 @@ int jpdse_vq_res_bwd(const jpdse_vq_res_bwd_args* a) {
 int jpdse_vq_res_bwd_grouped(const jpdse_vq_res_bwd_grouped_args* a) {
   JPDSE_REQUIRE(a != nullptr, "vq_res_bwd_grouped: null argument struct");
   return vqres_bwd_run("vq_res_bwd_grouped", &a->bwd, a->G, a->dhist, true);
+}
+
+int jpdse_vq_res_bwd_depth(const jpdse_vq_res_bwd_depth_args* a) {
+  JPDSE_REQUIRE(a != nullptr, "vq_res_bwd_depth: null argument struct");
+  return vqres_bwd_run("vq_res_bwd_depth", &a->bwd, a->G, nullptr, false, a->depth, true);
+}
+
+int jpdse_vq_depth_map(const jpdse_vq_depth_map_args* a) {
+  JPDSE_REQUIRE(a != nullptr, "vq_depth_map: null argument struct");
+  JPDSE_REQUIRE(a->N >= 1 && a->H >= 1 && a->W >= 1, "vq_depth_map: N, H, W = %d, %d, %d (at least 1 each)", a->N, a->H, a->W);
+  JPDSE_REQUIRE(a->step >= 1 && a->H % a->step == 0 && a->W % a->step == 0, "vq_depth_map: step = %d does not divide H = %d and W = %d",
+                a->step, a->H, a->W);
+  JPDSE_REQUIRE((long long)a->N * a->H * a->W < (1LL << 31), "vq_depth_map: N * H * W = %lld (below 2^31)", (long long)a->N * a->H * a->W);
+  JPDSE_REQUIRE(a->n_classes >= 0 && a->n_classes <= 65536, "vq_depth_map: n_classes = %d (0 .. 65536)", a->n_classes);
+  JPDSE_REQUIRE(a->label && a->depth && (a->table || a->n_classes == 0), "vq_depth_map: null pointer");
+  const long long cells = (long long)a->N * (a->H / a->step) * (a->W / a->step);
+  return vq_launch("vq_depth_map", vqres_depth_map_kernel, ew_blocks(cells), 256, 0, a->stream, a->label, a->table, a->N, a->H, a->W,
+                   a->step, a->n_classes, a->default_depth, a->depth);
 }
 
 }  // extern "C"

@@ -11,7 +11,7 @@ import contextlib
 import torch
 
 from jpdse_hip import ops
-from ctu.utils import bitstream, entropy, vqplane, vqstages, vqstream
+from ctu.utils import bitstream, entropy, vqdepth, vqplane, vqstages, vqstream
 
 
 def check_ec_arguments(rate_lambda, n_iter):
@@ -49,6 +49,11 @@ class _Codec:
   def rate_value(self):
     """fp32 [1] on the device: the rate term of the last armed forward, unscaled."""
     return self.netE._bottleneck.rate_value
+
+  def depth_term(self, label):
+    """The context in which the model runs the encoder, its code and the receiver's half for the device label map `label`: only
+    the codec of opt.vq_class_stages arms anything (VQDepthCodec)."""
+    return contextlib.nullcontext()
 
 
 class BinaryCodec(_Codec):
@@ -275,6 +280,7 @@ class VQStagesCodec(VQIndexCodec):
   The model picks this class; CODECS stays by quantizer."""
 
   RATE_OPTION = 'lambda_vq_stage_rate'
+  truncate = staticmethod(vqstages.truncate_stages)      # a blob cut after n stages: host only
 
   def _n_stages(self):
     return self.netE.vq_stages
@@ -362,6 +368,108 @@ class VQStagesCodec(VQIndexCodec):
     stages = vqstages.parse_stages(payloads[0], 'file_rates')[0]
     raw = vqstream.HEADER_BYTES + vqstream.packed_bytes(self.netE.vq_code_len(H, W), self.netE._vq.n_center)
     return coded, 8.0 * stages * raw / (H * W)
+
+
+class VQDepthCodec(VQStagesCodec):
+  """The residual bottleneck's code under opt.vq_class_stages: the stage depth of a code cell follows the classes
+  of the pixels it covers, derived on both sides from the label map -- no side information.  `class_stages` = (table, default) of
+  model_options.parse_vq_class_stages.  The code is VQStagesCodec's with -1 past a cell's depth, the files are .jpdm blobs
+  (ctu.utils.vqdepth).  depth_term(label) arms the bottleneck layer for one call; the host checks of payloads use the numpy
+  statement of the same rule on x_dict's label map, so a blob of another label map is refused before any device call."""
+
+  class_stages = None
+  _device_table = None      # (class_stages, device, int32 table on that device): made on first use, remade when either changes
+  truncate = staticmethod(vqdepth.truncate_depth_stages)
+
+  def _step(self):
+    return 1 << self.netE.n_downsampling
+
+  def device_depth(self, label):
+    """int32 [N, h, w] on the device (ops.vq_depth_map)."""
+    table, default = self.class_stages
+    cached = self._device_table
+    if cached is None or cached[0] is not self.class_stages or cached[1] != label.device:
+      cached = self._device_table = (self.class_stages, label.device, torch.tensor(table, dtype=torch.int32, device=label.device))
+    return ops.vq_depth_map(label, cached[2], default, self._step())
+
+  def host_depth(self, x_dict):
+    """int64 numpy [N, h, w]: the same rule on the host."""
+    table, default = self.class_stages
+    return vqdepth.depth_map_host(x_dict['label'], table, default, self._step())
+
+  @contextlib.contextmanager
+  def depth_term(self, label):
+    layer = self.netE._bottleneck
+    layer.depth = self.device_depth(label).view(-1)
+    try:
+      yield
+    finally:
+      layer.depth = None
+
+  def check_payloads(self, blobs, x_dict, who):
+    geo = N, H, W, code_len, L, groups = self.geometry(x_dict, who)
+    S = self._n_stages()
+    if not isinstance(blobs, (list, tuple)) or len(blobs) != N:
+      raise ValueError('%s: the blobs must be what get_coded returns: a list of %d .jpdm bytes objects, one per '
+                       'label map' % (who, N))
+    depth = self.host_depth(x_dict)
+    counts = []
+    for j, b in enumerate(blobs):                 # every header, and the counts against this label map's depths, on the host
+      Sb, n, cl, Lb, _, _ = vqdepth.parse_depth_stages(b, '%s: blob %d' % (who, j), depth=depth[j])
+      if Lb != L:
+        raise ValueError('%s: blob %d was coded for n_center %d, the code book has %d' % (who, j, Lb, L))
+      if n * cl != code_len:
+        raise ValueError('%s: blob %d holds %d x %d indices per stage, a %d x %d label map carries %d'
+                         % (who, j, n, cl, H, W, code_len))
+      if Sb > S:
+        raise ValueError('%s: blob %d holds %d stages, the model (vq_stages) has %d' % (who, j, Sb, S))
+      counts.append(Sb)
+    if len(set(counts)) > 1:
+      raise ValueError('%s: the blobs of one call must hold the same stage count, got %s' % (who, counts))
+    return geo + (depth,)
+
+  def features_of_code(self, code, geo, device, who):
+    """Runs inside depth_term: the layer's depth says which indices count; -1 (or anything) past it is not read."""
+    _, H, W, _, L, groups = geo[:6]
+
+    def features():
+      index = code.to(device(), non_blocking=True)
+      n = int(index.shape[1])
+      depth = self.netE._bottleneck.depth.view(index.shape[0], 1, -1).clamp(1, self._n_stages())
+      inside = torch.arange(n, device=index.device).view(1, n, 1) < depth.repeat_interleave(groups, dim=2)
+      if bool((((index < 0) | (index >= L)) & inside).any()):
+        raise ValueError('%s: an index outside [0, %d) inside its cell\'s depth' % (who, L))
+      y, _ = self.netE.decode_vq_code(index.clamp(-1, L).to(torch.int32).contiguous(), H, W)
+      return y
+
+    return features
+
+  def features_of_payloads(self, blobs, geo, device, who):
+    code_len, depth = geo[3], geo[6]
+
+    def features():
+      code = torch.stack([vqdepth.read_depth_stages(bytes(b), depth[j], device()).view(-1, code_len)
+                          for j, b in enumerate(blobs)], dim=0)
+      return self.features_of_code(code, geo, device, who)()
+
+    return features
+
+  def payloads(self, code, x_dict):
+    """One .jpdm blob per image: stage s holds the cells with depth > s, in (C / D) * 8 streams as VQIndexCodec writes its one."""
+    _, _, _, code_len, L, groups = self.geometry(x_dict, 'get_coded')
+    depth = self.host_depth(x_dict)
+    return [vqdepth.write_depth_stages(None, code[i].reshape(code.shape[1], 1, code_len).contiguous(), depth[i], L, groups,
+                                       n_streams=groups * self.INDEX_STREAMS_PER_GROUP) for i in range(code.shape[0])]
+
+  def file_rates(self, payloads, H, W):
+    """(coded bpp, raw bpp), batch means: the .jpdm blobs, and the packed-index files of the indices they hold (nb bits each
+    + one .jpdv header per non-empty stage)."""
+    coded = sum(8.0 * len(p) / (H * W) for p in payloads) / len(payloads)
+    raw, groups, L = 0.0, self.netE._vq.cout // self.netE._vq.center_size, self.netE._vq.n_center
+    for p in payloads:
+      counts = vqdepth.parse_depth_stages(p, 'file_rates')[4]
+      raw += sum(vqstream.HEADER_BYTES + vqstream.packed_bytes(c * groups, L) for c in counts if c > 0)
+    return coded, 8.0 * raw / len(payloads) / (H * W)
 
 
 CODECS = {'binarizer': BinaryCodec, 's2hvq': VQIndexCodec}

@@ -1,11 +1,13 @@
 """The coded-stream and receiver calls of Pix2PixHDModel (extensions: the reference stops at get_code / get_eval_rate): the
 encoder's code in its forms, its rate figures, the entropy-coded files, the coded label and instance maps, and the receiver
 that reconstructs an image from them.  DESIGN.md 4.4, 4.8 - 4.10, 4.12, 4.15 - 4.17, 4.19 and 4.20."""
+import contextlib
+
 import torch
 
 from jpdse_hip import F32, ops
 from ctu.utils import semantics as semantics_file
-from ctu.models.codec import VQIndexCodec, VQStagesCodec, check_ec_arguments
+from ctu.models.codec import VQDepthCodec, VQIndexCodec, VQStagesCodec, check_ec_arguments
 
 
 class CodedCalls(object):
@@ -59,7 +61,8 @@ class CodedCalls(object):
     """The encoder's eval-mode code of x_dict (the decoded frame with --use_compressed) in the codec's form."""
     pre = self.preprocess(x_dict, build_base=False)
     if isinstance(codec, VQStagesCodec):
-      return self._encoder_eval(lambda: codec.code(pre['src'], stages=stages))
+      with codec.depth_term(pre['label']):      # opt.vq_class_stages (DESIGN.md 4.27): -1 past a cell's depth
+        return self._encoder_eval(lambda: codec.code(pre['src'], stages=stages))
     if rate_lambda == 0:
       return self._encoder_eval(lambda: codec.code(pre['src']))
     return self._encoder_eval(lambda: codec.code(pre['src'], rate_lambda, n_iter))
@@ -190,7 +193,8 @@ class CodedCalls(object):
   def _generate_from_code(self, features, x_dict, N, H, W):
     """The receiver's device work, shared by decode and decode_coded: features() gives the encoder's output from the code."""
     label, inst = self._semantics(x_dict)
-    vis = None if self.zero_vis else features()      # --zero_vis: nothing visual reaches the generator, the code is not read
+    with self.codec.depth_term(label) if self.codec is not None else contextlib.nullcontext():
+      vis = None if self.zero_vis else features()    # --zero_vis: nothing visual reaches the generator, the code is not read
     base = None if self.zero_sem else ops.onehot_edge(label, inst, self.n_onehot, self.label_nc + self.feat_nc, self.cdtype)
     fake, _ = self.netG.fwd(self._g_input_from_vis(vis, base, N, H, W))
     return fake, label
@@ -237,8 +241,12 @@ class CodedCalls(object):
 
   # ---- the entropy-constrained code of the residual bottleneck (extension) ------------------------------------
   def _stages_codec(self, who, instead):
-    """The residual bottleneck's codec, or the refusal that names the one-stage call to use.  Host only."""
+    """The residual bottleneck's codec, or the refusal that names the one-stage call to use.  With opt.vq_class_stages the
+    entropy-constrained code and the per-stage histograms are refused (they have no depth form).  Host only."""
     codec = self._vq_codec(who)
+    if isinstance(codec, VQDepthCodec):
+      raise ValueError('%s: not available with opt.vq_class_stages: the entropy-constrained code and the stage histograms are '
+                       'built for a uniform stage depth' % who)
     if not isinstance(codec, VQStagesCodec):
       raise ValueError('%s: a call of the residual bottleneck, this model has vq_stages = 1: use %s' % (who, instead))
     return codec

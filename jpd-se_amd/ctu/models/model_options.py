@@ -175,6 +175,57 @@ ModelOptions = collections.namedtuple('ModelOptions', [
     'vq_stages', 'vq_train_stages'])
 
 
+def parse_vq_class_stages(spec, vq_stages, n_classes):
+  """opt.vq_class_stages, a string such as '24:3,26:3,*:1' -- class id : stage depth, '*' the depth of every class
+  not named (default: vq_stages) -> (table, default): table a tuple of n_classes depths, default the depth of a pixel whose label
+  is no class of the table.  None for None.  ValueError naming the field for a malformed entry, a class outside [0, n_classes), a
+  class or '*' named twice, and a depth outside 1 .. vq_stages."""
+  if spec is None:
+    return None
+  if not isinstance(spec, str) or not spec.strip():
+    raise ValueError("vq_class_stages must be a string such as '24:3,26:3,*:1' (class:depth, '*' for the others), got %r" % (spec,))
+  named, default = {}, None
+  for item in spec.split(','):
+    parts = item.strip().split(':')
+    if len(parts) != 2 or not parts[1].strip().isdigit() or not (parts[0].strip() == '*' or parts[0].strip().isdigit()):
+      raise ValueError("vq_class_stages: malformed entry %r in %r (class:depth, '*' for the others)" % (item, spec))
+    key, depth = parts[0].strip(), int(parts[1])
+    if not 1 <= depth <= vq_stages:
+      raise ValueError('vq_class_stages: depth %d of %r is outside 1 .. vq_stages = %d' % (depth, key, vq_stages))
+    if key == '*':
+      if default is not None:
+        raise ValueError("vq_class_stages: malformed entry %r in %r ('*' is named twice)" % (item, spec))
+      default = depth
+      continue
+    if not 0 <= int(key) < n_classes:
+      raise ValueError('vq_class_stages: malformed entry %r in %r (class %d is outside the %d classes of the label map)'
+                       % (item, spec, int(key), n_classes))
+    if int(key) in named:
+      raise ValueError('vq_class_stages: malformed entry %r in %r (class %d is named twice)' % (item, spec, int(key)))
+    named[int(key)] = depth
+  default = vq_stages if default is None else default
+  return tuple(named.get(k, default) for k in range(n_classes)), default
+
+
+def resolve_vq_class_stages(opt):
+  """(table, default) of opt.vq_class_stages, or None when the field is absent or None: today's model.  The refusals that need the
+  other options: vq_stages == 1, lambda_vq_stage_rate > 0, --zero_sem.  resolve_model_options calls this after
+  its own checks of those options, so ModelOptions stays the record it was; the model's constructor reads the value here."""
+  spec = getattr(opt, 'vq_class_stages', None)
+  if spec is None:
+    return None
+  vq_stages = getattr(opt, 'vq_stages', 1)
+  if vq_stages == 1 or getattr(opt, 'encoder_quantizer', 'binarizer') != 's2hvq':
+    raise ValueError('vq_class_stages sets the stage depth of the residual bottleneck per class: it needs --encoder_quantizer s2hvq '
+                     'and vq_stages > 1')
+  if float(getattr(opt, 'lambda_vq_stage_rate', 0.0) or 0.0) > 0.0:
+    raise ValueError('vq_class_stages cannot be combined with lambda_vq_stage_rate > 0: the rate term has no depth form')
+  if getattr(opt, 'zero_sem', False):
+    raise ValueError('vq_class_stages cannot be combined with --zero_sem: the generator sees no semantics there')
+  n_onehot = opt.num_labels + 1 if getattr(opt, 'contain_dontcare_label', False) else opt.num_labels
+  return parse_vq_class_stages(spec, vq_stages, n_onehot)
+
+
 def resolve_model_options(opt):
   """opt -> ModelOptions, or the refusal.  The order of the checks is part of the contract: first everything outside the
   accelerated path in ONE NotImplementedError, then distortion_loss_fn, lambda_rate, lambda_vq_rate, vq_context_coder,
@@ -281,6 +332,7 @@ def resolve_model_options(opt):
                      'bottleneck takes --lambda_vq_rate)')
   if lambda_vq_stage_rate > 0.0 and zero_vis:
     raise ValueError('lambda_vq_stage_rate > 0 needs an encoder that runs: it cannot be combined with --zero_vis')
+  resolve_vq_class_stages(opt)      # opt.vq_class_stages: its refusals; the value is the constructor's to read
   # semantics-weighted distortion: (class table, edge weight), or None when every weight is 1 -- the
   # step then takes the plain l1 / mse path
   n_onehot = opt.num_labels + 1 if g('contain_dontcare_label') else opt.num_labels

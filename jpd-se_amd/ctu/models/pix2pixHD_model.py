@@ -32,9 +32,9 @@ from jpdse_hip.ops import Act
 from jpdse_hip.optim import FusedAdam
 from jpdse_hip.layers import PackBatcher
 from ctu.utils.image_pool import ImagePool
-from ctu.models.codec import CODECS, VQStagesCodec
+from ctu.models.codec import CODECS, VQDepthCodec, VQStagesCodec
 from ctu.models.coded_calls import CodedCalls
-from ctu.models.model_options import add_model_options, parse_class_distortion_weights, resolve_model_options  # noqa: F401
+from ctu.models.model_options import add_model_options, parse_class_distortion_weights, resolve_model_options, resolve_vq_class_stages  # noqa: F401
 from ctu.models.pix2pixHD_networks.base_model import BaseModel
 from ctu.models.pix2pixHD_networks import networks
 
@@ -87,7 +87,11 @@ class Pix2PixHDModel(CodedCalls, BaseModel):
     if self.netE is not None and self.netE.quantizer is not None:
       # more than one stage of the vector quantizer (opt.vq_stages): the subclass that writes .jpdr files
       staged = self.netE.quantizer == 's2hvq' and o.vq_stages > 1
-      self.codec = (VQStagesCodec if staged else CODECS[self.netE.quantizer])(self.netE, self.cdtype)
+      # opt.vq_class_stages: the stage depth of a code cell follows its classes; None: today's model
+      class_stages = resolve_vq_class_stages(opt)
+      kind = VQDepthCodec if class_stages is not None else (VQStagesCodec if staged else CODECS[self.netE.quantizer])
+      self.codec = kind(self.netE, self.cdtype)
+      self.codec.class_stages = class_stages
       self.rate_weight = getattr(self, self.codec.RATE_OPTION)
       if self.vq_context_coder:
         self.codec.context_coder = True
@@ -247,7 +251,8 @@ class Pix2PixHDModel(CodedCalls, BaseModel):
     the --zero_vis / --zero_sem lanes blanked (:583-587; --zero_ins is already in the edge lane, see preprocess)."""
     vis = None if self.zero_vis else pre['src']      # --zero_vis: nothing visual reaches the generator
     if vis is not None and self.netE is not None:
-      vis, _ = self._encoder_eval(lambda: self.netE.fwd(vis))
+      with self.codec.depth_term(pre['label']) if self.codec is not None else contextlib.nullcontext():
+        vis, _ = self._encoder_eval(lambda: self.netE.fwd(vis))
     return self._g_input_from_vis(vis, pre['base'], pre['real'].N, pre['real'].H, pre['real'].W)
 
   def _g_input_from_vis(self, vis, base, N, H, W):
@@ -394,7 +399,8 @@ class Pix2PixHDModel(CodedCalls, BaseModel):
         # --lambda_rate / --lambda_vq_rate: a training step's forward also asks the bottleneck for its rate
         # term and the gradient, scaled like the distortion gradient: the weight, the kernel's mean over the local batch, and
         # the ranks' average in Adam's grad_scale
-        with self.codec.rate_term(self.rate_weight, B, H, W) if rate_on else contextlib.nullcontext():
+        with self.codec.rate_term(self.rate_weight, B, H, W) if rate_on else contextlib.nullcontext(), \
+            self.codec.depth_term(label) if self.codec is not None else contextlib.nullcontext():
           vis, e_ctx = self.netE.fwd(src)
         if self.netE.training:
           self.codec_draw += 1

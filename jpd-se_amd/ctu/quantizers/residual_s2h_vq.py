@@ -26,20 +26,24 @@ class _ResidualQuantize(torch.autograd.Function):
   ops.vq_res_bwd from the saved x, books and indices.  The books beyond `stages` get a zero gradient."""
 
   @staticmethod
-  def forward(ctx, x, books, sigma, stages):
+  def forward(ctx, x, books, sigma, stages, depth=None, groups=1):
     x, books = x.contiguous(), books.contiguous()
-    y, index = ops.vq_res_rows_fwd(x, books, stages)
+    y, index = ops.vq_res_rows_fwd(x, books, stages, depth=depth, groups=groups)
     ctx.save_for_backward(x, books, index)
-    ctx.sigma = sigma
+    ctx.sigma, ctx.depth, ctx.groups = sigma, depth, groups
     ctx.mark_non_differentiable(index)
     return y, index
 
   @staticmethod
   def backward(ctx, dy, _dindex):
     x, books, index = ctx.saved_tensors
-    dx, dc = ops.vq_res_bwd(dy.contiguous(), x, books, index, ctx.sigma, want_dx=ctx.needs_input_grad[0],
-                            want_dc=ctx.needs_input_grad[1])
-    return dx, dc, None, None
+    if ctx.depth is None:
+      dx, dc = ops.vq_res_bwd(dy.contiguous(), x, books, index, ctx.sigma, want_dx=ctx.needs_input_grad[0],
+                              want_dc=ctx.needs_input_grad[1])
+    else:                                        # the per-row recursion of DESIGN.md 4.27
+      dx, dc = ops.vq_res_bwd(dy.contiguous(), x, books, index, ctx.sigma, want_dx=ctx.needs_input_grad[0],
+                              want_dc=ctx.needs_input_grad[1], groups=ctx.groups, depth=ctx.depth)
+    return dx, dc, None, None, None, None
 
 
 class _ResidualRate(torch.autograd.Function):
@@ -130,12 +134,31 @@ class ResidualS2HVQ(nn.Module):
     _on_gpu(self._code_books, 'the code books')
     return x.contiguous().view(x.size(0) * code_len, self._center_size)
 
-  def quantize(self, x, code_len, stages=None, hard_forward=True):
+  def _depth(self, depth, groups, M):
+    """(depth int32 [M / groups] contiguous or None, groups) of a depth= / groups= pair, checked on the host."""
+    if depth is None:
+      if groups != 1:
+        raise ValueError('groups is the number of vectors of a depth cell: it comes with depth=, got groups = {!r} alone'.format(groups))
+      return None, 1
+    if isinstance(groups, bool) or not isinstance(groups, int) or groups < 1 or M % groups != 0:
+      raise ValueError('groups must be an int that divides n * code_len = {}, got {!r}'.format(M, groups))
+    if not torch.is_tensor(depth) or depth.dtype not in (torch.int32, torch.int64) or depth.numel() != M // groups:
+      raise ValueError('depth must be an int32 or int64 tensor of n * code_len / groups = {} cells, got {}'.format(
+          M // groups, (depth.dtype, tuple(depth.shape)) if torch.is_tensor(depth) else type(depth).__name__))
+    return depth.reshape(-1).to(torch.int32).contiguous(), groups      # a map on the CPU fails ops' device check with x's
+
+  def quantize(self, x, code_len, stages=None, hard_forward=True, depth=None, groups=1):
     """x [n, d], code_len dividing d with d // code_len == center_size -> (y [n, d] in x's dtype, code int64 [S', n, code_len]) of
     the first `stages` (default: all) stages, in one kernel.  Training mode: differentiable in x and the books, the gradient
     the soft form's at every stage; books beyond `stages` get a zero gradient.  Eval mode: nothing saved.  The soft forward
-    exists for one stage only (there it is S2HVQ.quantize's): with more it raises NotImplementedError before any device work."""
+    exists for one stage only (there it is S2HVQ.quantize's): with more it raises NotImplementedError before any device work.
+    depth / groups: depth an int tensor of n * code_len / groups cells, values 1 .. S (clamped); vector m of the
+    [n * code_len, center_size] matrix lies in cell m // groups and takes its first min(stages, depth) stages; code is -1 past a
+    vector's depth and the gradient is the per-row recursion's.  Hard forward only."""
     n_st = self._stages(stages)
+    depth, groups = self._depth(depth, groups, x.size(0) * code_len if torch.is_tensor(x) and x.dim() == 2 else 0)
+    if depth is not None and not hard_forward:
+      raise NotImplementedError('ResidualS2HVQ.quantize: a depth map goes with the hard forward only')
     if not hard_forward and self.n_stages > 1:
       raise NotImplementedError('ResidualS2HVQ.quantize: the soft forward is built for one stage, this module has %d' % self.n_stages)
     xm = self._vectors(x, code_len)
@@ -144,9 +167,9 @@ class ResidualS2HVQ(nn.Module):
       y, code, _ = S2HVQ.quantize(self, x, code_len, hard_forward=False)
       return y, code.unsqueeze(0)
     if self.training and torch.is_grad_enabled():
-      y, index = _ResidualQuantize.apply(xm, self._code_books, float(self._sigma), n_st)
+      y, index = _ResidualQuantize.apply(xm, self._code_books, float(self._sigma), n_st, depth, groups)
     else:
-      y, index = ops.vq_res_rows_fwd(xm.detach(), self._code_books.detach().contiguous(), n_st)
+      y, index = ops.vq_res_rows_fwd(xm.detach(), self._code_books.detach().contiguous(), n_st, depth=depth, groups=groups)
     return y.view(n, code_len * self._center_size), index.to(torch.int64).view(n_st, n, code_len)
 
   def rate(self, x, code_len, groups=1, denom=None, stages=None):
@@ -174,12 +197,14 @@ class ResidualS2HVQ(nn.Module):
                                 n_stages=n_st, want_grad=False)[0]
     return value.reshape(())
 
-  def encode(self, x, code_len, stages=None):
-    """The int64 code [S', n, code_len] of x [n, d].  Nothing is differentiable."""
+  def encode(self, x, code_len, stages=None, depth=None, groups=1):
+    """The int64 code [S', n, code_len] of x [n, d]; with depth / groups (see quantize) -1 past a vector's depth.  Nothing is
+    differentiable."""
     n_st = self._stages(stages)
+    depth, groups = self._depth(depth, groups, x.size(0) * code_len if torch.is_tensor(x) and x.dim() == 2 else 0)
     with torch.no_grad():
       xm = self._vectors(x, code_len).detach()
-      _, index = ops.vq_res_rows_fwd(xm, self._code_books.detach().contiguous(), n_st)
+      _, index = ops.vq_res_rows_fwd(xm, self._code_books.detach().contiguous(), n_st, depth=depth, groups=groups)
     return index.to(torch.int64).view(n_st, x.size(0), code_len)
 
   def _ec_groups(self, who, x, code_len, groups, n_st):
@@ -240,9 +265,11 @@ class ResidualS2HVQ(nn.Module):
       _, _, hist, _ = ops.vq_res_ec_assign(xm, self._code_books.detach().contiguous(), None, groups, n_st, want_y=False)
     return hist.to(torch.int64)
 
-  def decode(self, code, stages=None):
+  def decode(self, code, stages=None, depth=None, groups=1):
     """code int64 [S', n, code_len] -> float32 [n, code_len * center_size]: the sum of the centres of the first `stages` (default:
-    all S') stages, bit for bit quantize's y.  ValueError for an index outside [0, n_center) (this synchronises)."""
+    all S') stages, bit for bit quantize's y.  ValueError for an index outside [0, n_center) (this synchronises).
+    depth / groups (see quantize): vector m sums its first min(stages, depth) centres; what the code holds past a vector's depth
+    is neither read nor checked."""
     if not torch.is_tensor(code) or code.dim() != 3 or code.dtype != torch.int64 or not 1 <= code.size(0) <= self.n_stages:
       raise ValueError('code must be an int64 tensor (stages <= {}, n, code_len), got {}'.format(
           self.n_stages, (code.dtype, tuple(code.shape)) if torch.is_tensor(code) else type(code).__name__))
@@ -251,12 +278,18 @@ class ResidualS2HVQ(nn.Module):
       raise ValueError('stages must be an int in 1 .. {}, got {!r}'.format(code.size(0), stages))
     L = self._code_books.size(1)
     _rows_limit(code.size(1) * code.size(2), L)
+    depth, groups = self._depth(depth, groups, code.size(1) * code.size(2))      # host refusals first, then the device's
     _on_gpu(code, 'code')
     _on_gpu(self._code_books, 'the code books')
-    if bool(((code[:n_st] < 0) | (code[:n_st] >= L)).any()):     # before the cast to int32 could fold a far value into range
+    index = code[:n_st].reshape(n_st, -1)
+    bad = (index < 0) | (index >= L)
+    if depth is not None:                        # only inside the depth (the clamp is the device's); beyond it nothing is read
+      bad = bad & (torch.arange(n_st, device=code.device).view(n_st, 1) < depth.clamp(1, self.n_stages).repeat_interleave(groups))
+      index = index.clamp(-1, L)                 # so that the cast below cannot fold a far value into range
+    if bool(bad.any()):                          # before the cast to int32 could fold a far value into range
       raise ValueError('ResidualS2HVQ.decode: an index outside [0, {})'.format(L))
-    index = code[:n_st].reshape(n_st, -1).to(torch.int32).contiguous()
-    y, _ = ops.vq_res_decode(index, self._code_books.detach().contiguous(), n_st)
+    index = index.to(torch.int32).contiguous()
+    y, _ = ops.vq_res_decode(index, self._code_books.detach().contiguous(), n_st, depth=depth, groups=groups)
     return y.view(code.size(1), code.size(2) * self._center_size)
 
   def distortion(self, x, code_len):

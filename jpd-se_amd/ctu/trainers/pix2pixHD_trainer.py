@@ -156,7 +156,6 @@ class Pix2PixHDTrainer(BaseTrainer):
     pixel, batch mean) and `l1`, `mse`, `psnr`, `ms_ssim` of get_eval_metrics_decoded of that prefix.  One encoder run, one
     generator run per prefix.  rate_lambda > 0: the curve of the stream get_coded_stages_ec(x_dict, rate_lambda,
     n_iter) writes; the defaults take the plain code."""
-    from ctu.utils import vqstages
     from ctu.models.codec import check_ec_arguments
     self.eval()
     if check_ec_arguments(rate_lambda, n_iter) > 0:
@@ -170,8 +169,40 @@ class Pix2PixHDTrainer(BaseTrainer):
     rows = []
     for n in range(1, int(code.shape[1]) + 1):
       m = self.model.get_eval_metrics_decoded(code[:, :n].contiguous(), x_dict)
-      bpp = sum(8.0 * len(vqstages.truncate_stages(b, n)) / pixels for b in blobs) / len(blobs)
+      bpp = sum(8.0 * len(self.model.codec.truncate(b, n)) / pixels for b in blobs) / len(blobs)
       rows.append(dict(stages=n, bpp=bpp, l1=m['l1'], mse=m['mse'], psnr=m['psnr'], ms_ssim=m['ms_ssim']))
+    return rows
+
+  def _depth_codec(self, who):
+    from ctu.models.codec import VQDepthCodec
+    if not isinstance(self.model.codec, VQDepthCodec):
+      raise ValueError('%s: needs opt.vq_class_stages (DESIGN.md 4.27)' % who)
+    return self.model.codec
+
+  def get_stage_depth(self, x_dict):
+    """int64 [N, h, w] on the device: the stage depth of every code cell under opt.vq_class_stages -- the maximum
+    over the cell's pixels of the depth of the pixel's class -- as every call of the model derives it from x_dict's label map."""
+    codec = self._depth_codec('get_stage_depth')
+    with torch.no_grad():
+      label, _ = self.model._semantics(x_dict)
+      return codec.device_depth(label).to(torch.int64)
+
+  def get_depth_report(self, x_dict):
+    """A list of N dicts, one per image, of the .jpdm stream get_coded writes under opt.vq_class_stages: `cells` (cells per depth
+    1 .. vq_stages), `indices` and `bytes` per stage (the stage's .jpdv blob; 0 for a stage without a cell), `total_bytes` and
+    `bpp` of the whole file, headers included."""
+    from ctu.utils import vqdepth
+    codec = self._depth_codec('get_depth_report')
+    self.eval()
+    blobs = self.model.get_coded(x_dict)
+    depth = self.get_stage_depth(x_dict).cpu()
+    S, groups = self.model.vq_stages, codec.geometry(x_dict, 'get_depth_report')[5]
+    pixels = int(x_dict['image'].shape[-2]) * int(x_dict['image'].shape[-1])
+    rows = []
+    for j, b in enumerate(blobs):
+      _, _, _, _, counts, inner = vqdepth.parse_depth_stages(b, 'get_depth_report: blob %d' % j)
+      rows.append(dict(cells=[int((depth[j] == v).sum()) for v in range(1, S + 1)], indices=[c * groups for c in counts],
+                       bytes=[len(i) for i in inner], total_bytes=len(b), bpp=8.0 * len(b) / pixels))
     return rows
 
   def get_stage_code_ec(self, x_dict, rate_lambda, n_iter=2, stages=None):

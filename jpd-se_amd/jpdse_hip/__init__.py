@@ -277,6 +277,24 @@ class VqResBwdGroupedArgs(ctypes.Structure):
   _fields_ = [('bwd', VqResBwdArgs), ('G', ctypes.c_int32), ('dhist', ctypes.c_void_p)]
 
 
+# a stage depth per cell (vq_residual.hip): the plain struct, G vectors per cell, depth int32 [M / G]
+class VqResRowsFwdDepthArgs(ctypes.Structure):
+  _fields_ = [('fwd', VqResRowsFwdArgs), ('G', ctypes.c_int32), ('depth', ctypes.c_void_p)]
+
+
+class VqResDecodeDepthArgs(ctypes.Structure):
+  _fields_ = [('dec', VqResDecodeArgs), ('G', ctypes.c_int32), ('depth', ctypes.c_void_p)]
+
+
+class VqResBwdDepthArgs(ctypes.Structure):
+  _fields_ = [('bwd', VqResBwdArgs), ('G', ctypes.c_int32), ('depth', ctypes.c_void_p)]
+
+
+class VqDepthMapArgs(ctypes.Structure):
+  _fields_ = [(n, ctypes.c_int32) for n in ('N', 'H', 'W', 'step', 'n_classes', 'default_depth')] + \
+             [(n, ctypes.c_void_p) for n in ('label', 'table', 'depth', 'stream')]
+
+
 _P, _I32, _I64, _F, _SZ = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float,
                            ctypes.c_size_t)
 _CD, _ND = ctypes.POINTER(ConvDesc), ctypes.POINTER(InormDesc)
@@ -426,6 +444,10 @@ SIGNATURES = {
     'jpdse_vq_res_rate_workspace_size': (_SZ, [_I32, _I32, _I32, _I32, _I32]),
     'jpdse_vq_res_rate_fwd': (_I32, [ctypes.POINTER(VqResRateFwdArgs)]),
     'jpdse_vq_res_bwd_grouped': (_I32, [ctypes.POINTER(VqResBwdGroupedArgs)]),
+    'jpdse_vq_res_rows_fwd_depth': (_I32, [ctypes.POINTER(VqResRowsFwdDepthArgs)]),
+    'jpdse_vq_res_decode_depth': (_I32, [ctypes.POINTER(VqResDecodeDepthArgs)]),
+    'jpdse_vq_res_bwd_depth': (_I32, [ctypes.POINTER(VqResBwdDepthArgs)]),
+    'jpdse_vq_depth_map': (_I32, [ctypes.POINTER(VqDepthMapArgs)]),
 }
 
 # the developer build (same sources, -DJPDSE_DEV): the shipped ABI plus include/jpdse_dev.h

@@ -437,6 +437,15 @@ class HipVQBottleneck(nn.Module):
     return self.conv.bwd(c_conv, Act(dh.view(h.t.shape), h.C), need_dx, need_dw)
 
 
+class StageDepth(object):
+  """The fourth item of a HipResidualVQBottleneck context that was made with a depth map: told from a dhist
+  tensor by its type, not by the context's length."""
+  __slots__ = ('depth',)
+
+  def __init__(self, depth):
+    self.depth = depth
+
+
 class HipResidualVQBottleneck(nn.Module):
   """The residual (multi-stage) quantizer as the encoder's bottleneck: HipVQBottleneck's sibling with S code
   books.  A 1x1 conv (`conv`: `<prefix>.conv.weight`) and a ResidualS2HVQ (`vq`: `<prefix>.vq._code_books` [S, n_center,
@@ -450,6 +459,10 @@ class HipResidualVQBottleneck(nn.Module):
   ops.vq_res_rate_fwd(want_code=True) call on the conv's output -- y and index are ops.vq_res_rows_fwd's bit for bit, the unscaled
   total stays in `rate_value` (fp32 [1]), the per-stage values in `rate_stage_values` (fp32 [stages]), and dhist, scaled by
   rate_scale, travels with the context into the grouped backward.  With rate_scale None every call is the one above.
+  Stage depth: with `depth` set by the owner for a call -- int32 [N * h * w] on the device, one value per pixel of
+  the feature map, whose `groups` consecutive vectors form a cell -- fwd, code, decode and bwd run the depth forms of the same
+  kernels: a vector takes its first min(stages, depth) stages, its code is -1 beyond.  Not together with rate_scale.  With depth
+  None every call is the one above.
   Books: stage s is (2 * torch.rand(n_center, center_size) - 1) * 0.5 ** s from a CPU torch.Generator seeded with seed + s --
   the same books on every device and rank; load_state_dict replaces them."""
 
@@ -469,6 +482,7 @@ class HipResidualVQBottleneck(nn.Module):
     self.grad_ready_hook = None
     self.train_stages = None      # the owner's stage count for the next training forward (None: all); eval ignores it
     self.rate_scale, self.rate_denom, self.rate_value, self.rate_stage_values = None, 0, None, None
+    self.depth = None             # the owner's per-pixel stage depth for the next calls (None: every stage everywhere)
 
   @property
   def groups(self):
@@ -496,7 +510,10 @@ class HipResidualVQBottleneck(nn.Module):
     return n
 
   def _quantize(self, h, n):
-    y, index = ops.vq_res_rows_fwd(h.t.view(-1, self.center_size), self._books().detach(), n)
+    if self.depth is not None:
+      y, index = ops.vq_res_rows_fwd(h.t.view(-1, self.center_size), self._books().detach(), n, depth=self.depth, groups=self.groups)
+    else:
+      y, index = ops.vq_res_rows_fwd(h.t.view(-1, self.center_size), self._books().detach(), n)
     return Act(y.view(h.t.shape), h.C), index
 
   def fwd(self, x, stages=None):
@@ -504,6 +521,11 @@ class HipResidualVQBottleneck(nn.Module):
       stages = self.train_stages
     n = self._stages(stages)
     h, c_conv = self.conv.fwd(x)
+    if self.depth is not None:
+      if self.rate_scale is not None:
+        raise ValueError('HipResidualVQBottleneck: depth and rate_scale cannot be combined (the rate term has no depth form)')
+      y, index = self._quantize(h, n)
+      return y, Ctx(c_conv, h, index, StageDepth(self.depth))
     if self.rate_scale is not None:
       # opt.lambda_vq_stage_rate: the owner set rate_scale / rate_denom for this call; one kernel gives the code
       # and the histograms of the stages in use, and the gradient w.r.t. those sums travels with the context
@@ -558,7 +580,10 @@ class HipResidualVQBottleneck(nn.Module):
     from .ops import tdtype_of
     assert index.dim() == 3 and int(index.shape[0]) == N and 1 <= int(index.shape[1]) <= self.n_stages, tuple(index.shape)
     planes = index.transpose(0, 1).contiguous().view(int(index.shape[1]), -1)
-    y, status = ops.vq_res_decode(planes, self._books().detach(), dtype=tdtype_of(dtype_code))
+    if self.depth is not None:
+      y, status = ops.vq_res_decode(planes, self._books().detach(), dtype=tdtype_of(dtype_code), depth=self.depth, groups=self.groups)
+    else:
+      y, status = ops.vq_res_decode(planes, self._books().detach(), dtype=tdtype_of(dtype_code))
     return Act(y.view(N, h, w, self.cout), self.cout), status
 
   def bwd(self, ctx, dy, need_dx=True, need_dw=True):
@@ -568,7 +593,14 @@ class HipResidualVQBottleneck(nn.Module):
     D = self.center_size
     books = self._books()
     want_dc = need_dw and books.requires_grad
-    if len(ctx.items) == 4:      # a forward with a rate scale: its dhist joins dp of every stage in the grouped backward
+    extra = ctx.items[3] if len(ctx.items) > 3 else None
+    if isinstance(extra, StageDepth):
+      # a forward with a depth map: the per-row recursion under the map the FORWARD used, which travels with the
+      # context -- code and decode read self.depth at the time of their call, the owner may have unset it since
+      dh, _ = ops.vq_res_bwd(dy.t.view(-1, D), h.t.view(-1, D), books.detach(), index, self.vq.sigma, want_dx=True,
+                             want_dc=want_dc, dc_out=self._cgrad_buffer() if want_dc else None, groups=self.groups,
+                             depth=extra.depth)
+    elif extra is not None:    # a forward with a rate scale: its dhist joins dp of every stage in the grouped backward
       dh, _ = ops.vq_res_bwd(dy.t.view(-1, D), h.t.view(-1, D), books.detach(), index, self.vq.sigma, want_dx=True,
                              want_dc=want_dc, dc_out=self._cgrad_buffer() if want_dc else None, groups=self.groups,
                              dhist=ctx.items[3])

@@ -13,7 +13,7 @@ from . import (lib, check, JpdseError, F32, BF16, ConvDesc, PackEntry, InormDesc
 from . import (VqSoftFwdArgs, VqHardFwdArgs, VqSoftBwdArgs, VqDecodeArgs, VqDecodeBwdArgs, VqArgmaxArgs, VqPmfArgs, VqPmfBwdArgs,
                VqQuantizeFwdArgs, VqQuantizeBwdArgs, VqRateFwdArgs, VqQuantizeBwdGroupedArgs, VqLloydAccumArgs, VqLloydUpdateArgs,
                VqEcAssignArgs, VqEcLengthsArgs, VqResFwdArgs, VqResRowsFwdArgs, VqResDecodeArgs, VqResBwdArgs, VqResEcAssignArgs,
-               VqResRateFwdArgs, VqResBwdGroupedArgs)
+               VqResRateFwdArgs, VqResBwdGroupedArgs, VqResRowsFwdDepthArgs, VqResDecodeDepthArgs, VqResBwdDepthArgs, VqDepthMapArgs)
 from . import VQ_RES_MAX_STAGES as _VQ_RES_MAX_STAGES
 
 
@@ -1191,6 +1191,18 @@ def _vq_res_ws(M, D, L, n, dev):
   return workspace(max(lib().jpdse_vq_res_workspace_size(M, D, L, max(n, 1)), 1), dev)
 
 
+def _vq_res_depth(depth, groups, M, dev):
+  """G of a depth call after the host checks: depth int32 [M / G] (any shape), contiguous, on `dev`."""
+  G = int(groups)
+  if G < 1 or M % G != 0:
+    raise ValueError('groups must divide the %d vectors, got %r' % (M, groups))
+  if not torch.is_tensor(depth) or depth.dtype != torch.int32 or not depth.is_contiguous() or depth.device != dev or \
+      depth.numel() != M // G:
+    raise ValueError('depth must be a contiguous int32 tensor of %d cells on %s, got %s' % (
+        M // G, dev, (depth.dtype, tuple(depth.shape), depth.device) if torch.is_tensor(depth) else type(depth).__name__))
+  return G
+
+
 def vq_res_fwd(x, books, n_stages=None, want_sse=False, want_residual=False):
   """(y, index, sse, residual) of x [M, D] (fp32 or bf16) against the first n_stages (default: all) of books fp32 [S, L, D]
   (jpdse_vq_res_fwd): index int32 [n_stages, M], stage s the nearest centre of book s to the residual r_s (r_1 = x, r_{s+1} = r_s -
@@ -1215,9 +1227,12 @@ def vq_res_fwd(x, books, n_stages=None, want_sse=False, want_residual=False):
   return y, index, sse, residual
 
 
-def vq_res_rows_fwd(x, books, n_stages=None):
+def vq_res_rows_fwd(x, books, n_stages=None, depth=None, groups=1):
   """(y, index) of vq_res_fwd, bit for bit, from the thread-per-vector kernel with the residual in registers
-  (jpdse_vq_res_rows_fwd): no sse, no residual, no workspace.  n_stages in 1 .. S (default: all)."""
+  (jpdse_vq_res_rows_fwd): no sse, no residual, no workspace.  n_stages in 1 .. S (default: all).
+  depth (DESIGN.md 4.27): int32 [M / groups], the stage depth of the cell m // groups of vector m (clamped to 1 .. S on the device):
+  row m takes its first n_m = min(n_stages, depth) stages exactly as this call with n_stages = n_m would, and index[s][m] = -1 for
+  s >= n_m (jpdse_vq_res_rows_fwd_depth).  The defaults take exactly the call above."""
   assert x.dim() == 2 and x.is_contiguous(), tuple(x.shape)
   M, D = int(x.shape[0]), int(x.shape[1])
   S, L, _ = _vq_res_dims(books, D)
@@ -1227,14 +1242,20 @@ def vq_res_rows_fwd(x, books, n_stages=None):
   index = torch.empty((n, M), dtype=torch.int32, device=x.device)
   args = VqResRowsFwdArgs(code_of(x.dtype), M, D, L, S, n, x.data_ptr(), books.data_ptr(), y.data_ptr(), index.data_ptr(),
                           torch.cuda.current_stream().cuda_stream)
+  if depth is not None:
+    dargs = VqResRowsFwdDepthArgs(args, _vq_res_depth(depth, groups, M, x.device), depth.data_ptr())
+    check(lib().jpdse_vq_res_rows_fwd_depth(ctypes.byref(dargs)), 'vq_res_rows_fwd_depth')
+    return y, index
   check(lib().jpdse_vq_res_rows_fwd(ctypes.byref(args)), 'vq_res_rows_fwd')
   return y, index
 
 
-def vq_res_decode(index, books, n_stages=None, dtype=torch.float32, status=None):
+def vq_res_decode(index, books, n_stages=None, dtype=torch.float32, status=None, depth=None, groups=1):
   """(y, status): y[m] = books[0][index[0][m]] + .. over the first n_stages (default: all the rows of index) in `dtype` [M, D],
   bit for bit the y of vq_res_fwd with the same n_stages (jpdse_vq_res_decode).  index int32 [S', M].  An index outside [0, L)
-  reads as centre 0 and sets the int32 device word `status` (a zeroed one is made when None): the rule of vq_decode."""
+  reads as centre 0 and sets the int32 device word `status` (a zeroed one is made when None): the rule of vq_decode.
+  depth / groups (DESIGN.md 4.27): row m sums its first min(n_stages, depth[m // groups]) centres, the y of vq_res_rows_fwd with
+  the same depth; index[s][m] past the row's depth is never read (jpdse_vq_res_decode_depth)."""
   S, L, D = _vq_res_dims(books)
   assert index.dim() == 2 and index.dtype == torch.int32 and index.is_contiguous() and index.device == books.device, \
       (index.dtype, tuple(index.shape))
@@ -1246,17 +1267,24 @@ def vq_res_decode(index, books, n_stages=None, dtype=torch.float32, status=None)
   y = torch.empty((M, D), dtype=dtype, device=books.device)
   args = VqResDecodeArgs(code_of(dtype), M, D, L, S, n, index.data_ptr(), books.data_ptr(), y.data_ptr(), status.data_ptr(),
                          torch.cuda.current_stream().cuda_stream)
+  if depth is not None:
+    dargs = VqResDecodeDepthArgs(args, _vq_res_depth(depth, groups, M, books.device), depth.data_ptr())
+    check(lib().jpdse_vq_res_decode_depth(ctypes.byref(dargs)), 'vq_res_decode_depth')
+    return y, status
   check(lib().jpdse_vq_res_decode(ctypes.byref(args)), 'vq_res_decode')
   return y, status
 
 
-def vq_res_bwd(dy, x, books, index, sigma, want_dx=True, want_dc=True, dc_out=None, groups=1, dhist=None):
+def vq_res_bwd(dy, x, books, index, sigma, want_dx=True, want_dc=True, dc_out=None, groups=1, dhist=None, depth=None):
   """(dx, dbooks) of the SOFT form of every stage of vq_res_fwd -- the straight-through gradient -- for the upstream gradient dy
   [M, D] (x's dtype) (jpdse_vq_res_bwd; the residuals are recomputed from x and index int32 [S', M]).  dx in x's dtype; dbooks
   fp32 [S, L, D] (written into dc_out when given), zero for the books beyond S'; either is None when not wanted.
   groups / dhist: with either given the call is jpdse_vq_res_bwd_grouped -- vector m belongs to group m % groups
   and dhist fp32 [S', groups, L], the gradient w.r.t. vq_res_rate_fwd's un-normalised sums, is added to dp of stage s at the
-  vector's group.  The defaults take exactly the call above."""
+  vector's group.  The defaults take exactly the call above.
+  depth: int32 [M / groups]; the call is jpdse_vq_res_bwd_depth -- `groups` is then the number of vectors of a
+  cell, vector m belongs to cell m // groups, and row m runs the recursion over its first min(S', depth) stages (index[s][m]
+  beyond is not read); dbooks of a stage sums over the rows that reach it.  Not together with dhist."""
   assert x.dim() == 2 and x.is_contiguous(), tuple(x.shape)
   M, D = int(x.shape[0]), int(x.shape[1])
   S, L, _ = _vq_res_dims(books, D)
@@ -1275,6 +1303,12 @@ def vq_res_bwd(dy, x, books, index, sigma, want_dx=True, want_dc=True, dc_out=No
   args = VqResBwdArgs(code_of(x.dtype), M, D, L, S, n, float(sigma), dy.data_ptr(), x.data_ptr(), books.data_ptr(), index.data_ptr(),
                       dx.data_ptr() if want_dx else None, dc.data_ptr() if want_dc else None, ws.data_ptr() if want_dc else None,
                       ws.numel() if want_dc else 0, torch.cuda.current_stream().cuda_stream)
+  if depth is not None:
+    if dhist is not None:
+      raise ValueError('vq_res_bwd: depth and dhist cannot be combined (the rate term has no depth form)')
+    dargs = VqResBwdDepthArgs(args, _vq_res_depth(depth, groups, M, x.device), depth.data_ptr())
+    check(lib().jpdse_vq_res_bwd_depth(ctypes.byref(dargs)), 'vq_res_bwd_depth')
+    return dx, dc
   if dhist is not None or int(groups) != 1:
     G = int(groups)
     if dhist is not None:
@@ -1285,6 +1319,24 @@ def vq_res_bwd(dy, x, books, index, sigma, want_dx=True, want_dc=True, dc_out=No
     return dx, dc
   check(lib().jpdse_vq_res_bwd(ctypes.byref(args)), 'vq_res_bwd')
   return dx, dc
+
+
+def vq_depth_map(label, table, default_depth, step):
+  """int32 [N, H / step, W / step]: the stage depth of every cell of step x step pixels of label fp32 [N, 1, H, W] (DESIGN.md
+  4.27; jpdse_vq_depth_map): the maximum over the cell's pixels of table[class] (table int32 [n_classes] on the device, may be
+  empty), a pixel whose label is no integer in [0, n_classes) taking default_depth."""
+  assert label.dim() == 4 and label.size(1) == 1 and label.dtype == torch.float32 and label.is_contiguous(), \
+      (label.dtype, tuple(label.shape))
+  N, H, W, step = int(label.size(0)), int(label.size(2)), int(label.size(3)), int(step)
+  assert table.dim() == 1 and table.dtype == torch.int32 and table.is_contiguous() and table.device == label.device, \
+      (table.dtype, tuple(table.shape))
+  if step < 1 or H % step or W % step:
+    raise ValueError('step must divide H = %d and W = %d, got %r' % (H, W, step))
+  out = torch.empty((N, H // step, W // step), dtype=torch.int32, device=label.device)
+  args = VqDepthMapArgs(N, H, W, step, int(table.numel()), int(default_depth), label.data_ptr(),
+                        table.data_ptr() if table.numel() else None, out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+  check(lib().jpdse_vq_depth_map(ctypes.byref(args)), 'vq_depth_map')
+  return out
 
 
 def vq_res_rate_fwd(x, books, sigma, G, denom, scale=1.0, n_stages=None, want_code=False, want_hist=False, want_grad=True):

@@ -161,6 +161,38 @@ def stage_lambda_grid(trainer, args, lambdas):
     print('%10d %10d / %-3d %16d %14.5f' % (s + 1, used, usage.shape[2], dead, rates[s]))
 
 
+def class_stage_rows(trainer, args):
+  """--vq-class-stages SPEC --per-class: the coded bpp (files of trainer.get_coded_rate) and the per-class L1 / PSNR
+  of the SAME model under three depth maps -- the given one, uniform vq_stages and uniform 1 (the codec's table swapped between the
+  calls; the books and every weight stay)."""
+  from jpdse_hip import ops
+  codec, S = trainer.model.codec, trainer.model.vq_stages
+  given = codec.class_stages
+  n = len(given[0])
+  arms = (('map', given), ('uniform %d' % S, ((S,) * n, S)), ('uniform 1', ((1,) * n, 1)))
+  bpp, sums, images = dict.fromkeys([a for a, _ in arms], 0.0), {}, 0
+  try:
+    for x_dict in batches(args):
+      b = int(x_dict['image'].shape[0])
+      images += b
+      for name, cs in arms:
+        codec.class_stages = cs
+        bpp[name] += trainer.get_coded_rate(x_dict)[0] * b
+        tab = trainer.get_eval_metrics(x_dict, per_class=True)['per_class']['raw'].sum(dim=0, keepdim=True)
+        sums[name] = tab if name not in sums else sums[name] + tab
+  finally:
+    codec.class_stages = given      # whatever happened, the model leaves under its own table
+  res = {name: ops.eval_metrics_per_class(sums[name]) for name, _ in arms}
+  print('coded bpp (.jpdm files, %d images): ' % images + ', '.join('%s %.5f' % (name, bpp[name] / images) for name, _ in arms))
+  print('{:>5} {:>6} {:>12}'.format('class', 'depth', 'pixels') + ''.join(' {:>14} {:>9}'.format(name + ' L1', 'PSNR dB') for name, _ in arms))
+  first = res['map']
+  for k in range(first['pixels'].numel()):
+    if int(first['pixels'][k]):
+      depth = given[0][k] if k < n else given[1]
+      print('{:>5} {:>6} {:>12}'.format(k, depth, int(first['pixels'][k])) +
+            ''.join(' {:>14.4f} {:>9.3f}'.format(float(res[name]['l1'][k]), float(res[name]['psnr'][k])) for name, _ in arms))
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--batches', type=int, default=4)
@@ -187,6 +219,9 @@ def main():
   ap.add_argument('--vq-stages', type=int, default=1,
                   help='with --codec --encoder_quantizer s2hvq: code books of the residual bottleneck (opt.vq_stages, DESIGN.md 4.24).  '
                        'More than 1 prints the rate-distortion points of ONE stream cut after every stage (trainer.get_stage_curve)')
+  ap.add_argument('--vq-class-stages', default=None, metavar='SPEC',
+                  help="with --vq-stages S > 1 and --per-class: opt.vq_class_stages, e.g. '24:3,26:3,*:1' (DESIGN.md 4.27): bpp and the "
+                       'per-class L1 / PSNR rows under the map, next to uniform S and uniform 1 of the same model')
   ap.add_argument('--vq-train-stages', default='all', choices=['all', 'uniform'], help='opt.vq_train_stages (DESIGN.md 4.24)')
   ap.add_argument('--vq-rate-iters', type=int, default=2, help='rounds of the entropy-constrained assignment per image')
   ap.add_argument('--checkpoints_dir', default=None, help='load net_G.pth (and net_E.pth) from here')
@@ -227,6 +262,8 @@ def main():
       ap.error('--vq-rate-lambda takes numbers separated by commas, e.g. 0,0.5,2,8')
   if args.vq_stages != 1 and not vq:
     ap.error('--vq-stages needs --codec --encoder_quantizer s2hvq')
+  if args.vq_class_stages is not None and not (vq and args.vq_stages > 1 and args.per_class):
+    ap.error('--vq-class-stages needs --codec --encoder_quantizer s2hvq --vq-stages S > 1 and --per-class')
   if vq and args.roundtrip:
     ap.error('--roundtrip stores the binarizer\'s code: not available with --encoder_quantizer s2hvq '
              '(trainer.get_coded / decode_coded are its files)')
@@ -251,9 +288,13 @@ def main():
   opt = default_opt(**kw)
   if vq:      # fields without a training flag: set on the namespace
     opt.vq_stages, opt.vq_train_stages = args.vq_stages, args.vq_train_stages
+    if args.vq_class_stages is not None:
+      opt.vq_class_stages = args.vq_class_stages
   torch.manual_seed(1234)
   with contextlib.redirect_stdout(sys.stderr):
     trainer = get_trainer(opt)(opt, 'test' if args.checkpoints_dir else 'train')
+  if args.vq_class_stages is not None:
+    return class_stage_rows(trainer, args)
   if lambdas is not None and vq and args.vq_stages > 1:
     return stage_lambda_grid(trainer, args, lambdas)
   if lambdas is not None:
