@@ -59,11 +59,13 @@ int vqb_common_check(const char* who, int dtype, int M, int D, int L, float sigm
 }
 
 // jpdse_vq_res_* (vq_residual.hip): S books, of which the first n are in use
-int vq_res_check(const char* who, int dtype, int M, int D, int L, int S, int n) {
+// lowest: 0 for the calls that admit a quantizer without a stage in use, 1 for every other
+int vq_res_check(const char* who, int dtype, int M, int D, int L, int S, int n, int lowest) {
   JPDSE_REQUIRE(!bad_dtype(dtype), "%s: bad dtype %d", who, dtype);
   if (int rc = vq_shape_check(who, M, D, L)) return rc;
   JPDSE_REQUIRE(S >= 1 && S <= JPDSE_VQ_RES_MAX_STAGES, "%s: S = %d stages (1 .. %d)", who, S, JPDSE_VQ_RES_MAX_STAGES);
   JPDSE_REQUIRE(n >= 0 && n <= S, "%s: n_stages = %d (0 .. S = %d)", who, n, S);
+  JPDSE_REQUIRE(n >= lowest, "%s: n_stages = %d (%d .. S = %d)", who, n, lowest, S);
   return JPDSE_OK;
 }
 
@@ -71,6 +73,15 @@ int vqr_group_check(const char* who, int M, int L, int G) {
   JPDSE_REQUIRE(G >= 1, "%s: G = %d groups (at least 1)", who, G);
   JPDSE_REQUIRE(M % G == 0, "%s: G = %d does not divide M = %d", who, G, M);
   JPDSE_REQUIRE((long long)G * L <= 65536, "%s: G * L = %lld (at most 65536)", who, (long long)G * L);
+  return JPDSE_OK;
+}
+
+// the grouped jpdse_vq_res_* calls (vq_res_ec.hip, vq_res_rate.hip, jpdse_vq_res_bwd_grouped): at least one
+// stage in use, the groups, and tables [n][G][L] of at most kVqResCells cells
+int vq_res_grouped_check(const char* who, int dtype, int M, int D, int L, int S, int n, int G) {
+  if (int rc = vq_res_check(who, dtype, M, D, L, S, n, 1)) return rc;
+  if (int rc = vqr_group_check(who, M, L, G)) return rc;
+  JPDSE_REQUIRE((long long)n * G * L <= kVqResCells, "%s: n_stages * G * L = %lld (at most %d)", who, (long long)n * G * L, kVqResCells);
   return JPDSE_OK;
 }
 

@@ -45,8 +45,12 @@ int vq_ws_check(const char* who, const void* ws, size_t ws_bytes, size_t need);
 int vqb_common_check(const char* who, int dtype, int M, int D, int L, float sigma);
 int vqr_group_check(const char* who, int M, int L, int G);
 // the residual quantizer (kernels: vq_residual.hip): dtype, the shape limits above, 1 <= S <= 8 books and
-// 0 <= n <= S stages in use; vq_res_workspace_bytes (vq_residual.hip) is what jpdse_vq_res_workspace_size returns inside them
-int vq_res_check(const char* who, int dtype, int M, int D, int L, int S, int n);
+// lowest <= n <= S stages in use (lowest 0 or 1); vq_res_workspace_bytes (vq_residual.hip) is what jpdse_vq_res_workspace_size
+// returns inside them.  vq_res_grouped_check: the same with lowest 1, vqr_group_check, and n * G * L <= kVqResCells (what
+// ops.vq_ec_lengths takes as [n * G][L]): the calls with per-group tables (vq_res_ec.hip, vq_res_rate.hip, the grouped backward)
+constexpr int kVqResCells = 65536;
+int vq_res_check(const char* who, int dtype, int M, int D, int L, int S, int n, int lowest = 0);
+int vq_res_grouped_check(const char* who, int dtype, int M, int D, int L, int S, int n, int G);
 size_t vq_res_workspace_bytes(int M, int D, int L, int n);
 
 // the same for the jpdse_vq_index_* calls (api.cpp; kernels: vq_coder.hip).  vq_index_bits: the decisions per

@@ -1,6 +1,6 @@
 // What the soft-to-hard vector quantizer's sources share (vq.hip: DESIGN.md 4.13; vq_bottleneck.hip: 4.15, 4.16; vq_fit.hip:
 // 4.21): the launcher, the softmax weight, the block-partial idiom, the group layout of a row of scores with its score loop and
-// arg-min butterfly, and the two second-stage kernels that merge per-block partials.  The kernels have
+// arg-min butterfly, the block-order sum of per-block partials (vq_block_sum) and the two second-stage kernels that merge them.  The kernels have
 // internal linkage: each translation unit that includes this header gets its own copy, no relocatable device code is needed.
 #pragma once
 #include <math.h>
@@ -103,7 +103,18 @@ __device__ __forceinline__ void vq_group_arg(float& v, int& k, int G) {
   }
 }
 
+// sum_b partial[b][i] of nb partials of n words, b ascending, in the partials' own type (fp64 for the sums of squares of
+// vq_residual.hip and vq_res_ec.hip: DESIGN.md 4.23, 4.25; int32, exact, for the latter's counts)
+template <typename A>
+__device__ __forceinline__ A vq_block_sum(const A* __restrict__ partial, int nb, int n, int i) {
+  A acc = 0;
+  for (int b = 0; b < nb; ++b) acc += partial[(size_t)b * n + i];
+  return acc;
+}
+
 // out[i] = scale * sum_b partial[b][i], b ascending (fp32).  scale = 1: the bits of the sum
+// (vq_block_sum's loop, kept as written: through the helper the loop's branch compiles to the other sense in every object that
+// includes this header)
 static __global__ __launch_bounds__(256) void vq_merge_kernel(const float* __restrict__ partial, int nb, int n, float scale,
                                                              float* __restrict__ out) {
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {

@@ -1,11 +1,10 @@
 // Entropy-constrained code of the residual soft-to-hard vector quantizer (ctu.quantizers.ResidualS2HVQ.encode_ec).
 // Entry points: include/jpdse.h, "residual vector quantizer"; contract, the LDS rule, resources and measurements: DESIGN.md 4.25.
 //   x [M][D] (fp32 or bf16), S code books fp32 [S][L][D], n <= S stages in use, G groups, vector m in group m % G, bias fp32
-//   [n][G][L] or NULL.  r_1 = x widened once; cost_s[k] = d(r_s, C_s[k]) + bias[s][m % G][k], d the score of vq_rows.h
-//   (vqb_score), the bias one fp32 add after the score loop; k_s = the arg-min, strict <: the lowest index keeps a tie, a +inf
-//   cost never replaces anything, a row of +inf alone gives index 0; r_{s+1} = r_s - C_s[k_s] and y = C_1[k_1] + .. + C_n[k_n]
-//   as vqres_rows_fwd_kernel (vq_residual.hip) forms them.  hist int32 [n][G][L]: the counts of k_s; sse fp64 [n][G]: the sum
-//   of the chosen d WITHOUT the bias, each widened to fp64.
+//   [n][G][L] or NULL.  The chain of vq_res_rows.h with cost_s[k] = d(r_s, C_s[k]) + bias[s][m % G][k] in the place of the
+//   score d, the bias one fp32 add after the score loop: k_s = the arg-min of the cost by the same strict <, so a +inf cost
+//   never replaces anything and a row of +inf alone gives index 0.  hist int32 [n][G][L]: the counts of k_s; sse fp64 [n][G]:
+//   the sum of the chosen d WITHOUT the bias, each widened to fp64.
 // Kernels:
 //   vqres_ec_kernel      vqres_rows_fwd_kernel's layout: one THREAD per vector, r (and with WY the running sum a) in DP
 //       registers, the stage loop inside the thread, book s restaged as [L][DP] in LDS when CBL, otherwise read through L2 at
@@ -17,7 +16,8 @@
 //       [n][G][L] (LDS when it fits, otherwise the block's workspace slice); the fp64 sums of d: G a power of two <= 64 --
 //       xor-shuffles over the lanes that share lane % G (offsets 32 .. G), the four waves in order; any other G -- thread g
 //       sums its vectors ascending.  Either way thread g adds the tile's sum to the block's fp64 partial [n][G].
-//   vqres_ec_merge_kernel   hist = the sum of the blocks' tables (int32, exact), sse = the blocks' partials in block order.
+//   vqres_ec_merge_kernel   hist = the sum of the blocks' tables (int32, exact), sse = the blocks' partials in block order
+//       (vq_block_sum, vq_core.h).
 // A thread beyond M works on zeros, stores nothing, is outside every scan and reaches every barrier.  No atomics; grid, tiles,
 // owners and the LDS layout are functions of (M, D, L, G, n) alone: two calls give identical bits.
 #include <math.h>
@@ -30,7 +30,6 @@ namespace jpdse {
 
 constexpr int kVqResEcTile = 256;                 // vectors per tile = threads per block
 constexpr int kVqResEcPartialWords = 1 << 22;     // cap of blocks * n * G * L: tables of at most 16 MiB
-constexpr int kVqResEcCells = 65536;              // cap of n * G * L: what ops.vq_ec_lengths takes as [n * G][L]
 constexpr size_t kVqResEcLdsBudget = 48 * 1024;   // three blocks per CU (160 KiB): what 3 waves per SIMD at DP 32 can use
 
 // ---- launch geometry and LDS layout: functions of (M, D, L, G, n) alone -------------------------------------------------------
@@ -94,6 +93,8 @@ __global__ __launch_bounds__(256) void vqres_ec_kernel(const T* __restrict__ x, 
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int m0 = tile * V;
     const int nv = M - m0 < V ? M - m0 : V;
+    // vqres_row_begin's prologue and, below, vqres_advance's step and vqres_nearest's sweep with the bias, as this kernel wrote
+    // them before vq_res_rows.h: with the two helpers <float, 32, false, true> measured 0.9 % slower
     const bool live = t < nv;
     const int m = live ? m0 + t : M - 1;
     const int g = m % G;
@@ -118,6 +119,7 @@ __global__ __launch_bounds__(256) void vqres_ec_kernel(const T* __restrict__ x, 
       }
       const float* cc = CBL ? cb : c;
       const float* bg = bmode != 0 ? bs + (size_t)g * L : nullptr;
+      // vqres_nearest's sweep (vq_res_rows.h) with the bias added to the score: the same order, the same strict <
       float best = INFINITY, dsel = vqb_score<DP, CBL>(r, cc, D);   // centre 0 stays when nothing is below +inf
       int bk = 0;
       for (int k = 0; k < L; ++k) {
@@ -132,12 +134,12 @@ __global__ __launch_bounds__(256) void vqres_ec_kernel(const T* __restrict__ x, 
           bk = k;
         }
       }
-      const float* ck = cc + bk * ld;
+      const float* ck = cc + bk * ld;            // vqres_advance's step, as written before it (see the tile prologue above)
 #pragma unroll
       for (int j = 0; j < DP; ++j) {
         const float cj = (CBL || j < D) ? ck[j] : 0.f;
         r[j] = r[j] - cj;
-        if constexpr (WY) a[j] = s == 0 ? cj : a[j] + cj;  // vqres_sum's additions: stage order, starting FROM the first centre
+        if constexpr (WY) a[j] = s == 0 ? cj : a[j] + cj;
       }
       if (live) index[(size_t)s * M + m] = bk;
       if (!stats) continue;
@@ -179,27 +181,11 @@ __global__ __launch_bounds__(256) void vqres_ec_kernel(const T* __restrict__ x, 
 __global__ __launch_bounds__(256) void vqres_ec_merge_kernel(const int* __restrict__ phist, const double* __restrict__ psse, int nb,
                                                             int cells, int sums, int* __restrict__ hist, double* __restrict__ sse) {
   for (int i = blockIdx.x * 256 + threadIdx.x; i < cells + sums; i += gridDim.x * 256) {
-    if (i < cells) {
-      int acc = 0;
-      for (int b = 0; b < nb; ++b) acc += phist[(size_t)b * cells + i];
-      hist[i] = acc;
-    } else {
-      const int j = i - cells;
-      double acc = 0.0;
-      for (int b = 0; b < nb; ++b) acc += psse[(size_t)b * sums + j];
-      sse[j] = acc;
-    }
+    if (i < cells)
+      hist[i] = vq_block_sum(phist, nb, cells, i);
+    else
+      sse[i - cells] = vq_block_sum(psse, nb, sums, i - cells);
   }
-}
-
-// everything that can be refused without a device, workspace and pointers apart
-static int vqres_ec_check(const char* who, int dtype, int M, int D, int L, int S, int n, int G) {
-  if (int rc = vq_res_check(who, dtype, M, D, L, S, n)) return rc;
-  JPDSE_REQUIRE(n >= 1, "%s: n_stages = %d (1 .. S = %d)", who, n, S);
-  if (int rc = vqr_group_check(who, M, L, G)) return rc;
-  JPDSE_REQUIRE((long long)n * G * L <= kVqResEcCells, "%s: n_stages * G * L = %lld (at most %d)", who, (long long)n * G * L,
-                kVqResEcCells);
-  return JPDSE_OK;
 }
 
 }  // namespace jpdse
@@ -209,13 +195,13 @@ using namespace jpdse;
 extern "C" {
 
 size_t jpdse_vq_res_ec_workspace_size(int32_t M, int32_t D, int32_t L, int32_t G, int32_t n) {
-  if (vqres_ec_check("vq_res_ec_workspace_size", JPDSE_F32, M, D, L, JPDSE_VQ_RES_MAX_STAGES, n, G) != JPDSE_OK) return 0;
+  if (vq_res_grouped_check("vq_res_ec_workspace_size", JPDSE_F32, M, D, L, JPDSE_VQ_RES_MAX_STAGES, n, G) != JPDSE_OK) return 0;
   return vqres_ec_ws_bytes(M, L, G, n);
 }
 
 int jpdse_vq_res_ec_assign(const jpdse_vq_res_ec_assign_args* a) {
   JPDSE_REQUIRE(a != nullptr, "vq_res_ec_assign: null argument struct");
-  if (int rc = vqres_ec_check("vq_res_ec_assign", a->dtype, a->M, a->D, a->L, a->S, a->n_stages, a->G)) return rc;
+  if (int rc = vq_res_grouped_check("vq_res_ec_assign", a->dtype, a->M, a->D, a->L, a->S, a->n_stages, a->G)) return rc;
   JPDSE_REQUIRE(a->x && a->books && a->index, "vq_res_ec_assign: null pointer (x, books, index)");
   JPDSE_REQUIRE((a->hist == nullptr) == (a->sse == nullptr), "vq_res_ec_assign: hist and sse come together or not at all");
   const int M = a->M, D = a->D, L = a->L, G = a->G, n = a->n_stages;

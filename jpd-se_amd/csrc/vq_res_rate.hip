@@ -2,12 +2,10 @@
 // histograms of every stage's soft assignment, value and gradient w.r.t. the histograms.
 // Entry points: include/jpdse.h, "residual vector quantizer: the rate term"; definition, path selection, resources and
 // measurements: DESIGN.md 4.26.
-//   x [M][D] (fp32 or bf16), S code books fp32 [S][L][D], n <= S stages in use, G groups, vector m in group m % G.  The chain is
-//   vqres_rows_fwd_kernel's (vq_residual.hip): r_1 = x widened once, k_s the arg-min of vqb_score (strict <), r_{s+1} = r_s -
-//   C_s[k_s].  p_s[m][k] = e * (1 / sum) with e = vq_weight(score, minimum, sigma), as vqr_hist_kernel (vq_bottleneck.hip) forms it
-//   for one stage; hist[s][g][k] = the sum of p_s over the vectors of group g.
-// Kernels (one THREAD per vector, r -- and with WY the running sum a -- in DP registers, the stage loop inside the thread, book s
-// restaged as [L][DP] in LDS when CBL, otherwise read through L2 at wave-uniform addresses):
+//   x [M][D] (fp32 or bf16), S code books fp32 [S][L][D], n <= S stages in use, G groups, vector m in group m % G.  The chain and
+//   its barrier rule: vq_res_rows.h.  p_s[m][k] = e * (1 / sum) with e = vq_weight(score, minimum, sigma), as vqr_hist_kernel
+//   (vq_bottleneck.hip) forms it for one stage; hist[s][g][k] = the sum of p_s over the vectors of group g.
+// Kernels (the chain's pieces per stage, with the histogram of p between the sweeps and the step):
 //   vqrr_hist_kernel          G a power of two <= 64 whose tables fit (vqrr_waves): per stage, sweep 1 the minimum and the arg-min,
 //       sweep 2 the row sum, sweep 3 p: the lanes of a group (lane % G) are added across the wave with xor-shuffles, offsets 32,
 //       16, .. G, and lane g < G adds the sum into the wave's own table [n][G][L + 1] (the odd stride: the G owners on different
@@ -17,20 +15,20 @@
 //       partial in the workspace (zeroed by the block; the barrier after every chunk orders the tiles).
 //   vqrr_final_kernel         one block: per stage the partials in block order in fp64, q, bits, rates[s] and dhist in fp64, written
 //       as fp32; rate = the fp32 sum of the fp32 rates[s] in stage order.
-// With WY the kernels also store index and y: vqres_rows_fwd_kernel's, bit for bit (the same score, the same strict <, the same
-// a = c / a += c).  A thread beyond M works on zeros, adds zeros, stores nothing and reaches every barrier.  No atomics; grid, tile,
+// With WY the kernels also store index and y: vqres_rows_fwd_kernel's, bit for bit (the same helpers).  A thread beyond M works on
+// zeros, adds zeros, stores nothing and reaches every barrier.  No atomics; grid, tile,
 // path and every order of summation are functions of (M, D, L, G, n) alone: two calls give identical bits.
 #include <math.h>
 
 #include "common.h"
 #include "vq_core.h"
+#include "vq_res_rows.h"
 #include "vq_rows.h"
 
 namespace jpdse {
 
 constexpr int kVqrrBlocks = 512;                  // cap of the blocks (= fp32 partials [n][G][L]) of the histogram launch
 constexpr int kVqrrPartialWords = 1 << 22;        // cap of blocks * n * G * L: a workspace of at most 16 MiB
-constexpr int kVqrrCells = 65536;                 // cap of n * G * L
 constexpr size_t kVqrrSlabBytes = 48 * 1024;      // the tables of a block of 4, 2 or 1 waves: with the staged book below 64 KiB
 constexpr size_t kVqrrSlabOptin = 144 * 1024;     // one wave's tables above that: opted in; with the staged book below 160 KiB
 constexpr int kVqrrFinalThreads = 1024;
@@ -61,40 +59,6 @@ static inline size_t vqrr_lds(int D, int L, int G, int n) {
   return words * sizeof(float);
 }
 
-// ---- device helpers ---------------------------------------------------------------------------------------------------------------
-// sweeps 1 and 2 of a stage: the minimum score with its centre (vqres_rows_fwd_kernel's loop), then 1 / sum_k e[k], k ascending
-template <int DP, bool CBL>
-__device__ __forceinline__ float vqrr_nearest(const float (&r)[DP], const float* cc, int ld, int D, int L, int& bk) {
-  float dmin = INFINITY;
-  bk = 0;
-  for (int k = 0; k < L; ++k) {
-    const float d = vqb_score<DP, CBL>(r, cc + k * ld, D);
-    if (d < dmin) {                                // strict: the lower index keeps a tie, a NaN never wins
-      dmin = d;
-      bk = k;
-    }
-  }
-  return dmin;
-}
-
-template <int DP, bool CBL>
-__device__ __forceinline__ float vqrr_inv_sum(const float (&r)[DP], const float* cc, int ld, int D, int L, float dmin, float sigma) {
-  float s = 0.f;
-  for (int k = 0; k < L; ++k) s += vq_weight(vqb_score<DP, CBL>(r, cc + k * ld, D), dmin, sigma);
-  return 1.f / s;
-}
-
-// the end of a stage: r_{s+1} = r_s - C_s[bk] and, with WY, vqres_sum's additions into a (stage order, starting FROM the first centre)
-template <int DP, bool CBL, bool WY>
-__device__ __forceinline__ void vqrr_advance(float (&r)[DP], float (&a)[DP], const float* ck, int D, int s) {
-#pragma unroll
-  for (int j = 0; j < DP; ++j) {
-    const float cj = (CBL || j < D) ? ck[j] : 0.f;
-    r[j] = r[j] - cj;
-    if (WY) a[j] = s == 0 ? cj : a[j] + cj;
-  }
-}
-
 // ---- the histogram launch ---------------------------------------------------------------------------------------------------------
 // blockDim.x = 64 * waves = the vectors of a tile, a multiple of G.  partial: this block's [n][G][L] sums
 template <typename T, int DP, bool CBL, bool WY>
@@ -113,34 +77,25 @@ __global__ __launch_bounds__(256) void vqrr_hist_kernel(const T* __restrict__ x,
   if (!CBL) __syncthreads();
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int m0 = tile * V;                       // a multiple of G: the group of vector m0 + t is lane % G
-    const bool live = t < M - m0;
-    const int m = live ? m0 + t : M - 1;
-    const size_t row = (size_t)m * D;
     float r[DP], a[DP];
-#pragma unroll
-    for (int j = 0; j < DP; ++j) r[j] = a[j] = 0.f;
-    if (live) vqb_load_row<T, DP>(x + row, D, vec != 0, r);
+    const VqResRow me = vqres_row_begin<T, DP>(x, M, D, m0, vec != 0, r, a);
+    const bool live = me.live;
+    const int m = me.m;
     for (int s = 0; s < n; ++s) {
-      const float* c = books + (size_t)s * LD;
-      if (CBL) {
-        __syncthreads();                           // the book of the stage (or tile) before is free
-        vqb_stage(c, vqrr_lds_mem, D, L, DP);
-        __syncthreads();
-      }
-      const float* cc = CBL ? vqrr_lds_mem : c;
+      const float* cc = vqres_book<CBL>(books + (size_t)s * LD, vqrr_lds_mem, D, L, DP);
       int bk;
-      const float dmin = vqrr_nearest<DP, CBL>(r, cc, ld, D, L, bk);
-      const float inv = vqrr_inv_sum<DP, CBL>(r, cc, ld, D, L, dmin, sigma);
+      const float dmin = vqres_nearest<DP, CBL>(r, cc, ld, D, L, bk);
+      const float inv = vqres_inv_sum<DP, CBL>(r, cc, ld, D, L, dmin, sigma);
       float* tab = mine + (size_t)s * G * LS;
       for (int k = 0; k < L; ++k) {
         float v = live ? vq_weight(vqb_score<DP, CBL>(r, cc + k * ld, D), dmin, sigma) * inv : 0.f;
         for (int off = 32; off >= G; off >>= 1) v += __shfl_xor(v, off, 64);
         if (owner) tab[k] += v;
       }
-      vqrr_advance<DP, CBL, WY>(r, a, cc + bk * ld, D, s);
+      vqres_advance<DP, CBL, WY>(r, a, cc + bk * ld, D, s);
       if (WY && live) index[(size_t)s * M + m] = bk;
     }
-    if (WY && live) vqb_store_row<T, DP>(y + row, D, vec != 0, a);
+    if (WY && live) vqb_store_row<T, DP>(y + me.row, D, vec != 0, a);
   }
   __syncthreads();
   float* out = partial + (size_t)blockIdx.x * n * G * L;
@@ -170,25 +125,16 @@ __global__ __launch_bounds__(256) void vqrr_hist_general_kernel(const T* __restr
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int m0 = tile * V;
     const int nv = M - m0 < V ? M - m0 : V;
-    const bool live = t < nv;
-    const int m = live ? m0 + t : M - 1;
-    const size_t row = (size_t)m * D;
     const int ns = G < nv ? G : nv;                // slot j holds the tile's vectors j, j + G, ..: group (m0 + j) % G
     float r[DP], a[DP];
-#pragma unroll
-    for (int j = 0; j < DP; ++j) r[j] = a[j] = 0.f;
-    if (live) vqb_load_row<T, DP>(x + row, D, vec != 0, r);
+    const VqResRow me = vqres_row_begin<T, DP>(x, M, D, m0, vec != 0, r, a);
+    const bool live = me.live;
+    const int m = me.m;
     for (int s = 0; s < n; ++s) {
-      const float* c = books + (size_t)s * LD;
-      if (CBL) {
-        __syncthreads();
-        vqb_stage(c, vqrr_lds_mem, D, L, DP);
-        __syncthreads();
-      }
-      const float* cc = CBL ? vqrr_lds_mem : c;
+      const float* cc = vqres_book<CBL>(books + (size_t)s * LD, vqrr_lds_mem, D, L, DP);
       int bk;
-      const float dmin = vqrr_nearest<DP, CBL>(r, cc, ld, D, L, bk);
-      const float inv = vqrr_inv_sum<DP, CBL>(r, cc, ld, D, L, dmin, sigma);
+      const float dmin = vqres_nearest<DP, CBL>(r, cc, ld, D, L, bk);
+      const float inv = vqres_inv_sum<DP, CBL>(r, cc, ld, D, L, dmin, sigma);
       float* tab = mine + (size_t)s * G * L;
       for (int k0 = 0; k0 < L; k0 += KC) {
         const int kc = L - k0 < KC ? L - k0 : KC;
@@ -204,10 +150,10 @@ __global__ __launch_bounds__(256) void vqrr_hist_general_kernel(const T* __restr
         }
         __syncthreads();                           // pt is free again; the block's adds to `mine` are ordered tile by tile
       }
-      vqrr_advance<DP, CBL, WY>(r, a, cc + bk * ld, D, s);
+      vqres_advance<DP, CBL, WY>(r, a, cc + bk * ld, D, s);
       if (WY && live) index[(size_t)s * M + m] = bk;
     }
-    if (WY && live) vqb_store_row<T, DP>(y + row, D, vec != 0, a);
+    if (WY && live) vqb_store_row<T, DP>(y + me.row, D, vec != 0, a);
   }
 }
 
@@ -261,15 +207,6 @@ __global__ __launch_bounds__(kVqrrFinalThreads) void vqrr_final_kernel(const flo
   if (t == 0) rate[0] = total;
 }
 
-// everything that can be refused without a device, workspace and pointers apart
-static int vqrr_check(const char* who, int dtype, int M, int D, int L, int S, int n, int G) {
-  if (int rc = vq_res_check(who, dtype, M, D, L, S, n)) return rc;
-  JPDSE_REQUIRE(n >= 1, "%s: n_stages = %d (1 .. S = %d)", who, n, S);
-  if (int rc = vqr_group_check(who, M, L, G)) return rc;
-  JPDSE_REQUIRE((long long)n * G * L <= kVqrrCells, "%s: n_stages * G * L = %lld (at most %d)", who, (long long)n * G * L, kVqrrCells);
-  return JPDSE_OK;
-}
-
 }  // namespace jpdse
 
 using namespace jpdse;
@@ -277,13 +214,13 @@ using namespace jpdse;
 extern "C" {
 
 size_t jpdse_vq_res_rate_workspace_size(int32_t M, int32_t D, int32_t L, int32_t G, int32_t n) {
-  if (vqrr_check("vq_res_rate_workspace_size", JPDSE_F32, M, D, L, JPDSE_VQ_RES_MAX_STAGES, n, G) != JPDSE_OK) return 0;
+  if (vq_res_grouped_check("vq_res_rate_workspace_size", JPDSE_F32, M, D, L, JPDSE_VQ_RES_MAX_STAGES, n, G) != JPDSE_OK) return 0;
   return vqrr_workspace_bytes(M, L, G, n);
 }
 
 int jpdse_vq_res_rate_fwd(const jpdse_vq_res_rate_fwd_args* a) {
   JPDSE_REQUIRE(a != nullptr, "vq_res_rate_fwd: null argument struct");
-  if (int rc = vqrr_check("vq_res_rate_fwd", a->dtype, a->M, a->D, a->L, a->S, a->n_stages, a->G)) return rc;
+  if (int rc = vq_res_grouped_check("vq_res_rate_fwd", a->dtype, a->M, a->D, a->L, a->S, a->n_stages, a->G)) return rc;
   JPDSE_REQUIRE(isfinite(a->sigma) && a->sigma > 0.f, "vq_res_rate_fwd: sigma is %g (a finite value > 0)", (double)a->sigma);
   JPDSE_REQUIRE(isfinite(a->scale), "vq_res_rate_fwd: scale is %g (a finite value)", (double)a->scale);
   JPDSE_REQUIRE(isfinite(a->denom) && a->denom > 0.f, "vq_res_rate_fwd: denom is %g (a finite value > 0)", (double)a->denom);

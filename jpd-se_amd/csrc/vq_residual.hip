@@ -1,8 +1,8 @@
 // Residual (multi-stage) soft-to-hard vector quantizer (ctu.quantizers.ResidualS2HVQ).
 // Entry points: include/jpdse.h, "residual vector quantizer"; definition, surrogate gradient and measurements: DESIGN.md 4.23.
-//   x [M][D] (fp32 or bf16), S code books fp32 [S][L][D], n <= S stages in use.  r_1 = x widened to fp32 once;
-//   k_s = arg-min_k |r_s - C_s[k]|^2 (the direct score of vq.hip: vq_scores, lowest index on a tie); r_{s+1} = r_s - C_s[k_s], one
-//   fp32 subtraction per component, never rounded in between; y = C_1[k_1] + .. + C_n[k_n], fp32, stage order, rounded once.
+//   x [M][D] (fp32 or bf16), S code books fp32 [S][L][D], n <= S stages in use.  The chain (r_1 = x, k_s, r_{s+1} = r_s - C_s[k_s],
+//   y = C_1[k_1] + .. + C_n[k_n]) and the barrier rule of the per-row kernels: vq_res_rows.h.  The group kernel scores with
+//   vq.hip's direct score (vq_scores, lowest index on a tie) and forms the same r and y.
 // Kernels:
 //   vqres_fwd_kernel     a block walks tiles of 256 vectors whose residual sits in LDS as fp32 [256][D].  The S books do not fit
 //       in LDS together (4 x 512 x 32 fp32 = 256 KiB), so the STAGE loop is the outer loop of a tile: stage book s transposed
@@ -10,19 +10,18 @@
 //       of x), synchronise, subtract the chosen centres (one thread per (vector, component), the book still in LDS) and sum the
 //       squares of the new residual in fp64, synchronise, next book.  x is read once; y is summed at the end from the tile's
 //       indices (LDS) and the books (L2) by the function the decoder uses; a residual is written only when asked for.
-//   vqres_rows_fwd_kernel   index and y of the kernel above, bit for bit, by one THREAD per vector (vq_rows.h): the
-//       residual and the running sum in registers, the stage loop inside the thread, the book restaged per stage.  No sse, no residual.
+//   vqres_rows_fwd_kernel   index and y of the kernel above, bit for bit, by one THREAD per vector (vq_res_rows.h):
+//       the chain's pieces in stage order and nothing else.  No sse, no residual.
 //   vqres_decode_kernel  one thread per (vector, component): the same sum from the index planes.
 //   vqres_bwd_kernel     one THREAD per vector (vq_rows.h), stages descending.  r_s is recomputed from x and the indices by the
-//       forward's subtractions, a_s = dy - h_{s+1}, then the three sweeps and the code-book-gradient reduction of vqb_bwd_kernel
+//       chain's subtractions, a_s = dy - h_{s+1}, then the three sweeps and the code-book-gradient reduction of vqb_bwd_kernel
 //       (vq_bottleneck.hip) at (r_s, a_s): u_s into registers, the stage's [L][D] share into the block's partial [n][L][D];
 //       h_s = h_{s+1} + u_s; dx = h_1.  vq_merge_kernel (vq_core.h) adds the partials in block order.
-//   vqres_sse_kernel     sse[s] = the blocks' fp64 partials in block order.
+//   vqres_sse_kernel     sse[s] = the blocks' fp64 partials in block order (vq_block_sum, vq_core.h).
 //   DEP: a per-row stage depth on the three kernels above that work per row.  depth int32 [M / G], the cell of row m
-//       is m / G, n_m = min(n, depth clamped to 1 .. S).  BARRIER RULE: the stage loops hold __syncthreads() (the book restage, the
-//       code-book-gradient reduction), so n_m is a PREDICATE inside the loop and never a thread's loop bound: the bound stays n, every
-//       thread reaches every barrier, a row past its depth computes nothing and stores nothing but its -1 (forward) or the zeros of its
-//       LDS slots (backward); a wave whose rows are all past their depth skips the score loops by ordinary divergence.
+//       is m / G, n_m = min(n, depth clamped to 1 .. S).  By the barrier rule (vq_res_rows.h) n_m is a PREDICATE inside the stage
+//       loop: a row past its depth computes nothing and stores nothing but its -1 (forward) or the zeros of its LDS slots
+//       (backward); a wave whose rows are all past their depth skips the score loops by ordinary divergence.
 //   vqres_depth_map_kernel  the cell depths from a label map: one thread per cell, the maximum over its step x step pixels.
 // No atomics; grids, tiles and chunks are functions of (M, D, L, n) alone: two calls give identical bits.
 #include <limits.h>
@@ -30,6 +29,7 @@
 
 #include "common.h"
 #include "vq_core.h"
+#include "vq_res_rows.h"
 #include "vq_rows.h"
 
 namespace jpdse {
@@ -176,11 +176,10 @@ __global__ __launch_bounds__(256) void vqres_fwd_kernel(const T* __restrict__ x,
 }
 
 // ---- forward, one thread per vector ------------------------------------------------------------------------------
-// The residual r and the running sum a of a vector live in DP registers each; the stage loop runs inside the thread.  LDS: cb
-// [L][DP] when CBL, restaged per stage between two barriers that EVERY thread reaches (a thread without a vector works on zeros
-// and stores nothing); otherwise book s is read from global memory at wave-uniform addresses.  index: [n][M], n >= 1.
-// DEP: row m takes its first n_m stages and stores index[s][m] = -1 for the others.  The barrier rule of the file's head: the loop
-// bound is n for every thread, s < n_m is a predicate, and the `continue` of a row past its depth leads to the next stage's barriers.
+// The chain of vq_res_rows.h: r and the running sum a of a vector in DP registers each, the stage loop inside the thread.  LDS: cb
+// [L][DP] when CBL.  index: [n][M], n >= 1.
+// DEP: row m takes its first n_m stages and stores index[s][m] = -1 for the others.  The barrier rule: the loop bound is n for
+// every thread, s < n_m is a predicate, and the `continue` of a row past its depth leads to the next stage's barriers.
 template <typename T, int DP, bool CBL, bool DEP>
 __global__ __launch_bounds__(256) void vqres_rows_fwd_kernel(const T* __restrict__ x, const float* __restrict__ books, int M, int D,
                                                             int L, int n, int vec, T* __restrict__ y, int* __restrict__ index,
@@ -188,60 +187,33 @@ __global__ __launch_bounds__(256) void vqres_rows_fwd_kernel(const T* __restrict
   extern __shared__ float vqresr_lds[];
   constexpr int V = 256;
   const int ld = CBL ? DP : D;
-  const int t = threadIdx.x, LD = L * D;
+  const int LD = L * D;
   const int ntiles = (M + V - 1) / V;
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int m0 = tile * V;
-    const bool live = t < M - m0;
-    const int m = live ? m0 + t : M - 1;
-    const size_t row = (size_t)m * D;
     float r[DP], a[DP];
-#pragma unroll
-    for (int j = 0; j < DP; ++j) r[j] = a[j] = 0.f;
-    if (live) vqb_load_row<T, DP>(x + row, D, vec != 0, r);
-    const int nm = live ? vqres_row_stages(dep, m, n) : 0;     // DEP: a thread without a vector takes no stage
+    const VqResRow me = vqres_row_begin<T, DP>(x, M, D, tile * V, vec != 0, r, a);
+    const int nm = me.live ? vqres_row_stages(dep, me.m, n) : 0; // DEP: a thread without a vector takes no stage
     for (int s = 0; s < n; ++s) {
-      const float* c = books + (size_t)s * LD;
-      if (CBL) {
-        __syncthreads();                         // the book of the stage (or tile) before is free
-        vqb_stage(c, vqresr_lds, D, L, DP);
-        __syncthreads();
-      }
+      const float* cc = vqres_book<CBL>(books + (size_t)s * LD, vqresr_lds, D, L, DP);
       if constexpr (DEP) {
         if (s >= nm) {                           // past the row's depth: after this stage's barriers, before the next one's
-          if (live) index[(size_t)s * M + m] = -1;
+          if (me.live) index[(size_t)s * M + me.m] = -1;
           continue;
         }
       }
-      const float* cc = CBL ? vqresr_lds : c;
-      float dmin = INFINITY;
-      int bk = 0;
-      for (int k = 0; k < L; ++k) {
-        const float d = vqb_score<DP, CBL>(r, cc + k * ld, D);
-        if (d < dmin) {                          // strict: the lower index keeps a tie, a NaN never wins
-          dmin = d;
-          bk = k;
-        }
-      }
-      const float* ck = cc + bk * ld;
-#pragma unroll
-      for (int j = 0; j < DP; ++j) {
-        const float cj = (CBL || j < D) ? ck[j] : 0.f;
-        r[j] = r[j] - cj;
-        a[j] = s == 0 ? cj : a[j] + cj;          // vqres_sum's additions: stage order, starting FROM the first centre
-      }
-      if (live) index[(size_t)s * M + m] = bk;
+      int bk;
+      vqres_nearest<DP, CBL>(r, cc, ld, D, L, bk);
+      vqres_advance<DP, CBL, true>(r, a, cc + bk * ld, D, s);
+      if (me.live) index[(size_t)s * M + me.m] = bk;
     }
-    if (live) vqb_store_row<T, DP>(y + row, D, vec != 0, a);
+    if (me.live) vqb_store_row<T, DP>(y + me.row, D, vec != 0, a);
   }
 }
 
 __global__ __launch_bounds__(64) void vqres_sse_kernel(const double* __restrict__ psse, int nb, int n, double* __restrict__ sse) {
   const int s = threadIdx.x;
   if (s >= n) return;
-  double acc = 0.0;
-  for (int b = 0; b < nb; ++b) acc += psse[(size_t)b * n + s];
-  sse[s] = acc;
+  sse[s] = vq_block_sum(psse, nb, n, s);
 }
 
 // ---- decode -----------------------------------------------------------------------------------------------------------------
@@ -325,7 +297,7 @@ __global__ __launch_bounds__(256) void vqres_bwd_kernel(const T* __restrict__ dy
       for (int j = 0; j < DP; ++j) xr[j] = gr[j] = dxr[j] = 0.f;
       if (act) {
         vqb_load_row<T, DP>(x + row, D, vec != 0, xr);
-        for (int u = 0; u < s; ++u) {            // r_s by the forward's subtractions, in its order
+        for (int u = 0; u < s; ++u) {            // r_s by the chain's subtractions (vq_res_rows.h), in its order
           const float* cu = books + (size_t)u * LD + index[(size_t)u * M + m] * D;
 #pragma unroll
           for (int j = 0; j < DP; ++j)
@@ -351,10 +323,8 @@ __global__ __launch_bounds__(256) void vqres_bwd_kernel(const T* __restrict__ dy
       float dmin = INFINITY;
       float sum = 0.f, pd = 0.f;
       if (!DEP || act) {
-        for (int k = 0; k < L; ++k) {
-          const float d = vqb_score<DP, CBL>(xr, cc + k * ld, D);
-          if (d < dmin) dmin = d;
-        }
+        int bk;                                  // the chain's sweep 1; the forward stored its centre
+        dmin = vqres_nearest<DP, CBL>(xr, cc, ld, D, L, bk);
         for (int k = 0; k < L; ++k) {
           const float* ck = cc + k * ld;
           const float e = vq_weight(vqb_score<DP, CBL>(xr, ck, D), dmin, sigma);
@@ -429,16 +399,12 @@ static int vqres_depth_check(const char* who, int M, int G, const int32_t* depth
 // the cell size of depth [M / G] (no dhist)
 static int vqres_bwd_run(const char* who, const jpdse_vq_res_bwd_args* a, int G, const float* dhist, bool grouped = false,
                          const int32_t* depth = nullptr, bool deep = false) {
-  if (int rc = vq_res_check(who, a->dtype, a->M, a->D, a->L, a->S, a->n_stages)) return rc;
-  JPDSE_REQUIRE(a->n_stages >= 1, "%s: n_stages = %d (1 .. S = %d)", who, a->n_stages, a->S);
+  if (int rc = vq_res_check(who, a->dtype, a->M, a->D, a->L, a->S, a->n_stages, 1)) return rc;
   JPDSE_REQUIRE(isfinite(a->sigma) && a->sigma > 0.f, "%s: sigma is %g (a finite value > 0)", who, (double)a->sigma);
   if (deep)
     if (int rc = vqres_depth_check(who, a->M, G, depth)) return rc;
-  if (grouped) {
-    if (int rc = vqr_group_check(who, a->M, a->L, G)) return rc;
-    JPDSE_REQUIRE((long long)a->n_stages * G * a->L <= 65536, "%s: n_stages * G * L = %lld (at most 65536)", who,
-                  (long long)a->n_stages * G * a->L);
-  }
+  if (grouped)                                   // after sigma, as ever: what it repeats of the check above has passed
+    if (int rc = vq_res_grouped_check(who, a->dtype, a->M, a->D, a->L, a->S, a->n_stages, G)) return rc;
   JPDSE_REQUIRE(a->dy && a->x && a->books && a->index, "%s: null pointer", who);
   const int M = a->M, D = a->D, L = a->L, n = a->n_stages;
   const int V = vqb_bwd_threads(D), nb = vqres_bwd_blocks(M, D, L, n);
@@ -474,8 +440,7 @@ static int vqres_bwd_run(const char* who, const jpdse_vq_res_bwd_args* a, int G,
 
 // jpdse_vq_res_rows_fwd and its depth form: the same grid, tile and LDS
 static int vqres_rows_fwd_run(const char* who, const jpdse_vq_res_rows_fwd_args* a, int G, const int32_t* depth, bool deep) {
-  if (int rc = vq_res_check(who, a->dtype, a->M, a->D, a->L, a->S, a->n_stages)) return rc;
-  JPDSE_REQUIRE(a->n_stages >= 1, "%s: n_stages = %d (1 .. S = %d)", who, a->n_stages, a->S);
+  if (int rc = vq_res_check(who, a->dtype, a->M, a->D, a->L, a->S, a->n_stages, 1)) return rc;
   if (deep)
     if (int rc = vqres_depth_check(who, a->M, G, depth)) return rc;
   JPDSE_REQUIRE(a->x && a->books && a->y && a->index, "%s: null pointer", who);
@@ -494,8 +459,7 @@ static int vqres_rows_fwd_run(const char* who, const jpdse_vq_res_rows_fwd_args*
 }
 
 static int vqres_decode_run(const char* who, const jpdse_vq_res_decode_args* a, int G, const int32_t* depth, bool deep) {
-  if (int rc = vq_res_check(who, a->dtype, a->M, a->D, a->L, a->S, a->n_stages)) return rc;
-  JPDSE_REQUIRE(a->n_stages >= 1, "%s: n_stages = %d (1 .. S = %d)", who, a->n_stages, a->S);
+  if (int rc = vq_res_check(who, a->dtype, a->M, a->D, a->L, a->S, a->n_stages, 1)) return rc;
   if (deep)
     if (int rc = vqres_depth_check(who, a->M, G, depth)) return rc;
   JPDSE_REQUIRE(a->index && a->books && a->y && a->status, "%s: null pointer", who);

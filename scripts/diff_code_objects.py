@@ -6,7 +6,7 @@ them alone; it is what stands in for "kernel speed unchanged").
 
 CSRC_DIR_x: a csrc directory after `make` (it holds conv_gemm.o, conv_gemm.dev.o, norm.o, norm.dev.o, elementwise.o,
 binarize.o, metrics.o, msssim_loss.o, entropy.o, semantics.o, code_rate.o, sem_loss.o, code_cost.o, vq.o, vq_coder.o,
-vq_plane.o, vq_cost.o, vq_bottleneck.o, vq_fit.o).  Per object file the gfx950 code object is taken out of the .hip_fatbin section (llvm-objcopy + clang-offload-bundler), then compared PER SYMBOL -- host code that
+vq_plane.o, vq_cost.o, vq_bottleneck.o, vq_fit.o, vq_ec.o, vq_residual.o, vq_res_ec.o, vq_res_rate.o).  Per object file the gfx950 code object is taken out of the .hip_fatbin section (llvm-objcopy + clang-offload-bundler), then compared PER SYMBOL -- host code that
 instantiates kernels in another order may reorder them inside the object:
   * the set of kernels (the .kd symbols),
   * the resources of each (vgpr / sgpr / agpr count, LDS and scratch size, kernarg size: the metadata note),
@@ -25,7 +25,7 @@ import tempfile
 LLVM = os.environ.get('ROCM_LLVM_BIN', '/opt/rocm/llvm/bin')
 OBJECTS = ['conv_gemm.o', 'conv_gemm.dev.o', 'norm.o', 'norm.dev.o', 'elementwise.o', 'binarize.o', 'metrics.o', 'msssim_loss.o',
            'entropy.o', 'semantics.o', 'code_rate.o', 'sem_loss.o', 'code_cost.o', 'vq.o', 'vq_coder.o', 'vq_plane.o', 'vq_cost.o', 'vq_bottleneck.o',
-           'vq_fit.o']
+           'vq_fit.o', 'vq_ec.o', 'vq_residual.o', 'vq_res_ec.o', 'vq_res_rate.o']
 TARGET = 'hipv4-amdgcn-amd-amdhsa--gfx950'
 RESOURCES = ('.vgpr_count', '.sgpr_count', '.agpr_count', '.group_segment_fixed_size', '.private_segment_fixed_size',
              '.kernarg_segment_size')

@@ -152,6 +152,20 @@ def test_one_stage_is_the_bottleneck_rate_term(case, dtype):
   _close(dc[0], dc1.double().cpu(), F32, 'vq_res_bwd grouped dbooks vs vq_quantize_bwd grouped')
 
 
+# 66 tiles of 256 vectors on 64 blocks (the cap of the partials: 2^22 / (4 * 64 * 256)): the first two blocks walk a second tile,
+# the last tile holds 64 vectors.  G = 64 with L = 256 is the general path; M is the multiple of G next to 16384 + 300
+TWO_TILES = (16704, 256, 8, 4, 64)
+
+
+@pytest.mark.parametrize('dtype', hu.DTYPES)
+def test_a_block_that_walks_two_tiles(dtype):
+  M, L, D, S, G = TWO_TILES
+  xd, bd, (_, _, hist, _, y, index), want = _run(TWO_TILES, dtype)
+  y0, index0 = ops.vq_res_rows_fwd(xd, bd)
+  assert torch.equal(index, index0) and torch.equal(y, y0)
+  _close(hist / (M // G), want['hist'] / (M // G), F32, 'vq_res_rate_fwd hist / n, two tiles per block')
+
+
 def test_refusals_leave_the_outputs_untouched():
   M, L, D, S, G = 64, 16, 4, 2, 4
   g = torch.Generator().manual_seed(1)
